@@ -10,9 +10,12 @@ replayed from a hipGraph.  Inputs (several batches, rotated) are resident in HBM
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-Protocol: W untimed warm-up steps, then `--repeats` (default 5) timed blocks of EXACTLY K steps,
+Protocol: W untimed warm-up steps, then `--repeats` (default 1) timed blocks of EXACTLY K steps,
 each bracketed by a barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `value` and
-`ms_per_step` come from the MEDIAN block, min / max are reported beside it.  Rank 0 prints ONE JSON line.
+`ms_per_step` come from the MEDIAN block, min / max are reported beside it.  With the default, `--steps K` is the number of
+timed steps of the run (`timed_steps` in the line).  Rank 0 prints ONE JSON line.
+`--dump-outputs DIR`: after the timed blocks, what the timed path computed in its last step is written as DIR/<name>.npy
+(see dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 `roofline.traffic` is measured in the run: before touching the GPU the script runs itself twice as a child under
 `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (a few seconds each; `--no-live-pmc` skips them).
 Data: synthetic (seeded WDN topology with C-Town's size, N(0,1) pressures, PyG-style random-init weights); the
@@ -91,7 +94,9 @@ def parse():
                     help="do not run the two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic "
                          "in this run; the committed counter file of the round is used instead (accepted only inside its "
                          "duration band)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=1, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--shuffle-nodes", action="store_true",
                     help="randomly relabel the nodes of the synthetic topology (a junction order with no locality, as an "
                          "EPANET file may have): the plan's reverse Cuthill-McKee relabelling has to restore the row windows")
@@ -240,6 +245,28 @@ PMC_FILE = "r06_fused_pmc_raw.json"      # written by tests/micro/profile_r06.sh
 
 
 LIVE_PMC = {}          # filled by live_pmc() before this process touches the GPU
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor) as ``d/<name>.npy``, float64 tensors as float64, everything else as float32.
+    While all of them fit in DUMP_LIMIT_BYTES they are written whole; otherwise every array larger than an equal share of the
+    limit is cut to a fixed sample of its flat entries (seeded by the array's name and size, sorted indices: the same entries
+    in every run of the same arguments)."""
+    import numpy as np
+    import zlib
+    os.makedirs(d, exist_ok=True)
+    host = {k: v.detach().reshape(-1).cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32)
+            for k, v in arrays.items()}
+    share = DUMP_LIMIT_BYTES // max(1, len(host))
+    sampled = sum(a.nbytes for a in host.values()) > DUMP_LIMIT_BYTES
+    for k, a in host.items():
+        if sampled and a.nbytes > share:
+            rng = np.random.default_rng(zlib.crc32(f"{k}:{a.size}".encode()))
+            a = a[np.sort(rng.choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(d, k + ".npy"), a)
+    log(f"--dump-outputs: {', '.join(sorted(host))} -> {d}" + (" (sampled)" if sampled else ""))
 
 
 def live_pmc(args):
@@ -554,6 +581,7 @@ def drop_in_loop(args, G, model, topo, device, nb, nc):
         loss = crit(out[batch_mask], yd[batch_mask])
         loss.backward()
         opt.step()
+        step.out = out.detach()
         return float(loss)                                                               # train.py:190 (sync)
 
     for i in range(args.warmup):
@@ -564,8 +592,11 @@ def drop_in_loop(args, G, model, topo, device, nb, nc):
         last = step(i)
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor([last], dtype=torch.float64), "out": step.out,
+                                         "params": torch.cat([p.detach().reshape(-1) for p in model.parameters()])})
     print(json.dumps({"metric": "train snapshots/sec", "value": bs * args.steps / dt, "unit": "snapshots/s", "n_gpus": 1,
-                      "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+                      "steps": args.steps, "timed_steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
                       "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
                       "data": "synthetic",
                       "config": {"workload": f"{args.model}, drop-in nn.Module + "
@@ -598,6 +629,8 @@ def eval_loop(args, G, model, topo, device, nb, nc):
             out = timer.auto_measure(model, bs, 10)(x1, ei, None, None)                   # evaluation.py:321-323
     wall = time.perf_counter() - t0
     n_graphs = n_batches * bs
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": out})
     # The reference's two figures, by its own formulas (utils/timer.py:43-66).  Both carry a quirk of that file: compute_time
     # divides the sum of (batch time x graphs in the batch) by the NUMBER OF GRAPHS, which is the mean time of a BATCH, and
     # compute_throughput divides (batches x batch size) by that mean batch time in seconds -- N times the rate at which graphs
@@ -609,7 +642,7 @@ def eval_loop(args, G, model, topo, device, nb, nc):
     ach = sb["forward"] * bs / (ms_call * 1e-3) * 1e-9
     assert bool(torch.isfinite(out).all())
     print(json.dumps({"metric": "inference graphs/sec (forward only, Timer protocol)", "value": rate, "unit": "graphs/s", "n_gpus": 1,
-                      "steps": n_batches, "warmup": 10, "ms_per_step": ms_call, "higher_is_better": True, "scaling": "weak",
+                      "steps": n_batches, "timed_steps": n_batches, "warmup": 10, "ms_per_step": ms_call, "higher_is_better": True, "scaling": "weak",
                       "vs_baseline": None, "dtype": "bf16" if args.dtype == "bf16" else "f32", "data": "synthetic",
                       "reference_figures": {"test_time (evaluation.py:346, timer.py:43-51)": ms_graph,
                                             "test_throughput (evaluation.py:347, timer.py:53-66)": thr,
@@ -764,6 +797,12 @@ def main():
         raise SystemExit(f"bench.py: {graphs_after - graphs_before} hipGraph capture(s) happened INSIDE the timed region "
                          f"({graphs_before} -> {graphs_after} graphs): the measurement is invalid")
     dt = statistics.median(times)
+    if args.dump_outputs and rank == 0:
+        # the state the last timed step left, before anything below launches more work on the trainer
+        torch.cuda.synchronize(device)
+        dump_outputs(args.dump_outputs, {"loss": trainer.loss, "out": trainer.out, "mask": trainer.mask, "grads": trainer.grads,
+                                         "params": model.flat_parameters, "adam_exp_avg": trainer.exp_avg,
+                                         "adam_exp_avg_sq": trainer.exp_avg_sq})
     coll = None
     if trainer.split and trainer.reducer is not None and trainer.reducer.active and trainer._one_piece():
         # what the all-reduce itself takes: 20 more steps as EAGER launches with an event pair around the collective (events
@@ -801,7 +840,8 @@ def main():
     per_snap = lambda t: world * args.batch_size * args.steps / t
     result = {
         "metric": "train snapshots/sec", "value": per_snap(dt), "unit": "snapshots/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "n_gpus": world, "steps": args.steps, "timed_steps": args.steps * len(times), "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "bf16" if args.dtype == "bf16" else "f32", "data": "synthetic",
         "repeats": {"blocks": len(times), "statistic": "median", "ms_per_step_min": min(times) / args.steps * 1e3,

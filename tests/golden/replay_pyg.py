@@ -153,7 +153,7 @@ def replay(path, reference_root, tol, out_dir=None, versions=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--reference", default="/root/reference", help="root of the DiTEC-project/gnn-pressure-estimation checkout")
+    ap.add_argument("--reference", required=True, help="root of the DiTEC-project/gnn-pressure-estimation checkout")
     ap.add_argument("--tol", type=float, default=1e-5, help="relative tolerance on predictions / loss (north star: 1e-5)")
     ap.add_argument("--fixtures", nargs="*", default=None)
     ap.add_argument("--out-dir", default=None, help="write the *.pyg.npz files here instead of beside the fixtures")

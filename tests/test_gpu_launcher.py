@@ -77,3 +77,20 @@ def test_bench_refuses_a_smaller_job_than_asked_for(fork_ctx, tmp_path):
     if torch.cuda.device_count() >= 2:
         pytest.skip("this box has two GPUs: the refusal does not apply")
     assert res["rc"] != 0 and "refusing to report a smaller job" in (res["stderr"] + res["stdout"])
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(fork_ctx, tmp_path):
+    """`--steps K` times exactly K steps, and `--dump-outputs DIR` leaves what the last of them computed as DIR/<name>.npy."""
+    import numpy as np
+    d = tmp_path / "dump"
+    line = _launch(fork_ctx, tmp_path, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-roofline",
+                                        "--dump-outputs", str(d)], {})
+    assert line["steps"] == 3 and line["timed_steps"] == 3 and line["ms_per_step"] > 0
+    P, N = 65857, 388 * 32                                       # gatres_small; bench.py's default batch
+    want = {"loss": 1, "out": N, "mask": N, "grads": P, "params": P, "adam_exp_avg": P, "adam_exp_avg_sq": P}
+    assert sorted(p.name for p in d.iterdir()) == sorted(k + ".npy" for k in want)
+    for k, n in want.items():
+        a = np.load(d / (k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (n,) and np.isfinite(a).all(), k
+    assert abs(float(np.load(d / "loss.npy")[0]) - line["config"]["final_loss"]) <= 1e-6 * abs(line["config"]["final_loss"])
+    assert set(np.unique(np.load(d / "mask.npy"))) <= {0.0, 1.0}
