@@ -39,6 +39,13 @@ class GatresGraph(C.Structure):
 MODEL_INFERENCE = 1            # GATRES_MODEL_INFERENCE (gatres_model_t.flags)
 
 
+class GatresAutoClip(C.Structure):
+    """gatres_autoclip_t"""
+    _fields_ = [("log", C.c_void_p), ("sorted", C.c_void_p * 2), ("ctl", C.c_void_p), ("partials", C.c_void_p),
+                ("norm_out", C.c_void_p), ("clip_out", C.c_void_p), ("coef_out", C.c_void_p), ("capacity", C.c_int64),
+                ("partials_cap", C.c_int32), ("reserved", C.c_int32), ("percentile", C.c_double)]
+
+
 class GatresModel(C.Structure):
     """gatres_model_t"""
     _fields_ = [("num_blocks", C.c_int32), ("nc", C.c_int32), ("act_dtype", C.c_int32), ("flags", C.c_int32)]
@@ -128,12 +135,14 @@ SIGNATURES = {
     "gatres_fused_finish_folds": (C.c_int, [_MP, _GP]),
     "gatres_fused_param_grads_finish": (C.c_int, [_MP, _GP] + [_P] * 5 + [_I32] + [_P] * 4 + [_F64] * 5 +
                                         [_P, _F32, _I32, _I32, _P]),
+    "gatres_autoclip_partials": (_I32, [_I64]),
+    "gatres_autoclip_adam_step": (C.c_int, [_P] * 5 + [_I64] + [_F64] * 5 + [_F32, _P, _P]),
     "gatres_train_step": (C.c_int, [_P, _P]),
     "gatres_version": (C.c_char_p, []),
 }
 
 
-ABI_VERSION = 6                # GATRES_ABI_VERSION of include/gatres.h
+ABI_VERSION = 7                # GATRES_ABI_VERSION of include/gatres.h
 
 
 def diag_build() -> bool:

@@ -4,6 +4,7 @@
 #include <vector>
 #include "k_fused_dev.h"
 #include "k_mask.h"
+#include "k_autoclip.h"
 
 // the kernels live in translation units of their own (k_window.hip, k_fused_whole.hip); args: const FusedArgs*
 extern "C" __attribute__((visibility("hidden"))) int gatres_fused_launch_window(const void* args, int nc, unsigned grid, void* stream);
@@ -15,7 +16,11 @@ namespace {
 static unsigned long long* g_stamps = nullptr;      // gatres_fused_set_stamps (diagnostic build)
 static int g_stamp_cap = 0;
 
-// grads = sum of segment slabs (fixed order) ; optionally the Adam update and the loss finalisation in the same pass
+// grads = sum of segment slabs (fixed order) ; optionally the Adam update and the loss finalisation in the same pass.
+// NORM (AutoClip, with do_adam == 0): each workgroup also leaves the fp64 sum of squares of its slice of grads * grad_scale
+// in ac_partials[blockIdx.x], and block 0 snapshots the words the AutoClip update launch reads (k_autoclip.hip).  NORM == false
+// is the kernel of the step without clipping, unchanged.
+template <bool NORM>
 __global__ __launch_bounds__(256) void reduce_adam_kernel(const float* __restrict__ slabs, int num_slabs,
                                                           int num_loss, long long stride, long long count,
                                                           float* __restrict__ grads, const float* loss_part,
@@ -28,7 +33,8 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(const float* __restric
                                                           const int* __restrict__ mask_node_ptr, double mask_rate,
                                                           unsigned long long mask_seed, uint8_t* __restrict__ mask_next,
                                                           const unsigned long long* __restrict__ mask_snap, int use_snap,
-                                                          int reduce_blocks) {
+                                                          int reduce_blocks, double* __restrict__ ac_partials,
+                                                          unsigned long long* __restrict__ ac_ctl) {
   __shared__ float s_step_size, s_bc2_sqrt;
   __shared__ unsigned s_fault;
   // The device mask of the NEXT step (utils/auxil.py:166-182), sampled by the workgroups behind the reduction's: the
@@ -84,6 +90,7 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(const float* __restric
   const bool fault = s_fault != 0u;
   if (fault && loss && blockIdx.x == 0 && threadIdx.x == 0) loss[0] = NAN;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  [[maybe_unused]] double sq = 0.0;
   if (idx < count && (int)blockIdx.x < reduce_blocks) {
     float acc = 0.f;
     int s0 = 0;
@@ -107,6 +114,10 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(const float* __restric
     }
     for (; s0 < num_slabs; ++s0) acc += slabs[(size_t)s0 * stride + idx];
     grads[idx] = fault ? NAN : acc;
+    if constexpr (NORM) {
+      const double x = (double)(acc * grad_scale);
+      sq = fault ? 0.0 : x * x;
+    }
     if (do_adam && !fault) {
       float gv = acc * grad_scale;
       gv = gv + (float)wd * pv;
@@ -131,6 +142,14 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(const float* __restric
           }
         }
       }
+    }
+  }
+  if constexpr (NORM) {
+    __shared__ double lds4[4];
+    sq = ac_block_sum(sq, lds4);
+    if (threadIdx.x == 0) {
+      ac_partials[blockIdx.x] = sq;
+      if (blockIdx.x == 0) ac_snapshot(ac_ctl, step_counter, fault);      // (every block has read status[0]: s_fault)
     }
   }
   if (fault && snap && blockIdx.x == 0 && threadIdx.x == 0) {      // (the other blocks read the snapshot, not the word)
@@ -809,7 +828,7 @@ extern "C" __attribute__((visibility("hidden"))) int gatres_fused_finish_ex(
   Layout L;
   if (!make_layout_g(m, g, &L)) return GATRES_E_UNSUPPORTED;
   const int reduce_blocks = (int)((L.P + 255) / 256);
-  hipLaunchKernelGGL(reduce_adam_kernel, dim3((unsigned)(reduce_blocks + (mask_next ? mask_graphs * MASK_WGS_UPDATE : 0))), dim3(256), 0,
+  hipLaunchKernelGGL(reduce_adam_kernel<false>, dim3((unsigned)(reduce_blocks + (mask_next ? mask_graphs * MASK_WGS_UPDATE : 0))), dim3(256), 0,
                      gatres_stream(stream),
                      scratch + L.sc_slabs, g->num_segments, g->num_segments * fused_split(L, g),
                      (long long)L.slab_stride, (long long)L.P, grads, loss_part, loss, do_adam, params, exp_avg, exp_avg_sq,
@@ -818,7 +837,31 @@ extern "C" __attribute__((visibility("hidden"))) int gatres_fused_finish_ex(
                      fused_nodes_of(g) > 0 ? reinterpret_cast<unsigned*>(scratch + L.sc_flags + L.flag_words - 32) : nullptr,
                      hparams, mask_node_ptr, mask_rate, (unsigned long long)mask_seed, mask_next,
                      reinterpret_cast<const unsigned long long*>(scratch + L.sc_flags + L.flag_words - 32 + 8),
-                     (use_snap && do_adam) ? 1 : 0, reduce_blocks);
+                     (use_snap && do_adam) ? 1 : 0, reduce_blocks, (double*)nullptr, (unsigned long long*)nullptr);
+  return gatres_launch_status();
+}
+
+// (not part of include/gatres.h) the slab sum of the clipped step: gatres_fused_finish_ex without Adam, as the norm launch of
+// AutoClip (the update follows: gatres_autoclip_update_ex).  *num_partials = partials it leaves.
+extern "C" __attribute__((visibility("hidden"))) int gatres_fused_finish_norm_ex(
+    const gatres_model_t* m, const gatres_graph_t* g, float* scratch, float* grads, const float* loss_part, float* loss,
+    const uint64_t* step_counter, float grad_scale, const gatres_autoclip_t* ac, int32_t* num_partials, void* stream) {
+  if (!m || !g || !scratch || !grads || !step_counter || !ac || !ac->partials || !ac->ctl || !num_partials) return GATRES_E_BADARG;
+  if ((loss_part == nullptr) != (loss == nullptr)) return GATRES_E_BADARG;
+  Layout L;
+  if (!make_layout_g(m, g, &L)) return GATRES_E_UNSUPPORTED;
+  const int reduce_blocks = (int)((L.P + 255) / 256);
+  if (reduce_blocks > ac->partials_cap) return GATRES_E_BADARG;
+  hipLaunchKernelGGL(reduce_adam_kernel<true>, dim3((unsigned)reduce_blocks), dim3(256), 0, gatres_stream(stream),
+                     scratch + L.sc_slabs, g->num_segments, g->num_segments * fused_split(L, g),
+                     (long long)L.slab_stride, (long long)L.P, grads, loss_part, loss, 0, (float*)nullptr, (float*)nullptr,
+                     (float*)nullptr, const_cast<unsigned long long*>(reinterpret_cast<const unsigned long long*>(step_counter)),
+                     0., 0., 0., 0., 0., grad_scale, (float*)nullptr, L.nb, L.nc,
+                     fused_nodes_of(g) > 0 ? reinterpret_cast<unsigned*>(scratch + L.sc_flags + L.flag_words - 32) : nullptr,
+                     (const double*)nullptr, (const int*)nullptr, 0., 0ULL, (uint8_t*)nullptr,
+                     reinterpret_cast<const unsigned long long*>(scratch + L.sc_flags + L.flag_words - 32 + 8), 0,
+                     reduce_blocks, ac->partials, reinterpret_cast<unsigned long long*>(ac->ctl));
+  *num_partials = reduce_blocks;
   return gatres_launch_status();
 }
 

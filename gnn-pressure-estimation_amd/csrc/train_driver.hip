@@ -21,6 +21,34 @@ extern "C" __attribute__((visibility("hidden"))) int gatres_fused_finish_ex(
     int32_t do_adam, float* params, float* exp_avg, float* exp_avg_sq, uint64_t* step_counter, double lr, double beta1,
     double beta2, double eps, double weight_decay, const double* hparams, float grad_scale, const int32_t* mask_node_ptr,
     int32_t mask_graphs, double mask_rate, uint64_t mask_seed, uint8_t* mask_next, int32_t use_snap, void* stream);
+// AutoClip (k_autoclip.hip): the norm launch over a complete gradient, then the update
+extern "C" __attribute__((visibility("hidden"))) int gatres_autoclip_norm_ex(const float* grads, int64_t count, float grad_scale,
+                                                                             const uint64_t* step_counter,
+                                                                             const gatres_autoclip_t* ac, int32_t drop_nan,
+                                                                             int32_t* num_partials, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int gatres_autoclip_update_ex(
+    float* params, const float* grads, float* exp_avg, float* exp_avg_sq, uint64_t* step_counter, int64_t count, double lr,
+    double beta1, double beta2, double eps, double weight_decay, const double* hp, float grad_scale, float* wt,
+    int32_t num_blocks, int32_t nc, uint32_t* drop_count, const int32_t* mask_node_ptr, int32_t mask_graphs, double mask_rate,
+    uint64_t mask_seed, uint8_t* mask_next, const gatres_autoclip_t* ac, int32_t num_partials, void* stream);
+// ... and on the fused path the slab sum as the norm launch (k_fused_host.hip)
+extern "C" __attribute__((visibility("hidden"))) int gatres_fused_finish_norm_ex(
+    const gatres_model_t* m, const gatres_graph_t* g, float* scratch, float* grads, const float* loss_part, float* loss,
+    const uint64_t* step_counter, float grad_scale, const gatres_autoclip_t* ac, int32_t* num_partials, void* stream);
+
+// The clipped update of a complete gradient (per-op path, data-parallel Adam phase): norm launch + update launch
+static int autoclip_update(const gatres_train_step_t* ts, float* wt, uint32_t* drop_count, bool next, void* stream) {
+  const int64_t P = gatres_param_count(ts->model.num_blocks, ts->model.nc);
+  int32_t np = 0;
+  int rc = gatres_autoclip_norm_ex(ts->grads, P, ts->grad_scale, ts->step_counter, ts->autoclip, drop_count ? 1 : 0, &np,
+                                   stream);
+  if (rc) return rc;
+  return gatres_autoclip_update_ex(ts->params, ts->grads, ts->exp_avg, ts->exp_avg_sq, ts->step_counter, P, ts->lr, ts->beta1,
+                                   ts->beta2, ts->eps, ts->weight_decay, ts->hparams, ts->grad_scale, wt, ts->model.num_blocks,
+                                   ts->model.nc, drop_count, next ? ts->node_ptr : nullptr, ts->num_graphs, ts->mask_rate,
+                                   ts->seed, next ? ts->mask_next : nullptr, ts->autoclip, np, stream);
+}
+
 static int fused_grads_and_update(const gatres_train_step_t* ts, const float* loss_part, bool adam, void* stream) {
   const bool want_next = adam && (ts->flags & GATRES_FLAG_MASK_NEXT) && ts->node_ptr && ts->num_graphs > 0 && ts->mask_next &&
                          ts->mask_next != ts->mask;
@@ -34,6 +62,20 @@ static int fused_grads_and_update(const gatres_train_step_t* ts, const float* lo
   //  that leave CUs free form their parameter gradients on consumer workgroups instead -- no snapshot, no sampling ahead:
   //  the caller finds mask_next untouched... so it must not rely on it: GATResTrainer asks gatres_fused_finish_folds first)
   const bool mask_next = want_next && rc == 1;
+  if (adam && ts->autoclip) {      // the slab sum leaves the norm partials; the update launch clips, applies Adam, samples ahead
+    Layout L;
+    if (!make_layout_g(&ts->model, ts->graph, &L)) return GATRES_E_UNSUPPORTED;
+    int32_t np = 0;
+    const int rc2 = gatres_fused_finish_norm_ex(&ts->model, ts->graph, ts->scratch, ts->grads, loss_part,
+                                                loss_part ? ts->loss : nullptr, ts->step_counter, ts->grad_scale, ts->autoclip,
+                                                &np, stream);
+    if (rc2) return rc2;
+    return gatres_autoclip_update_ex(ts->params, ts->grads, ts->exp_avg, ts->exp_avg_sq, ts->step_counter, L.P, ts->lr,
+                                     ts->beta1, ts->beta2, ts->eps, ts->weight_decay, ts->hparams, ts->grad_scale,
+                                     ts->scratch + L.sc_wt, L.nb, L.nc, nullptr, mask_next ? ts->node_ptr : nullptr,
+                                     ts->num_graphs, ts->mask_rate, ts->seed, mask_next ? ts->mask_next : nullptr, ts->autoclip,
+                                     np, stream);
+  }
   return gatres_fused_finish_ex(&ts->model, ts->graph, ts->scratch, ts->grads, loss_part, loss_part ? ts->loss : nullptr,
                                 adam ? 1 : 0, ts->params, ts->exp_avg, ts->exp_avg_sq, ts->step_counter, ts->lr, ts->beta1,
                                 ts->beta2, ts->eps, ts->weight_decay, ts->hparams, ts->grad_scale,
@@ -55,6 +97,13 @@ extern "C" int gatres_train_step(const gatres_train_step_t* ts, void* stream) {
       ts->node_ptr && ts->num_graphs > 0 && ts->mask_next && ts->mask_next != ts->mask &&
       !gatres_fused_finish_folds(&ts->model, ts->graph))
     return GATRES_E_UNSUPPORTED;
+  if (ts->autoclip && (ts->phases & GATRES_PHASE_ADAM)) {      // (refused before anything is enqueued)
+    const gatres_autoclip_t* ac = ts->autoclip;
+    if (!ac->log || !ac->sorted[0] || !ac->sorted[1] || !ac->ctl || !ac->partials || !ac->norm_out || !ac->clip_out ||
+        !ac->coef_out || ac->capacity <= 0 || ac->partials_cap < gatres_autoclip_partials(gatres_param_count(ts->model.num_blocks, ts->model.nc)) ||
+        !(ac->percentile >= 0.0 && ac->percentile <= 100.0))
+      return GATRES_E_BADARG;
+  }
   if ((ts->phases & GATRES_PHASE_MASK) && ts->node_ptr) {
     rc = gatres_mask_generate(ts->node_ptr, ts->num_graphs, ts->mask_rate, ts->seed, ts->step_counter, ts->mask,
                               stream);
@@ -112,6 +161,7 @@ extern "C" int gatres_train_step(const gatres_train_step_t* ts, void* stream) {
       const bool next = (ts->flags & GATRES_FLAG_MASK_NEXT) && ts->node_ptr && ts->num_graphs > 0 && ts->mask_next &&
                         ts->mask_next != ts->mask;
       if (next && !gatres_fused_finish_folds(&ts->model, ts->graph)) return GATRES_E_UNSUPPORTED;      // (no snapshot was left)
+      if (ts->autoclip) return autoclip_update(ts, ts->scratch + L.sc_wt, status + 3, next, stream);
       return gatres_adam_step_ex(ts->params, ts->grads, ts->exp_avg, ts->exp_avg_sq, ts->step_counter,
                                  gatres_param_count(ts->model.num_blocks, ts->model.nc), ts->lr, ts->beta1, ts->beta2,
                                  ts->eps, ts->weight_decay, ts->hparams, ts->grad_scale, ts->scratch + L.sc_wt,
@@ -136,6 +186,7 @@ extern "C" int gatres_train_step(const gatres_train_step_t* ts, void* stream) {
   }
   if (ts->phases & GATRES_PHASE_ADAM) {
     if (!ts->grads || !ts->exp_avg || !ts->exp_avg_sq || !ts->step_counter) return GATRES_E_BADARG;
+    if (ts->autoclip) return autoclip_update(ts, nullptr, nullptr, false, stream);
     rc = gatres_adam_step_ex(ts->params, ts->grads, ts->exp_avg, ts->exp_avg_sq, ts->step_counter,
                              gatres_param_count(ts->model.num_blocks, ts->model.nc), ts->lr, ts->beta1, ts->beta2, ts->eps,
                              ts->weight_decay, ts->hparams, ts->grad_scale, nullptr, 0, 0, nullptr, nullptr, 0, 0., 0,

@@ -38,7 +38,61 @@ class _TrainStepC(C.Structure):
                 ("scratch", C.c_void_p),
                 ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("weight_decay", C.c_double), ("grad_scale", C.c_float), ("flags", C.c_int32),
-                ("hparams", C.c_void_p), ("block_lo", C.c_int32), ("block_hi", C.c_int32), ("mask_next", C.c_void_p)]
+                ("hparams", C.c_void_p), ("block_lo", C.c_int32), ("block_hi", C.c_int32), ("mask_next", C.c_void_p),
+                ("autoclip", C.POINTER(_native.GatresAutoClip))]
+
+
+class _AutoClipState:
+    """AutoClip's device state (``gatres_autoclip_t``; reference utils/gradient_clipping.py ``GradientClipping``): the norm
+    history as a log in step order and as a sorted copy in two ping-pong buffers, the count, and the last step's norm / clip
+    value / coefficient.  One object per optimizer state: a sibling trainer shares it like it shares the Adam moments.
+
+    The history never leaves the device while training.  Its buffers are pre-sized; ``reserve(k)`` -- called before every
+    launch sequence that can run k updates -- grows them (a copy into buffers of twice the size) before the count could get
+    there.  Captured steps hold the buffers' addresses, so a growth bumps ``generation`` and the trainers capture again."""
+
+    def __init__(self, percentile: float, num_params: int, device, capacity: int):
+        self.percentile = float(percentile)
+        self.device = device
+        f64 = dict(dtype=torch.float64, device=device)
+        self.ctl = torch.zeros(8, dtype=torch.int64, device=device)
+        self.partials = torch.zeros(max(int(_native.load().gatres_autoclip_partials(num_params)), 1), **f64)
+        self.out = torch.zeros(3, **f64)                  # {norm, clip value, coefficient}
+        self.capacity = 0
+        self.log = self.sorted0 = self.sorted1 = None
+        self.upper = 0           # host-side bound on the count: updates enqueued since the last reset
+        self.generation = 0
+        self._alloc(max(int(capacity), 1))
+
+    def _alloc(self, capacity: int) -> None:
+        f64 = dict(dtype=torch.float64, device=self.device)
+        new = [torch.zeros(capacity, **f64) for _ in range(3)]
+        for dst, src in zip(new, (self.log, self.sorted0, self.sorted1)):
+            if src is not None:
+                dst[:src.numel()].copy_(src)              # (stream-ordered behind every update enqueued so far)
+        self.log, self.sorted0, self.sorted1 = new
+        self.capacity = capacity
+        self.generation += 1
+        self.c = _native.GatresAutoClip(
+            self.log.data_ptr(), (C.c_void_p * 2)(self.sorted0.data_ptr(), self.sorted1.data_ptr()), self.ctl.data_ptr(),
+            self.partials.data_ptr(), self.out[0:1].data_ptr(), self.out[1:2].data_ptr(), self.out[2:3].data_ptr(),
+            capacity, self.partials.numel(), 0, self.percentile)
+
+    def reserve(self, updates: int) -> None:
+        self.upper += int(updates)
+        if self.upper > self.capacity:
+            self._alloc(max(2 * self.capacity, self.upper))
+
+    def reset(self) -> None:
+        self.ctl[0:1].zero_()
+        self.upper = 0
+
+    def save(self):
+        return [t.clone() for t in (self.ctl, self.out, self.sorted0, self.sorted1)]
+
+    def restore(self, saved) -> None:
+        for dst, src in zip((self.ctl, self.out, self.sorted0, self.sorted1), saved):
+            dst[:src.numel()].copy_(src)
 
 
 class GATResTrainer:
@@ -52,8 +106,15 @@ class GATResTrainer:
                  betas=(0.9, 0.999), eps: float = 1e-8, mask_rate: float = 0.95, seed: int = 0,
                  process_group=None, use_graph: bool = True, fused: bool = True,
                  force_collective_path: bool = False, targets_are_inputs: bool = False,
-                 blocks_per_bucket: int = 5, _share_state_with: Optional["GATResTrainer"] = None):
+                 blocks_per_bucket: int = 5, use_gradient_clipping: bool = False, percentile: float = 10.0,
+                 grad_history_capacity: int = 1 << 16, _share_state_with: Optional["GATResTrainer"] = None):
+        """``use_gradient_clipping`` / ``percentile``: the reference's ``--use_gradient_clipping True --percentile p``
+        (train.py:611-617): AutoClip in front of every Adam update -- the gradient is clipped to the p-th percentile of all
+        gradient norms seen so far (``grad_norm_history()``).  ``grad_history_capacity``: entries the device history holds
+        before it is grown."""
         self.lib = _native.load()
+        if not 0.0 <= float(percentile) <= 100.0:
+            raise ValueError(f"percentile must lie in [0, 100] (got {percentile})")
         self.model = model
         params = model.flat_parameters
         if not params.is_cuda:
@@ -78,6 +139,7 @@ class GATResTrainer:
             # is seen by both (a sibling's set_lr left the parent's host copy stale, and the parent's next
             # set_hparams(weight_decay=...) pushed the old lr back)
             self.hparams = _share_state_with.hparams
+            self._clip = _share_state_with._clip             # ... and ONE gradient-norm history
         else:
             self.exp_avg = torch.zeros(self.P, **f32)
             self.exp_avg_sq = torch.zeros(self.P, **f32)
@@ -85,6 +147,8 @@ class GATResTrainer:
             # the hyper-parameters the update kernels read (gatres_train_step_t.hparams): a captured step follows
             # set_lr() without being captured again
             self.hp = torch.tensor(self._hp_list(), dtype=torch.float64, device=dev)
+            self._clip = _AutoClipState(percentile, self.P, dev, grad_history_capacity) if use_gradient_clipping else None
+        self._clip_gen = self._clip.generation if self._clip is not None else 0
         self.x = torch.zeros(N, **f32)
         # targets_are_inputs: the reference's snapshots have data.y == data.x until the loop masks x (train.py:162-166),
         # and the masking happens inside the kernels here (x itself is never overwritten): one buffer serves both
@@ -210,7 +274,7 @@ class GATResTrainer:
             (self.loss if loss is None else loss).data_ptr(), self.saved.data_ptr(), self.scratch.data_ptr(), h["lr"], h["beta1"], h["beta2"],
             h["eps"], h["weight_decay"], 1.0 / self.world,
             (0 if self.fused else FLAG_PER_OP) | (FLAG_WT_VALID if wt_valid else 0) | flags, self.hp.data_ptr(),
-            block_lo, block_hi, mask_next.data_ptr())
+            block_lo, block_hi, mask_next.data_ptr(), C.pointer(self._clip.c) if self._clip is not None else None)
 
     def _count_native_update(self) -> None:
         """A native kernel (fused Adam pass, Adam-only phase) just changed the parameters without touching torch's
@@ -289,6 +353,8 @@ class GATResTrainer:
 
     def _enqueue(self, phases: int, device_mask: bool, wt_valid: bool = False, flags: int = 0, block_lo: int = 0,
                  block_hi: int = 0, batch=None, masks=None, loss=None) -> None:
+        if self._clip is not None and (phases & PHASE_ADAM) and not torch.cuda.is_current_stream_capturing():
+            self._clip.reserve(1)        # (a direct call; the step paths reserve for their replays too: a bound, not a count)
         ts = self._desc(phases, device_mask, wt_valid, flags, block_lo, block_hi, batch, masks, loss)
         _native.check(self.lib.gatres_train_step(C.byref(ts), _native.current_stream(self.device)),
                       "gatres_train_step")
@@ -298,8 +364,14 @@ class GATResTrainer:
         FusedAdam step moves the shared step count: the sampler's key would differ) and the sampler's own settings."""
         return (getattr(self.model, "_native_updates", 0), self.mask_rate, self.seed)
 
+    def _reserve(self, updates: int) -> None:
+        if self._clip is not None:
+            self._clip.reserve(updates)
+
     def _run(self, phases: int, device_mask: bool, batch=None, slot=None) -> None:
         full = PHASE_BACKWARD | PHASE_ADAM
+        if phases & PHASE_ADAM:
+            self._reserve(1)
         wt_valid = self.fused and (phases & PHASE_BACKWARD) != 0 and self._wt_current()
         flags = 0
         mask_next = self._mask_next and device_mask and (phases & (PHASE_FORWARD | full)) == (PHASE_FORWARD | full)
@@ -323,17 +395,25 @@ class GATResTrainer:
         if not self.use_graph:
             enqueue()
             return
+        if self._clip is not None and self._clip_gen != self._clip.generation:
+            # the gradient-norm history was grown: captured steps hold the old buffers' addresses
+            torch.cuda.synchronize(self.device)
+            self._graphs.clear()
+            self._clip_gen = self._clip.generation
         g = self._graphs.get(key)
         if g is None:
             # warm-up launch outside capture (module load, lazy init, RCCL communicator), then capture the same sequence
             state = (self.step_counter.clone(), self.model.flat_parameters.clone(), self.exp_avg.clone(),
-                     self.exp_avg_sq.clone(), self.mask.clone(), self._mask_spare.clone())
+                     self.exp_avg_sq.clone(), self.mask.clone(), self._mask_spare.clone(),
+                     self._clip.save() if self._clip is not None else None)
 
             def rollback():
                 self.step_counter.copy_(state[0]); self.model.flat_parameters.copy_(state[1])
                 self.exp_avg.copy_(state[2]); self.exp_avg_sq.copy_(state[3])
                 self.mask.copy_(state[4])        # (a warm-up that ran the sampler's launch re-sampled it: same bits; kept simple)
                 self._mask_spare.copy_(state[5])  # (a multi-step sequence samples into BOTH buffers, two steps ahead of the rollback)
+                if state[6] is not None:          # (the count, and the sorted copy a multi-step warm-up overwrote)
+                    self._clip.restore(state[6])
 
             enqueue()
             torch.cuda.synchronize(self.device)
@@ -445,6 +525,7 @@ class GATResTrainer:
         the batch is read in place (``batch``), and the Adam launch samples the next step's mask (``ahead``) exactly as the
         single-GPU update launch does.  ahead=False: the caller samples every step's mask itself (staged batches)."""
         # (fused path: the Adam-only phase refreshes scratch's transposed conv weights like the fused Adam pass does)
+        self._reserve(1)
         wt_valid = self.fused and self._wt_current()
         ahead = bool(ahead and self._mask_next and device_mask and self._one_piece())
         if ahead and not premasked and self._take_mask_ahead():
@@ -602,6 +683,7 @@ class GATResTrainer:
             win = self._rows_win = torch.zeros(k * bs, dtype=torch.int64, device=self.device)
             self._loss_seq = torch.zeros(k, dtype=torch.float32, device=self.device)
         win[:k * bs].copy_(rows)
+        self._reserve(k)
         lseq = self._loss_seq
         npg = self.N // bs
         full = PHASE_FORWARD | PHASE_BACKWARD | PHASE_ADAM
@@ -643,6 +725,7 @@ class GATResTrainer:
         """The single-GPU step on a mask that is already in self.mask (staged with the batch, or sampled by the previous
         step's update launch).  ahead=False: the caller samples every step's mask itself (the store's row collation)."""
         full = PHASE_FORWARD | PHASE_BACKWARD | PHASE_ADAM
+        self._reserve(1)
         wt_valid = self.fused and self._wt_current()
         ahead = ahead and self._mask_next
         flags = FLAG_MASK_NEXT if ahead else 0
@@ -694,6 +777,7 @@ class GATResTrainer:
         dev = self.device
         torch.cuda.synchronize(dev)
         keep = [t.clone() for t in (self.step_counter, self.model.flat_parameters, self.exp_avg, self.exp_avg_sq, self.loss)]
+        keep_clip = self._clip.save() if self._clip is not None else None
         try:
             n = len(self._bound)
             # (mask-ahead: the two mask buffers take turns, so a batch has two steady-state graphs; without it, one)
@@ -736,6 +820,8 @@ class GATResTrainer:
             torch.cuda.synchronize(dev)
             for dst, src in zip((self.step_counter, self.model.flat_parameters, self.exp_avg, self.exp_avg_sq, self.loss), keep):
                 dst.copy_(src)
+            if keep_clip is not None:
+                self._clip.restore(keep_clip)
             self._mask_sig = None
             self._wt_sig = None
         if self.fused:
@@ -794,6 +880,7 @@ class GATResTrainer:
                     losses[j:j + 1].copy_(self.loss)
             return self.loss
         full = PHASE_FORWARD | PHASE_BACKWARD | PHASE_ADAM
+        self._reserve(len(idx))
         m0, m1 = self._mask_spare, self.mask          # step 0 trains on the mask sampled ahead and samples step 1's into the other
 
         def enqueue():
@@ -843,6 +930,44 @@ class GATResTrainer:
     @property
     def optimizer_step(self) -> int:
         return int(self.step_counter[0].item())
+
+    # ---- AutoClip (use_gradient_clipping=True) -----------------------------------------------------------------------
+    def _clip_state(self) -> _AutoClipState:
+        if self._clip is None:
+            raise RuntimeError("gradient clipping is off: construct the trainer with use_gradient_clipping=True")
+        return self._clip
+
+    @property
+    def percentile(self) -> float:
+        return self._clip_state().percentile
+
+    def grad_norm_history(self):
+        """The gradient norms of every update so far, in step order (float64 numpy): the reference's
+        ``GradientClipping.grad_history``.  Synchronises."""
+        st = self._clip_state()
+        ctl = st.ctl.cpu()
+        if int(ctl[4]) != 0:
+            raise RuntimeError("the gradient-norm history overflowed its device buffers and updates were skipped")
+        return st.log[:int(ctl[0])].cpu().numpy()
+
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """Gradient norm of the last update that was not dropped (0-d float64 device tensor; no synchronisation)."""
+        return self._clip_state().out[0]
+
+    @property
+    def last_clip_value(self) -> torch.Tensor:
+        """Clip value (the percentile of the history) of that update (0-d float64 device tensor)."""
+        return self._clip_state().out[1]
+
+    @property
+    def last_clip_coef(self) -> torch.Tensor:
+        """The factor that update multiplied the gradient with, ``min(1, clip / (norm + 1e-6))`` (0-d float64 device tensor)."""
+        return self._clip_state().out[2]
+
+    def reset_gradient_clipping(self) -> None:
+        """``GradientClipping.reset()``: forget the history (stream-ordered; captured steps stay valid)."""
+        self._clip_state().reset()
 
     # ---- epoch-level loop (train.py:112-202) ---------------------------------------------------------------------------
     def _epoch_in_place(self, store, order: torch.Tensor, nfull: int, kseq: int, total: torch.Tensor) -> None:

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GATRES_ABI_VERSION 6
+#define GATRES_ABI_VERSION 7
 
 #define GATRES_E_BADARG      (-1)  /* null pointer, negative size, misaligned pointer            */
 #define GATRES_E_UNSUPPORTED (-2)  /* width not supported by the gfx950 kernels                  */
@@ -529,6 +529,42 @@ int gatres_fused_param_grads_finish(const gatres_model_t* m, const gatres_graph_
                                     float grad_scale, int32_t block_lo, int32_t block_hi, void* stream);
 
 /* --------------------------------------------------------------------------------------------------------
+ * AutoClip gradient-norm clipping (reference utils/gradient_clipping.py; train.py:186-187 with
+ * --use_gradient_clipping True --percentile p).  Per update, with g = grads * grad_scale (the gradient Adam sees, before
+ * weight decay):
+ *   n = ||g||_2 (fp64 sum of squares of the fp32 values, summed in a fixed order);  the history gets n appended;
+ *   c = np.percentile(history, percentile) (numpy's default "linear" method, the current norm included);
+ *   coef = min(1, c / (n + 1e-6)) (torch.nn.utils.clip_grad_norm_: ALWAYS applied, also when c >= n);
+ *   Adam on g * coef.
+ * A dropped step (a faulted fused launch, a data-parallel gradient carrying the NaN mark) adds nothing to the history and
+ * leaves the outputs alone.  `grads` keeps d loss / d params, unclipped.
+ * The history lives on the device twice: `log` in step order, and the same values sorted ascending in one of two ping-pong
+ * buffers -- sorted[count & 1] is current, the update writes sorted[(count + 1) & 1].  All pointers are device pointers.
+ * ------------------------------------------------------------------------------------------------------ */
+typedef struct gatres_autoclip {
+  double* log;                     /* [capacity] norms in step order                                                       */
+  double* sorted[2];               /* [capacity] each                                                                      */
+  uint64_t* ctl;                   /* uint64[8]: [0] = count (entries in the history; zero it to reset), [4] = overflow flag
+                                    * (a step found count == capacity: it was skipped); the rest is internal             */
+  double* partials;                /* [partials_cap] sum-of-squares partials of the update's norm launch                     */
+  double* norm_out;                /* [1] n of the last step that was not dropped                                          */
+  double* clip_out;                /* [1] c of that step                                                                   */
+  double* coef_out;                /* [1] coef of that step                                                                */
+  int64_t capacity;                /* entries log and sorted[] hold; the caller grows them before the count gets there      */
+  int32_t partials_cap;            /* >= gatres_autoclip_partials(P)                                                       */
+  int32_t reserved;
+  double percentile;               /* 0 .. 100                                                                             */
+} gatres_autoclip_t;
+
+/* Entries `partials` needs for a parameter vector of `count` floats. */
+int32_t gatres_autoclip_partials(int64_t count);
+
+/* gatres_adam_step with AutoClip in front, on a caller's flat gradient: two launches (norm partials, clip + Adam + history). */
+int gatres_autoclip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                              uint64_t* step_counter, int64_t count, double lr, double beta1, double beta2, double eps,
+                              double weight_decay, float grad_scale, const gatres_autoclip_t* ac, void* stream);
+
+/* --------------------------------------------------------------------------------------------------------
  * One reference training iteration (train.py:159-190) enqueued natively:
  *   PHASE_MASK     device mask sampler (utils/auxil.py:166-182) -- skipped when node_ptr == NULL (caller's mask)
  *   PHASE_FORWARD  x[mask] = 0 ; out = model(x) ; loss = MSE(out[mask], y[mask]) and d loss / d out
@@ -574,6 +610,8 @@ typedef struct gatres_train_step {
   int32_t block_lo, block_hi;      /* GATRES_FLAG_GRADS_ONLY: the blocks whose parameter gradients this call forms       */
   uint8_t* mask_next;              /* GATRES_FLAG_MASK_NEXT: [N] where the update launch leaves the NEXT step's mask (another
                                     * buffer than `mask`, which keeps the mask this step used); NULL: no sampling ahead     */
+  const gatres_autoclip_t* autoclip; /* HOST pointer: PHASE_ADAM clips the gradient with AutoClip first (see gatres_autoclip_t);
+                                    * NULL: no clipping, exactly the ABI-6 step                                            */
 } gatres_train_step_t;
 #define GATRES_FLAG_PER_OP 1
 /* Fused path, PHASE_BACKWARD: stop after the backward chain; the caller forms the parameter gradients itself, range by
