@@ -8,6 +8,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import numpy as np
 import torch
 import gnn_pressure_estimation_amd as G
+from tests import irregular_graphs as IG
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -16,28 +17,7 @@ seg_lo = int(sys.argv[4]) if len(sys.argv) > 4 else 1
 
 
 def random_graph(n):
-    kind = rng.randint(4)
-    if kind == 0:                                   # WDN-like, local order
-        return G.wdn_synth.make_wdn_topology(n, n - 1 + rng.randint(0, max(1, n // 8)), seed=int(rng.randint(1 << 30)))
-    src, dst = [], []
-    for v in range(1, n):                           # random tree with a locality window, then extra edges
-        u = rng.randint(max(0, v - rng.randint(1, 40)), v)
-        src += [u, v]; dst += [v, u]
-    extra = rng.randint(0, n)
-    for _ in range(extra):
-        u, v = rng.randint(n), rng.randint(n)
-        if kind == 1 and u != v:                    # undirected extras (degrees may exceed 6)
-            src += [u, v]; dst += [v, u]
-        elif kind == 2:                             # directed extras, self loops allowed
-            src.append(u); dst.append(v)
-        elif kind == 3 and u != v:                  # hub: many edges into node 0's neighbourhood
-            w = rng.randint(min(n, 5))
-            src += [u, w]; dst += [w, u]
-    ei = torch.tensor([src, dst], dtype=torch.int64)
-    if rng.rand() < 0.3:                            # shuffled node ids
-        perm = torch.from_numpy(rng.permutation(n))
-        ei = perm[ei]
-    return ei[:, torch.argsort(ei[0], stable=True)]
+    return IG.random_graph(rng, n, G.wdn_synth.make_wdn_topology)
 
 
 def relerr(a, b):

@@ -15,6 +15,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from test_gpu_model import build, ctown_batch, note, relerr      # noqa: E402
+from test_gpu_irregular import C_ALPHA, C_BF16, C_F32      # noqa: E402
+import irregular_graphs as IG      # noqa: E402
+import sparse_refs as R      # noqa: E402
 
 BF16 = 1
 
@@ -247,19 +250,39 @@ def _plan_for(pkg, bs, nodes=388, pipes=430, seed=0):
     return pkg.GraphPlan(ei, nodes * bs, device=ei.device, segments=False), ei
 
 
-@pytest.mark.parametrize("bs,nodes,pipes", [(5, 388, 430), (1, 131, 150)])
-def test_blocked_kernels_equal_the_per_op_pairs(pkg, lib, bs, nodes, pipes):
+@pytest.mark.parametrize("bs,nodes,pipes", [(5, 388, 430), (1, 131, 150)] +
+                         [pytest.param(1, name, 0, id=f"irregular-{name}") for name in ("sym_le32", "dir_le32", "sym_le32_shuffled")])
+def test_blocked_kernels_equal_the_per_op_pairs(pkg, lib, bs, nodes, pipes, monkeypatch):
     """k_blocked.hip: one launch = a sparse stage + the projection that consumes it.  Against the two per-op launches it
     replaces, on the same operands, EVERY output bit for bit: the sparse stage's (o1 / x_next / g_h, alpha, g_a_src: the same
     slot arithmetic), the projected rows (the same bf16 operands, the same k order on the matrix cores) and the next
     convolution's attention logits (summed from the fp32 accumulators in the projection kernel's association).  Ragged row
-    counts: the last 16-row tile and the last 32-row phase of a workgroup's share are partial."""
+    counts: the last 16-row tile and the last 32-row phase of a workgroup's share are partial.
+    irregular-*: plans with rows of 7 .. 32 entries (tests/irregular_graphs.py) -- waves that leave the slot path, rows of
+    6 in such waves on the divergent 6-slot branch, the edge-after-edge loop -- and, since the per-op pair states the same
+    arithmetic, the sparse outputs also against the fp64 statements of tests/sparse_refs.py."""
     nc = 128
-    plan, ei = _plan_for(pkg, bs, nodes, pipes)
-    assert plan.flags & 2, "the synthetic WDN topology has low degrees: GATRES_GRAPH_DEG_LE32"
+    irregular = isinstance(nodes, str)
+    if irregular:
+        ig = IG.named(nodes)
+        ei = ig.edge_index.cuda()
+        plan = pkg.GraphPlan(ei, ig.num_nodes, device=ei.device, segments=False)
+        assert plan.flags & 2 and not plan.flags & 4 and plan.num_nodes >= 64
+        rows = IG.row_counts(ig.edge_index, ig.num_nodes)["gat_in"]
+        # a mixed wave: a row of 7 .. 32 entries next to a row of 6 in one pair of rows (1 .. 4 rows per wave here)
+        pairs = rows[:len(rows) // 2 * 2].reshape(-1, 2)
+        assert nodes.endswith("shuffled") or (((pairs >= 7) & (pairs <= 32)).any(1) & (pairs == 6).any(1)).any()
+        assert ((rows >= 7) & (rows <= 32)).any()
+        monkeypatch.setenv("GATRES_BLOCKED", "1")
+        m = pkg.GATResMeanConv(num_blocks=1, nc=nc).cuda()
+        m.set_compute_dtype("bf16")
+        assert lib.gatres_blocked_supported(m._cmodel_ref(), plan.ref()) == 1          # (what the model driver would take)
+    else:
+        plan, ei = _plan_for(pkg, bs, nodes, pipes)
+        assert plan.flags & 2, "the synthetic WDN topology has low degrees: GATRES_GRAPH_DEG_LE32"
     N, Eg = plan.num_nodes, plan.num_edges_gat
     gp = plan.ref()
-    g = torch.Generator().manual_seed(bs * 1000 + nodes)
+    g = torch.Generator().manual_seed(bs * 1000 + (len(nodes) if irregular else nodes))
     rn = lambda *s: torch.randn(*s, generator=g).cuda()
     bf = lambda *s: rn(*s).bfloat16()
     st = lambda: pkg._native.current_stream(ei.device)
@@ -281,6 +304,13 @@ def test_blocked_kernels_equal_the_per_op_pairs(pkg, lib, bs, nodes, pipes):
                                      as_b.data_ptr(), ad_b.data_ptr(), nc, st()), "agg_proj")
     torch.cuda.synchronize()
     assert torch.equal(o_a, o_b) and torch.equal(al_a, al_b)
+    if irregular:
+        src, dst = R.gat_edges(ig.edge_index, N)
+        ref, ref_abs, al_ref = R.gat_aggregate_fwd(src, dst, h1.cpu(), a_s.cpu(), a_d.cpu(), bias.cpu(), N, 2, True)
+        need = {"o1": R.excess(o_b, ref, ref_abs, 2.0 ** -8), "alpha": R.excess(al_b, al_ref, al_ref, 0.0)}
+        note(f"irregular bf16 blocked kernels {nodes}: worst c needed per output", need)
+        R.assert_within("blocked agg: o1", o_b, ref, ref_abs, 2.0 ** -8, C_BF16)
+        R.assert_within("blocked agg: alpha", al_b, al_ref, al_ref, 0.0, C_ALPHA)
     assert torch.equal(h2_a, h2_b)
     assert torch.equal(as_b, as_a) and torch.equal(ad_b, ad_a)
     # ---- K3 (mean + residual + ReLU) -> the next block's conv1 projection (K = 128 -> M = 256, H = 2)
@@ -298,6 +328,11 @@ def test_blocked_kernels_equal_the_per_op_pairs(pkg, lib, bs, nodes, pipes):
         "mean_proj")
     torch.cuda.synchronize()
     assert torch.equal(xn_a, xn_b) and torch.equal(h1_a, h1_b)
+    if irregular:
+        ref, ref_abs = R.mean_residual_relu(ig.edge_index, y2.cpu(), x0.cpu(), N)
+        need["x_next"] = R.excess(xn_b, ref, ref_abs, 2.0 ** -8)
+        note(f"irregular bf16 blocked kernels {nodes}: worst c needed per output", need)
+        R.assert_within("blocked mean: x_next", xn_b, ref, ref_abs, 2.0 ** -8, C_BF16)
     assert torch.equal(as1_b, as1_a) and torch.equal(ad1_b, ad1_a)
     # ---- source-major backward -> input gradient, both convolutions
     for H, K, M in ((1, 128, 256), (2, 256, 128)):
@@ -319,6 +354,13 @@ def test_blocked_kernels_equal_the_per_op_pairs(pkg, lib, bs, nodes, pipes):
                                        ref_act.data_ptr(), gx_b.data_ptr(), H, nc, st()), "src_dx")
         torch.cuda.synchronize()
         assert torch.equal(gh_a, gh_b) and torch.equal(gas_a, gas_b), H
+        if irregular:
+            ref, ref_abs, gas_ref, gas_abs = R.gat_aggregate_bwd_src(src, dst, g_out.cpu(), alpha.cpu(), g_e.cpu(), g_ad.cpu(),
+                                                                     att_s2.cpu(), att_d2.cpu(), N, H)
+            need[f"g_h H{H}"], need[f"g_a_src H{H}"] = R.excess(gh_b, ref, ref_abs, 2.0 ** -8), R.excess(gas_b, gas_ref, gas_abs, 0.0)
+            note(f"irregular bf16 blocked kernels {nodes}: worst c needed per output", need)
+            R.assert_within(f"blocked src H{H}: g_h", gh_b, ref, ref_abs, 2.0 ** -8, C_BF16)
+            R.assert_within(f"blocked src H{H}: g_a_src", gas_b, gas_ref, gas_abs, 0.0, C_F32)
         assert torch.equal(gx_a, gx_b), H
 
 

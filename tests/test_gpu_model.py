@@ -65,6 +65,49 @@ def ctown_batch(pkg, bs, nodes=388, pipes=430):
     return pkg.wdn_synth.make_batch(bs, nodes, pipes)
 
 
+def judge_gradients(hip, ref32, g64):
+    """Per-tensor judge of a gradient against the fp64 oracle's (dicts: parameter name -> tensor).  Some tensors (att_dst:
+    sum_e g_e is ~0 by softmax symmetry) are pure cancellation noise in fp32, so each tensor's error is judged against the
+    fp32 oracle's own error vs fp64 and against the scale of the whole gradient.  Returns (failing tensors, worst error
+    over |g|max, worst (hip err) / (oracle32 err), whether every failing tensor is one a ReLU kink can excuse)."""
+    gscale = max(float(v.abs().max()) for v in g64.values())
+    worst_ratio, worst_rel, bad, kink = 0.0, 0.0, [], True
+    for k, ref in ref32.items():
+        e_hip = float((hip[k].double().cpu() - g64[k]).abs().max())
+        e_ref = float((ref.double() - g64[k]).abs().max())
+        floor = max(1e-5 * float(g64[k].abs().max()), 2e-6 * gscale)
+        if e_hip > max(2 * e_ref, floor):
+            bad.append((k, e_hip, e_ref))
+            # a kink can only excuse a tensor on which the fp32 ORACLE is off its own fp64 gradient as well
+            kink = kink and e_ref > floor
+        worst_ratio = max(worst_ratio, e_hip / max(e_ref, 1e-30))
+        worst_rel = max(worst_rel, e_hip / gscale)
+    return bad, worst_rel, worst_ratio, kink
+
+
+def check_gradients_vs_fp64(hip, ref32, grads64, p64, cache, key):
+    """judge_gradients at the fp64 parameters p64 (grads64: fp64 parameters -> fp64 gradient dict; cached per key).  The
+    network is piecewise linear: when an activation sits within fp32 round-off of a ReLU/LeakyReLU kink the gradient is
+    bimodal (the fp64 oracle itself jumps by ~1e-4 relative under 1e-7 parameter perturbations at the 15-block C-Town
+    point), so the check accepts agreement with the fp64 gradient on either side of such a kink: the base point or one of
+    8 perturbed evaluations.  The fallback fires only where it demonstrably applies: every failing tensor is one on which
+    the fp32 oracle itself disagrees with its fp64 gradient beyond the tolerance floor.  Returns (worst error over
+    |g|max, worst error ratio to the fp32 oracle's, fp64 kink branch used)."""
+    if key not in cache:
+        cache[key] = [grads64(p64)]
+    bad, worst_rel, worst_ratio, kink = judge_gradients(hip, ref32, cache[key][0])
+    branch = 0
+    gen = torch.Generator().manual_seed(1234)
+    while bad and kink and branch < 8:
+        branch += 1
+        if len(cache[key]) <= branch:
+            pert = {k: v * (1 + 1e-7 * torch.randn(v.shape, generator=gen, dtype=torch.float64)) for k, v in p64.items()}
+            cache[key].append(grads64(pert))
+        bad, worst_rel, worst_ratio, _ = judge_gradients(hip, ref32, cache[key][branch])
+    assert not bad, (bad[:3], kink, branch)
+    return worst_rel, worst_ratio, branch
+
+
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "per_op"])
 @pytest.mark.parametrize("nb,nc,bs,nodes,pipes", [(2, 8, 3, 40, 47), (15, 32, 2, 388, 430), (3, 128, 2, 60, 70),
                                                    (1, 4, 1, 9, 10), (0, 16, 2, 12, 14), (2, 64, 2, 130, 150),
@@ -103,38 +146,12 @@ def test_forward_backward_parity(pkg, oracle, nb, nc, bs, nodes, pipes, fused):
         torch.nn.functional.mse_loss(o[mask], y.double()[mask]).backward()
         return {k: v.grad for k, v in l.items()}
 
-    def judge(g64):
-        gscale = max(float(v.abs().max()) for v in g64.values())
-        worst_ratio, worst_rel, bad, kink = 0.0, 0.0, [], True
-        for (k, ref), prm in zip(leaves.items(), model.parameters()):
-            e_hip = float((prm.grad.double().cpu() - g64[k]).abs().max())
-            e_ref = float((ref.grad.double() - g64[k]).abs().max())
-            floor = max(1e-5 * float(g64[k].abs().max()), 2e-6 * gscale)
-            if e_hip > max(2 * e_ref, floor):
-                bad.append((k, e_hip, e_ref))
-                # a kink can only excuse a tensor on which the fp32 ORACLE is off its own fp64 gradient as well
-                kink = kink and e_ref > floor
-            worst_ratio = max(worst_ratio, e_hip / max(e_ref, 1e-30))
-            worst_rel = max(worst_rel, e_hip / gscale)
-        return bad, worst_rel, worst_ratio, kink
-
-    for k, prm in zip(leaves, model.parameters()):
-        assert prm.grad is not None and prm.grad.shape == leaves[k].shape, k
-    key = (nb, nc, bs, nodes, pipes)
-    if key not in _G64_CACHE:
-        _G64_CACHE[key] = [grads64(p64)]
-    bad, worst_rel, worst_ratio, kink = judge(_G64_CACHE[key][0])
-    branch = 0
-    gen = torch.Generator().manual_seed(1234)
-    # the kink fallback fires only where it demonstrably applies: every failing tensor is one on which the fp32 oracle
-    # itself disagrees with its fp64 gradient beyond the tolerance floor (committed runs: never needed, branch 0)
-    while bad and kink and branch < 8:
-        branch += 1
-        if len(_G64_CACHE[key]) <= branch:
-            pert = {k: v * (1 + 1e-7 * torch.randn(v.shape, generator=gen, dtype=torch.float64)) for k, v in p64.items()}
-            _G64_CACHE[key].append(grads64(pert))
-        bad, worst_rel, worst_ratio, _ = judge(_G64_CACHE[key][branch])
-    assert not bad, (bad[:3], kink, branch)
+    hip = {k: prm.grad for k, prm in zip(leaves, model.parameters())}
+    ref32 = {k: v.grad for k, v in leaves.items()}
+    for k in leaves:
+        assert hip[k] is not None and hip[k].shape == leaves[k].shape, k
+    worst_rel, worst_ratio, branch = check_gradients_vs_fp64(hip, ref32, grads64, p64, _G64_CACHE,
+                                                             (nb, nc, bs, nodes, pipes))
     flat_hip = torch.cat([q.grad.reshape(-1) for q in model.parameters()])
     flat_ref = torch.cat([v.grad.reshape(-1) for v in leaves.values()])
     note(f"bwd nb{nb} nc{nc} {'fused' if fused else 'per-op'}: flat grad rel err vs oracle32 / worst err over |g|max vs "
