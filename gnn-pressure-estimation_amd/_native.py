@@ -90,6 +90,8 @@ SIGNATURES = {
     "gatres_mask_generate": (C.c_int, [_P, _I32, _F64, _U64, _P, _P, _P]),
     "gatres_stage_batch_mask": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I32, _F64, _U64, _P, _P, _P]),
     "gatres_stage_rows_mask": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _F64, _U64, _P, _P, _P]),
+    "gatres_stage_rows_mask_required": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _F64, _U64, _P, _P, _I32, _P, _P]),
+    "gatres_masked_metrics": (C.c_int, [_P, _P, _P, _I32, _F64, _F64, _P, _I32, _I32, _P, _P]),
     "gatres_masked_mse": (C.c_int, [_P] * 5 + [_I32, _P]),
     "gatres_adam_step": (C.c_int, [_P] * 5 + [_I64] + [_F64] * 5 + [_F32, _P]),
     # typed per-op kernels (storage type argument): C ints
@@ -142,7 +144,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 7                # GATRES_ABI_VERSION of include/gatres.h
+ABI_VERSION = 8                # GATRES_ABI_VERSION of include/gatres.h
 
 
 def diag_build() -> bool:

@@ -21,12 +21,26 @@ __device__ __forceinline__ uint64_t mask_key(uint64_t seed, uint64_t step, int g
   return ((z >> 32) << 32) | (uint32_t)local;
 }
 
+// A required node's key (the sensor pass of the evaluation): its local id alone, below every random key.
+__device__ __forceinline__ uint64_t mask_key_required(uint64_t seed, uint64_t step, int n0, int local,
+                                                      const int* __restrict__ required, int num_required) {
+  for (int i = 0; i < num_required; ++i)
+    if (required[i] == local) return (uint64_t)(uint32_t)local;
+  return mask_key(seed, step, n0 + local, local);
+}
+
 constexpr int MASK_WGS = 4;          // workgroups per graph of the sampler's own launch: each ranks one slice of the graph's nodes
 constexpr int MASK_WGS_UPDATE = 16;  // ... of the update launch's sampling tail (256 threads each: smaller slices, 3 us beside the reduction)
 // Workgroup `wq` of WGS for graph g (T threads): mask[n0 .. n0 + n) for its slice (the whole graph beyond 2048 nodes, wq == 0).
-template <int T, int WGS>
+// REQ (the evaluation's sensor pass, utils/auxil.py:143-163 with required_idx): the num_required local indices in required[]
+// are always masked -- their keys drop the random upper half, so they rank below every other key -- and the remaining
+// int(n*rate) - num_required masked nodes are the smallest keys among the others: a uniform subset without replacement of the
+// non-required nodes, as np.random.choice(np.setdiff1d(...), k - r, replace=False).  The caller guarantees 0 <= required[i] < n,
+// no duplicates and num_required < int(n*rate).  REQ == false compiles to exactly the sampler without the list.
+template <int T, int WGS, bool REQ = false>
 __device__ __forceinline__ void mask_sample_graph(const int* __restrict__ node_ptr, double rate, uint64_t seed, uint64_t step,
-                                                  uint8_t* __restrict__ mask, int g, int wq) {
+                                                  uint8_t* __restrict__ mask, int g, int wq,
+                                                  const int* __restrict__ required = nullptr, int num_required = 0) {
   constexpr int SMALL = 2048;                      // graphs up to SMALL nodes: all-pairs rank in LDS (~2 us for C-Town)
   __shared__ uint64_t s_keys[SMALL];
   __shared__ int s_rank[SMALL];
@@ -47,6 +61,13 @@ __device__ __forceinline__ void mask_sample_graph(const int* __restrict__ node_p
     // over all threads: Q threads per node, each ranks the node against one slice of the keys.
     for (int v = tid; v < n; v += T) { s_keys[v] = mask_key(seed, step, n0 + v, v); s_rank[v] = 0; }
     __syncthreads();
+    if constexpr (REQ) {
+      for (int i = tid; i < num_required; i += T) {
+        const int v = required[i];
+        if (v >= 0 && v < n) s_keys[v] = (uint64_t)(uint32_t)v;
+      }
+      __syncthreads();
+    }
     const int Q = min(16, max(1, (n + 63) / 64));   // slices of ~64 keys: 7 for C-Town's 388 nodes
     const int slice = (n + Q - 1) / Q;
     const int per = (n + WGS - 1) / WGS, vlo = min(n, wq * per), vhi = min(n, vlo + per);
@@ -68,7 +89,7 @@ __device__ __forceinline__ void mask_sample_graph(const int* __restrict__ node_p
     __syncthreads();
     const uint64_t prefix = s_prefix;
     for (int v = tid; v < n; v += T) {
-      const uint64_t key = mask_key(seed, step, n0 + v, v);
+      const uint64_t key = REQ ? mask_key_required(seed, step, n0, v, required, num_required) : mask_key(seed, step, n0 + v, v);
       const bool match = (pass == 7) || ((key >> (8 * (pass + 1))) == prefix);
       if (match) atomicAdd(&hist[(int)((key >> (8 * pass)) & 255)], 1);
     }
@@ -82,7 +103,8 @@ __device__ __forceinline__ void mask_sample_graph(const int* __restrict__ node_p
     __syncthreads();
   }
   const uint64_t kth = s_prefix;
-  for (int v = tid; v < n; v += T) mask[n0 + v] = mask_key(seed, step, n0 + v, v) <= kth ? 1 : 0;
+  for (int v = tid; v < n; v += T) mask[n0 + v] = (REQ ? mask_key_required(seed, step, n0, v, required, num_required)
+                                                          : mask_key(seed, step, n0 + v, v)) <= kth ? 1 : 0;
 }
 
 }  // namespace

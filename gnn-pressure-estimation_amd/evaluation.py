@@ -7,13 +7,19 @@ the GATRes models run with (``use_data_batch=False``, no edge attributes), utils
 and their registry) and utils/timer.py:12-66 (``Timer``: warm-up, then one event pair per inference call).  The sensor
 indices themselves come from a secrets file the reference does not ship (evaluation.py:27-66: without it ``get_sensors``
 returns empty lists and the second pass equals the first); here they are an argument.
-The model call is the fused forward kernel (no activations kept under ``torch.no_grad()``); everything else here is
-caller-side tensor arithmetic, exactly as in the reference.
+The model call is the fused forward kernel (no activations kept under ``torch.no_grad()``); everything else in
+``test_one_epoch`` is caller-side tensor arithmetic, exactly as in the reference.
+
+``evaluate_store`` is the same epoch on the device for a ``SnapshotStore``: per batch one staging launch (collation + a mask
+that holds the sensor nodes on the sensor pass), the forward, and one launch that writes the batch's masked-metric moments
+(``gatres_masked_metrics``) into a device table; one synchronisation and one read-back per epoch, then
+``metrics_from_moments`` forms the loss and the seven metrics on the host in fp64.
 """
 from __future__ import annotations
 
+import weakref
 from functools import partial
-from typing import Callable, Dict, Iterable, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -155,6 +161,232 @@ def test_trials(model: torch.nn.Module, make_loader: Callable[[], Iterable], num
     for _ in range(int(num_test_trials)):
         loss, m = test_one_epoch(model, make_loader(), mask_rate, do_test_on_sensors=False, **kw)
         s_loss, s_m = test_one_epoch(model, make_loader(), mask_rate, do_test_on_sensors=True, required_idx=required_idx, **kw)
+        losses.append(loss); s_losses.append(s_loss)
+        for k, v in m.items():
+            metrics[k].append(v)
+        for k, v in s_m.items():
+            s_metrics[k].append(v)
+    return losses, dict(metrics), s_losses, dict(s_metrics)
+
+
+
+# ---- the epoch on the device (gatres_stage_rows_mask_required + gatres_model_forward + gatres_masked_metrics) ----------------
+METRICS_RECORD = 16            # GATRES_METRICS_RECORD of include/gatres.h: doubles per batch in the moment table
+
+
+def metrics_from_moments(table, graphs_per_batch: Sequence[int], prefix: str = "test") -> Tuple[float, Dict[str, float]]:
+    """The loss (``MSELoss`` on scaled values) and the seven metrics of ``get_metric_fn_collection(prefix)`` from a moment
+    table ``[B, METRICS_RECORD]``, each batch's value weighted by its graph count and divided by the dataset size
+    (train.py:278-279, evaluation.py:340-345).  fp64.  torch's NaN cases carry over: no kept element gives ``error`` NaN,
+    zero variance gives ``corr`` / ``r2`` NaN, an empty mask gives NaN everywhere."""
+    T = np.asarray(table, dtype=np.float64).reshape(-1, METRICS_RECORD)
+    w = [int(g) for g in graphs_per_batch]
+    if len(w) != T.shape[0]:
+        raise ValueError(f"{T.shape[0]} records for {len(w)} batches")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        M = T[:, 0]
+        corr = np.clip(T[:, 8] / (np.sqrt(T[:, 6]) * np.sqrt(T[:, 7])), -1.0, 1.0)
+        per = {"loss": T[:, 1] / M,
+               f"{prefix}_error": T[:, 10] / T[:, 9],
+               f"{prefix}_0.1": T[:, 11] / M,
+               f"{prefix}_corr": corr,
+               f"{prefix}_r2": corr * corr,
+               f"{prefix}_mae": T[:, 2] / M,
+               f"{prefix}_rmse": np.sqrt(T[:, 3] / M),
+               f"{prefix}_mynse": 1.0 - T[:, 3] / (T[:, 7] + 1e-12)}
+    n = sum(w)
+    out = {}
+    for k, v in per.items():
+        acc = 0.0
+        for b, g in enumerate(w):          # the host loop's order: total += metric * num_graphs, batch by batch
+            acc += float(v[b]) * g
+        out[k] = acc / n
+    return out.pop("loss"), out
+
+
+def _same_fn(a, b) -> bool:
+    if isinstance(a, partial) and isinstance(b, partial):
+        return a.func is b.func and a.args == b.args and a.keywords == b.keywords
+    return a is b
+
+
+def _check_reference_metrics(criterion, metric_fn_dict, prefix: str) -> None:
+    if criterion is not None and not (isinstance(criterion, torch.nn.MSELoss) and criterion.reduction == "mean"):
+        raise ValueError(f"evaluate_store computes MSELoss(reduction='mean') only; got {criterion!r}")
+    if metric_fn_dict is not None:
+        ref = get_metric_fn_collection(prefix)
+        if list(metric_fn_dict) != list(ref) or not all(_same_fn(metric_fn_dict[k], ref[k]) for k in ref):
+            raise ValueError("evaluate_store computes get_metric_fn_collection(prefix) only (the reference's seven metrics); "
+                             "use test_one_epoch for other metric functions")
+
+
+class _EvalPlan:
+    """Static buffers of one batch size: staged inputs / targets, mask, predictions, the plan and the forward's call state."""
+
+    def __init__(self, model, store, num_graphs: int):
+        npg = store.nodes_per_graph
+        self.num_graphs, self.num_nodes = num_graphs, num_graphs * npg
+        self.edge_index = store.edge_index(num_graphs)
+        self.plan = model.plan_for(self.edge_index, self.num_nodes)
+        self.node_ptr = self.plan.node_ptr_for([npg] * num_graphs)
+        dev = store.device
+        self.x = torch.empty(self.num_nodes, dtype=torch.float32, device=dev)
+        self.mask = torch.empty(self.num_nodes, dtype=torch.uint8, device=dev)
+        self.out = torch.empty((self.num_nodes, 1), dtype=torch.float32, device=dev)
+
+    def refresh(self, model) -> "_EvalPlan":
+        """The forward's call state and buffers as the model holds them now (through its caches: no device work)."""
+        self.state = model._call_state(self.plan)
+        self.saved = model._eval_saved_for(self.plan) if self.state["window"] else None
+        return self
+
+
+# model -> {(edge_index identity, nodes, engine configuration): _EvalPlan}.  The model's own plan cache remembers ONE edge_index
+# tensor by identity and hashes any other (a device hash and a read-back): the full and the ragged batch size alternate every
+# epoch, and each switch would cost a synchronisation.
+_EVAL_PLANS = weakref.WeakKeyDictionary()
+
+
+def _eval_plan(model, store, num_graphs: int) -> _EvalPlan:
+    ei = store.edge_index(num_graphs)
+    key = (ei.data_ptr(), ei._version, num_graphs * store.nodes_per_graph, str(ei.device), bool(model.fused))
+    plans = _EVAL_PLANS.setdefault(model, {})
+    P = plans.get(key)
+    if P is None or P.edge_index is not ei:
+        if len(plans) >= 8:
+            plans.clear()
+        P = plans[key] = _EvalPlan(model, store, num_graphs)
+    return P.refresh(model)
+
+
+def _mix_seed(seed: int, *salt: int) -> int:
+    z = int(seed) & 0xFFFFFFFFFFFFFFFF
+    for s in salt:
+        z = (z + 0x9E3779B97F4A7C15 * (int(s) + 1)) & 0xFFFFFFFFFFFFFFFF
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+        z ^= z >> 31
+    return z
+
+
+def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: float, *, prefix: str = "test",
+                   do_test_on_sensors: bool = False, required_idx: Sequence[int] = (), use_same_mask: bool = False,
+                   seed: int = 0, gpu_warmup_times: int = 10, norm_type: Optional[str] = None,
+                   criterion: Optional[Callable] = None, metric_fn_dict: Optional[Dict[str, Callable]] = None,
+                   _capture: Optional[List] = None) -> Tuple[float, Dict[str, float]]:
+    """``test_one_epoch`` over a ``SnapshotStore`` on the device: the same ``(loss, metrics)`` keys -- the reference's seven
+    metrics, ``{prefix}_time`` (ms/graph) and ``{prefix}_throughput``, ``_sensor`` postfixed on the sensor pass.
+
+    The store is taken in order (no shuffle) in batches of ``batch_size``; a ragged last batch runs on its own plan.  Per
+    batch, three launches on the current stream: staging + mask (``gatres_stage_rows_mask_required``: exactly
+    ``int(n * mask_rate)`` masked nodes per graph, the ``required_idx`` ones always on the sensor pass), the inference forward
+    with the mask (``gatres_model_forward``, as ``model(x1, edge_index)`` with ``x1[mask] = 0`` computes it), and the moments
+    (``gatres_masked_metrics``).  ``Timer``'s definition is kept: ``gpu_warmup_times`` untimed forwards on the first batch, then
+    one event pair around each forward; the events are read after the epoch's one synchronisation.  Masks come from the device
+    sampler (seeded by ``seed`` and the batch index; ``use_same_mask``: one mask per batch size, as the host loop reuses its
+    mask while the batch shape stays), not from numpy: the metrics agree with ``test_one_epoch`` given the same masks.  The
+    same ``seed`` draws the same masks: a validation pass per training epoch that wants fresh masks, as the host loop's numpy
+    stream gives it, passes ``seed=epoch``.
+    ``norm_type``: ``None`` takes the store's (``znorm``: descaled with its mean / std; ``unused``: not descaled).
+    Only ``MSELoss`` and ``get_metric_fn_collection(prefix)`` are computed; anything else passed as ``criterion`` /
+    ``metric_fn_dict`` is refused.  ``_capture`` (tests): a list that receives ``(mask, out, x, num_graphs)`` per batch."""
+    from . import _native
+    _check_reference_metrics(criterion, metric_fn_dict, prefix)
+    if batch_size <= 0:
+        raise ValueError("batch_size must be positive")
+    norm_type = store.norm_type if norm_type is None else norm_type
+    if norm_type == "znorm":
+        scale, offset = float(store.std), float(store.mean)
+    elif norm_type == "unused":
+        scale, offset = 1.0, 0.0
+    else:
+        raise ValueError(f"norm_type={norm_type!r}: a SnapshotStore is z-normalised ('znorm') or not normalised ('unused')")
+    npg, S = store.nodes_per_graph, len(store)
+    if S == 0:
+        raise ValueError("empty store")
+    required = sorted(set(int(i) for i in required_idx)) if do_test_on_sensors else []
+    if required and (required[0] < 0 or required[-1] >= npg):
+        raise ValueError(f"required_idx must lie in [0, {npg})")
+    if int(npg * mask_rate) - len(required) <= 0:
+        raise ValueError("mask length must be positive")
+    postfix = "_sensor" if do_test_on_sensors else ""
+    model.eval()
+    if not model._flat_is_current():
+        model._flatten_parameters()
+    flat = model._flat
+    dev = store.device
+    if flat.device != dev:
+        raise ValueError(f"model is on {flat.device}, the store on {dev}")
+    lib = _native.load()
+    nb = (S + batch_size - 1) // batch_size
+    sizes = [min(batch_size, S - b * batch_size) for b in range(nb)]
+    with torch.cuda.device(dev):
+        stream = _native.current_stream(dev)
+        plans = {g: _eval_plan(model, store, g) for g in sorted(set(sizes))}
+        order = torch.arange(S, dtype=torch.int64, device=dev)
+        # the sampler's step of each batch: the batch index, or one mask per batch size under use_same_mask
+        steps = [(0 if g == batch_size else 1) if use_same_mask else b for b, g in enumerate(sizes)]
+        # (uploads from pinned memory, asynchronous: a pageable copy would synchronise the stream; the host tensors stay
+        #  alive until the epoch's synchronisation below)
+        steps_host = torch.tensor(steps, dtype=torch.int64).pin_memory()
+        steps_dev = steps_host.to(dev, non_blocking=True)
+        req_host = torch.tensor(required, dtype=torch.int32).pin_memory() if required else None
+        req_dev = req_host.to(dev, non_blocking=True) if required else None
+        table = torch.zeros((nb, METRICS_RECORD), dtype=torch.float64, device=dev)
+        events = []
+        seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+        def forward(P: _EvalPlan) -> None:
+            st = P.state
+            _native.check(lib.gatres_model_forward(st["mref_infer"], st["gref"], flat.data_ptr(), P.x.data_ptr(),
+                                                   P.mask.data_ptr(), P.out.data_ptr(), _native.ptr(P.saved),
+                                                   st["scratch"].data_ptr(), stream), "gatres_model_forward")
+
+        for b, g in enumerate(sizes):
+            P = plans[g]
+            rows = order[b * batch_size: b * batch_size + g]
+            _native.check(lib.gatres_stage_rows_mask_required(
+                store.data.data_ptr(), rows.data_ptr(), npg, P.x.data_ptr(), None, P.node_ptr.data_ptr(), g,
+                float(mask_rate), seed64, steps_dev.data_ptr() + 8 * b, _native.ptr(req_dev), len(required),
+                P.mask.data_ptr(), stream), "gatres_stage_rows_mask_required")
+            if b == 0:
+                for _ in range(max(int(gpu_warmup_times), 0)):
+                    forward(P)
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            forward(P)
+            end.record()
+            events.append((start, end))
+            _native.check(lib.gatres_masked_metrics(P.out.data_ptr(), P.x.data_ptr(), P.mask.data_ptr(), P.num_nodes,
+                                                    scale, offset, table.data_ptr(), b, nb, None, stream),
+                          "gatres_masked_metrics")
+            if _capture is not None:
+                _capture.append((P.mask.clone(), P.out.clone(), P.x.clone(), g))
+        torch.cuda.synchronize(dev)
+        host = table.cpu().numpy()
+        del steps_host, req_host
+    timer = Timer()
+    timer.timings = [s.elapsed_time(e) for s, e in events]
+    timer.num_graphs = list(sizes)
+    loss, metrics = metrics_from_moments(host, sizes, prefix)
+    key = list(metrics.keys())[0].split("_")[0]            # (test_one_epoch's derivation of the timing keys' prefix)
+    metrics[key + "_time"] = timer.compute_time(S)
+    metrics[key + "_throughput"] = timer.compute_throughput(S)
+    return loss, {k + postfix: v for k, v in metrics.items()}
+
+
+def evaluate_store_trials(model: torch.nn.Module, store, batch_size: int, num_test_trials: int, mask_rate: float,
+                          required_idx: Sequence[int] = (), seed: int = 0, **kw):
+    """``test_trials`` on the device: per trial an all-nodes pass and a sensor pass of ``evaluate_store``, each with masks of
+    its own (the mask seed is derived from ``seed``, the trial and the pass).  Returns ``(test_losses, test_metrics,
+    sensor_losses, sensor_metrics)``, the metric dicts mapping a key to the list of its per-trial values."""
+    from collections import defaultdict
+    losses, metrics, s_losses, s_metrics = [], defaultdict(list), [], defaultdict(list)
+    for t in range(int(num_test_trials)):
+        loss, m = evaluate_store(model, store, batch_size, mask_rate, do_test_on_sensors=False,
+                                 seed=_mix_seed(seed, t, 0), **kw)
+        s_loss, s_m = evaluate_store(model, store, batch_size, mask_rate, do_test_on_sensors=True, required_idx=required_idx,
+                                     seed=_mix_seed(seed, t, 1), **kw)
         losses.append(loss); s_losses.append(s_loss)
         for k, v in m.items():
             metrics[k].append(v)

@@ -210,6 +210,9 @@ class GATResTrainer:
         # the fused path's parameter gradients can be formed range by range (a bucket's all-reduce starts in between)
         self._ranges = bool(self.fused and self.lib.gatres_fused_finish_folds(model._cmodel_ref(), self.plan.ref()))
         self._faults_seen = 0
+        # fit_epoch(device_metrics=True): the moment table, its cursor and the descale affine while such an epoch runs (None
+        # otherwise: then no launch and no graph key changes)
+        self._metrics: Optional[dict] = None
         self._warn_if_the_chip_is_not_ours()
 
     def _warn_if_the_chip_is_not_ours(self) -> None:
@@ -358,6 +361,21 @@ class GATResTrainer:
         ts = self._desc(phases, device_mask, wt_valid, flags, block_lo, block_hi, batch, masks, loss)
         _native.check(self.lib.gatres_train_step(C.byref(ts), _native.current_stream(self.device)),
                       "gatres_train_step")
+        if self._metrics is not None and (phases & PHASE_FORWARD):
+            self._enqueue_metrics(batch, masks)
+
+    def _enqueue_metrics(self, batch=None, masks=None) -> None:
+        """The masked-metric moments of the step just enqueued (fit_epoch(device_metrics=True)): ``out`` is written by its
+        forward and the step's mask is still in place -- the update launch samples the NEXT step's mask into the other buffer,
+        and in a captured sequence the step after this one overwrites it only in its own update launch.  The record goes to
+        the slot the table's device cursor names; the kernel advances the cursor, so replayed sequences and the sibling
+        trainer of the ragged batch write consecutive slots."""
+        met = self._metrics
+        by = self.y if batch is None else batch[1]
+        mask = self.mask if masks is None else masks[0]
+        _native.check(self.lib.gatres_masked_metrics(
+            self.out.data_ptr(), by.data_ptr(), mask.data_ptr(), self.N, met["scale"], met["offset"], met["table"].data_ptr(),
+            0, met["table"].shape[0], met["cursor"].data_ptr(), _native.current_stream(self.device)), "gatres_masked_metrics")
 
     def _mask_key(self):
         """What a mask sampled by the update launch is valid for: the optimizer state as this trainer left it (a sibling's or a
@@ -392,6 +410,9 @@ class GATResTrainer:
 
     def _replay(self, key: tuple, enqueue: Callable[[], None], wt_valid: bool = False) -> None:
         """Run ``enqueue`` -- eagerly, or captured once into a hipGraph (cached by ``key``) and replayed."""
+        met = self._metrics
+        if met is not None:            # (a step with the metrics launch is another graph than the same step without it)
+            key = key + (("metrics", met["table"].data_ptr(), met["cursor"].data_ptr(), met["scale"], met["offset"]),)
         if not self.use_graph:
             enqueue()
             return
@@ -405,7 +426,8 @@ class GATResTrainer:
             # warm-up launch outside capture (module load, lazy init, RCCL communicator), then capture the same sequence
             state = (self.step_counter.clone(), self.model.flat_parameters.clone(), self.exp_avg.clone(),
                      self.exp_avg_sq.clone(), self.mask.clone(), self._mask_spare.clone(),
-                     self._clip.save() if self._clip is not None else None)
+                     self._clip.save() if self._clip is not None else None,
+                     met["cursor"].clone() if met is not None else None)
 
             def rollback():
                 self.step_counter.copy_(state[0]); self.model.flat_parameters.copy_(state[1])
@@ -414,6 +436,8 @@ class GATResTrainer:
                 self._mask_spare.copy_(state[5])  # (a multi-step sequence samples into BOTH buffers, two steps ahead of the rollback)
                 if state[6] is not None:          # (the count, and the sorted copy a multi-step warm-up overwrote)
                     self._clip.restore(state[6])
+                if state[7] is not None:          # (the warm-up's records are overwritten by the real steps: same slots)
+                    met["cursor"].copy_(state[7])
 
             enqueue()
             torch.cuda.synchronize(self.device)
@@ -1022,6 +1046,45 @@ class GATResTrainer:
             self._graphs.clear()
             self._epoch_buf = self._epoch_bound = self._epoch_losses = None
 
+    def _fit_epoch_device_metrics(self, store, bs: int, shuffle: bool, drop_last: bool, generator,
+                                  metric_fn_dict) -> Tuple[float, Dict[str, float]]:
+        """fit_epoch with the metrics launch in every step (device_metrics=True)."""
+        from . import evaluation as E
+        keys = list(metric_fn_dict or {})
+        if not keys or not keys[0].endswith("_error"):
+            raise ValueError("device_metrics=True computes evaluation.get_metric_fn_collection(prefix) only; "
+                             "pass that collection as metric_fn_dict")
+        prefix = keys[0][:-len("_error")]
+        E._check_reference_metrics(None, metric_fn_dict, prefix)
+        if store.norm_type == "znorm":
+            scale, offset = float(store.std), float(store.mean)
+        else:
+            scale, offset = 1.0, 0.0
+        S = store.num_snapshots
+        sizes = [bs] * (S // bs) + ([S % bs] if S % bs and not drop_last else [])
+        if not sizes:
+            raise ValueError("the store yielded no batch")
+        table = getattr(self, "_metrics_table", None)
+        if table is None or table.shape[0] < len(sizes):
+            # persistent across epochs: its address is part of the captured steps' graph keys
+            table = self._metrics_table = torch.zeros((len(sizes), E.METRICS_RECORD), dtype=torch.float64, device=self.device)
+            self._metrics_cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+        table.zero_()
+        self._metrics_cursor.zero_()
+        met = {"table": table, "cursor": self._metrics_cursor, "scale": scale, "offset": offset}
+        self._metrics = met                 # (_sibling() hands it on to the ragged batch's trainer)
+        try:
+            loss, _ = self.fit_epoch(store, bs, shuffle=shuffle, drop_last=drop_last, generator=generator)
+        finally:
+            self._metrics = None
+            for t in self._siblings.values():
+                t._metrics = None
+        written = int(self._metrics_cursor.item())
+        if written != len(sizes):
+            raise RuntimeError(f"the epoch wrote {written} metric records for {len(sizes)} batches")
+        _, metrics = E.metrics_from_moments(table[:len(sizes)].cpu().numpy(), sizes, prefix)
+        return loss, metrics
+
     def _sibling(self, num_graphs: int, nodes_per_graph: int, edge_index: torch.Tensor) -> "GATResTrainer":
         """Trainer for another batch size of the same dataset (the ragged last batch of an epoch): its own plan and
         buffers, the SAME model, Adam moments and step counter."""
@@ -1038,24 +1101,35 @@ class GATResTrainer:
             t.seed = self.seed
             self._siblings[num_graphs] = t
         t.mask_rate = self.mask_rate
+        t._metrics = self._metrics          # (device_metrics: the ragged batch writes the epoch's last record)
         return t
 
     def fit_epoch(self, store, batch_size: Optional[int] = None, shuffle: bool = True, drop_last: bool = False,
                   generator: Optional[torch.Generator] = None, metric_fn_dict: Optional[Dict[str, Callable]] = None,
-                  ) -> Tuple[float, Dict[str, float]]:
+                  device_metrics: bool = False) -> Tuple[float, Dict[str, float]]:
         """One epoch over a ``SnapshotStore`` -- the loop of ``train_one_epoch`` (train.py:159-198): shuffled batches, a
         fresh per-graph mask every batch, one optimisation step each, loss weighted by the batch's graph count.
         Batches are row gathers of the device-resident store (no host collation, no H2D); a ragged last batch runs on
         a sibling trainer that shares this one's optimizer state.  Returns ``(mean loss, metrics)``; metrics (the
         reference's de-normalised per-batch metrics, train.py:179-198) are only computed when ``metric_fn_dict`` is
         given, since they need a boolean gather per batch.  Under data parallelism every rank passes its own shard of
-        the snapshots (``dp.shard_graphs``)."""
+        the snapshots (``dp.shard_graphs``).
+
+        ``device_metrics=True`` (with ``metric_fn_dict`` = ``evaluation.get_metric_fn_collection(prefix)``, the only collection
+        it computes): every step's forward is followed by the masked-metric moments launch (``gatres_masked_metrics``) inside
+        the same launch sequence -- the in-place epoch and the captured k-step sequences stay on -- and the metrics are formed
+        from the epoch's moment table at the end (``evaluation.metrics_from_moments``).  Training itself is untouched: the
+        same parameters, moments and loss bit for bit as without metrics.  ``device_metrics=False`` (default): nothing of
+        this runs."""
         npg = store.nodes_per_graph
         bs = int(batch_size) if batch_size is not None else self.num_graphs
         if bs != self.num_graphs or npg * bs != self.N:
             raise ValueError(f"this trainer was built for batches of {self.num_graphs} graphs x {self.N // max(self.num_graphs, 1)} nodes")
         if self.world > 1:
             drop_last = True                 # equal graph counts on every rank keep plain gradient averaging exact
+        host_metrics = bool(metric_fn_dict) and not device_metrics
+        if device_metrics:
+            return self._fit_epoch_device_metrics(store, bs, shuffle, drop_last, generator, metric_fn_dict)
         # the epoch's loss sum in DOUBLE (train.py:196 accumulates Python floats): a sum of fp32 losses is exact there, so a
         # sequence's k losses added at once and the same losses added one by one give the same bits
         total = torch.zeros(1, dtype=torch.float64, device=self.device)
@@ -1071,7 +1145,7 @@ class GATResTrainer:
         order = store.epoch_order(shuffle=shuffle, generator=generator)
         first = 0                                        # batches [0, first) are done by the in-place path below
         nfull = store.num_snapshots // bs
-        if (kseq > 1 and not metric_fn_dict and nfull >= 2 and self._mask_next and self.node_ptr is not None
+        if (kseq > 1 and not host_metrics and nfull >= 2 and self._mask_next and self.node_ptr is not None
                 and self._epoch_copy_fits(nfull * bs, npg)):
             # The epoch's full batches as ONE device gather into a persistent buffer (the shuffled store: S x N_g floats), then
             # trained IN PLACE, k per captured launch sequence, with the mask sampled ahead by the update launches -- the
@@ -1092,7 +1166,7 @@ class GATResTrainer:
                 seen += bs
 
         for rows, edge_index, ng in store.row_batches(bs, drop_last=drop_last, order=order, first=first):
-            if ng == bs and not metric_fn_dict and kseq > 1:
+            if ng == bs and not host_metrics and kseq > 1:
                 pending.append(rows)
                 if len(pending) == kseq:
                     # (row_batches yields consecutive slices of ONE order tensor: the run is its slice too)
@@ -1111,7 +1185,7 @@ class GATResTrainer:
                 tr.load_batch(x, x)
                 tr.run_step(device_mask=True)
             total.add_(tr.loss.double(), alpha=float(ng))
-            if metric_fn_dict:
+            if host_metrics:
                 m = tr.mask.bool()
                 p, t = store.descale(tr.out[m]), store.descale(tr.x[m])
                 for k, fn in metric_fn_dict.items():

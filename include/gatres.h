@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GATRES_ABI_VERSION 7
+#define GATRES_ABI_VERSION 8
 
 #define GATRES_E_BADARG      (-1)  /* null pointer, negative size, misaligned pointer            */
 #define GATRES_E_UNSUPPORTED (-2)  /* width not supported by the gfx950 kernels                  */
@@ -284,6 +284,29 @@ int gatres_stage_batch_mask(const float* x_src, const float* y_src, float* x_dst
 int gatres_stage_rows_mask(const float* data, const int64_t* rows, int32_t nodes_per_graph, float* x_dst, float* y_dst,
                            const int32_t* node_ptr, int32_t num_graphs, double mask_rate, uint64_t seed,
                            const uint64_t* step_counter, uint8_t* mask, void* stream);
+
+/* gatres_stage_rows_mask whose mask always holds the sensor nodes (utils/auxil.py:143-163 with required_idx, evaluation.py's
+ * second pass): required[num_required] (device int32) are node indices INSIDE a graph, distinct, in [0, nodes_per_graph);
+ * every graph masks exactly int(nodes_per_graph * mask_rate) nodes -- the required ones and a uniform subset without
+ * replacement of the others.  num_required >= int(nodes_per_graph * mask_rate) is refused (GATRES_E_BADARG), as the
+ * reference refuses a mask length <= 0.  num_required == 0 draws the same masks as gatres_stage_rows_mask. */
+int gatres_stage_rows_mask_required(const float* data, const int64_t* rows, int32_t nodes_per_graph, float* x_dst, float* y_dst,
+                                    const int32_t* node_ptr, int32_t num_graphs, double mask_rate, uint64_t seed,
+                                    const uint64_t* step_counter, const int32_t* required, int32_t num_required, uint8_t* mask,
+                                    void* stream);
+
+/* Masked-metric moments of one batch (evaluation.get_metric_fn_collection + MSELoss, utils/auxil.py:101-140,185-203):
+ * one record of GATRES_METRICS_RECORD doubles into table[slot] (slot += *cursor when cursor != NULL; the kernel then
+ * advances *cursor by one, so a replayed capture writes consecutive slots; a slot outside [0, capacity) is not written).
+ * out, y: scaled fp32 [num_nodes]; p = fp32(fp32(out * (float)scale) + (float)offset), t likewise from y, as torch rounds
+ * `descale()`.  Record over the masked nodes:
+ *   [0] M   [1] sum (out - y)^2 (scaled)   [2] sum |p - t|   [3] sum (p - t)^2   [4] sum p   [5] sum t
+ *   [6] sum (p - pm)^2   [7] sum (t - tm)^2   [8] sum (p - pm)(t - tm)     (pm, tm: the means of p, t; a second pass)
+ *   [9] #{|t| > 0.01f}   [10] sum over those of |t - p| / |t|   [11] #{|t - p| <= t * 0.1f}   [12..15] 0
+ * One workgroup, fixed-order fp64 reduction: the same bits on every run. */
+#define GATRES_METRICS_RECORD 16
+int gatres_masked_metrics(const float* out, const float* y, const uint8_t* mask, int32_t num_nodes, double scale,
+                          double offset, double* table, int32_t slot, int32_t capacity, uint64_t* cursor, void* stream);
 
 /* MSELoss(mean) over masked nodes + its gradient: loss[0] = mean_{mask}(out-y)^2, g_out[n] = mask ? 2(out-y)/M : 0. */
 int gatres_masked_mse(const float* out, const float* y, const uint8_t* mask, float* loss, float* g_out,
