@@ -27,7 +27,6 @@ struct gatres_knobs_t {
   int fused_split;            // GATRES_FUSED_SPLIT = 1 .. 8: workgroups per snapshot (0: automatic)
   int fused_safe_sync;        // GATRES_FUSED_SAFE_SYNC: always agent-scope hand-offs (what parts on different XCDs get)
   int fused_no_halo;          // GATRES_FUSED_NO_HALO: whole-segment kernel, bulk pulls (what an overflowing halo list gets)
-  int fused_no_consumers;     // 1 unless GATRES_FUSED_WITH_CONSUMERS=1: parameter gradients as a launch of their own (the default)
   int fused_no_rounds;        // GATRES_FUSED_NO_ROUNDS: 49 .. 96 segments resident at fewer parts instead of two rounds
   int agg_lane_features;      // GATRES_AGG_LANE_FEATURES = 4 | 8 (0: automatic -- 8 for rows of 64 features and more)
   int lin_bwd_wave;           // GATRES_LIN_BWD_WAVE: lin0 / lin1 backward, one wave per slab (what odd widths get)
@@ -47,13 +46,10 @@ struct gatres_knobs_t {
   int agg_wide_offsets;       // GATRES_AGG_WIDE_OFFSETS
   int fused_threads;          // GATRES_FUSED_THREADS = 512 (default 1024)
   int fused_no_window;        // GATRES_FUSED_NO_WINDOW
-  int fused_prefer_consumers; // GATRES_FUSED_PREFER_CONSUMERS
-  int fused_consumers_cap;    // GATRES_FUSED_CONSUMERS (default 2, at most 4)
   int fused_nocache;          // GATRES_FUSED_NOCACHE
   int fused_wide;             // GATRES_FUSED_WIDE (nc > 32 on the per-snapshot kernels)
   int fused_no_keep;          // GATRES_FUSED_NO_KEEP
   int fused_heartbeat;        // GATRES_FUSED_HEARTBEAT: pace the hand-offs by heartbeat granules even on symmetric plans
-  int param_grads_no_stream;  // GATRES_PARAM_GRADS_NO_STREAM
   int proj_rows;              // GATRES_PROJ_ROWS (0: default)
   int proj_stream;            // GATRES_PROJ_STREAM=1: bf16 projections of gatres_large by proj_bf16_stream_kernel
   int dw_fp32;                // GATRES_DW_FP32

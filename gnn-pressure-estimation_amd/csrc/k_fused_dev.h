@@ -65,7 +65,6 @@ struct FusedArgs {
   int safe_sync;            // diagnostic (GATRES_FUSED_SAFE_SYNC=1): always use agent-scope barriers
   int keep_lds;             // window kernel, forward + backward in one launch: ReLU sign masks and own-row g_pre stay in LDS
   int no_halo;              // diagnostic (GATRES_FUSED_NO_HALO=1): always take the bulk-pull fallback
-  int C;                    // consumer workgroups per segment (deferred parameter gradients on spare CUs), 0 = none
   int sym;                  // the plan's GATRES_GRAPH_SYMMETRIC: partners owe each other halo rows in both directions
   int facts;                // window kernel, host side only: what the launch may take as compile-time facts (k_window.hip: 0x400
                             // no row with more than MAXD entries, 0x1000 no part with more than 64 rows, 0x2000 a forward-only launch whose saved
@@ -73,7 +72,6 @@ struct FusedArgs {
                             // (gatres_probe_xcd_dispatch: the launch starts without its first cross-CU barrier)
   const int* ptab;          // the plan's part tables (gatres_graph_t.part_tables) and what they were built for; may be null
   int ptab_m, ptab_stride;
-  unsigned* ready;          // [segment][4] lines: items published by the segment's part 0 for each consumer
   unsigned long long* xch;  // window kernel: granule exchange regions, one per segment (Layout::sc_xch)
   int* urec;                // window kernel: GATRES_UREC_WORDS words per workgroup (Layout::sc_urec), written by its prologue
   XchLayout XL;
@@ -161,27 +159,6 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   float s = 0.f;
   for (int w = 0; w < THREADS / 64; ++w) s += red[w];
   return s;
-}
-
-// streaming read (nt): the deferred-gradient items read every kept / saved table exactly once; keep them from
-// evicting the L2 lines the per-snapshot workgroups on the same XCD are working with
-__device__ __forceinline__ float4 ld4_nt(const float* p) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-template <int KQ>
-__device__ __forceinline__ void load_frag_nt(const float* p, float (&f)[KQ]) {
-  if constexpr (KQ % 4 == 0) {
-#pragma unroll
-    for (int s = 0; s < KQ; s += 4) {
-      const float4 v = ld4_nt(p + s);
-      f[s] = v.x; f[s + 1] = v.y; f[s + 2] = v.z; f[s + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < KQ; ++s) f[s] = __builtin_nontemporal_load(p + s);
-  }
 }
 
 template <int KQ>
@@ -465,7 +442,7 @@ __device__ __forceinline__ void seg_dw(int n, const float* G, int gb, const floa
 // operands come from per-lane VECTOR loads (float4 / float2) of contiguous features instead of 4-byte column
 // slices; R row ranges run on R waves, their partial blocks meet in LDS (`part`, R*HC*K floats: the backward's idle
 // g_pre|g_y2 / g_out1 region) and are summed in range order -> the segment's slab.  Deterministic.
-template <int HC, int K, int THREADS, bool NT = false>
+template <int HC, int K, int THREADS>
 __device__ __forceinline__ void seg_dw_blk(int n, int R, const float* G, int gb, const float* X, int xb,
                                            float* __restrict__ slab, float* part) {
   constexpr int VC = HC / 16, VK = K / 16, STEPS = 5;              // 5 steps (20 rows) of loads in flight
@@ -486,13 +463,8 @@ __device__ __forceinline__ void seg_dw_blk(int n, int R, const float* G, int gb,
         const int r = nb + 4 * st + q;
         const bool ok = r < rend;
         const int rr = ok ? r : rbeg;
-        if constexpr (NT) {           // streaming reads when running beside the per-snapshot workgroups
-          load_frag_nt<VC>(G + (unsigned)((gb + rr) * HC + VC * i), av[st]);
-          load_frag_nt<VK>(X + (unsigned)((xb + rr) * K + VK * i), bv[st]);
-        } else {
-          load_frag<VC>(G + (unsigned)((gb + rr) * HC + VC * i), av[st]);
-          load_frag<VK>(X + (unsigned)((xb + rr) * K + VK * i), bv[st]);
-        }
+        load_frag<VC>(G + (unsigned)((gb + rr) * HC + VC * i), av[st]);
+        load_frag<VK>(X + (unsigned)((xb + rr) * K + VK * i), bv[st]);
         if (!ok) {
 #pragma unroll
           for (int a = 0; a < VC; ++a) av[st][a] = 0.f;
@@ -1045,7 +1017,7 @@ __device__ __forceinline__ void seg_agg_bwd_src(Rows rw, int e0, const u16* trp,
 
 // att_src / att_dst gradients of one GATConv for this segment -> the segment's slab (deferred launch).
 // thread = (column c, row group rg); 4 rows in flight; partials combined across row groups through LDS.
-template <int H, int C, int THREADS, bool NT = false>
+template <int H, int C, int THREADS>
 __device__ __forceinline__ void seg_att_grads(int n, const float* __restrict__ h, int hb,
                                               const float* __restrict__ g_a_src, const float* __restrict__ g_a_dst,
                                               int db, float* __restrict__ slab_as, float* __restrict__ slab_ad,
@@ -1062,7 +1034,7 @@ __device__ __forceinline__ void seg_att_grads(int n, const float* __restrict__ h
         const int r = r0 + k * R;
         const bool ok = r < n;
         const int rr = ok ? r : 0;
-        hv[k] = !ok ? 0.f : (NT ? __builtin_nontemporal_load(h + (size_t)(hb + rr) * HC + c) : h[(size_t)(hb + rr) * HC + c]);
+        hv[k] = ok ? h[(size_t)(hb + rr) * HC + c] : 0.f;
         gs[k] = ok ? g_a_src[(size_t)(db + rr) * H + hd] : 0.f;
         gd[k] = ok ? g_a_dst[(size_t)(db + rr) * H + hd] : 0.f;
       }
@@ -1215,9 +1187,9 @@ __device__ __forceinline__ void seg_lin0_bwd(Rows rw, int n0, const int* __restr
 // ------------------------------------------------------------------------------------------ deferred gradients
 // Deferred parameter gradients of the GATConvs.  Nothing on the backward's dependency chain reads dW / g_att, so
 // the per-snapshot workgroups only keep g_h and g_alpha_src / g_alpha_dst per block; one ITEM = (segment, block,
-// conv) turns them into slab entries (and folds the bias partials of a split segment).  Items run either on spare
-// CUs of the same launch (consumer workgroups, see gatres_fused_kernel) or in a second launch with one workgroup
-// per item (param_grads_kernel).  Writes are disjoint slab ranges: deterministic.
+// conv) turns them into slab entries (and folds the bias partials of a split segment).  Items run in a launch of their
+// own with one workgroup per item (param_grads_reg_kernel for nc 16 / 32, param_grads_kernel otherwise).  Writes are
+// disjoint slab ranges: deterministic.
 struct ParamGradArgs {
   const int* seg_ptr;
   const float* saved;
@@ -1227,13 +1199,12 @@ struct ParamGradArgs {
   int M;
   Layout L;
   SegLayout SL;
-  const float* wt = nullptr;                  // (consumer_item_dma: the transposed conv weights, gatres_fused_prepare_backward)
-  // param_grads_stream_kernel, training step: workgroup 0 copies the optimizer's step count and the split launches' fault word
+  const float* wt = nullptr;                  // (param_grads_item_reg: the transposed conv weights, gatres_fused_prepare_backward)
+  // param_grads_reg_kernel, training step: workgroup 0 copies the optimizer's step count and the split launches' fault word
   // into snap[0..1] -- stable words for the sampling tail of the update launch that follows (reduce_adam_kernel)
   const unsigned long long* step_counter = nullptr;
   const unsigned* status = nullptr;
   unsigned long long* snap = nullptr;
-  unsigned long long* dstamps = nullptr;      // diagnostic (consumer 0 under gatres_fused_set_stamps): steps inside an item
 };
 
 // A slab entry.  AG: the entry is read by ANOTHER workgroup of the same launch (the column's last arriver of
@@ -1255,7 +1226,7 @@ __device__ __forceinline__ void fold_parts(const ParamGradArgs& a, int seg, int6
 }
 
 // part: NW * 2*NC*NC floats of LDS when the block form applies (nc 16 / 32), red: 3 * THREADS floats
-template <int NC, int THREADS, bool NT>
+template <int NC, int THREADS>
 __device__ __forceinline__ void param_grads_item(const ParamGradArgs& a, int seg, int b, int conv, bool fold_lin,
                                                  float* part, float* red) {
   constexpr bool BLK = NC >= 16 && NC <= 32;
@@ -1276,20 +1247,17 @@ __device__ __forceinline__ void param_grads_item(const ParamGradArgs& a, int seg
     }
   }
   if (conv == 0) {
-    if constexpr (BLK) seg_dw_blk<2 * NC, NC, THREADS, NT>(n, NW, keep + L.k_gh1, n0, base + SL.xin, 0, sb + L.c1_W, part);
+    if constexpr (BLK) seg_dw_blk<2 * NC, NC, THREADS>(n, NW, keep + L.k_gh1, n0, base + SL.xin, 0, sb + L.c1_W, part);
     else               seg_dw<2 * NC, NC, THREADS>(n, keep + L.k_gh1, n0, base + SL.xin, 0, sb + L.c1_W, red);
-    seg_att_grads<2, NC, THREADS, NT>(n, base + SL.h1, 0, keep + L.k_gas1, keep + L.k_gad1, n0, sb + L.c1_as,
+    seg_att_grads<2, NC, THREADS>(n, base + SL.h1, 0, keep + L.k_gas1, keep + L.k_gad1, n0, sb + L.c1_as,
                                   sb + L.c1_ad, red);
   } else {
-    if constexpr (BLK) seg_dw_blk<NC, 2 * NC, THREADS, NT>(n, NW, keep + L.k_gh2, n0, base + SL.o1, 0, sb + L.c2_W, part);
+    if constexpr (BLK) seg_dw_blk<NC, 2 * NC, THREADS>(n, NW, keep + L.k_gh2, n0, base + SL.o1, 0, sb + L.c2_W, part);
     else               seg_dw<NC, 2 * NC, THREADS>(n, keep + L.k_gh2, n0, base + SL.o1, 0, sb + L.c2_W, red);
-    seg_att_grads<1, NC, THREADS, NT>(n, base + SL.h2, 0, keep + L.k_gas2, keep + L.k_gad2, n0, sb + L.c2_as,
+    seg_att_grads<1, NC, THREADS>(n, base + SL.h2, 0, keep + L.k_gas2, keep + L.k_gad2, n0, sb + L.c2_as,
                                   sb + L.c2_ad, red);
   }
 }
-
-template <int NC>
-__global__ __launch_bounds__(512) void param_grads_stream_kernel(const ParamGradArgs a);
 
 template <int NC, int THREADS>
 __global__ __launch_bounds__(THREADS) void param_grads_kernel(const ParamGradArgs a) {
@@ -1298,263 +1266,28 @@ __global__ __launch_bounds__(THREADS) void param_grads_kernel(const ParamGradArg
   __shared__ __attribute__((aligned(16))) float part[BLK ? NW * 2 * NC * NC : 4];
   __shared__ float red[3 * THREADS];
   const int conv = blockIdx.x & 1, b = (blockIdx.x >> 1) % a.L.nb, seg = (blockIdx.x >> 1) / a.L.nb;
-  param_grads_item<NC, THREADS, false>(a, seg, b, conv, b == 0 && conv == 0, part, red);
+  param_grads_item<NC, THREADS>(a, seg, b, conv, b == 0 && conv == 0, part, red);
 }
 
 
-// ---- consumer items, streamed form (nc 16 / 32, 1024 threads): the item's tables flow through four LDS chunk buffers of
-// 64 rows.  The LAST FOUR waves only issue LDS-DMA (global_load_lds: no registers, no waits in the issuing wave) two
-// chunks ahead of the TWELVE compute waves, which read operands from LDS only -- an item then costs its bytes over
-// what one CU streams from HBM beside 192 busy ones (~40 GB/s measured) instead of five dependent rounds of register
-// loads (13 - 15 us per item before; profiles/r02_consumer_items.txt).  One barrier per chunk.
-//   dW:  wave w takes 4-row steps w, w + 12 of a chunk and keeps the whole [HC, K] block in MFMA accumulators (the
-//        permuted operand map of seg_dw_blk: vector LDS reads of contiguous features); the twelve partial blocks meet
-//        in LDS after the last chunk and are summed in wave order -> slab.  Deterministic.
-//   attention-vector gradients WITHOUT reading h (a third of the item's bytes): with h = x W^T,
-//        g_att_src[c] = sum_r g_a_src[r, hd(c)] h[r, c] = sum_k W[c, k] T[hd(c), k],  T = [g_a_src | g_a_dst]^T x  ([2H, K]),
-//        and T is one more MFMA tile row on the x operands the dW already has in registers.  Same value up to fp32
-//        reassociation (sum over rows first, then over k); the parameter-gradient tests hold it to their usual tolerance.
-constexpr int CI_DMA_WAVES = 4, CI_NBUF = 4, CI_DEPTH = CI_NBUF - 1, CI_CR = 64;   // chunks in flight ahead of the compute waves: DEPTH - 1
+// Geometry of an item: conv1 (CONV 0) forms dW [2NC, NC] from g_h [n, 2NC] and x [n, NC] and has two heads, conv2 dW [NC, 2NC]
+// from g_h [n, NC] and x [n, 2NC] with one head.  The attention-vector gradients are formed WITHOUT reading h: with h = x W^T,
+//   g_att_src[c] = sum_r g_a_src[r, hd(c)] h[r, c] = sum_k W[c, k] T[hd(c), k],  T = [g_a_src | g_a_dst]^T x  ([2H, K]),
+// and T is one more operand row on the x fragments the dW already has in registers.  Same value up to fp32 reassociation (sum
+// over rows first, then over k); the parameter-gradient tests hold it to their usual tolerance.
 template <int NC, int CONV>
-struct CiGeom {
+struct ItemGeom {
   static constexpr int HC = CONV == 0 ? 2 * NC : NC, K = CONV == 0 ? NC : 2 * NC, H = CONV == 0 ? 2 : 1;
-  static constexpr int ROW = HC + K + 2 * H;                     // floats of one row over the four tables
-  static constexpr int CB = CI_CR * ROW;                         // floats of one chunk buffer
-  // LDS-DMA instructions one DMA wave issues per chunk (16-byte form: 256 floats per instruction; the two small tables
-  // share one 4-byte-form instruction per wave)
-  static constexpr int N_G = CI_CR * HC / 256 / CI_DMA_WAVES, N_X = CI_CR * K / 256 / CI_DMA_WAVES;
-  static constexpr int PER_WAVE = N_G + N_X + 1;
-  static_assert(CI_CR * HC % (256 * CI_DMA_WAVES) == 0 && CI_CR * K % (256 * CI_DMA_WAVES) == 0, "chunk / wave split");
-  static_assert(2 * CI_CR * H <= 64 * CI_DMA_WAVES && 2 * CI_CR * H % CI_DMA_WAVES == 0, "small tables: one 4-byte DMA instruction per wave");
 };
 
-// (NBUF chunk buffers: four in the consumers of the window kernel, which own a CU's whole LDS; three in the stand-alone
-//  launch, whose 512-thread workgroups then fit a CU in pairs -- one streams while the other folds its partial blocks)
-template <int NC, int THREADS, int CONV, int NBUF = CI_NBUF, bool AG = false>
-__device__ __forceinline__ void consumer_item_dma(const ParamGradArgs& a, int seg, int b, float* lds) {
-  using Gm = CiGeom<NC, CONV>;
-  constexpr int DEPTH = NBUF - 1;
-  constexpr int HC = Gm::HC, K = Gm::K, H = Gm::H, CB = Gm::CB, CR = CI_CR;
-  constexpr int NW = THREADS / 64, CW = NW - CI_DMA_WAVES;                         // compute waves
-  constexpr int VC = HC / 16, VK = K / 16;
-  const Layout& L = a.L;
-  const SegLayout& SL = a.SL;
-  const int n0 = uni(a.seg_ptr[seg]), n = uni(a.seg_ptr[seg + 1]) - n0;
-  const float* base = a.saved + (int64_t)seg * SL.total + (int64_t)b * SL.bstride;
-  const float* keep = a.keep + (int64_t)b * L.keep_stride;
-  const int64_t po = L.p_block0 + (int64_t)b * L.p_block_stride;
-  float* sb = a.slabs + (int64_t)seg * L.slab_stride + po;
-  const float* gG = keep + (CONV == 0 ? L.k_gh1 : L.k_gh2) + (int64_t)n0 * HC;      // [n][HC]
-  const float* gX = base + (CONV == 0 ? SL.xin : SL.o1);                              // [n][K]
-  const float* gS = keep + (CONV == 0 ? L.k_gas1 : L.k_gas2) + (int64_t)n0 * H;      // [n][H]
-  const float* gD = keep + (CONV == 0 ? L.k_gad1 : L.k_gad2) + (int64_t)n0 * H;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int chunks = (n + CR - 1) / CR;
-  // chunk buffer: [G CR x HC | X CR x K | g_a_src CR x H | g_a_dst CR x H]
-  auto bufp = [&](int c) { return lds + (c % NBUF) * CB; };
-  // [CW][4][K]: the waves' T blocks, after the loop (three buffers: behind the partial dW blocks, inside the dead buffers)
-  float* tred = NBUF < CI_NBUF ? lds + CW * HC * K : lds + NBUF * CB;
-  static_assert(NBUF >= CI_NBUF || CW * HC * K + CW * 4 * K + 4 * K <= NBUF * CB, "the item's epilogue lives in the chunk buffers");
-  float* tsum = tred + CW * 4 * K;                               // [4][K]
-#define ISTAMP(k) do { if (GATRES_DIAG && a.dstamps && threadIdx.x == 0) a.dstamps[k] = wall_clock64(); } while (0)
-  ISTAMP(0);
-  if (wave >= CW) {
-    // ------------------------------------------------------------------ DMA waves
-    const int dw = wave - CW;
-    auto issue = [&](int c) {
-      float* B = bufp(c);
-      const int r0 = c * CR;
-      // rows beyond the segment are read from its last row (never used: the compute waves zero them) so that every
-      // chunk costs the same number of instructions -- the waits below count them
-      auto rows16 = [&](const float* src, float* dst, int W, int cnt) {
-        for (int k = 0; k < cnt; ++k) {
-          const int f = (dw * cnt + k) * 256 + lane * 4;                 // float index inside the chunk's table
-          const int r = min(r0 + f / W, n - 1);
-          __builtin_amdgcn_global_load_lds(src + (size_t)r * W + f % W, dst + (dw * cnt + k) * 256, 16, 0, 0);
-        }
-      };
-      rows16(gG, B, HC, Gm::N_G);
-      rows16(gX, B + CR * HC, K, Gm::N_X);
-      {  // g_a_src | g_a_dst: 2 * CR * H floats, 4 bytes per lane, the same share (and ONE instruction) for every DMA wave
-        constexpr int SH = 2 * CR * H / CI_DMA_WAVES;
-        const int f = dw * SH + min(lane, SH - 1);
-        const int which = f / (CR * H), e = f % (CR * H);
-        const int r = min(r0 + e / H, n - 1);
-        const float* src = (which ? gD : gS) + (size_t)r * H + e % H;
-        if (lane < SH) __builtin_amdgcn_global_load_lds(src, B + CR * (HC + K) + dw * SH, 4, 0, 0);
-      }
-    };
-    for (int c = 0; c < min(chunks, DEPTH); ++c) issue(c);
-    for (int c = 0; c < chunks; ++c) {
-      // chunk c has landed when at most the instructions of the younger chunks in flight are outstanding
-      static_assert((DEPTH == 3 || DEPTH == 2) && 2 * Gm::PER_WAVE < 64, "the waits below");
-      switch (min(chunks - 1 - c, DEPTH - 1)) {                  // (wave-uniform)
-        case 0:  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Gm::PER_WAVE) : "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * Gm::PER_WAVE) : "memory"); break;
-      }
-      lds_barrier_raw();
-      if (c + DEPTH < chunks) issue(c + DEPTH);                  // into the buffer of chunk c - 1: every compute wave is past it
-    }
-    lds_barrier_raw();                                            // (the compute waves' "chunk buffers are dead" barrier)
-  } else {
-    // ------------------------------------------------------------------ compute waves
-    // bias partials of a split segment: loaded now, folded after the loop (their latency rides on the first chunks)
-    constexpr int MAXM = 8;
-    float bp[MAXM];
-    const bool folds = a.M > 1 && (int)threadIdx.x < HC;
-    const int64_t boff = po + (CONV == 0 ? L.c1_b : L.c2_b) + threadIdx.x;
-#pragma unroll
-    for (int p = 0; p < MAXM; ++p)
-      bp[p] = (folds && p < a.M) ? a.part_slabs[((int64_t)seg * a.M + p) * L.slab_stride + boff] : 0.f;
-    const int i = lane & 15, q = lane >> 4;
-    f32x4 acc[VC][VK], accT[VK];
-#pragma unroll
-    for (int y = 0; y < VK; ++y) {
-      accT[y] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int x = 0; x < VC; ++x) acc[x][y] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    ISTAMP(1);
-    for (int c = 0; c < chunks; ++c) {
-      lds_barrier_raw();
-      if (c == 0) ISTAMP(2);
-      if (c == 1) ISTAMP(3);
-      if (c == chunks - 1) ISTAMP(4);
-      const float* B = bufp(c);
-      const float* Sc = B + CR * (HC + K);                        // [CR][H] g_a_src, then [CR][H] g_a_dst
-      const int r0 = c * CR;
-      for (int st = wave; st < CR / 4; st += CW) {                // (wave-uniform)
-        const int r = 4 * st + q;
-        float av[VC], bv[VK];
-        load_frag<VC>(B + r * HC + VC * i, av);
-        load_frag<VK>(B + CR * HC + r * K + VK * i, bv);
-        // the extra tile row: column i < H is g_a_src[r, i], H <= i < 2H is g_a_dst[r, i - H]
-        float ae = i < 2 * H ? Sc[(i < H ? 0 : CR * H) + r * H + (i < H ? i : i - H)] : 0.f;
-        if (r0 + r >= n) {
-          ae = 0.f;
-#pragma unroll
-          for (int x = 0; x < VC; ++x) av[x] = 0.f;
-        }
-#pragma unroll
-        for (int y = 0; y < VK; ++y) {
-          accT[y] = __builtin_amdgcn_mfma_f32_16x16x4f32(ae, bv[y], accT[y], 0, 0, 0);
-#pragma unroll
-          for (int x = 0; x < VC; ++x) acc[x][y] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[x], bv[y], acc[x][y], 0, 0, 0);
-        }
-      }
-    }
-    ISTAMP(5);
-    lds_barrier_raw();                                            // every chunk buffer is dead: the partial blocks meet in them
-    float* mine = lds + wave * (HC * K);
-#pragma unroll
-    for (int x = 0; x < VC; ++x)
-#pragma unroll
-      for (int y = 0; y < VK; ++y)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) mine[(VC * (4 * q + rr) + x) * K + VK * i + y] = acc[x][y][rr];
-    if (q == 0) {                                                 // T rows 0 .. 3 live in the q = 0 lanes
-#pragma unroll
-      for (int y = 0; y < VK; ++y)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) tred[(wave * 4 + rr) * K + VK * i + y] = accT[y][rr];
-    }
-    if (folds) {
-      float sum = 0.f;
-#pragma unroll
-      for (int p = 0; p < MAXM; ++p)
-        if (p < a.M) sum += bp[p];
-      slab_st<AG>(a.slabs + (int64_t)seg * L.slab_stride + boff, sum);
-    }
-  }
-  lds_barrier_raw();
-  ISTAMP(6);
-  for (int idx = threadIdx.x; idx < HC * K; idx += THREADS) {
-    float sum = 0.f;
-#pragma unroll
-    for (int w = 0; w < CW; ++w) sum += lds[w * (HC * K) + idx];
-    slab_st<AG>(sb + (CONV == 0 ? L.c1_W : L.c2_W) + idx, sum);
-  }
-  if ((int)threadIdx.x < 4 * K) {
-    float sum = 0.f;
-#pragma unroll
-    for (int w = 0; w < CW; ++w) sum += tred[w * 4 * K + threadIdx.x];
-    tsum[threadIdx.x] = sum;
-  }
-  lds_barrier_raw();
-  {
-    // g_att[c] = sum_k W^T[k][c] T[hd(c)][k]: W^T [K][HC] is the scratch copy the dX stages use (L2-resident).  Thread
-    // (c, kg) takes k = kg, kg + KG, ... (coalesced over c), the KG partial sums meet in LDS and are added in order.
-    constexpr int KG = THREADS / HC, KPT = (K + KG - 1) / KG;
-    const int c = threadIdx.x % HC, kg = threadIdx.x / HC, hd = c / (HC / H);
-    const float* Wt = a.wt + ((int64_t)b * 2 + CONV) * (2LL * NC * NC) + c;
-    float wv[KPT];
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) wv[j] = (kg + j * KG < K) ? Wt[(kg + j * KG) * HC] : 0.f;
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) {
-      const int k = min(kg + j * KG, K - 1);
-      s0 = fmaf(wv[j], tsum[hd * K + k], s0);
-      s1 = fmaf(wv[j], tsum[(H + hd) * K + k], s1);
-    }
-    float* ared = lds;                                             // (the dW partial blocks are folded: reuse)  [2][KG][HC]
-    ared[kg * HC + c] = s0; ared[(KG + kg) * HC + c] = s1;
-    lds_barrier_raw();
-    if ((int)threadIdx.x < HC) {
-      float t0 = 0.f, t1 = 0.f;
-#pragma unroll 4
-      for (int g = 0; g < KG; ++g) { t0 += ared[g * HC + c]; t1 += ared[(KG + g) * HC + c]; }
-      slab_st<AG>(sb + (CONV == 0 ? L.c1_as : L.c2_as) + c, t0);
-      slab_st<AG>(sb + (CONV == 0 ? L.c1_ad : L.c2_ad) + c, t1);
-    }
-  }
-  ISTAMP(7);
-#undef ISTAMP
-}
-
-// the second-launch form of the streamed items (8 parts per snapshot leave no CU for consumers): one item per workgroup,
-// 512 threads (4 DMA + 4 compute waves) and three chunk buffers (77 KB): TWO workgroups per CU, so that a CU keeps
-// streaming while one of its items is in its epilogue (one 1024-thread workgroup per CU streamed 64 % of the time)
-constexpr int PGS_THREADS = 512, PGS_NBUF = 3;
-template <int NC>
-__global__ __launch_bounds__(PGS_THREADS) void param_grads_stream_kernel(const ParamGradArgs a) {
-  __shared__ __attribute__((aligned(16))) float lds[PGS_NBUF * CI_CR * (3 * NC + 4)];
-  // Item of this workgroup.  The kept g_h tables an item reads were written by the window kernel's parts of its segment -- on
-  // XCD (segment % 8), their ids being 8 apart -- and the LAST blocks the backward chain walked (b = 0, 1, ...) were written
-  // last: with a whole number of segments per XCD the item goes to a workgroup of THAT XCD (round-robin dispatch: id % 8) and
-  // the items are dealt block-major from b = 0, so the first wave of items finds its freshest tables still in its XCD's L2
-  // (4 MB hold the kept tables of four to five blocks of an XCD's four snapshots).  Speed only: any map is a bijection.
-  int conv = blockIdx.x & 1, b = (blockIdx.x >> 1) % a.L.nb, seg = (blockIdx.x >> 1) / a.L.nb;
-#ifndef GATRES_PROBE_PG_OLD_MAP
-  {
-    const int S = (int)(gridDim.x / (2 * a.L.nb));
-    if ((S & 7) == 0) {
-      const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3, per = (S >> 3) * 2;       // (segment, conv) pairs of one XCD
-      b = j / per; conv = (j % per) & 1; seg = ((j % per) >> 1) * 8 + xcd;
-    }
-  }
-#endif
-  if (a.snap && blockIdx.x == 0 && threadIdx.x == 0) {
-    a.snap[0] = a.step_counter ? __hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ULL;
-    a.snap[1] = a.status ? (unsigned long long)__hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ULL;
-  }
-  if (conv == 0) consumer_item_dma<NC, PGS_THREADS, 0, PGS_NBUF>(a, seg, b, lds);
-  else           consumer_item_dma<NC, PGS_THREADS, 1, PGS_NBUF>(a, seg, b, lds);
-  if (a.M > 1 && b == 0 && conv == 0) {
-    fold_parts<PGS_THREADS>(a, seg, a.L.p_lin0_w, 2 * NC);
-    fold_parts<PGS_THREADS>(a, seg, a.L.p_lin1_w, NC + 1);
-  }
-}
-
-// ---- items streamed through REGISTERS (round 5; the stand-alone launch for nc 16 / 32).  The LDS-DMA form above keeps two
-// 64-row chunks in flight per workgroup and paces its waves by one barrier per chunk; its launch moves 161 MB at 4.2 TB/s with the
+// ---- items streamed through REGISTERS (round 5; the stand-alone launch for nc 16 / 32).  The LDS-DMA form it replaced kept two
+// 64-row chunks in flight per workgroup and paced its waves by one barrier per chunk; its launch moved 161 MB at 4.2 TB/s with the
 // matrix pipe 42 % busy -- neither bound.  Here an item is one 256-thread workgroup whose four waves take the item's 4-row steps
 // round-robin (wave w: steps w, w + 4, ...), every lane loads its MFMA operands straight from the tables (the permuted operand map
 // of seg_dw_blk: 16 / 8 bytes of contiguous features per lane, a wave-load covers four whole rows) into a ring of P register
 // slots -- P steps in flight per wave, no barrier, no LDS until the four partial blocks meet -- and ALL 960 items of a bs-32 step
 // are resident at once (35 KB of LDS and 16 waves for the four workgroups of a CU).  T = [g_a_src | g_a_dst]^T x (the attention-
-// vector gradients without reading h, see above) is formed on the VALU beside the matrix pipe: 2H x VK fused multiply-adds per lane
+// vector gradients without reading h, see ItemGeom) is formed on the VALU beside the matrix pipe: 2H x VK fused multiply-adds per lane
 // and step, the four row phases of a wave summed by two shuffles at the end.  Every sum has a fixed order: deterministic.
 constexpr int PGR_THREADS = 256;
 #define PGR_LDS_FLOATS(NC) ((PGR_THREADS / 64) * 2 * (NC) * (NC) + (PGR_THREADS / 64 + 1) * 4 * (NC))
@@ -1596,7 +1329,7 @@ __device__ __forceinline__ void pgr_wait(A& a, B& b, C& c, D& d) {
 // (AG: slab entries by agent-scope stores, for param_grads_finish_kernel's last arriver)
 template <int NC, int CONV, bool AG = false>
 __device__ __forceinline__ void param_grads_item_reg(const ParamGradArgs& a, int seg, int b, float* lds) {
-  using Gm = CiGeom<NC, CONV>;
+  using Gm = ItemGeom<NC, CONV>;
   constexpr int HC = Gm::HC, K = Gm::K, H = Gm::H, P = PGR_SLOTS;
   constexpr int NW = PGR_THREADS / 64, VC = HC / 16, VK = K / 16;
   static_assert(4 * (P - 1) < 64, "vmcnt");
@@ -1775,7 +1508,11 @@ __device__ __forceinline__ void param_grads_item_reg(const ParamGradArgs& a, int
 template <int NC>
 __global__ __launch_bounds__(PGR_THREADS) void param_grads_reg_kernel(const ParamGradArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[PGR_LDS_FLOATS(NC)];
-  // item of this workgroup: on the XCD whose window-kernel parts wrote its kept tables (param_grads_stream_kernel's map)
+  // Item of this workgroup.  The kept g_h tables an item reads were written by the window kernel's parts of its segment -- on
+  // XCD (segment % 8), their ids being 8 apart -- and the LAST blocks the backward chain walked (b = 0, 1, ...) were written
+  // last: with a whole number of segments per XCD the item goes to a workgroup of THAT XCD (round-robin dispatch: id % 8) and
+  // the items are dealt block-major from b = 0, so the first wave of items finds its freshest tables still in its XCD's L2
+  // (4 MB hold the kept tables of four to five blocks of an XCD's four snapshots).  Speed only: any map is a bijection.
   int conv = blockIdx.x & 1, b = (blockIdx.x >> 1) % a.L.nb, seg = (blockIdx.x >> 1) / a.L.nb;
   {
     const int S = (int)(gridDim.x / (2 * a.L.nb));
@@ -2032,7 +1769,7 @@ __device__ __forceinline__ void xch_import(Xch& x, const u16* list, int cnt, u64
 // each, profiles/r02_exchange_steps.txt) -- a late part only delays the neighbours whose halo rows it owes.
 // Then EVERY wave drains its own outstanding global stores -- the sweeping waves did so while waiting for their loads,
 // the others wait here, beside them -- so that after the barrier that follows the exchange all stores issued before it
-// (saved activations, kept gradient tables) are complete: publish_items relies on that.
+// (saved activations, kept gradient tables) are complete.
 template <int THREADS>
 __device__ __forceinline__ void xch_heartbeat(Xch& x, int /*point*/) {
   u64* hb = x.base_hb;
@@ -2074,119 +1811,6 @@ __device__ __forceinline__ int build_export_rows(const int* __restrict__ ptr, co
   return total;
 }
 
-// Deferred-gradient items of a segment, in production order: item 2*(nb-1-b) is (block b, conv2), the next one
-// (block b, conv1); a split segment adds one last item that folds the lin0 / lin1 partials.  Part 0 publishes the
-// number of finished items after a barrier that all parts have passed; consumer c takes items c, c + C, ...
-// The published word also says where the data is: bits 16..19 the XCD of part 0, bit 24 "every part runs on that
-// XCD".  A consumer on the same XCD reads the tables through the shared L2 as soon as they are published; the LAST
-// publication is preceded by an agent-scope release, so a consumer that finds itself anywhere else waits for it,
-// acquires at agent scope and only then works through its items (correct wherever the workgroups were placed).
-constexpr unsigned PUB_COUNT_MASK = 0xffffu, PUB_LOCAL = 1u << 24;
-// EVERY part publishes its own progress (word `part` of each consumer's line): the tables of an item are complete when all
-// M parts have published its number.  Called right after a point where every wave of the workgroup has drained its
-// global stores (group_sync, or the granule import of the window kernel) and a workgroup barrier has been passed.
-template <int THREADS>
-__device__ __forceinline__ void publish_items(const FusedArgs& a, int seg, int part, int count, bool parts_local,
-                                              bool last) {
-  if (a.C > 0 && (int)threadIdx.x < 64) {
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if ((int)threadIdx.x < a.C)
-      __hip_atomic_store(a.ready + ((size_t)seg * 4 + threadIdx.x) * FLAG_STRIDE + part,
-                         (unsigned)count | (xcc_id() << 16) | (parts_local ? PUB_LOCAL : 0u), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-template <int NC, int THREADS>
-__device__ __forceinline__ void consumer_main(const FusedArgs& a, int cid, float* ldsf) {
-  const int C = a.C;
-  const int within = cid % (8 * C);
-  const int seg = a.seg0 + (cid / (8 * C)) * 8 + (within & 7), c = within >> 3;
-  if (seg >= a.seg0 + a.seg_cnt) return;
-  ParamGradArgs pg;
-  pg.seg_ptr = a.seg_ptr; pg.saved = a.saved; pg.keep = a.scratch + a.L.sc_keep; pg.slabs = a.slabs;
-  pg.part_slabs = a.part_slabs; pg.M = a.M; pg.L = a.L; pg.SL = a.SL;
-  pg.wt = a.wt;
-  pg.dstamps = (STAMPS_PTR && cid == 0 && a.stamp_cap >= 4096) ? STAMPS_PTR + 3072 : nullptr;
-  unsigned* my = a.ready + ((size_t)seg * 4 + c) * FLAG_STRIDE;       // words 0 .. M-1: one per producing part
-  float* part = ldsf;
-  float* red = ldsf + (LDS_BYTES / 4 - 3 * THREADS);
-  int* mode = reinterpret_cast<int*>(red + 3 * THREADS - 1);   // LDS word: 0 = hand-off through the shared L2, 1 = remote
-  const int nb = a.L.nb, items = 2 * nb + (a.M > 1 ? 1 : 0);
-  bool dead = false, remote = false;
-  const int lane = threadIdx.x;
-  const unsigned mine_xcc = xcc_id();
-  int cst = 1024;            // diagnostic stamps of consumer 0 (gatres_fused_set_stamps): [item available, item done] pairs
-#define CSTAMP()                                                                                    \
-  do {                                                                                              \
-    if (STAMPS_PTR && cid == 0 && threadIdx.x == 0 && cst < a.stamp_cap) STAMPS_PTR[cst++] = wall_clock64(); \
-  } while (0)
-  for (int i = c; i < items; i += C) {
-    if (threadIdx.x < 64) {
-      // lanes 0 .. M-1 poll one part each; the wave leaves the loop together
-      bool need_remote = false;
-      if (!remote) {
-        int spin = 0;
-        for (;;) {
-          unsigned w = PUB_COUNT_MASK;
-          if (lane < a.M && !dead) w = __hip_atomic_load(my + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const bool ok = lane >= a.M || dead || (int)(w & PUB_COUNT_MASK) >= i + 1;
-          if (ok && lane < a.M && !dead && (!(w & PUB_LOCAL) || ((w >> 16) & 0xfu) != mine_xcc || a.safe_sync))
-            need_remote = true;
-          if (__all(ok)) break;
-          if (++spin > SPIN_LIMIT) { if (lane == 0) *a.err = 1; dead = true; }
-        }
-        if (__any(need_remote)) {
-          // not behind every producer's L2: wait for the released, final publications
-          remote = true;
-          int spin2 = 0;
-          for (;;) {
-            unsigned w = PUB_COUNT_MASK;
-            if (lane < a.M && !dead) w = __hip_atomic_load(my + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all(lane >= a.M || dead || (int)(w & PUB_COUNT_MASK) >= items)) break;
-            if (++spin2 > SPIN_LIMIT) { if (lane == 0) *a.err = 1; dead = true; }
-          }
-        }
-        if (lane == 0) *mode = remote ? 1 : 0;
-      }
-      if (threadIdx.x == 0 && remote) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      else                            asm volatile("buffer_inv sc1" ::: "memory");
-      INV_WAIT();
-    }
-    __syncthreads();
-    CSTAMP();
-    if (i < 2 * nb) {
-      if constexpr (THREADS == 1024 && (NC == 16 || NC == 32)) {
-        if (pg.dstamps) pg.dstamps += 8;
-        if (i & 1) consumer_item_dma<NC, THREADS, 0>(pg, seg, nb - 1 - i / 2, ldsf);
-        else       consumer_item_dma<NC, THREADS, 1>(pg, seg, nb - 1 - i / 2, ldsf);
-      } else {
-        if (*mode) param_grads_item<NC, THREADS, false>(pg, seg, nb - 1 - i / 2, (i & 1) ? 0 : 1, false, part, red);
-        else       param_grads_item<NC, THREADS, true>(pg, seg, nb - 1 - i / 2, (i & 1) ? 0 : 1, false, part, red);
-      }
-    } else {
-      fold_parts<THREADS>(pg, seg, a.L.p_lin0_w, 2 * NC);
-      fold_parts<THREADS>(pg, seg, a.L.p_lin1_w, NC + 1);
-    }
-    __syncthreads();
-    CSTAMP();
-  }
-#undef CSTAMP
-  if (threadIdx.x < 64) {
-    // reset the line for the next launch -- only after every producer's LAST publication, or that one would survive
-    int spin = 0;
-    for (;;) {
-      unsigned w = PUB_COUNT_MASK;
-      if (lane < a.M && !dead) w = __hip_atomic_load(my + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__all(lane >= a.M || dead || (int)(w & PUB_COUNT_MASK) >= items)) break;
-      if (++spin > SPIN_LIMIT) { if (lane == 0) *a.err = 1; dead = true; }
-    }
-    if (lane < a.M) __hip_atomic_store(my + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
 // ------------------------------------------------------------------------------------------ window kernel
 // The same per-snapshot pipeline for split segments whose parts have compact ROW WINDOWS (gatres_graph_t.window: own
 // rows + the rows adjacent to them form a contiguous range that is a fraction of the segment when the node order is

@@ -170,14 +170,14 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(const float* __restric
 // Parameter gradients of a RANGE of blocks, summed over the segments, in ONE launch: what the data-parallel step of the
 // fused path forms its gradient buckets with (gatres_train_step: GATRES_FLAG_GRADS_ONLY) -- the upper blocks' bucket goes on
 // the wire while the lower blocks' launch runs.
-// A COLUMN is one (block, conv): the S = num_segments items of a column (one workgroup each, param_grads_stream_kernel's
+// A COLUMN is one (block, conv): the S = num_segments items of a column (one workgroup each, param_grads_reg_kernel's
 // items) write the column's range of S slab rows with agent-scope stores (sc1: written through), acknowledged (every wave's
 // s_waitcnt vmcnt(0)) before the item counts itself at the column's counter; the item that ARRIVES LAST reads the rows
 // back with agent-scope loads (never served from its L1 or a stale L2 line: the granule protocol's pair of accesses,
 // k_fused_dev.h), sums them in slab order -- reduce_adam_kernel's association: the same bits, whoever arrives last --,
 // writes grads and, if asked (do_adam: the whole model only), applies Adam to those parameters.  lin0's range rides on
 // column (block 0, conv1), lin1's on (last block, conv2).
-// As a replacement of the single-GPU step's two launches (param_grads_stream_kernel 37.6 us + reduce_adam_kernel 8.7 us
+// As a replacement of the single-GPU step's two launches (round 4's item launch 37.6 us + reduce_adam_kernel 8.7 us
 // inside the captured step) it was measured and is NOT used: 53 us with everything in it (47.7 without Adam) -- the column
 // sums are a serial tail of dependent memory round trips on the workgroups that finish last; a release fence per arriver
 // instead of agent-scope stores 73 us (960 L2 write-back walks); dedicated reducer workgroups behind the items 60 us
@@ -446,16 +446,13 @@ static bool window_kernel_fits(const Layout& L, const gatres_graph_t* g, int M, 
 }
 
 // CUs per segment.  B = the co-residency bound of the layout (at most 8, whole grid resident, no more parts than 16-row
-// tiles).  Preferred: B parts on the window kernel; the kept gradient tables then become parameter gradients on whatever
-// CUs are left for consumer workgroups (batches below 32 snapshots) or in the stand-alone launch that follows
-// (param_grads_stream_kernel).  Measured on gatres_small, C-Town, bs = 32 (B = 8; profiles/r02_split_sweep.txt), GPU time
-// of the two launches: 8 parts 462 + 38 us; 6 parts + 2 consumers 526 us (the part that owns a segment's last 68 rows
-// needs two trips through every conv1-width sparse stage and a fifth MFMA tile -- 384-node snapshots run 22 us faster --
-// and the consumers finish 15 - 20 us after the parts); 7 + 1 607 us (ONE consumer streams an item at ~23 GB/s, the
-// LDS-DMA rate of one CU beside 224 busy ones, and cannot keep up with two items per block).  GATRES_FUSED_PREFER_CONSUMERS=1
-// restores round 2's earlier choice (B - 2 parts + two consumers).  Otherwise the whole-segment-table kernel at
-// min(B, 4).  The choice depends on the plan only, never on the phases of a launch: the per-part hand-off epochs persist
-// in scratch.  GATRES_FUSED_SPLIT=1..8 overrides.
+// tiles).  Preferred: B parts on the window kernel; the kept gradient tables then become parameter gradients in the
+// stand-alone launch that follows (gatres_fused_param_grads).  Measured on gatres_small, C-Town, bs = 32 (B = 8;
+// profiles/r02_split_sweep.txt), GPU time of the two launches: 8 parts 462 + 38 us; 6 parts with the parameter gradients
+// on the two CUs per snapshot left over 526 us (the part that owns a segment's last 68 rows needs two trips through every
+// conv1-width sparse stage and a fifth MFMA tile -- 384-node snapshots run 22 us faster).  Otherwise the
+// whole-segment-table kernel at min(B, 4).  The choice depends on the plan only, never on the phases of a launch: the
+// per-part hand-off epochs persist in scratch.  GATRES_FUSED_SPLIT=1..8 overrides.
 static int fused_split(const Layout& L, const gatres_graph_t* g) {
   const int tiles = (g->max_segment_nodes + 15) / 16;
   const int padded = ((g->num_segments + 7) / 8) * 8;
@@ -468,7 +465,7 @@ static int fused_split(const Layout& L, const gatres_graph_t* g) {
   if (const int rp = rounds_parts_for(g->num_segments)) {
     const int per = ((padded / 2 + 7) / 8) * 8;
     if (L.split_max == rp && tiles >= rp && L.nb > 0 && per * rp <= device_cus() && !gatres_knobs()->fused_split &&
-        !gatres_knobs()->fused_no_rounds && !gatres_knobs()->fused_prefer_consumers && window_kernel_fits(L, g, rp))
+        !gatres_knobs()->fused_no_rounds && window_kernel_fits(L, g, rp))
       return rp;
   }
   int B = L.split_max;
@@ -476,24 +473,10 @@ static int fused_split(const Layout& L, const gatres_graph_t* g) {
   if (const int v = gatres_knobs()->fused_split) {
     if (v >= 1 && v <= B) return v;
   }
-  if (B >= 2 && window_kernel_fits(L, g, B) && !gatres_knobs()->fused_prefer_consumers) return B;
-  if (B >= 4 && window_kernel_fits(L, g, B - 2) && !gatres_knobs()->fused_no_consumers) return B - 2;
   if (B >= 2 && window_kernel_fits(L, g, B)) return B;
   int m = 1;
   while (m * 2 <= B && m < 4) m *= 2;
   return m;
-}
-
-// Consumer workgroups per segment for the deferred parameter gradients: only in launches that run the backward
-// phase, only with the 1024-thread kernel (the consumers reuse its LDS), and only if the whole grid -- per-snapshot
-// workgroups plus consumers, one per CU -- is still resident at once.
-static int fused_consumers(const Layout& L, const gatres_graph_t* g, int M) {
-  if (gatres_knobs()->fused_no_consumers || L.nb == 0 || threads_for(L.nc) != 1024) return 0;
-  const int padded = ((g->num_segments + 7) / 8) * 8;
-  int c = (device_cus() - padded * M) / padded;
-  const int cap = gatres_knobs()->fused_consumers_cap;   // default 2; measured: 1, 2 and 4 consumers per snapshot give the same step time
-  if (c > cap) c = cap;
-  return c > 0 ? c : 0;
 }
 
 static bool use_window_kernel(const FusedArgs& a, const gatres_graph_t* g) {
@@ -506,7 +489,7 @@ static int launch_fused(int nc, int threads, const FusedArgs& a0, const gatres_g
                      cache_fits(nc, threads, g->max_segment_nodes, g->max_segment_edges_gat, g->max_segment_edges_mean);
   // every workgroup of a split launch must be resident at once: more segments than that go round by round
   int per_round = g->num_segments;
-  if (a0.M > 1 && ((g->num_segments + 7) / 8) * 8 * (a0.M + a0.C) > device_cus()) {
+  if (a0.M > 1 && ((g->num_segments + 7) / 8) * 8 * a0.M > device_cus()) {
     const int padded = ((g->num_segments + 7) / 8) * 8, fit = (device_cus() / a0.M) & ~7;
     const int rounds = fit > 0 ? (padded + fit - 1) / fit : 0;
     per_round = rounds > 0 ? (((padded + rounds - 1) / rounds + 7) / 8) * 8 : 0;        // (equal rounds: 72 segments = 40 + 32)
@@ -516,7 +499,7 @@ static int launch_fused(int nc, int threads, const FusedArgs& a0, const gatres_g
   for (int s0 = 0; s0 < g->num_segments; s0 += per_round) {
     a.seg0 = s0;
     a.seg_cnt = g->num_segments - s0 < per_round ? g->num_segments - s0 : per_round;
-    const unsigned grid = (unsigned)(((a.seg_cnt + 7) / 8) * 8 * (a.M + a.C));
+    const unsigned grid = (unsigned)(((a.seg_cnt + 7) / 8) * 8 * a.M);
     const int rc = window ? gatres_fused_launch_window(&a, nc, grid, st)
                           : gatres_fused_launch_whole(&a, nc, threads, cache ? 1 : 0, grid, st);
     if (rc != 0) return rc;
@@ -546,7 +529,7 @@ extern "C" int gatres_fused_cus_per_segment(const gatres_model_t* m, const gatre
   return fused_split(L, g);
 }
 
-// Zero the split-segment barrier state (epochs, XCD words, consumer counters, error word) of a scratch buffer: what a
+// Zero the split-segment barrier state (epochs, XCD words, column counters, error word) of a scratch buffer: what a
 // freshly zeroed buffer has.  Only needed after a launch was aborted or the buffer was handed over from elsewhere.
 extern "C" int gatres_fused_reset_sync(const gatres_model_t* m, const gatres_graph_t* g, float* scratch, void* stream) {
   if (!m || !g || !scratch) return GATRES_E_BADARG;
@@ -557,7 +540,7 @@ extern "C" int gatres_fused_reset_sync(const gatres_model_t* m, const gatres_gra
     const hipError_t e = hipMemsetAsync(scratch + L.sc_xch, 0, (size_t)g->num_segments * L.xch_stride * 4, gatres_stream(stream));
     if (e != hipSuccess) return (int)e;
   }
-  return (int)hipMemsetAsync(scratch + L.sc_flags, 0, (size_t)(L.flag_words + L.ready_words + L.col_words) * 4, gatres_stream(stream));
+  return (int)hipMemsetAsync(scratch + L.sc_flags, 0, (size_t)(L.flag_words + L.col_words) * 4, gatres_stream(stream));
 }
 
 extern "C" int gatres_fused_window_kernel(const gatres_model_t* m, const gatres_graph_t* g) {
@@ -613,7 +596,6 @@ extern "C" int gatres_fused_run(const gatres_model_t* m, const gatres_graph_t* g
   a.safe_sync = gatres_knobs()->fused_safe_sync;
   // bits 1 / 2 (diagnostic build only, WRONG results): never-wait exchanges; dX epilogues without their global reads
   a.no_halo = gatres_knobs()->fused_no_halo | (gatres_knobs()->xch_nowait ? 2 : 0) | (gatres_knobs()->diag_nomask ? 4 : 0);
-  a.C = (phases & GATRES_PHASE_BACKWARD) ? fused_consumers(a.L, g, a.M) : 0;
   a.sym = (g->flags & GATRES_GRAPH_SYMMETRIC) && !gatres_knobs()->fused_heartbeat ? 1 : 0;
   a.ptab = g->part_tables; a.ptab_m = g->part_tables_m; a.ptab_stride = g->part_tables_stride;
   {
@@ -626,7 +608,6 @@ extern "C" int gatres_fused_run(const gatres_model_t* m, const gatres_graph_t* g
            window_kernel_fits(a.L, g, a.M, true) ? 1 : 0;
   a.flags = reinterpret_cast<unsigned*>(scratch + a.L.sc_flags);
   a.err = reinterpret_cast<int*>(a.flags + a.L.flag_words - 32);
-  a.ready = a.flags + a.L.flag_words;
   a.part_slabs = scratch + a.L.sc_part_slabs;
   a.SL = make_seg_layout(a.L.nb, a.L.nc, g->max_segment_nodes, g->max_segment_edges_gat);
   a.xch = reinterpret_cast<unsigned long long*>(scratch + a.L.sc_xch);
@@ -696,35 +677,27 @@ extern "C" __attribute__((visibility("hidden"))) int gatres_fused_param_grads_ex
   ParamGradArgs a;
   if (!make_layout_g(m, g, &a.L)) return GATRES_E_UNSUPPORTED;
   if (a.L.nb == 0) return 0;
-  if (fused_consumers(a.L, g, fused_split(a.L, g)) > 0) return 0;     // done by the backward launch's consumers
   a.seg_ptr = g->seg_ptr; a.saved = saved; a.keep = scratch + a.L.sc_keep; a.slabs = scratch + a.L.sc_slabs;
   a.M = fused_split(a.L, g); a.part_slabs = scratch + a.L.sc_part_slabs;
   a.SL = make_seg_layout(a.L.nb, a.L.nc, g->max_segment_nodes, g->max_segment_edges_gat);
   a.wt = scratch + a.L.sc_wt;
   const dim3 grid((unsigned)(2 * a.L.nb * g->num_segments));
   hipStream_t st = gatres_stream(stream);
-  if ((m->nc == 16 || m->nc == 32) && !gatres_knobs()->param_grads_no_stream) {
+  if (m->nc == 16 || m->nc == 32) {
     if (step_counter) {
       unsigned* status = reinterpret_cast<unsigned*>(scratch + a.L.sc_flags + a.L.flag_words - 32);
       a.step_counter = reinterpret_cast<const unsigned long long*>(step_counter);
       a.status = fused_nodes_of(g) > 0 ? status : nullptr;
       a.snap = reinterpret_cast<unsigned long long*>(status + 8);
     }
-#ifdef GATRES_PROBE_PG_DMA
-    if (m->nc == 16) hipLaunchKernelGGL((param_grads_stream_kernel<16>), grid, dim3(PGS_THREADS), 0, st, a);
-    else             hipLaunchKernelGGL((param_grads_stream_kernel<32>), grid, dim3(PGS_THREADS), 0, st, a);
-#else
     if (m->nc == 16) hipLaunchKernelGGL((param_grads_reg_kernel<16>), grid, dim3(PGR_THREADS), 0, st, a);
     else             hipLaunchKernelGGL((param_grads_reg_kernel<32>), grid, dim3(PGR_THREADS), 0, st, a);
-#endif
     const int rc = gatres_launch_status();
     return rc ? rc : (step_counter ? 1 : 0);
   }
   switch (m->nc) {
     case 4: hipLaunchKernelGGL((param_grads_kernel<4, 256>), grid, dim3(256), 0, st, a); break;
     case 8: hipLaunchKernelGGL((param_grads_kernel<8, 256>), grid, dim3(256), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((param_grads_kernel<16, 512>), grid, dim3(512), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((param_grads_kernel<32, 512>), grid, dim3(512), 0, st, a); break;
     case 64: hipLaunchKernelGGL((param_grads_kernel<64, 512>), grid, dim3(512), 0, st, a); break;
     case 128: hipLaunchKernelGGL((param_grads_kernel<128, 512>), grid, dim3(512), 0, st, a); break;
     default: return GATRES_E_UNSUPPORTED;
@@ -733,15 +706,14 @@ extern "C" __attribute__((visibility("hidden"))) int gatres_fused_param_grads_ex
 }
 
 // 1 when gatres_fused_param_grads_finish applies: streamed items (nc 16 / 32) in a launch of their own
-static bool finish_folds(const gatres_model_t* m, const gatres_graph_t* g, const Layout& L) {
-  if (!(m->nc == 16 || m->nc == 32) || gatres_knobs()->param_grads_no_stream || L.nb == 0) return false;
-  return fused_consumers(L, g, fused_split(L, g)) == 0;
+static bool finish_folds(const gatres_model_t* m, const Layout& L) {
+  return (m->nc == 16 || m->nc == 32) && L.nb > 0;
 }
 
 extern "C" int gatres_fused_finish_folds(const gatres_model_t* m, const gatres_graph_t* g) {
   Layout L;
   if (!gatres_fused_supported(m, g) || !make_layout_g(m, g, &L)) return 0;
-  return finish_folds(m, g, L) ? 1 : 0;
+  return finish_folds(m, L) ? 1 : 0;
 }
 
 extern "C" int gatres_fused_param_grads_finish(const gatres_model_t* m, const gatres_graph_t* g, const float* saved,
@@ -756,7 +728,7 @@ extern "C" int gatres_fused_param_grads_finish(const gatres_model_t* m, const ga
   if (!gatres_fused_supported(m, g)) return GATRES_E_UNSUPPORTED;
   ParamGradArgs a;
   if (!make_layout_g(m, g, &a.L)) return GATRES_E_UNSUPPORTED;
-  if (!finish_folds(m, g, a.L)) return GATRES_E_UNSUPPORTED;
+  if (!finish_folds(m, a.L)) return GATRES_E_UNSUPPORTED;
   if (block_lo < 0 || block_hi > a.L.nb || block_lo >= block_hi) return GATRES_E_BADARG;
   if (do_adam && (block_lo != 0 || block_hi != a.L.nb)) return GATRES_E_BADARG;      // (the step is counted per launch)
   a.seg_ptr = g->seg_ptr; a.saved = saved; a.keep = scratch + a.L.sc_keep; a.slabs = scratch + a.L.sc_slabs;
@@ -769,7 +741,7 @@ extern "C" int gatres_fused_param_grads_finish(const gatres_model_t* m, const ga
   f.lr = lr; f.b1 = beta1; f.b2 = beta2; f.eps = eps; f.wd = weight_decay; f.hp = hparams; f.grad_scale = grad_scale;
   f.wt = do_adam ? scratch + a.L.sc_wt : nullptr;
   f.status = fused_nodes_of(g) > 0 ? reinterpret_cast<unsigned*>(scratch + a.L.sc_flags + a.L.flag_words - 32) : nullptr;
-  f.colcnt = reinterpret_cast<unsigned*>(scratch + a.L.sc_flags + a.L.flag_words + a.L.ready_words);
+  f.colcnt = reinterpret_cast<unsigned*>(scratch + a.L.sc_flags + a.L.flag_words);
   f.S = g->num_segments; f.b_lo = block_lo; f.b_hi = block_hi; f.final_launch = block_lo == 0 ? 1 : 0;
   const dim3 grid((unsigned)(2 * (block_hi - block_lo) * g->num_segments));
   hipStream_t st = gatres_stream(stream);

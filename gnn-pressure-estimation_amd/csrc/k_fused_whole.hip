@@ -12,13 +12,6 @@ __global__ __launch_bounds__(THREADS) void gatres_fused_kernel(const FusedArgs a
   const Layout& L = a.L;
   // workgroup id -> (segment, part): ids of one segment are 8 apart (same XCD)
   const int M = a.M;
-  {
-    const int F = ((a.seg_cnt + 7) / 8) * 8 * M;       // per-snapshot workgroups come first, consumers after
-    if ((int)blockIdx.x >= F) {
-      if constexpr (THREADS == 1024) consumer_main<NC, THREADS>(a, (int)blockIdx.x - F, ldsf);
-      return;
-    }
-  }
   const int within = blockIdx.x % (8 * M);
   const int seg = a.seg0 + (blockIdx.x / (8 * M)) * 8 + (within & 7), part = within >> 3;
   if (seg >= a.seg0 + a.seg_cnt) return;
@@ -318,7 +311,6 @@ __global__ __launch_bounds__(THREADS) void gatres_fused_kernel(const FusedArgs a
       const float* wt1 = a.wt + (int64_t)b * 2 * w;
       const float* wt2 = wt1 + w;
       group_sync<THREADS>(grp);                  // K3 backward gathers g_pre of neighbours
-      publish_items<THREADS>(a, seg, part, 2 * (L.nb - 1 - b), grp.local || !split, false);   // the blocks above are kept
       const int elo = rp[rw.lo], ehi = rp[rw.hi];       // own in-edge range (edges are dst-sorted)
       if (pub) {
         if (halo) pull_list_rows<NC, THREADS>(gpT, gp_cur + (size_t)n0 * NC, hrow, hcnt);
@@ -369,7 +361,6 @@ __global__ __launch_bounds__(THREADS) void gatres_fused_kernel(const FusedArgs a
       seg_softmax_bwd<2, THREADS>(rw, 0, 0, rp, col, base + SL.al1, base + SL.as1, base + SL.ad1, ge1T, ge_b, gad1T,
                                   gd_b, pub ? sc + L.sc_ge : nullptr, e0, nullptr, 0);
       group_sync<THREADS>(grp);
-      publish_items<THREADS>(a, seg, part, 2 * (L.nb - 1 - b) + 1, grp.local || !split, false);   // conv2 tables complete
       if (pub) {
         if (halo) {
           pull_list_rows<2 * NC, THREADS>(go1T, sc + L.sc_go1 + (size_t)n0 * 2 * NC, hrow, hcnt);
@@ -394,12 +385,7 @@ __global__ __launch_bounds__(THREADS) void gatres_fused_kernel(const FusedArgs a
       float* t = gp_cur; gp_cur = gp_nxt; gp_nxt = t;
     }
     group_sync<THREADS>(grp);
-    publish_items<THREADS>(a, seg, part, 2 * L.nb, grp.local || !split, !split);
     seg_lin0_bwd<NC, THREADS>(rw, n0, a.perm, gp_cur, a.x, a.mask, slab + L.p_lin0_w, slab + L.p_lin0_b, red);
-    if (split && a.C > 0) {                   // last item: fold the lin0 / lin1 partial rows
-      group_sync<THREADS>(grp);
-      publish_items<THREADS>(a, seg, part, 2 * L.nb + 1, grp.local, true);
-    }
     if (a.g_x) {
       constexpr int G = NC / 4;
       const float4 wv = ld4(P + L.p_lin0_w + (tid % G) * 4);

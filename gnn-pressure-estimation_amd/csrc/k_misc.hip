@@ -24,10 +24,6 @@ void read_knobs(gatres_knobs_t* k) {
   k->fused_split = env_int("GATRES_FUSED_SPLIT", 0);
   k->fused_safe_sync = env_flag("GATRES_FUSED_SAFE_SYNC");
   k->fused_no_halo = env_flag("GATRES_FUSED_NO_HALO");
-  // consumer workgroups on a launch's spare CUs are opt-in since round 5: the stand-alone parameter-gradient launch
-  // (param_grads_reg_kernel) is faster at every batch size that leaves CUs free (bs 8 / 16 / 24: 0.317 / 0.322 / 0.328 against
-  // 0.347 / 0.349 / 0.352 ms/step), and it lets the update launch sample the next mask
-  k->fused_no_consumers = env_flag("GATRES_FUSED_WITH_CONSUMERS") ? 0 : 1;
   k->fused_no_rounds = env_flag("GATRES_FUSED_NO_ROUNDS");
   const int lf = env_int("GATRES_AGG_LANE_FEATURES", 0);
   k->agg_lane_features = (lf == 4 || lf == 8) ? lf : 0;
@@ -41,20 +37,17 @@ void read_knobs(gatres_knobs_t* k) {
   k->window_sync_start = env_flag("GATRES_WINDOW_SYNC_START");
   k->fused_no_keep = env_flag("GATRES_FUSED_NO_KEEP");
   // diagnostic build only
-  k->agg_wide_offsets = 0; k->fused_threads = 1024; k->fused_no_window = 0; k->fused_prefer_consumers = 0;
-  k->fused_consumers_cap = 2; k->fused_nocache = 0; k->fused_wide = 0; k->fused_heartbeat = 0;
-  k->param_grads_no_stream = 0; k->proj_rows = 0; k->proj_stream = 0; k->dw_fp32 = 0; k->no_co_launch = 0;
+  k->agg_wide_offsets = 0; k->fused_threads = 1024; k->fused_no_window = 0;
+  k->fused_nocache = 0; k->fused_wide = 0; k->fused_heartbeat = 0;
+  k->proj_rows = 0; k->proj_stream = 0; k->dw_fp32 = 0; k->no_co_launch = 0;
   k->co_launch_always = 0; k->dw_slab_rows = 0; k->xch_nowait = 0; k->diag_nomask = 0;
 #ifdef GATRES_DIAG_BUILD
   k->agg_wide_offsets = env_flag("GATRES_AGG_WIDE_OFFSETS");
   k->fused_threads = env_int("GATRES_FUSED_THREADS", 1024) == 512 ? 512 : 1024;
   k->fused_no_window = env_flag("GATRES_FUSED_NO_WINDOW");
-  k->fused_prefer_consumers = env_flag("GATRES_FUSED_PREFER_CONSUMERS");
-  { const int c = env_int("GATRES_FUSED_CONSUMERS", 2); k->fused_consumers_cap = c < 4 ? c : 4; }
   k->fused_nocache = env_flag("GATRES_FUSED_NOCACHE");
   k->fused_wide = env_flag("GATRES_FUSED_WIDE");
   k->fused_heartbeat = env_flag("GATRES_FUSED_HEARTBEAT");
-  k->param_grads_no_stream = env_flag("GATRES_PARAM_GRADS_NO_STREAM");
   k->proj_rows = (env_int("GATRES_PROJ_ROWS", 0) + 63) & ~63;
   k->proj_stream = env_flag("GATRES_PROJ_STREAM");
   k->dw_fp32 = env_flag("GATRES_DW_FP32");

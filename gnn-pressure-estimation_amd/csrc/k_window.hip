@@ -114,10 +114,9 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
   // allocations for the forward-only, backward-only and training instantiations); PH < 0: read from the arguments
   const int ph_ = PH < 0 ? a.phases : (PH & 0xff);
   const bool keep_ = PH < 0 ? a.keep_lds != 0 : (PH & 0x100) != 0;
-  // PH & 0x200: a symmetric plan (no pacing granules) and no consumer workgroups in this launch (the common case: undirected
-  // water networks, the parameter gradients as a launch of their own) -- the hand-offs' pace / drain paths are not compiled
-  constexpr bool LEAN = PH >= 0 && (PH & 0x200) != 0;
-  const int nC_ = LEAN ? 0 : a.C;
+  // PH & 0x200: a symmetric plan (no pacing granules; the common case: undirected water networks) -- the hand-offs' pacing
+  // path is not compiled
+  constexpr bool SYM = PH >= 0 && (PH & 0x200) != 0;
   // PH & 0x400: no row of any CSR of the plan has more than MAXD entries (GATRES_GRAPH_DEG_LE6): the stages' edge-at-a-time
   // paths and the alpha-table fallbacks are not compiled.  PH & 0x800: the plan carries this split's part tables (a record
   // that fails its magic check faults the launch instead of falling back to the in-kernel derivation).  PH & 0x1000: no part
@@ -146,13 +145,6 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
   float* ldsf = reinterpret_cast<float*>(lds_raw);
   const Layout& L = a.L;
   const int M = a.M;
-  if constexpr (!LEAN) {
-    const int F = ((a.seg_cnt + 7) / 8) * 8 * M;
-    if ((int)blockIdx.x >= F) {
-      consumer_main<NC, THREADS>(a, (int)blockIdx.x - F, ldsf);
-      return;
-    }
-  }
   const int within = blockIdx.x % (8 * M);
   const int seg = a.seg0 + (blockIdx.x / (8 * M)) * 8 + (within & 7), part = within >> 3;
   if (seg >= a.seg0 + a.seg_cnt) return;
@@ -217,9 +209,8 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
                                        // the launch would take if every hand-off were free
   xc.ep = (unsigned)uni((int)__hip_atomic_load(grp.flags + part * FLAG_STRIDE + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   const XchBuf xbuf = xch_buffer(xc.base, XL.total);
-  // pacing of the hand-offs by heartbeat granules: only when the plan does not promise two-sided halos; store drain at
-  // every hand-off: only when consumer workgroups read this part's tables in the same launch (xch_after)
-  const bool pace = LEAN ? false : !a.sym, drain = nC_ > 0;
+  // pacing of the hand-offs by heartbeat granules: only when the plan does not promise two-sided halos (xch_after)
+  const bool pace = SYM ? false : !a.sym;
   // first wave that issues LDS-DMA inside MFMA stages: the waves below it own a 16-row tile there (dma_copy16)
   constexpr int PW = 8;                    // waves that carry the work units of an MFMA stage (win_proj); NC == 32
   const int dw0 = NC == 32 ? PW : min((ow + 15) >> 4, THREADS / 64 - 4);
@@ -463,7 +454,7 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
         ++xc.ep;                                    // exchange F1: the gathers below read h1 / a_src of neighbour rows
         if (!xreg) xch_export2<2 * NC, 2, THREADS>(xc, xbuf, elist, ecnt, hA, (unsigned)XL.f1h, elist, ecnt, sa2, (unsigned)XL.f1a);
         xch_import2<2 * NC, 2, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f1h, hA, hlist, hcnt, (unsigned)XL.f1a, sa2);
-        xch_after<THREADS>(xc, pace, drain);
+        xch_after<THREADS>(xc, pace);
         lds_barrier();
         STAMP();
       }
@@ -536,7 +527,7 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
         ++xc.ep;                                    // exchange F2
         if (!xreg) xch_export2<NC, 1, THREADS>(xc, xbuf, elist, ecnt, hB, (unsigned)XL.f2h, elist, ecnt, sa1, (unsigned)XL.f2a);
         xch_import2<NC, 1, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f2h, hB, hlist, hcnt, (unsigned)XL.f2a, sa1);
-        xch_after<THREADS>(xc, pace, drain);
+        xch_after<THREADS>(xc, pace);
         lds_barrier();
         STAMP();
       }
@@ -577,7 +568,7 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
         ++xc.ep;                                    // exchange F3: K3 averages y2 over neighbour rows
         if (!(xreg && oeg <= wr * NC)) xch_export2<NC, 0, THREADS>(xc, xbuf, elist, ecnt, y2T, (unsigned)XL.f3, elist, 0, y2T, 0u);
         xch_import2<NC, 0, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f3, y2T, hlist, 0, 0u, y2T);
-        xch_after<THREADS>(xc, pace, drain);
+        xch_after<THREADS>(xc, pace);
         lds_barrier();
         STAMP();
       }
@@ -720,12 +711,10 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
     float* const red = ldsf;
     constexpr bool xedge = NC == 32;                 // win_bwd_dst stores the exported g_e granules itself
     const bool xrows = xedge && keep_;          // ... and so do the dX stages (win_proj) with their rows
-    constexpr bool pub = true;           // (the window kernel only runs split segments)
     constexpr int64_t w = 2LL * NC * NC;
     float* gp_cur = sc + L.sc_gpa;
     float* gp_nxt = sc + L.sc_gpb;
-    float* const slab = pub ? a.part_slabs + ((int64_t)seg * M + part) * L.slab_stride
-                            : a.slabs + (int64_t)seg * L.slab_stride;
+    float* const slab = a.part_slabs + ((int64_t)seg * M + part) * L.slab_stride;     // (the window kernel only runs split segments)
     {  // ---- prologue: LDS carve-up, the part's tables, lin1 backward; the geometry goes into the record
     // LDS: red | RA wr x 2NC | ge weg x 2 | gad own x 2 | hT wr x 2NC | asT wr x 2 | adT own x 2 | alT weg x 2 |
     //      xG own x 2NC | W slot A | W slot B | topology | halo lists
@@ -970,12 +959,11 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
         XSTAMP();
         xch_import2<NC, 0, THREADS>(xc, xbuf, hrow, hrcnt, (unsigned)XL.b1, gpT, hrow, 0, 0u, gpT);
         XSTAMP();
-        xch_after<THREADS>(xc, pace, drain);
+        xch_after<THREADS>(xc, pace);
         XSTAMP();
         lds_barrier();
         XSTAMP();
       }
-      if constexpr (!LEAN) publish_items<THREADS>(a, seg, part, 2 * (nb - 1 - b), grp.local, false);      // the blocks above are kept
       // K3 backward, conv2's edge dots and softmax backward: one stage (win_bwd_dst)
       STAMP();
       {
@@ -1016,7 +1004,7 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
         if (NC != 32 || !ow64)                   // (else the stage before ran the sweep on its idle waves)
         xch_import2<NC, 1, THREADS>(xc, xbuf, hrow, hrcnt, (unsigned)XL.b2y, gy2T, hedge, hecnt, (unsigned)XL.b2e, ge2);
         XSTAMP();
-        xch_after<THREADS>(xc, pace, drain);
+        xch_after<THREADS>(xc, pace);
         XSTAMP();
         if (!lean) lds_barrier();                  // (lean: nothing between the two stages touches LDS)
         XSTAMP();
@@ -1124,12 +1112,11 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
         XSTAMP();
         xch_import2<2 * NC, 2, THREADS>(xc, xbuf, hrow, hrcnt, (unsigned)XL.b3o, RA, hedge, hecnt, (unsigned)XL.b3e, ge1);
         XSTAMP();
-        xch_after<THREADS>(xc, pace, drain);
+        xch_after<THREADS>(xc, pace);
         XSTAMP();
         lds_barrier();
         XSTAMP();
       }
-      if constexpr (!LEAN) publish_items<THREADS>(a, seg, part, 2 * (nb - 1 - b) + 1, grp.local, false);      // conv2 tables complete
       STAMP();
       {
         FRESH_ARGS(); FRESH_BWD();
@@ -1196,13 +1183,10 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
     REC_PINS(LIST_);
     REC_DEFS(LIST_);
 #undef LIST_
-    // The parts only meet here for the consumers' sake (the last items are published behind this barrier); without consumer
-    // workgroups nothing of a partner is needed any more: a workgroup barrier that also drains this part's own stores (g_x below
-    // reads gp_cur back) replaces the flag barrier.  a.C is the same for every part: the barrier count per launch stays equal.
+    // Nothing of a partner is needed any more: a workgroup barrier that also drains this part's own stores (g_x below reads
+    // gp_cur back), not a flag barrier of the parts.
     if (assume_local) group_verify_local(grp);      // (one L2 round trip on wave 0, under the barrier below)
-    if (nC_ > 0) group_sync<THREADS>(grp);
-    else         __syncthreads();
-    if constexpr (!LEAN) publish_items<THREADS>(a, seg, part, 2 * L.nb, grp.local || !pub, !pub);
+    __syncthreads();
     // lin0's partial sums: g_pre of the own rows from LDS when the launch keeps them there (gkeep; gpT holds them divided by
     // the in-degrees for NC == 32), else from gp_cur
     seg_lin0_bwd<NC, THREADS>(rw, n0, a.perm, gp_cur, a.x, a.mask, slab + L.p_lin0_w, slab + L.p_lin0_b, red,
@@ -1213,10 +1197,6 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
                               nullptr
 #endif
                               );
-    if (pub && nC_ > 0) {
-      group_sync<THREADS>(grp);
-      publish_items<THREADS>(a, seg, part, 2 * L.nb + 1, grp.local, true);
-    }
     if (a.g_x) {
       constexpr int G = NC / 4;
       const float4 wv = ld4(P + L.p_lin0_w + (tid % G) * 4);
@@ -1254,9 +1234,9 @@ extern "C" __attribute__((visibility("hidden"))) int gatres_fused_launch_window(
     case 8: hipLaunchKernelGGL((gatres_window_kernel<8, 1024>), dim3(grid), dim3(1024), 0, st, a); break;
     case 16: hipLaunchKernelGGL((gatres_window_kernel<16, 1024>), dim3(grid), dim3(1024), 0, st, a); break;
     case 32: {
-      // the launch's compile-time facts (gatres_window_kernel): phases | 0x100 keep-in-LDS | 0x200 symmetric plan, no consumer
-      // workgroups | 0x400 rows of at most MAXD entries | 0x800 part tables | 0x1000 parts of at most 64 rows
-      int facts = ((a.sym && a.C == 0) ? 0x200 : 0) | (a.facts & 0x1400) | ((a.ptab && a.ptab_m == a.M) ? 0x800 : 0);
+      // the launch's compile-time facts (gatres_window_kernel): phases | 0x100 keep-in-LDS | 0x200 symmetric plan
+      // | 0x400 rows of at most MAXD entries | 0x800 part tables | 0x1000 parts of at most 64 rows
+      int facts = (a.sym ? 0x200 : 0) | (a.facts & 0x1400) | ((a.ptab && a.ptab_m == a.M) ? 0x800 : 0);
       if ((a.facts & 0x2000) && facts == 0x1e00) facts |= 0x2000;      // (inference: only with every other fact -- one instantiation)
       if ((a.facts & 0x4000) && (facts & 0x1e00) == 0x1e00 && !a.safe_sync) facts |= 0x4000;      // (probed dispatch: likewise)
       const int key = a.phases | (a.keep_lds ? 0x100 : 0) | (facts & gatres_knobs()->window_ph_mask);

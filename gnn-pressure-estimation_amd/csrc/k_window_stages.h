@@ -317,10 +317,9 @@ __device__ __forceinline__ void xch_import2_by(Xch& x, unsigned ep, const XchBuf
 // ep - 1 (k_fused_dev.h: xch_heartbeat) -- needed only when the plan cannot promise that partners owe each other rows in
 // both directions (GATRES_GRAPH_SYMMETRIC: then a part cannot reach the exchange that rewrites a cell before the cell's
 // readers have passed the exchange in between, because that one needs THEIR granules, which they store after their own
-// sweep).  drain: every wave waits for its outstanding global stores, so that the barrier that follows publishes them to
-// the consumer workgroups (publish_items) -- needed only in launches that have consumers.
+// sweep).
 template <int THREADS>
-__device__ __forceinline__ void xch_after(Xch& x, bool pace, bool drain) {
+__device__ __forceinline__ void xch_after(Xch& x, bool pace) {
   if (pace) {
     u64* hb = x.base_hb;
     if (threadIdx.x == 0) gran_store(hb + x.part, 0.f, x.ep, x.local);
@@ -335,7 +334,6 @@ __device__ __forceinline__ void xch_after(Xch& x, bool pace, bool drain) {
       }
     }
   }
-  if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // EXPORT FROM THE PRODUCING STAGE.  xch_export2 runs behind the producer's closing barrier and re-reads the rows it

@@ -58,9 +58,9 @@ static int fused_grads_and_update(const gatres_train_step_t* ts, const float* lo
   const int rc = gatres_fused_param_grads_ex(&ts->model, ts->graph, ts->saved, ts->scratch,
                                              (adam || snap_later) ? ts->step_counter : nullptr, stream);
   if (rc < 0 || rc > 1) return rc;
-  // (rc == 1: the launch left the step count / fault word snapshot the sampling tail of the update launch reads; batches
-  //  that leave CUs free form their parameter gradients on consumer workgroups instead -- no snapshot, no sampling ahead:
-  //  the caller finds mask_next untouched... so it must not rely on it: GATResTrainer asks gatres_fused_finish_folds first)
+  // (rc == 1: the launch left the step count / fault word snapshot the sampling tail of the update launch reads; models whose
+  //  parameter gradients do not fold (nc 4 / 8: param_grads_kernel) leave none -- no sampling ahead: the caller finds
+  //  mask_next untouched... so it must not rely on it: GATResTrainer asks gatres_fused_finish_folds first)
   const bool mask_next = want_next && rc == 1;
   if (adam && ts->autoclip) {      // the slab sum leaves the norm partials; the update launch clips, applies Adam, samples ahead
     Layout L;
@@ -90,8 +90,8 @@ extern "C" int gatres_train_step(const gatres_train_step_t* ts, void* stream) {
   const int N = ts->graph->num_nodes;
   int rc = 0;
   const bool fused = !(ts->flags & GATRES_FLAG_PER_OP) && gatres_fused_supported(&ts->model, ts->graph);
-  // GATRES_FLAG_MASK_NEXT can only be honoured where the parameter gradients are a launch of their own (it leaves the step
-  // count / fault snapshot the sampling tail reads).  Refused BEFORE anything is enqueued: a caller that asked for the next
+  // GATRES_FLAG_MASK_NEXT can only be honoured where the parameter gradients fold (gatres_fused_finish_folds: their launch
+  // leaves the step count / fault snapshot the sampling tail reads).  Refused BEFORE anything is enqueued: a caller that asked for the next
   // mask and did not get it would train on a stale one without noticing.
   if (fused && (ts->flags & GATRES_FLAG_MASK_NEXT) && (ts->phases & GATRES_PHASE_ADAM) && (ts->phases & GATRES_PHASE_BACKWARD) &&
       ts->node_ptr && ts->num_graphs > 0 && ts->mask_next && ts->mask_next != ts->mask &&

@@ -199,8 +199,8 @@ class GATResTrainer:
         # Single-GPU fused step: the update launch samples the NEXT step's device mask into the spare buffer
         # (GATRES_FLAG_MASK_NEXT); a step that finds it still valid swaps the buffers and leaves the sampler's launch out.
         # self.mask always is the mask of the step that ran last.  _mask_sig: what the spare buffer's mask was sampled for.
-        # (only where the parameter gradients are a launch of their own: it leaves the step count / fault snapshot the
-        #  sampling tail reads -- batches that leave CUs free use consumer workgroups and keep the sampler's own launch)
+        # (only where the parameter gradients fold: their launch leaves the step count / fault snapshot the sampling tail
+        #  reads -- models of nc 4 / 8 form them with param_grads_kernel and keep the sampler's own launch)
         # (the data-parallel step -- one gradient bucket -- does the same from its Adam launch, gatres_adam_step_ex)
         self._mask_next = bool(self.fused and self.node_ptr is not None
                                and self.lib.gatres_fused_finish_folds(model._cmodel_ref(), self.plan.ref())

@@ -541,8 +541,7 @@ int gatres_fused_finish_hp(const gatres_model_t* m, const gatres_graph_t* g, flo
  * model: 0, num_blocks): every (block, conv) column's last workgroup sums the column's slab rows, writes grads and (do_adam)
  * applies Adam to those parameters; lin0's gradient rides on block 0, lin1's on the last block, so the ranges
  * [0, p(block_hi)) ... tile the flat vector like gatres_model_backward_per_op_part's.  do_adam needs the whole model in one
- * call.  Returns GATRES_E_UNSUPPORTED where the two-launch form has to be used (nc other than 16 / 32, or parameter
- * gradients formed on consumer workgroups of the backward launch: batches that leave CUs free). */
+ * call.  Returns GATRES_E_UNSUPPORTED where the two-launch form has to be used (nc other than 16 / 32). */
 /* 1 if gatres_fused_param_grads_finish applies to this model / plan (else it returns GATRES_E_UNSUPPORTED). */
 int gatres_fused_finish_folds(const gatres_model_t* m, const gatres_graph_t* g);
 int gatres_fused_param_grads_finish(const gatres_model_t* m, const gatres_graph_t* g, const float* saved, float* scratch,

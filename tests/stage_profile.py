@@ -23,8 +23,6 @@ raw = stamps.cpu().numpy()
 clk = raw[cap:cap + 3]
 s = raw[:1024]
 s = s[s > 0]
-cs = raw[1024:2048]
-cs = cs[cs > 0]
 print('shader clock MHz ~', (clk[1] - clk[0]) / ((clk[2] - s[0]) / 100.0))
 d = (s[1:] - s[:-1]) / 100.0   # us
 print("stamps", len(s), "total us", (s[-1] - s[0]) / 100.0)
@@ -48,17 +46,6 @@ for k, v in acc.items():
     tot += sum(v)
 print("sum of block stages", tot, "remaining stamps", len(d) - i)
 
-if len(cs) >= 2:
-    # consumer workgroup 0: [item available, item done] pairs (100 MHz wall clock)
-    t0 = s[0]
-    avail, done = cs[0::2], cs[1::2]
-    n = min(len(avail), len(done))
-    work = (done[:n] - avail[:n]) / 100.0
-    print("consumer 0: %d items, work per item mean %.2f us (min %.2f max %.2f), first available at %.1f us, last done at %.1f us"
-          % (n, work.mean(), work.min(), work.max(), (avail[0] - t0) / 100.0, (done[n - 1] - t0) / 100.0))
-    print("   wait before each item (us):", " ".join("%.1f" % w for w in ((avail[1:n] - done[:n - 1]) / 100.0)))
-    print("   work of each item (us):   ", " ".join("%.1f" % w for w in work))
-
 # one backward block of segment 0, every part, wave 0 / last wave (k_fused.hip XSTAMP)
 xs = raw[2048:2048 + 16 * 64].reshape(16, 64)
 names_x = ["top", "bar", "B1 export", "B1 import", "B1 after", "bar", "k3+dots2+smax2+bar",
@@ -71,13 +58,3 @@ if xs[0, 0] > 0:
     print("%-18s" % "step" + "".join("   p%d w0   wL " % (r // 2) for r in rows if r % 2 == 0))
     for k, nme in enumerate(names_x):
         print("%-18s" % nme + "".join(" %6.2f" % ((int(xs[r, k]) - t0) / 100.0) + ("" if r % 2 else "") for r in rows))
-
-# steps inside the consumer's streamed items (k_fused.hip ISTAMP): 8 stamps per item from slot 3072 + 8
-it = raw[3072 + 8:3072 + 8 + 8 * 40].reshape(40, 8)
-it = it[it[:, 0] > 0]
-if len(it):
-    d = (it[:, 1:] - it[:, :1]) / 100.0
-    print("\nconsumer item steps, us since the item's start (mean over %d items):" % len(it))
-    for k, nme in enumerate(["fold done (compute waves)", "chunk 0 landed", "chunk 1 landed", "last chunk landed", "last chunk computed",
-                             "partials in LDS", "slab written"]):
-        print("  %-28s %6.2f" % (nme, d[:, k].mean()))

@@ -233,7 +233,7 @@ def test_shuffled_node_order_is_relabelled_and_exact(pkg, oracle, fused):
     lib = pkg._native.load()
     if fused:
         assert tr.plan.perm_host is not None and tr.plan.window_rows(4) < 388 // 2
-        assert lib.gatres_fused_cus_per_segment(model._cmodel_ref(), tr.plan.ref()) == 8      # 8 parts (+ 2 consumer CUs: a batch of 3 leaves CUs free)
+        assert lib.gatres_fused_cus_per_segment(model._cmodel_ref(), tr.plan.ref()) == 8      # 8 parts
         assert lib.gatres_fused_window_kernel(model._cmodel_ref(), tr.plan.ref()) == 1
     snaps = pkg.wdn_synth.make_snapshots(2 * bs, 388, seed=4)
     ref = oracle.OracleTrainer(p)
@@ -339,8 +339,7 @@ def test_load_state_dict_between_steps_is_noticed(pkg, oracle, use_graph):
 def test_set_lr_under_graph_replay(pkg, oracle):
     """The update kernels read the hyper-parameters from a device buffer (gatres_train_step_t.hparams): a
     ReduceLROnPlateau-style change (train.py:349-350) takes effect at the next step WITHOUT a new capture -- one family of
-    graphs for three learning rates (small batch: the two-launch update with consumer workgroups; the headline shape is in
-    tests/test_gpu_headline.py)."""
+    graphs for three learning rates (a small batch, bs 2; the headline shape is in tests/test_gpu_headline.py)."""
     model, p, tr, ei, y, mask = _small_setup(pkg, oracle, use_graph=True)
     twin, _, tr2, *_ = _small_setup(pkg, oracle, use_graph=False)
     counts = []

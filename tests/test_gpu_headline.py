@@ -17,8 +17,8 @@ pytestmark = pytest.mark.gpu
 NB, NC, BS, NODES, PIPES = 15, 32, 32, 388, 430
 
 
-def _trainer(pkg, oracle, seed=3, bs=BS, **kw):
-    model, p = build(pkg, oracle, NB, NC, seed=seed)
+def _trainer(pkg, oracle, seed=3, bs=BS, nc=NC, **kw):
+    model, p = build(pkg, oracle, NB, nc, seed=seed)
     ei = pkg.wdn_synth.collate_edge_index(pkg.wdn_synth.make_wdn_topology(NODES, PIPES, seed=0), NODES, bs)
     tr = pkg.GATResTrainer(model, ei.cuda(), NODES * bs, nodes_per_graph=[NODES] * bs, **kw)
     return model, p, tr, ei
@@ -27,7 +27,7 @@ def _trainer(pkg, oracle, seed=3, bs=BS, **kw):
 def test_headline_config_training_steps_vs_oracle(pkg, oracle, lib):
     model, p, tr, ei = _trainer(pkg, oracle, use_graph=True)
     # the configuration the bench line reports: window kernel at 8 CUs per snapshot, the parameter gradients as a launch of
-    # their own (no consumer workgroups at bs 32) that also carries the slab sum and Adam
+    # their own that also carries the slab sum and Adam
     assert tr.fused and tr.use_graph
     assert lib.gatres_fused_cus_per_segment(model._cmodel_ref(), tr.plan.ref()) == 8
     assert lib.gatres_fused_window_kernel(model._cmodel_ref(), tr.plan.ref()) == 1
@@ -369,14 +369,13 @@ def test_alternating_launch_kinds_on_one_scratch_buffer(pkg, oracle):
     assert tr.fault_count == 0
 
 
-def test_mask_next_is_refused_where_it_cannot_be_honoured(pkg, oracle, monkeypatch):
-    """GATRES_FLAG_MASK_NEXT on a configuration whose parameter gradients run on consumer workgroups (no step-count
+def test_mask_next_is_refused_where_the_gradients_do_not_fold(pkg, oracle, lib):
+    """GATRES_FLAG_MASK_NEXT on a fused configuration whose parameter gradients do not fold (no step-count
     snapshot for the sampling tail) used to be dropped silently; it is an error now, raised before anything is enqueued."""
     from gnn_pressure_estimation_amd import train_step as TS
-    monkeypatch.setenv("GATRES_FUSED_WITH_CONSUMERS", "1")              # (opt-in since round 5: the stand-alone launch is the default)
-    model, p, tr, ei = _trainer(pkg, oracle, bs=8, use_graph=False)      # bs 8: CUs are left, consumers form the gradients
-    if tr._mask_next:
-        pytest.skip("this configuration folds the update: nothing to refuse")
+    model, p, tr, ei = _trainer(pkg, oracle, bs=8, nc=8, use_graph=False)     # nc 8: param_grads_kernel, no fold
+    assert tr.fused
+    assert lib.gatres_fused_finish_folds(model._cmodel_ref(), tr.plan.ref()) == 0
     y = pkg.wdn_synth.make_snapshots(8, NODES, seed=2).reshape(-1).cuda()
     tr.load_batch(y, y)
     before = tr.optimizer_step

@@ -627,8 +627,7 @@ def test_parameter_gradient_items_on_segments_of_any_size(pkg, oracle, nc, monke
 
 
 @pytest.mark.parametrize("split,mode", [(1, ""), (2, ""), (4, ""), (8, ""), (3, ""), (7, ""), (4, "GATRES_FUSED_NO_HALO"),
-                                        (4, "GATRES_FUSED_SAFE_SYNC"), (2, "GATRES_FUSED_WITH_CONSUMERS"),
-                                        (4, "GATRES_FUSED_WITH_CONSUMERS")])
+                                        (4, "GATRES_FUSED_SAFE_SYNC")])
 def test_fused_split_over_cus_matches_per_op(pkg, oracle, split, mode, monkeypatch):
     """One snapshot carried by 1 / 2 / 4 / 8 workgroups (row windows + flag barriers + halo pulls): predictions stay
     bit-identical to the per-op kernels, gradients agree up to the slab partition.  The batch is ragged (a 388-node
@@ -636,7 +635,7 @@ def test_fused_split_over_cus_matches_per_op(pkg, oracle, split, mode, monkeypat
     neighbours are halo rows) and the launches are repeated so that the persistent barrier epochs are exercised."""
     monkeypatch.setenv("GATRES_FUSED_SPLIT", str(split))
     monkeypatch.setenv("GATRES_REORDER", "0")          # keep the shuffled ids: this test is about large halos
-    if mode:                 # the fallbacks: bulk pulls, agent-scope barriers; parameter gradients on consumer workgroups of the launch
+    if mode:                 # the fallbacks: bulk pulls, agent-scope barriers
         monkeypatch.setenv(mode, "1")
     nb, nc = 4, 32
     t_big = pkg.wdn_synth.make_wdn_topology(388, 430, seed=0)

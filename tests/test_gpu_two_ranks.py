@@ -21,7 +21,7 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NODES, PIPES, STEPS = 388, 430, 3
-CASES = {"fused": dict(nb=4, nc=32, per_rank=4, fused=True),           # 8 parts x 4 (+ consumers) per rank: both grids resident
+CASES = {"fused": dict(nb=4, nc=32, per_rank=4, fused=True),           # 8 parts x 4 per rank: both grids resident
          "per_op": dict(nb=3, nc=128, per_rank=2, fused=False)}        # gatres_large's path: one gradient bucket per block
 
 
