@@ -16,8 +16,13 @@ each bracketed by a barrier + torch.cuda.synchronize() on both sides and reduced
 timed steps of the run (`timed_steps` in the line).  Rank 0 prints ONE JSON line.
 `--dump-outputs DIR`: after the timed blocks, what the timed path computed in its last step is written as DIR/<name>.npy
 (see dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
-`roofline.traffic` is measured in the run: before touching the GPU the script runs itself twice as a child under
-`rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (a few seconds each; `--no-live-pmc` skips them).
+A plain run does only what the headline figure needs: set-up, warm-up, the timed blocks, the dump, the line.
+`--full` adds everything else the benchmark measures or checks, each still subject to its `--no-*` switch: `roofline`
+(live HIP-event timing of the kernels; for the per-op path the per-kernel table), `parity` against the oracle in the run,
+`cpu_baseline` (the oracle on the host cores, up to 2 x --cpu-seconds) and, for the data-parallel step,
+`config.collective` (the all-reduce timed over 20 eager steps).  `roofline.traffic` is measured in a `--full` run: before touching the GPU the
+script runs itself twice as a child under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (a few seconds each;
+`--no-live-pmc` skips them).
 Data: synthetic (seeded WDN topology with C-Town's size, N(0,1) pressures, PyG-style random-init weights); the
 reference's C-Town files are not shipped.
 """
@@ -87,6 +92,10 @@ def parse():
     ap.add_argument("--copy-batches", action="store_true",
                     help="stage every batch into the trainer's buffer (GATResTrainer.step(x, y): one more launch per step) "
                          "instead of training on the resident batches in place (bind_batches / step_bound)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, everything else the benchmark measures or checks: the roofline (with "
+                         "its rocprofv3 counter passes), in-run parity against the oracle, the CPU baseline, the all-reduce "
+                         "timing of a data-parallel run; the --no-* switches below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-roofline", action="store_true")
@@ -673,8 +682,9 @@ def main():
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    if (world == 1 and rank == 0 and not (args.no_roofline or args.no_live_pmc or args.per_op or args.drop_in or args.eval
-                                          or args.force_collective_path or args.dtype == "bf16" or args.model != "gatres_small")
+    if (args.full and world == 1 and rank == 0
+            and not (args.no_roofline or args.no_live_pmc or args.per_op or args.drop_in or args.eval
+                     or args.force_collective_path or args.dtype == "bf16" or args.model != "gatres_small")
             and not os.environ.get("GATRES_BENCH_CHILD") and torch.cuda.device_count() > 0):
         # (device_count() does not initialise the GPU on this image; the child passes must come before anything that does)
         log("two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) for roofline.traffic ...")
@@ -804,7 +814,7 @@ def main():
                                          "params": model.flat_parameters, "adam_exp_avg": trainer.exp_avg,
                                          "adam_exp_avg_sq": trainer.exp_avg_sq})
     coll = None
-    if trainer.split and trainer.reducer is not None and trainer.reducer.active and trainer._one_piece():
+    if args.full and trainer.split and trainer.reducer is not None and trainer.reducer.active and trainer._one_piece():
         # what the all-reduce itself takes: 20 more steps as EAGER launches with an event pair around the collective (events
         # inside a captured step cannot be read); untimed, after the timed blocks
         was = trainer.use_graph
@@ -868,7 +878,7 @@ def main():
     if DIST_BACKEND != "nccl" or SHARE_GPU:
         result["config"]["test_overrides"] = {"backend": DIST_BACKEND, "ranks_share_gpu": SHARE_GPU}
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         sb = survey_bytes_per_snapshot(nb, nc, args.nodes, 2 * args.pipes, 2 if args.dtype == "bf16" else 4)
         stated = SURVEY_STATED_BYTES.get((args.model, args.nodes, 2 * args.pipes, args.dtype))
         unit_bytes = stated if stated is not None else sb["total"]
@@ -956,7 +966,7 @@ def main():
             hs = hbm_side_rates(args)
             if hs is not None:
                 result["hbm_side_rates"] = hs
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["parity"] = in_run_parity(args, nb, nc, device)
         log(f"in-run parity vs the oracle: {result['parity']['out_rel']:.2e} (out) {result['parity']['loss_rel']:.2e} (loss) "
             f"{result['parity']['grad_rel']:.2e} (grad)")

@@ -1,7 +1,7 @@
 # Round-2 evidence, per-op configurations only (re-run after the per-op kernels changed): gpurun_out/r02s_perop/ -> profiles/ by hand.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r02s_perop; mkdir -p $O
-B="python3 bench.py"
+B="python3 bench.py --full"
 short='import sys,json; d=json.loads(sys.stdin.read()); print(round(d["value"]), "snapshots/s", round(d["ms_per_step"],4), "ms/step")'
 timeout 300 $B --no-cpu-baseline --per-op 2>/dev/null | tail -1 > $O/per_op.json; python3 -c "$short" < $O/per_op.json
 timeout 600 $B --no-cpu-baseline --model gatres_large --batch-size 128 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/large_fp32.json; python3 -c "$short" < $O/large_fp32.json

@@ -94,3 +94,17 @@ def test_bench_dump_outputs_of_the_last_timed_step(fork_ctx, tmp_path):
         assert a.dtype == np.float32 and a.shape == (n,) and np.isfinite(a).all(), k
     assert abs(float(np.load(d / "loss.npy")[0]) - line["config"]["final_loss"]) <= 1e-6 * abs(line["config"]["final_loss"])
     assert set(np.unique(np.load(d / "mask.npy"))) <= {0.0, 1.0}
+
+
+def test_bench_plain_run_is_the_headline_and_full_adds_the_rest(fork_ctx, tmp_path):
+    """A plain run reports the headline line and nothing that needs runs of its own; `--full` adds the roofline, in-run
+    parity against the oracle and the CPU baseline (the counter passes left out here: --no-live-pmc)."""
+    extra = {"roofline", "kernels", "parity", "cpu_baseline"}
+    plain = _launch(fork_ctx, tmp_path, ["--gpus", "1", "--steps", "3", "--warmup", "1"], {})
+    assert plain["metric"] == "train snapshots/sec" and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert not extra & set(plain)
+    full = _launch(fork_ctx, tmp_path, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-live-pmc",
+                                        "--cpu-seconds", "0.5"], {})
+    assert {"roofline", "parity", "cpu_baseline"} <= set(full)
+    assert full["roofline"]["avg_launch_us"] > 0 and full["cpu_baseline"]["value"] > 0
+    assert full["parity"]["out_rel"] < full["parity"]["tolerance"]["out_rel"]
