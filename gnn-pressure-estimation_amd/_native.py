@@ -93,6 +93,7 @@ SIGNATURES = {
     "gatres_stage_rows_mask_required": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _F64, _U64, _P, _P, _I32, _P, _P]),
     "gatres_masked_metrics": (C.c_int, [_P, _P, _P, _I32, _F64, _F64, _P, _I32, _I32, _P, _P]),
     "gatres_masked_mse": (C.c_int, [_P] * 5 + [_I32, _P]),
+    "gatres_masked_loss": (C.c_int, [_P] * 3 + [_I32] + [_P] * 2 + [_I32, _P]),
     "gatres_adam_step": (C.c_int, [_P] * 5 + [_I64] + [_F64] * 5 + [_F32, _P]),
     # typed per-op kernels (storage type argument): C ints
     "gatres_t_gat_aggregate_fwd": (C.c_int, [_GP] + [_P] * 6 + [C.c_int] * 4 + [_P]),
@@ -144,7 +145,9 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 8                # GATRES_ABI_VERSION of include/gatres.h
+ABI_VERSION = 9                # GATRES_ABI_VERSION of include/gatres.h
+LOSS_MSE, LOSS_MAE, LOSS_SCE = 0, 1, 2              # GATRES_LOSS_* (gatres_masked_loss)
+CRITERIA = {"mse": LOSS_MSE, "mae": LOSS_MAE, "sce": LOSS_SCE}      # the reference's train.py --criterion choices
 
 
 def diag_build() -> bool:

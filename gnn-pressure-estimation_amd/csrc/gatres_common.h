@@ -99,6 +99,25 @@ __device__ __forceinline__ double gatres_powi(double b, unsigned long long t) {
 
 __device__ __forceinline__ float gatres_leaky(float v) { return v > 0.f ? v : v * GATRES_NEG_SLOPE; }
 
+// The reference's other training criteria (gatres.h: GATRES_LOSS_MAE, GATRES_LOSS_SCE) on one masked node: returns the node's
+// loss term and leaves M * d loss / d out in *seed (the caller multiplies by 1 / M).  MSE keeps its own inline arithmetic at
+// every site (d * d and d * 2 / M), so its bits do not depend on this function.
+__device__ __forceinline__ float gatres_loss_term(int crit, float o, float y, float* seed) {
+  if (crit == GATRES_LOSS_MAE) {                        // L1Loss; torch's backward: sign(d), sign(0) = 0
+    const float d = o - y;
+    *seed = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    return fabsf(d);
+  }
+  // sce_loss, alpha = 3, on [M, 1] tensors: o^ = o / max(|o|, eps) is +-1 unless |o| < eps, where o^ = o / eps has slope
+  // 1 / eps (clamp_min's backward: at |o| == eps the norm branch is the live one, and o / |o| is flat)
+  constexpr float eps = 1e-12f;
+  const float ao = fabsf(o);
+  const float oh = o / fmaxf(ao, eps), yh = y / fmaxf(fabsf(y), eps);
+  const float t = fmaf(-oh, yh, 1.f);
+  *seed = ao < eps ? -3.f * (t * t) * yh / eps : 0.f;
+  return t * t * t;
+}
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }

@@ -50,7 +50,7 @@ struct FusedArgs {
   const float* y;
   float* out;
   float* g_out;             // written by the loss phase, read by the backward phase
-  float* loss_part;         // [num_segments + 1]: per-segment sum of squared errors; last = masked-node count
+  float* loss_part;         // [num_segments + 1]: per-segment sum of the criterion's terms; last = masked-node count
   float* g_x;               // may be null
   float* saved;             // may be null for inference
   float* scratch;
@@ -80,6 +80,8 @@ struct FusedArgs {
   int phases;               // GATRES_PHASE_FORWARD | _BACKWARD, bit 16: loss
   unsigned long long* stamps;   // diagnostic: segment 0 stamps the wall clock at every stage boundary
   int stamp_cap;
+  int criterion;            // the loss phase's criterion (GATRES_LOSS_*; 0 = MSE).  Last, so that no other member's kernel-
+                            // argument offset depends on it
 };
 
 enum { PH_LOSS = 16 };

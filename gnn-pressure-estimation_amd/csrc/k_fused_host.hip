@@ -581,6 +581,9 @@ extern "C" int gatres_fused_run(const gatres_model_t* m, const gatres_graph_t* g
   if (!make_layout_g(m, g, &a.L)) return GATRES_E_UNSUPPORTED;
   if ((phases & GATRES_PHASE_FORWARD) && !out) return GATRES_E_BADARG;
   if ((phases & GATRES_PHASE_LOSS) && (!mask || !y || !out || !g_out || !loss_part)) return GATRES_E_BADARG;
+  const int32_t crit_bits = phases & (GATRES_PHASE_LOSS_MAE | GATRES_PHASE_LOSS_SCE);
+  if (crit_bits && (!(phases & GATRES_PHASE_LOSS) || crit_bits == (GATRES_PHASE_LOSS_MAE | GATRES_PHASE_LOSS_SCE)))
+    return GATRES_E_BADARG;
   if ((phases & GATRES_PHASE_BACKWARD) && (!saved || !g_out)) return GATRES_E_BADARG;
   a.seg_ptr = g->seg_ptr;
   a.rowptr = g->rowptr; a.col = g->col; a.t_rowptr = g->t_rowptr; a.t_eid = g->t_eid; a.t_dst = g->t_dst;
@@ -615,6 +618,8 @@ extern "C" int gatres_fused_run(const gatres_model_t* m, const gatres_graph_t* g
   a.XL = make_xch_layout(a.L.nc, g->max_segment_nodes, g->max_segment_edges_gat);
   a.stamps = g_stamps; a.stamp_cap = g_stamp_cap;
   a.phases = (phases & (GATRES_PHASE_FORWARD | GATRES_PHASE_BACKWARD)) | ((phases & GATRES_PHASE_LOSS) ? PH_LOSS : 0);
+  a.criterion = crit_bits == GATRES_PHASE_LOSS_MAE ? GATRES_LOSS_MAE : crit_bits == GATRES_PHASE_LOSS_SCE ? GATRES_LOSS_SCE
+                                                                                                        : GATRES_LOSS_MSE;
   hipStream_t st = gatres_stream(stream);
   if (a.M > 1) serialize_split_launch(st);
   int rc = launch_fused(m->nc, threads_for(m->nc), a, g, st);

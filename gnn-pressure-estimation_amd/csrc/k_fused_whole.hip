@@ -218,12 +218,18 @@ __global__ __launch_bounds__(THREADS) void gatres_fused_kernel(const FusedArgs a
     float cnt = 0.f;
     for (int i = tid; i < a.N; i += THREADS) cnt += a.mask[i] ? 1.f : 0.f;
     const float Mn = block_sum<THREADS>(cnt, ldsf);
+    const int crit = a.criterion;               // (uniform: MSE keeps its own arithmetic, the others gatres_loss_term)
     float part_sum = 0.f;
     for (int r = rw.lo + tid; r < rw.hi; r += THREADS) {
       const int node = ext_id(a.perm, n0 + r);
       if (a.mask[node]) {
-        const float d = a.out[node] - a.y[node];
-        part_sum = fmaf(d, d, part_sum);
+        if (crit == GATRES_LOSS_MSE) {
+          const float d = a.out[node] - a.y[node];
+          part_sum = fmaf(d, d, part_sum);
+        } else {
+          float s;
+          part_sum += gatres_loss_term(crit, a.out[node], a.y[node], &s);
+        }
       }
     }
     part_sum = block_sum<THREADS>(part_sum, ldsf);
@@ -231,10 +237,20 @@ __global__ __launch_bounds__(THREADS) void gatres_fused_kernel(const FusedArgs a
       a.loss_part[seg * M + part] = part_sum;
       if (seg == 0 && part == 0) a.loss_part[a.num_segments * M] = Mn;
     }
-    const float scale = Mn > 0.f ? 2.f / Mn : 0.f;
-    for (int r = rw.lo + tid; r < rw.hi; r += THREADS) {
-      const int node = ext_id(a.perm, n0 + r);
-      a.g_out[node] = a.mask[node] ? (a.out[node] - a.y[node]) * scale : 0.f;
+    if (crit == GATRES_LOSS_MSE) {
+      const float scale = Mn > 0.f ? 2.f / Mn : 0.f;
+      for (int r = rw.lo + tid; r < rw.hi; r += THREADS) {
+        const int node = ext_id(a.perm, n0 + r);
+        a.g_out[node] = a.mask[node] ? (a.out[node] - a.y[node]) * scale : 0.f;
+      }
+    } else {
+      const float inv = Mn > 0.f ? 1.f / Mn : 0.f;
+      for (int r = rw.lo + tid; r < rw.hi; r += THREADS) {
+        const int node = ext_id(a.perm, n0 + r);
+        float s = 0.f;
+        if (a.mask[node]) (void)gatres_loss_term(crit, a.out[node], a.y[node], &s);
+        a.g_out[node] = s * inv;
+      }
     }
     __syncthreads();
     STAMP();

@@ -458,10 +458,12 @@ __global__ __launch_bounds__(1024) void mask_generate_kernel(const int* __restri
                           blockIdx.x % MASK_WGS);
 }
 
-// ------------------------------------------------------------------------------------------- masked MSE
-__global__ __launch_bounds__(1024) void masked_mse_kernel(const float* __restrict__ out, const float* __restrict__ y,
-                                                          const uint8_t* __restrict__ mask, float* __restrict__ loss,
-                                                          float* __restrict__ g_out, int N) {
+// ------------------------------------------------------------------------------------------- masked loss
+// CRIT = GATRES_LOSS_MSE is the masked MSE of gatres_masked_mse, instruction for instruction; MAE / SCE: gatres_loss_term
+template <int CRIT>
+__global__ __launch_bounds__(1024) void masked_loss_kernel(const float* __restrict__ out, const float* __restrict__ y,
+                                                           const uint8_t* __restrict__ mask, float* __restrict__ loss,
+                                                           float* __restrict__ g_out, int N) {
   __shared__ float s_sum[1024];
   __shared__ int s_cnt[1024];
   const int tid = threadIdx.x;
@@ -476,15 +478,25 @@ __global__ __launch_bounds__(1024) void masked_mse_kernel(const float* __restric
 #pragma unroll
     for (int u = 0; u < 4; ++u)
       if (mk[u]) {
-        const float d = o[u] - t[u];
-        acc = fmaf(d, d, acc);
+        if (CRIT == GATRES_LOSS_MSE) {
+          const float d = o[u] - t[u];
+          acc = fmaf(d, d, acc);
+        } else {
+          float s;
+          acc += gatres_loss_term(CRIT, o[u], t[u], &s);
+        }
         ++cnt;
       }
   }
   for (; n < N; n += 1024) {
     if (mask[n]) {
-      const float d = out[n] - y[n];
-      acc = fmaf(d, d, acc);
+      if (CRIT == GATRES_LOSS_MSE) {
+        const float d = out[n] - y[n];
+        acc = fmaf(d, d, acc);
+      } else {
+        float s;
+        acc += gatres_loss_term(CRIT, out[n], y[n], &s);
+      }
       ++cnt;
     }
   }
@@ -496,8 +508,17 @@ __global__ __launch_bounds__(1024) void masked_mse_kernel(const float* __restric
   }
   const int M = s_cnt[0];
   if (tid == 0) loss[0] = s_sum[0] / (float)M;            // M == 0 -> NaN, like torch's mean of an empty tensor
-  const float scale = M > 0 ? 2.f / (float)M : 0.f;
-  _Pragma("unroll 4") for (int n = tid; n < N; n += 1024) g_out[n] = mask[n] ? (out[n] - y[n]) * scale : 0.f;
+  if (CRIT == GATRES_LOSS_MSE) {
+    const float scale = M > 0 ? 2.f / (float)M : 0.f;
+    _Pragma("unroll 4") for (int n = tid; n < N; n += 1024) g_out[n] = mask[n] ? (out[n] - y[n]) * scale : 0.f;
+  } else {
+    const float inv = M > 0 ? 1.f / (float)M : 0.f;
+    for (int n = tid; n < N; n += 1024) {
+      float s = 0.f;
+      if (mask[n]) (void)gatres_loss_term(CRIT, out[n], y[n], &s);
+      g_out[n] = s * inv;
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------- Adam
@@ -805,9 +826,25 @@ extern "C" int gatres_stage_rows_mask(const float* data, const int64_t* rows, in
 
 extern "C" int gatres_masked_mse(const float* out, const float* y, const uint8_t* mask, float* loss, float* g_out,
                                  int32_t num_nodes, void* stream) {
+  return gatres_masked_loss(out, y, mask, GATRES_LOSS_MSE, loss, g_out, num_nodes, stream);
+}
+
+extern "C" int gatres_masked_loss(const float* out, const float* y, const uint8_t* mask, int32_t criterion, float* loss,
+                                  float* g_out, int32_t num_nodes, void* stream) {
   if (!out || !y || !mask || !loss || !g_out || num_nodes <= 0) return GATRES_E_BADARG;
-  hipLaunchKernelGGL(masked_mse_kernel, dim3(1), dim3(1024), 0, gatres_stream(stream), out, y, mask, loss, g_out,
-                     num_nodes);
+  hipStream_t st = gatres_stream(stream);
+  switch (criterion) {
+    case GATRES_LOSS_MSE:
+      hipLaunchKernelGGL(masked_loss_kernel<GATRES_LOSS_MSE>, dim3(1), dim3(1024), 0, st, out, y, mask, loss, g_out, num_nodes);
+      break;
+    case GATRES_LOSS_MAE:
+      hipLaunchKernelGGL(masked_loss_kernel<GATRES_LOSS_MAE>, dim3(1), dim3(1024), 0, st, out, y, mask, loss, g_out, num_nodes);
+      break;
+    case GATRES_LOSS_SCE:
+      hipLaunchKernelGGL(masked_loss_kernel<GATRES_LOSS_SCE>, dim3(1), dim3(1024), 0, st, out, y, mask, loss, g_out, num_nodes);
+      break;
+    default: return GATRES_E_BADARG;
+  }
   return gatres_launch_status();
 }
 

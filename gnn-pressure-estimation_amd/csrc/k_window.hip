@@ -131,6 +131,10 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
   // starts without its first cross-CU barrier and `local` is a compile-time truth -- the agent-scope forms of every granule
   // store and sweep are not compiled.  Every part still records its XCD id; the end of the launch compares (group_verify_local).
   constexpr bool XLOCAL = PH >= 0 && (PH & 0x4000) != 0;
+  // PH & 0x8000: a loss phase with another criterion than MSE (a.criterion: MAE or SCE, one uniform run-time branch inside
+  // gatres_loss_term); without it the instantiation's loss is MSE, a compile-time fact -- the MSE instantiations carry no
+  // trace of the other criteria.  PH < 0 reads a.criterion.
+  const bool mse_ = PH < 0 ? a.criterion == GATRES_LOSS_MSE : (PH & 0x8000) == 0;
   // Row padding of the MFMA stages' x operand tables (xA / xB forward, xG backward): 16 rows K floats apart share their banks,
   // K + 4 apart they do not (the x fragment reads of win_proj were 8- / 16-way conflicted).  Only where every writer and reader
   // of the table is a win_* stage of this instantiation: forward with the fallbacks compiled out (NOHUB), backward with
@@ -649,7 +653,7 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
         if (valid && (tid % G) == 0) {
           const float o = d + bias;
           a.out[node] = o;
-          if (fuse_loss) dml[r - rw.lo] = mk ? o - yv : 0.f;
+          if (fuse_loss) dml[r - rw.lo] = mse_ ? (mk ? o - yv : 0.f) : o;      // (other criteria: the prediction)
         }
       }
       if (fuse_loss) {
@@ -662,17 +666,37 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
           }
         }
         const float Mn = block_sum<THREADS>(cnt, ldsf);            // (its barriers also publish dml)
-        const float dv = tid < ow ? dml[tid] : 0.f;
-        float part_sum = block_sum<THREADS>(tid < ow ? fmaf(dv, dv, 0.f) : 0.f, ldsf);
-        if (tid == 0) {
-          a.loss_part[seg * M + part] = part_sum;
-          if (seg == 0 && part == 0) a.loss_part[a.num_segments * M] = Mn;
-        }
-        const float scale = Mn > 0.f ? 2.f / Mn : 0.f;
-        if (tid < ow) {
-          const float g = dv * scale;
-          a.g_out[ext_id(a.perm, n0 + rw.lo + tid)] = g;
-          dml[tid] = g;
+        if (mse_) {
+          const float dv = tid < ow ? dml[tid] : 0.f;
+          float part_sum = block_sum<THREADS>(tid < ow ? fmaf(dv, dv, 0.f) : 0.f, ldsf);
+          if (tid == 0) {
+            a.loss_part[seg * M + part] = part_sum;
+            if (seg == 0 && part == 0) a.loss_part[a.num_segments * M] = Mn;
+          }
+          const float scale = Mn > 0.f ? 2.f / Mn : 0.f;
+          if (tid < ow) {
+            const float g = dv * scale;
+            a.g_out[ext_id(a.perm, n0 + rw.lo + tid)] = g;
+            dml[tid] = g;
+          }
+        } else {      // (thread t: row lo + t, as the stand-alone pass -- the same terms, the same order, the same bits)
+          int node = 0;
+          float s = 0.f, term = 0.f;
+          if (tid < ow) {
+            node = ext_id(a.perm, n0 + rw.lo + tid);
+            if (a.mask[node]) term = gatres_loss_term(a.criterion, dml[tid], a.y[node], &s);
+          }
+          const float part_sum = block_sum<THREADS>(term, ldsf);
+          if (tid == 0) {
+            a.loss_part[seg * M + part] = part_sum;
+            if (seg == 0 && part == 0) a.loss_part[a.num_segments * M] = Mn;
+          }
+          const float inv = Mn > 0.f ? 1.f / Mn : 0.f;
+          if (tid < ow) {
+            const float g = s * inv;
+            a.g_out[node] = g;
+            dml[tid] = g;
+          }
         }
       }
     }
@@ -689,8 +713,13 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
     for (int r = rw.lo + tid; r < rw.hi; r += THREADS) {
       const int node = ext_id(a.perm, n0 + r);
       if (a.mask[node]) {
-        const float d = a.out[node] - a.y[node];
-        part_sum = fmaf(d, d, part_sum);
+        if (mse_) {
+          const float d = a.out[node] - a.y[node];
+          part_sum = fmaf(d, d, part_sum);
+        } else {
+          float s;
+          part_sum += gatres_loss_term(a.criterion, a.out[node], a.y[node], &s);
+        }
       }
     }
     part_sum = block_sum<THREADS>(part_sum, ldsf);
@@ -698,10 +727,20 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
       a.loss_part[seg * M + part] = part_sum;
       if (seg == 0 && part == 0) a.loss_part[a.num_segments * M] = Mn;
     }
-    const float scale = Mn > 0.f ? 2.f / Mn : 0.f;
-    for (int r = rw.lo + tid; r < rw.hi; r += THREADS) {
-      const int node = ext_id(a.perm, n0 + r);
-      a.g_out[node] = a.mask[node] ? (a.out[node] - a.y[node]) * scale : 0.f;
+    if (mse_) {
+      const float scale = Mn > 0.f ? 2.f / Mn : 0.f;
+      for (int r = rw.lo + tid; r < rw.hi; r += THREADS) {
+        const int node = ext_id(a.perm, n0 + r);
+        a.g_out[node] = a.mask[node] ? (a.out[node] - a.y[node]) * scale : 0.f;
+      }
+    } else {
+      const float inv = Mn > 0.f ? 1.f / Mn : 0.f;
+      for (int r = rw.lo + tid; r < rw.hi; r += THREADS) {
+        const int node = ext_id(a.perm, n0 + r);
+        float s = 0.f;
+        if (a.mask[node]) (void)gatres_loss_term(a.criterion, a.out[node], a.y[node], &s);
+        a.g_out[node] = s * inv;
+      }
     }
     __syncthreads();
     STAMP();
@@ -1235,11 +1274,12 @@ extern "C" __attribute__((visibility("hidden"))) int gatres_fused_launch_window(
     case 16: hipLaunchKernelGGL((gatres_window_kernel<16, 1024>), dim3(grid), dim3(1024), 0, st, a); break;
     case 32: {
       // the launch's compile-time facts (gatres_window_kernel): phases | 0x100 keep-in-LDS | 0x200 symmetric plan
-      // | 0x400 rows of at most MAXD entries | 0x800 part tables | 0x1000 parts of at most 64 rows
+      // | 0x400 rows of at most MAXD entries | 0x800 part tables | 0x1000 parts of at most 64 rows | 0x8000 not MSE
       int facts = (a.sym ? 0x200 : 0) | (a.facts & 0x1400) | ((a.ptab && a.ptab_m == a.M) ? 0x800 : 0);
       if ((a.facts & 0x2000) && facts == 0x1e00) facts |= 0x2000;      // (inference: only with every other fact -- one instantiation)
       if ((a.facts & 0x4000) && (facts & 0x1e00) == 0x1e00 && !a.safe_sync) facts |= 0x4000;      // (probed dispatch: likewise)
-      const int key = a.phases | (a.keep_lds ? 0x100 : 0) | (facts & gatres_knobs()->window_ph_mask);
+      const int key = a.phases | (a.keep_lds ? 0x100 : 0) | (facts & gatres_knobs()->window_ph_mask) |
+                      (a.criterion != GATRES_LOSS_MSE ? 0x8000 : 0);
       if (!gatres_knobs()->window_runtime_phases) {
         switch (key) {
           case 0x5f16: hipLaunchKernelGGL((gatres_window_kernel<32, 1024, 0x5f16>), dim3(grid), dim3(1024), 0, st, a); return gatres_launch_status();
@@ -1254,6 +1294,9 @@ extern "C" __attribute__((visibility("hidden"))) int gatres_fused_launch_window(
           case 0x3e02: hipLaunchKernelGGL((gatres_window_kernel<32, 1024, 0x3e02>), dim3(grid), dim3(1024), 0, st, a); return gatres_launch_status();
           case 0x1e02: hipLaunchKernelGGL((gatres_window_kernel<32, 1024, 0x1e02>), dim3(grid), dim3(1024), 0, st, a); return gatres_launch_status();
           case 0x1e04: hipLaunchKernelGGL((gatres_window_kernel<32, 1024, 0x1e04>), dim3(grid), dim3(1024), 0, st, a); return gatres_launch_status();
+          // the training launches of the headline-shaped plans with another criterion than MSE (0x8000)
+          case 0xdf16: hipLaunchKernelGGL((gatres_window_kernel<32, 1024, 0xdf16>), dim3(grid), dim3(1024), 0, st, a); return gatres_launch_status();
+          case 0x9f16: hipLaunchKernelGGL((gatres_window_kernel<32, 1024, 0x9f16>), dim3(grid), dim3(1024), 0, st, a); return gatres_launch_status();
           case 0x116: hipLaunchKernelGGL((gatres_window_kernel<32, 1024, 0x116>), dim3(grid), dim3(1024), 0, st, a); return gatres_launch_status();
           default: break;
         }

@@ -1,5 +1,5 @@
 // One reference training iteration (train.py:159-190) as a native launch sequence:
-// mask -> x[mask]=0 -> forward -> MSE on masked nodes -> backward -> Adam.  See gatres_train_step_t.
+// mask -> x[mask]=0 -> forward -> loss on masked nodes (MSE, MAE or SCE) -> backward -> Adam.  See gatres_train_step_t.
 #include "gatres_common.h"
 #include "gatres_layout.h"
 
@@ -89,6 +89,15 @@ extern "C" int gatres_train_step(const gatres_train_step_t* ts, void* stream) {
     return GATRES_E_BADARG;
   const int N = ts->graph->num_nodes;
   int rc = 0;
+  // the criterion (GATRES_FLAG_LOSS_*): formed where the forward phase forms the loss -- the window / whole-segment launch
+  // (a qualifier of GATRES_PHASE_LOSS) or gatres_masked_loss; the later phases only read the gradient it leaves in g_out
+  // and the loss partials it leaves in scratch
+  const int32_t crit_flags = ts->flags & (GATRES_FLAG_LOSS_MAE | GATRES_FLAG_LOSS_SCE);
+  if (crit_flags == (GATRES_FLAG_LOSS_MAE | GATRES_FLAG_LOSS_SCE)) return GATRES_E_BADARG;
+  const int32_t crit = crit_flags == GATRES_FLAG_LOSS_MAE ? GATRES_LOSS_MAE
+                       : crit_flags == GATRES_FLAG_LOSS_SCE ? GATRES_LOSS_SCE : GATRES_LOSS_MSE;
+  const int32_t loss_phase = GATRES_PHASE_LOSS | (crit == GATRES_LOSS_MAE ? GATRES_PHASE_LOSS_MAE : 0) |
+                             (crit == GATRES_LOSS_SCE ? GATRES_PHASE_LOSS_SCE : 0);
   const bool fused = !(ts->flags & GATRES_FLAG_PER_OP) && gatres_fused_supported(&ts->model, ts->graph);
   // GATRES_FLAG_MASK_NEXT can only be honoured where the parameter gradients fold (gatres_fused_finish_folds: their launch
   // leaves the step count / fault snapshot the sampling tail reads).  Refused BEFORE anything is enqueued: a caller that asked for the next
@@ -136,7 +145,7 @@ extern "C" int gatres_train_step(const gatres_train_step_t* ts, void* stream) {
     if (fwd && bwd) {
       rc = gatres_fused_run(&ts->model, ts->graph, ts->params, ts->x, ts->mask, ts->y, ts->out, ts->g_out, loss_part,
                             nullptr, ts->saved, ts->scratch,
-                            GATRES_PHASE_FORWARD | GATRES_PHASE_LOSS | GATRES_PHASE_BACKWARD, stream);
+                            GATRES_PHASE_FORWARD | loss_phase | GATRES_PHASE_BACKWARD, stream);
       if (rc || deferred) return rc;
       return fused_grads_and_update(ts, loss_part, adam, stream);
     }
@@ -144,7 +153,7 @@ extern "C" int gatres_train_step(const gatres_train_step_t* ts, void* stream) {
       rc = gatres_fused_run(&ts->model, ts->graph, ts->params, ts->x, ts->mask, nullptr, ts->out, nullptr, nullptr,
                             nullptr, ts->saved, ts->scratch, GATRES_PHASE_FORWARD, stream);
       if (rc) return rc;
-      rc = gatres_masked_mse(ts->out, ts->y, ts->mask, ts->loss, ts->g_out, N, stream);
+      rc = gatres_masked_loss(ts->out, ts->y, ts->mask, crit, ts->loss, ts->g_out, N, stream);
       if (rc) return rc;
     }
     if (bwd) {
@@ -175,7 +184,7 @@ extern "C" int gatres_train_step(const gatres_train_step_t* ts, void* stream) {
     rc = gatres_model_forward_per_op(&ts->model, ts->graph, ts->params, ts->x, ts->mask, ts->out, ts->saved, ts->scratch,
                               stream);
     if (rc) return rc;
-    rc = gatres_masked_mse(ts->out, ts->y, ts->mask, ts->loss, ts->g_out, N, stream);
+    rc = gatres_masked_loss(ts->out, ts->y, ts->mask, crit, ts->loss, ts->g_out, N, stream);
     if (rc) return rc;
   }
   if (ts->phases & GATRES_PHASE_BACKWARD) {

@@ -5,7 +5,9 @@ the flat fp32 gradient (RCCL over xGMI on the GPU box: torch.distributed backend
 The reference is single-process (train.py:306-309); this is the scheme its DataLoader batches extend to:
 a global batch of B graphs is split into `world` contiguous shards of B/world graphs.  Because every graph
 contributes the same number of masked nodes (int(n_g * mask_rate), utils/auxil.py:154), the mean of the per-rank
-mean-squared errors equals the global-batch loss, and the average of per-rank gradients equals its gradient.
+losses equals the global-batch loss, and the average of per-rank gradients equals its gradient.  This holds for each of
+the reference's criteria (``GATResTrainer(criterion=...)``: MSE, MAE, SCE): each is a mean of per-node terms over the
+masked nodes, and equal per-rank counts make the mean of the per-rank means the global mean.
 
 ``GATResTrainer`` drives its multi-rank step through ``run_data_parallel_step`` below; ``tests/test_ddp_gloo.py`` runs
 the very same function under two gloo ranks with the oracle as the per-rank compute.

@@ -56,6 +56,33 @@ def calculate_r2(y_pred, y_true):
     return calculate_correlation_coefficient(y_pred, y_true) ** 2
 
 
+# ---- training criteria (train.py:354-368, --criterion {mse,mae,sce}) ---------------------------------------------------
+def sce_loss(x: torch.Tensor, y: torch.Tensor, alpha: int = 3) -> torch.Tensor:
+    """The reference's scaled cosine error: ``mean((1 - <x^, y^>)^alpha)`` with ``x^``, ``y^`` the rows of ``x``, ``y``
+    L2-normalised along the last dimension (``F.normalize``, eps 1e-12).  On the masked predictions of a GATRes model
+    (``[M, 1]``) ``x^`` is +-1 wherever ``|x| >= 1e-12``, so the loss is flat there: its gradient is zero (in exact
+    arithmetic; torch's fp32 autograd returns rounding noise) and training with it moves the parameters by weight decay only.
+    ``GATResTrainer(criterion="sce")`` computes the exact value (gatres.h: GATRES_LOSS_SCE)."""
+    xn = F.normalize(x, p=2, dim=-1)
+    yn = F.normalize(y, p=2, dim=-1)
+    return torch.pow(1.0 - torch.sum(xn * yn, dim=-1), alpha).mean()
+
+
+CRITERIA = ("mse", "mae", "sce")
+
+
+def get_criterion(name: str) -> Callable:
+    """The callable ``train.py --criterion name`` trains and validates with: ``nn.MSELoss()``, ``nn.L1Loss()`` or
+    ``sce_loss``.  ``test_one_epoch(criterion=get_criterion(name))`` gives the reference's validation loss."""
+    if name == "mse":
+        return torch.nn.MSELoss(reduction="mean")
+    if name == "mae":
+        return torch.nn.L1Loss(reduction="mean")
+    if name == "sce":
+        return sce_loss
+    raise KeyError(f"criterion {name} is not supported (choices: {', '.join(CRITERIA)})")
+
+
 def get_metric_fn_collection(prefix: str) -> Dict[str, Callable]:
     """auxil.py:185-203: same keys, same order."""
     return {f"{prefix}_error": calculate_rel_error, f"{prefix}_0.1": partial(calculate_accuracy, threshold=0.1),
@@ -289,7 +316,8 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
     stream gives it, passes ``seed=epoch``.
     ``norm_type``: ``None`` takes the store's (``znorm``: descaled with its mean / std; ``unused``: not descaled).
     Only ``MSELoss`` and ``get_metric_fn_collection(prefix)`` are computed; anything else passed as ``criterion`` /
-    ``metric_fn_dict`` is refused.  ``_capture`` (tests): a list that receives ``(mask, out, x, num_graphs)`` per batch."""
+    ``metric_fn_dict`` is refused -- ``get_criterion("mae")`` / ``("sce")`` included, whatever criterion the model was trained
+    with (the moment record carries no such sums): their validation loss comes from ``test_one_epoch``.  ``_capture`` (tests): a list that receives ``(mask, out, x, num_graphs)`` per batch."""
     from . import _native
     _check_reference_metrics(criterion, metric_fn_dict, prefix)
     if batch_size <= 0:

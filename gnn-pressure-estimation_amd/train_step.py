@@ -1,6 +1,6 @@
 """Native training step for GATRes: the reference's inner loop body (train.py:159-190) as one stream-ordered
-launch sequence -- device mask sampling (auxil.py:143-182), ``x[mask] = 0``, forward, MSE on the masked nodes,
-backward, [RCCL gradient all-reduce], Adam(lr, weight_decay) -- captured once into a hipGraph and replayed.
+launch sequence -- device mask sampling (auxil.py:143-182), ``x[mask] = 0``, forward, the criterion (MSE, MAE or SCE:
+train.py --criterion) on the masked nodes, backward, [RCCL gradient all-reduce], Adam(lr, weight_decay) -- captured once into a hipGraph and replayed.
 
 Data-parallel: one process per GPU, snapshots sharded by graph across ranks, every rank holds the same topology
 plan and an identical replica of the flat parameter vector; the only exchange is ONE all-reduce of the flat fp32
@@ -24,6 +24,8 @@ from .graph_plan import GraphPlan
 PHASE_MASK, PHASE_FORWARD, PHASE_BACKWARD, PHASE_ADAM = 1, 2, 4, 8
 PART_FIRST, PART_LAST, PART_REDUCE = 1, 2, 4
 FLAG_PER_OP, FLAG_WT_VALID, FLAG_GRADS_DEFERRED, FLAG_GRADS_ONLY, FLAG_MASK_NEXT = 1, 2, 4, 8, 16
+FLAG_LOSS_MAE, FLAG_LOSS_SCE = 32, 64
+_CRITERION_FLAGS = {"mse": 0, "mae": FLAG_LOSS_MAE, "sce": FLAG_LOSS_SCE}
 MAX_CACHED_GRAPHS = 40          # floor of the captured-step cache; bind_batches() sizes it from the number of bound batches
 
 
@@ -107,11 +109,19 @@ class GATResTrainer:
                  process_group=None, use_graph: bool = True, fused: bool = True,
                  force_collective_path: bool = False, targets_are_inputs: bool = False,
                  blocks_per_bucket: int = 5, use_gradient_clipping: bool = False, percentile: float = 10.0,
-                 grad_history_capacity: int = 1 << 16, _share_state_with: Optional["GATResTrainer"] = None):
+                 grad_history_capacity: int = 1 << 16, criterion: str = "mse",
+                 _share_state_with: Optional["GATResTrainer"] = None):
         """``use_gradient_clipping`` / ``percentile``: the reference's ``--use_gradient_clipping True --percentile p``
         (train.py:611-617): AutoClip in front of every Adam update -- the gradient is clipped to the p-th percentile of all
         gradient norms seen so far (``grad_norm_history()``).  ``grad_history_capacity``: entries the device history holds
-        before it is grown."""
+        before it is grown.
+
+        ``criterion``: the reference's ``--criterion`` (train.py:354-368) -- ``"mse"`` (nn.MSELoss), ``"mae"`` (nn.L1Loss) or
+        ``"sce"`` (evaluation.sce_loss), over the masked nodes; every step entry point trains with it and ``loss`` is its
+        value.  Fixed for the trainer's lifetime (``criterion`` is read-only)."""
+        if criterion not in _CRITERION_FLAGS:
+            raise ValueError(f"criterion must be one of {sorted(_CRITERION_FLAGS)} (got {criterion!r})")
+        self._criterion = criterion
         self.lib = _native.load()
         if not 0.0 <= float(percentile) <= 100.0:
             raise ValueError(f"percentile must lie in [0, 100] (got {percentile})")
@@ -276,7 +286,8 @@ class GATResTrainer:
             self.num_graphs, phases, self.mask_rate, self.seed, self.out.data_ptr(), self.g_out.data_ptr(),
             (self.loss if loss is None else loss).data_ptr(), self.saved.data_ptr(), self.scratch.data_ptr(), h["lr"], h["beta1"], h["beta2"],
             h["eps"], h["weight_decay"], 1.0 / self.world,
-            (0 if self.fused else FLAG_PER_OP) | (FLAG_WT_VALID if wt_valid else 0) | flags, self.hp.data_ptr(),
+            (0 if self.fused else FLAG_PER_OP) | (FLAG_WT_VALID if wt_valid else 0) | _CRITERION_FLAGS[self._criterion] | flags,
+            self.hp.data_ptr(),
             block_lo, block_hi, mask_next.data_ptr(), C.pointer(self._clip.c) if self._clip is not None else None)
 
     def _count_native_update(self) -> None:
@@ -336,6 +347,11 @@ class GATResTrainer:
             return True
         self._mask_sig = None
         return False
+
+    @property
+    def criterion(self) -> str:
+        """The training criterion this trainer's steps use: ``"mse"``, ``"mae"`` or ``"sce"`` (fixed at construction)."""
+        return self._criterion
 
     @property
     def num_captured_graphs(self) -> int:
@@ -1097,7 +1113,7 @@ class GATResTrainer:
                               mask_rate=self.mask_rate, seed=0, process_group=self.pg, use_graph=self.use_graph,
                               fused=self.fused, force_collective_path=self.split and self.world == 1,
                               targets_are_inputs=True, blocks_per_bucket=self.blocks_per_bucket,
-                              _share_state_with=self)
+                              criterion=self._criterion, _share_state_with=self)
             t.seed = self.seed
             self._siblings[num_graphs] = t
         t.mask_rate = self.mask_rate

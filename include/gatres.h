@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GATRES_ABI_VERSION 8
+#define GATRES_ABI_VERSION 9
 
 #define GATRES_E_BADARG      (-1)  /* null pointer, negative size, misaligned pointer            */
 #define GATRES_E_UNSUPPORTED (-2)  /* width not supported by the gfx950 kernels                  */
@@ -312,6 +312,20 @@ int gatres_masked_metrics(const float* out, const float* y, const uint8_t* mask,
 int gatres_masked_mse(const float* out, const float* y, const uint8_t* mask, float* loss, float* g_out,
                       int32_t num_nodes, void* stream);
 
+/* Training criteria of the reference (train.py --criterion), over the M masked nodes, d = out - y:
+ *   GATRES_LOSS_MSE  nn.MSELoss():  loss = sum d^2 / M,   g_out = 2 d / M
+ *   GATRES_LOSS_MAE  nn.L1Loss():   loss = sum |d| / M,   g_out = sign(d) / M  (sign(0) = 0)
+ *   GATRES_LOSS_SCE  sce_loss(alpha=3) of F.normalize(., dim=-1) on [M, 1] tensors, eps = 1e-12:
+ *                    o^ = out / max(|out|, eps), y^ = y / max(|y|, eps), t = 1 - o^ y^;  loss = sum t^3 / M,
+ *                    g_out = |out| < eps ? -3 t^2 y^ / (eps M) : 0  (o^ is +-1 elsewhere: the gradient is zero there)
+ * Unmasked nodes get g_out = 0; M == 0 gives loss NaN and g_out = 0. */
+#define GATRES_LOSS_MSE 0
+#define GATRES_LOSS_MAE 1
+#define GATRES_LOSS_SCE 2
+/* The loss of `criterion` over the masked nodes and its gradient (GATRES_LOSS_MSE: the same bits as gatres_masked_mse). */
+int gatres_masked_loss(const float* out, const float* y, const uint8_t* mask, int32_t criterion, float* loss, float* g_out,
+                       int32_t num_nodes, void* stream);
+
 /* torch.optim.Adam step (weight_decay folded into the gradient), step counter on the device:
  * step_counter is device uint64[2] = {step, internal ticket (must start at 0)}; the kernel uses step+1 for the
  * bias corrections and then increments step.  grad_scale multiplies the gradient first (1/world_size). */
@@ -486,6 +500,11 @@ int gatres_model_reduce_grads(const gatres_model_t* m, const gatres_graph_t* g, 
  * call gatres_fused_prepare_backward (one small launch) after the parameters last changed.
  * ------------------------------------------------------------------------------------------------------ */
 #define GATRES_PHASE_LOSS 16
+/* Qualifiers of GATRES_PHASE_LOSS in gatres_fused_run's `phases`: the loss phase forms that criterion's loss and gradient
+ * (GATRES_LOSS_MAE / GATRES_LOSS_SCE, see gatres_masked_loss) instead of the masked MSE.  At most one; only with
+ * GATRES_PHASE_LOSS (else GATRES_E_BADARG). */
+#define GATRES_PHASE_LOSS_MAE 32
+#define GATRES_PHASE_LOSS_SCE 64
 int gatres_fused_supported(const gatres_model_t* m, const gatres_graph_t* g);
 /* Workgroups (CUs) that carry one segment in the fused launches (1, 2, 4 or 8); 0 if the fused path is unavailable. */
 int gatres_fused_cus_per_segment(const gatres_model_t* m, const gatres_graph_t* g);
@@ -589,7 +608,8 @@ int gatres_autoclip_adam_step(float* params, const float* grads, float* exp_avg,
 /* --------------------------------------------------------------------------------------------------------
  * One reference training iteration (train.py:159-190) enqueued natively:
  *   PHASE_MASK     device mask sampler (utils/auxil.py:166-182) -- skipped when node_ptr == NULL (caller's mask)
- *   PHASE_FORWARD  x[mask] = 0 ; out = model(x) ; loss = MSE(out[mask], y[mask]) and d loss / d out
+ *   PHASE_FORWARD  x[mask] = 0 ; out = model(x) ; loss = criterion(out[mask], y[mask]) and d loss / d out (MSE unless
+ *                  GATRES_FLAG_LOSS_MAE / GATRES_FLAG_LOSS_SCE)
  *   PHASE_BACKWARD grads = d loss / d params
  *   PHASE_ADAM     torch.optim.Adam(lr, weight_decay) update, step counter on the device
  * `phases` selects which of them a call enqueues, so a data-parallel caller can run its gradient all-reduce
@@ -650,6 +670,10 @@ typedef struct gatres_train_step {
 /* The transposed conv weights in `scratch` already match `params`: true right after a fused PHASE_ADAM step on the
  * same scratch (its Adam pass rewrites them) as long as nobody else has touched the parameters; skips the transposes. */
 #define GATRES_FLAG_WT_VALID 2
+/* The training criterion (gatres_masked_loss): GATRES_FLAG_LOSS_MAE -> nn.L1Loss, GATRES_FLAG_LOSS_SCE -> sce_loss; neither:
+ * MSE.  Both: GATRES_E_BADARG.  Every path of the step honours it (the loss is formed in the forward phase). */
+#define GATRES_FLAG_LOSS_MAE 32
+#define GATRES_FLAG_LOSS_SCE 64
 
 int gatres_train_step(const gatres_train_step_t* ts, void* stream);
 
