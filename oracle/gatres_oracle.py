@@ -212,6 +212,41 @@ def gatres_forward(p: Dict[str, torch.Tensor], x, edge_index, num_blocks: Option
     return x @ p["lin1.weight"].t() + p["lin1.bias"]
 
 
+def logit_regime(p: Dict[str, torch.Tensor], x, edge_index, num_blocks: Optional[int] = None, gap: float = 90.0):
+    """How far the attention logits of every GATConv of the fp64 forward spread: one dict per conv (forward order) with
+    ``max_gap`` (the largest top-two logit gap of any row and head), ``share_above`` (the share of rows with two or more
+    entries whose top-two gap exceeds ``gap``), ``neg_max_rows`` (rows whose maximum logit is below -``gap``) and ``max_abs``
+    (the largest |logit|).  At unit scale every gap is a few units; a wrong softmax maximum only shows at gaps of ~90 or
+    more (fp32 exp overflows beyond ~88 and underflows below ~-104), so tests of that regime assert these figures."""
+    p64 = {k: v.detach().double() for k, v in p.items()}
+    figures = []
+
+    def recording_conv(xx, ei, weight, att_src, att_dst, bias, heads, concat):
+        n = xx.shape[0]
+        h = (xx @ weight.t()).view(n, heads, -1)
+        a_s, a_d = (h * att_src).sum(-1), (h * att_dst).sum(-1)
+        e = add_self_loops(remove_self_loops(ei), n)
+        s = torch.nn.functional.leaky_relu(a_s[e[0]] + a_d[e[1]], NEG_SLOPE)
+        idx = e[1].view(-1, 1).expand(-1, heads)
+        top = torch.full((n, heads), float("-inf"), dtype=s.dtype).scatter_reduce(0, idx, s, "amax", include_self=True)
+        # second largest: drop ONE occurrence of each row's maximum (a tie leaves a gap of 0)
+        first = torch.full((n, heads), len(s), dtype=torch.int64)
+        pos = torch.arange(len(s)).view(-1, 1).expand(-1, heads)
+        first = first.scatter_reduce(0, idx, torch.where(s == top[e[1]], pos, len(s)), "amin", include_self=True)
+        rest = torch.where(pos == first[e[1]], torch.full_like(s, float("-inf")), s)
+        second = torch.full((n, heads), float("-inf"), dtype=s.dtype).scatter_reduce(0, idx, rest, "amax", include_self=True)
+        multi = torch.bincount(e[1], minlength=n) > 1
+        g = (top - second)[multi]
+        figures.append(dict(max_gap=float(g.max()) if g.numel() else 0.0,
+                            share_above=float((g > gap).any(-1).double().mean()) if g.numel() else 0.0,
+                            neg_max_rows=int((top < -gap).any(-1).sum()), max_abs=float(s.abs().max())))
+        return gat_conv(xx, ei, weight, att_src, att_dst, bias, heads, concat)
+
+    with torch.no_grad():
+        gatres_forward(p64, x.double(), edge_index, num_blocks=num_blocks, conv=recording_conv)
+    return figures
+
+
 # ----------------------------------------------------------------------------------------------
 # bf16 storage mode (BASELINE config 3): the same model with the build's rounding points
 # ----------------------------------------------------------------------------------------------
