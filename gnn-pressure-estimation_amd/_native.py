@@ -46,6 +46,13 @@ class GatresAutoClip(C.Structure):
                 ("partials_cap", C.c_int32), ("reserved", C.c_int32), ("percentile", C.c_double)]
 
 
+class GatresEpochConfig(C.Structure):
+    """gatres_epoch_config_t"""
+    _fields_ = [("min_delta", C.c_double), ("factor", C.c_double), ("threshold", C.c_double), ("min_lr", C.c_double),
+                ("eps", C.c_double), ("patience", C.c_int32), ("scheduler_patience", C.c_int32), ("use_scheduler", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class GatresModel(C.Structure):
     """gatres_model_t"""
     _fields_ = [("num_blocks", C.c_int32), ("nc", C.c_int32), ("act_dtype", C.c_int32), ("flags", C.c_int32)]
@@ -141,12 +148,16 @@ SIGNATURES = {
     "gatres_autoclip_partials": (_I32, [_I64]),
     "gatres_autoclip_adam_step": (C.c_int, [_P] * 5 + [_I64] + [_F64] * 5 + [_F32, _P, _P]),
     "gatres_train_step": (C.c_int, [_P, _P]),
+    "gatres_epoch_control": (C.c_int, [_P, _P, _P, _P, _I32, _P, C.POINTER(GatresEpochConfig), _P, _P, _P, _I32, _P]),
+    "gatres_epoch_val_sums": (C.c_int, [_P, _P, _P, _I32, _P, _P]),
+    "gatres_snapshot_if": (C.c_int, [_P] * 9 + [_I64, _P]),
     "gatres_version": (C.c_char_p, []),
 }
 
 
 ABI_VERSION = 9                # GATRES_ABI_VERSION of include/gatres.h
 LOSS_MSE, LOSS_MAE, LOSS_SCE = 0, 1, 2              # GATRES_LOSS_* (gatres_masked_loss)
+EPOCH_STATE, EPOCH_RECORD = 10, 16                  # GATRES_EPOCH_STATE, GATRES_EPOCH_RECORD
 CRITERIA = {"mse": LOSS_MSE, "mae": LOSS_MAE, "sce": LOSS_SCE}      # the reference's train.py --criterion choices
 
 

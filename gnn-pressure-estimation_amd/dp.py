@@ -45,6 +45,14 @@ def broadcast_params_(flat_params: torch.Tensor, src: int = 0, group=None) -> to
     return flat_params
 
 
+def all_reduce_sums_(sums: torch.Tensor, group=None) -> torch.Tensor:
+    """SUM all-reduce of a few scalars in place (``GATResTrainer.fit``: the epoch's four loss sums, one collective per epoch),
+    after which every rank holds the same values and takes the same decision from them."""
+    if world_size(group) > 1:
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+    return sums
+
+
 class BucketedAllReduce:
     """SUM all-reduce of contiguous ranges ("buckets") of one flat gradient vector, launched as soon as a range is
     final.  ``launch`` is asynchronous: with the nccl (= RCCL) backend the collective runs on the process group's own

@@ -286,6 +286,40 @@ def _eval_plan(model, store, num_graphs: int) -> _EvalPlan:
     return P.refresh(model)
 
 
+def _enqueue_stage(lib, store, P: _EvalPlan, rows: torch.Tensor, mask_rate: float, seed64: int, step_ptr: int, req_dev,
+                   num_required: int, stream) -> None:
+    """Collation of the snapshots ``rows`` into the plan's ``x`` + the batch's mask (sampler step read from ``step_ptr``)."""
+    from . import _native
+    _native.check(lib.gatres_stage_rows_mask_required(
+        store.data.data_ptr(), rows.data_ptr(), store.nodes_per_graph, P.x.data_ptr(), None, P.node_ptr.data_ptr(), P.num_graphs,
+        float(mask_rate), seed64, step_ptr, _native.ptr(req_dev), num_required, P.mask.data_ptr(), stream),
+        "gatres_stage_rows_mask_required")
+
+
+def _enqueue_forward(lib, flat: torch.Tensor, P: _EvalPlan, stream) -> None:
+    """The inference forward on the staged batch, as ``model(x1, edge_index)`` with ``x1[mask] = 0`` computes it."""
+    from . import _native
+    st = P.state
+    _native.check(lib.gatres_model_forward(st["mref_infer"], st["gref"], flat.data_ptr(), P.x.data_ptr(), P.mask.data_ptr(),
+                                           P.out.data_ptr(), _native.ptr(P.saved), st["scratch"].data_ptr(), stream),
+                  "gatres_model_forward")
+
+
+def _enqueue_moments(lib, P: _EvalPlan, scale: float, offset: float, table: torch.Tensor, slot: int, stream) -> None:
+    from . import _native
+    _native.check(lib.gatres_masked_metrics(P.out.data_ptr(), P.x.data_ptr(), P.mask.data_ptr(), P.num_nodes, scale, offset,
+                                            table.data_ptr(), slot, table.shape[0], None, stream), "gatres_masked_metrics")
+
+
+def _store_descale(store, norm_type: Optional[str]) -> Tuple[float, float]:
+    norm_type = store.norm_type if norm_type is None else norm_type
+    if norm_type == "znorm":
+        return float(store.std), float(store.mean)
+    if norm_type == "unused":
+        return 1.0, 0.0
+    raise ValueError(f"norm_type={norm_type!r}: a SnapshotStore is z-normalised ('znorm') or not normalised ('unused')")
+
+
 def _mix_seed(seed: int, *salt: int) -> int:
     z = int(seed) & 0xFFFFFFFFFFFFFFFF
     for s in salt:
@@ -322,13 +356,7 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
     _check_reference_metrics(criterion, metric_fn_dict, prefix)
     if batch_size <= 0:
         raise ValueError("batch_size must be positive")
-    norm_type = store.norm_type if norm_type is None else norm_type
-    if norm_type == "znorm":
-        scale, offset = float(store.std), float(store.mean)
-    elif norm_type == "unused":
-        scale, offset = 1.0, 0.0
-    else:
-        raise ValueError(f"norm_type={norm_type!r}: a SnapshotStore is z-normalised ('znorm') or not normalised ('unused')")
+    scale, offset = _store_descale(store, norm_type)
     npg, S = store.nodes_per_graph, len(store)
     if S == 0:
         raise ValueError("empty store")
@@ -365,18 +393,12 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
         seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF
 
         def forward(P: _EvalPlan) -> None:
-            st = P.state
-            _native.check(lib.gatres_model_forward(st["mref_infer"], st["gref"], flat.data_ptr(), P.x.data_ptr(),
-                                                   P.mask.data_ptr(), P.out.data_ptr(), _native.ptr(P.saved),
-                                                   st["scratch"].data_ptr(), stream), "gatres_model_forward")
+            _enqueue_forward(lib, flat, P, stream)
 
         for b, g in enumerate(sizes):
             P = plans[g]
             rows = order[b * batch_size: b * batch_size + g]
-            _native.check(lib.gatres_stage_rows_mask_required(
-                store.data.data_ptr(), rows.data_ptr(), npg, P.x.data_ptr(), None, P.node_ptr.data_ptr(), g,
-                float(mask_rate), seed64, steps_dev.data_ptr() + 8 * b, _native.ptr(req_dev), len(required),
-                P.mask.data_ptr(), stream), "gatres_stage_rows_mask_required")
+            _enqueue_stage(lib, store, P, rows, mask_rate, seed64, steps_dev.data_ptr() + 8 * b, req_dev, len(required), stream)
             if b == 0:
                 for _ in range(max(int(gpu_warmup_times), 0)):
                     forward(P)
@@ -385,9 +407,7 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
             forward(P)
             end.record()
             events.append((start, end))
-            _native.check(lib.gatres_masked_metrics(P.out.data_ptr(), P.x.data_ptr(), P.mask.data_ptr(), P.num_nodes,
-                                                    scale, offset, table.data_ptr(), b, nb, None, stream),
-                          "gatres_masked_metrics")
+            _enqueue_moments(lib, P, scale, offset, table, b, stream)
             if _capture is not None:
                 _capture.append((P.mask.clone(), P.out.clone(), P.x.clone(), g))
         torch.cuda.synchronize(dev)
@@ -401,6 +421,64 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
     metrics[key + "_time"] = timer.compute_time(S)
     metrics[key + "_throughput"] = timer.compute_throughput(S)
     return loss, {k + postfix: v for k, v in metrics.items()}
+
+
+class _ValidationPass:
+    """The validation epoch of ``GATResTrainer.fit``: ``evaluate_store``'s launches per batch -- staging + mask, inference
+    forward, masked-metric moments -- plus, for the ``mae`` / ``sce`` criteria, one ``gatres_masked_loss`` launch whose fp32
+    loss goes into a per-batch array (the reference's ``criterion(y_pred, y_true)``).  Nothing is read back and nothing
+    synchronises: the moment table, the loss array and the per-batch graph counts stay on the device for
+    ``gatres_epoch_control``.  Everything static (row order, sampler steps, graph counts, tables) is made once; with the same
+    ``seed`` the moment table is bit for bit the one ``evaluate_store(seed=seed, gpu_warmup_times=0)`` forms."""
+
+    def __init__(self, model, store, batch_size: int, mask_rate: float, criterion: str = "mse"):
+        from . import _native
+        if batch_size <= 0:
+            raise ValueError("batch_size must be positive")
+        S = len(store)
+        if S == 0:
+            raise ValueError("empty store")
+        if int(store.nodes_per_graph * mask_rate) <= 0:
+            raise ValueError("mask length must be positive")
+        self.model, self.store, self.batch_size, self.mask_rate = model, store, int(batch_size), float(mask_rate)
+        self.criterion = _native.CRITERIA[criterion]
+        self.scale, self.offset = _store_descale(store, None)
+        dev = store.device
+        nb = (S + batch_size - 1) // batch_size
+        self.sizes = [min(batch_size, S - b * batch_size) for b in range(nb)]
+        self.order = torch.arange(S, dtype=torch.int64, device=dev)
+        self.steps = torch.arange(nb, dtype=torch.int64, device=dev)          # the sampler's step of a batch: its index
+        self.graphs = torch.full((nb,), batch_size, dtype=torch.int32, device=dev)
+        self.graphs[nb - 1:].fill_(self.sizes[-1])
+        self.table = torch.zeros((nb, METRICS_RECORD), dtype=torch.float64, device=dev)
+        self.losses = self.g_out = None
+        if self.criterion != _native.LOSS_MSE:
+            self.losses = torch.zeros(nb, dtype=torch.float32, device=dev)
+            self.g_out = torch.empty(batch_size * store.nodes_per_graph, dtype=torch.float32, device=dev)
+
+    def enqueue(self, seed: int, _capture: Optional[List] = None) -> None:
+        from . import _native
+        model, store = self.model, self.store
+        flat = model.flat_parameters
+        if flat.device != store.device:
+            raise ValueError(f"model is on {flat.device}, the store on {store.device}")
+        lib = _native.load()
+        seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF
+        with torch.cuda.device(store.device):
+            stream = _native.current_stream(store.device)
+            plans = {g: _eval_plan(model, store, g) for g in sorted(set(self.sizes))}
+            for b, g in enumerate(self.sizes):
+                P = plans[g]
+                rows = self.order[b * self.batch_size: b * self.batch_size + g]
+                _enqueue_stage(lib, store, P, rows, self.mask_rate, seed64, self.steps.data_ptr() + 8 * b, None, 0, stream)
+                _enqueue_forward(lib, flat, P, stream)
+                _enqueue_moments(lib, P, self.scale, self.offset, self.table, b, stream)
+                if self.losses is not None:
+                    _native.check(lib.gatres_masked_loss(P.out.data_ptr(), P.x.data_ptr(), P.mask.data_ptr(), self.criterion,
+                                                         self.losses.data_ptr() + 4 * b, self.g_out.data_ptr(), P.num_nodes,
+                                                         stream), "gatres_masked_loss")
+                if _capture is not None:
+                    _capture.append((P.mask.clone(), P.out.clone(), P.x.clone(), g))
 
 
 def evaluate_store_trials(model: torch.nn.Module, store, batch_size: int, num_test_trials: int, mask_rate: float,

@@ -325,20 +325,25 @@ def load_checkpoint(path: str, model: torch.nn.Module, map_location=None):
     return model, cp
 
 
-def adam_state_dict(trainer) -> dict:
+def adam_state_dict(trainer, *, exp_avg: Optional[torch.Tensor] = None, exp_avg_sq: Optional[torch.Tensor] = None,
+                    step: Optional[int] = None, lr: Optional[float] = None) -> dict:
     """``torch.optim.Adam(model.parameters(), ...).state_dict()`` equivalent of a ``GATResTrainer``'s flat moments: one
-    state entry per parameter in ``model.parameters()`` order (train.py:348, :436)."""
+    state entry per parameter in ``model.parameters()`` order (train.py:348, :436).  The keyword arguments put other flat
+    moments, another step count or another learning rate in place of the trainer's current ones (``GATResTrainer.fit``: the
+    best epoch's state kept on the device)."""
     params = trainer.model._param_list
-    step = int(trainer.step_counter[0].item())
+    exp_avg = trainer.exp_avg if exp_avg is None else exp_avg
+    exp_avg_sq = trainer.exp_avg_sq if exp_avg_sq is None else exp_avg_sq
+    step = int(trainer.step_counter[0].item()) if step is None else int(step)
     state, off = {}, 0
     for i, p in enumerate(params):
         n = p.numel()
         state[i] = {"step": torch.tensor(float(step)),
-                    "exp_avg": trainer.exp_avg[off:off + n].view(p.shape).clone(),
-                    "exp_avg_sq": trainer.exp_avg_sq[off:off + n].view(p.shape).clone()}
+                    "exp_avg": exp_avg[off:off + n].view(p.shape).clone(),
+                    "exp_avg_sq": exp_avg_sq[off:off + n].view(p.shape).clone()}
         off += n
     h = trainer.hparams
-    group = {"lr": h["lr"], "betas": (h["beta1"], h["beta2"]), "eps": h["eps"], "weight_decay": h["weight_decay"],
+    group = {"lr": h["lr"] if lr is None else float(lr), "betas": (h["beta1"], h["beta2"]), "eps": h["eps"], "weight_decay": h["weight_decay"],
              "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
              "fused": None, "params": list(range(len(params)))}
     return {"state": state, "param_groups": [group]}

@@ -677,6 +677,80 @@ typedef struct gatres_train_step {
 
 int gatres_train_step(const gatres_train_step_t* ts, void* stream);
 
+/* --------------------------------------------------------------------------------------------------------
+ * The epoch boundary of the reference's training loop (train.py:426-511) on the device: GATResTrainer.fit.
+ * ------------------------------------------------------------------------------------------------------ */
+typedef struct gatres_epoch_config {
+  double min_delta;           /* EarlyStopping(mode="min", min_delta, patience): compared in fp32                        */
+  double factor;              /* ReduceLROnPlateau(mode="min", patience=scheduler_patience): torch's defaults are        */
+  double threshold;           /*   factor 0.1, threshold 1e-4 (relative), min_lr 0, eps 1e-8, cooldown 0 (fixed here)    */
+  double min_lr;
+  double eps;
+  int32_t patience;           /* 0: early stopping never stops                                                            */
+  int32_t scheduler_patience;
+  int32_t use_scheduler;      /* 0: the learning rate is left alone                                                       */
+  int32_t reserved;
+} gatres_epoch_config_t;
+
+/* The controller's persistent state: GATRES_EPOCH_STATE doubles.  Initial value: all 0 except BEST_LOSS = SCHED_BEST = +inf. */
+#define GATRES_EPOCH_STATE 10
+#define GATRES_EPOCH_S_EPOCH 0        /* epochs decided so far                                   */
+#define GATRES_EPOCH_S_BEST_LOSS 1
+#define GATRES_EPOCH_S_BEST_EPOCH 2
+#define GATRES_EPOCH_S_ES_HAS_BEST 3  /* EarlyStopping.best is set                               */
+#define GATRES_EPOCH_S_ES_BEST 4      /* an fp32 value                                           */
+#define GATRES_EPOCH_S_ES_BAD 5
+#define GATRES_EPOCH_S_SCHED_BEST 6
+#define GATRES_EPOCH_S_SCHED_BAD 7
+#define GATRES_EPOCH_S_IMPROVED 8     /* the last epoch improved best_loss: gatres_snapshot_if's flag */
+#define GATRES_EPOCH_S_STOPPED 9
+/* One history record per epoch: GATRES_EPOCH_RECORD doubles. */
+#define GATRES_EPOCH_RECORD 16
+#define GATRES_EPOCH_R_EPOCH 0
+#define GATRES_EPOCH_R_TR_LOSS 1
+#define GATRES_EPOCH_R_VAL_LOSS 2
+#define GATRES_EPOCH_R_LR_USED 3      /* hp[0] during the epoch                                  */
+#define GATRES_EPOCH_R_LR_AFTER 4     /* hp[0] after the scheduler's step                        */
+#define GATRES_EPOCH_R_IMPROVED 5
+#define GATRES_EPOCH_R_BEST_LOSS 6
+#define GATRES_EPOCH_R_BEST_EPOCH 7
+#define GATRES_EPOCH_R_ES_BAD 8
+#define GATRES_EPOCH_R_STOP 9
+#define GATRES_EPOCH_R_SCHED_BAD 10
+#define GATRES_EPOCH_R_SCHED_BEST 11
+#define GATRES_EPOCH_R_ES_BEST 12
+#define GATRES_EPOCH_R_VAL_GRAPHS 13  /* [14..15] 0                                              */
+
+/* The decision of one epoch as ONE single-wave launch, in the reference's order:
+ *   1. tr_loss = train_sums[0] / train_sums[1] (the epoch's fp64 loss sum and graph count); val_loss = sum_b loss_b g_b / n,
+ *      accumulated in fp64 batch by batch (product and sum each rounded), n = sum_b g_b, g_b = val_graphs[b], and
+ *      loss_b = val_table[b][1] / val_table[b][0] (moment records of gatres_masked_metrics) or val_losses[b] (fp32, e.g.
+ *      gatres_masked_loss) -- exactly one of the two is given.  num_batches == 0: val_sums = {sum_b loss_b g_b, n} instead
+ *      (data parallel: the all-reduced sums of gatres_epoch_val_sums);
+ *   2. improved = val_loss < best_loss (fp64, strict), best_epoch;
+ *   3. EarlyStopping.step on the fp32 value of val_loss: the first epoch only stores it; a NaN stops; otherwise
+ *      val < best - min_delta in fp32 resets the bad-epoch count, anything else counts; stop at count >= patience;
+ *   4. unless stopped, ReduceLROnPlateau.step(val_loss) in fp64; a new learning rate is written to hp[0] (hp: the double[5] the
+ *      update kernels read, gatres_train_step_t.hparams; hp[1..4] are not touched);
+ *   5. history[epoch - 1] (if epoch <= history_capacity) and the state.
+ * config_host is read by the call (HOST pointer); every other pointer is a device pointer. */
+int gatres_epoch_control(const double* train_sums, const double* val_table, const float* val_losses,
+                         const int32_t* val_graphs, int32_t num_batches, const double* val_sums,
+                         const gatres_epoch_config_t* config_host, double* hp, double* state, double* history,
+                         int32_t history_capacity, void* stream);
+
+/* out[0] = sum_b loss_b g_b, out[1] = n, formed as gatres_epoch_control forms them (one rank's share under data parallelism). */
+int gatres_epoch_val_sums(const double* val_table, const float* val_losses, const int32_t* val_graphs, int32_t num_batches,
+                          double* out, void* stream);
+
+/* The best checkpoint kept on the device: if flag[0] != 0 (flag == NULL: always) copy params, exp_avg, exp_avg_sq (count
+ * floats each) and step_counter[0] to the dst_* buffers; otherwise nothing is written.  The flag is read by the kernel, so
+ * the host enqueues the call unconditionally (flag = state + GATRES_EPOCH_S_IMPROVED).  Restoring is the same call with
+ * sources and destinations exchanged and flag == NULL.  step_counter / dst_step_counter: both or neither. */
+int gatres_snapshot_if(const double* flag, const float* params, const float* exp_avg, const float* exp_avg_sq,
+                       const uint64_t* step_counter, float* dst_params, float* dst_exp_avg, float* dst_exp_avg_sq,
+                       uint64_t* dst_step_counter, int64_t count, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
