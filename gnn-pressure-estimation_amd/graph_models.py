@@ -186,6 +186,10 @@ class GATResMeanConv(_TrackedModule):
     """GraphModels.py:471-494.  ``gatres_small`` = (num_blocks=15, nc=32), ``gatres_large`` = (25, 128)
     (ConfigModels.py:22-42)."""
 
+    # updates native kernels made to the parameters behind torch's version counters (GATResTrainer counts them); a class
+    # attribute, so that models unpickled or deep-copied from older objects have it too
+    _native_updates = 0
+
     def __init__(self, name: str = "GATResMeanConv", num_blocks: int = 5, nc: int = 32, fused: bool = True):
         super().__init__()
         self.fused = fused          # False: always run the per-op kernels (one launch per stage)

@@ -11,14 +11,16 @@ mean-losses equal the global-batch mean loss, so the result matches single-proce
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
+import warnings
 from collections import OrderedDict
 from typing import Callable, Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import _native, dp
+from .epoch_loop import EpochLoop
+from .fit_loop import FitHistory, FitLoop, internal_train  # noqa: F401  (part of this module's interface)
 from .graph_models import GATResMeanConv
 from .graph_plan import GraphPlan
 
@@ -28,6 +30,7 @@ FLAG_PER_OP, FLAG_WT_VALID, FLAG_GRADS_DEFERRED, FLAG_GRADS_ONLY, FLAG_MASK_NEXT
 FLAG_LOSS_MAE, FLAG_LOSS_SCE = 32, 64
 _CRITERION_FLAGS = {"mse": 0, "mae": FLAG_LOSS_MAE, "sce": FLAG_LOSS_SCE}
 MAX_CACHED_GRAPHS = 40          # floor of the captured-step cache; bind_batches() sizes it from the number of bound batches
+_STEP = PHASE_FORWARD | PHASE_BACKWARD | PHASE_ADAM          # a whole step on a mask that is in place
 
 
 class _TrainStepC(C.Structure):
@@ -98,7 +101,72 @@ class _AutoClipState:
             dst[:src.numel()].copy_(src)
 
 
-class GATResTrainer:
+def _save(tensors, clip: Optional[_AutoClipState] = None) -> Callable[[], None]:
+    """Clone ``tensors`` (and AutoClip's device state) now; the function returned puts them back (stream-ordered copies)."""
+    kept = [(t, t.clone()) for t in tensors]
+    kept_clip = clip.save() if clip is not None else None
+
+    def restore() -> None:
+        for t, c in kept:
+            t.copy_(c)
+        if clip is not None:              # (the count, and the sorted copy a multi-step warm-up overwrote)
+            clip.restore(kept_clip)
+    return restore
+
+
+class _GraphCache(OrderedDict):
+    """One trainer's captured launch sequences (``torch.cuda.CUDAGraph``) by graph key, least recently replayed first."""
+
+    def __init__(self, device):
+        super().__init__()
+        self.device = device
+
+    def drop_all(self) -> None:
+        """Forget every graph (the buffers they hold addresses of are going away)."""
+        if self:
+            torch.cuda.synchronize(self.device)      # (a replay may still be in flight on the stream)
+            self.clear()
+
+    def lookup(self, key: tuple):
+        g = self.get(key)
+        if g is not None:
+            self.move_to_end(key)
+        return g
+
+    def capture(self, key: tuple, enqueue: Callable[[], None], rollback: Callable[[], None], limit: int, may_fail: bool):
+        """Warm-up launch outside capture (module load, lazy init, RCCL communicator), then the same sequence captured, with
+        ``rollback()`` after each; the graph goes into the cache, which then evicts down to ``limit`` entries.  ``may_fail``: a
+        capture that raises is survived -- capture mode ended, state rolled back, cache emptied, None returned."""
+        enqueue()
+        torch.cuda.synchronize(self.device)
+        rollback()
+        g = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(g):
+                enqueue()
+        except Exception as e:                     # noqa: BLE001
+            if not may_fail:
+                raise
+            warnings.warn(f"hipGraph capture of the data-parallel step failed ({type(e).__name__}: {e}); "
+                          f"continuing with eager launches")
+            try:                                   # (a failed capture may leave the stream in capture mode: end it)
+                if torch.cuda.is_current_stream_capturing():
+                    g.capture_end()
+            except Exception:                      # noqa: BLE001
+                pass
+            torch.cuda.synchronize(self.device)
+            rollback()
+            self.clear()
+            return None
+        rollback()
+        self[key] = g
+        while len(self) > limit:
+            torch.cuda.synchronize(self.device)      # (its last replay may still be in flight on the stream)
+            self.popitem(last=False)
+        return g
+
+
+class GATResTrainer(EpochLoop, FitLoop):
     """Owns the static buffers of one (model, topology, batch size) and runs training steps on them.
 
     ``step(x, y)`` draws a fresh device-side mask; ``step(x, y, mask=...)`` uses the caller's mask (bool/uint8 [N]),
@@ -201,7 +269,7 @@ class GATResTrainer:
         # the step is a handful of native launch sequences, far from host-bound).  One-rank groups (force_collective_path)
         # keep the capture, so the in-graph form stays tested.
         self.use_graph = use_graph and (self.world <= 1 or os.environ.get("GATRES_DP_GRAPH") == "1")
-        self._graphs: "OrderedDict[tuple, torch.cuda.CUDAGraph]" = OrderedDict()
+        self._graphs = _GraphCache(dev)
         self._params_ptr = params.data_ptr()
         self._wt_sig = None
         self._siblings: Dict[int, "GATResTrainer"] = {}
@@ -224,6 +292,14 @@ class GATResTrainer:
         # fit_epoch(device_metrics=True): the moment table, its cursor and the descale affine while such an epoch runs (None
         # otherwise: then no launch and no graph key changes)
         self._metrics: Optional[dict] = None
+        self._metrics_table = self._metrics_cursor = None      # ... and what backs it, kept from epoch to epoch
+        # allocated on first use: prefetch_batch()'s two staging slots, their side stream and events; steps_rows()'s row window
+        # and loss vector; the in-place epoch's buffer, its batch views and loss vector; fit()'s buffers
+        self._stage = self._copy_stream = self._ready = self._free = None
+        self._slot_in = self._slot_out = 0
+        self._rows_win = self._loss_seq = None
+        self._epoch_buf = self._epoch_bound = self._epoch_losses = None
+        self._fit: Optional[dict] = None
         self._warn_if_the_chip_is_not_ours()
 
     def _warn_if_the_chip_is_not_ours(self) -> None:
@@ -244,7 +320,6 @@ class GATResTrainer:
             need = ((padded // 2 + 7) // 8) * 8 * cus       # (batches of 49 - 96 snapshots go in two rounds of half the segments)
         masked = [k for k in ("HSA_CU_MASK", "ROC_GLOBAL_CU_MASK") if os.environ.get(k)]
         if need > have or masked:
-            import warnings
             warnings.warn(f"GATResTrainer: the per-snapshot kernel launches {need} co-resident workgroups (one per CU, {cus} per "
                           f"snapshot) on a device that reports {have} CUs"
                           + (f" under {', '.join(masked)}" if masked else "") +
@@ -293,13 +368,34 @@ class GATResTrainer:
             self.hp.data_ptr(),
             block_lo, block_hi, mask_next.data_ptr(), C.pointer(self._clip.c) if self._clip is not None else None)
 
-    def _count_native_update(self) -> None:
+    def _count_native_update(self, n: int = 1) -> None:
         """A native kernel (fused Adam pass, Adam-only phase) just changed the parameters without touching torch's
         version counters.  The count lives on the MODEL: trainers that share it (``fit_epoch``'s sibling for the ragged
         last batch, a trainer per batch size) each keep transposed conv weights in their OWN scratch buffer, and a step
         of one must invalidate the copies of the others (the sibling's step left the main trainer's W^T one
         update behind while its signature still matched)."""
-        self.model._native_updates = getattr(self.model, "_native_updates", 0) + 1
+        self.model._native_updates += n
+
+    def _committed(self, updates: int = 0, wt: Optional[bool] = None, mask_ahead: Optional[bool] = None,
+                   swap: bool = False) -> None:
+        """The ledger of what launches left behind -- with ``_unknown`` the only writer of these facts.  ``updates`` native updates
+        ran to completion; ``swap``: the two mask buffers traded places an odd number of times; ``wt``: scratch holds / does not
+        hold the transposes of the current weights; ``mask_ahead``: the spare buffer holds / does not hold the next step's mask
+        (None: that fact stays as it was)."""
+        if updates:
+            self._count_native_update(updates)
+        if swap:
+            self.mask, self._mask_spare = self._mask_spare, self.mask
+        if wt is not None:
+            self._wt_sig = self._param_signature() if wt else None
+        if mask_ahead is not None:
+            self._mask_sig = self._mask_key() if mask_ahead else None
+
+    def _unknown(self) -> None:
+        """An unknown part of a launch sequence ran (it raised), or the training state was replaced under the trainer: siblings
+        must not trust their transposed weights (one update is counted), and neither scratch's transposes nor a mask sampled
+        ahead is taken for current -- the next step samples its own mask and re-derives the transposes."""
+        self._committed(1, wt=False, mask_ahead=False)
 
     def _param_signature(self) -> Tuple[int, int, int]:
         """Changes whenever anything wrote to the parameters THROUGH TORCH: the flat vector or any of the nn.Parameters
@@ -307,7 +403,7 @@ class GATResTrainer:
         ``init_`` / ``clip_`` calls bump those, not the flat vector's).  Writes that bypass autograd's bookkeeping
         (``p.data.mul_()``) are invisible to it: call ``invalidate_weights()`` after such an edit."""
         return (self.model.flat_parameters._version, sum(p._version for p in self.model._param_list),
-                getattr(self.model, "_native_updates", 0))
+                self.model._native_updates)
 
     def _wt_current(self) -> bool:
         """scratch's transposed conv weights are current: our last fused Adam step wrote them and nothing has modified
@@ -316,7 +412,7 @@ class GATResTrainer:
 
     def invalidate_weights(self) -> None:
         """The parameters were edited behind torch's back: re-derive the transposed weights at the next step."""
-        self._wt_sig = None
+        self._committed(wt=False)
 
     def set_lr(self, lr: float) -> None:
         """Learning-rate schedules (the reference runs ReduceLROnPlateau, train.py:349-350,510).  The update kernels read
@@ -344,12 +440,9 @@ class GATResTrainer:
     def _take_mask_ahead(self) -> bool:
         """If the previous step's update launch sampled THIS step's mask and nothing has moved since, make that buffer the
         current one (True); else the caller samples / stages a mask into self.mask as before."""
-        if self._mask_next and self._mask_sig is not None and self._mask_sig == self._mask_key():
-            self.mask, self._mask_spare = self._mask_spare, self.mask
-            self._mask_sig = None
-            return True
-        self._mask_sig = None
-        return False
+        taken = self._mask_next and self._mask_current()
+        self._committed(mask_ahead=False, swap=taken)
+        return taken
 
     @property
     def criterion(self) -> str:
@@ -399,33 +492,63 @@ class GATResTrainer:
     def _mask_key(self):
         """What a mask sampled by the update launch is valid for: the optimizer state as this trainer left it (a sibling's or a
         FusedAdam step moves the shared step count: the sampler's key would differ) and the sampler's own settings."""
-        return (getattr(self.model, "_native_updates", 0), self.mask_rate, self.seed)
+        return (self.model._native_updates, self.mask_rate, self.seed)
 
-    def _reserve(self, updates: int) -> None:
+    def _mask_current(self) -> bool:
+        """The spare buffer holds the next step's mask: an update launch sampled it and nothing has moved since."""
+        return self._mask_sig is not None and self._mask_sig == self._mask_key()
+
+    def _step(self, device_mask: bool, premasked: bool = False, batch=None, slot=None) -> None:
+        """THE step runner: one optimisation step on ``batch`` (default: the static buffers) -- [mask sampler,] forward, loss,
+        backward, Adam as one launch on a single GPU; backward pieces | bucketed all-reduce | Adam under data parallelism, which
+        with one gradient bucket on the fused path is the single-GPU step's launch sequence with the slab sum and the update as
+        two launches around ONE all-reduce.  ``premasked``: the step's mask is in ``self.mask`` already, staged with the batch --
+        such a caller samples every step's mask itself, so the update launch does not sample the next one.  Otherwise, where
+        the update launch can (``_mask_next``; data parallel: one gradient bucket), it samples the NEXT step's mask, and a step
+        that finds that mask still valid leaves the sampler's launch out.  ``slot`` names ``batch`` in the graph key."""
+        if device_mask and self.node_ptr is None:
+            raise ValueError("device mask sampling needs nodes_per_graph at construction")
+        # (fused path: the Adam pass / Adam-only phase leaves the transposed conv weights of the NEW parameters in scratch)
+        wt_valid = self.fused and self._wt_current()
+        ahead = bool(not premasked and device_mask and self._mask_next and (not self.split or self._one_piece()))
+        if ahead and self._take_mask_ahead():
+            premasked = True                       # the previous step's update launch has sampled this step's mask already
+        flags = FLAG_MASK_NEXT if ahead else 0
+        if self.split:
+            what = ("split", premasked, flags, slot)
+
+            def enqueue():
+                dp.run_data_parallel_step(self._backward_pieces(device_mask, wt_valid, premasked, batch, flags), self.reducer,
+                                          lambda: self._enqueue(PHASE_ADAM, device_mask, flags=flags))
+        else:
+            phases = _STEP if premasked else PHASE_MASK | _STEP
+            what = (phases, flags, slot)
+
+            def enqueue():
+                self._enqueue(phases, device_mask, wt_valid, flags=flags, batch=batch)
+        self._launch(self._graph_key(what, device_mask, wt_valid), enqueue, wt_valid, 1, wt=self.fused, mask_ahead=ahead)
+
+    def _launch(self, key: tuple, enqueue: Callable[[], None], wt_valid: bool, updates: int, wt: bool, mask_ahead: bool,
+                swap: bool = False) -> None:
+        """What every runner does around its launch sequence of ``updates`` steps: room in the gradient-norm history, ``_replay``,
+        and the ledger -- ``_committed`` with the facts the sequence establishes, ``_unknown`` if it raised."""
         if self._clip is not None:
             self._clip.reserve(updates)
-
-    def _run(self, phases: int, device_mask: bool, batch=None, slot=None) -> None:
-        full = PHASE_BACKWARD | PHASE_ADAM
-        if phases & PHASE_ADAM:
-            self._reserve(1)
-        wt_valid = self.fused and (phases & PHASE_BACKWARD) != 0 and self._wt_current()
-        flags = 0
-        mask_next = self._mask_next and device_mask and (phases & (PHASE_FORWARD | full)) == (PHASE_FORWARD | full)
-        if mask_next:
-            flags |= FLAG_MASK_NEXT
-            if (phases & PHASE_MASK) and self._take_mask_ahead():
-                phases &= ~PHASE_MASK            # the previous step's update launch has sampled this step's mask already
         try:
-            self._replay(self._graph_key((phases, flags, slot), device_mask, wt_valid),
-                         lambda: self._enqueue(phases, device_mask, wt_valid, flags=flags, batch=batch), wt_valid)
-        finally:
-            if phases & PHASE_ADAM:
-                self._count_native_update()
-            # a fused backward + Adam step leaves the transposed weights of the NEW parameters in (this trainer's) scratch
-            if self.fused and (phases & full) == full:
-                self._wt_sig = self._param_signature()
-            self._mask_sig = self._mask_key() if mask_next else None
+            self._replay(key, enqueue, wt_valid)
+        except BaseException:
+            self._unknown()
+            raise
+        self._committed(updates, wt, mask_ahead, swap)
+
+    def _prepare_backward(self) -> None:
+        """Derive scratch's transposed conv weights from the parameters as they are now (the promise behind ``wt_valid``)."""
+        _native.check(self.lib.gatres_fused_prepare_backward(
+            self.model._cmodel_ref(), C.byref(self._gstruct), self.model.flat_parameters.data_ptr(),
+            self.scratch.data_ptr(), _native.current_stream(self.device)), "gatres_fused_prepare_backward")
+
+    def _training_state(self) -> list:
+        return [self.step_counter, self.model.flat_parameters, self.exp_avg, self.exp_avg_sq]
 
     def _replay(self, key: tuple, enqueue: Callable[[], None], wt_valid: bool = False) -> None:
         """Run ``enqueue`` -- eagerly, or captured once into a hipGraph (cached by ``key``) and replayed."""
@@ -436,74 +559,27 @@ class GATResTrainer:
             enqueue()
             return
         if self._clip is not None and self._clip_gen != self._clip.generation:
-            # the gradient-norm history was grown: captured steps hold the old buffers' addresses
-            torch.cuda.synchronize(self.device)
-            self._graphs.clear()
+            self._graphs.drop_all()      # the gradient-norm history was grown: captured steps hold the old buffers' addresses
             self._clip_gen = self._clip.generation
-        g = self._graphs.get(key)
+        g = self._graphs.lookup(key)
         if g is None:
-            # warm-up launch outside capture (module load, lazy init, RCCL communicator), then capture the same sequence
-            state = (self.step_counter.clone(), self.model.flat_parameters.clone(), self.exp_avg.clone(),
-                     self.exp_avg_sq.clone(), self.mask.clone(), self._mask_spare.clone(),
-                     self._clip.save() if self._clip is not None else None,
-                     met["cursor"].clone() if met is not None else None)
-
-            def rollback():
-                self.step_counter.copy_(state[0]); self.model.flat_parameters.copy_(state[1])
-                self.exp_avg.copy_(state[2]); self.exp_avg_sq.copy_(state[3])
-                self.mask.copy_(state[4])        # (a warm-up that ran the sampler's launch re-sampled it: same bits; kept simple)
-                self._mask_spare.copy_(state[5])  # (a multi-step sequence samples into BOTH buffers, two steps ahead of the rollback)
-                if state[6] is not None:          # (the count, and the sorted copy a multi-step warm-up overwrote)
-                    self._clip.restore(state[6])
-                if state[7] is not None:          # (the warm-up's records are overwritten by the real steps: same slots)
-                    met["cursor"].copy_(state[7])
-
-            enqueue()
-            torch.cuda.synchronize(self.device)
-            rollback()
-            g = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(g):
-                    enqueue()
-            except Exception as e:                     # noqa: BLE001
-                # A multi-rank step holds RCCL collectives; if this runtime cannot capture them (every rank fails the
-                # same way: the sequence is identical), run the launch sequence eagerly from here on instead of dying.
-                # Single-rank captures hold only this library's kernels: a failure there is a bug and is raised.
-                if self.world <= 1:
-                    raise
-                import warnings
-                warnings.warn(f"hipGraph capture of the data-parallel step failed ({type(e).__name__}: {e}); "
-                              f"continuing with eager launches")
-                try:                                   # (a failed capture may leave the stream in capture mode: end it)
-                    if torch.cuda.is_current_stream_capturing():
-                        g.capture_end()
-                except Exception:                      # noqa: BLE001
-                    pass
-                torch.cuda.synchronize(self.device)
-                rollback()
-                if wt_valid:
-                    # the warm-up step left the transposes of ITS updated weights in scratch and the parameters were
-                    # rolled back: re-derive them, or this eager step's backward would use W^T of other weights
-                    _native.check(self.lib.gatres_fused_prepare_backward(
-                        self.model._cmodel_ref(), C.byref(self._gstruct), self.model.flat_parameters.data_ptr(),
-                        self.scratch.data_ptr(), _native.current_stream(self.device)), "gatres_fused_prepare_backward")
+            # the warm-up runs real steps: the training state comes back after it, with both mask buffers (a warm-up that ran the
+            # sampler's launch re-sampled self.mask: same bits; a multi-step sequence samples into BOTH, two steps ahead of the
+            # rollback) and the metrics cursor (the warm-up's records are overwritten by the real steps: same slots)
+            rollback = _save(self._training_state() + [self.mask, self._mask_spare] + ([met["cursor"]] if met is not None else []),
+                             self._clip)
+            # A multi-rank step holds RCCL collectives; if this runtime cannot capture them (every rank fails the same way: the
+            # sequence is identical), run the launch sequence eagerly from here on instead of dying.  Single-rank captures hold
+            # only this library's kernels: a failure there is a bug and is raised.
+            g = self._graphs.capture(key, enqueue, rollback, self._max_graphs, may_fail=self.world > 1)
+            if wt_valid:
+                # the warm-up step left the transposes of ITS updated weights in scratch; the parameters were rolled back, so
+                # make the promise this sequence relies on true again
+                self._prepare_backward()
+            if g is None:
                 self.use_graph = False
-                self._graphs.clear()
                 enqueue()
                 return
-            rollback()
-            if wt_valid:
-                # the warm-up step left the transposes of ITS updated weights in scratch; the parameters were rolled
-                # back, so make the promise this graph relies on true again
-                _native.check(self.lib.gatres_fused_prepare_backward(
-                    self.model._cmodel_ref(), C.byref(self._gstruct), self.model.flat_parameters.data_ptr(),
-                    self.scratch.data_ptr(), _native.current_stream(self.device)), "gatres_fused_prepare_backward")
-            self._graphs[key] = g
-            while len(self._graphs) > self._max_graphs:
-                torch.cuda.synchronize(self.device)      # (its last replay may still be in flight on the stream)
-                self._graphs.popitem(last=False)
-        else:
-            self._graphs.move_to_end(key)
         if self.fused:
             # a captured split launch cannot order itself behind one on another stream (include/gatres.h)
             _native.check(self.lib.gatres_fused_serialize(_native.current_stream(self.device)), "gatres_fused_serialize")
@@ -562,31 +638,6 @@ class GATResTrainer:
             pieces.append(piece)
         return pieces
 
-    def _run_split(self, device_mask: bool, premasked: bool = False, batch=None, slot=None, ahead: bool = True) -> None:
-        """The data-parallel step: backward pieces | bucketed all-reduce | Adam.  With one gradient bucket on the fused path
-        this is the single-GPU step's launch sequence with the slab sum and the update as two launches around ONE all-reduce:
-        the batch is read in place (``batch``), and the Adam launch samples the next step's mask (``ahead``) exactly as the
-        single-GPU update launch does.  ahead=False: the caller samples every step's mask itself (staged batches)."""
-        # (fused path: the Adam-only phase refreshes scratch's transposed conv weights like the fused Adam pass does)
-        self._reserve(1)
-        wt_valid = self.fused and self._wt_current()
-        ahead = bool(ahead and self._mask_next and device_mask and self._one_piece())
-        if ahead and not premasked and self._take_mask_ahead():
-            premasked = True                       # the previous step's Adam launch has sampled this step's mask already
-        elif not ahead:
-            self._mask_sig = None
-        flags = FLAG_MASK_NEXT if ahead else 0
-        try:
-            self._replay(self._graph_key(("split", premasked, flags, slot), device_mask, wt_valid),
-                         lambda: dp.run_data_parallel_step(
-                             self._backward_pieces(device_mask, wt_valid, premasked, batch, flags), self.reducer,
-                             lambda: self._enqueue(PHASE_ADAM, device_mask, flags=flags)), wt_valid)
-        finally:
-            self._count_native_update()
-            if self.fused:
-                self._wt_sig = self._param_signature()
-            self._mask_sig = self._mask_key() if ahead else None
-
     # ------------------------------------------------------------------------------------------
     def load_batch(self, x: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor] = None) -> None:
         """Stage a batch into the static buffers (async copies on the current stream)."""
@@ -595,13 +646,13 @@ class GATResTrainer:
             self.y.copy_(y.reshape(-1), non_blocking=True)
         if mask is not None:
             self.mask.copy_(mask.reshape(-1).to(torch.uint8), non_blocking=True)
-            self._mask_sig = None                # (the caller's mask replaced whatever the update launch had sampled)
+            self._committed(mask_ahead=False)    # (the caller's mask replaced whatever the update launch had sampled)
 
     def prefetch_batch(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> None:
         """Start copying the NEXT batch (typically pinned host memory) into a staging buffer on a side stream, so the
         PCIe transfer overlaps the step that is running; ``commit_batch()`` then moves it into place with a device copy.
         Two staging slots: at most one prefetch may be outstanding per ``commit_batch()``."""
-        if not hasattr(self, "_stage"):
+        if self._stage is None:
             f32 = dict(dtype=torch.float32, device=self.device)
             n = self.x.numel()
             self._stage = [(torch.empty(n, **f32), None if self.targets_are_inputs else torch.empty(n, **f32))
@@ -611,7 +662,6 @@ class GATResTrainer:
             self._free = [torch.cuda.Event() for _ in range(2)]
             for ev in self._free:
                 ev.record(torch.cuda.current_stream(self.device))
-            self._slot_in, self._slot_out = 0, 0
         k = self._slot_in
         sx, sy = self._stage[k]
         with torch.cuda.stream(self._copy_stream):
@@ -644,19 +694,14 @@ class GATResTrainer:
         cur.wait_event(self._ready[k])
         sx, sy = self._stage[k]
         batch = (sx, sx if sy is None else sy)
-        self._step_on(batch, ("at", batch[0].data_ptr(), batch[1].data_ptr()))
+        self._step_on(batch)
         self._free[k].record(cur)                  # (the slot may be refilled once this step has read it)
         self._slot_out = 1 - k
         return self.loss
 
     def run_step(self, device_mask: bool = True) -> None:
         """One optimisation step on the staged batch.  Nothing is synchronised; read ``self.loss`` afterwards."""
-        if device_mask and self.node_ptr is None:
-            raise ValueError("device mask sampling needs nodes_per_graph at construction")
-        if not self.split:
-            self._run(PHASE_MASK | PHASE_FORWARD | PHASE_BACKWARD | PHASE_ADAM, device_mask)
-        else:
-            self._run_split(device_mask)
+        self._step(device_mask)
 
     def _stage_with_mask(self, x: torch.Tensor, y: torch.Tensor) -> bool:
         """Device-resident batch + device mask: the copy into the static buffers rides on the mask
@@ -671,7 +716,7 @@ class GATResTrainer:
         # (a mask the previous update launch may have sampled ahead is NOT used here: the batch needs a staging launch anyway,
         #  and copy + sampling in one launch is cheaper than a copy launch of its own -- measured 0.4204 vs 0.4237 ms/step;
         #  step_bound() / run_step() are the paths without a staging launch)
-        self._mask_sig = None
+        self._committed(mask_ahead=False)
         ys = None if self.targets_are_inputs else y
         _native.check(self.lib.gatres_stage_batch_mask(
             x.data_ptr(), None if ys is None else ys.data_ptr(), self.x.data_ptr(), None if ys is None else self.y.data_ptr(), n,
@@ -684,21 +729,11 @@ class GATResTrainer:
         ``[S, N_g]`` (a ``SnapshotStore``): the batch is collated INSIDE the mask sampler's launch
         (``gatres_stage_rows_mask``) -- no ``index_select``, no copy.  Returns False (nothing done) when this trainer
         cannot take the path (no per-graph node counts, switched off)."""
-        if self.node_ptr is None or os.environ.get("GATRES_NO_STAGE_MASK"):
+        if not (self._rows_path_ok(data) and rows.is_cuda and rows.dtype == torch.int64 and rows.numel() == self.num_graphs
+                and rows.is_contiguous()):
             return False
-        npg = self.N // max(self.num_graphs, 1)
-        if not (data.is_cuda and data.device == self.x.device and data.dtype == torch.float32 and data.dim() == 2
-                and data.shape[1] == npg and data.is_contiguous() and rows.is_cuda and rows.dtype == torch.int64
-                and rows.numel() == self.num_graphs and rows.is_contiguous()):
-            return False
-        _native.check(self.lib.gatres_stage_rows_mask(
-            data.data_ptr(), rows.data_ptr(), npg, self.x.data_ptr(), None if self.targets_are_inputs else self.y.data_ptr(),
-            self.node_ptr.data_ptr(), self.num_graphs, self.mask_rate, self.seed, self.step_counter.data_ptr(),
-            self.mask.data_ptr(), _native.current_stream(self.device)), "gatres_stage_rows_mask")
-        if self.split:
-            self._run_split(True, premasked=True, ahead=False)
-        else:
-            self._run_premasked(ahead=False)
+        self._stage_rows(data, rows.data_ptr())
+        self._step(True, premasked=True)
         return True
 
     def _rows_path_ok(self, data: torch.Tensor) -> bool:
@@ -706,6 +741,15 @@ class GATResTrainer:
         return (self.node_ptr is not None and not os.environ.get("GATRES_NO_STAGE_MASK") and data.is_cuda
                 and data.device == self.x.device and data.dtype == torch.float32 and data.dim() == 2
                 and data.shape[1] == npg and data.is_contiguous())
+
+    def _stage_rows(self, data: torch.Tensor, rows_ptr: int) -> None:
+        """Collate the snapshots named by the ``num_graphs`` int64 row indices at device address ``rows_ptr`` into the static
+        buffers and sample the step's mask, in one launch."""
+        _native.check(self.lib.gatres_stage_rows_mask(
+            data.data_ptr(), rows_ptr, self.N // max(self.num_graphs, 1), self.x.data_ptr(),
+            None if self.targets_are_inputs else self.y.data_ptr(), self.node_ptr.data_ptr(), self.num_graphs, self.mask_rate,
+            self.seed, self.step_counter.data_ptr(), self.mask.data_ptr(), _native.current_stream(self.device)),
+            "gatres_stage_rows_mask")
 
     def steps_rows(self, data: torch.Tensor, rows: torch.Tensor, total: Optional[torch.Tensor] = None) -> bool:
         """``step_rows`` for k consecutive batches -- ``rows`` is a device int64 ``[k * num_graphs]`` slice of an epoch's
@@ -721,32 +765,20 @@ class GATResTrainer:
         if not (k > 1 and rows.numel() == k * bs and self.use_graph and self.fused and not self.split and self._rows_path_ok(data)
                 and rows.is_cuda and rows.dtype == torch.int64 and self._wt_current()):
             return False
-        win = getattr(self, "_rows_win", None)
+        win = self._rows_win
         if win is None or win.numel() < k * bs:
             win = self._rows_win = torch.zeros(k * bs, dtype=torch.int64, device=self.device)
             self._loss_seq = torch.zeros(k, dtype=torch.float32, device=self.device)
         win[:k * bs].copy_(rows)
-        self._reserve(k)
         lseq = self._loss_seq
-        npg = self.N // bs
-        full = PHASE_FORWARD | PHASE_BACKWARD | PHASE_ADAM
 
         def enqueue():
             for i in range(k):
-                _native.check(self.lib.gatres_stage_rows_mask(
-                    data.data_ptr(), win.data_ptr() + 8 * i * bs, npg, self.x.data_ptr(),
-                    None if self.targets_are_inputs else self.y.data_ptr(), self.node_ptr.data_ptr(), bs, self.mask_rate, self.seed,
-                    self.step_counter.data_ptr(), self.mask.data_ptr(), _native.current_stream(self.device)), "gatres_stage_rows_mask")
-                self._enqueue(full, True, True, flags=0, loss=lseq[i:i + 1])
+                self._stage_rows(data, win.data_ptr() + 8 * i * bs)
+                self._enqueue(_STEP, True, True, flags=0, loss=lseq[i:i + 1])
 
-        try:
-            self._replay(("rowseq", k, data.data_ptr(), win.data_ptr(), lseq.data_ptr(), self.mask_rate, self.seed, self.world),
-                         enqueue, True)
-        finally:
-            for _ in range(k):
-                self._count_native_update()
-            self._wt_sig = self._param_signature()
-            self._mask_sig = None
+        self._launch(("rowseq", k, data.data_ptr(), win.data_ptr(), lseq.data_ptr(), self.mask_rate, self.seed, self.world),
+                     enqueue, True, k, wt=True, mask_ahead=False)
         self.loss.copy_(lseq[k - 1:k])                   # (the loss of the step that ran last, as after single steps)
         if total is not None:
             total.add_(lseq[:k].double().sum(), alpha=float(bs))
@@ -754,32 +786,12 @@ class GATResTrainer:
 
     def step(self, x: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Reference-shaped call: one iteration of train.py:159-190.  Returns the (device) loss tensor."""
-        if mask is None and self._stage_with_mask(x, y):                        # (the mask of this step is in place)
-            if self.split:
-                self._run_split(True, premasked=True, ahead=False)
-            else:
-                self._run_premasked(ahead=False)
-            return self.loss
-        self.load_batch(x, y, mask)
-        self.run_step(device_mask=mask is None)
+        if mask is None and self._stage_with_mask(x, y):
+            self._step(True, premasked=True)                                    # (the mask of this step is in place)
+        else:
+            self.load_batch(x, y, mask)
+            self.run_step(device_mask=mask is None)
         return self.loss
-
-    def _run_premasked(self, batch=None, slot=None, ahead: bool = True) -> None:
-        """The single-GPU step on a mask that is already in self.mask (staged with the batch, or sampled by the previous
-        step's update launch).  ahead=False: the caller samples every step's mask itself (the store's row collation)."""
-        full = PHASE_FORWARD | PHASE_BACKWARD | PHASE_ADAM
-        self._reserve(1)
-        wt_valid = self.fused and self._wt_current()
-        ahead = ahead and self._mask_next
-        flags = FLAG_MASK_NEXT if ahead else 0
-        try:
-            self._replay(self._graph_key((full, flags, slot), True, wt_valid),
-                         lambda: self._enqueue(full, True, wt_valid, flags=flags, batch=batch), wt_valid)
-        finally:
-            self._count_native_update()
-            if self.fused:
-                self._wt_sig = self._param_signature()
-            self._mask_sig = self._mask_key() if ahead else None
 
     # ---- bound batches: the captured step reads the caller's buffers, nothing is copied -------------------------------------
     def bind_batches(self, xs, ys=None, precapture: bool = True, sequences=()) -> int:
@@ -796,9 +808,7 @@ class GATResTrainer:
                 if t.numel() != self.N or t.device != self.x.device:
                     raise ValueError(f"a bound batch must hold {self.N} values on {self.x.device}")
             bound.append((x.reshape(-1), y.reshape(-1)))
-        if self._graphs:                              # (captured steps of the previous binding read other buffers)
-            torch.cuda.synchronize(self.device)
-            self._graphs.clear()
+        self._graphs.drop_all()                       # (captured steps of the previous binding read other buffers)
         self._bound = bound
         # two captured steps per bound batch (the two mask buffers take turns) + the first-step variants + whatever else this
         # trainer replays: the cache must hold them all, or FIFO eviction makes every step pay for a capture
@@ -819,8 +829,7 @@ class GATResTrainer:
             return len(self._graphs)
         dev = self.device
         torch.cuda.synchronize(dev)
-        keep = [t.clone() for t in (self.step_counter, self.model.flat_parameters, self.exp_avg, self.exp_avg_sq, self.loss)]
-        keep_clip = self._clip.save() if self._clip is not None else None
+        restore = _save(self._training_state() + [self.loss], self._clip)
         try:
             n = len(self._bound)
             # (mask-ahead: the two mask buffers take turns, so a batch has two steady-state graphs; without it, one)
@@ -831,11 +840,8 @@ class GATResTrainer:
             while need and steps < 4 * n + 8:
                 # the step about to run is a steady-state one iff the weights' transposes are current and (mask-ahead) a mask was
                 # sampled ahead; it then trains with the (current) spare buffer as its mask
-                steady = (not self.fused) or self._wt_current()
-                ptr = None
-                if ahead_ok:
-                    steady = steady and self._mask_sig is not None and self._mask_sig == self._mask_key()
-                    ptr = self._mask_spare.data_ptr() if steady else None
+                steady = ((not self.fused) or self._wt_current()) and (not ahead_ok or self._mask_current())
+                ptr = self._mask_spare.data_ptr() if ahead_ok and steady else None
                 i = next((j for j in range(n) if (j, ptr) in need), 0)
                 self.step_bound(i)
                 if steady:
@@ -861,25 +867,17 @@ class GATResTrainer:
             # whatever happened above (a capture or a launch may raise midway): the caller's model, moments and step count
             # come back, and neither the sampled-ahead mask nor scratch's transposed weights is taken for current
             torch.cuda.synchronize(dev)
-            for dst, src in zip((self.step_counter, self.model.flat_parameters, self.exp_avg, self.exp_avg_sq, self.loss), keep):
-                dst.copy_(src)
-            if keep_clip is not None:
-                self._clip.restore(keep_clip)
-            self._mask_sig = None
-            self._wt_sig = None
+            restore()
+            self._unknown()                            # (siblings / other trainers of this model: their copies are stale too)
         if self.fused:
             # scratch holds the transposes of the LAST pre-capture step's weights: re-derive them for the restored parameters
-            _native.check(self.lib.gatres_fused_prepare_backward(
-                self.model._cmodel_ref(), C.byref(self._gstruct), self.model.flat_parameters.data_ptr(),
-                self.scratch.data_ptr(), _native.current_stream(dev)), "gatres_fused_prepare_backward")
-            self._count_native_update()                # (siblings / other trainers of this model: their copies are stale too)
-            self._wt_sig = self._param_signature()
+            self._prepare_backward()
         if ahead_ok:
             # the first step's mask, sampled where the previous step's update launch would have left it (same key: same bits)
             _native.check(self.lib.gatres_mask_generate(
                 self.node_ptr.data_ptr(), self.num_graphs, self.mask_rate, self.seed, self.step_counter.data_ptr(),
                 self._mask_spare.data_ptr(), _native.current_stream(dev)), "gatres_mask_generate")
-            self._mask_sig = self._mask_key()
+        self._committed(wt=self.fused, mask_ahead=ahead_ok)
         torch.cuda.synchronize(dev)
         self._faults_seen = self.fault_count + self.dropped_steps
         return len(self._graphs)
@@ -889,14 +887,7 @@ class GATResTrainer:
         path this is three launches -- the per-snapshot kernel, the parameter gradients, the update (which also samples the
         next step's mask) -- replayed from one hipGraph; the first step (and any step after the optimizer state moved under
         the trainer) runs the sampler's launch first."""
-        x, y = self._bound[i]
-        if self.node_ptr is None:
-            raise ValueError("device mask sampling needs nodes_per_graph at construction")
-        if self.split:                     # (data-parallel step: the same launches around the all-reduce, batch read in place)
-            self._run_split(True, batch=(x, y), slot=i)
-            return self.loss
-        self._run(PHASE_MASK | PHASE_FORWARD | PHASE_BACKWARD | PHASE_ADAM, True, batch=(x, y), slot=i)
-        return self.loss
+        return self._step_on(self._bound[i], slot=i)
 
     def steps_bound(self, indices, bound=None, losses: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``step_bound(i)`` for every i of ``indices``, in order -- as ONE captured launch sequence when the trainer is in its
@@ -912,56 +903,35 @@ class GATResTrainer:
         if losses is not None and losses.numel() < len(idx):
             raise ValueError(f"`losses` holds {losses.numel()} entries for {len(idx)} steps")
         steady = (len(idx) > 1 and self.use_graph and self.fused and not self.split and self._mask_next and self._wt_current()
-                  and self._mask_sig is not None and self._mask_sig == self._mask_key() and self.node_ptr is not None)
+                  and self._mask_current() and self.node_ptr is not None)
         if not steady:
             for j, i in enumerate(idx):
-                if bound is None:
-                    self.step_bound(i)
-                else:
-                    self._step_on(bnd[i], ("at", bnd[i][0].data_ptr(), bnd[i][1].data_ptr()))
+                self._step_on(bnd[i], slot=i if bound is None else None)
                 if losses is not None:
                     losses[j:j + 1].copy_(self.loss)
             return self.loss
-        full = PHASE_FORWARD | PHASE_BACKWARD | PHASE_ADAM
-        self._reserve(len(idx))
         m0, m1 = self._mask_spare, self.mask          # step 0 trains on the mask sampled ahead and samples step 1's into the other
 
         def enqueue():
             a, b = m0, m1
             for j, i in enumerate(idx):
-                self._enqueue(full, True, True, flags=FLAG_MASK_NEXT, batch=bnd[i], masks=(a, b),
+                self._enqueue(_STEP, True, True, flags=FLAG_MASK_NEXT, batch=bnd[i], masks=(a, b),
                               loss=None if losses is None else losses[j:j + 1])
                 a, b = b, a
 
-        try:
-            self._replay(("seq", idx, self.mask_rate, self.seed, self.world, m0.data_ptr(), bnd[idx[0]][0].data_ptr(),
-                          None if losses is None else losses.data_ptr()), enqueue, True)
-        except BaseException:
-            # an unknown number of the sequence's steps ran: nothing about the mask buffers or the transposed weights can be
-            # relied on -- the next step samples its own mask and re-derives the transposes
-            self._count_native_update()
-            self._mask_sig = None
-            self._wt_sig = None
-            raise
-        for _ in idx:
-            self._count_native_update()
-        self._wt_sig = self._param_signature()
-        if len(idx) % 2:                               # an odd number of steps leaves the buffers swapped
-            self.mask, self._mask_spare = self._mask_spare, self.mask
-        self._mask_sig = self._mask_key()              # (the last update launch sampled the next step's mask into the spare buffer)
+        # (the last update launch samples the next step's mask into the spare buffer; an odd number of steps leaves the buffers
+        #  swapped)
+        self._launch(("seq", idx, self.mask_rate, self.seed, self.world, m0.data_ptr(), bnd[idx[0]][0].data_ptr(),
+                      None if losses is None else losses.data_ptr()), enqueue, True, len(idx), wt=True, mask_ahead=True,
+                     swap=len(idx) % 2 == 1)
         if losses is not None:
             self.loss.copy_(losses[len(idx) - 1:len(idx)])
         return self.loss
 
-    def _step_on(self, batch, slot) -> torch.Tensor:
-        """``step_bound`` on a resident ``(x, y)`` batch that is not in the bound list (``slot`` names it in the graph cache: use
-        the buffers' addresses)."""
-        if self.node_ptr is None:
-            raise ValueError("device mask sampling needs nodes_per_graph at construction")
-        if self.split:
-            self._run_split(True, batch=batch, slot=slot)
-        else:
-            self._run(PHASE_MASK | PHASE_FORWARD | PHASE_BACKWARD | PHASE_ADAM, True, batch=batch, slot=slot)
+    def _step_on(self, batch, slot=None) -> torch.Tensor:
+        """``step_bound`` on a resident ``(x, y)`` batch: the kernels read it in place.  ``slot`` names it in the graph cache --
+        the index of a bound batch; for any other batch (None) the buffers' addresses."""
+        self._step(True, batch=batch, slot=("at", batch[0].data_ptr(), batch[1].data_ptr()) if slot is None else slot)
         return self.loss
 
     def forward_backward(self, x: torch.Tensor, y: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
@@ -1011,467 +981,3 @@ class GATResTrainer:
     def reset_gradient_clipping(self) -> None:
         """``GradientClipping.reset()``: forget the history (stream-ordered; captured steps stay valid)."""
         self._clip_state().reset()
-
-    # ---- epoch-level loop (train.py:112-202) ---------------------------------------------------------------------------
-    def _epoch_in_place(self, store, order: torch.Tensor, nfull: int, kseq: int, total: torch.Tensor) -> None:
-        bs, npg = self.num_graphs, store.nodes_per_graph
-        buf = getattr(self, "_epoch_buf", None)
-        if buf is None or tuple(buf.shape) != (nfull * bs, npg):
-            if buf is not None:
-                self.release_epoch_buffer()
-            buf = self._epoch_buf = torch.empty(nfull * bs, npg, dtype=torch.float32, device=self.device)
-            views = [buf[j * bs:(j + 1) * bs].reshape(-1) for j in range(nfull)]
-            self._epoch_bound = [(v, v) for v in views]            # (x is also y: train.py:162-166)
-            self._epoch_losses = None
-        if getattr(self, "_epoch_losses", None) is None or self._epoch_losses.numel() < max(kseq, 2):
-            # (also when epoch_graph_steps was raised between two epochs on the same store: a step's loss slot must exist --
-            #  ADVICE r5; the losses pointer is part of the sequences' graph key, so no stale graph meets the new vector)
-            self._epoch_losses = torch.zeros(max(kseq, 2), dtype=torch.float32, device=self.device)
-            # sequences of k (one graph per run of the epoch and mask orientation), single steps where a run starts or ends
-            self._max_graphs = max(self._max_graphs, MAX_CACHED_GRAPHS + 2 * (nfull // kseq + 1) + 2 * kseq + 8)
-        torch.index_select(store.data, 0, order[:nfull * bs], out=buf)
-        eb, lseq = self._epoch_bound, self._epoch_losses
-        j = 0
-        while j < nfull:
-            steady = (self._wt_current() and self._mask_sig is not None and self._mask_sig == self._mask_key())
-            k = min(kseq, nfull - j) if steady else 1
-            if k > 1:
-                self.steps_bound(range(j, j + k), bound=eb, losses=lseq)
-                total.add_(lseq[:k].double().sum(), alpha=float(bs))
-            else:
-                self._step_on(eb[j], ("at", eb[j][0].data_ptr(), eb[j][1].data_ptr()))   # (the slot names the buffers: a re-allocated epoch buffer never meets a stale graph)
-                total.add_(self.loss.double(), alpha=float(bs))
-            j += k
-
-    def _epoch_copy_fits(self, rows: int, npg: int) -> bool:
-        """May ``fit_epoch`` keep a device copy of the epoch's shuffled batches (``rows`` x ``npg`` floats: as large as the store
-        itself, i.e. the store's footprint doubles)?  Yes if it already exists, or if it is within ``epoch_copy_limit_bytes``
-        AND leaves a quarter of the device's free memory untouched; otherwise the epoch goes through the row-gather steps
-        (``steps_rows``), which need no copy."""
-        buf = getattr(self, "_epoch_buf", None)
-        if buf is not None and tuple(buf.shape) == (rows, npg):
-            return True
-        need = 4 * rows * npg
-        if need > int(self.epoch_copy_limit_bytes):
-            return False
-        held = 0 if buf is None else buf.numel() * 4          # (a buffer of another shape is released first)
-        free, _ = torch.cuda.mem_get_info(self.device)
-        return need <= 0.75 * (free + held)
-
-    def release_epoch_buffer(self) -> None:
-        """Free ``fit_epoch``'s device copy of the epoch (and the graphs captured on it)."""
-        if getattr(self, "_epoch_buf", None) is not None:
-            torch.cuda.synchronize(self.device)
-            self._graphs.clear()
-            self._epoch_buf = self._epoch_bound = self._epoch_losses = None
-
-    def _fit_epoch_device_metrics(self, store, bs: int, shuffle: bool, drop_last: bool, generator,
-                                  metric_fn_dict, total: Optional[torch.Tensor] = None):
-        """fit_epoch with the metrics launch in every step (device_metrics=True).  ``total`` (``fit``): the epoch's loss sum is
-        added to that device tensor and the graph count is returned in place of the mean loss."""
-        from . import evaluation as E
-        keys = list(metric_fn_dict or {})
-        if not keys or not keys[0].endswith("_error"):
-            raise ValueError("device_metrics=True computes evaluation.get_metric_fn_collection(prefix) only; "
-                             "pass that collection as metric_fn_dict")
-        prefix = keys[0][:-len("_error")]
-        E._check_reference_metrics(None, metric_fn_dict, prefix)
-        if store.norm_type == "znorm":
-            scale, offset = float(store.std), float(store.mean)
-        else:
-            scale, offset = 1.0, 0.0
-        S = store.num_snapshots
-        sizes = [bs] * (S // bs) + ([S % bs] if S % bs and not drop_last else [])
-        if not sizes:
-            raise ValueError("the store yielded no batch")
-        table = getattr(self, "_metrics_table", None)
-        if table is None or table.shape[0] < len(sizes):
-            # persistent across epochs: its address is part of the captured steps' graph keys
-            table = self._metrics_table = torch.zeros((len(sizes), E.METRICS_RECORD), dtype=torch.float64, device=self.device)
-            self._metrics_cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
-        table.zero_()
-        self._metrics_cursor.zero_()
-        met = {"table": table, "cursor": self._metrics_cursor, "scale": scale, "offset": offset}
-        self._metrics = met                 # (_sibling() hands it on to the ragged batch's trainer)
-        try:
-            if total is None:
-                loss, _ = self.fit_epoch(store, bs, shuffle=shuffle, drop_last=drop_last, generator=generator)
-            else:
-                loss, _ = self._fit_epoch_sums(store, bs, shuffle, drop_last, generator, None, total, check=False)
-        finally:
-            self._metrics = None
-            for t in self._siblings.values():
-                t._metrics = None
-        written = int(self._metrics_cursor.item())
-        if written != len(sizes):
-            raise RuntimeError(f"the epoch wrote {written} metric records for {len(sizes)} batches")
-        _, metrics = E.metrics_from_moments(table[:len(sizes)].cpu().numpy(), sizes, prefix)
-        return loss, metrics
-
-    def _sibling(self, num_graphs: int, nodes_per_graph: int, edge_index: torch.Tensor) -> "GATResTrainer":
-        """Trainer for another batch size of the same dataset (the ragged last batch of an epoch): its own plan and
-        buffers, the SAME model, Adam moments and step counter."""
-        t = self._siblings.get(num_graphs)
-        if t is None:
-            t = GATResTrainer(self.model, edge_index, num_graphs * nodes_per_graph,
-                              nodes_per_graph=[nodes_per_graph] * num_graphs, lr=self.hparams["lr"],
-                              weight_decay=self.hparams["weight_decay"],
-                              betas=(self.hparams["beta1"], self.hparams["beta2"]), eps=self.hparams["eps"],
-                              mask_rate=self.mask_rate, seed=0, process_group=self.pg, use_graph=self.use_graph,
-                              fused=self.fused, force_collective_path=self.split and self.world == 1,
-                              targets_are_inputs=True, blocks_per_bucket=self.blocks_per_bucket,
-                              criterion=self._criterion, _share_state_with=self)
-            t.seed = self.seed
-            self._siblings[num_graphs] = t
-        t.mask_rate = self.mask_rate
-        t._metrics = self._metrics          # (device_metrics: the ragged batch writes the epoch's last record)
-        return t
-
-    def fit_epoch(self, store, batch_size: Optional[int] = None, shuffle: bool = True, drop_last: bool = False,
-                  generator: Optional[torch.Generator] = None, metric_fn_dict: Optional[Dict[str, Callable]] = None,
-                  device_metrics: bool = False) -> Tuple[float, Dict[str, float]]:
-        """One epoch over a ``SnapshotStore`` -- the loop of ``train_one_epoch`` (train.py:159-198): shuffled batches, a
-        fresh per-graph mask every batch, one optimisation step each, loss weighted by the batch's graph count.
-        Batches are row gathers of the device-resident store (no host collation, no H2D); a ragged last batch runs on
-        a sibling trainer that shares this one's optimizer state.  Returns ``(mean loss, metrics)``; metrics (the
-        reference's de-normalised per-batch metrics, train.py:179-198) are only computed when ``metric_fn_dict`` is
-        given, since they need a boolean gather per batch.  Under data parallelism every rank passes its own shard of
-        the snapshots (``dp.shard_graphs``).
-
-        ``device_metrics=True`` (with ``metric_fn_dict`` = ``evaluation.get_metric_fn_collection(prefix)``, the only collection
-        it computes): every step's forward is followed by the masked-metric moments launch (``gatres_masked_metrics``) inside
-        the same launch sequence -- the in-place epoch and the captured k-step sequences stay on -- and the metrics are formed
-        from the epoch's moment table at the end (``evaluation.metrics_from_moments``).  Training itself is untouched: the
-        same parameters, moments and loss bit for bit as without metrics.  ``device_metrics=False`` (default): nothing of
-        this runs."""
-        npg = store.nodes_per_graph
-        bs = int(batch_size) if batch_size is not None else self.num_graphs
-        if bs != self.num_graphs or npg * bs != self.N:
-            raise ValueError(f"this trainer was built for batches of {self.num_graphs} graphs x {self.N // max(self.num_graphs, 1)} nodes")
-        if self.world > 1:
-            drop_last = True                 # equal graph counts on every rank keep plain gradient averaging exact
-        if device_metrics:
-            return self._fit_epoch_device_metrics(store, bs, shuffle, drop_last, generator, metric_fn_dict)
-        # the epoch's loss sum in DOUBLE (train.py:196 accumulates Python floats): a sum of fp32 losses is exact there, so a
-        # sequence's k losses added at once and the same losses added one by one give the same bits
-        total = torch.zeros(1, dtype=torch.float64, device=self.device)
-        seen, sums = self._fit_epoch_sums(store, bs, shuffle, drop_last, generator, metric_fn_dict, total)
-        mean_loss = float(total.item()) / seen
-        return mean_loss, {k: v / seen for k, v in sums.items()}
-
-    def _fit_epoch_sums(self, store, bs: int, shuffle: bool, drop_last: bool, generator, metric_fn_dict,
-                        total: torch.Tensor, check: bool = True) -> Tuple[int, Dict[str, float]]:
-        """The body of ``fit_epoch``: the epoch's loss sum (loss x graphs, fp64) is ADDED to the device tensor ``total`` and never
-        read here; returns the graph count and the host metrics' sums.  ``check=False``: the caller looks for dropped steps
-        itself (``fit`` does, with the epoch's one read-back)."""
-        npg = store.nodes_per_graph
-        if self.world > 1:
-            drop_last = True
-        host_metrics = bool(metric_fn_dict)
-        sums = {k: 0.0 for k in (metric_fn_dict or {})}
-        seen = 0
-        # the epoch's snapshot order goes to the device ONCE; a batch is a slice of it, collated inside the mask sampler's
-        # launch (step_rows) -- the reference collates on the host and copies every iteration (train.py:302-303).  Runs of
-        # `epoch_graph_steps` full batches go through ONE captured sequence each (steps_rows); what is left -- the first step
-        # of a run whose transposed weights are not current, the epoch's last few batches, the ragged one -- goes step by step.
-        kseq = int(self.epoch_graph_steps)
-        if not (self.use_graph and self.fused and not self.split and self._rows_path_ok(store.data)):
-            kseq = 1                                     # (eager / data-parallel / per-op trainers: step by step)
-        order = store.epoch_order(shuffle=shuffle, generator=generator)
-        first = 0                                        # batches [0, first) are done by the in-place path below
-        nfull = store.num_snapshots // bs
-        if (kseq > 1 and not host_metrics and nfull >= 2 and self._mask_next and self.node_ptr is not None
-                and self._epoch_copy_fits(nfull * bs, npg)):
-            # The epoch's full batches as ONE device gather into a persistent buffer (the shuffled store: S x N_g floats), then
-            # trained IN PLACE, k per captured launch sequence, with the mask sampled ahead by the update launches -- the
-            # bound-batch step of bench.py, three launches and nothing else: no collation launch, no per-step host work.
-            self._epoch_in_place(store, order, nfull, kseq, total)
-            first, seen = nfull, nfull * bs
-        pending = []                                     # full batches waiting for a sequence
-
-        def flush(n_keep: int = 0):
-            nonlocal seen
-            while len(pending) > n_keep:
-                rows_one = pending.pop(0)
-                if not self.step_rows(store.data, rows_one):
-                    x = store.batch(rows_one)
-                    self.load_batch(x, x)
-                    self.run_step(device_mask=True)
-                total.add_(self.loss.double(), alpha=float(bs))
-                seen += bs
-
-        for rows, edge_index, ng in store.row_batches(bs, drop_last=drop_last, order=order, first=first):
-            if ng == bs and not host_metrics and kseq > 1:
-                pending.append(rows)
-                if len(pending) == kseq:
-                    # (row_batches yields consecutive slices of ONE order tensor: the run is its slice too)
-                    run = torch.cat(pending) if pending[0].data_ptr() + 8 * bs * (kseq - 1) != pending[-1].data_ptr() else \
-                        torch.as_strided(pending[0], (kseq * bs,), (1,))
-                    if self.steps_rows(store.data, run, total):
-                        seen += kseq * bs
-                        pending.clear()
-                    else:
-                        flush(n_keep=kseq - 1)           # one step by itself (it makes the weights current), then try again
-                continue
-            flush()
-            tr = self if ng == bs else self._sibling(ng, npg, edge_index)
-            if not tr.step_rows(store.data, rows):
-                x = store.batch(rows)
-                tr.load_batch(x, x)
-                tr.run_step(device_mask=True)
-            total.add_(tr.loss.double(), alpha=float(ng))
-            if host_metrics:
-                m = tr.mask.bool()
-                p, t = store.descale(tr.out[m]), store.descale(tr.x[m])
-                for k, fn in metric_fn_dict.items():
-                    sums[k] += float(fn(p, t)) * ng
-            seen += ng
-        flush()
-        if seen == 0:
-            raise ValueError("the store yielded no batch")
-        # a dropped step (a split launch whose workgroups were not co-resident) trained on nothing: an epoch that contains one
-        # is an error, not a slightly smaller epoch
-        if check:
-            self.check_no_dropped_steps()
-            for t in self._siblings.values():
-                t.check_no_dropped_steps()
-        return seen, sums
-
-    # ---- the training loop (train.py:340-535 `internal_train`) ------------------------------------------------------------
-    def _fit_buffers(self, epochs: int, val_batches: int) -> dict:
-        """Device and pinned-host buffers of ``fit``: the epoch's four sums {train loss sum, train graphs, validation loss sum,
-        validation graphs}, the controller's state, the history table, the best checkpoint, and the pinned block the epoch's
-        one read-back lands in (history record, validation moment table, the trainers' status words)."""
-        from .epoch_control import RECORD, STATE
-        from .evaluation import METRICS_RECORD
-        fb = getattr(self, "_fit", None)
-        dev = self.device
-        if fb is None:
-            f32 = dict(dtype=torch.float32, device=dev)
-            fb = self._fit = {"sums": torch.zeros(4, dtype=torch.float64, device=dev),
-                              "state": torch.zeros(STATE, dtype=torch.float64, device=dev),
-                              "best": [torch.zeros(self.P, **f32) for _ in range(3)],
-                              "best_step": torch.zeros(1, dtype=torch.int64, device=dev),
-                              "event": torch.cuda.Event(), "history": None, "host": None, "status_host": None}
-        if fb["history"] is None or fb["history"].shape[0] < epochs:
-            fb["history"] = torch.zeros((epochs, RECORD), dtype=torch.float64, device=dev)
-        rows = 1 + val_batches * METRICS_RECORD // RECORD
-        if fb["host"] is None or fb["host"].shape[0] < rows:
-            fb["host"] = torch.zeros((rows, RECORD), dtype=torch.float64).pin_memory()
-            fb["status_host"] = torch.zeros((8, 4), dtype=torch.int32).pin_memory()
-        fb["state"].zero_()
-        fb["state"][1] = float("inf")          # GATRES_EPOCH_S_BEST_LOSS
-        fb["state"][6] = float("inf")          # GATRES_EPOCH_S_SCHED_BEST
-        fb["best_valid"] = False
-        return fb
-
-    def _snapshot(self, restore: bool = False) -> None:
-        """``gatres_snapshot_if``: live state -> best buffers if the controller's `improved` flag is set (read on the device), or,
-        ``restore``, best buffers -> live state unconditionally."""
-        fb = self._fit
-        live = [self.model.flat_parameters, self.exp_avg, self.exp_avg_sq]
-        src, dst = (fb["best"], live) if restore else (live, fb["best"])
-        s_step, d_step = (fb["best_step"], self.step_counter) if restore else (self.step_counter, fb["best_step"])
-        flag = None if restore else fb["state"].data_ptr() + 8 * 8          # GATRES_EPOCH_S_IMPROVED
-        _native.check(self.lib.gatres_snapshot_if(flag, src[0].data_ptr(), src[1].data_ptr(), src[2].data_ptr(), s_step.data_ptr(),
-                                                  dst[0].data_ptr(), dst[1].data_ptr(), dst[2].data_ptr(), d_step.data_ptr(),
-                                                  self.P, _native.current_stream(self.device)), "gatres_snapshot_if")
-
-    def best_state(self) -> Dict[str, torch.Tensor]:
-        """The best epoch's checkpoint that ``fit`` keeps on the device, as tensors (clones): the flat ``params``, ``exp_avg``,
-        ``exp_avg_sq`` and the optimizer ``step`` (0-d int64).  Stream-ordered; nothing synchronises."""
-        fb = getattr(self, "_fit", None)
-        if fb is None or not fb.get("best_valid"):
-            raise RuntimeError("no best state: fit() has not run, or no epoch had a validation loss below +inf")
-        p, m, v = (t.clone() for t in fb["best"])
-        return {"params": p, "exp_avg": m, "exp_avg_sq": v, "step": fb["best_step"][0].clone()}
-
-    def _state_dict_of(self, flat: torch.Tensor) -> "OrderedDict[str, torch.Tensor]":
-        """``model.state_dict()`` with the values taken from another flat parameter vector (same layout)."""
-        base = self.model.flat_parameters
-        lo, hi = base.data_ptr(), base.data_ptr() + 4 * base.numel()
-        out = OrderedDict()
-        for k, v in self.model.state_dict().items():
-            if lo <= v.data_ptr() < hi:
-                off = (v.data_ptr() - lo) // 4
-                out[k] = flat[off:off + v.numel()].view(v.shape).clone()
-            else:
-                out[k] = v.clone()
-        return out
-
-    def fit(self, train_store, val_store, epochs: int, *, batch_size: Optional[int] = None, val_batch_size: Optional[int] = None,
-            patience: int = 100, min_delta: float = 1e-4, scheduler: Optional[str] = "ReduceLROnPlateau",
-            scheduler_patience: int = 2, shuffle: bool = True, generator: Optional[torch.Generator] = None, val_seed: int = 0,
-            train_metrics: bool = False, save_path: Optional[str] = None, model_name: Optional[str] = None,
-            variant: Optional[str] = None, save_best: str = "reference", restore_best: bool = False,
-            checkpoint_extra: Optional[dict] = None) -> "FitHistory":
-        """The reference's training loop (train.py:376-511 ``internal_train``) with its epoch boundary on the device.
-
-        Per epoch e = 1 .. ``epochs``: ``fit_epoch`` on ``train_store`` (with the ``"train"`` metric collection computed on the
-        device when ``train_metrics``); a validation pass over ``val_store`` in order, in batches of ``val_batch_size``
-        (default: ``batch_size``), with the trainer's ``mask_rate`` and device masks of seed ``val_seed + e`` --
-        ``evaluation.evaluate_store(model, val_store, val_batch_size, mask_rate, seed=val_seed + e, prefix="val",
-        gpu_warmup_times=0)``'s launches, plus one ``gatres_masked_loss`` launch per batch when the trainer's criterion is
-        ``mae`` / ``sce`` (the validation loss is the trainer's criterion, as in the reference); then ONE launch
-        (``gatres_epoch_control``) that forms both losses, keeps the best loss / epoch, runs
-        ``EarlyStopping(mode="min", min_delta, patience)`` (fp32, on ``torch.tensor(val_loss)`` as the reference does) and, unless
-        that stopped, ``ReduceLROnPlateau(mode="min", patience=scheduler_patience)`` (fp64, torch's defaults) writing the new
-        learning rate straight into the buffer the update kernels read (no capture, no copy); then ``gatres_snapshot_if``, which
-        keeps parameters, Adam moments and step count of an improving epoch in a device buffer.  The host reads one small
-        pinned block per epoch (one event wait) and learns from it whether to stop; ``hparams["lr"]`` follows the device.
-        ``scheduler``: ``"ReduceLROnPlateau"`` or ``None``.  ``epoch_control.EpochController`` states the controller in Python.
-
-        Checkpoints (``save_path`` given; ``wdn_io.save_checkpoint``, the reference's keys plus ``checkpoint_extra``):
-        ``last_{model_name}_{variant}.pth`` at epoch 1 and every 5th epoch unless the training loss is NaN;
-        ``best_{model_name}_{variant}.pth`` at every improving epoch (``save_best="reference"``) or once, from the device
-        snapshot, when ``fit`` returns (``"end"``: no file I/O inside improving epochs).  ``restore_best``: the best epoch's
-        parameters, moments and step count are loaded back at the end (``best_state()`` hands them out either way).
-
-        Data parallel: every rank passes its shards; the epoch's four sums are all-reduced (one collective per epoch), so all
-        ranks take the same decision; metric dicts describe the rank's own shard.  Returns a ``FitHistory``."""
-        from . import evaluation as E, wdn_io
-        from .epoch_control import RECORD_FIELDS
-        if save_best not in ("reference", "end"):
-            raise ValueError("save_best must be 'reference' or 'end'")
-        if scheduler not in (None, "ReduceLROnPlateau"):
-            raise ValueError("scheduler must be 'ReduceLROnPlateau' or None")
-        epochs = int(epochs)
-        if epochs <= 0:
-            raise ValueError("epochs must be positive")
-        if save_path is not None and (model_name is None or variant is None):
-            raise ValueError("save_path needs model_name and variant (the files are best_/last_{model_name}_{variant}.pth)")
-        bs = int(batch_size) if batch_size is not None else self.num_graphs
-        vbs = int(val_batch_size) if val_batch_size is not None else bs
-        if bs != self.num_graphs or train_store.nodes_per_graph * bs != self.N:
-            raise ValueError(f"this trainer was built for batches of {self.num_graphs} graphs x {self.N // max(self.num_graphs, 1)} nodes")
-        cfg = _native.GatresEpochConfig(float(min_delta), 0.1, 1e-4, 0.0, 1e-8, int(patience), int(scheduler_patience),
-                                        int(scheduler is not None), 0)
-        val = E._ValidationPass(self.model, val_store, vbs, self.mask_rate, self._criterion)
-        nvb = len(val.sizes)
-        fb = self._fit_buffers(epochs, nvb)
-        sums, state, history, host, status_host, event = (fb[k] for k in ("sums", "state", "history", "host", "status_host", "event"))
-        train_fns = E.get_metric_fn_collection("train") if train_metrics else None
-        R = {k: i for i, k in enumerate(RECORD_FIELDS)}
-        hist = FitHistory()
-        best_table = None
-        paths = None
-        if save_path is not None:
-            os.makedirs(save_path, exist_ok=True)
-            paths = {k: os.path.join(save_path, f"{k}_{model_name}_{variant}.pth") for k in ("best", "last")}
-        stats = dict(mean=train_store.mean, std=train_store.std, min=getattr(train_store, "min", None),
-                     max=getattr(train_store, "max", None), norm_type=train_store.norm_type)
-
-        def val_metrics(table) -> Dict[str, float]:
-            return E.metrics_from_moments(table, val.sizes, "val")[1]
-
-        def save(which: str, rec, table, model_sd=None, adam=None) -> None:
-            wdn_io.save_checkpoint(
-                paths[which], model_state_dict=self.model.state_dict() if model_sd is None else model_sd,
-                optimizer_state_dict=wdn_io.adam_state_dict(self, lr=rec[R["lr_used"]]) if adam is None else adam,
-                epoch=int(rec[R["best_epoch"]]), loss=float(rec[R["best_loss"]]), val_metric_dict=val_metrics(table),
-                **stats, **(checkpoint_extra or {}))
-
-        stream = _native.current_stream(self.device)
-        best_rec = None
-        for e in range(1, epochs + 1):
-            sums.zero_()
-            if train_metrics:
-                seen, tr_m = self._fit_epoch_device_metrics(train_store, bs, shuffle, self.world > 1, generator, train_fns,
-                                                            total=sums[0:1])
-                hist.train_metrics.append(tr_m)
-            else:
-                seen, _ = self._fit_epoch_sums(train_store, bs, shuffle, False, generator, None, sums[0:1], check=False)
-            sums[1:2].fill_(float(seen))
-            val.enqueue(val_seed + e)
-            if self.world > 1:
-                _native.check(self.lib.gatres_epoch_val_sums(_native.ptr(val.table if val.losses is None else None),
-                                                             _native.ptr(val.losses), val.graphs.data_ptr(), nvb,
-                                                             sums[2:].data_ptr(), stream), "gatres_epoch_val_sums")
-                dp.all_reduce_sums_(sums, self.pg)
-                _native.check(self.lib.gatres_epoch_control(sums.data_ptr(), None, None, None, 0, sums[2:].data_ptr(), C.byref(cfg),
-                                                            self.hp.data_ptr(), state.data_ptr(), history.data_ptr(),
-                                                            history.shape[0], stream), "gatres_epoch_control")
-            else:
-                _native.check(self.lib.gatres_epoch_control(sums.data_ptr(), _native.ptr(val.table if val.losses is None else None),
-                                                            _native.ptr(val.losses), val.graphs.data_ptr(), nvb, None, C.byref(cfg),
-                                                            self.hp.data_ptr(), state.data_ptr(), history.data_ptr(),
-                                                            history.shape[0], stream), "gatres_epoch_control")
-            self._snapshot()
-            # the epoch's one read-back: its history record, the validation moments and every trainer's status words
-            trainers = [t for t in [self] + list(self._siblings.values()) if t._status is not None][:status_host.shape[0]]
-            host[0].copy_(history[e - 1], non_blocking=True)
-            host[1:].view(-1)[:val.table.numel()].copy_(val.table.view(-1), non_blocking=True)
-            for i, t in enumerate(trainers):
-                status_host[i].copy_(t._status, non_blocking=True)
-            event.record(torch.cuda.current_stream(self.device))
-            event.synchronize()
-            rec = host[0].numpy().copy()
-            for i, t in enumerate(trainers):
-                t.check_no_dropped_steps((int(status_host[i, 1]), int(status_host[i, 3])))
-            self.hparams["lr"] = float(rec[R["lr_after"]])          # (the device buffer holds it already; siblings share the dict)
-            improved, stop = bool(rec[R["improved"]]), bool(rec[R["stop"]])
-            hist.tr_loss.append(float(rec[R["tr_loss"]])); hist.val_loss.append(float(rec[R["val_loss"]]))
-            hist.lr.append(float(rec[R["lr_used"]])); hist.improved.append(improved)
-            hist.records.append(rec)
-            if improved:
-                fb["best_valid"] = True
-                best_rec = rec
-                best_table = host[1:].view(-1)[:val.table.numel()].numpy().copy()
-                if paths is not None and save_best == "reference":
-                    save("best", rec, best_table)
-            if paths is not None and (e == 1 or e % 5 == 0) and not math.isnan(rec[R["tr_loss"]]):
-                save("last", rec, host[1:].view(-1)[:val.table.numel()].numpy())
-            if stop:
-                hist.stopped_epoch = e
-                break
-        hist.best_loss = float(rec[R["best_loss"]])
-        hist.best_epoch = int(rec[R["best_epoch"]])
-        hist.final_lr = float(rec[R["lr_after"]])
-        if best_table is not None:
-            hist.best_metric_dict = val_metrics(best_table)
-            if paths is not None and save_best == "end":
-                b = self.best_state()
-                save("best", best_rec, best_table, model_sd=self._state_dict_of(b["params"]),
-                     adam=wdn_io.adam_state_dict(self, exp_avg=b["exp_avg"], exp_avg_sq=b["exp_avg_sq"], step=int(b["step"]),
-                                                 lr=best_rec[R["lr_used"]]))
-        if restore_best and fb["best_valid"]:
-            self._snapshot(restore=True)
-            # the parameters and the step count moved behind every trainer of this model: transposed weights in scratch and a
-            # mask sampled ahead belong to the state that was replaced
-            self._count_native_update()
-            for t in [self] + list(self._siblings.values()):
-                t.invalidate_weights()
-                t._mask_sig = None
-        return hist
-
-
-class FitHistory:
-    """What ``GATResTrainer.fit`` returns: per-epoch lists -- ``tr_loss``, ``val_loss``, ``lr`` (the rate the epoch trained
-    with), ``improved`` -- ``best_loss``, ``best_epoch``, ``stopped_epoch`` (None: ran all epochs), ``best_metric_dict`` (the
-    validation metrics of the best epoch, keys of ``get_metric_fn_collection("val")``), ``train_metrics`` (one dict per epoch
-    when asked for), ``final_lr`` and ``records`` (the controller's raw history records, ``epoch_control.RECORD_FIELDS``)."""
-
-    def __init__(self) -> None:
-        self.tr_loss, self.val_loss, self.lr, self.improved, self.records, self.train_metrics = [], [], [], [], [], []
-        self.best_loss, self.best_epoch, self.stopped_epoch, self.final_lr = float("inf"), 0, None, None
-        self.best_metric_dict: Dict[str, float] = {}
-
-
-def internal_train(args, model: GATResMeanConv, train_store, val_store, **fit_kw):
-    """``train.py``'s ``internal_train`` over the native loop: an ``argparse.Namespace`` with train.py's names (``lr``,
-    ``weight_decay``, ``epochs``, ``mask_rate``, ``criterion``, ``batch_size``, ``patience``, ``min_delta``, ``scheduler``,
-    ``scheduler_patience``, ``use_gradient_clipping``, ``percentile``, ``save_path``, ``model_name``, ``variant``) becomes a
-    ``GATResTrainer`` and one ``fit`` call.  Returns ``(best_loss, best_metric_dict)``.  ``fit_kw`` goes to ``fit``
-    (``generator``, ``val_seed``, ``save_best``, ...)."""
-    bs = int(args.batch_size)
-    trainer = GATResTrainer(model, train_store.edge_index(bs), bs * train_store.nodes_per_graph,
-                            nodes_per_graph=[train_store.nodes_per_graph] * bs, lr=args.lr, weight_decay=args.weight_decay,
-                            mask_rate=args.mask_rate, targets_are_inputs=True, criterion=getattr(args, "criterion", None) or "mse",
-                            use_gradient_clipping=bool(getattr(args, "use_gradient_clipping", False)),
-                            percentile=float(getattr(args, "percentile", 10.0)))
-    hist = trainer.fit(train_store, val_store, int(args.epochs), batch_size=bs, patience=int(args.patience),
-                       min_delta=float(args.min_delta),
-                       scheduler="ReduceLROnPlateau" if getattr(args, "scheduler", None) == "ReduceLROnPlateau" else None,
-                       scheduler_patience=int(getattr(args, "scheduler_patience", 2)), save_path=getattr(args, "save_path", None),
-                       model_name=getattr(args, "model_name", None), variant=getattr(args, "variant", None), **fit_kw)
-    return hist.best_loss, hist.best_metric_dict

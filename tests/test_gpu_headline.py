@@ -267,6 +267,59 @@ def test_mask_sampled_by_the_update_launch_equals_the_samplers_own_launch(pkg, o
         assert torch.equal(a[2], b[2]), f"parameters after step {k}"
 
 
+def test_a_runner_whose_launch_sequence_raises_leaves_nothing_trusted(pkg, oracle, monkeypatch):
+    """Every step runner follows one rule when its launch sequence raises: an unknown part of it ran, so neither scratch's
+    transposed weights nor a mask sampled ahead is taken for current afterwards (and one update is counted, so that siblings
+    drop their transposes too).  ``_replay`` is replaced by a function that raises -- nothing is provoked on the device --
+    under ``steps_bound``'s own sequence, ``step_bound``, ``step`` and ``step_rows``; the real steps in between and after them
+    must give, bit for bit, what a trainer gives that ran only the real steps with every mask sampled by the sampler's own
+    launch (GATRES_NO_MASK_NEXT=1, as in the test above)."""
+    snaps = pkg.wdn_synth.make_snapshots(3 * BS, NODES, seed=23).cuda()
+    batches = [snaps[i * BS:(i + 1) * BS].reshape(-1).contiguous() for i in range(3)]
+    rows = torch.arange(BS, dtype=torch.int64, device="cuda")
+    real = [0, 1, 2, 0, 1, 2]
+
+    def failing(*a, **kw):
+        raise RuntimeError("launch sequence failed")
+
+    runs = []
+    for fail in (False, True):
+        if not fail:
+            monkeypatch.setenv("GATRES_NO_MASK_NEXT", "1")
+        else:
+            monkeypatch.delenv("GATRES_NO_MASK_NEXT", raising=False)
+        model, p, tr, ei = _trainer(pkg, oracle, seed=8, use_graph=True)
+        assert tr._mask_next == fail
+        tr.bind_batches(batches, precapture=False)
+        hist = []
+
+        def broken(call, updates_before):
+            tr._replay = failing                         # (shadows the method on this trainer only)
+            with pytest.raises(RuntimeError, match="launch sequence failed"):
+                call()
+            del tr._replay
+            assert tr._wt_sig is None and tr._mask_sig is None
+            assert model._native_updates == updates_before + 1
+
+        for n, i in enumerate(real):
+            if fail and n == 2:
+                # steady state (transposes current, a mask sampled ahead): steps_bound takes its own k-step sequence
+                assert tr._wt_current() and tr._mask_current()
+                broken(lambda: tr.steps_bound([0, 1]), model._native_updates)
+            if fail and n == 3:
+                broken(lambda: tr.step_bound(0), model._native_updates)
+                broken(lambda: tr.step(batches[1], batches[1]), model._native_updates)
+                broken(lambda: tr.step_rows(snaps, rows), model._native_updates)
+            tr.step_bound(i)
+            hist.append((tr.mask.clone(), float(tr.loss), model.flat_parameters.clone()))
+        assert tr.optimizer_step == len(real) and tr.fault_count == 0
+        runs.append(hist)
+    for k, (a, b) in enumerate(zip(*runs)):
+        assert torch.equal(a[0], b[0]), f"mask of step {k}"
+        assert a[1] == b[1], f"loss of step {k}"
+        assert torch.equal(a[2], b[2]), f"parameters after step {k}"
+
+
 def test_data_parallel_step_is_the_single_gpu_step_around_one_all_reduce(pkg, oracle):
     """Round 5: the multi-rank step of the fused path is the single-GPU step's own launches -- window
     kernel, parameter gradients, slab sum -- then ONE all-reduce of the flat gradient and the Adam launch, which samples the
