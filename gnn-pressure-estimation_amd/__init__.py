@@ -7,7 +7,9 @@ from .graph_models import GATConv, GATResMeanConv, GResBlockMeanConv, Linear, Si
 from .fused_adam import FusedAdam
 from .graph_plan import GraphPlan, PlanCache
 from .snapshot_store import SnapshotStore
+from .multi_snapshot_store import MultiSnapshotStore
 from .train_step import FitHistory, GATResTrainer, internal_train
 
 __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "SimpleConv", "Linear", "GraphPlan", "PlanCache",
-           "GATResTrainer", "FitHistory", "internal_train", "epoch_control", "select_model", "config_gatres_small", "config_gatres_large", "build_native", "wdn_synth", "dp", "evaluation", "wdn_io", "SnapshotStore"]
+           "GATResTrainer", "FitHistory", "internal_train", "epoch_control", "select_model", "config_gatres_small", "config_gatres_large", "build_native", "wdn_synth", "dp", "evaluation", "wdn_io", "SnapshotStore",
+           "MultiSnapshotStore"]

@@ -8,6 +8,14 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 
+def refuse_multi_store_data_parallel(world: int) -> None:
+    """A ``MultiSnapshotStore`` trains on one device: sharding a batch's recipe across ranks is not implemented."""
+    if world > 1:
+        raise NotImplementedError(f"data-parallel training (world size {world}) from a MultiSnapshotStore is not implemented: a "
+                                  f"batch's recipe would have to be sharded across the ranks; train each rank's networks from "
+                                  f"SnapshotStore shards or on one device")
+
+
 class EpochLoop:
     def _epoch_in_place(self, store, order: torch.Tensor, nfull: int, kseq: int, total: torch.Tensor) -> None:
         from .train_step import MAX_CACHED_GRAPHS
@@ -27,6 +35,11 @@ class EpochLoop:
             # sequences of k (one graph per run of the epoch and mask orientation), single steps where a run starts or ends
             self._max_graphs = max(self._max_graphs, MAX_CACHED_GRAPHS + 2 * (nfull // kseq + 1) + 2 * kseq + 8)
         torch.index_select(store.data, 0, order[:nfull * bs], out=buf)
+        self._train_epoch_buffer(nfull, kseq, total)
+
+    def _train_epoch_buffer(self, nfull: int, kseq: int, total: torch.Tensor) -> None:
+        """Train on the ``nfull`` batches that lie in the epoch buffer, ``kseq`` per captured launch sequence."""
+        bs = self.num_graphs
         eb, lseq = self._epoch_bound, self._epoch_losses
         j = 0
         while j < nfull:
@@ -38,6 +51,32 @@ class EpochLoop:
                 self._step_on(eb[j])       # (its slot names the buffers: a re-allocated epoch buffer never meets a stale graph)
                 total.add_(self.loss.double(), alpha=float(bs))
             j += k
+
+    def _epoch_in_place_multi(self, store, recipe, rows: torch.Tensor, nfull: int, kseq: int, total: torch.Tensor) -> None:
+        """``_epoch_in_place`` for a ``MultiSnapshotStore``: the epoch's full batches are gathered from the networks' matrices by
+        ONE launch (``gatres_gather_multi_rows``) into the buffer ``[nfull, N]``, batch by batch, and trained there."""
+        from . import _native
+        from .train_step import MAX_CACHED_GRAPHS
+        buf = self._epoch_buf
+        stride = self._epoch_stride()
+        if buf is None or tuple(buf.shape) != (nfull, stride):
+            if buf is not None:
+                self.release_epoch_buffer()
+            buf = self._epoch_buf = torch.empty(nfull, stride, dtype=torch.float32, device=self.device)
+            self._epoch_bound = [(buf[j, :self.N], buf[j, :self.N]) for j in range(nfull)]
+            self._epoch_losses = None
+        if self._epoch_losses is None or self._epoch_losses.numel() < max(kseq, 2):
+            self._epoch_losses = torch.zeros(max(kseq, 2), dtype=torch.float32, device=self.device)
+            self._max_graphs = max(self._max_graphs, MAX_CACHED_GRAPHS + 2 * (nfull // kseq + 1) + 2 * kseq + 8)
+        _native.check(self.lib.gatres_gather_multi_rows(
+            store.table.data_ptr(), store.num_networks, store.net_of_graph(recipe).data_ptr(), rows.data_ptr(),
+            self.node_ptr.data_ptr(), self.num_graphs, nfull, buf.data_ptr(), stride, _native.current_stream(self.device)),
+            "gatres_gather_multi_rows")
+        self._train_epoch_buffer(nfull, kseq, total)
+
+    def _epoch_stride(self) -> int:
+        """Floats between two batches of the multi-network epoch buffer: every batch starts on a 16-byte boundary."""
+        return (self.N + 3) // 4 * 4
 
     def _epoch_copy_fits(self, rows: int, npg: int) -> bool:
         """May ``fit_epoch`` keep a device copy of the epoch's shuffled batches (``rows`` x ``npg`` floats: as large as the store
@@ -75,8 +114,12 @@ class EpochLoop:
             scale, offset = float(store.std), float(store.mean)
         else:
             scale, offset = 1.0, 0.0
-        S = store.num_snapshots
-        sizes = [bs] * (S // bs) + ([S % bs] if S % bs and not drop_last else [])
+        from .multi_snapshot_store import MultiSnapshotStore
+        if isinstance(store, MultiSnapshotStore):
+            sizes = store.schedule(bs, self._multi_recipe(store, bs), drop_last).sizes
+        else:
+            S = store.num_snapshots
+            sizes = [bs] * (S // bs) + ([S % bs] if S % bs and not drop_last else [])
         if not sizes:
             raise ValueError("the store yielded no batch")
         table = self._metrics_table
@@ -106,11 +149,16 @@ class EpochLoop:
     def _sibling(self, num_graphs: int, nodes_per_graph: int, edge_index: torch.Tensor) -> "GATResTrainer":
         """Trainer for another batch size of the same dataset (the ragged last batch of an epoch): its own plan and
         buffers, the SAME model, Adam moments and step counter."""
+        return self._sibling_for(num_graphs, edge_index, [nodes_per_graph] * num_graphs)
+
+    def _sibling_for(self, key, edge_index: torch.Tensor, nodes_per_graph) -> "GATResTrainer":
+        """The sibling trainer kept under ``key`` (a graph count; ``("recipe", recipe)`` for a ``MultiSnapshotStore``'s tail
+        batch), built on first use for the batch that ``edge_index`` / ``nodes_per_graph`` describe."""
         from .train_step import GATResTrainer
-        t = self._siblings.get(num_graphs)
+        t = self._siblings.get(key)
         if t is None:
-            t = GATResTrainer(self.model, edge_index, num_graphs * nodes_per_graph,
-                              nodes_per_graph=[nodes_per_graph] * num_graphs, lr=self.hparams["lr"],
+            t = GATResTrainer(self.model, edge_index, sum(nodes_per_graph),
+                              nodes_per_graph=nodes_per_graph, lr=self.hparams["lr"],
                               weight_decay=self.hparams["weight_decay"],
                               betas=(self.hparams["beta1"], self.hparams["beta2"]), eps=self.hparams["eps"],
                               mask_rate=self.mask_rate, seed=0, process_group=self.pg, use_graph=self.use_graph,
@@ -118,10 +166,76 @@ class EpochLoop:
                               targets_are_inputs=True, blocks_per_bucket=self.blocks_per_bucket,
                               criterion=self._criterion, _share_state_with=self)
             t.seed = self.seed
-            self._siblings[num_graphs] = t
+            self._siblings[key] = t
         t.mask_rate = self.mask_rate
         t._metrics = self._metrics          # (device_metrics: the ragged batch writes the epoch's last record)
         return t
+
+    def _sibling_recipe(self, store, recipe) -> "GATResTrainer":
+        """``_sibling`` for a tail batch of a ``MultiSnapshotStore``: the trainer of another recipe, kept under the recipe --
+        single-store siblings stay under their graph counts."""
+        t = self._sibling_for(("recipe", tuple(recipe)), store.edge_index(recipe), store.nodes_per_graph(recipe))
+        t._recipe = tuple(recipe)
+        return t
+
+    def _multi_recipe(self, store, bs: int):
+        """The recipe this trainer's batches of ``bs`` graphs have in ``store`` (a ``MultiSnapshotStore``), checked against what
+        the trainer was built for."""
+        refuse_multi_store_data_parallel(self.world)
+        recipe = self._recipe if self._recipe is not None else store.recipe(bs)
+        if (bs != self.num_graphs or len(recipe) != store.num_networks or sum(recipe) != bs
+                or store.nodes_per_graph(recipe) != self._npg_list):
+            raise ValueError(f"this trainer was not built for batches of {bs} graphs of this store's recipe {tuple(recipe)}: "
+                             f"use GATResTrainer.for_store(model, store, batch_size)")
+        return tuple(recipe)
+
+    def _fit_epoch_multi_sums(self, store, bs: int, shuffle: bool, drop_last: bool, generator, metric_fn_dict,
+                              total: torch.Tensor, check: bool = True) -> Tuple[int, Dict[str, float]]:
+        """``_fit_epoch_sums`` over a ``MultiSnapshotStore``: the schedule's full batches through the in-place epoch buffer (one
+        gather launch per epoch, captured k-step sequences) where the single-store conditions hold, step by step through
+        ``gatres_stage_multi_rows_mask_required`` otherwise; every tail batch on the sibling trainer of its recipe.  The
+        epoch's rows go to the device once; nothing is read back per batch."""
+        recipe = self._multi_recipe(store, bs)
+        sched = store.schedule(bs, recipe, drop_last)
+        host_metrics = bool(metric_fn_dict)
+        sums = {k: 0.0 for k in (metric_fn_dict or {})}
+        if not sched.sizes:
+            raise ValueError("the store yielded no batch")
+        rows = store.epoch_rows(sched, shuffle=shuffle, generator=generator)
+        nfull = sched.nfull
+        kseq = int(self.epoch_graph_steps)
+        if not (self.use_graph and self.fused and not self.split):
+            kseq = 1
+        first = 0
+        if (kseq > 1 and not host_metrics and nfull >= 2 and self._mask_next and self.node_ptr is not None
+                and self._epoch_copy_fits(nfull, self._epoch_stride())):
+            self._epoch_in_place_multi(store, recipe, rows, nfull, kseq, total)
+            first = nfull
+        seen = first * bs
+
+        def one(tr, rcp, offset: int, ng: int) -> None:
+            nonlocal seen
+            tr._stage_multi(store, rcp, rows.data_ptr() + 8 * offset)
+            tr._step(True, premasked=True)
+            total.add_(tr.loss.double(), alpha=float(ng))
+            if host_metrics:
+                m = tr.mask.bool()
+                p, t = store.descale(tr.out[m]), store.descale(tr.x[m])
+                for k, fn in metric_fn_dict.items():
+                    sums[k] += float(fn(p, t)) * ng
+            seen += ng
+
+        for j in range(first, nfull):
+            one(self, recipe, j * bs, bs)
+        offset = nfull * bs
+        for t in sched.tails:
+            one(self._sibling_recipe(store, t), t, offset, sum(t))
+            offset += sum(t)
+        if check:
+            self.check_no_dropped_steps()
+            for t in self._siblings.values():
+                t.check_no_dropped_steps()
+        return seen, sums
 
     def fit_epoch(self, store, batch_size: Optional[int] = None, shuffle: bool = True, drop_last: bool = False,
                   generator: Optional[torch.Generator] = None, metric_fn_dict: Optional[Dict[str, Callable]] = None,
@@ -140,9 +254,11 @@ class EpochLoop:
         from the epoch's moment table at the end (``evaluation.metrics_from_moments``).  Training itself is untouched: the
         same parameters, moments and loss bit for bit as without metrics.  ``device_metrics=False`` (default): nothing of
         this runs."""
-        npg = store.nodes_per_graph
+        from .multi_snapshot_store import MultiSnapshotStore
         bs = int(batch_size) if batch_size is not None else self.num_graphs
-        if bs != self.num_graphs or npg * bs != self.N:
+        if isinstance(store, MultiSnapshotStore):
+            self._multi_recipe(store, bs)
+        elif bs != self.num_graphs or store.nodes_per_graph * bs != self.N:
             raise ValueError(f"this trainer was built for batches of {self.num_graphs} graphs x {self.N // max(self.num_graphs, 1)} nodes")
         if self.world > 1:
             drop_last = True                 # equal graph counts on every rank keep plain gradient averaging exact
@@ -160,6 +276,9 @@ class EpochLoop:
         """The body of ``fit_epoch``: the epoch's loss sum (loss x graphs, fp64) is ADDED to the device tensor ``total`` and never
         read here; returns the graph count and the host metrics' sums.  ``check=False``: the caller looks for dropped steps
         itself (``fit`` does, with the epoch's one read-back)."""
+        from .multi_snapshot_store import MultiSnapshotStore
+        if isinstance(store, MultiSnapshotStore):
+            return self._fit_epoch_multi_sums(store, bs, shuffle, drop_last, generator, metric_fn_dict, total, check)
         npg = store.nodes_per_graph
         if self.world > 1:
             drop_last = True

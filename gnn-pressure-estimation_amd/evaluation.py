@@ -250,12 +250,15 @@ def _check_reference_metrics(criterion, metric_fn_dict, prefix: str) -> None:
 class _EvalPlan:
     """Static buffers of one batch size: staged inputs / targets, mask, predictions, the plan and the forward's call state."""
 
-    def __init__(self, model, store, num_graphs: int):
-        npg = store.nodes_per_graph
-        self.num_graphs, self.num_nodes = num_graphs, num_graphs * npg
-        self.edge_index = store.edge_index(num_graphs)
+    def __init__(self, model, store, num_graphs: int, recipe=None):
+        if recipe is None:
+            npg = store.nodes_per_graph
+            self.num_nodes, self.edge_index, sizes = num_graphs * npg, store.edge_index(num_graphs), [npg] * num_graphs
+        else:          # a MultiSnapshotStore's batch: ``recipe[k]`` graphs of network k
+            self.num_nodes, self.edge_index, sizes = store.num_nodes(recipe), store.edge_index(recipe), store.nodes_per_graph(recipe)
+        self.num_graphs, self.recipe = num_graphs, recipe
         self.plan = model.plan_for(self.edge_index, self.num_nodes)
-        self.node_ptr = self.plan.node_ptr_for([npg] * num_graphs)
+        self.node_ptr = self.plan.node_ptr_for(sizes)
         dev = store.device
         self.x = torch.empty(self.num_nodes, dtype=torch.float32, device=dev)
         self.mask = torch.empty(self.num_nodes, dtype=torch.uint8, device=dev)
@@ -272,17 +275,20 @@ class _EvalPlan:
 # tensor by identity and hashes any other (a device hash and a read-back): the full and the ragged batch size alternate every
 # epoch, and each switch would cost a synchronisation.
 _EVAL_PLANS = weakref.WeakKeyDictionary()
+_EVAL_PLANS_MAX = 32          # (a multi-network schedule has one plan per distinct recipe: the main one and its tails)
 
 
-def _eval_plan(model, store, num_graphs: int) -> _EvalPlan:
-    ei = store.edge_index(num_graphs)
-    key = (ei.data_ptr(), ei._version, num_graphs * store.nodes_per_graph, str(ei.device), bool(model.fused))
+def _eval_plan(model, store, num_graphs: int, recipe=None) -> _EvalPlan:
+    ei = store.edge_index(num_graphs if recipe is None else recipe)
+    nodes = num_graphs * store.nodes_per_graph if recipe is None else store.num_nodes(recipe)
+    # (the recipe is part of the key: a one-network recipe shares its edge_index tensor with that network's SnapshotStore)
+    key = (ei.data_ptr(), ei._version, nodes, str(ei.device), bool(model.fused), None if recipe is None else tuple(recipe))
     plans = _EVAL_PLANS.setdefault(model, {})
     P = plans.get(key)
     if P is None or P.edge_index is not ei:
-        if len(plans) >= 8:
+        if len(plans) >= _EVAL_PLANS_MAX:
             plans.clear()
-        P = plans[key] = _EvalPlan(model, store, num_graphs)
+        P = plans[key] = _EvalPlan(model, store, num_graphs, recipe)
     return P.refresh(model)
 
 
@@ -294,6 +300,17 @@ def _enqueue_stage(lib, store, P: _EvalPlan, rows: torch.Tensor, mask_rate: floa
         store.data.data_ptr(), rows.data_ptr(), store.nodes_per_graph, P.x.data_ptr(), None, P.node_ptr.data_ptr(), P.num_graphs,
         float(mask_rate), seed64, step_ptr, _native.ptr(req_dev), num_required, P.mask.data_ptr(), stream),
         "gatres_stage_rows_mask_required")
+
+
+def _enqueue_stage_multi(lib, store, P: _EvalPlan, rows_ptr: int, mask_rate: float, seed64: int, step_ptr: int, req_ptr,
+                         req_idx, stream) -> None:
+    """``_enqueue_stage`` for a ``MultiSnapshotStore``: the rows (at device address ``rows_ptr``) name snapshots inside their
+    networks; the required nodes are a CSR per network."""
+    from . import _native
+    _native.check(lib.gatres_stage_multi_rows_mask_required(
+        store.table.data_ptr(), store.num_networks, store.net_of_graph(P.recipe).data_ptr(), rows_ptr, P.node_ptr.data_ptr(),
+        P.num_graphs, P.x.data_ptr(), None, float(mask_rate), seed64, step_ptr, _native.ptr(req_ptr), _native.ptr(req_idx),
+        P.mask.data_ptr(), stream), "gatres_stage_multi_rows_mask_required")
 
 
 def _enqueue_forward(lib, flat: torch.Tensor, P: _EvalPlan, stream) -> None:
@@ -334,6 +351,7 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
                    do_test_on_sensors: bool = False, required_idx: Sequence[int] = (), use_same_mask: bool = False,
                    seed: int = 0, gpu_warmup_times: int = 10, norm_type: Optional[str] = None,
                    criterion: Optional[Callable] = None, metric_fn_dict: Optional[Dict[str, Callable]] = None,
+                   per_network: bool = False, graphs_per_network: Optional[Sequence[int]] = None,
                    _capture: Optional[List] = None) -> Tuple[float, Dict[str, float]]:
     """``test_one_epoch`` over a ``SnapshotStore`` on the device: the same ``(loss, metrics)`` keys -- the reference's seven
     metrics, ``{prefix}_time`` (ms/graph) and ``{prefix}_throughput``, ``_sensor`` postfixed on the sensor pass.
@@ -351,20 +369,29 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
     ``norm_type``: ``None`` takes the store's (``znorm``: descaled with its mean / std; ``unused``: not descaled).
     Only ``MSELoss`` and ``get_metric_fn_collection(prefix)`` are computed; anything else passed as ``criterion`` /
     ``metric_fn_dict`` is refused -- ``get_criterion("mae")`` / ``("sce")`` included, whatever criterion the model was trained
-    with (the moment record carries no such sums): their validation loss comes from ``test_one_epoch``.  ``_capture`` (tests): a list that receives ``(mask, out, x, num_graphs)`` per batch."""
+    with (the moment record carries no such sums): their validation loss comes from ``test_one_epoch``.  ``_capture`` (tests): a list that receives ``(mask, out, x, num_graphs)`` per batch.
+
+    A ``MultiSnapshotStore`` is taken by its schedule (``store.schedule(batch_size, drop_last=False)``, the recipe the
+    default or ``graphs_per_network``), every network's snapshots in order, staged by ``gatres_stage_multi_rows_mask_required``.
+    ``required_idx`` is then a sequence of K sequences, one per network (sensor sets differ between networks).
+    ``per_network=True`` returns ``(loss, metrics, per_network)``: the third value lists, per network, ``{"loss": ..,
+    "{prefix}_error": .., ...}`` over that network's masked nodes only, each batch weighted by its graphs of that network --
+    from one more moments launch per network and batch over the network's node range; without it the launches are those of a
+    single store."""
     from . import _native
+    from .multi_snapshot_store import MultiSnapshotStore
     _check_reference_metrics(criterion, metric_fn_dict, prefix)
     if batch_size <= 0:
         raise ValueError("batch_size must be positive")
+    multi = isinstance(store, MultiSnapshotStore)
+    if not multi and (per_network or graphs_per_network is not None):
+        raise ValueError("per_network / graphs_per_network belong to a MultiSnapshotStore")
     scale, offset = _store_descale(store, norm_type)
-    npg, S = store.nodes_per_graph, len(store)
+    S = len(store)
     if S == 0:
         raise ValueError("empty store")
-    required = sorted(set(int(i) for i in required_idx)) if do_test_on_sensors else []
-    if required and (required[0] < 0 or required[-1] >= npg):
-        raise ValueError(f"required_idx must lie in [0, {npg})")
-    if int(npg * mask_rate) - len(required) <= 0:
-        raise ValueError("mask length must be positive")
+    cut = (_MultiBatches if multi else _SingleBatches)(store, batch_size, mask_rate, required_idx if do_test_on_sensors else None,
+                                                        graphs_per_network)
     postfix = "_sensor" if do_test_on_sensors else ""
     model.eval()
     if not model._flat_is_current():
@@ -374,21 +401,19 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
     if flat.device != dev:
         raise ValueError(f"model is on {flat.device}, the store on {dev}")
     lib = _native.load()
-    nb = (S + batch_size - 1) // batch_size
-    sizes = [min(batch_size, S - b * batch_size) for b in range(nb)]
+    sizes, nb = cut.sizes, len(cut.sizes)
     with torch.cuda.device(dev):
         stream = _native.current_stream(dev)
-        plans = {g: _eval_plan(model, store, g) for g in sorted(set(sizes))}
-        order = torch.arange(S, dtype=torch.int64, device=dev)
-        # the sampler's step of each batch: the batch index, or one mask per batch size under use_same_mask
-        steps = [(0 if g == batch_size else 1) if use_same_mask else b for b, g in enumerate(sizes)]
+        plans = cut.plans(model)
+        # the sampler's step of each batch: the batch index, or one mask per kind of batch under use_same_mask
+        steps = [cut.kind(b) if use_same_mask else b for b in range(nb)]
         # (uploads from pinned memory, asynchronous: a pageable copy would synchronise the stream; the host tensors stay
         #  alive until the epoch's synchronisation below)
         steps_host = torch.tensor(steps, dtype=torch.int64).pin_memory()
         steps_dev = steps_host.to(dev, non_blocking=True)
-        req_host = torch.tensor(required, dtype=torch.int32).pin_memory() if required else None
-        req_dev = req_host.to(dev, non_blocking=True) if required else None
+        pinned = cut.upload(pinned=True)
         table = torch.zeros((nb, METRICS_RECORD), dtype=torch.float64, device=dev)
+        net_tables = torch.zeros((store.num_networks, nb, METRICS_RECORD), dtype=torch.float64, device=dev) if per_network else None
         events = []
         seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF
 
@@ -396,9 +421,8 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
             _enqueue_forward(lib, flat, P, stream)
 
         for b, g in enumerate(sizes):
-            P = plans[g]
-            rows = order[b * batch_size: b * batch_size + g]
-            _enqueue_stage(lib, store, P, rows, mask_rate, seed64, steps_dev.data_ptr() + 8 * b, req_dev, len(required), stream)
+            P = plans[cut.keys[b]]
+            cut.stage(lib, P, b, mask_rate, seed64, steps_dev.data_ptr() + 8 * b, True, stream)
             if b == 0:
                 for _ in range(max(int(gpu_warmup_times), 0)):
                     forward(P)
@@ -408,11 +432,18 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
             end.record()
             events.append((start, end))
             _enqueue_moments(lib, P, scale, offset, table, b, stream)
+            if per_network:          # one more moments launch per network of the batch, over that network's node range
+                for k, (lo, hi) in enumerate(store.node_ranges(cut.keys[b])):
+                    if hi > lo:
+                        _native.check(lib.gatres_masked_metrics(
+                            P.out.data_ptr() + 4 * lo, P.x.data_ptr() + 4 * lo, P.mask.data_ptr() + lo, hi - lo, scale, offset,
+                            net_tables[k].data_ptr(), b, nb, None, stream), "gatres_masked_metrics")
             if _capture is not None:
                 _capture.append((P.mask.clone(), P.out.clone(), P.x.clone(), g))
         torch.cuda.synchronize(dev)
         host = table.cpu().numpy()
-        del steps_host, req_host
+        net_host = net_tables.cpu().numpy() if per_network else None
+        del steps_host, pinned
     timer = Timer()
     timer.timings = [s.elapsed_time(e) for s, e in events]
     timer.num_graphs = list(sizes)
@@ -420,7 +451,130 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
     key = list(metrics.keys())[0].split("_")[0]            # (test_one_epoch's derivation of the timing keys' prefix)
     metrics[key + "_time"] = timer.compute_time(S)
     metrics[key + "_throughput"] = timer.compute_throughput(S)
-    return loss, {k + postfix: v for k, v in metrics.items()}
+    metrics = {k + postfix: v for k, v in metrics.items()}
+    if not per_network:
+        return loss, metrics
+    nets = []
+    for k in range(store.num_networks):
+        used = [b for b, r in enumerate(cut.keys) if r[k] > 0]
+        if not used:
+            nets.append({})
+            continue
+        l_k, m_k = metrics_from_moments(net_host[k][used], [cut.keys[b][k] for b in used], prefix)
+        nets.append({"loss": l_k, **{name + postfix: v for name, v in m_k.items()}})
+    return loss, metrics, nets
+
+
+def required_csr(store, required_idx, mask_rate: float):
+    """Per-network required nodes of a ``MultiSnapshotStore`` as host CSR lists ``(req_ptr [K + 1], req_idx)``: ``required_idx``
+    must be a sequence of K sequences (a flat list is refused for K > 1: sensor sets belong to a network), every index inside
+    its network, and every network must keep a positive sampled part (utils/auxil.py:151-153)."""
+    K = store.num_networks
+    seq = list(required_idx)
+    flat = all(isinstance(i, (int, np.integer)) for i in seq)
+    if flat and seq and K > 1:
+        raise ValueError(f"required_idx is a flat list, the store holds {K} networks: pass one sequence per network")
+    if flat:
+        seq = [seq] + [[] for _ in range(K - 1)] if seq else [[] for _ in range(K)]
+    if len(seq) != K:
+        raise ValueError(f"required_idx holds {len(seq)} sequences for {K} networks")
+    ptr, idx = [0], []
+    for k, r in enumerate(seq):
+        r = sorted(set(int(i) for i in r))
+        n = store.nodes_per_graph_of(k)
+        if r and (r[0] < 0 or r[-1] >= n):
+            raise ValueError(f"required_idx of network {k} must lie in [0, {n})")
+        if int(n * mask_rate) - len(r) <= 0:
+            raise ValueError(f"mask length must be positive (network {k})")
+        idx += r
+        ptr.append(len(idx))
+    return ptr, idx
+
+
+class _SingleBatches:
+    """How an evaluation pass cuts a ``SnapshotStore`` into batches -- in order, ``batch_size`` at a time, a ragged last one --
+    and stages batch ``b``.  ``keys[b]`` names the batch's plan (its graph count); ``required``: the sensor nodes (None: no
+    sensor pass)."""
+
+    def __init__(self, store, batch_size: int, mask_rate: float, required=None, graphs_per_network=None):
+        npg, S = store.nodes_per_graph, len(store)
+        self.required = sorted(set(int(i) for i in required)) if required is not None else []
+        if self.required and (self.required[0] < 0 or self.required[-1] >= npg):
+            raise ValueError(f"required_idx must lie in [0, {npg})")
+        if int(npg * mask_rate) - len(self.required) <= 0:
+            raise ValueError("mask length must be positive")
+        self.store, self.batch_size = store, int(batch_size)
+        nb = (S + batch_size - 1) // batch_size
+        self.sizes = [min(batch_size, S - b * batch_size) for b in range(nb)]
+        self.keys = list(self.sizes)
+        self.offsets = [b * batch_size for b in range(nb)]
+        self.rows = self.req = None
+
+    def kind(self, b: int) -> int:
+        """Which of the pass's batch shapes batch ``b`` has (``use_same_mask``: one mask per shape)."""
+        return 0 if self.sizes[b] == self.batch_size else 1
+
+    def plans(self, model) -> dict:
+        return {g: _eval_plan(model, self.store, g) for g in sorted(set(self.sizes))}
+
+    def upload(self, pinned: bool) -> list:
+        """Rows and required nodes onto the device; returns the pinned host tensors, to be kept alive until the pass's
+        synchronisation (``pinned=False``: plain copies, for buffers made once)."""
+        dev = self.store.device
+        self.rows = torch.arange(len(self.store), dtype=torch.int64, device=dev)
+        keep = []
+        if self.required:
+            host = torch.tensor(self.required, dtype=torch.int32)
+            keep = [host.pin_memory()] if pinned else [host]
+            self.req = keep[0].to(dev, non_blocking=pinned)
+        return keep
+
+    def stage(self, lib, P: _EvalPlan, b: int, mask_rate: float, seed64: int, step_ptr: int, sensors: bool, stream) -> None:
+        rows = self.rows[self.offsets[b]: self.offsets[b] + self.sizes[b]]
+        _enqueue_stage(lib, self.store, P, rows, mask_rate, seed64, step_ptr, self.req if sensors else None,
+                       len(self.required) if sensors else 0, stream)
+
+
+class _MultiBatches(_SingleBatches):
+    """``_SingleBatches`` for a ``MultiSnapshotStore``: the batches of its in-order schedule (``drop_last=False``), a plan per
+    distinct recipe (``keys[b]``: batch b's recipe), staged by ``gatres_stage_multi_rows_mask_required`` with the required
+    nodes as a CSR per network."""
+
+    def __init__(self, store, batch_size: int, mask_rate: float, required=None, graphs_per_network=None):
+        self.req_ptr_l, self.req_idx_l = required_csr(
+            store, required if required is not None else [[] for _ in range(store.num_networks)], mask_rate)
+        self.store, self.batch_size = store, int(batch_size)
+        recipe = store.recipe(batch_size, graphs_per_network)
+        self.schedule = store.schedule(batch_size, recipe, drop_last=False)
+        self.keys = [self.schedule.recipe] * self.schedule.nfull + list(self.schedule.tails)
+        self.sizes = self.schedule.sizes
+        self.offsets = [0]
+        for r in self.keys[:-1]:
+            self.offsets.append(self.offsets[-1] + sum(r))
+        self.kinds = list(dict.fromkeys(self.keys))
+        self.rows = self.req = self.req_ptr = None
+
+    def kind(self, b: int) -> int:
+        return self.kinds.index(self.keys[b])
+
+    def plans(self, model) -> dict:
+        return {r: _eval_plan(model, self.store, sum(r), r) for r in self.kinds}
+
+    def upload(self, pinned: bool) -> list:
+        dev = self.store.device
+        host = [self.store.epoch_rows_host(self.schedule, shuffle=False)]
+        if self.req_idx_l:
+            host += [torch.tensor(self.req_ptr_l, dtype=torch.int32), torch.tensor(self.req_idx_l, dtype=torch.int32)]
+        keep = [t.pin_memory() for t in host] if pinned else host
+        on_dev = [t.to(dev, non_blocking=pinned) for t in keep]
+        self.rows = on_dev[0]
+        if self.req_idx_l:
+            self.req_ptr, self.req = on_dev[1], on_dev[2]
+        return keep
+
+    def stage(self, lib, P: _EvalPlan, b: int, mask_rate: float, seed64: int, step_ptr: int, sensors: bool, stream) -> None:
+        _enqueue_stage_multi(lib, self.store, P, self.rows.data_ptr() + 8 * self.offsets[b], mask_rate, seed64, step_ptr,
+                             self.req_ptr if sensors else None, self.req if sensors else None, stream)
 
 
 class _ValidationPass:
@@ -429,36 +583,37 @@ class _ValidationPass:
     loss goes into a per-batch array (the reference's ``criterion(y_pred, y_true)``).  Nothing is read back and nothing
     synchronises: the moment table, the loss array and the per-batch graph counts stay on the device for
     ``gatres_epoch_control``.  Everything static (row order, sampler steps, graph counts, tables) is made once; with the same
-    ``seed`` the moment table is bit for bit the one ``evaluate_store(seed=seed, gpu_warmup_times=0)`` forms."""
+    ``seed`` the moment table is bit for bit the one ``evaluate_store(seed=seed, gpu_warmup_times=0)`` forms.  ``store``: a
+    ``SnapshotStore`` or a ``MultiSnapshotStore`` (then the batches are its in-order schedule's)."""
 
     def __init__(self, model, store, batch_size: int, mask_rate: float, criterion: str = "mse"):
         from . import _native
+        from .multi_snapshot_store import MultiSnapshotStore
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
-        S = len(store)
-        if S == 0:
+        if len(store) == 0:
             raise ValueError("empty store")
-        if int(store.nodes_per_graph * mask_rate) <= 0:
-            raise ValueError("mask length must be positive")
+        multi = isinstance(store, MultiSnapshotStore)
+        self.cut = (_MultiBatches if multi else _SingleBatches)(store, int(batch_size), float(mask_rate))
+        self.cut.upload(pinned=False)
         self.model, self.store, self.batch_size, self.mask_rate = model, store, int(batch_size), float(mask_rate)
         self.criterion = _native.CRITERIA[criterion]
         self.scale, self.offset = _store_descale(store, None)
         dev = store.device
-        nb = (S + batch_size - 1) // batch_size
-        self.sizes = [min(batch_size, S - b * batch_size) for b in range(nb)]
-        self.order = torch.arange(S, dtype=torch.int64, device=dev)
+        self.sizes = self.cut.sizes
+        nb = len(self.sizes)
         self.steps = torch.arange(nb, dtype=torch.int64, device=dev)          # the sampler's step of a batch: its index
-        self.graphs = torch.full((nb,), batch_size, dtype=torch.int32, device=dev)
-        self.graphs[nb - 1:].fill_(self.sizes[-1])
+        self.graphs = torch.tensor(self.sizes, dtype=torch.int32).to(dev)
         self.table = torch.zeros((nb, METRICS_RECORD), dtype=torch.float64, device=dev)
         self.losses = self.g_out = None
         if self.criterion != _native.LOSS_MSE:
+            nodes = max(store.num_nodes(r) for r in self.cut.keys) if multi else batch_size * store.nodes_per_graph
             self.losses = torch.zeros(nb, dtype=torch.float32, device=dev)
-            self.g_out = torch.empty(batch_size * store.nodes_per_graph, dtype=torch.float32, device=dev)
+            self.g_out = torch.empty(nodes, dtype=torch.float32, device=dev)
 
     def enqueue(self, seed: int, _capture: Optional[List] = None) -> None:
         from . import _native
-        model, store = self.model, self.store
+        model, store, cut = self.model, self.store, self.cut
         flat = model.flat_parameters
         if flat.device != store.device:
             raise ValueError(f"model is on {flat.device}, the store on {store.device}")
@@ -466,11 +621,10 @@ class _ValidationPass:
         seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF
         with torch.cuda.device(store.device):
             stream = _native.current_stream(store.device)
-            plans = {g: _eval_plan(model, store, g) for g in sorted(set(self.sizes))}
+            plans = cut.plans(model)
             for b, g in enumerate(self.sizes):
-                P = plans[g]
-                rows = self.order[b * self.batch_size: b * self.batch_size + g]
-                _enqueue_stage(lib, store, P, rows, self.mask_rate, seed64, self.steps.data_ptr() + 8 * b, None, 0, stream)
+                P = plans[cut.keys[b]]
+                cut.stage(lib, P, b, self.mask_rate, seed64, self.steps.data_ptr() + 8 * b, False, stream)
                 _enqueue_forward(lib, flat, P, stream)
                 _enqueue_moments(lib, P, self.scale, self.offset, self.table, b, stream)
                 if self.losses is not None:

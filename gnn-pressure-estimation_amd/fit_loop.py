@@ -120,8 +120,18 @@ class FitLoop:
             raise ValueError("save_path needs model_name and variant (the files are best_/last_{model_name}_{variant}.pth)")
         bs = int(batch_size) if batch_size is not None else self.num_graphs
         vbs = int(val_batch_size) if val_batch_size is not None else bs
-        if bs != self.num_graphs or train_store.nodes_per_graph * bs != self.N:
+        from .multi_snapshot_store import MultiSnapshotStore
+        multi = isinstance(train_store, MultiSnapshotStore)
+        if multi:
+            # (several networks: the batch's recipe is the trainer's, GATResTrainer.for_store; one device only)
+            self._multi_recipe(train_store, bs)
+            if isinstance(val_store, MultiSnapshotStore) and val_store.num_networks != train_store.num_networks:
+                raise ValueError(f"the validation store holds {val_store.num_networks} networks, the training store "
+                                 f"{train_store.num_networks}: a multi-network validation store must have the same networks")
+        elif bs != self.num_graphs or train_store.nodes_per_graph * bs != self.N:
             raise ValueError(f"this trainer was built for batches of {self.num_graphs} graphs x {self.N // max(self.num_graphs, 1)} nodes")
+        if isinstance(val_store, MultiSnapshotStore) and not multi:
+            raise ValueError("a multi-network validation store needs a multi-network training store (same number of networks)")
         cfg = _native.GatresEpochConfig(float(min_delta), 0.1, 1e-4, 0.0, 1e-8, int(patience), int(scheduler_patience),
                                         int(scheduler is not None), 0)
         val = E._ValidationPass(self.model, val_store, vbs, self.mask_rate, self._criterion)
@@ -241,11 +251,11 @@ def internal_train(args, model: GATResMeanConv, train_store, val_store, **fit_kw
     (``generator``, ``val_seed``, ``save_best``, ...)."""
     from .train_step import GATResTrainer
     bs = int(args.batch_size)
-    trainer = GATResTrainer(model, train_store.edge_index(bs), bs * train_store.nodes_per_graph,
-                            nodes_per_graph=[train_store.nodes_per_graph] * bs, lr=args.lr, weight_decay=args.weight_decay,
-                            mask_rate=args.mask_rate, targets_are_inputs=True, criterion=getattr(args, "criterion", None) or "mse",
-                            use_gradient_clipping=bool(getattr(args, "use_gradient_clipping", False)),
-                            percentile=float(getattr(args, "percentile", 10.0)))
+    # (a SnapshotStore or, for several networks, a MultiSnapshotStore: the batch's composition is the store's default recipe)
+    trainer = GATResTrainer.for_store(model, train_store, bs, lr=args.lr, weight_decay=args.weight_decay,
+                                      mask_rate=args.mask_rate, criterion=getattr(args, "criterion", None) or "mse",
+                                      use_gradient_clipping=bool(getattr(args, "use_gradient_clipping", False)),
+                                      percentile=float(getattr(args, "percentile", 10.0)))
     hist = trainer.fit(train_store, val_store, int(args.epochs), batch_size=bs, patience=int(args.patience),
                        min_delta=float(args.min_delta),
                        scheduler="ReduceLROnPlateau" if getattr(args, "scheduler", None) == "ReduceLROnPlateau" else None,

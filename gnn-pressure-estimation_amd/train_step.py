@@ -242,6 +242,7 @@ class GATResTrainer(EpochLoop, FitLoop):
         self.scratch = model._scratch_for(self.plan)
         self.node_ptr = self.plan.node_ptr_for(nodes_per_graph) if nodes_per_graph is not None else None
         self.num_graphs = len(nodes_per_graph) if nodes_per_graph is not None else 0
+        self._npg_list = [int(n) for n in nodes_per_graph] if nodes_per_graph is not None else None
         self.pg = process_group
         self.world, self.rank = 1, 0
         if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
@@ -300,7 +301,27 @@ class GATResTrainer(EpochLoop, FitLoop):
         self._rows_win = self._loss_seq = None
         self._epoch_buf = self._epoch_bound = self._epoch_losses = None
         self._fit: Optional[dict] = None
+        self._recipe = None                  # for_store() on a MultiSnapshotStore: the batch's graphs per network
         self._warn_if_the_chip_is_not_ours()
+
+    @classmethod
+    def for_store(cls, model: GATResMeanConv, store, batch_size: int, graphs_per_network: Optional[Sequence[int]] = None,
+                  **kw) -> "GATResTrainer":
+        """The trainer of ``fit_epoch(store)`` / ``fit(store, ...)`` for batches of ``batch_size`` graphs: ``edge_index``, node
+        count and per-graph node counts come from the store, targets are the inputs.  ``store``: a ``SnapshotStore`` or a
+        ``MultiSnapshotStore`` -- for the latter the batch's composition is the store's default recipe (proportional to the
+        networks' snapshot counts) or ``graphs_per_network``.  ``kw``: the constructor's other arguments."""
+        from .multi_snapshot_store import MultiSnapshotStore
+        kw.setdefault("targets_are_inputs", True)
+        if isinstance(store, MultiSnapshotStore):
+            recipe = store.recipe(batch_size, graphs_per_network)
+            t = cls(model, store.edge_index(recipe), store.num_nodes(recipe), nodes_per_graph=store.nodes_per_graph(recipe), **kw)
+            t._recipe = recipe
+            return t
+        if graphs_per_network is not None:
+            raise ValueError("graphs_per_network belongs to a MultiSnapshotStore")
+        bs = int(batch_size)
+        return cls(model, store.edge_index(bs), bs * store.nodes_per_graph, nodes_per_graph=[store.nodes_per_graph] * bs, **kw)
 
     def _warn_if_the_chip_is_not_ours(self) -> None:
         """A split launch (several workgroups per snapshot, spin-waiting on each other's granules) needs EVERY workgroup of
@@ -750,6 +771,15 @@ class GATResTrainer(EpochLoop, FitLoop):
             None if self.targets_are_inputs else self.y.data_ptr(), self.node_ptr.data_ptr(), self.num_graphs, self.mask_rate,
             self.seed, self.step_counter.data_ptr(), self.mask.data_ptr(), _native.current_stream(self.device)),
             "gatres_stage_rows_mask")
+
+    def _stage_multi(self, store, recipe, rows_ptr: int) -> None:
+        """``_stage_rows`` for a ``MultiSnapshotStore``: the batch's graphs come from several matrices (``recipe``: how many
+        of each network; ``rows_ptr``: their int64 rows, each inside its network), collated and masked in one launch."""
+        _native.check(self.lib.gatres_stage_multi_rows_mask_required(
+            store.table.data_ptr(), store.num_networks, store.net_of_graph(recipe).data_ptr(), rows_ptr, self.node_ptr.data_ptr(),
+            self.num_graphs, self.x.data_ptr(), None if self.targets_are_inputs else self.y.data_ptr(), self.mask_rate, self.seed,
+            self.step_counter.data_ptr(), None, None, self.mask.data_ptr(), _native.current_stream(self.device)),
+            "gatres_stage_multi_rows_mask_required")
 
     def steps_rows(self, data: torch.Tensor, rows: torch.Tensor, total: Optional[torch.Tensor] = None) -> bool:
         """``step_rows`` for k consecutive batches -- ``rows`` is a device int64 ``[k * num_graphs]`` slice of an epoch's

@@ -371,12 +371,8 @@ def load_adam_state_dict(trainer, state_dict: dict) -> None:
 
 
 # --------------------------------------------------------------------------------------------------------- all of it
-def load_wdn(inp_path: str, zip_path: str, feature: str = "pressure", split: str = "train",
-             removal: str = "keep_junction", num_records: Optional[int] = None, device=None, **store_kw):
-    """``WDNDataset.collect`` + ``compute_stats`` for one file pair (DataLoader.py:206-258, :120-147): the ``feature`` array
-    of ``split``, its columns restricted to the kept nodes (``np.take(array, taken_indices, axis=-1)`` over
-    ``wn.node_name_list``), on the device as a ``SnapshotStore`` together with the junction-subgraph ``edge_index``."""
-    from .snapshot_store import SnapshotStore
+def _load_wdn_arrays(inp_path: str, zip_path: str, feature: str, split: str, removal: str, num_records: Optional[int]):
+    """One file pair's ``(snapshots fp32 [S, N_kept], edge_index, kept node names)`` on the host."""
     inp = parse_inp(inp_path)
     edge_index, kept = inp_edge_index(inp, removal)
     root = ZarrZip(zip_path)
@@ -394,5 +390,37 @@ def load_wdn(inp_path: str, zip_path: str, feature: str = "pressure", split: str
     if arr.shape[-1] < len(order):
         raise ValueError(f"the store has {arr.shape[-1]} columns, the network {len(order)} nodes")
     arr = np.take(arr, cols, axis=-1)
-    store = SnapshotStore(torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)), edge_index, device=device, **store_kw)
+    return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)), edge_index, kept
+
+
+def load_wdn(inp_path: str, zip_path: str, feature: str = "pressure", split: str = "train",
+             removal: str = "keep_junction", num_records: Optional[int] = None, device=None, **store_kw):
+    """``WDNDataset.collect`` + ``compute_stats`` for one file pair (DataLoader.py:206-258, :120-147): the ``feature`` array
+    of ``split``, its columns restricted to the kept nodes (``np.take(array, taken_indices, axis=-1)`` over
+    ``wn.node_name_list``), on the device as a ``SnapshotStore`` together with the junction-subgraph ``edge_index``."""
+    from .snapshot_store import SnapshotStore
+    snaps, edge_index, kept = _load_wdn_arrays(inp_path, zip_path, feature, split, removal, num_records)
+    store = SnapshotStore(snaps, edge_index, device=device, **store_kw)
     return store, kept
+
+
+def load_wdns(input_paths, zip_paths, feature: str = "pressure", split: str = "train", removal: str = "keep_junction",
+              num_records=None, mean: Optional[float] = None, std: Optional[float] = None, device=None, **store_kw):
+    """The list form of ``load_wdn`` (``WDNDataset`` takes lists of ``.inp`` / ``.zip`` paths, DataLoader.py:61-183; train.py's
+    ``--input_paths`` / ``--dataset_paths``): one network per file pair, all on the device as ONE ``MultiSnapshotStore``
+    whose statistics are taken over all networks' arrays together -- or are ``mean`` / ``std`` (a validation or test split
+    takes the training store's, train.py:67-86).  ``num_records``: an int for every network or one value per network.
+    Returns ``(store, kept)``, ``kept`` the kept node names per network."""
+    from .multi_snapshot_store import MultiSnapshotStore
+    input_paths, zip_paths = list(input_paths), list(zip_paths)
+    if not input_paths or len(input_paths) != len(zip_paths):
+        raise ValueError(f"{len(input_paths)} input paths for {len(zip_paths)} dataset paths")
+    records = list(num_records) if isinstance(num_records, (list, tuple)) else [num_records] * len(input_paths)
+    if len(records) != len(input_paths):
+        raise ValueError(f"num_records holds {len(records)} values for {len(input_paths)} networks")
+    networks, kept = [], []
+    for inp_path, zip_path, n in zip(input_paths, zip_paths, records):
+        snaps, edge_index, names = _load_wdn_arrays(inp_path, zip_path, feature, split, removal, n)
+        networks.append((snaps, edge_index))
+        kept.append(names)
+    return MultiSnapshotStore(networks, device=device, mean=mean, std=std, **store_kw), kept

@@ -26,6 +26,9 @@
 extern "C" {
 #endif
 
+/* 9 also after gatres_stage_multi_rows_mask_required and gatres_gather_multi_rows were added: two new symbols, no existing
+ * signature or struct changed, so a library of ABI 9 exists with and without them.  gatres_version()'s build id (a hash of
+ * the sources) tells such libraries apart; _native.load() checks it. */
 #define GATRES_ABI_VERSION 9
 
 #define GATRES_E_BADARG      (-1)  /* null pointer, negative size, misaligned pointer            */
@@ -294,6 +297,27 @@ int gatres_stage_rows_mask_required(const float* data, const int64_t* rows, int3
                                     const int32_t* node_ptr, int32_t num_graphs, double mask_rate, uint64_t seed,
                                     const uint64_t* step_counter, const int32_t* required, int32_t num_required, uint8_t* mask,
                                     void* stream);
+
+/* gatres_stage_rows_mask_required for a batch whose graphs come from SEVERAL snapshot matrices (one [S_k][N_k] matrix per
+ * water network; utils/DataLoader.py:61-183 takes lists of networks): src_table[num_networks] (device) holds the matrices'
+ * device addresses; graph g is row rows[g] (device, int64) of matrix net_of_graph[g] (device, int32), node_ptr[g + 1] -
+ * node_ptr[g] floats wide -- the caller guarantees that this is the matrix's row length and that the row exists -- and goes
+ * to x_dst + node_ptr[g] (and y_dst likewise when given).  Required nodes are a CSR per network: network k's sensor nodes
+ * are req_idx[req_ptr[k] .. req_ptr[k + 1]) (device, int32; indices inside a graph, distinct, fewer than int(N_k * mask_rate));
+ * req_ptr == NULL (then req_idx == NULL too): none.  The sampler and its keys (seed, step, node) are those of the entry
+ * points above: with one network the call writes the x and the mask bytes of gatres_stage_rows_mask_required.  A graph whose
+ * table entry is out of range or null is not copied. */
+int gatres_stage_multi_rows_mask_required(const float* const* src_table, int32_t num_networks, const int32_t* net_of_graph,
+                                          const int64_t* rows, const int32_t* node_ptr, int32_t num_graphs, float* x_dst,
+                                          float* y_dst, double mask_rate, uint64_t seed, const uint64_t* step_counter,
+                                          const int32_t* req_ptr, const int32_t* req_idx, uint8_t* mask, void* stream);
+
+/* The gather of gatres_stage_multi_rows_mask_required alone, for num_batches batches of the same composition in ONE launch:
+ * rows[num_batches * num_graphs]; graph g of batch b goes to dst + b * batch_stride + node_ptr[g] (batch_stride in floats).
+ * An epoch's full batches laid out batch by batch in one buffer. */
+int gatres_gather_multi_rows(const float* const* src_table, int32_t num_networks, const int32_t* net_of_graph,
+                             const int64_t* rows, const int32_t* node_ptr, int32_t num_graphs, int32_t num_batches, float* dst,
+                             int64_t batch_stride, void* stream);
 
 /* Masked-metric moments of one batch (evaluation.get_metric_fn_collection + MSELoss, utils/auxil.py:101-140,185-203):
  * one record of GATRES_METRICS_RECORD doubles into table[slot] (slot += *cursor when cursor != NULL; the kernel then
