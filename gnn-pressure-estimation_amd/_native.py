@@ -153,6 +153,9 @@ SIGNATURES = {
     "gatres_epoch_control": (C.c_int, [_P, _P, _P, _P, _I32, _P, C.POINTER(GatresEpochConfig), _P, _P, _P, _I32, _P]),
     "gatres_epoch_val_sums": (C.c_int, [_P, _P, _P, _I32, _P, _P]),
     "gatres_snapshot_if": (C.c_int, [_P] * 9 + [_I64, _P]),
+    "gatres_grad_flow": (C.c_int, [_MP, _P, _F64, _P, _P, _P]),
+    "gatres_grad_flow_count": (_I32, [_I32, _I32]),
+    "gatres_mean_abs_diff": (C.c_int, [_P, _P, _I64, _P, _P]),
     "gatres_version": (C.c_char_p, []),
 }
 

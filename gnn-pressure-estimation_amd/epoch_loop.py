@@ -212,11 +212,13 @@ class EpochLoop:
             self._epoch_in_place_multi(store, recipe, rows, nfull, kseq, total)
             first = nfull
         seen = first * bs
+        last = self
 
         def one(tr, rcp, offset: int, ng: int) -> None:
-            nonlocal seen
+            nonlocal seen, last
             tr._stage_multi(store, rcp, rows.data_ptr() + 8 * offset)
             tr._step(True, premasked=True)
+            last = tr
             total.add_(tr.loss.double(), alpha=float(ng))
             if host_metrics:
                 m = tr.mask.bool()
@@ -231,6 +233,7 @@ class EpochLoop:
         for t in sched.tails:
             one(self._sibling_recipe(store, t), t, offset, sum(t))
             offset += sum(t)
+        self._last_stepper = None if last is self else last      # (whose grads / out describe the epoch's last batch)
         if check:
             self.check_no_dropped_steps()
             for t in self._siblings.values():
@@ -303,6 +306,7 @@ class EpochLoop:
             self._epoch_in_place(store, order, nfull, kseq, total)
             first, seen = nfull, nfull * bs
         pending = []                                     # full batches waiting for a sequence
+        last = self                                      # the trainer of the epoch's last step: a ragged batch's sibling, or this one
 
         def flush(n_keep: int = 0):
             nonlocal seen
@@ -334,6 +338,7 @@ class EpochLoop:
                 x = store.batch(rows)
                 tr.load_batch(x, x)
                 tr.run_step(device_mask=True)
+            last = tr
             total.add_(tr.loss.double(), alpha=float(ng))
             if host_metrics:
                 m = tr.mask.bool()
@@ -344,6 +349,7 @@ class EpochLoop:
         flush()
         if seen == 0:
             raise ValueError("the store yielded no batch")
+        self._last_stepper = None if last is self else last
         # a dropped step (a split launch whose workgroups were not co-resident) trained on nothing: an epoch that contains one
         # is an error, not a slightly smaller epoch
         if check:

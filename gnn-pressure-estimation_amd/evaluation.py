@@ -100,6 +100,33 @@ def descale(scaled_data, norm_type="minmax", mean=None, std=None, min=None, max=
     return scaled_data
 
 
+# ---- gradient flow (auxil.py:295-313) -----------------------------------------------------------------------------------
+GRAD_FLOW_WORDS = ("block", "mlp", "res")
+
+
+def gradient_flow_names(model: torch.nn.Module) -> List[str]:
+    """The parameters ``get_gradient_norm`` reports, in ``named_parameters()`` order: those whose name contains ``block``,
+    ``mlp`` or ``res``.  For ``GATResMeanConv`` that is every parameter of ``blocks`` (``blocks.0.conv1.att_src``, ...): eight
+    per block, without ``lin0`` / ``lin1``."""
+    return [n for n, _ in model.named_parameters() if any(w in n for w in GRAD_FLOW_WORDS)]
+
+
+def get_gradient_norm(model: torch.nn.Module, norm_type=2) -> Tuple[torch.Tensor, List[torch.Tensor], List[str]]:
+    """The reference's per-epoch gradient report on the host, for a module trained through ``loss.backward()``:
+    ``(total_norm, block_norms, block_names)`` -- the ``norm_type`` norm of ``p.grad`` for every parameter of
+    ``gradient_flow_names(model)`` and the norm of those norms.  Plain torch ops on whatever device the gradients are on.
+    ``GATResTrainer.gradient_flow()`` is the same report for the native step, computed by one launch."""
+    names = gradient_flow_names(model)
+    params = dict(model.named_parameters())
+    missing = [n for n in names if params[n].grad is None]
+    if missing:
+        raise ValueError(f"no gradient on {missing[0]} (and {len(missing) - 1} more): call loss.backward() first")
+    if not names:
+        raise ValueError("the model has no parameter whose name contains " + ", ".join(GRAD_FLOW_WORDS))
+    block_norms = [torch.norm(params[n].grad.detach(), p=norm_type) for n in names]
+    return torch.norm(torch.stack(block_norms), norm_type), block_norms, names
+
+
 # ---- timing (timer.py:12-66) --------------------------------------------------------------------------------------
 class Timer:
     """One HIP event pair per inference call after ``gpu_warmup_times`` untimed calls (timer.py:22-41)."""

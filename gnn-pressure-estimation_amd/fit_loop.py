@@ -7,7 +7,7 @@ import ctypes as C
 import math
 import os
 from collections import OrderedDict
-from typing import Dict, Optional
+from typing import Callable, Dict, Optional
 
 import torch
 
@@ -42,6 +42,16 @@ class FitLoop:
         fb["state"][6] = float("inf")          # GATRES_EPOCH_S_SCHED_BEST
         fb["best_valid"] = False
         return fb
+
+    def _grad_flow_buffers(self) -> None:
+        """``fit(log_gradient=True)``: the epoch's device row {total norm, 8 * num_blocks tensor norms, model update} and the
+        pinned row its copy lands in with the epoch's read-back.  ``first_out`` (epoch 1's output) is taken inside ``fit``."""
+        fb = self._fit
+        n = 2 + 8 * self.model.num_blocks
+        if fb.get("flow") is None or fb["flow"].numel() != n:
+            fb["flow"] = torch.zeros(n, dtype=torch.float64, device=self.device)
+            fb["flow_host"] = torch.zeros(n, dtype=torch.float64).pin_memory()
+        fb["first_out"] = None
 
     def _snapshot(self, restore: bool = False) -> None:
         """``gatres_snapshot_if``: live state -> best buffers if the controller's `improved` flag is set (read on the device), or,
@@ -82,7 +92,8 @@ class FitLoop:
             scheduler_patience: int = 2, shuffle: bool = True, generator: Optional[torch.Generator] = None, val_seed: int = 0,
             train_metrics: bool = False, save_path: Optional[str] = None, model_name: Optional[str] = None,
             variant: Optional[str] = None, save_best: str = "reference", restore_best: bool = False,
-            checkpoint_extra: Optional[dict] = None) -> "FitHistory":
+            checkpoint_extra: Optional[dict] = None, log_gradient: bool = False,
+            on_epoch: Optional[Callable[[int, dict], None]] = None) -> "FitHistory":
         """The reference's training loop (train.py:376-511 ``internal_train``) with its epoch boundary on the device.
 
         Per epoch e = 1 .. ``epochs``: ``fit_epoch`` on ``train_store`` (with the ``"train"`` metric collection computed on the
@@ -105,8 +116,23 @@ class FitLoop:
         snapshot, when ``fit`` returns (``"end"``: no file I/O inside improving epochs).  ``restore_best``: the best epoch's
         parameters, moments and step count are loaded back at the end (``best_state()`` hands them out either way).
 
+        ``log_gradient`` (the reference's ``--log_gradient``, train.py:476-493): after the epoch's training pass, one
+        ``gatres_grad_flow`` launch on the trainer that ran the epoch's last step (``gradient_flow()``: this trainer, or the
+        sibling of a ragged last batch) and one ``gatres_mean_abs_diff`` launch of that trainer's ``out`` against a device copy
+        taken in epoch 1 -- ``model_update = mean |out - first_out|``, 0 in epoch 1 -- into a device row that travels with the
+        epoch's read-back (no further synchronisation).  The history then holds ``total_grad_norm``, ``block_norms`` (a numpy
+        array per epoch, in the order of ``block_names``), ``model_update`` and its running sum ``accum_model_update``.  A later
+        epoch whose last batch has another size than epoch 1's raises ``ValueError``.  Off (default): none of this is enqueued.
+
+        ``on_epoch(epoch, info)``: called once per epoch after its read-back and checkpoints, before early stopping ends the
+        loop -- where the reference calls ``log_metrics_on_wandb`` (train.py:476-504).  ``info``: ``tr_loss``, ``val_loss``,
+        ``best_loss``, ``best_epoch``, ``lr`` (the rate the epoch trained with), ``improved``, ``val_metric_dict``,
+        ``train_metric_dict`` (with ``train_metrics``) and, with ``log_gradient``, ``total_grad_norm``, ``block_norms``,
+        ``model_update``, ``accum_model_update``.  An exception it raises propagates.
+
         Data parallel: every rank passes its shards; the epoch's four sums are all-reduced (one collective per epoch), so all
-        ranks take the same decision; metric dicts describe the rank's own shard.  Returns a ``FitHistory``."""
+        ranks take the same decision; metric dicts and ``model_update`` describe the rank's own shard, the gradient norms the
+        all-reduced gradient (the same on every rank).  Returns a ``FitHistory``."""
         from . import evaluation as E, wdn_io
         from .epoch_control import RECORD_FIELDS
         if save_best not in ("reference", "end"):
@@ -141,6 +167,10 @@ class FitLoop:
         train_fns = E.get_metric_fn_collection("train") if train_metrics else None
         R = {k: i for i, k in enumerate(RECORD_FIELDS)}
         hist = FitHistory()
+        if log_gradient:
+            self._grad_flow_buffers()
+            hist.block_names = self.gradient_flow_names()
+        accum_update = 0.0
         best_table = None
         paths = None
         if save_path is not None:
@@ -170,6 +200,17 @@ class FitLoop:
             else:
                 seen, _ = self._fit_epoch_sums(train_store, bs, shuffle, False, generator, None, sums[0:1], check=False)
             sums[1:2].fill_(float(seen))
+            if log_gradient:
+                # (before the validation pass; epoch 1 also pays one device copy of `out`)
+                last = self.last_step_trainer
+                if fb["first_out"] is None:
+                    fb["first_out"] = last.out.clone()
+                elif fb["first_out"].numel() != last.out.numel():
+                    raise ValueError(f"log_gradient: the last training batch of epoch {e} holds {last.out.numel()} nodes, that of "
+                                     f"epoch 1 held {fb['first_out'].numel()}: model_update = mean |out - first_out| needs the same "
+                                     f"batch size at the end of every epoch (a fixed store and drop_last)")
+                last._enqueue_grad_flow(fb["flow"])
+                last._enqueue_model_update(fb["first_out"], fb["flow"][-1:])
             val.enqueue(val_seed + e)
             if self.world > 1:
                 _native.check(self.lib.gatres_epoch_val_sums(_native.ptr(val.table if val.losses is None else None),
@@ -191,6 +232,8 @@ class FitLoop:
             host[1:].view(-1)[:val.table.numel()].copy_(val.table.view(-1), non_blocking=True)
             for i, t in enumerate(trainers):
                 status_host[i].copy_(t._status, non_blocking=True)
+            if log_gradient:
+                fb["flow_host"].copy_(fb["flow"], non_blocking=True)
             event.record(torch.cuda.current_stream(self.device))
             event.synchronize()
             rec = host[0].numpy().copy()
@@ -201,6 +244,11 @@ class FitLoop:
             hist.tr_loss.append(float(rec[R["tr_loss"]])); hist.val_loss.append(float(rec[R["val_loss"]]))
             hist.lr.append(float(rec[R["lr_used"]])); hist.improved.append(improved)
             hist.records.append(rec)
+            if log_gradient:
+                flow = fb["flow_host"].numpy().copy()
+                accum_update += float(flow[-1])
+                hist.total_grad_norm.append(float(flow[0])); hist.block_norms.append(flow[1:-1])
+                hist.model_update.append(float(flow[-1])); hist.accum_model_update.append(accum_update)
             if improved:
                 fb["best_valid"] = True
                 best_rec = rec
@@ -209,6 +257,16 @@ class FitLoop:
                     save("best", rec, best_table)
             if paths is not None and (e == 1 or e % 5 == 0) and not math.isnan(rec[R["tr_loss"]]):
                 save("last", rec, host[1:].view(-1)[:val.table.numel()].numpy())
+            if on_epoch is not None:
+                info = dict(tr_loss=hist.tr_loss[-1], val_loss=hist.val_loss[-1], best_loss=float(rec[R["best_loss"]]),
+                            best_epoch=int(rec[R["best_epoch"]]), lr=hist.lr[-1], improved=improved,
+                            val_metric_dict=val_metrics(host[1:].view(-1)[:val.table.numel()].numpy()))
+                if train_metrics:
+                    info["train_metric_dict"] = hist.train_metrics[-1]
+                if log_gradient:
+                    info.update(total_grad_norm=hist.total_grad_norm[-1], block_norms=hist.block_norms[-1],
+                                model_update=hist.model_update[-1], accum_model_update=hist.accum_model_update[-1])
+                on_epoch(e, info)
             if stop:
                 hist.stopped_epoch = e
                 break
@@ -235,12 +293,15 @@ class FitHistory:
     """What ``GATResTrainer.fit`` returns: per-epoch lists -- ``tr_loss``, ``val_loss``, ``lr`` (the rate the epoch trained
     with), ``improved`` -- ``best_loss``, ``best_epoch``, ``stopped_epoch`` (None: ran all epochs), ``best_metric_dict`` (the
     validation metrics of the best epoch, keys of ``get_metric_fn_collection("val")``), ``train_metrics`` (one dict per epoch
-    when asked for), ``final_lr`` and ``records`` (the controller's raw history records, ``epoch_control.RECORD_FIELDS``)."""
+    when asked for), ``final_lr`` and ``records`` (the controller's raw history records, ``epoch_control.RECORD_FIELDS``).  With
+    ``fit(log_gradient=True)`` also per epoch ``total_grad_norm``, ``block_norms`` (a float64 numpy array ``[8 * num_blocks]`` in
+    the order of ``block_names``), ``model_update`` and ``accum_model_update``; empty lists otherwise."""
 
     def __init__(self) -> None:
         self.tr_loss, self.val_loss, self.lr, self.improved, self.records, self.train_metrics = [], [], [], [], [], []
         self.best_loss, self.best_epoch, self.stopped_epoch, self.final_lr = float("inf"), 0, None, None
         self.best_metric_dict: Dict[str, float] = {}
+        self.total_grad_norm, self.block_norms, self.block_names, self.model_update, self.accum_model_update = [], [], [], [], []
 
 
 def internal_train(args, model: GATResMeanConv, train_store, val_store, **fit_kw):
@@ -248,7 +309,7 @@ def internal_train(args, model: GATResMeanConv, train_store, val_store, **fit_kw
     ``weight_decay``, ``epochs``, ``mask_rate``, ``criterion``, ``batch_size``, ``patience``, ``min_delta``, ``scheduler``,
     ``scheduler_patience``, ``use_gradient_clipping``, ``percentile``, ``save_path``, ``model_name``, ``variant``) becomes a
     ``GATResTrainer`` and one ``fit`` call.  Returns ``(best_loss, best_metric_dict)``.  ``fit_kw`` goes to ``fit``
-    (``generator``, ``val_seed``, ``save_best``, ...)."""
+    (``generator``, ``val_seed``, ``save_best``, ``log_gradient``, ``on_epoch``, ...)."""
     from .train_step import GATResTrainer
     bs = int(args.batch_size)
     # (a SnapshotStore or, for several networks, a MultiSnapshotStore: the batch's composition is the store's default recipe)

@@ -21,6 +21,7 @@ import torch
 from . import _native, dp
 from .epoch_loop import EpochLoop
 from .fit_loop import FitHistory, FitLoop, internal_train  # noqa: F401  (part of this module's interface)
+from .grad_flow import GradFlow
 from .graph_models import GATResMeanConv
 from .graph_plan import GraphPlan
 
@@ -166,7 +167,7 @@ class _GraphCache(OrderedDict):
         return g
 
 
-class GATResTrainer(EpochLoop, FitLoop):
+class GATResTrainer(EpochLoop, FitLoop, GradFlow):
     """Owns the static buffers of one (model, topology, batch size) and runs training steps on them.
 
     ``step(x, y)`` draws a fresh device-side mask; ``step(x, y, mask=...)`` uses the caller's mask (bool/uint8 [N]),
@@ -301,6 +302,11 @@ class GATResTrainer(EpochLoop, FitLoop):
         self._rows_win = self._loss_seq = None
         self._epoch_buf = self._epoch_bound = self._epoch_losses = None
         self._fit: Optional[dict] = None
+        self._grad_flow_out: Optional[torch.Tensor] = None      # gradient_flow()'s output buffer
+        self._grad_flow_names: Optional[list] = None          # ... and its names (named_parameters() is walked once)
+        # the trainer that ran the last step of the last fit_epoch: a sibling, or None for this one (no reference to itself:
+        # a trainer's buffers go when its last reference goes)
+        self._last_stepper: Optional["GATResTrainer"] = None
         self._recipe = None                  # for_store() on a MultiSnapshotStore: the batch's graphs per network
         self._warn_if_the_chip_is_not_ours()
 

@@ -775,6 +775,29 @@ int gatres_snapshot_if(const double* flag, const float* params, const float* exp
                        const uint64_t* step_counter, float* dst_params, float* dst_exp_avg, float* dst_exp_avg_sq,
                        uint64_t* dst_step_counter, int64_t count, void* stream);
 
+/* --------------------------------------------------------------------------------------------------------
+ * Gradient flow and model update per epoch (train.py:476-504 with --log_gradient; k_grad_flow.hip).  New symbols only: the
+ * ABI version stays (see GATRES_ABI_VERSION).
+ * ------------------------------------------------------------------------------------------------------ */
+
+/* get_gradient_norm(model, norm_type=2) (utils/auxil.py:295-313) on a flat gradient in the parameter layout above: the L2 norm
+ * of every parameter tensor whose name contains "block" -- per block conv1.att_src, conv1.att_dst, conv1.bias,
+ * conv1.lin.weight, conv2.att_src, conv2.att_dst, conv2.bias, conv2.lin.weight, the order of named_parameters(); lin0 / lin1
+ * are left out -- and the norm of those norms.  out: device double[1 + gatres_grad_flow_count()]:
+ *   out[1 + t] = sqrt(sum_i (double)g_i^2) * |scale| * c   over tensor t
+ *   out[0]     = sqrt(sum_t sumsq_t) * |scale| * c
+ * c = coef ? coef[0] : 1 (device double[1], read by the kernel).  `scale` is the factor the update applies to the gradient
+ * (gatres_train_step_t.grad_scale), `coef` AutoClip's coefficient of the last update (gatres_autoclip_t.coef_out): the reference
+ * reads .grad after clip_grad_norm_ scaled it in place, this engine keeps `grads` unclipped.  The tensor boundaries follow from
+ * (num_blocks, nc).  One launch, one workgroup per tensor and one for the total; fp64 sums in a fixed order, no atomics: the
+ * same bits on every run.  A NaN in a tensor gives NaN for that tensor and for out[0]; an all-zero tensor gives 0. */
+int gatres_grad_flow(const gatres_model_t* m, const float* grads, double scale, const double* coef, double* out, void* stream);
+int32_t gatres_grad_flow_count(int32_t num_blocks, int32_t nc);   /* 8 * num_blocks */
+
+/* out[0] = (sum_i (double)fabsf(a_i - b_i)) / n: torch.abs(a - b).mean() with the difference and the absolute value in fp32, as
+ * torch forms them, and the sum in fp64 in a fixed order (one workgroup). */
+int gatres_mean_abs_diff(const float* a, const float* b, int64_t n, double* out, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
