@@ -73,6 +73,26 @@ struct gatres_side_t {
 extern "C" __attribute__((visibility("hidden"))) gatres_side_t* gatres_side();
 extern "C" __attribute__((visibility("hidden"))) gatres_side_t* gatres_side_peek();      // never creates one
 
+// Functions one translation unit defines for another (not part of include/gatres.h), declared here ONCE; those of the update
+// launches are in k_update.h.
+// k_window.hip, k_fused_whole.hip -> k_fused_host.hip: the per-snapshot kernels' launches; args: const FusedArgs*
+extern "C" __attribute__((visibility("hidden"))) int gatres_fused_launch_window(const void* args, int nc, unsigned grid, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int gatres_fused_launch_whole(const void* args, int nc, int threads, int cache,
+                                                                              unsigned grid, void* stream);
+// k_fused_host.hip -> train_driver.hip: gatres_fused_param_grads; step_counter != null (gatres_train_step): the launch also
+// snapshots the step count and the fault word for the update launch (the status block's snapshot words, gatres_layout.h).
+// Returns 1 instead of 0 when it did (the caller may then ask for mask_next).
+extern "C" __attribute__((visibility("hidden"))) int gatres_fused_param_grads_ex(
+    const gatres_model_t* m, const gatres_graph_t* g, const float* saved, float* scratch, const uint64_t* step_counter, void* stream);
+// k_misc.hip, k_proj.hip -> model_driver.hip (per-op backward)
+extern "C" __attribute__((visibility("hidden"))) int gatres_reduce_slabs_regions(
+    const float* slabs, int32_t num_slabs, int32_t w_slabs, int64_t slab_stride, int64_t lo_abs, int64_t count, int32_t nc,
+    int32_t nb, float* out, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int gatres_proj_bwd_dw_with_conv_grads(
+    const void* g_h, const void* x, float* slab_W, int w_slabs, int64_t slab_stride, int num_nodes, int K, int HC,
+    const void* h, const float* g_a_src, const float* g_a_dst, const void* g_out, float* slab_att_src, float* slab_att_dst,
+    float* slab_bias, int num_slabs, int H, int C, int dtype, void* stream);
+
 static inline int gatres_launch_status() { return (int)hipGetLastError(); }
 static inline hipStream_t gatres_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline bool gatres_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -29,8 +29,8 @@ struct Layout {
   // fused path only: every block keeps its g_h / g_alpha tables until the deferred parameter-gradient launch
   // (k_fused.hip: param_grads_kernel) has consumed them.  Block-major, global node index.
   int64_t sc_keep, keep_stride, k_gh1, k_gh2, k_gas1, k_gad1, k_gas2, k_gad2;
-  // fused path, segments split over several CUs: flag lines (8 x 32 words per segment, + one error word at the
-  // end) and one partial slab row per (segment, part)
+  // fused path, segments split over several CUs: flag lines (8 x 32 words per segment, + the status block at the
+  // end: fused_status) and one partial slab row per (segment, part)
   int split_max;
   int64_t sc_flags, flag_words, col_words, sc_part_slabs;    // (col_words: arrival counters of param_grads_finish_kernel)
   int num_slabs;      // node-range slabs of the per-op path
@@ -200,6 +200,27 @@ static inline bool make_layout_g(const gatres_model_t* m, const gatres_graph_t* 
                           g->max_segment_edges_gat, L);
 }
 
+// The fused path's STATUS BLOCK: the last 32 of the flag region's 32-bit words (gatres_fused_status_offset: its float index
+// in scratch; zeroed with the flags, gatres_fused_reset_sync).  This is the description of its layout:
+//   FAULT          a split launch gave up waiting for a partner workgroup (every kernel's `err` word): its results are
+//                  poisoned.  The step is then dropped -- loss and gradients NaN, no update, no step count -- and whoever
+//                  drops it clears the word: the finish launches, or fused_status_kernel behind a forward-only launch.
+//   FAULT_COUNT    faults so far (GATResTrainer.fault_count)
+//   FAULT_TICKETS  arrival counter of the finish launches' workgroups where no snapshot was left: the last one clears FAULT
+//   DROPPED_STEPS  data-parallel Adam phases skipped because the all-reduced gradient carried a fault mark
+//                  (UpdateArgs.drop_count, GATResTrainer.dropped_steps)
+//   SNAPSHOT       two 64-bit words {the optimizer's step count, FAULT} as the step's parameter-gradient launch found them
+//                  (gatres_fused_param_grads_ex): stable while the update launch changes both (UpdateArgs.mask_snap)
+// Words 4 .. 7 and 12 .. 31 are unused.  train_step.py (STATUS_*) reads FAULT_COUNT and DROPPED_STEPS.
+constexpr int FUSED_STATUS_FAULT = 0, FUSED_STATUS_FAULT_COUNT = 1, FUSED_STATUS_FAULT_TICKETS = 2,
+              FUSED_STATUS_DROPPED_STEPS = 3, FUSED_STATUS_SNAPSHOT = 8;
+static inline int64_t fused_status_offset(const Layout& L) { return L.sc_flags + L.flag_words - 32; }
+static inline unsigned* fused_status(float* scratch, const Layout& L) {
+  return reinterpret_cast<unsigned*>(scratch + fused_status_offset(L));
+}
+static inline unsigned long long* fused_status_snapshot(unsigned* status) {
+  return reinterpret_cast<unsigned long long*>(status + FUSED_STATUS_SNAPSHOT);
+}
 
 
 // Saved activations of the FUSED path: segment-major.  Every segment (snapshot) owns one contiguous slot of

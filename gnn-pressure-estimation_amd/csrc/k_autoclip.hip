@@ -12,6 +12,7 @@
 #include "gatres_common.h"
 #include "k_autoclip.h"
 #include "k_mask.h"
+#include "k_update.h"
 
 namespace {
 
@@ -36,22 +37,7 @@ __global__ __launch_bounds__(256) void autoclip_norm_kernel(const float* __restr
 }
 
 struct AutoClipUpdate {
-  float* p;
-  const float* g;
-  float* m;
-  float* v;
-  unsigned long long* step_counter;
-  long long count;
-  double lr, b1, b2, eps, wd;
-  const double* hp;
-  float grad_scale;
-  float* wt;                     // the fused path's transposed conv weights (kept current like the other update kernels), or null
-  int nb, nc;
-  unsigned* drop_count;          // dropped steps are counted here (data-parallel Adam phase), or null
-  const int* mask_node_ptr;
-  double mask_rate;
-  unsigned long long mask_seed;
-  uint8_t* mask_next;            // the NEXT step's device mask, sampled by workgroups behind the update's, or null
+  UpdateArgs u;
   int update_blocks;
   int num_partials;
   const double* partials;
@@ -86,21 +72,21 @@ __global__ __launch_bounds__(256) void autoclip_adam_kernel(const AutoClipUpdate
   const unsigned long long cnt = a.ctl[AC_SNAP_COUNT], step = a.ctl[AC_SNAP_STEP];
   const bool overflow = cnt >= (unsigned long long)a.capacity;
   const bool drop = a.ctl[AC_SNAP_DROP] != 0ULL || overflow;
-  if (a.mask_next && (int)blockIdx.x >= a.update_blocks) {       // (the step count this update leaves behind)
+  if (a.u.mask_next && (int)blockIdx.x >= a.update_blocks) {       // (the step count this update leaves behind)
     const int mb = (int)blockIdx.x - a.update_blocks;
-    mask_sample_graph<256, MASK_WGS_UPDATE>(a.mask_node_ptr, a.mask_rate, a.mask_seed, step + (drop ? 0ULL : 1ULL), a.mask_next,
-                                            mb / MASK_WGS_UPDATE, mb % MASK_WGS_UPDATE);
+    mask_sample_graph<256, MASK_WGS_UPDATE>(a.u.mask_node_ptr, a.u.mask_rate, a.u.mask_seed, step + (drop ? 0ULL : 1ULL),
+                                            a.u.mask_next, mb / MASK_WGS_UPDATE, mb % MASK_WGS_UPDATE);
     return;
   }
   if (drop) {                    // no update, no step count, no history entry, outputs untouched
     if (blockIdx.x == 0 && tid == 0) {
       if (overflow) a.ctl[AC_OVERFLOW] = 1ULL;
-      else if (a.drop_count) atomicAdd(a.drop_count, 1u);
+      else if (a.u.drop_count) atomicAdd(a.u.drop_count, 1u);
     }
     return;
   }
-  double lr = a.lr, b1 = a.b1, b2 = a.b2, eps = a.eps, wd = a.wd;
-  if (a.hp) { lr = a.hp[0]; b1 = a.hp[1]; b2 = a.hp[2]; eps = a.hp[3]; wd = a.hp[4]; }
+  double lr = a.u.lr, b1 = a.u.b1, b2 = a.u.b2, eps = a.u.eps, wd = a.u.wd;
+  if (a.u.hp) { lr = a.u.hp[0]; b1 = a.u.hp[1]; b2 = a.u.hp[2]; eps = a.u.hp[3]; wd = a.u.hp[4]; }
   if (tid == 0) {
     const unsigned long long t = step + 1ULL;
     s_step_size = (float)(lr / (1.0 - gatres_powi(b1, t)));
@@ -147,35 +133,35 @@ __global__ __launch_bounds__(256) void autoclip_adam_kernel(const AutoClipUpdate
     a.clip_out[0] = c;
     a.coef_out[0] = coef_d;
     a.ctl[AC_COUNT] = (unsigned long long)t;
-    a.step_counter[0] = step + 1ULL;
+    a.u.step_counter[0] = step + 1ULL;
   }
   __syncthreads();                       // (s_step_size, s_bc2_sqrt)
   const long long gstride = (long long)a.update_blocks * 256;
   for (long long i = (long long)blockIdx.x * 256 + tid; i < t; i += gstride) B[i] = sorted_at(i);
   // Adam on the clipped gradient: adam_kernel's arithmetic (k_misc.hip) with the one multiplication in front of weight decay
-  for (long long idx = (long long)blockIdx.x * 256 + tid; idx < a.count; idx += gstride) {
-    const float pv = a.p[idx];
-    float gv = a.g[idx] * a.grad_scale;
+  for (long long idx = (long long)blockIdx.x * 256 + tid; idx < a.u.count; idx += gstride) {
+    const float pv = a.u.p[idx];
+    float gv = a.u.g[idx] * a.u.grad_scale;
     gv = gv * coef;
     gv = gv + (float)wd * pv;
-    float mv = a.m[idx];
+    float mv = a.u.m[idx];
     mv = mv + (float)(1.0 - b1) * (gv - mv);
-    const float vv = (float)b2 * a.v[idx] + (float)(1.0 - b2) * gv * gv;
+    const float vv = (float)b2 * a.u.v[idx] + (float)(1.0 - b2) * gv * gv;
     const float denom = sqrtf(vv) / s_bc2_sqrt + (float)eps;
     const float pn = pv + (-s_step_size * mv) / denom;
-    a.p[idx] = pn;
-    a.m[idx] = mv;
-    a.v[idx] = vv;
-    if (a.wt) {                  // keep the fused kernels' transposed conv weights current (transpose_conv_weights_kernel's layout)
-      const long long nc = a.nc, per = 2LL * nc * nc, stride = 9LL * nc + 2 * per, off = idx - 2LL * nc;
-      if (off >= 0 && off < (long long)a.nb * stride) {
+    a.u.p[idx] = pn;
+    a.u.m[idx] = mv;
+    a.u.v[idx] = vv;
+    if (a.u.wt) {                // keep the fused kernels' transposed conv weights current (transpose_conv_weights_kernel's layout)
+      const long long nc = a.u.nc, per = 2LL * nc * nc, stride = 9LL * nc + 2 * per, off = idx - 2LL * nc;
+      if (off >= 0 && off < (long long)a.u.nb * stride) {
         const long long b = off / stride, o = off % stride;
         if (o >= 6LL * nc && o < 6LL * nc + per) {                        // W1 [2nc][nc] -> [nc][2nc]
           const long long e = o - 6LL * nc, row = e / nc, col = e % nc;
-          a.wt[b * 2 * per + col * 2 * nc + row] = pn;
+          a.u.wt[b * 2 * per + col * 2 * nc + row] = pn;
         } else if (o >= 9LL * nc + per) {                                 // W2 [nc][2nc] -> [2nc][nc]
           const long long e = o - 9LL * nc - per, row = e / (2 * nc), col = e % (2 * nc);
-          a.wt[b * 2 * per + per + col * nc + row] = pn;
+          a.u.wt[b * 2 * per + per + col * nc + row] = pn;
         }
       }
     }
@@ -194,50 +180,36 @@ extern "C" int32_t gatres_autoclip_partials(int64_t count) {
   return count <= 0 ? 0 : (int32_t)((count + 255) / 256);
 }
 
-// (not part of include/gatres.h) the stand-alone norm launch over a complete gradient; *num_partials = partials it leaves
-extern "C" __attribute__((visibility("hidden"))) int gatres_autoclip_norm_ex(const float* grads, int64_t count, float grad_scale,
-                                                                             const uint64_t* step_counter,
-                                                                             const gatres_autoclip_t* ac, int32_t drop_nan,
+extern "C" __attribute__((visibility("hidden"))) int gatres_autoclip_norm_ex(const UpdateArgs& u, const gatres_autoclip_t* ac,
                                                                              int32_t* num_partials, void* stream) {
-  if (!grads || !step_counter || count <= 0 || !ac_valid(ac) || !num_partials) return GATRES_E_BADARG;
-  const long long need = (count + 255) / 256;
+  if (!u.g || !u.step_counter || u.count <= 0 || !ac_valid(ac) || !num_partials) return GATRES_E_BADARG;
+  const long long need = (u.count + 255) / 256;
   const int blocks = (int)(need < AC_NORM_MAX_BLOCKS ? need : AC_NORM_MAX_BLOCKS);
   if (blocks > ac->partials_cap) return GATRES_E_BADARG;
-  hipLaunchKernelGGL(autoclip_norm_kernel, dim3((unsigned)blocks), dim3(256), 0, gatres_stream(stream), grads, (long long)count,
-                     grad_scale, ac->partials, reinterpret_cast<unsigned long long*>(ac->ctl),
-                     reinterpret_cast<const unsigned long long*>(step_counter), drop_nan ? 1 : 0);
+  hipLaunchKernelGGL(autoclip_norm_kernel, dim3((unsigned)blocks), dim3(256), 0, gatres_stream(stream), u.g, u.count,
+                     u.grad_scale, ac->partials, reinterpret_cast<unsigned long long*>(ac->ctl), u.step_counter,
+                     u.drop_count ? 1 : 0);
   *num_partials = blocks;
   return gatres_launch_status();
 }
 
-// (not part of include/gatres.h) the update launch behind a norm launch that left num_partials partials
-extern "C" __attribute__((visibility("hidden"))) int gatres_autoclip_update_ex(
-    float* params, const float* grads, float* exp_avg, float* exp_avg_sq, uint64_t* step_counter, int64_t count, double lr,
-    double beta1, double beta2, double eps, double weight_decay, const double* hp, float grad_scale, float* wt,
-    int32_t num_blocks, int32_t nc, uint32_t* drop_count, const int32_t* mask_node_ptr, int32_t mask_graphs, double mask_rate,
-    uint64_t mask_seed, uint8_t* mask_next, const gatres_autoclip_t* ac, int32_t num_partials, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !step_counter || count <= 0 || !ac_valid(ac)) return GATRES_E_BADARG;
+extern "C" __attribute__((visibility("hidden"))) int gatres_autoclip_update_ex(const UpdateArgs& u, const gatres_autoclip_t* ac,
+                                                                               int32_t num_partials, void* stream) {
+  if (!u.p || !u.g || !u.m || !u.v || !u.step_counter || u.count <= 0 || !ac_valid(ac)) return GATRES_E_BADARG;
   if (num_partials <= 0 || num_partials > ac->partials_cap) return GATRES_E_BADARG;
-  const bool sample = mask_next && mask_node_ptr && mask_graphs > 0;
-  const long long need = (count + 255) / 256;
+  const bool sample = u.mask_next && u.mask_node_ptr && u.mask_graphs > 0;
+  const long long need = (u.count + 255) / 256;
   const int ub = (int)(need < AC_UPDATE_MAX_BLOCKS ? need : AC_UPDATE_MAX_BLOCKS);
   AutoClipUpdate a;
-  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq;
-  a.step_counter = reinterpret_cast<unsigned long long*>(step_counter);
-  a.count = count;
-  a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.hp = hp;
-  a.grad_scale = grad_scale;
-  a.wt = wt; a.nb = num_blocks; a.nc = nc;
-  a.drop_count = drop_count;
-  a.mask_node_ptr = sample ? mask_node_ptr : nullptr; a.mask_rate = mask_rate; a.mask_seed = (unsigned long long)mask_seed;
-  a.mask_next = sample ? mask_next : nullptr;
+  a.u = u;
+  if (!sample) { a.u.mask_node_ptr = nullptr; a.u.mask_next = nullptr; }
   a.update_blocks = ub;
   a.num_partials = num_partials; a.partials = ac->partials;
   a.log = ac->log; a.sorted0 = ac->sorted[0]; a.sorted1 = ac->sorted[1];
   a.ctl = reinterpret_cast<unsigned long long*>(ac->ctl);
   a.norm_out = ac->norm_out; a.clip_out = ac->clip_out; a.coef_out = ac->coef_out;
   a.capacity = ac->capacity; a.percentile = ac->percentile;
-  hipLaunchKernelGGL(autoclip_adam_kernel, dim3((unsigned)(ub + (sample ? mask_graphs * MASK_WGS_UPDATE : 0))), dim3(256), 0,
+  hipLaunchKernelGGL(autoclip_adam_kernel, dim3((unsigned)(ub + (sample ? u.mask_graphs * MASK_WGS_UPDATE : 0))), dim3(256), 0,
                      gatres_stream(stream), a);
   return gatres_launch_status();
 }
@@ -247,9 +219,10 @@ extern "C" int gatres_autoclip_adam_step(float* params, const float* grads, floa
                                          double eps, double weight_decay, float grad_scale, const gatres_autoclip_t* ac,
                                          void* stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || !step_counter || count <= 0 || !ac_valid(ac)) return GATRES_E_BADARG;
+  const UpdateArgs u = update_args_of(params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps,
+                                      weight_decay, nullptr, grad_scale);
   int32_t np = 0;
-  int rc = gatres_autoclip_norm_ex(grads, count, grad_scale, step_counter, ac, 0, &np, stream);
+  int rc = gatres_autoclip_norm_ex(u, ac, &np, stream);
   if (rc) return rc;
-  return gatres_autoclip_update_ex(params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
-                                   nullptr, grad_scale, nullptr, 0, 0, nullptr, nullptr, 0, 0.0, 0, nullptr, ac, np, stream);
+  return gatres_autoclip_update_ex(u, ac, np, stream);
 }

@@ -5,36 +5,34 @@
 #include "k_fused_dev.h"
 #include "k_mask.h"
 #include "k_autoclip.h"
-
-// the kernels live in translation units of their own (k_window.hip, k_fused_whole.hip); args: const FusedArgs*
-extern "C" __attribute__((visibility("hidden"))) int gatres_fused_launch_window(const void* args, int nc, unsigned grid, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int gatres_fused_launch_whole(const void* args, int nc, int threads, int cache,
-                                                                              unsigned grid, void* stream);
+#include "k_update.h"
 
 namespace {
 
 static unsigned long long* g_stamps = nullptr;      // gatres_fused_set_stamps (diagnostic build)
 static int g_stamp_cap = 0;
 
+// What the slab sum is given; the update behind it: UpdateArgs (a.count = the length of a slab row that is summed; a.g is
+// not read: the update takes the sum)
+struct SlabSumArgs {
+  const float* slabs;            // num_slabs rows, `stride` floats apart
+  int num_slabs, num_loss;
+  long long stride;
+  float* grads;                  // receives the sum (NaN on a faulted step)
+  const float* loss_part;        // num_loss partial sums and the masked-node count behind them, or null
+  float* loss;
+  int do_adam, use_snap, reduce_blocks;
+  unsigned* status;              // the status block (fused_status), or null: the plan has no split launches
+  double* ac_partials;           // NORM only
+  unsigned long long* ac_ctl;
+};
+
 // grads = sum of segment slabs (fixed order) ; optionally the Adam update and the loss finalisation in the same pass.
 // NORM (AutoClip, with do_adam == 0): each workgroup also leaves the fp64 sum of squares of its slice of grads * grad_scale
 // in ac_partials[blockIdx.x], and block 0 snapshots the words the AutoClip update launch reads (k_autoclip.hip).  NORM == false
 // is the kernel of the step without clipping, unchanged.
 template <bool NORM>
-__global__ __launch_bounds__(256) void reduce_adam_kernel(const float* __restrict__ slabs, int num_slabs,
-                                                          int num_loss, long long stride, long long count,
-                                                          float* __restrict__ grads, const float* loss_part,
-                                                          float* loss, int do_adam, float* __restrict__ p,
-                                                          float* __restrict__ m, float* __restrict__ v,
-                                                          unsigned long long* __restrict__ step_counter, double lr,
-                                                          double b1, double b2, double eps, double wd,
-                                                          float grad_scale, float* __restrict__ wt, int nb, int nc,
-                                                          unsigned* __restrict__ status, const double* __restrict__ hp,
-                                                          const int* __restrict__ mask_node_ptr, double mask_rate,
-                                                          unsigned long long mask_seed, uint8_t* __restrict__ mask_next,
-                                                          const unsigned long long* __restrict__ mask_snap, int use_snap,
-                                                          int reduce_blocks, double* __restrict__ ac_partials,
-                                                          unsigned long long* __restrict__ ac_ctl) {
+__global__ __launch_bounds__(256) void reduce_adam_kernel(const UpdateArgs a, const SlabSumArgs r) {
   __shared__ float s_step_size, s_bc2_sqrt;
   __shared__ unsigned s_fault;
   // The device mask of the NEXT step (utils/auxil.py:166-182), sampled by the workgroups behind the reduction's: the
@@ -42,103 +40,105 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(const float* __restric
   // count this update leaves behind -- exactly what gatres_mask_generate would read at the start of the next step: the
   // count and the fault word as the parameter-gradient launch in front of this one snapshotted them (mask_snap: this
   // launch changes both, and 512 more tickets on the one counter address would cost 10 us).
-  if (mask_next && (int)blockIdx.x >= reduce_blocks) {
-    const int mb = (int)blockIdx.x - reduce_blocks;
-    const unsigned long long next_step = mask_snap[1] == 0ULL ? mask_snap[0] + 1ULL : mask_snap[0];      // (a dropped step: unchanged)
-    mask_sample_graph<256, MASK_WGS_UPDATE>(mask_node_ptr, mask_rate, mask_seed, next_step, mask_next, mb / MASK_WGS_UPDATE,
-                                            mb % MASK_WGS_UPDATE);
+  if (a.mask_next && (int)blockIdx.x >= r.reduce_blocks) {
+    const int mb = (int)blockIdx.x - r.reduce_blocks;
+    const unsigned long long next_step = a.mask_snap[1] == 0ULL ? a.mask_snap[0] + 1ULL : a.mask_snap[0];      // (dropped: unchanged)
+    mask_sample_graph<256, MASK_WGS_UPDATE>(a.mask_node_ptr, a.mask_rate, a.mask_seed, next_step, a.mask_next,
+                                            mb / MASK_WGS_UPDATE, mb % MASK_WGS_UPDATE);
     return;
   }
-  if (hp) { lr = hp[0]; b1 = hp[1]; b2 = hp[2]; eps = hp[3]; wd = hp[4]; }      // (gatres_train_step_t.hparams)
-  // status[0]: a split launch of this step gave up waiting for a partner workgroup (its results are poisoned).  The step
-  // is then DROPPED: no Adam update, no step count, loss = NaN, gradients = NaN; the last block clears the word and
-  // counts the event in status[1], so one transient stall costs one step instead of the whole run.
+  double lr = a.lr, b1 = a.b1, b2 = a.b2, eps = a.eps, wd = a.wd;
+  if (a.hp) { lr = a.hp[0]; b1 = a.hp[1]; b2 = a.hp[2]; eps = a.hp[3]; wd = a.hp[4]; }      // (gatres_train_step_t.hparams)
+  // The status block's FAULT word (gatres_layout.h): a split launch of this step gave up waiting for a partner workgroup (its
+  // results are poisoned).  The step is then DROPPED: no Adam update, no step count, loss = NaN, gradients = NaN; the last
+  // block clears the word and counts the event in FAULT_COUNT, so one transient stall costs one step instead of the whole run.
   // snap: the parameter-gradient launch in front of this one left the step count and the fault word in mask_snap (the training
   // step's sequence, gatres_train_step).  Every block then reads THOSE -- stable words -- and block 0 alone counts the step:
   // no tickets (258 read-modify-writes on one address serialise in the L2 at ~20 ns each: 5 of this launch's 8 us).
-  const bool snap = use_snap != 0;
+  const bool snap = r.use_snap != 0;
   if (threadIdx.x == 0)
-    s_fault = snap ? (unsigned)mask_snap[1] : (status ? __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u);
-  if (do_adam && threadIdx.x == 0) {
+    s_fault = snap ? (unsigned)a.mask_snap[1]
+                   : (r.status ? __hip_atomic_load(r.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u);
+  if (r.do_adam && threadIdx.x == 0) {
     const unsigned long long t =
-        (snap ? mask_snap[0] : __hip_atomic_load(step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1ULL;
+        (snap ? a.mask_snap[0] : __hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1ULL;
     s_step_size = (float)(lr / (1.0 - gatres_powi(b1, t)));
     s_bc2_sqrt = (float)sqrt(1.0 - gatres_powi(b2, t));
-    if (snap && s_fault == 0u && blockIdx.x == 0) step_counter[0] = t;      // (nobody reads the counter in this launch)
+    if (snap && s_fault == 0u && blockIdx.x == 0) a.step_counter[0] = t;      // (nobody reads the counter in this launch)
     // The step is counted once every block has READ the counter: a ticket drawn right after this block's read (its value is
     // in a register: the wait below), the last ticket increments.  Nothing orders the count behind the parameter stores --
     // the next launch is -- so no fence: the ticket used to follow the block's stores behind a __threadfence(), an L2
     // write-back + invalidate of ~3.5 us at the end of every block of a 14-us launch.
     if (!snap) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if (!snap && s_fault == 0u) {
-      const unsigned long long done = atomicAdd(&step_counter[1], 1ULL);
-      if (done == (unsigned long long)reduce_blocks - 1ULL) {
-        step_counter[1] = 0ULL;
-        atomicAdd(&step_counter[0], 1ULL);
+      const unsigned long long done = atomicAdd(&a.step_counter[1], 1ULL);
+      if (done == (unsigned long long)r.reduce_blocks - 1ULL) {
+        a.step_counter[1] = 0ULL;
+        atomicAdd(&a.step_counter[0], 1ULL);
       }
     }
   }
-  if (loss_part && blockIdx.x == 0 && threadIdx.x < 64) {
+  if (r.loss_part && blockIdx.x == 0 && threadIdx.x < 64) {
     // the loss: sum of the per-(segment, part) squared errors / masked-node count.  One wave, strided partial sums
     // and a fixed-order butterfly (a single thread walking 128 dependent loads made block 0 the kernel's critical path)
     float s = 0.f;
-    for (int k = threadIdx.x; k < num_loss; k += 64) s += loss_part[k];
+    for (int k = threadIdx.x; k < r.num_loss; k += 64) s += r.loss_part[k];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (threadIdx.x == 0) loss[0] = s / loss_part[num_loss];
+    if (threadIdx.x == 0) r.loss[0] = s / r.loss_part[r.num_loss];
   }
   __syncthreads();
   const bool fault = s_fault != 0u;
-  if (fault && loss && blockIdx.x == 0 && threadIdx.x == 0) loss[0] = NAN;
+  if (fault && r.loss && blockIdx.x == 0 && threadIdx.x == 0) r.loss[0] = NAN;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   [[maybe_unused]] double sq = 0.0;
-  if (idx < count && (int)blockIdx.x < reduce_blocks) {
+  if (idx < a.count && (int)blockIdx.x < r.reduce_blocks) {
     float acc = 0.f;
     int s0 = 0;
     // the parameter and its moments are requested together with the first slab rows: one memory round trip for a
     // 32-snapshot batch instead of five dependent ones (this launch is pure latency: 258 workgroups x 4 waves)
     float pv = 0.f, mv0 = 0.f, vv0 = 0.f;
-    if (do_adam && !fault) { pv = p[idx]; mv0 = m[idx]; vv0 = v[idx]; }
-    for (; s0 + 32 <= num_slabs; s0 += 32) {            // 32 loads in flight, summed in slab order
+    if (r.do_adam && !fault) { pv = a.p[idx]; mv0 = a.m[idx]; vv0 = a.v[idx]; }
+    for (; s0 + 32 <= r.num_slabs; s0 += 32) {          // 32 loads in flight, summed in slab order
       float v32[32];
 #pragma unroll
-      for (int u = 0; u < 32; ++u) v32[u] = slabs[(size_t)(s0 + u) * stride + idx];
+      for (int u = 0; u < 32; ++u) v32[u] = r.slabs[(size_t)(s0 + u) * r.stride + idx];
 #pragma unroll
       for (int u = 0; u < 32; ++u) acc += v32[u];
     }
-    for (; s0 + 8 <= num_slabs; s0 += 8) {
+    for (; s0 + 8 <= r.num_slabs; s0 += 8) {
       float v8[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v8[u] = slabs[(size_t)(s0 + u) * stride + idx];
+      for (int u = 0; u < 8; ++u) v8[u] = r.slabs[(size_t)(s0 + u) * r.stride + idx];
 #pragma unroll
       for (int u = 0; u < 8; ++u) acc += v8[u];
     }
-    for (; s0 < num_slabs; ++s0) acc += slabs[(size_t)s0 * stride + idx];
-    grads[idx] = fault ? NAN : acc;
+    for (; s0 < r.num_slabs; ++s0) acc += r.slabs[(size_t)s0 * r.stride + idx];
+    r.grads[idx] = fault ? NAN : acc;
     if constexpr (NORM) {
-      const double x = (double)(acc * grad_scale);
+      const double x = (double)(acc * a.grad_scale);
       sq = fault ? 0.0 : x * x;
     }
-    if (do_adam && !fault) {
-      float gv = acc * grad_scale;
+    if (r.do_adam && !fault) {
+      float gv = acc * a.grad_scale;
       gv = gv + (float)wd * pv;
       float mv = mv0;
       mv = mv + (float)(1.0 - b1) * (gv - mv);
       const float vv = (float)b2 * vv0 + (float)(1.0 - b2) * gv * gv;
       const float denom = sqrtf(vv) / s_bc2_sqrt + (float)eps;
       const float pn = pv + (-s_step_size * mv) / denom;
-      p[idx] = pn;
-      m[idx] = mv;
-      v[idx] = vv;
-      if (wt) {                   // keep the transposed conv weights of the next backward current (k_misc.hip layout)
-        const long long per = 2LL * nc * nc, stride = 9LL * nc + 2 * per, off = idx - 2LL * nc;
-        if (off >= 0 && off < (long long)nb * stride) {
+      a.p[idx] = pn;
+      a.m[idx] = mv;
+      a.v[idx] = vv;
+      if (a.wt) {                 // keep the transposed conv weights of the next backward current (k_misc.hip layout)
+        const long long per = 2LL * a.nc * a.nc, stride = 9LL * a.nc + 2 * per, off = idx - 2LL * a.nc;
+        if (off >= 0 && off < (long long)a.nb * stride) {
           const long long b = off / stride, o = off % stride;
-          if (o >= 6LL * nc && o < 6LL * nc + per) {                        // W1 [2nc][nc] -> [nc][2nc]
-            const long long e = o - 6LL * nc, row = e / nc, col = e % nc;
-            wt[b * 2 * per + col * 2 * nc + row] = pn;
-          } else if (o >= 9LL * nc + per) {                                 // W2 [nc][2nc] -> [2nc][nc]
-            const long long e = o - 9LL * nc - per, row = e / (2 * nc), col = e % (2 * nc);
-            wt[b * 2 * per + per + col * nc + row] = pn;
+          if (o >= 6LL * a.nc && o < 6LL * a.nc + per) {                    // W1 [2nc][nc] -> [nc][2nc]
+            const long long e = o - 6LL * a.nc, row = e / a.nc, col = e % a.nc;
+            a.wt[b * 2 * per + col * 2 * a.nc + row] = pn;
+          } else if (o >= 9LL * a.nc + per) {                               // W2 [nc][2nc] -> [2nc][nc]
+            const long long e = o - 9LL * a.nc - per, row = e / (2 * a.nc), col = e % (2 * a.nc);
+            a.wt[b * 2 * per + per + col * a.nc + row] = pn;
           }
         }
       }
@@ -148,20 +148,20 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(const float* __restric
     __shared__ double lds4[4];
     sq = ac_block_sum(sq, lds4);
     if (threadIdx.x == 0) {
-      ac_partials[blockIdx.x] = sq;
-      if (blockIdx.x == 0) ac_snapshot(ac_ctl, step_counter, fault);      // (every block has read status[0]: s_fault)
+      r.ac_partials[blockIdx.x] = sq;
+      if (blockIdx.x == 0) ac_snapshot(r.ac_ctl, a.step_counter, fault);      // (every block has read the fault word: s_fault)
     }
   }
   if (fault && snap && blockIdx.x == 0 && threadIdx.x == 0) {      // (the other blocks read the snapshot, not the word)
-    status[1] += 1u;
-    __hip_atomic_store(status, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    r.status[FUSED_STATUS_FAULT_COUNT] += 1u;
+    __hip_atomic_store(r.status, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (fault && !snap && threadIdx.x == 0) {      // every block has read status[0] before the last ticket is drawn
+  if (fault && !snap && threadIdx.x == 0) {      // every block has read the fault word before the last ticket is drawn
     __threadfence();
-    if (atomicAdd(status + 2, 1u) == (unsigned)reduce_blocks - 1u) {
-      status[2] = 0u;
-      status[1] += 1u;
-      __hip_atomic_store(status, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (atomicAdd(r.status + FUSED_STATUS_FAULT_TICKETS, 1u) == (unsigned)r.reduce_blocks - 1u) {
+      r.status[FUSED_STATUS_FAULT_TICKETS] = 0u;
+      r.status[FUSED_STATUS_FAULT_COUNT] += 1u;
+      __hip_atomic_store(r.status, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 }
@@ -182,19 +182,14 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(const float* __restric
 // sums are a serial tail of dependent memory round trips on the workgroups that finish last; a release fence per arriver
 // instead of agent-scope stores 73 us (960 L2 write-back walks); dedicated reducer workgroups behind the items 60 us
 // (a third round of workgroups): profiles/r04_param_grads_finish_probe.txt, tests/micro/pgf_probe.py.
-// A faulted split launch (status[0]) turns grads and loss into NaN and skips the update, as gatres_fused_finish;
+// A faulted split launch (the status block's FAULT word) turns grads and loss into NaN and skips the update, as gatres_fused_finish;
 // `final_launch`: this launch holds block 0 (it clears the fault).
 struct FinishArgs {
+  UpdateArgs u;                  // (u.g is not read: the update takes the column sums; no sampling ahead, no drop count)
   float* grads;
   const float* loss_part;
   float* loss;
   int num_loss, do_adam;
-  float *p, *m, *v;
-  unsigned long long* step_counter;
-  double lr, b1, b2, eps, wd;
-  const double* hp;
-  float grad_scale;
-  float* wt;
   unsigned* status;
   unsigned* colcnt;
   int S, b_lo, b_hi, final_launch;
@@ -237,13 +232,13 @@ __global__ __launch_bounds__(PGR_THREADS) void param_grads_finish_kernel(const P
   }
   __syncthreads();
   if (!s_last) return;
-  double lr = f.lr, b1 = f.b1, b2 = f.b2, eps = f.eps, wd = f.wd;
-  if (f.hp) { lr = f.hp[0]; b1 = f.hp[1]; b2 = f.hp[2]; eps = f.hp[3]; wd = f.hp[4]; }
+  double lr = f.u.lr, b1 = f.u.b1, b2 = f.u.b2, eps = f.u.eps, wd = f.u.wd;
+  if (f.u.hp) { lr = f.u.hp[0]; b1 = f.u.hp[1]; b2 = f.u.hp[2]; eps = f.u.hp[3]; wd = f.u.hp[4]; }
   if (tid == 0) {
     __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);           // (the next launch starts from zero)
     s_fault = f.status ? __hip_atomic_load(f.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
     if (f.do_adam) {
-      const unsigned long long t = __hip_atomic_load(f.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ULL;
+      const unsigned long long t = __hip_atomic_load(f.u.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ULL;
       s_step_size = (float)(lr / (1.0 - gatres_powi(b1, t)));
       s_bc2_sqrt = (float)sqrt(1.0 - gatres_powi(b2, t));
     }
@@ -264,24 +259,24 @@ __global__ __launch_bounds__(PGR_THREADS) void param_grads_finish_kernel(const P
   auto update = [&](int64_t idx, float acc, float pv, float mv0, float vv0) {
     f.grads[idx] = fault ? NAN : acc;
     if (f.do_adam && !fault) {
-      float gv = acc * f.grad_scale;
+      float gv = acc * f.u.grad_scale;
       gv = gv + (float)wd * pv;
       float mv = mv0;
       mv = mv + (float)(1.0 - b1) * (gv - mv);
       const float vv = (float)b2 * vv0 + (float)(1.0 - b2) * gv * gv;
       const float denom = sqrtf(vv) / s_bc2_sqrt + (float)eps;
       const float pn = pv + (-s_step_size * mv) / denom;
-      f.p[idx] = pn;
-      f.m[idx] = mv;
-      f.v[idx] = vv;
-      if (f.wt) {               // keep the transposed conv weights of the next backward current (k_misc.hip layout)
+      f.u.p[idx] = pn;
+      f.u.m[idx] = mv;
+      f.u.v[idx] = vv;
+      if (f.u.wt) {               // keep the transposed conv weights of the next backward current (k_misc.hip layout)
         const long long per = 2LL * NC * NC, o = idx - po;
         if (o >= 6LL * NC && o < 6LL * NC + per) {                          // W1 [2nc][nc] -> [nc][2nc]
           const long long e = o - 6LL * NC, row = e / NC, cl = e % NC;
-          f.wt[(long long)b * 2 * per + cl * 2 * NC + row] = pn;
+          f.u.wt[(long long)b * 2 * per + cl * 2 * NC + row] = pn;
         } else if (o >= 9LL * NC + per && o < 9LL * NC + 2 * per) {         // W2 [nc][2nc] -> [2nc][nc]
           const long long e = o - 9LL * NC - per, row = e / (2 * NC), cl = e % (2 * NC);
-          f.wt[(long long)b * 2 * per + per + cl * NC + row] = pn;
+          f.u.wt[(long long)b * 2 * per + per + cl * NC + row] = pn;
         }
       }
     }
@@ -293,7 +288,7 @@ __global__ __launch_bounds__(PGR_THREADS) void param_grads_finish_kernel(const P
     for (int64_t q = tid; q < n4; q += PGR_THREADS) {
       const int64_t idx = lo + 4 * q;
       float4 pv = f4zero(), mv0 = f4zero(), vv0 = f4zero();
-      if (f.do_adam && !fault) { pv = ld4(f.p + idx); mv0 = ld4(f.m + idx); vv0 = ld4(f.v + idx); }
+      if (f.do_adam && !fault) { pv = ld4(f.u.p + idx); mv0 = ld4(f.u.m + idx); vv0 = ld4(f.u.v + idx); }
       float4 acc = f4zero();
       int s0 = 0;
       for (; s0 + 12 <= S; s0 += 12) {
@@ -321,7 +316,7 @@ __global__ __launch_bounds__(PGR_THREADS) void param_grads_finish_kernel(const P
     }
     for (int64_t idx = lo + 4 * n4 + tid; idx < hi; idx += PGR_THREADS) {      // (lin1's odd element)
       float pv = 0.f, mv0 = 0.f, vv0 = 0.f;
-      if (f.do_adam && !fault) { pv = f.p[idx]; mv0 = f.m[idx]; vv0 = f.v[idx]; }
+      if (f.do_adam && !fault) { pv = f.u.p[idx]; mv0 = f.u.m[idx]; vv0 = f.u.v[idx]; }
       float acc = 0.f;
       for (int s0 = 0; s0 < S; ++s0)
         acc += __hip_atomic_load(a.slabs + (size_t)s0 * L.slab_stride + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -336,17 +331,17 @@ __global__ __launch_bounds__(PGR_THREADS) void param_grads_finish_kernel(const P
     const unsigned ncols = (unsigned)ncol;
     if (f.do_adam && !fault) {
       // counted by the column that finishes last; every column has read the count before it draws
-      const unsigned long long done = atomicAdd(&f.step_counter[1], 1ULL);
+      const unsigned long long done = atomicAdd(&f.u.step_counter[1], 1ULL);
       if (done == (unsigned long long)ncols - 1ULL) {
-        f.step_counter[1] = 0ULL;
-        atomicAdd(&f.step_counter[0], 1ULL);
+        f.u.step_counter[1] = 0ULL;
+        atomicAdd(&f.u.step_counter[0], 1ULL);
       }
     }
-    if (fault && f.final_launch) {                 // every column of this launch has read status[0] before the last ticket
+    if (fault && f.final_launch) {                 // every column of this launch has read the fault word before the last ticket
       __threadfence();
-      if (atomicAdd(f.status + 2, 1u) == ncols - 1u) {
-        f.status[2] = 0u;
-        f.status[1] += 1u;
+      if (atomicAdd(f.status + FUSED_STATUS_FAULT_TICKETS, 1u) == ncols - 1u) {
+        f.status[FUSED_STATUS_FAULT_TICKETS] = 0u;
+        f.status[FUSED_STATUS_FAULT_COUNT] += 1u;
         __hip_atomic_store(f.status, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
@@ -365,7 +360,7 @@ __global__ __launch_bounds__(1024) void xcd_probe_kernel(unsigned* __restrict__ 
 // The same bookkeeping after a split launch that no gatres_fused_finish follows (forward / inference launches)
 __global__ __launch_bounds__(64) void fused_status_kernel(unsigned* __restrict__ status) {
   if (threadIdx.x == 0 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-    status[1] += 1u;
+    status[FUSED_STATUS_FAULT_COUNT] += 1u;
     __hip_atomic_store(status, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -610,7 +605,7 @@ extern "C" int gatres_fused_run(const gatres_model_t* m, const gatres_graph_t* g
   a.keep_lds = (phases & GATRES_PHASE_FORWARD) && (phases & GATRES_PHASE_BACKWARD) && !gatres_knobs()->fused_no_keep &&
            window_kernel_fits(a.L, g, a.M, true) ? 1 : 0;
   a.flags = reinterpret_cast<unsigned*>(scratch + a.L.sc_flags);
-  a.err = reinterpret_cast<int*>(a.flags + a.L.flag_words - 32);
+  a.err = reinterpret_cast<int*>(fused_status(scratch, a.L));
   a.part_slabs = scratch + a.L.sc_part_slabs;
   a.SL = make_seg_layout(a.L.nb, a.L.nc, g->max_segment_nodes, g->max_segment_edges_gat);
   a.xch = reinterpret_cast<unsigned long long*>(scratch + a.L.sc_xch);
@@ -662,21 +657,15 @@ extern "C" int gatres_probe_xcd_dispatch(void* stream) {
 extern "C" int64_t gatres_fused_status_offset(const gatres_model_t* m, const gatres_graph_t* g) {
   Layout L;
   if (!gatres_fused_supported(m, g) || !make_layout_g(m, g, &L)) return -1;
-  return L.sc_flags + L.flag_words - 32;
+  return fused_status_offset(L);
 }
 
-extern "C" __attribute__((visibility("hidden"))) int gatres_fused_param_grads_ex(const gatres_model_t* m, const gatres_graph_t* g,
-                                                                                 const float* saved, float* scratch,
-                                                                                 const uint64_t* step_counter, void* stream);
 extern "C" int gatres_fused_param_grads(const gatres_model_t* m, const gatres_graph_t* g, const float* saved,
                                         float* scratch, void* stream) {
   return gatres_fused_param_grads_ex(m, g, saved, scratch, nullptr, stream);
 }
-// step_counter != null (gatres_train_step): the launch also snapshots the step count and the fault word for the update
-// launch's sampling tail (status words 8 .. 11).  Returns 1 instead of 0 when it did (the caller may then ask for mask_next).
-extern "C" __attribute__((visibility("hidden"))) int gatres_fused_param_grads_ex(const gatres_model_t* m, const gatres_graph_t* g,
-                                                                                 const float* saved, float* scratch,
-                                                                                 const uint64_t* step_counter, void* stream) {
+extern "C" __attribute__((visibility("hidden"))) int gatres_fused_param_grads_ex(
+    const gatres_model_t* m, const gatres_graph_t* g, const float* saved, float* scratch, const uint64_t* step_counter, void* stream) {
   if (!m || !g || !saved || !scratch) return GATRES_E_BADARG;
   if (!gatres_fused_supported(m, g)) return GATRES_E_UNSUPPORTED;
   ParamGradArgs a;
@@ -690,10 +679,10 @@ extern "C" __attribute__((visibility("hidden"))) int gatres_fused_param_grads_ex
   hipStream_t st = gatres_stream(stream);
   if (m->nc == 16 || m->nc == 32) {
     if (step_counter) {
-      unsigned* status = reinterpret_cast<unsigned*>(scratch + a.L.sc_flags + a.L.flag_words - 32);
+      unsigned* status = fused_status(scratch, a.L);
       a.step_counter = reinterpret_cast<const unsigned long long*>(step_counter);
       a.status = fused_nodes_of(g) > 0 ? status : nullptr;
-      a.snap = reinterpret_cast<unsigned long long*>(status + 8);
+      a.snap = fused_status_snapshot(status);
     }
     if (m->nc == 16) hipLaunchKernelGGL((param_grads_reg_kernel<16>), grid, dim3(PGR_THREADS), 0, st, a);
     else             hipLaunchKernelGGL((param_grads_reg_kernel<32>), grid, dim3(PGR_THREADS), 0, st, a);
@@ -741,11 +730,11 @@ extern "C" int gatres_fused_param_grads_finish(const gatres_model_t* m, const ga
   a.SL = make_seg_layout(a.L.nb, a.L.nc, g->max_segment_nodes, g->max_segment_edges_gat);
   a.wt = scratch + a.L.sc_wt;
   FinishArgs f;
+  f.u = update_args_of(params, nullptr, exp_avg, exp_avg_sq, step_counter, a.L.P, lr, beta1, beta2, eps, weight_decay, hparams,
+                       grad_scale);
+  f.u.wt = do_adam ? scratch + a.L.sc_wt : nullptr;      // (its blocks and width: a.L, NC)
   f.grads = grads; f.loss_part = loss_part; f.loss = loss; f.num_loss = g->num_segments * a.M; f.do_adam = do_adam ? 1 : 0;
-  f.p = params; f.m = exp_avg; f.v = exp_avg_sq; f.step_counter = reinterpret_cast<unsigned long long*>(step_counter);
-  f.lr = lr; f.b1 = beta1; f.b2 = beta2; f.eps = eps; f.wd = weight_decay; f.hp = hparams; f.grad_scale = grad_scale;
-  f.wt = do_adam ? scratch + a.L.sc_wt : nullptr;
-  f.status = fused_nodes_of(g) > 0 ? reinterpret_cast<unsigned*>(scratch + a.L.sc_flags + a.L.flag_words - 32) : nullptr;
+  f.status = fused_nodes_of(g) > 0 ? fused_status(scratch, a.L) : nullptr;
   f.colcnt = reinterpret_cast<unsigned*>(scratch + a.L.sc_flags + a.L.flag_words);
   f.S = g->num_segments; f.b_lo = block_lo; f.b_hi = block_hi; f.final_launch = block_lo == 0 ? 1 : 0;
   const dim3 grid((unsigned)(2 * (block_hi - block_lo) * g->num_segments));
@@ -754,19 +743,6 @@ extern "C" int gatres_fused_param_grads_finish(const gatres_model_t* m, const ga
   else             hipLaunchKernelGGL((param_grads_finish_kernel<32>), grid, dim3(PGR_THREADS), 0, st, a, f);
   return gatres_launch_status();
 }
-
-extern "C" int gatres_fused_finish_hp(const gatres_model_t* m, const gatres_graph_t* g, float* scratch, float* grads,
-                                      const float* loss_part, float* loss, int32_t do_adam, float* params,
-                                      float* exp_avg, float* exp_avg_sq, uint64_t* step_counter, double lr, double beta1,
-                                      double beta2, double eps, double weight_decay, const double* hparams,
-                                      float grad_scale, const int32_t* mask_node_ptr, int32_t mask_graphs, double mask_rate,
-                                      uint64_t mask_seed, uint8_t* mask_next, void* stream);
-
-extern "C" __attribute__((visibility("hidden"))) int gatres_fused_finish_ex(
-    const gatres_model_t* m, const gatres_graph_t* g, float* scratch, float* grads, const float* loss_part, float* loss,
-    int32_t do_adam, float* params, float* exp_avg, float* exp_avg_sq, uint64_t* step_counter, double lr, double beta1,
-    double beta2, double eps, double weight_decay, const double* hparams, float grad_scale, const int32_t* mask_node_ptr,
-    int32_t mask_graphs, double mask_rate, uint64_t mask_seed, uint8_t* mask_next, int32_t use_snap, void* stream);
 
 extern "C" int gatres_fused_finish(const gatres_model_t* m, const gatres_graph_t* g, float* scratch, float* grads,
                                    const float* loss_part, float* loss, int32_t do_adam, float* params,
@@ -783,62 +759,63 @@ extern "C" int gatres_fused_finish_hp(const gatres_model_t* m, const gatres_grap
                                       float grad_scale, const int32_t* mask_node_ptr, int32_t mask_graphs, double mask_rate,
                                       uint64_t mask_seed, uint8_t* mask_next, void* stream) {
   // (mask_next through the public entry: the caller vouches that gatres_fused_param_grads ran under gatres_train_step's
-  //  sequence -- the snapshot it reads is only written there; without one the sampling tail is refused)
+  //  sequence -- the snapshot it reads is only written there; without one the sampling tail is refused, and the other
+  //  mask_* arguments have nothing to say)
   if (mask_next) return GATRES_E_UNSUPPORTED;
-  return gatres_fused_finish_ex(m, g, scratch, grads, loss_part, loss, do_adam, params, exp_avg, exp_avg_sq, step_counter, lr,
-                                beta1, beta2, eps, weight_decay, hparams, grad_scale, mask_node_ptr, mask_graphs, mask_rate,
-                                mask_seed, mask_next, 0, stream);
+  return gatres_fused_finish_ex(m, g, scratch, grads, loss_part, loss, do_adam,
+                                update_args_of(params, nullptr, exp_avg, exp_avg_sq, step_counter, 0, lr, beta1, beta2, eps,
+                                               weight_decay, hparams, grad_scale), 0, stream);
 }
 
-// (not part of include/gatres.h) use_snap: the parameter-gradient launch in front of this one (gatres_fused_param_grads_ex)
-// left the step count / fault word snapshot: the update reads those instead of drawing tickets, and may sample the next mask
+// The slab sum's arguments for a plan and its scratch (do_adam, use_snap and the AutoClip words: the caller's)
+static bool slab_sum_args(const gatres_model_t* m, const gatres_graph_t* g, float* scratch, float* grads, const float* loss_part,
+                          float* loss, Layout* L, SlabSumArgs* r) {
+  if (!make_layout_g(m, g, L)) return false;
+  *r = SlabSumArgs{};
+  r->slabs = scratch + L->sc_slabs; r->num_slabs = g->num_segments; r->num_loss = g->num_segments * fused_split(*L, g);
+  r->stride = L->slab_stride;
+  r->grads = grads; r->loss_part = loss_part; r->loss = loss;
+  r->reduce_blocks = (int)((L->P + 255) / 256);
+  r->status = fused_nodes_of(g) > 0 ? fused_status(scratch, *L) : nullptr;
+  return true;
+}
+
 extern "C" __attribute__((visibility("hidden"))) int gatres_fused_finish_ex(
     const gatres_model_t* m, const gatres_graph_t* g, float* scratch, float* grads, const float* loss_part, float* loss,
-    int32_t do_adam, float* params, float* exp_avg, float* exp_avg_sq, uint64_t* step_counter, double lr, double beta1,
-    double beta2, double eps, double weight_decay, const double* hparams, float grad_scale, const int32_t* mask_node_ptr,
-    int32_t mask_graphs, double mask_rate, uint64_t mask_seed, uint8_t* mask_next, int32_t use_snap, void* stream) {
+    int32_t do_adam, const UpdateArgs& u, int32_t use_snap, void* stream) {
   if (!m || !g || !scratch || !grads) return GATRES_E_BADARG;
-  if (mask_next && !use_snap) return GATRES_E_BADARG;
-  if (mask_next && (!do_adam || !mask_node_ptr || mask_graphs <= 0 || !(mask_rate >= 0.0 && mask_rate <= 1.0))) return GATRES_E_BADARG;
-  if (do_adam && (!params || !exp_avg || !exp_avg_sq || !step_counter)) return GATRES_E_BADARG;
+  if (u.mask_next && !use_snap) return GATRES_E_BADARG;
+  if (u.mask_next && (!do_adam || !u.mask_node_ptr || u.mask_graphs <= 0 || !(u.mask_rate >= 0.0 && u.mask_rate <= 1.0)))
+    return GATRES_E_BADARG;
+  if (do_adam && (!u.p || !u.m || !u.v || !u.step_counter)) return GATRES_E_BADARG;
   if ((loss_part == nullptr) != (loss == nullptr)) return GATRES_E_BADARG;
   Layout L;
-  if (!make_layout_g(m, g, &L)) return GATRES_E_UNSUPPORTED;
-  const int reduce_blocks = (int)((L.P + 255) / 256);
-  hipLaunchKernelGGL(reduce_adam_kernel<false>, dim3((unsigned)(reduce_blocks + (mask_next ? mask_graphs * MASK_WGS_UPDATE : 0))), dim3(256), 0,
-                     gatres_stream(stream),
-                     scratch + L.sc_slabs, g->num_segments, g->num_segments * fused_split(L, g),
-                     (long long)L.slab_stride, (long long)L.P, grads, loss_part, loss, do_adam, params, exp_avg, exp_avg_sq,
-                     reinterpret_cast<unsigned long long*>(step_counter), lr, beta1, beta2, eps, weight_decay,
-                     grad_scale, do_adam ? scratch + L.sc_wt : nullptr, L.nb, L.nc,
-                     fused_nodes_of(g) > 0 ? reinterpret_cast<unsigned*>(scratch + L.sc_flags + L.flag_words - 32) : nullptr,
-                     hparams, mask_node_ptr, mask_rate, (unsigned long long)mask_seed, mask_next,
-                     reinterpret_cast<const unsigned long long*>(scratch + L.sc_flags + L.flag_words - 32 + 8),
-                     (use_snap && do_adam) ? 1 : 0, reduce_blocks, (double*)nullptr, (unsigned long long*)nullptr);
+  SlabSumArgs r;
+  if (!slab_sum_args(m, g, scratch, grads, loss_part, loss, &L, &r)) return GATRES_E_UNSUPPORTED;
+  r.do_adam = do_adam; r.use_snap = (use_snap && do_adam) ? 1 : 0;
+  UpdateArgs a = u;
+  a.count = L.P;
+  a.wt = do_adam ? scratch + L.sc_wt : nullptr; a.nb = L.nb; a.nc = L.nc;
+  a.mask_snap = fused_status_snapshot(fused_status(scratch, L));
+  const unsigned grid = (unsigned)(r.reduce_blocks + (a.mask_next ? a.mask_graphs * MASK_WGS_UPDATE : 0));
+  hipLaunchKernelGGL(reduce_adam_kernel<false>, dim3(grid), dim3(256), 0, gatres_stream(stream), a, r);
   return gatres_launch_status();
 }
 
-// (not part of include/gatres.h) the slab sum of the clipped step: gatres_fused_finish_ex without Adam, as the norm launch of
-// AutoClip (the update follows: gatres_autoclip_update_ex).  *num_partials = partials it leaves.
+// The slab sum of the clipped step: gatres_fused_finish_ex without Adam, as the norm launch of AutoClip
 extern "C" __attribute__((visibility("hidden"))) int gatres_fused_finish_norm_ex(
     const gatres_model_t* m, const gatres_graph_t* g, float* scratch, float* grads, const float* loss_part, float* loss,
-    const uint64_t* step_counter, float grad_scale, const gatres_autoclip_t* ac, int32_t* num_partials, void* stream) {
-  if (!m || !g || !scratch || !grads || !step_counter || !ac || !ac->partials || !ac->ctl || !num_partials) return GATRES_E_BADARG;
+    const UpdateArgs& u, const gatres_autoclip_t* ac, int32_t* num_partials, void* stream) {
+  if (!m || !g || !scratch || !grads || !u.step_counter || !ac || !ac->partials || !ac->ctl || !num_partials) return GATRES_E_BADARG;
   if ((loss_part == nullptr) != (loss == nullptr)) return GATRES_E_BADARG;
   Layout L;
-  if (!make_layout_g(m, g, &L)) return GATRES_E_UNSUPPORTED;
-  const int reduce_blocks = (int)((L.P + 255) / 256);
-  if (reduce_blocks > ac->partials_cap) return GATRES_E_BADARG;
-  hipLaunchKernelGGL(reduce_adam_kernel<true>, dim3((unsigned)reduce_blocks), dim3(256), 0, gatres_stream(stream),
-                     scratch + L.sc_slabs, g->num_segments, g->num_segments * fused_split(L, g),
-                     (long long)L.slab_stride, (long long)L.P, grads, loss_part, loss, 0, (float*)nullptr, (float*)nullptr,
-                     (float*)nullptr, const_cast<unsigned long long*>(reinterpret_cast<const unsigned long long*>(step_counter)),
-                     0., 0., 0., 0., 0., grad_scale, (float*)nullptr, L.nb, L.nc,
-                     fused_nodes_of(g) > 0 ? reinterpret_cast<unsigned*>(scratch + L.sc_flags + L.flag_words - 32) : nullptr,
-                     (const double*)nullptr, (const int*)nullptr, 0., 0ULL, (uint8_t*)nullptr,
-                     reinterpret_cast<const unsigned long long*>(scratch + L.sc_flags + L.flag_words - 32 + 8), 0,
-                     reduce_blocks, ac->partials, reinterpret_cast<unsigned long long*>(ac->ctl));
-  *num_partials = reduce_blocks;
+  SlabSumArgs r;
+  if (!slab_sum_args(m, g, scratch, grads, loss_part, loss, &L, &r)) return GATRES_E_UNSUPPORTED;
+  if (r.reduce_blocks > ac->partials_cap) return GATRES_E_BADARG;
+  r.ac_partials = ac->partials; r.ac_ctl = reinterpret_cast<unsigned long long*>(ac->ctl);
+  UpdateArgs a{};
+  a.step_counter = u.step_counter; a.count = L.P; a.grad_scale = u.grad_scale;
+  hipLaunchKernelGGL(reduce_adam_kernel<true>, dim3((unsigned)r.reduce_blocks), dim3(256), 0, gatres_stream(stream), a, r);
+  *num_partials = r.reduce_blocks;
   return gatres_launch_status();
 }
-

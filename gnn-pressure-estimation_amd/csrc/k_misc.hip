@@ -8,6 +8,7 @@
 #include "gatres_common.h"
 #include "k_conv_grads.h"
 #include "k_mask.h"
+#include "k_update.h"
 
 // ---------------------------------------------------------------------------------------------------- environment knobs
 #include <atomic>
@@ -525,15 +526,7 @@ __global__ __launch_bounds__(1024) void masked_loss_kernel(const float* __restri
 // torch.optim.Adam (single-tensor path): g += wd*p; m.lerp_(g, 1-b1); v = b2*v + (1-b2) g*g;
 // p += (-(lr/bc1) * m) / (sqrt(v)/sqrt(bc2) + eps).   step_counter[0] = step, [1] = block ticket.
 constexpr int ADAM_MAX_BLOCKS = 512;
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v,
-                                                   unsigned long long* __restrict__ step_counter, long long count,
-                                                   double lr, double b1, double b2, double eps, double wd,
-                                                   float grad_scale, float* __restrict__ wt, int nb, int nc,
-                                                   unsigned* __restrict__ drop_count, const double* __restrict__ hp,
-                                                   const int* __restrict__ mask_node_ptr, double mask_rate,
-                                                   unsigned long long mask_seed, uint8_t* __restrict__ mask_next,
-                                                   const unsigned long long* __restrict__ mask_snap, int update_blocks) {
+__global__ __launch_bounds__(256) void adam_kernel(const UpdateArgs a, int update_blocks) {
   __shared__ float s_step_size, s_bc2_sqrt;
   __shared__ int s_drop;
   unsigned long long done = 0ULL;
@@ -541,80 +534,81 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   // single-GPU step does the same in reduce_adam_kernel, k_fused_host.hip).  Its key uses the step count this update leaves
   // behind: the count as the parameter-gradient launch of this step snapshotted it (mask_snap[0]: nothing has moved it since;
   // the update blocks increment it at their very end), + 1 unless the step is dropped (the all-reduced gradient's fault mark).
-  if (mask_next && (int)blockIdx.x >= update_blocks) {
+  if (a.mask_next && (int)blockIdx.x >= update_blocks) {
     const int mb = (int)blockIdx.x - update_blocks;
-    const bool dropped = drop_count && g[0] != g[0];
-    mask_sample_graph<256, MASK_WGS_UPDATE>(mask_node_ptr, mask_rate, mask_seed, mask_snap[0] + (dropped ? 0ULL : 1ULL),
-                                            mask_next, mb / MASK_WGS_UPDATE, mb % MASK_WGS_UPDATE);
+    const bool dropped = a.drop_count && a.g[0] != a.g[0];
+    mask_sample_graph<256, MASK_WGS_UPDATE>(a.mask_node_ptr, a.mask_rate, a.mask_seed, a.mask_snap[0] + (dropped ? 0ULL : 1ULL),
+                                            a.mask_next, mb / MASK_WGS_UPDATE, mb % MASK_WGS_UPDATE);
     return;
   }
-  if (hp) { lr = hp[0]; b1 = hp[1]; b2 = hp[2]; eps = hp[3]; wd = hp[4]; }      // (gatres_train_step_t.hparams)
+  double lr = a.lr, b1 = a.b1, b2 = a.b2, eps = a.eps, wd = a.wd;
+  if (a.hp) { lr = a.hp[0]; b1 = a.hp[1]; b2 = a.hp[2]; eps = a.hp[3]; wd = a.hp[4]; }      // (gatres_train_step_t.hparams)
   // drop_count != null (the data-parallel Adam phase of the fused path only): a fused launch that faulted marks EVERY
   // gradient entry NaN (gatres_fused_finish) and the all-reduce spreads the mark to all ranks; the step is then dropped on
-  // every replica alike -- no update, no step count -- and COUNTED in *drop_count (status word 3: a NaN that a diverging run
+  // every replica alike -- no update, no step count -- and COUNTED in *drop_count (the status block's DROPPED_STEPS: a NaN that a diverging run
   // puts into g[0] drops steps too, and must not do so silently; GATResTrainer.dropped_steps).  Everywhere else
   // (gatres_adam_step, FusedAdam) a NaN gradient propagates exactly as in torch.optim.Adam, which the reference uses
   // (train.py:348).
-  if (threadIdx.x == 0) s_drop = (drop_count && g[0] != g[0]) ? 1 : 0;
+  if (threadIdx.x == 0) s_drop = (a.drop_count && a.g[0] != a.g[0]) ? 1 : 0;
   __syncthreads();
   if (s_drop) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(drop_count, 1u);
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.drop_count, 1u);
     return;
   }
   // No tickets where the step count was snapshotted for this launch (mask_next != null: the data-parallel step's Adam phase
   // behind a parameter-gradient launch that left mask_snap, exactly the condition under which the sampling blocks above use
   // it): every block reads the SNAPSHOT and block 0 alone stores the new count -- up to 258 read-modify-writes on one address
   // serialise in the L2 at ~20 ns each, measured 7.5 -> 6.4 us for this launch (reduce_adam_kernel lost its tickets the same way).
-  const bool snap = mask_next != nullptr;
+  const bool snap = a.mask_next != nullptr;
   if (threadIdx.x == 0) {
-    const unsigned long long t = (snap ? mask_snap[0]
-                                       : __hip_atomic_load(step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1ULL;
+    const unsigned long long t = (snap ? a.mask_snap[0]
+                                       : __hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1ULL;
     const double bc1 = 1.0 - gatres_powi(b1, t), bc2 = 1.0 - gatres_powi(b2, t);
     s_step_size = (float)(lr / bc1);
     s_bc2_sqrt = (float)sqrt(bc2);
     if (snap) {
-      if (blockIdx.x == 0) step_counter[0] = t;         // (nobody reads the counter in this launch: the blocks read the snapshot)
+      if (blockIdx.x == 0) a.step_counter[0] = t;       // (nobody reads the counter in this launch: the blocks read the snapshot)
     } else {
       // the step is counted once every block has READ the counter: the ticket follows this block's read (no fence: nothing
-      // orders the count behind the parameter stores but the next launch -- see reduce_adam_kernel, k_fused.hip)
+      // orders the count behind the parameter stores but the next launch -- see reduce_adam_kernel, k_fused_host.hip)
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      done = atomicAdd(&step_counter[1], 1ULL);         // (its result is only looked at after this block's elements)
+      done = atomicAdd(&a.step_counter[1], 1ULL);       // (its result is only looked at after this block's elements)
     }
   }
   __syncthreads();
   // Grid-stride: the launch has at most ADAM_MAX_BLOCKS blocks.  One block per 256 parameters meant 6.6 k tickets on ONE
   // address for gatres_large -- they serialise in the L2 at ~20 ns each and were the whole 146 us of the launch.
-  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < count; idx += (long long)update_blocks * 256) {
+  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < a.count; idx += (long long)update_blocks * 256) {
   {
-    const float pv = p[idx];
-    float gv = g[idx] * grad_scale;
+    const float pv = a.p[idx];
+    float gv = a.g[idx] * a.grad_scale;
     gv = gv + (float)wd * pv;
-    float mv = m[idx];
+    float mv = a.m[idx];
     mv = mv + (float)(1.0 - b1) * (gv - mv);
-    const float vv = (float)b2 * v[idx] + (float)(1.0 - b2) * gv * gv;
+    const float vv = (float)b2 * a.v[idx] + (float)(1.0 - b2) * gv * gv;
     const float denom = sqrtf(vv) / s_bc2_sqrt + (float)eps;
     const float pn = pv + (-s_step_size * mv) / denom;
-    p[idx] = pn;
-    m[idx] = mv;
-    v[idx] = vv;
-    if (wt) {                     // keep the fused kernels' transposed conv weights current (transpose_conv_weights_kernel's layout)
-      const long long per = 2LL * nc * nc, stride = 9LL * nc + 2 * per, off = idx - 2LL * nc;
-      if (off >= 0 && off < (long long)nb * stride) {
+    a.p[idx] = pn;
+    a.m[idx] = mv;
+    a.v[idx] = vv;
+    if (a.wt) {                   // keep the fused kernels' transposed conv weights current (transpose_conv_weights_kernel's layout)
+      const long long per = 2LL * a.nc * a.nc, stride = 9LL * a.nc + 2 * per, off = idx - 2LL * a.nc;
+      if (off >= 0 && off < (long long)a.nb * stride) {
         const long long b = off / stride, o = off % stride;
-        if (o >= 6LL * nc && o < 6LL * nc + per) {                        // W1 [2nc][nc] -> [nc][2nc]
-          const long long e = o - 6LL * nc, row = e / nc, col = e % nc;
-          wt[b * 2 * per + col * 2 * nc + row] = pn;
-        } else if (o >= 9LL * nc + per) {                                 // W2 [nc][2nc] -> [2nc][nc]
-          const long long e = o - 9LL * nc - per, row = e / (2 * nc), col = e % (2 * nc);
-          wt[b * 2 * per + per + col * nc + row] = pn;
+        if (o >= 6LL * a.nc && o < 6LL * a.nc + per) {                    // W1 [2nc][nc] -> [nc][2nc]
+          const long long e = o - 6LL * a.nc, row = e / a.nc, col = e % a.nc;
+          a.wt[b * 2 * per + col * 2 * a.nc + row] = pn;
+        } else if (o >= 9LL * a.nc + per) {                               // W2 [nc][2nc] -> [2nc][nc]
+          const long long e = o - 9LL * a.nc - per, row = e / (2 * a.nc), col = e % (2 * a.nc);
+          a.wt[b * 2 * per + per + col * a.nc + row] = pn;
         }
       }
     }
   }
   }
   if (!snap && threadIdx.x == 0 && done == (unsigned long long)update_blocks - 1ULL) {
-    step_counter[1] = 0ULL;
-    atomicAdd(&step_counter[0], 1ULL);
+    a.step_counter[1] = 0ULL;
+    atomicAdd(&a.step_counter[0], 1ULL);
   }
 }
 
@@ -765,10 +759,9 @@ extern "C" int gatres_reduce_slabs(const float* slabs, int32_t num_slabs, int64_
 }
 
 // (internal: model_driver.hip)
-extern "C" __attribute__((visibility("hidden"))) int gatres_reduce_slabs_regions(const float* slabs, int32_t num_slabs,
-                                                                                 int32_t w_slabs, int64_t slab_stride,
-                                                                                 int64_t lo_abs, int64_t count, int32_t nc,
-                                                                                 int32_t nb, float* out, void* stream) {
+extern "C" __attribute__((visibility("hidden"))) int gatres_reduce_slabs_regions(
+    const float* slabs, int32_t num_slabs, int32_t w_slabs, int64_t slab_stride, int64_t lo_abs, int64_t count, int32_t nc,
+    int32_t nb, float* out, void* stream) {
   if (!slabs || !out || num_slabs <= 0 || w_slabs <= 0 || w_slabs > num_slabs || count <= 0) return GATRES_E_BADARG;
   hipLaunchKernelGGL(reduce_slabs_regions_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, gatres_stream(stream),
                      slabs, num_slabs, w_slabs, (long long)slab_stride, (long long)lo_abs, (long long)count, nc, nb, out);
@@ -856,34 +849,18 @@ static inline unsigned adam_blocks(long long count) {
 extern "C" int gatres_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
                                 uint64_t* step_counter, int64_t count, double lr, double beta1, double beta2,
                                 double eps, double weight_decay, float grad_scale, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !step_counter || count <= 0) return GATRES_E_BADARG;
-  hipLaunchKernelGGL(adam_kernel, dim3(adam_blocks(count)), dim3(256), 0, gatres_stream(stream), params,
-                     grads, exp_avg, exp_avg_sq, reinterpret_cast<unsigned long long*>(step_counter),
-                     (long long)count, lr, beta1, beta2, eps, weight_decay, grad_scale, (float*)nullptr, 0, 0,
-                     (unsigned*)nullptr, (const double*)nullptr, (const int*)nullptr, 0., 0ULL, (uint8_t*)nullptr,
-                     (const unsigned long long*)nullptr, (int)adam_blocks(count));
-  return gatres_launch_status();
+  return gatres_adam_step_ex(update_args_of(params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps,
+                                            weight_decay, nullptr, grad_scale), stream);
 }
 
-// (not part of include/gatres.h) Adam with everything gatres_train_step may ask for: hyper-parameters from a device buffer
-// (hp: double[5] {lr, beta1, beta2, eps, weight_decay}, or null), the fused path's transposed conv weights kept current
-// (wt, or null), fault-marked steps dropped and counted (drop_count, or null), the next step's device mask sampled by extra
-// workgroups (mask_next, or null; mask_snap: {step count before this update, -}, stable during the launch).
-extern "C" __attribute__((visibility("hidden"))) int gatres_adam_step_ex(float* params, const float* grads, float* exp_avg,
-                                   float* exp_avg_sq, uint64_t* step_counter, int64_t count, double lr, double beta1,
-                                   double beta2, double eps, double weight_decay, const double* hp, float grad_scale,
-                                   float* wt, int32_t num_blocks, int32_t nc, uint32_t* drop_count,
-                                   const int32_t* mask_node_ptr, int32_t mask_graphs, double mask_rate, uint64_t mask_seed,
-                                   uint8_t* mask_next, const uint64_t* mask_snap, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !step_counter || count <= 0) return GATRES_E_BADARG;
-  const bool sample = mask_next && mask_node_ptr && mask_snap && mask_graphs > 0;
-  const unsigned ub = adam_blocks(count);
-  hipLaunchKernelGGL(adam_kernel, dim3(ub + (sample ? (unsigned)mask_graphs * MASK_WGS_UPDATE : 0u)), dim3(256), 0,
-                     gatres_stream(stream), params,
-                     grads, exp_avg, exp_avg_sq, reinterpret_cast<unsigned long long*>(step_counter),
-                     (long long)count, lr, beta1, beta2, eps, weight_decay, grad_scale, wt, (int)num_blocks, (int)nc,
-                     drop_count, hp, sample ? mask_node_ptr : nullptr, mask_rate, (unsigned long long)mask_seed,
-                     sample ? mask_next : nullptr, reinterpret_cast<const unsigned long long*>(mask_snap), (int)ub);
+extern "C" __attribute__((visibility("hidden"))) int gatres_adam_step_ex(const UpdateArgs& u, void* stream) {
+  if (!u.p || !u.g || !u.m || !u.v || !u.step_counter || u.count <= 0) return GATRES_E_BADARG;
+  const bool sample = u.mask_next && u.mask_node_ptr && u.mask_snap && u.mask_graphs > 0;
+  const unsigned ub = adam_blocks(u.count);
+  UpdateArgs a = u;
+  if (!sample) { a.mask_node_ptr = nullptr; a.mask_next = nullptr; }
+  hipLaunchKernelGGL(adam_kernel, dim3(ub + (sample ? (unsigned)u.mask_graphs * MASK_WGS_UPDATE : 0u)), dim3(256), 0,
+                     gatres_stream(stream), a, (int)ub);
   return gatres_launch_status();
 }
 

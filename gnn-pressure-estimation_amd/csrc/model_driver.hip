@@ -157,10 +157,6 @@ extern "C" int gatres_model_backward(const gatres_model_t* m, const gatres_graph
   return gatres_model_backward_per_op(m, g, params, x, mask, g_out, saved, scratch, grads, g_x, stream);
 }
 
-extern "C" __attribute__((visibility("hidden"))) int gatres_reduce_slabs_regions(const float* slabs, int32_t num_slabs,
-                                                                                 int32_t w_slabs, int64_t slab_stride,
-                                                                                 int64_t lo_abs, int64_t count, int32_t nc,
-                                                                                 int32_t nb, float* out, void* stream);
 // Slab rows the GATConv weight gradients occupy: the bf16 dW kernel of wide models forms two-dimensional partials (64 rows of
 // 64 x 64 blocks instead of one whole [2nc, nc] matrix per workgroup): 4x less slab traffic in dW and in the final sum
 static int dw_slab_rows(const gatres_model_t* m, const Layout& L) {
@@ -193,10 +189,6 @@ extern "C" int gatres_model_reduce_grads(const gatres_model_t* m, const gatres_g
                                      grads, stream);
 }
 
-extern "C" __attribute__((visibility("hidden"))) int gatres_proj_bwd_dw_with_conv_grads(
-    const void* g_h, const void* x, float* slab_W, int w_slabs, int64_t slab_stride, int num_nodes, int K, int HC,
-    const void* h, const float* g_a_src, const float* g_a_dst, const void* g_out, float* slab_att_src, float* slab_att_dst,
-    float* slab_bias, int num_slabs, int H, int C, int dtype, void* stream);
 // A convolution's two partial-sum launches (attention-vector / bias partials, weight partials): ONE launch (extra workgroups
 // of the weight-gradient kernel run the column sums) where a co-launching kernel applies, else one after the other.
 static int conv_partials(const void* gh, const void* xin, float* slab_W, int Sw, int64_t st, int N, int K, int HC,

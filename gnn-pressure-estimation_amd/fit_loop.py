@@ -135,6 +135,7 @@ class FitLoop:
         all-reduced gradient (the same on every rank).  Returns a ``FitHistory``."""
         from . import evaluation as E, wdn_io
         from .epoch_control import RECORD_FIELDS
+        from .train_step import STATUS_DROPPED_STEPS, STATUS_FAULT_COUNT
         if save_best not in ("reference", "end"):
             raise ValueError("save_best must be 'reference' or 'end'")
         if scheduler not in (None, "ReduceLROnPlateau"):
@@ -238,7 +239,7 @@ class FitLoop:
             event.synchronize()
             rec = host[0].numpy().copy()
             for i, t in enumerate(trainers):
-                t.check_no_dropped_steps((int(status_host[i, 1]), int(status_host[i, 3])))
+                t.check_no_dropped_steps((int(status_host[i, STATUS_FAULT_COUNT]), int(status_host[i, STATUS_DROPPED_STEPS])))
             self.hparams["lr"] = float(rec[R["lr_after"]])          # (the device buffer holds it already; siblings share the dict)
             improved, stop = bool(rec[R["improved"]]), bool(rec[R["stop"]])
             hist.tr_loss.append(float(rec[R["tr_loss"]])); hist.val_loss.append(float(rec[R["val_loss"]]))

@@ -26,6 +26,7 @@ from .graph_models import GATResMeanConv
 from .graph_plan import GraphPlan
 
 PHASE_MASK, PHASE_FORWARD, PHASE_BACKWARD, PHASE_ADAM = 1, 2, 4, 8
+STATUS_FAULT_COUNT, STATUS_DROPPED_STEPS = 1, 3      # words of the fused path's status block (csrc/gatres_layout.h: FUSED_STATUS_*)
 PART_FIRST, PART_LAST, PART_REDUCE = 1, 2, 4
 FLAG_PER_OP, FLAG_WT_VALID, FLAG_GRADS_DEFERRED, FLAG_GRADS_ONLY, FLAG_MASK_NEXT = 1, 2, 4, 8, 16
 FLAG_LOSS_MAE, FLAG_LOSS_SCE = 32, 64
@@ -485,13 +486,13 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         """Data-parallel steps whose update was skipped because the all-reduced gradient carried a fault mark -- the mark is
         "entry 0 is NaN", so a diverging run that puts a NaN there shows up here too (it would otherwise freeze silently:
         ADVICE r3).  Synchronises."""
-        return int(self._status[3].item()) if self._status is not None else 0
+        return int(self._status[STATUS_DROPPED_STEPS].item()) if self._status is not None else 0
 
     @property
     def fault_count(self) -> int:
         """Split launches that gave up waiting for a partner workgroup so far (each cost exactly one dropped step: loss
         NaN, no update).  Synchronises."""
-        return int(self._status[1].item()) if self._status is not None else 0
+        return int(self._status[STATUS_FAULT_COUNT].item()) if self._status is not None else 0
 
     def _enqueue(self, phases: int, device_mask: bool, wt_valid: bool = False, flags: int = 0, block_lo: int = 0,
                  block_hi: int = 0, batch=None, masks=None, loss=None) -> None:
