@@ -1,6 +1,6 @@
 """MI355X-native GATRes message-passing engine (drop-in for the GATResMeanConv hot path of
 DiTEC-project/gnn-pressure-estimation).  See DESIGN.md / INTEGRATION.md at the repository root."""
-from . import _native, dp, epoch_control, evaluation, wdn_io, wdn_synth
+from . import _native, dp, epoch_control, estimation, evaluation, wdn_io, wdn_synth
 from ._build import build_native
 from .config_models import config_gatres_large, config_gatres_small, select_model
 from .graph_models import GATConv, GATResMeanConv, GResBlockMeanConv, Linear, SimpleConv
@@ -9,7 +9,8 @@ from .graph_plan import GraphPlan, PlanCache
 from .snapshot_store import SnapshotStore
 from .multi_snapshot_store import MultiSnapshotStore
 from .train_step import FitHistory, GATResTrainer, internal_train
+from .estimation import PressureEstimator, observed_from_names
 
 __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "SimpleConv", "Linear", "GraphPlan", "PlanCache",
            "GATResTrainer", "FitHistory", "internal_train", "epoch_control", "select_model", "config_gatres_small", "config_gatres_large", "build_native", "wdn_synth", "dp", "evaluation", "wdn_io", "SnapshotStore",
-           "MultiSnapshotStore"]
+           "MultiSnapshotStore", "estimation", "PressureEstimator", "observed_from_names"]

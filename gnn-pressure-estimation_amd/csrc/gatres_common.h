@@ -117,6 +117,12 @@ __device__ __forceinline__ double gatres_powi(double b, unsigned long long t) {
   return r;
 }
 
+// torch's `scaled * scale + offset` on fp32 tensors with Python-float scalars (SnapshotStore.descale, evaluation.descale): a
+// multiply and an add, each rounded to fp32
+__device__ __forceinline__ float gatres_descale(float s, float scale, float offset) {
+  return __fadd_rn(__fmul_rn(s, scale), offset);
+}
+
 __device__ __forceinline__ float gatres_leaky(float v) { return v > 0.f ? v : v * GATRES_NEG_SLOPE; }
 
 // The reference's other training criteria (gatres.h: GATRES_LOSS_MAE, GATRES_LOSS_SCE) on one masked node: returns the node's

@@ -1,0 +1,265 @@
+// Device side of pressure estimation with a FIXED sensor set (estimation.PressureEstimator): what a deployed model does with the
+// readings of its sensors, and the back-test report over a snapshot store.
+//   gatres_stage_observed      one batch's input: zero and mask = 1 at every node but the observed ones, which carry their value;
+//   gatres_estimate_write      one batch's result into the pass's [S][stride] matrix in physical units;
+//   gatres_node_error_moments  per-node error moments of an estimate matrix against the truth, one fp64 record per node.
+// The first two are memory-bound element passes over one batch (16-byte accesses on the batch's flat arrays, which are aligned
+// whatever the graph size); the third streams two [S][N] matrices once with the lanes of a wave on consecutive nodes and sums in
+// fp64 in a fixed order, without atomics: the same bits on every run.
+#include "gatres_common.h"
+
+namespace {
+
+// ---- staging -------------------------------------------------------------------------------------------------------------------
+constexpr int OBS_T = 256;                     // threads of a workgroup: one 4-element chunk each
+constexpr int OBS_TILE = 4 * OBS_T + 4;        // nodes a workgroup's chunks can touch: 4 * OBS_T plus the alignment shift
+constexpr int OBS_MAX_GY = 256;                // workgroups that share the graphs of one tile
+
+// (v - offset) / factor as torch forms it on fp32 tensors with Python-float scalars: the subtraction rounded to fp32, then a
+// division (mode 1) or the product with the fp32 reciprocal (mode 2: `scale` is then 1.0f / (float)factor, formed on the host)
+__device__ __forceinline__ float obs_normalise(float v, int mode, float offset, float scale) {
+  if (mode == GATRES_NORMALISE_NONE) return v;
+  const float c = __fsub_rn(v, offset);
+  return mode == GATRES_NORMALISE_DIVIDE ? __fdiv_rn(c, scale) : __fmul_rn(c, scale);
+}
+
+// Workgroup (tile, y): chunk j = tile * OBS_T + thread of graph g covers the nodes [shift + 4 (j - 1), shift + 4 j) of the graph,
+// shift = (-g * N) mod 4 -- so every whole chunk starts at a multiple of four in the batch's flat arrays (one float4 and one
+// 32-bit mask store), whatever N is; the first and the last chunk of a graph may be partial and store element by element.  The
+// inverse of observed[] over the tile's nodes is built ONCE in LDS (k + 1, 0: not observed) and serves every graph this
+// workgroup takes (g = y, y + gridDim.y, ...).  Every node of every graph is written exactly once.
+__global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __restrict__ src, int readings, long long src_rows,
+                                                               const long long* __restrict__ rows, long long first_row, int N,
+                                                               int G, const int* __restrict__ observed, int K, int mode,
+                                                               float offset, float scale, float* __restrict__ x_dst,
+                                                               uint8_t* __restrict__ mask, int vec) {
+  __shared__ int slot[OBS_TILE];
+  const int tid = threadIdx.x;
+  const int j = blockIdx.x * OBS_T + tid;
+  const int tile_lo = blockIdx.x * (4 * OBS_T) - 4;          // first node slot[] speaks of
+  for (int i = tid; i < OBS_TILE; i += OBS_T) slot[i] = 0;
+  __syncthreads();
+  for (int k = tid; k < K; k += OBS_T) {
+    const int v = observed[k];
+    if (v >= 0 && v < N && v >= tile_lo && v < tile_lo + OBS_TILE) slot[v - tile_lo] = k + 1;
+  }
+  __syncthreads();
+  for (int g = blockIdx.y; g < G; g += gridDim.y) {
+    const long long base = (long long)g * N;
+    const int shift = vec ? (int)((4 - (base & 3)) & 3) : 0;
+    const int v0 = shift + 4 * (j - 1);
+    if (v0 >= N || v0 + 4 <= 0) continue;
+    const long long row = rows ? rows[g] : first_row + g;
+    const bool row_ok = row >= 0 && row < src_rows;          // (a row outside the matrix is not read: its nodes get 0)
+    float val[4];
+    uint8_t mk[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int v = v0 + e;
+      const int s = (v >= 0 && v < N) ? slot[v - tile_lo] : 0;
+      mk[e] = s ? 0 : 1;
+      val[e] = 0.f;
+      if (s && row_ok) {
+        const float r = readings ? src[row * K + (s - 1)] : src[row * N + v];
+        val[e] = obs_normalise(r, readings ? mode : GATRES_NORMALISE_NONE, offset, scale);
+      }
+    }
+    if (vec && v0 >= 0 && v0 + 4 <= N) {
+      st4(x_dst + base + v0, make_float4(val[0], val[1], val[2], val[3]));
+      *reinterpret_cast<uint32_t*>(mask + base + v0) =
+          (uint32_t)mk[0] | ((uint32_t)mk[1] << 8) | ((uint32_t)mk[2] << 16) | ((uint32_t)mk[3] << 24);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int v = v0 + e;
+        if (v >= 0 && v < N) {
+          x_dst[base + v] = val[e];
+          mask[base + v] = mk[e];
+        }
+      }
+    }
+  }
+}
+
+// ---- write-back ----------------------------------------------------------------------------------------------------------------
+constexpr int EW_T = 256;
+
+// One 4-element chunk of the batch's flat arrays per thread per trip (16-byte loads of out and x, one 32-bit load of the mask).
+// The destination rows are dst_stride apart: a chunk is stored as one float4 when `vec_store` says that every chunk lies inside
+// one row at a 16-byte boundary (N and dst_stride multiples of four, dst aligned), element by element otherwise.
+__global__ __launch_bounds__(EW_T) void estimate_write_kernel(const float* __restrict__ out, const float* __restrict__ x,
+                                                              const uint8_t* __restrict__ mask, int N, long long total,
+                                                              float scale, float offset, int keep_observed,
+                                                              float* __restrict__ dst, long long dst_stride, long long first_row,
+                                                              int vec_load, int vec_store) {
+  for (long long i0 = 4 * ((long long)blockIdx.x * EW_T + threadIdx.x); i0 < total; i0 += 4LL * gridDim.x * EW_T) {
+    float o[4], xv[4] = {0.f, 0.f, 0.f, 0.f};
+    uint8_t mk[4] = {1, 1, 1, 1};
+    const int n = total - i0 < 4 ? (int)(total - i0) : 4;
+    if (vec_load && n == 4) {
+      const float4 a = ld4(out + i0);
+      o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+      if (keep_observed) {
+        const float4 b = ld4(x + i0);
+        const uint32_t m = *reinterpret_cast<const uint32_t*>(mask + i0);
+        xv[0] = b.x; xv[1] = b.y; xv[2] = b.z; xv[3] = b.w;
+        mk[0] = m & 0xff; mk[1] = (m >> 8) & 0xff; mk[2] = (m >> 16) & 0xff; mk[3] = m >> 24;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        o[e] = e < n ? out[i0 + e] : 0.f;
+        if (keep_observed && e < n) {
+          xv[e] = x[i0 + e];
+          mk[e] = mask[i0 + e];
+        }
+      }
+    }
+    float r[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = gatres_descale(mk[e] ? o[e] : xv[e], scale, offset);
+    const long long g = i0 / N;
+    const int v = (int)(i0 - g * N);
+    if (vec_store && n == 4) {
+      st4(dst + (first_row + g) * dst_stride + v, make_float4(r[0], r[1], r[2], r[3]));
+    } else {
+      long long ge = g;
+      int ve = v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (e < n) dst[(first_row + ge) * dst_stride + ve] = r[e];
+        if (++ve == N) { ve = 0; ++ge; }
+      }
+    }
+  }
+}
+
+// ---- per-node error moments ----------------------------------------------------------------------------------------------------
+constexpr int NE_WAVES = 8;
+constexpr int NE_T = NE_WAVES * GATRES_WAVE;
+constexpr int NE_U = 8;                        // rows in flight per wave and trip
+constexpr int NE_F = 6;                        // accumulated fields: the record's slots [1..6]
+
+// Workgroup b takes the 64 nodes [64 b, 64 b + 64): lane l of every wave is node 64 b + l, so a wave reads 256 consecutive bytes
+// of a row.  Wave w takes the rows w, w + NE_WAVES, ... in ascending order (NE_U of them in flight per trip: a chunk of
+// GATRES_NODE_ERROR_CHUNK = NE_WAVES * NE_U rows per workgroup), each lane adding its node's terms in that order; the waves'
+// partials go through LDS and are added in wave order.  The association depends on S alone.
+__global__ __launch_bounds__(NE_T) void node_error_moments_kernel(const float* __restrict__ est, const float* __restrict__ truth,
+                                                                  long long S, int N, float scale, float offset,
+                                                                  const int* __restrict__ observed, int K,
+                                                                  double* __restrict__ table) {
+  __shared__ double part[NE_WAVES][NE_F][GATRES_WAVE];
+  __shared__ int seen[GATRES_WAVE];
+  const int lane = threadIdx.x % GATRES_WAVE, wave = threadIdx.x / GATRES_WAVE;
+  const int v_lo = blockIdx.x * GATRES_WAVE, v = v_lo + lane;
+  if (threadIdx.x < GATRES_WAVE) seen[threadIdx.x] = 0;
+  __syncthreads();
+  for (int k = threadIdx.x; k < K; k += NE_T) {
+    const int o = observed[k];
+    if (o >= v_lo && o < v_lo + GATRES_WAVE) seen[o - v_lo] = 1;
+  }
+  double a[NE_F] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};        // sum e, sum |e|, sum e^2, max |e|, #kept, sum |e| / |t|
+  float amax = 0.f;
+  if (v < N) {
+    for (long long s0 = wave; s0 < S; s0 += (long long)NE_U * NE_WAVES) {
+      float p[NE_U], t[NE_U];
+#pragma unroll
+      for (int u = 0; u < NE_U; ++u) {
+        const long long s = s0 + (long long)u * NE_WAVES;
+        p[u] = s < S ? est[s * N + v] : 0.f;
+        t[u] = s < S ? truth[s * N + v] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < NE_U; ++u) {           // (in row order: the same association as a plain loop)
+        if (s0 + (long long)u * NE_WAVES >= S) continue;
+        const float tr = gatres_descale(t[u], scale, offset);
+        const float e = __fsub_rn(p[u], tr);
+        const float ae = fabsf(e), at = fabsf(tr);
+        a[0] += (double)e;
+        a[1] += (double)ae;
+        a[2] += (double)e * (double)e;
+        amax = fmaxf(amax, ae);
+        if (at > 0.01f) {
+          a[4] += 1.0;
+          a[5] += (double)ae / (double)at;
+        }
+      }
+    }
+  }
+  a[3] = (double)amax;
+#pragma unroll
+  for (int f = 0; f < NE_F; ++f) part[wave][f][lane] = a[f];
+  __syncthreads();
+  if (wave == 0 && v < N) {
+    double r[NE_F];
+#pragma unroll
+    for (int f = 0; f < NE_F; ++f) {
+      double s = part[0][f][lane];
+      for (int w = 1; w < NE_WAVES; ++w) s = f == 3 ? fmax(s, part[w][f][lane]) : s + part[w][f][lane];
+      r[f] = s;
+    }
+    double* rec = table + (size_t)v * GATRES_NODE_ERROR_RECORD;
+    rec[0] = (double)S;
+    rec[1] = r[0]; rec[2] = r[1]; rec[3] = r[2]; rec[4] = r[3]; rec[5] = r[4]; rec[6] = r[5];
+    rec[7] = seen[lane] ? 1.0 : 0.0;
+  }
+}
+
+}  // namespace
+
+extern "C" int gatres_stage_observed(const float* src, int32_t layout, int64_t src_rows, const int64_t* rows, int64_t first_row,
+                                     int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed, int32_t num_observed,
+                                     int32_t normalise, double offset, double factor, float* x_dst, uint8_t* mask,
+                                     void* stream) {
+  if (!src || !observed || !x_dst || !mask || src == x_dst) return GATRES_E_BADARG;
+  if (nodes_per_graph <= 0 || num_graphs <= 0 || num_observed <= 0 || num_observed > nodes_per_graph) return GATRES_E_BADARG;
+  if ((int64_t)nodes_per_graph * num_graphs > INT32_MAX) return GATRES_E_BADARG;
+  if (layout != GATRES_OBSERVED_FULL_ROWS && layout != GATRES_OBSERVED_READINGS) return GATRES_E_BADARG;
+  if (layout == GATRES_OBSERVED_READINGS && rows) return GATRES_E_BADARG;
+  if (src_rows <= 0 || (!rows && (first_row < 0 || first_row > src_rows - num_graphs))) return GATRES_E_BADARG;
+  if (normalise < GATRES_NORMALISE_NONE || normalise > GATRES_NORMALISE_RECIPROCAL) return GATRES_E_BADARG;
+  float scale = 1.f;
+  if (normalise != GATRES_NORMALISE_NONE) {
+    if (!((float)factor != 0.f)) return GATRES_E_BADARG;
+    scale = normalise == GATRES_NORMALISE_RECIPROCAL ? 1.0f / (float)factor : (float)factor;
+  }
+  const int vec = gatres_aligned16(x_dst) && (reinterpret_cast<uintptr_t>(mask) & 3u) == 0;
+  const int chunks = (nodes_per_graph + 3) / 4 + 1;
+  const dim3 grid((chunks + OBS_T - 1) / OBS_T, num_graphs < OBS_MAX_GY ? num_graphs : OBS_MAX_GY);
+  hipLaunchKernelGGL(stage_observed_kernel, grid, dim3(OBS_T), 0, gatres_stream(stream), src,
+                     (int)(layout == GATRES_OBSERVED_READINGS), (long long)src_rows, reinterpret_cast<const long long*>(rows),
+                     (long long)first_row, (int)nodes_per_graph, (int)num_graphs, observed, (int)num_observed, (int)normalise,
+                     (float)offset, scale, x_dst, mask, vec);
+  return gatres_launch_status();
+}
+
+extern "C" int gatres_estimate_write(const float* out, const float* x, const uint8_t* mask, int32_t nodes_per_graph,
+                                     int32_t num_graphs, double scale, double offset, int32_t keep_observed, float* dst,
+                                     int64_t dst_rows, int64_t dst_stride, int64_t first_row, void* stream) {
+  if (!out || !dst || out == dst || nodes_per_graph <= 0 || num_graphs <= 0) return GATRES_E_BADARG;
+  if (keep_observed && (!x || !mask || x == dst)) return GATRES_E_BADARG;
+  if ((int64_t)nodes_per_graph * num_graphs > INT32_MAX) return GATRES_E_BADARG;
+  if (dst_stride < nodes_per_graph || dst_rows <= 0 || first_row < 0 || first_row > dst_rows - num_graphs) return GATRES_E_BADARG;
+  const long long total = (long long)nodes_per_graph * num_graphs;
+  const int vec_load = gatres_aligned16(out) && (!keep_observed || (gatres_aligned16(x) && (reinterpret_cast<uintptr_t>(mask) & 3u) == 0));
+  const int vec_store = gatres_aligned16(dst) && nodes_per_graph % 4 == 0 && dst_stride % 4 == 0;
+  long long wgs = (total + 4LL * EW_T - 1) / (4LL * EW_T);
+  if (wgs > 4096) wgs = 4096;
+  hipLaunchKernelGGL(estimate_write_kernel, dim3((unsigned)wgs), dim3(EW_T), 0, gatres_stream(stream), out, x, mask,
+                     (int)nodes_per_graph, total, (float)scale, (float)offset, (int)(keep_observed != 0), dst,
+                     (long long)dst_stride, (long long)first_row, vec_load, vec_store);
+  return gatres_launch_status();
+}
+
+extern "C" int gatres_node_error_moments(const float* est, const float* truth, int64_t num_snapshots, int32_t nodes_per_graph,
+                                         double scale, double offset, const int32_t* observed, int32_t num_observed,
+                                         double* table, void* stream) {
+  if (!est || !truth || !observed || !table || num_snapshots <= 0 || nodes_per_graph <= 0) return GATRES_E_BADARG;
+  if (num_observed <= 0 || num_observed > nodes_per_graph) return GATRES_E_BADARG;
+  static_assert(GATRES_NODE_ERROR_CHUNK == NE_WAVES * NE_U, "gatres.h states the chunk of the moments kernel");
+  static_assert(GATRES_NODE_ERROR_RECORD == 8, "record layout");
+  hipLaunchKernelGGL(node_error_moments_kernel, dim3((nodes_per_graph + GATRES_WAVE - 1) / GATRES_WAVE), dim3(NE_T), 0,
+                     gatres_stream(stream), est, truth, (long long)num_snapshots, (int)nodes_per_graph, (float)scale,
+                     (float)offset, observed, (int)num_observed, table);
+  return gatres_launch_status();
+}

@@ -44,11 +44,6 @@ __device__ __forceinline__ void met_block_sum(double (&v)[F], double (*lds)[F]) 
   __syncthreads();
 }
 
-// torch's `scaled * scale + offset` on fp32 tensors with Python-float scalars
-__device__ __forceinline__ float met_descale(float s, float scale, float offset) {
-  return __fadd_rn(__fmul_rn(s, scale), offset);
-}
-
 __global__ __launch_bounds__(MET_T) void masked_metrics_kernel(const float* __restrict__ out, const float* __restrict__ y,
                                                                const uint8_t* __restrict__ mask, int N, float scale,
                                                                float offset, double* __restrict__ table, int slot,
@@ -76,7 +71,7 @@ __global__ __launch_bounds__(MET_T) void masked_metrics_kernel(const float* __re
       if (!mk[u]) continue;
       const float so = ov[u], st = yv[u];
       const double ds = (double)so - (double)st;
-      const float p = met_descale(so, scale, offset), t = met_descale(st, scale, offset);
+      const float p = gatres_descale(so, scale, offset), t = gatres_descale(st, scale, offset);
       const double d = (double)p - (double)t;
       a[0] += 1.0;
       a[1] += ds * ds;
@@ -113,7 +108,7 @@ __global__ __launch_bounds__(MET_T) void masked_metrics_kernel(const float* __re
 #pragma unroll
     for (int u = 0; u < MET_U; ++u) {
       if (!mk[u]) continue;
-      const double dp = (double)met_descale(ov[u], scale, offset) - pm, dt = (double)met_descale(yv[u], scale, offset) - tm;
+      const double dp = (double)gatres_descale(ov[u], scale, offset) - pm, dt = (double)gatres_descale(yv[u], scale, offset) - tm;
       c[0] += dp * dp;
       c[1] += dt * dt;
       c[2] += dp * dt;

@@ -798,6 +798,55 @@ int32_t gatres_grad_flow_count(int32_t num_blocks, int32_t nc);   /* 8 * num_blo
  * torch forms them, and the sum in fp64 in a fixed order (one workgroup). */
 int gatres_mean_abs_diff(const float* a, const float* b, int64_t n, double* out, void* stream);
 
+/* --------------------------------------------------------------------------------------------------------
+ * Pressure estimation with a fixed sensor set (estimation.PressureEstimator; k_estimate.hip).  New symbols only: the ABI version
+ * stays.
+ * ------------------------------------------------------------------------------------------------------ */
+
+/* One batch's input for a FIXED set of observed nodes, in one launch.  observed[num_observed] (device int32): node indices inside
+ * a graph, distinct, each in [0, nodes_per_graph); 1 <= num_observed <= nodes_per_graph.  For g in [0, num_graphs):
+ *   mask[g * N + v] = 1, x_dst[g * N + v] = 0.0f   at every node that is not observed,
+ *   mask[g * N + v] = 0, x_dst[g * N + v] = value  at v = observed[k].
+ * Every byte of mask and every float of x_dst in [0, num_graphs * N) is written exactly once: no memset beforehand.
+ * layout GATRES_OBSERVED_FULL_ROWS: src is a snapshot matrix [src_rows][N], already scaled; graph g takes row
+ *   rows ? rows[g] : first_row + g (rows: device int64), column observed[k], unchanged.
+ * layout GATRES_OBSERVED_READINGS: src is [src_rows][num_observed] in physical units; graph g takes row first_row + g (rows must
+ *   be NULL), column k for node observed[k], normalised as `normalise` says with o = (float)offset, f = (float)factor:
+ *     GATRES_NORMALISE_NONE        value = r
+ *     GATRES_NORMALISE_DIVIDE      value = fp32(fp32(r - o) / f)
+ *     GATRES_NORMALISE_RECIPROCAL  value = fp32(fp32(r - o) * fp32(1.0f / f))   (torch's device kernel for tensor / host scalar)
+ * A row outside [0, src_rows) named by rows[] is not read (its observed nodes get 0); without rows, first_row + num_graphs must
+ * not pass src_rows. */
+#define GATRES_OBSERVED_FULL_ROWS 0
+#define GATRES_OBSERVED_READINGS  1
+#define GATRES_NORMALISE_NONE       0
+#define GATRES_NORMALISE_DIVIDE     1
+#define GATRES_NORMALISE_RECIPROCAL 2
+int gatres_stage_observed(const float* src, int32_t layout, int64_t src_rows, const int64_t* rows, int64_t first_row,
+                          int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed, int32_t num_observed,
+                          int32_t normalise, double offset, double factor, float* x_dst, uint8_t* mask, void* stream);
+
+/* One batch's estimates into the result matrix dst[dst_rows][dst_stride] (physical units), in one launch:
+ *   dst[(first_row + g) * dst_stride + v] = mask[g*N+v] ? D(out[g*N+v]) : (keep_observed ? D(x[g*N+v]) : D(out[g*N+v]))
+ * with D(s) = fp32(fp32(s * (float)scale) + (float)offset), gatres_masked_metrics' rounding.  out, x, mask: the forward's
+ * prediction, the staged input and the mask of gatres_stage_observed (x and mask may be NULL when keep_observed == 0).
+ * dst_stride >= nodes_per_graph; first_row + num_graphs <= dst_rows; nothing outside the batch's rows and columns is written. */
+int gatres_estimate_write(const float* out, const float* x, const uint8_t* mask, int32_t nodes_per_graph, int32_t num_graphs,
+                          double scale, double offset, int32_t keep_observed, float* dst, int64_t dst_rows, int64_t dst_stride,
+                          int64_t first_row, void* stream);
+
+/* Per-node error moments of an estimate matrix est[S][N] (physical units) against the scaled truth[S][N], t = D(truth) as above,
+ * e = fp32(p - t): table[N][GATRES_NODE_ERROR_RECORD] (device double), per node v over the snapshots s = 0 .. S - 1:
+ *   [0] S   [1] sum e   [2] sum |e|   [3] sum e^2   [4] max |e|   [5] #{|t| > 0.01f}   [6] sum over those of |e| / |t|
+ *   [7] 1.0 if v is in observed[num_observed], else 0.0
+ * Observed nodes get their moments like any other.  One launch; the lanes of a wave take consecutive nodes, the waves of a
+ * workgroup take the rows of a chunk of GATRES_NODE_ERROR_CHUNK snapshots in turn; fp64 sums in a fixed order (the waves'
+ * partials are added in wave order through LDS), no atomics: the same bits on every run. */
+#define GATRES_NODE_ERROR_RECORD 8
+#define GATRES_NODE_ERROR_CHUNK 64
+int gatres_node_error_moments(const float* est, const float* truth, int64_t num_snapshots, int32_t nodes_per_graph, double scale,
+                              double offset, const int32_t* observed, int32_t num_observed, double* table, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
