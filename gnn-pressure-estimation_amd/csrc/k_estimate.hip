@@ -3,6 +3,8 @@
 //   gatres_stage_observed      one batch's input: zero and mask = 1 at every node but the observed ones, which carry their value;
 //   gatres_estimate_write      one batch's result into the pass's [S][stride] matrix in physical units;
 //   gatres_node_error_moments  per-node error moments of an estimate matrix against the truth, one fp64 record per node.
+// gatres_stage_observed_available and gatres_node_error_moments_available are the same two kernels compiled with AVAIL = true:
+// a sensor without a reading in a snapshot is one more hidden node there (x = 0, mask = 1; its error counts as a hidden entry's).
 // The first two are memory-bound element passes over one batch (16-byte accesses on the batch's flat arrays, which are aligned
 // whatever the graph size); the third streams two [S][N] matrices once with the lanes of a wave on consecutive nodes and sums in
 // fp64 in a fixed order, without atomics: the same bits on every run.
@@ -23,16 +25,24 @@ __device__ __forceinline__ float obs_normalise(float v, int mode, float offset, 
   return mode == GATRES_NORMALISE_DIVIDE ? __fdiv_rn(c, scale) : __fmul_rn(c, scale);
 }
 
+// (by the bits: the test holds whatever the compiler may assume about floating-point comparisons)
+__device__ __forceinline__ bool obs_is_nan(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
+
 // Workgroup (tile, y): chunk j = tile * OBS_T + thread of graph g covers the nodes [shift + 4 (j - 1), shift + 4 j) of the graph,
 // shift = (-g * N) mod 4 -- so every whole chunk starts at a multiple of four in the batch's flat arrays (one float4 and one
 // 32-bit mask store), whatever N is; the first and the last chunk of a graph may be partial and store element by element.  The
 // inverse of observed[] over the tile's nodes is built ONCE in LDS (k + 1, 0: not observed) and serves every graph this
 // workgroup takes (g = y, y + gridDim.y, ...).  Every node of every graph is written exactly once.
+// AVAIL (a compile-time fact of the launch; gatres_stage_observed is the instantiation without it and reads neither argument):
+// the reading of sensor k in source row r counts only where available[r * K + k] != 0 (available == NULL: everywhere) and, with
+// nan_missing in the readings layout, is no NaN; a missing reading is not loaded, its node gets x = 0 and mask = 1.
+template <bool AVAIL>
 __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __restrict__ src, int readings, long long src_rows,
                                                                const long long* __restrict__ rows, long long first_row, int N,
                                                                int G, const int* __restrict__ observed, int K, int mode,
                                                                float offset, float scale, float* __restrict__ x_dst,
-                                                               uint8_t* __restrict__ mask, int vec) {
+                                                               uint8_t* __restrict__ mask, int vec,
+                                                               const uint8_t* __restrict__ available, int nan_missing) {
   __shared__ int slot[OBS_TILE];
   const int tid = threadIdx.x;
   const int j = blockIdx.x * OBS_T + tid;
@@ -60,8 +70,14 @@ __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __re
       mk[e] = s ? 0 : 1;
       val[e] = 0.f;
       if (s && row_ok) {
-        const float r = readings ? src[row * K + (s - 1)] : src[row * N + v];
-        val[e] = obs_normalise(r, readings ? mode : GATRES_NORMALISE_NONE, offset, scale);
+        bool have = true;
+        if (AVAIL && available) have = available[row * K + (s - 1)] != 0;
+        if (have) {
+          const float r = readings ? src[row * K + (s - 1)] : src[row * N + v];
+          if (AVAIL && nan_missing && readings && obs_is_nan(r)) have = false;
+          else val[e] = obs_normalise(r, readings ? mode : GATRES_NORMALISE_NONE, offset, scale);
+        }
+        if (AVAIL && !have) mk[e] = 1;
       }
     }
     if (vec && v0 >= 0 && v0 + 4 <= N) {
@@ -138,17 +154,23 @@ __global__ __launch_bounds__(EW_T) void estimate_write_kernel(const float* __res
 constexpr int NE_WAVES = 8;
 constexpr int NE_T = NE_WAVES * GATRES_WAVE;
 constexpr int NE_U = 8;                        // rows in flight per wave and trip
-constexpr int NE_F = 6;                        // accumulated fields: the record's slots [1..6]
+constexpr int NE_F = 6;                        // accumulated fields: the record's slots [1..6] (AVAIL: and the hidden count)
 
 // Workgroup b takes the 64 nodes [64 b, 64 b + 64): lane l of every wave is node 64 b + l, so a wave reads 256 consecutive bytes
 // of a row.  Wave w takes the rows w, w + NE_WAVES, ... in ascending order (NE_U of them in flight per trip: a chunk of
 // GATRES_NODE_ERROR_CHUNK = NE_WAVES * NE_U rows per workgroup), each lane adding its node's terms in that order; the waves'
 // partials go through LDS and are added in wave order.  The association depends on S alone.
+// AVAIL: seen[] holds k + 1 for the sensor observed[k]; a sensor lane reads available[s * K + k] with its rows and skips the
+// entries it was observed in (they add nothing, so a lane that skips none forms the sums of the kernel without AVAIL, bit for
+// bit); the hidden entries are counted as a seventh field.  Record: [0] hidden entries, [1..6] over them, [7] S - [0].
+template <bool AVAIL>
 __global__ __launch_bounds__(NE_T) void node_error_moments_kernel(const float* __restrict__ est, const float* __restrict__ truth,
                                                                   long long S, int N, float scale, float offset,
                                                                   const int* __restrict__ observed, int K,
-                                                                  double* __restrict__ table) {
-  __shared__ double part[NE_WAVES][NE_F][GATRES_WAVE];
+                                                                  double* __restrict__ table,
+                                                                  const uint8_t* __restrict__ available) {
+  constexpr int NF = AVAIL ? NE_F + 1 : NE_F;
+  __shared__ double part[NE_WAVES][NF][GATRES_WAVE];
   __shared__ int seen[GATRES_WAVE];
   const int lane = threadIdx.x % GATRES_WAVE, wave = threadIdx.x / GATRES_WAVE;
   const int v_lo = blockIdx.x * GATRES_WAVE, v = v_lo + lane;
@@ -156,22 +178,38 @@ __global__ __launch_bounds__(NE_T) void node_error_moments_kernel(const float* _
   __syncthreads();
   for (int k = threadIdx.x; k < K; k += NE_T) {
     const int o = observed[k];
-    if (o >= v_lo && o < v_lo + GATRES_WAVE) seen[o - v_lo] = 1;
+    if (o >= v_lo && o < v_lo + GATRES_WAVE) seen[o - v_lo] = AVAIL ? k + 1 : 1;
   }
-  double a[NE_F] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};        // sum e, sum |e|, sum e^2, max |e|, #kept, sum |e| / |t|
+  if (AVAIL) __syncthreads();
+  const int sensor = AVAIL ? seen[lane] - 1 : -1;          // (AVAIL: this lane's column of available[], -1: not a sensor)
+  double a[NF] = {};                                        // sum e, sum |e|, sum e^2, max |e|, #kept, sum |e| / |t| (, #hidden)
   float amax = 0.f;
   if (v < N) {
     for (long long s0 = wave; s0 < S; s0 += (long long)NE_U * NE_WAVES) {
       float p[NE_U], t[NE_U];
+      uint8_t av[NE_U] = {};
 #pragma unroll
       for (int u = 0; u < NE_U; ++u) {
         const long long s = s0 + (long long)u * NE_WAVES;
         p[u] = s < S ? est[s * N + v] : 0.f;
         t[u] = s < S ? truth[s * N + v] : 0.f;
       }
+      // (one region for the sensor lanes, so that the trip's NE_U bytes are in flight together with its rows; a row past the
+      //  end reads the last row's byte, which the loop below skips)
+      if (AVAIL && sensor >= 0) {
+#pragma unroll
+        for (int u = 0; u < NE_U; ++u) {
+          const long long s = s0 + (long long)u * NE_WAVES;
+          av[u] = available[(s < S ? s : S - 1) * K + sensor];
+        }
+      }
 #pragma unroll
       for (int u = 0; u < NE_U; ++u) {           // (in row order: the same association as a plain loop)
         if (s0 + (long long)u * NE_WAVES >= S) continue;
+        if (AVAIL) {
+          if (av[u]) continue;
+          a[NF - 1] += 1.0;
+        }
         const float tr = gatres_descale(t[u], scale, offset);
         const float e = __fsub_rn(p[u], tr);
         const float ae = fabsf(e), at = fabsf(tr);
@@ -188,29 +226,29 @@ __global__ __launch_bounds__(NE_T) void node_error_moments_kernel(const float* _
   }
   a[3] = (double)amax;
 #pragma unroll
-  for (int f = 0; f < NE_F; ++f) part[wave][f][lane] = a[f];
+  for (int f = 0; f < NF; ++f) part[wave][f][lane] = a[f];
   __syncthreads();
   if (wave == 0 && v < N) {
-    double r[NE_F];
+    double r[NF];
 #pragma unroll
-    for (int f = 0; f < NE_F; ++f) {
+    for (int f = 0; f < NF; ++f) {
       double s = part[0][f][lane];
       for (int w = 1; w < NE_WAVES; ++w) s = f == 3 ? fmax(s, part[w][f][lane]) : s + part[w][f][lane];
       r[f] = s;
     }
-    double* rec = table + (size_t)v * GATRES_NODE_ERROR_RECORD;
-    rec[0] = (double)S;
+    double* rec = table + (size_t)v * (AVAIL ? GATRES_NODE_ERROR_AVAIL_RECORD : GATRES_NODE_ERROR_RECORD);
+    rec[0] = AVAIL ? r[NF - 1] : (double)S;
     rec[1] = r[0]; rec[2] = r[1]; rec[3] = r[2]; rec[4] = r[3]; rec[5] = r[4]; rec[6] = r[5];
-    rec[7] = seen[lane] ? 1.0 : 0.0;
+    rec[7] = AVAIL ? (double)S - r[NF - 1] : (seen[lane] ? 1.0 : 0.0);
   }
 }
 
-}  // namespace
-
-extern "C" int gatres_stage_observed(const float* src, int32_t layout, int64_t src_rows, const int64_t* rows, int64_t first_row,
-                                     int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed, int32_t num_observed,
-                                     int32_t normalise, double offset, double factor, float* x_dst, uint8_t* mask,
-                                     void* stream) {
+// The checks and the launch of both staging entry points (AVAIL: with the availability arguments).
+template <bool AVAIL>
+int stage_observed(const float* src, int32_t layout, int64_t src_rows, const int64_t* rows, int64_t first_row,
+                   int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed, int32_t num_observed, int32_t normalise,
+                   double offset, double factor, float* x_dst, uint8_t* mask, const uint8_t* available, int32_t nan_is_missing,
+                   void* stream) {
   if (!src || !observed || !x_dst || !mask || src == x_dst) return GATRES_E_BADARG;
   if (nodes_per_graph <= 0 || num_graphs <= 0 || num_observed <= 0 || num_observed > nodes_per_graph) return GATRES_E_BADARG;
   if ((int64_t)nodes_per_graph * num_graphs > INT32_MAX) return GATRES_E_BADARG;
@@ -218,6 +256,14 @@ extern "C" int gatres_stage_observed(const float* src, int32_t layout, int64_t s
   if (layout == GATRES_OBSERVED_READINGS && rows) return GATRES_E_BADARG;
   if (src_rows <= 0 || (!rows && (first_row < 0 || first_row > src_rows - num_graphs))) return GATRES_E_BADARG;
   if (normalise < GATRES_NORMALISE_NONE || normalise > GATRES_NORMALISE_RECIPROCAL) return GATRES_E_BADARG;
+  if (AVAIL) {
+    if (!available && !nan_is_missing) return GATRES_E_BADARG;
+    // (available[src_rows][num_observed] must not overlap the bytes this launch writes)
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(available), a1 = a0 + (uintptr_t)src_rows * (uintptr_t)num_observed;
+    const uintptr_t total = (uintptr_t)nodes_per_graph * (uintptr_t)num_graphs;
+    const uintptr_t x0 = reinterpret_cast<uintptr_t>(x_dst), m0 = reinterpret_cast<uintptr_t>(mask);
+    if (available && ((a0 < x0 + 4 * total && x0 < a1) || (a0 < m0 + total && m0 < a1))) return GATRES_E_BADARG;
+  }
   float scale = 1.f;
   if (normalise != GATRES_NORMALISE_NONE) {
     if (!((float)factor != 0.f)) return GATRES_E_BADARG;
@@ -226,11 +272,30 @@ extern "C" int gatres_stage_observed(const float* src, int32_t layout, int64_t s
   const int vec = gatres_aligned16(x_dst) && (reinterpret_cast<uintptr_t>(mask) & 3u) == 0;
   const int chunks = (nodes_per_graph + 3) / 4 + 1;
   const dim3 grid((chunks + OBS_T - 1) / OBS_T, num_graphs < OBS_MAX_GY ? num_graphs : OBS_MAX_GY);
-  hipLaunchKernelGGL(stage_observed_kernel, grid, dim3(OBS_T), 0, gatres_stream(stream), src,
+  hipLaunchKernelGGL(stage_observed_kernel<AVAIL>, grid, dim3(OBS_T), 0, gatres_stream(stream), src,
                      (int)(layout == GATRES_OBSERVED_READINGS), (long long)src_rows, reinterpret_cast<const long long*>(rows),
                      (long long)first_row, (int)nodes_per_graph, (int)num_graphs, observed, (int)num_observed, (int)normalise,
-                     (float)offset, scale, x_dst, mask, vec);
+                     (float)offset, scale, x_dst, mask, vec, available, (int)(nan_is_missing != 0));
   return gatres_launch_status();
+}
+
+}  // namespace
+
+extern "C" int gatres_stage_observed(const float* src, int32_t layout, int64_t src_rows, const int64_t* rows, int64_t first_row,
+                                     int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed, int32_t num_observed,
+                                     int32_t normalise, double offset, double factor, float* x_dst, uint8_t* mask,
+                                     void* stream) {
+  return stage_observed<false>(src, layout, src_rows, rows, first_row, nodes_per_graph, num_graphs, observed, num_observed,
+                               normalise, offset, factor, x_dst, mask, nullptr, 0, stream);
+}
+
+extern "C" int gatres_stage_observed_available(const float* src, int32_t layout, int64_t src_rows, const int64_t* rows,
+                                               int64_t first_row, int32_t nodes_per_graph, int32_t num_graphs,
+                                               const int32_t* observed, int32_t num_observed, int32_t normalise, double offset,
+                                               double factor, float* x_dst, uint8_t* mask, const uint8_t* available,
+                                               int32_t nan_is_missing, void* stream) {
+  return stage_observed<true>(src, layout, src_rows, rows, first_row, nodes_per_graph, num_graphs, observed, num_observed,
+                              normalise, offset, factor, x_dst, mask, available, nan_is_missing, stream);
 }
 
 extern "C" int gatres_estimate_write(const float* out, const float* x, const uint8_t* mask, int32_t nodes_per_graph,
@@ -258,8 +323,21 @@ extern "C" int gatres_node_error_moments(const float* est, const float* truth, i
   if (num_observed <= 0 || num_observed > nodes_per_graph) return GATRES_E_BADARG;
   static_assert(GATRES_NODE_ERROR_CHUNK == NE_WAVES * NE_U, "gatres.h states the chunk of the moments kernel");
   static_assert(GATRES_NODE_ERROR_RECORD == 8, "record layout");
-  hipLaunchKernelGGL(node_error_moments_kernel, dim3((nodes_per_graph + GATRES_WAVE - 1) / GATRES_WAVE), dim3(NE_T), 0,
+  hipLaunchKernelGGL(node_error_moments_kernel<false>, dim3((nodes_per_graph + GATRES_WAVE - 1) / GATRES_WAVE), dim3(NE_T), 0,
                      gatres_stream(stream), est, truth, (long long)num_snapshots, (int)nodes_per_graph, (float)scale,
-                     (float)offset, observed, (int)num_observed, table);
+                     (float)offset, observed, (int)num_observed, table, (const uint8_t*)nullptr);
+  return gatres_launch_status();
+}
+
+extern "C" int gatres_node_error_moments_available(const float* est, const float* truth, int64_t num_snapshots,
+                                                   int32_t nodes_per_graph, double scale, double offset, const int32_t* observed,
+                                                   int32_t num_observed, const uint8_t* available, double* table, void* stream) {
+  if (!est || !truth || !observed || !available || !table || num_snapshots <= 0 || nodes_per_graph <= 0) return GATRES_E_BADARG;
+  if (num_observed <= 0 || num_observed > nodes_per_graph) return GATRES_E_BADARG;
+  if (reinterpret_cast<const void*>(available) == reinterpret_cast<const void*>(table)) return GATRES_E_BADARG;
+  static_assert(GATRES_NODE_ERROR_AVAIL_RECORD == 8, "record layout");
+  hipLaunchKernelGGL(node_error_moments_kernel<true>, dim3((nodes_per_graph + GATRES_WAVE - 1) / GATRES_WAVE), dim3(NE_T), 0,
+                     gatres_stream(stream), est, truth, (long long)num_snapshots, (int)nodes_per_graph, (float)scale,
+                     (float)offset, observed, (int)num_observed, table, available);
   return gatres_launch_status();
 }

@@ -847,6 +847,42 @@ int gatres_estimate_write(const float* out, const float* x, const uint8_t* mask,
 int gatres_node_error_moments(const float* est, const float* truth, int64_t num_snapshots, int32_t nodes_per_graph, double scale,
                               double offset, const int32_t* observed, int32_t num_observed, double* table, void* stream);
 
+/* Estimation when some sensor readings are missing (symbols only: the ABI stays).  A sensor without a reading in a snapshot is
+ * one more hidden node of that snapshot: the model was trained with random masks.
+ *
+ * gatres_stage_observed with an availability: the arguments and checks of gatres_stage_observed, and
+ *   available       device uint8 [src_rows][num_observed], non-zero: the reading is present.  It is indexed by the SOURCE row
+ *                   r = rows ? rows[g] : first_row + g of graph g, like src.  NULL (every reading present) only with
+ *                   nan_is_missing != 0; it must not overlap x_dst or mask.
+ *   nan_is_missing  non-zero: in layout GATRES_OBSERVED_READINGS a raw reading that is a NaN is missing.  In layout
+ *                   GATRES_OBSERVED_FULL_ROWS it has no effect: available alone decides.
+ * At v = observed[k] of graph g:
+ *   present  (available == NULL || available[r * K + k] != 0) and not (nan_is_missing, readings layout, reading is NaN):
+ *            mask = 0, x_dst = the value exactly as gatres_stage_observed forms it (same normalisation, same rounding);
+ *   missing  mask = 1, x_dst = 0.0f; the reading is not used (and not loaded when available says so).
+ * Every other node: mask = 1, x_dst = 0.0f.  Every byte of mask and every float of x_dst of the batch is written exactly once,
+ * in one launch of the same grid: the kernel of gatres_stage_observed compiled with the availability as a compile-time fact.  A
+ * row outside [0, src_rows) named by rows[] is read in neither array (its observed nodes get mask = 0, x_dst = 0, as there).
+ * GATRES_E_BADARG before any launch: whatever gatres_stage_observed refuses, available == NULL with nan_is_missing == 0, and an
+ * available that overlaps x_dst or mask. */
+int gatres_stage_observed_available(const float* src, int32_t layout, int64_t src_rows, const int64_t* rows, int64_t first_row,
+                                    int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed, int32_t num_observed,
+                                    int32_t normalise, double offset, double factor, float* x_dst, uint8_t* mask,
+                                    const uint8_t* available, int32_t nan_is_missing, void* stream);
+
+/* gatres_node_error_moments over the HIDDEN entries only.  available: device uint8 [S][num_observed], required.  The entry
+ * (s, v) is hidden unless v == observed[k] and available[s * K + k] != 0.  table[N][GATRES_NODE_ERROR_AVAIL_RECORD] (device
+ * double), per node v over its hidden entries, with e, t and D() as in gatres_node_error_moments:
+ *   [0] number of hidden entries   [1] sum e   [2] sum |e|   [3] sum e^2   [4] max |e|   [5] #{|t| > 0.01f}
+ *   [6] sum over those of |e| / |t|   [7] number of snapshots in which v was observed ([0] + [7] == S)
+ * The traversal and the order of the fp64 sums are those of gatres_node_error_moments and an entry that is not hidden adds
+ * nothing: a node outside observed[] gets that kernel's record bit for bit, a sensor present in every snapshot [0] = 0,
+ * [7] = S and zero sums.  Only the lanes of sensor nodes read available.  One launch, no atomics: the same bits on every run. */
+#define GATRES_NODE_ERROR_AVAIL_RECORD 8
+int gatres_node_error_moments_available(const float* est, const float* truth, int64_t num_snapshots, int32_t nodes_per_graph,
+                                        double scale, double offset, const int32_t* observed, int32_t num_observed,
+                                        const uint8_t* available, double* table, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
