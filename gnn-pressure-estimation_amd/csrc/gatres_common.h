@@ -123,6 +123,14 @@ __device__ __forceinline__ float gatres_descale(float s, float scale, float offs
   return __fadd_rn(__fmul_rn(s, scale), offset);
 }
 
+// The 64-bit finaliser of splitmix64 (arithmetic modulo 2^64): the hash behind the device mask sampler's keys (k_mask.h), the
+// edge-index hash (k_misc.hip) and the measurement noise of gatres_stage_observed_noisy (k_estimate.hip)
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+  return z ^ (z >> 31);
+}
+
 __device__ __forceinline__ float gatres_leaky(float v) { return v > 0.f ? v : v * GATRES_NEG_SLOPE; }
 
 // The reference's other training criteria (gatres.h: GATRES_LOSS_MAE, GATRES_LOSS_SCE) on one masked node: returns the node's

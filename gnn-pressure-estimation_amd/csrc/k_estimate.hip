@@ -8,6 +8,11 @@
 // The first two are memory-bound element passes over one batch (16-byte accesses on the batch's flat arrays, which are aligned
 // whatever the graph size); the third streams two [S][N] matrices once with the lanes of a wave on consecutive nodes and sums in
 // fp64 in a fixed order, without atomics: the same bits on every run.
+// Measurement noise (estimate_ensemble, noise_report):
+//   gatres_stage_observed_noisy   the staging kernel with NOISE = true: graph g is one (snapshot, member) pair and every present
+//                                 reading gets sigma[k] * z, z drawn in the launch from (seed, member, source row, k);
+//   gatres_ensemble_reduce        mean and sample standard deviation over the members of each snapshot, one element pass;
+//   gatres_node_spread_moments    per-node moments of a [S][N] matrix of standard deviations: the traversal of the error moments.
 #include "gatres_common.h"
 
 namespace {
@@ -36,13 +41,40 @@ __device__ __forceinline__ bool obs_is_nan(float v) { return (__float_as_uint(v)
 // AVAIL (a compile-time fact of the launch; gatres_stage_observed is the instantiation without it and reads neither argument):
 // the reading of sensor k in source row r counts only where available[r * K + k] != 0 (available == NULL: everywhere) and, with
 // nan_missing in the readings layout, is no NaN; a missing reading is not loaded, its node gets x = 0 and mask = 1.
-template <bool AVAIL>
+// NOISE (gatres_stage_observed_noisy; always with AVAIL): graph g is pair p = first_row + g of a snapshot-major list of
+// (source row, member) pairs -- source row p / members, member member0 + p % members -- and a PRESENT reading r of sensor k is
+// staged as normalise(r + sigma[k] * z).  z = obs_noise(...) is a pure function of (seed, member, source row, k): the launch,
+// the batch and the graph's place in it do not enter.  A missing reading draws nothing.  The draws are taken in a loop of their
+// own, one trip per present sensor of the lane's chunk: the wave runs the division, the hashes and logf / sqrtf / cosf as often as
+// its busiest lane holds sensors (once, as a rule), not once per element of the chunk.
+struct ObsNoise {
+  const float* sigma;      // [K], in the units of src
+  uint64_t seed;
+  long long member0;
+  int members;
+};
+
+// One standard normal by Box-Muller from the 48 upper bits of one hash (gatres.h states the generator): u1 in (0, 1] and u2 in
+// [0, 1) are 24-bit integers times 2^-24, both exact in fp32.
+__device__ __forceinline__ uint64_t obs_noise_stream(uint64_t seed, uint64_t member) {
+  return mix64(seed + 0x9E3779B97F4A7C15ULL * (member + 1));
+}
+__device__ __forceinline__ float obs_noise(uint64_t stream, long long row, int K, int k) {
+  const uint64_t h = mix64(stream + 0xBF58476D1CE4E5B9ULL * ((uint64_t)row * (uint64_t)K + (uint64_t)k + 1));
+  const float u1 = __fmul_rn((float)(uint32_t)((h >> 40) + 1), 0x1p-24f);
+  const float u2 = __fmul_rn((float)(uint32_t)((h >> 8) & 0xFFFFFFu), 0x1p-24f);
+  return __fmul_rn(sqrtf(__fmul_rn(-2.f, logf(u1))), cosf(__fmul_rn(6.283185307179586f, u2)));
+}
+
+template <bool AVAIL, bool NOISE>
 __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __restrict__ src, int readings, long long src_rows,
                                                                const long long* __restrict__ rows, long long first_row, int N,
                                                                int G, const int* __restrict__ observed, int K, int mode,
                                                                float offset, float scale, float* __restrict__ x_dst,
                                                                uint8_t* __restrict__ mask, int vec,
-                                                               const uint8_t* __restrict__ available, int nan_missing) {
+                                                               const uint8_t* __restrict__ available, int nan_missing,
+                                                               ObsNoise nz) {
+  static_assert(AVAIL || !NOISE, "the noisy launch carries the availability arguments");
   __shared__ int slot[OBS_TILE];
   const int tid = threadIdx.x;
   const int j = blockIdx.x * OBS_T + tid;
@@ -59,8 +91,22 @@ __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __re
     const int shift = vec ? (int)((4 - (base & 3)) & 3) : 0;
     const int v0 = shift + 4 * (j - 1);
     if (v0 >= N || v0 + 4 <= 0) continue;
-    const long long row = rows ? rows[g] : first_row + g;
-    const bool row_ok = row >= 0 && row < src_rows;          // (a row outside the matrix is not read: its nodes get 0)
+    // (NOISE: the pair's row lies inside the matrix, the host checked the pair range; the 64-bit division is left to the lanes
+    //  that hold a sensor)
+    long long row = NOISE ? 0 : (rows ? rows[g] : first_row + g);
+    const bool row_ok = NOISE || (row >= 0 && row < src_rows);          // (a row outside the matrix is not read: its nodes get 0)
+    uint64_t noise_stream = 0;
+    unsigned draw = 0;                                                  // NOISE: the elements that hold a present reading
+    if (NOISE) {
+      bool any = false;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) any |= v0 + e >= 0 && v0 + e < N && slot[v0 + e - tile_lo] != 0;
+      if (any) {
+        const long long pair = first_row + g;
+        row = pair / nz.members;
+        noise_stream = obs_noise_stream(nz.seed, (uint64_t)(nz.member0 + (pair - row * nz.members)));
+      }
+    }
     float val[4];
     uint8_t mk[4];
 #pragma unroll
@@ -75,9 +121,25 @@ __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __re
         if (have) {
           const float r = readings ? src[row * K + (s - 1)] : src[row * N + v];
           if (AVAIL && nan_missing && readings && obs_is_nan(r)) have = false;
-          else val[e] = obs_normalise(r, readings ? mode : GATRES_NORMALISE_NONE, offset, scale);
+          else if (NOISE) {
+            val[e] = r;                                                 // (raw: the loop below adds the noise and normalises)
+            draw |= 1u << e;
+          } else val[e] = obs_normalise(r, readings ? mode : GATRES_NORMALISE_NONE, offset, scale);
         }
         if (AVAIL && !have) mk[e] = 1;
+      }
+    }
+    if (NOISE) {
+      while (draw) {
+        const int e = __ffs(draw) - 1;
+        draw &= draw - 1;
+        const int k = slot[v0 + e - tile_lo] - 1;
+        float r = e == 0 ? val[0] : e == 1 ? val[1] : e == 2 ? val[2] : val[3];
+        r = __fadd_rn(r, __fmul_rn(nz.sigma[k], obs_noise(noise_stream, row, K, k)));
+        r = obs_normalise(r, readings ? mode : GATRES_NORMALISE_NONE, offset, scale);
+#pragma unroll
+        for (int f = 0; f < 4; ++f)
+          if (f == e) val[f] = r;
       }
     }
     if (vec && v0 >= 0 && v0 + 4 <= N) {
@@ -156,6 +218,24 @@ constexpr int NE_T = NE_WAVES * GATRES_WAVE;
 constexpr int NE_U = 8;                        // rows in flight per wave and trip
 constexpr int NE_F = 6;                        // accumulated fields: the record's slots [1..6] (AVAIL: and the hidden count)
 
+// The end of both moments kernels: the waves' partial records go through LDS and wave 0 combines them in wave order, field
+// MAXF by fmax and every other field by addition.  True in the lanes of wave 0, which then hold the combined record in r[].
+template <int NF, int MAXF>
+__device__ __forceinline__ bool ne_combine(double (*part)[NF][GATRES_WAVE], const double (&a)[NF], int lane, int wave,
+                                           double (&r)[NF]) {
+#pragma unroll
+  for (int f = 0; f < NF; ++f) part[wave][f][lane] = a[f];
+  __syncthreads();
+  if (wave != 0) return false;
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    double s = part[0][f][lane];
+    for (int w = 1; w < NE_WAVES; ++w) s = f == MAXF ? fmax(s, part[w][f][lane]) : s + part[w][f][lane];
+    r[f] = s;
+  }
+  return true;
+}
+
 // Workgroup b takes the 64 nodes [64 b, 64 b + 64): lane l of every wave is node 64 b + l, so a wave reads 256 consecutive bytes
 // of a row.  Wave w takes the rows w, w + NE_WAVES, ... in ascending order (NE_U of them in flight per trip: a chunk of
 // GATRES_NODE_ERROR_CHUNK = NE_WAVES * NE_U rows per workgroup), each lane adding its node's terms in that order; the waves'
@@ -225,17 +305,8 @@ __global__ __launch_bounds__(NE_T) void node_error_moments_kernel(const float* _
     }
   }
   a[3] = (double)amax;
-#pragma unroll
-  for (int f = 0; f < NF; ++f) part[wave][f][lane] = a[f];
-  __syncthreads();
-  if (wave == 0 && v < N) {
-    double r[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      double s = part[0][f][lane];
-      for (int w = 1; w < NE_WAVES; ++w) s = f == 3 ? fmax(s, part[w][f][lane]) : s + part[w][f][lane];
-      r[f] = s;
-    }
+  double r[NF];
+  if (ne_combine<NF, 3>(part, a, lane, wave, r) && v < N) {
     double* rec = table + (size_t)v * (AVAIL ? GATRES_NODE_ERROR_AVAIL_RECORD : GATRES_NODE_ERROR_RECORD);
     rec[0] = AVAIL ? r[NF - 1] : (double)S;
     rec[1] = r[0]; rec[2] = r[1]; rec[3] = r[2]; rec[4] = r[3]; rec[5] = r[4]; rec[6] = r[5];
@@ -243,21 +314,128 @@ __global__ __launch_bounds__(NE_T) void node_error_moments_kernel(const float* _
   }
 }
 
-// The checks and the launch of both staging entry points (AVAIL: with the availability arguments).
-template <bool AVAIL>
+// ---- per-node spread moments ---------------------------------------------------------------------------------------------------
+// The traversal of node_error_moments_kernel over ONE matrix: workgroup b takes the nodes [64 b, 64 b + 64), wave w the rows
+// w, w + NE_WAVES, ... in ascending order with NE_U of them in flight, each lane adding its node's terms in that order, the
+// waves' partials combined in wave order.  Record: [0] S, [1] sum (double)sd * (double)sd, [2] max sd, [3] sum sd.
+__global__ __launch_bounds__(NE_T) void node_spread_moments_kernel(const float* __restrict__ sd, long long S, int N,
+                                                                   double* __restrict__ table) {
+  constexpr int NF = 3;                                     // sum sd^2, max sd, sum sd
+  __shared__ double part[NE_WAVES][NF][GATRES_WAVE];
+  const int lane = threadIdx.x % GATRES_WAVE, wave = threadIdx.x / GATRES_WAVE;
+  const int v = blockIdx.x * GATRES_WAVE + lane;
+  double a[NF] = {};
+  float smax = 0.f;
+  if (v < N) {
+    for (long long s0 = wave; s0 < S; s0 += (long long)NE_U * NE_WAVES) {
+      float p[NE_U];
+#pragma unroll
+      for (int u = 0; u < NE_U; ++u) {
+        const long long s = s0 + (long long)u * NE_WAVES;
+        p[u] = s < S ? sd[s * N + v] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < NE_U; ++u) {           // (in row order: the same association as a plain loop)
+        if (s0 + (long long)u * NE_WAVES >= S) continue;
+        a[0] += (double)p[u] * (double)p[u];
+        smax = fmaxf(smax, p[u]);
+        a[2] += (double)p[u];
+      }
+    }
+  }
+  a[1] = (double)smax;
+  double r[NF];
+  if (ne_combine<NF, 1>(part, a, lane, wave, r) && v < N) {
+    double* rec = table + (size_t)v * GATRES_NODE_SPREAD_RECORD;
+    rec[0] = (double)S; rec[1] = r[0]; rec[2] = r[1]; rec[3] = r[2];
+  }
+}
+
+// ---- ensemble reduce -----------------------------------------------------------------------------------------------------------
+constexpr int ER_T = 256;
+
+// One chunk of W consecutive nodes of one snapshot per thread and trip (W = 4: 16-byte accesses, when the host found N, both
+// strides and the three pointers fit; W = 1 otherwise); the chunks of all snapshots are numbered row by row, so the lanes of a
+// wave read consecutive bytes of a member's row whatever N is, and the grid is capped and strides over them.  Two passes over the snapshot's M member rows in member order, both in fp64: the sum for the mean, then the sum of the
+// squared deviations from the fp64 mean (the second pass finds the rows in L2; M rows of registers would bound M).  No
+// contraction (the library is compiled with -ffp-contract=off), no atomics.
+template <int W>
+__global__ __launch_bounds__(ER_T) void ensemble_reduce_kernel(const float* __restrict__ mem, long long C, int M, int N,
+                                                               long long stride, float* __restrict__ mean,
+                                                               float* __restrict__ sd, long long out_stride,
+                                                               long long first_row) {
+  const int per_row = (N + W - 1) / W;
+  for (long long i = (long long)blockIdx.x * ER_T + threadIdx.x; i < C * per_row; i += (long long)gridDim.x * ER_T) {
+    const long long s = i / per_row;
+    const int v0 = W * (int)(i - s * per_row);
+    const float* row0 = mem + s * M * stride + v0;
+    double sum[W], m64[W], sq[W];
+#pragma unroll
+    for (int e = 0; e < W; ++e) sum[e] = sq[e] = 0.0;
+    for (int m = 0; m < M; ++m) {
+      float x[W];
+      if constexpr (W == 4) { const float4 t = ld4(row0 + m * stride); x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w; }
+      else x[0] = row0[m * stride];
+#pragma unroll
+      for (int e = 0; e < W; ++e) sum[e] += (double)x[e];
+    }
+#pragma unroll
+    for (int e = 0; e < W; ++e) m64[e] = sum[e] / (double)M;
+    for (int m = 0; m < M; ++m) {
+      float x[W];
+      if constexpr (W == 4) { const float4 t = ld4(row0 + m * stride); x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w; }
+      else x[0] = row0[m * stride];
+#pragma unroll
+      for (int e = 0; e < W; ++e) {
+        const double d = (double)x[e] - m64[e];
+        sq[e] += d * d;
+      }
+    }
+    float om[W], os[W];
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+      om[e] = (float)m64[e];
+      os[e] = M > 1 ? (float)sqrt(sq[e] / (double)(M - 1)) : 0.f;
+    }
+    const long long o = (first_row + s) * out_stride + v0;
+    if constexpr (W == 4) {
+      st4(mean + o, make_float4(om[0], om[1], om[2], om[3]));
+      st4(sd + o, make_float4(os[0], os[1], os[2], os[3]));
+    } else {
+      mean[o] = om[0];
+      sd[o] = os[0];
+    }
+  }
+}
+
+static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// The checks and the launch of the staging entry points (AVAIL: with the availability arguments; NOISE: first_row is the first
+// pair, rows is NULL and nz holds the noise arguments).
+template <bool AVAIL, bool NOISE = false>
 int stage_observed(const float* src, int32_t layout, int64_t src_rows, const int64_t* rows, int64_t first_row,
                    int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed, int32_t num_observed, int32_t normalise,
                    double offset, double factor, float* x_dst, uint8_t* mask, const uint8_t* available, int32_t nan_is_missing,
-                   void* stream) {
+                   void* stream, ObsNoise nz = ObsNoise{nullptr, 0, 0, 1}) {
   if (!src || !observed || !x_dst || !mask || src == x_dst) return GATRES_E_BADARG;
   if (nodes_per_graph <= 0 || num_graphs <= 0 || num_observed <= 0 || num_observed > nodes_per_graph) return GATRES_E_BADARG;
   if ((int64_t)nodes_per_graph * num_graphs > INT32_MAX) return GATRES_E_BADARG;
   if (layout != GATRES_OBSERVED_FULL_ROWS && layout != GATRES_OBSERVED_READINGS) return GATRES_E_BADARG;
   if (layout == GATRES_OBSERVED_READINGS && rows) return GATRES_E_BADARG;
-  if (src_rows <= 0 || (!rows && (first_row < 0 || first_row > src_rows - num_graphs))) return GATRES_E_BADARG;
+  if (NOISE) {
+    // (pairs [first_row, first_row + num_graphs) of the src_rows * members there are)
+    if (!nz.sigma || nz.members < 1 || nz.member0 < 0 || src_rows <= 0 || src_rows > INT64_MAX / nz.members) return GATRES_E_BADARG;
+    if (first_row < 0 || first_row > src_rows * nz.members - num_graphs) return GATRES_E_BADARG;
+    const uint64_t total = (uint64_t)nodes_per_graph * (uint64_t)num_graphs;
+    if (bytes_overlap(nz.sigma, 4 * (uint64_t)num_observed, x_dst, 4 * total) ||
+        bytes_overlap(nz.sigma, 4 * (uint64_t)num_observed, mask, total)) return GATRES_E_BADARG;
+  } else if (src_rows <= 0 || (!rows && (first_row < 0 || first_row > src_rows - num_graphs))) return GATRES_E_BADARG;
   if (normalise < GATRES_NORMALISE_NONE || normalise > GATRES_NORMALISE_RECIPROCAL) return GATRES_E_BADARG;
   if (AVAIL) {
-    if (!available && !nan_is_missing) return GATRES_E_BADARG;
+    if (!NOISE && !available && !nan_is_missing) return GATRES_E_BADARG;
     // (available[src_rows][num_observed] must not overlap the bytes this launch writes)
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(available), a1 = a0 + (uintptr_t)src_rows * (uintptr_t)num_observed;
     const uintptr_t total = (uintptr_t)nodes_per_graph * (uintptr_t)num_graphs;
@@ -272,10 +450,10 @@ int stage_observed(const float* src, int32_t layout, int64_t src_rows, const int
   const int vec = gatres_aligned16(x_dst) && (reinterpret_cast<uintptr_t>(mask) & 3u) == 0;
   const int chunks = (nodes_per_graph + 3) / 4 + 1;
   const dim3 grid((chunks + OBS_T - 1) / OBS_T, num_graphs < OBS_MAX_GY ? num_graphs : OBS_MAX_GY);
-  hipLaunchKernelGGL(stage_observed_kernel<AVAIL>, grid, dim3(OBS_T), 0, gatres_stream(stream), src,
+  hipLaunchKernelGGL((stage_observed_kernel<AVAIL, NOISE>), grid, dim3(OBS_T), 0, gatres_stream(stream), src,
                      (int)(layout == GATRES_OBSERVED_READINGS), (long long)src_rows, reinterpret_cast<const long long*>(rows),
                      (long long)first_row, (int)nodes_per_graph, (int)num_graphs, observed, (int)num_observed, (int)normalise,
-                     (float)offset, scale, x_dst, mask, vec, available, (int)(nan_is_missing != 0));
+                     (float)offset, scale, x_dst, mask, vec, available, (int)(nan_is_missing != 0), nz);
   return gatres_launch_status();
 }
 
@@ -296,6 +474,16 @@ extern "C" int gatres_stage_observed_available(const float* src, int32_t layout,
                                                int32_t nan_is_missing, void* stream) {
   return stage_observed<true>(src, layout, src_rows, rows, first_row, nodes_per_graph, num_graphs, observed, num_observed,
                               normalise, offset, factor, x_dst, mask, available, nan_is_missing, stream);
+}
+
+extern "C" int gatres_stage_observed_noisy(const float* src, int32_t layout, int64_t src_rows, int64_t first_pair, int32_t members,
+                                           int64_t member0, int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed,
+                                           int32_t num_observed, int32_t normalise, double offset, double factor, float* x_dst,
+                                           uint8_t* mask, const uint8_t* available, int32_t nan_is_missing, const float* sigma,
+                                           uint64_t seed, void* stream) {
+  return stage_observed<true, true>(src, layout, src_rows, nullptr, first_pair, nodes_per_graph, num_graphs, observed,
+                                    num_observed, normalise, offset, factor, x_dst, mask, available, nan_is_missing, stream,
+                                    ObsNoise{sigma, seed, (long long)member0, (int)members});
 }
 
 extern "C" int gatres_estimate_write(const float* out, const float* x, const uint8_t* mask, int32_t nodes_per_graph,
@@ -339,5 +527,44 @@ extern "C" int gatres_node_error_moments_available(const float* est, const float
   hipLaunchKernelGGL(node_error_moments_kernel<true>, dim3((nodes_per_graph + GATRES_WAVE - 1) / GATRES_WAVE), dim3(NE_T), 0,
                      gatres_stream(stream), est, truth, (long long)num_snapshots, (int)nodes_per_graph, (float)scale,
                      (float)offset, observed, (int)num_observed, table, available);
+  return gatres_launch_status();
+}
+
+extern "C" int gatres_ensemble_reduce(const float* members_mat, int64_t num_snapshots, int32_t members, int32_t nodes_per_graph,
+                                      int64_t stride, float* mean, float* std_dev, int64_t out_rows, int64_t out_stride,
+                                      int64_t first_row, void* stream) {
+  if (!members_mat || !mean || !std_dev || num_snapshots <= 0 || members < 1 || nodes_per_graph <= 0) return GATRES_E_BADARG;
+  if (stride < nodes_per_graph || out_stride < nodes_per_graph) return GATRES_E_BADARG;
+  if (out_rows <= 0 || first_row < 0 || first_row > out_rows - num_snapshots) return GATRES_E_BADARG;
+  if (num_snapshots > INT64_MAX / 4 / members / stride || out_rows > INT64_MAX / 4 / out_stride) return GATRES_E_BADARG;
+  // (the rows of the source and the rows [first_row, first_row + num_snapshots) of either destination, strides included)
+  const uint64_t src_bytes = 4 * (uint64_t)num_snapshots * (uint64_t)members * (uint64_t)stride;
+  const uint64_t dst_bytes = 4 * (uint64_t)num_snapshots * (uint64_t)out_stride;
+  const float* m0 = mean + first_row * out_stride;
+  const float* s0 = std_dev + first_row * out_stride;
+  if (bytes_overlap(members_mat, src_bytes, m0, dst_bytes) || bytes_overlap(members_mat, src_bytes, s0, dst_bytes) ||
+      bytes_overlap(m0, dst_bytes, s0, dst_bytes)) return GATRES_E_BADARG;
+  const bool vec = nodes_per_graph % 4 == 0 && stride % 4 == 0 && out_stride % 4 == 0 && gatres_aligned16(members_mat) &&
+                   gatres_aligned16(mean) && gatres_aligned16(std_dev);
+  const int per = vec ? 4 : 1;
+  long long wgs = (num_snapshots * ((nodes_per_graph + per - 1) / per) + ER_T - 1) / ER_T;
+  if (wgs > 2048) wgs = 2048;
+  const dim3 grid((unsigned)wgs);
+  if (vec)
+    hipLaunchKernelGGL(ensemble_reduce_kernel<4>, grid, dim3(ER_T), 0, gatres_stream(stream), members_mat, (long long)num_snapshots,
+                       (int)members, (int)nodes_per_graph, (long long)stride, mean, std_dev, (long long)out_stride, (long long)first_row);
+  else
+    hipLaunchKernelGGL(ensemble_reduce_kernel<1>, grid, dim3(ER_T), 0, gatres_stream(stream), members_mat, (long long)num_snapshots,
+                       (int)members, (int)nodes_per_graph, (long long)stride, mean, std_dev, (long long)out_stride, (long long)first_row);
+  return gatres_launch_status();
+}
+
+extern "C" int gatres_node_spread_moments(const float* std_dev, int64_t num_snapshots, int32_t nodes_per_graph, double* table,
+                                          void* stream) {
+  if (!std_dev || !table || num_snapshots <= 0 || nodes_per_graph <= 0) return GATRES_E_BADARG;
+  if (reinterpret_cast<const void*>(std_dev) == reinterpret_cast<const void*>(table)) return GATRES_E_BADARG;
+  static_assert(GATRES_NODE_SPREAD_RECORD == 4, "record layout");
+  hipLaunchKernelGGL(node_spread_moments_kernel, dim3((nodes_per_graph + GATRES_WAVE - 1) / GATRES_WAVE), dim3(NE_T), 0,
+                     gatres_stream(stream), std_dev, (long long)num_snapshots, (int)nodes_per_graph, table);
   return gatres_launch_status();
 }

@@ -6,12 +6,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  return z ^ (z >> 31);
-}
-
 // Every node gets a unique 64-bit key (hash32(seed, step, node) << 32 | local id); the k = int(n*rate) smallest keys are
 // masked: an exactly-k uniform subset without replacement, the same distribution as np.random.choice(n, k, replace=False)
 // in utils/auxil.py:154-157.  The k-th key is found by an 8-pass byte-wise radix select in LDS (graphs beyond 2048 nodes)

@@ -14,10 +14,18 @@ Telemetry has gaps.  With ``available`` (uint8 / bool ``[S, K]`` on the device) 
 ``mask = 1``), which is what the model's training masks taught it.  Still three launches per batch, still nothing read back: no
 host scan for NaN.  ``error_map(available=...)`` reports over the hidden entries, ``sensor_failure_report`` is the leave-one-out
 back-test of a sensor layout (what does the loss of sensor k cost?) as K + 1 passes of one estimator.
+
+Readings carry error.  ``noise_std`` on the two passes stages one noisy realisation (``gatres_stage_observed_noisy``: the noise
+is drawn in the staging launch from ``(seed, member, snapshot, sensor)``, ``reading_noise`` restates it on the host);
+``estimate_ensemble`` / ``estimate_store_ensemble`` run M members per snapshot as one long pass over the S * M (snapshot, member)
+pairs and reduce them on the device (``gatres_ensemble_reduce``) to the mean and the standard deviation per junction, so the M
+result matrices never exist; ``noise_report`` adds the back-test error of the mean and the per-node spread
+(``gatres_node_spread_moments``): which junctions are sensitive to sensor error.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -28,6 +36,7 @@ from .snapshot_store import SnapshotStore
 
 NODE_ERROR_RECORD = _native.NODE_ERROR_RECORD
 NODE_ERROR_AVAIL_RECORD = _native.NODE_ERROR_AVAIL_RECORD
+NODE_SPREAD_RECORD = _native.NODE_SPREAD_RECORD
 
 
 def observed_from_names(node_names: Sequence[str], sensor_names: Sequence[str]) -> List[int]:
@@ -99,6 +108,68 @@ def _error_map_from_available_moments(table, observed_idx) -> Dict[str, np.ndarr
     out["nonsensor_mae"], out["nonsensor_rmse"] = pooled(~sensor)
     out["missing_sensor_mae"], out["missing_sensor_rmse"] = pooled(sensor)
     return out
+
+
+def _mix64(z: np.ndarray) -> np.ndarray:
+    """``mix64`` of csrc/gatres_common.h on uint64 arrays (numpy's unsigned array arithmetic is modulo 2^64)."""
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _check_seed(seed) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"the noise seed must be an integer in [0, 2**64); got {seed!r}")
+    return int(seed)
+
+
+def _noise_bits(seed, members: int, rows: int, num_sensors: int, member0: int = 0) -> np.ndarray:
+    """``h`` of the generator (include/gatres.h, gatres_stage_observed_noisy) as uint64 ``[rows, members, K]``."""
+    seed = _check_seed(seed)
+    members, rows, K, member0 = int(members), int(rows), int(num_sensors), int(member0)
+    if members < 1 or rows < 1 or K < 1 or member0 < 0:
+        raise ValueError("reading_noise needs members, rows, num_sensors >= 1 and member0 >= 0")
+    member = np.arange(member0, member0 + members, dtype=np.uint64)
+    stream = _mix64(np.uint64(seed) + np.uint64(0x9E3779B97F4A7C15) * (member + np.uint64(1)))
+    cell = np.arange(1, rows * K + 1, dtype=np.uint64).reshape(rows, 1, K)          # row * K + k + 1
+    return _mix64(stream.reshape(1, members, 1) + np.uint64(0xBF58476D1CE4E5B9) * cell)
+
+
+def reading_noise(seed, members: int, rows: int, num_sensors: int, member0: int = 0) -> np.ndarray:
+    """The standard normal draws of ``gatres_stage_observed_noisy``, restated on the host: float64 ``[rows, members, K]``,
+    entry ``[r, m, k]`` the ``z`` of (``seed``, member ``member0 + m``, source row ``r``, sensor ``k``).  The integers are formed
+    in numpy ``uint64`` exactly as on the device; Box-Muller is evaluated in fp64 (the device evaluates it in fp32: the two
+    agree to a few 1e-6)."""
+    h = _noise_bits(seed, members, rows, num_sensors, member0)
+    u1 = ((h >> np.uint64(40)) + np.uint64(1)).astype(np.float64) * 2.0 ** -24
+    u2 = ((h >> np.uint64(8)) & np.uint64(0xFFFFFF)).astype(np.float64) * 2.0 ** -24
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def ensemble_chunk(num_snapshots: int, members: int, batch_size: int, row_bytes: int, max_scratch_bytes: int) -> int:
+    """Snapshots per chunk of the ensemble's scratch matrix (``row_bytes`` per pair).  The pass over the S * M pairs is cut into
+    batches of ``batch_size`` once, from pair 0; a chunk must hold whole snapshots AND whole batches, so it is a multiple of the
+    unit ``lcm(batch_size, M) / M`` snapshots: as many units as ``max_scratch_bytes`` holds, at least one, and the whole pass
+    when that is less.  The batch partition therefore does not depend on the budget."""
+    S, M, bs = int(num_snapshots), int(members), int(batch_size)
+    unit = bs // math.gcd(bs, M)                                    # lcm(bs, M) / M
+    units = max(1, int(max_scratch_bytes) // (unit * M * int(row_bytes)))
+    return min(S, units * unit)
+
+
+def noise_report_from_moments(table, observed_idx) -> Dict[str, np.ndarray]:
+    """The per-node spread report from a ``gatres_node_spread_moments`` table ``[N, NODE_SPREAD_RECORD]`` (include/gatres.h), in
+    fp64: ``spread`` = sqrt(sum std^2 / S), the root-mean-square standard deviation of the node's estimate over the snapshots,
+    ``max_std``, ``mean_std``, ``nonsensor_spread`` pooled over the nodes outside ``observed_idx`` (NaN when every node is a
+    sensor) and ``most_sensitive``, the node indices by descending ``spread`` (ties in node order)."""
+    T = np.asarray(table, dtype=np.float64).reshape(-1, NODE_SPREAD_RECORD)
+    S = T[:, 0]
+    sensor = np.zeros(T.shape[0], dtype=np.bool_)
+    sensor[np.asarray(list(observed_idx), dtype=np.int64)] = True
+    spread = np.sqrt(T[:, 1] / S)
+    pooled = np.float64(np.sqrt(T[~sensor, 1].sum() / S[~sensor].sum())) if (~sensor).any() else np.float64("nan")
+    return {"spread": spread, "max_std": T[:, 2].copy(), "mean_std": T[:, 3] / S, "nonsensor_spread": pooled,
+            "most_sensitive": np.argsort(-spread, kind="stable")}
 
 
 _RECIPROCAL: Dict[str, bool] = {}
@@ -180,6 +251,7 @@ class PressureEstimator:
         if norm_type == "znorm":
             self._normalise = _native.NORMALISE_RECIPROCAL if _divides_by_reciprocal(dev) else _native.NORMALISE_DIVIDE
         self._observed = torch.tensor(self.observed_idx, dtype=torch.int32).to(dev)
+        self._sigma_cache = {}                      # layout -> (bytes, device sigma[K]) of the last noise_std: uploaded when it changes
 
     @classmethod
     def for_store(cls, model, store, observed_idx, **kw) -> "PressureEstimator":
@@ -227,42 +299,128 @@ class PressureEstimator:
                 or tuple(available.shape) != (S, K) or available.device != self.device or not available.is_contiguous()):
             raise ValueError(f"available must be uint8 or bool, contiguous [{S}, {K}] on {self.device}")
 
-    def _run(self, src: torch.Tensor, layout: int, normalise: int, out: Optional[torch.Tensor],
-             available: Optional[torch.Tensor] = None, nan_is_missing: bool = False) -> torch.Tensor:
-        model, N, S = self.model, self.nodes_per_graph, int(src.shape[0])
-        if available is not None:
-            self._check_available(available, S)
-        with_gaps = available is not None or bool(nan_is_missing)
-        out = self._result(S, out)
-        model.eval()
-        flat = model.flat_parameters
+    def _sigma(self, noise_std, layout: int) -> torch.Tensor:
+        """``noise_std`` (physical units; one value or K of them) as the device ``sigma[K]`` of gatres_stage_observed_noisy: in
+        the units of the launch's source, that is divided by ``std + eps`` for the full rows of a z-normalised store."""
+        K = len(self.observed_idx)
+        try:
+            v = np.asarray(noise_std, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"noise_std must be a non-negative number or a sequence of {K} of them") from None
+        if v.ndim == 0:
+            v = np.full(K, float(v))
+        if v.shape != (K,):
+            raise ValueError(f"noise_std must be a non-negative number or a sequence of {K} of them, one per sensor; got shape "
+                             f"{tuple(v.shape)}")
+        if not np.isfinite(v).all() or (v < 0).any():
+            raise ValueError("noise_std must be finite and non-negative")
+        if layout == _native.OBSERVED_FULL_ROWS and self.norm_type == "znorm":
+            v = v / (self.std + self.eps)
+        v = v.astype(np.float32)
+        cached = self._sigma_cache.get(layout)
+        if cached is None or cached[0] != v.tobytes():
+            cached = self._sigma_cache[layout] = (v.tobytes(), torch.from_numpy(v).to(self.device))
+        return cached[1]
+
+    def _launches(self, src: torch.Tensor, layout: int, normalise: int, available, nan_is_missing: bool, noise):
+        """The three launches of one batch as a function ``batch(P, first, g, dst, dst_rows, dst_first)``: stage the ``g`` graphs
+        from ``first`` on (source rows -- or, with ``noise = (sigma, seed, members, member0)``, pairs) into the plan ``P``, run
+        the forward, write rows ``dst_first ...`` of ``dst``."""
+        N, K, lib = self.nodes_per_graph, len(self.observed_idx), _native.load()
+        S = int(src.shape[0])
+        flat = self.model.flat_parameters
         if flat.device != self.device:
             raise ValueError(f"the model moved to {flat.device}; the estimator was built on {self.device}")
-        lib = _native.load()
         factor = self.std + self.eps if self.norm_type == "znorm" else 1.0
+        stream = _native.current_stream(self.device)
+        with_gaps = available is not None or bool(nan_is_missing)
+        tail = (self._observed.data_ptr(), K, normalise, self.offset, factor)
+
+        def batch(P, first, g, dst, dst_rows, dst_first):
+            to = (P.x.data_ptr(), P.mask.data_ptr())
+            if noise is not None:
+                sigma, seed, members, member0 = noise
+                _native.check(lib.gatres_stage_observed_noisy(
+                    src.data_ptr(), layout, S, first, members, member0, N, g, *tail, *to, _native.ptr(available),
+                    int(bool(nan_is_missing)), sigma.data_ptr(), seed, stream), "gatres_stage_observed_noisy")
+            elif with_gaps:
+                _native.check(lib.gatres_stage_observed_available(
+                    src.data_ptr(), layout, S, None, first, N, g, *tail, *to, _native.ptr(available),
+                    int(bool(nan_is_missing)), stream), "gatres_stage_observed_available")
+            else:
+                _native.check(lib.gatres_stage_observed(src.data_ptr(), layout, S, None, first, N, g, *tail, *to, stream),
+                              "gatres_stage_observed")
+            _enqueue_forward(lib, flat, P, stream)
+            _native.check(lib.gatres_estimate_write(
+                P.out.data_ptr(), P.x.data_ptr(), P.mask.data_ptr(), N, g, self.scale, self.offset, int(self.keep_observed),
+                dst.data_ptr(), dst_rows, N, dst_first, stream), "gatres_estimate_write")
+
+        return batch
+
+    def _noise(self, noise_std, noise_seed, noise_member, layout: int):
+        if noise_std is None:
+            return None
+        if isinstance(noise_member, bool) or not isinstance(noise_member, (int, np.integer)) or not 0 <= int(noise_member) < 1 << 62:
+            raise ValueError(f"noise_member must be a non-negative integer; got {noise_member!r}")
+        return self._sigma(noise_std, layout), _check_seed(noise_seed), 1, int(noise_member)
+
+    def _run(self, src: torch.Tensor, layout: int, normalise: int, out: Optional[torch.Tensor],
+             available: Optional[torch.Tensor] = None, nan_is_missing: bool = False, noise=None) -> torch.Tensor:
+        model, S = self.model, int(src.shape[0])
+        if available is not None:
+            self._check_available(available, S)
+        out = self._result(S, out)
+        model.eval()
         with torch.cuda.device(self.device):
-            stream = _native.current_stream(self.device)
+            batch = self._launches(src, layout, normalise, available, nan_is_missing, noise)
             sizes = [min(self.batch_size, S - first) for first in range(0, S, self.batch_size)]
             plans = {g: _eval_plan(model, self._topo, g) for g in sorted(set(sizes))}
             for b, g in enumerate(sizes):
-                P, first = plans[g], b * self.batch_size
-                if with_gaps:
-                    _native.check(lib.gatres_stage_observed_available(
-                        src.data_ptr(), layout, S, None, first, N, g, self._observed.data_ptr(), len(self.observed_idx),
-                        normalise, self.offset, factor, P.x.data_ptr(), P.mask.data_ptr(), _native.ptr(available),
-                        int(bool(nan_is_missing)), stream), "gatres_stage_observed_available")
-                else:
-                    _native.check(lib.gatres_stage_observed(
-                        src.data_ptr(), layout, S, None, first, N, g, self._observed.data_ptr(), len(self.observed_idx),
-                        normalise, self.offset, factor, P.x.data_ptr(), P.mask.data_ptr(), stream), "gatres_stage_observed")
-                _enqueue_forward(lib, flat, P, stream)
-                _native.check(lib.gatres_estimate_write(
-                    P.out.data_ptr(), P.x.data_ptr(), P.mask.data_ptr(), N, g, self.scale, self.offset, int(self.keep_observed),
-                    out.data_ptr(), S, N, first, stream), "gatres_estimate_write")
+                batch(plans[g], b * self.batch_size, g, out, S, b * self.batch_size)
         return out
 
+    def _run_ensemble(self, src: torch.Tensor, layout: int, normalise: int, noise_std, members, seed, available,
+                      nan_is_missing: bool, mean_out, std_out, max_scratch_bytes) -> Tuple[torch.Tensor, torch.Tensor]:
+        N, S, bs = self.nodes_per_graph, int(src.shape[0]), self.batch_size
+        if isinstance(members, bool) or not isinstance(members, (int, np.integer)) or int(members) < 1:
+            raise ValueError(f"members must be a positive integer; got {members!r}")
+        M = int(members)
+        if int(max_scratch_bytes) <= 0:
+            raise ValueError("max_scratch_bytes must be positive")
+        if available is not None:
+            self._check_available(available, S)
+        noise = (self._sigma(noise_std, layout), _check_seed(seed), M, 0)
+        mean, std = self._result(S, mean_out), self._result(S, std_out)
+        if mean_out is not None and mean_out is std_out:
+            raise ValueError("mean_out and std_out must be different tensors")
+        C = ensemble_chunk(S, M, bs, 4 * N, max_scratch_bytes)
+        model, lib = self.model, _native.load()
+        model.eval()
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream(self.device)
+            batch = self._launches(src, layout, normalise, available, nan_is_missing, noise)
+            scratch = torch.empty((C * M, N), dtype=torch.float32, device=self.device)
+            sizes = {min(bs, S * M - first) for first in (0, (S * M - 1) // bs * bs)}
+            plans = {g: _eval_plan(model, self._topo, g) for g in sorted(sizes)}
+            for s0 in range(0, S, C):                               # (s0 * M is a multiple of bs: a chunk starts a batch)
+                c = min(C, S - s0)
+                for off in range(0, c * M, bs):
+                    g = min(bs, c * M - off)
+                    batch(plans[g], s0 * M + off, g, scratch, C * M, off)
+                _native.check(lib.gatres_ensemble_reduce(scratch.data_ptr(), c, M, N, N, mean.data_ptr(), std.data_ptr(), S, N,
+                                                         s0, stream), "gatres_ensemble_reduce")
+        return mean, std
+
+    def _check_readings(self, readings) -> None:
+        K = len(self.observed_idx)
+        if (not isinstance(readings, torch.Tensor) or readings.dtype != torch.float32 or readings.dim() != 2
+                or readings.shape[1] != K or readings.shape[0] == 0 or readings.device != self.device
+                or not readings.is_contiguous()):
+            raise ValueError(f"readings must be fp32 contiguous [S, {K}] on {self.device}")
+
     def estimate(self, readings: torch.Tensor, out: Optional[torch.Tensor] = None, *,
-                 available: Optional[torch.Tensor] = None, nan_is_missing: bool = False) -> torch.Tensor:
+                 available: Optional[torch.Tensor] = None, nan_is_missing: bool = False, noise_std=None, noise_seed: int = 0,
+                 noise_member: int = 0) -> torch.Tensor:
         """``readings``: fp32 contiguous ``[S, K]`` on the model's device, in physical units, column ``k`` the sensor at
         ``observed_idx[k]``.  Returns the pressures ``[S, N_g]`` in physical units (``out``: write them there), a device tensor
         ordered on the current stream.
@@ -270,20 +428,73 @@ class PressureEstimator:
         ``available``: uint8 or bool contiguous ``[S, K]`` on the same device, non-zero where the reading is present;
         ``nan_is_missing``: a NaN reading is missing (decided on the device: nothing is scanned on the host).  A missing reading
         is not used: its node is hidden in that snapshot and, with ``keep_observed``, carries the model's prediction.  A
-        snapshot without any reading is legal (the model's output on an all-zero input)."""
-        K = len(self.observed_idx)
-        if (not isinstance(readings, torch.Tensor) or readings.dtype != torch.float32 or readings.dim() != 2
-                or readings.shape[1] != K or readings.shape[0] == 0 or readings.device != self.device
-                or not readings.is_contiguous()):
-            raise ValueError(f"readings must be fp32 contiguous [S, {K}] on {self.device}")
-        return self._run(readings, _native.OBSERVED_READINGS, self._normalise, out, available, nan_is_missing)
+        snapshot without any reading is legal (the model's output on an all-zero input).
+
+        ``noise_std`` (``None``: exactly the launches above): one noisy realisation of the readings.  A non-negative float, or
+        a sequence of K of them, in physical units: every present reading ``r`` of sensor ``k`` in snapshot ``s`` is taken as
+        ``r + float32(noise_std[k]) * z`` with ``z = reading_noise(noise_seed, 1, S, K, member0=noise_member)[s, 0, k]``, drawn
+        in the staging launch (``gatres_stage_observed_noisy``); a missing reading draws nothing.  With ``keep_observed`` the
+        sensor nodes of the result carry the NOISY reading after the normalise / descale round trip, not the one passed in."""
+        self._check_readings(readings)
+        noise = self._noise(noise_std, noise_seed, noise_member, _native.OBSERVED_READINGS)
+        return self._run(readings, _native.OBSERVED_READINGS, self._normalise, out, available, nan_is_missing, noise)
 
     def estimate_store(self, store, out: Optional[torch.Tensor] = None, *,
-                       available: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       available: Optional[torch.Tensor] = None, noise_std=None, noise_seed: int = 0,
+                       noise_member: int = 0) -> torch.Tensor:
         """The same for every snapshot of a ``SnapshotStore``, in store order, with everything but the sensors hidden --
-        and, with ``available`` (``[len(store), K]``), the sensors without a reading too."""
+        and, with ``available`` (``[len(store), K]``), the sensors without a reading too.  ``noise_std`` (physical units, as in
+        ``estimate``): the store's normalised sensor entries get ``float32(noise_std[k] / (std + eps)) * z`` (``float32(noise_std[k])
+        * z`` for an ``unused`` store); with ``keep_observed`` the sensor nodes carry the noisy value."""
         self._check_store(store)
-        return self._run(store.data, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, out, available)
+        noise = self._noise(noise_std, noise_seed, noise_member, _native.OBSERVED_FULL_ROWS)
+        return self._run(store.data, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, out, available, False, noise)
+
+    def estimate_ensemble(self, readings: torch.Tensor, noise_std, members: int, *, seed: int = 0,
+                          available: Optional[torch.Tensor] = None, nan_is_missing: bool = False,
+                          mean_out: Optional[torch.Tensor] = None, std_out: Optional[torch.Tensor] = None,
+                          max_scratch_bytes: int = 64 << 20) -> Tuple[torch.Tensor, torch.Tensor]:
+        """A Monte-Carlo ensemble under measurement noise: for every snapshot of ``readings`` (as in ``estimate``) the mean and
+        the sample standard deviation (``M - 1`` in the denominator; 0 for one member), per junction, of the estimates from
+        ``members`` noisy realisations -- member ``m`` is ``estimate(readings, noise_std=noise_std, noise_seed=seed,
+        noise_member=m)`` up to the batch it is computed in.  Returns ``(mean, std)``, fp32 ``[S, N_g]`` device tensors in
+        physical units ordered on the current stream (``mean_out`` / ``std_out``: write them there).
+
+        The S * M (snapshot, member) pairs, snapshot-major, are one long pass cut into batches of ``batch_size`` -- one
+        snapshot's 32 members at batch size 32 are ONE forward launch -- with the three launches of ``estimate`` per batch.  The
+        members' estimates go to a scratch matrix of at most ``max_scratch_bytes`` (``ensemble_chunk``: whole snapshots and whole
+        batches, at least one such unit), one ``gatres_ensemble_reduce`` launch per chunk folds them in fp64 in member order.
+        The bits of the result depend on neither the budget nor the run.  Nothing is read back, nothing synchronises."""
+        self._check_readings(readings)
+        return self._run_ensemble(readings, _native.OBSERVED_READINGS, self._normalise, noise_std, members, seed, available,
+                                  nan_is_missing, mean_out, std_out, max_scratch_bytes)
+
+    def estimate_store_ensemble(self, store, noise_std, members: int, *, seed: int = 0,
+                                available: Optional[torch.Tensor] = None, mean_out: Optional[torch.Tensor] = None,
+                                std_out: Optional[torch.Tensor] = None,
+                                max_scratch_bytes: int = 64 << 20) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``estimate_ensemble`` over the snapshots of a ``SnapshotStore`` (noise in physical units, scaled as in
+        ``estimate_store``)."""
+        self._check_store(store)
+        return self._run_ensemble(store.data, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, noise_std, members, seed,
+                                  available, False, mean_out, std_out, max_scratch_bytes)
+
+    def noise_report(self, store, noise_std, members: int, *, seed: int = 0,
+                     available: Optional[torch.Tensor] = None) -> Dict[str, object]:
+        """Which junctions are sensitive to sensor error: ``estimate_store_ensemble(store, noise_std, members, seed=seed,
+        available=available)``, then ``error`` = ``error_map(store, estimates=mean, available=available)`` of the ensemble mean
+        and, from one ``gatres_node_spread_moments`` launch over the standard deviations, the entries of
+        ``noise_report_from_moments``: ``spread``, ``max_std``, ``mean_std`` per node, ``nonsensor_spread`` and
+        ``most_sensitive``.  Two read-backs: the error table and the spread table."""
+        mean, std = self.estimate_store_ensemble(store, noise_std, members, seed=seed, available=available)
+        out: Dict[str, object] = {"error": self.error_map(store, estimates=mean, available=available)}
+        table = torch.empty((self.nodes_per_graph, NODE_SPREAD_RECORD), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().gatres_node_spread_moments(
+                std.data_ptr(), len(store), self.nodes_per_graph, table.data_ptr(), _native.current_stream(self.device)),
+                "gatres_node_spread_moments")
+        out.update(noise_report_from_moments(table.cpu().numpy(), self.observed_idx))
+        return out
 
     def error_map(self, store, estimates: Optional[torch.Tensor] = None, *,
                   available: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:

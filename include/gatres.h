@@ -883,6 +883,56 @@ int gatres_node_error_moments_available(const float* est, const float* truth, in
                                         double scale, double offset, const int32_t* observed, int32_t num_observed,
                                         const uint8_t* available, double* table, void* stream);
 
+/* Estimates and their spread under sensor noise (symbols only: the ABI stays).  A Monte-Carlo ensemble of `members` noisy
+ * realisations per snapshot is one long pass over (snapshot, member) PAIRS, snapshot-major: pair p is source row p / members
+ * and member p % members.
+ *
+ * gatres_stage_observed_noisy: the kernel of gatres_stage_observed_available compiled with the noise as one more compile-time
+ * fact.  The arguments, the layouts and the checks of gatres_stage_observed_available, without rows, and
+ *   first_pair   graph g of the launch is pair p = first_pair + g: it reads source row p / members (of src and of available)
+ *                and is member member0 + p % members.  0 <= first_pair, first_pair + num_graphs <= src_rows * members.
+ *   members      >= 1;  member0 >= 0 (a single realisation: members = 1, member0 = its member)
+ *   sigma        device float[num_observed], >= 0, in the units of src (layout GATRES_OBSERVED_FULL_ROWS: normalised units)
+ *   seed         any 64-bit value
+ *   available    may be NULL with nan_is_missing == 0 here: every reading is present.
+ * At a PRESENT sensor k with the raw value r (src[row * K + k] in the readings layout, src[row * N + observed[k]] in full rows):
+ *   x_dst = normalise(fp32(r + fp32(sigma[k] * z)))   (normalise: as gatres_stage_observed, the identity for full rows)
+ * A missing reading draws nothing and is staged as gatres_stage_observed_available stages it.  z is a pure function of
+ * (seed, member, source row, k) -- not of the batch, the graph's position in it, the availability or the launch geometry --
+ * with mix64(z) = { z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31; } and
+ * all integer arithmetic modulo 2^64:
+ *   stream = mix64(seed + 0x9E3779B97F4A7C15 * (member + 1))
+ *   h      = mix64(stream + 0xBF58476D1CE4E5B9 * (row * K + k + 1))
+ *   u1     = ((h >> 40) + 1) * 2^-24   in (0, 1],   u2 = ((h >> 8) & 0xFFFFFF) * 2^-24   in [0, 1)   (both exact in fp32)
+ *   z      = sqrtf(-2 * logf(u1)) * cosf(6.283185307179586f * u2)      (|z| <= sqrt(48 ln 2) = 5.77)
+ * estimation.reading_noise restates it on the host.  GATRES_E_BADARG before any launch: whatever
+ * gatres_stage_observed_available refuses (but for the NULL available), a pair range outside [0, src_rows * members),
+ * members < 1, member0 < 0, sigma == NULL or overlapping x_dst or mask. */
+int gatres_stage_observed_noisy(const float* src, int32_t layout, int64_t src_rows, int64_t first_pair, int32_t members,
+                                int64_t member0, int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed,
+                                int32_t num_observed, int32_t normalise, double offset, double factor, float* x_dst, uint8_t* mask,
+                                const uint8_t* available, int32_t nan_is_missing, const float* sigma, uint64_t seed, void* stream);
+
+/* Mean and sample standard deviation over the members of each snapshot.  members_mat[num_snapshots * members][stride] is what
+ * gatres_estimate_write produced with the pair index as the row; mean and std_dev are [out_rows][out_stride] and get the rows
+ * first_row + s, columns [0, nodes_per_graph); nothing else is written.  Per (s, v), in fp64, in member order m = 0 .. M - 1,
+ * without contraction and without atomics (the same bits on every run, whatever the launch geometry):
+ *   mean64 = (sum_m (double)x_m) / M        var = (sum_m (x_m - mean64)^2) / (M - 1)
+ *   mean   = (float)mean64                  std_dev = (float)sqrt(var), 0 for M == 1
+ * One launch; the lanes of a wave take consecutive v, in 16-byte accesses where nodes_per_graph, both strides and the three
+ * pointers allow it.  GATRES_E_BADARG before any launch: members < 1, a stride below nodes_per_graph, rows outside
+ * [0, out_rows), and source, mean rows and std_dev rows that overlap one another. */
+int gatres_ensemble_reduce(const float* members_mat, int64_t num_snapshots, int32_t members, int32_t nodes_per_graph,
+                           int64_t stride, float* mean, float* std_dev, int64_t out_rows, int64_t out_stride, int64_t first_row,
+                           void* stream);
+
+/* Per-node moments of a matrix of standard deviations std_dev[S][N] (gatres_ensemble_reduce's, contiguous):
+ * table[N][GATRES_NODE_SPREAD_RECORD] (device double), per node v over the snapshots s = 0 .. S - 1:
+ *   [0] S   [1] sum (double)sd * (double)sd   [2] max sd   [3] sum (double)sd
+ * The geometry and the fixed summation order of gatres_node_error_moments (chunks of GATRES_NODE_ERROR_CHUNK rows). */
+#define GATRES_NODE_SPREAD_RECORD 4
+int gatres_node_spread_moments(const float* std_dev, int64_t num_snapshots, int32_t nodes_per_graph, double* table, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
