@@ -166,6 +166,10 @@ SIGNATURES = {
                                               _I32, _P, _U64, _P]),
     "gatres_ensemble_reduce": (C.c_int, [_P, _I64, _I32, _I32, _I64, _P, _P, _I64, _I64, _I64, _P]),
     "gatres_node_spread_moments": (C.c_int, [_P, _I64, _I32, _P, _P]),
+    "gatres_stage_observed_layouts": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _I32, _I32, _F64, _F64, _P, _P, _P,
+                                                _I32, _P, _P]),
+    "gatres_layout_pair_errors": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I64, _I32, _F64, _F64, _P, _P, _I64, _I64, _P]),
+    "gatres_layout_error_reduce": (C.c_int, [_P, _I64, _I32, _P, _I32, _P]),
     "gatres_version": (C.c_char_p, []),
 }
 
@@ -178,6 +182,8 @@ NORMALISE_NONE, NORMALISE_DIVIDE, NORMALISE_RECIPROCAL = 0, 1, 2      # GATRES_N
 NODE_ERROR_RECORD, NODE_ERROR_CHUNK = 8, 64         # GATRES_NODE_ERROR_RECORD, GATRES_NODE_ERROR_CHUNK
 NODE_ERROR_AVAIL_RECORD = 8                         # GATRES_NODE_ERROR_AVAIL_RECORD (gatres_node_error_moments_available)
 NODE_SPREAD_RECORD = 4                              # GATRES_NODE_SPREAD_RECORD (gatres_node_spread_moments)
+LAYOUT_PAIR_RECORD = 4                              # GATRES_LAYOUT_PAIR_RECORD (gatres_layout_pair_errors)
+LAYOUT_ERROR_RECORD = 4                             # GATRES_LAYOUT_ERROR_RECORD (gatres_layout_error_reduce)
 CRITERIA = {"mse": LOSS_MSE, "mae": LOSS_MAE, "sce": LOSS_SCE}      # the reference's train.py --criterion choices
 
 

@@ -13,6 +13,11 @@
 //                                 reading gets sigma[k] * z, z drawn in the launch from (seed, member, source row, k);
 //   gatres_ensemble_reduce        mean and sample standard deviation over the members of each snapshot, one element pass;
 //   gatres_node_spread_moments    per-node moments of a [S][N] matrix of standard deviations: the traversal of the error moments.
+// Sensor placement (layout_errors, place_sensors): one long pass over (snapshot, layout) pairs, as the ensemble's over members:
+//   gatres_stage_observed_layouts the staging kernel with LAYOUTS = true: graph g is one (snapshot, layout) pair and a sensor
+//                                 counts only where the pair's layout installs it;
+//   gatres_layout_pair_errors     one batch's error against the truth, one fp64 record per graph, from the forward's buffers;
+//   gatres_layout_error_reduce    the pairs' records folded into one record per layout, in snapshot order.
 #include "gatres_common.h"
 
 namespace {
@@ -53,6 +58,14 @@ struct ObsNoise {
   long long member0;
   int members;
 };
+// LAYOUTS (gatres_stage_observed_layouts; always with AVAIL, never with NOISE): graph g is pair p = first_row + g of a
+// snapshot-major list of (source row, layout) pairs -- source row p / count, layout p % count -- and sensor k is read only where
+// on[(p % count) * K + k] != 0; a sensor the layout leaves out is staged as a missing reading.  As with NOISE the 64-bit division
+// is left to the lanes that hold a sensor.
+struct ObsLayouts {
+  const uint8_t* on;       // [count][K]
+  int count;
+};
 
 // One standard normal by Box-Muller from the 48 upper bits of one hash (gatres.h states the generator): u1 in (0, 1] and u2 in
 // [0, 1) are 24-bit integers times 2^-24, both exact in fp32.
@@ -66,15 +79,16 @@ __device__ __forceinline__ float obs_noise(uint64_t stream, long long row, int K
   return __fmul_rn(sqrtf(__fmul_rn(-2.f, logf(u1))), cosf(__fmul_rn(6.283185307179586f, u2)));
 }
 
-template <bool AVAIL, bool NOISE>
+template <bool AVAIL, bool NOISE, bool LAYOUTS>
 __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __restrict__ src, int readings, long long src_rows,
                                                                const long long* __restrict__ rows, long long first_row, int N,
                                                                int G, const int* __restrict__ observed, int K, int mode,
                                                                float offset, float scale, float* __restrict__ x_dst,
                                                                uint8_t* __restrict__ mask, int vec,
                                                                const uint8_t* __restrict__ available, int nan_missing,
-                                                               ObsNoise nz) {
-  static_assert(AVAIL || !NOISE, "the noisy launch carries the availability arguments");
+                                                               ObsNoise nz, ObsLayouts lay) {
+  static_assert(AVAIL || !(NOISE || LAYOUTS), "the noisy and the layouts launch carry the availability arguments");
+  static_assert(!(NOISE && LAYOUTS), "noise combined with layouts is not built");
   __shared__ int slot[OBS_TILE];
   const int tid = threadIdx.x;
   const int j = blockIdx.x * OBS_T + tid;
@@ -93,18 +107,20 @@ __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __re
     if (v0 >= N || v0 + 4 <= 0) continue;
     // (NOISE: the pair's row lies inside the matrix, the host checked the pair range; the 64-bit division is left to the lanes
     //  that hold a sensor)
-    long long row = NOISE ? 0 : (rows ? rows[g] : first_row + g);
-    const bool row_ok = NOISE || (row >= 0 && row < src_rows);          // (a row outside the matrix is not read: its nodes get 0)
+    long long row = (NOISE || LAYOUTS) ? 0 : (rows ? rows[g] : first_row + g);
+    const bool row_ok = NOISE || LAYOUTS || (row >= 0 && row < src_rows);   // (a row outside the matrix is not read: its nodes get 0)
     uint64_t noise_stream = 0;
     unsigned draw = 0;                                                  // NOISE: the elements that hold a present reading
-    if (NOISE) {
+    const uint8_t* installed = nullptr;                                 // LAYOUTS: the pair's row of lay.on
+    if (NOISE || LAYOUTS) {
       bool any = false;
 #pragma unroll
       for (int e = 0; e < 4; ++e) any |= v0 + e >= 0 && v0 + e < N && slot[v0 + e - tile_lo] != 0;
       if (any) {
         const long long pair = first_row + g;
-        row = pair / nz.members;
-        noise_stream = obs_noise_stream(nz.seed, (uint64_t)(nz.member0 + (pair - row * nz.members)));
+        row = pair / (NOISE ? nz.members : lay.count);
+        if (NOISE) noise_stream = obs_noise_stream(nz.seed, (uint64_t)(nz.member0 + (pair - row * nz.members)));
+        else installed = lay.on + (pair - row * lay.count) * K;
       }
     }
     float val[4];
@@ -117,7 +133,8 @@ __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __re
       val[e] = 0.f;
       if (s && row_ok) {
         bool have = true;
-        if (AVAIL && available) have = available[row * K + (s - 1)] != 0;
+        if (LAYOUTS) have = installed[s - 1] != 0;
+        if (AVAIL && have && available) have = available[row * K + (s - 1)] != 0;
         if (have) {
           const float r = readings ? src[row * K + (s - 1)] : src[row * N + v];
           if (AVAIL && nan_missing && readings && obs_is_nan(r)) have = false;
@@ -408,18 +425,144 @@ __global__ __launch_bounds__(ER_T) void ensemble_reduce_kernel(const float* __re
   }
 }
 
+// ---- layout errors -------------------------------------------------------------------------------------------------------------
+constexpr int PE_WAVES = 4;                    // graphs per workgroup: one wave each
+constexpr int PE_T = PE_WAVES * GATRES_WAVE;
+
+// The sum of a over the lanes of a wave by a butterfly (xor 32, 16, ... 1): every lane ends with the same bits, and the
+// association is fixed.
+__device__ __forceinline__ double pe_wave_sum(double a) {
+#pragma unroll
+  for (int off = GATRES_WAVE / 2; off > 0; off >>= 1) a += __shfl_xor(a, off, GATRES_WAVE);
+  return a;
+}
+
+// Wave w of workgroup b takes graph g = b * PE_WAVES + w: pair p = first_pair + g, truth row s = p / L.  Lane l takes the chunks
+// l, l + 64, ... of four consecutive nodes [4 j, 4 j + 4) of the graph, in ascending order, and adds the terms of a chunk's
+// counted nodes in node order; the lanes' partials go through the butterfly above.  The association depends on N alone: not on
+// g, on the alignment or on which loads were taken.  A whole chunk is one 16-byte load of out, one 32-bit load of mask and of
+// score and one 16-byte load of truth where g * N, resp. s * N, is a multiple of four and the pointer is aligned (out_vec,
+// mask_vec, score_vec, truth_vec: facts of the pointers, the rest is uniform over the wave); element loads otherwise.
+__global__ __launch_bounds__(PE_T) void layout_pair_errors_kernel(const float* __restrict__ out, const uint8_t* __restrict__ mask,
+                                                                  const float* __restrict__ truth, int N, int G,
+                                                                  long long first_pair, int L, float scale, float offset,
+                                                                  const uint8_t* __restrict__ score, double* __restrict__ rec,
+                                                                  int out_vec, int mask_vec, int truth_vec, int score_vec) {
+  const int lane = threadIdx.x % GATRES_WAVE, wave = threadIdx.x / GATRES_WAVE;
+  const int g = blockIdx.x * PE_WAVES + wave;
+  if (g >= G) return;                                       // (no barrier below: a wave works alone)
+  const long long s = (first_pair + g) / L;
+  const long long base = (long long)g * N, tbase = s * N;
+  const bool ov = out_vec && (base & 3) == 0, mv = mask_vec && (base & 3) == 0, tv = truth_vec && (tbase & 3) == 0;
+  double sum_abs = 0.0, sum_sq = 0.0;
+  float amax = 0.f;
+  int count = 0;
+  for (int v0 = 4 * lane; v0 < N; v0 += 4 * GATRES_WAVE) {
+    const bool whole = v0 + 4 <= N;
+    float o[4], t[4];
+    uint8_t mk[4], sc[4] = {1, 1, 1, 1};
+    if (whole && ov) {
+      const float4 a = ld4(out + base + v0);
+      o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = v0 + e < N ? out[base + v0 + e] : 0.f;
+    }
+    if (whole && tv) {
+      const float4 a = ld4(truth + tbase + v0);
+      t[0] = a.x; t[1] = a.y; t[2] = a.z; t[3] = a.w;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) t[e] = v0 + e < N ? truth[tbase + v0 + e] : 0.f;
+    }
+    if (whole && mv) {
+      const uint32_t m = *reinterpret_cast<const uint32_t*>(mask + base + v0);
+      mk[0] = m & 0xff; mk[1] = (m >> 8) & 0xff; mk[2] = (m >> 16) & 0xff; mk[3] = m >> 24;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) mk[e] = v0 + e < N ? mask[base + v0 + e] : 0;
+    }
+    if (score) {
+      if (whole && score_vec) {
+        const uint32_t m = *reinterpret_cast<const uint32_t*>(score + v0);
+        sc[0] = m & 0xff; sc[1] = (m >> 8) & 0xff; sc[2] = (m >> 16) & 0xff; sc[3] = m >> 24;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sc[e] = v0 + e < N ? score[v0 + e] : 0;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {                           // (in node order; a node past N has mk = 0)
+      if (!mk[e] || !sc[e]) continue;
+      const float err = __fsub_rn(gatres_descale(o[e], scale, offset), gatres_descale(t[e], scale, offset));
+      const float ae = fabsf(err);
+      ++count;
+      sum_abs += (double)ae;
+      sum_sq += (double)err * (double)err;
+      amax = fmaxf(amax, ae);
+    }
+  }
+  const double r_abs = pe_wave_sum(sum_abs), r_sq = pe_wave_sum(sum_sq);
+#pragma unroll
+  for (int off = GATRES_WAVE / 2; off > 0; off >>= 1) {
+    count += __shfl_xor(count, off, GATRES_WAVE);
+    amax = fmaxf(amax, __shfl_xor(amax, off, GATRES_WAVE));
+  }
+  if (lane == 0) {
+    double* r = rec + (size_t)g * GATRES_LAYOUT_PAIR_RECORD;
+    r[0] = (double)count; r[1] = r_abs; r[2] = r_sq; r[3] = (double)amax;
+  }
+}
+
+// ---- layout error reduce -------------------------------------------------------------------------------------------------------
+constexpr int LR_T = 64;
+
+// Lane l is layout l: it folds the records rec[s * L + l], s = 0 .. S - 1, strictly in that order (so the table's bits do not
+// depend on how a pass was cut into launches), starting from the table's record when `accumulate`.  The lanes of a wave read
+// consecutive records; LR_U of a lane's records are in flight per trip.
+constexpr int LR_U = 8;
+__global__ __launch_bounds__(LR_T) void layout_error_reduce_kernel(const double* __restrict__ rec, long long S, int L,
+                                                                   double* __restrict__ table, int accumulate) {
+  const int l = blockIdx.x * LR_T + threadIdx.x;
+  if (l >= L) return;
+  double* t = table + (size_t)l * GATRES_LAYOUT_ERROR_RECORD;
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  if (accumulate) {
+#pragma unroll
+    for (int f = 0; f < 4; ++f) a[f] = t[f];
+  }
+  for (long long s0 = 0; s0 < S; s0 += LR_U) {
+    double r[LR_U][4];
+#pragma unroll
+    for (int u = 0; u < LR_U; ++u) {
+      const long long s = s0 + u < S ? s0 + u : S - 1;      // (a row past the end reads the last one, which the loop below skips)
+      const double* p = rec + ((size_t)s * L + l) * GATRES_LAYOUT_PAIR_RECORD;
+#pragma unroll
+      for (int f = 0; f < 4; ++f) r[u][f] = p[f];
+    }
+#pragma unroll
+    for (int u = 0; u < LR_U; ++u) {                        // (in snapshot order: the same association as a plain loop)
+      if (s0 + u >= S) continue;
+      a[0] += r[u][0]; a[1] += r[u][1]; a[2] += r[u][2];
+      a[3] = fmax(a[3], r[u][3]);
+    }
+  }
+#pragma unroll
+  for (int f = 0; f < 4; ++f) t[f] = a[f];
+}
+
 static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
   return a0 < b0 + nb && b0 < a0 + na;
 }
 
-// The checks and the launch of the staging entry points (AVAIL: with the availability arguments; NOISE: first_row is the first
-// pair, rows is NULL and nz holds the noise arguments).
-template <bool AVAIL, bool NOISE = false>
+// The checks and the launch of the staging entry points (AVAIL: with the availability arguments; NOISE / LAYOUTS: first_row is
+// the first pair, rows is NULL and nz / lay holds the noise / layout arguments).
+template <bool AVAIL, bool NOISE = false, bool LAYOUTS = false>
 int stage_observed(const float* src, int32_t layout, int64_t src_rows, const int64_t* rows, int64_t first_row,
                    int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed, int32_t num_observed, int32_t normalise,
                    double offset, double factor, float* x_dst, uint8_t* mask, const uint8_t* available, int32_t nan_is_missing,
-                   void* stream, ObsNoise nz = ObsNoise{nullptr, 0, 0, 1}) {
+                   void* stream, ObsNoise nz = ObsNoise{nullptr, 0, 0, 1}, ObsLayouts lay = ObsLayouts{nullptr, 1}) {
   if (!src || !observed || !x_dst || !mask || src == x_dst) return GATRES_E_BADARG;
   if (nodes_per_graph <= 0 || num_graphs <= 0 || num_observed <= 0 || num_observed > nodes_per_graph) return GATRES_E_BADARG;
   if ((int64_t)nodes_per_graph * num_graphs > INT32_MAX) return GATRES_E_BADARG;
@@ -432,10 +575,17 @@ int stage_observed(const float* src, int32_t layout, int64_t src_rows, const int
     const uint64_t total = (uint64_t)nodes_per_graph * (uint64_t)num_graphs;
     if (bytes_overlap(nz.sigma, 4 * (uint64_t)num_observed, x_dst, 4 * total) ||
         bytes_overlap(nz.sigma, 4 * (uint64_t)num_observed, mask, total)) return GATRES_E_BADARG;
+  } else if (LAYOUTS) {
+    // (pairs [first_row, first_row + num_graphs) of the src_rows * count there are)
+    if (!lay.on || lay.count < 1 || src_rows <= 0 || src_rows > INT64_MAX / lay.count) return GATRES_E_BADARG;
+    if (first_row < 0 || first_row > src_rows * lay.count - num_graphs) return GATRES_E_BADARG;
+    const uint64_t total = (uint64_t)nodes_per_graph * (uint64_t)num_graphs;
+    const uint64_t lay_bytes = (uint64_t)lay.count * (uint64_t)num_observed;
+    if (bytes_overlap(lay.on, lay_bytes, x_dst, 4 * total) || bytes_overlap(lay.on, lay_bytes, mask, total)) return GATRES_E_BADARG;
   } else if (src_rows <= 0 || (!rows && (first_row < 0 || first_row > src_rows - num_graphs))) return GATRES_E_BADARG;
   if (normalise < GATRES_NORMALISE_NONE || normalise > GATRES_NORMALISE_RECIPROCAL) return GATRES_E_BADARG;
   if (AVAIL) {
-    if (!NOISE && !available && !nan_is_missing) return GATRES_E_BADARG;
+    if (!NOISE && !LAYOUTS && !available && !nan_is_missing) return GATRES_E_BADARG;
     // (available[src_rows][num_observed] must not overlap the bytes this launch writes)
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(available), a1 = a0 + (uintptr_t)src_rows * (uintptr_t)num_observed;
     const uintptr_t total = (uintptr_t)nodes_per_graph * (uintptr_t)num_graphs;
@@ -450,10 +600,10 @@ int stage_observed(const float* src, int32_t layout, int64_t src_rows, const int
   const int vec = gatres_aligned16(x_dst) && (reinterpret_cast<uintptr_t>(mask) & 3u) == 0;
   const int chunks = (nodes_per_graph + 3) / 4 + 1;
   const dim3 grid((chunks + OBS_T - 1) / OBS_T, num_graphs < OBS_MAX_GY ? num_graphs : OBS_MAX_GY);
-  hipLaunchKernelGGL((stage_observed_kernel<AVAIL, NOISE>), grid, dim3(OBS_T), 0, gatres_stream(stream), src,
+  hipLaunchKernelGGL((stage_observed_kernel<AVAIL, NOISE, LAYOUTS>), grid, dim3(OBS_T), 0, gatres_stream(stream), src,
                      (int)(layout == GATRES_OBSERVED_READINGS), (long long)src_rows, reinterpret_cast<const long long*>(rows),
                      (long long)first_row, (int)nodes_per_graph, (int)num_graphs, observed, (int)num_observed, (int)normalise,
-                     (float)offset, scale, x_dst, mask, vec, available, (int)(nan_is_missing != 0), nz);
+                     (float)offset, scale, x_dst, mask, vec, available, (int)(nan_is_missing != 0), nz, lay);
   return gatres_launch_status();
 }
 
@@ -566,5 +716,47 @@ extern "C" int gatres_node_spread_moments(const float* std_dev, int64_t num_snap
   static_assert(GATRES_NODE_SPREAD_RECORD == 4, "record layout");
   hipLaunchKernelGGL(node_spread_moments_kernel, dim3((nodes_per_graph + GATRES_WAVE - 1) / GATRES_WAVE), dim3(NE_T), 0,
                      gatres_stream(stream), std_dev, (long long)num_snapshots, (int)nodes_per_graph, table);
+  return gatres_launch_status();
+}
+
+extern "C" int gatres_stage_observed_layouts(const float* src, int32_t layout, int64_t src_rows, int64_t first_pair,
+                                             int32_t num_layouts, int32_t nodes_per_graph, int32_t num_graphs,
+                                             const int32_t* observed, int32_t num_observed, int32_t normalise, double offset,
+                                             double factor, float* x_dst, uint8_t* mask, const uint8_t* available,
+                                             int32_t nan_is_missing, const uint8_t* layouts, void* stream) {
+  return stage_observed<true, false, true>(src, layout, src_rows, nullptr, first_pair, nodes_per_graph, num_graphs, observed,
+                                           num_observed, normalise, offset, factor, x_dst, mask, available, nan_is_missing, stream,
+                                           ObsNoise{nullptr, 0, 0, 1}, ObsLayouts{layouts, (int)num_layouts});
+}
+
+extern "C" int gatres_layout_pair_errors(const float* out, const uint8_t* mask, const float* truth, int64_t truth_rows,
+                                         int32_t nodes_per_graph, int32_t num_graphs, int64_t first_pair, int32_t num_layouts,
+                                         double scale, double offset, const uint8_t* score, double* rec, int64_t rec_rows,
+                                         int64_t rec_first, void* stream) {
+  if (!out || !mask || !truth || !rec || nodes_per_graph <= 0 || num_graphs <= 0 || num_layouts < 1) return GATRES_E_BADARG;
+  if ((int64_t)nodes_per_graph * num_graphs > INT32_MAX) return GATRES_E_BADARG;
+  if (truth_rows <= 0 || truth_rows > INT64_MAX / num_layouts || truth_rows > INT64_MAX / 4 / nodes_per_graph) return GATRES_E_BADARG;
+  if (first_pair < 0 || first_pair > truth_rows * num_layouts - num_graphs) return GATRES_E_BADARG;
+  static_assert(GATRES_LAYOUT_PAIR_RECORD == 4, "record layout");
+  if (rec_rows <= 0 || rec_rows > INT64_MAX / 32 || rec_first < 0 || rec_first > rec_rows - num_graphs) return GATRES_E_BADARG;
+  const uint64_t total = (uint64_t)nodes_per_graph * (uint64_t)num_graphs, rec_bytes = 32 * (uint64_t)rec_rows;
+  if (bytes_overlap(rec, rec_bytes, out, 4 * total) || bytes_overlap(rec, rec_bytes, mask, total) ||
+      bytes_overlap(rec, rec_bytes, truth, 4 * (uint64_t)truth_rows * (uint64_t)nodes_per_graph) ||
+      (score && bytes_overlap(rec, rec_bytes, score, (uint64_t)nodes_per_graph))) return GATRES_E_BADARG;
+  hipLaunchKernelGGL(layout_pair_errors_kernel, dim3((num_graphs + PE_WAVES - 1) / PE_WAVES), dim3(PE_T), 0, gatres_stream(stream),
+                     out, mask, truth, (int)nodes_per_graph, (int)num_graphs, (long long)first_pair, (int)num_layouts, (float)scale,
+                     (float)offset, score, rec + rec_first * GATRES_LAYOUT_PAIR_RECORD, (int)gatres_aligned16(out),
+                     (int)((reinterpret_cast<uintptr_t>(mask) & 3u) == 0), (int)gatres_aligned16(truth),
+                     (int)((reinterpret_cast<uintptr_t>(score) & 3u) == 0));
+  return gatres_launch_status();
+}
+
+extern "C" int gatres_layout_error_reduce(const double* rec, int64_t num_snapshots, int32_t num_layouts, double* table,
+                                          int32_t accumulate, void* stream) {
+  if (!rec || !table || num_snapshots <= 0 || num_layouts < 1 || num_snapshots > INT64_MAX / 32 / num_layouts) return GATRES_E_BADARG;
+  static_assert(GATRES_LAYOUT_ERROR_RECORD == 4 && GATRES_LAYOUT_PAIR_RECORD == 4, "record layout");
+  if (bytes_overlap(rec, 32 * (uint64_t)num_snapshots * (uint64_t)num_layouts, table, 32 * (uint64_t)num_layouts)) return GATRES_E_BADARG;
+  hipLaunchKernelGGL(layout_error_reduce_kernel, dim3((num_layouts + LR_T - 1) / LR_T), dim3(LR_T), 0, gatres_stream(stream), rec,
+                     (long long)num_snapshots, (int)num_layouts, table, (int)(accumulate != 0));
   return gatres_launch_status();
 }

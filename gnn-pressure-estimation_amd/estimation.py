@@ -21,6 +21,15 @@ is drawn in the staging launch from ``(seed, member, snapshot, sensor)``, ``read
 pairs and reduce them on the device (``gatres_ensemble_reduce``) to the mean and the standard deviation per junction, so the M
 result matrices never exist; ``noise_report`` adds the back-test error of the mean and the per-node spread
 (``gatres_node_spread_moments``): which junctions are sensitive to sensor error.
+
+Where to put the sensors.  ``layout_errors`` scores L sensor layouts -- subsets of the estimator's ``observed_idx``, the candidate
+sensors -- over a store as one long pass over the S * L (snapshot, layout) pairs, again three launches per batch:
+``gatres_stage_observed_layouts`` (a sensor the pair's layout leaves out is one more hidden node), the forward, and
+``gatres_layout_pair_errors``, which reduces the batch's error against the store's truth to one small record per pair while the
+predictions are still in the batch buffers; ``gatres_layout_error_reduce`` folds the records per layout.  No estimate matrix, no
+per-node table, no read-back: the result is a device table ``[L, LAYOUT_ERROR_RECORD]`` (``layout_scores_from_table``).
+``place_sensors`` is greedy forward selection on top of it (``greedy_selection`` holds the rule): one ``layout_errors`` call and
+one read-back per round.
 """
 from __future__ import annotations
 
@@ -37,6 +46,9 @@ from .snapshot_store import SnapshotStore
 NODE_ERROR_RECORD = _native.NODE_ERROR_RECORD
 NODE_ERROR_AVAIL_RECORD = _native.NODE_ERROR_AVAIL_RECORD
 NODE_SPREAD_RECORD = _native.NODE_SPREAD_RECORD
+LAYOUT_PAIR_RECORD = _native.LAYOUT_PAIR_RECORD
+LAYOUT_ERROR_RECORD = _native.LAYOUT_ERROR_RECORD
+PLACEMENT_CRITERIA = ("mae", "rmse", "max_abs")   # place_sensors(criterion=...): entries of layout_scores_from_table
 
 
 def observed_from_names(node_names: Sequence[str], sensor_names: Sequence[str]) -> List[int]:
@@ -172,6 +184,60 @@ def noise_report_from_moments(table, observed_idx) -> Dict[str, np.ndarray]:
             "most_sensitive": np.argsort(-spread, kind="stable")}
 
 
+def layout_scores_from_table(table) -> Dict[str, np.ndarray]:
+    """The per-layout scores from a ``gatres_layout_error_reduce`` table ``[L, LAYOUT_ERROR_RECORD]`` (include/gatres.h), in fp64:
+    ``count`` (the entries scored: hidden nodes times snapshots), ``mae``, ``rmse`` and ``max_abs`` over them.  A layout with
+    ``count == 0`` (every scored node carries a sensor) gives NaN."""
+    T = np.asarray(table, dtype=np.float64).reshape(-1, LAYOUT_ERROR_RECORD)
+    n = T[:, 0]
+    some = n > 0
+    d = np.where(some, n, 1.0)
+    return {"count": n.copy(), "mae": np.where(some, T[:, 1] / d, np.nan), "rmse": np.where(some, np.sqrt(T[:, 2] / d), np.nan),
+            "max_abs": np.where(some, T[:, 3], np.nan)}
+
+
+def greedy_selection(score_round, candidates: Sequence[int], num: int) -> Tuple[List[int], List[float]]:
+    """Greedy forward selection of ``num`` of ``candidates``.  Each round calls ``score_round(chosen, remaining)`` -- the
+    candidates chosen so far in order of choice, and the others in ``candidates`` order -- which returns one score per
+    remaining candidate: the score of ``chosen`` plus that candidate.  The smallest score wins; a NaN counts as worse than any
+    number; ties (and a round of NaNs) go to the earliest candidate in ``candidates`` order.  Returns the chosen candidates in
+    order of choice and the winning score of each round."""
+    remaining = [int(c) for c in candidates]
+    if len(set(remaining)) != len(remaining):
+        raise ValueError("candidates holds duplicates")
+    if isinstance(num, bool) or not isinstance(num, (int, np.integer)) or not 0 <= int(num) <= len(remaining):
+        raise ValueError(f"num must be an integer in [0, {len(remaining)}]; got {num!r}")
+    chosen: List[int] = []
+    scores: List[float] = []
+    for _ in range(int(num)):
+        sc = np.asarray(score_round(list(chosen), list(remaining)), dtype=np.float64).reshape(-1)
+        if sc.shape[0] != len(remaining):
+            raise ValueError(f"score_round returned {sc.shape[0]} scores for {len(remaining)} candidates")
+        best = 0
+        for i in range(1, len(remaining)):
+            if not np.isnan(sc[i]) and (np.isnan(sc[best]) or sc[i] < sc[best]):
+                best = i
+        chosen.append(remaining.pop(best))
+        scores.append(float(sc[best]))
+    return chosen, scores
+
+
+def _check_placement(nodes_per_graph: int, num_sensors, candidates, fixed, criterion) -> Tuple[List[int], List[int]]:
+    """The refusals of ``place_sensors`` (no device needed): returns (fixed, candidates) as lists."""
+    N = int(nodes_per_graph)
+    if criterion not in PLACEMENT_CRITERIA:
+        raise ValueError(f"criterion={criterion!r}: one of {', '.join(repr(c) for c in PLACEMENT_CRITERIA)}")
+    fix = [int(i) for i in fixed]
+    cand = [v for v in range(N) if v not in set(fix)] if candidates is None else [int(i) for i in candidates]
+    both = sorted(set(fix) & set(cand))
+    if both:
+        raise ValueError(f"fixed and candidates overlap at node {both[0]}")
+    if isinstance(num_sensors, bool) or not isinstance(num_sensors, (int, np.integer)) or not 1 <= int(num_sensors) <= len(cand):
+        raise ValueError(f"num_sensors must be an integer in [1, {len(cand)}] (the number of candidates); got {num_sensors!r}")
+    _check_observed(fix + cand, N)                     # (range and duplicates, in observed_idx's wording)
+    return fix, cand
+
+
 _RECIPROCAL: Dict[str, bool] = {}
 
 
@@ -252,6 +318,7 @@ class PressureEstimator:
             self._normalise = _native.NORMALISE_RECIPROCAL if _divides_by_reciprocal(dev) else _native.NORMALISE_DIVIDE
         self._observed = torch.tensor(self.observed_idx, dtype=torch.int32).to(dev)
         self._sigma_cache = {}                      # layout -> (bytes, device sigma[K]) of the last noise_std: uploaded when it changes
+        self._score_cache = None                    # (nodes, device score[N]) of the last score_nodes: uploaded when it changes
 
     @classmethod
     def for_store(cls, model, store, observed_idx, **kw) -> "PressureEstimator":
@@ -495,6 +562,126 @@ class PressureEstimator:
                 "gatres_node_spread_moments")
         out.update(noise_report_from_moments(table.cpu().numpy(), self.observed_idx))
         return out
+
+    def _score_mask(self, score_nodes) -> Optional[torch.Tensor]:
+        """``score_nodes`` as the device uint8 ``[N]`` of gatres_layout_pair_errors (``None``: every node); uploaded when it
+        changes."""
+        if score_nodes is None:
+            return None
+        N = self.nodes_per_graph
+        nodes = [int(v) for v in score_nodes]
+        bad = [v for v in nodes if v < 0 or v >= N]
+        if bad or not nodes:
+            raise ValueError(f"score_nodes must be node indices in [0, {N}), at least one; got {bad[0] if bad else 'none'}")
+        if len(set(nodes)) != len(nodes):
+            raise ValueError("score_nodes holds duplicates")
+        key = tuple(nodes)
+        cached = self._score_cache
+        if cached is None or cached[0] != key:
+            m = np.zeros(N, dtype=np.uint8)
+            m[nodes] = 1
+            cached = self._score_cache = (key, torch.from_numpy(m).to(self.device))
+        return cached[1]
+
+    def layout_errors(self, store, layouts: torch.Tensor, *, available: Optional[torch.Tensor] = None, score_nodes=None,
+                      out: Optional[torch.Tensor] = None, max_scratch_bytes: int = 64 << 20) -> torch.Tensor:
+        """The back-test error of L sensor layouts over the store's snapshots, on the device.  ``layouts``: uint8 or bool,
+        contiguous ``[L, K]`` on the model's device, non-zero where sensor ``observed_idx[k]`` is installed in the layout: the
+        estimator's sensors are the CANDIDATES, a layout is a subset of them (an empty layout is legal).  Returns the fp64
+        device table ``[L, LAYOUT_ERROR_RECORD]`` (``out``: write it there), ordered on the current stream: per layout the
+        number of entries scored, sum |e|, sum e^2 and max |e| (``layout_scores_from_table``), ``e`` the error of the model's
+        prediction against the store's descaled value as in ``error_map``.  Scored are the nodes HIDDEN in the layout (every
+        node without an installed sensor with a reading, as ``error_map(available=...)``'s ``hidden_*``) -- with ``score_nodes``
+        (node indices) only those of them: a pool disjoint from the candidates gives every layout the same pool.
+        ``available`` (``[len(store), K]``) takes readings away in every layout, as in ``estimate_store``.
+
+        The S * L (snapshot, layout) pairs, snapshot-major, are one long pass cut into batches of ``batch_size`` once, from pair
+        0, with three launches per batch (``gatres_stage_observed_layouts``, the forward, ``gatres_layout_pair_errors``): the
+        estimates are never written out.  The pairs' records go to a scratch of at most ``max_scratch_bytes``
+        (``ensemble_chunk``), one ``gatres_layout_error_reduce`` launch per chunk folds them in snapshot order: the bits of the
+        table depend on neither the budget nor the run.  Nothing is read back, nothing synchronises."""
+        self._check_store(store)
+        K, N, S, bs = len(self.observed_idx), self.nodes_per_graph, len(store), self.batch_size
+        if (not isinstance(layouts, torch.Tensor) or layouts.dtype not in (torch.uint8, torch.bool) or layouts.dim() != 2
+                or layouts.shape[1] != K or layouts.shape[0] == 0 or layouts.device != self.device or not layouts.is_contiguous()):
+            raise ValueError(f"layouts must be uint8 or bool, contiguous [L, {K}] on {self.device}")
+        L = int(layouts.shape[0])
+        if available is not None:
+            self._check_available(available, S)
+        if int(max_scratch_bytes) <= 0:
+            raise ValueError("max_scratch_bytes must be positive")
+        score = self._score_mask(score_nodes)
+        if out is None:
+            out = torch.empty((L, LAYOUT_ERROR_RECORD), dtype=torch.float64, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != self.device
+                or tuple(out.shape) != (L, LAYOUT_ERROR_RECORD) or not out.is_contiguous()):
+            raise ValueError(f"out must be fp64 contiguous [{L}, {LAYOUT_ERROR_RECORD}] on {self.device}")
+        C = ensemble_chunk(S, L, bs, 8 * LAYOUT_PAIR_RECORD, max_scratch_bytes)
+        model, lib, flat = self.model, _native.load(), self.model.flat_parameters
+        if flat.device != self.device:
+            raise ValueError(f"the model moved to {flat.device}; the estimator was built on {self.device}")
+        model.eval()
+        src = store.data
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream(self.device)
+            rec = torch.empty((C * L, LAYOUT_PAIR_RECORD), dtype=torch.float64, device=self.device)
+            sizes = {min(bs, S * L - first) for first in (0, (S * L - 1) // bs * bs)}
+            plans = {g: _eval_plan(model, self._topo, g) for g in sorted(sizes)}
+            for s0 in range(0, S, C):                               # (s0 * L is a multiple of bs: a chunk starts a batch)
+                c = min(C, S - s0)
+                for off in range(0, c * L, bs):
+                    g = min(bs, c * L - off)
+                    P = plans[g]
+                    _native.check(lib.gatres_stage_observed_layouts(
+                        src.data_ptr(), _native.OBSERVED_FULL_ROWS, S, s0 * L + off, L, N, g, self._observed.data_ptr(), K,
+                        _native.NORMALISE_NONE, 0.0, 1.0, P.x.data_ptr(), P.mask.data_ptr(), _native.ptr(available), 0,
+                        layouts.data_ptr(), stream), "gatres_stage_observed_layouts")
+                    _enqueue_forward(lib, flat, P, stream)
+                    _native.check(lib.gatres_layout_pair_errors(
+                        P.out.data_ptr(), P.mask.data_ptr(), src.data_ptr(), S, N, g, s0 * L + off, L, self.scale, self.offset,
+                        _native.ptr(score), rec.data_ptr(), C * L, off, stream), "gatres_layout_pair_errors")
+                _native.check(lib.gatres_layout_error_reduce(rec.data_ptr(), c, L, out.data_ptr(), int(s0 > 0), stream),
+                              "gatres_layout_error_reduce")
+        return out
+
+    @classmethod
+    def place_sensors(cls, model, store, num_sensors: int, *, candidates: Optional[Sequence[int]] = None,
+                      fixed: Sequence[int] = (), criterion: str = "mae", score_nodes=None, batch_size: int = 32,
+                      available: Optional[torch.Tensor] = None, **kw) -> Dict[str, object]:
+        """Where to put ``num_sensors`` sensors: greedy forward selection (``greedy_selection``) among ``candidates`` (node
+        indices; ``None``: every node not in ``fixed``) on top of the sensors ``fixed`` that are there already (may be empty:
+        the first round then scores single-sensor layouts), by the back-test error over ``store``.  ``criterion``: ``"mae"``,
+        ``"rmse"`` or ``"max_abs"`` of ``layout_scores_from_table``.
+
+        One estimator with ``observed_idx = list(fixed) + list(candidates)`` serves every round (``batch_size`` and ``**kw`` go to
+        ``for_store``; ``available``: ``[len(store), len(fixed) + len(candidates)]`` in that column order).  A round is ONE
+        ``layout_errors`` call -- the layouts ``fixed + chosen + {c}``, one per remaining candidate ``c`` -- and ONE read-back of
+        its table.  The error is pooled over the nodes hidden in the layout, so the pool shrinks by the node a candidate
+        occupies; ``score_nodes`` restricts it to those of the given nodes that are hidden, and a pool disjoint from the
+        candidates and from ``fixed`` gives every layout the same pool.
+
+        Returns ``observed_idx`` (``fixed`` plus the chosen nodes in order of choice: ready for ``for_store``), ``chosen``,
+        ``scores`` (the winning score of each round) and ``rounds``: per round a dict with ``candidates`` (the remaining nodes,
+        in ``candidates`` order) and the ``layout_scores_from_table`` entries, one value per candidate."""
+        _refuse_multi(store)
+        fix, cand = _check_placement(store.nodes_per_graph, num_sensors, candidates, fixed, criterion)
+        est = cls.for_store(model, store, fix + cand, batch_size=batch_size, **kw)
+        F, K = len(fix), len(fix) + len(cand)
+        column = {c: F + i for i, c in enumerate(cand)}
+        rounds: List[Dict[str, object]] = []
+
+        def score_round(chosen, remaining):
+            lay = np.zeros((len(remaining), K), dtype=np.uint8)
+            lay[:, :F] = 1
+            lay[:, [column[c] for c in chosen]] = 1
+            lay[np.arange(len(remaining)), [column[c] for c in remaining]] = 1
+            table = est.layout_errors(store, torch.from_numpy(lay).to(est.device), available=available, score_nodes=score_nodes)
+            scores = layout_scores_from_table(table.cpu().numpy())
+            rounds.append({"candidates": list(remaining), **scores})
+            return scores[criterion]
+
+        chosen, scores = greedy_selection(score_round, cand, int(num_sensors))
+        return {"observed_idx": fix + chosen, "chosen": chosen, "scores": scores, "rounds": rounds}
 
     def error_map(self, store, estimates: Optional[torch.Tensor] = None, *,
                   available: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:

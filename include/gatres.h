@@ -933,6 +933,60 @@ int gatres_ensemble_reduce(const float* members_mat, int64_t num_snapshots, int3
 #define GATRES_NODE_SPREAD_RECORD 4
 int gatres_node_spread_moments(const float* std_dev, int64_t num_snapshots, int32_t nodes_per_graph, double* table, void* stream);
 
+/* Scoring sensor layouts (symbols only: the ABI stays).  A sensor layout is a subset of the estimator's observed[] (the candidate
+ * sensors): layouts[L][num_observed] (device uint8), non-zero: sensor k is installed in that layout.  Scoring L layouts over S
+ * snapshots is one long pass over (snapshot, layout) PAIRS, snapshot-major: pair p is source row p / L and layout p % L.  Per
+ * batch of pairs: gatres_stage_observed_layouts, the forward, gatres_layout_pair_errors (one small record per pair, read from the
+ * forward's buffers: no estimate matrix); per chunk of snapshots one gatres_layout_error_reduce.
+ *
+ * gatres_stage_observed_layouts: the kernel of gatres_stage_observed_available compiled with the layout as one more compile-time
+ * fact.  The arguments, the source layouts and the checks of gatres_stage_observed_available, without rows, and
+ *   first_pair   graph g of the launch is pair p = first_pair + g: it reads source row p / num_layouts (of src and of available)
+ *                under layout p % num_layouts.  0 <= first_pair, first_pair + num_graphs <= src_rows * num_layouts.
+ *   num_layouts  >= 1
+ *   layouts      device uint8 [num_layouts][num_observed], required; it must not overlap x_dst or mask
+ *   available    [src_rows][num_observed]; may be NULL with nan_is_missing == 0 here: every reading is there.
+ * At v = observed[k] of graph g the reading is PRESENT when layouts[(p % L) * K + k] != 0 and (available == NULL or
+ * available[(p / L) * K + k] != 0) and it is no NaN under nan_is_missing in the readings layout: mask = 0, x_dst = the value
+ * exactly as gatres_stage_observed forms it (same normalisation, same rounding).  Everything else -- a sensor the layout leaves
+ * out, a missing reading, a node without a sensor -- gets x_dst = 0.0f, mask = 1; a reading that is not present is not loaded
+ * where layouts or available says so.  Every byte of mask and every float of x_dst of the batch is written exactly once.
+ * GATRES_E_BADARG before any launch: whatever gatres_stage_observed_available refuses (but for the NULL available),
+ * layouts == NULL or overlapping x_dst or mask, a pair range outside [0, src_rows * num_layouts), num_layouts < 1. */
+int gatres_stage_observed_layouts(const float* src, int32_t layout, int64_t src_rows, int64_t first_pair, int32_t num_layouts,
+                                  int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed, int32_t num_observed,
+                                  int32_t normalise, double offset, double factor, float* x_dst, uint8_t* mask,
+                                  const uint8_t* available, int32_t nan_is_missing, const uint8_t* layouts, void* stream);
+
+/* One batch's error, one record per graph.  out, mask: the forward's prediction and the staged mask of the batch,
+ * [num_graphs * N]; truth: the store's scaled matrix [truth_rows][N]; graph g is pair p = first_pair + g and is compared with
+ * truth row s = p / num_layouts.  The nodes counted are those with mask[g*N+v] != 0 && (score == NULL || score[v] != 0) (score:
+ * device uint8 [N]): the hidden nodes of the pair, or those of them that a caller's pool names.  With D() as in
+ * gatres_estimate_write and e = fp32(D(out[g*N+v]) - D(truth[s*N+v])), the e of gatres_node_error_moments at a hidden node,
+ * rec[rec_first + g][GATRES_LAYOUT_PAIR_RECORD] (device double) gets
+ *   [0] nodes counted   [1] sum (double)|e|   [2] sum (double)e * (double)e   [3] max |e|
+ * and four zeros when nothing is counted; nothing but the batch's num_graphs records is written.  One wave per graph; a lane
+ * takes chunks of four consecutive nodes (16-byte loads of out and truth, 32-bit loads of mask and score, where g * N, s * N and
+ * the pointers allow), the chunks of a wave are consecutive.  fp64 sums in an order that is a function of N alone (a lane's
+ * terms in node order, the lanes by a fixed butterfly), no atomics: the same bits on every run and in every batch composition.
+ * GATRES_E_BADARG before any launch: a NULL out, mask, truth or rec, num_layouts < 1, a pair range outside
+ * [0, truth_rows * num_layouts), records outside [0, rec_rows), rec[rec_rows] overlapping out, mask, truth or score. */
+#define GATRES_LAYOUT_PAIR_RECORD 4
+int gatres_layout_pair_errors(const float* out, const uint8_t* mask, const float* truth, int64_t truth_rows,
+                              int32_t nodes_per_graph, int32_t num_graphs, int64_t first_pair, int32_t num_layouts, double scale,
+                              double offset, const uint8_t* score, double* rec, int64_t rec_rows, int64_t rec_first, void* stream);
+
+/* The records of num_snapshots * num_layouts pairs, snapshot-major (rec[(s * L + l)][GATRES_LAYOUT_PAIR_RECORD]), folded into
+ * table[L][GATRES_LAYOUT_ERROR_RECORD] (device double).  Per layout l, strictly in the order s = 0 .. num_snapshots - 1:
+ *   [0] += count   [1] += sum |e|   [2] += sum e^2   [3] = fmax([3], max |e|)
+ * from zero when accumulate == 0, from the table's current record otherwise: a pass cut into chunks of snapshots (the first
+ * launch with accumulate == 0, the others with 1) leaves the bits of one launch over all of them.  One lane per layout,
+ * consecutive lanes read consecutive records; no atomics.  GATRES_E_BADARG before any launch: a NULL pointer, num_snapshots < 1,
+ * num_layouts < 1, rec overlapping table. */
+#define GATRES_LAYOUT_ERROR_RECORD 4
+int gatres_layout_error_reduce(const double* rec, int64_t num_snapshots, int32_t num_layouts, double* table, int32_t accumulate,
+                               void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
