@@ -7,6 +7,8 @@ from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
+from .sensor_layout import refuse_layout_multi_store
+
 
 def refuse_multi_store_data_parallel(world: int) -> None:
     """A ``MultiSnapshotStore`` trains on one device: sharding a batch's recipe across ranks is not implemented."""
@@ -168,6 +170,7 @@ class EpochLoop:
             t.seed = self.seed
             self._siblings[key] = t
         t.mask_rate = self.mask_rate
+        t._layout = self._layout            # (a sensor layout set or cleared since the sibling was built)
         t._metrics = self._metrics          # (device_metrics: the ragged batch writes the epoch's last record)
         return t
 
@@ -196,6 +199,8 @@ class EpochLoop:
         ``gatres_stage_multi_rows_mask_required`` otherwise; every tail batch on the sibling trainer of its recipe.  The
         epoch's rows go to the device once; nothing is read back per batch."""
         recipe = self._multi_recipe(store, bs)
+        if self._layout is not None:
+            refuse_layout_multi_store(store)
         sched = store.schedule(bs, recipe, drop_last)
         host_metrics = bool(metric_fn_dict)
         sums = {k: 0.0 for k in (metric_fn_dict or {})}
@@ -259,6 +264,8 @@ class EpochLoop:
         this runs."""
         from .multi_snapshot_store import MultiSnapshotStore
         bs = int(batch_size) if batch_size is not None else self.num_graphs
+        if self._layout is not None:
+            refuse_layout_multi_store(store)
         if isinstance(store, MultiSnapshotStore):
             self._multi_recipe(store, bs)
         elif bs != self.num_graphs or store.nodes_per_graph * bs != self.N:
@@ -298,8 +305,9 @@ class EpochLoop:
         order = store.epoch_order(shuffle=shuffle, generator=generator)
         first = 0                                        # batches [0, first) are done by the in-place path below
         nfull = store.num_snapshots // bs
+        # (under a sensor layout every batch needs its staging launch -- the layout's mask is written there: no in-place epoch)
         if (kseq > 1 and not host_metrics and nfull >= 2 and self._mask_next and self.node_ptr is not None
-                and self._epoch_copy_fits(nfull * bs, npg)):
+                and self._layout is None and self._epoch_copy_fits(nfull * bs, npg)):
             # The epoch's full batches as ONE device gather into a persistent buffer (the shuffled store: S x N_g floats), then
             # trained IN PLACE, k per captured launch sequence, with the mask sampled ahead by the update launches -- the
             # bound-batch step of bench.py, three launches and nothing else: no collation launch, no per-step host work.

@@ -517,6 +517,23 @@ class PressureEstimator:
         noise = self._noise(noise_std, noise_seed, noise_member, _native.OBSERVED_FULL_ROWS)
         return self._run(store.data, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, out, available, False, noise)
 
+    def fine_tune(self, train_store, val_store, epochs: int, *, lr: float, batch_size: Optional[int] = None,
+                  sensor_dropout: float = 0.0, layout_share: float = 1.0, mask_rate: float = 0.95, **fit_kw):
+        """Fine-tune the estimator's model to its own sensor layout: ``GATResTrainer.for_store(model, train_store, batch_size,
+        lr=lr, mask_rate=mask_rate)``, ``set_sensor_layout(observed_idx, sensor_dropout=..., layout_share=...)`` and
+        ``fit(train_store, val_store, epochs, **fit_kw)`` -- validated under the layout mask unless ``val_layout=False`` is
+        passed on.  ``batch_size`` defaults to the estimator's.  Returns the ``FitHistory``.  The training happens in the model's
+        own parameter vector, which every estimate reads at its launches: the estimator estimates with the tuned parameters
+        from the next call on, nothing is refreshed.  The trainer's constructor arguments other than ``lr`` and ``mask_rate``
+        keep their defaults: build the trainer yourself for anything else."""
+        from .train_step import GATResTrainer
+        self._check_store(train_store)
+        self._check_store(val_store)
+        bs = self.batch_size if batch_size is None else int(batch_size)
+        trainer = GATResTrainer.for_store(self.model, train_store, bs, lr=lr, mask_rate=mask_rate)
+        trainer.set_sensor_layout(self.observed_idx, sensor_dropout=sensor_dropout, layout_share=layout_share)
+        return trainer.fit(train_store, val_store, int(epochs), batch_size=bs, **fit_kw)
+
     def estimate_ensemble(self, readings: torch.Tensor, noise_std, members: int, *, seed: int = 0,
                           available: Optional[torch.Tensor] = None, nan_is_missing: bool = False,
                           mean_out: Optional[torch.Tensor] = None, std_out: Optional[torch.Tensor] = None,

@@ -379,7 +379,7 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
                    seed: int = 0, gpu_warmup_times: int = 10, norm_type: Optional[str] = None,
                    criterion: Optional[Callable] = None, metric_fn_dict: Optional[Dict[str, Callable]] = None,
                    per_network: bool = False, graphs_per_network: Optional[Sequence[int]] = None,
-                   _capture: Optional[List] = None) -> Tuple[float, Dict[str, float]]:
+                   observed_idx: Optional[Sequence[int]] = None, _capture: Optional[List] = None) -> Tuple[float, Dict[str, float]]:
     """``test_one_epoch`` over a ``SnapshotStore`` on the device: the same ``(loss, metrics)`` keys -- the reference's seven
     metrics, ``{prefix}_time`` (ms/graph) and ``{prefix}_throughput``, ``_sensor`` postfixed on the sensor pass.
 
@@ -398,6 +398,12 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
     ``metric_fn_dict`` is refused -- ``get_criterion("mae")`` / ``("sce")`` included, whatever criterion the model was trained
     with (the moment record carries no such sums): their validation loss comes from ``test_one_epoch``.  ``_capture`` (tests): a list that receives ``(mask, out, x, num_graphs)`` per batch.
 
+    ``observed_idx`` (a fixed sensor layout: node indices inside a graph, distinct): every batch is staged by
+    ``gatres_stage_rows_mask_sensors`` without dropout and with every graph under the layout -- all nodes hidden but these, the
+    mask a ``PressureEstimator`` of that layout is deployed under.  The mask is deterministic: ``seed`` and ``mask_rate`` do not
+    enter.  Forward, moments, keys and prefixes are unchanged.  Refused together with ``do_test_on_sensors``, ``required_idx``,
+    ``use_same_mask`` and a ``MultiSnapshotStore``.
+
     A ``MultiSnapshotStore`` is taken by its schedule (``store.schedule(batch_size, drop_last=False)``, the recipe the
     default or ``graphs_per_network``), every network's snapshots in order, staged by ``gatres_stage_multi_rows_mask_required``.
     ``required_idx`` is then a sequence of K sequences, one per network (sensor sets differ between networks).
@@ -413,12 +419,17 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
     multi = isinstance(store, MultiSnapshotStore)
     if not multi and (per_network or graphs_per_network is not None):
         raise ValueError("per_network / graphs_per_network belong to a MultiSnapshotStore")
+    if observed_idx is not None:
+        _check_layout_options(multi, do_test_on_sensors, required_idx, use_same_mask)
     scale, offset = _store_descale(store, norm_type)
     S = len(store)
     if S == 0:
         raise ValueError("empty store")
-    cut = (_MultiBatches if multi else _SingleBatches)(store, batch_size, mask_rate, required_idx if do_test_on_sensors else None,
-                                                        graphs_per_network)
+    if observed_idx is not None:
+        cut = _SingleBatches(store, batch_size, mask_rate, observed=observed_idx)
+    else:
+        cut = (_MultiBatches if multi else _SingleBatches)(store, batch_size, mask_rate,
+                                                            required_idx if do_test_on_sensors else None, graphs_per_network)
     postfix = "_sensor" if do_test_on_sensors else ""
     model.eval()
     if not model._flat_is_current():
@@ -492,6 +503,18 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
     return loss, metrics, nets
 
 
+def _check_layout_options(multi: bool, do_test_on_sensors: bool, required_idx, use_same_mask: bool) -> None:
+    """What ``evaluate_store(observed_idx=...)`` excludes: the layout IS the mask, so the sampler's options have no meaning."""
+    if multi:
+        raise NotImplementedError("observed_idx with a MultiSnapshotStore is not implemented (a layout per network would be "
+                                  "needed): evaluate one network's SnapshotStore")
+    if do_test_on_sensors or len(tuple(required_idx or ())) > 0:
+        raise ValueError("observed_idx fixes the mask (everything hidden but the sensors): do_test_on_sensors / required_idx "
+                         "belong to the sampled masks")
+    if use_same_mask:
+        raise ValueError("observed_idx fixes the mask: use_same_mask belongs to the sampled masks")
+
+
 def required_csr(store, required_idx, mask_rate: float):
     """Per-network required nodes of a ``MultiSnapshotStore`` as host CSR lists ``(req_ptr [K + 1], req_idx)``: ``required_idx``
     must be a sequence of K sequences (a flat list is refused for K > 1: sensor sets belong to a network), every index inside
@@ -523,13 +546,20 @@ class _SingleBatches:
     and stages batch ``b``.  ``keys[b]`` names the batch's plan (its graph count); ``required``: the sensor nodes (None: no
     sensor pass)."""
 
-    def __init__(self, store, batch_size: int, mask_rate: float, required=None, graphs_per_network=None):
+    def __init__(self, store, batch_size: int, mask_rate: float, required=None, graphs_per_network=None, observed=None):
         npg, S = store.nodes_per_graph, len(store)
         self.required = sorted(set(int(i) for i in required)) if required is not None else []
         if self.required and (self.required[0] < 0 or self.required[-1] >= npg):
             raise ValueError(f"required_idx must lie in [0, {npg})")
-        if int(npg * mask_rate) - len(self.required) <= 0:
+        # observed: a fixed sensor layout -- every batch gets its mask (gatres_stage_rows_mask_sensors without dropout, every
+        # graph under the layout) and the sampler draws nothing
+        self.observed = None
+        if observed is not None:
+            from .estimation import _check_observed
+            self.observed = _check_observed(observed, npg)
+        elif int(npg * mask_rate) - len(self.required) <= 0:
             raise ValueError("mask length must be positive")
+        self.obs = None
         self.store, self.batch_size = store, int(batch_size)
         nb = (S + batch_size - 1) // batch_size
         self.sizes = [min(batch_size, S - b * batch_size) for b in range(nb)]
@@ -554,10 +584,19 @@ class _SingleBatches:
             host = torch.tensor(self.required, dtype=torch.int32)
             keep = [host.pin_memory()] if pinned else [host]
             self.req = keep[0].to(dev, non_blocking=pinned)
+        if self.observed is not None:
+            host = torch.tensor(self.observed, dtype=torch.int32)
+            keep.append(host.pin_memory() if pinned else host)
+            self.obs = keep[-1].to(dev, non_blocking=pinned)
         return keep
 
     def stage(self, lib, P: _EvalPlan, b: int, mask_rate: float, seed64: int, step_ptr: int, sensors: bool, stream) -> None:
         rows = self.rows[self.offsets[b]: self.offsets[b] + self.sizes[b]]
+        if self.observed is not None:
+            from .sensor_layout import stage_rows
+            stage_rows(lib, self.store.data, rows.data_ptr(), self.store.nodes_per_graph, P.x, None, P.node_ptr, P.num_graphs,
+                       self.obs, len(self.observed), 0.0, 1.0, min(max(float(mask_rate), 0.0), 1.0), seed64, step_ptr, P.mask, stream)
+            return
         _enqueue_stage(lib, self.store, P, rows, mask_rate, seed64, step_ptr, self.req if sensors else None,
                        len(self.required) if sensors else 0, stream)
 
@@ -611,17 +650,24 @@ class _ValidationPass:
     synchronises: the moment table, the loss array and the per-batch graph counts stay on the device for
     ``gatres_epoch_control``.  Everything static (row order, sampler steps, graph counts, tables) is made once; with the same
     ``seed`` the moment table is bit for bit the one ``evaluate_store(seed=seed, gpu_warmup_times=0)`` forms.  ``store``: a
-    ``SnapshotStore`` or a ``MultiSnapshotStore`` (then the batches are its in-order schedule's)."""
+    ``SnapshotStore`` or a ``MultiSnapshotStore`` (then the batches are its in-order schedule's).  ``observed_idx``: the pass
+    of ``evaluate_store(observed_idx=...)`` -- everything hidden but a fixed sensor layout."""
 
-    def __init__(self, model, store, batch_size: int, mask_rate: float, criterion: str = "mse"):
+    def __init__(self, model, store, batch_size: int, mask_rate: float, criterion: str = "mse",
+                 observed_idx: Optional[Sequence[int]] = None):
         from . import _native
         from .multi_snapshot_store import MultiSnapshotStore
+        multi = isinstance(store, MultiSnapshotStore)
+        if observed_idx is not None:
+            _check_layout_options(multi, False, (), False)
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
         if len(store) == 0:
             raise ValueError("empty store")
-        multi = isinstance(store, MultiSnapshotStore)
-        self.cut = (_MultiBatches if multi else _SingleBatches)(store, int(batch_size), float(mask_rate))
+        if observed_idx is not None:          # (the layout mask of evaluate_store(observed_idx=...): deterministic, no sampler)
+            self.cut = _SingleBatches(store, int(batch_size), float(mask_rate), observed=observed_idx)
+        else:
+            self.cut = (_MultiBatches if multi else _SingleBatches)(store, int(batch_size), float(mask_rate))
         self.cut.upload(pinned=False)
         self.model, self.store, self.batch_size, self.mask_rate = model, store, int(batch_size), float(mask_rate)
         self.criterion = _native.CRITERIA[criterion]

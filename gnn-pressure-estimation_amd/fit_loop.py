@@ -93,7 +93,7 @@ class FitLoop:
             train_metrics: bool = False, save_path: Optional[str] = None, model_name: Optional[str] = None,
             variant: Optional[str] = None, save_best: str = "reference", restore_best: bool = False,
             checkpoint_extra: Optional[dict] = None, log_gradient: bool = False,
-            on_epoch: Optional[Callable[[int, dict], None]] = None) -> "FitHistory":
+            on_epoch: Optional[Callable[[int, dict], None]] = None, val_layout: bool = True) -> "FitHistory":
         """The reference's training loop (train.py:376-511 ``internal_train``) with its epoch boundary on the device.
 
         Per epoch e = 1 .. ``epochs``: ``fit_epoch`` on ``train_store`` (with the ``"train"`` metric collection computed on the
@@ -130,6 +130,13 @@ class FitLoop:
         ``train_metric_dict`` (with ``train_metrics``) and, with ``log_gradient``, ``total_grad_norm``, ``block_norms``,
         ``model_update``, ``accum_model_update``.  An exception it raises propagates.
 
+        Sensor layout (``set_sensor_layout``): the training epochs stage under the layout, and the validation pass masks
+        everything but the layout's sensors -- ``evaluate_store(..., observed_idx=layout, seed=val_seed + e)``'s launches, the
+        deployment mask without dropout -- so ``val_loss``, early stopping, the scheduler and ``best_metric_dict`` speak of the
+        deployed error.  ``val_layout=False`` keeps the random-mask validation.  Checkpoints then carry ``sensor_layout``
+        (``observed_idx``, ``sensor_dropout``, ``layout_share``) beside ``checkpoint_extra``.  Without a layout ``val_layout`` is
+        not looked at.
+
         Data parallel: every rank passes its shards; the epoch's four sums are all-reduced (one collective per epoch), so all
         ranks take the same decision; metric dicts and ``model_update`` describe the rank's own shard, the gradient norms the
         all-reduced gradient (the same on every rank).  Returns a ``FitHistory``."""
@@ -148,6 +155,12 @@ class FitLoop:
         bs = int(batch_size) if batch_size is not None else self.num_graphs
         vbs = int(val_batch_size) if val_batch_size is not None else bs
         from .multi_snapshot_store import MultiSnapshotStore
+        from .sensor_layout import refuse_layout_data_parallel, refuse_layout_multi_store
+        layout = self._layout
+        if layout is not None:
+            refuse_layout_data_parallel(self.world)
+            refuse_layout_multi_store(train_store)
+            refuse_layout_multi_store(val_store)
         multi = isinstance(train_store, MultiSnapshotStore)
         if multi:
             # (several networks: the batch's recipe is the trainer's, GATResTrainer.for_store; one device only)
@@ -161,7 +174,11 @@ class FitLoop:
             raise ValueError("a multi-network validation store needs a multi-network training store (same number of networks)")
         cfg = _native.GatresEpochConfig(float(min_delta), 0.1, 1e-4, 0.0, 1e-8, int(patience), int(scheduler_patience),
                                         int(scheduler is not None), 0)
-        val = E._ValidationPass(self.model, val_store, vbs, self.mask_rate, self._criterion)
+        val = E._ValidationPass(self.model, val_store, vbs, self.mask_rate, self._criterion,
+                                observed_idx=layout.observed_idx if layout is not None and val_layout else None)
+        extra = dict(checkpoint_extra or {})
+        if layout is not None:
+            extra["sensor_layout"] = layout.describe()
         nvb = len(val.sizes)
         fb = self._fit_buffers(epochs, nvb)
         sums, state, history, host, status_host, event = (fb[k] for k in ("sums", "state", "history", "host", "status_host", "event"))
@@ -188,7 +205,7 @@ class FitLoop:
                 paths[which], model_state_dict=self.model.state_dict() if model_sd is None else model_sd,
                 optimizer_state_dict=wdn_io.adam_state_dict(self, lr=rec[R["lr_used"]]) if adam is None else adam,
                 epoch=int(rec[R["best_epoch"]]), loss=float(rec[R["best_loss"]]), val_metric_dict=val_metrics(table),
-                **stats, **(checkpoint_extra or {}))
+                **stats, **extra)
 
         stream = _native.current_stream(self.device)
         best_rec = None

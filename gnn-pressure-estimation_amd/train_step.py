@@ -24,6 +24,7 @@ from .fit_loop import FitHistory, FitLoop, internal_train  # noqa: F401  (part o
 from .grad_flow import GradFlow
 from .graph_models import GATResMeanConv
 from .graph_plan import GraphPlan
+from .sensor_layout import SensorLayout, refuse_layout_data_parallel, stage_rows as _stage_rows_sensors
 
 PHASE_MASK, PHASE_FORWARD, PHASE_BACKWARD, PHASE_ADAM = 1, 2, 4, 8
 STATUS_FAULT_COUNT, STATUS_DROPPED_STEPS = 1, 3      # words of the fused path's status block (csrc/gatres_layout.h: FUSED_STATUS_*)
@@ -309,6 +310,9 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         # a trainer's buffers go when its last reference goes)
         self._last_stepper: Optional["GATResTrainer"] = None
         self._recipe = None                  # for_store() on a MultiSnapshotStore: the batch's graphs per network
+        # set_sensor_layout(): the fixed sensor layout the store-fed steps train under (None: the sampler's random masks); a
+        # sibling takes its parent's
+        self._layout: Optional[SensorLayout] = _share_state_with._layout if _share_state_with is not None else None
         self._warn_if_the_chip_is_not_ours()
 
     @classmethod
@@ -461,6 +465,48 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         if changed:
             self._push_hparams()                       # (siblings share both the dict and the device buffer)
 
+    # ---- fine-tuning to a fixed sensor layout -----------------------------------------------------------------------------
+    def set_sensor_layout(self, observed_idx: Sequence[int], *, sensor_dropout: float = 0.0, layout_share: float = 1.0) -> None:
+        """Train the store-fed steps (``step_rows``, ``steps_rows``, ``fit_epoch``, ``fit``) under the mask of a FIXED sensor
+        layout: every node hidden but ``observed_idx`` (node indices inside a graph, distinct -- the layout of a
+        ``PressureEstimator``).  Per step and graph, each sensor loses its reading with probability ``sensor_dropout`` (in
+        ``[0, 1)``; a graph may lose all of them: it then trains all-hidden), and with probability ``1 - layout_share`` the graph
+        takes the sampler's random mask of ``mask_rate`` instead, so that the model keeps the general task.  The batch is staged
+        by ``gatres_stage_rows_mask_sensors`` -- collation and mask in one launch, as without a layout; the step's own launches
+        are untouched.  The indices are uploaded once, here.  ``sensor_layout_draws(self.seed, step, ...)`` restates the draws.
+
+        While a layout is set the epoch goes through the row-gather steps (the in-place epoch has no staging launch), and the
+        calls that would train under the sampler's mask alone raise ``ValueError``: ``step(x, y)`` without a mask,
+        ``run_step(device_mask=True)``, ``step_prefetched``, ``bind_batches`` / ``step_bound`` / ``steps_bound``.
+        ``step(x, y, mask)`` with the caller's mask stays.  Siblings (the ragged batch's trainer) follow.  Data parallelism and a
+        ``MultiSnapshotStore`` are refused (``NotImplementedError``)."""
+        refuse_layout_data_parallel(self.world)
+        if self._recipe is not None:
+            raise NotImplementedError("a sensor layout with a MultiSnapshotStore is not implemented (a layout per network would "
+                                      "be needed): fine-tune on one network's SnapshotStore")
+        if self.node_ptr is None or not self._npg_list or len(set(self._npg_list)) != 1:
+            raise ValueError("a sensor layout needs nodes_per_graph at construction, the same for every graph of the batch")
+        self._adopt_layout(SensorLayout(observed_idx, self._npg_list[0], sensor_dropout, layout_share, self.device))
+
+    def clear_sensor_layout(self) -> None:
+        """Back to the sampler's random masks: every path, graph key and launch is the one of a trainer that never had a layout."""
+        self._adopt_layout(None)
+
+    def _adopt_layout(self, layout: Optional[SensorLayout]) -> None:
+        for t in [self] + list(self._siblings.values()):
+            t._layout = layout
+            t._committed(mask_ahead=False)      # (a mask sampled ahead belongs to the setting that was replaced)
+
+    @property
+    def sensor_layout(self) -> Optional[dict]:
+        """``{"observed_idx", "sensor_dropout", "layout_share"}`` of the layout set (a copy), or None."""
+        return None if self._layout is None else self._layout.describe()
+
+    def _refuse_under_layout(self, what: str) -> None:
+        if self._layout is not None:
+            raise ValueError(f"{what} would train under the sampler's random mask, not under the sensor layout that is set: use "
+                             f"step_rows / steps_rows / fit_epoch / fit, pass a mask of your own, or clear_sensor_layout()")
+
     def _graph_key(self, what, device_mask: bool, wt_valid: bool) -> tuple:
         # (no hyper-parameter in here: the kernels read them from self.hp; which of the two mask buffers is current is)
         return (what, device_mask, wt_valid, self.mask_rate, self.seed, self.world, self.mask.data_ptr())
@@ -583,6 +629,8 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         met = self._metrics
         if met is not None:            # (a step with the metrics launch is another graph than the same step without it)
             key = key + (("metrics", met["table"].data_ptr(), met["cursor"].data_ptr(), met["scale"], met["offset"]),)
+        if self._layout is not None:   # (a sequence that stages under a layout holds its buffer and its probabilities)
+            key = key + (self._layout.key(),)
         if not self.use_graph:
             enqueue()
             return
@@ -717,6 +765,7 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         side stream filled -- they never write x -- so there is no device copy and, with the mask sampled ahead by the previous
         update launch, no sampler launch either: the bound-batch step's three launches, the PCIe transfer of the next batch
         under them.  ``commit_batch()`` + ``run_step()`` is the same step through the static buffers (two launches more)."""
+        self._refuse_under_layout("step_prefetched")
         k = self._slot_out
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(self._ready[k])
@@ -729,6 +778,8 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
 
     def run_step(self, device_mask: bool = True) -> None:
         """One optimisation step on the staged batch.  Nothing is synchronised; read ``self.loss`` afterwards."""
+        if device_mask:
+            self._refuse_under_layout("run_step(device_mask=True)")
         self._step(device_mask)
 
     def _stage_with_mask(self, x: torch.Tensor, y: torch.Tensor) -> bool:
@@ -772,7 +823,14 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
 
     def _stage_rows(self, data: torch.Tensor, rows_ptr: int) -> None:
         """Collate the snapshots named by the ``num_graphs`` int64 row indices at device address ``rows_ptr`` into the static
-        buffers and sample the step's mask, in one launch."""
+        buffers and sample the step's mask, in one launch -- under a sensor layout, the layout's mask."""
+        lay = self._layout
+        if lay is not None:
+            _stage_rows_sensors(self.lib, data, rows_ptr, self.N // max(self.num_graphs, 1), self.x,
+                                None if self.targets_are_inputs else self.y, self.node_ptr, self.num_graphs, lay.observed,
+                                len(lay.observed_idx), lay.sensor_dropout, lay.layout_share, self.mask_rate, self.seed,
+                                self.step_counter.data_ptr(), self.mask, _native.current_stream(self.device))
+            return
         _native.check(self.lib.gatres_stage_rows_mask(
             data.data_ptr(), rows_ptr, self.N // max(self.num_graphs, 1), self.x.data_ptr(),
             None if self.targets_are_inputs else self.y.data_ptr(), self.node_ptr.data_ptr(), self.num_graphs, self.mask_rate,
@@ -823,6 +881,8 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
 
     def step(self, x: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Reference-shaped call: one iteration of train.py:159-190.  Returns the (device) loss tensor."""
+        if mask is None:
+            self._refuse_under_layout("step(x, y) without a mask")
         if mask is None and self._stage_with_mask(x, y):
             self._step(True, premasked=True)                                    # (the mask of this step is in place)
         else:
@@ -837,6 +897,7 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         so no staging copy is needed -- one captured step per buffer and mask-buffer orientation.  ``precapture``: capture
         every one of those steps NOW (``precapture_bound()``), so that no ``step_bound`` call ever pays for a capture.  The
         trainer keeps the tensors alive; do not resize them.  Returns the number of bound batches."""
+        self._refuse_under_layout("bind_batches")
         ys = xs if ys is None else ys
         bound = []
         for x, y in zip(xs, ys):
@@ -924,6 +985,7 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         path this is three launches -- the per-snapshot kernel, the parameter gradients, the update (which also samples the
         next step's mask) -- replayed from one hipGraph; the first step (and any step after the optimizer state moved under
         the trainer) runs the sampler's launch first."""
+        self._refuse_under_layout("step_bound")
         return self._step_on(self._bound[i], slot=i)
 
     def steps_bound(self, indices, bound=None, losses: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -935,6 +997,7 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         step, data-parallel trainer, eager launches) falls back to the single calls.  ``bound``: another list of resident
         ``(x, y)`` batches than the one ``bind_batches`` registered (``fit_epoch``'s epoch buffer); ``losses``: a float32 vector
         whose entry j receives step j's loss.  Returns the last step's loss tensor."""
+        self._refuse_under_layout("steps_bound")
         idx = tuple(int(i) for i in indices)
         bnd = self._bound if bound is None else bound
         if losses is not None and losses.numel() < len(idx):

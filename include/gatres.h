@@ -298,6 +298,33 @@ int gatres_stage_rows_mask_required(const float* data, const int64_t* rows, int3
                                     const uint64_t* step_counter, const int32_t* required, int32_t num_required, uint8_t* mask,
                                     void* stream);
 
+/* gatres_stage_rows_mask's collation with the mask of a FIXED sensor layout (fine-tuning a model to the sensors it is deployed
+ * with; new symbol only: the ABI version stays).  observed[num_observed] (device int32): the sensors' node indices inside a
+ * graph, distinct, each in [0, nodes_per_graph) -- the caller's duty, as for required[].
+ * Collation: x_dst[g * N + v] = data[rows[g] * N + v] at EVERY node (and y_dst likewise when given), N = nodes_per_graph: the
+ * step zeroes masked inputs itself and its target is x.
+ * Draws (all integer arithmetic modulo 2^64; mix64: the splitmix64 finaliser behind the sampler's keys):
+ *   step = step_counter ? step_counter[0] : 0,   base = seed + 0x9E3779B97F4A7C15 * (step + 1),
+ *   T_drop = (uint32_t)(sensor_dropout * 16777216.0),   T_share = (uint32_t)(layout_share * 16777216.0);
+ *   graph g takes the LAYOUT mask iff (mix64(base + 0x94D049BB133111EB * (g + 1)) >> 40) < T_share, else the RANDOM mask.
+ * Layout mask of graph g, n0 = node_ptr[g]: mask[n0 + v] = 0 iff v == observed[k] for some k and
+ *   (mix64(base + 0xBF58476D1CE4E5B9 * (n0 + v + 1)) >> 40) >= T_drop  (the hash of the sampler's key of that node, before its
+ *   truncation); every other node of the graph, and every dropped sensor, gets mask = 1.  A graph that loses all its sensors
+ *   to the dropout is masked everywhere: allowed (its loss then is the all-hidden one).
+ * Random mask of graph g: byte for byte what gatres_stage_rows_mask writes for that graph with the same
+ *   (mask_rate, seed, step_counter, node_ptr).
+ * One launch of the sampler's grid; every byte of mask and every float of x_dst (y_dst) of the batch is written exactly once,
+ * with plain stores.  A pure function of the arguments and *step_counter: a replayed capture draws fresh masks as the counter
+ * advances.  sensor_dropout 0 and layout_share 1 give the mask bytes of gatres_stage_observed (seed, step and mask_rate unused);
+ * layout_share 0 gives gatres_stage_rows_mask.
+ * GATRES_E_BADARG before any launch: data, rows, x_dst, node_ptr, observed or mask NULL; data == x_dst; num_graphs <= 0 or
+ * nodes_per_graph <= 0; num_observed < 1 or > nodes_per_graph; sensor_dropout outside [0, 1); layout_share or mask_rate
+ * outside [0, 1]. */
+int gatres_stage_rows_mask_sensors(const float* data, const int64_t* rows, int32_t nodes_per_graph, float* x_dst, float* y_dst,
+                                   const int32_t* node_ptr, int32_t num_graphs, const int32_t* observed, int32_t num_observed,
+                                   double sensor_dropout, double layout_share, double mask_rate, uint64_t seed,
+                                   const uint64_t* step_counter, uint8_t* mask, void* stream);
+
 /* gatres_stage_rows_mask_required for a batch whose graphs come from SEVERAL snapshot matrices (one [S_k][N_k] matrix per
  * water network; utils/DataLoader.py:61-183 takes lists of networks): src_table[num_networks] (device) holds the matrices'
  * device addresses; graph g is row rows[g] (device, int64) of matrix net_of_graph[g] (device, int32), node_ptr[g + 1] -
