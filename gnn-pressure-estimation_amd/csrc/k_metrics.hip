@@ -1,7 +1,7 @@
-// Device side of the evaluation epoch (evaluation.py:240-351 of the reference, our evaluation.evaluate_store): the staging
-// launch whose mask always holds the sensor nodes (gatres_stage_rows_mask_required), and the masked-metric moments of one
-// batch (gatres_masked_metrics) -- one fixed-layout fp64 record per batch from which evaluation.metrics_from_moments forms the
-// loss and the seven metrics of get_metric_fn_collection (utils/auxil.py:101-140,185-203) on the host.
+// Device side of the evaluation epoch (evaluation.py:240-351 of the reference, our evaluation.evaluate_store): the
+// masked-metric moments of one batch (gatres_masked_metrics) -- one fixed-layout fp64 record per batch from which
+// evaluation.metrics_from_moments forms the loss and the seven metrics of get_metric_fn_collection
+// (utils/auxil.py:101-140,185-203) on the host.  (The epoch's staging launch, gatres_stage_rows_mask_required: k_stage.hip.)
 //
 // The moments kernel is ONE workgroup: each thread accumulates its strided elements in index order, the waves reduce by a
 // fixed butterfly, thread 0 adds the 16 wave partials in wave order.  No atomics, no floating-point reordering between runs:
@@ -10,7 +10,6 @@
 // therefore the two counts are those of the host functions.  The sums themselves are fp64; the centred sums are taken in a
 // second pass around the first pass's means (descaled pressures sit around 50 m: raw second moments would cancel).
 #include "gatres_common.h"
-#include "k_mask.h"
 
 namespace {
 
@@ -131,23 +130,6 @@ __global__ __launch_bounds__(MET_T) void masked_metrics_kernel(const float* __re
   }
 }
 
-// gatres_stage_rows_mask's launch with the required-node sampler: collate x (and y) from the snapshot matrix, then sample.
-__global__ __launch_bounds__(1024) void stage_rows_mask_required_kernel(const int* __restrict__ node_ptr, double rate,
-                                                                        uint64_t seed, const uint64_t* __restrict__ step_counter,
-                                                                        uint8_t* __restrict__ mask, const float* __restrict__ data,
-                                                                        float* __restrict__ x_dst, float* __restrict__ y_dst,
-                                                                        long long num_nodes, const long long* __restrict__ rows,
-                                                                        int rows_npg, const int* __restrict__ required,
-                                                                        int num_required) {
-  for (long long v = (long long)blockIdx.x * 1024 + threadIdx.x; v < num_nodes; v += (long long)gridDim.x * 1024) {
-    const float s = data[rows[v / rows_npg] * rows_npg + v % rows_npg];
-    x_dst[v] = s;
-    if (y_dst) y_dst[v] = s;
-  }
-  mask_sample_graph<1024, MASK_WGS, true>(node_ptr, rate, seed, step_counter ? step_counter[0] : 0, mask, blockIdx.x / MASK_WGS,
-                                          blockIdx.x % MASK_WGS, required, num_required);
-}
-
 }  // namespace
 
 extern "C" int gatres_masked_metrics(const float* out, const float* y, const uint8_t* mask, int32_t num_nodes, double scale,
@@ -158,20 +140,5 @@ extern "C" int gatres_masked_metrics(const float* out, const float* y, const uin
   hipLaunchKernelGGL(masked_metrics_kernel, dim3(1), dim3(MET_T), 0, gatres_stream(stream), out, y, mask, (int)num_nodes,
                      (float)scale, (float)offset, table, (int)slot, (int)capacity,
                      reinterpret_cast<unsigned long long*>(cursor));
-  return gatres_launch_status();
-}
-
-extern "C" int gatres_stage_rows_mask_required(const float* data, const int64_t* rows, int32_t nodes_per_graph, float* x_dst,
-                                               float* y_dst, const int32_t* node_ptr, int32_t num_graphs, double mask_rate,
-                                               uint64_t seed, const uint64_t* step_counter, const int32_t* required,
-                                               int32_t num_required, uint8_t* mask, void* stream) {
-  if (!node_ptr || !mask || num_graphs <= 0 || !(mask_rate >= 0.0 && mask_rate <= 1.0)) return GATRES_E_BADARG;
-  if (!data || !rows || !x_dst || nodes_per_graph <= 0 || data == x_dst) return GATRES_E_BADARG;
-  if (num_required < 0 || (num_required > 0 && !required)) return GATRES_E_BADARG;
-  // utils/auxil.py:151-153: the sampled part int(n*rate) - r must be positive
-  if (num_required > 0 && (int)((double)nodes_per_graph * mask_rate) - num_required <= 0) return GATRES_E_BADARG;
-  hipLaunchKernelGGL(stage_rows_mask_required_kernel, dim3(num_graphs * MASK_WGS), dim3(1024), 0, gatres_stream(stream),
-                     node_ptr, mask_rate, seed, step_counter, mask, data, x_dst, y_dst, (long long)num_graphs * nodes_per_graph,
-                     reinterpret_cast<const long long*>(rows), (int)nodes_per_graph, required, (int)num_required);
   return gatres_launch_status();
 }

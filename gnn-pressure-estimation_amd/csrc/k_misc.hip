@@ -1,6 +1,7 @@
 // Small dense / reduction kernels around the message-passing stack: lin0 / lin1 (PyG Linear(1,nc), Linear(nc,1);
 // GraphModels.py:477,484,487,492), parameter-gradient column reductions, the slab reducer, weight transposes,
-// and the caller-side pieces of the training step (device mask sampler, masked MSE, Adam; train.py:174-188).
+// and the caller-side pieces of the training step (masked loss, Adam; train.py:174-188).  The mask sampler's own launches
+// are in k_stage.hip.
 //
 // Reductions over nodes: `num_slabs` waves each own a contiguous node range and write their partial sums to
 // their own slab at the parameter's flat offset; gatres_reduce_slabs adds the slabs in index order.  No atomics,
@@ -438,27 +439,6 @@ __global__ __launch_bounds__(256) void edge_hash_kernel(const int64_t* __restric
   if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);      // integer add: order-independent
 }
 
-// ---------------------------------------------------------------------------------- device mask sampler (k_mask.h)
-// One launch: MASK_WGS workgroups per graph; the batch copy -- or its collation from the snapshot matrix -- rides on it
-// (gatres_stage_batch_mask / gatres_stage_rows_mask: grid-stride, before the sampling: its stores drain while the keys are ranked)
-__global__ __launch_bounds__(1024) void mask_generate_kernel(const int* __restrict__ node_ptr, double rate,
-                                                             uint64_t seed, const uint64_t* __restrict__ step_counter,
-                                                             uint8_t* __restrict__ mask,
-                                                             const float* __restrict__ x_src, const float* __restrict__ y_src,
-                                                             float* __restrict__ x_dst, float* __restrict__ y_dst,
-                                                             long long num_nodes, const long long* __restrict__ rows,
-                                                             int rows_npg) {
-  if (x_src && x_src != x_dst) {
-    for (long long v = (long long)blockIdx.x * 1024 + threadIdx.x; v < num_nodes; v += (long long)gridDim.x * 1024) {
-      const long long u = rows ? rows[v / rows_npg] * rows_npg + v % rows_npg : v;
-      x_dst[v] = x_src[u];
-      if (y_src && y_dst) y_dst[v] = y_src[u];
-    }
-  }
-  mask_sample_graph<1024, MASK_WGS>(node_ptr, rate, seed, step_counter ? step_counter[0] : 0, mask, blockIdx.x / MASK_WGS,
-                          blockIdx.x % MASK_WGS);
-}
-
 // ------------------------------------------------------------------------------------------- masked loss
 // CRIT = GATRES_LOSS_MSE is the masked MSE of gatres_masked_mse, instruction for instruction; MAE / SCE: gatres_loss_term
 template <int CRIT>
@@ -784,36 +764,6 @@ extern "C" int gatres_edge_index_hash(const int64_t* edge_index, int64_t num_edg
   if (num_edges == 0) return 0;
   hipLaunchKernelGGL(edge_hash_kernel, dim3((unsigned)((num_edges + 255) / 256)), dim3(256), 0, gatres_stream(stream),
                      edge_index, (long long)num_edges, reinterpret_cast<unsigned long long*>(hash_out));
-  return gatres_launch_status();
-}
-
-extern "C" int gatres_mask_generate(const int32_t* node_ptr, int32_t num_graphs, double mask_rate, uint64_t seed,
-                                    const uint64_t* step_counter, uint8_t* mask, void* stream) {
-  if (!node_ptr || !mask || num_graphs <= 0 || !(mask_rate >= 0.0 && mask_rate <= 1.0)) return GATRES_E_BADARG;
-  hipLaunchKernelGGL(mask_generate_kernel, dim3(num_graphs * MASK_WGS), dim3(1024), 0, gatres_stream(stream), node_ptr, mask_rate,
-                     seed, step_counter, mask, nullptr, nullptr, nullptr, nullptr, 0LL, nullptr, 1);
-  return gatres_launch_status();
-}
-
-extern "C" int gatres_stage_batch_mask(const float* x_src, const float* y_src, float* x_dst, float* y_dst, int64_t num_nodes,
-                                       const int32_t* node_ptr, int32_t num_graphs, double mask_rate, uint64_t seed,
-                                       const uint64_t* step_counter, uint8_t* mask, void* stream) {
-  if (!node_ptr || !mask || num_graphs <= 0 || !(mask_rate >= 0.0 && mask_rate <= 1.0)) return GATRES_E_BADARG;
-  if (!x_src || !x_dst || num_nodes <= 0 || ((y_src == nullptr) != (y_dst == nullptr))) return GATRES_E_BADARG;
-  hipLaunchKernelGGL(mask_generate_kernel, dim3(num_graphs * MASK_WGS), dim3(1024), 0, gatres_stream(stream), node_ptr, mask_rate,
-                     seed, step_counter, mask, x_src, y_src, x_dst, y_dst, (long long)num_nodes, nullptr, 1);
-  return gatres_launch_status();
-}
-
-extern "C" int gatres_stage_rows_mask(const float* data, const int64_t* rows, int32_t nodes_per_graph, float* x_dst,
-                                      float* y_dst, const int32_t* node_ptr, int32_t num_graphs, double mask_rate,
-                                      uint64_t seed, const uint64_t* step_counter, uint8_t* mask, void* stream) {
-  if (!node_ptr || !mask || num_graphs <= 0 || !(mask_rate >= 0.0 && mask_rate <= 1.0)) return GATRES_E_BADARG;
-  if (!data || !rows || !x_dst || nodes_per_graph <= 0 || data == x_dst) return GATRES_E_BADARG;
-  static_assert(sizeof(long long) == sizeof(int64_t), "row indices");
-  hipLaunchKernelGGL(mask_generate_kernel, dim3(num_graphs * MASK_WGS), dim3(1024), 0, gatres_stream(stream), node_ptr, mask_rate,
-                     seed, step_counter, mask, data, y_dst ? data : nullptr, x_dst, y_dst,
-                     (long long)num_graphs * nodes_per_graph, reinterpret_cast<const long long*>(rows), (int)nodes_per_graph);
   return gatres_launch_status();
 }
 

@@ -1,4 +1,4 @@
-"""Fine-tuning to a FIXED sensor layout: the host side of ``gatres_stage_rows_mask_sensors`` (csrc/k_sensor_mask.hip).
+"""Fine-tuning to a FIXED sensor layout: the host side of ``gatres_stage_rows_mask_sensors`` (csrc/k_stage.hip).
 
 ``sensor_layout_draws`` restates the launch's draws in numpy ``uint64`` arithmetic (no device use): which graphs of a batch take
 the layout mask and which sensors keep their reading.  ``SensorLayout`` is what ``GATResTrainer.set_sensor_layout`` holds: the

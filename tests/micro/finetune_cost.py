@@ -11,7 +11,7 @@ C-Town-sized snapshots, 20 sensors, on one device.
               repetition by repetition.  One JSON line per configuration: raw repetitions, median and range.
   --accuracy  an observation on synthetic data, not a claim: the validation MAE under the layout mask and under random 95 %
               masks, before and after ``--epochs`` epochs of ``PressureEstimator.fine_tune`` (dropout 0.1, share 0.7).
-  --kernels   ``--launches`` launches each of ``gatres_stage_rows_mask`` (``mask_generate_kernel``) and
+  --kernels   ``--launches`` launches each of ``gatres_stage_rows_mask`` (``stage_rows_mask_kernel<false>``) and
               ``gatres_stage_rows_mask_sensors`` at (0, 1) and (0.1, 0.7) on one batch, for a kernel trace of the process.
 
 ``--root``: import the package of another checkout (the parent commit) instead of the one this file lies in.  Not collected by
