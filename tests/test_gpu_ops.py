@@ -241,6 +241,15 @@ def test_device_mask_sampler_exact_count_and_fresh_per_step(ops):
         step[0] = t
         cnt += 1 - ops.mask_generate(node_ptr, len(sizes), 0.95, 99, step, n).cpu().numpy()[:388]
     assert abs(cnt.mean() / 400 - 20 / 388) < 1e-9 and cnt.max() < 60 and cnt.min() > 1
+    # ... by the chi-square of those counts (387 degrees of freedom; the bound of test_gpu_eval_device.py and of
+    # test_sampler_ref_host.py, where the reference's own sampler is held to it), and what the sampler must output is stated:
+    # the host restatement's bytes (tests/sampler_ref.py; every other launch of the sampler: test_gpu_mask_sampler.py)
+    import sampler_ref
+    expect = 400 * 20 / 388
+    chi2 = float(((cnt - expect) ** 2 / expect).sum())
+    assert chi2 < 387 + 6 * np.sqrt(2 * 387), chi2
+    assert np.array_equal(m0, sampler_ref.sampler_mask(1234, 0, sizes, 0.95))
+    assert np.array_equal(m1, sampler_ref.sampler_mask(1234, 1, sizes, 0.95))
 
 
 def test_masked_mse_and_adam_match_torch(ops):

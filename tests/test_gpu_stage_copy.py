@@ -6,7 +6,8 @@ NaN with a payload, -0.0, a denormal and +-inf, and everything is compared as ``
 around every destination and around the mask must survive.
 
 The mask is compared only where it is ``gatres_mask_generate``'s by contract (no required nodes, layout share 0); the required
-and layout masks have their own tests (test_gpu_eval_device.py, test_gpu_sensor_layout.py) and the sampler is not restated."""
+and layout masks have their own tests (test_gpu_eval_device.py, test_gpu_sensor_layout.py); what the sampler itself must output is
+restated on the host in tests/sampler_ref.py, and test_gpu_mask_sampler.py holds every launch of it to that, byte for byte."""
 import itertools
 
 import numpy as np
