@@ -19,7 +19,8 @@ LIB_PATH = os.path.join(LIB_DIR, "libgatres_hip.so")
 ARCH = "gfx950"
 
 SOURCES = ["k_window.hip", "k_fused_whole.hip", "k_fused_host.hip", "k_aggregate.hip", "k_proj.hip", "k_misc.hip", "k_blocked.hip", "graph_plan.hip",
-           "model_driver.hip", "train_driver.hip", "k_autoclip.hip", "k_metrics.hip", "k_epoch.hip", "k_stage.hip", "k_grad_flow.hip", "k_estimate.hip"]
+           "model_driver.hip", "train_driver.hip", "k_autoclip.hip", "k_metrics.hip", "k_epoch.hip", "k_stage.hip", "k_grad_flow.hip", "k_estimate.hip",
+           "k_bounds.hip"]
 
 
 def _hipcc() -> str:

@@ -160,6 +160,9 @@ SIGNATURES = {
     "gatres_stage_observed": (C.c_int, [_P, _I32, _I64, _P, _I64, _I32, _I32, _P, _I32, _I32, _F64, _F64, _P, _P, _P]),
     "gatres_estimate_write": (C.c_int, [_P, _P, _P, _I32, _I32, _F64, _F64, _I32, _P, _I64, _I64, _I64, _P]),
     "gatres_node_error_moments": (C.c_int, [_P, _P, _I64, _I32, _F64, _F64, _P, _I32, _P, _P]),
+    # (levels: a HOST array of doubles)
+    "gatres_node_error_quantiles": (C.c_int, [_P, _P, _I64, _I32, _F64, _F64, _P, _I32, _P, _P, _I32, _P, _P, _P]),
+    "gatres_node_bound_coverage": (C.c_int, [_P, _P, _I64, _I32, _F64, _F64, _P, _I32, _P, _P, _I32, _P, _P]),
     "gatres_stage_observed_available": (C.c_int, [_P, _I32, _I64, _P, _I64, _I32, _I32, _P, _I32, _I32, _F64, _F64, _P, _P, _P,
                                                   _I32, _P]),
     "gatres_node_error_moments_available": (C.c_int, [_P, _P, _I64, _I32, _F64, _F64, _P, _I32, _P, _P, _P]),
@@ -182,6 +185,8 @@ OBSERVED_FULL_ROWS, OBSERVED_READINGS = 0, 1         # GATRES_OBSERVED_* (gatres
 NORMALISE_NONE, NORMALISE_DIVIDE, NORMALISE_RECIPROCAL = 0, 1, 2      # GATRES_NORMALISE_*
 NODE_ERROR_RECORD, NODE_ERROR_CHUNK = 8, 64         # GATRES_NODE_ERROR_RECORD, GATRES_NODE_ERROR_CHUNK
 NODE_ERROR_AVAIL_RECORD = 8                         # GATRES_NODE_ERROR_AVAIL_RECORD (gatres_node_error_moments_available)
+NODE_QUANTILE_MAX_LEVELS = 8                        # GATRES_NODE_QUANTILE_MAX_LEVELS (gatres_node_error_quantiles)
+NODE_COVERAGE_RECORD = 1 + NODE_QUANTILE_MAX_LEVELS  # a record of gatres_node_bound_coverage: n_v and the hits per level
 NODE_SPREAD_RECORD = 4                              # GATRES_NODE_SPREAD_RECORD (gatres_node_spread_moments)
 LAYOUT_PAIR_RECORD = 4                              # GATRES_LAYOUT_PAIR_RECORD (gatres_layout_pair_errors)
 LAYOUT_ERROR_RECORD = 4                             # GATRES_LAYOUT_ERROR_RECORD (gatres_layout_error_reduce)

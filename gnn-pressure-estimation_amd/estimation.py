@@ -30,9 +30,17 @@ predictions are still in the batch buffers; ``gatres_layout_error_reduce`` folds
 per-node table, no read-back: the result is a device table ``[L, LAYOUT_ERROR_RECORD]`` (``layout_scores_from_table``).
 ``place_sensors`` is greedy forward selection on top of it (``greedy_selection`` holds the rule): one ``layout_errors`` call and
 one read-back per round.
+
+How far off may an estimate be.  ``calibrate_bounds`` is split-conformal calibration over a held-out store: per junction ONE order
+statistic of ``|estimate - truth|`` per level, from one ``gatres_node_error_quantiles`` launch (an exact radix select per column
+of the error matrix, which is never formed or sorted); the ``ErrorBounds`` stay on the device.  If a new snapshot is exchangeable
+with the calibration ones, ``p_v +- b_v`` holds with probability >= level, per junction.  ``coverage_report`` counts, on another
+store, how often it did (``gatres_node_bound_coverage``, one read-back); ``estimate_with_bounds`` and ``reading_residuals`` use the
+bounds.  ``conformal_rank`` / ``node_error_bounds`` / ``coverage_from_table`` restate all of it in numpy, without a device.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -48,6 +56,8 @@ NODE_ERROR_AVAIL_RECORD = _native.NODE_ERROR_AVAIL_RECORD
 NODE_SPREAD_RECORD = _native.NODE_SPREAD_RECORD
 LAYOUT_PAIR_RECORD = _native.LAYOUT_PAIR_RECORD
 LAYOUT_ERROR_RECORD = _native.LAYOUT_ERROR_RECORD
+NODE_QUANTILE_MAX_LEVELS = _native.NODE_QUANTILE_MAX_LEVELS
+NODE_COVERAGE_RECORD = _native.NODE_COVERAGE_RECORD
 PLACEMENT_CRITERIA = ("mae", "rmse", "max_abs")   # place_sensors(criterion=...): entries of layout_scores_from_table
 
 
@@ -194,6 +204,145 @@ def layout_scores_from_table(table) -> Dict[str, np.ndarray]:
     d = np.where(some, n, 1.0)
     return {"count": n.copy(), "mae": np.where(some, T[:, 1] / d, np.nan), "rmse": np.where(some, np.sqrt(T[:, 2] / d), np.nan),
             "max_abs": np.where(some, T[:, 3], np.nan)}
+
+
+def conformal_rank(n, level):
+    """The split-conformal rank of ``gatres_node_error_quantiles`` (include/gatres.h), 1-based, in numpy fp64:
+    ``ceil(float64(n + 1) * float64(level))`` -- one product, one ceil.  ``n`` may be an array.  A rank above ``n`` means too few
+    samples for the level: the bound is +inf."""
+    return np.ceil((np.asarray(n, dtype=np.int64) + 1).astype(np.float64) * np.float64(level))
+
+
+def _check_levels(levels) -> Tuple[float, ...]:
+    try:
+        lv = tuple(float(q) for q in levels)
+    except TypeError:
+        raise ValueError(f"levels must be a sequence of 1 to {NODE_QUANTILE_MAX_LEVELS} floats in (0, 1)") from None
+    if not 1 <= len(lv) <= NODE_QUANTILE_MAX_LEVELS:
+        raise ValueError(f"levels must hold 1 to {NODE_QUANTILE_MAX_LEVELS} values; got {len(lv)}")
+    if any(not 0.0 < q < 1.0 for q in lv):
+        raise ValueError(f"levels must lie in the open interval (0, 1); got {lv}")
+    if any(b <= a for a, b in zip(lv, lv[1:])):
+        raise ValueError(f"levels must be strictly increasing; got {lv}")
+    return lv
+
+
+def node_error_bounds(est, truth_descaled, levels, hidden=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The statement ``gatres_node_error_quantiles`` is held to, in numpy (no device): ``e = float32(est) - float32(truth_descaled)``
+    rounded to fp32, the ``uint32`` patterns of ``|e|`` sorted per column -- over the entries where ``hidden`` (bool ``[S, N]``) is
+    true, when given -- and per level the element of rank ``conformal_rank(n_v, level)``, +inf where the rank exceeds ``n_v``.
+    As unsigned integers the patterns are in IEEE order, with a NaN above +inf.  Returns ``(bounds[Q, N] float32, counts[N]
+    float64)``.  ``levels``: any floats in (0, 1)."""
+    e = np.asarray(est, dtype=np.float32) - np.asarray(truth_descaled, dtype=np.float32)
+    if e.ndim != 2:
+        raise ValueError("est and truth_descaled must be [S, N]")
+    lv = [float(q) for q in levels]
+    if not lv or any(not 0.0 < q < 1.0 for q in lv):
+        raise ValueError("levels must be floats in the open interval (0, 1), at least one")
+    S, N = e.shape
+    keys = np.ascontiguousarray(np.abs(e)).view(np.uint32)
+    counted = np.ones((S, N), dtype=np.bool_) if hidden is None else np.asarray(hidden, dtype=np.bool_)
+    if counted.shape != (S, N):
+        raise ValueError(f"hidden must be bool [{S}, {N}]")
+    bounds = np.full((len(lv), N), np.inf, dtype=np.float32)
+    bits = bounds.view(np.uint32)
+    counts = counted.sum(axis=0).astype(np.int64)
+    for v in range(N):
+        col = np.sort(keys[counted[:, v], v])
+        for q, level in enumerate(lv):
+            r = int(conformal_rank(counts[v], level))
+            if r <= counts[v]:
+                bits[q, v] = col[r - 1]
+    return bounds, counts.astype(np.float64)
+
+
+def coverage_from_table(table, bounds, levels, observed_idx) -> Dict[str, object]:
+    """The coverage report from a ``gatres_node_bound_coverage`` table ``[N, NODE_COVERAGE_RECORD]`` (include/gatres.h) and the
+    ``bounds[Q, N]`` it was counted against, in fp64: ``levels``, ``coverage[Q, N]`` = hits / n_v (NaN where n_v == 0), and over
+    the nodes outside ``observed_idx`` ``nonsensor_coverage[Q]`` (sum of hits / sum of counts; NaN without any), ``min_coverage[Q]``
+    with ``worst_node[Q]`` (the first node that attains it; NaN and -1 when no such node has an entry), ``mean_width[Q]`` = the
+    mean of ``2 * bounds`` over those of them with a finite bound (NaN without any) and ``unbounded[Q]``, the number of them with
+    an infinite bound."""
+    T = np.asarray(table, dtype=np.float64).reshape(-1, NODE_COVERAGE_RECORD)
+    lv = [float(q) for q in levels]
+    Q, N = len(lv), T.shape[0]
+    B = np.asarray(bounds, dtype=np.float64).reshape(Q, N)
+    n, hits = T[:, 0], T[:, 1:1 + Q].T
+    some = n > 0
+    coverage = np.where(some, hits / np.where(some, n, 1.0), np.nan)
+    free = np.ones(N, dtype=np.bool_)
+    free[np.asarray(list(observed_idx), dtype=np.int64)] = False
+    pool = free & some
+    out = {"levels": tuple(lv), "coverage": coverage,
+           "nonsensor_coverage": np.full(Q, np.nan), "min_coverage": np.full(Q, np.nan),
+           "worst_node": np.full(Q, -1, dtype=np.int64), "mean_width": np.full(Q, np.nan),
+           "unbounded": np.zeros(Q, dtype=np.int64)}
+    nodes = np.nonzero(pool)[0]
+    for q in range(Q):
+        if nodes.size:
+            out["nonsensor_coverage"][q] = hits[q, pool].sum() / n[pool].sum()
+            worst = nodes[np.argmin(coverage[q, nodes])]
+            out["min_coverage"][q], out["worst_node"][q] = coverage[q, worst], worst
+        finite = free & np.isfinite(B[q])
+        if finite.any():
+            out["mean_width"][q] = (2.0 * B[q, finite]).mean()
+        out["unbounded"][q] = int((free & np.isinf(B[q])).sum())
+    return out
+
+
+class ErrorBounds:
+    """Calibrated per-node error bounds: ``levels`` (a tuple of floats), ``bounds`` (fp32 ``[Q, N]``: ``|estimate - truth| <=
+    bounds[q, v]`` at node ``v`` with probability >= ``levels[q]``; +inf: too few calibration samples), ``counts`` (fp64 ``[N]``:
+    the samples behind each node's bounds) and ``observed_idx``, the sensor layout they were calibrated for.  The tensors stay
+    where ``calibrate_bounds`` left them, on the device."""
+
+    def __init__(self, levels, bounds: torch.Tensor, counts: torch.Tensor, observed_idx):
+        self.levels = tuple(float(q) for q in levels)
+        if (not isinstance(bounds, torch.Tensor) or bounds.dtype != torch.float32 or bounds.dim() != 2
+                or bounds.shape[0] != len(self.levels)):
+            raise ValueError(f"bounds must be an fp32 tensor [{len(self.levels)}, N]")
+        if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.float64 or tuple(counts.shape) != (bounds.shape[1],)
+                or counts.device != bounds.device):
+            raise ValueError(f"counts must be an fp64 tensor [{bounds.shape[1]}] on {bounds.device}")
+        self.bounds, self.counts = bounds, counts
+        self.observed_idx = [int(i) for i in observed_idx]
+
+    @property
+    def nodes_per_graph(self) -> int:
+        return int(self.bounds.shape[1])
+
+    @property
+    def device(self) -> torch.device:
+        return self.bounds.device
+
+    def level_index(self, level=None) -> int:
+        """The row of ``bounds`` for ``level``: an exact match of a stored level (``None``: the only one)."""
+        if level is None:
+            if len(self.levels) != 1:
+                raise ValueError(f"level=None needs bounds with one level; these hold {self.levels}")
+            return 0
+        if float(level) not in self.levels:
+            raise ValueError(f"level {level!r} is not one of the calibrated levels {self.levels}")
+        return self.levels.index(float(level))
+
+    def interval(self, estimates: torch.Tensor, level=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(estimates - b, estimates + b)`` with ``b = bounds[level_index(level)]`` broadcast over the rows of ``estimates``
+        (``[..., N]`` on the bounds' device): two torch element passes, nothing read back."""
+        b = self.bounds[self.level_index(level)]
+        return estimates - b, estimates + b
+
+    def state_dict(self) -> Dict[str, object]:
+        """CPU tensors and plain lists (one read-back of each tensor): what ``wdn_io.save_checkpoint(path, ...,
+        error_bounds=eb.state_dict())`` can carry."""
+        return {"levels": list(self.levels), "bounds": self.bounds.detach().cpu(), "counts": self.counts.detach().cpu(),
+                "observed_idx": list(self.observed_idx)}
+
+    @classmethod
+    def from_state_dict(cls, d, device=None) -> "ErrorBounds":
+        bounds, counts = torch.as_tensor(d["bounds"], dtype=torch.float32), torch.as_tensor(d["counts"], dtype=torch.float64)
+        if device is not None:
+            bounds, counts = bounds.to(device), counts.to(device)
+        return cls(d["levels"], bounds, counts, d["observed_idx"])
 
 
 def greedy_selection(score_round, candidates: Sequence[int], num: int) -> Tuple[List[int], List[float]]:
@@ -728,6 +877,118 @@ class PressureEstimator:
         if available is None:
             return error_map_from_moments(table.cpu().numpy())
         return error_map_from_moments(table.cpu().numpy(), available=True, observed_idx=self.observed_idx)
+
+    # ---- calibrated error bounds ------------------------------------------------------------------------------------------------
+    def _error_inputs(self, store, estimates, available, noise_std, noise_seed) -> torch.Tensor:
+        self._check_store(store)
+        if available is not None:
+            self._check_available(available, len(store))
+        if estimates is None:
+            return self.estimate_store(store, available=available, noise_std=noise_std, noise_seed=noise_seed)
+        return self._result(len(store), estimates)
+
+    def calibrate_bounds(self, store, levels=(0.9,), *, estimates: Optional[torch.Tensor] = None,
+                         available: Optional[torch.Tensor] = None, noise_std=None, noise_seed: int = 0) -> ErrorBounds:
+        """Split-conformal error bounds per junction from a held-out ``store`` (not the training data): for every level ``q`` of
+        ``levels`` (1 to 8 floats in (0, 1), strictly increasing) and every node ``v`` the element of rank
+        ``conformal_rank(n_v, q)`` of ``|estimate - truth|`` over the store's snapshots.  If a new snapshot is exchangeable with
+        the store's, ``|estimate - truth| <= bounds[q, v]`` holds with probability >= ``q``, per node (not jointly over the
+        nodes); with fewer than ``q / (1 - q)`` snapshots no finite bound has that coverage and the bound is +inf.
+
+        The estimates are ``estimates`` (fp32 ``[len(store), N_g]`` on the device) or ``estimate_store(store, available=,
+        noise_std=, noise_seed=)``.  With ``noise_std`` the calibration errors contain one noisy realisation of the readings per
+        snapshot, so one number covers model error and sensor error.  With ``available`` (``[len(store), K]``) the bound at a
+        sensor node is over the snapshots in which its reading was missing (as ``error_map(available=)``): a sensor that
+        always delivered gets ``counts = 0`` and +inf.  With ``keep_observed`` the bounds at sensor nodes are those of the
+        normalise / descale round trip of the reading itself (about 0), not of the model; the reports pool over the nodes
+        outside ``observed_idx``, as ``error_map`` does.
+
+        One ``gatres_node_error_quantiles`` launch behind the pass.  Nothing is read back and nothing synchronises: the
+        ``ErrorBounds`` hold device tensors ordered on the current stream."""
+        lv = _check_levels(levels)
+        est = self._error_inputs(store, estimates, available, noise_std, noise_seed)
+        N, Q = self.nodes_per_graph, len(lv)
+        bounds = torch.empty((Q, N), dtype=torch.float32, device=self.device)
+        counts = torch.empty((N,), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().gatres_node_error_quantiles(
+                est.data_ptr(), store.data.data_ptr(), len(store), N, self.scale, self.offset, self._observed.data_ptr(),
+                len(self.observed_idx), _native.ptr(available), (ctypes.c_double * Q)(*lv), Q, bounds.data_ptr(),
+                counts.data_ptr(), _native.current_stream(self.device)), "gatres_node_error_quantiles")
+        return ErrorBounds(lv, bounds, counts, self.observed_idx)
+
+    def _check_bounds(self, bounds) -> None:
+        if not isinstance(bounds, ErrorBounds):
+            raise ValueError("bounds must be the ErrorBounds of calibrate_bounds")
+        if bounds.observed_idx != self.observed_idx:
+            raise ValueError(f"the bounds were calibrated for the sensor layout {bounds.observed_idx}, the estimator's is "
+                             f"{self.observed_idx}")
+        if bounds.nodes_per_graph != self.nodes_per_graph:
+            raise ValueError(f"the bounds cover {bounds.nodes_per_graph} nodes, the estimator {self.nodes_per_graph}")
+        if bounds.device != self.device or not bounds.bounds.is_contiguous():
+            raise ValueError(f"the bounds must be contiguous on {self.device} (got {bounds.device})")
+
+    def coverage_report(self, store, bounds: ErrorBounds, *, estimates: Optional[torch.Tensor] = None,
+                        available: Optional[torch.Tensor] = None, noise_std=None, noise_seed: int = 0) -> Dict[str, object]:
+        """How often the bounds held over ``store`` (a test store: on the calibration store itself the coverage is at least the
+        level by construction): the entries of ``coverage_from_table``.  The estimates as in ``calibrate_bounds``.  One
+        ``gatres_node_bound_coverage`` launch and one read-back, of the table and the bounds together."""
+        self._check_bounds(bounds)
+        est = self._error_inputs(store, estimates, available, noise_std, noise_seed)
+        N, Q = self.nodes_per_graph, len(bounds.levels)
+        table = torch.empty((N, NODE_COVERAGE_RECORD), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().gatres_node_bound_coverage(
+                est.data_ptr(), store.data.data_ptr(), len(store), N, self.scale, self.offset, self._observed.data_ptr(),
+                len(self.observed_idx), _native.ptr(available), bounds.bounds.data_ptr(), Q, table.data_ptr(),
+                _native.current_stream(self.device)), "gatres_node_bound_coverage")
+        # (one transfer: fp32 -> fp64 is exact)
+        both = torch.cat([table.reshape(-1), bounds.bounds.reshape(-1).to(torch.float64)]).cpu().numpy()
+        return coverage_from_table(both[:N * NODE_COVERAGE_RECORD], both[N * NODE_COVERAGE_RECORD:].reshape(Q, N),
+                                   bounds.levels, self.observed_idx)
+
+    def estimate_with_bounds(self, readings: torch.Tensor, bounds: ErrorBounds, level=None,
+                             **estimate_kw) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``est = estimate(readings, **estimate_kw)`` and ``(lo, hi) = bounds.interval(est, level)`` (``level=None``: the
+        bounds hold one level): the pressure at every junction with its calibrated interval, all on the device.  No launch
+        beyond those of ``estimate`` and torch's two element passes."""
+        self._check_bounds(bounds)
+        bounds.level_index(level)                                   # (refused before the pass)
+        est = self.estimate(readings, **estimate_kw)
+        lo, hi = bounds.interval(est, level)
+        return est, lo, hi
+
+    def reading_residuals(self, readings: torch.Tensor, bounds, level=None, *,
+                          nan_is_missing: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Is a reading plausible given the others?  For every sensor column ``k`` one ``estimate(readings, available=)`` with
+        column ``k`` unavailable in every snapshot; ``residual[:, k]`` = reading - prediction at ``observed_idx[k]`` and
+        ``flagged[:, k]`` = ``|residual| > b_k``, ``b_k`` the bound at that node with the reading hidden.  Returns
+        ``(residual[S, K] fp32, flagged[S, K] bool)`` on the device; K passes, nothing read back.
+
+        ``bounds``: a list of K ``ErrorBounds``, the k-th from ``calibrate_bounds(store, available=a_k)`` with ``a_k`` all ones
+        but column ``k``, which is all zero -- the same column hidden as here; or ONE ``ErrorBounds`` that holds such a bound
+        at every sensor node (for a single sensor: made with ``available`` all zero in its column).  Bounds calibrated
+        without ``available`` are those of the sensors' own values (about 0 with ``keep_observed``) and would flag
+        everything.  A missing reading (``nan_is_missing``) gives a NaN residual and is not flagged."""
+        self._check_readings(readings)
+        K, S = len(self.observed_idx), int(readings.shape[0])
+        each = list(bounds) if isinstance(bounds, (list, tuple)) else [bounds] * K
+        if len(each) != K:
+            raise ValueError(f"bounds must be one ErrorBounds or a list of {K}, one per sensor; got {len(each)}")
+        for b in each:
+            self._check_bounds(b)
+        rows = [b.bounds[b.level_index(level)] for b in each]
+        available = torch.ones((S, K), dtype=torch.uint8, device=self.device)
+        est = torch.empty((S, self.nodes_per_graph), dtype=torch.float32, device=self.device)
+        residual = torch.empty((S, K), dtype=torch.float32, device=self.device)
+        flagged = torch.empty((S, K), dtype=torch.bool, device=self.device)
+        for k, v in enumerate(self.observed_idx):
+            available[:, k] = 0
+            self.estimate(readings, out=est, available=available, nan_is_missing=nan_is_missing)
+            available[:, k] = 1
+            residual[:, k] = readings[:, k] - est[:, v]
+            flagged[:, k] = residual[:, k].abs() > rows[k][v]
+        return residual, flagged
 
     def sensor_failure_report(self, store, sensors: Optional[Sequence[int]] = None) -> Dict[str, object]:
         """Leave-one-out back-test of the sensor layout over ``store``: a baseline pass with every reading available, then for

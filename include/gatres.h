@@ -874,6 +874,46 @@ int gatres_estimate_write(const float* out, const float* x, const uint8_t* mask,
 int gatres_node_error_moments(const float* est, const float* truth, int64_t num_snapshots, int32_t nodes_per_graph, double scale,
                               double offset, const int32_t* observed, int32_t num_observed, double* table, void* stream);
 
+/* Calibrated per-node error bounds (symbols only: the ABI stays).  Split-conformal calibration: per node ONE order statistic
+ * per level of |e| over the snapshots of a held-out store; a new snapshot exchangeable with those lies inside the bound with
+ * probability >= level, per node.
+ *
+ * gatres_node_error_quantiles: est, truth, scale, offset, e = fp32(est - D(truth)) and D() as in gatres_node_error_moments.
+ *   available  NULL: every entry (s, v) is COUNTED and observed / num_observed are not read.  Device uint8 [S][num_observed]:
+ *              the entry is counted when it is hidden in the sense of gatres_node_error_moments_available, that is unless
+ *              v == observed[k] and available[s * K + k] != 0.
+ *   levels     HOST double[num_levels], each in the open interval (0, 1); read before the call returns.
+ *   bounds     device float [num_levels][N];  counts: device double [N].
+ * Per node v, A_v is the multiset of the 32-bit patterns of fabsf(e) over the counted entries, ordered as unsigned integers:
+ * the IEEE order for finite values and +inf, a NaN above +inf, -0.0 and +0.0 one element.  n_v = |A_v|, counts[v] = n_v.  For
+ * level q the rank is r = ceil((double)(n_v + 1) * levels[q]) (one fp64 product, one ceil; 1-based, r >= 1):
+ *   r >  n_v   bounds[q * N + v] = +inf (too few samples; n_v == 0 included)
+ *   r <= n_v   bounds[q * N + v] = the float whose bits are the r-th smallest element of A_v
+ * exactly: a sort gives the same bits (estimation.node_error_bounds is that statement on the host), whatever the launch
+ * geometry.  One launch: an MSB-first radix select, eight bits per pass, with histograms in LDS; every pass re-reads est and
+ * truth.  No global atomics, no scratch in global memory, nothing written but bounds and counts.
+ * GATRES_E_BADARG before any launch: a NULL est, truth, levels, bounds or counts; num_snapshots < 1 or above 2^31 - 1 (the
+ * histograms count in 32 bits); nodes_per_graph < 1; num_levels outside [1, GATRES_NODE_QUANTILE_MAX_LEVELS]; a level that is
+ * NaN or outside (0, 1); available != NULL with observed == NULL or num_observed outside [1, N]; bounds or counts overlapping
+ * est, truth, available, observed or each other. */
+#define GATRES_NODE_QUANTILE_MAX_LEVELS 8
+int gatres_node_error_quantiles(const float* est, const float* truth, int64_t num_snapshots, int32_t nodes_per_graph,
+                                double scale, double offset, const int32_t* observed, int32_t num_observed,
+                                const uint8_t* available, const double* levels, int32_t num_levels, float* bounds,
+                                double* counts, void* stream);
+
+/* How many entries lie inside the bounds.  The inputs, e and the counted entries of gatres_node_error_quantiles; bounds: device
+ * float [num_levels][N] (read).  table[N][1 + GATRES_NODE_QUANTILE_MAX_LEVELS] (device double), per node v over its counted
+ * entries:
+ *   [0] n_v   [1 + q] #{ fabsf(e) <= bounds[q * N + v] } by float comparison, q < num_levels   the other slots 0
+ * A NaN error is never inside, a NaN bound covers nothing, a +inf bound covers every error that is no NaN.  The traversal of
+ * gatres_node_error_moments; the counters are integers (exact as doubles), no atomics.
+ * GATRES_E_BADARG before any launch: as gatres_node_error_quantiles, with bounds and table for levels, bounds and counts; table
+ * overlapping est, truth, available, observed or bounds. */
+int gatres_node_bound_coverage(const float* est, const float* truth, int64_t num_snapshots, int32_t nodes_per_graph,
+                               double scale, double offset, const int32_t* observed, int32_t num_observed,
+                               const uint8_t* available, const float* bounds, int32_t num_levels, double* table, void* stream);
+
 /* Estimation when some sensor readings are missing (symbols only: the ABI stays).  A sensor without a reading in a snapshot is
  * one more hidden node of that snapshot: the model was trained with random masks.
  *
