@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from estimation_refs import garbage, torch_stage      # noqa: E402,F401
 from test_gpu_model import build, relerr      # noqa: E402
 
 DEV = "cuda:0"
@@ -45,12 +46,6 @@ def stream():
     return torch.cuda.current_stream(torch.device(DEV)).cuda_stream
 
 
-def garbage(n):
-    """A staging target that shows any element the launch leaves unwritten: NaN inputs and mask bytes of 0xAB."""
-    return (torch.full((n,), float("nan"), dtype=torch.float32, device=DEV),
-            torch.full((n,), 0xAB, dtype=torch.uint8, device=DEV))
-
-
 def stage(pkg, lib, src, layout, rows, first, n, g, observed, normalise=0, offset=0.0, factor=1.0):
     x, mask = garbage(g * n)
     obs = torch.tensor(observed, dtype=torch.int32, device=DEV)
@@ -58,18 +53,6 @@ def stage(pkg, lib, src, layout, rows, first, n, g, observed, normalise=0, offse
                                                 obs.data_ptr(), len(observed), normalise, offset, factor, x.data_ptr(),
                                                 mask.data_ptr(), stream()), "gatres_stage_observed")
     return x, mask
-
-
-def torch_stage(values, n, observed):
-    """The reference's collation for a fixed sensor set: zeros, the sensors' values put at their nodes, a mask of ones with
-    zeros there.  ``values``: [g, K]."""
-    g = values.shape[0]
-    obs = torch.tensor(observed, dtype=torch.int64, device=DEV)
-    x = torch.zeros((g, n), dtype=torch.float32, device=DEV)
-    x.index_put_((torch.arange(g, device=DEV).unsqueeze(1), obs.unsqueeze(0)), values)
-    mask = torch.ones((g, n), dtype=torch.uint8, device=DEV)
-    mask[:, obs] = 0
-    return x.reshape(-1), mask.reshape(-1)
 
 
 # ---- 1. staging --------------------------------------------------------------------------------------------------------------

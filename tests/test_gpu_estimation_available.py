@@ -16,6 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import test_gpu_estimation as E      # noqa: E402
+from estimation_refs import torch_stage_available      # noqa: E402
 from test_gpu_estimation import (DEV, N37, OBS, check_against_module, check_against_oracle, garbage, hand_loop, make_store,      # noqa: E402
                                  moments_table, raw_snapshots, small_model, stream, topology, torch_stage)
 
@@ -52,19 +53,6 @@ def row_pattern(S, K):
 def column_pattern(S):
     """[S, 3]: column 0 never missing, column 1 missing in every snapshot, column 2 missing in every third snapshot."""
     return avail([[1, 0, 0 if s % 3 == 0 else 1] for s in range(S)])
-
-
-def torch_stage_available(values, n, observed, available):
-    """The reference's collation with gaps: zeros, ``index_put_`` of the PRESENT values at their nodes, a mask of ones with
-    zeros where present.  ``values``, ``available``: [g, K]."""
-    g = values.shape[0]
-    obs = torch.tensor(observed, dtype=torch.int64, device=DEV)
-    gi, ki = available.bool().nonzero(as_tuple=True)
-    x = torch.zeros((g, n), dtype=torch.float32, device=DEV)
-    x.index_put_((gi, obs[ki]), values[gi, ki])
-    mask = torch.ones((g, n), dtype=torch.uint8, device=DEV)
-    mask[gi, obs[ki]] = 0
-    return x.reshape(-1), mask.reshape(-1)
 
 
 def stage_available(pkg, lib, src, layout, rows, first, n, g, observed, available, nan_is_missing=0, normalise=0, offset=0.0,

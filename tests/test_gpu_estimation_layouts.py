@@ -14,6 +14,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from estimation_refs import check_records, numpy_fold, numpy_pair_errors      # noqa: E402
 from test_gpu_estimation import DEV, N37, garbage, make_store, raw_snapshots, small_model, stream, topology      # noqa: E402
 from test_gpu_estimation_noise import OBS40, avail, torch_stage_available      # noqa: E402
 
@@ -23,7 +24,6 @@ OBS37 = [36, 0, 5, 17, 20]                        # unsorted: column k of the la
 LAYOUTS = [[0, 0, 0, 0, 0], [1, 1, 1, 1, 1], [1, 0, 1, 0, 0], [0, 1, 0, 0, 1], [0, 0, 1, 1, 0], [1, 0, 1, 0, 0]]
 # [S5, 5]: a snapshot with every reading, one with none, mixed rows
 AVAIL = [[1, 1, 1, 1, 1], [0, 0, 0, 0, 0], [1, 0, 1, 1, 0], [0, 1, 1, 0, 1], [1, 1, 0, 1, 1]]
-U = 2.0 ** -53
 
 
 def observed_of(n):
@@ -128,36 +128,6 @@ def test_layout_staging_across_the_tile_boundary(pkg, lib):
 
 
 # ---- 2. pair errors ---------------------------------------------------------------------------------------------------------------
-def numpy_pair_errors(out, mask, truth, scale, offset, score=None):
-    """gatres_layout_pair_errors restated: ``out``, ``truth`` fp32 [G, N] (truth: the row of each graph), ``mask`` uint8 [G, N],
-    ``score`` uint8 [N] or None.  D() and the difference in fp32 with separate roundings, the sums in fp64."""
-    out, truth = np.asarray(out, dtype=np.float32), np.asarray(truth, dtype=np.float32)
-    sc, of = np.float32(scale), np.float32(offset)
-    e = ((out * sc).astype(np.float32) + of).astype(np.float32) - ((truth * sc).astype(np.float32) + of).astype(np.float32)
-    assert e.dtype == np.float32
-    counted = np.asarray(mask) != 0
-    if score is not None:
-        counted = counted & (np.asarray(score) != 0)[None, :]
-    rec = np.zeros((out.shape[0], 4), dtype=np.float64)
-    for g in range(out.shape[0]):
-        eg = e[g][counted[g]].astype(np.float64)
-        if eg.size:
-            rec[g] = [eg.size, np.abs(eg).sum(), (eg * eg).sum(), np.abs(eg).max()]
-    return rec
-
-
-def check_records(got, want, terms):
-    """Count and max exact; the two sums within 2 * terms * 2^-53 relative (non-negative terms that are exact in fp64: only the
-    order of the additions can differ, and either order is within (terms - 1) * 2^-53 of the exact sum)."""
-    np.testing.assert_array_equal(got[:, 0], want[:, 0])
-    np.testing.assert_array_equal(got[:, 3], want[:, 3])
-    for f in (1, 2):
-        d = np.abs(got[:, f] - want[:, f])
-        print(f"field {f}: max relative difference {float((d / np.maximum(want[:, f], 1e-300)).max()):.3e} "
-              f"(bound {2 * terms * U:.3e})")
-        assert (d <= 2 * terms * U * want[:, f]).all(), f
-
-
 @pytest.mark.parametrize("n", [N37, 40], ids=["odd", "vector"])
 @pytest.mark.parametrize("scored", [False, True], ids=["every_node", "score"])
 def test_pair_errors_against_numpy(pkg, lib, n, scored):
@@ -200,16 +170,6 @@ def test_pair_errors_against_numpy(pkg, lib, n, scored):
 
 
 # ---- 3. the reduce ----------------------------------------------------------------------------------------------------------------
-def numpy_fold(rec, S, L, table=None):
-    """gatres_layout_error_reduce restated: per layout in snapshot order."""
-    t = np.zeros((L, 4), dtype=np.float64) if table is None else table.copy()
-    r = rec.reshape(S, L, 4)
-    for s in range(S):
-        t[:, :3] = t[:, :3] + r[s, :, :3]
-        t[:, 3] = np.maximum(t[:, 3], r[s, :, 3])
-    return t
-
-
 def synthetic_records(S, L, seed):
     gen = torch.Generator().manual_seed(seed)
     rec = torch.rand((S * L, 4), generator=gen, dtype=torch.float64) * 3.0 + 0.1

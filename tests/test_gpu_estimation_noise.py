@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 from test_gpu_estimation import (DEV, N37, OBS, garbage, hand_loop, make_store, raw_snapshots, small_model, stage,      # noqa: E402
                                  stream, topology, torch_stage)
+from estimation_refs import numpy_reduce, torch_stage_available      # noqa: E402,F401
 from test_gpu_model import relerr      # noqa: E402
 
 SEED = 20260
@@ -60,35 +61,6 @@ def pair_values(values, sigma, Z):
 
 def avail(rows):
     return torch.tensor(rows, dtype=torch.uint8, device=DEV)
-
-
-def torch_stage_available(values, n, observed, available):
-    """``torch_stage`` with gaps: only the PRESENT values are put at their nodes and unmasked.  ``values``, ``available``: [g, K]."""
-    g = values.shape[0]
-    obs = torch.tensor(observed, dtype=torch.int64, device=DEV)
-    gi, ki = available.bool().nonzero(as_tuple=True)
-    x = torch.zeros((g, n), dtype=torch.float32, device=DEV)
-    x.index_put_((gi, obs[ki]), values[gi, ki])
-    mask = torch.ones((g, n), dtype=torch.uint8, device=DEV)
-    mask[gi, obs[ki]] = 0
-    return x.reshape(-1), mask.reshape(-1)
-
-
-def numpy_reduce(x):
-    """Mean and sample standard deviation over axis 1 of fp32 ``x`` [C, M, N] as include/gatres.h states them: fp64 sums in
-    member order, written as loops (np.mean / np.std associate pairwise)."""
-    x = np.asarray(x, dtype=np.float32)
-    C, M, N = x.shape
-    acc = np.zeros((C, N), dtype=np.float64)
-    for m in range(M):
-        acc = acc + x[:, m].astype(np.float64)
-    mean64 = acc / np.float64(M)
-    sq = np.zeros((C, N), dtype=np.float64)
-    for m in range(M):
-        d = x[:, m].astype(np.float64) - mean64
-        sq = sq + d * d
-    sd = np.sqrt(sq / np.float64(M - 1)).astype(np.float32) if M > 1 else np.zeros((C, N), dtype=np.float32)
-    return mean64.astype(np.float32), sd
 
 
 # ---- 1. the draws -----------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 
 * ``gatres_grad_flow`` against fp64 torch on the tensors of the flat layout -- both sides sum exact fp64 products of fp32
   values, so each sum is off by at most n * 2^-53 <= 3.7e-12 for n <= 32 768: ``rtol = 1e-11``;
-* ``gatres_mean_abs_diff`` against ``(a - b).abs().double().mean()`` (n <= 4097 terms: ``rtol = 1e-12``);
+* ``gatres_mean_abs_diff`` against ``(a - b).abs().double().mean()`` (n <= 4097 terms: ``rtol = 1e-12``), and past the
+  kernel's first trip of 8192 elements against numpy within the reordering bound 2 n 2^-53;
 * ``GATResTrainer.gradient_flow()`` on the fused and the per-op path, with AutoClip, under bf16 storage;
 * ``fit(log_gradient=True, on_epoch=...)``: training untouched bit for bit, the report equal bit for bit to a hand-written loop
   over ``fit_epoch`` + ``gradient_flow()`` + ``gatres_mean_abs_diff``."""
@@ -14,6 +15,9 @@ import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+
+from turnover_cases import MEAN_ABS_DIFF_N      # noqa: E402
+
 DEV = "cuda:0"
 RTOL = 1e-11
 NODES, PIPES = 24, 28
@@ -97,8 +101,12 @@ def test_grad_flow_kernel_equals_fp64_torch(pkg, lib, nb, nc):
 
 
 # ---- 2. mean |a - b| ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 4097])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 4097] + MEAN_ABS_DIFF_N)
 def test_mean_abs_diff_equals_torch(pkg, lib, n):
+    """n <= 4097: one trip of the kernel's loop (GF_U * GF_T = 8192 elements), against torch within 1e-12.  The sizes of
+    tests/turnover_cases.py straddle the trip: against numpy on the host -- the difference in fp32, the sum in fp64 -- within
+    2 n 2^-53 relative (n non-negative terms that are exact in fp64: only the order of the additions can differ, and either
+    order is within (n - 1) 2^-53 of the exact sum)."""
     g = torch.Generator().manual_seed(n)
     a = (torch.randn(n, generator=g) * 3.0).float()
     b = (a + torch.randn(n, generator=g) * torch.logspace(-3, 0, n)).float()
@@ -106,8 +114,14 @@ def test_mean_abs_diff_equals_torch(pkg, lib, n):
     out = torch.full((3,), -7.25, dtype=torch.float64, device=DEV)
     assert lib.gatres_mean_abs_diff(da.data_ptr(), db.data_ptr(), n, out[1:].data_ptr(), None) == 0
     torch.cuda.synchronize()
-    want = float((a - b).abs().double().mean())
-    assert want > 0.0 and abs(float(out[1]) - want) <= 1e-12 * want, (float(out[1]), want)
+    if n in MEAN_ABS_DIFF_N:
+        d32 = a.numpy() - b.numpy()
+        assert d32.dtype == np.float32
+        want, bound = float(np.abs(d32).astype(np.float64).sum() / n), 2.0 * n * 2.0 ** -53
+    else:
+        want, bound = float((a - b).abs().double().mean()), 1e-12
+    print(f"n = {n}: relative difference {abs(float(out[1]) - want) / want:.3e} (bound {bound:.3e})")
+    assert want > 0.0 and abs(float(out[1]) - want) <= bound * want, (float(out[1]), want)
     assert float(out[0]) == -7.25 and float(out[2]) == -7.25
     assert lib.gatres_mean_abs_diff(da.data_ptr(), da.data_ptr(), n, out[1:].data_ptr(), None) == 0
     assert float(out[1].item()) == 0.0                                            # a == b: exactly 0
