@@ -6,8 +6,8 @@
 // reduction itself (reduce_adam_kernel<true>, k_fused_host.hip); elsewhere the gradient is complete already and
 // autoclip_norm_kernel below reads it.  The UPDATE launch, in every workgroup redundantly: sums the partials in a fixed
 // order (n), finds the rank of n in the sorted history (rounds of a 256-way search: no atomics, no spinning), forms the
-// percentile c and coef = min(1, c / (n + 1e-6)) in double, then applies Adam to its slice of the parameters with the
-// clipped gradient and writes its slice of the history's next sorted copy.  Block 0 appends n to the log and stores the
+// percentile c and coef = min(1, c / (n + 1e-6)) in double (NaN where the norm is not finite, as torch's clamp), then
+// applies Adam to its slice of the parameters with the clipped gradient and writes its slice of the history's next sorted copy.  Block 0 appends n to the log and stores the
 // counts; every other workgroup reads the snapshot only, so nothing in the launch waits for anything.
 #include "gatres_common.h"
 #include "k_autoclip.h"
@@ -124,8 +124,11 @@ __global__ __launch_bounds__(256) void autoclip_adam_kernel(const AutoClipUpdate
   const long long i1 = i0 + 1 < t ? i0 + 1 : t - 1;
   const double gam = h - (double)i0, va = sorted_at(i0), vb = sorted_at(i1), diff = vb - va;
   const double c = gam >= 0.5 ? vb - diff * (1.0 - gam) : va + diff * gam;
-  // torch.nn.utils.clip_grad_norm_(params, c): always multiplies, also by n / (n + 1e-6) when c >= n
-  const double coef_d = fmin(1.0, c / (n + 1e-6));
+  // torch.nn.utils.clip_grad_norm_(params, c): always multiplies, also by n / (n + 1e-6) when c >= n.  Its clamp(max=1) lets a
+  // NaN quotient through -- a norm that is not finite (an inf or NaN gradient entry) makes EVERY entry NaN, and Adam then every
+  // parameter -- which fmin(1, q) would turn into 1: an unclipped update of the finite entries
+  const double q = c / (n + 1e-6);
+  const double coef_d = q > 1.0 ? 1.0 : q;
   const float coef = (float)coef_d;
   if (blockIdx.x == 0 && tid == 0) {     // (nobody in this launch reads these words: the workgroups read the snapshot)
     a.log[cnt] = n;

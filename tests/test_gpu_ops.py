@@ -282,6 +282,10 @@ def _adam_against_torch(ops, P):
         opt.step()
         ops.adam_step(pd, (gr * (it + 1)).cuda(), m, v, step, 5e-4, 0.9, 0.999, 1e-8, 6e-6)
         assert relerr(pd, pt) < 1e-6
+        # the moments against torch's state (the same criterion: a handful of fp32 roundings of the largest entry; the
+        # element-by-element statement is test_gpu_adam_elementwise.py)
+        s = opt.state[pt]
+        assert relerr(m, s["exp_avg"]) < 1e-6 and relerr(v, s["exp_avg_sq"]) < 1e-6
     assert int(step[0]) == 3 and int(step[1]) == 0
 
 
