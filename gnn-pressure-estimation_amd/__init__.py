@@ -10,11 +10,14 @@ from .snapshot_store import SnapshotStore
 from .multi_snapshot_store import MultiSnapshotStore
 from .train_step import FitHistory, GATResTrainer, internal_train
 from .sensor_layout import sensor_layout_draws
-from .estimation import (ErrorBounds, PressureEstimator, conformal_rank, coverage_from_table, greedy_selection,
+from .estimation import (ErrorBounds, PressureEstimator, SensitivityMap, conformal_rank, coverage_from_table, greedy_selection,
                          layout_scores_from_table, node_error_bounds, observed_from_names, reading_noise)
+from .sensitivity import (influence_from_table, linear_spread_ref, sensitivity_fold_ref, sensitivity_rows_from_gx,
+                          sensitivity_seeds)
 
 __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "SimpleConv", "Linear", "GraphPlan", "PlanCache",
            "GATResTrainer", "FitHistory", "internal_train", "epoch_control", "select_model", "config_gatres_small", "config_gatres_large", "build_native", "wdn_synth", "dp", "evaluation", "wdn_io", "SnapshotStore",
            "MultiSnapshotStore", "estimation", "PressureEstimator", "observed_from_names", "reading_noise",
            "layout_scores_from_table", "greedy_selection", "sensor_layout_draws", "ErrorBounds", "conformal_rank",
-           "node_error_bounds", "coverage_from_table"]
+           "node_error_bounds", "coverage_from_table", "SensitivityMap", "influence_from_table", "linear_spread_ref",
+           "sensitivity_fold_ref", "sensitivity_rows_from_gx", "sensitivity_seeds"]

@@ -174,6 +174,11 @@ SIGNATURES = {
                                                 _I32, _P, _P]),
     "gatres_layout_pair_errors": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I64, _I32, _F64, _F64, _P, _P, _I64, _I64, _P]),
     "gatres_layout_error_reduce": (C.c_int, [_P, _I64, _I32, _P, _I32, _P]),
+    "gatres_stage_observed_targets": (C.c_int, [_P, _I32, _I64, _I64, _I32, _P, _I32, _I32, _P, _I32, _I32, _F64, _F64, _P, _P, _P,
+                                                _P, _I32, _P]),
+    "gatres_sensitivity_gather": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _I32, _F64, _P, _I64, _I64, _I64, _P]),
+    "gatres_sensitivity_fold": (C.c_int, [_P, _I64, _I32, _I32, _I64, _P, _I32, _P]),
+    "gatres_sensitivity_spread": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _P]),
     "gatres_version": (C.c_char_p, []),
 }
 
@@ -190,6 +195,7 @@ NODE_COVERAGE_RECORD = 1 + NODE_QUANTILE_MAX_LEVELS  # a record of gatres_node_b
 NODE_SPREAD_RECORD = 4                              # GATRES_NODE_SPREAD_RECORD (gatres_node_spread_moments)
 LAYOUT_PAIR_RECORD = 4                              # GATRES_LAYOUT_PAIR_RECORD (gatres_layout_pair_errors)
 LAYOUT_ERROR_RECORD = 4                             # GATRES_LAYOUT_ERROR_RECORD (gatres_layout_error_reduce)
+SENSITIVITY_RECORD = 5                              # GATRES_SENSITIVITY_RECORD (gatres_sensitivity_fold)
 CRITERIA = {"mse": LOSS_MSE, "mae": LOSS_MAE, "sce": LOSS_SCE}      # the reference's train.py --criterion choices
 
 

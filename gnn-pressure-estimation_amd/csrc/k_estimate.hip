@@ -67,6 +67,18 @@ struct ObsLayouts {
   int count;
 };
 
+// TARGETS (gatres_stage_observed_targets; always with AVAIL, never with NOISE or LAYOUTS): graph g is pair p = first_row + g of a
+// snapshot-major list of (source row, target) pairs -- source row p / count, target p % count -- staged as the launch with AVAIL
+// alone stages that row, and g_out gets the pair's seed: 1.0f at the target's node (nodes[p % count]; nodes == NULL: node
+// p % count), 0.0f at every other node, from the chunks that x_dst and mask are written from.  Every lane writes seeds, so the
+// division is taken once per graph by everyone (it is uniform over the workgroup).
+struct ObsTargets {
+  const int* nodes;        // [count] or NULL
+  float* g_out;            // [G * N]
+  int count;
+  int vec;                 // g_out is 16-byte aligned: whole chunks are one float4 store where x_dst's are
+};
+
 // One standard normal by Box-Muller from the 48 upper bits of one hash (gatres.h states the generator): u1 in (0, 1] and u2 in
 // [0, 1) are 24-bit integers times 2^-24, both exact in fp32.
 __device__ __forceinline__ uint64_t obs_noise_stream(uint64_t seed, uint64_t member) {
@@ -79,16 +91,17 @@ __device__ __forceinline__ float obs_noise(uint64_t stream, long long row, int K
   return __fmul_rn(sqrtf(__fmul_rn(-2.f, logf(u1))), cosf(__fmul_rn(6.283185307179586f, u2)));
 }
 
-template <bool AVAIL, bool NOISE, bool LAYOUTS>
+template <bool AVAIL, bool NOISE, bool LAYOUTS, bool TARGETS>
 __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __restrict__ src, int readings, long long src_rows,
                                                                const long long* __restrict__ rows, long long first_row, int N,
                                                                int G, const int* __restrict__ observed, int K, int mode,
                                                                float offset, float scale, float* __restrict__ x_dst,
                                                                uint8_t* __restrict__ mask, int vec,
                                                                const uint8_t* __restrict__ available, int nan_missing,
-                                                               ObsNoise nz, ObsLayouts lay) {
-  static_assert(AVAIL || !(NOISE || LAYOUTS), "the noisy and the layouts launch carry the availability arguments");
+                                                               ObsNoise nz, ObsLayouts lay, ObsTargets tg) {
+  static_assert(AVAIL || !(NOISE || LAYOUTS || TARGETS), "the noisy, the layouts and the targets launch carry the availability arguments");
   static_assert(!(NOISE && LAYOUTS), "noise combined with layouts is not built");
+  static_assert(!(TARGETS && (NOISE || LAYOUTS)), "targets combined with noise or layouts are not built");
   __shared__ int slot[OBS_TILE];
   const int tid = threadIdx.x;
   const int j = blockIdx.x * OBS_T + tid;
@@ -107,8 +120,15 @@ __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __re
     if (v0 >= N || v0 + 4 <= 0) continue;
     // (NOISE: the pair's row lies inside the matrix, the host checked the pair range; the 64-bit division is left to the lanes
     //  that hold a sensor)
-    long long row = (NOISE || LAYOUTS) ? 0 : (rows ? rows[g] : first_row + g);
-    const bool row_ok = NOISE || LAYOUTS || (row >= 0 && row < src_rows);   // (a row outside the matrix is not read: its nodes get 0)
+    long long row = (NOISE || LAYOUTS || TARGETS) ? 0 : (rows ? rows[g] : first_row + g);
+    const bool row_ok = NOISE || LAYOUTS || TARGETS || (row >= 0 && row < src_rows);   // (a row outside the matrix is not read: its nodes get 0)
+    int target = -1;                                                    // TARGETS: the node of the pair's seed
+    if (TARGETS) {
+      const long long pair = first_row + g;
+      row = pair / tg.count;
+      const int t = (int)(pair - row * tg.count);
+      target = tg.nodes ? tg.nodes[t] : t;
+    }
     uint64_t noise_stream = 0;
     unsigned draw = 0;                                                  // NOISE: the elements that hold a present reading
     const uint8_t* installed = nullptr;                                 // LAYOUTS: the pair's row of lay.on
@@ -163,6 +183,15 @@ __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __re
       st4(x_dst + base + v0, make_float4(val[0], val[1], val[2], val[3]));
       *reinterpret_cast<uint32_t*>(mask + base + v0) =
           (uint32_t)mk[0] | ((uint32_t)mk[1] << 8) | ((uint32_t)mk[2] << 16) | ((uint32_t)mk[3] << 24);
+      if (TARGETS) {
+        if (tg.vec) {
+          st4(tg.g_out + base + v0, make_float4(v0 == target ? 1.f : 0.f, v0 + 1 == target ? 1.f : 0.f,
+                                                v0 + 2 == target ? 1.f : 0.f, v0 + 3 == target ? 1.f : 0.f));
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) tg.g_out[base + v0 + e] = v0 + e == target ? 1.f : 0.f;
+        }
+      }
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -170,6 +199,7 @@ __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __re
         if (v >= 0 && v < N) {
           x_dst[base + v] = val[e];
           mask[base + v] = mk[e];
+          if (TARGETS) tg.g_out[base + v] = v == target ? 1.f : 0.f;
         }
       }
     }
@@ -556,13 +586,14 @@ static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint
   return a0 < b0 + nb && b0 < a0 + na;
 }
 
-// The checks and the launch of the staging entry points (AVAIL: with the availability arguments; NOISE / LAYOUTS: first_row is
-// the first pair, rows is NULL and nz / lay holds the noise / layout arguments).
-template <bool AVAIL, bool NOISE = false, bool LAYOUTS = false>
+// The checks and the launch of the staging entry points (AVAIL: with the availability arguments; NOISE / LAYOUTS / TARGETS:
+// first_row is the first pair, rows is NULL and nz / lay / tg holds the noise / layout / target arguments).
+template <bool AVAIL, bool NOISE = false, bool LAYOUTS = false, bool TARGETS = false>
 int stage_observed(const float* src, int32_t layout, int64_t src_rows, const int64_t* rows, int64_t first_row,
                    int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed, int32_t num_observed, int32_t normalise,
                    double offset, double factor, float* x_dst, uint8_t* mask, const uint8_t* available, int32_t nan_is_missing,
-                   void* stream, ObsNoise nz = ObsNoise{nullptr, 0, 0, 1}, ObsLayouts lay = ObsLayouts{nullptr, 1}) {
+                   void* stream, ObsNoise nz = ObsNoise{nullptr, 0, 0, 1}, ObsLayouts lay = ObsLayouts{nullptr, 1},
+                   ObsTargets tg = ObsTargets{nullptr, nullptr, 1, 0}) {
   if (!src || !observed || !x_dst || !mask || src == x_dst) return GATRES_E_BADARG;
   if (nodes_per_graph <= 0 || num_graphs <= 0 || num_observed <= 0 || num_observed > nodes_per_graph) return GATRES_E_BADARG;
   if ((int64_t)nodes_per_graph * num_graphs > INT32_MAX) return GATRES_E_BADARG;
@@ -582,10 +613,23 @@ int stage_observed(const float* src, int32_t layout, int64_t src_rows, const int
     const uint64_t total = (uint64_t)nodes_per_graph * (uint64_t)num_graphs;
     const uint64_t lay_bytes = (uint64_t)lay.count * (uint64_t)num_observed;
     if (bytes_overlap(lay.on, lay_bytes, x_dst, 4 * total) || bytes_overlap(lay.on, lay_bytes, mask, total)) return GATRES_E_BADARG;
+  } else if (TARGETS) {
+    // (pairs [first_row, first_row + num_graphs) of the src_rows * count there are; without nodes[] target t is node t)
+    if (!tg.g_out || tg.count < 1 || src_rows <= 0 || src_rows > INT64_MAX / tg.count) return GATRES_E_BADARG;
+    if (!tg.nodes && tg.count > nodes_per_graph) return GATRES_E_BADARG;
+    if (first_row < 0 || first_row > src_rows * tg.count - num_graphs) return GATRES_E_BADARG;
+    const uint64_t total = (uint64_t)nodes_per_graph * (uint64_t)num_graphs;
+    const uint64_t width = layout == GATRES_OBSERVED_READINGS ? (uint64_t)num_observed : (uint64_t)nodes_per_graph;
+    const uint64_t src_bytes = (uint64_t)src_rows > (uint64_t)INT64_MAX / 4 / width ? (uint64_t)INT64_MAX : 4 * (uint64_t)src_rows * width;
+    if (bytes_overlap(tg.g_out, 4 * total, x_dst, 4 * total) || bytes_overlap(tg.g_out, 4 * total, mask, total) ||
+        bytes_overlap(tg.g_out, 4 * total, src, src_bytes) ||
+        (tg.nodes && (bytes_overlap(tg.g_out, 4 * total, tg.nodes, 4 * (uint64_t)tg.count) ||
+                      bytes_overlap(tg.nodes, 4 * (uint64_t)tg.count, x_dst, 4 * total) ||
+                      bytes_overlap(tg.nodes, 4 * (uint64_t)tg.count, mask, total)))) return GATRES_E_BADARG;
   } else if (src_rows <= 0 || (!rows && (first_row < 0 || first_row > src_rows - num_graphs))) return GATRES_E_BADARG;
   if (normalise < GATRES_NORMALISE_NONE || normalise > GATRES_NORMALISE_RECIPROCAL) return GATRES_E_BADARG;
   if (AVAIL) {
-    if (!NOISE && !LAYOUTS && !available && !nan_is_missing) return GATRES_E_BADARG;
+    if (!NOISE && !LAYOUTS && !TARGETS && !available && !nan_is_missing) return GATRES_E_BADARG;
     // (available[src_rows][num_observed] must not overlap the bytes this launch writes)
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(available), a1 = a0 + (uintptr_t)src_rows * (uintptr_t)num_observed;
     const uintptr_t total = (uintptr_t)nodes_per_graph * (uintptr_t)num_graphs;
@@ -600,10 +644,11 @@ int stage_observed(const float* src, int32_t layout, int64_t src_rows, const int
   const int vec = gatres_aligned16(x_dst) && (reinterpret_cast<uintptr_t>(mask) & 3u) == 0;
   const int chunks = (nodes_per_graph + 3) / 4 + 1;
   const dim3 grid((chunks + OBS_T - 1) / OBS_T, num_graphs < OBS_MAX_GY ? num_graphs : OBS_MAX_GY);
-  hipLaunchKernelGGL((stage_observed_kernel<AVAIL, NOISE, LAYOUTS>), grid, dim3(OBS_T), 0, gatres_stream(stream), src,
+  tg.vec = vec && gatres_aligned16(tg.g_out);
+  hipLaunchKernelGGL((stage_observed_kernel<AVAIL, NOISE, LAYOUTS, TARGETS>), grid, dim3(OBS_T), 0, gatres_stream(stream), src,
                      (int)(layout == GATRES_OBSERVED_READINGS), (long long)src_rows, reinterpret_cast<const long long*>(rows),
                      (long long)first_row, (int)nodes_per_graph, (int)num_graphs, observed, (int)num_observed, (int)normalise,
-                     (float)offset, scale, x_dst, mask, vec, available, (int)(nan_is_missing != 0), nz, lay);
+                     (float)offset, scale, x_dst, mask, vec, available, (int)(nan_is_missing != 0), nz, lay, tg);
   return gatres_launch_status();
 }
 
@@ -727,6 +772,17 @@ extern "C" int gatres_stage_observed_layouts(const float* src, int32_t layout, i
   return stage_observed<true, false, true>(src, layout, src_rows, nullptr, first_pair, nodes_per_graph, num_graphs, observed,
                                            num_observed, normalise, offset, factor, x_dst, mask, available, nan_is_missing, stream,
                                            ObsNoise{nullptr, 0, 0, 1}, ObsLayouts{layouts, (int)num_layouts});
+}
+
+extern "C" int gatres_stage_observed_targets(const float* src, int32_t layout, int64_t src_rows, int64_t first_pair,
+                                             int32_t num_targets, const int32_t* targets, int32_t nodes_per_graph,
+                                             int32_t num_graphs, const int32_t* observed, int32_t num_observed, int32_t normalise,
+                                             double offset, double factor, float* x_dst, uint8_t* mask, float* g_out,
+                                             const uint8_t* available, int32_t nan_is_missing, void* stream) {
+  return stage_observed<true, false, false, true>(src, layout, src_rows, nullptr, first_pair, nodes_per_graph, num_graphs, observed,
+                                                  num_observed, normalise, offset, factor, x_dst, mask, available, nan_is_missing,
+                                                  stream, ObsNoise{nullptr, 0, 0, 1}, ObsLayouts{nullptr, 1},
+                                                  ObsTargets{targets, g_out, (int)num_targets, 0});
 }
 
 extern "C" int gatres_layout_pair_errors(const float* out, const uint8_t* mask, const float* truth, int64_t truth_rows,

@@ -37,6 +37,15 @@ of the error matrix, which is never formed or sorted); the ``ErrorBounds`` stay 
 with the calibration ones, ``p_v +- b_v`` holds with probability >= level, per junction.  ``coverage_report`` counts, on another
 store, how often it did (``gatres_node_bound_coverage``, one read-back); ``estimate_with_bounds`` and ``reading_residuals`` use the
 bounds.  ``conformal_rank`` / ``node_error_bounds`` / ``coverage_from_table`` restate all of it in numpy, without a device.
+
+Which sensor does an estimate rest on.  ``sensitivity`` / ``sensitivity_store`` give the Jacobian ``J[s, j, k] = d estimate_j /
+d reading_k`` in reverse mode: one graph of a batch carries ONE target junction, so the S * T (snapshot, target) pairs are one
+long pass with four launches per batch -- ``gatres_stage_observed_targets`` (the staging launch, which also writes the seeds
+``g_out = e_j``), ``gatres_model_forward`` keeping the activations, ``gatres_model_backward`` with ``g_x``, and
+``gatres_sensitivity_gather`` (the sensors' entries of ``g_x``, in physical units per physical unit, 0 where a reading is
+missing).  ``sensitivity_map`` folds the rows per (junction, sensor) over a store without ever forming ``[S, T, K]``
+(``gatres_sensitivity_fold``), ``influence_report`` reads that table back once, ``linear_spread`` is the first-order, noise-free
+counterpart of ``estimate_ensemble``'s standard deviation (``gatres_sensitivity_spread``).  sensitivity.py restates the launches.
 """
 from __future__ import annotations
 
@@ -49,6 +58,8 @@ import torch
 
 from . import _native
 from .evaluation import _enqueue_forward, _eval_plan
+from .sensitivity import (SENSITIVITY_RECORD, influence_from_table, linear_spread_ref, sensitivity_fold_ref,  # noqa: F401
+                          sensitivity_rows_from_gx, sensitivity_seeds)
 from .snapshot_store import SnapshotStore
 
 NODE_ERROR_RECORD = _native.NODE_ERROR_RECORD
@@ -468,6 +479,9 @@ class PressureEstimator:
         self._observed = torch.tensor(self.observed_idx, dtype=torch.int32).to(dev)
         self._sigma_cache = {}                      # layout -> (bytes, device sigma[K]) of the last noise_std: uploaded when it changes
         self._score_cache = None                    # (nodes, device score[N]) of the last score_nodes: uploaded when it changes
+        self._targets_cache = None                  # (targets, device int32[T]) of the last targets: uploaded when they change
+        self._sens_buffers = {}                     # plan key -> (saved, g_out, g_x, grads) of the sensitivity pass
+        self._sens_scratch = {}                     # name -> the pass's scratch matrix, kept while its shape stays
 
     @classmethod
     def for_store(cls, model, store, observed_idx, **kw) -> "PressureEstimator":
@@ -1020,3 +1034,258 @@ class PressureEstimator:
             mae[i], rmse[i], failed[i] = m["nonsensor_mae"], m["nonsensor_rmse"], m["mae"][self.observed_idx[k]]
         return {"sensors": cols, "baseline": baseline, "nonsensor_mae": mae, "nonsensor_rmse": rmse,
                 "failed_sensor_mae": failed, "delta_nonsensor_mae": mae - baseline["nonsensor_mae"]}
+
+    # ---- sensitivity ------------------------------------------------------------------------------------------------------------
+    def _targets(self, targets) -> Tuple[List[int], Optional[torch.Tensor]]:
+        """``targets`` (node indices; ``None``: every junction, in node order) as (list, device int32 ``[T]`` or ``None`` for
+        all); uploaded when they change."""
+        N = self.nodes_per_graph
+        if targets is None:
+            return list(range(N)), None
+        try:
+            nodes = [int(v) for v in targets]
+        except (TypeError, ValueError):
+            raise ValueError(f"targets must be node indices in [0, {N})") from None
+        bad = [v for v in nodes if v < 0 or v >= N]
+        if bad or not nodes:
+            raise ValueError(f"targets must be node indices in [0, {N}), at least one; got {bad[0] if bad else 'none'}")
+        key = tuple(nodes)
+        cached = self._targets_cache
+        if cached is None or cached[0] != key:
+            cached = self._targets_cache = (key, torch.tensor(nodes, dtype=torch.int32).to(self.device))
+        return nodes, cached[1]
+
+    def _sensitivity_buffers(self, P):
+        """The backward's buffers for the plan ``P``: the saved activations, the seeds, ``g_x`` and the throw-away parameter
+        gradient.  Allocated once per plan and kept."""
+        flat = self.model.flat_parameters
+        key = (P.num_nodes, int(P.state["saved_floats"]), int(flat.numel()))
+        bufs = self._sens_buffers.get(key)
+        if bufs is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            bufs = self._sens_buffers[key] = (torch.empty(P.state["saved_floats"], **f32), torch.empty(P.num_nodes, **f32),
+                                              torch.empty(P.num_nodes, **f32), torch.empty(flat.numel(), **f32))
+        return bufs
+
+    def _scratch(self, name: str, shape, dtype=torch.float32) -> torch.Tensor:
+        buf = self._sens_scratch.get(name)
+        if buf is None or tuple(buf.shape) != tuple(shape) or buf.dtype != dtype:
+            buf = self._sens_scratch[name] = torch.empty(tuple(shape), dtype=dtype, device=self.device)
+        return buf
+
+    def _sensitivity_launches(self, src: torch.Tensor, layout: int, normalise: int, targets_dev, T: int, available,
+                              nan_is_missing: bool):
+        """The four launches of one batch of (snapshot, target) pairs as a function ``batch(P, first_pair, g, J, J_rows,
+        J_first)``: stage the ``g`` pairs from ``first_pair`` on into the plan ``P`` with their seeds, run the forward keeping
+        the activations and the backward with ``g_x`` -- the two calls the module's autograd node enqueues, with the training
+        model reference and a throw-away parameter gradient --, gather the sensors' entries into rows ``J_first ...`` of ``J``."""
+        N, K, lib = self.nodes_per_graph, len(self.observed_idx), _native.load()
+        S = int(src.shape[0])
+        flat = self.model.flat_parameters
+        if flat.device != self.device:
+            raise ValueError(f"the model moved to {flat.device}; the estimator was built on {self.device}")
+        factor = self.std + self.eps if self.norm_type == "znorm" else 1.0
+        unit = self.scale / factor                              # d physical estimate / d physical reading per d out / d x
+        stream = _native.current_stream(self.device)
+        tail = (self._observed.data_ptr(), K, normalise, self.offset, factor)
+
+        def batch(P, first_pair, g, J, J_rows, J_first):
+            saved, g_out, g_x, grads = self._sensitivity_buffers(P)
+            st = P.state
+            _native.check(lib.gatres_stage_observed_targets(
+                src.data_ptr(), layout, S, first_pair, T, _native.ptr(targets_dev), N, g, *tail, P.x.data_ptr(),
+                P.mask.data_ptr(), g_out.data_ptr(), _native.ptr(available), int(bool(nan_is_missing)), stream),
+                "gatres_stage_observed_targets")
+            _native.check(lib.gatres_model_forward(st["mref"], st["gref"], flat.data_ptr(), P.x.data_ptr(), None,
+                                                   P.out.data_ptr(), saved.data_ptr(), st["scratch"].data_ptr(), stream),
+                          "gatres_model_forward")
+            _native.check(lib.gatres_model_backward(st["mref"], st["gref"], flat.data_ptr(), P.x.data_ptr(), None,
+                                                    g_out.data_ptr(), saved.data_ptr(), st["scratch"].data_ptr(),
+                                                    grads.data_ptr(), g_x.data_ptr(), stream), "gatres_model_backward")
+            # (fault: the last float of the parameter gradient, lin1.bias -- a NaN there marks a failed split launch)
+            _native.check(lib.gatres_sensitivity_gather(
+                g_x.data_ptr(), P.mask.data_ptr(), grads.data_ptr() + 4 * (grads.numel() - 1), N, g, self._observed.data_ptr(),
+                K, unit, J.data_ptr(), J_rows, K, J_first, stream), "gatres_sensitivity_gather")
+
+        return batch
+
+    def _sensitivity_plans(self, pairs: int):
+        bs = self.batch_size
+        sizes = {min(bs, pairs - first) for first in (0, (pairs - 1) // bs * bs)}
+        return {g: _eval_plan(self.model, self._topo, g) for g in sorted(sizes)}
+
+    def _run_sensitivity(self, src: torch.Tensor, layout: int, normalise: int, targets, available, nan_is_missing: bool,
+                         out: Optional[torch.Tensor]) -> torch.Tensor:
+        S, K, bs = int(src.shape[0]), len(self.observed_idx), self.batch_size
+        nodes, targets_dev = self._targets(targets)
+        T = len(nodes)
+        if available is not None:
+            self._check_available(available, S)
+        if out is None:
+            out = torch.empty((S, T, K), dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != self.device
+                or tuple(out.shape) != (S, T, K) or not out.is_contiguous()):
+            raise ValueError(f"out must be fp32 contiguous [{S}, {T}, {K}] on {self.device}")
+        self.model.eval()
+        with torch.cuda.device(self.device):
+            batch = self._sensitivity_launches(src, layout, normalise, targets_dev, T, available, nan_is_missing)
+            plans = self._sensitivity_plans(S * T)
+            for first in range(0, S * T, bs):
+                g = min(bs, S * T - first)
+                batch(plans[g], first, g, out, S * T, first)
+        return out
+
+    def _store_rows(self, store, first, count) -> Tuple[torch.Tensor, int]:
+        """The snapshots ``[first, first + count)`` of ``store`` (``count=None``: to the end) as a view of its matrix."""
+        self._check_store(store)
+        n = len(store)
+        for name, v in (("first", first), ("count", count)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise ValueError(f"{name} must be an integer; got {v!r}")
+        first = int(first)
+        count = n - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > n:
+            raise ValueError(f"first / count must name snapshots inside the store: [{first}, {first + count}) of {n}")
+        return store.data[first:first + count], count
+
+    def sensitivity(self, readings: torch.Tensor, *, targets=None, available: Optional[torch.Tensor] = None,
+                    nan_is_missing: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Which readings an estimate rests on, and by how much: the Jacobian ``J[s, t, k] = d p[s, targets[t]] / d
+        readings[s, k]`` of the model's prediction ``p`` (physical units) at the junction ``targets[t]`` with respect to the
+        reading of the sensor at ``observed_idx[k]`` (physical units), for every snapshot of ``readings`` (as in ``estimate``).
+        ``targets``: node indices (``None``: every junction, in node order).  Returns fp32 ``[S, T, K]`` (``out``: write it
+        there), a device tensor ordered on the current stream; nothing is read back.
+
+        The rows describe the MODEL'S PREDICTION at every node, sensor nodes included, whatever ``keep_observed`` says: the
+        self-entry ``J[s, t, k]`` at ``targets[t] == observed_idx[k]`` is how far the model's own prediction at a sensor
+        follows that sensor (with ``keep_observed`` the estimate there is the reading itself, whose derivative is trivially 1).
+        A missing reading (``available`` / ``nan_is_missing``, as in ``estimate``) is no input of that snapshot: its column is
+        exactly 0 there.  The network is piecewise linear in the readings up to the attention softmax, so ``J`` is the exact
+        derivative at these readings, not a finite difference.
+
+        Reverse mode: the S * T (snapshot, target) pairs, snapshot-major, are one long pass cut into batches of ``batch_size``
+        (a batch may straddle snapshots, the last one may be ragged), four launches per batch: ``gatres_stage_observed_targets``
+        (the staging of ``estimate`` plus the pair's seed ``e_j``), the forward keeping its activations, the backward with
+        ``g_x``, ``gatres_sensitivity_gather``.  A full Jacobian of one snapshot is ``ceil(N_g / batch_size)`` batches.  The
+        backward's buffers are allocated once per plan and kept on the estimator."""
+        self._check_readings(readings)
+        return self._run_sensitivity(readings, _native.OBSERVED_READINGS, self._normalise, targets, available, nan_is_missing, out)
+
+    def sensitivity_store(self, store, *, first: int = 0, count: Optional[int] = None, targets=None,
+                          available: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``sensitivity`` for the snapshots ``[first, first + count)`` of a ``SnapshotStore`` (``count=None``: to the end), with
+        everything but the sensors hidden; ``available``: ``[count, K]``, row ``i`` for snapshot ``first + i``.  In physical
+        units per physical unit, as ``sensitivity``."""
+        src, _ = self._store_rows(store, first, count)
+        return self._run_sensitivity(src, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, targets, available, False, out)
+
+    def sensitivity_map(self, store, *, first: int = 0, count: Optional[int] = None, targets=None,
+                        available: Optional[torch.Tensor] = None, max_scratch_bytes: int = 64 << 20) -> "SensitivityMap":
+        """The influence of the sensor layout over a store: ``sensitivity_store`` folded per (junction, sensor) over the
+        snapshots on the device -- the number of non-zero entries, sum J, sum \\|J\\|, sum J^2 and max \\|J\\|
+        (``gatres_sensitivity_fold``; ``influence_from_table`` reads the table).  The ``[S, T, K]`` tensor is never formed: the
+        pass runs in chunks of snapshots whose rows fit ``max_scratch_bytes`` (``ensemble_chunk``: whole snapshots and whole
+        batches, so the batches are those of ``sensitivity_store``), one fold per chunk in snapshot order: the bits of the
+        table depend on neither the budget nor the run.  Nothing is read back."""
+        src, S = self._store_rows(store, first, count)
+        if isinstance(max_scratch_bytes, bool) or int(max_scratch_bytes) <= 0:
+            raise ValueError("max_scratch_bytes must be positive")
+        nodes, targets_dev = self._targets(targets)
+        T, K, bs = len(nodes), len(self.observed_idx), self.batch_size
+        if available is not None:
+            self._check_available(available, S)
+        C = ensemble_chunk(S, T, bs, 4 * K, max_scratch_bytes)
+        table = torch.empty((T, K, SENSITIVITY_RECORD), dtype=torch.float64, device=self.device)
+        lib = _native.load()
+        self.model.eval()
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream(self.device)
+            batch = self._sensitivity_launches(src, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, targets_dev, T,
+                                               available, False)
+            J = self._scratch("map", (C * T, K))
+            plans = self._sensitivity_plans(S * T)
+            for s0 in range(0, S, C):                               # (s0 * T is a multiple of bs: a chunk starts a batch)
+                c = min(C, S - s0)
+                for off in range(0, c * T, bs):
+                    g = min(bs, c * T - off)
+                    batch(plans[g], s0 * T + off, g, J, C * T, off)
+                _native.check(lib.gatres_sensitivity_fold(J.data_ptr(), c, T, K, K, table.data_ptr(), int(s0 > 0), stream),
+                              "gatres_sensitivity_fold")
+        return SensitivityMap(table, nodes, self.observed_idx, S)
+
+    def influence_report(self, store_or_map, **kw) -> Dict[str, object]:
+        """``influence_from_table`` of a ``SensitivityMap`` -- or of ``sensitivity_map(store, **kw)`` when given a store: per
+        (junction, sensor) the mean, mean absolute and rms sensitivity, per junction the dominant sensor, its share and the
+        participation ratio, per sensor its total influence, the junctions it dominates and its self-entry.  ONE read-back:
+        the table."""
+        if isinstance(store_or_map, SensitivityMap) and kw:
+            raise ValueError("influence_report of a SensitivityMap takes no further arguments")
+        m = store_or_map if isinstance(store_or_map, SensitivityMap) else self.sensitivity_map(store_or_map, **kw)
+        return influence_from_table(m.table.cpu().numpy(), m.targets, m.observed_idx, m.num_snapshots)
+
+    def _run_linear_spread(self, src: torch.Tensor, layout: int, normalise: int, noise_std, available, nan_is_missing: bool,
+                           out: Optional[torch.Tensor]) -> torch.Tensor:
+        S, N, K = int(src.shape[0]), self.nodes_per_graph, len(self.observed_idx)
+        # (J is in physical units per PHYSICAL unit of a reading in both layouts: sigma in physical units)
+        sigma = self._sigma(noise_std, _native.OBSERVED_READINGS)
+        out = self._result(S, out)
+        J = self._run_sensitivity(src, layout, normalise, None, available, nan_is_missing, self._scratch("spread", (S, N, K)))
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().gatres_sensitivity_spread(J.data_ptr(), S * N, K, K, sigma.data_ptr(), out.data_ptr(),
+                                                                   _native.current_stream(self.device)),
+                          "gatres_sensitivity_spread")
+        return out
+
+    def linear_spread(self, readings: torch.Tensor, noise_std, *, available: Optional[torch.Tensor] = None,
+                      nan_is_missing: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The FIRST-ORDER spread of the estimates under independent reading errors of standard deviation ``noise_std``
+        (physical units; one value or K, as in ``estimate``): ``sqrt(sum_k (J[s, j, k] * noise_std[k])^2)`` per junction, fp32
+        ``[S, N_g]`` in physical units (``out``: write it there), from ``sensitivity`` over every junction and one
+        ``gatres_sensitivity_spread`` launch.  A missing reading contributes nothing.  As ``sensitivity``, it describes the
+        model's prediction at every node, sensor nodes included.
+
+        It is the linearised, noise-free counterpart of ``estimate_ensemble``'s standard deviation: no seed, no sampling error
+        (M members carry a relative error of about ``1 / sqrt(2 (M - 1))``), but only the first order -- where the noise carries
+        a reading across a kink of the network the two differ.  Cost per snapshot: ``ceil(N_g / batch_size)`` batches of a
+        forward AND a backward, against ``ceil(M / batch_size)`` forwards of the ensemble: the ensemble is cheaper whenever
+        ``M < N_g``.  The ``[S, N_g, K]`` Jacobian is a scratch kept on the estimator."""
+        self._check_readings(readings)
+        return self._run_linear_spread(readings, _native.OBSERVED_READINGS, self._normalise, noise_std, available,
+                                       nan_is_missing, out)
+
+    def linear_spread_store(self, store, noise_std, *, first: int = 0, count: Optional[int] = None,
+                            available: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``linear_spread`` for the snapshots ``[first, first + count)`` of a ``SnapshotStore`` (noise in physical units)."""
+        src, _ = self._store_rows(store, first, count)
+        return self._run_linear_spread(src, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, noise_std, available, False, out)
+
+
+class SensitivityMap:
+    """The folded sensitivities of a sensor layout over ``num_snapshots`` snapshots: ``table`` fp64 ``[T, K,
+    SENSITIVITY_RECORD]`` on the device (per junction ``targets[t]`` and sensor ``observed_idx[k]``: the entries that are not 0,
+    sum J, sum \\|J\\|, sum J^2, max \\|J\\|).  ``influence_from_table`` / ``PressureEstimator.influence_report`` read it."""
+
+    def __init__(self, table: torch.Tensor, targets, observed_idx, num_snapshots: int):
+        self.targets = [int(v) for v in targets]
+        self.observed_idx = [int(v) for v in observed_idx]
+        self.num_snapshots = int(num_snapshots)
+        if (not isinstance(table, torch.Tensor) or table.dtype != torch.float64
+                or tuple(table.shape) != (len(self.targets), len(self.observed_idx), SENSITIVITY_RECORD)):
+            raise ValueError(f"table must be fp64 [{len(self.targets)}, {len(self.observed_idx)}, {SENSITIVITY_RECORD}]")
+        if self.num_snapshots < 1:
+            raise ValueError("num_snapshots must be positive")
+        self.table = table
+
+    @property
+    def device(self) -> torch.device:
+        return self.table.device
+
+    def state_dict(self) -> Dict[str, object]:
+        """Plain values and a CPU tensor, for ``torch.save``."""
+        return {"table": self.table.detach().cpu(), "targets": list(self.targets), "observed_idx": list(self.observed_idx),
+                "num_snapshots": self.num_snapshots}
+
+    @classmethod
+    def from_state_dict(cls, d, device=None) -> "SensitivityMap":
+        table = torch.as_tensor(d["table"], dtype=torch.float64)
+        return cls(table if device is None else table.to(device), d["targets"], d["observed_idx"], d["num_snapshots"])

@@ -1054,6 +1054,71 @@ int gatres_layout_pair_errors(const float* out, const uint8_t* mask, const float
 int gatres_layout_error_reduce(const double* rec, int64_t num_snapshots, int32_t num_layouts, double* table, int32_t accumulate,
                                void* stream);
 
+/* Sensitivity of the estimates to each sensor reading (symbols only: the ABI stays; k_sensitivity.hip).  The Jacobian
+ * J[j][k] = d estimate_j / d reading_k in reverse mode: one graph of a batch carries ONE target junction j, its seed is
+ * g_out = e_j, and g_x = d out_j / d x of gatres_model_backward at the sensor nodes is row j of J.  Computing T rows for each of
+ * S snapshots is one long pass over (snapshot, target) PAIRS, snapshot-major: pair p is source row p / T and target p % T.  Per
+ * batch of pairs: gatres_stage_observed_targets, gatres_model_forward with a saved buffer, gatres_model_backward with g_x,
+ * gatres_sensitivity_gather.
+ *
+ * gatres_stage_observed_targets: the kernel of gatres_stage_observed_available compiled with the targets as one more compile-time
+ * fact.  The arguments, the source layouts and the checks of gatres_stage_observed_layouts, without layouts, and
+ *   first_pair   graph g of the launch is pair p = first_pair + g: it reads source row p / num_targets (of src and of available)
+ *                and is staged exactly as gatres_stage_observed_available stages that row (with available == NULL and
+ *                nan_is_missing == 0, legal here: as gatres_stage_observed stages it).
+ *                0 <= first_pair, first_pair + num_graphs <= src_rows * num_targets.
+ *   num_targets  T >= 1
+ *   targets      device int32 [T], each in [0, N): target t is node targets[t].  NULL: target t is node t, which needs T <= N.
+ *                A value outside [0, N) seeds nothing (its graph's g_out is all zero).
+ *   g_out        device float [num_graphs * N]:  g_out[g * N + v] = (v == target(p % T)) ? 1.0f : 0.0f
+ * Every float of x_dst and g_out and every byte of mask of the batch is written exactly once, from the same chunks of the same
+ * grid: no memset beforehand.  g_out is stored 16 bytes at a time where x_dst is and g_out is aligned so, element by element
+ * otherwise.  GATRES_E_BADARG before any launch: whatever gatres_stage_observed_layouts refuses of the arguments they share, a
+ * NULL g_out, a g_out that overlaps x_dst, mask, src or targets, targets overlapping x_dst or mask, num_targets < 1, a NULL
+ * targets with num_targets > N, a pair range outside [0, src_rows * num_targets). */
+int gatres_stage_observed_targets(const float* src, int32_t layout, int64_t src_rows, int64_t first_pair, int32_t num_targets,
+                                  const int32_t* targets, int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed,
+                                  int32_t num_observed, int32_t normalise, double offset, double factor, float* x_dst,
+                                  uint8_t* mask, float* g_out, const uint8_t* available, int32_t nan_is_missing, void* stream);
+
+/* One batch's rows of J[J_rows][J_stride] (device float), one launch.  g_x, mask: [num_graphs * N], the backward's input
+ * gradient and the staged mask of the batch; observed[num_observed] as in gatres_stage_observed.  For g in [0, num_graphs),
+ * k in [0, K):
+ *   J[(first_row + g) * J_stride + k] = mask[g*N + observed[k]] ? 0.0f : fp32(g_x[g*N + observed[k]] * (float)unit)
+ * one fp32 product, rounded once.  The mask decides: the fused kernels write g_x at every node, so the entry of a sensor that is
+ * missing or hidden means nothing and reads as exactly 0, whatever it holds (a NaN included).  unit = scale / factor of the
+ * descale and of the normalisation turns d out / d x into physical units per physical unit.
+ *   fault   device float, may be NULL.  When *fault is a NaN, every J of the batch is a NaN.  The caller passes the last float
+ *           of the backward's parameter gradient (lin1.bias), which a split launch whose partner never arrived turns into NaN
+ *           (see the fused per-snapshot path above).
+ * Nothing outside the batch's rows and the K columns is written.  GATRES_E_BADARG before any launch: a NULL g_x, mask, observed
+ * or J, num_observed outside [1, N], J_stride < num_observed, rows outside [0, J_rows), the batch's rows of J overlapping g_x,
+ * mask, observed or fault. */
+int gatres_sensitivity_gather(const float* g_x, const uint8_t* mask, const float* fault, int32_t nodes_per_graph,
+                              int32_t num_graphs, const int32_t* observed, int32_t num_observed, double unit, float* J,
+                              int64_t J_rows, int64_t J_stride, int64_t first_row, void* stream);
+
+/* The rows of num_snapshots * num_targets pairs, pair-major (J[(s * T + t)][J_stride]), folded into
+ * table[T][K][GATRES_SENSITIVITY_RECORD] (device double).  Per (t, k), strictly in the order s = 0 .. num_snapshots - 1, with
+ * j = (double)J[(s * T + t) * J_stride + k]:
+ *   [0] += 1 where j != 0 (a NaN counts)   [1] += j   [2] += |j|   [3] += j * j   [4] = fmax([4], |j|)
+ * from zero when accumulate == 0, from the table's current record otherwise: a pass cut into chunks of snapshots (the first
+ * launch with accumulate == 0, the others with 1) leaves the bits of one launch over all of them.  fp64, no contraction, no
+ * atomics; one lane per (t, k), consecutive lanes read consecutive floats.  GATRES_E_BADARG before any launch: a NULL pointer,
+ * num_snapshots < 1, num_targets < 1, num_observed < 1, J_stride < num_observed, J overlapping table. */
+#define GATRES_SENSITIVITY_RECORD 5
+int gatres_sensitivity_fold(const float* J, int64_t num_snapshots, int32_t num_targets, int32_t num_observed, int64_t J_stride,
+                            double* table, int32_t accumulate, void* stream);
+
+/* The first-order spread of every row of J[rows][J_stride] under independent reading errors of standard deviation
+ * sigma[num_observed] (device float, in the units of the readings J was formed for):
+ *   out[r] = (float)sqrt(sum_k ((double)J[r][k] * (double)sigma[k])^2)
+ * summed in the order k = 0 .. K - 1, in fp64, every operation rounded once (the product of two floats is exact in fp64), without
+ * contraction and without atomics, as gatres_ensemble_reduce sums: the same bits on every run.  GATRES_E_BADARG before any
+ * launch: a NULL pointer, rows < 1, num_observed < 1, J_stride < num_observed, J, sigma and out overlapping one another. */
+int gatres_sensitivity_spread(const float* J, int64_t rows, int32_t num_observed, int64_t J_stride, const float* sigma, float* out,
+                              void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
