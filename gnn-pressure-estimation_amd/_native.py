@@ -179,6 +179,8 @@ SIGNATURES = {
     "gatres_sensitivity_gather": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _I32, _F64, _P, _I64, _I64, _I64, _P]),
     "gatres_sensitivity_fold": (C.c_int, [_P, _I64, _I32, _I32, _I64, _P, _I32, _P]),
     "gatres_sensitivity_spread": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _P]),
+    "gatres_loo_residuals": (C.c_int, [_P, _P, _P, _I32, _I64, _I64, _I32, _I32, _P, _I32, _F64, _F64, _P, _I32, _P, _P, _P]),
+    "gatres_screen_reject": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "gatres_version": (C.c_char_p, []),
 }
 

@@ -46,6 +46,15 @@ long pass with four launches per batch -- ``gatres_stage_observed_targets`` (the
 missing).  ``sensitivity_map`` folds the rows per (junction, sensor) over a store without ever forming ``[S, T, K]``
 (``gatres_sensitivity_fold``), ``influence_report`` reads that table back once, ``linear_spread`` is the first-order, noise-free
 counterpart of ``estimate_ensemble``'s standard deviation (``gatres_sensitivity_spread``).  sensitivity.py restates the launches.
+
+A reading that is present and wrong.  ``loo_residuals`` / ``loo_residuals_store`` give every reading's LEAVE-ONE-OUT residual,
+the reading against the model's prediction at its node with that one sensor hidden: "every sensor but k" is a layout, so the
+S * K (snapshot, left-out sensor) pairs are one long pass with three launches per batch -- ``gatres_stage_observed_layouts``
+with the K x K layouts "all ones, zero diagonal", the forward and ``gatres_loo_residuals`` -- and no ``[S, N]`` matrix.
+``calibrate_screening`` turns the residuals of a held-out store into per-sensor split-conformal bounds (``ScreeningBounds``; one
+``gatres_node_error_quantiles`` launch on the ``[S, K]`` matrices), ``screen`` rejects, per snapshot and round, the available
+sensor that exceeds its bound by the largest factor (``gatres_screen_reject``), ``estimate_screened`` estimates without the
+rejected readings, ``screening_report`` back-tests all of it with planted faults.  screening.py restates the launches.
 """
 from __future__ import annotations
 
@@ -60,6 +69,8 @@ from . import _native
 from .evaluation import _enqueue_forward, _eval_plan
 from .sensitivity import (SENSITIVITY_RECORD, influence_from_table, linear_spread_ref, sensitivity_fold_ref,  # noqa: F401
                           sensitivity_rows_from_gx, sensitivity_seeds)
+from .screening import (fault_draws, loo_layouts, loo_residuals_from_estimates, screen_ref, screen_reject_ref,  # noqa: F401
+                        screening_rates)
 from .snapshot_store import SnapshotStore
 
 NODE_ERROR_RECORD = _native.NODE_ERROR_RECORD
@@ -356,6 +367,65 @@ class ErrorBounds:
         return cls(d["levels"], bounds, counts, d["observed_idx"])
 
 
+class ScreeningBounds:
+    """Calibrated bounds on the leave-one-out residuals of a sensor set: ``levels`` (a tuple of floats), ``bounds`` (fp32
+    ``[Q, K]``: ``|reading - leave-one-out prediction| <= bounds[q, k]`` for sensor ``observed_idx[k]`` with probability >=
+    ``levels[q]`` while every other reading is present; +inf: too few calibration samples), ``counts`` (fp64 ``[K]``: the samples
+    behind each sensor's bounds) and ``observed_idx``.  ``calibrate_screening`` leaves the tensors on the device; arrays are taken
+    too (``device``: where to put them).  ``inverse`` is ``float32(1) / bounds`` formed in numpy on the host (so that the
+    statement of ``gatres_screen_reject`` holds no device division) the first time it is asked for -- one read-back of ``bounds``,
+    once -- and kept."""
+
+    def __init__(self, levels, bounds, counts, observed_idx, device=None):
+        self.levels = _check_levels(levels)
+        self.observed_idx = [int(i) for i in observed_idx]
+        if not isinstance(bounds, torch.Tensor):
+            bounds = torch.from_numpy(np.ascontiguousarray(bounds, dtype=np.float32))
+        if not isinstance(counts, torch.Tensor):
+            counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.float64))
+        if device is not None:
+            bounds, counts = bounds.to(device), counts.to(device)
+        Q, K = len(self.levels), len(self.observed_idx)
+        if bounds.dtype != torch.float32 or tuple(bounds.shape) != (Q, K) or not bounds.is_contiguous():
+            raise ValueError(f"bounds must be fp32 contiguous [{Q}, {K}]: one row per level, one column per sensor")
+        if counts.dtype != torch.float64 or tuple(counts.shape) != (K,) or counts.device != bounds.device:
+            raise ValueError(f"counts must be fp64 [{K}] on {bounds.device}")
+        self.bounds, self.counts = bounds, counts
+        self._inverse = None
+
+    @property
+    def device(self) -> torch.device:
+        return self.bounds.device
+
+    def level_index(self, level=None) -> int:
+        """The row of ``bounds`` for ``level``: an exact match of a stored level (``None``: the only one)."""
+        if level is None:
+            if len(self.levels) != 1:
+                raise ValueError(f"level=None needs bounds with one level; these hold {self.levels}")
+            return 0
+        if float(level) not in self.levels:
+            raise ValueError(f"level {level!r} is not one of the calibrated levels {self.levels}")
+        return self.levels.index(float(level))
+
+    @property
+    def inverse(self) -> torch.Tensor:
+        if self._inverse is None:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                inv = (np.float32(1.0) / self.bounds.detach().cpu().numpy()).astype(np.float32)
+            self._inverse = torch.from_numpy(inv).to(self.device)
+        return self._inverse
+
+    def state_dict(self) -> Dict[str, object]:
+        """CPU tensors and plain lists (one read-back of each tensor), for ``torch.save``."""
+        return {"levels": list(self.levels), "bounds": self.bounds.detach().cpu(), "counts": self.counts.detach().cpu(),
+                "observed_idx": list(self.observed_idx)}
+
+    @classmethod
+    def from_state_dict(cls, d, device=None) -> "ScreeningBounds":
+        return cls(d["levels"], torch.as_tensor(d["bounds"], dtype=torch.float32).contiguous(),
+                   torch.as_tensor(d["counts"], dtype=torch.float64), d["observed_idx"], device=device)
+
+
 def greedy_selection(score_round, candidates: Sequence[int], num: int) -> Tuple[List[int], List[float]]:
     """Greedy forward selection of ``num`` of ``candidates``.  Each round calls ``score_round(chosen, remaining)`` -- the
     candidates chosen so far in order of choice, and the others in ``candidates`` order -- which returns one score per
@@ -482,6 +552,7 @@ class PressureEstimator:
         self._targets_cache = None                  # (targets, device int32[T]) of the last targets: uploaded when they change
         self._sens_buffers = {}                     # plan key -> (saved, g_out, g_x, grads) of the sensitivity pass
         self._sens_scratch = {}                     # name -> the pass's scratch matrix, kept while its shape stays
+        self._loo_layouts = None                    # device uint8 [K, K] of the leave-one-out pass: all ones, zero diagonal
 
     @classmethod
     def for_store(cls, model, store, observed_idx, **kw) -> "PressureEstimator":
@@ -1258,6 +1329,225 @@ class PressureEstimator:
         """``linear_spread`` for the snapshots ``[first, first + count)`` of a ``SnapshotStore`` (noise in physical units)."""
         src, _ = self._store_rows(store, first, count)
         return self._run_linear_spread(src, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, noise_std, available, False, out)
+
+    # ---- screening: a reading that is present and wrong ---------------------------------------------------------------------------
+    def _loo_ready(self) -> int:
+        K = len(self.observed_idx)
+        if K < 2:
+            raise ValueError(f"leave-one-out residuals need at least two sensors; the estimator has {K}")
+        if self._loo_layouts is None:                               # (built once per estimator)
+            self._loo_layouts = torch.from_numpy(loo_layouts(K)).to(self.device)
+        return K
+
+    def _run_loo(self, src: torch.Tensor, layout: int, normalise: int, available, nan_is_missing: bool, resid: torch.Tensor,
+                 pred: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The leave-one-out pass over the S * K (snapshot, left-out sensor) pairs of ``src`` into ``resid`` / ``pred``
+        (``[S, K]``): per batch ``gatres_stage_observed_layouts`` under the layouts "all ones, zero diagonal", the forward,
+        ``gatres_loo_residuals``."""
+        S, N, K, bs = int(src.shape[0]), self.nodes_per_graph, len(self.observed_idx), self.batch_size
+        lib, flat, layouts = _native.load(), self.model.flat_parameters, self._loo_layouts
+        if flat.device != self.device:
+            raise ValueError(f"the model moved to {flat.device}; the estimator was built on {self.device}")
+        factor = self.std + self.eps if self.norm_type == "znorm" else 1.0
+        nan = int(bool(nan_is_missing))
+        self.model.eval()
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream(self.device)
+            plans = self._sensitivity_plans(S * K)
+            for first in range(0, S * K, bs):
+                g = min(bs, S * K - first)
+                P = plans[g]
+                _native.check(lib.gatres_stage_observed_layouts(
+                    src.data_ptr(), layout, S, first, K, N, g, self._observed.data_ptr(), K, normalise, self.offset, factor,
+                    P.x.data_ptr(), P.mask.data_ptr(), _native.ptr(available), nan, layouts.data_ptr(), stream),
+                    "gatres_stage_observed_layouts")
+                _enqueue_forward(lib, flat, P, stream)
+                _native.check(lib.gatres_loo_residuals(
+                    P.out.data_ptr(), P.mask.data_ptr(), src.data_ptr(), layout, S, first, N, g, self._observed.data_ptr(), K,
+                    self.scale, self.offset, _native.ptr(available), nan, pred.data_ptr(), resid.data_ptr(), stream),
+                    "gatres_loo_residuals")
+        return resid, pred
+
+    def loo_residuals(self, readings: torch.Tensor, *, available: Optional[torch.Tensor] = None,
+                      nan_is_missing: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Is a reading plausible given the others?  ``(resid, pred)``, fp32 ``[S, K]`` on the device, in physical units:
+        ``pred[s, k]`` is the model's prediction at node ``observed_idx[k]`` from every reading of snapshot ``s`` but that one,
+        ``resid[s, k] = readings[s, k] - pred[s, k]``.  ``readings``, ``available``, ``nan_is_missing`` as in ``estimate``; a
+        reading that is not there has a NaN residual (its ``pred`` is still the prediction from the others).  The numbers are
+        those of ``reading_residuals``, bit for bit, from ONE pass: the S * K (snapshot, left-out sensor) pairs, snapshot-major,
+        are cut into batches of ``batch_size`` once, from pair 0 (a batch may straddle snapshots, the last may be ragged), three
+        launches per batch -- ``gatres_stage_observed_layouts`` with the layouts "all ones, zero diagonal", the forward,
+        ``gatres_loo_residuals``.  No ``[S, N]`` matrix is written, nothing is read back, and the two results are a scratch
+        kept on the estimator: nothing is allocated after the first call, and the next call of this method overwrites them
+        (``clone()`` what must outlive it).  Needs K >= 2."""
+        self._check_readings(readings)
+        K, S = self._loo_ready(), int(readings.shape[0])
+        if available is not None:
+            self._check_available(available, S)
+        return self._run_loo(readings, _native.OBSERVED_READINGS, self._normalise, available, nan_is_missing,
+                             self._scratch("loo_resid", (S, K)), self._scratch("loo_pred", (S, K)))
+
+    def loo_residuals_store(self, store, *, available: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``loo_residuals`` for every snapshot of a ``SnapshotStore``: the readings are the store's values at the sensors
+        (descaled as ``gatres_estimate_write`` descales), everything else is hidden."""
+        self._check_store(store)
+        K, S = self._loo_ready(), len(store)
+        if available is not None:
+            self._check_available(available, S)
+        return self._run_loo(store.data, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, available, False,
+                             self._scratch("loo_resid", (S, K)), self._scratch("loo_pred", (S, K)))
+
+    def calibrate_screening(self, store, levels=(0.99,), *, available: Optional[torch.Tensor] = None) -> ScreeningBounds:
+        """Split-conformal bounds on the leave-one-out residuals, per sensor, from a held-out ``store`` (not the training
+        data): one ``loo_residuals_store`` pass and one ``gatres_node_error_quantiles`` launch on the ``[S, K]`` matrices --
+        ``pred`` as the estimates, the store's values at the sensors as the truth, the K sensors as the K "nodes".  For every
+        level ``q`` (1 to 8 floats in (0, 1), strictly increasing) and sensor ``k`` the element of rank ``conformal_rank(n_k,
+        q)`` of ``|reading - leave-one-out prediction|`` over the ``n_k`` snapshots in which the reading was there
+        (``available``: ``[len(store), K]``; a missing reading is left out through that launch's own rule for counted
+        entries).  In numpy: ``node_error_bounds(pred, reading, levels, hidden=present)``.  It replaces K ``calibrate_bounds``
+        calls with hand-built ``available`` matrices, and gives their values at the sensor nodes.  If a new snapshot is
+        exchangeable with the store's and every other reading is present and right, a right reading of sensor ``k`` exceeds
+        ``bounds[q, k]`` with probability <= 1 - q.  Nothing is read back."""
+        lv = _check_levels(levels)
+        _, pred = self.loo_residuals_store(store, available=available)
+        S, K, Q = len(store), len(self.observed_idx), len(lv)
+        truth = store.data.index_select(1, self._observed).contiguous()          # (scaled: the launch descales it as the pass did)
+        sensors = torch.arange(K, dtype=torch.int32, device=self.device)
+        missing = None if available is None else (available == 0).to(torch.uint8)  # (counted: unless that entry is non-zero)
+        bounds = torch.empty((Q, K), dtype=torch.float32, device=self.device)
+        counts = torch.empty((K,), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().gatres_node_error_quantiles(
+                pred.data_ptr(), truth.data_ptr(), S, K, self.scale, self.offset, sensors.data_ptr(), K, _native.ptr(missing),
+                (ctypes.c_double * Q)(*lv), Q, bounds.data_ptr(), counts.data_ptr(), _native.current_stream(self.device)),
+                "gatres_node_error_quantiles")
+        return ScreeningBounds(lv, bounds, counts, self.observed_idx)
+
+    def _check_screening(self, bounds, level, max_reject, min_sensors) -> Tuple[int, int, int]:
+        K = len(self.observed_idx)
+        if not isinstance(bounds, ScreeningBounds):
+            raise ValueError("bounds must be the ScreeningBounds of calibrate_screening")
+        if bounds.observed_idx != self.observed_idx:
+            raise ValueError(f"the bounds were calibrated for the sensors {bounds.observed_idx}, the estimator's are "
+                             f"{self.observed_idx}")
+        if bounds.device != self.device:
+            raise ValueError(f"the bounds must be on {self.device} (got {bounds.device})")
+        for name, v, lo, hi in (("max_reject", max_reject, 1, None), ("min_sensors", min_sensors, 1, K)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+                raise ValueError(f"{name} must be an integer in [{lo}, {'...' if hi is None else hi}]; got {v!r}")
+        return bounds.level_index(level), int(max_reject), int(min_sensors)
+
+    def screen(self, readings: torch.Tensor, bounds: ScreeningBounds, level=None, *, max_reject: int = 1, min_sensors: int = 1,
+               available: Optional[torch.Tensor] = None,
+               nan_is_missing: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Which readings are not to be believed?  ``max_reject`` rounds of one ``loo_residuals`` pass under the current
+        availability and one ``gatres_screen_reject``: in every snapshot the available sensor whose ``|residual|`` exceeds its
+        bound ``bounds[level, k]`` by the largest factor (ties: the first) is taken out, as long as ``min_sensors`` readings
+        stay.  ONE rejection per round on purpose: a wrong reading also bends the leave-one-out predictions of its
+        neighbours, so the largest standardised residual goes first and the others are judged again without it.  Returns
+        ``(available_out [S, K] uint8, rejected [S, max_reject] int32`` (column ``r``: the sensor round ``r`` rejected, -1:
+        none), ``resid0 [S, K], flagged0 [S, K] uint8)``; the last two are round 0's residuals and its exceedances (what
+        ``reading_residuals`` returns).  All on the device, nothing read back (but the bounds' ``inverse`` the first time they
+        are used); the results are a scratch kept on the estimator, overwritten by the next ``screen`` / ``estimate_screened``.
+
+        The bounds are calibrated with every OTHER reading present.  From round 1 on they are applied under an availability
+        that a rejection has changed (and, with ``available`` gaps, in round 0 too): the coverage statement of
+        ``calibrate_screening`` holds for round 0 of complete readings only; later rounds are a heuristic with the same
+        numbers.  A round after a clean round repeats it and rejects nothing: skipping it would need a read-back."""
+        self._check_readings(readings)
+        K, S = self._loo_ready(), int(readings.shape[0])
+        qi, R, min_sensors = self._check_screening(bounds, level, max_reject, min_sensors)
+        if available is not None:
+            self._check_available(available, S)
+        bound, inv = bounds.bounds[qi], bounds.inverse[qi]
+        avail = self._scratch("screen_available", (S, K), torch.uint8)
+        rejected = self._scratch("screen_rejected", (S, R), torch.int32)
+        resid0, flagged0 = self._scratch("screen_resid0", (S, K)), self._scratch("screen_flagged0", (S, K), torch.uint8)
+        later, pred = (self._scratch("screen_resid", (S, K)) if R > 1 else None), self._scratch("screen_pred", (S, K))
+        if available is None:
+            avail.fill_(1)
+        else:
+            avail.copy_(available)
+        lib = _native.load()
+        for rnd in range(R):
+            resid = resid0 if rnd == 0 else later
+            self._run_loo(readings, _native.OBSERVED_READINGS, self._normalise, avail, nan_is_missing, resid, pred)
+            with torch.cuda.device(self.device):
+                _native.check(lib.gatres_screen_reject(
+                    resid.data_ptr(), bound.data_ptr(), inv.data_ptr(), avail.data_ptr(), S, K, min_sensors, rnd, R,
+                    rejected.data_ptr(), flagged0.data_ptr() if rnd == 0 else None, _native.current_stream(self.device)),
+                    "gatres_screen_reject")
+        return avail, rejected, resid0, flagged0
+
+    def estimate_screened(self, readings: torch.Tensor, bounds: ScreeningBounds, level=None, *,
+                          out: Optional[torch.Tensor] = None, max_reject: int = 1, min_sensors: int = 1,
+                          available: Optional[torch.Tensor] = None,
+                          nan_is_missing: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Readings in; estimates, and which sensors were not believed, out: ``screen`` and then the ordinary three-launch
+        ``estimate`` pass with ``available_out``.  Returns ``(est [S, N_g], rejected [S, max_reject] int32)``; ``out`` as in
+        ``estimate``.  A rejected sensor's node carries the model's estimate, not its reading, whatever ``keep_observed``
+        says about the others.  Nothing is read back."""
+        self._check_readings(readings)
+        if out is not None:
+            self._result(int(readings.shape[0]), out)               # (refused before the pass)
+        avail, rejected, _, _ = self.screen(readings, bounds, level, max_reject=max_reject, min_sensors=min_sensors,
+                                            available=available, nan_is_missing=nan_is_missing)
+        return self.estimate(readings, out, available=avail, nan_is_missing=nan_is_missing), rejected
+
+    def screening_report(self, store, bounds: ScreeningBounds, *, fault_offset, fault_share: float = 0.5, seed: int = 0,
+                         max_reject: int = 1, level=None) -> Dict[str, object]:
+        """Back-test of the screening over ``store`` with planted faults.  ``fault_draws(seed, S, K, fault_share)`` chooses one
+        faulty sensor in a ``fault_share`` of the snapshots (on the host, uploaded once); its reading -- the store's descaled
+        value -- is shifted by ``fault_offset`` (physical units; one value or K).  Four passes, one read-back each: the clean
+        readings, the faulted readings unscreened, the faulted readings through ``estimate_screened``, and the faulted readings
+        with the faulty sensor taken out by hand (the best a screening can do).  Returns ``screening_rates`` of the third
+        pass's ``rejected`` (detection, misidentification and the false-rejection rates over faulted and clean snapshots),
+        ``nonsensor_mae`` (a dict: ``clean``, ``faulted``, ``screened``, ``oracle``: the MAE over the nodes outside
+        ``observed_idx``, as ``error_map`` pools it), ``fault_col`` and ``rejected`` (numpy)."""
+        self._check_store(store)
+        K, S, N = self._loo_ready(), len(store), self.nodes_per_graph
+        self._check_screening(bounds, level, max_reject, 1)
+        try:
+            shift = np.asarray(fault_offset, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"fault_offset must be a number or a sequence of {K} of them") from None
+        if shift.ndim == 0:
+            shift = np.full(K, float(shift))
+        if shift.shape != (K,) or not np.isfinite(shift).all():
+            raise ValueError(f"fault_offset must be a finite number or a sequence of {K} of them, one per sensor")
+        fault_col = fault_draws(seed, S, K, fault_share)
+        rows = np.nonzero(fault_col >= 0)[0]
+        plan = np.zeros((2, S, K), dtype=np.float32)                # [0] the shift of every reading, [1] 1 where it is faulty
+        plan[0, rows, fault_col[rows]] = shift[fault_col[rows]].astype(np.float32)
+        plan[1, rows, fault_col[rows]] = 1.0
+        plan = torch.from_numpy(plan).to(self.device)
+        readings = store.descale(store.data.index_select(1, self._observed)).contiguous()
+        faulted = (readings + plan[0]).contiguous()
+        without = (plan[1] == 0).to(torch.uint8).contiguous()
+        est = torch.empty((S, N), dtype=torch.float32, device=self.device)
+        lib = _native.load()
+
+        def judged(extra=None):                                     # (one read-back: the moments, and the rejections behind them)
+            table = torch.empty((N, NODE_ERROR_RECORD), dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                _native.check(lib.gatres_node_error_moments(
+                    est.data_ptr(), store.data.data_ptr(), S, N, self.scale, self.offset, self._observed.data_ptr(), K,
+                    table.data_ptr(), _native.current_stream(self.device)), "gatres_node_error_moments")
+            flat = table.reshape(-1) if extra is None else torch.cat([table.reshape(-1), extra.reshape(-1).to(torch.float64)])
+            host = flat.cpu().numpy()
+            return float(error_map_from_moments(host[:N * NODE_ERROR_RECORD])["hidden_mae"]), host[N * NODE_ERROR_RECORD:]
+
+        mae = {}
+        self.estimate(readings, est)
+        mae["clean"], _ = judged()
+        self.estimate(faulted, est)
+        mae["faulted"], _ = judged()
+        _, rejected = self.estimate_screened(faulted, bounds, level, out=est, max_reject=max_reject)
+        mae["screened"], rej = judged(rejected)
+        rej = rej.astype(np.int64).reshape(S, int(max_reject))
+        self.estimate(faulted, est, available=without)
+        mae["oracle"], _ = judged()
+        return {**screening_rates(rej, fault_col), "nonsensor_mae": mae, "fault_col": fault_col, "rejected": rej}
 
 
 class SensitivityMap:

@@ -1119,6 +1119,56 @@ int gatres_sensitivity_fold(const float* J, int64_t num_snapshots, int32_t num_t
 int gatres_sensitivity_spread(const float* J, int64_t rows, int32_t num_observed, int64_t J_stride, const float* sigma, float* out,
                               void* stream);
 
+/* Screening of sensor readings (symbols only: the ABI stays; k_screen.hip).  A reading that is present and wrong -- stuck,
+ * drifting, off by a constant -- shows in its LEAVE-ONE-OUT residual: the reading against the model's prediction at its node
+ * with that one sensor hidden.  "Every sensor but k" is a layout: the S * K (snapshot, left-out sensor) PAIRS, snapshot-major,
+ * are one long pass of gatres_stage_observed_layouts with layouts[K][K] = all ones, zero diagonal (pair p is source row p / K
+ * under layout p % K), the forward and gatres_loo_residuals per batch; gatres_screen_reject then decides, per snapshot.
+ *
+ * gatres_loo_residuals: one batch of pairs.  out, mask: [num_graphs * N], the forward's prediction and the staged mask of the
+ * batch; observed[K] as in gatres_stage_observed; src, layout, src_rows: the reading source of the staging launch, in either
+ * layout; scale, offset: those of gatres_estimate_write, D() its descale (two roundings, no contraction).  Graph g is pair
+ * p = first_pair + g: snapshot s = p / K, sensor k = p % K, node v = observed[k], and
+ *   r = src[s * K + k]  (GATRES_OBSERVED_READINGS, physical units)   or   r = D(src[s * N + v])  (GATRES_OBSERVED_FULL_ROWS)
+ *   pred[s * K + k]  = D(out[g * N + v])
+ *   resid[s * K + k] = fp32(r - pred[s * K + k])
+ * pred and resid: device float [src_rows][K].  The residual is the quiet NaN 0x7fc00000 (and pred is still written) when
+ *   the reading is not there: available != NULL and available[s * K + k] == 0 (device uint8 [src_rows][K]; the reading is then
+ *     not loaded), or nan_is_missing != 0 and r is a NaN;
+ *   mask[g * N + v] == 0: the pair was not staged with its sensor hidden and the number would be the sensor looking at itself
+ *     (gatres_sensitivity_gather guards its mask in the same way).
+ * A NaN reading without nan_is_missing gives the NaN of the subtraction.  An observed[k] outside [0, N) reads nothing: pred and
+ * resid are that quiet NaN.  Nothing but the batch's num_graphs entries of pred and of resid is written.  One graph per thread
+ * and trip, a capped grid that strides over the graphs.
+ * GATRES_E_BADARG before any launch: a NULL out, mask, src, observed, pred or resid; a layout that is neither of the two;
+ * nodes_per_graph < 1, num_graphs < 1, num_observed outside [1, N]; src_rows < 1; a pair range outside [0, src_rows * K); the
+ * batch's entries of pred or resid overlapping each other, out, mask, src, observed or available. */
+int gatres_loo_residuals(const float* out, const uint8_t* mask, const float* src, int32_t layout, int64_t src_rows,
+                         int64_t first_pair, int32_t nodes_per_graph, int32_t num_graphs, const int32_t* observed,
+                         int32_t num_observed, double scale, double offset, const uint8_t* available, int32_t nan_is_missing,
+                         float* pred, float* resid, void* stream);
+
+/* One rejection round for num_snapshots snapshots, one launch.  resid[S][K] (device float); bound[K] and inv_bound[K] (device
+ * float; the caller forms inv_bound = 1.0f / bound on the host, so no device division enters this statement); available[S][K]
+ * (device uint8), UPDATED IN PLACE; rejected[S][max_rounds] (device int32), of which only column `round` is written; flagged
+ * [S][K] (device uint8), may be NULL.  Sensor k of snapshot s is a CANDIDATE when
+ *   available[s * K + k] != 0  and  resid[s * K + k] is no NaN  and  fabsf(resid[s * K + k]) > bound[k]   (float comparison)
+ * so a NaN or +inf bound never yields a candidate.  flagged, when given, is the candidate indicator (1 / 0), written for every
+ * (s, k).  Among the candidates of a snapshot the one with the largest score = fp32(fabsf(resid) * inv_bound[k]) is chosen, ties
+ * going to the smallest k: the total order (score descending, k ascending), the scores ordered by IEEE value with -0 below +0
+ * and a NaN score (possible only with an inv_bound that is not 1 / bound) below every other.  With n_s the number of non-zero
+ * entries of row s of available:
+ *   a candidate k* exists and n_s - 1 >= min_sensors:   available[s * K + k*] = 0,  rejected[s * max_rounds + round] = k*
+ *   otherwise:                                           rejected[s * max_rounds + round] = -1,  available untouched
+ * One wave per snapshot, the lanes stride over k; a lane's best and the butterfly over the lanes use that total order, so the
+ * result is a function of the inputs alone, whatever the geometry.  The snapshots beyond the (capped) grid are taken by a loop.
+ * GATRES_E_BADARG before any launch: a NULL resid, bound, inv_bound, available or rejected; num_snapshots < 1, num_observed < 1,
+ * min_sensors < 1, max_rounds < 1, round outside [0, max_rounds); available, rejected or flagged overlapping resid, bound,
+ * inv_bound or one another. */
+int gatres_screen_reject(const float* resid, const float* bound, const float* inv_bound, uint8_t* available,
+                         int64_t num_snapshots, int32_t num_observed, int32_t min_sensors, int32_t round, int32_t max_rounds,
+                         int32_t* rejected, uint8_t* flagged, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
