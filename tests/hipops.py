@@ -135,3 +135,38 @@ def adam_step(p, g, m, v, step_counter, lr, b1, b2, eps, wd, scale=1.0):
     lib = N_.load()
     N_.check(lib.gatres_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), step_counter.data_ptr(),
                                   p.numel(), lr, b1, b2, eps, wd, scale, _s(p)), "adam")
+
+
+# ---- the typed projection entry points, on buffers the caller owns (tests/test_gpu_proj_turnover.py) ---------------------------------
+# Every pointer argument is a tensor, a raw address (int) or None; the return code is handed back unchecked, so that a test can
+# look at refusals, keep guard rows behind its buffers and choose the slab stride.
+DTYPE = {torch.float32: N_.DTYPE_F32, torch.bfloat16: N_.DTYPE_BF16, "f32": N_.DTYPE_F32, "bf16": N_.DTYPE_BF16}
+
+
+def _p(t):
+    return t if t is None or isinstance(t, int) else t.data_ptr()
+
+
+def _s0():
+    return N_.current_stream("cuda")
+
+
+def t_proj_attn_fwd(x, W, att_src, att_dst, h, a_src, a_dst, n, K, H, C_, dtype):
+    return N_.load().gatres_t_proj_attn_fwd(_p(x), _p(W), _p(att_src), _p(att_dst), _p(h), _p(a_src), _p(a_dst), n, K, H, C_,
+                                            DTYPE[dtype], _s0())
+
+
+def t_proj_bwd_dx(g_h, Wt, resid, relu_ref, g_x, n, K, HC, dtype):
+    """g_x [n, K] = (g_h [n, HC] @ Wt^T + resid) masked by relu_ref > 0, with Wt [K, HC] row-major."""
+    return N_.load().gatres_t_proj_bwd_dx(_p(g_h), _p(Wt), _p(resid), _p(relu_ref), _p(g_x), n, K, HC, DTYPE[dtype], _s0())
+
+
+def t_proj_bwd_dw(g_h, x, slabs, num_slabs, slab_stride, n, K, HC, dtype):
+    return N_.load().gatres_t_proj_bwd_dw(_p(g_h), _p(x), _p(slabs), num_slabs, slab_stride, n, K, HC, DTYPE[dtype], _s0())
+
+
+def t_conv_param_grads(h, g_a_src, g_a_dst, g_out, slabs, num_slabs, slab_stride, n, H, C_, dtype):
+    """``slabs`` [num_slabs, slab_stride]: per slab the att_src, att_dst and bias partial sums, H * C_ columns each."""
+    base, HC = slabs.data_ptr(), H * C_
+    return N_.load().gatres_t_conv_param_grads(_p(h), _p(g_a_src), _p(g_a_dst), _p(g_out), base, base + 4 * HC, base + 8 * HC,
+                                               num_slabs, slab_stride, n, H, C_, DTYPE[dtype], _s0())

@@ -30,7 +30,9 @@ def _st(t):
 @pytest.mark.parametrize("nc,H", [(32, 2), (32, 1), (64, 2), (128, 2), (128, 1)])
 def test_bf16_projection_kernels(pkg, lib, nc, H):
     """v_mfma_f32_16x16x32_bf16 projection (forward with the attention-logit epilogue, data gradient with the residual /
-    ReLU-mask epilogue) and the fp32-accumulated weight gradient on bf16 operands, against torch."""
+    ReLU-mask epilogue) and the fp32-accumulated weight gradient on bf16 operands, against torch.  One size, errors relative
+    to the largest entry; tests/test_gpu_proj_turnover.py holds the same kernels element by element to float64 at the sizes
+    where their tiling turns over (second trips, capped grids, empty and NaN-prefilled slabs)."""
     N = 1000 + 7                                         # a ragged last tile
     K = nc if H == 2 else 2 * nc
     C, HC = nc, H * nc
