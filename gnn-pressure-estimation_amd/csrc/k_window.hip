@@ -124,6 +124,12 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
   constexpr bool NOHUB = PH >= 0 && (PH & 0x400) != 0;
   constexpr bool PTAB = PH >= 0 && (PH & 0x800) != 0;
   constexpr bool OW64 = PH >= 0 && (PH & 0x1000) != 0;
+  // With all three (and 1024 threads) a lane holds the same row in every block, at conv1's width and at conv2's: the sparse
+  // stages' per-row descriptors are read ONCE per phase, behind its prologue, and live in registers across the block loop
+  // (k_window_stages.h: the REG forms) -- forward: nbin at both widths and mbin (12 VGPRs); backward: nbin at both widths,
+  // mout and tout at conv1's width (24).  tout at conv2's width does not fit beside them without scratch and stays in LDS,
+  // as every descriptor does in every other instantiation (profiles/window_descriptor_hoist.txt).
+  constexpr bool HOIST = NC == 32 && THREADS == 1024 && NOHUB && PTAB && OW64;
   // PH & 0x2000 (forward-only launches): nobody reads the saved activations (GATRES_MODEL_INFERENCE) -- their stores, a
   // tenth of the forward's VMEM and VALU work, are not compiled
   constexpr bool NOSAVE = PH >= 0 && (PH & 0x2000) != 0 && (PH & 0xff) == GATRES_PHASE_FORWARD;
@@ -414,6 +420,17 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
     };
     STAMP();
 #define RECP rf_
+    [[maybe_unused]] uint4 qn1 = uint4{}, qn2 = uint4{}, qm2 = uint4{};
+    if constexpr (HOIST) {     // the forward's descriptors of this lane's rows (conv2's carries the row's export flag)
+      FRESH_FWD();
+#define LIST_(T_, N_, I_) I_(lo) I_(hi) T_(const u16, nbin) T_(const u16, mbin) T_(const unsigned char, fflag)
+      REC_LOADS(LIST_);
+      REC_DEFS(LIST_);
+#undef LIST_
+      qn1 = win_hoist_in<2 * NC / 4>(rw, nbin, nullptr);
+      qn2 = win_hoist_in<NC / 4>(rw, nbin, fflag);
+      qm2 = win_hoist_in<NC / 4>(rw, mbin, nullptr);
+    }
     const int nb = L.nb;
     for (int b = 0; b < nb; ++b) {
       // (per stage: FRESH_ARGS() / FRESH_FWD() re-read the offsets and tables the stage needs; base / pb are formed where
@@ -474,8 +491,8 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
         // K2 conv1: alpha -> HBM, the gather's o1 -> HBM + the x buffer of proj2
         if (NOHUB || __builtin_expect(2 * oeg <= wr * NC, 1)) {
           if constexpr (NC == 32) {
-            win_fwd_agg<true, 2, NC, THREADS, NOHUB, 2 * NC + XPF>(rw, nbin, rp, colo, hA, sa2, sd2, NOSAVE ? nullptr : base + SL.al1, elo, hBw, wlA + B1OFF,
-                                              NOSAVE ? nullptr : base + SL.o1, 0, xB, mo1 ? mo1 + b * ow : nullptr, xout(false, fflag, 0, 0));
+            win_fwd_agg<true, 2, NC, THREADS, NOHUB, 2 * NC + XPF, HOIST>(rw, nbin, rp, colo, hA, sa2, sd2, NOSAVE ? nullptr : base + SL.al1, elo, hBw, wlA + B1OFF,
+                                              NOSAVE ? nullptr : base + SL.o1, 0, xB, mo1 ? mo1 + b * ow : nullptr, xout(false, fflag, 0, 0), qn1);
           } else {
             win_softmax<2, THREADS>(rw, nbin, rp, colo, sa2, sd2, base + SL.al1, elo, hBw);
             lds_barrier();
@@ -547,8 +564,8 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
 #undef LIST_
         if (NOHUB || __builtin_expect(oeg <= wr * NC, 1)) {
           if constexpr (NC == 32) {
-            win_fwd_agg<false, 1, NC, THREADS, NOHUB>(rw, nbin, rp, colo, hB, sa1, sd1, NOSAVE ? nullptr : base + SL.al2, elo, al2L, wlB + B2OFF, y2T,
-                                               0, nullptr, nullptr, xout(xreg, fflag, XL.f3, 0));
+            win_fwd_agg<false, 1, NC, THREADS, NOHUB, NC, HOIST>(rw, nbin, rp, colo, hB, sa1, sd1, NOSAVE ? nullptr : base + SL.al2, elo, al2L, wlB + B2OFF, y2T,
+                                               0, nullptr, nullptr, xout(xreg, fflag, XL.f3, 0), qn2);
           } else {
             win_softmax<1, THREADS>(rw, nbin, rp, colo, sa1, sd1, base + SL.al2, elo, al2L);
             lds_barrier();
@@ -585,8 +602,8 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
 #undef LIST_
         // K3: residual from the x buffer, result back into it (and to HBM: saved xin of the next block)
         float* xnext = segbase + (int64_t)(launder_s(b) + 1) * SL.bstride + SL.xin;
-        win_mean_fwd<NC, THREADS, NOHUB, NC + XPF>(rw, mbin, mrp, mcolo, y2T, xA, NOSAVE ? nullptr : xnext, xA,
-                                       (mxin && b + 1 < nb) ? mxin + (b + 1) * ow : nullptr);
+        win_mean_fwd<NC, THREADS, NOHUB, NC + XPF, HOIST>(rw, mbin, mrp, mcolo, y2T, xA, NOSAVE ? nullptr : xnext, xA,
+                                       (mxin && b + 1 < nb) ? mxin + (b + 1) * ow : nullptr, qm2);
         lds_barrier();
         STAMP();
       }
@@ -970,6 +987,18 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
       const float* bs = segbase + (int64_t)blk * SL.bstride;
       dma_copy4<THREADS>(alTw, bs + SL.al2 + ewlo, weg, w0);
     };
+    [[maybe_unused]] uint4 bn1 = uint4{}, bn2 = uint4{}, bma = uint4{}, bmb = uint4{}, bt1a = uint4{}, bt1b = uint4{};
+    if constexpr (HOIST) {     // the backward's descriptors of this lane's rows (conv2's nbin carries the row's export flag)
+      FRESH_BWD();
+#define LIST_(T_, N_, I_) I_(lo) I_(hi) T_(const u16, nbin) T_(const u16, mout) T_(const u16, tout) T_(const unsigned char, bflag)
+      REC_LOADS(LIST_);
+      REC_DEFS(LIST_);
+#undef LIST_
+      bn1 = win_hoist_in<2 * NC / 4>(rw, nbin, nullptr);
+      bn2 = win_hoist_in<NC / 4>(rw, nbin, bflag);
+      win_hoist_out<NC / 4>(rw, mout, bma, bmb);
+      win_hoist_out<2 * NC / 4>(rw, tout, bt1a, bt1b);
+    }
     STAMP();
     const int nb = L.nb;
     for (int b = nb - 1; b >= 0; --b) {
@@ -1023,8 +1052,8 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
                                                      (unsigned)XL.b2y, gy2T, LDS_TABLE(const u16, lds_raw, rb2_->hedge),
                                                      rb2_->hecnt, (unsigned)XL.b2e, ge2);
         } else
-        win_bwd_dst<true, 1, NC, THREADS, NC == 32, NOHUB>(rw, nbin, rp, colo, gy2T, hT2, alT2 + elo, asT2, adT2, ge2 + elo, gad2, mout, mrp,
-                                               mtrp, mtdsto, gpT, xout(xedge, bflag, (unsigned)XL.b2y, (unsigned)XL.b2e), elo);
+        win_bwd_dst<true, 1, NC, THREADS, NC == 32, NOHUB, HOIST>(rw, nbin, rp, colo, gy2T, hT2, alT2 + elo, asT2, adT2, ge2 + elo, gad2, mout, mrp,
+                                               mtrp, mtdsto, gpT, xout(xedge, bflag, (unsigned)XL.b2y, (unsigned)XL.b2e), elo, bn2, bma, bmb);
         lds_barrier();
         XSTAMP();
       }
@@ -1131,9 +1160,9 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
         REC_DEFS(LIST_);
 #undef LIST_
         seg_bias_part<2 * NC, THREADS>(rw, RA, 0, red);
-        win_bwd_dst<false, 2, NC, THREADS, false, NOHUB>(rw, nbin, rp, colo, RA, hT1, alT1 + elo * 2, asT1, adT1, ge1 + elo * 2, gad1,
+        win_bwd_dst<false, 2, NC, THREADS, false, NOHUB, HOIST>(rw, nbin, rp, colo, RA, hT1, alT1 + elo * 2, asT1, adT1, ge1 + elo * 2, gad1,
                                                 nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                xout(xedge, bflag, 0u, (unsigned)XL.b3e), elo);
+                                                xout(xedge, bflag, 0u, (unsigned)XL.b3e), elo, bn1);
         if (NC != 32 || !xrows) lds_barrier();     // (else B3's sweep starts without one: see the top of the loop)
         XSTAMP();
       }
@@ -1167,8 +1196,8 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
         REC_DEFS(LIST_);
 #undef LIST_
         seg_bias_finish<2 * NC, THREADS>(red, sb + L.c1_b);
-        win_agg_bwd_src<2, NC, THREADS, NOHUB, 2 * NC + XPB>(rw, tout, trp, teido, tdsto, 0, RA, alT1, ge1, gad1, wlB + A1OFF, wlB + A1OFF + 2 * NC,
-                                             keep + L.k_gh1, n0, keep + L.k_gas1, keep + L.k_gad1, xG1);
+        win_agg_bwd_src<2, NC, THREADS, NOHUB, 2 * NC + XPB, HOIST>(rw, tout, trp, teido, tdsto, 0, RA, alT1, ge1, gad1, wlB + A1OFF, wlB + A1OFF + 2 * NC,
+                                             keep + L.k_gh1, n0, keep + L.k_gas1, keep + L.k_gad1, xG1, bt1a, bt1b);
         lds_barrier();
         XSTAMP();
         STAMP();

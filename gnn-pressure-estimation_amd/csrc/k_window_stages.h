@@ -586,6 +586,45 @@ template <bool NH> __device__ __forceinline__ bool wave_has_hub_t(int deg) {
   else return wave_has_hub(deg);
 }
 
+// DESCRIPTORS IN REGISTERS (the REG forms of the stages below).  When no part owns more than 64 rows, a stage of G lanes per
+// row (G = 16 at conv1's width, 8 at conv2's) is ONE trip of its row loop and a lane holds the same row -- lo + tid / G, clamped
+// to hi - 1 -- in every block: the row's descriptor depends on the topology alone, so the kernel reads it once, behind the
+// prologue's barrier, and hands it to the stage by value.  The stage then opens with its batch of row reads (the row's own
+// operands ride in that batch) instead of descriptor -> wait -> rows.  Bit 31 of word 0 (deg <= MAXD: the high bits of the
+// degree half-word are free) carries the row's export flag, so the epilogues read no flag byte.  Waves that hold no row
+// load nothing.  The operands and their order are those of the LDS form: the same bits.
+constexpr unsigned NBR_FLAG = 0x80000000u;
+template <int G>
+__device__ __forceinline__ uint4 win_hoist_in(Rows rw, const u16* tab, const unsigned char* flag) {
+  const int tid = stage_tid();
+  uint4 w = make_uint4(0u, 0u, 0u, 0u);
+  if (rw.lo + (int)((tid & ~63u) / G) >= rw.hi) return w;      // (wave-uniform) no row for this wave
+  const int r = min(rw.lo + tid / G, rw.hi - 1);
+  w = lds_rd128(lds_addr(tab) + (unsigned)(r - rw.lo) * 16u);
+  if (flag && flag[r] != 0) w.x |= NBR_FLAG;
+  return w;
+}
+template <int G>
+__device__ __forceinline__ void win_hoist_out(Rows rw, const u16* tab, uint4& wa, uint4& wb) {
+  const int tid = stage_tid();
+  wa = make_uint4(0u, 0u, 0u, 0u); wb = wa;
+  if (rw.lo + (int)((tid & ~63u) / G) >= rw.hi) return;
+  const int r = min(rw.lo + tid / G, rw.hi - 1);
+  const unsigned a = lds_addr(tab) + (unsigned)(r - rw.lo) * 32u;
+  lds_rd128x2(a, a + 16u, wa, wb);
+}
+// The stage's copy, without the flag and opaque to the optimiser (as stage_tid): what a stage unpacks from it -- degree, six
+// ids, six row addresses -- is formed inside the stage, not hoisted out of the block loop and kept alive across it.
+__device__ __forceinline__ uint4 nbr_opaque(uint4 w) {
+  asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z), "+v"(w.w));
+  return w;
+}
+__device__ __forceinline__ uint4 nbr_plain(uint4 w) {
+  w = nbr_opaque(w);
+  w.x &= ~NBR_FLAG;
+  return w;
+}
+
 // ---------------------------------------------------------------------------------------------- forward stages
 // K2 forward, sub-stage A (seg_softmax): one thread per (row, head).
 //   nb: in-edge descriptors; asrc: [row][H] over the window (shifted view); adst: [row][H] own rows (shifted view);
@@ -719,12 +758,15 @@ __device__ __forceinline__ void win_gather(Rows rw, const u16* nb, const u16* rp
 template <int K> __device__ __forceinline__ float group8_bcast(float v) {
   return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x18 | (K << 5)));      // lane (l & 0x18) | K
 }
-template <bool RELU, int H, int C, int THREADS, bool NH = false, int OPS = H * C>
+// REG: the row's descriptor comes by value (wreg: see win_hoist_in); the six row reads, a_src of the lane's slot and the
+// row's own a_dst are one batch.
+template <bool RELU, int H, int C, int THREADS, bool NH = false, int OPS = H * C, bool REG = false>
 __device__ __forceinline__ void win_fwd_agg(Rows rw, const u16* nb, const u16* rp, const u16* col, const float* hsrc,
                                             const float* asrc, const float* adst_t, float* __restrict__ alpha_g, int eb,
                                             float* alpha_l, const float* bias, float* out, int ob, float* out_pub,
-                                            unsigned long long* mask64, const XOut& xo) {
+                                            unsigned long long* mask64, const XOut& xo, const uint4 wreg = uint4{}) {
   static_assert(C == 32 && MAXD <= 8, "one edge slot per lane of a head's eight lanes");
+  static_assert(!REG || (NH && THREADS / (H * C / 4) >= 64), "REG: one trip, no hub rows");
   const int tid = stage_tid();
   constexpr int HC = H * C, G = HC / 4, LH = C / 4, RPP = THREADS / G;
   const int c0 = (tid % G) * 4;
@@ -733,14 +775,15 @@ __device__ __forceinline__ void win_fwd_agg(Rows rw, const u16* nb, const u16* r
   const unsigned a_nb = lds_addr(nb), a_h = lds_addr(hsrc) + (unsigned)c0 * 4u, a_as = lds_addr(asrc) + (unsigned)hd * 4u,
                  a_ad = lds_addr(adst_t) + (unsigned)hd * 4u;
   const float4 b = ld4(bias + c0);
-  for (int r0 = rw.lo; r0 < rw.hi; r0 += RPP) {
+  for (int r0 = rw.lo; REG ? r0 == rw.lo : r0 < rw.hi; r0 += RPP) {      // (REG: exactly one trip)
     if (r0 + (int)((tid & ~63u) / G) >= rw.hi) continue;      // no row of this trip for this wave
     int r = r0 + tid / G;
     const bool valid = r < rw.hi;
     if (!valid) r = rw.hi - 1;
     uint4 w;
     float adst;
-    lds_rd128_32(a_nb + (unsigned)(r - rw.lo) * 16u, a_ad + (unsigned)(r * H) * 4u, w, adst);
+    if constexpr (REG) w = nbr_plain(wreg);
+    else lds_rd128_32(a_nb + (unsigned)(r - rw.lo) * 16u, a_ad + (unsigned)(r * H) * 4u, w, adst);
     const NbrIn d = unpack_in(w);
     float4 acc = f4zero();
 #ifdef GATRES_VALU_PROBE      // experiment builds only (profiles/r04_valu_probe.txt): N extra VALU instructions per lane and call
@@ -781,6 +824,16 @@ __device__ __forceinline__ void win_fwd_agg(Rows rw, const u16* nb, const u16* r
       for (int k = 0; k < MAXD; ++k) av[k] = a_h + (unsigned)(d.n[k] * HC) * 4u;
       f32x4 v[MAXD];
       float asj;
+      if constexpr (REG)
+        asm volatile(
+            "ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %10\n\t"
+            "ds_read_b128 %3, %11\n\tds_read_b128 %4, %12\n\tds_read_b128 %5, %13\n\tds_read_b32 %6, %14\n\t"
+            "ds_read_b32 %7, %15\n\ts_waitcnt lgkmcnt(0)"
+            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(asj), "=&v"(adst)
+            : "v"(av[0]), "v"(av[1]), "v"(av[2]), "v"(av[3]), "v"(av[4]), "v"(av[5]), "v"(a_as + (unsigned)(nj * H) * 4u),
+              "v"(a_ad + (unsigned)(r * H) * 4u)
+            : "memory");
+      else
       asm volatile(
           "ds_read_b128 %0, %7\n\tds_read_b128 %1, %8\n\tds_read_b128 %2, %9\n\t"
           "ds_read_b128 %3, %10\n\tds_read_b128 %4, %11\n\tds_read_b128 %5, %12\n\tds_read_b32 %6, %13\n\t"
@@ -818,7 +871,7 @@ __device__ __forceinline__ void win_fwd_agg(Rows rw, const u16* nb, const u16* r
     if (valid) {
       if (out) st4(out + (unsigned)((ob + r) * HC + c0), acc);
       if (out_pub) st4(out_pub + (unsigned)(r * OPS + c0), acc);      // (OPS: row stride of the x operand table it fills)
-      if (xo.on && xo.flag[r] != 0) xout_store4(xo, xo.t_rows + (unsigned)(r * HC + c0), acc);
+      if (xo.on && (REG ? (wreg.x & NBR_FLAG) != 0 : xo.flag[r] != 0)) xout_store4(xo, xo.t_rows + (unsigned)(r * HC + c0), acc);
     }
     if constexpr (RELU && G <= 16) {
       if (mask64) {                                             // (workgroup-uniform)
@@ -830,22 +883,25 @@ __device__ __forceinline__ void win_fwd_agg(Rows rw, const u16* nb, const u16* r
 }
 
 // K3 forward (seg_mean_fwd): out = relu(mean_{j->r} y[j] + x0[r]).
-template <int C, int THREADS, bool NH = false, int XS = C>
+// REG: the row's descriptor comes by value (win_hoist_in); the six row reads and the residual row are one batch.
+template <int C, int THREADS, bool NH = false, int XS = C, bool REG = false>
 __device__ __forceinline__ void win_mean_fwd(Rows rw, const u16* mb, const u16* mrp, const u16* mcol, const float* y,
-                                             const float* x0, float* out, float* out2, unsigned* mask32) {
+                                             const float* x0, float* out, float* out2, unsigned* mask32,
+                                             const uint4 wreg = uint4{}) {
+  static_assert(!REG || (NH && THREADS / (C / 4) >= 64), "REG: one trip, no hub rows");
   const int tid = stage_tid();
   constexpr int G = C / 4, RPP = THREADS / G;
   const int c0 = (tid % G) * 4;
   const unsigned a_mb = lds_addr(mb), a_y = lds_addr(y) + (unsigned)c0 * 4u, a_x = lds_addr(x0) + (unsigned)c0 * 4u;
-  for (int r0 = rw.lo; r0 < rw.hi; r0 += RPP) {
+  for (int r0 = rw.lo; REG ? r0 == rw.lo : r0 < rw.hi; r0 += RPP) {      // (REG: exactly one trip)
     if (r0 + (int)((tid & ~63u) / G) >= rw.hi) continue;
     int r = r0 + tid / G;
     const bool valid = r < rw.hi;
     if (!valid) r = rw.hi - 1;
     uint4 w, xr;
-    lds_rd128x2(a_mb + (unsigned)(r - rw.lo) * 16u, a_x + (unsigned)(r * XS) * 4u, w, xr);      // (x0 / out2: the x table, row stride XS)
+    if constexpr (REG) w = nbr_plain(wreg);
+    else lds_rd128x2(a_mb + (unsigned)(r - rw.lo) * 16u, a_x + (unsigned)(r * XS) * 4u, w, xr);      // (x0 / out2: the x table, row stride XS)
     const NbrIn d = unpack_in(w);
-    const float4 rr = as_f4(xr);
     float4 acc = f4zero();
     if (__builtin_expect(wave_has_hub_t<NH>(d.deg), 0)) {
       const int beg = mrp[r], end = mrp[r + 1];
@@ -855,10 +911,19 @@ __device__ __forceinline__ void win_mean_fwd(Rows rw, const u16* mb, const u16* 
 #pragma unroll
       for (int k = 0; k < MAXD; ++k) av[k] = a_y + (unsigned)(d.n[k] * C) * 4u;
       f32x4 v[MAXD];
-      lds_rd128x6(av, v);
+      if constexpr (REG)
+        asm volatile(
+            "ds_read_b128 %0, %7\n\tds_read_b128 %1, %8\n\tds_read_b128 %2, %9\n\t"
+            "ds_read_b128 %3, %10\n\tds_read_b128 %4, %11\n\tds_read_b128 %5, %12\n\tds_read_b128 %6, %13\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(xr)
+            : "v"(av[0]), "v"(av[1]), "v"(av[2]), "v"(av[3]), "v"(av[4]), "v"(av[5]), "v"(a_x + (unsigned)(r * XS) * 4u)
+            : "memory");
+      else lds_rd128x6(av, v);
 #pragma unroll
       for (int k = 0; k < MAXD; ++k) gatres_axpy4(acc, k < d.deg ? 1.f : 0.f, as_f4(v[k]));   // fma(1,v,acc) = acc+v
     }
+    const float4 rr = as_f4(xr);
     const float cnt = (float)max(d.deg, 1);
     float4 o;
     o.x = fmaxf(acc.x / cnt + rr.x, 0.f); o.y = fmaxf(acc.y / cnt + rr.y, 0.f);
@@ -1028,14 +1093,19 @@ __device__ __forceinline__ void win_softmax_bwd(Rows rw, const u16* nb, const u1
 // MEAN (conv2 only, H == 1): the stage starts with K3 backward (win_mean_bwd) for the same row -- its result g_y2[r] is
 // the g_out operand of the edge dots, held by the same lanes -- so  B1 exchange -> [K3 bwd, edge dots, softmax bwd] -> B2
 // exchange  is ONE stage.  g_out_rw: [row][HC] over the window (shifted view): read (MEAN = false) or written (MEAN).
-template <bool MEAN, int H, int C, int THREADS, bool PRE = false, bool NH = false>
+// REG: the row's in-edge descriptor comes by value (wreg: win_hoist_in, with the row's export flag) and, with MEAN, so does
+// its out-edge descriptor in SimpleConv's graph (mra | mrb: win_hoist_out).  The row's own operands ride in the first batch
+// of row reads: K3 backward opens with its six rows + a_dst, conv1's stage with g_out, a_dst and everything else at once.
+template <bool MEAN, int H, int C, int THREADS, bool PRE = false, bool NH = false, bool REG = false>
 __device__ __forceinline__ void win_bwd_dst(Rows rw, const u16* nb, const u16* rp, const u16* col, float* g_out_rw,
                                             const float* h, const float* alpha, const float* a_src, const float* a_dst,
                                             float* g_e, float* g_a_dst,
                                             const u16* mo, const u16* mrp, const u16* mtrp, const u16* mtdst,
-                                            const float* g_pre, const XOut& xo, int eabs) {
+                                            const float* g_pre, const XOut& xo, int eabs, const uint4 wreg = uint4{},
+                                            const uint4 mra = uint4{}, const uint4 mrb = uint4{}) {
   // (eabs: absolute local id of the part's first own edge -- the edge tables of the hand-offs are indexed by it)
   static_assert(!MEAN || H == 1, "K3 runs at conv2's width");
+  static_assert(!REG || (NH && C == 32 && THREADS / (H * C / 4) >= 64), "REG: one trip, no hub rows");
   const int tid = stage_tid();
   constexpr int HC = H * C, G = HC / 4, LH = C / 4, RPP = THREADS / G;
   const int c0 = (tid % G) * 4;
@@ -1043,7 +1113,7 @@ __device__ __forceinline__ void win_bwd_dst(Rows rw, const u16* nb, const u16* r
   const unsigned a_nb = lds_addr(nb), a_go = lds_addr(g_out_rw) + (unsigned)c0 * 4u, a_h = lds_addr(h) + (unsigned)c0 * 4u,
                  a_al = lds_addr(alpha) + (unsigned)hd * 4u, a_as = lds_addr(a_src) + (unsigned)hd * 4u,
                  a_ad = lds_addr(a_dst) + (unsigned)hd * 4u;
-  for (int r0 = rw.lo; r0 < rw.hi; r0 += RPP) {
+  for (int r0 = rw.lo; REG ? r0 == rw.lo : r0 < rw.hi; r0 += RPP) {      // (REG: exactly one trip)
     if (r0 + (int)((tid & ~63u) / G) >= rw.hi) continue;
     int r = r0 + tid / G;
     const bool valid = r < rw.hi;          // every lane stays in the loop: the head reduction spans the head's lanes
@@ -1055,6 +1125,8 @@ __device__ __forceinline__ void win_bwd_dst(Rows rw, const u16* nb, const u16* r
     if constexpr (MEAN) {
       const unsigned a_mo = lds_addr(mo) + (unsigned)(r - rw.lo) * 32u;
       uint4 wa, wb, w;
+      if constexpr (REG) { wa = nbr_opaque(mra); wb = nbr_opaque(mrb); w = nbr_plain(wreg); }      // (a_dst rides with the six row reads below)
+      else
       asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %5\n\tds_read_b32 %3, %6\n\t"
                    "s_waitcnt lgkmcnt(0)"
                    : "=&v"(wa), "=&v"(wb), "=&v"(w), "=&v"(adst)
@@ -1081,11 +1153,19 @@ __device__ __forceinline__ void win_bwd_dst(Rows rw, const u16* nb, const u16* r
 #pragma unroll
         for (int k = 0; k < MAXD; ++k) av[k] = a_g + (unsigned)(od.d[k] * C) * 4u;
         f32x4 v[MAXD];
-        lds_rd128x6(av, v);
+        if constexpr (REG)
+          asm volatile(
+              "ds_read_b128 %0, %7\n\tds_read_b128 %1, %8\n\tds_read_b128 %2, %9\n\t"
+              "ds_read_b128 %3, %10\n\tds_read_b128 %4, %11\n\tds_read_b128 %5, %12\n\tds_read_b32 %6, %13\n\t"
+              "s_waitcnt lgkmcnt(0)"
+              : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(adst)
+              : "v"(av[0]), "v"(av[1]), "v"(av[2]), "v"(av[3]), "v"(av[4]), "v"(av[5]), "v"(a_ad + (unsigned)(r * H) * 4u)
+              : "memory");
+        else lds_rd128x6(av, v);
 #pragma unroll
         for (int k = 0; k < MAXD; ++k) {
           const float w1 = k < od.deg ? 1.f : 0.f;                      // x + 0 * q == x exactly
-          if constexpr (PRE) {                                          // g_pre holds g / max(indeg, 1): win_proj's cnt_rp
+          if constexpr (PRE) {                                        // g_pre holds g / max(indeg, 1): win_proj's cnt_rp
             gatres_axpy4(acc, w1, as_f4(v[k]));
           } else {
             const float cnt = (float)od.x[k];
@@ -1097,8 +1177,10 @@ __device__ __forceinline__ void win_bwd_dst(Rows rw, const u16* nb, const u16* r
       go = acc;
       if (valid) {
         st4(g_out_rw + (unsigned)(r * HC + c0), acc);
-        if (xo.on && xo.flag[r] != 0) xout_store4(xo, xo.t_rows + (unsigned)(r * HC + c0), acc);
+        if (xo.on && (REG ? (wreg.x & NBR_FLAG) != 0 : xo.flag[r] != 0)) xout_store4(xo, xo.t_rows + (unsigned)(r * HC + c0), acc);
       }
+    } else if constexpr (REG) {
+      d = unpack_in(nbr_plain(wreg));          // (g_out and a_dst of the row ride with the six row reads below)
     } else {
       uint4 w, gw;
       lds_rd128x2_32(a_nb + (unsigned)(r - rw.lo) * 16u, a_go + (unsigned)(r * HC) * 4u, a_ad + (unsigned)(r * H) * 4u, w,
@@ -1144,6 +1226,20 @@ __device__ __forceinline__ void win_bwd_dst(Rows rw, const u16* nb, const u16* r
       const unsigned aaj = a_al + (unsigned)((d.beg + min(jj, d.deg - 1)) * H) * 4u, asj = a_as + (unsigned)(nj * H) * 4u;
       f32x4 hv[MAXD];
       float alj, rawj;
+      if constexpr (REG && !MEAN) {
+        uint4 gw;
+        asm volatile(
+            "ds_read_b128 %0, %10\n\tds_read_b128 %1, %11\n\tds_read_b128 %2, %12\n\t"
+            "ds_read_b128 %3, %13\n\tds_read_b128 %4, %14\n\tds_read_b128 %5, %15\n\t"
+            "ds_read_b32 %6, %16\n\tds_read_b32 %7, %17\n\tds_read_b128 %8, %18\n\tds_read_b32 %9, %19\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(hv[0]), "=&v"(hv[1]), "=&v"(hv[2]), "=&v"(hv[3]), "=&v"(hv[4]), "=&v"(hv[5]), "=&v"(alj), "=&v"(rawj),
+              "=&v"(gw), "=&v"(adst)
+            : "v"(av[0]), "v"(av[1]), "v"(av[2]), "v"(av[3]), "v"(av[4]), "v"(av[5]), "v"(aaj), "v"(asj),
+              "v"(a_go + (unsigned)(r * HC) * 4u), "v"(a_ad + (unsigned)(r * H) * 4u)
+            : "memory");
+        go = as_f4(gw);
+      } else
       asm volatile(
           "ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %10\n\t"
           "ds_read_b128 %3, %11\n\tds_read_b128 %4, %12\n\tds_read_b128 %5, %13\n\t"
@@ -1211,12 +1307,15 @@ __device__ __forceinline__ void win_bwd_dst(Rows rw, const u16* nb, const u16* r
 //   to: out-edge descriptors (x_k = window-relative edge id); g_out: [row][HC] over the window; alpha / g_e: LDS [e][H]
 //   over the WINDOW's edges; g_a_dst: [row][H] own rows; g_h: global (kept for the deferred parameter gradients, row
 //   hb + r); g_h2: LDS x operand of the dX stage.
-template <int H, int C, int THREADS, bool NH = false, int G2S = H * C>
+// REG: the row's out-edge descriptor comes by value (tra | trb: win_hoist_out); g_a_dst of the row rides with the row reads.
+template <int H, int C, int THREADS, bool NH = false, int G2S = H * C, bool REG = false>
 __device__ __forceinline__ void win_agg_bwd_src(Rows rw, const u16* to, const u16* trp, const u16* teid, const u16* tdst,
                                                 int eid_sub, const float* g_out, const float* alpha, const float* g_e,
                                                 const float* g_a_dst, const float* att_src, const float* att_dst,
                                                 float* g_h, int hb,
-                                                float* keep_gas, float* keep_gad, float* g_h2) {
+                                                float* keep_gas, float* keep_gad, float* g_h2, const uint4 tra = uint4{},
+                                                const uint4 trb = uint4{}) {
+  static_assert(!REG || (NH && C == 32 && THREADS / (H * C / 4) >= 64), "REG: one trip, no hub rows");
   const int tid = stage_tid();
   constexpr int HC = H * C, G = HC / 4, RPP = THREADS / G;
   const int c0 = (tid % G) * 4;
@@ -1225,13 +1324,15 @@ __device__ __forceinline__ void win_agg_bwd_src(Rows rw, const u16* to, const u1
                  a_al = lds_addr(alpha) + (unsigned)hd * 4u, a_ge = lds_addr(g_e) + (unsigned)hd * 4u,
                  a_gd = lds_addr(g_a_dst) + (unsigned)hd * 4u;
   const float4 as = ld4(att_src + c0), ad = ld4(att_dst + c0);
-  for (int r0 = rw.lo; r0 < rw.hi; r0 += RPP) {
+  for (int r0 = rw.lo; REG ? r0 == rw.lo : r0 < rw.hi; r0 += RPP) {      // (REG: exactly one trip)
     if (r0 + (int)((tid & ~63u) / G) >= rw.hi) continue;
     int r = r0 + tid / G;
     const bool valid = r < rw.hi;
     if (!valid) r = rw.hi - 1;
     uint4 wa, wb;
     float gad;
+    if constexpr (REG) { wa = nbr_opaque(tra); wb = nbr_opaque(trb); }
+    else
     lds_rd128x2_32(a_to + (unsigned)(r - rw.lo) * 32u, a_to + (unsigned)(r - rw.lo) * 32u + 16u,
                    a_gd + (unsigned)(r * H) * 4u, wa, wb, gad);
     const NbrOut d = unpack_out(wa, wb);
@@ -1257,6 +1358,16 @@ __device__ __forceinline__ void win_agg_bwd_src(Rows rw, const u16* to, const u1
         for (int k = 0; k < MAXD; ++k) av[k] = a_go + (unsigned)(d.d[k] * HC) * 4u;
         f32x4 v[MAXD];
         float alj, gej;
+        if constexpr (REG)
+          asm volatile(
+              "ds_read_b128 %0, %9\n\tds_read_b128 %1, %10\n\tds_read_b128 %2, %11\n\t"
+              "ds_read_b128 %3, %12\n\tds_read_b128 %4, %13\n\tds_read_b128 %5, %14\n\t"
+              "ds_read_b32 %6, %15\n\tds_read_b32 %7, %16\n\tds_read_b32 %8, %17\n\ts_waitcnt lgkmcnt(0)"
+              : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(alj), "=&v"(gej), "=&v"(gad)
+              : "v"(av[0]), "v"(av[1]), "v"(av[2]), "v"(av[3]), "v"(av[4]), "v"(av[5]), "v"(a_al + (unsigned)(xj * H) * 4u),
+                "v"(a_ge + (unsigned)(xj * H) * 4u), "v"(a_gd + (unsigned)(r * H) * 4u)
+              : "memory");
+        else
         asm volatile(
             "ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %10\n\t"
             "ds_read_b128 %3, %11\n\tds_read_b128 %4, %12\n\tds_read_b128 %5, %13\n\t"
