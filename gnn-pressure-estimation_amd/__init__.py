@@ -10,9 +10,11 @@ from .snapshot_store import SnapshotStore
 from .multi_snapshot_store import MultiSnapshotStore
 from .train_step import FitHistory, GATResTrainer, internal_train
 from .sensor_layout import sensor_layout_draws
-from .estimation import (ErrorBounds, PressureEstimator, ScreeningBounds, SensitivityMap, conformal_rank, coverage_from_table, greedy_selection,
+from .estimation import (ErrorBounds, MonitorBaseline, MonitorResult, PressureEstimator, ScreeningBounds, SensitivityMap, conformal_rank, coverage_from_table, greedy_selection,
                          layout_scores_from_table, node_error_bounds, observed_from_names, reading_noise)
 from .screening import fault_draws, loo_layouts, loo_residuals_from_estimates, screen_ref, screen_reject_ref, screening_rates
+from .monitoring import (cusum_compose, cusum_fixed, cusum_scan_ref, drift_draws, drift_offsets, monitor_baseline_from_moments,
+                         monitor_latch_ref, monitor_ref, monitoring_rates)
 from .sensitivity import (influence_from_table, linear_spread_ref, sensitivity_fold_ref, sensitivity_rows_from_gx,
                           sensitivity_seeds)
 
@@ -22,4 +24,6 @@ __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "Simpl
            "layout_scores_from_table", "greedy_selection", "sensor_layout_draws", "ErrorBounds", "conformal_rank",
            "node_error_bounds", "coverage_from_table", "SensitivityMap", "influence_from_table", "linear_spread_ref",
            "sensitivity_fold_ref", "sensitivity_rows_from_gx", "sensitivity_seeds", "ScreeningBounds", "screening", "loo_layouts",
-           "loo_residuals_from_estimates", "screen_reject_ref", "screen_ref", "fault_draws", "screening_rates"]
+           "loo_residuals_from_estimates", "screen_reject_ref", "screen_ref", "fault_draws", "screening_rates", "MonitorBaseline", "MonitorResult",
+           "monitoring", "cusum_scan_ref", "cusum_fixed", "cusum_compose", "monitor_latch_ref", "monitor_ref",
+           "monitor_baseline_from_moments", "drift_draws", "drift_offsets", "monitoring_rates"]

@@ -181,6 +181,8 @@ SIGNATURES = {
     "gatres_sensitivity_spread": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _P]),
     "gatres_loo_residuals": (C.c_int, [_P, _P, _P, _I32, _I64, _I64, _I32, _I32, _P, _I32, _F64, _F64, _P, _I32, _P, _P, _P]),
     "gatres_screen_reject": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "gatres_cusum_scan": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "gatres_monitor_latch": (C.c_int, [_P, _P, _I64, _I32, _I64, _I64, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "gatres_version": (C.c_char_p, []),
 }
 
@@ -198,6 +200,7 @@ NODE_SPREAD_RECORD = 4                              # GATRES_NODE_SPREAD_RECORD 
 LAYOUT_PAIR_RECORD = 4                              # GATRES_LAYOUT_PAIR_RECORD (gatres_layout_pair_errors)
 LAYOUT_ERROR_RECORD = 4                             # GATRES_LAYOUT_ERROR_RECORD (gatres_layout_error_reduce)
 SENSITIVITY_RECORD = 5                              # GATRES_SENSITIVITY_RECORD (gatres_sensitivity_fold)
+CUSUM_STATE, CUSUM_RECORD = 4, 6                    # GATRES_CUSUM_STATE, GATRES_CUSUM_RECORD (gatres_cusum_scan)
 CRITERIA = {"mse": LOSS_MSE, "mae": LOSS_MAE, "sce": LOSS_SCE}      # the reference's train.py --criterion choices
 
 

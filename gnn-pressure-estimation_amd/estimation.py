@@ -55,6 +55,13 @@ with the K x K layouts "all ones, zero diagonal", the forward and ``gatres_loo_r
 ``gatres_node_error_quantiles`` launch on the ``[S, K]`` matrices), ``screen`` rejects, per snapshot and round, the available
 sensor that exceeds its bound by the largest factor (``gatres_screen_reject``), ``estimate_screened`` estimates without the
 rejected readings, ``screening_report`` back-tests all of it with planted faults.  screening.py restates the launches.
+
+A sensor that drifts.  A reading that is off by a fraction of its bound for a long time passes every per-snapshot screening.
+``monitor`` / ``monitor_store`` read the S snapshots as a time series: per round the leave-one-out pass, ``gatres_cusum_scan`` (a
+two-sided CUSUM per sensor along time as one parallel scan in int64 fixed point, against the ``MonitorBaseline`` of
+``calibrate_monitor``) and ``gatres_monitor_latch`` (per series the sensor that alarmed first leaves the availability from its
+estimated onset on); ``estimate_monitored`` estimates without it, ``monitoring_report`` back-tests with planted ramps.  The state
+is carried, so readings may arrive in chunks.  monitoring.py restates the launches.
 """
 from __future__ import annotations
 
@@ -71,6 +78,8 @@ from .sensitivity import (SENSITIVITY_RECORD, influence_from_table, linear_sprea
                           sensitivity_rows_from_gx, sensitivity_seeds)
 from .screening import (fault_draws, loo_layouts, loo_residuals_from_estimates, screen_ref, screen_reject_ref,  # noqa: F401
                         screening_rates)
+from .monitoring import (SINCE as MONITOR_SINCE, cusum_compose, cusum_fixed, cusum_scan_ref, drift_draws,  # noqa: F401
+                         drift_offsets, monitor_baseline_from_moments, monitor_latch_ref, monitor_ref, monitoring_rates)
 from .snapshot_store import SnapshotStore
 
 NODE_ERROR_RECORD = _native.NODE_ERROR_RECORD
@@ -424,6 +433,70 @@ class ScreeningBounds:
     def from_state_dict(cls, d, device=None) -> "ScreeningBounds":
         return cls(d["levels"], torch.as_tensor(d["bounds"], dtype=torch.float32).contiguous(),
                    torch.as_tensor(d["counts"], dtype=torch.float64), d["observed_idx"], device=device)
+
+
+class MonitorBaseline:
+    """The in-control behaviour of the leave-one-out residuals of a sensor set, for the drift monitor: ``mu`` and ``inv_sigma``
+    (fp32 ``[K]`` on the device: what ``gatres_cusum_scan`` reads), ``sigma`` and ``counts`` (fp64 ``[K]`` on the device) and
+    ``observed_idx``.  Built from ``mu`` and ``sigma`` as arrays or tensors (read to the host here, once; ``device``: where to
+    put the result): ``inv_sigma = float32(1 / sigma)`` is formed on the host in fp64, so that the statement of the scan holds
+    no device division.  A zero or NaN ``sigma`` leaves a sensor whose entries are never counted."""
+
+    def __init__(self, mu, sigma, counts, observed_idx, device=None):
+        self.observed_idx = [int(i) for i in observed_idx]
+        K = len(self.observed_idx)
+
+        def host(v, what):
+            a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+            if a.shape != (K,):
+                raise ValueError(f"{what} must hold {K} values, one per sensor")
+            return np.ascontiguousarray(a, dtype=np.float64)
+
+        if device is None:
+            device = mu.device if isinstance(mu, torch.Tensor) else "cpu"
+        mu, sigma, counts = host(mu, "mu"), host(sigma, "sigma"), host(counts, "counts")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            inv = (1.0 / sigma).astype(np.float32)
+        self.mu = torch.from_numpy(mu.astype(np.float32)).to(device)
+        self.inv_sigma = torch.from_numpy(inv).to(device)
+        self.sigma = torch.from_numpy(sigma).to(device)
+        self.counts = torch.from_numpy(counts).to(device)
+
+    @property
+    def device(self) -> torch.device:
+        return self.mu.device
+
+    def state_dict(self) -> Dict[str, object]:
+        """CPU tensors and plain lists (one read-back of each tensor), for ``torch.save``."""
+        return {"mu": self.mu.detach().cpu(), "sigma": self.sigma.detach().cpu(), "counts": self.counts.detach().cpu(),
+                "observed_idx": list(self.observed_idx)}
+
+    @classmethod
+    def from_state_dict(cls, d, device=None) -> "MonitorBaseline":
+        return cls(torch.as_tensor(d["mu"]), torch.as_tensor(d["sigma"]), torch.as_tensor(d["counts"]), d["observed_idx"],
+                   device="cpu" if device is None else device)
+
+
+class MonitorResult:
+    """What ``PressureEstimator.monitor`` leaves, all on the device: ``available_out`` (uint8 ``[S, K]``), ``latched`` (int32
+    ``[E, R]``: the sensor round ``r`` latched in series ``e``, -1: none), ``latched_rec`` (int64 ``[E, R, 6]``: its record
+    ``[alarm, side, onset, n, sum q, statistic]``), ``records0`` (int64 ``[E, K, 6]``: every sensor's record of round 0),
+    ``state`` (int64 ``[E, K, 4]``: the last round's state after the last row, what the next chunk's call takes) and
+    ``stat_pos`` / ``stat_neg`` (fp32 ``[S, K]``, round 0's paths in sigma; ``None`` unless asked for).  The tensors are a
+    scratch kept on the estimator: the next ``monitor`` / ``estimate_monitored`` overwrites them."""
+
+    def __init__(self, available_out, latched, latched_rec, records0, state, stat_pos=None, stat_neg=None):
+        self.available_out, self.latched, self.latched_rec, self.records0 = available_out, latched, latched_rec, records0
+        self.state, self.stat_pos, self.stat_neg = state, stat_pos, stat_neg
+
+    def shift(self, baseline: MonitorBaseline) -> torch.Tensor:
+        """The estimated size of each latched sensor's shift, fp64 ``[E, R]`` in physical units: the mean standardised
+        residual over the excursion that alarmed, ``sigma[k*] * sum q / (65536 n)``; NaN where nothing was latched.  Device
+        torch operations, nothing read back."""
+        k = self.latched.clamp(min=0).long()
+        mean_z = self.latched_rec[..., 4].double() / (65536.0 * self.latched_rec[..., 3].double())
+        nan = torch.full_like(mean_z, float("nan"))
+        return torch.where(self.latched >= 0, baseline.sigma[k] * mean_z, nan)
 
 
 def greedy_selection(score_round, candidates: Sequence[int], num: int) -> Tuple[List[int], List[float]]:
@@ -1548,6 +1621,223 @@ class PressureEstimator:
         self.estimate(faulted, est, available=without)
         mae["oracle"], _ = judged()
         return {**screening_rates(rej, fault_col), "nonsensor_mae": mae, "fault_col": fault_col, "rejected": rej}
+
+    # ---- monitoring: a sensor that drifts --------------------------------------------------------------------------------------
+    def calibrate_monitor(self, store, *, available: Optional[torch.Tensor] = None) -> MonitorBaseline:
+        """The in-control mean and spread of every sensor's leave-one-out residual, from a clean held-out ``store``: one
+        ``loo_residuals_store`` pass and one ``gatres_node_error_moments`` launch on the ``[S, K]`` matrices -- ``pred`` as the
+        estimates, the store's values at the sensors as the truth, the K sensors as the K "nodes" (with ``available`` gaps:
+        ``gatres_node_error_moments_available``, which counts the readings that are there).  ONE read-back, of that ``[K, 8]``
+        table; on the host in fp64 ``mu = -sum e / n`` (the table's ``e`` is prediction - reading), ``sigma = sqrt(max(sum e^2
+        / n - mu^2, 0))`` and ``inv_sigma = float32(1 / sigma)``: ``monitor_baseline_from_moments``."""
+        _, pred = self.loo_residuals_store(store, available=available)
+        S, K = len(store), len(self.observed_idx)
+        truth = store.data.index_select(1, self._observed).contiguous()          # (scaled: the launch descales it as the pass did)
+        sensors = torch.arange(K, dtype=torch.int32, device=self.device)
+        table = torch.empty((K, NODE_ERROR_RECORD), dtype=torch.float64, device=self.device)
+        lib = _native.load()
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream(self.device)
+            if available is None:
+                _native.check(lib.gatres_node_error_moments(
+                    pred.data_ptr(), truth.data_ptr(), S, K, self.scale, self.offset, sensors.data_ptr(), K, table.data_ptr(),
+                    stream), "gatres_node_error_moments")
+            else:
+                missing = (available == 0).to(torch.uint8)               # (counted there: unless that entry is non-zero)
+                _native.check(lib.gatres_node_error_moments_available(
+                    pred.data_ptr(), truth.data_ptr(), S, K, self.scale, self.offset, sensors.data_ptr(), K, missing.data_ptr(),
+                    table.data_ptr(), stream), "gatres_node_error_moments_available")
+        b = monitor_baseline_from_moments(table.cpu().numpy())
+        return MonitorBaseline(b["mu"], b["sigma"], b["counts"], self.observed_idx, device=self.device)
+
+    def _check_monitor(self, baseline, S: int, kappa, threshold, series_length, first_index, max_latch, min_sensors, since,
+                       state) -> Tuple[int, int, int, int, int, int, int, int]:
+        """``(kappa_q, h_q, E, T, t0, R, min_sensors, since)`` of a monitoring call, or a ``ValueError``."""
+        K = len(self.observed_idx)
+        if not isinstance(baseline, MonitorBaseline):
+            raise ValueError("baseline must be the MonitorBaseline of calibrate_monitor")
+        if baseline.observed_idx != self.observed_idx:
+            raise ValueError(f"the baseline was calibrated for the sensors {baseline.observed_idx}, the estimator's are "
+                             f"{self.observed_idx}")
+        if baseline.device != self.device:
+            raise ValueError(f"the baseline must be on {self.device} (got {baseline.device})")
+        fixed = []
+        for name, v in (("kappa", kappa), ("threshold", threshold)):
+            try:
+                fixed.append(cusum_fixed(v))
+            except ValueError:
+                raise ValueError(f"{name} must be a number in [0, 32768] (in sigma); got {v!r}") from None
+        for name, v, lo, hi in (("max_latch", max_latch, 1, None), ("min_sensors", min_sensors, 1, K),
+                                ("first_index", first_index, 0, 2 ** 61 - 1),
+                                ("series_length", S if series_length is None else series_length, 1, 2 ** 30 - 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+                raise ValueError(f"{name} must be an integer in [{lo}, {'...' if hi is None else hi}]; got {v!r}")
+        T = S if series_length is None else int(series_length)
+        if S % T:
+            raise ValueError(f"the {S} snapshots are no whole number of series of series_length {T}")
+        if since not in MONITOR_SINCE:
+            raise ValueError(f"since must be one of {sorted(MONITOR_SINCE)}; got {since!r}")
+        E = S // T
+        if state is not None and (not isinstance(state, torch.Tensor) or state.dtype != torch.int64
+                                  or tuple(state.shape) != (E, K, _native.CUSUM_STATE) or state.device != self.device
+                                  or not state.is_contiguous()):
+            raise ValueError(f"state must be int64 contiguous [{E}, {K}, {_native.CUSUM_STATE}] on {self.device}: the state of "
+                             "an earlier call's result")
+        return fixed[0], fixed[1], E, T, int(first_index), int(max_latch), int(min_sensors), MONITOR_SINCE[since]
+
+    def _run_monitor(self, src: torch.Tensor, layout: int, normalise: int, S: int, baseline, kappa, threshold, series_length,
+                     first_index, max_latch, min_sensors, since, available, nan_is_missing: bool, state,
+                     paths: bool) -> MonitorResult:
+        K = self._loo_ready()
+        kq, hq, E, T, t0, R, min_sensors, since = self._check_monitor(baseline, S, kappa, threshold, series_length, first_index,
+                                                                      max_latch, min_sensors, since, state)
+        if available is not None:
+            self._check_available(available, S)
+        i64, rec = torch.int64, _native.CUSUM_RECORD
+        avail = self._scratch("monitor_available", (S, K), torch.uint8)
+        latched = self._scratch("monitor_latched", (E, R), torch.int32)
+        latched_rec = self._scratch("monitor_latched_rec", (E, R, rec), i64)
+        records0 = self._scratch("monitor_records0", (E, K, rec), i64)
+        later = self._scratch("monitor_records", (E, K, rec), i64) if R > 1 else None
+        state_out = self._scratch("monitor_state", (E, K, _native.CUSUM_STATE), i64)
+        resid, pred = self._scratch("monitor_resid", (S, K)), self._scratch("monitor_pred", (S, K))
+        pos = self._scratch("monitor_stat_pos", (S, K)) if paths else None
+        neg = self._scratch("monitor_stat_neg", (S, K)) if paths else None
+        state_in = None
+        if state is not None:                                       # (every round starts from it; it may be `state_out` itself)
+            state_in = self._scratch("monitor_state_in", (E, K, _native.CUSUM_STATE), i64)
+            state_in.copy_(state)
+        if available is None:
+            avail.fill_(1)
+        else:
+            avail.copy_(available)
+        lib = _native.load()
+        for rnd in range(R):
+            # (round 0 of complete readings is the pass without an availability: the same bits, nothing to load per pair)
+            self._run_loo(src, layout, normalise, avail if rnd > 0 or available is not None else None, nan_is_missing, resid, pred)
+            records = records0 if rnd == 0 else later
+            with torch.cuda.device(self.device):
+                stream = _native.current_stream(self.device)
+                _native.check(lib.gatres_cusum_scan(
+                    resid.data_ptr(), baseline.mu.data_ptr(), baseline.inv_sigma.data_ptr(), avail.data_ptr(), S, K, T, t0, kq, hq,
+                    _native.ptr(state_in), state_out.data_ptr(), records.data_ptr(), _native.ptr(pos if rnd == 0 else None),
+                    _native.ptr(neg if rnd == 0 else None), stream), "gatres_cusum_scan")
+                _native.check(lib.gatres_monitor_latch(
+                    records.data_ptr(), avail.data_ptr(), S, K, T, t0, since, min_sensors, rnd, R, latched.data_ptr(),
+                    latched_rec.data_ptr(), stream), "gatres_monitor_latch")
+        return MonitorResult(avail, latched, latched_rec, records0, state_out, pos, neg)
+
+    def monitor(self, readings: torch.Tensor, baseline: MonitorBaseline, *, kappa: float = 0.5, threshold: float = 5.0,
+                series_length: Optional[int] = None, first_index: int = 0, max_latch: int = 1, min_sensors: int = 1,
+                since: str = "onset", available: Optional[torch.Tensor] = None, nan_is_missing: bool = False,
+                state: Optional[torch.Tensor] = None, paths: bool = False) -> MonitorResult:
+        """Which sensor has been drifting, and since when?  The S rows of ``readings`` are a TIME SERIES here (``series_length``:
+        E = S / series_length independent series of consecutive rows; ``None``: one).  ``max_latch`` rounds of one leave-one-out
+        pass under the current availability, one ``gatres_cusum_scan`` and one ``gatres_monitor_latch``: per sensor a two-sided
+        CUSUM of the standardised residual ``z = (resid - mu) / sigma`` with allowance ``kappa`` and threshold ``threshold``
+        (both in sigma), ``P = max(0, P + z - kappa)``, ``M = max(0, M - z - kappa)``, in int64 fixed point (2^-16 sigma), so
+        the result is a function of the inputs alone; an entry that is missing, NaN or of a sensor without a spread is not
+        counted and holds the state.  The first step with ``P`` or ``M`` above the threshold is the sensor's alarm, the step
+        after the statistic's last zero before it the estimated onset.  Per series and round the sensor that alarmed first
+        (ties: the larger statistic, then the first) is LATCHED: taken out of the availability from its onset on
+        (``since="alarm"``: from the alarm on), as long as ``min_sensors`` sensors stay.  ONE latch per round, for the reason
+        ``screen`` gives: a drifting sensor bends its neighbours' leave-one-out predictions, so they are judged again without
+        it.  A round after a clean round repeats it and latches nothing: skipping it would need a read-back.
+
+        Readings that arrive in chunks: pass ``state=previous.state`` and ``first_index=`` the number of rows seen so far; the
+        paths, the final state, the first alarm and its onset are those of one call over all rows (a record's ``n`` and
+        ``sum q`` count this call's rows only).  Every round starts from ``state``; nothing is reset after an alarm.
+
+        Returns a ``MonitorResult``: all on the device, nothing is read back, and the tensors are a scratch kept on the
+        estimator -- nothing is allocated after the first call, the next ``monitor`` / ``estimate_monitored`` overwrites them.
+        ``paths=True`` adds round 0's ``stat_pos`` / ``stat_neg``.
+
+        What the numbers mean: with independent standard-normal ``z``, ``kappa=0.5`` and ``threshold=5`` give the textbook
+        two-sided in-control run length of about 465 counted readings.  What they do not: real leave-one-out residuals are
+        autocorrelated in time, so the defaults are a starting point; the clean-series false-alarm rate of
+        ``monitoring_report`` on a held-out store of one's own is the number to tune against.  No coverage statement is made."""
+        self._check_readings(readings)
+        return self._run_monitor(readings, _native.OBSERVED_READINGS, self._normalise, int(readings.shape[0]), baseline, kappa,
+                                 threshold, series_length, first_index, max_latch, min_sensors, since, available, nan_is_missing,
+                                 state, paths)
+
+    def monitor_store(self, store, baseline: MonitorBaseline, *, kappa: float = 0.5, threshold: float = 5.0,
+                      series_length: Optional[int] = None, first_index: int = 0, max_latch: int = 1, min_sensors: int = 1,
+                      since: str = "onset", available: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+                      paths: bool = False) -> MonitorResult:
+        """``monitor`` over the snapshots of a ``SnapshotStore`` in their order: the readings are the store's values at the
+        sensors, as in ``loo_residuals_store``."""
+        self._check_store(store)
+        return self._run_monitor(store.data, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, len(store), baseline, kappa,
+                                 threshold, series_length, first_index, max_latch, min_sensors, since, available, False, state,
+                                 paths)
+
+    def estimate_monitored(self, readings: torch.Tensor, baseline: MonitorBaseline, *, out: Optional[torch.Tensor] = None,
+                           nan_is_missing: bool = False, **kw) -> Tuple[torch.Tensor, MonitorResult]:
+        """Readings in; estimates, and which sensors were latched as drifting, out: ``monitor`` (its keywords) and then the
+        ordinary three-launch ``estimate`` pass with ``available_out``.  Returns ``(est [S, N_g], result)``; ``out`` as in
+        ``estimate``.  A latched sensor's node carries the model's estimate from its onset on.  Nothing is read back."""
+        self._check_readings(readings)
+        if out is not None:
+            self._result(int(readings.shape[0]), out)               # (refused before the pass)
+        result = self.monitor(readings, baseline, nan_is_missing=nan_is_missing, **kw)
+        return self.estimate(readings, out, available=result.available_out, nan_is_missing=nan_is_missing), result
+
+    def monitoring_report(self, store, baseline: MonitorBaseline, *, series_length: int, drift_rate, drift_share: float = 0.5,
+                          min_lead: Optional[int] = None, seed: int = 0, kappa: float = 0.5, threshold: float = 5.0,
+                          max_latch: int = 1, min_sensors: int = 1, since: str = "onset") -> Dict[str, object]:
+        """Back-test of the monitor over ``store``, read as series of ``series_length`` snapshots, with planted drifts.
+        ``drift_draws(seed, E, T, K, drift_share, min_lead)`` chooses one drifting sensor and one onset in ``[min_lead, T -
+        min_lead)`` (default ``T // 4``) in a ``drift_share`` of the series; ``drift_offsets`` adds the ramp ``drift_rate[k] *
+        (t - onset + 1)`` (physical units per step; one value or K) to the store's descaled readings (host, uploaded once).
+        Four passes, one read-back each: the clean readings, the drifted readings unmonitored, the drifted readings through
+        ``estimate_monitored``, and the drifted readings with the drifting sensor taken out by hand from its true onset (the
+        best a monitor can do).  Returns ``monitoring_rates`` of the third pass (detection, misidentification, the
+        false-alarm rate on clean series, detection delays, the onset error), ``nonsensor_mae`` (a dict: ``clean``,
+        ``drifted``, ``monitored``, ``oracle``: the MAE over the nodes outside ``observed_idx``, as ``error_map`` pools it),
+        ``draws``, ``latched`` and ``latched_rec`` (numpy)."""
+        self._check_store(store)
+        K, S, N = self._loo_ready(), len(store), self.nodes_per_graph
+        _, _, E, T, _, R, _, _ = self._check_monitor(baseline, S, kappa, threshold, series_length, 0, max_latch, min_sensors,
+                                                     since, None)
+        draws = drift_draws(seed, E, T, K, drift_share, T // 4 if min_lead is None else min_lead)
+        offsets = drift_offsets(draws, T, K, drift_rate)
+        without = np.ones((S, K), dtype=np.uint8)
+        for e, (k, onset) in enumerate(draws.tolist()):
+            if k >= 0:
+                without[e * T + onset:(e + 1) * T, k] = 0
+        readings = store.descale(store.data.index_select(1, self._observed)).contiguous()
+        drifted = (readings + torch.from_numpy(offsets).to(self.device)).contiguous()
+        without = torch.from_numpy(without).to(self.device)
+        est = torch.empty((S, N), dtype=torch.float32, device=self.device)
+        lib = _native.load()
+
+        def judged(extra=()):                                       # (one read-back: the moments, and the latches behind them)
+            table = torch.empty((N, NODE_ERROR_RECORD), dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                _native.check(lib.gatres_node_error_moments(
+                    est.data_ptr(), store.data.data_ptr(), S, N, self.scale, self.offset, self._observed.data_ptr(), K,
+                    table.data_ptr(), _native.current_stream(self.device)), "gatres_node_error_moments")
+            # (the integers travel as the bits of doubles: exact at any size)
+            flat = torch.cat([table.reshape(-1)] + [t.to(torch.int64).reshape(-1).view(torch.float64) for t in extra])
+            host = flat.cpu().numpy()
+            return (float(error_map_from_moments(host[:N * NODE_ERROR_RECORD])["hidden_mae"]),
+                    host[N * NODE_ERROR_RECORD:].view(np.int64))
+
+        mae = {}
+        self.estimate(readings, est)
+        mae["clean"], _ = judged()
+        self.estimate(drifted, est)
+        mae["drifted"], _ = judged()
+        _, res = self.estimate_monitored(drifted, baseline, out=est, kappa=kappa, threshold=threshold, series_length=T,
+                                         max_latch=max_latch, min_sensors=min_sensors, since=since)
+        mae["monitored"], ints = judged((res.latched, res.latched_rec))
+        latched = ints[:E * R].reshape(E, R).copy()
+        latched_rec = ints[E * R:].reshape(E, R, _native.CUSUM_RECORD).copy()
+        self.estimate(drifted, est, available=without)
+        mae["oracle"], _ = judged()
+        return {**monitoring_rates(latched_rec, latched, draws), "nonsensor_mae": mae, "draws": draws, "latched": latched,
+                "latched_rec": latched_rec}
 
 
 class SensitivityMap:

@@ -1169,6 +1169,62 @@ int gatres_screen_reject(const float* resid, const float* bound, const float* in
                          int64_t num_snapshots, int32_t num_observed, int32_t min_sensors, int32_t round, int32_t max_rounds,
                          int32_t* rejected, uint8_t* flagged, void* stream);
 
+/* Drift monitoring of sensor readings (symbols only: the ABI stays; k_monitor.hip).  A sensor that drifts by a fraction of its
+ * screening bound per step never exceeds a per-snapshot bound; a two-sided CUSUM per sensor along time sees it.  resid[S][K] is
+ * the matrix gatres_loo_residuals writes, read as E = S / T independent SERIES of T = series_length consecutive rows (series e:
+ * rows [eT, (e + 1)T)); first_index = t0 is the global time index of row 0 of every series, so that two calls on consecutive
+ * chunks, the second with the first's state_out and t0 advanced, give what one call gives.
+ *
+ * gatres_cusum_scan.  mu[K], inv_sigma[K]: device float; available[S][K]: device uint8 or NULL; kappa_q, h_q: the allowance and
+ * the threshold in units of 2^-16 sigma, llrint(kappa * 65536.0) formed by the caller.  All state is int64 in those units.
+ * Entry (t, k) is COUNTED when available is NULL or non-zero there, resid is no NaN and
+ *   z = fp32(fp32(resid - mu[k]) * inv_sigma[k])          (two roundings, no contraction)
+ * is no NaN.  z is clamped to +-32768.0f, q = llrintf(z * 65536.0f), a+ = q - kappa_q, a- = -q - kappa_q.  The state per
+ * (e, k) is int64[4] = {P, M, zP, zM}: from state_in (device [E][K][4]; P and M clamped into [0, 2^61] on entry) or, with
+ * state_in == NULL, {0, 0, t0, t0}.  At a counted step with global index tau = t0 + t
+ *   P = max(0, P + a+), and zP = tau + 1 if P == 0;     M = max(0, M + a-), and zM = tau + 1 if M == 0
+ * and at any other step nothing changes.  The first counted step at which P > h_q or M > h_q (strictly) is the ALARM; if both
+ * hold there the larger statistic wins, a tie going to +.  records[E][K][GATRES_CUSUM_RECORD] (device int64):
+ *   [0] the alarm's tau, or -1   [1] side +1 / -1, or 0   [2] onset: zP or zM of that side after that step, the first snapshot
+ *   of the excursion that alarmed   [3] n: the counted entries of this call with tau in [max(onset, t0), alarm]
+ *   [4] the sum of q over those entries   [5] the alarming statistic                  ([1] .. [5] are 0 without an alarm)
+ * The scan goes on after the alarm without a reset; state_out (device [E][K][4]; may be NULL, may equal state_in) is the state
+ * after the last row.  stat_pos, stat_neg (device float [S][K], both or neither NULL) receive __ll2float_rn(P) * 2^-16f and the
+ * same of M at every row, counted or not.
+ * One workgroup per (series, sensor) on a capped grid that strides over the pairs; every thread owns a contiguous slice of the
+ * T rows and folds it into the summary (A, C) of the map g -> max(C, g + A) per side, (A1, C1) o (A2, C2) = (A1 + A2,
+ * max(C2, C1 + A2)) with the identity C = -2^62; an exclusive scan of the summaries (wave shuffles, LDS across waves) gives every
+ * slice its carry-in, a second sweep walks the slice with the true values, an exclusive max-scan of the slices' last zeros and
+ * a min-reduce of their first alarms give the record, a third sweep sums [3] and [4].  Integer addition and max are
+ * associative: the bits of the sequential loop (monitoring.cusum_scan_ref), whatever the geometry.  No atomics.
+ * GATRES_E_BADARG before any launch: a NULL resid, mu, inv_sigma or records; num_snapshots, num_observed or series_length < 1;
+ * num_snapshots no multiple of series_length; series_length >= 2^30 (the bound that keeps every sum below 2^63);
+ * first_index < 0 or above 2^61 - 1, a num_snapshots whose byte counts do not fit; kappa_q or h_q outside [0, 2^31]; one of stat_pos / stat_neg NULL and the other not; state_out, records,
+ * stat_pos or stat_neg overlapping resid, mu, inv_sigma, available, state_in or one another (state_out == state_in excepted). */
+#define GATRES_CUSUM_STATE 4
+#define GATRES_CUSUM_RECORD 6
+int gatres_cusum_scan(const float* resid, const float* mu, const float* inv_sigma, const uint8_t* available,
+                      int64_t num_snapshots, int32_t num_observed, int64_t series_length, int64_t first_index, int64_t kappa_q,
+                      int64_t h_q, const int64_t* state_in, int64_t* state_out, int64_t* records, float* stat_pos,
+                      float* stat_neg, void* stream);
+
+/* One latching round, one workgroup per series.  records[E][K][GATRES_CUSUM_RECORD] as gatres_cusum_scan writes them;
+ * available[S][K] (device uint8), UPDATED IN PLACE; latched[E][max_rounds] (device int32), of which column `round` is written
+ * and the columns before it are read; latched_rec[E][max_rounds][GATRES_CUSUM_RECORD] (device int64), of which row `round` is
+ * written.  Sensor k is a CANDIDATE of series e when records[e][k][0] >= 0 and k is not in latched[e][0 .. round).  The
+ * candidate with the smallest alarm index is chosen, ties going to the larger records[..][5], then to the smaller k: one total
+ * order, used by a lane's own best and by the butterfly over the lanes.  If a candidate k* exists and
+ * K - #{latched[e][r] >= 0, r < round} - 1 >= min_sensors:
+ *   latched[e][round] = k*, latched_rec[e][round] = its record, and available[row][k*] = 0 for every row of the series with
+ *   tau >= max(onset, t0) (since == 0) or tau >= alarm (since == 1);
+ * otherwise latched[e][round] = -1, latched_rec[e][round] is six zeros and available is untouched.
+ * GATRES_E_BADARG before any launch: a NULL pointer; num_snapshots, num_observed or series_length < 1; num_snapshots no multiple
+ * of series_length; series_length >= 2^30; first_index < 0 or above 2^61 - 1; since other than 0 or 1; min_sensors < 1; max_rounds < 1; round
+ * outside [0, max_rounds); available, latched or latched_rec overlapping records or one another. */
+int gatres_monitor_latch(const int64_t* records, uint8_t* available, int64_t num_snapshots, int32_t num_observed,
+                         int64_t series_length, int64_t first_index, int32_t since, int32_t min_sensors, int32_t round,
+                         int32_t max_rounds, int32_t* latched, int64_t* latched_rec, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
