@@ -9,7 +9,7 @@ from .graph_plan import GraphPlan, PlanCache
 from .snapshot_store import SnapshotStore
 from .multi_snapshot_store import MultiSnapshotStore
 from .train_step import FitHistory, GATResTrainer, internal_train
-from .sensor_layout import sensor_layout_draws
+from .sensor_layout import sensor_layout_draws, sensor_layout_noise
 from .estimation import (ErrorBounds, MonitorBaseline, MonitorResult, PressureEstimator, ScreeningBounds, SensitivityMap, conformal_rank, coverage_from_table, greedy_selection,
                          layout_scores_from_table, node_error_bounds, observed_from_names, reading_noise)
 from .screening import fault_draws, loo_layouts, loo_residuals_from_estimates, screen_ref, screen_reject_ref, screening_rates
@@ -21,7 +21,7 @@ from .sensitivity import (influence_from_table, linear_spread_ref, sensitivity_f
 __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "SimpleConv", "Linear", "GraphPlan", "PlanCache",
            "GATResTrainer", "FitHistory", "internal_train", "epoch_control", "select_model", "config_gatres_small", "config_gatres_large", "build_native", "wdn_synth", "dp", "evaluation", "wdn_io", "SnapshotStore",
            "MultiSnapshotStore", "estimation", "PressureEstimator", "observed_from_names", "reading_noise",
-           "layout_scores_from_table", "greedy_selection", "sensor_layout_draws", "ErrorBounds", "conformal_rank",
+           "layout_scores_from_table", "greedy_selection", "sensor_layout_draws", "sensor_layout_noise", "ErrorBounds", "conformal_rank",
            "node_error_bounds", "coverage_from_table", "SensitivityMap", "influence_from_table", "linear_spread_ref",
            "sensitivity_fold_ref", "sensitivity_rows_from_gx", "sensitivity_seeds", "ScreeningBounds", "screening", "loo_layouts",
            "loo_residuals_from_estimates", "screen_reject_ref", "screen_ref", "fault_draws", "screening_rates", "MonitorBaseline", "MonitorResult",

@@ -99,6 +99,8 @@ SIGNATURES = {
     "gatres_stage_rows_mask": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _F64, _U64, _P, _P, _P]),
     "gatres_stage_rows_mask_required": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _F64, _U64, _P, _P, _I32, _P, _P]),
     "gatres_stage_rows_mask_sensors": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _P, _I32, _F64, _F64, _F64, _U64, _P, _P, _P]),
+    "gatres_stage_rows_mask_sensors_noisy": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _P, _I32, _F64, _F64, _F64, _U64, _P, _P, _P,
+                                                       _U64, _P]),
     "gatres_stage_multi_rows_mask_required": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _P, _F64, _U64, _P, _P, _P, _P, _P]),
     "gatres_gather_multi_rows": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P]),
     "gatres_masked_metrics": (C.c_int, [_P, _P, _P, _I32, _F64, _F64, _P, _I32, _I32, _P, _P]),

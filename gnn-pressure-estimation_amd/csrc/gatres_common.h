@@ -131,6 +131,19 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   return z ^ (z >> 31);
 }
 
+// The measurement-noise generator of gatres_stage_observed_noisy (k_estimate.hip) and gatres_stage_rows_mask_sensors_noisy
+// (k_stage.hip); gatres.h states it.  One standard normal by Box-Muller from the 48 upper bits of one hash: u1 in (0, 1] and u2
+// in [0, 1) are 24-bit integers times 2^-24, both exact in fp32.  z is a pure function of (seed, member, row, K, k).
+__device__ __forceinline__ uint64_t obs_noise_stream(uint64_t seed, uint64_t member) {
+  return mix64(seed + 0x9E3779B97F4A7C15ULL * (member + 1));
+}
+__device__ __forceinline__ float obs_noise(uint64_t stream, long long row, int K, int k) {
+  const uint64_t h = mix64(stream + 0xBF58476D1CE4E5B9ULL * ((uint64_t)row * (uint64_t)K + (uint64_t)k + 1));
+  const float u1 = __fmul_rn((float)(uint32_t)((h >> 40) + 1), 0x1p-24f);
+  const float u2 = __fmul_rn((float)(uint32_t)((h >> 8) & 0xFFFFFFu), 0x1p-24f);
+  return __fmul_rn(sqrtf(__fmul_rn(-2.f, logf(u1))), cosf(__fmul_rn(6.283185307179586f, u2)));
+}
+
 __device__ __forceinline__ float gatres_leaky(float v) { return v > 0.f ? v : v * GATRES_NEG_SLOPE; }
 
 // The reference's other training criteria (gatres.h: GATRES_LOSS_MAE, GATRES_LOSS_SCE) on one masked node: returns the node's

@@ -79,17 +79,7 @@ struct ObsTargets {
   int vec;                 // g_out is 16-byte aligned: whole chunks are one float4 store where x_dst's are
 };
 
-// One standard normal by Box-Muller from the 48 upper bits of one hash (gatres.h states the generator): u1 in (0, 1] and u2 in
-// [0, 1) are 24-bit integers times 2^-24, both exact in fp32.
-__device__ __forceinline__ uint64_t obs_noise_stream(uint64_t seed, uint64_t member) {
-  return mix64(seed + 0x9E3779B97F4A7C15ULL * (member + 1));
-}
-__device__ __forceinline__ float obs_noise(uint64_t stream, long long row, int K, int k) {
-  const uint64_t h = mix64(stream + 0xBF58476D1CE4E5B9ULL * ((uint64_t)row * (uint64_t)K + (uint64_t)k + 1));
-  const float u1 = __fmul_rn((float)(uint32_t)((h >> 40) + 1), 0x1p-24f);
-  const float u2 = __fmul_rn((float)(uint32_t)((h >> 8) & 0xFFFFFFu), 0x1p-24f);
-  return __fmul_rn(sqrtf(__fmul_rn(-2.f, logf(u1))), cosf(__fmul_rn(6.283185307179586f, u2)));
-}
+// (obs_noise_stream / obs_noise, the generator: gatres_common.h -- the layout staging launch of k_stage.hip draws from it too)
 
 template <bool AVAIL, bool NOISE, bool LAYOUTS, bool TARGETS>
 __global__ __launch_bounds__(OBS_T) void stage_observed_kernel(const float* __restrict__ src, int readings, long long src_rows,

@@ -6,6 +6,7 @@
 //   gatres_stage_rows_mask                  collation of rows of ONE snapshot matrix [S][N], then the sampler
 //   gatres_stage_rows_mask_required         ... then the sampler that always masks the required (sensor) nodes
 //   gatres_stage_rows_mask_sensors          ... then, per graph, the mask of a FIXED sensor layout or the sampler's
+//   gatres_stage_rows_mask_sensors_noisy    ... with measurement noise on the readings the layout keeps, drawn in the launch
 //   gatres_stage_multi_rows_mask_required   collation from SEVERAL snapshot matrices (one per water network), required sampler
 //   gatres_gather_multi_rows                that collation alone, for num_batches x num_graphs graphs in one launch
 // A collated graph's row is contiguous in the source and in the destination: copy_row walks it 16 bytes per lane where the two
@@ -112,34 +113,62 @@ constexpr int SENS_TILE = 4 * SENS_T;          // mask bytes of one LDS pass: on
 // is [lo, hi); tiles start at lo rounded down to a multiple of four, so that thread t of a tile holds the four bytes of one
 // aligned 32-bit word (words_ok: the mask's address is a multiple of four; else byte stores).  A word that straddles lo or hi
 // is stored byte by byte, only the bytes inside: the neighbouring slice's workgroup, or another graph's, writes the others.
+// NOISE (gatres_stage_rows_mask_sensors_noisy; the instantiation without it reads neither argument and is today's kernel): a
+// sensor that KEEPS its reading in a layout-mode graph is staged as data + sigma[k] * z in x_dst, z = obs_noise(...) keyed by
+// (noise_seed, member = step, source row, k).  Interleaved over the graph's workgroups (collate_graph), the element at a sensor
+// node may be copied by another workgroup than the one that owns the node's mask slice, and a later store of the noisy value
+// would race with it.  So here the mode is drawn before any store; a random-mode graph is collated as ever, and in a layout-mode
+// graph every workgroup copies its OWN slice of the row, meets the first tile's barrier and then, in the k-loop that opens
+// s_open[], stores the noisy value (read from data, not from x_dst) over its own clean copy: every element of x_dst has one
+// final writer, ordered by the workgroup's barrier.  Only lanes that hold a kept sensor with sigma[k] != 0 draw; sigma[k] == 0
+// leaves the clean copy, bit for bit.  y_dst (when it is another buffer) gets the clean row.
+template <bool NOISE>
 __global__ __launch_bounds__(SENS_T) void stage_rows_mask_sensors_kernel(
     const float* __restrict__ data, const long long* __restrict__ rows, int N, float* x_dst, float* y_dst,
     const int* __restrict__ node_ptr, const int* __restrict__ observed, int K, uint32_t t_drop, uint32_t t_share, double rate,
-    uint64_t seed, const uint64_t* __restrict__ step_counter, uint8_t* __restrict__ mask, int words_ok) {
+    uint64_t seed, const uint64_t* __restrict__ step_counter, uint8_t* __restrict__ mask, int words_ok,
+    const float* __restrict__ sigma, uint64_t noise_seed) {
   __shared__ uint32_t s_word[SENS_T];
   const int g = blockIdx.x / MASK_WGS, wq = blockIdx.x % MASK_WGS;
   const int tid = threadIdx.x;
-  collate_matrix_graph(data, rows, N, x_dst, y_dst, g, wq);
+  if constexpr (!NOISE) collate_matrix_graph(data, rows, N, x_dst, y_dst, g, wq);
   const uint64_t step = step_counter ? step_counter[0] : 0;
   const uint64_t base = seed + 0x9E3779B97F4A7C15ULL * (step + 1);
   const bool layout = (uint32_t)(mix64(base + 0x94D049BB133111EBULL * (uint64_t)(g + 1)) >> 40) < t_share;
   if (!layout) {
+    if constexpr (NOISE) collate_matrix_graph(data, rows, N, x_dst, y_dst, g, wq);
     mask_sample_graph<SENS_T, MASK_WGS>(node_ptr, rate, seed, step, mask, g, wq);
     return;
   }
   const int n0 = node_ptr[g], n = node_ptr[g + 1] - n0;
   const int per = (n + MASK_WGS - 1) / MASK_WGS, vlo = min(n, wq * per), vhi = min(n, vlo + per);
   const long long lo = (long long)n0 + vlo, hi = (long long)n0 + vhi;
+  // NOISE: the slice [clo, chi) of the row this workgroup copies -- the mask slice [vlo, vhi) of a graph of N nodes; cut from N,
+  // so that the copy stays inside the row whatever node_ptr says -- and the noise's stream of this step
+  const long long row = NOISE ? rows[g] : 0, xoff = (long long)g * N;
+  const int cper = (N + MASK_WGS - 1) / MASK_WGS, clo = min(N, wq * cper), chi = min(N, clo + cper);
+  uint64_t noise_stream = 0;
+  if constexpr (NOISE) {
+    copy_row(data + row * (long long)N + clo, x_dst + xoff + clo, y_dst && y_dst != x_dst ? y_dst + xoff + clo : nullptr, chi - clo,
+             tid, SENS_T);
+    noise_stream = obs_noise_stream(noise_seed, step);
+  }
   uint8_t* s_open = reinterpret_cast<uint8_t*>(s_word);          // [SENS_TILE]: 1 = hidden, 0 = a sensor that kept its reading
   for (long long t0 = lo & ~3LL; t0 < hi; t0 += SENS_TILE) {      // (uniform in the workgroup: every thread meets the barriers)
     s_word[tid] = 0x01010101u;
-    __syncthreads();
+    __syncthreads();                                              // (NOISE: the slice's clean copy is behind this barrier)
     for (int k = tid; k < K; k += SENS_T) {
       const int v = observed[k];
       const long long f = (long long)n0 + v;
       if (v >= vlo && v < vhi && f >= t0 && f < t0 + SENS_TILE &&
-          (uint32_t)(mix64(base + 0xBF58476D1CE4E5B9ULL * (uint64_t)(n0 + v + 1)) >> 40) >= t_drop)
+          (uint32_t)(mix64(base + 0xBF58476D1CE4E5B9ULL * (uint64_t)(n0 + v + 1)) >> 40) >= t_drop) {
         s_open[f - t0] = 0;
+        if constexpr (NOISE) {
+          const float sg = sigma[k];
+          if (v >= clo && v < chi && sg != 0.f)                    // (a sensor met in one tile pass only: one store)
+            x_dst[xoff + v] = __fadd_rn(data[row * (long long)N + v], __fmul_rn(sg, obs_noise(noise_stream, row, K, k)));
+        }
+      }
     }
     __syncthreads();
     const long long f = t0 + 4 * tid;
@@ -226,6 +255,11 @@ bool stage_args_ok(const int32_t* node_ptr, const uint8_t* mask, int32_t num_gra
 
 static_assert(sizeof(long long) == sizeof(int64_t), "row indices");
 
+static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+
 }  // namespace
 
 extern "C" int gatres_mask_generate(const int32_t* node_ptr, int32_t num_graphs, double mask_rate, uint64_t seed,
@@ -270,19 +304,47 @@ extern "C" int gatres_stage_rows_mask_required(const float* data, const int64_t*
   return gatres_launch_status();
 }
 
+// gatres_stage_rows_mask_sensors and its noisy sibling: one set of checks, one launch, the noise a compile-time fact.
+template <bool NOISE>
+static int stage_rows_mask_sensors(const float* data, const int64_t* rows, int32_t nodes_per_graph, float* x_dst, float* y_dst,
+                                   const int32_t* node_ptr, int32_t num_graphs, const int32_t* observed, int32_t num_observed,
+                                   double sensor_dropout, double layout_share, double mask_rate, uint64_t seed,
+                                   const uint64_t* step_counter, uint8_t* mask, const float* sigma, uint64_t noise_seed,
+                                   void* stream) {
+  if (!stage_args_ok(node_ptr, mask, num_graphs, mask_rate, true, data, rows, x_dst, nodes_per_graph)) return GATRES_E_BADARG;
+  if (!observed || num_observed < 1 || num_observed > nodes_per_graph) return GATRES_E_BADARG;
+  if (!(sensor_dropout >= 0.0 && sensor_dropout < 1.0) || !(layout_share >= 0.0 && layout_share <= 1.0)) return GATRES_E_BADARG;
+  if (NOISE) {
+    if (!sigma) return GATRES_E_BADARG;
+    const uint64_t total = (uint64_t)nodes_per_graph * (uint64_t)num_graphs, sb = 4 * (uint64_t)num_observed;
+    if (bytes_overlap(sigma, sb, x_dst, 4 * total) || bytes_overlap(sigma, sb, y_dst, 4 * total) ||
+        bytes_overlap(sigma, sb, mask, total)) return GATRES_E_BADARG;
+  }
+  const uint32_t t_drop = (uint32_t)(sensor_dropout * 16777216.0), t_share = (uint32_t)(layout_share * 16777216.0);
+  const int words_ok = (reinterpret_cast<uintptr_t>(mask) & 3u) == 0;
+  hipLaunchKernelGGL(stage_rows_mask_sensors_kernel<NOISE>, dim3((unsigned)num_graphs * MASK_WGS), dim3(SENS_T), 0,
+                     gatres_stream(stream), data, reinterpret_cast<const long long*>(rows), (int)nodes_per_graph, x_dst, y_dst,
+                     node_ptr, observed, (int)num_observed, t_drop, t_share, mask_rate, seed, step_counter, mask, words_ok, sigma,
+                     noise_seed);
+  return gatres_launch_status();
+}
+
 extern "C" int gatres_stage_rows_mask_sensors(const float* data, const int64_t* rows, int32_t nodes_per_graph, float* x_dst,
                                               float* y_dst, const int32_t* node_ptr, int32_t num_graphs, const int32_t* observed,
                                               int32_t num_observed, double sensor_dropout, double layout_share, double mask_rate,
                                               uint64_t seed, const uint64_t* step_counter, uint8_t* mask, void* stream) {
-  if (!stage_args_ok(node_ptr, mask, num_graphs, mask_rate, true, data, rows, x_dst, nodes_per_graph)) return GATRES_E_BADARG;
-  if (!observed || num_observed < 1 || num_observed > nodes_per_graph) return GATRES_E_BADARG;
-  if (!(sensor_dropout >= 0.0 && sensor_dropout < 1.0) || !(layout_share >= 0.0 && layout_share <= 1.0)) return GATRES_E_BADARG;
-  const uint32_t t_drop = (uint32_t)(sensor_dropout * 16777216.0), t_share = (uint32_t)(layout_share * 16777216.0);
-  const int words_ok = (reinterpret_cast<uintptr_t>(mask) & 3u) == 0;
-  hipLaunchKernelGGL(stage_rows_mask_sensors_kernel, dim3((unsigned)num_graphs * MASK_WGS), dim3(SENS_T), 0, gatres_stream(stream),
-                     data, reinterpret_cast<const long long*>(rows), (int)nodes_per_graph, x_dst, y_dst, node_ptr, observed,
-                     (int)num_observed, t_drop, t_share, mask_rate, seed, step_counter, mask, words_ok);
-  return gatres_launch_status();
+  return stage_rows_mask_sensors<false>(data, rows, nodes_per_graph, x_dst, y_dst, node_ptr, num_graphs, observed, num_observed,
+                                        sensor_dropout, layout_share, mask_rate, seed, step_counter, mask, nullptr, 0, stream);
+}
+
+extern "C" int gatres_stage_rows_mask_sensors_noisy(const float* data, const int64_t* rows, int32_t nodes_per_graph, float* x_dst,
+                                                    float* y_dst, const int32_t* node_ptr, int32_t num_graphs,
+                                                    const int32_t* observed, int32_t num_observed, double sensor_dropout,
+                                                    double layout_share, double mask_rate, uint64_t seed,
+                                                    const uint64_t* step_counter, uint8_t* mask, const float* sigma,
+                                                    uint64_t noise_seed, void* stream) {
+  return stage_rows_mask_sensors<true>(data, rows, nodes_per_graph, x_dst, y_dst, node_ptr, num_graphs, observed, num_observed,
+                                       sensor_dropout, layout_share, mask_rate, seed, step_counter, mask, sigma, noise_seed, stream);
 }
 
 extern "C" int gatres_stage_multi_rows_mask_required(const float* const* src_table, int32_t num_networks,

@@ -171,6 +171,7 @@ class EpochLoop:
             self._siblings[key] = t
         t.mask_rate = self.mask_rate
         t._layout = self._layout            # (a sensor layout set or cleared since the sibling was built)
+        t.store_norm = self.store_norm
         t._metrics = self._metrics          # (device_metrics: the ragged batch writes the epoch's last record)
         return t
 

@@ -199,6 +199,34 @@ def reading_noise(seed, members: int, rows: int, num_sensors: int, member0: int 
     return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
 
 
+def noise_std_vector(noise_std, num_sensors: int) -> np.ndarray:
+    """``noise_std`` -- one non-negative finite number or ``num_sensors`` of them, physical units -- as float64 ``[K]``."""
+    K = int(num_sensors)
+    try:
+        v = np.asarray(noise_std, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"noise_std must be a non-negative number or a sequence of {K} of them") from None
+    if v.ndim == 0:
+        v = np.full(K, float(v))
+    if v.shape != (K,):
+        raise ValueError(f"noise_std must be a non-negative number or a sequence of {K} of them, one per sensor; got shape "
+                         f"{tuple(v.shape)}")
+    if not np.isfinite(v).all() or (v < 0).any():
+        raise ValueError("noise_std must be finite and non-negative")
+    return v
+
+
+def noise_sigma(noise_std, num_sensors: int, norm_type: str, std: Optional[float], eps: float, full_rows: bool) -> np.ndarray:
+    """``noise_std`` (physical units) as the float32 ``sigma[K]`` of the noisy staging launches (gatres_stage_observed_noisy,
+    gatres_stage_rows_mask_sensors_noisy), in the units of the launch's source: divided by ``std + eps`` for the full rows of a
+    z-normalised store, unchanged for raw readings and for an ``unused`` store.  The one statement of that conversion:
+    ``PressureEstimator`` and ``SensorLayout`` both come here."""
+    v = noise_std_vector(noise_std, num_sensors)
+    if full_rows and norm_type == "znorm":
+        v = v / (float(std) + float(eps))
+    return v.astype(np.float32)
+
+
 def ensemble_chunk(num_snapshots: int, members: int, batch_size: int, row_bytes: int, max_scratch_bytes: int) -> int:
     """Snapshots per chunk of the ensemble's scratch matrix (``row_bytes`` per pair).  The pass over the S * M pairs is cut into
     batches of ``batch_size`` once, from pair 0; a chunk must hold whole snapshots AND whole batches, so it is a multiple of the
@@ -676,21 +704,8 @@ class PressureEstimator:
     def _sigma(self, noise_std, layout: int) -> torch.Tensor:
         """``noise_std`` (physical units; one value or K of them) as the device ``sigma[K]`` of gatres_stage_observed_noisy: in
         the units of the launch's source, that is divided by ``std + eps`` for the full rows of a z-normalised store."""
-        K = len(self.observed_idx)
-        try:
-            v = np.asarray(noise_std, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"noise_std must be a non-negative number or a sequence of {K} of them") from None
-        if v.ndim == 0:
-            v = np.full(K, float(v))
-        if v.shape != (K,):
-            raise ValueError(f"noise_std must be a non-negative number or a sequence of {K} of them, one per sensor; got shape "
-                             f"{tuple(v.shape)}")
-        if not np.isfinite(v).all() or (v < 0).any():
-            raise ValueError("noise_std must be finite and non-negative")
-        if layout == _native.OBSERVED_FULL_ROWS and self.norm_type == "znorm":
-            v = v / (self.std + self.eps)
-        v = v.astype(np.float32)
+        v = noise_sigma(noise_std, len(self.observed_idx), self.norm_type, self.std, self.eps,
+                        full_rows=layout == _native.OBSERVED_FULL_ROWS)
         cached = self._sigma_cache.get(layout)
         if cached is None or cached[0] != v.tobytes():
             cached = self._sigma_cache[layout] = (v.tobytes(), torch.from_numpy(v).to(self.device))
@@ -825,20 +840,27 @@ class PressureEstimator:
         return self._run(store.data, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, out, available, False, noise)
 
     def fine_tune(self, train_store, val_store, epochs: int, *, lr: float, batch_size: Optional[int] = None,
-                  sensor_dropout: float = 0.0, layout_share: float = 1.0, mask_rate: float = 0.95, **fit_kw):
+                  sensor_dropout: float = 0.0, layout_share: float = 1.0, mask_rate: float = 0.95, noise_std=None,
+                  noise_seed: Optional[int] = None, **fit_kw):
         """Fine-tune the estimator's model to its own sensor layout: ``GATResTrainer.for_store(model, train_store, batch_size,
         lr=lr, mask_rate=mask_rate)``, ``set_sensor_layout(observed_idx, sensor_dropout=..., layout_share=...)`` and
         ``fit(train_store, val_store, epochs, **fit_kw)`` -- validated under the layout mask unless ``val_layout=False`` is
         passed on.  ``batch_size`` defaults to the estimator's.  Returns the ``FitHistory``.  The training happens in the model's
         own parameter vector, which every estimate reads at its launches: the estimator estimates with the tuned parameters
         from the next call on, nothing is refreshed.  The trainer's constructor arguments other than ``lr`` and ``mask_rate``
-        keep their defaults: build the trainer yourself for anything else."""
+        keep their defaults: build the trainer yourself for anything else.
+
+        ``noise_std`` / ``noise_seed`` (``set_sensor_layout``'s: physical units, one value or one per sensor; the seed defaults to
+        the trainer's): fine-tune under measurement noise on the kept readings -- what makes a model that ``noise_report`` shows
+        to be fragile robust.  ``fit`` then validates under the same ``noise_std`` with a fixed realisation (``val_noise``,
+        ``val_noise_seed`` in ``fit_kw``)."""
         from .train_step import GATResTrainer
         self._check_store(train_store)
         self._check_store(val_store)
         bs = self.batch_size if batch_size is None else int(batch_size)
         trainer = GATResTrainer.for_store(self.model, train_store, bs, lr=lr, mask_rate=mask_rate)
-        trainer.set_sensor_layout(self.observed_idx, sensor_dropout=sensor_dropout, layout_share=layout_share)
+        trainer.set_sensor_layout(self.observed_idx, sensor_dropout=sensor_dropout, layout_share=layout_share,
+                                  noise_std=noise_std, noise_seed=noise_seed)
         return trainer.fit(train_store, val_store, int(epochs), batch_size=bs, **fit_kw)
 
     def estimate_ensemble(self, readings: torch.Tensor, noise_std, members: int, *, seed: int = 0,

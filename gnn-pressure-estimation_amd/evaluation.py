@@ -379,7 +379,8 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
                    seed: int = 0, gpu_warmup_times: int = 10, norm_type: Optional[str] = None,
                    criterion: Optional[Callable] = None, metric_fn_dict: Optional[Dict[str, Callable]] = None,
                    per_network: bool = False, graphs_per_network: Optional[Sequence[int]] = None,
-                   observed_idx: Optional[Sequence[int]] = None, _capture: Optional[List] = None) -> Tuple[float, Dict[str, float]]:
+                   observed_idx: Optional[Sequence[int]] = None, noise_std=None, noise_seed: int = 0,
+                   _capture: Optional[List] = None) -> Tuple[float, Dict[str, float]]:
     """``test_one_epoch`` over a ``SnapshotStore`` on the device: the same ``(loss, metrics)`` keys -- the reference's seven
     metrics, ``{prefix}_time`` (ms/graph) and ``{prefix}_throughput``, ``_sensor`` postfixed on the sensor pass.
 
@@ -404,6 +405,12 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
     enter.  Forward, moments, keys and prefixes are unchanged.  Refused together with ``do_test_on_sensors``, ``required_idx``,
     ``use_same_mask`` and a ``MultiSnapshotStore``.
 
+    ``noise_std`` (with ``observed_idx`` only; one non-negative finite number or one per sensor, physical units) and
+    ``noise_seed``: the layout pass under one realisation of measurement noise.  Every batch is staged by
+    ``gatres_stage_rows_mask_sensors_noisy`` (dropout 0, share 1, no step counter: member 0), so the staged ``x`` at the sensors
+    is bit for bit that of ``PressureEstimator.estimate_store(store, noise_std=, noise_seed=, noise_member=0)``; the targets at
+    the hidden nodes stay clean.  A ``noise_std`` of zeros is the clean layout pass.
+
     A ``MultiSnapshotStore`` is taken by its schedule (``store.schedule(batch_size, drop_last=False)``, the recipe the
     default or ``graphs_per_network``), every network's snapshots in order, staged by ``gatres_stage_multi_rows_mask_required``.
     ``required_idx`` is then a sequence of K sequences, one per network (sensor sets differ between networks).
@@ -421,12 +428,14 @@ def evaluate_store(model: torch.nn.Module, store, batch_size: int, mask_rate: fl
         raise ValueError("per_network / graphs_per_network belong to a MultiSnapshotStore")
     if observed_idx is not None:
         _check_layout_options(multi, do_test_on_sensors, required_idx, use_same_mask)
+    elif noise_std is not None:
+        raise ValueError("noise_std belongs to the layout pass: pass observed_idx (the sensors whose readings are noisy)")
     scale, offset = _store_descale(store, norm_type)
     S = len(store)
     if S == 0:
         raise ValueError("empty store")
     if observed_idx is not None:
-        cut = _SingleBatches(store, batch_size, mask_rate, observed=observed_idx)
+        cut = _SingleBatches(store, batch_size, mask_rate, observed=observed_idx, noise_std=noise_std, noise_seed=noise_seed)
     else:
         cut = (_MultiBatches if multi else _SingleBatches)(store, batch_size, mask_rate,
                                                             required_idx if do_test_on_sensors else None, graphs_per_network)
@@ -546,7 +555,8 @@ class _SingleBatches:
     and stages batch ``b``.  ``keys[b]`` names the batch's plan (its graph count); ``required``: the sensor nodes (None: no
     sensor pass)."""
 
-    def __init__(self, store, batch_size: int, mask_rate: float, required=None, graphs_per_network=None, observed=None):
+    def __init__(self, store, batch_size: int, mask_rate: float, required=None, graphs_per_network=None, observed=None,
+                 noise_std=None, noise_seed: int = 0):
         npg, S = store.nodes_per_graph, len(store)
         self.required = sorted(set(int(i) for i in required)) if required is not None else []
         if self.required and (self.required[0] < 0 or self.required[-1] >= npg):
@@ -557,9 +567,20 @@ class _SingleBatches:
         if observed is not None:
             from .estimation import _check_observed
             self.observed = _check_observed(observed, npg)
+            # noise_std: one realisation of measurement noise on the sensors' readings (gatres_stage_rows_mask_sensors_noisy,
+            # member 0); sigma in the store's units, by the statement PressureEstimator uses for full rows.  All zeros: none.
+            if noise_std is not None:
+                from .estimation import _check_seed, noise_sigma
+                self.noise_seed = _check_seed(noise_seed)
+                sigma = noise_sigma(noise_std, len(self.observed), store.norm_type, store.std, getattr(store, "eps", 1e-8),
+                                    full_rows=True)
+                self.sigma_host = sigma if sigma.any() else None
         elif int(npg * mask_rate) - len(self.required) <= 0:
             raise ValueError("mask length must be positive")
         self.obs = None
+        if observed is None or noise_std is None:
+            self.sigma_host, self.noise_seed = None, 0
+        self.sigma = None
         self.store, self.batch_size = store, int(batch_size)
         nb = (S + batch_size - 1) // batch_size
         self.sizes = [min(batch_size, S - b * batch_size) for b in range(nb)]
@@ -588,6 +609,10 @@ class _SingleBatches:
             host = torch.tensor(self.observed, dtype=torch.int32)
             keep.append(host.pin_memory() if pinned else host)
             self.obs = keep[-1].to(dev, non_blocking=pinned)
+            if self.sigma_host is not None:
+                host = torch.from_numpy(self.sigma_host)
+                keep.append(host.pin_memory() if pinned else host)
+                self.sigma = keep[-1].to(dev, non_blocking=pinned)
         return keep
 
     def stage(self, lib, P: _EvalPlan, b: int, mask_rate: float, seed64: int, step_ptr: int, sensors: bool, stream) -> None:
@@ -595,7 +620,8 @@ class _SingleBatches:
         if self.observed is not None:
             from .sensor_layout import stage_rows
             stage_rows(lib, self.store.data, rows.data_ptr(), self.store.nodes_per_graph, P.x, None, P.node_ptr, P.num_graphs,
-                       self.obs, len(self.observed), 0.0, 1.0, min(max(float(mask_rate), 0.0), 1.0), seed64, step_ptr, P.mask, stream)
+                       self.obs, len(self.observed), 0.0, 1.0, min(max(float(mask_rate), 0.0), 1.0), seed64,
+                       step_ptr if self.sigma is None else None, P.mask, stream, sigma=self.sigma, noise_seed=self.noise_seed)
             return
         _enqueue_stage(lib, self.store, P, rows, mask_rate, seed64, step_ptr, self.req if sensors else None,
                        len(self.required) if sensors else 0, stream)
@@ -651,10 +677,11 @@ class _ValidationPass:
     ``gatres_epoch_control``.  Everything static (row order, sampler steps, graph counts, tables) is made once; with the same
     ``seed`` the moment table is bit for bit the one ``evaluate_store(seed=seed, gpu_warmup_times=0)`` forms.  ``store``: a
     ``SnapshotStore`` or a ``MultiSnapshotStore`` (then the batches are its in-order schedule's).  ``observed_idx``: the pass
-    of ``evaluate_store(observed_idx=...)`` -- everything hidden but a fixed sensor layout."""
+    of ``evaluate_store(observed_idx=...)`` -- everything hidden but a fixed sensor layout; ``noise_std`` / ``noise_seed``: that
+    pass under one fixed realisation of measurement noise, ``evaluate_store(observed_idx=, noise_std=, noise_seed=)``'s."""
 
     def __init__(self, model, store, batch_size: int, mask_rate: float, criterion: str = "mse",
-                 observed_idx: Optional[Sequence[int]] = None):
+                 observed_idx: Optional[Sequence[int]] = None, noise_std=None, noise_seed: int = 0):
         from . import _native
         from .multi_snapshot_store import MultiSnapshotStore
         multi = isinstance(store, MultiSnapshotStore)
@@ -664,8 +691,11 @@ class _ValidationPass:
             raise ValueError("batch_size must be positive")
         if len(store) == 0:
             raise ValueError("empty store")
+        if observed_idx is None and noise_std is not None:
+            raise ValueError("noise_std belongs to the layout pass: pass observed_idx")
         if observed_idx is not None:          # (the layout mask of evaluate_store(observed_idx=...): deterministic, no sampler)
-            self.cut = _SingleBatches(store, int(batch_size), float(mask_rate), observed=observed_idx)
+            self.cut = _SingleBatches(store, int(batch_size), float(mask_rate), observed=observed_idx, noise_std=noise_std,
+                                      noise_seed=noise_seed)
         else:
             self.cut = (_MultiBatches if multi else _SingleBatches)(store, int(batch_size), float(mask_rate))
         self.cut.upload(pinned=False)

@@ -93,7 +93,8 @@ class FitLoop:
             train_metrics: bool = False, save_path: Optional[str] = None, model_name: Optional[str] = None,
             variant: Optional[str] = None, save_best: str = "reference", restore_best: bool = False,
             checkpoint_extra: Optional[dict] = None, log_gradient: bool = False,
-            on_epoch: Optional[Callable[[int, dict], None]] = None, val_layout: bool = True) -> "FitHistory":
+            on_epoch: Optional[Callable[[int, dict], None]] = None, val_layout: bool = True, val_noise: bool = True,
+            val_noise_seed: int = 0) -> "FitHistory":
         """The reference's training loop (train.py:376-511 ``internal_train``) with its epoch boundary on the device.
 
         Per epoch e = 1 .. ``epochs``: ``fit_epoch`` on ``train_store`` (with the ``"train"`` metric collection computed on the
@@ -137,6 +138,14 @@ class FitLoop:
         (``observed_idx``, ``sensor_dropout``, ``layout_share``) beside ``checkpoint_extra``.  Without a layout ``val_layout`` is
         not looked at.
 
+        Measurement noise (``set_sensor_layout(noise_std=...)``): the training batches are staged under it, and the layout
+        validation pass is staged under the same ``noise_std`` -- ``evaluate_store(..., observed_idx=layout, noise_std=noise_std,
+        noise_seed=val_noise_seed)``'s launches, member 0.  The seed is FIXED and the member is 0 in every epoch: the noise
+        realisation of the validation set is the same each epoch, so early stopping and ``ReduceLROnPlateau`` compare like with
+        like (a fresh realisation per epoch would add the realisation's own variance to every comparison).  ``val_noise=False``
+        validates on exact readings; ``val_layout=False`` implies that (the random-mask pass carries no noise).  Checkpoints'
+        ``sensor_layout`` then also carries ``noise_std`` (physical units) and ``noise_seed``.
+
         Data parallel: every rank passes its shards; the epoch's four sums are all-reduced (one collective per epoch), so all
         ranks take the same decision; metric dicts and ``model_update`` describe the rank's own shard, the gradient norms the
         all-reduced gradient (the same on every rank).  Returns a ``FitHistory``."""
@@ -175,7 +184,9 @@ class FitLoop:
         cfg = _native.GatresEpochConfig(float(min_delta), 0.1, 1e-4, 0.0, 1e-8, int(patience), int(scheduler_patience),
                                         int(scheduler is not None), 0)
         val = E._ValidationPass(self.model, val_store, vbs, self.mask_rate, self._criterion,
-                                observed_idx=layout.observed_idx if layout is not None and val_layout else None)
+                                observed_idx=layout.observed_idx if layout is not None and val_layout else None,
+                                noise_std=layout.noise_std if layout is not None and val_layout and val_noise else None,
+                                noise_seed=val_noise_seed)
         extra = dict(checkpoint_extra or {})
         if layout is not None:
             extra["sensor_layout"] = layout.describe()

@@ -1,8 +1,11 @@
-"""Fine-tuning to a FIXED sensor layout: the host side of ``gatres_stage_rows_mask_sensors`` (csrc/k_stage.hip).
+"""Fine-tuning to a FIXED sensor layout: the host side of ``gatres_stage_rows_mask_sensors`` and of its noisy sibling
+``gatres_stage_rows_mask_sensors_noisy`` (csrc/k_stage.hip).
 
 ``sensor_layout_draws`` restates the launch's draws in numpy ``uint64`` arithmetic (no device use): which graphs of a batch take
-the layout mask and which sensors keep their reading.  ``SensorLayout`` is what ``GATResTrainer.set_sensor_layout`` holds: the
-checked indices, their device copy (uploaded once) and the two probabilities."""
+the layout mask and which sensors keep their reading; ``sensor_layout_noise`` names the standard normal draw of each (graph,
+sensor) of the noisy launch.  ``SensorLayout`` is what ``GATResTrainer.set_sensor_layout`` holds: the checked indices, their
+device copy (uploaded once), the two probabilities and, under measurement noise, the device ``sigma[K]`` (uploaded once) and
+the noise seed."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
@@ -71,24 +74,60 @@ def sensor_layout_draws(seed: int, step: int, num_graphs: int, nodes_per_graph: 
     return mode, keep
 
 
+def sensor_layout_noise(noise_seed: int, step: int, rows, num_sensors: int) -> np.ndarray:
+    """The standard normal draws of ``gatres_stage_rows_mask_sensors_noisy`` for a batch whose graphs are the source rows
+    ``rows`` at sampler step ``step``: float64 ``[G, K]``, entry ``[g, k]`` the ``z`` that sensor ``k`` of graph ``g`` gets if it
+    keeps its reading in a layout-mode graph.  The generator is ``gatres_stage_observed_noisy``'s with the step as the member:
+    ``reading_noise(noise_seed, 1, S, K, member0=step)[rows[g], 0, k]`` -- the graph's place in the batch does not enter."""
+    from .estimation import reading_noise
+    r = np.asarray([int(i) for i in rows], dtype=np.int64).reshape(-1)
+    if r.size < 1 or r.min() < 0:
+        raise ValueError("sensor_layout_noise needs at least one row, none of them negative")
+    return reading_noise(noise_seed, 1, int(r.max()) + 1, num_sensors, member0=int(step))[r, 0, :]
+
+
 class SensorLayout:
     """A trainer's sensor layout: ``observed_idx`` (checked), its int32 device copy, ``sensor_dropout`` and ``layout_share``.
-    One object serves a trainer and its siblings."""
+    One object serves a trainer and its siblings.
 
-    def __init__(self, observed_idx: Sequence[int], nodes_per_graph: int, sensor_dropout: float, layout_share: float, device):
+    ``noise_std`` (``None``: no noise; one non-negative finite number or K of them, physical units): the measurement noise the
+    kept readings are staged under.  ``norm = (norm_type, std, eps)`` of the store converts it to the device ``sigma[K]`` in
+    store units (``estimation.noise_sigma``, the statement ``PressureEstimator`` uses for full rows), uploaded once, here.  A
+    ``noise_std`` of zeros is no noise: ``sigma`` stays None and every launch is the noise-free one."""
+
+    def __init__(self, observed_idx: Sequence[int], nodes_per_graph: int, sensor_dropout: float, layout_share: float, device,
+                 noise_std=None, noise_seed: Optional[int] = None, norm: Optional[Tuple[str, Optional[float], float]] = None):
         import torch
-        from .estimation import _check_observed
+        from .estimation import _check_observed, _check_seed, noise_sigma, noise_std_vector
         self.sensor_dropout, self.layout_share = check_probabilities(sensor_dropout, layout_share)
         self.observed_idx: List[int] = _check_observed(observed_idx, int(nodes_per_graph))
         self.nodes_per_graph = int(nodes_per_graph)
+        self.noise_std: Optional[List[float]] = None
+        self.noise_seed: Optional[int] = None
+        self.sigma = None
+        if noise_std is not None:
+            std = noise_std_vector(noise_std, len(self.observed_idx))
+            seed = _check_seed(noise_seed)
+            if std.any():
+                if norm is None:
+                    raise ValueError("noise_std is in physical units and the store's normalisation is unknown to this trainer: "
+                                     "build it with GATResTrainer.for_store(model, store, ...), or set trainer.store_norm = "
+                                     "(norm_type, std, eps) -- ('unused', None, 0.0) for a store that is not normalised")
+                self.noise_std, self.noise_seed = [float(v) for v in std], seed
+                self.sigma = torch.from_numpy(noise_sigma(std, len(self.observed_idx), norm[0], norm[1], norm[2],
+                                                          full_rows=True)).to(device)
         self.observed = torch.tensor(self.observed_idx, dtype=torch.int32).to(device)
 
     def key(self) -> tuple:
         """What a captured launch sequence that stages under this layout depends on."""
-        return ("layout", self.observed.data_ptr(), len(self.observed_idx), self.sensor_dropout, self.layout_share)
+        key = ("layout", self.observed.data_ptr(), len(self.observed_idx), self.sensor_dropout, self.layout_share)
+        return key if self.sigma is None else key + (self.sigma.data_ptr(), self.noise_seed)
 
     def describe(self) -> dict:
-        return {"observed_idx": list(self.observed_idx), "sensor_dropout": self.sensor_dropout, "layout_share": self.layout_share}
+        d = {"observed_idx": list(self.observed_idx), "sensor_dropout": self.sensor_dropout, "layout_share": self.layout_share}
+        if self.sigma is not None:
+            d["noise_std"], d["noise_seed"] = list(self.noise_std), self.noise_seed
+        return d
 
 
 def refuse_layout_data_parallel(world: int) -> None:
@@ -108,9 +147,17 @@ def refuse_layout_multi_store(store) -> None:
 
 def stage_rows(lib, data, rows_ptr: int, nodes_per_graph: int, x, y: Optional[object], node_ptr, num_graphs: int,
                layout_observed, num_observed: int, sensor_dropout: float, layout_share: float, mask_rate: float, seed: int,
-               step_ptr: Optional[int], mask, stream) -> None:
-    """Enqueue ``gatres_stage_rows_mask_sensors`` (tensors in, addresses out)."""
+               step_ptr: Optional[int], mask, stream, sigma=None, noise_seed: int = 0) -> None:
+    """Enqueue ``gatres_stage_rows_mask_sensors`` -- with ``sigma`` (device fp32 ``[K]``, store units)
+    ``gatres_stage_rows_mask_sensors_noisy`` -- (tensors in, addresses out)."""
     from . import _native
+    if sigma is not None:
+        _native.check(lib.gatres_stage_rows_mask_sensors_noisy(
+            data.data_ptr(), rows_ptr, int(nodes_per_graph), x.data_ptr(), None if y is None else y.data_ptr(),
+            node_ptr.data_ptr(), int(num_graphs), layout_observed.data_ptr(), int(num_observed), float(sensor_dropout),
+            float(layout_share), float(mask_rate), int(seed) & 0xFFFFFFFFFFFFFFFF, step_ptr, mask.data_ptr(), sigma.data_ptr(),
+            int(noise_seed) & 0xFFFFFFFFFFFFFFFF, stream), "gatres_stage_rows_mask_sensors_noisy")
+        return
     _native.check(lib.gatres_stage_rows_mask_sensors(
         data.data_ptr(), rows_ptr, int(nodes_per_graph), x.data_ptr(), None if y is None else y.data_ptr(), node_ptr.data_ptr(),
         int(num_graphs), layout_observed.data_ptr(), int(num_observed), float(sensor_dropout), float(layout_share),

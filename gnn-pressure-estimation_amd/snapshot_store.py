@@ -32,6 +32,7 @@ class SnapshotStore:
         self.mean = float(data.mean()) if mean is None else float(mean)
         self.std = float(data.std(unbiased=False)) if std is None else float(std)     # np.std semantics
         self.norm_type = "znorm" if normalize else "unused"
+        self.eps = float(eps)
         self.data = ((data - self.mean) / (self.std + eps)).contiguous() if normalize else data.contiguous()
         self.num_snapshots, self.nodes_per_graph = int(data.shape[0]), int(data.shape[1])
         if int(edge_index.max()) >= self.nodes_per_graph if edge_index.numel() else False:

@@ -313,6 +313,10 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         # set_sensor_layout(): the fixed sensor layout the store-fed steps train under (None: the sampler's random masks); a
         # sibling takes its parent's
         self._layout: Optional[SensorLayout] = _share_state_with._layout if _share_state_with is not None else None
+        # (norm_type, std, eps) of the store the batches come from -- for_store() takes it from the store -- or None: what
+        # converts set_sensor_layout(noise_std=...) from physical units into the store's
+        self.store_norm: Optional[Tuple[str, Optional[float], float]] = (
+            _share_state_with.store_norm if _share_state_with is not None else None)
         self._warn_if_the_chip_is_not_ours()
 
     @classmethod
@@ -332,7 +336,9 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         if graphs_per_network is not None:
             raise ValueError("graphs_per_network belongs to a MultiSnapshotStore")
         bs = int(batch_size)
-        return cls(model, store.edge_index(bs), bs * store.nodes_per_graph, nodes_per_graph=[store.nodes_per_graph] * bs, **kw)
+        t = cls(model, store.edge_index(bs), bs * store.nodes_per_graph, nodes_per_graph=[store.nodes_per_graph] * bs, **kw)
+        t.store_norm = (store.norm_type, store.std, store.eps)
+        return t
 
     def _warn_if_the_chip_is_not_ours(self) -> None:
         """A split launch (several workgroups per snapshot, spin-waiting on each other's granules) needs EVERY workgroup of
@@ -466,7 +472,8 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
             self._push_hparams()                       # (siblings share both the dict and the device buffer)
 
     # ---- fine-tuning to a fixed sensor layout -----------------------------------------------------------------------------
-    def set_sensor_layout(self, observed_idx: Sequence[int], *, sensor_dropout: float = 0.0, layout_share: float = 1.0) -> None:
+    def set_sensor_layout(self, observed_idx: Sequence[int], *, sensor_dropout: float = 0.0, layout_share: float = 1.0,
+                          noise_std=None, noise_seed: Optional[int] = None) -> None:
         """Train the store-fed steps (``step_rows``, ``steps_rows``, ``fit_epoch``, ``fit``) under the mask of a FIXED sensor
         layout: every node hidden but ``observed_idx`` (node indices inside a graph, distinct -- the layout of a
         ``PressureEstimator``).  Per step and graph, each sensor loses its reading with probability ``sensor_dropout`` (in
@@ -479,14 +486,28 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
         calls that would train under the sampler's mask alone raise ``ValueError``: ``step(x, y)`` without a mask,
         ``run_step(device_mask=True)``, ``step_prefetched``, ``bind_batches`` / ``step_bound`` / ``steps_bound``.
         ``step(x, y, mask)`` with the caller's mask stays.  Siblings (the ragged batch's trainer) follow.  Data parallelism and a
-        ``MultiSnapshotStore`` are refused (``NotImplementedError``)."""
+        ``MultiSnapshotStore`` are refused (``NotImplementedError``).
+
+        ``noise_std`` (``None`` or all zeros: today's launch and today's bits): measurement noise on the readings.  One
+        non-negative finite number, or one per sensor, in PHYSICAL units.  A sensor that keeps its reading in a layout-mode
+        graph is then staged as ``r + sigma[k] * z`` -- ``sigma`` is ``noise_std`` in the store's units (divided by ``std + eps``
+        for a z-normalised store; ``store_norm``, which ``for_store`` takes from the store, says which: without it ``noise_std``
+        is refused), uploaded once, here; ``z = sensor_layout_noise(noise_seed, step, rows, K)[g, k]`` is drawn in the batch's own
+        staging launch (``gatres_stage_rows_mask_sensors_noisy``) from the optimizer's step count, read on the device, so every
+        step of a captured sequence draws its own noise.  No launch, read-back or per-step tensor is added.  Dropped sensors,
+        random-mode graphs and the targets stay clean: the noise sits where ``mask == 0`` and the loss reads its target where
+        ``mask == 1``, so a trainer whose targets ARE its inputs trains on clean targets.  ``noise_seed`` (an integer in
+        ``[0, 2**64)``) defaults to the trainer's effective seed.  Whatever a layout refuses, noise refuses with it."""
         refuse_layout_data_parallel(self.world)
         if self._recipe is not None:
             raise NotImplementedError("a sensor layout with a MultiSnapshotStore is not implemented (a layout per network would "
                                       "be needed): fine-tune on one network's SnapshotStore")
         if self.node_ptr is None or not self._npg_list or len(set(self._npg_list)) != 1:
             raise ValueError("a sensor layout needs nodes_per_graph at construction, the same for every graph of the batch")
-        self._adopt_layout(SensorLayout(observed_idx, self._npg_list[0], sensor_dropout, layout_share, self.device))
+        if noise_std is not None and noise_seed is None:
+            noise_seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
+        self._adopt_layout(SensorLayout(observed_idx, self._npg_list[0], sensor_dropout, layout_share, self.device,
+                                        noise_std=noise_std, noise_seed=noise_seed, norm=getattr(self, "store_norm", None)))
 
     def clear_sensor_layout(self) -> None:
         """Back to the sampler's random masks: every path, graph key and launch is the one of a trainer that never had a layout."""
@@ -499,7 +520,8 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
 
     @property
     def sensor_layout(self) -> Optional[dict]:
-        """``{"observed_idx", "sensor_dropout", "layout_share"}`` of the layout set (a copy), or None."""
+        """``{"observed_idx", "sensor_dropout", "layout_share"}`` of the layout set (a copy), or None; under measurement noise
+        also ``"noise_std"`` (K floats, physical units) and ``"noise_seed"``."""
         return None if self._layout is None else self._layout.describe()
 
     def _refuse_under_layout(self, what: str) -> None:
@@ -829,7 +851,8 @@ class GATResTrainer(EpochLoop, FitLoop, GradFlow):
             _stage_rows_sensors(self.lib, data, rows_ptr, self.N // max(self.num_graphs, 1), self.x,
                                 None if self.targets_are_inputs else self.y, self.node_ptr, self.num_graphs, lay.observed,
                                 len(lay.observed_idx), lay.sensor_dropout, lay.layout_share, self.mask_rate, self.seed,
-                                self.step_counter.data_ptr(), self.mask, _native.current_stream(self.device))
+                                self.step_counter.data_ptr(), self.mask, _native.current_stream(self.device),
+                                sigma=lay.sigma, noise_seed=lay.noise_seed or 0)
             return
         _native.check(self.lib.gatres_stage_rows_mask(
             data.data_ptr(), rows_ptr, self.N // max(self.num_graphs, 1), self.x.data_ptr(),

@@ -325,6 +325,35 @@ int gatres_stage_rows_mask_sensors(const float* data, const int64_t* rows, int32
                                    double sensor_dropout, double layout_share, double mask_rate, uint64_t seed,
                                    const uint64_t* step_counter, uint8_t* mask, void* stream);
 
+/* gatres_stage_rows_mask_sensors with MEASUREMENT NOISE on the readings the layout keeps (fine-tuning a model to noisy sensors;
+ * new symbol only: the ABI version stays).  The kernel of gatres_stage_rows_mask_sensors compiled with the noise as one more
+ * compile-time fact; its arguments, and
+ *   sigma        device float[num_observed], >= 0, in the units of data
+ *   noise_seed   any 64-bit value.
+ * The mask: byte for byte that of gatres_stage_rows_mask_sensors with the same arguments -- the mode draw per graph, the dropout
+ *   draw per sensor and the random-mode mask do not see the noise.
+ * A RANDOM-mode graph is staged clean: x_dst and y_dst are the row.
+ * A LAYOUT-mode graph g, n0 = node_ptr[g] = g * N, source row r = rows[g]: at every sensor k that KEEPS its reading (mask = 0)
+ *   x_dst[n0 + observed[k]] = fp32(data[r * N + observed[k]] + fp32(sigma[k] * z))
+ *   with z the draw of gatres_stage_observed_noisy's generator (below) for (seed = noise_seed, member = step, row = r, k), K =
+ *   num_observed, step = step_counter ? step_counter[0] : 0 -- estimation.reading_noise(noise_seed, 1, S, K, member0=step)[r, 0, k]
+ *   restates it, sensor_layout.sensor_layout_noise names it.  z depends on nothing else: not on the graph's place in the batch,
+ *   the launch geometry or the dropout of other sensors.  sigma[k] == 0 stores the row's value itself.
+ * Every other element of x_dst is the clean row, the dropped sensors (mask = 1) included; y_dst, when given and another buffer
+ *   than x_dst, is the clean row everywhere.  The noise sits only where mask == 0, and the loss and the metrics read their target
+ *   only where mask == 1: a step whose target buffer IS x_dst (y_dst NULL or == x_dst) trains on clean targets.
+ * One launch of the same grid, plain stores, no atomics: in a layout-mode graph each of the graph's workgroups copies its own
+ * slice of the row and, behind a workgroup barrier, stores the noisy values of that slice over its own copy, so every element
+ * has one final writer.  Only lanes that hold a kept sensor draw.  A pure function of the arguments and *step_counter: every
+ * step of a replayed capture draws its own noise.
+ * GATRES_E_BADARG before any launch: whatever gatres_stage_rows_mask_sensors refuses, sigma == NULL, and a sigma that overlaps
+ * x_dst, y_dst or mask. */
+int gatres_stage_rows_mask_sensors_noisy(const float* data, const int64_t* rows, int32_t nodes_per_graph, float* x_dst,
+                                         float* y_dst, const int32_t* node_ptr, int32_t num_graphs, const int32_t* observed,
+                                         int32_t num_observed, double sensor_dropout, double layout_share, double mask_rate,
+                                         uint64_t seed, const uint64_t* step_counter, uint8_t* mask, const float* sigma,
+                                         uint64_t noise_seed, void* stream);
+
 /* gatres_stage_rows_mask_required for a batch whose graphs come from SEVERAL snapshot matrices (one [S_k][N_k] matrix per
  * water network; utils/DataLoader.py:61-183 takes lists of networks): src_table[num_networks] (device) holds the matrices'
  * device addresses; graph g is row rows[g] (device, int64) of matrix net_of_graph[g] (device, int32), node_ptr[g + 1] -
