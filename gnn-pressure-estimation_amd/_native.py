@@ -18,8 +18,8 @@ _LIB: Optional[C.CDLL] = None
 DTYPE_F32, DTYPE_BF16 = 0, 1
 
 ERRORS = {-1: "GATRES_E_BADARG (null/misaligned pointer or bad size)",
-          -2: "GATRES_E_UNSUPPORTED (width / storage type not supported: nc must be a power of two in [4, 128]; bf16 "
-              "needs nc >= 32)",
+          -2: "GATRES_E_UNSUPPORTED (width / storage type not supported: the model drivers take nc a power of two in [4, 128]; "
+              "bf16 projections need nc >= 32; include/gatres.h states each per-op entry point's widths)",
           -3: "GATRES_E_GRAPH (edge endpoint out of range)"}
 
 

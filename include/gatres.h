@@ -15,7 +15,10 @@
  *     synchronisation) so a caller may capture any sequence of calls into a hipGraph;
  *   - return value: 0 = ok; < 0 = argument error (GATRES_E_*); > 0 = hipError_t from the launch.
  *
- * Supported widths: nc (hidden channels) a power of two, 4 <= nc <= 128  (gatres_small: 32, gatres_large: 128).
+ * Supported widths: the whole-network drivers (gatres_model_t) take nc (hidden channels) a power of two in [4, 128]
+ * (gatres_small: 32, gatres_large: 128).  The per-op entry points state their own, wider, contract beside their
+ * declarations: lin0 forward takes any multiple of 4, lin1 forward a power of two up to 256, the two lin backward calls
+ * every width from 1 to 256.  A width outside an entry point's contract is refused with GATRES_E_UNSUPPORTED.
  */
 #ifndef GATRES_H
 #define GATRES_H
@@ -172,7 +175,10 @@ int64_t gatres_lz4_decompress_host(const uint8_t* src, int64_t src_len, uint8_t*
 int gatres_knobs_reload(void);
 
 /* 64-bit content hash of an int64 [2,E] DEVICE edge_index (for plan caching); hash_out: device uint64[1],
- * must be zeroed by the caller on the same stream before the call. */
+ * must be zeroed by the caller on the same stream before the call.  The call ADDS to hash_out, modulo 2^64, the sum over
+ * the edges e of mix64(mix64(src_e + 0x9E3779B97F4A7C15 * (e + 1)) ^ (dst_e + 0xD1B54A32D192ED03)), mix64 being the
+ * finaliser of splitmix64: it depends on every endpoint and on every edge's position, not on the order of the additions.
+ * num_edges == 0: returns 0 and leaves hash_out untouched (edge_index may then be NULL). */
 int gatres_edge_index_hash(const int64_t* edge_index, int64_t num_edges, uint64_t* hash_out, void* stream);
 
 /* --------------------------------------------------------------------------------------------------------
@@ -180,7 +186,9 @@ int gatres_edge_index_hash(const int64_t* edge_index, int64_t num_edges, uint64_
  * ------------------------------------------------------------------------------------------------------ */
 
 /* lin0: PyG Linear(1, nc) (GraphModels.py:477,487).  out[n,c] = xm[n]*w[c] + b[c], where xm[n] = 0 if
- * mask != NULL and mask[n] != 0 (the caller-side `data.x[batch_mask] = 0`, train.py:174). */
+ * mask != NULL and mask[n] != 0 (the caller-side `data.x[batch_mask] = 0`, train.py:174) -- whatever x[n] holds, NaN
+ * included.  One fp32 product and one fp32 sum per element (no fused multiply-add).  nc: any multiple of 4, nc >= 4 (others:
+ * GATRES_E_UNSUPPORTED); w, b and out 16-byte aligned (GATRES_E_BADARG). */
 int gatres_lin0_fwd(const float* x, const uint8_t* mask, const float* w, const float* b, float* out,
                     int32_t num_nodes, int32_t nc, void* stream);
 
@@ -202,7 +210,9 @@ int gatres_gat_aggregate_fwd(const gatres_graph_t* g, const float* h, const floa
 int gatres_mean_residual_relu_fwd(const gatres_graph_t* g, const float* y, const float* x0, float* out,
                                   int32_t C, void* stream);
 
-/* lin1: PyG Linear(nc, 1) (GraphModels.py:484,492).  out[n] = sum_c x[n,c]*w[c] + b[0]. */
+/* lin1: PyG Linear(nc, 1) (GraphModels.py:484,492).  out[n] = sum_c x[n,c]*w[c] + b[0]; b == NULL adds nothing.
+ * nc: a power of two, 4 <= nc <= 256 (others: GATRES_E_UNSUPPORTED); x and w 16-byte aligned (GATRES_E_BADARG).  A row's sum
+ * does not depend on the row's position. */
 int gatres_lin1_fwd(const float* x, const float* w, const float* b, float* out,
                     int32_t num_nodes, int32_t nc, void* stream);
 
@@ -210,12 +220,19 @@ int gatres_lin1_fwd(const float* x, const float* w, const float* b, float* out,
 
 /* Gradient partial sums.  Every reduction over nodes is done by `num_slabs` waves, each writing its partial
  * into its own slab of a [num_slabs, slab_stride] fp32 buffer at the parameter's flat offset; a final
- * gatres_reduce_slabs sums the slabs in a fixed order (bitwise reproducible, no atomics). */
+ * gatres_reduce_slabs sums the slabs in a fixed order (bitwise reproducible, no atomics): out[i] is the fp32 sum of
+ * slabs[s * slab_stride + i], s = 0 .. num_slabs - 1 in that order, starting from +0.0f, for i < count.
+ * slab_stride < count, count <= 0 or num_slabs <= 0: GATRES_E_BADARG.
+ * Slab s of every such reduction holds the rows [s * nps, min(N, (s + 1) * nps)), nps = ceil(N / num_slabs) rounded up to a
+ * multiple of 4; a slab without rows is written as +0.0f. */
 int gatres_reduce_slabs(const float* slabs, int32_t num_slabs, int64_t slab_stride, int64_t count,
                         float* out, void* stream);
 
-/* lin1 backward.  g_x[n,c] = g_out[n]*w[c], masked by (x[n,c] > 0) when relu_mask != 0 (x is the last block's
- * post-ReLU output).  slab_w / slab_b: this parameter's position inside slab 0. */
+/* lin1 backward.  g_x[n,c] = g_out[n]*w[c] (one fp32 product), exactly 0 where relu_mask != 0 and x[n,c] is not > 0 (x is
+ * the last block's post-ReLU output).  slab_w / slab_b: this parameter's position inside slab 0; slab s gets
+ * slab_w[c] = sum g_out[n]*x[n,c] and slab_b[0] = sum g_out[n] over its rows.  nc: 1 <= nc <= 256 (others:
+ * GATRES_E_UNSUPPORTED).  A power of two >= 4 with 16-byte aligned x and g_x takes 256 threads per slab, every other width or
+ * alignment (and GATRES_LIN_BWD_WAVE=1) one wave per slab: the same sums in another order. */
 int gatres_lin1_bwd(const float* g_out, const float* x, const float* w, float* g_x,
                     float* slab_w, float* slab_b, int32_t num_slabs, int64_t slab_stride,
                     int32_t num_nodes, int32_t nc, int32_t relu_mask, void* stream);
@@ -252,16 +269,19 @@ int gatres_conv_param_grads(const float* h, const float* g_a_src, const float* g
                             float* slab_att_src, float* slab_att_dst, float* slab_bias, int32_t num_slabs,
                             int64_t slab_stride, int32_t num_nodes, int32_t H, int32_t C, void* stream);
 
-/* lin0 backward partials: g_w[c] = sum_n g[n,c]*xm[n], g_b[c] = sum_n g[n,c]. */
+/* lin0 backward partials: g_w[c] = sum_n g[n,c]*xm[n], g_b[c] = sum_n g[n,c] (mask == NULL: xm = x).  nc: 1 <= nc <= 256
+ * (others: GATRES_E_UNSUPPORTED); the two forms of lin1's backward, chosen by nc and by the alignment of g. */
 int gatres_lin0_bwd(const float* g, const float* x, const uint8_t* mask, float* slab_w, float* slab_b,
                     int32_t num_slabs, int64_t slab_stride, int32_t num_nodes, int32_t nc, void* stream);
 
-/* Relabelled plans (gatres_graph_t.perm), per-op path: dst[i] = src[perm[i]] (scatter == 0) or dst[perm[i]] = src[i]. */
+/* Relabelled plans (gatres_graph_t.perm), per-op path: dst[i] = src[perm[i]] (scatter == 0) or dst[perm[i]] = src[i],
+ * i < num_nodes: plain copies, every bit pattern is kept.  perm must be a permutation of 0 .. num_nodes - 1. */
 int gatres_permute_f32(const float* src, const int32_t* perm, float* dst, int32_t num_nodes, int32_t scatter,
                        void* stream);
 int gatres_gather_u8(const uint8_t* src, const int32_t* perm, uint8_t* dst, int32_t num_nodes, void* stream);
 
-/* out[c*rows + r] = in[r*cols + c] for every GATConv weight of the flat parameter vector (see layout below). */
+/* out[c*rows + r] = in[r*cols + c] for every GATConv weight of the flat parameter vector (see layout below): wt holds per
+ * block [W1^T : nc x 2nc][W2^T : 2nc x nc], 4 nc^2 floats.  num_blocks == 0 returns 0 and writes nothing; nc >= 1. */
 int gatres_transpose_conv_weights(const float* params, float* wt, int32_t num_blocks, int32_t nc, void* stream);
 
 /* ---- caller side of the step (train.py:174-188) ---------------------------------------------------- */
@@ -434,7 +454,9 @@ int gatres_t_mean_residual_relu_fwd(const gatres_graph_t* g, const void* y, cons
                                     void* stream);
 int gatres_t_mean_bwd(const gatres_graph_t* g, const void* g_pre, void* g_y, int C, int dtype, void* stream);
 
-/* k_misc.hip */
+/* k_misc.hip.  Widths and alignments as stated at the fp32 entry points above: lin0 forward any multiple of 4, lin1 forward a
+ * power of two up to 256, both backward calls 1 .. 256 (bf16 tables included: a bf16 activation one element off a 16-byte
+ * boundary takes the one-wave form like an fp32 one). */
 int gatres_t_lin0_fwd(const float* x, const uint8_t* mask, const float* w, const float* b, void* out, int num_nodes, int nc,
                       int dtype, void* stream);
 int gatres_t_lin0_bwd(const void* g, const float* x, const uint8_t* mask, float* slab_w, float* slab_b, int num_slabs,
@@ -455,7 +477,8 @@ int gatres_t_conv_partials(const void* g_h, const void* x, float* slab_W, int w_
                            float* slab_att_src, float* slab_att_dst, float* slab_bias, int num_slabs, int H, int C, int dtype,
                            void* stream);
 /* bf16 copies of every GATConv weight and of its transpose: wb block layout [W1 : 2nc x nc][W2 : nc x 2nc] */
-/* [W1^T : nc x 2nc][W2^T : 2nc x nc] (4 * 2nc^2 bf16 per block) */
+/* [W1^T : nc x 2nc][W2^T : 2nc x nc] (4 * 2nc^2 bf16 per block), each element rounded to nearest-even.  num_blocks == 0 */
+/* returns 0 and writes nothing; nc >= 1. */
 int gatres_convert_conv_weights_bf16(const float* params, void* wb, int num_blocks, int nc, void* stream);
 
 /* k_proj.hip.  W / Wt: fp32 for GATRES_DTYPE_F32, bf16 (from gatres_convert_conv_weights_bf16) for GATRES_DTYPE_BF16. */
