@@ -1,6 +1,6 @@
 """MI355X-native GATRes message-passing engine (drop-in for the GATResMeanConv hot path of
 DiTEC-project/gnn-pressure-estimation).  See DESIGN.md / INTEGRATION.md at the repository root."""
-from . import _native, dp, epoch_control, estimation, evaluation, wdn_io, wdn_synth
+from . import _native, dp, epoch_control, estimation, evaluation, hydraulics, wdn_io, wdn_synth
 from ._build import build_native
 from .config_models import config_gatres_large, config_gatres_small, select_model
 from .graph_models import GATConv, GATResMeanConv, GResBlockMeanConv, Linear, SimpleConv
@@ -15,6 +15,8 @@ from .estimation import (ErrorBounds, MonitorBaseline, MonitorResult, PressureEs
 from .screening import fault_draws, loo_layouts, loo_residuals_from_estimates, screen_ref, screen_reject_ref, screening_rates
 from .monitoring import (cusum_compose, cusum_fixed, cusum_scan_ref, drift_draws, drift_offsets, monitor_baseline_from_moments,
                          monitor_latch_ref, monitor_ref, monitoring_rates)
+from .hydraulics import (HydraulicNetwork, HydraulicResult, hydraulic_draws, hydraulic_residuals, pipe_headloss, solve_ref,
+                         tree_solution)
 from .sensitivity import (influence_from_table, linear_spread_ref, sensitivity_fold_ref, sensitivity_rows_from_gx,
                           sensitivity_seeds)
 
@@ -26,4 +28,5 @@ __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "Simpl
            "sensitivity_fold_ref", "sensitivity_rows_from_gx", "sensitivity_seeds", "ScreeningBounds", "screening", "loo_layouts",
            "loo_residuals_from_estimates", "screen_reject_ref", "screen_ref", "fault_draws", "screening_rates", "MonitorBaseline", "MonitorResult",
            "monitoring", "cusum_scan_ref", "cusum_fixed", "cusum_compose", "monitor_latch_ref", "monitor_ref",
-           "monitor_baseline_from_moments", "drift_draws", "drift_offsets", "monitoring_rates"]
+           "monitor_baseline_from_moments", "drift_draws", "drift_offsets", "monitoring_rates", "hydraulics", "HydraulicNetwork",
+           "HydraulicResult", "pipe_headloss", "solve_ref", "hydraulic_residuals", "hydraulic_draws", "tree_solution"]

@@ -185,6 +185,9 @@ SIGNATURES = {
     "gatres_screen_reject": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "gatres_cusum_scan": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P]),
     "gatres_monitor_latch": (C.c_int, [_P, _P, _I64, _I32, _I64, _I64, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "gatres_hydraulic_draw": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _U64, _I64, _P, _P, _P]),
+    "gatres_hydraulic_solve": (C.c_int, [_P] * 8 + [_I32, _P, _P, _P, _I64, _I64, _I32, _I32, _F64, _I32] + [_P] * 6),
+    "gatres_hydraulic_valid": (C.c_int, [_P, _P, _P, _I64, _I32, _F64, _F64, _P, _P]),
     "gatres_version": (C.c_char_p, []),
 }
 
@@ -203,6 +206,7 @@ LAYOUT_PAIR_RECORD = 4                              # GATRES_LAYOUT_PAIR_RECORD 
 LAYOUT_ERROR_RECORD = 4                             # GATRES_LAYOUT_ERROR_RECORD (gatres_layout_error_reduce)
 SENSITIVITY_RECORD = 5                              # GATRES_SENSITIVITY_RECORD (gatres_sensitivity_fold)
 CUSUM_STATE, CUSUM_RECORD = 4, 6                    # GATRES_CUSUM_STATE, GATRES_CUSUM_RECORD (gatres_cusum_scan)
+HYD_STATUS, HYD_LDS_BUDGET, HYD_GRID_CAP = 4, 163840, 1024      # GATRES_HYD_* (gatres_hydraulic_solve)
 CRITERIA = {"mse": LOSS_MSE, "mae": LOSS_MAE, "sce": LOSS_SCE}      # the reference's train.py --criterion choices
 
 

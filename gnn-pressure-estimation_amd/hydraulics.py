@@ -1,0 +1,558 @@
+"""Hydraulically consistent pressure snapshots, generated on the device (csrc/k_hydraulics.hip).
+
+The reference gets its training data from a hydraulic solver (EPANET through its scene generator) run over random scenarios of
+demand, roughness and so on; ``wdn_synth.make_snapshots`` is N(0, 1) noise.  This module is the steady-state solver in between:
+``HydraulicNetwork.simulate`` solves S independent scenarios, one workgroup each, and ``generate_store`` draws, solves and
+filters scenarios straight into a ``SnapshotStore``.
+
+THE MODEL (include/gatres.h states it for the kernel; this is the host statement).  Pipes, junctions and fixed-head nodes
+(reservoirs, or tanks held at a level); demand-driven, steady, Hazen-Williams in SI units.  Pipe p from a to b carries q_p
+(m3/s, positive from a to b):
+
+    H_a - H_b = h_p(q_p),    h_p(q) = r_p |q|^0.852 q,    r_p = 10.667 L_p / (C_p^1.852 D_p^4.871)
+
+and at every junction inflow - outflow = demand.  At low flow the law is EPANET's (``pipe_headloss``): where the gradient
+g = 1.852 r |q|^0.852 falls below 1e-7, g = 1e-7 and h = 1e-7 q.  The solver is Newton's method in the global-gradient form of
+Todini & Pilati, as in EPANET: per iteration one symmetric positive definite solve ``A H = F`` over the junctions
+(A_ii = sum 1/g_p, A_ij = -1/g_p), then q <- q - (h - (H_a - H_b)) / g; flows start at 1 ft/s; it stops once
+sum |dq| <= accuracy * sum |q|, or after ``max_iter`` iterations.  Pumps, valves, minor losses and extended-period simulation
+are not modelled.
+
+WHAT DOES NOT HOLD: flows that should be zero do not come to rest on the linear branch.  A head of 100 m resolves 1.4e-14 m
+in fp64, and on the linear branch a head difference becomes a flow with 1 / g = 1e7: one ulp between two neighbours is
+1e-7 m3/s, which is off the linear branch again (it ends near 1e-12 m3/s).  Such flows jitter at 1e-7 .. 1e-6 m3/s from one
+iteration to the next, and each adds its jitter to sum |dq|.  A scenario with zero demand everywhere never meets the stop
+rule (all iterations used, ``converged`` False, heads right to 1e-7 m), and one in which many pipes carry next to nothing --
+dead ends without demand -- may not meet it either once their jitter exceeds accuracy * sum |q|: measured, the 388-node
+network with three reservoirs and zero demand (0.04 m3/s between the reservoirs) does not converge in 40 iterations.
+``generate_store`` counts such scenarios as not_converged and drops them; give every junction a demand range above zero, as
+the default does not (``DEMAND_RANGE`` starts at 0: its draws are positive with probability 1 - 2^-53 per junction, and of
+the order of the upper end).
+
+Host restatements in numpy fp64 (the yardsticks of the tests): ``pipe_headloss``, ``solve_ref``, ``hydraulic_residuals``,
+``hydraulic_draws`` and ``tree_solution``.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+from typing import Dict, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _native
+from .snapshot_store import SnapshotStore
+
+HW_EXPONENT = 1.852
+HW_FACTOR = 10.667
+HW_DIAMETER_EXPONENT = 4.871
+LINEAR_GRADIENT = 1e-7                  # the law at low flow
+START_VELOCITY = 0.3048                 # m/s: 1 ft/s, EPANET's starting flows
+ACCURACY = 1e-6
+MAX_ITER = 40
+HYD_STATUS = _native.HYD_STATUS         # GATRES_HYD_STATUS: iterations, converged, failed, 0
+LDS_BUDGET = _native.HYD_LDS_BUDGET     # GATRES_HYD_LDS_BUDGET
+GRID_CAP = _native.HYD_GRID_CAP         # GATRES_HYD_GRID_CAP
+
+# the ranges of the reference's scenario generator for C-Town (configs/v7.1: pipe, junction and reservoir sections), SI units
+ROUGHNESS_RANGE = (60.128711911111104, 139.0834768)
+DIAMETER_RANGE = (0.051, 0.61)
+LENGTH_RANGE = (4.3, 1280.3)
+ELEVATION_RANGE = (3.48, 113.08)
+HEAD_RANGE = (60.0, 126.21526763089759)
+DEMAND_RANGE = (0.0, 1e-4)
+
+HydraulicResult = namedtuple("HydraulicResult", "pressure head flow iterations converged failed status final_dq")
+HydraulicReference = namedtuple("HydraulicReference", "head flow iterations converged failed final_dq")
+
+
+def pipe_headloss(q, r) -> Tuple[np.ndarray, np.ndarray]:
+    """THE LAW: head loss h and its gradient g at the flow q for the resistance r, with EPANET's rule at low flow."""
+    q = np.asarray(q, dtype=np.float64)
+    r = np.asarray(r, dtype=np.float64)
+    ra = r * np.power(np.abs(q), 0.852)
+    g = 1.852 * ra
+    h = ra * q
+    low = g < LINEAR_GRADIENT
+    g = np.where(low, LINEAR_GRADIENT, g)
+    h = np.where(low, LINEAR_GRADIENT * q, h)
+    return h, g
+
+
+def lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int) -> int:
+    """What a solve workgroup takes of the LDS (gatres.h states the same sum)."""
+    return 8 * (num_nodes * (half_bandwidth + 1) + 2 * num_nodes + 4 * num_pipes) + 4 * (2 * num_pipes + num_nodes) + 64
+
+
+def _mix64(z: np.ndarray) -> np.ndarray:
+    z = z.astype(np.uint64)
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def hydraulic_draws(seed: int, first_scenario: int, num_scenarios: int, d_lo, d_hi, c_lo, c_hi) -> Tuple[np.ndarray, np.ndarray]:
+    """``gatres_hydraulic_draw`` in numpy, bit for bit: (demand [S, N], roughness [S, P]) of the global scenarios
+    ``first_scenario .. first_scenario + num_scenarios``."""
+    d_lo, d_hi = np.asarray(d_lo, dtype=np.float64), np.asarray(d_hi, dtype=np.float64)
+    c_lo, c_hi = np.asarray(c_lo, dtype=np.float64), np.asarray(c_hi, dtype=np.float64)
+    N, P = d_lo.shape[0], c_lo.shape[0]
+    with np.errstate(over="ignore"):
+        g = np.arange(num_scenarios, dtype=np.uint64) + np.uint64(first_scenario % (1 << 64)) + np.uint64(1)
+        stream = _mix64(np.uint64(seed % (1 << 64)) + np.uint64(0x9E3779B97F4A7C15) * g)
+        cell = np.arange(N + P, dtype=np.uint64) + np.uint64(1)
+        h = _mix64(stream[:, None] + np.uint64(0xBF58476D1CE4E5B9) * cell[None, :])
+    u = (h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    demand = d_lo[None, :] + (d_hi - d_lo)[None, :] * u[:, :N]
+    roughness = c_lo[None, :] + (c_hi - c_lo)[None, :] * u[:, N:]
+    return demand, roughness
+
+
+def _half_bandwidth(pipes: np.ndarray, fixed: np.ndarray, position: np.ndarray) -> int:
+    both = ~fixed[pipes[:, 0]] & ~fixed[pipes[:, 1]]
+    if not both.any():
+        return 0
+    return int(np.abs(position[pipes[both, 0]] - position[pipes[both, 1]]).max())
+
+
+def _reverse_cuthill_mckee(num_nodes: int, pipes: np.ndarray, fixed: np.ndarray) -> np.ndarray:
+    """Reverse Cuthill-McKee over the junction-to-junction pipes (a fixed-head node is an identity row: it couples nothing and
+    goes last).  Returns order: solver row -> node."""
+    adj = [[] for _ in range(num_nodes)]
+    for a, b in pipes:
+        if not fixed[a] and not fixed[b]:
+            adj[a].append(int(b))
+            adj[b].append(int(a))
+    deg = np.array([len(set(x)) for x in adj])
+    seen = fixed.copy()
+    out = []
+    for start in sorted(np.flatnonzero(~fixed), key=lambda v: (deg[v], v)):
+        if seen[start]:
+            continue
+        seen[start] = True
+        queue, head = [int(start)], 0
+        while head < len(queue):
+            v = queue[head]
+            head += 1
+            for w in sorted(set(adj[v]), key=lambda x: (deg[x], x)):
+                if not seen[w]:
+                    seen[w] = True
+                    queue.append(w)
+        out.extend(queue)
+    return np.array(out[::-1] + [int(v) for v in np.flatnonzero(fixed)], dtype=np.int32)
+
+
+class HydraulicNetwork:
+    """One water network for the steady-state solver.
+
+    ``edge_index``: int64 [2, 2 P], both directions of every pipe (``wdn_synth.make_wdn_topology``'s layout); pipe p is the p-th
+    column with source < destination, and runs from its source to its destination.  ``length``, ``diameter``: [P] metres;
+    ``elevation``: [N] metres; ``fixed_nodes``: the fixed-head nodes, ``fixed_head``: their heads in metres (the default of
+    ``simulate``).  Refused with ``ValueError``: a graph that is not symmetric or has a pipe from a node to itself, a junction
+    that no path connects to a fixed-head node, a length or diameter that is not positive and finite, a band that does not fit
+    the LDS budget of the kernel.  The solver order is the narrower of the given node order and reverse Cuthill-McKee.
+
+    ``junctions`` are the nodes of a generated store and ``junction_edge_index`` its graph: the pipes between two junctions,
+    renumbered.  A junction whose every pipe leads to a fixed-head node keeps no edge there; such nodes are listed in
+    ``isolated_junctions`` (a model sees them without neighbours -- drop them from the sensor set, or model the reservoir's
+    neighbour as the fixed node)."""
+
+    def __init__(self, edge_index, length, diameter, elevation, fixed_nodes: Sequence[int], fixed_head,
+                 start_velocity: float = START_VELOCITY, device=None):
+        ei = torch.as_tensor(edge_index).detach().cpu()
+        if ei.dim() != 2 or ei.shape[0] != 2 or ei.dtype != torch.int64:
+            raise ValueError("edge_index must be int64 [2, E]")
+        e = ei.numpy()
+        elevation = np.asarray(elevation, dtype=np.float64).reshape(-1)
+        N = int(elevation.shape[0])
+        if N < 2:
+            raise ValueError("a network has at least two nodes")
+        if e.size == 0 or e.min() < 0 or e.max() >= N:
+            raise ValueError("edge_index refers to nodes outside the network")
+        if (e[0] == e[1]).any():
+            raise ValueError("a pipe from a node to itself")
+        fwd = np.sort(e[0] * N + e[1])
+        if not np.array_equal(fwd, np.sort(e[1] * N + e[0])):
+            raise ValueError("edge_index is not symmetric: every pipe needs both directions")
+        pipes = e[:, e[0] < e[1]].T.astype(np.int32)
+        P = int(pipes.shape[0])
+        length = np.asarray(length, dtype=np.float64).reshape(-1)
+        diameter = np.asarray(diameter, dtype=np.float64).reshape(-1)
+        if length.shape[0] != P or diameter.shape[0] != P:
+            raise ValueError(f"length and diameter must have one entry per pipe ({P})")
+        if not (np.isfinite(length).all() and (length > 0).all() and np.isfinite(diameter).all() and (diameter > 0).all()):
+            raise ValueError("lengths and diameters must be positive and finite")
+        if not np.isfinite(elevation).all():
+            raise ValueError("elevations must be finite")
+        fixed_nodes = np.asarray(fixed_nodes, dtype=np.int64).reshape(-1)
+        heads = np.asarray(fixed_head, dtype=np.float64).reshape(-1)
+        if fixed_nodes.size == 0 or fixed_nodes.min() < 0 or fixed_nodes.max() >= N or np.unique(fixed_nodes).size != fixed_nodes.size:
+            raise ValueError("fixed_nodes must be distinct nodes of the network, at least one")
+        if heads.shape[0] != fixed_nodes.size or not np.isfinite(heads).all():
+            raise ValueError("fixed_head must have one finite head per fixed node")
+        fixed = np.zeros(N, dtype=bool)
+        fixed[fixed_nodes] = True
+        reach = fixed.copy()                                # every junction is fed from a fixed-head node
+        adj = [[] for _ in range(N)]
+        for a, b in pipes:
+            adj[a].append(int(b))
+            adj[b].append(int(a))
+        stack = [int(v) for v in fixed_nodes]
+        while stack:
+            v = stack.pop()
+            for w in adj[v]:
+                if not reach[w]:
+                    reach[w] = True
+                    stack.append(w)
+        if not reach.all():
+            raise ValueError(f"junctions {np.flatnonzero(~reach)[:8].tolist()} are not connected to a fixed-head node")
+
+        self.num_nodes, self.num_pipes = N, P
+        self.edge_index = ei
+        self.pipes = pipes
+        self.length, self.diameter, self.elevation = length, diameter, elevation
+        self.fixed = fixed
+        self.fixed_nodes = fixed_nodes
+        self.fixed_head = np.zeros(N, dtype=np.float64)    # [N]: the heads at the fixed nodes, 0 elsewhere
+        self.fixed_head[fixed_nodes] = heads
+        self.junctions = np.flatnonzero(~fixed)
+        self.coef = HW_FACTOR * length / np.power(diameter, HW_DIAMETER_EXPONENT)
+        self.q_start = float(start_velocity) * (np.pi * diameter * diameter / 4.0)
+        identity = np.arange(N, dtype=np.int32)
+        rcm = _reverse_cuthill_mckee(N, pipes, fixed)
+        rcm_pos = np.empty(N, dtype=np.int32)
+        rcm_pos[rcm] = identity
+        if _half_bandwidth(pipes, fixed, rcm_pos) < _half_bandwidth(pipes, fixed, identity):
+            self.order, self.position = rcm, rcm_pos
+        else:                                               # (the given order is already as narrow: keep it)
+            self.order, self.position = identity, identity.copy()
+        self.half_bandwidth = max(1, _half_bandwidth(pipes, fixed, self.position))
+        if lds_bytes(N, P, self.half_bandwidth) > LDS_BUDGET:
+            raise ValueError(f"the band of {N} rows with half-bandwidth {self.half_bandwidth} needs "
+                             f"{lds_bytes(N, P, self.half_bandwidth)} bytes of LDS, the kernel has {LDS_BUDGET}")
+        # the junction subgraph, renumbered: what a SnapshotStore over the junctions takes
+        renum = np.full(N, -1, dtype=np.int64)
+        renum[self.junctions] = np.arange(self.junctions.size)
+        keep = ~fixed[e[0]] & ~fixed[e[1]]
+        self.junction_edge_index = torch.from_numpy(renum[e[:, keep]])
+        has_edge = np.zeros(N, dtype=bool)
+        has_edge[e[0, keep]] = True
+        self.isolated_junctions = renum[np.flatnonzero(~fixed & ~has_edge)]      # indices INSIDE the junction graph
+        self.device = torch.device(device) if device is not None else None
+        self._static: Dict[str, torch.Tensor] = {}
+
+    # ---- the device side ----------------------------------------------------------------------------------------------------------
+    def _dev(self) -> torch.device:
+        if self.device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("the hydraulic solver runs on a ROCm device; this engine has no CPU path (solve_ref is the "
+                                   "host restatement)")
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        return self.device
+
+    def static(self) -> Dict[str, torch.Tensor]:
+        """The static arrays of ``gatres_hydraulic_solve``, uploaded once."""
+        if not self._static:
+            dev = self._dev()
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+            self._static = {"pipe_a": up(self.pipes[:, 0], np.int32), "pipe_b": up(self.pipes[:, 1], np.int32),
+                            "coef": up(self.coef, np.float64), "q_start": up(self.q_start, np.float64),
+                            "fixed": up(self.fixed, np.uint8), "elevation": up(self.elevation, np.float64),
+                            "order": up(self.order, np.int32), "position": up(self.position, np.int32),
+                            "fixed_head": up(self.fixed_head, np.float64),
+                            "junctions": up(self.junctions, np.int64)}
+        return self._static
+
+    def _f64(self, a, shape, name) -> torch.Tensor:
+        t = torch.as_tensor(a, dtype=torch.float64).to(self._dev()).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+        return t
+
+    def draw(self, num_scenarios: int, seed: int, first_scenario: int, d_lo: torch.Tensor, d_hi: torch.Tensor, c_lo: torch.Tensor,
+             c_hi: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``gatres_hydraulic_draw``: (demand [S, N], roughness [S, P]) on the device."""
+        dev, lib = self._dev(), _native.load()
+        demand = torch.empty((num_scenarios, self.num_nodes), dtype=torch.float64, device=dev)
+        roughness = torch.empty((num_scenarios, self.num_pipes), dtype=torch.float64, device=dev)
+        rc = lib.gatres_hydraulic_draw(d_lo.data_ptr(), d_hi.data_ptr(), c_lo.data_ptr(), c_hi.data_ptr(), num_scenarios,
+                                       self.num_nodes, self.num_pipes, seed % (1 << 64), first_scenario, demand.data_ptr(),
+                                       roughness.data_ptr(), _native.current_stream(dev))
+        _native.check(rc, "gatres_hydraulic_draw")
+        return demand, roughness
+
+    def simulate(self, demand, roughness, fixed_head=None, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
+                 want_head: bool = True, want_flow: bool = True) -> HydraulicResult:
+        """Solve S scenarios on the device.  ``demand`` [S, N] m3/s (ignored at fixed nodes), ``roughness`` [S, P]
+        Hazen-Williams coefficients, ``fixed_head`` None (the network's), [N] or [S, N] (read at fixed nodes).  Every field
+        of the result is a device tensor; nothing is read back."""
+        st, dev, lib = self.static(), self._dev(), _native.load()
+        N, P = self.num_nodes, self.num_pipes
+        demand = torch.as_tensor(demand)
+        if demand.dim() != 2:
+            raise ValueError("demand must be [S, N]")
+        S = int(demand.shape[0])
+        if S < 1:
+            raise ValueError("no scenarios")
+        demand = self._f64(demand, (S, N), "demand")
+        roughness = self._f64(roughness, (S, P), "roughness")
+        if fixed_head is None:
+            fh, stride = st["fixed_head"], 0
+        else:
+            fh = torch.as_tensor(fixed_head, dtype=torch.float64).to(dev).contiguous()
+            if tuple(fh.shape) == (N,):
+                stride = 0
+            elif tuple(fh.shape) == (S, N):
+                stride = N
+            else:
+                raise ValueError(f"fixed_head must be [{N}] or [{S}, {N}]")
+        pressure = torch.empty((S, N), dtype=torch.float32, device=dev)
+        head = torch.empty((S, N), dtype=torch.float64, device=dev) if want_head else None
+        flow = torch.empty((S, P), dtype=torch.float64, device=dev) if want_flow else None
+        status = torch.empty((S, HYD_STATUS), dtype=torch.int32, device=dev)
+        final_dq = torch.empty((S,), dtype=torch.float64, device=dev)
+        rc = lib.gatres_hydraulic_solve(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
+                                        st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
+                                        st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth, demand.data_ptr(),
+                                        roughness.data_ptr(), fh.data_ptr(), stride, S, N, P, float(accuracy), int(max_iter),
+                                        pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), status.data_ptr(),
+                                        final_dq.data_ptr(), _native.current_stream(dev))
+        _native.check(rc, "gatres_hydraulic_solve")
+        return HydraulicResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status, final_dq)
+
+    def valid(self, result: HydraulicResult, pressure_range: Tuple[float, float]) -> torch.Tensor:
+        """``gatres_hydraulic_valid``: uint8 [S], 1 where the scenario converged, did not fail and every junction pressure lies
+        in the range."""
+        st, dev, lib = self.static(), self._dev(), _native.load()
+        S = int(result.pressure.shape[0])
+        out = torch.empty((S,), dtype=torch.uint8, device=dev)
+        rc = lib.gatres_hydraulic_valid(result.pressure.data_ptr(), result.status.data_ptr(), st["fixed"].data_ptr(), S,
+                                        self.num_nodes, float(pressure_range[0]), float(pressure_range[1]), out.data_ptr(),
+                                        _native.current_stream(dev))
+        _native.check(rc, "gatres_hydraulic_valid")
+        return out
+
+    def draw_ranges(self, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE):
+        """(d_lo, d_hi, c_lo, c_hi) as host fp64 arrays: a (lo, hi) pair of scalars for every junction / pipe, or of arrays
+        [N] / [P]; fixed-head nodes get d_lo = d_hi = 0."""
+        d_lo = np.broadcast_to(np.asarray(demand_range[0], dtype=np.float64), (self.num_nodes,)).copy()
+        d_hi = np.broadcast_to(np.asarray(demand_range[1], dtype=np.float64), (self.num_nodes,)).copy()
+        d_lo[self.fixed] = 0.0
+        d_hi[self.fixed] = 0.0
+        c_lo = np.broadcast_to(np.asarray(roughness_range[0], dtype=np.float64), (self.num_pipes,)).copy()
+        c_hi = np.broadcast_to(np.asarray(roughness_range[1], dtype=np.float64), (self.num_pipes,)).copy()
+        return d_lo, d_hi, c_lo, c_hi
+
+    def generate_store(self, num_scenarios: int, seed: int, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE,
+                       pressure_range: Tuple[float, float] = (0.0, 150.0), chunk: int = 1024, normalize: bool = True,
+                       accuracy: float = ACCURACY, max_iter: int = MAX_ITER):
+        """Draw, solve and filter ``num_scenarios`` scenarios into a ``SnapshotStore`` over the junctions (pressures in metres
+        before the store's normalisation).  Per chunk: draw -> solve -> valid, ONE read-back (status and the valid bytes as one
+        tensor), a device ``index_select`` of the kept rows.  Returns ``(store, report)``; the report counts drawn, converged,
+        failed, not_converged, out_of_range and kept scenarios (drawn = kept + out_of_range + not_converged + failed) and gives
+        the maximum and the mean of the iterations over the scenarios that did not fail.  ``RuntimeError`` when nothing is
+        kept.  Rows of all-zero or mostly-zero demand do not meet the ratio stop rule (the module's docstring says why) and
+        are counted as not_converged, not kept: watch that count when the demand range reaches down to zero."""
+        if num_scenarios < 1 or chunk < 1:
+            raise ValueError("num_scenarios and chunk must be positive")
+        st, dev = self.static(), self._dev()
+        ranges = [torch.from_numpy(a).to(dev) for a in self.draw_ranges(demand_range, roughness_range)]
+        kept_rows = []
+        report = {"drawn": 0, "converged": 0, "failed": 0, "not_converged": 0, "out_of_range": 0, "kept": 0, "max_iterations": 0,
+                  "mean_iterations": 0.0}
+        iter_sum = 0
+        for first in range(0, num_scenarios, chunk):
+            n = min(chunk, num_scenarios - first)
+            demand, roughness = self.draw(n, seed, first, *ranges)
+            res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False)
+            ok = self.valid(res, pressure_range)
+            table = torch.cat([res.status[:, :3], ok.to(torch.int32)[:, None]], dim=1).cpu().numpy()     # the read-back
+            rows = np.flatnonzero(table[:, 3])
+            alive = table[:, 2] == 0
+            report["drawn"] += n
+            report["converged"] += int(table[:, 1].sum())
+            report["failed"] += int(table[:, 2].sum())
+            report["kept"] += int(rows.size)
+            if alive.any():
+                report["max_iterations"] = max(report["max_iterations"], int(table[alive, 0].max()))
+                iter_sum += int(table[alive, 0].sum())
+            if rows.size:
+                idx = torch.from_numpy(rows).to(dev)
+                kept_rows.append(res.pressure.index_select(0, idx).index_select(1, st["junctions"]))
+        report["not_converged"] = report["drawn"] - report["converged"] - report["failed"]
+        report["out_of_range"] = report["converged"] - report["kept"]
+        alive_n = report["drawn"] - report["failed"]
+        report["mean_iterations"] = iter_sum / alive_n if alive_n else 0.0
+        if not kept_rows:
+            raise RuntimeError(f"no scenario of {num_scenarios} converged with every junction pressure in {tuple(pressure_range)}: "
+                               f"{report}")
+        store = SnapshotStore(torch.cat(kept_rows, dim=0), self.junction_edge_index, device=dev, normalize=normalize)
+        return store, report
+
+
+# ---- host restatements ----------------------------------------------------------------------------------------------------------------
+def _resistance(network: HydraulicNetwork, roughness: np.ndarray) -> np.ndarray:
+    return network.coef / np.power(roughness, HW_EXPONENT)
+
+
+def _fixed_heads(network: HydraulicNetwork, fixed_head, S: int) -> np.ndarray:
+    fh = network.fixed_head if fixed_head is None else np.asarray(fixed_head, dtype=np.float64)
+    return np.broadcast_to(fh, (S, network.num_nodes))
+
+
+def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, solver: str = "dense", accuracy: float = ACCURACY,
+              max_iter: int = MAX_ITER) -> HydraulicReference:
+    """The algorithm and the stop rule of the kernel in numpy fp64, scenario by scenario, with the kernel's order in every
+    sum of the assembly and of the stop rule; the linear solve is the library's.  ``solver``: "dense"
+    (``numpy.linalg.solve`` on the N x N system in the given node order) or "banded" (``scipy.linalg.solveh_banded`` in the
+    solver order)."""
+    if solver not in ("dense", "banded"):
+        raise ValueError("solver must be 'dense' or 'banded'")
+    demand = np.asarray(demand, dtype=np.float64)
+    roughness = np.asarray(roughness, dtype=np.float64)
+    S, N, P = demand.shape[0], network.num_nodes, network.num_pipes
+    fh = _fixed_heads(network, fixed_head, S)
+    a, b, fixed = network.pipes[:, 0].astype(np.int64), network.pipes[:, 1].astype(np.int64), network.fixed
+    if solver == "banded":
+        from scipy.linalg import solveh_banded
+        pos, W = network.position.astype(np.int64), network.half_bandwidth
+    head = np.full((S, N), np.nan)
+    flow = np.full((S, P), np.nan)
+    iterations = np.zeros(S, dtype=np.int32)
+    converged = np.zeros(S, dtype=bool)
+    failed = np.zeros(S, dtype=bool)
+    final_dq = np.full(S, np.nan)
+    ja, jb = ~fixed[a], ~fixed[b]
+    jj = ja & jb
+    for s in range(S):
+        c = roughness[s]
+        with np.errstate(all="ignore"):
+            r = _resistance(network, c)
+        d = np.where(fixed, 0.0, demand[s])
+        hf = np.where(fixed, fh[s], 0.0)
+        if not (np.isfinite(d).all() and np.isfinite(hf).all() and np.isfinite(c).all() and (c > 0).all()
+                and np.isfinite(r).all() and (r > 0).all()):
+            failed[s] = True
+            continue
+        q = network.q_start.copy()
+        H = hf.copy()
+        rel, ok = 0.0, True
+        for it in range(1, max_iter + 1):
+            iterations[s] = it
+            h, g = pipe_headloss(q, r)
+            pinv, y = 1.0 / g, h / g
+            t = q - y
+            diag = np.zeros(N)
+            F = -d.copy()
+            for p in range(P):                              # a row's sums run over its pipes in pipe order, as in the kernel
+                ap, bp, pi, tp = a[p], b[p], pinv[p], t[p]
+                if ja[p]:
+                    diag[ap] += pi
+                    F[ap] -= tp
+                    if not jb[p]:
+                        F[ap] += pi * hf[bp]
+                if jb[p]:
+                    diag[bp] += pi
+                    F[bp] += tp
+                    if not ja[p]:
+                        F[bp] += pi * hf[ap]
+            diag[fixed] = 1.0
+            F[fixed] = hf[fixed]
+            try:
+                if solver == "dense":
+                    A = np.zeros((N, N))
+                    A[np.arange(N), np.arange(N)] = diag
+                    np.add.at(A, (a[jj], b[jj]), -pinv[jj])
+                    np.add.at(A, (b[jj], a[jj]), -pinv[jj])
+                    H = np.linalg.solve(A, F)
+                else:
+                    ab = np.zeros((W + 1, N))
+                    ab[0, pos] = diag
+                    hi, lo = np.maximum(pos[a[jj]], pos[b[jj]]), np.minimum(pos[a[jj]], pos[b[jj]])
+                    np.add.at(ab, (hi - lo, lo), -pinv[jj])
+                    Fb = np.empty(N)
+                    Fb[pos] = F
+                    H = solveh_banded(ab, Fb, lower=True)[pos]
+            except (np.linalg.LinAlgError, ValueError):
+                ok = False
+                break
+            dq = y - (H[a] - H[b]) * pinv
+            q = q - dq
+            dqs, qs = float(np.cumsum(np.abs(dq))[-1]), float(np.cumsum(np.abs(q))[-1])      # (added up in pipe order)
+            if not (np.isfinite(dqs) and np.isfinite(qs)):
+                ok = False
+                break
+            rel = dqs / qs if qs > 0 else (np.inf if dqs > 0 else 0.0)
+            if dqs <= accuracy * qs:
+                converged[s] = True
+                break
+        if not ok:
+            failed[s] = True
+            continue
+        head[s], flow[s], final_dq[s] = H, q, rel
+    return HydraulicReference(head, flow, iterations, converged, failed, final_dq)
+
+
+def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness, fixed_head=None) -> Tuple[np.ndarray, np.ndarray]:
+    """How well (head, flow) satisfy the model, per scenario: (mass, energy).  mass: the largest junction imbalance
+    |inflow - outflow - demand| divided by sum |q| (not divided where that sum is 0); energy: the largest
+    |H_a - H_b - h_p(q_p)| over the pipes and |H_f - fixed head| over the fixed nodes, in metres.  NaN where an input is."""
+    head, flow = np.asarray(head, dtype=np.float64), np.asarray(flow, dtype=np.float64)
+    demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
+    S, N = head.shape[0], network.num_nodes
+    fh = _fixed_heads(network, fixed_head, S)
+    a, b, fixed = network.pipes[:, 0].astype(np.int64), network.pipes[:, 1].astype(np.int64), network.fixed
+    mass, energy = np.empty(S), np.empty(S)
+    for s in range(S):
+        net = np.zeros(N)
+        np.add.at(net, b, flow[s])
+        np.add.at(net, a, -flow[s])
+        imbalance = np.abs(net - demand[s])[~fixed]
+        total = np.abs(flow[s]).sum()
+        worst = imbalance.max() if imbalance.size else 0.0
+        mass[s] = worst / total if total > 0 else worst
+        h, _ = pipe_headloss(flow[s], _resistance(network, roughness[s]))
+        e_pipe = np.abs(head[s][a] - head[s][b] - h).max()
+        e_fixed = np.abs(head[s] - fh[s])[fixed].max()
+        energy[s] = max(e_pipe, e_fixed) if not (np.isnan(e_pipe) or np.isnan(e_fixed)) else np.nan
+    return mass, energy
+
+
+def tree_solution(network: HydraulicNetwork, demand, roughness, fixed_head=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The exact answer on a tree with one fixed-head node, without Newton: a pipe's flow is the demand downstream of it, and the
+    heads follow by path sums of ``pipe_headloss`` from the fixed node.  Returns (head [S, N], flow [S, P])."""
+    N, P = network.num_nodes, network.num_pipes
+    if P != N - 1 or network.fixed_nodes.size != 1:
+        raise ValueError("tree_solution needs a tree (num_pipes == num_nodes - 1) with one fixed-head node")
+    demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
+    S = demand.shape[0]
+    fh = _fixed_heads(network, fixed_head, S)
+    root = int(network.fixed_nodes[0])
+    adj = [[] for _ in range(N)]
+    for p, (a, b) in enumerate(network.pipes):
+        adj[a].append((int(b), p))
+        adj[b].append((int(a), p))
+    parent, parent_pipe, bfs = np.full(N, -1), np.full(N, -1), [root]
+    seen = np.zeros(N, dtype=bool)
+    seen[root] = True
+    for v in bfs:
+        for w, p in adj[v]:
+            if not seen[w]:
+                seen[w] = True
+                parent[w], parent_pipe[w] = v, p
+                bfs.append(w)
+    head, flow = np.empty((S, N)), np.empty((S, P))
+    for s in range(S):
+        below = np.where(network.fixed, 0.0, demand[s]).copy()
+        for v in reversed(bfs[1:]):
+            below[parent[v]] += below[v]
+        r = _resistance(network, roughness[s])
+        head[s, root] = fh[s, root]
+        for v in bfs[1:]:
+            p = parent_pipe[v]
+            sign = 1.0 if network.pipes[p, 1] == v else -1.0          # the pipe runs towards v: its flow is positive
+            flow[s, p] = sign * below[v]
+            h, _ = pipe_headloss(flow[s, p], r[p])
+            head[s, v] = head[s, parent[v]] - sign * float(h)
+    return head, flow

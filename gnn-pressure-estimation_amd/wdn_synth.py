@@ -65,6 +65,25 @@ def make_wdn_topology(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_PIPES
     return torch.tensor([src, dst], dtype=torch.int64)
 
 
+def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_PIPES, num_reservoirs: int = 1, seed: int = 0,
+                           length_range=None, diameter_range=None, elevation_range=None, head_range=None, device=None):
+    """A ``hydraulics.HydraulicNetwork`` on ``make_wdn_topology(num_nodes, num_pipes, seed)``: ``num_reservoirs`` of the nodes
+    are fixed-head nodes, and lengths, diameters, elevations and reservoir heads are seeded uniform numpy draws from the ranges
+    of the reference's scenario generator for C-Town (``hydraulics.LENGTH_RANGE`` and so on) unless given."""
+    from . import hydraulics as H
+    if not 1 <= num_reservoirs < num_nodes:
+        raise ValueError("num_reservoirs must lie in [1, num_nodes)")
+    ei = make_wdn_topology(num_nodes, num_pipes, seed=seed)
+    rng = np.random.RandomState(seed + 7919)
+    fixed_nodes = np.sort(rng.choice(num_nodes, num_reservoirs, replace=False))
+    draw = lambda rg, n: rng.uniform(rg[0], rg[1], n)
+    length = draw(length_range or H.LENGTH_RANGE, num_pipes)
+    diameter = draw(diameter_range or H.DIAMETER_RANGE, num_pipes)
+    elevation = draw(elevation_range or H.ELEVATION_RANGE, num_nodes)
+    head = draw(head_range or H.HEAD_RANGE, num_reservoirs)
+    return H.HydraulicNetwork(ei, length, diameter, elevation, fixed_nodes, head, device=device)
+
+
 def collate_edge_index(edge_index: torch.Tensor, num_nodes: int, batch_size: int) -> torch.Tensor:
     """Block-diagonal batch of ``batch_size`` copies of one topology (PyG ``Batch`` edge_index:
     per-graph edge lists concatenated, node ids offset by ``k * num_nodes``)."""

@@ -1277,6 +1277,83 @@ int gatres_monitor_latch(const int64_t* records, uint8_t* available, int64_t num
                          int64_t series_length, int64_t first_index, int32_t since, int32_t min_sensors, int32_t round,
                          int32_t max_rounds, int32_t* latched, int64_t* latched_rec, void* stream);
 
+/* Hydraulically consistent snapshots (symbols only: the ABI stays; k_hydraulics.hip, hydraulics.py).  THE MODEL, stated once:
+ * a network of N nodes and P pipes; a node is a JUNCTION or a FIXED-HEAD node (a reservoir, or a tank held at a level).  The
+ * analysis is demand-driven and steady, with Hazen-Williams in SI units.  Pipe p runs from node a_p to node b_p, carries the flow
+ * q_p (m3/s, positive from a to b) and loses the head
+ *   H_a - H_b = h_p(q_p),   h_p(q) = r_p |q|^0.852 q,   r_p = 10.667 L_p / (C_p^1.852 D_p^4.871)
+ * (L, D in metres, C the Hazen-Williams roughness coefficient); at every junction, inflow - outflow = demand.  THE LAW AT LOW
+ * FLOW (EPANET's rule, a part of the law and not of the solver), pipe_headloss(q, r) -> (h, g), every operation rounded to fp64:
+ *   a = pow(|q|, 0.852);  ra = r * a;  g = 1.852 * ra;  h = ra * q;   where g < 1e-7:  g = 1e-7, h = 1e-7 * q.
+ * THE SOLVER is Newton's method in the global-gradient form of Todini & Pilati, as in EPANET.  Flows start at
+ * q_p = 0.3048 m/s * pi D_p^2 / 4 (1 ft/s).  One iteration: (h_p, g_p) = pipe_headloss(q_p, r_p), y_p = h_p / g_p; the symmetric
+ * positive definite system A H = F over the junctions, with, for every pipe p at junction i and its other end j,
+ *   A_ii += 1 / g_p;   A_ij -= 1 / g_p (j a junction)  or  F_i += H_j / g_p (j fixed);
+ *   F_i = -demand_i + sum over pipes INTO i of (q_p - y_p) - sum over pipes OUT OF i of (q_p - y_p) + the fixed-head terms;
+ * fixed nodes are identity rows (A_ff = 1, F_f = H_f); then dq_p = y_p - (H_a - H_b) / g_p and q_p <- q_p - dq_p.  The iteration
+ * stops as CONVERGED once sum_p |dq_p| <= accuracy * sum_p |q_p| (the new flows), and otherwise after max_iter iterations.
+ * WHAT DOES NOT HOLD: a flow that should be zero does not come to rest on the linear branch.  A head of 100 m resolves 1.4e-14 m
+ * in fp64 and the linear branch turns a head difference into a flow with 1 / g = 1e7, so one ulp between neighbours is 1e-7 m3/s,
+ * off the linear branch again.  Such flows jitter at 1e-7 .. 1e-6 m3/s between iterations and add that to sum |dq|: a scenario
+ * of zero demand never meets the stop rule (heads right to 1e-7 m, converged 0), and one with many idle pipes may not either.
+ *
+ * gatres_hydraulic_draw: random scenarios.  d_lo, d_hi: device double[N]; c_lo, c_hi: device double[P]; it writes
+ * demand[S][N] and roughness[S][P] (device double).  With all integer arithmetic modulo 2^64 and mix64 as stated at
+ * gatres_stage_observed_noisy, scenario s of the call being the GLOBAL scenario g = first_scenario + s:
+ *   stream = mix64(seed + 0x9E3779B97F4A7C15 * (g + 1))
+ *   h      = mix64(stream + 0xBF58476D1CE4E5B9 * (cell + 1))      cell = i for demand[s][i],  N + p for roughness[s][p]
+ *   u      = (h >> 11) * 2^-53                                    in [0, 1), exact in fp64
+ *   value  = lo + (hi - lo) * u                                   the subtraction, the product and the sum rounded separately
+ * so a value is a pure function of (seed, g, cell): chunks of scenarios give the bits of one call, and hydraulics.hydraulic_draws
+ * gives them in numpy.  Fixed-head nodes are given d_lo = d_hi = 0 by the caller.  GATRES_E_BADARG before any launch: a NULL
+ * pointer; num_scenarios, num_nodes or num_pipes < 1; first_scenario < 0 or first_scenario + num_scenarios above 2^62; demand
+ * or roughness overlapping an input or one another.
+ *
+ * gatres_hydraulic_solve: one workgroup per scenario on a grid capped at GATRES_HYD_GRID_CAP; the scenarios beyond it are taken by
+ * a loop.  STATIC inputs (device): pipe_a, pipe_b int32[P]; coef double[P] = 10.667 L / D^4.871 (so r = coef / pow(C, 1.852));
+ * q_start double[P]; fixed uint8[N]; elevation double[N]; order int32[N] (solver row -> node) and position int32[N] (node ->
+ * solver row), a permutation chosen by the caller for a narrow band; half_bandwidth W: |position[a] - position[b]| <= W for every
+ * pipe between two junctions.  PER-SCENARIO inputs (device): demand double[S][N] (ignored at fixed nodes), roughness double[S][P],
+ * fixed_head double, row s at fixed_head + s * fixed_head_stride, fixed_head_stride 0 (one row for all) or N (read at fixed
+ * nodes only).  The lower band of A ((W + 1) doubles per row), the vectors and the pipe state live in LDS in fp64; the whole
+ * Newton loop runs inside the kernel: assembly row by row over the pipes in pipe order, a banded LDL^T without pivoting, column
+ * by column, with the forward substitution in the same sweep, the backward substitution column by column, and the two sums of the
+ * stop rule added up in pipe order by one thread each.  Every order is fixed: a scenario's bits depend neither on S, nor on its
+ * position, nor on the launch.  A shape whose LDS need
+ *   8 * (N * (W + 1) + 2 N + 4 P) + 4 * (2 P + N) + 64 bytes
+ * exceeds GATRES_HYD_LDS_BUDGET is refused.  The budget is a CU's whole LDS; the largest launch the tests make takes 162 932
+ * bytes of it (139 rows with the full band).  Above 64 KB the call raises the kernel's dynamic-LDS limit first; should the
+ * runtime refuse that, the call returns its HIP error code (positive), launches nothing and leaves the outputs untouched.  OUTPUTS, in the caller's node and pipe order: pressure float[S][N] =
+ * (float)(head - elevation); head double[S][N] or NULL; flow double[S][P] or NULL; status int32[S][GATRES_HYD_STATUS] =
+ * {iterations used, converged, failed, 0}; final_dq double[S], the last sum |dq| / sum |q| (0 where both are 0).
+ * FAILED: a non-finite demand at a junction, fixed head at a fixed node, or a roughness that is not positive and finite; a pivot
+ * that is not positive and finite; a non-finite sum in the stop rule; static arrays that are not what is stated above (an end
+ * node outside [0, N), a pipe from a node to itself, order / position no permutation pair, a junction pair wider than W).  A
+ * failed scenario gets NaN in pressure, head, flow and final_dq, status {iterations so far, 0, 1, 0}, and the next scenario is
+ * taken: every loop is bounded by max_iter, N, P and W and every index is checked, whatever the inputs hold.
+ * GATRES_E_BADARG before any launch: a NULL pointer other than head or flow; S, N or P < 1; N < 2; W outside [1, N - 1]; the LDS
+ * need above; max_iter < 1; accuracy not positive and finite; a stride other than 0 or N; an output overlapping an input or
+ * another output. */
+#define GATRES_HYD_STATUS 4
+#define GATRES_HYD_LDS_BUDGET 163840
+#define GATRES_HYD_GRID_CAP 1024
+int gatres_hydraulic_draw(const double* d_lo, const double* d_hi, const double* c_lo, const double* c_hi, int64_t num_scenarios,
+                          int32_t num_nodes, int32_t num_pipes, uint64_t seed, int64_t first_scenario, double* demand,
+                          double* roughness, void* stream);
+int gatres_hydraulic_solve(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                           const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                           int32_t half_bandwidth, const double* demand, const double* roughness, const double* fixed_head,
+                           int64_t fixed_head_stride, int64_t num_scenarios, int32_t num_nodes, int32_t num_pipes, double accuracy,
+                           int32_t max_iter, float* pressure, double* head, double* flow, int32_t* status, double* final_dq,
+                           void* stream);
+
+/* valid[s] (device uint8) = 1 iff status[s] says converged and not failed and pressure[s][i] lies in [p_lo, p_hi] (compared in
+ * fp64; a NaN lies outside) at every junction i (fixed[i] == 0); else 0.  One wave per scenario on a capped grid.
+ * GATRES_E_BADARG before any launch: a NULL pointer; num_scenarios or num_nodes < 1; p_lo or p_hi NaN, or p_lo > p_hi; valid
+ * overlapping an input. */
+int gatres_hydraulic_valid(const float* pressure, const int32_t* status, const uint8_t* fixed, int64_t num_scenarios,
+                           int32_t num_nodes, double p_lo, double p_hi, uint8_t* valid, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
