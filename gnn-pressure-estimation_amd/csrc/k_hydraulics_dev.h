@@ -1,0 +1,197 @@
+// The hydraulic Newton loop, stated once for the two kernels of k_hydraulics.hip (hydraulic_solve_kernel: one steady scenario per
+// workgroup; hydraulic_series_kernel: one series of steps per workgroup).  gatres.h states the model, the law at low flow and the
+// solver.  Everything here works on one workgroup's LDS arrays; every sum runs in a fixed order.
+#pragma once
+#include "gatres_common.h"
+
+#include <float.h>
+#include <math.h>
+
+namespace {
+
+constexpr int HY_T = 256;                                  // threads of a solve workgroup
+constexpr double HY_LINEAR_G = 1e-7;                       // the law at low flow (gatres.h)
+
+__device__ __forceinline__ bool hy_finite(double v) { return fabs(v) <= DBL_MAX; }        // (false for a NaN)
+
+// pipe_headloss of gatres.h / hydraulics.py
+__device__ __forceinline__ void pipe_headloss(double q, double r, double* h, double* g) {
+  const double ra = r * pow(fabs(q), 0.852);
+  double gg = 1.852 * ra, hh = ra * q;
+  if (gg < HY_LINEAR_G) {
+    gg = HY_LINEAR_G;
+    hh = HY_LINEAR_G * q;
+  }
+  *h = hh;
+  *g = gg;
+}
+
+// The LDS arrays of the Newton loop (a workgroup's own; the kernels lay them out)
+struct HyLds {
+  double* band;                                            // [N][W + 1]: band[r * BW + k] = A[r][r - k], rows in solver order
+  double* y;                                               // [N] the right-hand side, then the substitutions' vector
+  double* H;                                               // [N] heads by solver row; the fixed rows are set by the caller
+  double* q;                                               // [P] flows: the start on entry, the result on return
+  double* rr;                                              // [P] resistance r_p
+  double* pinv;                                            // [P] 1 / g_p; after the flow update |dq_p|
+  double* yv;                                              // [P] h_p / g_p; after the flow update |q_p|
+  double* red;                                             // [4] the two sums of the stop rule
+  int *sa, *sb;                                            // [P] solver rows of a pipe's ends
+  int* fx;                                                 // [N] fixed flag by solver row
+};
+
+// The static arrays of a launch, checked: nothing in the kernels indexes with a value that was not checked here.  Fills L.fx,
+// L.sa and L.sb; flag[0] is the workgroup's word for the verdict.  Returns true where an array is not what gatres.h states; the
+// permutation is good (position may index L.fx) exactly where *perm_ok.  Ends behind a barrier.
+__device__ __forceinline__ bool hy_check_static(const HyLds& L, const int* __restrict__ position, const int* __restrict__ order,
+                                                const uint8_t* __restrict__ fixed, const int* __restrict__ pipe_a,
+                                                const int* __restrict__ pipe_b, int N, int P, int W, int* flag, int tid,
+                                                bool* perm_good = nullptr) {
+  int *sa = L.sa, *sb = L.sb, *fx = L.fx;
+  if (tid == 0) flag[0] = 0;
+  __syncthreads();
+  for (int n = tid; n < N; n += HY_T) {
+    const int r = position[n];
+    bool ok = r >= 0 && r < N;
+    if (ok) ok = order[r] == n;                            // (holds for every n: position is a permutation, order its inverse)
+    if (ok) fx[r] = fixed[n] ? 1 : 0;
+    else flag[0] = 1;
+  }
+  __syncthreads();
+  const bool perm_ok = flag[0] == 0;
+  if (perm_good) *perm_good = perm_ok;
+  for (int p = tid; p < P; p += HY_T) {
+    const int a = pipe_a[p], b = pipe_b[p];
+    bool ok = perm_ok && a >= 0 && a < N && b >= 0 && b < N && a != b;
+    int ra = 0, rb = 0;
+    if (ok) {
+      ra = position[a];
+      rb = position[b];
+      const int gap = ra > rb ? ra - rb : rb - ra;
+      if (fx[ra] == 0 && fx[rb] == 0 && gap > W) ok = false;
+    }
+    if (!ok) {
+      ra = rb = 0;
+      flag[0] = 1;
+    }
+    sa[p] = ra;
+    sb[p] = rb;
+  }
+  __syncthreads();
+  return flag[0] != 0;
+}
+
+struct HyNewton {
+  int iters;
+  bool converged, failed;
+  double rel;                                              // the last sum |dq| / sum |q|
+};
+
+// The whole Newton loop of one scenario, run by all HY_T threads of the workgroup.  position: node -> solver row (checked by the
+// caller); dem: the demands by node, in global memory or in LDS.  The caller has put a barrier behind its writes to L; the loop
+// ends behind a barrier or with values that are the same in every thread.
+__device__ __forceinline__ HyNewton hy_newton(const HyLds& L, const int* __restrict__ position, const double* dem, int N, int P,
+                                              int W, int max_iter, double accuracy, int tid) {
+  const int BW = W + 1;
+  double *band = L.band, *y = L.y, *H = L.H, *q = L.q, *rr = L.rr, *pinv = L.pinv, *yv = L.yv, *red = L.red;
+  const int *sa = L.sa, *sb = L.sb, *fx = L.fx;
+  HyNewton out;
+  out.iters = 0;
+  out.converged = false;
+  out.failed = false;
+  out.rel = 0.0;
+  for (int it = 1; it <= max_iter; ++it) {
+    out.iters = it;
+    // the law at the present flows
+    for (int p = tid; p < P; p += HY_T) {
+      double h, g;
+      pipe_headloss(q[p], rr[p], &h, &g);
+      pinv[p] = 1.0 / g;
+      yv[p] = h / g;
+    }
+    __syncthreads();
+    // assembly: one thread per row, over the pipes in pipe order
+    for (int n = tid; n < N; n += HY_T) {
+      const int r = position[n];
+      double* row = band + (size_t)r * BW;
+      for (int k = 0; k < BW; ++k) row[k] = 0.0;
+      if (fx[r]) {
+        row[0] = 1.0;
+        y[r] = H[r];
+      } else {
+        double diag = 0.0, f = -dem[n];
+        for (int p = 0; p < P; ++p) {
+          const int a = sa[p], b = sb[p];
+          if (a != r && b != r) continue;
+          const int o = a == r ? b : a;
+          const double pi = pinv[p], t = q[p] - yv[p];
+          diag += pi;
+          f = b == r ? f + t : f - t;
+          if (fx[o]) f += pi * H[o];
+          else if (o < r) row[r - o] -= pi;                // (r - o <= W: checked by the caller)
+        }
+        row[0] = diag;
+        y[r] = f;
+      }
+    }
+    __syncthreads();
+    // banded LDL^T, column by column, the columns left unscaled (v_ij = L_ij d_j), with the forward substitution
+    bool bad = false;
+    for (int j = 0; j < N; ++j) {
+      const double d = band[(size_t)j * BW];
+      if (!(d > 0.0) || !hy_finite(d)) {                   // (the same value in every thread)
+        bad = true;
+        break;
+      }
+      const int m = W < N - 1 - j ? W : N - 1 - j;
+      const double zj = y[j] / d;
+      for (int e = tid; e < m * m; e += HY_T) {
+        const int r = e / m + 1, c = e - (r - 1) * m + 1;
+        if (c <= r) {
+          const double vr = band[(size_t)(j + r) * BW + r], vc = band[(size_t)(j + c) * BW + c];
+          band[(size_t)(j + r) * BW + (r - c)] -= vr * (vc / d);
+        }
+      }
+      for (int t = tid; t < m; t += HY_T) y[j + 1 + t] -= band[(size_t)(j + 1 + t) * BW + (t + 1)] * zj;
+      __syncthreads();
+    }
+    if (bad) {
+      out.failed = true;
+      break;
+    }
+    // backward substitution, column by column
+    for (int k = N - 1; k >= 0; --k) {
+      const double xk = y[k] / band[(size_t)k * BW];
+      const int m = W < k ? W : k;
+      for (int t = tid + 1; t <= m; t += HY_T) y[k - t] -= band[(size_t)k * BW + t] * xk;
+      if (tid == 0) H[k] = xk;
+      __syncthreads();
+    }
+    // the flows
+    for (int p = tid; p < P; p += HY_T) {
+      const double dq = yv[p] - (H[sa[p]] - H[sb[p]]) * pinv[p], qn = q[p] - dq;
+      q[p] = qn;
+      pinv[p] = fabs(dq);
+      yv[p] = fabs(qn);
+    }
+    __syncthreads();
+    if (tid == 0 || tid == 64) {                           // one thread per sum, in pipe order
+      const double* v = tid == 0 ? pinv : yv;
+      double sum = 0.0;
+      for (int p = 0; p < P; ++p) sum += v[p];
+      red[tid == 0 ? 0 : 1] = sum;
+    }
+    __syncthreads();
+    const double dqs = red[0], qs = red[1];
+    if (!hy_finite(dqs) || !hy_finite(qs)) {
+      out.failed = true;
+      break;
+    }
+    out.rel = qs > 0.0 ? dqs / qs : (dqs > 0.0 ? __longlong_as_double(0x7FF0000000000000ll) : 0.0);
+    out.converged = dqs <= accuracy * qs;
+    if (out.converged) break;
+  }
+  return out;
+}
+
+}  // namespace

@@ -15,8 +15,27 @@ and at every junction inflow - outflow = demand.  At low flow the law is EPANET'
 g = 1.852 r |q|^0.852 falls below 1e-7, g = 1e-7 and h = 1e-7 q.  The solver is Newton's method in the global-gradient form of
 Todini & Pilati, as in EPANET: per iteration one symmetric positive definite solve ``A H = F`` over the junctions
 (A_ii = sum 1/g_p, A_ij = -1/g_p), then q <- q - (h - (H_a - H_b)) / g; flows start at 1 ft/s; it stops once
-sum |dq| <= accuracy * sum |q|, or after ``max_iter`` iterations.  Pumps, valves, minor losses and extended-period simulation
-are not modelled.
+sum |dq| <= accuracy * sum |q|, or after ``max_iter`` iterations.  Pumps, valves, minor losses, controls and rules are not
+modelled.
+
+THE SERIES (``simulate_series``, ``generate_series_store``; gatres.h: THE SERIES): extended-period simulation, T steps of
+``step_seconds`` of one scenario in one launch, one workgroup per series.  Tanks are a subset of the fixed-head nodes: tank k
+has its bottom at the node's elevation, a diameter D_k, the area A_k = pi D_k^2 / 4 and level limits min_level[k] <=
+max_level[k]; during step t its head is elevation + level[t][k], one fp64 add.  Reservoirs, the other fixed-head nodes, keep
+their heads.  Junction n of series s draws demand[s][n] * mult[pattern_of_node[n]][t] at step t (one rounded product).  A step
+is the steady solve above; step 0 starts from the starting flows, step t > 0 from the final flows of step t - 1 (``warm_start``,
+EPANET's way) or from the starting flows again.  After step t the levels move by explicit Euler, as in EPANET:
+inflow_k = the sum over the pipes in pipe order of +q_p where the pipe ends at the tank and -q_p where it starts there, and
+level[t + 1][k] = clamp(level[t][k] + (inflow_k * dt) / A_k, min_level[k], max_level[k]), every operation rounded on its own.
+A multiplier that is negative or not finite, a non-finite product or tank head, a bad pivot or non-finite sums fail the step and
+every later step of the series (NaN outputs, status failed; earlier steps keep theirs); a step that merely does not converge is
+no failure and the series goes on from its flows.
+
+WHAT DOES NOT HOLD IN A SERIES: EPANET shortens a time step at the moment a tank becomes full or empty and closes the pipes of
+such a tank; this model clamps the level and does neither.  A step after which any level was clamped has status[s][t][3] = 1
+(``limited``), and volume is not conserved across such a step; ``series_valid`` and ``generate_series_store`` drop such series
+unless told otherwise.  Pumps, valves, minor losses, controls and rules stay out of scope.  The limit on flows that should be
+zero (below) carries over unchanged: a step with a zero multiplier will not meet the stop rule.
 
 WHAT DOES NOT HOLD: flows that should be zero do not come to rest on the linear branch.  A head of 100 m resolves 1.4e-14 m
 in fp64, and on the linear branch a head difference becomes a flow with 1 / g = 1e7: one ulp between two neighbours is
@@ -30,7 +49,8 @@ the default does not (``DEMAND_RANGE`` starts at 0: its draws are positive with 
 the order of the upper end).
 
 Host restatements in numpy fp64 (the yardsticks of the tests): ``pipe_headloss``, ``solve_ref``, ``hydraulic_residuals``,
-``hydraulic_draws`` and ``tree_solution``.
+``hydraulic_draws``, ``tree_solution``, ``simulate_series_ref``, ``level_update_ref``, ``series_valid_ref`` and
+``series_volume_balance``.
 """
 from __future__ import annotations
 
@@ -61,9 +81,14 @@ LENGTH_RANGE = (4.3, 1280.3)
 ELEVATION_RANGE = (3.48, 113.08)
 HEAD_RANGE = (60.0, 126.21526763089759)
 DEMAND_RANGE = (0.0, 1e-4)
+TANK_DIAMETER_RANGE = (7.140000000000001, 31.3)       # (the tank section of the same file)
+TANK_LEVEL_RANGE = (0.0, 4.940000000000007)
+LEVEL_SEED_OFFSET = 0x74616E6B          # generate_series_store draws the initial levels with seed + this, mod 2^64
 
 HydraulicResult = namedtuple("HydraulicResult", "pressure head flow iterations converged failed status final_dq")
 HydraulicReference = namedtuple("HydraulicReference", "head flow iterations converged failed final_dq")
+HydraulicSeriesResult = namedtuple("HydraulicSeriesResult", "pressure head flow level iterations converged failed limited status final_dq")
+HydraulicSeriesReference = namedtuple("HydraulicSeriesReference", "head flow level iterations converged failed limited final_dq")
 
 
 def pipe_headloss(q, r) -> Tuple[np.ndarray, np.ndarray]:
@@ -82,6 +107,12 @@ def pipe_headloss(q, r) -> Tuple[np.ndarray, np.ndarray]:
 def lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int) -> int:
     """What a solve workgroup takes of the LDS (gatres.h states the same sum)."""
     return 8 * (num_nodes * (half_bandwidth + 1) + 2 * num_nodes + 4 * num_pipes) + 4 * (2 * num_pipes + num_nodes) + 64
+
+
+def series_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_tanks: int) -> int:
+    """What a series workgroup takes of the LDS (gatres.h states the same sum): a solve workgroup's arrays, the step's demand
+    and per tank the level, the area, two limits, the node and its row."""
+    return lds_bytes(num_nodes, num_pipes, half_bandwidth) + 8 * num_nodes + 40 * num_tanks
 
 
 def _mix64(z: np.ndarray) -> np.ndarray:
@@ -153,13 +184,20 @@ class HydraulicNetwork:
     that no path connects to a fixed-head node, a length or diameter that is not positive and finite, a band that does not fit
     the LDS budget of the kernel.  The solver order is the narrower of the given node order and reverse Cuthill-McKee.
 
+    TANKS (``simulate_series``): ``tank_nodes`` are a subset of ``fixed_nodes``; ``tank_diameter`` [K] metres; ``tank_min_level``,
+    ``tank_max_level`` [K] metres above the node's elevation, default (0, +inf).  An infinite maximum IS allowed: a tank that
+    is never full.  Refused with ``ValueError``: a tank that is not a fixed node, duplicate tanks, a diameter that is not
+    positive and finite, a minimum that is not finite, a maximum that is NaN or -inf, min > max.  ``simulate`` ignores the tanks:
+    there every fixed-head node is held at its head.
+
     ``junctions`` are the nodes of a generated store and ``junction_edge_index`` its graph: the pipes between two junctions,
     renumbered.  A junction whose every pipe leads to a fixed-head node keeps no edge there; such nodes are listed in
     ``isolated_junctions`` (a model sees them without neighbours -- drop them from the sensor set, or model the reservoir's
     neighbour as the fixed node)."""
 
     def __init__(self, edge_index, length, diameter, elevation, fixed_nodes: Sequence[int], fixed_head,
-                 start_velocity: float = START_VELOCITY, device=None):
+                 start_velocity: float = START_VELOCITY, device=None, tank_nodes=None, tank_diameter=None, tank_min_level=None,
+                 tank_max_level=None):
         ei = torch.as_tensor(edge_index).detach().cpu()
         if ei.dim() != 2 or ei.shape[0] != 2 or ei.dtype != torch.int64:
             raise ValueError("edge_index must be int64 [2, E]")
@@ -217,6 +255,28 @@ class HydraulicNetwork:
         self.fixed_head = np.zeros(N, dtype=np.float64)    # [N]: the heads at the fixed nodes, 0 elsewhere
         self.fixed_head[fixed_nodes] = heads
         self.junctions = np.flatnonzero(~fixed)
+        # the tanks of a series (simulate_series): a subset of the fixed-head nodes
+        tanks = np.asarray([] if tank_nodes is None else tank_nodes, dtype=np.int64).reshape(-1)
+        K = int(tanks.size)
+        if K and (tanks.min() < 0 or tanks.max() >= N or not fixed[tanks].all()):
+            raise ValueError("tank_nodes must be fixed-head nodes of the network")
+        if np.unique(tanks).size != K:
+            raise ValueError("tank_nodes must be distinct")
+        if K == 0 and any(v is not None and np.asarray(v).size for v in (tank_diameter, tank_min_level, tank_max_level)):
+            raise ValueError("tank_diameter and the level limits need tank_nodes")
+        t_dia = np.asarray([] if tank_diameter is None else tank_diameter, dtype=np.float64).reshape(-1)
+        t_min = np.zeros(K) if tank_min_level is None else np.asarray(tank_min_level, dtype=np.float64).reshape(-1)
+        t_max = np.full(K, np.inf) if tank_max_level is None else np.asarray(tank_max_level, dtype=np.float64).reshape(-1)
+        if t_dia.shape[0] != K or t_min.shape[0] != K or t_max.shape[0] != K:
+            raise ValueError(f"tank_diameter and the level limits must have one entry per tank ({K})")
+        if not (np.isfinite(t_dia).all() and (t_dia > 0).all()):
+            raise ValueError("tank diameters must be positive and finite")
+        # the maximum may be +inf (the default: a tank that is never full); a minimum is finite, and nothing is NaN
+        if not np.isfinite(t_min).all() or np.isnan(t_max).any() or (t_max == -np.inf).any() or (t_min > t_max).any():
+            raise ValueError("tank level limits must be finite (the maximum may be +inf) with min <= max")
+        self.tank_nodes, self.tank_diameter, self.tank_min_level, self.tank_max_level = tanks, t_dia, t_min, t_max
+        self.num_tanks = K
+        self.tank_area = np.pi * t_dia * t_dia / 4.0
         self.coef = HW_FACTOR * length / np.power(diameter, HW_DIAMETER_EXPONENT)
         self.q_start = float(start_velocity) * (np.pi * diameter * diameter / 4.0)
         identity = np.arange(N, dtype=np.int32)
@@ -261,7 +321,10 @@ class HydraulicNetwork:
                             "fixed": up(self.fixed, np.uint8), "elevation": up(self.elevation, np.float64),
                             "order": up(self.order, np.int32), "position": up(self.position, np.int32),
                             "fixed_head": up(self.fixed_head, np.float64),
-                            "junctions": up(self.junctions, np.int64)}
+                            "junctions": up(self.junctions, np.int64),
+                            "tank_node": up(self.tank_nodes, np.int32), "tank_area": up(self.tank_area, np.float64),
+                            "tank_min": up(self.tank_min_level, np.float64), "tank_max": up(self.tank_max_level, np.float64),
+                            "pattern0": torch.zeros(self.num_nodes, dtype=torch.int32, device=dev)}
         return self._static
 
     def _f64(self, a, shape, name) -> torch.Tensor:
@@ -333,6 +396,173 @@ class HydraulicNetwork:
         _native.check(rc, "gatres_hydraulic_valid")
         return out
 
+    # ---- the series ---------------------------------------------------------------------------------------------------------------
+    def simulate_series(self, demand, roughness, multipliers, *, step_seconds: float, initial_level=None, pattern_of_node=None,
+                        fixed_head=None, warm_start: bool = True, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
+                        want_head: bool = True, want_flow: bool = True) -> HydraulicSeriesResult:
+        """``gatres_hydraulic_series``: S series of T steps on the device, one launch.  ``demand`` [S, N] base demands,
+        ``roughness`` [S, P], ``multipliers`` [M, T] (for every series) or [S, M, T], ``pattern_of_node`` int [N] with values in
+        [0, M) (default: pattern 0 everywhere; host data outside the range raises ``ValueError``, a DEVICE tensor is not read back
+        and a value outside the range makes the kernel fail every series of the launch), ``initial_level`` [S, K] or [K] (default: fixed_head - elevation at the tank
+        nodes), ``fixed_head`` as in ``simulate``.  Every field of the result is a device tensor; nothing is read back:
+        pressure [S, T, N] fp32, head [S, T, N], flow [S, T, P], level [S, T + 1, K], iterations / converged / failed / limited
+        [S, T], status [S, T, 4], final_dq [S, T].  A network without tanks works (K = 0: patterns only)."""
+        st, dev, lib = self.static(), self._dev(), _native.load()
+        N, P, K = self.num_nodes, self.num_pipes, self.num_tanks
+        demand = torch.as_tensor(demand)
+        if demand.dim() != 2:
+            raise ValueError("demand must be [S, N]")
+        S = int(demand.shape[0])
+        if S < 1:
+            raise ValueError("no series")
+        demand = self._f64(demand, (S, N), "demand")
+        roughness = self._f64(roughness, (S, P), "roughness")
+        mult = torch.as_tensor(multipliers, dtype=torch.float64).to(dev).contiguous()
+        if mult.dim() == 2 and mult.shape[0] >= 1 and mult.shape[1] >= 1:
+            M, T, mult_stride = int(mult.shape[0]), int(mult.shape[1]), 0
+        elif mult.dim() == 3 and mult.shape[0] == S and mult.shape[1] >= 1 and mult.shape[2] >= 1:
+            M, T = int(mult.shape[1]), int(mult.shape[2])
+            mult_stride = M * T
+        else:
+            raise ValueError(f"multipliers must be [M, T] or [{S}, M, T]")
+        if pattern_of_node is None:
+            pattern = st["pattern0"]
+        else:
+            on_device = isinstance(pattern_of_node, torch.Tensor) and pattern_of_node.is_cuda
+            pattern = torch.as_tensor(pattern_of_node)
+            if tuple(pattern.shape) != (N,):
+                raise ValueError(f"pattern_of_node must be [{N}]")
+            if not on_device and (int(pattern.min()) < 0 or int(pattern.max()) >= M):      # (host data: no read-back)
+                raise ValueError(f"pattern_of_node must hold values in [0, {M})")
+            pattern = pattern.to(device=dev, dtype=torch.int32).contiguous()
+        if fixed_head is None:
+            fh, stride = st["fixed_head"], 0
+        else:
+            fh = torch.as_tensor(fixed_head, dtype=torch.float64).to(dev).contiguous()
+            if tuple(fh.shape) == (N,):
+                stride = 0
+            elif tuple(fh.shape) == (S, N):
+                stride = N
+            else:
+                raise ValueError(f"fixed_head must be [{N}] or [{S}, {N}]")
+        if initial_level is None:
+            elev = st["elevation"].index_select(0, st["tank_node"].to(torch.int64))
+            level0 = (fh.reshape(-1, N).index_select(1, st["tank_node"].to(torch.int64)) - elev[None, :]).expand(S, K).contiguous()
+        else:
+            if isinstance(initial_level, np.ndarray):
+                initial_level = np.array(initial_level, dtype=np.float64)                     # (a copy: the array may be read-only)
+            level0 = torch.as_tensor(initial_level, dtype=torch.float64).to(dev)
+            if tuple(level0.shape) == (K,):
+                level0 = level0[None, :].expand(S, K)
+            if tuple(level0.shape) != (S, K):
+                raise ValueError(f"initial_level must be [{K}] or [{S}, {K}]")
+            level0 = level0.contiguous()
+        if not (float(step_seconds) > 0.0 and np.isfinite(float(step_seconds))):
+            raise ValueError("step_seconds must be positive and finite")
+        pressure = torch.empty((S, T, N), dtype=torch.float32, device=dev)
+        head = torch.empty((S, T, N), dtype=torch.float64, device=dev) if want_head else None
+        flow = torch.empty((S, T, P), dtype=torch.float64, device=dev) if want_flow else None
+        level = torch.empty((S, T + 1, K), dtype=torch.float64, device=dev)
+        status = torch.empty((S, T, HYD_STATUS), dtype=torch.int32, device=dev)
+        final_dq = torch.empty((S, T), dtype=torch.float64, device=dev)
+        tp = (lambda t: t.data_ptr()) if K else (lambda t: None)
+        rc = lib.gatres_hydraulic_series(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
+                                         st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
+                                         st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
+                                         tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
+                                         pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(),
+                                         roughness.data_ptr(), fh.data_ptr(), stride, tp(level0), S, T, N, P, float(step_seconds),
+                                         1 if warm_start else 0, float(accuracy), int(max_iter), pressure.data_ptr(),
+                                         _native.ptr(head), _native.ptr(flow), tp(level), status.data_ptr(), final_dq.data_ptr(),
+                                         _native.current_stream(dev))
+        _native.check(rc, "gatres_hydraulic_series")
+        return HydraulicSeriesResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0, status[:, :, 2] != 0,
+                                     status[:, :, 3] != 0, status, final_dq)
+
+    def series_valid(self, result: HydraulicSeriesResult, pressure_range: Tuple[float, float], allow_limited: bool = False) -> torch.Tensor:
+        """``gatres_hydraulic_series_valid``: uint8 [S], 1 where every step of the series converged and none failed, no level
+        was clamped (unless ``allow_limited``) and every junction pressure of every step lies in the range."""
+        st, dev, lib = self.static(), self._dev(), _native.load()
+        S, T = int(result.pressure.shape[0]), int(result.pressure.shape[1])
+        out = torch.empty((S,), dtype=torch.uint8, device=dev)
+        rc = lib.gatres_hydraulic_series_valid(result.pressure.data_ptr(), result.status.data_ptr(), st["fixed"].data_ptr(), S, T,
+                                               self.num_nodes, float(pressure_range[0]), float(pressure_range[1]),
+                                               1 if allow_limited else 0, out.data_ptr(), _native.current_stream(dev))
+        _native.check(rc, "gatres_hydraulic_series_valid")
+        return out
+
+    def level_ranges(self, level_range=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(lo, hi) [K] of the initial-level draw: ``level_range`` (default ``TANK_LEVEL_RANGE``), clipped to the tanks' limits."""
+        lo, hi = TANK_LEVEL_RANGE if level_range is None else level_range
+        lo = np.maximum(np.broadcast_to(np.asarray(lo, dtype=np.float64), (self.num_tanks,)), self.tank_min_level)
+        hi = np.minimum(np.broadcast_to(np.asarray(hi, dtype=np.float64), (self.num_tanks,)), self.tank_max_level)
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all()):
+            raise ValueError("level_range does not meet the tanks' level limits")
+        return lo, hi
+
+    def draw_levels(self, num_series: int, seed: int, first_series: int, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
+        """Initial levels [S, K]: ``gatres_hydraulic_draw`` once more, with N := K and P := 1 and the seed
+        ``seed + LEVEL_SEED_OFFSET`` (mod 2^64); ``hydraulic_draws`` restates it."""
+        dev, lib, K = self._dev(), _native.load(), self.num_tanks
+        level = torch.empty((num_series, K), dtype=torch.float64, device=dev)
+        if K == 0:
+            return level
+        unit = torch.zeros(2, dtype=torch.float64, device=dev)
+        spare = torch.empty((num_series, 1), dtype=torch.float64, device=dev)
+        rc = lib.gatres_hydraulic_draw(lo.data_ptr(), hi.data_ptr(), unit[:1].data_ptr(), unit[1:].data_ptr(), num_series, K, 1,
+                                       (seed + LEVEL_SEED_OFFSET) % (1 << 64), first_series, level.data_ptr(), spare.data_ptr(),
+                                       _native.current_stream(dev))
+        _native.check(rc, "gatres_hydraulic_draw")
+        return level
+
+    def generate_series_store(self, num_series: int, steps: int, seed: int, *, step_seconds: float = 300.0, multipliers=None,
+                              pattern_of_node=None, level_range=None, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE,
+                              pressure_range: Tuple[float, float] = (0.0, 150.0), chunk: int = 256, normalize: bool = True,
+                              allow_limited: bool = False, warm_start: bool = True, accuracy: float = ACCURACY,
+                              max_iter: int = MAX_ITER):
+        """Draw, simulate and filter ``num_series`` series of ``steps`` steps into a ``SnapshotStore`` over the junctions whose
+        rows are series-major (E * steps rows for E kept series: what ``monitor_store(series_length=steps)`` expects).  Base
+        demands and roughness per series come from ``draw``, the initial levels from ``draw_levels``; ``multipliers`` default to
+        ``wdn_synth.make_demand_patterns(1, steps, step_seconds, seed)``.  Per chunk: draws -> series -> series_valid, ONE
+        read-back (status and the valid bytes as one tensor), a device ``index_select`` of whole series.  Returns
+        ``(store, report)``; the report counts series: drawn = kept + failed + not_converged + limited + out_of_range, each dropped
+        series counted once by the first cause in that order (``series_report``), and gives max_iterations, mean_iterations
+        (over the steps that did not fail), mean_iterations_first_step and series_length.  ``RuntimeError`` when nothing is
+        kept."""
+        if num_series < 1 or chunk < 1 or steps < 1:
+            raise ValueError("num_series, steps and chunk must be positive")
+        st, dev = self.static(), self._dev()
+        if multipliers is None:
+            from . import wdn_synth
+            multipliers = wdn_synth.make_demand_patterns(1, steps, step_seconds, seed)
+        mult = torch.as_tensor(multipliers, dtype=torch.float64).to(dev).contiguous()
+        if mult.dim() != 2 or mult.shape[1] != steps:
+            raise ValueError(f"multipliers must be [M, {steps}]")
+        ranges = [torch.from_numpy(a).to(dev) for a in self.draw_ranges(demand_range, roughness_range)]
+        lv = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in self.level_ranges(level_range)]
+        kept_rows, tables = [], []
+        for first in range(0, num_series, chunk):
+            n = min(chunk, num_series - first)
+            demand, roughness = self.draw(n, seed, first, *ranges)
+            level0 = self.draw_levels(n, seed, first, *lv)
+            res = self.simulate_series(demand, roughness, mult, step_seconds=step_seconds, initial_level=level0,
+                                       pattern_of_node=pattern_of_node, warm_start=warm_start, accuracy=accuracy,
+                                       max_iter=max_iter, want_head=False, want_flow=False)
+            ok = self.series_valid(res, pressure_range, allow_limited)
+            table = torch.cat([res.status.reshape(n, -1), ok.to(torch.int32)[:, None]], dim=1).cpu().numpy()     # the read-back
+            tables.append(table)
+            rows = np.flatnonzero(table[:, -1])
+            if rows.size:
+                idx = torch.from_numpy(rows).to(dev)
+                kept = res.pressure.index_select(0, idx).index_select(2, st["junctions"])
+                kept_rows.append(kept.reshape(rows.size * steps, -1))
+        table = np.concatenate(tables, axis=0)
+        report = series_report(table[:, :-1].reshape(-1, steps, HYD_STATUS), table[:, -1], allow_limited)
+        if not kept_rows:
+            raise RuntimeError(f"no series of {num_series} was kept with every junction pressure in {tuple(pressure_range)}: {report}")
+        store = SnapshotStore(torch.cat(kept_rows, dim=0), self.junction_edge_index, device=dev, normalize=normalize)
+        return store, report
+
     def draw_ranges(self, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE):
         """(d_lo, d_hi, c_lo, c_hi) as host fp64 arrays: a (lo, hi) pair of scalars for every junction / pipe, or of arrays
         [N] / [P]; fixed-head nodes get d_lo = d_hi = 0."""
@@ -401,45 +631,37 @@ def _fixed_heads(network: HydraulicNetwork, fixed_head, S: int) -> np.ndarray:
     return np.broadcast_to(fh, (S, network.num_nodes))
 
 
-def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, solver: str = "dense", accuracy: float = ACCURACY,
-              max_iter: int = MAX_ITER) -> HydraulicReference:
-    """The algorithm and the stop rule of the kernel in numpy fp64, scenario by scenario, with the kernel's order in every
-    sum of the assembly and of the stop rule; the linear solve is the library's.  ``solver``: "dense"
-    (``numpy.linalg.solve`` on the N x N system in the given node order) or "banded" (``scipy.linalg.solveh_banded`` in the
-    solver order)."""
-    if solver not in ("dense", "banded"):
-        raise ValueError("solver must be 'dense' or 'banded'")
-    demand = np.asarray(demand, dtype=np.float64)
-    roughness = np.asarray(roughness, dtype=np.float64)
-    S, N, P = demand.shape[0], network.num_nodes, network.num_pipes
-    fh = _fixed_heads(network, fixed_head, S)
-    a, b, fixed = network.pipes[:, 0].astype(np.int64), network.pipes[:, 1].astype(np.int64), network.fixed
-    if solver == "banded":
-        from scipy.linalg import solveh_banded
-        pos, W = network.position.astype(np.int64), network.half_bandwidth
-    head = np.full((S, N), np.nan)
-    flow = np.full((S, P), np.nan)
-    iterations = np.zeros(S, dtype=np.int32)
-    converged = np.zeros(S, dtype=bool)
-    failed = np.zeros(S, dtype=bool)
-    final_dq = np.full(S, np.nan)
-    ja, jb = ~fixed[a], ~fixed[b]
-    jj = ja & jb
-    for s in range(S):
-        c = roughness[s]
-        with np.errstate(all="ignore"):
-            r = _resistance(network, c)
-        d = np.where(fixed, 0.0, demand[s])
-        hf = np.where(fixed, fh[s], 0.0)
-        if not (np.isfinite(d).all() and np.isfinite(hf).all() and np.isfinite(c).all() and (c > 0).all()
-                and np.isfinite(r).all() and (r > 0).all()):
-            failed[s] = True
-            continue
-        q = network.q_start.copy()
+class _NewtonRef:
+    """The per-scenario Newton loop of ``solve_ref`` and ``simulate_series_ref``: the algorithm and the stop rule of the kernel in
+    numpy fp64, with the kernel's order in every sum of the assembly and of the stop rule; the linear solve is the library's."""
+
+    def __init__(self, network: "HydraulicNetwork", solver: str, accuracy: float, max_iter: int):
+        if solver not in ("dense", "banded"):
+            raise ValueError("solver must be 'dense' or 'banded'")
+        self.net, self.solver, self.accuracy, self.max_iter = network, solver, accuracy, max_iter
+        self.a, self.b = network.pipes[:, 0].astype(np.int64), network.pipes[:, 1].astype(np.int64)
+        self.fixed = network.fixed
+        self.ja, self.jb = ~self.fixed[self.a], ~self.fixed[self.b]
+        self.jj = self.ja & self.jb
+        if solver == "banded":
+            from scipy.linalg import solveh_banded
+            self.solveh_banded = solveh_banded
+            self.pos, self.W = network.position.astype(np.int64), network.half_bandwidth
+
+    def inputs_ok(self, d, hf, c, r) -> bool:
+        return bool(np.isfinite(d).all() and np.isfinite(hf).all() and np.isfinite(c).all() and (c > 0).all()
+                    and np.isfinite(r).all() and (r > 0).all())
+
+    def run(self, d, hf, r, q_start):
+        """(H, q, iterations, converged, ok, rel) from the flows ``q_start``; d: demands (0 at fixed nodes), hf: fixed heads (0 at
+        junctions), r: resistances."""
+        N, P = self.net.num_nodes, self.net.num_pipes
+        a, b, fixed, ja, jb, jj = self.a, self.b, self.fixed, self.ja, self.jb, self.jj
+        q = q_start.copy()
         H = hf.copy()
-        rel, ok = 0.0, True
-        for it in range(1, max_iter + 1):
-            iterations[s] = it
+        rel, ok, iterations, converged = 0.0, True, 0, False
+        for it in range(1, self.max_iter + 1):
+            iterations = it
             h, g = pipe_headloss(q, r)
             pinv, y = 1.0 / g, h / g
             t = q - y
@@ -460,20 +682,21 @@ def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, sol
             diag[fixed] = 1.0
             F[fixed] = hf[fixed]
             try:
-                if solver == "dense":
+                if self.solver == "dense":
                     A = np.zeros((N, N))
                     A[np.arange(N), np.arange(N)] = diag
                     np.add.at(A, (a[jj], b[jj]), -pinv[jj])
                     np.add.at(A, (b[jj], a[jj]), -pinv[jj])
                     H = np.linalg.solve(A, F)
                 else:
+                    pos, W = self.pos, self.W
                     ab = np.zeros((W + 1, N))
                     ab[0, pos] = diag
                     hi, lo = np.maximum(pos[a[jj]], pos[b[jj]]), np.minimum(pos[a[jj]], pos[b[jj]])
                     np.add.at(ab, (hi - lo, lo), -pinv[jj])
                     Fb = np.empty(N)
                     Fb[pos] = F
-                    H = solveh_banded(ab, Fb, lower=True)[pos]
+                    H = self.solveh_banded(ab, Fb, lower=True)[pos]
             except (np.linalg.LinAlgError, ValueError):
                 ok = False
                 break
@@ -484,14 +707,184 @@ def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, sol
                 ok = False
                 break
             rel = dqs / qs if qs > 0 else (np.inf if dqs > 0 else 0.0)
-            if dqs <= accuracy * qs:
-                converged[s] = True
+            if dqs <= self.accuracy * qs:
+                converged = True
                 break
+        return H, q, iterations, converged, ok, rel
+
+
+def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, solver: str = "dense", accuracy: float = ACCURACY,
+              max_iter: int = MAX_ITER) -> HydraulicReference:
+    """The algorithm and the stop rule of the kernel in numpy fp64, scenario by scenario, with the kernel's order in every
+    sum of the assembly and of the stop rule; the linear solve is the library's.  ``solver``: "dense"
+    (``numpy.linalg.solve`` on the N x N system in the given node order) or "banded" (``scipy.linalg.solveh_banded`` in the
+    solver order)."""
+    newton = _NewtonRef(network, solver, accuracy, max_iter)
+    demand = np.asarray(demand, dtype=np.float64)
+    roughness = np.asarray(roughness, dtype=np.float64)
+    S, N, P = demand.shape[0], network.num_nodes, network.num_pipes
+    fh = _fixed_heads(network, fixed_head, S)
+    fixed = network.fixed
+    head = np.full((S, N), np.nan)
+    flow = np.full((S, P), np.nan)
+    iterations = np.zeros(S, dtype=np.int32)
+    converged = np.zeros(S, dtype=bool)
+    failed = np.zeros(S, dtype=bool)
+    final_dq = np.full(S, np.nan)
+    for s in range(S):
+        c = roughness[s]
+        with np.errstate(all="ignore"):
+            r = _resistance(network, c)
+        d = np.where(fixed, 0.0, demand[s])
+        hf = np.where(fixed, fh[s], 0.0)
+        if not newton.inputs_ok(d, hf, c, r):
+            failed[s] = True
+            continue
+        H, q, iterations[s], converged[s], ok, rel = newton.run(d, hf, r, network.q_start)
         if not ok:
             failed[s] = True
             continue
         head[s], flow[s], final_dq[s] = H, q, rel
     return HydraulicReference(head, flow, iterations, converged, failed, final_dq)
+
+
+def level_update_ref(network: HydraulicNetwork, level, flow, step_seconds: float) -> Tuple[np.ndarray, np.ndarray]:
+    """THE LEVEL UPDATE of the kernel in numpy, bit for bit: ``level`` [..., K] and ``flow`` [..., P] of one step give
+    (level of the next step [..., K], clamped [..., K] bool).  Per tank the pipes are added up in pipe order (+q where the pipe
+    ends at the tank, -q where it starts there), then level + (inflow * dt) / A, then the clamp; every operation is rounded on
+    its own.  A NaN stays a NaN and is not clamped."""
+    level, flow = np.asarray(level, dtype=np.float64), np.asarray(flow, dtype=np.float64)
+    dt = np.float64(step_seconds)
+    nxt, clamped = np.empty_like(level), np.zeros(level.shape, dtype=bool)
+    a, b = network.pipes[:, 0], network.pipes[:, 1]
+    with np.errstate(all="ignore"):
+        for k, node in enumerate(network.tank_nodes):
+            inflow = np.zeros(level.shape[:-1])
+            for p in range(network.num_pipes):
+                if b[p] == node:
+                    inflow = inflow + flow[..., p]
+                if a[p] == node:
+                    inflow = inflow - flow[..., p]
+            vol = inflow * dt
+            nl = level[..., k] + vol / network.tank_area[k]
+            low, high = nl < network.tank_min_level[k], nl > network.tank_max_level[k]
+            nl = np.where(low, network.tank_min_level[k], np.where(high, network.tank_max_level[k], nl))
+            nxt[..., k], clamped[..., k] = nl, low | high
+    return nxt, clamped
+
+
+def _series_inputs(network, demand, multipliers, pattern_of_node):
+    demand = np.asarray(demand, dtype=np.float64)
+    S, N = demand.shape[0], network.num_nodes
+    mult = np.asarray(multipliers, dtype=np.float64)
+    if mult.ndim == 2:
+        mult = np.broadcast_to(mult, (S,) + mult.shape)
+    if mult.ndim != 3 or mult.shape[0] != S:
+        raise ValueError("multipliers must be [M, T] or [S, M, T]")
+    pattern = np.zeros(N, dtype=np.int64) if pattern_of_node is None else np.asarray(pattern_of_node, dtype=np.int64)
+    if pattern.shape != (N,) or pattern.min() < 0 or pattern.max() >= mult.shape[1]:
+        raise ValueError("pattern_of_node must be [N] with values in [0, M)")
+    return demand, mult, pattern
+
+
+def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multipliers, step_seconds: float, initial_level=None,
+                        pattern_of_node=None, fixed_head=None, solver: str = "dense", warm_start: bool = True,
+                        accuracy: float = ACCURACY, max_iter: int = MAX_ITER) -> HydraulicSeriesReference:
+    """``gatres_hydraulic_series`` in numpy fp64, series by series and step by step, on the Newton loop of ``solve_ref``: the
+    rounded product demand * multiplier, the tank heads elevation + level, the warm or cold start, ``level_update_ref`` and
+    the kernel's failure rules.  head [S, T, N], flow [S, T, P], level [S, T + 1, K], the rest [S, T]."""
+    newton = _NewtonRef(network, solver, accuracy, max_iter)
+    demand, mult, pattern = _series_inputs(network, demand, multipliers, pattern_of_node)
+    roughness = np.asarray(roughness, dtype=np.float64)
+    S, N, P, K, T = demand.shape[0], network.num_nodes, network.num_pipes, network.num_tanks, mult.shape[2]
+    fh = _fixed_heads(network, fixed_head, S)
+    fixed, tanks = network.fixed, network.tank_nodes
+    if initial_level is None:
+        level0 = fh[:, tanks] - network.elevation[tanks][None, :]
+    else:
+        level0 = np.broadcast_to(np.asarray(initial_level, dtype=np.float64), (S, K))
+    head, flow, level = np.full((S, T, N), np.nan), np.full((S, T, P), np.nan), np.full((S, T + 1, K), np.nan)
+    iterations = np.zeros((S, T), dtype=np.int32)
+    converged, limited = np.zeros((S, T), dtype=bool), np.zeros((S, T), dtype=bool)
+    failed = np.ones((S, T), dtype=bool)
+    final_dq = np.full((S, T), np.nan)
+    level[:, 0] = level0
+    for s in range(S):
+        c = roughness[s]
+        with np.errstate(all="ignore"):
+            r = _resistance(network, c)
+        hf = np.where(fixed, fh[s], 0.0)
+        if not newton.inputs_ok(np.zeros(N), hf, c, r):
+            continue
+        q, lev = network.q_start, level0[s].copy()
+        for t in range(T):
+            m = mult[s, :, t]
+            with np.errstate(all="ignore"):
+                d = np.where(fixed, 0.0, demand[s] * m[pattern])
+                hf[tanks] = network.elevation[tanks] + lev
+            if not (np.isfinite(m).all() and (m >= 0).all() and np.isfinite(d).all() and np.isfinite(hf[tanks]).all()):
+                break
+            H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run(d, hf, r, q if warm_start else network.q_start)
+            if not ok:
+                break
+            q = q_new
+            failed[s, t] = False
+            head[s, t], flow[s, t], final_dq[s, t] = H, q, rel
+            lev, clamped = level_update_ref(network, lev, q, step_seconds)
+            level[s, t + 1], limited[s, t] = lev, clamped.any()
+        converged[s] &= ~failed[s]
+    return HydraulicSeriesReference(head, flow, level, iterations, converged, failed, limited, final_dq)
+
+
+def series_valid_ref(network: HydraulicNetwork, pressure, status, pressure_range, allow_limited: bool = False) -> np.ndarray:
+    """``gatres_hydraulic_series_valid`` in numpy: uint8 [S] from pressure [S, T, N] fp32 and status [S, T, 4]."""
+    pressure, status = np.asarray(pressure), np.asarray(status)
+    p64 = pressure.astype(np.float64)[:, :, ~network.fixed]
+    inside = ((p64 >= pressure_range[0]) & (p64 <= pressure_range[1])).all(axis=(1, 2))
+    ok = (status[:, :, 1] != 0).all(axis=1) & (status[:, :, 2] == 0).all(axis=1) & inside
+    if not allow_limited:
+        ok &= (status[:, :, 3] == 0).all(axis=1)
+    return ok.astype(np.uint8)
+
+
+def series_report(status, valid, allow_limited: bool = False) -> Dict[str, float]:
+    """The report of ``generate_series_store`` from the read-back tables: status [S, T, 4] and valid [S].  Counts are per
+    series; a dropped series is counted once, by the first cause in the order failed, not_converged, limited, out_of_range, so
+    drawn = kept + failed + not_converged + limited + out_of_range."""
+    status, valid = np.asarray(status), np.asarray(valid) != 0
+    S, T = status.shape[0], status.shape[1]
+    failed = (status[:, :, 2] != 0).any(axis=1)
+    not_conv = ~failed & (status[:, :, 1] == 0).any(axis=1)
+    limited = ~failed & ~not_conv & (status[:, :, 3] != 0).any(axis=1) & (not allow_limited)
+    out = ~failed & ~not_conv & ~limited & ~valid
+    alive = status[:, :, 2] == 0
+    first = alive[:, 0]
+    return {"drawn": int(S), "kept": int((valid & ~failed & ~not_conv & ~limited).sum()), "failed": int(failed.sum()),
+            "not_converged": int(not_conv.sum()), "limited": int(limited.sum()), "out_of_range": int(out.sum()),
+            "max_iterations": int(status[:, :, 0][alive].max()) if alive.any() else 0,
+            "mean_iterations": float(status[:, :, 0][alive].mean()) if alive.any() else 0.0,
+            "mean_iterations_first_step": float(status[first, 0, 0].mean()) if first.any() else 0.0,
+            "series_length": int(T)}
+
+
+def series_volume_balance(network: HydraulicNetwork, result, demand, multipliers, step_seconds: float,
+                          pattern_of_node=None) -> np.ndarray:
+    """THE INVARIANT of a series, per series and step, in m3 [S, T]: the change of the stored volume sum_k A_k level_k across the
+    step minus dt times the net inflow to the tanks, the latter taken from the OTHER side of the network -- the net outflow of
+    the reservoirs (from ``result.flow``) minus the step's total demand (from ``demand`` and ``multipliers``).  It is zero up
+    to the mass residual of the step's solution, except across a step whose level was clamped.  ``result`` has ``flow``
+    [S, T, P] and ``level`` [S, T + 1, K] (a ``HydraulicSeriesReference``, or a device result brought to numpy)."""
+    demand, mult, pattern = _series_inputs(network, demand, multipliers, pattern_of_node)
+    flow, level = np.asarray(result.flow, dtype=np.float64), np.asarray(result.level, dtype=np.float64)
+    a, b = network.pipes[:, 0], network.pipes[:, 1]
+    tank = np.zeros(network.num_nodes, dtype=bool)
+    tank[network.tank_nodes] = True
+    reservoir = network.fixed & ~tank
+    out_of_reservoirs = flow[:, :, reservoir[a]].sum(axis=2) - flow[:, :, reservoir[b]].sum(axis=2)
+    per_node = demand[:, None, :] * np.swapaxes(mult, 1, 2)[:, :, pattern]              # [S, T, N]
+    total_demand = per_node[:, :, ~network.fixed].sum(axis=2)
+    stored = (level * network.tank_area[None, None, :]).sum(axis=2)                     # [S, T + 1]
+    return (stored[:, 1:] - stored[:, :-1]) - float(step_seconds) * (out_of_reservoirs - total_demand)
 
 
 def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness, fixed_head=None) -> Tuple[np.ndarray, np.ndarray]:

@@ -66,13 +66,20 @@ def make_wdn_topology(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_PIPES
 
 
 def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_PIPES, num_reservoirs: int = 1, seed: int = 0,
-                           length_range=None, diameter_range=None, elevation_range=None, head_range=None, device=None):
+                           length_range=None, diameter_range=None, elevation_range=None, head_range=None, device=None,
+                           num_tanks: int = 0):
     """A ``hydraulics.HydraulicNetwork`` on ``make_wdn_topology(num_nodes, num_pipes, seed)``: ``num_reservoirs`` of the nodes
     are fixed-head nodes, and lengths, diameters, elevations and reservoir heads are seeded uniform numpy draws from the ranges
-    of the reference's scenario generator for C-Town (``hydraulics.LENGTH_RANGE`` and so on) unless given."""
+    of the reference's scenario generator for C-Town (``hydraulics.LENGTH_RANGE`` and so on) unless given.  The last
+    ``num_tanks`` of the fixed-head nodes are tanks: a diameter from ``hydraulics.TANK_DIAMETER_RANGE`` and a starting level from
+    ``hydraulics.TANK_LEVEL_RANGE`` each, drawn AFTER everything else (``num_tanks=0`` returns what it always did); a tank's
+    elevation is set to its head minus that level, so the network's ``fixed_head`` is the tank's starting head (a drawn elevation
+    and a drawn head would put the level anywhere).  Level limits: the constructor's default, (0, +inf)."""
     from . import hydraulics as H
     if not 1 <= num_reservoirs < num_nodes:
         raise ValueError("num_reservoirs must lie in [1, num_nodes)")
+    if not 0 <= num_tanks <= num_reservoirs:
+        raise ValueError("num_tanks must lie in [0, num_reservoirs]: the tanks are the last of the fixed-head nodes")
     ei = make_wdn_topology(num_nodes, num_pipes, seed=seed)
     rng = np.random.RandomState(seed + 7919)
     fixed_nodes = np.sort(rng.choice(num_nodes, num_reservoirs, replace=False))
@@ -81,7 +88,28 @@ def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_
     diameter = draw(diameter_range or H.DIAMETER_RANGE, num_pipes)
     elevation = draw(elevation_range or H.ELEVATION_RANGE, num_nodes)
     head = draw(head_range or H.HEAD_RANGE, num_reservoirs)
-    return H.HydraulicNetwork(ei, length, diameter, elevation, fixed_nodes, head, device=device)
+    if num_tanks == 0:
+        return H.HydraulicNetwork(ei, length, diameter, elevation, fixed_nodes, head, device=device)
+    tanks = fixed_nodes[num_reservoirs - num_tanks:]
+    tank_diameter = draw(H.TANK_DIAMETER_RANGE, num_tanks)
+    level = draw(H.TANK_LEVEL_RANGE, num_tanks)
+    elevation[tanks] = head[num_reservoirs - num_tanks:] - level
+    return H.HydraulicNetwork(ei, length, diameter, elevation, fixed_nodes, head, device=device, tank_nodes=tanks,
+                              tank_diameter=tank_diameter)
+
+
+def make_demand_patterns(num_patterns: int, steps: int, step_seconds: float, seed: int) -> np.ndarray:
+    """Demand multipliers fp64 [num_patterns, steps]: seeded, smooth (a constant plus the first three harmonics of a day),
+    strictly positive, with a period of 24 h in time and a mean of 1 over the ``steps`` given.  Host numpy."""
+    if num_patterns < 1 or steps < 1 or not step_seconds > 0:
+        raise ValueError("num_patterns, steps and step_seconds must be positive")
+    rng = np.random.RandomState(seed + 104729)
+    day = 2.0 * np.pi * (np.arange(steps, dtype=np.float64) * float(step_seconds)) / 86400.0
+    amplitude = rng.uniform(0.0, 1.0, (num_patterns, 3)) * np.array([0.35, 0.2, 0.1])       # (their sum stays below 0.65 < 1)
+    phase = rng.uniform(0.0, 2.0 * np.pi, (num_patterns, 3))
+    wave = sum(amplitude[:, k, None] * np.cos((k + 1) * day[None, :] + phase[:, k, None]) for k in range(3))
+    mult = 1.0 + wave
+    return mult / mult.mean(axis=1, keepdims=True)
 
 
 def collate_edge_index(edge_index: torch.Tensor, num_nodes: int, batch_size: int) -> torch.Tensor:

@@ -1354,6 +1354,65 @@ int gatres_hydraulic_solve(const int32_t* pipe_a, const int32_t* pipe_b, const d
 int gatres_hydraulic_valid(const float* pressure, const int32_t* status, const uint8_t* fixed, int64_t num_scenarios,
                            int32_t num_nodes, double p_lo, double p_hi, uint8_t* valid, void* stream);
 
+/* THE SERIES: extended-period simulation (symbols only: the ABI stays; k_hydraulics.hip, hydraulics.py).  A series is T steps of
+ * dt seconds of one scenario.  TANKS are K of the fixed-head nodes: tank k sits at node tank_node[k], its bottom at that node's
+ * elevation, with the area A_k = pi D_k^2 / 4 (tank_area, formed by the caller) and the level limits tank_min_level[k] <=
+ * tank_max_level[k] (the maximum may be +infinity: a tank that is never full).  During step t its head is
+ * elevation + level[t][k], one fp64 add.  RESERVOIRS are the other fixed-head nodes; they keep fixed_head for the whole series.
+ * DEMAND: junction n of series s draws demand[s][n] * mult[pattern_of_node[n]][t] at step t, one rounded fp64 product that is
+ * stored before the assembly reads it.  mult is double[M][T] for every series (mult_stride 0) or double[S][M][T] (mult_stride
+ * M * T); pattern_of_node int32[N] holds values in [0, M) (read at every node).  A STEP is the steady solve stated above: the
+ * same law, assembly, factorisation, flow update and stop rule, one function in k_hydraulics_dev.h for both kernels.  Step 0
+ * starts from q_start; step t > 0 starts from the final flows of step t - 1 where warm_start != 0 (EPANET's way), else from
+ * q_start again.  LEVEL UPDATE, explicit Euler as in EPANET, after step t, one thread per tank:
+ *   inflow_k = 0;  for p = 0 .. P - 1:  inflow_k += q_p where pipe_b[p] is the tank,  inflow_k -= q_p where pipe_a[p] is the tank;
+ *   v = inflow_k * dt;   l = level[t][k] + v / A_k;   level[t + 1][k] = min_level[k] if l < min_level[k], max_level[k] if
+ *   l > max_level[k], else l
+ * with every operation rounded to fp64 on its own.  level[0] is initial_level as given.
+ * WHAT DOES NOT HOLD: EPANET shortens a time step at the moment a tank becomes full or empty and closes the pipes of such a
+ * tank; this model clamps the level and does neither.  A step after which a level was clamped gets status[s][t][3] = 1, and
+ * volume is not conserved across it.  Pumps, valves, minor losses, controls and rules are not modelled.  The limit on flows that
+ * should be zero carries over: a step with a zero multiplier does not meet the stop rule.
+ * FAILURE: a step fails on a multiplier of the step (any of the M) that is negative or not finite, a product demand * mult or
+ * a tank head that is not finite, a pivot that is not positive and finite or a non-finite sum of the stop rule; a series fails
+ * from step 0 on a roughness that is not positive and finite or a non-finite fixed_head at a fixed node (tanks included: the
+ * value is read and then replaced).  Once a step has failed, it and every later step of the series are failed: pressure, head,
+ * flow, final_dq of those steps and level[t + 1] are NaN, status {iterations so far, 0, 1, 0}; the earlier steps keep their
+ * outputs.  A step that does not converge is no failure: the series goes on from its flows and heads with converged = 0.  Static
+ * arrays that are not what is stated (those of gatres_hydraulic_solve; a tank node outside [0, N), not fixed or listed twice; an
+ * area that is not positive and finite; min > max or a NaN limit; a pattern index outside [0, M)) fail every series of the launch.
+ *
+ * gatres_hydraulic_series: one workgroup of 256 threads per series on a grid capped at GATRES_HYD_GRID_CAP, the series beyond
+ * it taken by a loop; the band stays in LDS for the whole series and nothing goes to the host between steps.  LDS need:
+ *   the bytes of gatres_hydraulic_solve  +  8 N (the step's demand)  +  40 K (levels, area, two limits, node and row per tank)
+ * refused above GATRES_HYD_LDS_BUDGET (hydraulics.series_lds_bytes restates it).  Inputs as for gatres_hydraulic_solve, and
+ * tank_node int32[K], tank_area, tank_min_level, tank_max_level double[K], initial_level double[S][K].  OUTPUTS:
+ * pressure float[S][T][N]; head double[S][T][N] or NULL; flow double[S][T][P] or NULL; level double[S][T + 1][K];
+ * status int32[S][T][GATRES_HYD_STATUS] = {iterations, converged, failed, a level was clamped}; final_dq double[S][T].  No
+ * atomics; every sum runs in a fixed order; a series' bits depend on nothing but its own inputs.  K == 0 is legal (patterns
+ * only): the tank arrays, initial_level and level may then be NULL.
+ * GATRES_E_BADARG before any launch: a NULL pointer other than head or flow (and, with K == 0, the tank arrays); S, T, N, P or
+ * M < 1; N < 2; K < 0; W outside [1, N - 1]; dt, accuracy not positive and finite; max_iter < 1; mult_stride neither 0 nor
+ * M * T; fixed_head_stride neither 0 nor N; byte counts that do not fit in 64 bits; the LDS need above; an output overlapping
+ * an input or another output. */
+int gatres_hydraulic_series(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                            const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                            int32_t half_bandwidth, const int32_t* tank_node, const double* tank_area,
+                            const double* tank_min_level, const double* tank_max_level, int32_t num_tanks,
+                            const int32_t* pattern_of_node, const double* mult, int64_t mult_stride, int32_t num_patterns,
+                            const double* demand, const double* roughness, const double* fixed_head, int64_t fixed_head_stride,
+                            const double* initial_level, int64_t num_series, int32_t num_steps, int32_t num_nodes,
+                            int32_t num_pipes, double dt, int32_t warm_start, double accuracy, int32_t max_iter, float* pressure,
+                            double* head, double* flow, double* level, int32_t* status, double* final_dq, void* stream);
+
+/* valid[s] (device uint8) = 1 iff every step of series s converged and none failed, no step has status[s][t][3] != 0 (unless
+ * allow_limited != 0) and pressure[s][t][i] lies in [p_lo, p_hi] (compared in fp64; a NaN lies outside) at every junction i of
+ * every step; else 0.  One wave per series on a capped grid.  GATRES_E_BADARG before any launch: a NULL pointer; num_series,
+ * num_steps or num_nodes < 1; byte counts that do not fit; p_lo or p_hi NaN, or p_lo > p_hi; valid overlapping an input. */
+int gatres_hydraulic_series_valid(const float* pressure, const int32_t* status, const uint8_t* fixed, int64_t num_series,
+                                  int32_t num_steps, int32_t num_nodes, double p_lo, double p_hi, int32_t allow_limited,
+                                  uint8_t* valid, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
