@@ -23,6 +23,20 @@ static void counting_sort(const std::vector<int32_t>& key, int64_t N, int32_t* p
   for (int64_t e = 0; e < n; ++e) perm[cur[key[e]]++] = (int32_t)e;
 }
 
+// a segment table over [0, N): starts at 0, never decreases, ends at N
+static bool seg_table_ok(const int32_t* seg_ptr, int32_t num_segments, int64_t N) {
+  if (seg_ptr[0] != 0) return false;
+  for (int32_t s = 0; s < num_segments; ++s)
+    if (seg_ptr[s + 1] < seg_ptr[s]) return false;
+  return seg_ptr[num_segments] == N;
+}
+
+static bool endpoints_ok(const int64_t* ei, int64_t E, int64_t N) {
+  for (int64_t e = 0; e < 2 * E; ++e)
+    if (ei[e] < 0 || ei[e] >= N) return false;
+  return true;
+}
+
 }  // namespace
 
 extern "C" int gatres_graph_count_host(const int64_t* ei, int64_t E, int64_t N, int64_t* num_edges_gat_out) {
@@ -163,6 +177,10 @@ extern "C" int gatres_graph_windows_host(const int64_t* ei, int64_t E, int64_t N
                                          int32_t num_segments, int32_t* out9) {
   // (out9 holds 28 entries: three window figures for each M = 2 .. 8, then the seven halo sizes)
   if ((!ei && E > 0) || !seg_ptr || !out9 || num_segments <= 0 || N <= 0 || E < 0) return GATRES_E_BADARG;
+  if (N > INT32_MAX) return GATRES_E_UNSUPPORTED;
+  // everything below indexes with the segment table and with the endpoints: both are checked first
+  if (!seg_table_ok(seg_ptr, num_segments, N)) return GATRES_E_BADARG;
+  if (!endpoints_ok(ei, E, N)) return GATRES_E_GRAPH;
   std::vector<int32_t> seg_of(N);
   for (int32_t s = 0; s < num_segments; ++s)
     for (int32_t i = seg_ptr[s]; i < seg_ptr[s + 1]; ++i) seg_of[i] = s;
@@ -247,8 +265,43 @@ extern "C" int gatres_graph_part_tables_host(const int32_t* rowptr, const int32_
                                              const int32_t* seg_ptr, int32_t num_segments, int32_t M, int32_t* out,
                                              int64_t stride_words, int64_t* stride_words_out) {
   if (!rowptr || !col || !t_rowptr || !t_eid || !t_dst || !m_rowptr || !m_col || !mt_rowptr || !mt_dst || !seg_ptr ||
-      num_segments <= 0 || M < 2 || M > 8 || !stride_words_out)
+      num_segments <= 0 || M < 2 || M > 8 || !stride_words_out || (out && stride_words < 0))
     return GATRES_E_BADARG;
+  // What can be checked without the arrays' lengths, before anything is written: a segment table and row pointers that
+  // never decrease (GATRES_E_BADARG), segments within the 16-bit tables (GATRES_E_UNSUPPORTED), and every neighbour and
+  // saved-edge id inside its own segment (GATRES_E_GRAPH) -- the kernel indexes its LDS window with them.
+  if (seg_ptr[0] < 0) return GATRES_E_BADARG;
+  for (int32_t s = 0; s < num_segments; ++s)
+    if (seg_ptr[s + 1] < seg_ptr[s]) return GATRES_E_BADARG;
+  for (int32_t s = 0; s < num_segments; ++s) {
+    const int32_t n0 = seg_ptr[s], n1 = seg_ptr[s + 1];
+    for (const int32_t* ptr : {rowptr, t_rowptr, m_rowptr, mt_rowptr}) {
+      if (ptr[n0] < 0) return GATRES_E_BADARG;
+      for (int32_t i = n0; i < n1; ++i)
+        if (ptr[i + 1] < ptr[i]) return GATRES_E_BADARG;
+    }
+  }
+  for (int32_t s = 0; s < num_segments; ++s) {
+    const int32_t n0 = seg_ptr[s], n1 = seg_ptr[s + 1];
+    if (rowptr[n1] - rowptr[n0] != t_rowptr[n1] - t_rowptr[n0] || m_rowptr[n1] - m_rowptr[n0] != mt_rowptr[n1] - mt_rowptr[n0])
+      return GATRES_E_GRAPH;                         // (an edge leaves the segment: its CSR and the transpose disagree)
+  }
+  for (int32_t s = 0; s < num_segments; ++s) {
+    const int32_t n0 = seg_ptr[s], n1 = seg_ptr[s + 1];
+    if (n1 - n0 > 65535 || rowptr[n1] - rowptr[n0] > 65535 || m_rowptr[n1] - m_rowptr[n0] > 65535) return GATRES_E_UNSUPPORTED;
+  }
+  for (int32_t s = 0; s < num_segments; ++s) {
+    const int32_t n0 = seg_ptr[s], n1 = seg_ptr[s + 1];
+    auto inside = [&](const int32_t* ptr, const int32_t* idx) {
+      for (int32_t e = ptr[n0]; e < ptr[n1]; ++e)
+        if (idx[e] < n0 || idx[e] >= n1) return false;
+      return true;
+    };
+    if (!inside(rowptr, col) || !inside(t_rowptr, t_dst) || !inside(m_rowptr, m_col) || !inside(mt_rowptr, mt_dst))
+      return GATRES_E_GRAPH;
+    for (int32_t e = t_rowptr[n0]; e < t_rowptr[n1]; ++e)
+      if (t_eid[e] < rowptr[n0] || t_eid[e] >= rowptr[n1]) return GATRES_E_GRAPH;
+  }
   int64_t need = 0;
   std::vector<uint16_t> img;
   std::vector<int32_t> words;
@@ -256,7 +309,6 @@ extern "C" int gatres_graph_part_tables_host(const int32_t* rowptr, const int32_
     PartGeom g;
     g.n0 = seg_ptr[s]; g.n = seg_ptr[s + 1] - g.n0;
     g.e0 = rowptr[g.n0]; g.em0 = m_rowptr[g.n0]; g.t0 = t_rowptr[g.n0]; g.mt0 = mt_rowptr[g.n0];
-    if (g.n > 65535 || rowptr[g.n0 + g.n] - g.e0 > 65535 || m_rowptr[g.n0 + g.n] - g.em0 > 65535) return GATRES_E_UNSUPPORTED;
     const int tiles = (g.n + 15) >> 4;
     for (int p = 0; p < M; ++p) {
       g.lo = 16 * (int)((long long)tiles * p / M);
@@ -387,6 +439,7 @@ extern "C" int gatres_graph_part_tables_host(const int32_t* rowptr, const int32_
         for (int i = 0; i < GATRES_PT_HEADER; ++i) dst[i] = hdr[i];
         for (size_t i = 0; i + 1 < img.size() + 1 && i < img.size(); i += 2)
           dst[GATRES_PT_HEADER + i / 2] = (int32_t)((uint32_t)img[i] | ((uint32_t)img[i + 1] << 16));
+        for (int64_t i = total_words; i < stride_words; ++i) dst[i] = 0;      // every word of the record is defined
       }
     }
   }
@@ -403,6 +456,7 @@ extern "C" int gatres_graph_reorder_host(const int64_t* ei, int64_t E, int64_t N
                                          int32_t num_segments, int32_t* perm) {
   if ((!ei && E > 0) || !seg_ptr || !perm || num_segments <= 0 || N <= 0 || E < 0) return GATRES_E_BADARG;
   if (N > INT32_MAX || 2 * E > INT32_MAX) return GATRES_E_UNSUPPORTED;
+  if (!seg_table_ok(seg_ptr, num_segments, N)) return GATRES_E_BADARG;
   // undirected adjacency (self loops dropped; duplicates are harmless)
   std::vector<int32_t> key(2 * E), val(2 * E);
   int64_t k = 0;

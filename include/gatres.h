@@ -140,7 +140,20 @@ int gatres_graph_flags_host(const int64_t* edge_index_host, int64_t num_edges, i
 /* Part tables (host): see gatres_graph_t.part_tables.  Inputs: the plan's HOST arrays (as gatres_graph_build_host filled
  * them) and its segment table; m = workgroups per segment (2 .. 8, gatres_fused_cus_per_segment).  Call once with
  * out = NULL to learn the record size (*stride_words_out, a multiple of 4), then with an array of
- * num_segments * m * stride words. */
+ * num_segments * m * stride words.
+ * Contract.  The arrays' lengths are not passed, so the caller owes: seg_ptr holds num_segments + 1 entries, every row
+ * pointer array reaches index seg_ptr[num_segments], and the column arrays reach the last row pointer.  Checked before
+ * anything is written, in this order:
+ *   GATRES_E_BADARG       a NULL array, seg_ptr or stride_words_out; num_segments <= 0; m outside 2 .. 8; a negative
+ *                         stride_words with out != NULL; seg_ptr[0] < 0 or a seg_ptr that decreases; a row pointer array
+ *                         that is negative at, or decreases over, a segment's rows;
+ *   GATRES_E_GRAPH        a segment whose CSR and transposed CSR hold different edge counts;
+ *   GATRES_E_UNSUPPORTED  a segment of more than 65535 nodes, GATConv edges or SimpleConv edges (16-bit tables);
+ *   GATRES_E_GRAPH        a col / t_dst / m_col / mt_dst entry outside its row's segment, or a t_eid outside the
+ *                         segment's GATConv edge range.
+ * While filling: a record longer than stride_words returns GATRES_E_BADARG; the records before it have been written,
+ * nothing at or beyond it.  Words of a record beyond its last list are written as zeros.
+ * *stride_words_out is written on success only.  Empty segments and parts without rows are records like any other. */
 int gatres_graph_part_tables_host(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid,
                                   const int32_t* t_dst, const int32_t* m_rowptr, const int32_t* m_col,
                                   const int32_t* mt_rowptr, const int32_t* mt_dst, const int32_t* seg_ptr,
@@ -156,13 +169,22 @@ int gatres_graph_segments_host(const int64_t* edge_index_host, int64_t num_edges
 
 /* Row windows of split segments (see gatres_graph_t.window): for M = 2 .. 8 workgroups per segment, the largest
  * contiguous row range a part needs (own rows + the rows adjacent to them), in rows / GATConv edges / SimpleConv edges,
- * followed by gatres_graph_t.halo: out28 = {rows2, gat2, mean2, ..., rows8, gat8, mean8, halo2, ..., halo8}. */
+ * followed by gatres_graph_t.halo: out28 = {rows2, gat2, mean2, ..., rows8, gat8, mean8, halo2, ..., halo8}.
+ * These figures size the LDS that gatres_graph_part_tables_host's records fill: for every m, no record's window has more
+ * rows, GATConv edges or SimpleConv edges than window[m - 2], and no hand-off list more entries than halo[m - 2].
+ * Contract, checked in this order before any index is formed: GATRES_E_BADARG for a NULL edge_index (with
+ * num_edges > 0), seg_ptr or out28, num_edges < 0, num_nodes <= 0 or num_segments <= 0; GATRES_E_UNSUPPORTED for
+ * num_nodes > INT32_MAX; GATRES_E_BADARG for a segment table that does not start at 0, decreases, or does not end at
+ * num_nodes; GATRES_E_GRAPH for an endpoint outside [0, num_nodes) and for an edge that joins two segments.  out28 is
+ * written on success only. */
 int gatres_graph_windows_host(const int64_t* edge_index, int64_t num_edges, int64_t num_nodes, const int32_t* seg_ptr,
                               int32_t num_segments, int32_t* out28);
 
 /* Bandwidth-reducing relabelling (host): reverse Cuthill-McKee inside every segment (nodes never leave their segment, so
  * seg_ptr stays valid).  perm_new2old_host[new] = old, N entries.  The fused kernels' row windows (above) are what it
- * shrinks: real .inp junction orders are not locality-preserving (utils/DataLoader.py:28-37 keeps the file order). */
+ * shrinks: real .inp junction orders are not locality-preserving (utils/DataLoader.py:28-37 keeps the file order).
+ * The segment table is held to the contract of gatres_graph_windows_host (GATRES_E_BADARG); an endpoint out of range or
+ * an edge that leaves its segment is GATRES_E_GRAPH. */
 int gatres_graph_reorder_host(const int64_t* edge_index_host, int64_t num_edges, int64_t num_nodes,
                               const int32_t* seg_ptr_host, int32_t num_segments, int32_t* perm_new2old_host);
 

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from plan_refs import ref_plan          # the numpy restatement of the plan (tests/plan_refs.py)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
@@ -47,26 +49,6 @@ def test_c_abi_exports_every_declared_symbol(pkg, lib):
         assert hasattr(lib, name), f"{name} declared in gatres.h but not exported"
     assert declared == set(pkg._native.SIGNATURES), declared ^ set(pkg._native.SIGNATURES)
     assert lib.gatres_param_count(15, 32) == 65857 and lib.gatres_param_count(25, 128) == 1667585
-
-
-def ref_plan(ei, n):
-    """numpy restatement of the plan: PyG edge order, stable sorts."""
-    src, dst = ei[0].numpy(), ei[1].numpy()
-    keep = src != dst
-    gs = np.concatenate([src[keep], np.arange(n)])
-    gd = np.concatenate([dst[keep], np.arange(n)])
-    order = np.argsort(gd, kind="stable")
-    rowptr = np.concatenate([[0], np.cumsum(np.bincount(gd, minlength=n))])
-    col = gs[order]
-    pos = np.empty_like(order); pos[order] = np.arange(order.size)
-    torder = np.argsort(gs, kind="stable")
-    t_rowptr = np.concatenate([[0], np.cumsum(np.bincount(gs, minlength=n))])
-    morder = np.argsort(dst, kind="stable")
-    m_rowptr = np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=n))])
-    mtorder = np.argsort(src, kind="stable")
-    return dict(rowptr=rowptr, col=col, t_rowptr=t_rowptr, t_eid=pos[torder], t_dst=gd[torder], m_rowptr=m_rowptr,
-                m_col=src[morder], mt_rowptr=np.concatenate([[0], np.cumsum(np.bincount(src, minlength=n))]),
-                mt_dst=dst[mtorder])
 
 
 def test_graph_plan_matches_numpy_restatement(pkg):
