@@ -29,6 +29,7 @@ struct gatres_knobs_t {
   int fused_no_halo;          // GATRES_FUSED_NO_HALO: whole-segment kernel, bulk pulls (what an overflowing halo list gets)
   int fused_no_rounds;        // GATRES_FUSED_NO_ROUNDS: 49 .. 96 segments resident at fewer parts instead of two rounds
   int agg_lane_features;      // GATRES_AGG_LANE_FEATURES = 4 | 8 (0: automatic -- 8 for rows of 64 features and more)
+  int agg_wide_offsets;       // GATRES_AGG_WIDE_OFFSETS: the 64-bit-offset instances of the sparse kernels (what tables of 4 GiB get)
   int lin_bwd_wave;           // GATRES_LIN_BWD_WAVE: lin0 / lin1 backward, one wave per slab (what odd widths get)
   int no_proj_lds;            // GATRES_NO_PROJ_LDS: fp32 projections without the LDS copy of W (what small batches get)
   int dw_1d;                  // GATRES_DW_1D: bf16 weight gradients, one matrix per workgroup (what narrow models get)
@@ -43,7 +44,6 @@ struct gatres_knobs_t {
   int window_ph_mask;         // GATRES_WINDOW_PH_MASK (default all ones): which compile-time facts a launch may use (k_window.hip)
   // DIAGNOSTIC build only (fixed at the defaults in the product build): measured-and-lost alternatives, tuning sweeps and the
   // switches that give WRONG results
-  int agg_wide_offsets;       // GATRES_AGG_WIDE_OFFSETS
   int fused_threads;          // GATRES_FUSED_THREADS = 512 (default 1024)
   int fused_no_window;        // GATRES_FUSED_NO_WINDOW
   int fused_nocache;          // GATRES_FUSED_NOCACHE

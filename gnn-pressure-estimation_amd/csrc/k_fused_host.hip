@@ -448,7 +448,7 @@ static bool window_kernel_fits(const Layout& L, const gatres_graph_t* g, int M, 
 // conv1-width sparse stage and a fifth MFMA tile -- 384-node snapshots run 22 us faster).  Otherwise the
 // whole-segment-table kernel at min(B, 4).  The choice depends on the plan only, never on the phases of a launch: the
 // per-part hand-off epochs persist in scratch.  GATRES_FUSED_SPLIT=1..8 overrides.
-static int fused_split(const Layout& L, const gatres_graph_t* g) {
+static int fused_split(const Layout& L, const gatres_graph_t* g, int cus) {
   const int tiles = (g->max_segment_nodes + 15) / 16;
   const int padded = ((g->num_segments + 7) / 8) * 8;
   // Rounds: 49 .. 96 segments fit the chip only at 4 .. 2 parts each -- whole-segment tables, where a snapshot costs MORE
@@ -459,12 +459,12 @@ static int fused_split(const Layout& L, const gatres_graph_t* g) {
   // (bs 72 .. 96: 1.24 .. 1.29 vs 1.14 .. 1.27).  GATRES_FUSED_NO_ROUNDS=1: the resident choice.
   if (const int rp = rounds_parts_for(g->num_segments)) {
     const int per = ((padded / 2 + 7) / 8) * 8;
-    if (L.split_max == rp && tiles >= rp && L.nb > 0 && per * rp <= device_cus() && !gatres_knobs()->fused_split &&
+    if (L.split_max == rp && tiles >= rp && L.nb > 0 && per * rp <= cus && !gatres_knobs()->fused_split &&
         !gatres_knobs()->fused_no_rounds && window_kernel_fits(L, g, rp))
       return rp;
   }
   int B = L.split_max;
-  while (B > 1 && (B > tiles || L.nb == 0 || padded * B > device_cus())) --B;   // (a partitioned / smaller device)
+  while (B > 1 && (B > tiles || L.nb == 0 || padded * B > cus)) --B;   // (a partitioned / smaller device)
   if (const int v = gatres_knobs()->fused_split) {
     if (v >= 1 && v <= B) return v;
   }
@@ -473,30 +473,57 @@ static int fused_split(const Layout& L, const gatres_graph_t* g) {
   while (m * 2 <= B && m < 4) m *= 2;
   return m;
 }
+static int fused_split(const Layout& L, const gatres_graph_t* g) { return fused_split(L, g, device_cus()); }
 
-static bool use_window_kernel(const FusedArgs& a, const gatres_graph_t* g) {
-  return a.saved && window_kernel_fits(a.L, g, a.M);        // (it writes the saved tables: training launches only)
-}
+// Workgroups of one launch that carries seg_cnt segments at M parts each: ids of one segment are 8 apart
+static unsigned fused_grid(int seg_cnt, int M) { return (unsigned)(((seg_cnt + 7) / 8) * 8 * M); }
 
-static int launch_fused(int nc, int threads, const FusedArgs& a0, const gatres_graph_t* g, hipStream_t st) {
-  const bool window = threads == 1024 && nc <= 32 && use_window_kernel(a0, g);
-  const bool cache = !gatres_knobs()->fused_nocache &&
-                     cache_fits(nc, threads, g->max_segment_nodes, g->max_segment_edges_gat, g->max_segment_edges_mean);
+// Everything a fused launch decides from the plan, the model and the phases, in ONE place: gatres_fused_run launches what
+// this says and gatres_fused_plan reports it (include/gatres.h: GATRES_FUSED_PLAN_*), so the two cannot drift apart.
+// has_saved: the launch is given a `saved` buffer (the window kernel writes the saved tables); cus: the CUs every
+// workgroup of a split launch must be resident on; probed: the device's dispatch was probed (gatres_probe_xcd_dispatch).
+struct FusedPlan {
+  int M, window, cache, keep, facts, launches, per_launch, grid0, threads, part_rows, cus;
+};
+static int fused_decide(const gatres_model_t* m, const gatres_graph_t* g, const Layout& L, int32_t phases, bool has_saved,
+                        int cus, bool probed, FusedPlan* p) {
+  const int nc = m->nc, threads = threads_for(nc);
+  p->cus = cus;
+  p->threads = threads;
+  p->M = fused_split(L, g, cus);
+  p->window = threads == 1024 && nc <= 32 && has_saved && window_kernel_fits(L, g, p->M) ? 1 : 0;
+  p->cache = !gatres_knobs()->fused_nocache &&
+             cache_fits(nc, threads, g->max_segment_nodes, g->max_segment_edges_gat, g->max_segment_edges_mean) ? 1 : 0;
+  const int tiles = (g->max_segment_nodes + 15) / 16;
+  p->part_rows = p->M > 0 ? 16 * ((tiles + p->M - 1) / p->M) : INT32_MAX;
+  p->facts = ((g->flags & GATRES_GRAPH_DEG_LE6) ? 0x400 : 0) | (p->part_rows <= 64 ? 0x1000 : 0) |
+             (((m->flags & GATRES_MODEL_INFERENCE) && phases == GATRES_PHASE_FORWARD) ? 0x2000 : 0) |
+             ((probed && !gatres_knobs()->window_sync_start) ? 0x4000 : 0);
+  p->keep = (phases & GATRES_PHASE_FORWARD) && (phases & GATRES_PHASE_BACKWARD) && !gatres_knobs()->fused_no_keep &&
+            window_kernel_fits(L, g, p->M, true) ? 1 : 0;
   // every workgroup of a split launch must be resident at once: more segments than that go round by round
   int per_round = g->num_segments;
-  if (a0.M > 1 && ((g->num_segments + 7) / 8) * 8 * a0.M > device_cus()) {
-    const int padded = ((g->num_segments + 7) / 8) * 8, fit = (device_cus() / a0.M) & ~7;
+  if (p->M > 1 && ((g->num_segments + 7) / 8) * 8 * p->M > cus) {
+    const int padded = ((g->num_segments + 7) / 8) * 8, fit = (cus / p->M) & ~7;
     const int rounds = fit > 0 ? (padded + fit - 1) / fit : 0;
     per_round = rounds > 0 ? (((padded + rounds - 1) / rounds + 7) / 8) * 8 : 0;        // (equal rounds: 72 segments = 40 + 32)
   }
+  p->per_launch = per_round;
+  p->launches = per_round > 0 ? (g->num_segments + per_round - 1) / per_round : 0;
+  p->grid0 = per_round > 0 ? (int)fused_grid(g->num_segments < per_round ? g->num_segments : per_round, p->M) : 0;
+  return per_round > 0 ? 0 : GATRES_E_UNSUPPORTED;
+}
+
+static int launch_fused(int nc, const FusedPlan& p, const FusedArgs& a0, const gatres_graph_t* g, hipStream_t st) {
+  const int per_round = p.per_launch;
   if (per_round <= 0) return GATRES_E_UNSUPPORTED;
   FusedArgs a = a0;
   for (int s0 = 0; s0 < g->num_segments; s0 += per_round) {
     a.seg0 = s0;
     a.seg_cnt = g->num_segments - s0 < per_round ? g->num_segments - s0 : per_round;
-    const unsigned grid = (unsigned)(((a.seg_cnt + 7) / 8) * 8 * a.M);
-    const int rc = window ? gatres_fused_launch_window(&a, nc, grid, st)
-                          : gatres_fused_launch_whole(&a, nc, threads, cache ? 1 : 0, grid, st);
+    const unsigned grid = fused_grid(a.seg_cnt, a.M);
+    const int rc = p.window ? gatres_fused_launch_window(&a, nc, grid, st)
+                            : gatres_fused_launch_whole(&a, nc, p.threads, p.cache, grid, st);
     if (rc != 0) return rc;
   }
   return 0;
@@ -544,6 +571,30 @@ extern "C" int gatres_fused_window_kernel(const gatres_model_t* m, const gatres_
   return window_kernel_fits(L, g, fused_split(L, g)) ? 1 : 0;
 }
 
+static std::atomic<int> g_xcd_rr[64];          // per device: 0 = not probed, 1 = no, 2 = workgroups 8 ids apart share an XCD
+static int xcd_rr_cached() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  return g_xcd_rr[dev].load(std::memory_order_acquire) == 2 ? 1 : 0;
+}
+
+extern "C" int gatres_fused_plan(const gatres_model_t* m, const gatres_graph_t* g, int32_t phases, int32_t num_cus,
+                                 int32_t* out) {
+  if (!m || !g || !out) return GATRES_E_BADARG;
+  for (int k = 0; k < GATRES_FUSED_PLAN_WORDS; ++k) out[k] = 0;
+  Layout L;
+  if (!gatres_fused_supported(m, g) || !make_layout_g(m, g, &L)) return GATRES_E_UNSUPPORTED;
+  FusedPlan p;
+  const int rc = fused_decide(m, g, L, phases, true, num_cus > 0 ? num_cus : device_cus(), xcd_rr_cached() != 0, &p);
+  out[GATRES_FUSED_PLAN_PARTS] = p.M;                 out[GATRES_FUSED_PLAN_WINDOW] = p.window;
+  out[GATRES_FUSED_PLAN_CACHED] = p.cache;            out[GATRES_FUSED_PLAN_KEEP] = p.keep;
+  out[GATRES_FUSED_PLAN_FACTS] = p.facts;             out[GATRES_FUSED_PLAN_LAUNCHES] = p.launches;
+  out[GATRES_FUSED_PLAN_PER_LAUNCH] = p.per_launch;   out[GATRES_FUSED_PLAN_GRID] = p.grid0;
+  out[GATRES_FUSED_PLAN_THREADS] = p.threads;         out[GATRES_FUSED_PLAN_PART_ROWS] = p.part_rows;
+  out[GATRES_FUSED_PLAN_CUS] = p.cus;
+  return rc;
+}
+
 // Diagnostic: segment 0 of the next fused launches writes a 100 MHz wall-clock stamp at every stage boundary into
 // stamps[0..capacity) (device memory).  Pass nullptr to switch it off.
 extern "C" int gatres_fused_set_stamps(uint64_t* stamps, int32_t capacity) {
@@ -560,12 +611,6 @@ extern "C" int gatres_fused_prepare_backward(const gatres_model_t* m, const gatr
   return gatres_transpose_conv_weights(params, scratch + L.sc_wt, L.nb, L.nc, stream);
 }
 
-static std::atomic<int> g_xcd_rr[64];          // per device: 0 = not probed, 1 = no, 2 = workgroups 8 ids apart share an XCD
-static int xcd_rr_cached() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  return g_xcd_rr[dev].load(std::memory_order_acquire) == 2 ? 1 : 0;
-}
 extern "C" int gatres_fused_run(const gatres_model_t* m, const gatres_graph_t* g, const float* params,
                                 const float* x, const uint8_t* mask, const float* y, float* out, float* g_out,
                                 float* loss_part, float* g_x, float* saved, float* scratch, int32_t phases,
@@ -590,20 +635,16 @@ extern "C" int gatres_fused_run(const gatres_model_t* m, const gatres_graph_t* g
   a.saved = saved; a.scratch = scratch; a.slabs = scratch + a.L.sc_slabs;
   a.num_segments = g->num_segments;
   a.seg0 = 0; a.seg_cnt = g->num_segments;
-  a.M = fused_split(a.L, g);
+  FusedPlan plan;
+  (void)fused_decide(m, g, a.L, phases, saved != nullptr, device_cus(), xcd_rr_cached() != 0, &plan);      // (launch_fused refuses)
+  a.M = plan.M;
   a.safe_sync = gatres_knobs()->fused_safe_sync;
   // bits 1 / 2 (diagnostic build only, WRONG results): never-wait exchanges; dX epilogues without their global reads
   a.no_halo = gatres_knobs()->fused_no_halo | (gatres_knobs()->xch_nowait ? 2 : 0) | (gatres_knobs()->diag_nomask ? 4 : 0);
   a.sym = (g->flags & GATRES_GRAPH_SYMMETRIC) && !gatres_knobs()->fused_heartbeat ? 1 : 0;
   a.ptab = g->part_tables; a.ptab_m = g->part_tables_m; a.ptab_stride = g->part_tables_stride;
-  {
-    const int tiles = (g->max_segment_nodes + 15) / 16, part_rows = a.M > 0 ? 16 * ((tiles + a.M - 1) / a.M) : INT32_MAX;
-    a.facts = ((g->flags & GATRES_GRAPH_DEG_LE6) ? 0x400 : 0) | (part_rows <= 64 ? 0x1000 : 0) |
-              (((m->flags & GATRES_MODEL_INFERENCE) && phases == GATRES_PHASE_FORWARD) ? 0x2000 : 0) |
-              ((xcd_rr_cached() && !gatres_knobs()->window_sync_start) ? 0x4000 : 0);
-  }
-  a.keep_lds = (phases & GATRES_PHASE_FORWARD) && (phases & GATRES_PHASE_BACKWARD) && !gatres_knobs()->fused_no_keep &&
-           window_kernel_fits(a.L, g, a.M, true) ? 1 : 0;
+  a.facts = plan.facts;
+  a.keep_lds = plan.keep;
   a.flags = reinterpret_cast<unsigned*>(scratch + a.L.sc_flags);
   a.err = reinterpret_cast<int*>(fused_status(scratch, a.L));
   a.part_slabs = scratch + a.L.sc_part_slabs;
@@ -617,7 +658,7 @@ extern "C" int gatres_fused_run(const gatres_model_t* m, const gatres_graph_t* g
                                                                                                         : GATRES_LOSS_MSE;
   hipStream_t st = gatres_stream(stream);
   if (a.M > 1) serialize_split_launch(st);
-  int rc = launch_fused(m->nc, threads_for(m->nc), a, g, st);
+  int rc = launch_fused(m->nc, plan, a, g, st);
   if (rc == 0 && a.M > 1 && !(phases & GATRES_PHASE_BACKWARD)) {      // (a backward launch is followed by gatres_fused_finish)
     hipLaunchKernelGGL(fused_status_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned*>(a.err));
     rc = gatres_launch_status();

@@ -38,13 +38,13 @@ void read_knobs(gatres_knobs_t* k) {
   k->window_ph_mask = env_int("GATRES_WINDOW_PH_MASK", 0xffff);
   k->window_sync_start = env_flag("GATRES_WINDOW_SYNC_START");
   k->fused_no_keep = env_flag("GATRES_FUSED_NO_KEEP");
+  k->agg_wide_offsets = env_flag("GATRES_AGG_WIDE_OFFSETS");
   // diagnostic build only
-  k->agg_wide_offsets = 0; k->fused_threads = 1024; k->fused_no_window = 0;
+  k->fused_threads = 1024; k->fused_no_window = 0;
   k->fused_nocache = 0; k->fused_wide = 0; k->fused_heartbeat = 0;
   k->proj_rows = 0; k->proj_stream = 0; k->dw_fp32 = 0; k->no_co_launch = 0;
   k->co_launch_always = 0; k->dw_slab_rows = 0; k->xch_nowait = 0; k->diag_nomask = 0;
 #ifdef GATRES_DIAG_BUILD
-  k->agg_wide_offsets = env_flag("GATRES_AGG_WIDE_OFFSETS");
   k->fused_threads = env_int("GATRES_FUSED_THREADS", 1024) == 512 ? 512 : 1024;
   k->fused_no_window = env_flag("GATRES_FUSED_NO_WINDOW");
   k->fused_nocache = env_flag("GATRES_FUSED_NOCACHE");

@@ -637,6 +637,37 @@ int gatres_fused_cus_per_segment(const gatres_model_t* m, const gatres_graph_t* 
  * gatres_graph_t.window).  It is faster than the whole-segment-table kernel even for inference, so a caller that only
  * wants predictions may pass a throw-away `saved` buffer of gatres_saved_floats() to gatres_model_forward. */
 int gatres_fused_window_kernel(const gatres_model_t* m, const gatres_graph_t* g);
+/* What gatres_fused_run launches for this model, plan and `phases` (its argument) when it is given a `saved` buffer: the
+ * decision function the launch itself calls, so the answer is the launch.  (Without a `saved` buffer a launch never takes
+ * the window kernel; nothing else changes.)  num_cus <= 0: the current device's CUs; a positive value stands in for them in
+ * this call only, so the decision for a full MI355X (256) can be asked for anywhere.  out[GATRES_FUSED_PLAN_WORDS]:
+ *   PARTS       workgroups (CUs) per segment, gatres_fused_cus_per_segment
+ *   WINDOW      1: the window kernel (LDS tables sized by the parts' row windows); 0: the whole-segment-table kernel
+ *   CACHED      1: the whole-segment kernel keeps its gathered tables in LDS; 0: in global scratch (read when WINDOW == 0)
+ *   KEEP        1: a forward + backward launch of the window kernel keeps ReLU masks and own-row g_pre in LDS
+ *   FACTS       the launch facts that select the window kernel's instantiation: 0x400 rows of at most six entries,
+ *               0x1000 parts of at most 64 own rows, 0x2000 inference (GATRES_MODEL_INFERENCE, forward only), 0x4000 probed
+ *               dispatch (gatres_probe_xcd_dispatch)
+ *   LAUNCHES    kernel launches (more than one when the whole grid would not be resident: rounds)
+ *   PER_LAUNCH  segments per launch (the last launch takes what is left)
+ *   GRID        workgroups of the first launch
+ *   THREADS     threads per workgroup
+ *   PART_ROWS   own rows of the largest part, 16 * ceil(tiles / PARTS)
+ *   CUS         the CU count the decision was taken for
+ * Returns 0; GATRES_E_UNSUPPORTED (out zeroed) where gatres_fused_supported() is 0: the per-op path takes the model. */
+#define GATRES_FUSED_PLAN_PARTS 0
+#define GATRES_FUSED_PLAN_WINDOW 1
+#define GATRES_FUSED_PLAN_CACHED 2
+#define GATRES_FUSED_PLAN_KEEP 3
+#define GATRES_FUSED_PLAN_FACTS 4
+#define GATRES_FUSED_PLAN_LAUNCHES 5
+#define GATRES_FUSED_PLAN_PER_LAUNCH 6
+#define GATRES_FUSED_PLAN_GRID 7
+#define GATRES_FUSED_PLAN_THREADS 8
+#define GATRES_FUSED_PLAN_PART_ROWS 9
+#define GATRES_FUSED_PLAN_CUS 10
+#define GATRES_FUSED_PLAN_WORDS 12
+int gatres_fused_plan(const gatres_model_t* m, const gatres_graph_t* g, int32_t phases, int32_t num_cus, int32_t* out);
 /* Zero the split-segment barrier state inside `scratch` (as in a freshly zeroed buffer).  Only needed after an aborted
  * launch or when the buffer comes from elsewhere; not inside a captured graph that also holds fused launches. */
 int gatres_fused_reset_sync(const gatres_model_t* m, const gatres_graph_t* g, float* scratch, void* stream);

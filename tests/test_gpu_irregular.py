@@ -121,6 +121,75 @@ def test_bf16_sparse_kernels_vs_fp64(pkg, lib, H, C, monkeypatch):
                 assert not gy.cpu()[iso].float().any()
 
 
+@pytest.mark.parametrize("H,C", [(2, 32), (1, 64)])
+@pytest.mark.parametrize("dtype", [0, BF16], ids=["fp32", "bf16"])
+def test_sparse_kernels_wide_offset_instances(pkg, lib, dtype, H, C, monkeypatch):
+    """Every sparse kernel of k_aggregate.hip is compiled twice: with 32-bit byte offsets, and with 64-bit ones for tables of
+    4 GiB and more (offsets_fit_32), which the launchers take by themselves there.  GATRES_AGG_WIDE_OFFSETS=1 takes the wide
+    instance at any size.  Only the addressing differs, so the five kernels' outputs must equal the narrow instance's BYTE FOR
+    BYTE -- on hub graphs (slot paths, edge loops, the whole-wave path), fp32 and bf16, 4 and 8 features per lane -- and they
+    are held to tests/sparse_refs.py by the bounds above (fp32 stores: the bound of the fp32 results)."""
+    chk = pkg._native.check
+    HC = H * C
+    cast = (lambda t: t.bfloat16()) if dtype == BF16 else (lambda t: t)
+    rel, c_store = (2.0 ** -8, C_BF16) if dtype == BF16 else (0.0, C_F32)
+    for name in ("sym_hub", "dir_hub_shuffled"):
+        g = IG.named(name)
+        n, ei = g.num_nodes, g.edge_index
+        plan = _plan(pkg, g)
+        Eg, gp = plan.num_edges_gat, plan.ref()
+        gen = torch.Generator().manual_seed(7 * H + C + dtype + len(name))
+        h, g_out, y, x0, g_pre = (cast(_f(gen, n, w)) for w in (HC, HC, C, C, C))
+        a_s, a_d, bias, g_ad_in = _f(gen, n, H), _f(gen, n, H), _f(gen, HC), _f(gen, n, H)
+        g_e_in, att_s, att_d = _f(gen, Eg, H), _f(gen, HC), _f(gen, HC)
+        src, dst = R.gat_edges(ei, n)
+        out_ref, out_abs, al_ref = R.gat_aggregate_fwd(src, dst, h.cpu(), a_s.cpu(), a_d.cpu(), bias.cpu(), n, H, True)
+        alpha_in = al_ref.float().cuda()
+        ge_ref, ge_abs, gad_ref, gad_abs = R.gat_aggregate_bwd_dst(src, dst, g_out.cpu(), h.cpu(), alpha_in.cpu(), a_s.cpu(),
+                                                                   a_d.cpu(), n, H)
+        gh_ref, gh_abs, gas_ref, gas_abs = R.gat_aggregate_bwd_src(src, dst, g_out.cpu(), alpha_in.cpu(), g_e_in.cpu(),
+                                                                   g_ad_in.cpu(), att_s.cpu(), att_d.cpu(), n, H)
+        m_ref, m_abs = R.mean_residual_relu(ei, y.cpu(), x0.cpu(), n)
+        mb_ref, mb_abs = R.mean_bwd(ei, g_pre.cpu(), n)
+        refs = {"out": (out_ref, out_abs, rel, c_store), "alpha": (al_ref, al_ref, 0.0, C_ALPHA),
+                "g_e": (ge_ref, ge_abs, 0.0, C_F32), "g_a_dst": (gad_ref, gad_abs, 0.0, C_F32),
+                "g_h": (gh_ref, gh_abs, rel, c_store), "g_a_src": (gas_ref, gas_abs, 0.0, C_F32),
+                "mean": (m_ref, m_abs, rel, c_store), "mean_bwd": (mb_ref, mb_abs, rel, c_store)}
+
+        def run():
+            nan = lambda *s: cast(torch.full(s, float("nan"), device="cuda"))
+            nanf = lambda *s: torch.full(s, float("nan"), device="cuda")
+            o = dict(out=nan(n, HC), alpha=nanf(Eg, H), g_e=nanf(Eg, H), g_a_dst=nanf(n, H), g_h=nan(n, HC), g_a_src=nanf(n, H),
+                     mean=nan(n, C), mean_bwd=nan(n, C))
+            chk(lib.gatres_t_gat_aggregate_fwd(gp, h.data_ptr(), a_s.data_ptr(), a_d.data_ptr(), bias.data_ptr(),
+                                               o["out"].data_ptr(), o["alpha"].data_ptr(), H, C, 1, dtype, _st()), "agg fwd")
+            chk(lib.gatres_t_gat_aggregate_bwd_dst(gp, g_out.data_ptr(), h.data_ptr(), alpha_in.data_ptr(), a_s.data_ptr(),
+                                                   a_d.data_ptr(), o["g_e"].data_ptr(), o["g_a_dst"].data_ptr(), H, C, dtype,
+                                                   _st()), "bwd dst")
+            chk(lib.gatres_t_gat_aggregate_bwd_src(gp, g_out.data_ptr(), alpha_in.data_ptr(), g_e_in.data_ptr(),
+                                                   g_ad_in.data_ptr(), att_s.data_ptr(), att_d.data_ptr(), o["g_h"].data_ptr(),
+                                                   o["g_a_src"].data_ptr(), H, C, dtype, _st()), "bwd src")
+            chk(lib.gatres_t_mean_residual_relu_fwd(gp, y.data_ptr(), x0.data_ptr(), o["mean"].data_ptr(), C, dtype, _st()), "mean")
+            chk(lib.gatres_t_mean_bwd(gp, g_pre.data_ptr(), o["mean_bwd"].data_ptr(), C, dtype, _st()), "mean bwd")
+            torch.cuda.synchronize()
+            return o
+
+        need = {}
+        for lf in ("4", "8"):
+            monkeypatch.setenv("GATRES_AGG_LANE_FEATURES", lf)
+            monkeypatch.delenv("GATRES_AGG_WIDE_OFFSETS", raising=False)
+            narrow = run()
+            monkeypatch.setenv("GATRES_AGG_WIDE_OFFSETS", "1")
+            wide = run()
+            for what, (ref, ref_abs, r, c) in refs.items():
+                need[what] = max(need.get(what, 0.0), R.excess(wide[what], ref, ref_abs, r))
+            note(f"irregular sparse kernels, wide offsets, {'bf16' if dtype == BF16 else 'fp32'} H{H} C{C} {name}: worst c needed "
+                 f"per output (bounds: stores {c_store:.2g}, C_ALPHA {C_ALPHA:.2g}, C_F32 {C_F32:.2g})", need)
+            for what, (ref, ref_abs, r, c) in refs.items():
+                assert torch.equal(wide[what].view(torch.uint8), narrow[what].view(torch.uint8)), (name, lf, what)
+                R.assert_within(f"{name} lane features {lf}, wide offsets: {what}", wide[what], ref, ref_abs, r, c)
+
+
 @pytest.mark.parametrize("nc", [32, 64, 128])
 def test_bf16_lin0_lin1_vs_fp64(pkg, lib, nc):
     """gatres_t_lin0_fwd (bf16 store of xm w + b) and gatres_t_lin1_fwd (fp32 sum over bf16 rows) on a ragged row count."""
