@@ -9,6 +9,11 @@ with the plans and the forward's call state of ``evaluation.evaluate_store``.  N
 result is a device tensor, ordered on the stream.  ``error_map`` is the back-test report: one ``gatres_node_error_moments`` launch
 and one read-back.
 
+Every pass below is ``PressureEstimator._pair_pass`` over S x W (snapshot, something) pairs, snapshot-major -- W = 1, the M
+members, the L layouts, the T targets, the K left-out sensors -- cut into batches of ``batch_size`` once, from pair 0, in chunks of
+whole snapshots and whole batches (``pass_schedule``; a pass that keeps every pair's result is one chunk).  What a pass
+contributes is its batch closure -- the launches of one batch -- and, where it chunks, its fold.
+
 Telemetry has gaps.  With ``available`` (uint8 / bool ``[S, K]`` on the device) or ``nan_is_missing`` the staging launch is
 ``gatres_stage_observed_available``: a sensor without a reading in a snapshot is one more hidden node there (``x = 0``,
 ``mask = 1``), which is what the model's training masks taught it.  Still three launches per batch, still nothing read back: no
@@ -238,6 +243,41 @@ def ensemble_chunk(num_snapshots: int, members: int, batch_size: int, row_bytes:
     return min(S, units * unit)
 
 
+def pass_schedule(num_snapshots: int, width: int, batch_size: int, chunk: Optional[int] = None):
+    """The cut of a pass over the S * W pairs (snapshot-major, W = ``width`` pairs per snapshot): one ``(s0, c, batches)`` per
+    chunk of ``chunk`` snapshots (``ensemble_chunk``; ``None``: one chunk of all S) -- the chunk holds the snapshots ``[s0, s0 +
+    c)`` -- with ``batches`` its ``(first_pair, g, off)``: ``g`` pairs from pair ``first_pair = s0 * W + off`` on, ``off`` the
+    batch's first pair inside the chunk.  A chunk of ``ensemble_chunk`` starts a batch, so the batches are those of the one
+    chunk, whatever the chunk.  ``batches`` is an iterator: a long pass enqueues its first batch before the last is cut."""
+    S, W, bs = int(num_snapshots), int(width), int(batch_size)
+    C = S if chunk is None else int(chunk)
+
+    def batches(first, pairs):
+        for off in range(0, pairs, bs):
+            yield first + off, min(bs, pairs - off), off
+
+    for s0 in range(0, S, C):
+        c = min(C, S - s0)
+        yield s0, c, batches(s0 * W, c * W)
+
+
+def pass_batch_sizes(num_snapshots: int, width: int, batch_size: int) -> set:
+    """The batch sizes that occur in ``pass_schedule``: the first batch's and the last one's."""
+    P, bs = int(num_snapshots) * int(width), int(batch_size)
+    return {min(bs, P), P - (P - 1) // bs * bs}
+
+
+def _level_index(levels: Tuple[float, ...], level) -> int:
+    """The row of a bounds matrix for ``level``: an exact match of one of ``levels`` (``None``: the only one)."""
+    if level is None:
+        if len(levels) != 1:
+            raise ValueError(f"level=None needs bounds with one level; these hold {levels}")
+        return 0
+    if float(level) not in levels:
+        raise ValueError(f"level {level!r} is not one of the calibrated levels {levels}")
+    return levels.index(float(level))
+
+
 def noise_report_from_moments(table, observed_idx) -> Dict[str, np.ndarray]:
     """The per-node spread report from a ``gatres_node_spread_moments`` table ``[N, NODE_SPREAD_RECORD]`` (include/gatres.h), in
     fp64: ``spread`` = sqrt(sum std^2 / S), the root-mean-square standard deviation of the node's estimate over the snapshots,
@@ -376,13 +416,7 @@ class ErrorBounds:
 
     def level_index(self, level=None) -> int:
         """The row of ``bounds`` for ``level``: an exact match of a stored level (``None``: the only one)."""
-        if level is None:
-            if len(self.levels) != 1:
-                raise ValueError(f"level=None needs bounds with one level; these hold {self.levels}")
-            return 0
-        if float(level) not in self.levels:
-            raise ValueError(f"level {level!r} is not one of the calibrated levels {self.levels}")
-        return self.levels.index(float(level))
+        return _level_index(self.levels, level)
 
     def interval(self, estimates: torch.Tensor, level=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(estimates - b, estimates + b)`` with ``b = bounds[level_index(level)]`` broadcast over the rows of ``estimates``
@@ -436,13 +470,7 @@ class ScreeningBounds:
 
     def level_index(self, level=None) -> int:
         """The row of ``bounds`` for ``level``: an exact match of a stored level (``None``: the only one)."""
-        if level is None:
-            if len(self.levels) != 1:
-                raise ValueError(f"level=None needs bounds with one level; these hold {self.levels}")
-            return 0
-        if float(level) not in self.levels:
-            raise ValueError(f"level {level!r} is not one of the calibrated levels {self.levels}")
-        return self.levels.index(float(level))
+        return _level_index(self.levels, level)
 
     @property
     def inverse(self) -> torch.Tensor:
@@ -644,6 +672,7 @@ class PressureEstimator:
         if self._topo.device != dev:
             raise ValueError(f"model is on {dev}, the store on {self._topo.device}")
         self.scale, self.offset = (self.std, self.mean) if norm_type == "znorm" else (1.0, 0.0)     # descale: no eps, as the stores
+        self._factor = self.std + self.eps if norm_type == "znorm" else 1.0           # normalise: with eps, as the stores
         self._normalise = _native.NORMALISE_NONE
         if norm_type == "znorm":
             self._normalise = _native.NORMALISE_RECIPROCAL if _divides_by_reciprocal(dev) else _native.NORMALISE_DIVIDE
@@ -687,13 +716,74 @@ class PressureEstimator:
         if len(store) == 0:
             raise ValueError("empty store")
 
-    def _result(self, S: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+    def _out(self, out: Optional[torch.Tensor], shape, dtype=torch.float32) -> torch.Tensor:
+        """A caller's ``out`` if it is what the pass writes -- contiguous ``shape`` of ``dtype`` on the device --, a new tensor
+        for ``None``."""
+        shape = tuple(shape)
         if out is None:
-            return torch.empty((S, self.nodes_per_graph), dtype=torch.float32, device=self.device)
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != self.device
-                or tuple(out.shape) != (S, self.nodes_per_graph) or not out.is_contiguous()):
-            raise ValueError(f"out must be fp32 contiguous [{S}, {self.nodes_per_graph}] on {self.device}")
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if (not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != self.device or tuple(out.shape) != shape
+                or not out.is_contiguous()):
+            raise ValueError(f"out must be {'fp64' if dtype == torch.float64 else 'fp32'} contiguous "
+                             f"[{', '.join(str(n) for n in shape)}] on {self.device}")
         return out
+
+    def _result(self, S: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+        return self._out(out, (S, self.nodes_per_graph))
+
+    def _staging_tail(self, normalise: int) -> tuple:
+        """The arguments ``(observed, K, normalise, offset, factor)`` every staging launch ends its source description with."""
+        return self._observed.data_ptr(), len(self.observed_idx), normalise, self.offset, self._factor
+
+    def _parameters(self) -> torch.Tensor:
+        """The model's parameter vector, for a pass's closure (one look-up per pass: the property walks every parameter)."""
+        flat = self.model.flat_parameters
+        if flat.device != self.device:
+            raise ValueError(f"the model moved to {flat.device}; the estimator was built on {self.device}")
+        return flat
+
+    def _pair_pass(self, S: int, width: int, chunk: Optional[int], batch, fold=None) -> None:
+        """One pass over the ``S * width`` pairs in the cut of ``pass_schedule``: ``batch(P, first_pair, g, off)`` enqueues the
+        launches of one batch on the plan ``P`` of its size, ``fold(s0, c)`` what follows a chunk.  The plans of the two batch
+        sizes that occur are fetched up front.  (The closure holds the parameter vector of ``_parameters``, which is where a
+        model that moved is refused: the vector is looked up once per pass.)"""
+        model = self.model
+        model.eval()
+        with torch.cuda.device(self.device):
+            plans = {g: _eval_plan(model, self._topo, g) for g in sorted(pass_batch_sizes(S, width, self.batch_size))}
+            for s0, c, batches in pass_schedule(S, width, self.batch_size, chunk):
+                for first_pair, g, off in batches:
+                    batch(plans[g], first_pair, g, off)
+                if fold is not None:
+                    fold(s0, c)
+
+    def _error_moments(self, est: torch.Tensor, truth: torch.Tensor, rows: int, cols: int, observed: torch.Tensor,
+                       available: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The fp64 device table of one ``gatres_node_error_moments`` launch over ``est`` / ``truth`` (``[rows, cols]``, ``truth``
+        scaled) -- with ``available`` (``[rows, len(observed)]``: an entry at an observed node counts unless this is non-zero)
+        of one ``gatres_node_error_moments_available`` launch."""
+        lib, head = _native.load(), (est.data_ptr(), truth.data_ptr(), rows, cols, self.scale, self.offset, observed.data_ptr(),
+                                     int(observed.numel()))
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream(self.device)
+            if available is None:
+                table = torch.empty((cols, NODE_ERROR_RECORD), dtype=torch.float64, device=self.device)
+                _native.check(lib.gatres_node_error_moments(*head, table.data_ptr(), stream), "gatres_node_error_moments")
+            else:
+                table = torch.empty((cols, NODE_ERROR_AVAIL_RECORD), dtype=torch.float64, device=self.device)
+                _native.check(lib.gatres_node_error_moments_available(*head, available.data_ptr(), table.data_ptr(), stream),
+                              "gatres_node_error_moments_available")
+        return table
+
+    def _judged(self, store, est: torch.Tensor, ints: Sequence[torch.Tensor] = ()) -> Tuple[float, np.ndarray]:
+        """What a back-test report reads of one of its passes, in ONE read-back: the MAE of ``est`` over the nodes outside
+        ``observed_idx`` (``error_map``'s ``hidden_mae``, from one moments launch) and, flat behind one another, the integer
+        device tensors ``ints`` as host int64.  The integers travel as the bits of doubles: exact at any size."""
+        n = self.nodes_per_graph * NODE_ERROR_RECORD
+        table = self._error_moments(est, store.data, len(store), self.nodes_per_graph, self._observed)
+        flat = torch.cat([table.reshape(-1)] + [t.to(torch.int64).reshape(-1).view(torch.float64) for t in ints])
+        host = flat.cpu().numpy()
+        return float(error_map_from_moments(host[:n])["hidden_mae"]), host[n:].view(np.int64)
 
     def _check_available(self, available, S: int) -> None:
         K = len(self.observed_idx)
@@ -711,38 +801,34 @@ class PressureEstimator:
             cached = self._sigma_cache[layout] = (v.tobytes(), torch.from_numpy(v).to(self.device))
         return cached[1]
 
-    def _launches(self, src: torch.Tensor, layout: int, normalise: int, available, nan_is_missing: bool, noise):
-        """The three launches of one batch as a function ``batch(P, first, g, dst, dst_rows, dst_first)``: stage the ``g`` graphs
+    def _launches(self, src: torch.Tensor, layout: int, normalise: int, available, nan_is_missing: bool, noise,
+                  dst: torch.Tensor):
+        """The three launches of one batch as a function ``batch(P, first, g, off)`` for ``_pair_pass``: stage the ``g`` graphs
         from ``first`` on (source rows -- or, with ``noise = (sigma, seed, members, member0)``, pairs) into the plan ``P``, run
-        the forward, write rows ``dst_first ...`` of ``dst``."""
-        N, K, lib = self.nodes_per_graph, len(self.observed_idx), _native.load()
-        S = int(src.shape[0])
-        flat = self.model.flat_parameters
-        if flat.device != self.device:
-            raise ValueError(f"the model moved to {flat.device}; the estimator was built on {self.device}")
-        factor = self.std + self.eps if self.norm_type == "znorm" else 1.0
-        stream = _native.current_stream(self.device)
+        the forward, write rows ``off ...`` of ``dst`` (a chunk's rows: the pass's result when it is one chunk)."""
+        N, lib, flat, check = self.nodes_per_graph, _native.load(), self._parameters(), _native.check
+        S, src_p, avail_p = int(src.shape[0]), src.data_ptr(), _native.ptr(available)
+        dst_p, dst_rows = dst.data_ptr(), int(dst.shape[0])
+        stream, nan, tail = _native.current_stream(self.device), int(bool(nan_is_missing)), self._staging_tail(normalise)
         with_gaps = available is not None or bool(nan_is_missing)
-        tail = (self._observed.data_ptr(), K, normalise, self.offset, factor)
+        scale, offset, keep = self.scale, self.offset, int(self.keep_observed)
+        if noise is not None:
+            sigma, seed, members, member0 = noise
+            sigma_p = sigma.data_ptr()
 
-        def batch(P, first, g, dst, dst_rows, dst_first):
-            to = (P.x.data_ptr(), P.mask.data_ptr())
+        def batch(P, first, g, off):
+            x, mask = P.x.data_ptr(), P.mask.data_ptr()
             if noise is not None:
-                sigma, seed, members, member0 = noise
-                _native.check(lib.gatres_stage_observed_noisy(
-                    src.data_ptr(), layout, S, first, members, member0, N, g, *tail, *to, _native.ptr(available),
-                    int(bool(nan_is_missing)), sigma.data_ptr(), seed, stream), "gatres_stage_observed_noisy")
+                check(lib.gatres_stage_observed_noisy(src_p, layout, S, first, members, member0, N, g, *tail, x, mask, avail_p, nan,
+                                                      sigma_p, seed, stream), "gatres_stage_observed_noisy")
             elif with_gaps:
-                _native.check(lib.gatres_stage_observed_available(
-                    src.data_ptr(), layout, S, None, first, N, g, *tail, *to, _native.ptr(available),
-                    int(bool(nan_is_missing)), stream), "gatres_stage_observed_available")
+                check(lib.gatres_stage_observed_available(src_p, layout, S, None, first, N, g, *tail, x, mask, avail_p, nan, stream),
+                      "gatres_stage_observed_available")
             else:
-                _native.check(lib.gatres_stage_observed(src.data_ptr(), layout, S, None, first, N, g, *tail, *to, stream),
-                              "gatres_stage_observed")
+                check(lib.gatres_stage_observed(src_p, layout, S, None, first, N, g, *tail, x, mask, stream), "gatres_stage_observed")
             _enqueue_forward(lib, flat, P, stream)
-            _native.check(lib.gatres_estimate_write(
-                P.out.data_ptr(), P.x.data_ptr(), P.mask.data_ptr(), N, g, self.scale, self.offset, int(self.keep_observed),
-                dst.data_ptr(), dst_rows, N, dst_first, stream), "gatres_estimate_write")
+            check(lib.gatres_estimate_write(P.out.data_ptr(), x, mask, N, g, scale, offset, keep, dst_p, dst_rows, N, off, stream),
+                  "gatres_estimate_write")
 
         return batch
 
@@ -755,22 +841,16 @@ class PressureEstimator:
 
     def _run(self, src: torch.Tensor, layout: int, normalise: int, out: Optional[torch.Tensor],
              available: Optional[torch.Tensor] = None, nan_is_missing: bool = False, noise=None) -> torch.Tensor:
-        model, S = self.model, int(src.shape[0])
+        S = int(src.shape[0])
         if available is not None:
             self._check_available(available, S)
         out = self._result(S, out)
-        model.eval()
-        with torch.cuda.device(self.device):
-            batch = self._launches(src, layout, normalise, available, nan_is_missing, noise)
-            sizes = [min(self.batch_size, S - first) for first in range(0, S, self.batch_size)]
-            plans = {g: _eval_plan(model, self._topo, g) for g in sorted(set(sizes))}
-            for b, g in enumerate(sizes):
-                batch(plans[g], b * self.batch_size, g, out, S, b * self.batch_size)
+        self._pair_pass(S, 1, None, self._launches(src, layout, normalise, available, nan_is_missing, noise, out))
         return out
 
     def _run_ensemble(self, src: torch.Tensor, layout: int, normalise: int, noise_std, members, seed, available,
                       nan_is_missing: bool, mean_out, std_out, max_scratch_bytes) -> Tuple[torch.Tensor, torch.Tensor]:
-        N, S, bs = self.nodes_per_graph, int(src.shape[0]), self.batch_size
+        N, S = self.nodes_per_graph, int(src.shape[0])
         if isinstance(members, bool) or not isinstance(members, (int, np.integer)) or int(members) < 1:
             raise ValueError(f"members must be a positive integer; got {members!r}")
         M = int(members)
@@ -782,22 +862,15 @@ class PressureEstimator:
         mean, std = self._result(S, mean_out), self._result(S, std_out)
         if mean_out is not None and mean_out is std_out:
             raise ValueError("mean_out and std_out must be different tensors")
-        C = ensemble_chunk(S, M, bs, 4 * N, max_scratch_bytes)
-        model, lib = self.model, _native.load()
-        model.eval()
-        with torch.cuda.device(self.device):
-            stream = _native.current_stream(self.device)
-            batch = self._launches(src, layout, normalise, available, nan_is_missing, noise)
-            scratch = torch.empty((C * M, N), dtype=torch.float32, device=self.device)
-            sizes = {min(bs, S * M - first) for first in (0, (S * M - 1) // bs * bs)}
-            plans = {g: _eval_plan(model, self._topo, g) for g in sorted(sizes)}
-            for s0 in range(0, S, C):                               # (s0 * M is a multiple of bs: a chunk starts a batch)
-                c = min(C, S - s0)
-                for off in range(0, c * M, bs):
-                    g = min(bs, c * M - off)
-                    batch(plans[g], s0 * M + off, g, scratch, C * M, off)
-                _native.check(lib.gatres_ensemble_reduce(scratch.data_ptr(), c, M, N, N, mean.data_ptr(), std.data_ptr(), S, N,
-                                                         s0, stream), "gatres_ensemble_reduce")
+        C = ensemble_chunk(S, M, self.batch_size, 4 * N, max_scratch_bytes)
+        lib, stream = _native.load(), _native.current_stream(self.device)
+        scratch = torch.empty((C * M, N), dtype=torch.float32, device=self.device)
+
+        def fold(s0, c):
+            _native.check(lib.gatres_ensemble_reduce(scratch.data_ptr(), c, M, N, N, mean.data_ptr(), std.data_ptr(), S, N, s0,
+                                                     stream), "gatres_ensemble_reduce")
+
+        self._pair_pass(S, M, C, self._launches(src, layout, normalise, available, nan_is_missing, noise, scratch), fold)
         return mean, std
 
     def _check_readings(self, readings) -> None:
@@ -873,11 +946,11 @@ class PressureEstimator:
         noise_member=m)`` up to the batch it is computed in.  Returns ``(mean, std)``, fp32 ``[S, N_g]`` device tensors in
         physical units ordered on the current stream (``mean_out`` / ``std_out``: write them there).
 
-        The S * M (snapshot, member) pairs, snapshot-major, are one long pass cut into batches of ``batch_size`` -- one
-        snapshot's 32 members at batch size 32 are ONE forward launch -- with the three launches of ``estimate`` per batch.  The
-        members' estimates go to a scratch matrix of at most ``max_scratch_bytes`` (``ensemble_chunk``: whole snapshots and whole
-        batches, at least one such unit), one ``gatres_ensemble_reduce`` launch per chunk folds them in fp64 in member order.
-        The bits of the result depend on neither the budget nor the run.  Nothing is read back, nothing synchronises."""
+        One pass over the S * M (snapshot, member) pairs -- one snapshot's 32 members at batch size 32 are ONE forward launch --
+        with the three launches of ``estimate`` per batch.  The members' estimates go to a scratch matrix of at most
+        ``max_scratch_bytes`` (``ensemble_chunk``, at least one unit of it), one ``gatres_ensemble_reduce`` launch per chunk folds
+        them in fp64 in member order.  The bits of the result depend on neither the budget nor the run.  Nothing is read back,
+        nothing synchronises."""
         self._check_readings(readings)
         return self._run_ensemble(readings, _native.OBSERVED_READINGS, self._normalise, noise_std, members, seed, available,
                                   nan_is_missing, mean_out, std_out, max_scratch_bytes)
@@ -941,13 +1014,13 @@ class PressureEstimator:
         (node indices) only those of them: a pool disjoint from the candidates gives every layout the same pool.
         ``available`` (``[len(store), K]``) takes readings away in every layout, as in ``estimate_store``.
 
-        The S * L (snapshot, layout) pairs, snapshot-major, are one long pass cut into batches of ``batch_size`` once, from pair
-        0, with three launches per batch (``gatres_stage_observed_layouts``, the forward, ``gatres_layout_pair_errors``): the
-        estimates are never written out.  The pairs' records go to a scratch of at most ``max_scratch_bytes``
-        (``ensemble_chunk``), one ``gatres_layout_error_reduce`` launch per chunk folds them in snapshot order: the bits of the
-        table depend on neither the budget nor the run.  Nothing is read back, nothing synchronises."""
+        One pass over the S * L (snapshot, layout) pairs with three launches per batch (``gatres_stage_observed_layouts``, the
+        forward, ``gatres_layout_pair_errors``): the estimates are never written out.  The pairs' records go to a scratch of at
+        most ``max_scratch_bytes`` (``ensemble_chunk``), one ``gatres_layout_error_reduce`` launch per chunk folds them in
+        snapshot order: the bits of the table depend on neither the budget nor the run.  Nothing is read back, nothing
+        synchronises."""
         self._check_store(store)
-        K, N, S, bs = len(self.observed_idx), self.nodes_per_graph, len(store), self.batch_size
+        K, N, S = len(self.observed_idx), self.nodes_per_graph, len(store)
         if (not isinstance(layouts, torch.Tensor) or layouts.dtype not in (torch.uint8, torch.bool) or layouts.dim() != 2
                 or layouts.shape[1] != K or layouts.shape[0] == 0 or layouts.device != self.device or not layouts.is_contiguous()):
             raise ValueError(f"layouts must be uint8 or bool, contiguous [L, {K}] on {self.device}")
@@ -957,37 +1030,29 @@ class PressureEstimator:
         if int(max_scratch_bytes) <= 0:
             raise ValueError("max_scratch_bytes must be positive")
         score = self._score_mask(score_nodes)
-        if out is None:
-            out = torch.empty((L, LAYOUT_ERROR_RECORD), dtype=torch.float64, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != self.device
-                or tuple(out.shape) != (L, LAYOUT_ERROR_RECORD) or not out.is_contiguous()):
-            raise ValueError(f"out must be fp64 contiguous [{L}, {LAYOUT_ERROR_RECORD}] on {self.device}")
-        C = ensemble_chunk(S, L, bs, 8 * LAYOUT_PAIR_RECORD, max_scratch_bytes)
-        model, lib, flat = self.model, _native.load(), self.model.flat_parameters
-        if flat.device != self.device:
-            raise ValueError(f"the model moved to {flat.device}; the estimator was built on {self.device}")
-        model.eval()
-        src = store.data
-        with torch.cuda.device(self.device):
-            stream = _native.current_stream(self.device)
-            rec = torch.empty((C * L, LAYOUT_PAIR_RECORD), dtype=torch.float64, device=self.device)
-            sizes = {min(bs, S * L - first) for first in (0, (S * L - 1) // bs * bs)}
-            plans = {g: _eval_plan(model, self._topo, g) for g in sorted(sizes)}
-            for s0 in range(0, S, C):                               # (s0 * L is a multiple of bs: a chunk starts a batch)
-                c = min(C, S - s0)
-                for off in range(0, c * L, bs):
-                    g = min(bs, c * L - off)
-                    P = plans[g]
-                    _native.check(lib.gatres_stage_observed_layouts(
-                        src.data_ptr(), _native.OBSERVED_FULL_ROWS, S, s0 * L + off, L, N, g, self._observed.data_ptr(), K,
-                        _native.NORMALISE_NONE, 0.0, 1.0, P.x.data_ptr(), P.mask.data_ptr(), _native.ptr(available), 0,
-                        layouts.data_ptr(), stream), "gatres_stage_observed_layouts")
-                    _enqueue_forward(lib, flat, P, stream)
-                    _native.check(lib.gatres_layout_pair_errors(
-                        P.out.data_ptr(), P.mask.data_ptr(), src.data_ptr(), S, N, g, s0 * L + off, L, self.scale, self.offset,
-                        _native.ptr(score), rec.data_ptr(), C * L, off, stream), "gatres_layout_pair_errors")
-                _native.check(lib.gatres_layout_error_reduce(rec.data_ptr(), c, L, out.data_ptr(), int(s0 > 0), stream),
-                              "gatres_layout_error_reduce")
+        out = self._out(out, (L, LAYOUT_ERROR_RECORD), torch.float64)
+        C = ensemble_chunk(S, L, self.batch_size, 8 * LAYOUT_PAIR_RECORD, max_scratch_bytes)
+        lib, flat, stream, check = _native.load(), self._parameters(), _native.current_stream(self.device), _native.check
+        rec = torch.empty((C * L, LAYOUT_PAIR_RECORD), dtype=torch.float64, device=self.device)
+        stage, errors, full_rows = lib.gatres_stage_observed_layouts, lib.gatres_layout_pair_errors, _native.OBSERVED_FULL_ROWS
+        src_p, rec_p, rec_rows, scale, offset = store.data.data_ptr(), rec.data_ptr(), C * L, self.scale, self.offset
+        avail_p, layouts_p, score_p = _native.ptr(available), layouts.data_ptr(), _native.ptr(score)
+        # (a store's rows are normalised already.  Under NORMALISE_NONE the staging launch reads neither the tail's offset nor
+        # its factor -- obs_normalise returns the value, the scale stays 1 -- so they may be the estimator's: the same bits)
+        tail = self._staging_tail(_native.NORMALISE_NONE)
+
+        def batch(P, first, g, off):
+            mask = P.mask.data_ptr()
+            check(stage(src_p, full_rows, S, first, L, N, g, *tail, P.x.data_ptr(), mask, avail_p, 0, layouts_p, stream),
+                  "gatres_stage_observed_layouts")
+            _enqueue_forward(lib, flat, P, stream)
+            check(errors(P.out.data_ptr(), mask, src_p, S, N, g, first, L, scale, offset, score_p, rec_p, rec_rows, off,
+                         stream), "gatres_layout_pair_errors")
+
+        def fold(s0, c):
+            check(lib.gatres_layout_error_reduce(rec_p, c, L, out.data_ptr(), int(s0 > 0), stream), "gatres_layout_error_reduce")
+
+        self._pair_pass(S, L, C, batch, fold)
         return out
 
     @classmethod
@@ -1040,20 +1105,7 @@ class PressureEstimator:
         if available is not None:
             self._check_available(available, len(store))
         est = self.estimate_store(store, available=available) if estimates is None else self._result(len(store), estimates)
-        lib = _native.load()
-        with torch.cuda.device(self.device):
-            stream = _native.current_stream(self.device)
-            if available is None:
-                table = torch.empty((self.nodes_per_graph, NODE_ERROR_RECORD), dtype=torch.float64, device=self.device)
-                _native.check(lib.gatres_node_error_moments(
-                    est.data_ptr(), store.data.data_ptr(), len(store), self.nodes_per_graph, self.scale, self.offset,
-                    self._observed.data_ptr(), len(self.observed_idx), table.data_ptr(), stream), "gatres_node_error_moments")
-            else:
-                table = torch.empty((self.nodes_per_graph, NODE_ERROR_AVAIL_RECORD), dtype=torch.float64, device=self.device)
-                _native.check(lib.gatres_node_error_moments_available(
-                    est.data_ptr(), store.data.data_ptr(), len(store), self.nodes_per_graph, self.scale, self.offset,
-                    self._observed.data_ptr(), len(self.observed_idx), available.data_ptr(), table.data_ptr(), stream),
-                    "gatres_node_error_moments_available")
+        table = self._error_moments(est, store.data, len(store), self.nodes_per_graph, self._observed, available)
         if available is None:
             return error_map_from_moments(table.cpu().numpy())
         return error_map_from_moments(table.cpu().numpy(), available=True, observed_idx=self.observed_idx)
@@ -1240,65 +1292,45 @@ class PressureEstimator:
         return buf
 
     def _sensitivity_launches(self, src: torch.Tensor, layout: int, normalise: int, targets_dev, T: int, available,
-                              nan_is_missing: bool):
-        """The four launches of one batch of (snapshot, target) pairs as a function ``batch(P, first_pair, g, J, J_rows,
-        J_first)``: stage the ``g`` pairs from ``first_pair`` on into the plan ``P`` with their seeds, run the forward keeping
+                              nan_is_missing: bool, J: torch.Tensor):
+        """The four launches of one batch of (snapshot, target) pairs as a function ``batch(P, first_pair, g, off)`` for
+        ``_pair_pass``: stage the ``g`` pairs from ``first_pair`` on into the plan ``P`` with their seeds, run the forward keeping
         the activations and the backward with ``g_x`` -- the two calls the module's autograd node enqueues, with the training
-        model reference and a throw-away parameter gradient --, gather the sensors' entries into rows ``J_first ...`` of ``J``."""
-        N, K, lib = self.nodes_per_graph, len(self.observed_idx), _native.load()
-        S = int(src.shape[0])
-        flat = self.model.flat_parameters
-        if flat.device != self.device:
-            raise ValueError(f"the model moved to {flat.device}; the estimator was built on {self.device}")
-        factor = self.std + self.eps if self.norm_type == "znorm" else 1.0
-        unit = self.scale / factor                              # d physical estimate / d physical reading per d out / d x
-        stream = _native.current_stream(self.device)
-        tail = (self._observed.data_ptr(), K, normalise, self.offset, factor)
+        model reference and a throw-away parameter gradient --, gather the sensors' entries into rows ``off ...`` of ``J`` (a
+        chunk's rows of K: the pass's result when it is one chunk)."""
+        N, K, lib, check = self.nodes_per_graph, len(self.observed_idx), _native.load(), _native.check
+        S, J_p, J_rows = int(src.shape[0]), J.data_ptr(), J.numel() // K
+        unit = self.scale / self._factor                        # d physical estimate / d physical reading per d out / d x
+        stream, nan, tail = _native.current_stream(self.device), int(bool(nan_is_missing)), self._staging_tail(normalise)
+        flat_p, src_p, observed_p = self._parameters().data_ptr(), src.data_ptr(), self._observed.data_ptr()
+        targets_p, avail_p = _native.ptr(targets_dev), _native.ptr(available)
 
-        def batch(P, first_pair, g, J, J_rows, J_first):
+        def batch(P, first_pair, g, off):
             saved, g_out, g_x, grads = self._sensitivity_buffers(P)
             st = P.state
-            _native.check(lib.gatres_stage_observed_targets(
-                src.data_ptr(), layout, S, first_pair, T, _native.ptr(targets_dev), N, g, *tail, P.x.data_ptr(),
-                P.mask.data_ptr(), g_out.data_ptr(), _native.ptr(available), int(bool(nan_is_missing)), stream),
-                "gatres_stage_observed_targets")
-            _native.check(lib.gatres_model_forward(st["mref"], st["gref"], flat.data_ptr(), P.x.data_ptr(), None,
-                                                   P.out.data_ptr(), saved.data_ptr(), st["scratch"].data_ptr(), stream),
-                          "gatres_model_forward")
-            _native.check(lib.gatres_model_backward(st["mref"], st["gref"], flat.data_ptr(), P.x.data_ptr(), None,
-                                                    g_out.data_ptr(), saved.data_ptr(), st["scratch"].data_ptr(),
-                                                    grads.data_ptr(), g_x.data_ptr(), stream), "gatres_model_backward")
+            x, mask, scratch = P.x.data_ptr(), P.mask.data_ptr(), st["scratch"].data_ptr()
+            check(lib.gatres_stage_observed_targets(src_p, layout, S, first_pair, T, targets_p, N, g, *tail, x, mask,
+                                                    g_out.data_ptr(), avail_p, nan, stream), "gatres_stage_observed_targets")
+            check(lib.gatres_model_forward(st["mref"], st["gref"], flat_p, x, None, P.out.data_ptr(), saved.data_ptr(), scratch,
+                                           stream), "gatres_model_forward")
+            check(lib.gatres_model_backward(st["mref"], st["gref"], flat_p, x, None, g_out.data_ptr(), saved.data_ptr(), scratch,
+                                            grads.data_ptr(), g_x.data_ptr(), stream), "gatres_model_backward")
             # (fault: the last float of the parameter gradient, lin1.bias -- a NaN there marks a failed split launch)
-            _native.check(lib.gatres_sensitivity_gather(
-                g_x.data_ptr(), P.mask.data_ptr(), grads.data_ptr() + 4 * (grads.numel() - 1), N, g, self._observed.data_ptr(),
-                K, unit, J.data_ptr(), J_rows, K, J_first, stream), "gatres_sensitivity_gather")
+            check(lib.gatres_sensitivity_gather(g_x.data_ptr(), mask, grads.data_ptr() + 4 * (grads.numel() - 1), N, g, observed_p,
+                                                K, unit, J_p, J_rows, K, off, stream), "gatres_sensitivity_gather")
 
         return batch
 
-    def _sensitivity_plans(self, pairs: int):
-        bs = self.batch_size
-        sizes = {min(bs, pairs - first) for first in (0, (pairs - 1) // bs * bs)}
-        return {g: _eval_plan(self.model, self._topo, g) for g in sorted(sizes)}
-
     def _run_sensitivity(self, src: torch.Tensor, layout: int, normalise: int, targets, available, nan_is_missing: bool,
                          out: Optional[torch.Tensor]) -> torch.Tensor:
-        S, K, bs = int(src.shape[0]), len(self.observed_idx), self.batch_size
+        S, K = int(src.shape[0]), len(self.observed_idx)
         nodes, targets_dev = self._targets(targets)
         T = len(nodes)
         if available is not None:
             self._check_available(available, S)
-        if out is None:
-            out = torch.empty((S, T, K), dtype=torch.float32, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != self.device
-                or tuple(out.shape) != (S, T, K) or not out.is_contiguous()):
-            raise ValueError(f"out must be fp32 contiguous [{S}, {T}, {K}] on {self.device}")
-        self.model.eval()
-        with torch.cuda.device(self.device):
-            batch = self._sensitivity_launches(src, layout, normalise, targets_dev, T, available, nan_is_missing)
-            plans = self._sensitivity_plans(S * T)
-            for first in range(0, S * T, bs):
-                g = min(bs, S * T - first)
-                batch(plans[g], first, g, out, S * T, first)
+        out = self._out(out, (S, T, K))
+        self._pair_pass(S, T, None, self._sensitivity_launches(src, layout, normalise, targets_dev, T, available,
+                                                               nan_is_missing, out))
         return out
 
     def _store_rows(self, store, first, count) -> Tuple[torch.Tensor, int]:
@@ -1329,11 +1361,10 @@ class PressureEstimator:
         exactly 0 there.  The network is piecewise linear in the readings up to the attention softmax, so ``J`` is the exact
         derivative at these readings, not a finite difference.
 
-        Reverse mode: the S * T (snapshot, target) pairs, snapshot-major, are one long pass cut into batches of ``batch_size``
-        (a batch may straddle snapshots, the last one may be ragged), four launches per batch: ``gatres_stage_observed_targets``
-        (the staging of ``estimate`` plus the pair's seed ``e_j``), the forward keeping its activations, the backward with
-        ``g_x``, ``gatres_sensitivity_gather``.  A full Jacobian of one snapshot is ``ceil(N_g / batch_size)`` batches.  The
-        backward's buffers are allocated once per plan and kept on the estimator."""
+        Reverse mode: one pass over the S * T (snapshot, target) pairs, four launches per batch:
+        ``gatres_stage_observed_targets`` (the staging of ``estimate`` plus the pair's seed ``e_j``), the forward keeping its
+        activations, the backward with ``g_x``, ``gatres_sensitivity_gather``.  A full Jacobian of one snapshot is ``ceil(N_g /
+        batch_size)`` batches.  The backward's buffers are allocated once per plan and kept on the estimator."""
         self._check_readings(readings)
         return self._run_sensitivity(readings, _native.OBSERVED_READINGS, self._normalise, targets, available, nan_is_missing, out)
 
@@ -1357,26 +1388,19 @@ class PressureEstimator:
         if isinstance(max_scratch_bytes, bool) or int(max_scratch_bytes) <= 0:
             raise ValueError("max_scratch_bytes must be positive")
         nodes, targets_dev = self._targets(targets)
-        T, K, bs = len(nodes), len(self.observed_idx), self.batch_size
+        T, K = len(nodes), len(self.observed_idx)
         if available is not None:
             self._check_available(available, S)
-        C = ensemble_chunk(S, T, bs, 4 * K, max_scratch_bytes)
+        C = ensemble_chunk(S, T, self.batch_size, 4 * K, max_scratch_bytes)
         table = torch.empty((T, K, SENSITIVITY_RECORD), dtype=torch.float64, device=self.device)
-        lib = _native.load()
-        self.model.eval()
-        with torch.cuda.device(self.device):
-            stream = _native.current_stream(self.device)
-            batch = self._sensitivity_launches(src, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, targets_dev, T,
-                                               available, False)
-            J = self._scratch("map", (C * T, K))
-            plans = self._sensitivity_plans(S * T)
-            for s0 in range(0, S, C):                               # (s0 * T is a multiple of bs: a chunk starts a batch)
-                c = min(C, S - s0)
-                for off in range(0, c * T, bs):
-                    g = min(bs, c * T - off)
-                    batch(plans[g], s0 * T + off, g, J, C * T, off)
-                _native.check(lib.gatres_sensitivity_fold(J.data_ptr(), c, T, K, K, table.data_ptr(), int(s0 > 0), stream),
-                              "gatres_sensitivity_fold")
+        lib, stream, J = _native.load(), _native.current_stream(self.device), self._scratch("map", (C * T, K))
+
+        def fold(s0, c):
+            _native.check(lib.gatres_sensitivity_fold(J.data_ptr(), c, T, K, K, table.data_ptr(), int(s0 > 0), stream),
+                          "gatres_sensitivity_fold")
+
+        self._pair_pass(S, T, C, self._sensitivity_launches(src, _native.OBSERVED_FULL_ROWS, _native.NORMALISE_NONE, targets_dev,
+                                                            T, available, False, J), fold)
         return SensitivityMap(table, nodes, self.observed_idx, S)
 
     def influence_report(self, store_or_map, **kw) -> Dict[str, object]:
@@ -1434,33 +1458,37 @@ class PressureEstimator:
             self._loo_layouts = torch.from_numpy(loo_layouts(K)).to(self.device)
         return K
 
+    def _working_available(self, name: str, S: int, available: Optional[torch.Tensor]) -> torch.Tensor:
+        """The availability the rounds of a screening or monitoring call take readings out of: the scratch ``name`` (uint8
+        ``[S, K]``), set to ``available`` (``None``: every reading is there)."""
+        avail = self._scratch(name, (S, len(self.observed_idx)), torch.uint8)
+        if available is None:
+            avail.fill_(1)
+        else:
+            avail.copy_(available)
+        return avail
+
     def _run_loo(self, src: torch.Tensor, layout: int, normalise: int, available, nan_is_missing: bool, resid: torch.Tensor,
                  pred: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """The leave-one-out pass over the S * K (snapshot, left-out sensor) pairs of ``src`` into ``resid`` / ``pred``
         (``[S, K]``): per batch ``gatres_stage_observed_layouts`` under the layouts "all ones, zero diagonal", the forward,
         ``gatres_loo_residuals``."""
-        S, N, K, bs = int(src.shape[0]), self.nodes_per_graph, len(self.observed_idx), self.batch_size
-        lib, flat, layouts = _native.load(), self.model.flat_parameters, self._loo_layouts
-        if flat.device != self.device:
-            raise ValueError(f"the model moved to {flat.device}; the estimator was built on {self.device}")
-        factor = self.std + self.eps if self.norm_type == "znorm" else 1.0
-        nan = int(bool(nan_is_missing))
-        self.model.eval()
-        with torch.cuda.device(self.device):
-            stream = _native.current_stream(self.device)
-            plans = self._sensitivity_plans(S * K)
-            for first in range(0, S * K, bs):
-                g = min(bs, S * K - first)
-                P = plans[g]
-                _native.check(lib.gatres_stage_observed_layouts(
-                    src.data_ptr(), layout, S, first, K, N, g, self._observed.data_ptr(), K, normalise, self.offset, factor,
-                    P.x.data_ptr(), P.mask.data_ptr(), _native.ptr(available), nan, layouts.data_ptr(), stream),
-                    "gatres_stage_observed_layouts")
-                _enqueue_forward(lib, flat, P, stream)
-                _native.check(lib.gatres_loo_residuals(
-                    P.out.data_ptr(), P.mask.data_ptr(), src.data_ptr(), layout, S, first, N, g, self._observed.data_ptr(), K,
-                    self.scale, self.offset, _native.ptr(available), nan, pred.data_ptr(), resid.data_ptr(), stream),
-                    "gatres_loo_residuals")
+        S, N, K = int(src.shape[0]), self.nodes_per_graph, len(self.observed_idx)
+        lib, flat, stream, check = _native.load(), self._parameters(), _native.current_stream(self.device), _native.check
+        stage, residuals, nan = lib.gatres_stage_observed_layouts, lib.gatres_loo_residuals, int(bool(nan_is_missing))
+        tail, observed_p, scale, offset = self._staging_tail(normalise), self._observed.data_ptr(), self.scale, self.offset
+        src_p, avail_p, layouts_p = src.data_ptr(), _native.ptr(available), self._loo_layouts.data_ptr()
+        pred_p, resid_p = pred.data_ptr(), resid.data_ptr()
+
+        def batch(P, first, g, off):
+            mask = P.mask.data_ptr()
+            check(stage(src_p, layout, S, first, K, N, g, *tail, P.x.data_ptr(), mask, avail_p, nan, layouts_p, stream),
+                  "gatres_stage_observed_layouts")
+            _enqueue_forward(lib, flat, P, stream)
+            check(residuals(P.out.data_ptr(), mask, src_p, layout, S, first, N, g, observed_p, K, scale, offset, avail_p, nan,
+                            pred_p, resid_p, stream), "gatres_loo_residuals")
+
+        self._pair_pass(S, K, None, batch)
         return resid, pred
 
     def loo_residuals(self, readings: torch.Tensor, *, available: Optional[torch.Tensor] = None,
@@ -1469,8 +1497,7 @@ class PressureEstimator:
         ``pred[s, k]`` is the model's prediction at node ``observed_idx[k]`` from every reading of snapshot ``s`` but that one,
         ``resid[s, k] = readings[s, k] - pred[s, k]``.  ``readings``, ``available``, ``nan_is_missing`` as in ``estimate``; a
         reading that is not there has a NaN residual (its ``pred`` is still the prediction from the others).  The numbers are
-        those of ``reading_residuals``, bit for bit, from ONE pass: the S * K (snapshot, left-out sensor) pairs, snapshot-major,
-        are cut into batches of ``batch_size`` once, from pair 0 (a batch may straddle snapshots, the last may be ragged), three
+        those of ``reading_residuals``, bit for bit, from ONE pass over the S * K (snapshot, left-out sensor) pairs, three
         launches per batch -- ``gatres_stage_observed_layouts`` with the layouts "all ones, zero diagonal", the forward,
         ``gatres_loo_residuals``.  No ``[S, N]`` matrix is written, nothing is read back, and the two results are a scratch
         kept on the estimator: nothing is allocated after the first call, and the next call of this method overwrites them
@@ -1555,14 +1582,10 @@ class PressureEstimator:
         if available is not None:
             self._check_available(available, S)
         bound, inv = bounds.bounds[qi], bounds.inverse[qi]
-        avail = self._scratch("screen_available", (S, K), torch.uint8)
+        avail = self._working_available("screen_available", S, available)
         rejected = self._scratch("screen_rejected", (S, R), torch.int32)
         resid0, flagged0 = self._scratch("screen_resid0", (S, K)), self._scratch("screen_flagged0", (S, K), torch.uint8)
         later, pred = (self._scratch("screen_resid", (S, K)) if R > 1 else None), self._scratch("screen_pred", (S, K))
-        if available is None:
-            avail.fill_(1)
-        else:
-            avail.copy_(available)
         lib = _native.load()
         for rnd in range(R):
             resid = resid0 if rnd == 0 else later
@@ -1620,28 +1643,16 @@ class PressureEstimator:
         faulted = (readings + plan[0]).contiguous()
         without = (plan[1] == 0).to(torch.uint8).contiguous()
         est = torch.empty((S, N), dtype=torch.float32, device=self.device)
-        lib = _native.load()
-
-        def judged(extra=None):                                     # (one read-back: the moments, and the rejections behind them)
-            table = torch.empty((N, NODE_ERROR_RECORD), dtype=torch.float64, device=self.device)
-            with torch.cuda.device(self.device):
-                _native.check(lib.gatres_node_error_moments(
-                    est.data_ptr(), store.data.data_ptr(), S, N, self.scale, self.offset, self._observed.data_ptr(), K,
-                    table.data_ptr(), _native.current_stream(self.device)), "gatres_node_error_moments")
-            flat = table.reshape(-1) if extra is None else torch.cat([table.reshape(-1), extra.reshape(-1).to(torch.float64)])
-            host = flat.cpu().numpy()
-            return float(error_map_from_moments(host[:N * NODE_ERROR_RECORD])["hidden_mae"]), host[N * NODE_ERROR_RECORD:]
-
         mae = {}
         self.estimate(readings, est)
-        mae["clean"], _ = judged()
+        mae["clean"], _ = self._judged(store, est)
         self.estimate(faulted, est)
-        mae["faulted"], _ = judged()
+        mae["faulted"], _ = self._judged(store, est)
         _, rejected = self.estimate_screened(faulted, bounds, level, out=est, max_reject=max_reject)
-        mae["screened"], rej = judged(rejected)
-        rej = rej.astype(np.int64).reshape(S, int(max_reject))
+        mae["screened"], rej = self._judged(store, est, (rejected,))
+        rej = rej.reshape(S, int(max_reject)).copy()
         self.estimate(faulted, est, available=without)
-        mae["oracle"], _ = judged()
+        mae["oracle"], _ = self._judged(store, est)
         return {**screening_rates(rej, fault_col), "nonsensor_mae": mae, "fault_col": fault_col, "rejected": rej}
 
     # ---- monitoring: a sensor that drifts --------------------------------------------------------------------------------------
@@ -1656,20 +1667,8 @@ class PressureEstimator:
         S, K = len(store), len(self.observed_idx)
         truth = store.data.index_select(1, self._observed).contiguous()          # (scaled: the launch descales it as the pass did)
         sensors = torch.arange(K, dtype=torch.int32, device=self.device)
-        table = torch.empty((K, NODE_ERROR_RECORD), dtype=torch.float64, device=self.device)
-        lib = _native.load()
-        with torch.cuda.device(self.device):
-            stream = _native.current_stream(self.device)
-            if available is None:
-                _native.check(lib.gatres_node_error_moments(
-                    pred.data_ptr(), truth.data_ptr(), S, K, self.scale, self.offset, sensors.data_ptr(), K, table.data_ptr(),
-                    stream), "gatres_node_error_moments")
-            else:
-                missing = (available == 0).to(torch.uint8)               # (counted there: unless that entry is non-zero)
-                _native.check(lib.gatres_node_error_moments_available(
-                    pred.data_ptr(), truth.data_ptr(), S, K, self.scale, self.offset, sensors.data_ptr(), K, missing.data_ptr(),
-                    table.data_ptr(), stream), "gatres_node_error_moments_available")
-        b = monitor_baseline_from_moments(table.cpu().numpy())
+        missing = None if available is None else (available == 0).to(torch.uint8)  # (counted: unless that entry is non-zero)
+        b = monitor_baseline_from_moments(self._error_moments(pred, truth, S, K, sensors, missing).cpu().numpy())
         return MonitorBaseline(b["mu"], b["sigma"], b["counts"], self.observed_idx, device=self.device)
 
     def _check_monitor(self, baseline, S: int, kappa, threshold, series_length, first_index, max_latch, min_sensors, since,
@@ -1716,7 +1715,7 @@ class PressureEstimator:
         if available is not None:
             self._check_available(available, S)
         i64, rec = torch.int64, _native.CUSUM_RECORD
-        avail = self._scratch("monitor_available", (S, K), torch.uint8)
+        avail = self._working_available("monitor_available", S, available)
         latched = self._scratch("monitor_latched", (E, R), torch.int32)
         latched_rec = self._scratch("monitor_latched_rec", (E, R, rec), i64)
         records0 = self._scratch("monitor_records0", (E, K, rec), i64)
@@ -1729,10 +1728,6 @@ class PressureEstimator:
         if state is not None:                                       # (every round starts from it; it may be `state_out` itself)
             state_in = self._scratch("monitor_state_in", (E, K, _native.CUSUM_STATE), i64)
             state_in.copy_(state)
-        if available is None:
-            avail.fill_(1)
-        else:
-            avail.copy_(available)
         lib = _native.load()
         for rnd in range(R):
             # (round 0 of complete readings is the pass without an availability: the same bits, nothing to load per pair)
@@ -1832,32 +1827,18 @@ class PressureEstimator:
         drifted = (readings + torch.from_numpy(offsets).to(self.device)).contiguous()
         without = torch.from_numpy(without).to(self.device)
         est = torch.empty((S, N), dtype=torch.float32, device=self.device)
-        lib = _native.load()
-
-        def judged(extra=()):                                       # (one read-back: the moments, and the latches behind them)
-            table = torch.empty((N, NODE_ERROR_RECORD), dtype=torch.float64, device=self.device)
-            with torch.cuda.device(self.device):
-                _native.check(lib.gatres_node_error_moments(
-                    est.data_ptr(), store.data.data_ptr(), S, N, self.scale, self.offset, self._observed.data_ptr(), K,
-                    table.data_ptr(), _native.current_stream(self.device)), "gatres_node_error_moments")
-            # (the integers travel as the bits of doubles: exact at any size)
-            flat = torch.cat([table.reshape(-1)] + [t.to(torch.int64).reshape(-1).view(torch.float64) for t in extra])
-            host = flat.cpu().numpy()
-            return (float(error_map_from_moments(host[:N * NODE_ERROR_RECORD])["hidden_mae"]),
-                    host[N * NODE_ERROR_RECORD:].view(np.int64))
-
         mae = {}
         self.estimate(readings, est)
-        mae["clean"], _ = judged()
+        mae["clean"], _ = self._judged(store, est)
         self.estimate(drifted, est)
-        mae["drifted"], _ = judged()
+        mae["drifted"], _ = self._judged(store, est)
         _, res = self.estimate_monitored(drifted, baseline, out=est, kappa=kappa, threshold=threshold, series_length=T,
                                          max_latch=max_latch, min_sensors=min_sensors, since=since)
-        mae["monitored"], ints = judged((res.latched, res.latched_rec))
+        mae["monitored"], ints = self._judged(store, est, (res.latched, res.latched_rec))
         latched = ints[:E * R].reshape(E, R).copy()
         latched_rec = ints[E * R:].reshape(E, R, _native.CUSUM_RECORD).copy()
         self.estimate(drifted, est, available=without)
-        mae["oracle"], _ = judged()
+        mae["oracle"], _ = self._judged(store, est)
         return {**monitoring_rates(latched_rec, latched, draws), "nonsensor_mae": mae, "draws": draws, "latched": latched,
                 "latched_rec": latched_rec}
 

@@ -393,6 +393,26 @@ def test_ensemble_on_raw_readings_equals_the_store_form(pkg, lib, oracle):
         assert (a[1][1] == 0).all()                                 # the snapshot without any reading: every member the same
 
 
+def test_ensemble_in_three_chunks_equals_the_ensemble_in_one(pkg, oracle):
+    """S = 5 snapshots of M = 6 members at batch size 4: the 30 pairs fall as seven batches of 4 and a ragged 2, a snapshot's
+    members straddle batches, and a chunk is a multiple of lcm(4, 6) / 6 = 2 snapshots -- the smallest budget gives the chunks
+    2, 2 and 1, the last one short.  The bits are those of the pass in one chunk, in both forms."""
+    M6 = 6
+    store = make_store(pkg, S5)
+    model, _ = small_model(pkg, oracle)
+    est = pkg.PressureEstimator.for_store(model, store, OBS, batch_size=BS4)
+    readings = raw_snapshots(pkg, S5).to(DEV)[:, OBS].contiguous()
+    assert pkg.estimation.ensemble_chunk(S5, M6, BS4, 4 * N37, 1) == 2
+    assert pkg.estimation.ensemble_chunk(S5, M6, BS4, 4 * N37, 1 << 40) == S5
+    av = avail(AVAIL5)
+    for run in (lambda budget: est.estimate_store_ensemble(store, SIGMA[3], M6, seed=SEED, max_scratch_bytes=budget),
+                lambda budget: est.estimate_ensemble(readings, SIGMA[3], M6, seed=SEED, available=av, max_scratch_bytes=budget)):
+        mean, sd = run(1 << 40)
+        m3, s3 = run(1)
+        assert torch.equal(m3, mean) and torch.equal(s3, sd)
+        assert torch.isfinite(mean).all() and float(sd.max()) > 0
+
+
 def test_without_noise_the_ensemble_is_the_plain_pass(pkg, oracle):
     store = make_store(pkg, S5)
     model, _ = small_model(pkg, oracle)
