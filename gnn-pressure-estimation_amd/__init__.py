@@ -15,9 +15,11 @@ from .estimation import (ErrorBounds, MonitorBaseline, MonitorResult, PressureEs
 from .screening import fault_draws, loo_layouts, loo_residuals_from_estimates, screen_ref, screen_reject_ref, screening_rates
 from .monitoring import (cusum_compose, cusum_fixed, cusum_scan_ref, drift_draws, drift_offsets, monitor_baseline_from_moments,
                          monitor_latch_ref, monitor_ref, monitoring_rates)
-from .hydraulics import (HydraulicNetwork, HydraulicResult, HydraulicSeriesResult, hydraulic_draws, hydraulic_residuals,
-                         level_update_ref, pipe_headloss, series_report, series_valid_ref, series_volume_balance,
+from .hydraulics import (HydraulicLinksResult, HydraulicNetwork, HydraulicResult, HydraulicSeriesLinksResult, HydraulicSeriesResult,
+                         hydraulic_draws, hydraulic_link_draws, hydraulic_residuals, level_update_ref, link_headloss, link_state_ref, pipe_headloss,
+                         pump_curve_from_points, series_report, series_valid_ref, series_volume_balance,
                          simulate_series_ref, solve_ref, tree_solution)
+from .wdn_io import parse_inp_hydraulics
 from .sensitivity import (influence_from_table, linear_spread_ref, sensitivity_fold_ref, sensitivity_rows_from_gx,
                           sensitivity_seeds)
 
@@ -31,4 +33,6 @@ __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "Simpl
            "monitoring", "cusum_scan_ref", "cusum_fixed", "cusum_compose", "monitor_latch_ref", "monitor_ref",
            "monitor_baseline_from_moments", "drift_draws", "drift_offsets", "monitoring_rates", "hydraulics", "HydraulicNetwork",
            "HydraulicResult", "pipe_headloss", "solve_ref", "hydraulic_residuals", "hydraulic_draws", "tree_solution", "HydraulicSeriesResult",
-           "simulate_series_ref", "level_update_ref", "series_valid_ref", "series_report", "series_volume_balance"]
+           "simulate_series_ref", "level_update_ref", "series_valid_ref", "series_report", "series_volume_balance",
+           "HydraulicLinksResult", "HydraulicSeriesLinksResult", "link_headloss", "link_state_ref", "pump_curve_from_points",
+           "hydraulic_link_draws", "parse_inp_hydraulics"]

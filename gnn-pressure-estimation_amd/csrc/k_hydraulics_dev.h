@@ -1,5 +1,6 @@
 // The hydraulic Newton loop, stated once for the two kernels of k_hydraulics.hip (hydraulic_solve_kernel: one steady scenario per
-// workgroup; hydraulic_series_kernel: one series of steps per workgroup).  gatres.h states the model, the law at low flow and the
+// workgroup; hydraulic_series_kernel: one series of steps per workgroup) and their two counterparts with pumps, check valves,
+// closed links and minor losses in k_hydraulic_links.hip.  gatres.h states the model, the law at low flow, the link law and the
 // solver.  Everything here works on one workgroup's LDS arrays; every sum runs in a fixed order.
 #pragma once
 #include "gatres_common.h"
@@ -26,6 +27,46 @@ __device__ __forceinline__ void pipe_headloss(double q, double r, double* h, dou
   *g = gg;
 }
 
+// THE LINK LAW of gatres.h (pumps, check valves, closed links, minor losses), link_headloss of hydraulics.py.  code: HY_PUMP,
+// HY_CHECK (set for every pump), HY_SHUT (shut in this scenario or step: by the static flag HY_CLOSED, by the scenario's byte
+// or by a pump speed of zero); pump: the pump's {h0, rp, n, w^2, w^(2-n), w}, read where HY_PUMP is set and HY_SHUT is not.
+// With code 0 and m = 0 it is pipe_headloss in every bit: ra + 0 is ra, and 1.852 ra + 0 is 1.852 ra.
+constexpr int HY_PUMP = 1, HY_CHECK = 2, HY_SHUT = 4, HY_CLOSED = 8;
+constexpr int HY_PUMP_SHIFT = 4;                           // a link's code holds its pump's index above the four bits
+constexpr int HY_PUMP_REC = 6;                             // doubles of a pump's record
+constexpr double HY_SHUT_G = 1e8;                          // the gradient of a shut link and of a CHECK link's reverse branch
+
+__device__ __forceinline__ void link_headloss(double q, double r, double m, int code, const double* pump, double* h, double* g) {
+  if (code & HY_SHUT) {
+    *g = HY_SHUT_G;
+    *h = HY_SHUT_G * q;
+    return;
+  }
+  double lift = 0.0;                                       // -h(0): w^2 h0 of a pump
+  if (code & HY_PUMP) lift = pump[3] * pump[0];
+  if ((code & HY_CHECK) && q < 0.0) {
+    *g = HY_SHUT_G;
+    *h = HY_SHUT_G * q - lift;
+    return;
+  }
+  double gg, hh;
+  if (code & HY_PUMP) {
+    const double n = pump[2], ca = (pump[4] * pump[1]) * pow(q, n - 1.0);      // (q >= 0 here; pow(0, 0) is 1)
+    gg = n * ca;
+    hh = ca * q;
+  } else {
+    const double aq = fabs(q), ra = r * pow(aq, 0.852), ma = m * aq;
+    gg = 1.852 * ra + 2.0 * ma;
+    hh = (ra + ma) * q;
+  }
+  if (gg < HY_LINEAR_G) {
+    gg = HY_LINEAR_G;
+    hh = HY_LINEAR_G * q;
+  }
+  *h = hh - lift;
+  *g = gg;
+}
+
 // The LDS arrays of the Newton loop (a workgroup's own; the kernels lay them out)
 struct HyLds {
   double* band;                                            // [N][W + 1]: band[r * BW + k] = A[r][r - k], rows in solver order
@@ -38,6 +79,10 @@ struct HyLds {
   double* red;                                             // [4] the two sums of the stop rule
   int *sa, *sb;                                            // [P] solver rows of a pipe's ends
   int* fx;                                                 // [N] fixed flag by solver row
+  // the link law's arrays (hy_newton<true> alone reads them; the pipe-only kernels leave them out)
+  double* minor = nullptr;                                 // [P] minor-loss coefficient m_p
+  double* pump = nullptr;                                  // [Kp][HY_PUMP_REC] h0, rp, n, w^2, w^(2-n), w
+  int* code = nullptr;                                     // [P] HY_PUMP | HY_CHECK | HY_SHUT | HY_CLOSED | pump index << HY_PUMP_SHIFT
 };
 
 // The static arrays of a launch, checked: nothing in the kernels indexes with a value that was not checked here.  Fills L.fx,
@@ -89,7 +134,9 @@ struct HyNewton {
 
 // The whole Newton loop of one scenario, run by all HY_T threads of the workgroup.  position: node -> solver row (checked by the
 // caller); dem: the demands by node, in global memory or in LDS.  The caller has put a barrier behind its writes to L; the loop
-// ends behind a barrier or with values that are the same in every thread.
+// ends behind a barrier or with values that are the same in every thread.  LINKS chooses the law at compile time: pipe_headloss
+// (the default: the loop the pipe-only kernels have always had) or link_headloss; nothing else differs.
+template <bool LINKS = false>
 __device__ __forceinline__ HyNewton hy_newton(const HyLds& L, const int* __restrict__ position, const double* dem, int N, int P,
                                               int W, int max_iter, double accuracy, int tid) {
   const int BW = W + 1;
@@ -105,7 +152,12 @@ __device__ __forceinline__ HyNewton hy_newton(const HyLds& L, const int* __restr
     // the law at the present flows
     for (int p = tid; p < P; p += HY_T) {
       double h, g;
-      pipe_headloss(q[p], rr[p], &h, &g);
+      if constexpr (LINKS) {
+        const int code = L.code[p];
+        link_headloss(q[p], rr[p], L.minor[p], code, L.pump + (size_t)(code >> HY_PUMP_SHIFT) * HY_PUMP_REC, &h, &g);
+      } else {
+        pipe_headloss(q[p], rr[p], &h, &g);
+      }
       pinv[p] = 1.0 / g;
       yv[p] = h / g;
     }

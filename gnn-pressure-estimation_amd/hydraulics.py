@@ -15,8 +15,25 @@ and at every junction inflow - outflow = demand.  At low flow the law is EPANET'
 g = 1.852 r |q|^0.852 falls below 1e-7, g = 1e-7 and h = 1e-7 q.  The solver is Newton's method in the global-gradient form of
 Todini & Pilati, as in EPANET: per iteration one symmetric positive definite solve ``A H = F`` over the junctions
 (A_ii = sum 1/g_p, A_ij = -1/g_p), then q <- q - (h - (H_a - H_b)) / g; flows start at 1 ft/s; it stops once
-sum |dq| <= accuracy * sum |q|, or after ``max_iter`` iterations.  Pumps, valves, minor losses, controls and rules are not
-modelled.
+sum |dq| <= accuracy * sum |q|, or after ``max_iter`` iterations.
+
+THE LINK LAW (gatres.h: THE LINK LAW; csrc/k_hydraulic_links.hip; ``link_headloss``).  A network built with ``minor_loss``,
+``check_valve``, ``closed`` or ``pump_links`` takes the two links launches, which differ from the pipe launches in the law alone.
+Every link has a kind, PIPE = 0 or PUMP = 1, and flags CHECK (flow only from a to b) and CLOSED; a pump is always CHECK.
+PIPE, forward branch: h = r |q|^0.852 q + m |q| q, g = 1.852 r |q|^0.852 + 2 m |q|, with m = 8 K / (pi^2 * 9.80665 * D^4) from the
+minor-loss coefficient K; m = 0 is the pipe above in every bit; r = 0 (length 0) with m > 0 is a throttle valve (EPANET's TCV);
+where g < 1e-7: g = 1e-7, h = 1e-7 q.  PUMP, forward branch (q >= 0), at speed w with shut-off head h0 >= 0, coefficient rp > 0 and
+exponent n >= 1: the gain is w^2 h0 - w^(2-n) rp q^n (the affinity laws), so h = -w^2 h0 + w^(2-n) rp q^n and
+g = n w^(2-n) rp q^(n-1); where g < 1e-7: g = 1e-7, h = -w^2 h0 + 1e-7 q.  REVERSE BRANCH of a CHECK link (q < 0): g = 1e8,
+h = h(0) + 1e8 q, h(0) = 0 for a pipe and -w^2 h0 for a pump.  A CLOSED link (by its flag or by ``link_closed``) or a pump with
+w == 0: g = 1e8, h = 1e8 q at every q, and it starts at q = 0.  The law is continuous and monotone up to the jump at the low-flow
+floor, so the system stays symmetric positive definite.  There is no status machine: a link that holds shut carries -dh / 1e8.
+``link_state`` (uint8, at the returned flows): 0 forward, 1 a CHECK link on its reverse branch, 2 shut by input or by w == 0.
+A link runs from the lower-numbered node to the higher one unless ``link_reversed`` says otherwise.  WHAT DOES NOT HOLD: a zone
+that CHECK or shut links cut off from every fixed-head node gets heads near -1e8 x demand and usually does not meet the stop
+rule; the constructor refuses a network in which that is so statically, and a scenario in which ``link_closed`` or a speed of 0
+causes it is not converged and is dropped by ``valid``, never repaired.  Pressure-regulating valves (PRV, PSV, PBV, FCV, GPV),
+power-rated pumps, controls and rules stay out of scope.  Parity with EPANET is not claimed and has not been checked.
 
 THE SERIES (``simulate_series``, ``generate_series_store``; gatres.h: THE SERIES): extended-period simulation, T steps of
 ``step_seconds`` of one scenario in one launch, one workgroup per series.  Tanks are a subset of the fixed-head nodes: tank k
@@ -34,7 +51,7 @@ no failure and the series goes on from its flows.
 WHAT DOES NOT HOLD IN A SERIES: EPANET shortens a time step at the moment a tank becomes full or empty and closes the pipes of
 such a tank; this model clamps the level and does neither.  A step after which any level was clamped has status[s][t][3] = 1
 (``limited``), and volume is not conserved across such a step; ``series_valid`` and ``generate_series_store`` drop such series
-unless told otherwise.  Pumps, valves, minor losses, controls and rules stay out of scope.  The limit on flows that should be
+unless told otherwise.  Regulating valves, controls and rules stay out of scope.  The limit on flows that should be
 zero (below) carries over unchanged: a step with a zero multiplier will not meet the stop rule.
 
 WHAT DOES NOT HOLD: flows that should be zero do not come to rest on the linear branch.  A head of 100 m resolves 1.4e-14 m
@@ -49,8 +66,8 @@ the default does not (``DEMAND_RANGE`` starts at 0: its draws are positive with 
 the order of the upper end).
 
 Host restatements in numpy fp64 (the yardsticks of the tests): ``pipe_headloss``, ``solve_ref``, ``hydraulic_residuals``,
-``hydraulic_draws``, ``tree_solution``, ``simulate_series_ref``, ``level_update_ref``, ``series_valid_ref`` and
-``series_volume_balance``.
+``hydraulic_draws``, ``tree_solution``, ``simulate_series_ref``, ``level_update_ref``, ``series_valid_ref``,
+``series_volume_balance``, ``link_headloss``, ``link_state_ref``, ``hydraulic_link_draws`` and ``pump_curve_from_points``.
 """
 from __future__ import annotations
 
@@ -67,6 +84,10 @@ HW_EXPONENT = 1.852
 HW_FACTOR = 10.667
 HW_DIAMETER_EXPONENT = 4.871
 LINEAR_GRADIENT = 1e-7                  # the law at low flow
+SHUT_GRADIENT = 1e8                     # the gradient of a shut link and of a CHECK link's reverse branch
+GRAVITY = 9.80665                       # m/s2, in m = 8 K / (pi^2 g D^4)
+LINK_PIPE, LINK_PUMP = 0, 1             # GATRES_HYD_PIPE, GATRES_HYD_PUMP
+LINK_CHECK, LINK_CLOSED = 1, 2          # GATRES_HYD_LINK_CHECK, GATRES_HYD_LINK_CLOSED
 START_VELOCITY = 0.3048                 # m/s: 1 ft/s, EPANET's starting flows
 ACCURACY = 1e-6
 MAX_ITER = 40
@@ -89,6 +110,11 @@ HydraulicResult = namedtuple("HydraulicResult", "pressure head flow iterations c
 HydraulicReference = namedtuple("HydraulicReference", "head flow iterations converged failed final_dq")
 HydraulicSeriesResult = namedtuple("HydraulicSeriesResult", "pressure head flow level iterations converged failed limited status final_dq")
 HydraulicSeriesReference = namedtuple("HydraulicSeriesReference", "head flow level iterations converged failed limited final_dq")
+# what a network with special links returns: the fields above, and link_state
+HydraulicLinksResult = namedtuple("HydraulicLinksResult", HydraulicResult._fields + ("link_state",))
+HydraulicLinksReference = namedtuple("HydraulicLinksReference", HydraulicReference._fields + ("link_state",))
+HydraulicSeriesLinksResult = namedtuple("HydraulicSeriesLinksResult", HydraulicSeriesResult._fields + ("link_state",))
+HydraulicSeriesLinksReference = namedtuple("HydraulicSeriesLinksReference", HydraulicSeriesReference._fields + ("link_state",))
 
 
 def pipe_headloss(q, r) -> Tuple[np.ndarray, np.ndarray]:
@@ -102,6 +128,75 @@ def pipe_headloss(q, r) -> Tuple[np.ndarray, np.ndarray]:
     g = np.where(low, LINEAR_GRADIENT, g)
     h = np.where(low, LINEAR_GRADIENT * q, h)
     return h, g
+
+
+def link_headloss(q, r, minor=0.0, pump=False, check=False, shut=False, h0=0.0, rp=1.0, n=1.0, speed=1.0) -> Tuple[np.ndarray, np.ndarray]:
+    """THE LINK LAW, elementwise with the kernel's operations: head loss h and gradient g at the flow q of a link with resistance
+    r and minor-loss term ``minor`` (m, not K); ``pump`` links have (h0, rp, n) and run at ``speed``; ``check`` links (every pump
+    is one) take the reverse branch at q < 0; ``shut`` links, and pumps at speed 0, are closed.  With the defaults it is
+    ``pipe_headloss`` in every bit."""
+    q, r, minor = np.asarray(q, dtype=np.float64), np.asarray(r, dtype=np.float64), np.asarray(minor, dtype=np.float64)
+    pump, check, shut = np.asarray(pump, dtype=bool), np.asarray(check, dtype=bool), np.asarray(shut, dtype=bool)
+    h0, rp, n, w = (np.asarray(v, dtype=np.float64) for v in (h0, rp, n, speed))
+    with np.errstate(all="ignore"):
+        aq = np.abs(q)
+        ra, ma = r * np.power(aq, 0.852), minor * aq
+        g = 1.852 * ra + 2.0 * ma
+        h = (ra + ma) * q
+        w2, w2n = w * w, np.where(w > 0, np.power(np.where(w > 0, w, 1.0), 2.0 - n), 0.0)
+        ca = (w2n * rp) * np.power(np.maximum(q, 0.0), n - 1.0)
+        g = np.where(pump, n * ca, g)
+        h = np.where(pump, ca * q, h)
+        low = g < LINEAR_GRADIENT
+        g = np.where(low, LINEAR_GRADIENT, g)
+        h = np.where(low, LINEAR_GRADIENT * q, h)
+        lift = np.where(pump, w2 * h0, 0.0)
+        h = h - lift
+        reverse = (check | pump) & (q < 0)
+        g = np.where(reverse, SHUT_GRADIENT, g)
+        h = np.where(reverse, SHUT_GRADIENT * q - lift, h)
+        closed = shut | (pump & (w == 0))
+        g = np.where(closed, SHUT_GRADIENT, g)
+        h = np.where(closed, SHUT_GRADIENT * q, h)
+    return h, g
+
+
+def link_state_ref(q, pump=False, check=False, shut=False, speed=1.0) -> np.ndarray:
+    """``link_state`` of gatres.h at the flows q: 0 forward, 1 a CHECK link on its reverse branch, 2 shut."""
+    q, pump = np.asarray(q, dtype=np.float64), np.asarray(pump, dtype=bool)
+    closed = np.asarray(shut, dtype=bool) | (pump & (np.asarray(speed, dtype=np.float64) == 0))
+    reverse = (np.asarray(check, dtype=bool) | pump) & (q < 0)
+    return np.where(closed, 2, np.where(reverse, 1, 0)).astype(np.uint8)
+
+
+def pump_curve_from_points(flows, heads) -> Tuple[float, float, float]:
+    """(h0, rp, n) of the head curve gain = h0 - rp q^n, EPANET's way.  One point (q_d, h_d): the shut-off head is 1.33 h_d and
+    the head is zero at 2 q_d, with n = 2 fitted through the three.  Three points (0, h0), (q1, h1), (q2, h2) with
+    h0 > h1 > h2 >= 0 and 0 < q1 < q2: the power fit n = ln((h0 - h2) / (h0 - h1)) / ln(q2 / q1), rp = (h0 - h1) / q1^n."""
+    q, h = np.asarray(flows, dtype=np.float64).reshape(-1), np.asarray(heads, dtype=np.float64).reshape(-1)
+    if q.shape != h.shape or q.size not in (1, 3) or not (np.isfinite(q).all() and np.isfinite(h).all()):
+        raise ValueError("a pump curve has one point or three, all finite")
+    if q.size == 1:
+        if not (q[0] > 0 and h[0] > 0):
+            raise ValueError("a single-point pump curve needs q > 0 and h > 0")
+        q, h = np.array([0.0, q[0], 2.0 * q[0]]), np.array([1.33 * h[0], h[0], 0.0])
+    if not (q[0] == 0 and 0 < q[1] < q[2] and h[0] > h[1] > h[2] >= 0):
+        raise ValueError("a three-point pump curve needs q = 0 < q1 < q2 and h0 > h1 > h2 >= 0")
+    n = float(np.log((h[0] - h[2]) / (h[0] - h[1])) / np.log(q[2] / q[1]))
+    if not (np.isfinite(n) and n >= 1.0):
+        raise ValueError(f"the pump curve's exponent {n} is below 1")
+    return float(h[0]), float((h[0] - h[1]) / q[1] ** n), n
+
+
+def links_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_pumps: int) -> int:
+    """What a workgroup of ``gatres_hydraulic_solve_links`` takes of the LDS (gatres.h states the same sum): a solve workgroup's
+    arrays, per link m and its code, per pump h0, rp, n, w^2, w^(2-n) and w."""
+    return lds_bytes(num_nodes, num_pipes, half_bandwidth) + 12 * num_pipes + 48 * num_pumps
+
+
+def series_links_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_tanks: int, num_pumps: int) -> int:
+    """What a workgroup of ``gatres_hydraulic_series_links`` takes of the LDS (gatres.h states the same sum)."""
+    return series_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_tanks) + 12 * num_pipes + 48 * num_pumps
 
 
 def lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int) -> int:
@@ -138,6 +233,30 @@ def hydraulic_draws(seed: int, first_scenario: int, num_scenarios: int, d_lo, d_
     demand = d_lo[None, :] + (d_hi - d_lo)[None, :] * u[:, :N]
     roughness = c_lo[None, :] + (c_hi - c_lo)[None, :] * u[:, N:]
     return demand, roughness
+
+
+def link_draw_ranges(c_lo, c_hi, num_pumps: int, pump_speed_range=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The roughness ranges [P] extended by the cells of the link draws, which come AFTER the N + P cells of a scenario (so the
+    demands and the roughness of a scenario are what they are without them): Kp cells for the pump speeds, uniform in
+    ``pump_speed_range`` (None: (1, 1)), then P cells uniform in [0, 1) that decide the closures."""
+    c_lo, c_hi = np.asarray(c_lo, dtype=np.float64), np.asarray(c_hi, dtype=np.float64)
+    w_lo, w_hi = (1.0, 1.0) if pump_speed_range is None else (float(pump_speed_range[0]), float(pump_speed_range[1]))
+    if not (np.isfinite(w_lo) and np.isfinite(w_hi) and 0 <= w_lo <= w_hi):
+        raise ValueError("pump_speed_range must be 0 <= lo <= hi, finite")
+    P = c_lo.shape[0]
+    return (np.concatenate([c_lo, np.full(num_pumps, w_lo), np.zeros(P)]), np.concatenate([c_hi, np.full(num_pumps, w_hi), np.ones(P)]))
+
+
+def hydraulic_link_draws(seed: int, first_scenario: int, num_scenarios: int, d_lo, d_hi, c_lo, c_hi, num_pumps: int,
+                         pump_speed_range=None, closed_probability: float = 0.0):
+    """What ``generate_store(pump_speed_range=, closed_probability=)`` draws, in numpy, bit for bit: (demand [S, N], roughness
+    [S, P], pump_speed [S, Kp], link_closed uint8 [S, P]); link p of a scenario is closed where its cell's uniform number is
+    below ``closed_probability``."""
+    P = np.asarray(c_lo).shape[0]
+    lo, hi = link_draw_ranges(c_lo, c_hi, num_pumps, pump_speed_range)
+    demand, cells = hydraulic_draws(seed, first_scenario, num_scenarios, d_lo, d_hi, lo, hi)
+    closed = (cells[:, P + num_pumps:] < float(closed_probability)).astype(np.uint8)
+    return demand, np.ascontiguousarray(cells[:, :P]), np.ascontiguousarray(cells[:, P:P + num_pumps]), closed
 
 
 def _half_bandwidth(pipes: np.ndarray, fixed: np.ndarray, position: np.ndarray) -> int:
@@ -197,7 +316,8 @@ class HydraulicNetwork:
 
     def __init__(self, edge_index, length, diameter, elevation, fixed_nodes: Sequence[int], fixed_head,
                  start_velocity: float = START_VELOCITY, device=None, tank_nodes=None, tank_diameter=None, tank_min_level=None,
-                 tank_max_level=None):
+                 tank_max_level=None, minor_loss=None, check_valve=None, closed=None, pump_links=None, pump_h0=None, pump_r=None,
+                 pump_n=None, pump_q_start=None, link_reversed=None):
         ei = torch.as_tensor(edge_index).detach().cpu()
         if ei.dim() != 2 or ei.shape[0] != 2 or ei.dtype != torch.int64:
             raise ValueError("edge_index must be int64 [2, E]")
@@ -219,7 +339,36 @@ class HydraulicNetwork:
         diameter = np.asarray(diameter, dtype=np.float64).reshape(-1)
         if length.shape[0] != P or diameter.shape[0] != P:
             raise ValueError(f"length and diameter must have one entry per pipe ({P})")
-        if not (np.isfinite(length).all() and (length > 0).all() and np.isfinite(diameter).all() and (diameter > 0).all()):
+        # the special links (THE LINK LAW): all absent by default, and then nothing below differs from a network of pipes
+        per_link = lambda v, dt: np.zeros(P, dtype=dt) if v is None else np.asarray(v, dtype=dt).reshape(-1)
+        minor_k = per_link(minor_loss, np.float64)
+        check = per_link(check_valve, bool)
+        shut = per_link(closed, bool)
+        flip = per_link(link_reversed, bool)
+        if not (minor_k.shape[0] == check.shape[0] == shut.shape[0] == flip.shape[0] == P):
+            raise ValueError(f"minor_loss, check_valve, closed and link_reversed must have one entry per link ({P})")
+        if not (np.isfinite(minor_k).all() and (minor_k >= 0).all()):
+            raise ValueError("minor-loss coefficients must be finite and not negative")
+        pumps = np.asarray([] if pump_links is None else pump_links, dtype=np.int64).reshape(-1)
+        Kp = int(pumps.size)
+        if Kp and (pumps.min() < 0 or pumps.max() >= P or np.unique(pumps).size != Kp):
+            raise ValueError("pump_links must be distinct links of the network")
+        p_h0 = np.asarray([] if pump_h0 is None else pump_h0, dtype=np.float64).reshape(-1)
+        p_r = np.asarray([] if pump_r is None else pump_r, dtype=np.float64).reshape(-1)
+        p_n = np.full(Kp, 2.0) if pump_n is None else np.asarray(pump_n, dtype=np.float64).reshape(-1)
+        if p_h0.shape[0] != Kp or p_r.shape[0] != Kp or p_n.shape[0] != Kp:
+            raise ValueError(f"pump_h0, pump_r and pump_n must have one entry per pump ({Kp})")
+        if not (np.isfinite(p_h0).all() and (p_h0 >= 0).all() and np.isfinite(p_r).all() and (p_r > 0).all()
+                and np.isfinite(p_n).all() and (p_n >= 1).all()):
+            raise ValueError("a pump needs h0 >= 0, r > 0 and n >= 1, all finite")
+        is_pump = np.zeros(P, dtype=bool)
+        is_pump[pumps] = True
+        if (minor_k[is_pump] != 0).any():
+            raise ValueError("a pump has no minor loss")
+        pipes[flip] = pipes[flip][:, ::-1]                  # a reversed link runs from its higher node to its lower one
+        throttle = (length == 0) & (minor_k > 0)            # r = 0 with m > 0: a throttle valve
+        if not (np.isfinite(length).all() and ((length > 0) | throttle | is_pump).all()
+                and np.isfinite(diameter).all() and (diameter > 0).all()):
             raise ValueError("lengths and diameters must be positive and finite")
         if not np.isfinite(elevation).all():
             raise ValueError("elevations must be finite")
@@ -233,9 +382,12 @@ class HydraulicNetwork:
         fixed[fixed_nodes] = True
         reach = fixed.copy()                                # every junction is fed from a fixed-head node
         adj = [[] for _ in range(N)]
-        for a, b in pipes:
+        for p, (a, b) in enumerate(pipes):                  # a CHECK link is walked from a to b only, a closed one not at all
+            if shut[p]:
+                continue
             adj[a].append(int(b))
-            adj[b].append(int(a))
+            if not (check[p] or is_pump[p]):
+                adj[b].append(int(a))
         stack = [int(v) for v in fixed_nodes]
         while stack:
             v = stack.pop()
@@ -279,6 +431,26 @@ class HydraulicNetwork:
         self.tank_area = np.pi * t_dia * t_dia / 4.0
         self.coef = HW_FACTOR * length / np.power(diameter, HW_DIAMETER_EXPONENT)
         self.q_start = float(start_velocity) * (np.pi * diameter * diameter / 4.0)
+        # the link arrays of gatres_hydraulic_solve_links
+        self.num_pumps, self.pump_links, self.pump_h0, self.pump_r, self.pump_n = Kp, pumps, p_h0, p_r, p_n
+        self.is_pump, self.check_valve, self.closed, self.minor_loss = is_pump, check | is_pump, shut, minor_k
+        self.link_kind = is_pump.astype(np.uint8) * LINK_PUMP
+        self.link_flags = (check.astype(np.uint8) * LINK_CHECK) | (shut.astype(np.uint8) * LINK_CLOSED)
+        self.minor = 8.0 * minor_k / (np.pi ** 2 * GRAVITY * np.power(diameter, 4))
+        self.has_links = bool(Kp or check.any() or shut.any() or (minor_k > 0).any())
+        if Kp:
+            self.coef[pumps] = 0.0                          # (a pump has no resistance; its coef is not read)
+            if pump_q_start is None:                        # the flow at which the gain is 3/4 of the shut-off head
+                q0 = np.power(p_h0 / (4.0 * p_r), 1.0 / p_n)
+            else:
+                q0 = np.asarray(pump_q_start, dtype=np.float64).reshape(-1)
+                if q0.shape[0] != Kp or not (np.isfinite(q0).all() and (q0 >= 0).all()):
+                    raise ValueError(f"pump_q_start must have one finite flow >= 0 per pump ({Kp})")
+            self.q_start[pumps] = q0
+        elif pump_q_start is not None and np.asarray(pump_q_start).size:
+            raise ValueError("pump_q_start needs pump_links")
+        self.pump_of_link = np.full(P, -1, dtype=np.int64)
+        self.pump_of_link[pumps] = np.arange(Kp)
         identity = np.arange(N, dtype=np.int32)
         rcm = _reverse_cuthill_mckee(N, pipes, fixed)
         rcm_pos = np.empty(N, dtype=np.int32)
@@ -288,9 +460,10 @@ class HydraulicNetwork:
         else:                                               # (the given order is already as narrow: keep it)
             self.order, self.position = identity, identity.copy()
         self.half_bandwidth = max(1, _half_bandwidth(pipes, fixed, self.position))
-        if lds_bytes(N, P, self.half_bandwidth) > LDS_BUDGET:
+        need = links_lds_bytes(N, P, self.half_bandwidth, Kp) if self.has_links else lds_bytes(N, P, self.half_bandwidth)
+        if need > LDS_BUDGET:
             raise ValueError(f"the band of {N} rows with half-bandwidth {self.half_bandwidth} needs "
-                             f"{lds_bytes(N, P, self.half_bandwidth)} bytes of LDS, the kernel has {LDS_BUDGET}")
+                             f"{need} bytes of LDS, the kernel has {LDS_BUDGET}")
         # the junction subgraph, renumbered: what a SnapshotStore over the junctions takes
         renum = np.full(N, -1, dtype=np.int64)
         renum[self.junctions] = np.arange(self.junctions.size)
@@ -301,6 +474,13 @@ class HydraulicNetwork:
         self.isolated_junctions = renum[np.flatnonzero(~fixed & ~has_edge)]      # indices INSIDE the junction graph
         self.device = torch.device(device) if device is not None else None
         self._static: Dict[str, torch.Tensor] = {}
+
+    @classmethod
+    def from_inp(cls, source=None, **kw) -> "HydraulicNetwork":
+        """The network of an EPANET input file: ``wdn_io.parse_inp_hydraulics(source, **kw).network`` (that function also returns
+        the base demands, the roughness, the patterns and the pump speeds of the file, and says what it reads and refuses)."""
+        from . import wdn_io
+        return wdn_io.parse_inp_hydraulics(source, **kw).network
 
     # ---- the device side ----------------------------------------------------------------------------------------------------------
     def _dev(self) -> torch.device:
@@ -327,6 +507,39 @@ class HydraulicNetwork:
                             "pattern0": torch.zeros(self.num_nodes, dtype=torch.int32, device=dev)}
         return self._static
 
+    def _link_args(self, S: int, state_shape, pump_speed, link_closed):
+        """The twelve link arguments of the two links launches (the static arrays are uploaded once), the ``link_state`` tensor
+        to fill, and the tensors of this call that the arguments point into: the caller holds them until the launch is queued."""
+        st, dev, P, Kp = self.static(), self._dev(), self.num_pipes, self.num_pumps
+        if "link_kind" not in st:
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+            st.update({"link_kind": up(self.link_kind, np.uint8), "link_flags": up(self.link_flags, np.uint8),
+                       "minor": up(self.minor, np.float64), "pump_link": up(self.pump_links, np.int32),
+                       "pump_h0": up(self.pump_h0, np.float64), "pump_r": up(self.pump_r, np.float64),
+                       "pump_n": up(self.pump_n, np.float64), "speed1": torch.ones(max(Kp, 1), dtype=torch.float64, device=dev)})
+        if pump_speed is None:
+            speed, speed_stride = st["speed1"], 0
+        else:
+            speed = torch.as_tensor(pump_speed, dtype=torch.float64).to(dev).contiguous()
+            if tuple(speed.shape) == (Kp,):
+                speed_stride = 0
+            elif tuple(speed.shape) == (S, Kp):
+                speed_stride = Kp
+            else:
+                raise ValueError(f"pump_speed must be [{Kp}] or [{S}, {Kp}]")
+        closed, closed_stride = None, 0
+        if link_closed is not None:
+            closed = torch.as_tensor(link_closed).to(device=dev, dtype=torch.uint8).contiguous()
+            if tuple(closed.shape) == (S, P):
+                closed_stride = P
+            elif tuple(closed.shape) != (P,):
+                raise ValueError(f"link_closed must be [{P}] or [{S}, {P}]")
+        link_state = torch.empty(state_shape, dtype=torch.uint8, device=dev)
+        pp = (lambda t: t.data_ptr()) if Kp else (lambda t: None)
+        return [st["link_kind"].data_ptr(), st["link_flags"].data_ptr(), st["minor"].data_ptr(), pp(st["pump_link"]),
+                pp(st["pump_h0"]), pp(st["pump_r"]), pp(st["pump_n"]), Kp, pp(speed), speed_stride, _native.ptr(closed),
+                closed_stride], link_state, (speed, closed)
+
     def _f64(self, a, shape, name) -> torch.Tensor:
         t = torch.as_tensor(a, dtype=torch.float64).to(self._dev()).contiguous()
         if tuple(t.shape) != tuple(shape):
@@ -345,12 +558,42 @@ class HydraulicNetwork:
         _native.check(rc, "gatres_hydraulic_draw")
         return demand, roughness
 
+    def draw_links(self, num_scenarios: int, seed: int, first_scenario: int, d_lo: torch.Tensor, d_hi: torch.Tensor,
+                   x_lo: torch.Tensor, x_hi: torch.Tensor, closed_probability: float):
+        """``gatres_hydraulic_draw`` over the N + P cells of a scenario and the Kp + P link cells after them (``x_lo``, ``x_hi``:
+        ``link_draw_ranges`` on the device): (demand [S, N], roughness [S, P], pump_speed [S, Kp], link_closed uint8 [S, P]).
+        ``hydraulic_link_draws`` restates it."""
+        dev, lib, P, Kp = self._dev(), _native.load(), self.num_pipes, self.num_pumps
+        demand = torch.empty((num_scenarios, self.num_nodes), dtype=torch.float64, device=dev)
+        cells = torch.empty((num_scenarios, 2 * P + Kp), dtype=torch.float64, device=dev)
+        rc = lib.gatres_hydraulic_draw(d_lo.data_ptr(), d_hi.data_ptr(), x_lo.data_ptr(), x_hi.data_ptr(), num_scenarios,
+                                       self.num_nodes, 2 * P + Kp, seed % (1 << 64), first_scenario, demand.data_ptr(),
+                                       cells.data_ptr(), _native.current_stream(dev))
+        _native.check(rc, "gatres_hydraulic_draw")
+        closed = (cells[:, P + Kp:] < float(closed_probability)).to(torch.uint8).contiguous()
+        return demand, cells[:, :P].contiguous(), cells[:, P:P + Kp].contiguous(), closed
+
+    def _link_draw_setup(self, ranges, pump_speed_range, closed_probability):
+        """None where a store is generated without link draws (the call it always was), else the device ranges of ``draw_links``."""
+        if pump_speed_range is None and not closed_probability:
+            return None
+        if not 0.0 <= float(closed_probability) < 1.0:
+            raise ValueError("closed_probability must lie in [0, 1)")
+        if pump_speed_range is not None and self.num_pumps == 0:
+            raise ValueError("pump_speed_range needs a network with pumps")
+        lo, hi = link_draw_ranges(ranges[2], ranges[3], self.num_pumps, pump_speed_range)
+        return torch.from_numpy(lo).to(self._dev()), torch.from_numpy(hi).to(self._dev())
+
     def simulate(self, demand, roughness, fixed_head=None, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
-                 want_head: bool = True, want_flow: bool = True) -> HydraulicResult:
+                 want_head: bool = True, want_flow: bool = True, pump_speed=None, link_closed=None, links=None) -> HydraulicResult:
         """Solve S scenarios on the device.  ``demand`` [S, N] m3/s (ignored at fixed nodes), ``roughness`` [S, P]
         Hazen-Williams coefficients, ``fixed_head`` None (the network's), [N] or [S, N] (read at fixed nodes).  Every field
-        of the result is a device tensor; nothing is read back."""
+        of the result is a device tensor; nothing is read back.  A network with a special link or a minor loss (or
+        ``pump_speed`` [Kp] / [S, Kp], default 1; ``link_closed`` bytes [P] / [S, P]; or ``links=True``) takes
+        ``gatres_hydraulic_solve_links`` and returns a ``HydraulicLinksResult``: the same fields and ``link_state`` uint8 [S, P].
+        A network of pipes takes ``gatres_hydraulic_solve`` as it always did."""
         st, dev, lib = self.static(), self._dev(), _native.load()
+        with_links = bool(links) if links is not None else (self.has_links or pump_speed is not None or link_closed is not None)
         N, P = self.num_nodes, self.num_pipes
         demand = torch.as_tensor(demand)
         if demand.dim() != 2:
@@ -375,6 +618,18 @@ class HydraulicNetwork:
         flow = torch.empty((S, P), dtype=torch.float64, device=dev) if want_flow else None
         status = torch.empty((S, HYD_STATUS), dtype=torch.int32, device=dev)
         final_dq = torch.empty((S,), dtype=torch.float64, device=dev)
+        if with_links:
+            link_args, link_state, _held = self._link_args(S, (S, P), pump_speed, link_closed)
+            rc = lib.gatres_hydraulic_solve_links(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
+                                                  st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
+                                                  st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
+                                                  demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P,
+                                                  float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head),
+                                                  _native.ptr(flow), status.data_ptr(), final_dq.data_ptr(), *link_args,
+                                                  link_state.data_ptr(), _native.current_stream(dev))
+            _native.check(rc, "gatres_hydraulic_solve_links")
+            return HydraulicLinksResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status, final_dq,
+                                        link_state)
         rc = lib.gatres_hydraulic_solve(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
                                         st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
                                         st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth, demand.data_ptr(),
@@ -399,15 +654,22 @@ class HydraulicNetwork:
     # ---- the series ---------------------------------------------------------------------------------------------------------------
     def simulate_series(self, demand, roughness, multipliers, *, step_seconds: float, initial_level=None, pattern_of_node=None,
                         fixed_head=None, warm_start: bool = True, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
-                        want_head: bool = True, want_flow: bool = True) -> HydraulicSeriesResult:
+                        want_head: bool = True, want_flow: bool = True, pump_speed=None, link_closed=None, speed_multipliers=None,
+                        speed_pattern_of_pump=None, links=None) -> HydraulicSeriesResult:
         """``gatres_hydraulic_series``: S series of T steps on the device, one launch.  ``demand`` [S, N] base demands,
         ``roughness`` [S, P], ``multipliers`` [M, T] (for every series) or [S, M, T], ``pattern_of_node`` int [N] with values in
         [0, M) (default: pattern 0 everywhere; host data outside the range raises ``ValueError``, a DEVICE tensor is not read back
         and a value outside the range makes the kernel fail every series of the launch), ``initial_level`` [S, K] or [K] (default: fixed_head - elevation at the tank
         nodes), ``fixed_head`` as in ``simulate``.  Every field of the result is a device tensor; nothing is read back:
         pressure [S, T, N] fp32, head [S, T, N], flow [S, T, P], level [S, T + 1, K], iterations / converged / failed / limited
-        [S, T], status [S, T, 4], final_dq [S, T].  A network without tanks works (K = 0: patterns only)."""
+        [S, T], status [S, T, 4], final_dq [S, T].  A network without tanks works (K = 0: patterns only).  A network with a
+        special link or a minor loss (or one of the link arguments, or ``links=True``) takes ``gatres_hydraulic_series_links`` and
+        returns a ``HydraulicSeriesLinksResult`` with ``link_state`` uint8 [S, T, P]: ``pump_speed`` and ``link_closed`` as in
+        ``simulate``, ``speed_multipliers`` [Ms, T] (default ones) and ``speed_pattern_of_pump`` int [Kp] (default 0); pump k
+        runs at pump_speed[s][k] * speed_multipliers[pattern][t] in step t, and 0 switches it off for that step."""
         st, dev, lib = self.static(), self._dev(), _native.load()
+        with_links = bool(links) if links is not None else (
+            self.has_links or any(v is not None for v in (pump_speed, link_closed, speed_multipliers, speed_pattern_of_pump)))
         N, P, K = self.num_nodes, self.num_pipes, self.num_tanks
         demand = torch.as_tensor(demand)
         if demand.dim() != 2:
@@ -466,6 +728,29 @@ class HydraulicNetwork:
         status = torch.empty((S, T, HYD_STATUS), dtype=torch.int32, device=dev)
         final_dq = torch.empty((S, T), dtype=torch.float64, device=dev)
         tp = (lambda t: t.data_ptr()) if K else (lambda t: None)
+        if with_links:
+            Kp = self.num_pumps
+            link_args, link_state, _held = self._link_args(S, (S, T, P), pump_speed, link_closed)
+            smult = torch.ones((1, T), dtype=torch.float64, device=dev) if speed_multipliers is None else \
+                torch.as_tensor(speed_multipliers, dtype=torch.float64).to(dev).contiguous()
+            if smult.dim() != 2 or smult.shape[0] < 1 or smult.shape[1] != T:
+                raise ValueError(f"speed_multipliers must be [Ms, {T}]")
+            spat = np.zeros(Kp, dtype=np.int64) if speed_pattern_of_pump is None else np.asarray(speed_pattern_of_pump, dtype=np.int64)
+            if spat.shape != (Kp,) or (Kp and (spat.min() < 0 or spat.max() >= smult.shape[0])):
+                raise ValueError(f"speed_pattern_of_pump must be [{Kp}] with values in [0, {int(smult.shape[0])})")
+            spat = torch.from_numpy(spat.astype(np.int32)).to(dev)
+            rc = lib.gatres_hydraulic_series_links(
+                st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
+                st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
+                self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
+                pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride,
+                tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0, float(accuracy), int(max_iter),
+                pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(level), status.data_ptr(), final_dq.data_ptr(),
+                *link_args, smult.data_ptr() if Kp else None, spat.data_ptr() if Kp else None, int(smult.shape[0]) if Kp else 0,
+                link_state.data_ptr(), _native.current_stream(dev))
+            _native.check(rc, "gatres_hydraulic_series_links")
+            return HydraulicSeriesLinksResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0, status[:, :, 2] != 0,
+                                              status[:, :, 3] != 0, status, final_dq, link_state)
         rc = lib.gatres_hydraulic_series(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
                                          st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
                                          st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
@@ -519,7 +804,8 @@ class HydraulicNetwork:
                               pattern_of_node=None, level_range=None, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE,
                               pressure_range: Tuple[float, float] = (0.0, 150.0), chunk: int = 256, normalize: bool = True,
                               allow_limited: bool = False, warm_start: bool = True, accuracy: float = ACCURACY,
-                              max_iter: int = MAX_ITER):
+                              max_iter: int = MAX_ITER, pump_speed_range=None, closed_probability: float = 0.0,
+                              speed_multipliers=None, speed_pattern_of_pump=None):
         """Draw, simulate and filter ``num_series`` series of ``steps`` steps into a ``SnapshotStore`` over the junctions whose
         rows are series-major (E * steps rows for E kept series: what ``monitor_store(series_length=steps)`` expects).  Base
         demands and roughness per series come from ``draw``, the initial levels from ``draw_levels``; ``multipliers`` default to
@@ -528,7 +814,8 @@ class HydraulicNetwork:
         ``(store, report)``; the report counts series: drawn = kept + failed + not_converged + limited + out_of_range, each dropped
         series counted once by the first cause in that order (``series_report``), and gives max_iterations, mean_iterations
         (over the steps that did not fail), mean_iterations_first_step and series_length.  ``RuntimeError`` when nothing is
-        kept."""
+        kept.  ``pump_speed_range`` and ``closed_probability`` as in ``generate_store``, per series (a closure holds for the whole
+        series); ``speed_multipliers`` and ``speed_pattern_of_pump`` go to ``simulate_series``."""
         if num_series < 1 or chunk < 1 or steps < 1:
             raise ValueError("num_series, steps and chunk must be positive")
         st, dev = self.static(), self._dev()
@@ -538,16 +825,25 @@ class HydraulicNetwork:
         mult = torch.as_tensor(multipliers, dtype=torch.float64).to(dev).contiguous()
         if mult.dim() != 2 or mult.shape[1] != steps:
             raise ValueError(f"multipliers must be [M, {steps}]")
-        ranges = [torch.from_numpy(a).to(dev) for a in self.draw_ranges(demand_range, roughness_range)]
+        host_ranges = self.draw_ranges(demand_range, roughness_range)
+        ranges = [torch.from_numpy(a).to(dev) for a in host_ranges]
+        link_ranges = self._link_draw_setup(host_ranges, pump_speed_range, closed_probability)
+        link_kw = {k: v for k, v in (("speed_multipliers", speed_multipliers), ("speed_pattern_of_pump", speed_pattern_of_pump))
+                   if v is not None}
         lv = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in self.level_ranges(level_range)]
         kept_rows, tables = [], []
         for first in range(0, num_series, chunk):
             n = min(chunk, num_series - first)
-            demand, roughness = self.draw(n, seed, first, *ranges)
+            if link_ranges is None:
+                demand, roughness = self.draw(n, seed, first, *ranges)
+            else:
+                demand, roughness, speed, closed = self.draw_links(n, seed, first, ranges[0], ranges[1], *link_ranges,
+                                                                   closed_probability)
+                link_kw.update(pump_speed=speed if self.num_pumps else None, link_closed=closed)
             level0 = self.draw_levels(n, seed, first, *lv)
             res = self.simulate_series(demand, roughness, mult, step_seconds=step_seconds, initial_level=level0,
                                        pattern_of_node=pattern_of_node, warm_start=warm_start, accuracy=accuracy,
-                                       max_iter=max_iter, want_head=False, want_flow=False)
+                                       max_iter=max_iter, want_head=False, want_flow=False, **link_kw)
             ok = self.series_valid(res, pressure_range, allow_limited)
             table = torch.cat([res.status.reshape(n, -1), ok.to(torch.int32)[:, None]], dim=1).cpu().numpy()     # the read-back
             tables.append(table)
@@ -576,26 +872,38 @@ class HydraulicNetwork:
 
     def generate_store(self, num_scenarios: int, seed: int, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE,
                        pressure_range: Tuple[float, float] = (0.0, 150.0), chunk: int = 1024, normalize: bool = True,
-                       accuracy: float = ACCURACY, max_iter: int = MAX_ITER):
+                       accuracy: float = ACCURACY, max_iter: int = MAX_ITER, pump_speed_range=None, closed_probability: float = 0.0):
         """Draw, solve and filter ``num_scenarios`` scenarios into a ``SnapshotStore`` over the junctions (pressures in metres
         before the store's normalisation).  Per chunk: draw -> solve -> valid, ONE read-back (status and the valid bytes as one
         tensor), a device ``index_select`` of the kept rows.  Returns ``(store, report)``; the report counts drawn, converged,
         failed, not_converged, out_of_range and kept scenarios (drawn = kept + out_of_range + not_converged + failed) and gives
         the maximum and the mean of the iterations over the scenarios that did not fail.  ``RuntimeError`` when nothing is
         kept.  Rows of all-zero or mostly-zero demand do not meet the ratio stop rule (the module's docstring says why) and
-        are counted as not_converged, not kept: watch that count when the demand range reaches down to zero."""
+        are counted as not_converged, not kept: watch that count when the demand range reaches down to zero.
+        ``pump_speed_range`` (lo, hi) draws a speed per scenario and pump, ``closed_probability`` closes every link of a scenario
+        with that probability (``draw_links``: new cells after the existing ones, so a call without the two gives the store it
+        always gave).  A scenario whose closures or check valves cut a zone off does not converge: it is counted as
+        not_converged, apart from out_of_range, and dropped, never repaired."""
         if num_scenarios < 1 or chunk < 1:
             raise ValueError("num_scenarios and chunk must be positive")
         st, dev = self.static(), self._dev()
-        ranges = [torch.from_numpy(a).to(dev) for a in self.draw_ranges(demand_range, roughness_range)]
+        host_ranges = self.draw_ranges(demand_range, roughness_range)
+        ranges = [torch.from_numpy(a).to(dev) for a in host_ranges]
+        link_ranges = self._link_draw_setup(host_ranges, pump_speed_range, closed_probability)
         kept_rows = []
         report = {"drawn": 0, "converged": 0, "failed": 0, "not_converged": 0, "out_of_range": 0, "kept": 0, "max_iterations": 0,
                   "mean_iterations": 0.0}
         iter_sum = 0
         for first in range(0, num_scenarios, chunk):
             n = min(chunk, num_scenarios - first)
-            demand, roughness = self.draw(n, seed, first, *ranges)
-            res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False)
+            if link_ranges is None:
+                demand, roughness = self.draw(n, seed, first, *ranges)
+                res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False)
+            else:
+                demand, roughness, speed, closed = self.draw_links(n, seed, first, ranges[0], ranges[1], *link_ranges,
+                                                                   closed_probability)
+                res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False,
+                                    pump_speed=speed if self.num_pumps else None, link_closed=closed)
             ok = self.valid(res, pressure_range)
             table = torch.cat([res.status[:, :3], ok.to(torch.int32)[:, None]], dim=1).cpu().numpy()     # the read-back
             rows = np.flatnonzero(table[:, 3])
@@ -652,17 +960,32 @@ class _NewtonRef:
         return bool(np.isfinite(d).all() and np.isfinite(hf).all() and np.isfinite(c).all() and (c > 0).all()
                     and np.isfinite(r).all() and (r > 0).all())
 
-    def run(self, d, hf, r, q_start):
+    def link_inputs_ok(self, d, hf, c, r, law) -> bool:
+        """``inputs_ok`` under THE LINK LAW: a pump's roughness is not read, r = 0 is allowed where m > 0, speeds are finite and
+        not negative (``law`` is None where a speed or a closed byte was refused)."""
+        if law is None:
+            return False
+        pipe = ~law["pump"]
+        w = law["speed"]
+        with np.errstate(all="ignore"):
+            w_ok = np.isfinite(w * w).all() and np.isfinite(np.power(np.where(w > 0, w, 1.0), 2.0 - law["n"])).all()
+        return bool(np.isfinite(d).all() and np.isfinite(hf).all() and np.isfinite(c[pipe]).all() and (c[pipe] > 0).all()
+                    and np.isfinite(r[pipe]).all() and (r[pipe] >= 0).all() and (law["minor"][pipe & (r == 0)] > 0).all() and w_ok)
+
+    def run(self, d, hf, r, q_start, law=None):
         """(H, q, iterations, converged, ok, rel) from the flows ``q_start``; d: demands (0 at fixed nodes), hf: fixed heads (0 at
-        junctions), r: resistances."""
+        junctions), r: resistances; ``law``: None for pipes, or the per-link arrays of ``link_headloss`` (a shut link then
+        starts at rest)."""
         N, P = self.net.num_nodes, self.net.num_pipes
         a, b, fixed, ja, jb, jj = self.a, self.b, self.fixed, self.ja, self.jb, self.jj
         q = q_start.copy()
+        if law is not None:
+            q[law["shut"] | (law["pump"] & (law["speed"] == 0))] = 0.0
         H = hf.copy()
         rel, ok, iterations, converged = 0.0, True, 0, False
         for it in range(1, self.max_iter + 1):
             iterations = it
-            h, g = pipe_headloss(q, r)
+            h, g = pipe_headloss(q, r) if law is None else link_headloss(q, r, **law)
             pinv, y = 1.0 / g, h / g
             t = q - y
             diag = np.zeros(N)
@@ -713,12 +1036,63 @@ class _NewtonRef:
         return H, q, iterations, converged, ok, rel
 
 
+def link_law(network: HydraulicNetwork, pump_speed=None, link_closed=None):
+    """The per-link arrays of ``link_headloss`` for one scenario: ``pump_speed`` [Kp] (default 1), ``link_closed`` [P] bytes
+    (default none).  None where a speed is negative or not finite or a byte is above 1: the scenario fails."""
+    P, Kp = network.num_pipes, network.num_pumps
+    w = np.ones(Kp) if pump_speed is None else np.asarray(pump_speed, dtype=np.float64).reshape(Kp)
+    cl = np.zeros(P, dtype=np.uint8) if link_closed is None else np.asarray(link_closed).reshape(P)
+    if not (np.isfinite(w).all() and (w >= 0).all() and (cl <= 1).all() and (cl >= 0).all()):
+        return None
+    k = np.maximum(network.pump_of_link, 0)
+    pick = lambda v, fill: np.where(network.is_pump, v[k], fill) if Kp else np.full(P, fill)
+    return {"minor": network.minor, "pump": network.is_pump, "check": network.check_valve, "shut": network.closed | (cl != 0),
+            "h0": pick(network.pump_h0, 0.0), "rp": pick(network.pump_r, 1.0), "n": pick(network.pump_n, 1.0), "speed": pick(w, 1.0)}
+
+
+def _link_rows(network, S, pump_speed, link_closed):
+    """[S, Kp] speeds and [S, P] bytes (or None) from what ``simulate`` takes."""
+    w = None if pump_speed is None else np.broadcast_to(np.asarray(pump_speed, dtype=np.float64), (S, network.num_pumps))
+    cl = None if link_closed is None else np.broadcast_to(np.asarray(link_closed), (S, network.num_pipes))
+    return w, cl
+
+
+def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed):
+    newton = _NewtonRef(network, solver, accuracy, max_iter)
+    demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
+    S, N, P = demand.shape[0], network.num_nodes, network.num_pipes
+    fh, fixed = _fixed_heads(network, fixed_head, S), network.fixed
+    speeds, closed = _link_rows(network, S, pump_speed, link_closed)
+    head, flow = np.full((S, N), np.nan), np.full((S, P), np.nan)
+    iterations, converged, failed = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=bool), np.zeros(S, dtype=bool)
+    final_dq, state = np.full(S, np.nan), np.zeros((S, P), dtype=np.uint8)
+    for s in range(S):
+        c = roughness[s]
+        with np.errstate(all="ignore"):
+            r = np.where(network.is_pump, 0.0, _resistance(network, c))
+        d, hf = np.where(fixed, 0.0, demand[s]), np.where(fixed, fh[s], 0.0)
+        law = link_law(network, None if speeds is None else speeds[s], None if closed is None else closed[s])
+        if not newton.link_inputs_ok(d, hf, c, r, law):
+            failed[s] = True
+            continue
+        H, q, iterations[s], converged[s], ok, rel = newton.run(d, hf, r, network.q_start, law)
+        if not ok:
+            failed[s] = True
+            continue
+        head[s], flow[s], final_dq[s] = H, q, rel
+        state[s] = link_state_ref(q, law["pump"], law["check"], law["shut"], law["speed"])
+    return HydraulicLinksReference(head, flow, iterations, converged, failed, final_dq, state)
+
+
 def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, solver: str = "dense", accuracy: float = ACCURACY,
-              max_iter: int = MAX_ITER) -> HydraulicReference:
+              max_iter: int = MAX_ITER, pump_speed=None, link_closed=None, links=None) -> HydraulicReference:
     """The algorithm and the stop rule of the kernel in numpy fp64, scenario by scenario, with the kernel's order in every
     sum of the assembly and of the stop rule; the linear solve is the library's.  ``solver``: "dense"
     (``numpy.linalg.solve`` on the N x N system in the given node order) or "banded" (``scipy.linalg.solveh_banded`` in the
-    solver order)."""
+    solver order).  A network with special links (or ``pump_speed`` [Kp] / [S, Kp], ``link_closed`` [P] / [S, P], or
+    ``links=True``) is solved under THE LINK LAW and returns a ``HydraulicLinksReference``."""
+    if links or (links is None and (network.has_links or pump_speed is not None or link_closed is not None)):
+        return _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed)
     newton = _NewtonRef(network, solver, accuracy, max_iter)
     demand = np.asarray(demand, dtype=np.float64)
     roughness = np.asarray(roughness, dtype=np.float64)
@@ -789,12 +1163,22 @@ def _series_inputs(network, demand, multipliers, pattern_of_node):
 
 def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multipliers, step_seconds: float, initial_level=None,
                         pattern_of_node=None, fixed_head=None, solver: str = "dense", warm_start: bool = True,
-                        accuracy: float = ACCURACY, max_iter: int = MAX_ITER) -> HydraulicSeriesReference:
+                        accuracy: float = ACCURACY, max_iter: int = MAX_ITER, pump_speed=None, link_closed=None,
+                        speed_multipliers=None, speed_pattern_of_pump=None, links=None) -> HydraulicSeriesReference:
     """``gatres_hydraulic_series`` in numpy fp64, series by series and step by step, on the Newton loop of ``solve_ref``: the
     rounded product demand * multiplier, the tank heads elevation + level, the warm or cold start, ``level_update_ref`` and
-    the kernel's failure rules.  head [S, T, N], flow [S, T, P], level [S, T + 1, K], the rest [S, T]."""
+    the kernel's failure rules.  head [S, T, N], flow [S, T, P], level [S, T + 1, K], the rest [S, T].  With special links (as
+    in ``simulate_series``) it is ``gatres_hydraulic_series_links`` and returns a ``HydraulicSeriesLinksReference``."""
     newton = _NewtonRef(network, solver, accuracy, max_iter)
     demand, mult, pattern = _series_inputs(network, demand, multipliers, pattern_of_node)
+    with_links = bool(links) if links is not None else (
+        network.has_links or any(v is not None for v in (pump_speed, link_closed, speed_multipliers, speed_pattern_of_pump)))
+    if with_links:
+        speeds, closed = _link_rows(network, demand.shape[0], pump_speed, link_closed)
+        smult = np.ones((1, mult.shape[2])) if speed_multipliers is None else np.asarray(speed_multipliers, dtype=np.float64)
+        spat = np.zeros(network.num_pumps, dtype=np.int64) if speed_pattern_of_pump is None else \
+            np.asarray(speed_pattern_of_pump, dtype=np.int64)
+        state = np.zeros(demand.shape[:1] + (mult.shape[2], network.num_pipes), dtype=np.uint8)
     roughness = np.asarray(roughness, dtype=np.float64)
     S, N, P, K, T = demand.shape[0], network.num_nodes, network.num_pipes, network.num_tanks, mult.shape[2]
     fh = _fixed_heads(network, fixed_head, S)
@@ -814,7 +1198,11 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
         with np.errstate(all="ignore"):
             r = _resistance(network, c)
         hf = np.where(fixed, fh[s], 0.0)
-        if not newton.inputs_ok(np.zeros(N), hf, c, r):
+        if with_links:
+            r = np.where(network.is_pump, 0.0, r)
+            if not newton.link_inputs_ok(np.zeros(N), hf, c, r, link_law(network)):
+                continue
+        elif not newton.inputs_ok(np.zeros(N), hf, c, r):
             continue
         q, lev = network.q_start, level0[s].copy()
         for t in range(T):
@@ -824,15 +1212,29 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                 hf[tanks] = network.elevation[tanks] + lev
             if not (np.isfinite(m).all() and (m >= 0).all() and np.isfinite(d).all() and np.isfinite(hf[tanks]).all()):
                 break
-            H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run(d, hf, r, q if warm_start else network.q_start)
+            law = None
+            if with_links:
+                sm = smult[:, t]
+                if not (np.isfinite(sm).all() and (sm >= 0).all()):
+                    break
+                with np.errstate(all="ignore"):
+                    w = (np.ones(network.num_pumps) if speeds is None else speeds[s]) * sm[spat]
+                law = link_law(network, w, None if closed is None else closed[s])
+                if not newton.link_inputs_ok(d, hf, c, r, law):
+                    break
+            H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run(d, hf, r, q if warm_start else network.q_start, law)
             if not ok:
                 break
             q = q_new
             failed[s, t] = False
             head[s, t], flow[s, t], final_dq[s, t] = H, q, rel
+            if with_links:
+                state[s, t] = link_state_ref(q, law["pump"], law["check"], law["shut"], law["speed"])
             lev, clamped = level_update_ref(network, lev, q, step_seconds)
             level[s, t + 1], limited[s, t] = lev, clamped.any()
         converged[s] &= ~failed[s]
+    if with_links:
+        return HydraulicSeriesLinksReference(head, flow, level, iterations, converged, failed, limited, final_dq, state)
     return HydraulicSeriesReference(head, flow, level, iterations, converged, failed, limited, final_dq)
 
 
@@ -887,13 +1289,18 @@ def series_volume_balance(network: HydraulicNetwork, result, demand, multipliers
     return (stored[:, 1:] - stored[:, :-1]) - float(step_seconds) * (out_of_reservoirs - total_demand)
 
 
-def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness, fixed_head=None) -> Tuple[np.ndarray, np.ndarray]:
+def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness, fixed_head=None, pump_speed=None,
+                        link_closed=None, law=link_headloss) -> Tuple[np.ndarray, np.ndarray]:
     """How well (head, flow) satisfy the model, per scenario: (mass, energy).  mass: the largest junction imbalance
     |inflow - outflow - demand| divided by sum |q| (not divided where that sum is 0); energy: the largest
-    |H_a - H_b - h_p(q_p)| over the pipes and |H_f - fixed head| over the fixed nodes, in metres.  NaN where an input is."""
+    |H_a - H_b - h_p(q_p)| over the pipes and |H_f - fixed head| over the fixed nodes, in metres.  NaN where an input is.
+    A network with special links (or ``pump_speed`` / ``link_closed``) is held to THE LINK LAW, ``law`` (``link_headloss``; the
+    tests plant wrong ones)."""
     head, flow = np.asarray(head, dtype=np.float64), np.asarray(flow, dtype=np.float64)
     demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
     S, N = head.shape[0], network.num_nodes
+    with_links = network.has_links or pump_speed is not None or link_closed is not None
+    speeds, closed = _link_rows(network, S, pump_speed, link_closed)
     fh = _fixed_heads(network, fixed_head, S)
     a, b, fixed = network.pipes[:, 0].astype(np.int64), network.pipes[:, 1].astype(np.int64), network.fixed
     mass, energy = np.empty(S), np.empty(S)
@@ -905,7 +1312,12 @@ def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness
         total = np.abs(flow[s]).sum()
         worst = imbalance.max() if imbalance.size else 0.0
         mass[s] = worst / total if total > 0 else worst
-        h, _ = pipe_headloss(flow[s], _resistance(network, roughness[s]))
+        if with_links:
+            arrays = link_law(network, None if speeds is None else speeds[s], None if closed is None else closed[s])
+            h = np.full(network.num_pipes, np.nan) if arrays is None else \
+                law(flow[s], np.where(network.is_pump, 0.0, _resistance(network, roughness[s])), **arrays)[0]
+        else:
+            h, _ = pipe_headloss(flow[s], _resistance(network, roughness[s]))
         e_pipe = np.abs(head[s][a] - head[s][b] - h).max()
         e_fixed = np.abs(head[s] - fh[s])[fixed].max()
         energy[s] = max(e_pipe, e_fixed) if not (np.isnan(e_pipe) or np.isnan(e_fixed)) else np.nan

@@ -26,7 +26,7 @@ import json
 import struct
 import zipfile
 import zlib
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import os
@@ -154,6 +154,206 @@ def inp_edge_index(inp: Dict[str, list], removal: str = "keep_junction") -> Tupl
 def inp_node_order(inp: Dict[str, list]) -> List[str]:
     """``wn.node_name_list``: the column order of the zarr arrays (DataLoader.py:243-249)."""
     return list(inp["JUNCTIONS"]) + list(inp["RESERVOIRS"]) + list(inp["TANKS"])
+
+
+# ------------------------------------------------------------------------------------------------- .inp: hydraulics
+# flow units -> m3/s (EPANET 2.2 users manual, appendix A); the first five are SI (metres, millimetres), the others US customary
+# (feet for lengths, elevations and heads, inches for diameters)
+_GALLON, _FOOT = 3.785411784e-3, 0.3048
+FLOW_UNITS = {"LPS": 1e-3, "LPM": 1e-3 / 60.0, "MLD": 1e3 / 86400.0, "CMH": 1.0 / 3600.0, "CMD": 1.0 / 86400.0,
+              "GPM": _GALLON / 60.0, "CFS": _FOOT ** 3, "MGD": 1e6 * _GALLON / 86400.0}
+_SI_UNITS = ("LPS", "LPM", "MLD", "CMH", "CMD")
+_REGULATING = ("PRV", "PSV", "PBV", "FCV", "GPV")
+NOMINAL_ROUGHNESS = 100.0               # what a pump or a valve gets in the roughness row: it has no resistance and it is not read
+NOMINAL_PUMP_DIAMETER = 1.0             # metres: a pump has no diameter; HydraulicNetwork asks for one and reads it nowhere
+
+InpHydraulics = namedtuple("InpHydraulics", "network demand roughness multipliers pattern_of_node pump_speed node_names link_names "
+                                            "pattern_names")
+
+
+def _inp_sections(source, text) -> "OrderedDict[str, list]":
+    """Every section of an EPANET input file as its token lists, comments stripped, in file order."""
+    if (source is None) == (text is None):
+        raise ValueError("give a path OR text=")
+    if text is None:
+        if isinstance(source, os.PathLike) or os.path.exists(str(source)) or "\n" not in str(source):
+            with open(source, "r", encoding="latin-1") as f:
+                text = f.read()
+        else:
+            text = str(source)
+    out: "OrderedDict[str, list]" = OrderedDict()
+    section = None
+    for raw in str(text).splitlines():
+        line = raw.split(";", 1)[0].strip()
+        if not line:
+            continue
+        if line.startswith("["):
+            section = line.strip("[]").strip().upper()
+            out.setdefault(section, [])
+        elif section is not None:
+            out[section].append(line.split())
+    if "JUNCTIONS" not in out:
+        raise ValueError("no [JUNCTIONS] section: not an EPANET .inp file")
+    return out
+
+
+def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported_valves: str = "refuse", ignore_controls: bool = False,
+                         device=None) -> "InpHydraulics":
+    """The hydraulic attributes of an EPANET input file as a ``hydraulics.HydraulicNetwork`` and the arrays ``simulate`` and
+    ``simulate_series`` take, in SI units.  Read: [JUNCTIONS] (elevation, base demand, pattern), [RESERVOIRS] (head), [TANKS]
+    (elevation, initial, minimum and maximum level, diameter), [PIPES] (length, diameter, roughness, minor loss, Open / Closed /
+    CV), [PUMPS] (``HEAD`` curve, ``SPEED``), [CURVES], [VALVES] (TCV: the setting is its loss coefficient), [STATUS] (Open,
+    Closed, or a pump's speed), [PATTERNS] and of [OPTIONS] ``UNITS``, ``HEADLOSS`` and ``PATTERN``.  Nodes come in the order
+    junctions, reservoirs, tanks, links in the order pipes, pumps, valves, each in file order; a link runs from its first node
+    to its second.  Returns ``InpHydraulics``: network; demand [N] m3/s; roughness [P] (``NOMINAL_ROUGHNESS`` for pumps and
+    valves); multipliers [M, T], row 0 the constant pattern 1 and then the file's patterns, the shorter ones repeated up to the
+    longest, as EPANET wraps them; pattern_of_node int32 [N] (a junction without a pattern takes the default pattern of
+    [OPTIONS], "1" if there is one, else row 0); pump_speed [Kp] (0 for a pump that [STATUS] closes); the names.
+
+    Refused with a ``ValueError`` that names the offender: flow units other than ``FLOW_UNITS``, a head-loss formula other than
+    H-W, a ``POWER`` pump or one without a ``HEAD`` curve, a regulating valve (PRV, PSV, PBV, FCV, GPV) unless
+    ``unsupported_valves="open"``, which makes it an open link with its minor loss, [CONTROLS] or [RULES] with content unless
+    ``ignore_controls=True``.  What EPANET does with the rest of the file (demand multiplier, emitters, quality, energy, times)
+    is not read."""
+    from . import hydraulics as H
+    if unsupported_valves not in ("refuse", "open"):
+        raise ValueError('unsupported_valves must be "refuse" or "open"')
+    sec = _inp_sections(source, text)
+    options = {" ".join(t[:-1]).upper(): t[-1] for t in sec.get("OPTIONS", []) if len(t) >= 2}
+    units = options.get("UNITS", "GPM").upper()
+    if units not in FLOW_UNITS:
+        raise ValueError(f"[OPTIONS] UNITS {units}: flow units must be one of {sorted(FLOW_UNITS)}")
+    formula = options.get("HEADLOSS", "H-W").upper()
+    if formula != "H-W":
+        raise ValueError(f"[OPTIONS] HEADLOSS {formula}: only the Hazen-Williams formula (H-W) is modelled")
+    for name in ("CONTROLS", "RULES"):
+        if sec.get(name) and not ignore_controls:
+            raise ValueError(f"[{name}] has {len(sec[name])} lines: controls and rules are not modelled (ignore_controls=True drops them)")
+    flow = FLOW_UNITS[units]
+    metre, dia = (1.0, 1e-3) if units in _SI_UNITS else (_FOOT, _FOOT / 12.0)
+    num = lambda tok, i, default=0.0: float(tok[i]) if len(tok) > i else default
+
+    # nodes
+    names, elevation, demand, pattern_id = [], [], [], []
+    for t in sec["JUNCTIONS"]:
+        names.append(t[0]); elevation.append(num(t, 1) * metre); demand.append(num(t, 2) * flow); pattern_id.append(t[3] if len(t) > 3 else None)
+    fixed_nodes, fixed_head, tanks, t_dia, t_min, t_max = [], [], [], [], [], []
+    for t in sec.get("RESERVOIRS", []):
+        fixed_nodes.append(len(names)); fixed_head.append(num(t, 1) * metre)
+        names.append(t[0]); elevation.append(num(t, 1) * metre); demand.append(0.0); pattern_id.append(None)
+    for t in sec.get("TANKS", []):
+        if len(t) < 6:
+            raise ValueError(f"[TANKS] {t[0]}: needs elevation, initial, minimum and maximum level and diameter")
+        fixed_nodes.append(len(names)); fixed_head.append((num(t, 1) + num(t, 2)) * metre)
+        tanks.append(len(names)); t_min.append(num(t, 3) * metre); t_max.append(num(t, 4) * metre); t_dia.append(num(t, 5) * metre)
+        names.append(t[0]); elevation.append(num(t, 1) * metre); demand.append(0.0); pattern_id.append(None)
+    index = {n: i for i, n in enumerate(names)}
+    if len(index) != len(names):
+        raise ValueError("a node id appears twice")
+
+    # links: pipes, pumps, valves
+    links, ends, length, diameter, rough, minor, check, closed = [], [], [], [], [], [], [], []
+
+    def add(section, t, L, D, C, K, cv=False, shut=False):
+        for n in t[1:3]:
+            if n not in index:
+                raise ValueError(f"[{section}] {t[0]}: no node {n}")
+        links.append(t[0]); ends.append((index[t[1]], index[t[2]])); length.append(L); diameter.append(D); rough.append(C)
+        minor.append(K); check.append(cv); closed.append(shut)
+
+    for t in sec.get("PIPES", []):
+        if len(t) < 6:
+            raise ValueError(f"[PIPES] {t[0]}: needs two nodes, length, diameter and roughness")
+        status = t[7].upper() if len(t) > 7 else "OPEN"
+        if status not in ("OPEN", "CLOSED", "CV"):
+            raise ValueError(f"[PIPES] {t[0]}: status {t[7]}")
+        add("PIPES", t, num(t, 3) * metre, num(t, 4) * dia, num(t, 5), num(t, 6), status == "CV", status == "CLOSED")
+    curves: Dict[str, list] = {}
+    for t in sec.get("CURVES", []):
+        if len(t) < 3:
+            raise ValueError(f"[CURVES] {t[0]}: needs an x and a y")
+        curves.setdefault(t[0], []).append((float(t[1]), float(t[2])))
+    pump_links, pump_curve, pump_speed = [], [], []
+    for t in sec.get("PUMPS", []):
+        if len(t) < 5 or len(t) % 2 == 0:
+            raise ValueError(f"[PUMPS] {t[0]}: needs two nodes and keyword-value pairs")
+        props = {t[i].upper(): t[i + 1] for i in range(3, len(t), 2)}
+        if "POWER" in props:
+            raise ValueError(f"[PUMPS] {t[0]}: a POWER pump is not modelled, give it a HEAD curve")
+        if "HEAD" not in props or props["HEAD"] not in curves:
+            raise ValueError(f"[PUMPS] {t[0]}: needs a HEAD curve that [CURVES] defines")
+        pts = curves[props["HEAD"]]
+        try:
+            pump_curve.append(H.pump_curve_from_points([q * flow for q, _ in pts], [h * metre for _, h in pts]))
+        except ValueError as err:
+            raise ValueError(f"[PUMPS] {t[0]}, curve {props['HEAD']}: {err}") from None
+        pump_links.append(len(links)); pump_speed.append(float(props.get("SPEED", 1.0)))
+        add("PUMPS", t, 0.0, NOMINAL_PUMP_DIAMETER, NOMINAL_ROUGHNESS, 0.0)
+    for t in sec.get("VALVES", []):
+        if len(t) < 6:
+            raise ValueError(f"[VALVES] {t[0]}: needs two nodes, diameter, type and setting")
+        kind, K = t[4].upper(), num(t, 6)
+        if kind == "TCV":
+            K = max(K, float(t[5]))
+        elif kind in _REGULATING and unsupported_valves == "open":
+            pass
+        else:
+            raise ValueError(f'[VALVES] {t[0]}: a {kind} valve is not modelled (unsupported_valves="open" makes it an open link)')
+        if not K > 0:
+            raise ValueError(f"[VALVES] {t[0]}: an open valve without a loss coefficient has no head-loss law")
+        add("VALVES", t, 0.0, num(t, 3) * dia, NOMINAL_ROUGHNESS, K)
+    link_index = {n: i for i, n in enumerate(links)}
+    if len(link_index) != len(links):
+        raise ValueError("a link id appears twice")
+    for t in sec.get("STATUS", []):
+        if len(t) < 2 or t[0] not in link_index:
+            raise ValueError(f"[STATUS] {t[0]}: no such link")
+        p, word = link_index[t[0]], t[1].upper()
+        k = pump_links.index(p) if p in pump_links else None
+        if word in ("OPEN", "CLOSED"):
+            if k is None:
+                closed[p] = word == "CLOSED"
+            elif word == "CLOSED":
+                pump_speed[k] = 0.0
+        elif k is not None:
+            pump_speed[k] = float(t[1])
+        else:
+            raise ValueError(f"[STATUS] {t[0]}: a setting for a link that is no pump")
+
+    # patterns: row 0 is the constant 1
+    pats: "OrderedDict[str, list]" = OrderedDict()
+    for t in sec.get("PATTERNS", []):
+        pats.setdefault(t[0], []).extend(float(x) for x in t[1:])
+    T = max([len(v) for v in pats.values()] + [1])
+    mult = np.ones((1 + len(pats), T))
+    for i, v in enumerate(pats.values()):
+        if not v:
+            raise ValueError(f"[PATTERNS] {list(pats)[i]}: no multipliers")
+        mult[1 + i] = np.resize(np.asarray(v), T)
+    row = {n: 1 + i for i, n in enumerate(pats)}
+    default = row.get(options.get("PATTERN", "1"), 0)
+    pattern_of_node = np.zeros(len(names), dtype=np.int32)
+    for i, pid in enumerate(pattern_id):
+        if pid is not None and pid not in row:
+            raise ValueError(f"[JUNCTIONS] {names[i]}: no pattern {pid}")
+        pattern_of_node[i] = default if pid is None else row[pid]
+    pattern_of_node[fixed_nodes] = 0
+
+    ends_a = np.asarray(ends, dtype=np.int64).reshape(-1, 2)
+    if (ends_a[:, 0] == ends_a[:, 1]).any():
+        raise ValueError(f"link {links[int(np.flatnonzero(ends_a[:, 0] == ends_a[:, 1])[0])]} joins a node to itself")
+    lo, hi = ends_a.min(axis=1), ends_a.max(axis=1)
+    edge_index = torch.from_numpy(np.stack([np.concatenate([lo, hi]), np.concatenate([hi, lo])]))
+    kw = {}
+    if tanks:
+        kw.update(tank_nodes=tanks, tank_diameter=t_dia, tank_min_level=t_min, tank_max_level=t_max)
+    if pump_links:
+        h0, rp, n = (np.asarray(v) for v in zip(*pump_curve))
+        kw.update(pump_links=pump_links, pump_h0=h0, pump_r=rp, pump_n=n)
+    network = H.HydraulicNetwork(edge_index, length, diameter, elevation, fixed_nodes, fixed_head, device=device, minor_loss=minor,
+                                 check_valve=check, closed=closed, link_reversed=ends_a[:, 0] > ends_a[:, 1], **kw)
+    return InpHydraulics(network, np.asarray(demand), np.asarray(rough), mult, pattern_of_node, np.asarray(pump_speed, dtype=np.float64),
+                         names, links, ["1 (constant)"] + list(pats))
 
 
 # ------------------------------------------------------------------------------------------------------------- blosc

@@ -67,14 +67,21 @@ def make_wdn_topology(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_PIPES
 
 def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_PIPES, num_reservoirs: int = 1, seed: int = 0,
                            length_range=None, diameter_range=None, elevation_range=None, head_range=None, device=None,
-                           num_tanks: int = 0):
+                           num_tanks: int = 0, num_pumps: int = 0, num_check_valves: int = 0, minor_loss_range=None):
     """A ``hydraulics.HydraulicNetwork`` on ``make_wdn_topology(num_nodes, num_pipes, seed)``: ``num_reservoirs`` of the nodes
     are fixed-head nodes, and lengths, diameters, elevations and reservoir heads are seeded uniform numpy draws from the ranges
     of the reference's scenario generator for C-Town (``hydraulics.LENGTH_RANGE`` and so on) unless given.  The last
     ``num_tanks`` of the fixed-head nodes are tanks: a diameter from ``hydraulics.TANK_DIAMETER_RANGE`` and a starting level from
     ``hydraulics.TANK_LEVEL_RANGE`` each, drawn AFTER everything else (``num_tanks=0`` returns what it always did); a tank's
     elevation is set to its head minus that level, so the network's ``fixed_head`` is the tank's starting head (a drawn elevation
-    and a drawn head would put the level anywhere).  Level limits: the constructor's default, (0, +inf)."""
+    and a drawn head would put the level anywhere).  Level limits: the constructor's default, (0, +inf).
+
+    SPECIAL LINKS (hydraulics.py: THE LINK LAW), drawn after the tanks, so the defaults return what they always did:
+    ``num_pumps`` of the links that leave a fixed-head node become pumps that run from that node to the junction, with a shut-off
+    head from ``PUMP_SHUTOFF_RANGE`` and a quadratic curve that gives half of it at ``PUMP_DESIGN_VELOCITY`` in the link;
+    ``minor_loss_range`` (lo, hi) draws a minor-loss coefficient K for every link but the pumps; ``num_check_valves`` of the
+    other links, in a drawn order and a drawn direction each, become check valves -- one that would leave a junction without
+    a directed path from a fixed-head node is passed over.  ``ValueError`` where that many cannot be placed."""
     from . import hydraulics as H
     if not 1 <= num_reservoirs < num_nodes:
         raise ValueError("num_reservoirs must lie in [1, num_nodes)")
@@ -88,14 +95,78 @@ def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_
     diameter = draw(diameter_range or H.DIAMETER_RANGE, num_pipes)
     elevation = draw(elevation_range or H.ELEVATION_RANGE, num_nodes)
     head = draw(head_range or H.HEAD_RANGE, num_reservoirs)
-    if num_tanks == 0:
-        return H.HydraulicNetwork(ei, length, diameter, elevation, fixed_nodes, head, device=device)
-    tanks = fixed_nodes[num_reservoirs - num_tanks:]
-    tank_diameter = draw(H.TANK_DIAMETER_RANGE, num_tanks)
-    level = draw(H.TANK_LEVEL_RANGE, num_tanks)
-    elevation[tanks] = head[num_reservoirs - num_tanks:] - level
-    return H.HydraulicNetwork(ei, length, diameter, elevation, fixed_nodes, head, device=device, tank_nodes=tanks,
-                              tank_diameter=tank_diameter)
+    kw = {}
+    if num_tanks:
+        tanks = fixed_nodes[num_reservoirs - num_tanks:]
+        tank_diameter = draw(H.TANK_DIAMETER_RANGE, num_tanks)
+        level = draw(H.TANK_LEVEL_RANGE, num_tanks)
+        elevation[tanks] = head[num_reservoirs - num_tanks:] - level
+        kw.update(tank_nodes=tanks, tank_diameter=tank_diameter)
+    if num_pumps < 0 or num_check_valves < 0:
+        raise ValueError("num_pumps and num_check_valves must not be negative")
+    if not (num_pumps or num_check_valves or minor_loss_range is not None):
+        return H.HydraulicNetwork(ei, length, diameter, elevation, fixed_nodes, head, device=device, **kw)
+    # the special links, drawn after everything else
+    e = ei.numpy()
+    pipes = e[:, e[0] < e[1]].T
+    fixed = np.zeros(num_nodes, dtype=bool)
+    fixed[fixed_nodes] = True
+    a, b = pipes[:, 0], pipes[:, 1]
+    at_source = np.flatnonzero(fixed[a] ^ fixed[b])
+    if num_pumps > at_source.size:
+        raise ValueError(f"num_pumps = {num_pumps}, but only {at_source.size} links leave a fixed-head node")
+    pumps = rng.permutation(at_source)[:num_pumps]
+    flip = np.zeros(num_pipes, dtype=bool)
+    flip[pumps] = fixed[b[pumps]]                                   # a pump runs from the fixed-head node to the junction
+    h0 = draw(PUMP_SHUTOFF_RANGE, num_pumps)
+    q_design = PUMP_DESIGN_VELOCITY * np.pi * diameter[pumps] ** 2 / 4.0
+    kw.update(pump_links=pumps, pump_h0=h0, pump_r=0.5 * h0 / q_design ** 2, pump_n=np.full(num_pumps, 2.0))
+    minor = np.zeros(num_pipes)
+    if minor_loss_range is not None:
+        minor = draw(minor_loss_range, num_pipes)
+        minor[pumps] = 0.0
+    check = np.zeros(num_pipes, dtype=bool)
+    is_pump = np.zeros(num_pipes, dtype=bool)
+    is_pump[pumps] = True
+    placed = 0
+    for p, way in zip(rng.permutation(num_pipes), rng.randint(0, 2, num_pipes).astype(bool)):
+        if placed == num_check_valves:
+            break
+        if is_pump[p]:
+            continue
+        check[p], flip[p] = True, way
+        if _all_fed(num_nodes, pipes, flip, check | is_pump, fixed):
+            placed += 1
+        else:                                                       # (it would cut a zone off from every source: not this one)
+            check[p], flip[p] = False, False
+    if placed < num_check_valves:
+        raise ValueError(f"only {placed} of {num_check_valves} check valves can be placed without cutting a zone off")
+    return H.HydraulicNetwork(ei, length, diameter, elevation, fixed_nodes, head, device=device, minor_loss=minor, check_valve=check,
+                              link_reversed=flip, **kw)
+
+
+PUMP_SHUTOFF_RANGE = (20.0, 40.0)       # metres: the shut-off heads make_hydraulic_network draws
+PUMP_DESIGN_VELOCITY = 1.0              # m/s in the pump's link at the design flow, where the gain is half the shut-off head
+
+
+def _all_fed(num_nodes: int, pipes: np.ndarray, flip: np.ndarray, one_way: np.ndarray, fixed: np.ndarray) -> bool:
+    """Does a directed path reach every junction from a fixed-head node, one-way links walked from a to b only?  (What the
+    constructor of ``HydraulicNetwork`` refuses otherwise.)"""
+    adj = [[] for _ in range(num_nodes)]
+    for (lo, hi), f, ow in zip(pipes, flip, one_way):
+        u, v = (hi, lo) if f else (lo, hi)
+        adj[u].append(int(v))
+        if not ow:
+            adj[v].append(int(u))
+    seen = fixed.copy()
+    stack = [int(v) for v in np.flatnonzero(fixed)]
+    while stack:
+        u = stack.pop()
+        for v in adj[u]:
+            if not seen[v]:
+                seen[v] = True
+                stack.append(v)
+    return bool(seen.all())
 
 
 def make_demand_patterns(num_patterns: int, steps: int, step_seconds: float, seed: int) -> np.ndarray:

@@ -1424,7 +1424,8 @@ int gatres_hydraulic_valid(const float* pressure, const int32_t* status, const u
  * with every operation rounded to fp64 on its own.  level[0] is initial_level as given.
  * WHAT DOES NOT HOLD: EPANET shortens a time step at the moment a tank becomes full or empty and closes the pipes of such a
  * tank; this model clamps the level and does neither.  A step after which a level was clamped gets status[s][t][3] = 1, and
- * volume is not conserved across it.  Pumps, valves, minor losses, controls and rules are not modelled.  The limit on flows that
+ * volume is not conserved across it.  Pumps, check valves, closed links and minor losses are the matter of THE LINK LAW below
+ * (gatres_hydraulic_series_links); regulating valves, controls and rules are not modelled.  The limit on flows that
  * should be zero carries over: a step with a zero multiplier does not meet the stop rule.
  * FAILURE: a step fails on a multiplier of the step (any of the M) that is negative or not finite, a product demand * mult or
  * a tank head that is not finite, a pivot that is not positive and finite or a non-finite sum of the stop rule; a series fails
@@ -1465,6 +1466,80 @@ int gatres_hydraulic_series(const int32_t* pipe_a, const int32_t* pipe_b, const 
 int gatres_hydraulic_series_valid(const float* pressure, const int32_t* status, const uint8_t* fixed, int64_t num_series,
                                   int32_t num_steps, int32_t num_nodes, double p_lo, double p_hi, int32_t allow_limited,
                                   uint8_t* valid, void* stream);
+
+/* THE LINK LAW: pumps, check valves, closed links and minor losses (symbols only: the ABI stays; k_hydraulic_links.hip,
+ * hydraulics.py).  The two launches below are gatres_hydraulic_solve and gatres_hydraulic_series with one thing replaced: the law
+ * h_p(q), g_p(q) of a link.  Every link p has a KIND, link_kind[p] = GATRES_HYD_PIPE or GATRES_HYD_PUMP, and FLAGS, link_flags[p],
+ * a sum of GATRES_HYD_LINK_CHECK (flow only from a_p to b_p) and GATRES_HYD_LINK_CLOSED.  A pump is always CHECK.  The law gives
+ * the head loss H_a - H_b = h_p(q) and its gradient g_p, every operation rounded to fp64 on its own:
+ *   PIPE, forward branch:   h = r |q|^0.852 q + m |q| q,   g = 1.852 r |q|^0.852 + 2 m |q|,   formed as
+ *     ra = r * pow(|q|, 0.852);  ma = m * |q|;  g = 1.852 * ra + 2 * ma;  h = (ra + ma) * q;   where g < 1e-7:  g = 1e-7, h = 1e-7 * q
+ *     (the law at low flow).  m = minor[p] = 8 K / (pi^2 * 9.80665 * D^4) is formed by the caller from the minor-loss coefficient
+ *     K; m = 0 is the pipe of THE MODEL in every bit; r = 0 (coef = 0) with m > 0 is allowed, a throttle valve (EPANET's TCV).
+ *   PUMP k, forward branch (q >= 0): speed w, shut-off head h0 >= 0, coefficient rp > 0, exponent n >= 1; by the affinity laws
+ *     the head gain is w^2 h0 - w^(2-n) rp q^n, so   h = -w^2 h0 + w^(2-n) rp q^n,   g = n w^(2-n) rp q^(n-1),   formed as
+ *     ca = (w2n * rp) * pow(q, n - 1);  g = n * ca;  hq = ca * q;   where g < 1e-7:  g = 1e-7, hq = 1e-7 * q;   h = hq - w2 * h0
+ *     with w2 = w * w and w2n = pow(w, 2 - n) formed once per scenario (or step) and pump.  A pump's coef and roughness are not read.
+ *   REVERSE BRANCH of a CHECK link (q < 0):   g = 1e8,   h = h(0) + 1e8 q,   h(0) = 0 for a pipe and -w2 * h0 for a pump.
+ *   A CLOSED link -- by its flag, by the scenario's byte closed[s][p] = 1, or a pump with w == 0:   g = 1e8,   h = 1e8 q at every q;
+ *     such a link starts at q = 0 (in a series at every step in which it is shut, warm start or not).
+ * The law is continuous and monotone in q, up to the jump at the low-flow floor that THE MODEL already has, so the system stays
+ * symmetric positive definite and the solution unique.  THERE IS NO STATUS MACHINE: a link that holds shut carries -dh / 1e8, as a
+ * closed link does in EPANET.  Assembly, factorisation, flow update and stop rule are those of THE SOLVER, the same function
+ * (hy_newton in k_hydraulics_dev.h) with the law chosen at compile time.  New output link_state uint8[S][P] (series: [S][T][P]),
+ * evaluated at the returned flows: 0 forward; 1 a CHECK link on its reverse branch (q < 0); 2 shut by input or by w == 0; 0
+ * where the scenario or step failed.
+ * WHAT DOES NOT HOLD: a zone that CHECK or shut links cut off from every fixed-head node gets heads near -1e8 x demand and
+ * usually does not meet the stop rule; such scenarios are counted and dropped by the generators, never repaired.
+ * Pressure-regulating valves (PRV, PSV, PBV, FCV, GPV), power-rated pumps, controls and rules stay out of scope.  Parity with
+ * EPANET is not claimed and has not been checked.
+ * STATIC link inputs (device): link_kind, link_flags uint8[P]; minor double[P]; pump_link int32[Kp], the link of pump k;
+ * pump_h0, pump_r, pump_n double[Kp].  Kp == 0 is legal, the pump arrays and speed may then be NULL.  PER-SCENARIO: speed
+ * double, row s at speed + s * speed_stride, speed_stride 0 or Kp; closed uint8 or NULL, row s at closed + s * closed_stride,
+ * closed_stride 0 or P.  In the series the speed of pump k in step t is speed[s][k] * speed_mult[speed_pattern_of_pump[k]][t],
+ * one rounded product, speed_mult double[Ms][T]; 0 is legal: the pump is off in that step.
+ * FAILED, every scenario of the launch: a kind above 1, flags above 3, m negative or not finite, a pipe's coef negative, not
+ * finite, or 0 with m = 0; pump_link outside [0, P), on a link that is no pump or listed twice, a pump link without a pump;
+ * h0 < 0, rp <= 0, n < 1 or any of them not finite; in the series a speed pattern outside [0, Ms).  That scenario (in the series
+ * that step and the later ones) alone: a speed, or in the series a speed multiplier of the step, that is negative or not finite,
+ * a w^2 or w^(2-n) that is not finite, a closed byte above 1, and what fails a scenario of gatres_hydraulic_solve (a pipe's
+ * r = 0 fails only where m = 0).
+ * LDS need (hydraulics.links_lds_bytes, series_links_lds_bytes): the bytes of gatres_hydraulic_solve (of gatres_hydraulic_series)
+ *   + 12 P (m and the link's code)  +  48 Kp (h0, rp, n, w^2, w^(2-n), w per pump),
+ * refused above GATRES_HYD_LDS_BUDGET.  The 12 P bytes are taken whether or not a link is special, so a pipe-only network whose
+ * band leaves fewer than 12 P bytes of the budget runs through gatres_hydraulic_solve and is refused here (a full band of 139
+ * rows is such a network).
+ * GATRES_E_BADARG before any launch: what gatres_hydraulic_solve (gatres_hydraulic_series) refuses; link_kind, link_flags, minor
+ * or link_state NULL; Kp < 0 or Kp > P; Kp > 0 with a NULL pump array or speed (in the series: speed_mult or
+ * speed_pattern_of_pump NULL, or Ms < 1); Ms < 0; speed_stride neither 0 nor Kp; closed_stride neither 0 nor P, or not 0 with
+ * closed NULL; the LDS need above; an output, link_state included, overlapping an input or another output. */
+#define GATRES_HYD_PIPE 0
+#define GATRES_HYD_PUMP 1
+#define GATRES_HYD_LINK_CHECK 1
+#define GATRES_HYD_LINK_CLOSED 2
+int gatres_hydraulic_solve_links(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                                 const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                                 int32_t half_bandwidth, const double* demand, const double* roughness, const double* fixed_head,
+                                 int64_t fixed_head_stride, int64_t num_scenarios, int32_t num_nodes, int32_t num_pipes,
+                                 double accuracy, int32_t max_iter, float* pressure, double* head, double* flow, int32_t* status,
+                                 double* final_dq, const uint8_t* link_kind, const uint8_t* link_flags, const double* minor,
+                                 const int32_t* pump_link, const double* pump_h0, const double* pump_r, const double* pump_n,
+                                 int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+                                 int64_t closed_stride, uint8_t* link_state, void* stream);
+int gatres_hydraulic_series_links(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                                  const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                                  int32_t half_bandwidth, const int32_t* tank_node, const double* tank_area,
+                                  const double* tank_min_level, const double* tank_max_level, int32_t num_tanks,
+                                  const int32_t* pattern_of_node, const double* mult, int64_t mult_stride, int32_t num_patterns,
+                                  const double* demand, const double* roughness, const double* fixed_head,
+                                  int64_t fixed_head_stride, const double* initial_level, int64_t num_series, int32_t num_steps,
+                                  int32_t num_nodes, int32_t num_pipes, double dt, int32_t warm_start, double accuracy,
+                                  int32_t max_iter, float* pressure, double* head, double* flow, double* level, int32_t* status,
+                                  double* final_dq, const uint8_t* link_kind, const uint8_t* link_flags, const double* minor,
+                                  const int32_t* pump_link, const double* pump_h0, const double* pump_r, const double* pump_n,
+                                  int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+                                  int64_t closed_stride, const double* speed_mult, const int32_t* speed_pattern_of_pump,
+                                  int32_t num_speed_patterns, uint8_t* link_state, void* stream);
 
 const char* gatres_version(void);
 
