@@ -1,6 +1,7 @@
 // The hydraulic Newton loop, stated once for the two kernels of k_hydraulics.hip (hydraulic_solve_kernel: one steady scenario per
 // workgroup; hydraulic_series_kernel: one series of steps per workgroup) and their two counterparts with pumps, check valves,
-// closed links and minor losses in k_hydraulic_links.hip.  gatres.h states the model, the law at low flow, the link law and the
+// closed links and minor losses in k_hydraulic_links.hip; and, at the end, with the status machine of the regulating valves for the
+// two kernels of k_hydraulic_valves.hip.  gatres.h states the model, the law at low flow, the link law, the valves and the
 // solver.  Everything here works on one workgroup's LDS arrays; every sum runs in a fixed order.
 #pragma once
 #include "gatres_common.h"
@@ -242,6 +243,222 @@ __device__ __forceinline__ HyNewton hy_newton(const HyLds& L, const int* __restr
     out.rel = qs > 0.0 ? dqs / qs : (dqs > 0.0 ? __longlong_as_double(0x7FF0000000000000ll) : 0.0);
     out.converged = dqs <= accuracy * qs;
     if (out.converged) break;
+  }
+  return out;
+}
+
+// ---- THE REGULATING VALVES of gatres.h (k_hydraulic_valves.hip) -------------------------------------------------------------------
+// A regulating valve's link keeps, above the bits of the link law, what it is and where its status machine stands; a valve is
+// never a pump, so the bits of a pump's index are free.  OPEN is neither status bit.  fx[row] of a valve's controlled node is
+// HY_FX_VALVE while the valve is ACTIVE and 0 otherwise; a fixed-head node has 1 and is never a controlled node.
+constexpr int HY_VALVE = 1 << 30, HY_VALVE_ACTIVE = 1 << 29, HY_VALVE_CLOSED = 1 << 28, HY_VALVE_PSV = 1 << 27;
+constexpr int HY_FX_VALVE = 2;
+constexpr int HY_ST_OPEN = 0, HY_ST_ACTIVE = 3, HY_ST_CLOSED = 4;      // link_state of a regulating valve
+constexpr double HY_HTOL = 1.524e-4, HY_QTOL = 2.8316846592e-6;        // EPANET's 0.0005 ft and 0.0001 cfs
+
+struct HyValves {
+  double* hset;                                            // [Kv] the target head elevation[c] + setting of the scenario
+  int* link;                                               // [Kv] the valve's link
+  int* row;                                                // [Kv] solver row of the controlled node c
+  int* node;                                               // [Kv] c itself
+  int* chg;                                                // [Kv] 1 where the status changed in this iteration
+  int Kv;
+};
+
+__device__ __forceinline__ int hy_valve_status(int code) {
+  return (code & HY_VALVE_ACTIVE) ? HY_ST_ACTIVE : ((code & HY_VALVE_CLOSED) ? HY_ST_CLOSED : HY_ST_OPEN);
+}
+
+// The six rules of gatres.h: the next status from the old one, the new heads at the valve's ends and its new flow.
+__device__ __forceinline__ int hy_valve_next(bool psv, int st, double Ha, double Hb, double q, double hml, double hset) {
+  if (st != HY_ST_CLOSED) {
+    if (q < -HY_QTOL) return HY_ST_CLOSED;
+    if (!psv) {
+      if (st == HY_ST_ACTIVE) return Ha - hml < hset - HY_HTOL ? HY_ST_OPEN : HY_ST_ACTIVE;
+      return Hb >= hset + HY_HTOL ? HY_ST_ACTIVE : HY_ST_OPEN;
+    }
+    if (st == HY_ST_ACTIVE) return Hb + hml > hset + HY_HTOL ? HY_ST_OPEN : HY_ST_ACTIVE;
+    return Ha < hset - HY_HTOL ? HY_ST_ACTIVE : HY_ST_OPEN;
+  }
+  if (!psv) {
+    if (Ha >= hset + HY_HTOL && Hb < hset - HY_HTOL) return HY_ST_ACTIVE;
+    if (Ha < hset - HY_HTOL && Ha > Hb + HY_HTOL) return HY_ST_OPEN;
+    return HY_ST_CLOSED;
+  }
+  if (Hb > hset + HY_HTOL && Ha > Hb + HY_HTOL) return HY_ST_OPEN;
+  if (Ha >= hset + HY_HTOL && Ha > Hb + HY_HTOL) return HY_ST_ACTIVE;
+  return HY_ST_CLOSED;
+}
+
+struct HyNewtonValves {
+  HyNewton n;
+  int changes;                                             // status changes over all iterations
+};
+
+// hy_newton<true> with the status machine of the regulating valves; with Kv == 0 every operation on a double is the one of
+// hy_newton<true>, in the same order.  L.code carries the valves' bits (set by the caller: a valve that its input does not shut
+// starts with a status bit or none), L.fx the fixed-head nodes as 1; red[2] takes the iteration's count of changes.
+__device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const HyValves& V, const int* __restrict__ position,
+                                                           const double* dem, int N, int P, int W, int max_iter, double accuracy,
+                                                           int tid) {
+  const int BW = W + 1, Kv = V.Kv;
+  double *band = L.band, *y = L.y, *H = L.H, *q = L.q, *rr = L.rr, *pinv = L.pinv, *yv = L.yv, *red = L.red;
+  const int *sa = L.sa, *sb = L.sb;
+  int *fx = L.fx, *code = L.code;
+  HyNewtonValves out;
+  out.n.iters = 0;
+  out.n.converged = false;
+  out.n.failed = false;
+  out.n.rel = 0.0;
+  out.changes = 0;
+  for (int it = 1; it <= max_iter; ++it) {
+    out.n.iters = it;
+    // the law at the present flows and statuses; an ACTIVE valve is not in the matrix, and its controlled node is a fixed row
+    for (int p = tid; p < P; p += HY_T) {
+      int c = code[p];
+      if (c & HY_VALVE_ACTIVE) {
+        pinv[p] = 0.0;
+        yv[p] = 0.0;
+        continue;
+      }
+      if (c & HY_VALVE_CLOSED) c |= HY_SHUT;
+      double h, g;
+      link_headloss(q[p], rr[p], L.minor[p], c, L.pump + (size_t)((c & HY_PUMP) ? c >> HY_PUMP_SHIFT : 0) * HY_PUMP_REC, &h, &g);
+      pinv[p] = 1.0 / g;
+      yv[p] = h / g;
+    }
+    for (int k = tid; k < Kv; k += HY_T) {
+      const bool active = (code[V.link[k]] & HY_VALVE_ACTIVE) != 0;
+      fx[V.row[k]] = active ? HY_FX_VALVE : 0;
+      if (active) H[V.row[k]] = V.hset[k];
+    }
+    __syncthreads();
+    // assembly: one thread per row, over the pipes in pipe order; an ACTIVE valve's flow is a fixed draw at its two ends
+    for (int n = tid; n < N; n += HY_T) {
+      const int r = position[n];
+      double* row = band + (size_t)r * BW;
+      for (int k = 0; k < BW; ++k) row[k] = 0.0;
+      if (fx[r]) {
+        row[0] = 1.0;
+        y[r] = H[r];
+      } else {
+        double diag = 0.0, f = -dem[n];
+        for (int p = 0; p < P; ++p) {
+          const int a = sa[p], b = sb[p];
+          if (a != r && b != r) continue;
+          if (code[p] & HY_VALVE_ACTIVE) {
+            f = b == r ? f + q[p] : f - q[p];
+            continue;
+          }
+          const int o = a == r ? b : a;
+          const double pi = pinv[p], t = q[p] - yv[p];
+          diag += pi;
+          f = b == r ? f + t : f - t;
+          if (fx[o]) f += pi * H[o];
+          else if (o < r) row[r - o] -= pi;                // (r - o <= W: checked by the caller)
+        }
+        row[0] = diag;
+        y[r] = f;
+      }
+    }
+    __syncthreads();
+    // banded LDL^T and the substitutions, as in hy_newton
+    bool bad = false;
+    for (int j = 0; j < N; ++j) {
+      const double d = band[(size_t)j * BW];
+      if (!(d > 0.0) || !hy_finite(d)) {                   // (the same value in every thread)
+        bad = true;
+        break;
+      }
+      const int m = W < N - 1 - j ? W : N - 1 - j;
+      const double zj = y[j] / d;
+      for (int e = tid; e < m * m; e += HY_T) {
+        const int r = e / m + 1, c = e - (r - 1) * m + 1;
+        if (c <= r) {
+          const double vr = band[(size_t)(j + r) * BW + r], vc = band[(size_t)(j + c) * BW + c];
+          band[(size_t)(j + r) * BW + (r - c)] -= vr * (vc / d);
+        }
+      }
+      for (int t = tid; t < m; t += HY_T) y[j + 1 + t] -= band[(size_t)(j + 1 + t) * BW + (t + 1)] * zj;
+      __syncthreads();
+    }
+    if (bad) {
+      out.n.failed = true;
+      break;
+    }
+    for (int k = N - 1; k >= 0; --k) {
+      const double xk = y[k] / band[(size_t)k * BW];
+      const int m = W < k ? W : k;
+      for (int t = tid + 1; t <= m; t += HY_T) y[k - t] -= band[(size_t)k * BW + t] * xk;
+      if (tid == 0) H[k] = xk;
+      __syncthreads();
+    }
+    // the flows of every link that is not an ACTIVE valve
+    for (int p = tid; p < P; p += HY_T) {
+      if (code[p] & HY_VALVE_ACTIVE) continue;
+      const double dq = yv[p] - (H[sa[p]] - H[sb[p]]) * pinv[p], qn = q[p] - dq;
+      q[p] = qn;
+      pinv[p] = fabs(dq);
+      yv[p] = fabs(qn);
+    }
+    __syncthreads();
+    // one thread per valve: an ACTIVE valve's flow closes the mass balance at its controlled node over the other links in pipe
+    // order; then the status from the new heads and the valve's own new flow.  No valve shares a node with another (checked by
+    // the caller), so no thread reads a flow that another writes here.
+    for (int k = tid; k < Kv; k += HY_T) {
+      const int p = V.link[k], c = code[p];
+      V.chg[k] = 0;
+      if (c & HY_SHUT) continue;                           // shut by its input: a shut link, without a status
+      const int st = hy_valve_status(c), cr = V.row[k];
+      const bool psv = (c & HY_VALVE_PSV) != 0;
+      double qv = q[p];
+      if (st == HY_ST_ACTIVE) {
+        double inflow = 0.0;
+        for (int o = 0; o < P; ++o) {
+          if (o == p) continue;
+          if (sb[o] == cr) inflow += q[o];
+          if (sa[o] == cr) inflow -= q[o];
+        }
+        const double d = dem[V.node[k]], qn = psv ? inflow - d : d - inflow;
+        pinv[p] = fabs(qv - qn);
+        yv[p] = fabs(qn);
+        q[p] = qn;
+        qv = qn;
+      }
+      const double hml = (L.minor[p] * fabs(qv)) * qv;
+      const int ns = hy_valve_next(psv, st, H[sa[p]], H[sb[p]], qv, hml, V.hset[k]);
+      if (ns != st) {
+        V.chg[k] = 1;
+        code[p] = (c & ~(HY_VALVE_ACTIVE | HY_VALVE_CLOSED)) | (ns == HY_ST_ACTIVE ? HY_VALVE_ACTIVE : 0) |
+                  (ns == HY_ST_CLOSED ? HY_VALVE_CLOSED : 0);
+        if (ns == HY_ST_CLOSED) {                          // (its |dq| stays the one from before)
+          q[p] = 0.0;
+          yv[p] = 0.0;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid == 0 || tid == 64) {                           // one thread per sum, in pipe order
+      const double* v = tid == 0 ? pinv : yv;
+      double sum = 0.0;
+      for (int p = 0; p < P; ++p) sum += v[p];
+      red[tid == 0 ? 0 : 1] = sum;
+    } else if (tid == 128) {
+      int n = 0;
+      for (int k = 0; k < Kv; ++k) n += V.chg[k];
+      red[2] = (double)n;
+    }
+    __syncthreads();
+    const double dqs = red[0], qs = red[1];
+    const int changed = (int)red[2];
+    out.changes += changed;
+    if (!hy_finite(dqs) || !hy_finite(qs)) {
+      out.n.failed = true;
+      break;
+    }
+    out.n.rel = qs > 0.0 ? dqs / qs : (dqs > 0.0 ? __longlong_as_double(0x7FF0000000000000ll) : 0.0);
+    out.n.converged = dqs <= accuracy * qs && changed == 0;
+    if (out.n.converged) break;
   }
   return out;
 }

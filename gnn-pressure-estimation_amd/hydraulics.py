@@ -32,8 +32,49 @@ floor, so the system stays symmetric positive definite.  There is no status mach
 A link runs from the lower-numbered node to the higher one unless ``link_reversed`` says otherwise.  WHAT DOES NOT HOLD: a zone
 that CHECK or shut links cut off from every fixed-head node gets heads near -1e8 x demand and usually does not meet the stop
 rule; the constructor refuses a network in which that is so statically, and a scenario in which ``link_closed`` or a speed of 0
-causes it is not converged and is dropped by ``valid``, never repaired.  Pressure-regulating valves (PRV, PSV, PBV, FCV, GPV),
-power-rated pumps, controls and rules stay out of scope.  Parity with EPANET is not claimed and has not been checked.
+causes it is not converged and is dropped by ``valid``, never repaired.  PRV and PSV valves are the matter of THE REGULATING
+VALVES below; PBV, FCV and GPV valves, power-rated pumps, controls and rules stay out of scope.  Parity with EPANET is not
+claimed and has not been checked.
+
+THE REGULATING VALVES (gatres.h: THE REGULATING VALVES; csrc/k_hydraulic_valves.hip; ``_NewtonRef.run_valves``).  A network built
+with ``valve_links`` takes the two valves launches: the links launches with a status machine for pressure-reducing (PRV) and
+pressure-sustaining (PSV) valves.  A regulating valve is a link from a to b without pipe resistance (r = 0; its length and its
+roughness are not read, as for a pump) and with the minor-loss term m of any link (K = 0 is allowed).  It has a kind and a
+setting s, a pressure in metres, and one controlled node c: PRV c = b, the downstream end; PSV c = a, the upstream end.  The
+target head is hset = elevation[c] + s.  During the Newton loop it carries a status, OPEN, ACTIVE or CLOSED, and starts ACTIVE.
+Law by status -- OPEN: the PIPE branch of THE LINK LAW with r = 0 (with the linear floor where g < 1e-7, so K = 0 is a valve
+that loses nothing); CLOSED: g = 1e8, h = 1e8 q; ACTIVE: the link is not in the matrix at all.  Assembly: the controlled node of
+an ACTIVE valve is a fixed-head row at hset for that iteration -- the identity row that a reservoir's is, its neighbours take
+pi * hset on their right-hand side, no off-diagonal is written for it, so the band never widens -- and the valve's present flow
+q_v is a fixed draw, -q_v on the right-hand side of row a and +q_v on that of row b wherever that row is not fixed and not
+effectively fixed; every sum stays in pipe order.  Flows: after the head solve every link that is not ACTIVE updates as ever;
+each ACTIVE valve then takes the flow that closes the mass balance at c over the other links' new flows, added up in pipe order:
+PRV q_v = d_c - inflow, PSV q_v = inflow - d_c.  Status: every valve reads the new heads H_a, H_b and its own new q, all valves
+from the old statuses at once, with HTOL = 1.524e-4 m and QTOL = 2.8316846592e-6 m3/s (EPANET's 0.0005 ft and 0.0001 cfs) and
+hml = m |q| q (``valve_status_ref``):
+
+    PRV ACTIVE   q < -QTOL -> CLOSED; else H_a - hml < hset - HTOL -> OPEN; else ACTIVE
+    PRV OPEN     q < -QTOL -> CLOSED; else H_b >= hset + HTOL -> ACTIVE; else OPEN
+    PRV CLOSED   H_a >= hset + HTOL and H_b < hset - HTOL -> ACTIVE; else H_a < hset - HTOL and H_a > H_b + HTOL -> OPEN; else CLOSED
+    PSV ACTIVE   q < -QTOL -> CLOSED; else H_b + hml > hset + HTOL -> OPEN; else ACTIVE
+    PSV OPEN     q < -QTOL -> CLOSED; else H_a < hset - HTOL -> ACTIVE; else OPEN
+    PSV CLOSED   H_b > hset + HTOL and H_a > H_b + HTOL -> OPEN; else H_a >= hset + HTOL and H_a > H_b + HTOL -> ACTIVE; else CLOSED
+
+A valve that turns CLOSED gets q = 0.  Stop rule: sum |dq| <= accuracy * sum |q| AND no status changed in this iteration; the dq
+of a valve that has just closed is the one from before it was zeroed, the q in the sum the one after.  A valve shut by its
+static flag or by ``link_closed`` is a shut link as ever (state 2), and its status machine does not run.  ``link_state`` of a
+regulating valve: 0 OPEN, 3 ACTIVE, 4 CLOSED by its own status, 2 shut by input; ``valve_changes`` counts the status changes of
+a scenario or step.  In a series with ``warm_start`` the statuses carry over from step to step along with the flows; without it
+they start ACTIVE at every step; settings do not follow patterns.  Refused by the constructor (``ValueError``): a valve that is
+also a pump or a CHECK link, a controlled node that is a fixed-head node, two regulating valves that share any node, a setting
+that is not finite, and the two layouts in which the ACTIVE system is singular -- with all regulating valves removed, the
+uncontrolled end of every valve must still reach a fixed-head node (under the walk rules for CHECK and closed links), and every
+junction must reach a fixed-head node or the controlled node of some valve.  A scenario that still produces a bad pivot fails.
+WHAT DOES NOT HOLD: the valve's flow lags one iteration behind the heads, as in EPANET, so convergence across a valve is linear,
+not quadratic.  Statuses can cycle: such a scenario uses all its iterations, is not converged, and is dropped by ``valid``,
+never repaired.  An OPEN valve with K = 0 sits on the linear branch, where its flow jitters by 1e-7 m3/s per ulp of the heads
+(WHAT DOES NOT HOLD, below) and the stop rule is met by chance: give a valve a loss coefficient where that matters
+(``make_hydraulic_network`` does).  Parity with EPANET is not claimed.  FCV, PBV and GPV valves stay out of scope.
 
 THE SERIES (``simulate_series``, ``generate_series_store``; gatres.h: THE SERIES): extended-period simulation, T steps of
 ``step_seconds`` of one scenario in one launch, one workgroup per series.  Tanks are a subset of the fixed-head nodes: tank k
@@ -51,7 +92,7 @@ no failure and the series goes on from its flows.
 WHAT DOES NOT HOLD IN A SERIES: EPANET shortens a time step at the moment a tank becomes full or empty and closes the pipes of
 such a tank; this model clamps the level and does neither.  A step after which any level was clamped has status[s][t][3] = 1
 (``limited``), and volume is not conserved across such a step; ``series_valid`` and ``generate_series_store`` drop such series
-unless told otherwise.  Regulating valves, controls and rules stay out of scope.  The limit on flows that should be
+unless told otherwise.  Controls and rules stay out of scope.  The limit on flows that should be
 zero (below) carries over unchanged: a step with a zero multiplier will not meet the stop rule.
 
 WHAT DOES NOT HOLD: flows that should be zero do not come to rest on the linear branch.  A head of 100 m resolves 1.4e-14 m
@@ -67,7 +108,8 @@ the order of the upper end).
 
 Host restatements in numpy fp64 (the yardsticks of the tests): ``pipe_headloss``, ``solve_ref``, ``hydraulic_residuals``,
 ``hydraulic_draws``, ``tree_solution``, ``simulate_series_ref``, ``level_update_ref``, ``series_valid_ref``,
-``series_volume_balance``, ``link_headloss``, ``link_state_ref``, ``hydraulic_link_draws`` and ``pump_curve_from_points``.
+``series_volume_balance``, ``link_headloss``, ``link_state_ref``, ``hydraulic_link_draws``, ``pump_curve_from_points``,
+``valve_status_ref`` and ``hydraulic_valve_draws``.
 """
 from __future__ import annotations
 
@@ -115,6 +157,83 @@ HydraulicLinksResult = namedtuple("HydraulicLinksResult", HydraulicResult._field
 HydraulicLinksReference = namedtuple("HydraulicLinksReference", HydraulicReference._fields + ("link_state",))
 HydraulicSeriesLinksResult = namedtuple("HydraulicSeriesLinksResult", HydraulicSeriesResult._fields + ("link_state",))
 HydraulicSeriesLinksReference = namedtuple("HydraulicSeriesLinksReference", HydraulicSeriesReference._fields + ("link_state",))
+# what a network with regulating valves returns: the fields above, and valve_changes (status changes per scenario or step)
+HydraulicValvesResult = namedtuple("HydraulicValvesResult", HydraulicLinksResult._fields + ("valve_changes",))
+HydraulicValvesReference = namedtuple("HydraulicValvesReference", HydraulicLinksReference._fields + ("valve_changes", "margin"))
+HydraulicSeriesValvesResult = namedtuple("HydraulicSeriesValvesResult", HydraulicSeriesLinksResult._fields + ("valve_changes",))
+HydraulicSeriesValvesReference = namedtuple("HydraulicSeriesValvesReference",
+                                            HydraulicSeriesLinksReference._fields + ("valve_changes", "margin"))
+LINK_PRV, LINK_PSV = 2, 3               # GATRES_HYD_PRV, GATRES_HYD_PSV
+VALVE_OPEN, VALVE_ACTIVE, VALVE_CLOSED = 0, 3, 4      # link_state of a regulating valve (2: shut by input)
+VALVE_HTOL, VALVE_QTOL = 1.524e-4, 2.8316846592e-6    # EPANET's 0.0005 ft and 0.0001 cfs
+VALVE_KINDS = {"PRV": LINK_PRV, "PSV": LINK_PSV}
+
+
+def _valve_rule(psv: bool, status: int, Ha: float, Hb: float, q: float, hml: float, hset: float):
+    """One valve's next status by the six rules, and how far the comparisons it made were from their thresholds: (status,
+    margin in metres, margin in m3/s); a margin is +inf where no comparison of its kind was made."""
+    mh, mq = [np.inf], [np.inf]
+
+    def lt(x, y, m=mh):                                     # x < y, recorded
+        m[0] = min(m[0], abs(x - y))
+        return x < y
+
+    ge = lambda x, y: not lt(x, y)
+    gt = lambda x, y: lt(y, x)
+    lo, hi = hset - VALVE_HTOL, hset + VALVE_HTOL
+    if status != VALVE_CLOSED:
+        if lt(q, -VALVE_QTOL, mq):
+            return VALVE_CLOSED, mh[0], mq[0]
+        if not psv:
+            if status == VALVE_ACTIVE:
+                ns = VALVE_OPEN if lt(Ha - hml, lo) else VALVE_ACTIVE
+            else:
+                ns = VALVE_ACTIVE if ge(Hb, hi) else VALVE_OPEN
+        elif status == VALVE_ACTIVE:
+            ns = VALVE_OPEN if gt(Hb + hml, hi) else VALVE_ACTIVE
+        else:
+            ns = VALVE_ACTIVE if lt(Ha, lo) else VALVE_OPEN
+    elif not psv:
+        if ge(Ha, hi) and lt(Hb, lo):
+            ns = VALVE_ACTIVE
+        elif lt(Ha, lo) and gt(Ha, Hb + VALVE_HTOL):
+            ns = VALVE_OPEN
+        else:
+            ns = VALVE_CLOSED
+    else:
+        if gt(Hb, hi) and gt(Ha, Hb + VALVE_HTOL):
+            ns = VALVE_OPEN
+        elif ge(Ha, hi) and gt(Ha, Hb + VALVE_HTOL):
+            ns = VALVE_ACTIVE
+        else:
+            ns = VALVE_CLOSED
+    return ns, mh[0], mq[0]
+
+
+def valve_status_ref(kind, status, head_a, head_b, q, minor, hset) -> np.ndarray:
+    """THE REGULATING VALVES, the six status rules, elementwise: the next status (``VALVE_OPEN``, ``VALVE_ACTIVE``,
+    ``VALVE_CLOSED``) of valves of ``kind`` ("PRV" / "PSV" or ``LINK_PRV`` / ``LINK_PSV``) at ``status`` from the new heads at their
+    ends, their own new flow, their minor-loss term m (hml = (m |q|) q) and their target head."""
+    kinds = np.array([VALVE_KINDS.get(k, k) for k in np.atleast_1d(kind)])
+    args = np.broadcast_arrays(kinds, *[np.asarray(v, dtype=np.float64) for v in (status, head_a, head_b, q, minor, hset)])
+    out = np.empty(args[0].shape, dtype=np.uint8)
+    for i in np.ndindex(out.shape):
+        k, st, ha, hb, qv, m, hs = (a[i] for a in args)
+        if k not in (LINK_PRV, LINK_PSV) or int(st) not in (VALVE_OPEN, VALVE_ACTIVE, VALVE_CLOSED):
+            raise ValueError("valve_status_ref takes kinds PRV / PSV and statuses OPEN, ACTIVE, CLOSED")
+        out[i] = _valve_rule(k == LINK_PSV, int(st), float(ha), float(hb), float(qv), (float(m) * abs(float(qv))) * float(qv), float(hs))[0]
+    return out
+
+
+def valves_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_pumps: int, num_valves: int) -> int:
+    """What a workgroup of ``gatres_hydraulic_solve_valves`` takes of the LDS (gatres.h states the same sum): the arrays of the
+    links launch, and per valve hset, its link, the row and the node of c and a change flag."""
+    return links_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_pumps) + 24 * num_valves
+
+
+def series_valves_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_tanks: int, num_pumps: int, num_valves: int) -> int:
+    """What a workgroup of ``gatres_hydraulic_series_valves`` takes of the LDS (gatres.h states the same sum)."""
+    return series_links_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_tanks, num_pumps) + 24 * num_valves
 
 
 def pipe_headloss(q, r) -> Tuple[np.ndarray, np.ndarray]:
@@ -161,12 +280,18 @@ def link_headloss(q, r, minor=0.0, pump=False, check=False, shut=False, h0=0.0, 
     return h, g
 
 
-def link_state_ref(q, pump=False, check=False, shut=False, speed=1.0) -> np.ndarray:
-    """``link_state`` of gatres.h at the flows q: 0 forward, 1 a CHECK link on its reverse branch, 2 shut."""
+def link_state_ref(q, pump=False, check=False, shut=False, speed=1.0, valve_status=None) -> np.ndarray:
+    """``link_state`` of gatres.h at the flows q: 0 forward, 1 a CHECK link on its reverse branch, 2 shut.  ``valve_status``: per
+    link, the status of a regulating valve (0 OPEN, 3 ACTIVE, 4 CLOSED) and -1 where the link is none; a valve that its input
+    shuts is 2 like any link."""
     q, pump = np.asarray(q, dtype=np.float64), np.asarray(pump, dtype=bool)
     closed = np.asarray(shut, dtype=bool) | (pump & (np.asarray(speed, dtype=np.float64) == 0))
     reverse = (np.asarray(check, dtype=bool) | pump) & (q < 0)
-    return np.where(closed, 2, np.where(reverse, 1, 0)).astype(np.uint8)
+    state = np.where(reverse, 1, 0)
+    if valve_status is not None:
+        vs = np.asarray(valve_status)
+        state = np.where(vs >= 0, vs, state)
+    return np.where(closed, 2, state).astype(np.uint8)
 
 
 def pump_curve_from_points(flows, heads) -> Tuple[float, float, float]:
@@ -259,6 +384,22 @@ def hydraulic_link_draws(seed: int, first_scenario: int, num_scenarios: int, d_l
     return demand, np.ascontiguousarray(cells[:, :P]), np.ascontiguousarray(cells[:, P:P + num_pumps]), closed
 
 
+def hydraulic_valve_draws(seed: int, first_scenario: int, num_scenarios: int, d_lo, d_hi, c_lo, c_hi, num_pumps: int,
+                          num_valves: int, valve_setting_range, pump_speed_range=None, closed_probability: float = 0.0):
+    """What ``generate_store(valve_setting_range=)`` draws, in numpy, bit for bit: the four arrays of ``hydraulic_link_draws``,
+    unchanged by the Kv cells that come AFTER all of theirs, and valve_setting [S, Kv], uniform in ``valve_setting_range``."""
+    P = np.asarray(c_lo).shape[0]
+    lo, hi = link_draw_ranges(c_lo, c_hi, num_pumps, pump_speed_range)
+    v_lo, v_hi = float(valve_setting_range[0]), float(valve_setting_range[1])
+    if not (np.isfinite(v_lo) and np.isfinite(v_hi) and v_lo <= v_hi):
+        raise ValueError("valve_setting_range must be lo <= hi, finite")
+    lo, hi = np.concatenate([lo, np.full(num_valves, v_lo)]), np.concatenate([hi, np.full(num_valves, v_hi)])
+    demand, cells = hydraulic_draws(seed, first_scenario, num_scenarios, d_lo, d_hi, lo, hi)
+    closed = (cells[:, P + num_pumps:2 * P + num_pumps] < float(closed_probability)).astype(np.uint8)
+    return (demand, np.ascontiguousarray(cells[:, :P]), np.ascontiguousarray(cells[:, P:P + num_pumps]), closed,
+            np.ascontiguousarray(cells[:, 2 * P + num_pumps:]))
+
+
 def _half_bandwidth(pipes: np.ndarray, fixed: np.ndarray, position: np.ndarray) -> int:
     both = ~fixed[pipes[:, 0]] & ~fixed[pipes[:, 1]]
     if not both.any():
@@ -312,12 +453,16 @@ class HydraulicNetwork:
     ``junctions`` are the nodes of a generated store and ``junction_edge_index`` its graph: the pipes between two junctions,
     renumbered.  A junction whose every pipe leads to a fixed-head node keeps no edge there; such nodes are listed in
     ``isolated_junctions`` (a model sees them without neighbours -- drop them from the sensor set, or model the reservoir's
-    neighbour as the fixed node)."""
+    neighbour as the fixed node).
+
+    REGULATING VALVES (the module's docstring: THE REGULATING VALVES): ``valve_links`` [Kv] links, ``valve_kind`` "PRV" / "PSV" (one
+    for all, or one per valve), ``valve_setting`` [Kv] pressures in metres; a valve runs from a to b as its link does
+    (``link_reversed``), its ``minor_loss`` K may be 0, its length is not read.  ``valve_node`` holds the controlled nodes."""
 
     def __init__(self, edge_index, length, diameter, elevation, fixed_nodes: Sequence[int], fixed_head,
                  start_velocity: float = START_VELOCITY, device=None, tank_nodes=None, tank_diameter=None, tank_min_level=None,
                  tank_max_level=None, minor_loss=None, check_valve=None, closed=None, pump_links=None, pump_h0=None, pump_r=None,
-                 pump_n=None, pump_q_start=None, link_reversed=None):
+                 pump_n=None, pump_q_start=None, link_reversed=None, valve_links=None, valve_kind=None, valve_setting=None):
         ei = torch.as_tensor(edge_index).detach().cpu()
         if ei.dim() != 2 or ei.shape[0] != 2 or ei.dtype != torch.int64:
             raise ValueError("edge_index must be int64 [2, E]")
@@ -366,8 +511,29 @@ class HydraulicNetwork:
         if (minor_k[is_pump] != 0).any():
             raise ValueError("a pump has no minor loss")
         pipes[flip] = pipes[flip][:, ::-1]                  # a reversed link runs from its higher node to its lower one
+        # the regulating valves (THE REGULATING VALVES): none by default
+        valves = np.asarray([] if valve_links is None else valve_links, dtype=np.int64).reshape(-1)
+        Kv = int(valves.size)
+        if Kv and (valves.min() < 0 or valves.max() >= P or np.unique(valves).size != Kv):
+            raise ValueError("valve_links must be distinct links of the network")
+        v_names = [] if valve_kind is None else ([valve_kind] * Kv if isinstance(valve_kind, str) else list(valve_kind))
+        if len(v_names) != Kv or any(k not in VALVE_KINDS for k in v_names):
+            raise ValueError(f"valve_kind must be 'PRV' or 'PSV', one per valve ({Kv})")
+        v_kind = np.array([VALVE_KINDS[k] for k in v_names], dtype=np.uint8)
+        v_set = np.asarray([] if valve_setting is None else valve_setting, dtype=np.float64).reshape(-1)
+        if v_set.shape[0] != Kv or not np.isfinite(v_set).all():
+            raise ValueError(f"valve_setting must have one finite pressure per valve ({Kv})")
+        is_valve = np.zeros(P, dtype=bool)
+        is_valve[valves] = True
+        if (is_valve & (is_pump | check)).any():
+            raise ValueError("a regulating valve is neither a pump nor a CHECK link")
+        v_ctrl = np.where(v_kind == LINK_PRV, pipes[valves, 1], pipes[valves, 0]).astype(np.int64)      # c: PRV b, PSV a
+        v_free = np.where(v_kind == LINK_PRV, pipes[valves, 0], pipes[valves, 1]).astype(np.int64)      # the uncontrolled end
+        if np.unique(pipes[valves].reshape(-1)).size != 2 * Kv:
+            raise ValueError("two regulating valves share a node")
+        length = np.where(is_valve, 0.0, length)            # (a valve's length is not read)
         throttle = (length == 0) & (minor_k > 0)            # r = 0 with m > 0: a throttle valve
-        if not (np.isfinite(length).all() and ((length > 0) | throttle | is_pump).all()
+        if not (np.isfinite(length).all() and ((length > 0) | throttle | is_pump | is_valve).all()
                 and np.isfinite(diameter).all() and (diameter > 0).all()):
             raise ValueError("lengths and diameters must be positive and finite")
         if not np.isfinite(elevation).all():
@@ -380,21 +546,37 @@ class HydraulicNetwork:
             raise ValueError("fixed_head must have one finite head per fixed node")
         fixed = np.zeros(N, dtype=bool)
         fixed[fixed_nodes] = True
-        reach = fixed.copy()                                # every junction is fed from a fixed-head node
+        if Kv and fixed[v_ctrl].any():
+            raise ValueError("the controlled node of a regulating valve is a fixed-head node")
         adj = [[] for _ in range(N)]
-        for p, (a, b) in enumerate(pipes):                  # a CHECK link is walked from a to b only, a closed one not at all
-            if shut[p]:
+        for p, (a, b) in enumerate(pipes):                  # a CHECK link is walked from a to b only, a closed one not at all,
+            if shut[p] or is_valve[p]:                      # and a regulating valve not at all: ACTIVE, it is not in the matrix
                 continue
             adj[a].append(int(b))
             if not (check[p] or is_pump[p]):
                 adj[b].append(int(a))
-        stack = [int(v) for v in fixed_nodes]
-        while stack:
-            v = stack.pop()
-            for w in adj[v]:
-                if not reach[w]:
-                    reach[w] = True
-                    stack.append(w)
+
+        def walk(sources):
+            reach = np.zeros(N, dtype=bool)
+            reach[sources] = True
+            stack = [int(v) for v in sources]
+            while stack:
+                v = stack.pop()
+                for w in adj[v]:
+                    if not reach[w]:
+                        reach[w] = True
+                        stack.append(w)
+            return reach
+
+        reach = walk(fixed_nodes)                           # every junction is fed from a fixed-head node
+        if Kv:                                              # the two rules without which the ACTIVE system is singular
+            if not reach[v_free].all():
+                raise ValueError(f"the uncontrolled end of the regulating valves {valves[~reach[v_free]][:8].tolist()} does not "
+                                 "reach a fixed-head node with all regulating valves removed")
+            reach = walk(np.concatenate([fixed_nodes, v_ctrl]))
+            if not reach.all():
+                raise ValueError(f"junctions {np.flatnonzero(~reach)[:8].tolist()} reach neither a fixed-head node nor the "
+                                 "controlled node of a regulating valve with all regulating valves removed")
         if not reach.all():
             raise ValueError(f"junctions {np.flatnonzero(~reach)[:8].tolist()} are not connected to a fixed-head node")
 
@@ -435,6 +617,12 @@ class HydraulicNetwork:
         self.num_pumps, self.pump_links, self.pump_h0, self.pump_r, self.pump_n = Kp, pumps, p_h0, p_r, p_n
         self.is_pump, self.check_valve, self.closed, self.minor_loss = is_pump, check | is_pump, shut, minor_k
         self.link_kind = is_pump.astype(np.uint8) * LINK_PUMP
+        self.link_kind[valves] = v_kind
+        # the valve arrays of gatres_hydraulic_solve_valves
+        self.num_valves, self.valve_links, self.valve_kind, self.valve_setting = Kv, valves, v_kind, v_set
+        self.valve_kind_names = tuple(v_names)
+        self.is_valve, self.valve_node, self.has_valves = is_valve, v_ctrl, Kv > 0
+        self.coef[valves] = 0.0                             # (a valve has no resistance; its coef is not read)
         self.link_flags = (check.astype(np.uint8) * LINK_CHECK) | (shut.astype(np.uint8) * LINK_CLOSED)
         self.minor = 8.0 * minor_k / (np.pi ** 2 * GRAVITY * np.power(diameter, 4))
         self.has_links = bool(Kp or check.any() or shut.any() or (minor_k > 0).any())
@@ -461,6 +649,8 @@ class HydraulicNetwork:
             self.order, self.position = identity, identity.copy()
         self.half_bandwidth = max(1, _half_bandwidth(pipes, fixed, self.position))
         need = links_lds_bytes(N, P, self.half_bandwidth, Kp) if self.has_links else lds_bytes(N, P, self.half_bandwidth)
+        if Kv:
+            need = series_valves_lds_bytes(N, P, self.half_bandwidth, K, Kp, Kv) if K else valves_lds_bytes(N, P, self.half_bandwidth, Kp, Kv)
         if need > LDS_BUDGET:
             raise ValueError(f"the band of {N} rows with half-bandwidth {self.half_bandwidth} needs "
                              f"{need} bytes of LDS, the kernel has {LDS_BUDGET}")
@@ -540,6 +730,28 @@ class HydraulicNetwork:
                 pp(st["pump_h0"]), pp(st["pump_r"]), pp(st["pump_n"]), Kp, pp(speed), speed_stride, _native.ptr(closed),
                 closed_stride], link_state, (speed, closed)
 
+    def _valve_args(self, S: int, changes_shape, valve_setting):
+        """The five valve arguments of the two valves launches before ``valve_changes``, that tensor, and the setting tensor of
+        this call, which the caller holds until the launch is queued."""
+        st, dev, Kv = self.static(), self._dev(), self.num_valves
+        if "valve_link" not in st:
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+            st.update({"valve_link": up(self.valve_links, np.int32), "valve_kind": up(self.valve_kind, np.uint8),
+                       "valve_setting": up(self.valve_setting, np.float64)})
+        if valve_setting is None:
+            setting, stride = st["valve_setting"], 0
+        else:
+            setting = torch.as_tensor(valve_setting, dtype=torch.float64).to(dev).contiguous()
+            if tuple(setting.shape) == (Kv,):
+                stride = 0
+            elif tuple(setting.shape) == (S, Kv):
+                stride = Kv
+            else:
+                raise ValueError(f"valve_setting must be [{Kv}] or [{S}, {Kv}]")
+        changes = torch.empty(changes_shape, dtype=torch.int32, device=dev)
+        vp = (lambda t: t.data_ptr()) if Kv else (lambda t: None)
+        return [vp(st["valve_link"]), vp(st["valve_kind"]), vp(setting), stride, Kv], changes, setting
+
     def _f64(self, a, shape, name) -> torch.Tensor:
         t = torch.as_tensor(a, dtype=torch.float64).to(self._dev()).contiguous()
         if tuple(t.shape) != tuple(shape):
@@ -563,37 +775,61 @@ class HydraulicNetwork:
         """``gatres_hydraulic_draw`` over the N + P cells of a scenario and the Kp + P link cells after them (``x_lo``, ``x_hi``:
         ``link_draw_ranges`` on the device): (demand [S, N], roughness [S, P], pump_speed [S, Kp], link_closed uint8 [S, P]).
         ``hydraulic_link_draws`` restates it."""
+        return self.draw_valves(num_scenarios, seed, first_scenario, d_lo, d_hi, x_lo, x_hi, closed_probability)[:4]
+
+    def draw_valves(self, num_scenarios: int, seed: int, first_scenario: int, d_lo: torch.Tensor, d_hi: torch.Tensor,
+                    x_lo: torch.Tensor, x_hi: torch.Tensor, closed_probability: float):
+        """``draw_links`` with the valve cells behind the link cells where ``x_lo``, ``x_hi`` hold their ranges (Kv more entries,
+        or none): the four arrays of ``draw_links`` and valve_setting [S, Kv] or [S, 0].  ``hydraulic_valve_draws`` restates it."""
         dev, lib, P, Kp = self._dev(), _native.load(), self.num_pipes, self.num_pumps
+        C = int(x_lo.shape[0])
+        if C not in (2 * P + Kp, 2 * P + Kp + self.num_valves):
+            raise ValueError("the ranges of the link cells do not fit the network")
         demand = torch.empty((num_scenarios, self.num_nodes), dtype=torch.float64, device=dev)
-        cells = torch.empty((num_scenarios, 2 * P + Kp), dtype=torch.float64, device=dev)
+        cells = torch.empty((num_scenarios, C), dtype=torch.float64, device=dev)
         rc = lib.gatres_hydraulic_draw(d_lo.data_ptr(), d_hi.data_ptr(), x_lo.data_ptr(), x_hi.data_ptr(), num_scenarios,
-                                       self.num_nodes, 2 * P + Kp, seed % (1 << 64), first_scenario, demand.data_ptr(),
+                                       self.num_nodes, C, seed % (1 << 64), first_scenario, demand.data_ptr(),
                                        cells.data_ptr(), _native.current_stream(dev))
         _native.check(rc, "gatres_hydraulic_draw")
-        closed = (cells[:, P + Kp:] < float(closed_probability)).to(torch.uint8).contiguous()
-        return demand, cells[:, :P].contiguous(), cells[:, P:P + Kp].contiguous(), closed
+        closed = (cells[:, P + Kp:2 * P + Kp] < float(closed_probability)).to(torch.uint8).contiguous()
+        return (demand, cells[:, :P].contiguous(), cells[:, P:P + Kp].contiguous(), closed, cells[:, 2 * P + Kp:].contiguous())
 
-    def _link_draw_setup(self, ranges, pump_speed_range, closed_probability):
-        """None where a store is generated without link draws (the call it always was), else the device ranges of ``draw_links``."""
-        if pump_speed_range is None and not closed_probability:
+    def _link_draw_setup(self, ranges, pump_speed_range, closed_probability, valve_setting_range=None):
+        """None where a store is generated without link draws (the call it always was), else the device ranges of ``draw_links``
+        (of ``draw_valves``: with ``valve_setting_range`` the Kv valve cells come after all the others)."""
+        if pump_speed_range is None and not closed_probability and valve_setting_range is None:
             return None
+        if valve_setting_range is not None and self.num_valves == 0:
+            raise ValueError("valve_setting_range needs a network with regulating valves")
         if not 0.0 <= float(closed_probability) < 1.0:
             raise ValueError("closed_probability must lie in [0, 1)")
         if pump_speed_range is not None and self.num_pumps == 0:
             raise ValueError("pump_speed_range needs a network with pumps")
         lo, hi = link_draw_ranges(ranges[2], ranges[3], self.num_pumps, pump_speed_range)
+        if valve_setting_range is not None:
+            v_lo, v_hi = float(valve_setting_range[0]), float(valve_setting_range[1])
+            if not (np.isfinite(v_lo) and np.isfinite(v_hi) and v_lo <= v_hi):
+                raise ValueError("valve_setting_range must be lo <= hi, finite")
+            lo, hi = np.concatenate([lo, np.full(self.num_valves, v_lo)]), np.concatenate([hi, np.full(self.num_valves, v_hi)])
         return torch.from_numpy(lo).to(self._dev()), torch.from_numpy(hi).to(self._dev())
 
     def simulate(self, demand, roughness, fixed_head=None, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
-                 want_head: bool = True, want_flow: bool = True, pump_speed=None, link_closed=None, links=None) -> HydraulicResult:
+                 want_head: bool = True, want_flow: bool = True, pump_speed=None, link_closed=None, links=None,
+                 valve_setting=None, valves=None) -> HydraulicResult:
         """Solve S scenarios on the device.  ``demand`` [S, N] m3/s (ignored at fixed nodes), ``roughness`` [S, P]
         Hazen-Williams coefficients, ``fixed_head`` None (the network's), [N] or [S, N] (read at fixed nodes).  Every field
         of the result is a device tensor; nothing is read back.  A network with a special link or a minor loss (or
         ``pump_speed`` [Kp] / [S, Kp], default 1; ``link_closed`` bytes [P] / [S, P]; or ``links=True``) takes
         ``gatres_hydraulic_solve_links`` and returns a ``HydraulicLinksResult``: the same fields and ``link_state`` uint8 [S, P].
-        A network of pipes takes ``gatres_hydraulic_solve`` as it always did."""
+        A network of pipes takes ``gatres_hydraulic_solve`` as it always did.  A network with a regulating valve (or
+        ``valve_setting`` [Kv] / [S, Kv] metres of pressure, default the network's; or ``valves=True``) takes
+        ``gatres_hydraulic_solve_valves`` and returns a ``HydraulicValvesResult``: the links fields and ``valve_changes`` int32 [S]."""
         st, dev, lib = self.static(), self._dev(), _native.load()
-        with_links = bool(links) if links is not None else (self.has_links or pump_speed is not None or link_closed is not None)
+        with_valves = bool(valves) if valves is not None else (self.has_valves or valve_setting is not None)
+        if self.has_valves and not with_valves:
+            raise ValueError("a network with regulating valves takes the valves launch")
+        with_links = with_valves or (bool(links) if links is not None else
+                                     (self.has_links or pump_speed is not None or link_closed is not None))
         N, P = self.num_nodes, self.num_pipes
         demand = torch.as_tensor(demand)
         if demand.dim() != 2:
@@ -618,6 +854,20 @@ class HydraulicNetwork:
         flow = torch.empty((S, P), dtype=torch.float64, device=dev) if want_flow else None
         status = torch.empty((S, HYD_STATUS), dtype=torch.int32, device=dev)
         final_dq = torch.empty((S,), dtype=torch.float64, device=dev)
+        if with_valves:
+            link_args, link_state, _held = self._link_args(S, (S, P), pump_speed, link_closed)
+            valve_args, changes, _held_v = self._valve_args(S, (S,), valve_setting)
+            rc = lib.gatres_hydraulic_solve_valves(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
+                                                   st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
+                                                   st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
+                                                   demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P,
+                                                   float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head),
+                                                   _native.ptr(flow), status.data_ptr(), final_dq.data_ptr(), *link_args,
+                                                   link_state.data_ptr(), *valve_args, changes.data_ptr(),
+                                                   _native.current_stream(dev))
+            _native.check(rc, "gatres_hydraulic_solve_valves")
+            return HydraulicValvesResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status, final_dq,
+                                         link_state, changes)
         if with_links:
             link_args, link_state, _held = self._link_args(S, (S, P), pump_speed, link_closed)
             rc = lib.gatres_hydraulic_solve_links(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
@@ -655,7 +905,7 @@ class HydraulicNetwork:
     def simulate_series(self, demand, roughness, multipliers, *, step_seconds: float, initial_level=None, pattern_of_node=None,
                         fixed_head=None, warm_start: bool = True, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
                         want_head: bool = True, want_flow: bool = True, pump_speed=None, link_closed=None, speed_multipliers=None,
-                        speed_pattern_of_pump=None, links=None) -> HydraulicSeriesResult:
+                        speed_pattern_of_pump=None, links=None, valve_setting=None, valves=None) -> HydraulicSeriesResult:
         """``gatres_hydraulic_series``: S series of T steps on the device, one launch.  ``demand`` [S, N] base demands,
         ``roughness`` [S, P], ``multipliers`` [M, T] (for every series) or [S, M, T], ``pattern_of_node`` int [N] with values in
         [0, M) (default: pattern 0 everywhere; host data outside the range raises ``ValueError``, a DEVICE tensor is not read back
@@ -666,10 +916,18 @@ class HydraulicNetwork:
         special link or a minor loss (or one of the link arguments, or ``links=True``) takes ``gatres_hydraulic_series_links`` and
         returns a ``HydraulicSeriesLinksResult`` with ``link_state`` uint8 [S, T, P]: ``pump_speed`` and ``link_closed`` as in
         ``simulate``, ``speed_multipliers`` [Ms, T] (default ones) and ``speed_pattern_of_pump`` int [Kp] (default 0); pump k
-        runs at pump_speed[s][k] * speed_multipliers[pattern][t] in step t, and 0 switches it off for that step."""
+        runs at pump_speed[s][k] * speed_multipliers[pattern][t] in step t, and 0 switches it off for that step.  A network with
+        a regulating valve (or ``valve_setting`` [Kv] / [S, Kv], or ``valves=True``) takes ``gatres_hydraulic_series_valves`` and
+        returns a ``HydraulicSeriesValvesResult`` with ``valve_changes`` int32 [S, T]; with ``warm_start`` the statuses carry over
+        from step to step, without it they start ACTIVE at every step.  The series launch takes 8 N bytes of LDS more than the
+        steady one; a network with valves and without tanks that the constructor accepted for ``simulate`` but whose series does
+        not fit is refused here with ``ValueError``."""
         st, dev, lib = self.static(), self._dev(), _native.load()
-        with_links = bool(links) if links is not None else (
-            self.has_links or any(v is not None for v in (pump_speed, link_closed, speed_multipliers, speed_pattern_of_pump)))
+        with_valves = bool(valves) if valves is not None else (self.has_valves or valve_setting is not None)
+        if self.has_valves and not with_valves:
+            raise ValueError("a network with regulating valves takes the valves launch")
+        with_links = with_valves or (bool(links) if links is not None else (
+            self.has_links or any(v is not None for v in (pump_speed, link_closed, speed_multipliers, speed_pattern_of_pump))))
         N, P, K = self.num_nodes, self.num_pipes, self.num_tanks
         demand = torch.as_tensor(demand)
         if demand.dim() != 2:
@@ -739,6 +997,25 @@ class HydraulicNetwork:
             if spat.shape != (Kp,) or (Kp and (spat.min() < 0 or spat.max() >= smult.shape[0])):
                 raise ValueError(f"speed_pattern_of_pump must be [{Kp}] with values in [0, {int(smult.shape[0])})")
             spat = torch.from_numpy(spat.astype(np.int32)).to(dev)
+            if with_valves:
+                need = series_valves_lds_bytes(N, P, self.half_bandwidth, K, Kp, self.num_valves)
+                if need > LDS_BUDGET:                       # (the constructor held a network without tanks to the steady launch's sum)
+                    raise ValueError(f"a series on the band of {N} rows with half-bandwidth {self.half_bandwidth} needs {need} bytes "
+                                     f"of LDS, the kernel has {LDS_BUDGET}")
+                valve_args, changes, _held_v = self._valve_args(S, (S, T), valve_setting)
+                rc = lib.gatres_hydraulic_series_valves(
+                    st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
+                    st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
+                    self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
+                    pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(),
+                    stride, tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0, float(accuracy), int(max_iter),
+                    pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(level), status.data_ptr(), final_dq.data_ptr(),
+                    *link_args, smult.data_ptr() if Kp else None, spat.data_ptr() if Kp else None,
+                    int(smult.shape[0]) if Kp else 0, link_state.data_ptr(), *valve_args, changes.data_ptr(),
+                    _native.current_stream(dev))
+                _native.check(rc, "gatres_hydraulic_series_valves")
+                return HydraulicSeriesValvesResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
+                                                   status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq, link_state, changes)
             rc = lib.gatres_hydraulic_series_links(
                 st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
                 st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
@@ -805,7 +1082,7 @@ class HydraulicNetwork:
                               pressure_range: Tuple[float, float] = (0.0, 150.0), chunk: int = 256, normalize: bool = True,
                               allow_limited: bool = False, warm_start: bool = True, accuracy: float = ACCURACY,
                               max_iter: int = MAX_ITER, pump_speed_range=None, closed_probability: float = 0.0,
-                              speed_multipliers=None, speed_pattern_of_pump=None):
+                              speed_multipliers=None, speed_pattern_of_pump=None, valve_setting_range=None):
         """Draw, simulate and filter ``num_series`` series of ``steps`` steps into a ``SnapshotStore`` over the junctions whose
         rows are series-major (E * steps rows for E kept series: what ``monitor_store(series_length=steps)`` expects).  Base
         demands and roughness per series come from ``draw``, the initial levels from ``draw_levels``; ``multipliers`` default to
@@ -815,7 +1092,8 @@ class HydraulicNetwork:
         series counted once by the first cause in that order (``series_report``), and gives max_iterations, mean_iterations
         (over the steps that did not fail), mean_iterations_first_step and series_length.  ``RuntimeError`` when nothing is
         kept.  ``pump_speed_range`` and ``closed_probability`` as in ``generate_store``, per series (a closure holds for the whole
-        series); ``speed_multipliers`` and ``speed_pattern_of_pump`` go to ``simulate_series``."""
+        series); ``speed_multipliers`` and ``speed_pattern_of_pump`` go to ``simulate_series``; ``valve_setting_range`` as in
+        ``generate_store``, per series and valve."""
         if num_series < 1 or chunk < 1 or steps < 1:
             raise ValueError("num_series, steps and chunk must be positive")
         st, dev = self.static(), self._dev()
@@ -827,7 +1105,7 @@ class HydraulicNetwork:
             raise ValueError(f"multipliers must be [M, {steps}]")
         host_ranges = self.draw_ranges(demand_range, roughness_range)
         ranges = [torch.from_numpy(a).to(dev) for a in host_ranges]
-        link_ranges = self._link_draw_setup(host_ranges, pump_speed_range, closed_probability)
+        link_ranges = self._link_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range)
         link_kw = {k: v for k, v in (("speed_multipliers", speed_multipliers), ("speed_pattern_of_pump", speed_pattern_of_pump))
                    if v is not None}
         lv = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in self.level_ranges(level_range)]
@@ -837,9 +1115,11 @@ class HydraulicNetwork:
             if link_ranges is None:
                 demand, roughness = self.draw(n, seed, first, *ranges)
             else:
-                demand, roughness, speed, closed = self.draw_links(n, seed, first, ranges[0], ranges[1], *link_ranges,
-                                                                   closed_probability)
+                demand, roughness, speed, closed, setting = self.draw_valves(n, seed, first, ranges[0], ranges[1], *link_ranges,
+                                                                             closed_probability)
                 link_kw.update(pump_speed=speed if self.num_pumps else None, link_closed=closed)
+                if valve_setting_range is not None:
+                    link_kw.update(valve_setting=setting)
             level0 = self.draw_levels(n, seed, first, *lv)
             res = self.simulate_series(demand, roughness, mult, step_seconds=step_seconds, initial_level=level0,
                                        pattern_of_node=pattern_of_node, warm_start=warm_start, accuracy=accuracy,
@@ -872,7 +1152,8 @@ class HydraulicNetwork:
 
     def generate_store(self, num_scenarios: int, seed: int, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE,
                        pressure_range: Tuple[float, float] = (0.0, 150.0), chunk: int = 1024, normalize: bool = True,
-                       accuracy: float = ACCURACY, max_iter: int = MAX_ITER, pump_speed_range=None, closed_probability: float = 0.0):
+                       accuracy: float = ACCURACY, max_iter: int = MAX_ITER, pump_speed_range=None, closed_probability: float = 0.0,
+                       valve_setting_range=None):
         """Draw, solve and filter ``num_scenarios`` scenarios into a ``SnapshotStore`` over the junctions (pressures in metres
         before the store's normalisation).  Per chunk: draw -> solve -> valid, ONE read-back (status and the valid bytes as one
         tensor), a device ``index_select`` of the kept rows.  Returns ``(store, report)``; the report counts drawn, converged,
@@ -883,13 +1164,15 @@ class HydraulicNetwork:
         ``pump_speed_range`` (lo, hi) draws a speed per scenario and pump, ``closed_probability`` closes every link of a scenario
         with that probability (``draw_links``: new cells after the existing ones, so a call without the two gives the store it
         always gave).  A scenario whose closures or check valves cut a zone off does not converge: it is counted as
-        not_converged, apart from out_of_range, and dropped, never repaired."""
+        not_converged, apart from out_of_range, and dropped, never repaired.  ``valve_setting_range`` (lo, hi) draws a setting per
+        scenario and regulating valve, on Kv cells after all the others (``draw_valves``); a scenario whose statuses cycle is
+        counted as not_converged and dropped in the same way."""
         if num_scenarios < 1 or chunk < 1:
             raise ValueError("num_scenarios and chunk must be positive")
         st, dev = self.static(), self._dev()
         host_ranges = self.draw_ranges(demand_range, roughness_range)
         ranges = [torch.from_numpy(a).to(dev) for a in host_ranges]
-        link_ranges = self._link_draw_setup(host_ranges, pump_speed_range, closed_probability)
+        link_ranges = self._link_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range)
         kept_rows = []
         report = {"drawn": 0, "converged": 0, "failed": 0, "not_converged": 0, "out_of_range": 0, "kept": 0, "max_iterations": 0,
                   "mean_iterations": 0.0}
@@ -900,10 +1183,11 @@ class HydraulicNetwork:
                 demand, roughness = self.draw(n, seed, first, *ranges)
                 res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False)
             else:
-                demand, roughness, speed, closed = self.draw_links(n, seed, first, ranges[0], ranges[1], *link_ranges,
-                                                                   closed_probability)
+                demand, roughness, speed, closed, setting = self.draw_valves(n, seed, first, ranges[0], ranges[1], *link_ranges,
+                                                                             closed_probability)
                 res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False,
-                                    pump_speed=speed if self.num_pumps else None, link_closed=closed)
+                                    pump_speed=speed if self.num_pumps else None, link_closed=closed,
+                                    valve_setting=setting if valve_setting_range is not None else None)
             ok = self.valid(res, pressure_range)
             table = torch.cat([res.status[:, :3], ok.to(torch.int32)[:, None]], dim=1).cpu().numpy()     # the read-back
             rows = np.flatnonzero(table[:, 3])
@@ -965,7 +1249,7 @@ class _NewtonRef:
         not negative (``law`` is None where a speed or a closed byte was refused)."""
         if law is None:
             return False
-        pipe = ~law["pump"]
+        pipe = ~law["pump"] & ~self.net.is_valve           # (a valve's roughness is not read either)
         w = law["speed"]
         with np.errstate(all="ignore"):
             w_ok = np.isfinite(w * w).all() and np.isfinite(np.power(np.where(w > 0, w, 1.0), 2.0 - law["n"])).all()
@@ -1035,6 +1319,146 @@ class _NewtonRef:
                 break
         return H, q, iterations, converged, ok, rel
 
+    def run_valves(self, d, hf, r, q_start, law, valves):
+        """``run`` with THE REGULATING VALVES, the loop of ``hy_newton_valves``: ``valves`` is the record of ``valve_record``; its
+        ``status`` [Kv] is the start and is replaced by the end, ``changes`` counts the status changes, ``margin_h`` and
+        ``margin_q`` keep the smallest distance of a comparison of the status rules from its threshold (metres, m3/s).  With no
+        valve it is ``run`` in every bit."""
+        N, P = self.net.num_nodes, self.net.num_pipes
+        a, b, fixed = self.a, self.b, self.fixed
+        link, psv, node, hset, live = valves["link"], valves["psv"], valves["node"], valves["hset"], valves["live"]
+        status = valves["status"]
+        status[~live] = VALVE_OPEN
+        Kv = link.size
+        shut0 = law["shut"] | (law["pump"] & (law["speed"] == 0))
+        q = q_start.copy()
+        q[shut0] = 0.0
+        H = hf.copy()
+        rel, ok, iterations, converged = 0.0, True, 0, False
+        for it in range(1, self.max_iter + 1):
+            iterations = it
+            active = np.zeros(P, dtype=bool)
+            active[link[live & (status == VALVE_ACTIVE)]] = True
+            closed = np.zeros(P, dtype=bool)
+            closed[link[live & (status == VALVE_CLOSED)]] = True
+            h, g = link_headloss(q, r, **dict(law, shut=law["shut"] | closed))
+            pinv, y = np.where(active, 0.0, 1.0 / g), np.where(active, 0.0, h / g)
+            on = live & (status == VALVE_ACTIVE)
+            fx, hfe = fixed.copy(), hf.copy()               # the controlled node of an ACTIVE valve is a fixed row at hset
+            fx[node[on]] = True
+            hfe[node[on]] = hset[on]
+            ja, jb = ~fx[a], ~fx[b]
+            jj = ja & jb & ~active
+            t = q - y
+            diag = np.zeros(N)
+            F = -d.copy()
+            for p in range(P):                              # a row's sums run over its pipes in pipe order, as in the kernel
+                ap, bp, pi, tp = a[p], b[p], pinv[p], t[p]
+                if active[p]:                               # a fixed draw at both ends
+                    if ja[p]:
+                        F[ap] -= q[p]
+                    if jb[p]:
+                        F[bp] += q[p]
+                    continue
+                if ja[p]:
+                    diag[ap] += pi
+                    F[ap] -= tp
+                    if not jb[p]:
+                        F[ap] += pi * hfe[bp]
+                if jb[p]:
+                    diag[bp] += pi
+                    F[bp] += tp
+                    if not ja[p]:
+                        F[bp] += pi * hfe[ap]
+            diag[fx] = 1.0
+            F[fx] = hfe[fx]
+            try:
+                if self.solver == "dense":
+                    A = np.zeros((N, N))
+                    A[np.arange(N), np.arange(N)] = diag
+                    np.add.at(A, (a[jj], b[jj]), -pinv[jj])
+                    np.add.at(A, (b[jj], a[jj]), -pinv[jj])
+                    H = np.linalg.solve(A, F)
+                else:
+                    pos, W = self.pos, self.W
+                    ab = np.zeros((W + 1, N))
+                    ab[0, pos] = diag
+                    hi, lo = np.maximum(pos[a[jj]], pos[b[jj]]), np.minimum(pos[a[jj]], pos[b[jj]])
+                    np.add.at(ab, (hi - lo, lo), -pinv[jj])
+                    Fb = np.empty(N)
+                    Fb[pos] = F
+                    H = self.solveh_banded(ab, Fb, lower=True)[pos]
+            except (np.linalg.LinAlgError, ValueError):
+                ok = False
+                break
+            H[node[on]] = hset[on]                          # (an identity row: the kernel's y / 1)
+            dq = y - (H[a] - H[b]) * pinv
+            q_new = q - dq
+            changed = 0
+            for k in range(Kv):                             # every valve from the old statuses, the new heads and its own new flow
+                if not live[k]:
+                    continue
+                p, st = link[k], int(status[k])
+                if st == VALVE_ACTIVE:
+                    inflow = 0.0
+                    for o in range(P):
+                        if o == p:
+                            continue
+                        if b[o] == node[k]:
+                            inflow += q_new[o]
+                        if a[o] == node[k]:
+                            inflow -= q_new[o]
+                    qn = inflow - d[node[k]] if psv[k] else d[node[k]] - inflow
+                    dq[p], q_new[p] = q[p] - qn, qn
+                qv = q_new[p]
+                ns, mh, mq = _valve_rule(bool(psv[k]), st, H[a[p]], H[b[p]], qv, (law["minor"][p] * abs(qv)) * qv, hset[k])
+                valves["margin_h"], valves["margin_q"] = min(valves["margin_h"], mh), min(valves["margin_q"], mq)
+                if ns != st:
+                    changed += 1
+                    status[k] = ns
+                    if ns == VALVE_CLOSED:
+                        q_new[p] = 0.0
+            valves["changes"] += changed
+            q = q_new
+            dqs, qs = float(np.cumsum(np.abs(dq))[-1]), float(np.cumsum(np.abs(q))[-1])      # (added up in pipe order)
+            if not (np.isfinite(dqs) and np.isfinite(qs)):
+                ok = False
+                break
+            rel = dqs / qs if qs > 0 else (np.inf if dqs > 0 else 0.0)
+            if dqs <= self.accuracy * qs and changed == 0:
+                converged = True
+                break
+        return H, q, iterations, converged, ok, rel
+
+
+def valve_record(network: "HydraulicNetwork", valve_setting=None, shut=None, status=None):
+    """The valves of one scenario for ``_NewtonRef.run_valves``: target heads from ``valve_setting`` [Kv] (default the network's),
+    ``live`` where the scenario's ``shut`` [P] leaves the valve its status machine, ``status`` (default: ACTIVE).  None where a
+    setting or a target head is not finite: the scenario fails."""
+    Kv = network.num_valves
+    s = network.valve_setting if valve_setting is None else np.asarray(valve_setting, dtype=np.float64).reshape(Kv)
+    with np.errstate(all="ignore"):
+        hset = network.elevation[network.valve_node] + s
+    if not np.isfinite(hset).all():
+        return None
+    live = np.ones(Kv, dtype=bool) if shut is None else ~np.asarray(shut, dtype=bool)[network.valve_links]
+    st = np.full(Kv, VALVE_ACTIVE, dtype=np.int64) if status is None else np.asarray(status, dtype=np.int64).copy()
+    return {"link": network.valve_links, "psv": network.valve_kind == LINK_PSV, "node": network.valve_node, "hset": hset,
+            "live": live, "status": st, "changes": 0, "margin_h": np.inf, "margin_q": np.inf}
+
+
+def _valve_link_status(network, record) -> np.ndarray:
+    """Per link: the status of a live valve, -1 elsewhere (what ``link_state_ref`` takes)."""
+    vs = np.full(network.num_pipes, -1, dtype=np.int64)
+    vs[record["link"][record["live"]]] = record["status"][record["live"]]
+    return vs
+
+
+def _link_resistance(network, roughness):
+    """r per link under THE LINK LAW: a pump and a regulating valve have none, and their roughness is not read."""
+    with np.errstate(all="ignore"):
+        return np.where(network.is_pump | network.is_valve, 0.0, _resistance(network, roughness))
+
 
 def link_law(network: HydraulicNetwork, pump_speed=None, link_closed=None):
     """The per-link arrays of ``link_headloss`` for one scenario: ``pump_speed`` [Kp] (default 1), ``link_closed`` [P] bytes
@@ -1057,40 +1481,62 @@ def _link_rows(network, S, pump_speed, link_closed):
     return w, cl
 
 
-def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed):
+def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed,
+                     with_valves=False, valve_setting=None):
     newton = _NewtonRef(network, solver, accuracy, max_iter)
     demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
     S, N, P = demand.shape[0], network.num_nodes, network.num_pipes
     fh, fixed = _fixed_heads(network, fixed_head, S), network.fixed
     speeds, closed = _link_rows(network, S, pump_speed, link_closed)
+    settings = None if valve_setting is None else np.broadcast_to(np.asarray(valve_setting, dtype=np.float64), (S, network.num_valves))
     head, flow = np.full((S, N), np.nan), np.full((S, P), np.nan)
     iterations, converged, failed = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=bool), np.zeros(S, dtype=bool)
     final_dq, state = np.full(S, np.nan), np.zeros((S, P), dtype=np.uint8)
+    changes, margin = np.zeros(S, dtype=np.int32), np.full((S, 2), np.inf)
     for s in range(S):
         c = roughness[s]
-        with np.errstate(all="ignore"):
-            r = np.where(network.is_pump, 0.0, _resistance(network, c))
+        r = _link_resistance(network, c)
         d, hf = np.where(fixed, 0.0, demand[s]), np.where(fixed, fh[s], 0.0)
         law = link_law(network, None if speeds is None else speeds[s], None if closed is None else closed[s])
         if not newton.link_inputs_ok(d, hf, c, r, law):
             failed[s] = True
             continue
-        H, q, iterations[s], converged[s], ok, rel = newton.run(d, hf, r, network.q_start, law)
+        vs = None
+        if with_valves:
+            rec = valve_record(network, None if settings is None else settings[s], law["shut"])
+            if rec is None:
+                failed[s] = True
+                continue
+            H, q, iterations[s], converged[s], ok, rel = newton.run_valves(d, hf, r, network.q_start, law, rec)
+            vs = _valve_link_status(network, rec)
+        else:
+            H, q, iterations[s], converged[s], ok, rel = newton.run(d, hf, r, network.q_start, law)
         if not ok:
             failed[s] = True
             continue
         head[s], flow[s], final_dq[s] = H, q, rel
-        state[s] = link_state_ref(q, law["pump"], law["check"], law["shut"], law["speed"])
+        state[s] = link_state_ref(q, law["pump"], law["check"], law["shut"], law["speed"], vs)
+        if with_valves:
+            changes[s], margin[s] = rec["changes"], (rec["margin_h"], rec["margin_q"])
+    if with_valves:
+        return HydraulicValvesReference(head, flow, iterations, converged, failed, final_dq, state, changes, margin)
     return HydraulicLinksReference(head, flow, iterations, converged, failed, final_dq, state)
 
 
 def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, solver: str = "dense", accuracy: float = ACCURACY,
-              max_iter: int = MAX_ITER, pump_speed=None, link_closed=None, links=None) -> HydraulicReference:
+              max_iter: int = MAX_ITER, pump_speed=None, link_closed=None, links=None, valve_setting=None,
+              valves=None) -> HydraulicReference:
     """The algorithm and the stop rule of the kernel in numpy fp64, scenario by scenario, with the kernel's order in every
     sum of the assembly and of the stop rule; the linear solve is the library's.  ``solver``: "dense"
     (``numpy.linalg.solve`` on the N x N system in the given node order) or "banded" (``scipy.linalg.solveh_banded`` in the
     solver order).  A network with special links (or ``pump_speed`` [Kp] / [S, Kp], ``link_closed`` [P] / [S, P], or
-    ``links=True``) is solved under THE LINK LAW and returns a ``HydraulicLinksReference``."""
+    ``links=True``) is solved under THE LINK LAW and returns a ``HydraulicLinksReference``.  A network with regulating valves (or
+    ``valve_setting`` [Kv] / [S, Kv], or ``valves=True``) is solved with their status machine (``_NewtonRef.run_valves``) and
+    returns a ``HydraulicValvesReference``: the links fields, ``valve_changes`` [S] and ``margin`` [S, 2], the smallest distance
+    of a comparison of the status rules from its threshold over all iterations, in metres and in m3/s."""
+    if valves or (valves is None and (network.has_valves or valve_setting is not None)):
+        return _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed,
+                                True, valve_setting)
     if links or (links is None and (network.has_links or pump_speed is not None or link_closed is not None)):
         return _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed)
     newton = _NewtonRef(network, solver, accuracy, max_iter)
@@ -1164,15 +1610,24 @@ def _series_inputs(network, demand, multipliers, pattern_of_node):
 def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multipliers, step_seconds: float, initial_level=None,
                         pattern_of_node=None, fixed_head=None, solver: str = "dense", warm_start: bool = True,
                         accuracy: float = ACCURACY, max_iter: int = MAX_ITER, pump_speed=None, link_closed=None,
-                        speed_multipliers=None, speed_pattern_of_pump=None, links=None) -> HydraulicSeriesReference:
+                        speed_multipliers=None, speed_pattern_of_pump=None, links=None, valve_setting=None,
+                        valves=None) -> HydraulicSeriesReference:
     """``gatres_hydraulic_series`` in numpy fp64, series by series and step by step, on the Newton loop of ``solve_ref``: the
     rounded product demand * multiplier, the tank heads elevation + level, the warm or cold start, ``level_update_ref`` and
     the kernel's failure rules.  head [S, T, N], flow [S, T, P], level [S, T + 1, K], the rest [S, T].  With special links (as
-    in ``simulate_series``) it is ``gatres_hydraulic_series_links`` and returns a ``HydraulicSeriesLinksReference``."""
+    in ``simulate_series``) it is ``gatres_hydraulic_series_links`` and returns a ``HydraulicSeriesLinksReference``; with
+    regulating valves (as in ``simulate_series``) it is ``gatres_hydraulic_series_valves`` and returns a
+    ``HydraulicSeriesValvesReference`` (``valve_changes`` [S, T]; ``margin`` [S, T, 2] as in ``solve_ref``)."""
     newton = _NewtonRef(network, solver, accuracy, max_iter)
     demand, mult, pattern = _series_inputs(network, demand, multipliers, pattern_of_node)
-    with_links = bool(links) if links is not None else (
-        network.has_links or any(v is not None for v in (pump_speed, link_closed, speed_multipliers, speed_pattern_of_pump)))
+    with_valves = bool(valves) if valves is not None else (network.has_valves or valve_setting is not None)
+    with_links = with_valves or (bool(links) if links is not None else (
+        network.has_links or any(v is not None for v in (pump_speed, link_closed, speed_multipliers, speed_pattern_of_pump))))
+    if with_valves:
+        settings = None if valve_setting is None else np.broadcast_to(np.asarray(valve_setting, dtype=np.float64),
+                                                                      (demand.shape[0], network.num_valves))
+        changes = np.zeros(demand.shape[:1] + (mult.shape[2],), dtype=np.int32)
+        margin = np.full(changes.shape + (2,), np.inf)
     if with_links:
         speeds, closed = _link_rows(network, demand.shape[0], pump_speed, link_closed)
         smult = np.ones((1, mult.shape[2])) if speed_multipliers is None else np.asarray(speed_multipliers, dtype=np.float64)
@@ -1199,12 +1654,12 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
             r = _resistance(network, c)
         hf = np.where(fixed, fh[s], 0.0)
         if with_links:
-            r = np.where(network.is_pump, 0.0, r)
+            r = _link_resistance(network, c)
             if not newton.link_inputs_ok(np.zeros(N), hf, c, r, link_law(network)):
                 continue
         elif not newton.inputs_ok(np.zeros(N), hf, c, r):
             continue
-        q, lev = network.q_start, level0[s].copy()
+        q, lev, valve_status = network.q_start, level0[s].copy(), None
         for t in range(T):
             m = mult[s, :, t]
             with np.errstate(all="ignore"):
@@ -1222,17 +1677,32 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                 law = link_law(network, w, None if closed is None else closed[s])
                 if not newton.link_inputs_ok(d, hf, c, r, law):
                     break
-            H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run(d, hf, r, q if warm_start else network.q_start, law)
+            if with_valves:                                 # a warm series carries the statuses along with the flows
+                rec = valve_record(network, None if settings is None else settings[s], law["shut"],
+                                   valve_status if warm_start else None)
+                if rec is None:
+                    break
+                H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run_valves(
+                    d, hf, r, q if warm_start else network.q_start, law, rec)
+            else:
+                H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run(d, hf, r, q if warm_start else network.q_start, law)
             if not ok:
                 break
             q = q_new
             failed[s, t] = False
             head[s, t], flow[s, t], final_dq[s, t] = H, q, rel
+            if with_valves:
+                valve_status = rec["status"]
+                changes[s, t], margin[s, t] = rec["changes"], (rec["margin_h"], rec["margin_q"])
             if with_links:
-                state[s, t] = link_state_ref(q, law["pump"], law["check"], law["shut"], law["speed"])
+                state[s, t] = link_state_ref(q, law["pump"], law["check"], law["shut"], law["speed"],
+                                             _valve_link_status(network, rec) if with_valves else None)
             lev, clamped = level_update_ref(network, lev, q, step_seconds)
             level[s, t + 1], limited[s, t] = lev, clamped.any()
         converged[s] &= ~failed[s]
+    if with_valves:
+        return HydraulicSeriesValvesReference(head, flow, level, iterations, converged, failed, limited, final_dq, state, changes,
+                                              margin)
     if with_links:
         return HydraulicSeriesLinksReference(head, flow, level, iterations, converged, failed, limited, final_dq, state)
     return HydraulicSeriesReference(head, flow, level, iterations, converged, failed, limited, final_dq)
@@ -1290,17 +1760,25 @@ def series_volume_balance(network: HydraulicNetwork, result, demand, multipliers
 
 
 def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness, fixed_head=None, pump_speed=None,
-                        link_closed=None, law=link_headloss) -> Tuple[np.ndarray, np.ndarray]:
+                        link_closed=None, law=link_headloss, valve_setting=None, link_state=None) -> Tuple[np.ndarray, np.ndarray]:
     """How well (head, flow) satisfy the model, per scenario: (mass, energy).  mass: the largest junction imbalance
     |inflow - outflow - demand| divided by sum |q| (not divided where that sum is 0); energy: the largest
     |H_a - H_b - h_p(q_p)| over the pipes and |H_f - fixed head| over the fixed nodes, in metres.  NaN where an input is.
     A network with special links (or ``pump_speed`` / ``link_closed``) is held to THE LINK LAW, ``law`` (``link_headloss``; the
-    tests plant wrong ones)."""
+    tests plant wrong ones).  A network with regulating valves needs ``link_state`` [S, P], the statuses the solution was
+    returned with (and takes ``valve_setting`` [Kv] / [S, Kv], default the network's): an OPEN valve is held to the PIPE branch
+    with r = 0, a CLOSED one to h = 1e8 q, and the energy check of an ACTIVE valve is |H_c - hset|."""
     head, flow = np.asarray(head, dtype=np.float64), np.asarray(flow, dtype=np.float64)
     demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
     S, N = head.shape[0], network.num_nodes
-    with_links = network.has_links or pump_speed is not None or link_closed is not None
+    with_links = network.has_links or network.has_valves or pump_speed is not None or link_closed is not None
     speeds, closed = _link_rows(network, S, pump_speed, link_closed)
+    if network.has_valves:
+        if link_state is None:
+            raise ValueError("a network with regulating valves needs link_state")
+        vstate = np.asarray(link_state)[:, network.valve_links]
+        settings = np.broadcast_to(network.valve_setting if valve_setting is None else np.asarray(valve_setting, dtype=np.float64),
+                                   (S, network.num_valves))
     fh = _fixed_heads(network, fixed_head, S)
     a, b, fixed = network.pipes[:, 0].astype(np.int64), network.pipes[:, 1].astype(np.int64), network.fixed
     mass, energy = np.empty(S), np.empty(S)
@@ -1314,11 +1792,18 @@ def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness
         mass[s] = worst / total if total > 0 else worst
         if with_links:
             arrays = link_law(network, None if speeds is None else speeds[s], None if closed is None else closed[s])
-            h = np.full(network.num_pipes, np.nan) if arrays is None else \
-                law(flow[s], np.where(network.is_pump, 0.0, _resistance(network, roughness[s])), **arrays)[0]
+            if arrays is not None and network.has_valves:   # a valve CLOSED by its status obeys the shut law
+                own = np.zeros(network.num_pipes, dtype=bool)
+                own[network.valve_links[vstate[s] == VALVE_CLOSED]] = True
+                arrays = dict(arrays, shut=arrays["shut"] | own)
+            h = np.full(network.num_pipes, np.nan) if arrays is None else law(flow[s], _link_resistance(network, roughness[s]), **arrays)[0]
         else:
             h, _ = pipe_headloss(flow[s], _resistance(network, roughness[s]))
-        e_pipe = np.abs(head[s][a] - head[s][b] - h).max()
+        e_link = np.abs(head[s][a] - head[s][b] - h)
+        if network.has_valves:
+            on = vstate[s] == VALVE_ACTIVE
+            e_link[network.valve_links[on]] = np.abs(head[s][network.valve_node[on]] - (network.elevation[network.valve_node[on]] + settings[s][on]))
+        e_pipe = e_link.max()
         e_fixed = np.abs(head[s] - fh[s])[fixed].max()
         energy[s] = max(e_pipe, e_fixed) if not (np.isnan(e_pipe) or np.isnan(e_fixed)) else np.nan
     return mass, energy

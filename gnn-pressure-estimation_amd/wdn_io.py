@@ -164,6 +164,7 @@ FLOW_UNITS = {"LPS": 1e-3, "LPM": 1e-3 / 60.0, "MLD": 1e3 / 86400.0, "CMH": 1.0 
               "GPM": _GALLON / 60.0, "CFS": _FOOT ** 3, "MGD": 1e6 * _GALLON / 86400.0}
 _SI_UNITS = ("LPS", "LPM", "MLD", "CMH", "CMD")
 _REGULATING = ("PRV", "PSV", "PBV", "FCV", "GPV")
+_PSI_PER_FOOT, _KPA_PER_PSI = 0.4333, 6.895     # EPANET's own constants for a pressure in psi or kPa
 NOMINAL_ROUGHNESS = 100.0               # what a pump or a valve gets in the roughness row: it has no resistance and it is not read
 NOMINAL_PUMP_DIAMETER = 1.0             # metres: a pump has no diameter; HydraulicNetwork asks for one and reads it nowhere
 
@@ -198,7 +199,7 @@ def _inp_sections(source, text) -> "OrderedDict[str, list]":
 
 
 def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported_valves: str = "refuse", ignore_controls: bool = False,
-                         device=None) -> "InpHydraulics":
+                         device=None, regulating: Optional[str] = None) -> "InpHydraulics":
     """The hydraulic attributes of an EPANET input file as a ``hydraulics.HydraulicNetwork`` and the arrays ``simulate`` and
     ``simulate_series`` take, in SI units.  Read: [JUNCTIONS] (elevation, base demand, pattern), [RESERVOIRS] (head), [TANKS]
     (elevation, initial, minimum and maximum level, diameter), [PIPES] (length, diameter, roughness, minor loss, Open / Closed /
@@ -214,10 +215,18 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
     H-W, a ``POWER`` pump or one without a ``HEAD`` curve, a regulating valve (PRV, PSV, PBV, FCV, GPV) unless
     ``unsupported_valves="open"``, which makes it an open link with its minor loss, [CONTROLS] or [RULES] with content unless
     ``ignore_controls=True``.  What EPANET does with the rest of the file (demand multiplier, emitters, quality, energy, times)
-    is not read."""
+    is not read.
+
+    ``regulating="model"`` (default ``None``: everything above, as it always was) makes PRV and PSV valves the regulating valves
+    of ``hydraulics`` (THE REGULATING VALVES): the valve runs from its first node to its second, its setting is a pressure in the
+    file's pressure unit, converted to metres (SI flow units: metres, or kPa with ``PRESSURE KPA``; US units: psi), and its loss
+    coefficient may be 0.  [STATUS] may close such a valve (a shut link); a fixed OPEN status is refused by name.  FCV, PBV and
+    GPV still go by ``unsupported_valves``."""
     from . import hydraulics as H
     if unsupported_valves not in ("refuse", "open"):
         raise ValueError('unsupported_valves must be "refuse" or "open"')
+    if regulating not in (None, "model"):
+        raise ValueError('regulating must be None or "model"')
     sec = _inp_sections(source, text)
     options = {" ".join(t[:-1]).upper(): t[-1] for t in sec.get("OPTIONS", []) if len(t) >= 2}
     units = options.get("UNITS", "GPM").upper()
@@ -232,6 +241,10 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
     flow = FLOW_UNITS[units]
     metre, dia = (1.0, 1e-3) if units in _SI_UNITS else (_FOOT, _FOOT / 12.0)
     num = lambda tok, i, default=0.0: float(tok[i]) if len(tok) > i else default
+    pressure_unit = options.get("PRESSURE", "METERS" if units in _SI_UNITS else "PSI").upper()
+    if regulating and pressure_unit not in (("METERS", "KPA") if units in _SI_UNITS else ("PSI",)):
+        raise ValueError(f"[OPTIONS] PRESSURE {pressure_unit} does not go with UNITS {units}")
+    pressure = {"METERS": 1.0, "PSI": _FOOT / _PSI_PER_FOOT, "KPA": _FOOT / _PSI_PER_FOOT / _KPA_PER_PSI}[pressure_unit] if regulating else 1.0
 
     # nodes
     names, elevation, demand, pattern_id = [], [], [], []
@@ -289,12 +302,17 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
             raise ValueError(f"[PUMPS] {t[0]}, curve {props['HEAD']}: {err}") from None
         pump_links.append(len(links)); pump_speed.append(float(props.get("SPEED", 1.0)))
         add("PUMPS", t, 0.0, NOMINAL_PUMP_DIAMETER, NOMINAL_ROUGHNESS, 0.0)
+    valve_links, valve_kind, valve_setting = [], [], []
     for t in sec.get("VALVES", []):
         if len(t) < 6:
             raise ValueError(f"[VALVES] {t[0]}: needs two nodes, diameter, type and setting")
         kind, K = t[4].upper(), num(t, 6)
         if kind == "TCV":
             K = max(K, float(t[5]))
+        elif regulating == "model" and kind in ("PRV", "PSV"):
+            valve_links.append(len(links)); valve_kind.append(kind); valve_setting.append(float(t[5]) * pressure)
+            add("VALVES", t, 0.0, num(t, 3) * dia, NOMINAL_ROUGHNESS, K)
+            continue
         elif kind in _REGULATING and unsupported_valves == "open":
             pass
         else:
@@ -311,6 +329,8 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
         p, word = link_index[t[0]], t[1].upper()
         k = pump_links.index(p) if p in pump_links else None
         if word in ("OPEN", "CLOSED"):
+            if word == "OPEN" and p in valve_links:        # (EPANET: fixed open, the setting overridden; not modelled)
+                raise ValueError(f"[STATUS] {t[0]}: a fixed OPEN status of a regulating valve is not modelled")
             if k is None:
                 closed[p] = word == "CLOSED"
             elif word == "CLOSED":
@@ -350,6 +370,8 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
     if pump_links:
         h0, rp, n = (np.asarray(v) for v in zip(*pump_curve))
         kw.update(pump_links=pump_links, pump_h0=h0, pump_r=rp, pump_n=n)
+    if valve_links:
+        kw.update(valve_links=valve_links, valve_kind=valve_kind, valve_setting=valve_setting)
     network = H.HydraulicNetwork(edge_index, length, diameter, elevation, fixed_nodes, fixed_head, device=device, minor_loss=minor,
                                  check_valve=check, closed=closed, link_reversed=ends_a[:, 0] > ends_a[:, 1], **kw)
     return InpHydraulics(network, np.asarray(demand), np.asarray(rough), mult, pattern_of_node, np.asarray(pump_speed, dtype=np.float64),

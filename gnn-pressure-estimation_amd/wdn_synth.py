@@ -67,7 +67,9 @@ def make_wdn_topology(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_PIPES
 
 def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_PIPES, num_reservoirs: int = 1, seed: int = 0,
                            length_range=None, diameter_range=None, elevation_range=None, head_range=None, device=None,
-                           num_tanks: int = 0, num_pumps: int = 0, num_check_valves: int = 0, minor_loss_range=None):
+                           num_tanks: int = 0, num_pumps: int = 0, num_check_valves: int = 0, minor_loss_range=None,
+                           num_prvs: int = 0, num_psvs: int = 0, valve_seed: int = 0,
+                           valve_minor_loss: float = 2.5):
     """A ``hydraulics.HydraulicNetwork`` on ``make_wdn_topology(num_nodes, num_pipes, seed)``: ``num_reservoirs`` of the nodes
     are fixed-head nodes, and lengths, diameters, elevations and reservoir heads are seeded uniform numpy draws from the ranges
     of the reference's scenario generator for C-Town (``hydraulics.LENGTH_RANGE`` and so on) unless given.  The last
@@ -81,7 +83,16 @@ def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_
     head from ``PUMP_SHUTOFF_RANGE`` and a quadratic curve that gives half of it at ``PUMP_DESIGN_VELOCITY`` in the link;
     ``minor_loss_range`` (lo, hi) draws a minor-loss coefficient K for every link but the pumps; ``num_check_valves`` of the
     other links, in a drawn order and a drawn direction each, become check valves -- one that would leave a junction without
-    a directed path from a fixed-head node is passed over.  ``ValueError`` where that many cannot be placed."""
+    a directed path from a fixed-head node is passed over.  ``ValueError`` where that many cannot be placed.
+
+    REGULATING VALVES (hydraulics.py: THE REGULATING VALVES), drawn after everything else with a generator of their own, so the
+    defaults return what they always did: ``num_prvs`` + ``num_psvs`` of the links that are neither pumps nor check valves, in a
+    drawn order, become valves (the PRVs first) wherever the constructor accepts them, oriented along the flow of the network
+    without valves in one nominal scenario (mid-range demand and roughness, ``solve_ref``); a valve's setting is the pressure
+    of its controlled node in that scenario; ``valve_seed`` picks another layout of the valves on the same network.  A valve
+    gets the minor-loss coefficient ``valve_minor_loss``: with K = 0 an OPEN valve sits on the linear floor of the law, where
+    its flow jitters by 1e-7 m3/s per ulp of the heads and the stop rule is met by chance (hydraulics.py: WHAT DOES NOT HOLD).
+    ``ValueError`` where that many cannot be placed."""
     from . import hydraulics as H
     if not 1 <= num_reservoirs < num_nodes:
         raise ValueError("num_reservoirs must lie in [1, num_nodes)")
@@ -105,7 +116,7 @@ def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_
     if num_pumps < 0 or num_check_valves < 0:
         raise ValueError("num_pumps and num_check_valves must not be negative")
     if not (num_pumps or num_check_valves or minor_loss_range is not None):
-        return H.HydraulicNetwork(ei, length, diameter, elevation, fixed_nodes, head, device=device, **kw)
+        return _with_valves(H, num_prvs, num_psvs, seed, valve_seed, valve_minor_loss, (ei, length, diameter, elevation, fixed_nodes, head), dict(device=device, **kw))
     # the special links, drawn after everything else
     e = ei.numpy()
     pipes = e[:, e[0] < e[1]].T
@@ -141,8 +152,53 @@ def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_
             check[p], flip[p] = False, False
     if placed < num_check_valves:
         raise ValueError(f"only {placed} of {num_check_valves} check valves can be placed without cutting a zone off")
-    return H.HydraulicNetwork(ei, length, diameter, elevation, fixed_nodes, head, device=device, minor_loss=minor, check_valve=check,
-                              link_reversed=flip, **kw)
+    return _with_valves(H, num_prvs, num_psvs, seed, valve_seed, valve_minor_loss, (ei, length, diameter, elevation, fixed_nodes, head),
+                        dict(device=device, minor_loss=minor, check_valve=check, link_reversed=flip, **kw))
+
+
+def _with_valves(H, num_prvs: int, num_psvs: int, seed: int, valve_seed: int, valve_minor_loss: float, args, kw):
+    """The network of ``make_hydraulic_network`` with its regulating valves placed (none: the constructor's call as it was)."""
+    if num_prvs < 0 or num_psvs < 0:
+        raise ValueError("num_prvs and num_psvs must not be negative")
+    net = H.HydraulicNetwork(*args, **kw)
+    want = ["PRV"] * num_prvs + ["PSV"] * num_psvs
+    if not want:
+        return net
+    demand = np.where(net.fixed, 0.0, 0.5 * (H.DEMAND_RANGE[0] + H.DEMAND_RANGE[1]))[None, :]
+    roughness = np.full((1, net.num_pipes), 0.5 * (H.ROUGHNESS_RANGE[0] + H.ROUGHNESS_RANGE[1]))
+    nominal = H.solve_ref(net, demand, roughness, solver="banded")
+    if nominal.failed[0]:
+        raise ValueError("the nominal scenario of the network without valves fails: no flow to orient the valves along")
+    flow, pressure = nominal.flow[0], nominal.head[0] - net.elevation
+    rng = np.random.RandomState(seed + 15485863 + valve_seed)
+    flip = net.pipes[:, 0] > net.pipes[:, 1]                        # the orientation the network has
+    links, kinds, settings = [], [], []
+    minor = net.minor_loss.copy()
+
+    def build(flip, links, kinds, settings):
+        k = minor.copy()
+        k[links] = valve_minor_loss
+        return H.HydraulicNetwork(*args, **dict(kw, link_reversed=flip, minor_loss=k, valve_links=links, valve_kind=kinds,
+                                                valve_setting=settings))
+    for p in rng.permutation(net.num_pipes):
+        if len(links) == len(want):
+            break
+        if net.is_pump[p] or net.check_valve[p] or net.closed[p]:
+            continue
+        kind = want[len(links)]
+        trial = flip.copy()
+        trial[p] = flip[p] ^ (flow[p] < 0)                          # along the flow
+        a, b = (net.pipes[p, 1], net.pipes[p, 0]) if flow[p] < 0 else (net.pipes[p, 0], net.pipes[p, 1])
+        c = b if kind == "PRV" else a
+        try:
+            build(trial, links + [int(p)], kinds + [kind], settings + [float(pressure[c])])
+        except ValueError:
+            continue
+        flip = trial
+        links, kinds, settings = links + [int(p)], kinds + [kind], settings + [float(pressure[c])]
+    if len(links) < len(want):
+        raise ValueError(f"only {len(links)} of {len(want)} regulating valves can be placed")
+    return build(flip, links, kinds, settings)
 
 
 PUMP_SHUTOFF_RANGE = (20.0, 40.0)       # metres: the shut-off heads make_hydraulic_network draws

@@ -1425,7 +1425,8 @@ int gatres_hydraulic_valid(const float* pressure, const int32_t* status, const u
  * WHAT DOES NOT HOLD: EPANET shortens a time step at the moment a tank becomes full or empty and closes the pipes of such a
  * tank; this model clamps the level and does neither.  A step after which a level was clamped gets status[s][t][3] = 1, and
  * volume is not conserved across it.  Pumps, check valves, closed links and minor losses are the matter of THE LINK LAW below
- * (gatres_hydraulic_series_links); regulating valves, controls and rules are not modelled.  The limit on flows that
+ * (gatres_hydraulic_series_links), PRV and PSV valves of THE REGULATING VALVES (gatres_hydraulic_series_valves); controls and
+ * rules are not modelled.  The limit on flows that
  * should be zero carries over: a step with a zero multiplier does not meet the stop rule.
  * FAILURE: a step fails on a multiplier of the step (any of the M) that is negative or not finite, a product demand * mult or
  * a tank head that is not finite, a pivot that is not positive and finite or a non-finite sum of the stop rule; a series fails
@@ -1491,8 +1492,8 @@ int gatres_hydraulic_series_valid(const float* pressure, const int32_t* status, 
  * where the scenario or step failed.
  * WHAT DOES NOT HOLD: a zone that CHECK or shut links cut off from every fixed-head node gets heads near -1e8 x demand and
  * usually does not meet the stop rule; such scenarios are counted and dropped by the generators, never repaired.
- * Pressure-regulating valves (PRV, PSV, PBV, FCV, GPV), power-rated pumps, controls and rules stay out of scope.  Parity with
- * EPANET is not claimed and has not been checked.
+ * PRV and PSV valves are the matter of THE REGULATING VALVES below, which do have one; PBV, FCV and GPV valves, power-rated pumps,
+ * controls and rules stay out of scope.  Parity with EPANET is not claimed and has not been checked.
  * STATIC link inputs (device): link_kind, link_flags uint8[P]; minor double[P]; pump_link int32[Kp], the link of pump k;
  * pump_h0, pump_r, pump_n double[Kp].  Kp == 0 is legal, the pump arrays and speed may then be NULL.  PER-SCENARIO: speed
  * double, row s at speed + s * speed_stride, speed_stride 0 or Kp; closed uint8 or NULL, row s at closed + s * closed_stride,
@@ -1540,6 +1541,90 @@ int gatres_hydraulic_series_links(const int32_t* pipe_a, const int32_t* pipe_b, 
                                   int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
                                   int64_t closed_stride, const double* speed_mult, const int32_t* speed_pattern_of_pump,
                                   int32_t num_speed_patterns, uint8_t* link_state, void* stream);
+
+/* THE REGULATING VALVES: pressure-reducing (PRV) and pressure-sustaining (PSV) valves, with a status machine (symbols only: the
+ * ABI stays; k_hydraulic_valves.hip, hydraulics.py).  The two launches below are gatres_hydraulic_solve_links and
+ * gatres_hydraulic_series_links with link_kind values GATRES_HYD_PRV and GATRES_HYD_PSV allowed; the links launches refuse them as
+ * they always did.  A regulating valve is a link from a to b without pipe resistance (r = 0: its coef and roughness are not read,
+ * as for a pump) and with the minor-loss term m = minor[p] of any link (m = 0 is allowed).  It has a setting s, a pressure in
+ * metres, and one CONTROLLED NODE c:  PRV: c = b, the downstream end;  PSV: c = a, the upstream end.  Its target head is
+ * hset = elevation[c] + s, one fp64 add.  During the Newton loop it carries a STATUS, OPEN, ACTIVE or CLOSED; it starts ACTIVE.
+ * LAW BY STATUS.  OPEN: the PIPE branch of THE LINK LAW with r = 0 (where g < 1e-7 the linear floor, so m = 0 is a valve that loses
+ * nothing).  CLOSED: g = 1e8, h = 1e8 q.  ACTIVE: the link is not in the matrix at all.
+ * ASSEMBLY WITH ACTIVE VALVES.  The controlled node of an ACTIVE valve is a fixed-head row at hset for that iteration: its row is
+ * the identity row that a reservoir's is, its neighbours take pi * hset on their right-hand side, and no off-diagonal is written
+ * for it, so the band never widens.  The valve's present flow q_v is a fixed draw: -q_v on the right-hand side of row a and +q_v
+ * on that of row b, wherever that row is neither fixed nor the controlled node of an ACTIVE valve; it takes its place in the
+ * row's sum in pipe order.
+ * FLOWS.  After the head solve every link that is not an ACTIVE valve updates as in THE SOLVER.  Each ACTIVE valve then takes the
+ * flow that closes the mass balance at c over the other links' new flows, added up in pipe order (+q_p where link p ends at c,
+ * -q_p where it starts there):  PRV: q_v = d_c - inflow;  PSV: q_v = inflow - d_c;  its dq is old flow - new flow.
+ * STATUS.  Every valve reads the new heads H_a, H_b and its own new q, all valves from the old statuses at once, with
+ * HTOL = 1.524e-4 m and QTOL = 2.8316846592e-6 m3/s (EPANET's 0.0005 ft and 0.0001 cfs) and hml = (m * |q|) * q:
+ *   PRV ACTIVE:  q < -QTOL -> CLOSED;  else H_a - hml < hset - HTOL -> OPEN;  else ACTIVE
+ *   PRV OPEN:    q < -QTOL -> CLOSED;  else H_b >= hset + HTOL -> ACTIVE;  else OPEN
+ *   PRV CLOSED:  H_a >= hset + HTOL and H_b < hset - HTOL -> ACTIVE;  else H_a < hset - HTOL and H_a > H_b + HTOL -> OPEN;  else CLOSED
+ *   PSV ACTIVE:  q < -QTOL -> CLOSED;  else H_b + hml > hset + HTOL -> OPEN;  else ACTIVE
+ *   PSV OPEN:    q < -QTOL -> CLOSED;  else H_a < hset - HTOL -> ACTIVE;  else OPEN
+ *   PSV CLOSED:  H_b > hset + HTOL and H_a > H_b + HTOL -> OPEN;  else H_a >= hset + HTOL and H_a > H_b + HTOL -> ACTIVE;  else CLOSED
+ * A valve that turns CLOSED gets q = 0.
+ * STOP RULE.  sum |dq| <= accuracy * sum |q| AND no status changed in this iteration; the dq of a valve that has just closed is
+ * the one from before it was zeroed, the q in the sum the one after.
+ * SHUT VALVES.  A valve shut by GATRES_HYD_LINK_CLOSED or by closed[s][p] = 1 is a shut link of THE LINK LAW (link_state 2) and its
+ * status machine does not run.  link_state of a regulating valve otherwise: 0 OPEN, 3 ACTIVE, 4 CLOSED by its own status.
+ * SERIES.  With warm_start the statuses carry over from step to step along with the flows; without it they start ACTIVE at every
+ * step.  Settings do not follow patterns.
+ * WHAT DOES NOT HOLD: the valve's flow lags one iteration behind the heads, as in EPANET, so convergence across a valve is linear,
+ * not quadratic.  Statuses can cycle: such a scenario uses all its iterations, is not converged, and is dropped by
+ * gatres_hydraulic_valid, never repaired.  An OPEN valve with m = 0 sits on the linear floor (1 / g = 1e7): its flow moves by
+ * 1e-7 m3/s per ulp of the heads, as THE MODEL says of every flow on that branch, and whether such a scenario meets the stop rule
+ * is decided by rounding; give a valve a loss coefficient where that matters.  Parity with EPANET is not claimed.  FCV, PBV, GPV, power-rated pumps, controls and rules
+ * stay out of scope.  The ACTIVE system is singular unless, with all regulating valves removed, the uncontrolled end of every valve
+ * still reaches a fixed-head node and every junction reaches a fixed-head node or the controlled node of some valve; the caller
+ * sees to that (hydraulics.HydraulicNetwork refuses other networks), and a scenario that still produces a bad pivot fails.
+ * INPUTS after those of the links launches: valve_link int32[Kv], the link of valve k; valve_kind uint8[Kv], GATRES_HYD_PRV or
+ * GATRES_HYD_PSV; valve_setting double, row s at valve_setting + s * valve_setting_stride, the stride 0 or Kv; Kv == 0 is legal (the
+ * three may be NULL), and the launch then gives every bit of the links launch.  OUTPUT valve_changes int32[S] (series: [S][T]):
+ * the status changes of the scenario or step over all its iterations, 0 where it failed.
+ * FAILED, every scenario of the launch: what fails every scenario of the links launches, with kinds up to GATRES_HYD_PSV allowed; a
+ * valve link with the CHECK flag; valve_link outside [0, P), on a link whose kind is not valve_kind[k], or listed twice; a link of
+ * kind PRV or PSV without a valve; two valves that share a node; a controlled node that is a fixed-head node.  That scenario (in
+ * the series that step and the later ones) alone: a setting or an hset that is not finite.
+ * LDS need (hydraulics.valves_lds_bytes, series_valves_lds_bytes): the bytes of gatres_hydraulic_solve_links (of
+ * gatres_hydraulic_series_links)  +  24 Kv (hset, link, row and node of c, change flag per valve), refused above
+ * GATRES_HYD_LDS_BUDGET.
+ * GATRES_E_BADARG before any launch: what the links launches refuse; valve_changes NULL; Kv < 0 or Kv > P; Kv > 0 with a NULL
+ * valve array; valve_setting_stride neither 0 nor Kv; the LDS need above; an output, valve_changes included, overlapping an input
+ * or another output. */
+#define GATRES_HYD_PRV 2
+#define GATRES_HYD_PSV 3
+int gatres_hydraulic_solve_valves(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                                  const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                                  int32_t half_bandwidth, const double* demand, const double* roughness, const double* fixed_head,
+                                  int64_t fixed_head_stride, int64_t num_scenarios, int32_t num_nodes, int32_t num_pipes,
+                                  double accuracy, int32_t max_iter, float* pressure, double* head, double* flow, int32_t* status,
+                                  double* final_dq, const uint8_t* link_kind, const uint8_t* link_flags, const double* minor,
+                                  const int32_t* pump_link, const double* pump_h0, const double* pump_r, const double* pump_n,
+                                  int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+                                  int64_t closed_stride, uint8_t* link_state, const int32_t* valve_link, const uint8_t* valve_kind,
+                                  const double* valve_setting, int64_t valve_setting_stride, int32_t num_valves,
+                                  int32_t* valve_changes, void* stream);
+int gatres_hydraulic_series_valves(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                                   const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                                   int32_t half_bandwidth, const int32_t* tank_node, const double* tank_area,
+                                   const double* tank_min_level, const double* tank_max_level, int32_t num_tanks,
+                                   const int32_t* pattern_of_node, const double* mult, int64_t mult_stride, int32_t num_patterns,
+                                   const double* demand, const double* roughness, const double* fixed_head,
+                                   int64_t fixed_head_stride, const double* initial_level, int64_t num_series, int32_t num_steps,
+                                   int32_t num_nodes, int32_t num_pipes, double dt, int32_t warm_start, double accuracy,
+                                   int32_t max_iter, float* pressure, double* head, double* flow, double* level, int32_t* status,
+                                   double* final_dq, const uint8_t* link_kind, const uint8_t* link_flags, const double* minor,
+                                   const int32_t* pump_link, const double* pump_h0, const double* pump_r, const double* pump_n,
+                                   int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+                                   int64_t closed_stride, const double* speed_mult, const int32_t* speed_pattern_of_pump,
+                                   int32_t num_speed_patterns, uint8_t* link_state, const int32_t* valve_link,
+                                   const uint8_t* valve_kind, const double* valve_setting, int64_t valve_setting_stride,
+                                   int32_t num_valves, int32_t* valve_changes, void* stream);
 
 const char* gatres_version(void);
 
