@@ -19,7 +19,8 @@ from .hydraulics import (HydraulicLinksResult, HydraulicNetwork, HydraulicResult
                          hydraulic_draws, hydraulic_link_draws, hydraulic_residuals, level_update_ref, link_headloss, link_state_ref, pipe_headloss,
                          pump_curve_from_points, series_report, series_valid_ref, series_volume_balance,
                          simulate_series_ref, solve_ref, tree_solution, HydraulicValvesResult, HydraulicSeriesValvesResult,
-                         valve_status_ref, hydraulic_valve_draws)
+                         valve_status_ref, hydraulic_valve_draws, HydraulicEmittersResult, HydraulicSeriesEmittersResult,
+                         emitter_headloss, hydraulic_emitter_draws)
 from .wdn_io import parse_inp_hydraulics
 from .sensitivity import (influence_from_table, linear_spread_ref, sensitivity_fold_ref, sensitivity_rows_from_gx,
                           sensitivity_seeds)
@@ -37,4 +38,5 @@ __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "Simpl
            "simulate_series_ref", "level_update_ref", "series_valid_ref", "series_report", "series_volume_balance",
            "HydraulicLinksResult", "HydraulicSeriesLinksResult", "link_headloss", "link_state_ref", "pump_curve_from_points",
            "hydraulic_link_draws", "parse_inp_hydraulics", "HydraulicValvesResult", "HydraulicSeriesValvesResult", "valve_status_ref",
-           "hydraulic_valve_draws"]
+           "hydraulic_valve_draws", "HydraulicEmittersResult", "HydraulicSeriesEmittersResult", "emitter_headloss",
+           "hydraulic_emitter_draws"]

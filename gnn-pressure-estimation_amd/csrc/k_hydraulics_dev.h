@@ -1,8 +1,9 @@
 // The hydraulic Newton loop, stated once for the two kernels of k_hydraulics.hip (hydraulic_solve_kernel: one steady scenario per
 // workgroup; hydraulic_series_kernel: one series of steps per workgroup) and their two counterparts with pumps, check valves,
 // closed links and minor losses in k_hydraulic_links.hip; and, at the end, with the status machine of the regulating valves for the
-// two kernels of k_hydraulic_valves.hip.  gatres.h states the model, the law at low flow, the link law, the valves and the
-// solver.  Everything here works on one workgroup's LDS arrays; every sum runs in a fixed order.
+// two kernels of k_hydraulic_valves.hip and, by a compile-time argument of that loop, with the node term of the emitters for the two
+// kernels of k_hydraulic_emitters.hip.  gatres.h states the model, the law at low flow, the link law, the valves, the emitters and
+// the solver.  Everything here works on one workgroup's LDS arrays; every sum runs in a fixed order.
 #pragma once
 #include "gatres_common.h"
 
@@ -295,12 +296,50 @@ struct HyNewtonValves {
   int changes;                                             // status changes over all iterations
 };
 
+// ---- THE EMITTERS of gatres.h (k_hydraulic_emitters.hip) ----------------------------------------------------------------------------
+// An emitter is a virtual link from its junction to the fixed head z = elevation, with a flow of its own, positive out of the
+// network.  ce < 0 marks an emitter that is off in this scenario or step (C == 0): its row gets nothing and its flow is +0.0.
+struct HyEmitters {
+  double* ce = nullptr;                                    // [Ke] C^(-n) of the scenario or step, -1 where the emitter is off
+  double* z = nullptr;                                     // [Ke] elevation of the emitter's junction
+  double* q = nullptr;                                     // [Ke] the emitter's flow: the start on entry, the result on return
+  double* einv = nullptr;                                  // [Ke] 1 / g; after the flow update |dq|
+  double* ey = nullptr;                                    // [Ke] h / g; after the flow update |q|
+  int* row = nullptr;                                      // [Ke] solver row of the junction
+  int* node = nullptr;                                     // [Ke] the junction itself
+  int Ke = 0;
+  double n = 2.0;                                          // 1 / gamma, one value per launch
+};
+
+// emitter_headloss of gatres.h / hydraulics.py
+__device__ __forceinline__ void emitter_headloss(double q, double ce, double n, double* h, double* g) {
+  if (q < 0.0) {                                           // a leak takes no water in: the reverse branch of a CHECK link
+    *g = HY_SHUT_G;
+    *h = HY_SHUT_G * q;
+    return;
+  }
+  const double ca = ce * pow(q, n - 1.0);                  // (pow(0, 0) is 1; pow(0, n - 1 < 0) is +inf)
+  double gg = n * ca, hh = ca * q;
+  if (gg < HY_LINEAR_G) {
+    gg = HY_LINEAR_G;
+    hh = HY_LINEAR_G * q;
+  } else if (!(gg <= HY_SHUT_G)) {                         // (also where g is not finite)
+    gg = HY_SHUT_G;
+    hh = HY_SHUT_G * q;
+  }
+  *h = hh;
+  *g = gg;
+}
+
 // hy_newton<true> with the status machine of the regulating valves; with Kv == 0 every operation on a double is the one of
 // hy_newton<true>, in the same order.  L.code carries the valves' bits (set by the caller: a valve that its input does not shut
-// starts with a status bit or none), L.fx the fixed-head nodes as 1; red[2] takes the iteration's count of changes.
+// starts with a status bit or none), L.fx the fixed-head nodes as 1; red[2] takes the iteration's count of changes.  EMIT adds
+// the node term of the emitters E at compile time (the default: the loop the valves kernels have always had); an emitter's
+// junction is never a fixed row nor a valve's controlled node (checked by the caller).
+template <bool EMIT = false>
 __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const HyValves& V, const int* __restrict__ position,
                                                            const double* dem, int N, int P, int W, int max_iter, double accuracy,
-                                                           int tid) {
+                                                           int tid, const HyEmitters& E = HyEmitters()) {
   const int BW = W + 1, Kv = V.Kv;
   double *band = L.band, *y = L.y, *H = L.H, *q = L.q, *rr = L.rr, *pinv = L.pinv, *yv = L.yv, *red = L.red;
   const int *sa = L.sa, *sb = L.sb;
@@ -332,6 +371,15 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
       fx[V.row[k]] = active ? HY_FX_VALVE : 0;
       if (active) H[V.row[k]] = V.hset[k];
     }
+    if constexpr (EMIT) {                                  // one thread per emitter evaluates the law
+      for (int k = tid; k < E.Ke; k += HY_T) {
+        double h = 0.0, g = 1.0;
+        const bool on = E.ce[k] >= 0.0;
+        if (on) emitter_headloss(E.q[k], E.ce[k], E.n, &h, &g);
+        E.einv[k] = on ? 1.0 / g : 0.0;
+        E.ey[k] = on ? h / g : 0.0;
+      }
+    }
     __syncthreads();
     // assembly: one thread per row, over the pipes in pipe order; an ACTIVE valve's flow is a fixed draw at its two ends
     for (int n = tid; n < N; n += HY_T) {
@@ -356,6 +404,15 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
           f = b == r ? f + t : f - t;
           if (fx[o]) f += pi * H[o];
           else if (o < r) row[r - o] -= pi;                // (r - o <= W: checked by the caller)
+        }
+        if constexpr (EMIT) {                              // the row's thread adds its emitter's term, after the links
+          for (int k = 0; k < E.Ke; ++k) {
+            if (E.row[k] != r || !(E.ce[k] >= 0.0)) continue;
+            const double ei = E.einv[k];
+            diag += ei;
+            f -= E.q[k] - E.ey[k];
+            f += E.z[k] * ei;
+          }
         }
         row[0] = diag;
         y[r] = f;
@@ -401,6 +458,15 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
       pinv[p] = fabs(dq);
       yv[p] = fabs(qn);
     }
+    if constexpr (EMIT) {                                  // the emitters' flows, after the links'
+      for (int k = tid; k < E.Ke; k += HY_T) {
+        if (!(E.ce[k] >= 0.0)) continue;
+        const double dq = E.ey[k] - (H[E.row[k]] - E.z[k]) * E.einv[k], qn = E.q[k] - dq;
+        E.q[k] = qn;
+        E.einv[k] = fabs(dq);
+        E.ey[k] = fabs(qn);
+      }
+    }
     __syncthreads();
     // one thread per valve: an ACTIVE valve's flow closes the mass balance at its controlled node over the other links in pipe
     // order; then the status from the new heads and the valve's own new flow.  No valve shares a node with another (checked by
@@ -442,6 +508,11 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
       const double* v = tid == 0 ? pinv : yv;
       double sum = 0.0;
       for (int p = 0; p < P; ++p) sum += v[p];
+      if constexpr (EMIT) {                                // then the emitters that are on, in emitter order
+        const double* w = tid == 0 ? E.einv : E.ey;
+        for (int k = 0; k < E.Ke; ++k)
+          if (E.ce[k] >= 0.0) sum += w[k];
+      }
       red[tid == 0 ? 0 : 1] = sum;
     } else if (tid == 128) {
       int n = 0;

@@ -76,6 +76,27 @@ never repaired.  An OPEN valve with K = 0 sits on the linear branch, where its f
 (WHAT DOES NOT HOLD, below) and the stop rule is met by chance: give a valve a loss coefficient where that matters
 (``make_hydraulic_network`` does).  Parity with EPANET is not claimed.  FCV, PBV and GPV valves stay out of scope.
 
+THE EMITTERS (gatres.h: THE EMITTERS; csrc/k_hydraulic_emitters.hip; ``emitter_headloss``, ``_NewtonRef.run_valves(emit=)``).  A
+network built with ``emitter_nodes`` takes the two emitters launches: the valves launches with a node term for pressure-dependent
+outflow, EPANET's emitter q = C p^gamma -- a leak.  An emitter sits on a junction i; its coefficient C >= 0 (m3/s per m^gamma)
+belongs to the scenario (``simulate(emitter_coefficient=)``), the exponent gamma to the network, as in EPANET.  It is a virtual
+link from i to the fixed head z_i = elevation[i] with a flow q_e of its own, positive out of the network.  With n = 1 / gamma and
+ce = C^(-n) -- forward branch (q_e >= 0): ca = ce q_e^(n-1), g = n ca, h = ca q_e; where g < 1e-7 the linear floor; where g > 1e8
+or g is not finite (q_e -> 0 with gamma > 1): g = 1e8, h = 1e8 q_e.  Reverse branch (q_e < 0): a leak takes no water in: g = 1e8,
+h = 1e8 q_e, so a junction under negative pressure p carries -|p| / 1e8, as every shut link does.  C == 0 means no emitter in that
+scenario or step: its row gets nothing, q_e is +0.0 and it adds nothing to the sums of the stop rule, so a network whose
+coefficients are all 0 has every bit of the network without emitters.  Assembly, on the row of i after its links in pipe order:
+diag += 1/g, f -= q_e - h/g, f += z_i (1/g); no off-diagonal, so the band never widens.  Flow update after the links':
+dq = h/g - (H_i - z_i) (1/g), q_e -= dq; |dq| and |q_e| join the sums of the stop rule after the links, in emitter order.  Start:
+q_e = C, the flow at one metre of pressure.  In a series ``emitter_onset`` [Ke] / [S, Ke] keeps emitter k off (C = 0) at the steps
+t < onset -- a leak that begins mid-series; with ``warm_start`` an emitter that was on in the step before keeps its q_e, one that
+has just switched on starts at C.  Refused by the constructor (``ValueError``; the kernels fail every scenario): gamma that is not
+finite and positive, an emitter node outside the network, listed twice, fixed-head, or the controlled node of a regulating valve.
+A coefficient that is negative or not finite fails its scenario (a series: from step 0 on, whatever the onset).  WHAT DOES NOT
+HOLD: an emitter on a valve's controlled node is refused, not modelled (an ACTIVE valve closes that node's mass balance over the
+links alone, and that rule stays as it stands).  Pressure-driven demand (EPANET 2.2's ``DEMAND MODEL PDA``) would take the same
+node slot and is out of scope.  Parity with EPANET is not claimed.
+
 THE SERIES (``simulate_series``, ``generate_series_store``; gatres.h: THE SERIES): extended-period simulation, T steps of
 ``step_seconds`` of one scenario in one launch, one workgroup per series.  Tanks are a subset of the fixed-head nodes: tank k
 has its bottom at the node's elevation, a diameter D_k, the area A_k = pi D_k^2 / 4 and level limits min_level[k] <=
@@ -109,7 +130,7 @@ the order of the upper end).
 Host restatements in numpy fp64 (the yardsticks of the tests): ``pipe_headloss``, ``solve_ref``, ``hydraulic_residuals``,
 ``hydraulic_draws``, ``tree_solution``, ``simulate_series_ref``, ``level_update_ref``, ``series_valid_ref``,
 ``series_volume_balance``, ``link_headloss``, ``link_state_ref``, ``hydraulic_link_draws``, ``pump_curve_from_points``,
-``valve_status_ref`` and ``hydraulic_valve_draws``.
+``valve_status_ref``, ``hydraulic_valve_draws``, ``emitter_headloss`` and ``hydraulic_emitter_draws``.
 """
 from __future__ import annotations
 
@@ -167,6 +188,46 @@ LINK_PRV, LINK_PSV = 2, 3               # GATRES_HYD_PRV, GATRES_HYD_PSV
 VALVE_OPEN, VALVE_ACTIVE, VALVE_CLOSED = 0, 3, 4      # link_state of a regulating valve (2: shut by input)
 VALVE_HTOL, VALVE_QTOL = 1.524e-4, 2.8316846592e-6    # EPANET's 0.0005 ft and 0.0001 cfs
 VALVE_KINDS = {"PRV": LINK_PRV, "PSV": LINK_PSV}
+# what a network with emitters returns: the fields above, and emitter_flow (m3/s out of the network, per scenario or step and emitter)
+HydraulicEmittersResult = namedtuple("HydraulicEmittersResult", HydraulicValvesResult._fields + ("emitter_flow",))
+HydraulicEmittersReference = namedtuple("HydraulicEmittersReference", HydraulicValvesReference._fields + ("emitter_flow",))
+HydraulicSeriesEmittersResult = namedtuple("HydraulicSeriesEmittersResult", HydraulicSeriesValvesResult._fields + ("emitter_flow",))
+HydraulicSeriesEmittersReference = namedtuple("HydraulicSeriesEmittersReference",
+                                              HydraulicSeriesValvesReference._fields + ("emitter_flow",))
+EMITTER_EXPONENT = 0.5                  # EPANET's default
+
+
+def emitter_headloss(q, coefficient, exponent=EMITTER_EXPONENT) -> Tuple[np.ndarray, np.ndarray]:
+    """THE EMITTERS, elementwise with the kernel's operations: head loss h and gradient g of an emitter with coefficient C > 0 and
+    exponent gamma at its flow q (positive out of the network).  n = 1 / gamma, ce = C^(-n).  Forward (q >= 0): ca = ce q^(n - 1),
+    g = n ca, h = ca q; the linear floor where g < 1e-7; g = 1e8, h = 1e8 q where g > 1e8 or g is not finite.  Reverse (q < 0):
+    g = 1e8, h = 1e8 q.  (C == 0 is no emitter and has no law: the callers leave such an emitter out.)"""
+    q, C = np.asarray(q, dtype=np.float64), np.asarray(coefficient, dtype=np.float64)
+    n = 1.0 / np.float64(exponent)
+    with np.errstate(all="ignore"):
+        ce = np.power(C, -n)
+        ca = ce * np.power(np.maximum(q, 0.0), n - 1.0)
+        g, h = n * ca, ca * q
+        low = g < LINEAR_GRADIENT
+        high = ~low & ~(g <= SHUT_GRADIENT)
+        g = np.where(low, LINEAR_GRADIENT, np.where(high, SHUT_GRADIENT, g))
+        h = np.where(low, LINEAR_GRADIENT * q, np.where(high, SHUT_GRADIENT * q, h))
+        reverse = q < 0
+        g = np.where(reverse, SHUT_GRADIENT, g)
+        h = np.where(reverse, SHUT_GRADIENT * q, h)
+    return h, g
+
+
+def emitters_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_pumps: int, num_valves: int, num_emitters: int) -> int:
+    """What a workgroup of ``gatres_hydraulic_solve_emitters`` takes of the LDS (gatres.h states the same sum): the arrays of the
+    valves launch, and per emitter ce, z, q_e, 1 / g, h / g, its row and its node."""
+    return valves_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_pumps, num_valves) + 48 * num_emitters
+
+
+def series_emitters_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_tanks: int, num_pumps: int, num_valves: int,
+                              num_emitters: int) -> int:
+    """What a workgroup of ``gatres_hydraulic_series_emitters`` takes of the LDS (gatres.h states the same sum)."""
+    return series_valves_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_tanks, num_pumps, num_valves) + 48 * num_emitters
 
 
 def _valve_rule(psv: bool, status: int, Ha: float, Hb: float, q: float, hml: float, hset: float):
@@ -400,6 +461,50 @@ def hydraulic_valve_draws(seed: int, first_scenario: int, num_scenarios: int, d_
             np.ascontiguousarray(cells[:, 2 * P + num_pumps:]))
 
 
+def emitter_draw_ranges(c_lo, c_hi, num_pumps: int, num_valves: int, num_emitters: int, emitter_coefficient_range,
+                        leak_onset_range=None, pump_speed_range=None, valve_setting_range=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The ranges of ``link_draw_ranges`` extended by the Kv valve cells (``valve_setting_range``, None: (0, 0), not used) and,
+    AFTER all of those, by the cells of the emitter draws: Ke cells for the coefficients, uniform in
+    ``emitter_coefficient_range``, Ke cells uniform in [0, 1) that decide whether the emitter leaks at all, and with
+    ``leak_onset_range`` (lo, hi) Ke cells uniform in [lo, hi) whose floor is the onset step."""
+    lo, hi = link_draw_ranges(c_lo, c_hi, num_pumps, pump_speed_range)
+    v_lo, v_hi = (0.0, 0.0) if valve_setting_range is None else (float(valve_setting_range[0]), float(valve_setting_range[1]))
+    e_lo, e_hi = float(emitter_coefficient_range[0]), float(emitter_coefficient_range[1])
+    if not (np.isfinite(v_lo) and np.isfinite(v_hi) and v_lo <= v_hi):
+        raise ValueError("valve_setting_range must be lo <= hi, finite")
+    if not (np.isfinite(e_lo) and np.isfinite(e_hi) and 0 <= e_lo <= e_hi):
+        raise ValueError("emitter_coefficient_range must be 0 <= lo <= hi, finite")
+    parts_lo = [lo, np.full(num_valves, v_lo), np.full(num_emitters, e_lo), np.zeros(num_emitters)]
+    parts_hi = [hi, np.full(num_valves, v_hi), np.full(num_emitters, e_hi), np.ones(num_emitters)]
+    if leak_onset_range is not None:
+        o_lo, o_hi = float(leak_onset_range[0]), float(leak_onset_range[1])
+        if not (np.isfinite(o_lo) and np.isfinite(o_hi) and 0 <= o_lo <= o_hi < 2 ** 31):
+            raise ValueError("leak_onset_range must be 0 <= lo <= hi, in steps")
+        parts_lo.append(np.full(num_emitters, o_lo))
+        parts_hi.append(np.full(num_emitters, o_hi))
+    return np.concatenate(parts_lo), np.concatenate(parts_hi)
+
+
+def hydraulic_emitter_draws(seed: int, first_scenario: int, num_scenarios: int, d_lo, d_hi, c_lo, c_hi, num_pumps: int,
+                            num_valves: int, num_emitters: int, emitter_coefficient_range, leak_probability: float = 1.0,
+                            leak_onset_range=None, pump_speed_range=None, closed_probability: float = 0.0,
+                            valve_setting_range=None):
+    """What ``generate_store(emitter_coefficient_range=, leak_probability=)`` and ``generate_series_store(..., leak_onset_range=)``
+    draw, in numpy, bit for bit: the five arrays of ``hydraulic_valve_draws`` (the settings all 0 without
+    ``valve_setting_range``), unchanged by the cells that come AFTER all of theirs, then emitter_coefficient [S, Ke] (0 where the
+    emitter's second cell is not below ``leak_probability``) and emitter_onset int32 [S, Ke] (None without ``leak_onset_range``)."""
+    P, Kp, Kv, Ke = np.asarray(c_lo).shape[0], num_pumps, num_valves, num_emitters
+    lo, hi = emitter_draw_ranges(c_lo, c_hi, Kp, Kv, Ke, emitter_coefficient_range, leak_onset_range, pump_speed_range,
+                                 valve_setting_range)
+    demand, cells = hydraulic_draws(seed, first_scenario, num_scenarios, d_lo, d_hi, lo, hi)
+    base = 2 * P + Kp + Kv
+    closed = (cells[:, P + Kp:2 * P + Kp] < float(closed_probability)).astype(np.uint8)
+    coef = np.where(cells[:, base + Ke:base + 2 * Ke] < float(leak_probability), cells[:, base:base + Ke], 0.0)
+    onset = None if leak_onset_range is None else np.floor(cells[:, base + 2 * Ke:base + 3 * Ke]).astype(np.int32)
+    return (demand, np.ascontiguousarray(cells[:, :P]), np.ascontiguousarray(cells[:, P:P + Kp]), closed,
+            np.ascontiguousarray(cells[:, 2 * P + Kp:base]), np.ascontiguousarray(coef), onset)
+
+
 def _half_bandwidth(pipes: np.ndarray, fixed: np.ndarray, position: np.ndarray) -> int:
     both = ~fixed[pipes[:, 0]] & ~fixed[pipes[:, 1]]
     if not both.any():
@@ -457,12 +562,16 @@ class HydraulicNetwork:
 
     REGULATING VALVES (the module's docstring: THE REGULATING VALVES): ``valve_links`` [Kv] links, ``valve_kind`` "PRV" / "PSV" (one
     for all, or one per valve), ``valve_setting`` [Kv] pressures in metres; a valve runs from a to b as its link does
-    (``link_reversed``), its ``minor_loss`` K may be 0, its length is not read.  ``valve_node`` holds the controlled nodes."""
+    (``link_reversed``), its ``minor_loss`` K may be 0, its length is not read.  ``valve_node`` holds the controlled nodes.
+
+    EMITTERS (the module's docstring: THE EMITTERS): ``emitter_nodes`` [Ke] junctions on which a leak can be, ``emitter_exponent``
+    gamma (one for the network, default 0.5).  The coefficients are a scenario's: ``simulate(emitter_coefficient=)``."""
 
     def __init__(self, edge_index, length, diameter, elevation, fixed_nodes: Sequence[int], fixed_head,
                  start_velocity: float = START_VELOCITY, device=None, tank_nodes=None, tank_diameter=None, tank_min_level=None,
                  tank_max_level=None, minor_loss=None, check_valve=None, closed=None, pump_links=None, pump_h0=None, pump_r=None,
-                 pump_n=None, pump_q_start=None, link_reversed=None, valve_links=None, valve_kind=None, valve_setting=None):
+                 pump_n=None, pump_q_start=None, link_reversed=None, valve_links=None, valve_kind=None, valve_setting=None,
+                 emitter_nodes=None, emitter_exponent: float = EMITTER_EXPONENT):
         ei = torch.as_tensor(edge_index).detach().cpu()
         if ei.dim() != 2 or ei.shape[0] != 2 or ei.dtype != torch.int64:
             raise ValueError("edge_index must be int64 [2, E]")
@@ -548,6 +657,19 @@ class HydraulicNetwork:
         fixed[fixed_nodes] = True
         if Kv and fixed[v_ctrl].any():
             raise ValueError("the controlled node of a regulating valve is a fixed-head node")
+        # the emitters (THE EMITTERS): none by default
+        emitters = np.asarray([] if emitter_nodes is None else emitter_nodes, dtype=np.int64).reshape(-1)
+        Ke = int(emitters.size)
+        gamma = float(emitter_exponent)
+        with np.errstate(all="ignore"):
+            if not (np.isfinite(gamma) and gamma > 0 and np.isfinite(np.float64(1.0) / np.float64(gamma))):
+                raise ValueError("emitter_exponent must be finite and positive")
+        if Ke and (emitters.min() < 0 or emitters.max() >= N or np.unique(emitters).size != Ke):
+            raise ValueError("emitter_nodes must be distinct nodes of the network")
+        if Ke and fixed[emitters].any():
+            raise ValueError("an emitter sits on a junction, not on a fixed-head node")
+        if Ke and Kv and np.isin(emitters, v_ctrl).any():
+            raise ValueError("an emitter on the controlled node of a regulating valve is not modelled")
         adj = [[] for _ in range(N)]
         for p, (a, b) in enumerate(pipes):                  # a CHECK link is walked from a to b only, a closed one not at all,
             if shut[p] or is_valve[p]:                      # and a regulating valve not at all: ACTIVE, it is not in the matrix
@@ -651,6 +773,11 @@ class HydraulicNetwork:
         need = links_lds_bytes(N, P, self.half_bandwidth, Kp) if self.has_links else lds_bytes(N, P, self.half_bandwidth)
         if Kv:
             need = series_valves_lds_bytes(N, P, self.half_bandwidth, K, Kp, Kv) if K else valves_lds_bytes(N, P, self.half_bandwidth, Kp, Kv)
+        # the emitter arrays of gatres_hydraulic_solve_emitters
+        self.num_emitters, self.emitter_nodes, self.emitter_exponent, self.has_emitters = Ke, emitters, gamma, Ke > 0
+        if Ke:
+            need = series_emitters_lds_bytes(N, P, self.half_bandwidth, K, Kp, Kv, Ke) if K else \
+                emitters_lds_bytes(N, P, self.half_bandwidth, Kp, Kv, Ke)
         if need > LDS_BUDGET:
             raise ValueError(f"the band of {N} rows with half-bandwidth {self.half_bandwidth} needs "
                              f"{need} bytes of LDS, the kernel has {LDS_BUDGET}")
@@ -752,6 +879,41 @@ class HydraulicNetwork:
         vp = (lambda t: t.data_ptr()) if Kv else (lambda t: None)
         return [vp(st["valve_link"]), vp(st["valve_kind"]), vp(setting), stride, Kv], changes, setting
 
+    def _emitter_args(self, S: int, flow_shape, emitter_coefficient, emitter_onset=None, series: bool = False):
+        """The emitter arguments of the two emitters launches (``emitter_flow`` included), the ``emitter_flow`` tensor, and the
+        tensors of this call that the arguments point into, which the caller holds until the launch is queued."""
+        st, dev, Ke = self.static(), self._dev(), self.num_emitters
+        if "emitter_node" not in st:
+            st["emitter_node"] = torch.from_numpy(np.ascontiguousarray(self.emitter_nodes, dtype=np.int32)).to(dev)
+        if Ke and emitter_coefficient is None:
+            raise ValueError("a network with emitters needs emitter_coefficient")
+        coef, stride = None, 0
+        if Ke:
+            coef = torch.as_tensor(emitter_coefficient, dtype=torch.float64).to(dev).contiguous()
+            if tuple(coef.shape) == (S, Ke):
+                stride = Ke
+            elif tuple(coef.shape) != (Ke,):
+                raise ValueError(f"emitter_coefficient must be [{Ke}] or [{S}, {Ke}]")
+        elif emitter_coefficient is not None and torch.as_tensor(emitter_coefficient).numel():
+            raise ValueError("emitter_coefficient needs a network with emitters")
+        onset, onset_stride = None, 0
+        if emitter_onset is not None:
+            if not series:
+                raise ValueError("emitter_onset belongs to a series")
+            onset = torch.as_tensor(emitter_onset).to(device=dev, dtype=torch.int32).contiguous()
+            if tuple(onset.shape) == (S, Ke):
+                onset_stride = Ke
+            elif tuple(onset.shape) != (Ke,):
+                raise ValueError(f"emitter_onset must be [{Ke}] or [{S}, {Ke}]")
+            if Ke == 0:
+                onset, onset_stride = None, 0
+        flow = torch.empty(tuple(flow_shape) + (Ke,), dtype=torch.float64, device=dev)
+        ep = (lambda t: t.data_ptr()) if Ke else (lambda t: None)
+        args = [ep(st["emitter_node"]), ep(coef), stride, Ke, float(self.emitter_exponent)]
+        if series:
+            args += [_native.ptr(onset), onset_stride]
+        return args + [ep(flow)], flow, (coef, onset)
+
     def _f64(self, a, shape, name) -> torch.Tensor:
         t = torch.as_tensor(a, dtype=torch.float64).to(self._dev()).contiguous()
         if tuple(t.shape) != tuple(shape):
@@ -794,6 +956,50 @@ class HydraulicNetwork:
         closed = (cells[:, P + Kp:2 * P + Kp] < float(closed_probability)).to(torch.uint8).contiguous()
         return (demand, cells[:, :P].contiguous(), cells[:, P:P + Kp].contiguous(), closed, cells[:, 2 * P + Kp:].contiguous())
 
+    def draw_emitters(self, num_scenarios: int, seed: int, first_scenario: int, d_lo: torch.Tensor, d_hi: torch.Tensor,
+                      x_lo: torch.Tensor, x_hi: torch.Tensor, closed_probability: float, leak_probability: float):
+        """``draw_valves`` with the emitter cells behind the Kv valve cells (``x_lo``, ``x_hi``: ``emitter_draw_ranges`` on the
+        device, 2 Ke or 3 Ke entries more): the five arrays of ``draw_valves``, emitter_coefficient [S, Ke] and emitter_onset
+        int32 [S, Ke] or None.  ``hydraulic_emitter_draws`` restates it."""
+        dev, lib, P, Kp, Kv, Ke = self._dev(), _native.load(), self.num_pipes, self.num_pumps, self.num_valves, self.num_emitters
+        C, base = int(x_lo.shape[0]), 2 * P + Kp + Kv
+        if C not in (base + 2 * Ke, base + 3 * Ke):
+            raise ValueError("the ranges of the emitter cells do not fit the network")
+        demand = torch.empty((num_scenarios, self.num_nodes), dtype=torch.float64, device=dev)
+        cells = torch.empty((num_scenarios, C), dtype=torch.float64, device=dev)
+        rc = lib.gatres_hydraulic_draw(d_lo.data_ptr(), d_hi.data_ptr(), x_lo.data_ptr(), x_hi.data_ptr(), num_scenarios,
+                                       self.num_nodes, C, seed % (1 << 64), first_scenario, demand.data_ptr(),
+                                       cells.data_ptr(), _native.current_stream(dev))
+        _native.check(rc, "gatres_hydraulic_draw")
+        closed = (cells[:, P + Kp:2 * P + Kp] < float(closed_probability)).to(torch.uint8).contiguous()
+        leaks = cells[:, base + Ke:base + 2 * Ke] < float(leak_probability)
+        coef = torch.where(leaks, cells[:, base:base + Ke], torch.zeros((), dtype=torch.float64, device=dev)).contiguous()
+        onset = cells[:, base + 2 * Ke:].floor().to(torch.int32).contiguous() if C == base + 3 * Ke and Ke else None
+        return (demand, cells[:, :P].contiguous(), cells[:, P:P + Kp].contiguous(), closed, cells[:, 2 * P + Kp:base].contiguous(),
+                coef, onset)
+
+    def _emitter_draw_setup(self, ranges, pump_speed_range, closed_probability, valve_setting_range, emitter_coefficient_range,
+                            leak_probability, leak_onset_range=None):
+        """None where a store is generated without emitter draws (the call it always was), else the device ranges of
+        ``draw_emitters``."""
+        if emitter_coefficient_range is None:
+            if float(leak_probability) != 1.0 or leak_onset_range is not None:
+                raise ValueError("leak_probability and leak_onset_range need emitter_coefficient_range")
+            return None
+        if self.num_emitters == 0:
+            raise ValueError("emitter_coefficient_range needs a network with emitters")
+        if not 0.0 <= float(leak_probability) <= 1.0:
+            raise ValueError("leak_probability must lie in [0, 1]")
+        if not 0.0 <= float(closed_probability) < 1.0:
+            raise ValueError("closed_probability must lie in [0, 1)")
+        if pump_speed_range is not None and self.num_pumps == 0:
+            raise ValueError("pump_speed_range needs a network with pumps")
+        if valve_setting_range is not None and self.num_valves == 0:
+            raise ValueError("valve_setting_range needs a network with regulating valves")
+        lo, hi = emitter_draw_ranges(ranges[2], ranges[3], self.num_pumps, self.num_valves, self.num_emitters,
+                                     emitter_coefficient_range, leak_onset_range, pump_speed_range, valve_setting_range)
+        return torch.from_numpy(lo).to(self._dev()), torch.from_numpy(hi).to(self._dev())
+
     def _link_draw_setup(self, ranges, pump_speed_range, closed_probability, valve_setting_range=None):
         """None where a store is generated without link draws (the call it always was), else the device ranges of ``draw_links``
         (of ``draw_valves``: with ``valve_setting_range`` the Kv valve cells come after all the others)."""
@@ -815,7 +1021,7 @@ class HydraulicNetwork:
 
     def simulate(self, demand, roughness, fixed_head=None, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
                  want_head: bool = True, want_flow: bool = True, pump_speed=None, link_closed=None, links=None,
-                 valve_setting=None, valves=None) -> HydraulicResult:
+                 valve_setting=None, valves=None, emitter_coefficient=None, emitters=None) -> HydraulicResult:
         """Solve S scenarios on the device.  ``demand`` [S, N] m3/s (ignored at fixed nodes), ``roughness`` [S, P]
         Hazen-Williams coefficients, ``fixed_head`` None (the network's), [N] or [S, N] (read at fixed nodes).  Every field
         of the result is a device tensor; nothing is read back.  A network with a special link or a minor loss (or
@@ -823,8 +1029,16 @@ class HydraulicNetwork:
         ``gatres_hydraulic_solve_links`` and returns a ``HydraulicLinksResult``: the same fields and ``link_state`` uint8 [S, P].
         A network of pipes takes ``gatres_hydraulic_solve`` as it always did.  A network with a regulating valve (or
         ``valve_setting`` [Kv] / [S, Kv] metres of pressure, default the network's; or ``valves=True``) takes
-        ``gatres_hydraulic_solve_valves`` and returns a ``HydraulicValvesResult``: the links fields and ``valve_changes`` int32 [S]."""
+        ``gatres_hydraulic_solve_valves`` and returns a ``HydraulicValvesResult``: the links fields and ``valve_changes`` int32 [S].
+        A network with emitters (or ``emitters=True``) takes ``gatres_hydraulic_solve_emitters`` with ``emitter_coefficient`` [Ke] /
+        [S, Ke] (m3/s per m^gamma, required; 0 is no leak there) and returns a ``HydraulicEmittersResult``: the valves fields and
+        ``emitter_flow`` fp64 [S, Ke], the leaked flows."""
         st, dev, lib = self.static(), self._dev(), _native.load()
+        with_emitters = bool(emitters) if emitters is not None else (self.has_emitters or emitter_coefficient is not None)
+        if self.has_emitters and not with_emitters:
+            raise ValueError("a network with emitters takes the emitters launch")
+        if with_emitters:
+            valves = True
         with_valves = bool(valves) if valves is not None else (self.has_valves or valve_setting is not None)
         if self.has_valves and not with_valves:
             raise ValueError("a network with regulating valves takes the valves launch")
@@ -857,6 +1071,19 @@ class HydraulicNetwork:
         if with_valves:
             link_args, link_state, _held = self._link_args(S, (S, P), pump_speed, link_closed)
             valve_args, changes, _held_v = self._valve_args(S, (S,), valve_setting)
+            if with_emitters:
+                emitter_args, emitter_flow, _held_e = self._emitter_args(S, (S,), emitter_coefficient)
+                rc = lib.gatres_hydraulic_solve_emitters(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
+                                                         st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
+                                                         st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
+                                                         demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P,
+                                                         float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head),
+                                                         _native.ptr(flow), status.data_ptr(), final_dq.data_ptr(), *link_args,
+                                                         link_state.data_ptr(), *valve_args, changes.data_ptr(), *emitter_args,
+                                                         _native.current_stream(dev))
+                _native.check(rc, "gatres_hydraulic_solve_emitters")
+                return HydraulicEmittersResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status,
+                                               final_dq, link_state, changes, emitter_flow)
             rc = lib.gatres_hydraulic_solve_valves(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
                                                    st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
                                                    st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
@@ -905,7 +1132,8 @@ class HydraulicNetwork:
     def simulate_series(self, demand, roughness, multipliers, *, step_seconds: float, initial_level=None, pattern_of_node=None,
                         fixed_head=None, warm_start: bool = True, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
                         want_head: bool = True, want_flow: bool = True, pump_speed=None, link_closed=None, speed_multipliers=None,
-                        speed_pattern_of_pump=None, links=None, valve_setting=None, valves=None) -> HydraulicSeriesResult:
+                        speed_pattern_of_pump=None, links=None, valve_setting=None, valves=None, emitter_coefficient=None,
+                        emitter_onset=None, emitters=None) -> HydraulicSeriesResult:
         """``gatres_hydraulic_series``: S series of T steps on the device, one launch.  ``demand`` [S, N] base demands,
         ``roughness`` [S, P], ``multipliers`` [M, T] (for every series) or [S, M, T], ``pattern_of_node`` int [N] with values in
         [0, M) (default: pattern 0 everywhere; host data outside the range raises ``ValueError``, a DEVICE tensor is not read back
@@ -921,8 +1149,17 @@ class HydraulicNetwork:
         returns a ``HydraulicSeriesValvesResult`` with ``valve_changes`` int32 [S, T]; with ``warm_start`` the statuses carry over
         from step to step, without it they start ACTIVE at every step.  The series launch takes 8 N bytes of LDS more than the
         steady one; a network with valves and without tanks that the constructor accepted for ``simulate`` but whose series does
-        not fit is refused here with ``ValueError``."""
+        not fit is refused here with ``ValueError``.  A network with emitters (or ``emitters=True``) takes
+        ``gatres_hydraulic_series_emitters`` with ``emitter_coefficient`` [Ke] / [S, Ke] and ``emitter_onset`` int [Ke] / [S, Ke]
+        (default 0: emitter k leaks nothing at the steps t < onset) and returns a ``HydraulicSeriesEmittersResult`` with
+        ``emitter_flow`` fp64 [S, T, Ke]; with ``warm_start`` an emitter's flow carries over while it stays on."""
         st, dev, lib = self.static(), self._dev(), _native.load()
+        with_emitters = bool(emitters) if emitters is not None else (
+            self.has_emitters or emitter_coefficient is not None or emitter_onset is not None)
+        if self.has_emitters and not with_emitters:
+            raise ValueError("a network with emitters takes the emitters launch")
+        if with_emitters:
+            valves = True
         with_valves = bool(valves) if valves is not None else (self.has_valves or valve_setting is not None)
         if self.has_valves and not with_valves:
             raise ValueError("a network with regulating valves takes the valves launch")
@@ -998,11 +1235,27 @@ class HydraulicNetwork:
                 raise ValueError(f"speed_pattern_of_pump must be [{Kp}] with values in [0, {int(smult.shape[0])})")
             spat = torch.from_numpy(spat.astype(np.int32)).to(dev)
             if with_valves:
-                need = series_valves_lds_bytes(N, P, self.half_bandwidth, K, Kp, self.num_valves)
+                need = series_emitters_lds_bytes(N, P, self.half_bandwidth, K, Kp, self.num_valves, self.num_emitters)
                 if need > LDS_BUDGET:                       # (the constructor held a network without tanks to the steady launch's sum)
                     raise ValueError(f"a series on the band of {N} rows with half-bandwidth {self.half_bandwidth} needs {need} bytes "
                                      f"of LDS, the kernel has {LDS_BUDGET}")
                 valve_args, changes, _held_v = self._valve_args(S, (S, T), valve_setting)
+                if with_emitters:
+                    emitter_args, emitter_flow, _held_e = self._emitter_args(S, (S, T), emitter_coefficient, emitter_onset, True)
+                    rc = lib.gatres_hydraulic_series_emitters(
+                        st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
+                        st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
+                        self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
+                        pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(),
+                        fh.data_ptr(), stride, tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0,
+                        float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(level),
+                        status.data_ptr(), final_dq.data_ptr(), *link_args, smult.data_ptr() if Kp else None,
+                        spat.data_ptr() if Kp else None, int(smult.shape[0]) if Kp else 0, link_state.data_ptr(), *valve_args,
+                        changes.data_ptr(), *emitter_args, _native.current_stream(dev))
+                    _native.check(rc, "gatres_hydraulic_series_emitters")
+                    return HydraulicSeriesEmittersResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
+                                                         status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq, link_state,
+                                                         changes, emitter_flow)
                 rc = lib.gatres_hydraulic_series_valves(
                     st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
                     st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
@@ -1082,7 +1335,8 @@ class HydraulicNetwork:
                               pressure_range: Tuple[float, float] = (0.0, 150.0), chunk: int = 256, normalize: bool = True,
                               allow_limited: bool = False, warm_start: bool = True, accuracy: float = ACCURACY,
                               max_iter: int = MAX_ITER, pump_speed_range=None, closed_probability: float = 0.0,
-                              speed_multipliers=None, speed_pattern_of_pump=None, valve_setting_range=None):
+                              speed_multipliers=None, speed_pattern_of_pump=None, valve_setting_range=None,
+                              emitter_coefficient_range=None, leak_probability: float = 1.0, leak_onset_range=None):
         """Draw, simulate and filter ``num_series`` series of ``steps`` steps into a ``SnapshotStore`` over the junctions whose
         rows are series-major (E * steps rows for E kept series: what ``monitor_store(series_length=steps)`` expects).  Base
         demands and roughness per series come from ``draw``, the initial levels from ``draw_levels``; ``multipliers`` default to
@@ -1093,7 +1347,10 @@ class HydraulicNetwork:
         (over the steps that did not fail), mean_iterations_first_step and series_length.  ``RuntimeError`` when nothing is
         kept.  ``pump_speed_range`` and ``closed_probability`` as in ``generate_store``, per series (a closure holds for the whole
         series); ``speed_multipliers`` and ``speed_pattern_of_pump`` go to ``simulate_series``; ``valve_setting_range`` as in
-        ``generate_store``, per series and valve."""
+        ``generate_store``, per series and valve; ``emitter_coefficient_range`` and ``leak_probability`` as in ``generate_store``,
+        per series and emitter, and ``leak_onset_range`` (lo, hi) draws the step at which each leak begins, the floor of a uniform
+        number in [lo, hi), on Ke cells after those.  The report then has ``report["leak"]``: device tensors ``coefficient``
+        [kept, Ke], ``flow`` [kept, steps, Ke] and, with ``leak_onset_range``, ``onset`` int32 [kept, Ke] -- the labels."""
         if num_series < 1 or chunk < 1 or steps < 1:
             raise ValueError("num_series, steps and chunk must be positive")
         st, dev = self.static(), self._dev()
@@ -1105,14 +1362,27 @@ class HydraulicNetwork:
             raise ValueError(f"multipliers must be [M, {steps}]")
         host_ranges = self.draw_ranges(demand_range, roughness_range)
         ranges = [torch.from_numpy(a).to(dev) for a in host_ranges]
-        link_ranges = self._link_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range)
+        leak_ranges = self._emitter_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range,
+                                               emitter_coefficient_range, leak_probability, leak_onset_range)
+        if leak_ranges is None and self.has_emitters:
+            raise ValueError("a network with emitters needs emitter_coefficient_range")
+        link_ranges = None if leak_ranges is not None else \
+            self._link_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range)
+        leak_rows = []
         link_kw = {k: v for k, v in (("speed_multipliers", speed_multipliers), ("speed_pattern_of_pump", speed_pattern_of_pump))
                    if v is not None}
         lv = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in self.level_ranges(level_range)]
         kept_rows, tables = [], []
         for first in range(0, num_series, chunk):
             n = min(chunk, num_series - first)
-            if link_ranges is None:
+            if leak_ranges is not None:
+                demand, roughness, speed, closed, setting, leak_c, leak_t = self.draw_emitters(
+                    n, seed, first, ranges[0], ranges[1], *leak_ranges, closed_probability, leak_probability)
+                link_kw.update(pump_speed=speed if self.num_pumps else None, link_closed=closed, emitter_coefficient=leak_c,
+                               emitter_onset=leak_t)
+                if valve_setting_range is not None:
+                    link_kw.update(valve_setting=setting)
+            elif link_ranges is None:
                 demand, roughness = self.draw(n, seed, first, *ranges)
             else:
                 demand, roughness, speed, closed, setting = self.draw_valves(n, seed, first, ranges[0], ranges[1], *link_ranges,
@@ -1132,10 +1402,18 @@ class HydraulicNetwork:
                 idx = torch.from_numpy(rows).to(dev)
                 kept = res.pressure.index_select(0, idx).index_select(2, st["junctions"])
                 kept_rows.append(kept.reshape(rows.size * steps, -1))
+                if leak_ranges is not None:
+                    leak_rows.append((leak_c.index_select(0, idx), res.emitter_flow.index_select(0, idx),
+                                      None if leak_t is None else leak_t.index_select(0, idx)))
         table = np.concatenate(tables, axis=0)
         report = series_report(table[:, :-1].reshape(-1, steps, HYD_STATUS), table[:, -1], allow_limited)
         if not kept_rows:
             raise RuntimeError(f"no series of {num_series} was kept with every junction pressure in {tuple(pressure_range)}: {report}")
+        if leak_ranges is not None:
+            report["leak"] = {"coefficient": torch.cat([c for c, _, _ in leak_rows], dim=0),
+                              "flow": torch.cat([f for _, f, _ in leak_rows], dim=0)}
+            if leak_onset_range is not None:
+                report["leak"]["onset"] = torch.cat([t for _, _, t in leak_rows], dim=0)
         store = SnapshotStore(torch.cat(kept_rows, dim=0), self.junction_edge_index, device=dev, normalize=normalize)
         return store, report
 
@@ -1153,7 +1431,7 @@ class HydraulicNetwork:
     def generate_store(self, num_scenarios: int, seed: int, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE,
                        pressure_range: Tuple[float, float] = (0.0, 150.0), chunk: int = 1024, normalize: bool = True,
                        accuracy: float = ACCURACY, max_iter: int = MAX_ITER, pump_speed_range=None, closed_probability: float = 0.0,
-                       valve_setting_range=None):
+                       valve_setting_range=None, emitter_coefficient_range=None, leak_probability: float = 1.0):
         """Draw, solve and filter ``num_scenarios`` scenarios into a ``SnapshotStore`` over the junctions (pressures in metres
         before the store's normalisation).  Per chunk: draw -> solve -> valid, ONE read-back (status and the valid bytes as one
         tensor), a device ``index_select`` of the kept rows.  Returns ``(store, report)``; the report counts drawn, converged,
@@ -1166,20 +1444,35 @@ class HydraulicNetwork:
         always gave).  A scenario whose closures or check valves cut a zone off does not converge: it is counted as
         not_converged, apart from out_of_range, and dropped, never repaired.  ``valve_setting_range`` (lo, hi) draws a setting per
         scenario and regulating valve, on Kv cells after all the others (``draw_valves``); a scenario whose statuses cycle is
-        counted as not_converged and dropped in the same way."""
+        counted as not_converged and dropped in the same way.  ``emitter_coefficient_range`` (lo, hi) draws a coefficient per
+        scenario and emitter on Ke cells after all the others, and ``leak_probability`` decides on Ke further cells whether the
+        emitter leaks at all (C = 0 where its cell is not below the probability; ``draw_emitters``).  The report then has
+        ``report["leak"]``: device tensors ``coefficient`` and ``flow`` [kept, Ke] of the kept rows -- the labels."""
         if num_scenarios < 1 or chunk < 1:
             raise ValueError("num_scenarios and chunk must be positive")
         st, dev = self.static(), self._dev()
         host_ranges = self.draw_ranges(demand_range, roughness_range)
         ranges = [torch.from_numpy(a).to(dev) for a in host_ranges]
-        link_ranges = self._link_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range)
-        kept_rows = []
+        leak_ranges = self._emitter_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range,
+                                               emitter_coefficient_range, leak_probability)
+        if leak_ranges is None and self.has_emitters:
+            raise ValueError("a network with emitters needs emitter_coefficient_range")
+        link_ranges = None if leak_ranges is not None else \
+            self._link_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range)
+        kept_rows, leak_rows = [], []
         report = {"drawn": 0, "converged": 0, "failed": 0, "not_converged": 0, "out_of_range": 0, "kept": 0, "max_iterations": 0,
                   "mean_iterations": 0.0}
         iter_sum = 0
         for first in range(0, num_scenarios, chunk):
             n = min(chunk, num_scenarios - first)
-            if link_ranges is None:
+            if leak_ranges is not None:
+                demand, roughness, speed, closed, setting, leak_c, _ = self.draw_emitters(
+                    n, seed, first, ranges[0], ranges[1], *leak_ranges, closed_probability, leak_probability)
+                res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False,
+                                    pump_speed=speed if self.num_pumps else None, link_closed=closed,
+                                    valve_setting=setting if valve_setting_range is not None else None,
+                                    emitter_coefficient=leak_c)
+            elif link_ranges is None:
                 demand, roughness = self.draw(n, seed, first, *ranges)
                 res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False)
             else:
@@ -1202,6 +1495,8 @@ class HydraulicNetwork:
             if rows.size:
                 idx = torch.from_numpy(rows).to(dev)
                 kept_rows.append(res.pressure.index_select(0, idx).index_select(1, st["junctions"]))
+                if leak_ranges is not None:
+                    leak_rows.append((leak_c.index_select(0, idx), res.emitter_flow.index_select(0, idx)))
         report["not_converged"] = report["drawn"] - report["converged"] - report["failed"]
         report["out_of_range"] = report["converged"] - report["kept"]
         alive_n = report["drawn"] - report["failed"]
@@ -1209,6 +1504,9 @@ class HydraulicNetwork:
         if not kept_rows:
             raise RuntimeError(f"no scenario of {num_scenarios} converged with every junction pressure in {tuple(pressure_range)}: "
                                f"{report}")
+        if leak_ranges is not None:
+            report["leak"] = {"coefficient": torch.cat([c for c, _ in leak_rows], dim=0),
+                              "flow": torch.cat([f for _, f in leak_rows], dim=0)}
         store = SnapshotStore(torch.cat(kept_rows, dim=0), self.junction_edge_index, device=dev, normalize=normalize)
         return store, report
 
@@ -1319,11 +1617,13 @@ class _NewtonRef:
                 break
         return H, q, iterations, converged, ok, rel
 
-    def run_valves(self, d, hf, r, q_start, law, valves):
+    def run_valves(self, d, hf, r, q_start, law, valves, emit=None):
         """``run`` with THE REGULATING VALVES, the loop of ``hy_newton_valves``: ``valves`` is the record of ``valve_record``; its
         ``status`` [Kv] is the start and is replaced by the end, ``changes`` counts the status changes, ``margin_h`` and
         ``margin_q`` keep the smallest distance of a comparison of the status rules from its threshold (metres, m3/s).  With no
-        valve it is ``run`` in every bit."""
+        valve it is ``run`` in every bit.  ``emit``: None, or the record of ``emitter_record`` (THE EMITTERS, the loop of
+        ``hy_newton_valves<true>``); its ``q`` [Ke] is the start and is replaced by the end; with no emitter that is on, every
+        bit is the one without the record."""
         N, P = self.net.num_nodes, self.net.num_pipes
         a, b, fixed = self.a, self.b, self.fixed
         link, psv, node, hset, live = valves["link"], valves["psv"], valves["node"], valves["hset"], valves["live"]
@@ -1352,6 +1652,11 @@ class _NewtonRef:
             t = q - y
             diag = np.zeros(N)
             F = -d.copy()
+            if emit is not None:
+                e_on, qe = emit["C"] > 0, emit["q"]
+                with np.errstate(all="ignore"):
+                    he, ge = emitter_headloss(qe, np.where(e_on, emit["C"], 1.0), emit["gamma"])
+                    einv, ey = np.where(e_on, 1.0 / ge, 0.0), np.where(e_on, he / ge, 0.0)
             for p in range(P):                              # a row's sums run over its pipes in pipe order, as in the kernel
                 ap, bp, pi, tp = a[p], b[p], pinv[p], t[p]
                 if active[p]:                               # a fixed draw at both ends
@@ -1370,6 +1675,12 @@ class _NewtonRef:
                     F[bp] += tp
                     if not ja[p]:
                         F[bp] += pi * hfe[ap]
+            if emit is not None:                            # the emitter's term, after the row's links
+                for k in np.flatnonzero(e_on):
+                    i = emit["node"][k]
+                    diag[i] += einv[k]
+                    F[i] -= qe[k] - ey[k]
+                    F[i] += emit["z"][k] * einv[k]
             diag[fx] = 1.0
             F[fx] = hfe[fx]
             try:
@@ -1394,6 +1705,9 @@ class _NewtonRef:
             H[node[on]] = hset[on]                          # (an identity row: the kernel's y / 1)
             dq = y - (H[a] - H[b]) * pinv
             q_new = q - dq
+            if emit is not None:                            # the emitters' flows, after the links'
+                dqe = np.where(e_on, ey - (H[emit["node"]] - emit["z"]) * einv, 0.0)
+                emit["q"] = qe = np.where(e_on, qe - dqe, 0.0)
             changed = 0
             for k in range(Kv):                             # every valve from the old statuses, the new heads and its own new flow
                 if not live[k]:
@@ -1420,7 +1734,10 @@ class _NewtonRef:
                         q_new[p] = 0.0
             valves["changes"] += changed
             q = q_new
-            dqs, qs = float(np.cumsum(np.abs(dq))[-1]), float(np.cumsum(np.abs(q))[-1])      # (added up in pipe order)
+            adq, aq = np.abs(dq), np.abs(q)
+            if emit is not None:                            # the emitters that are on join the sums after the links
+                adq, aq = np.concatenate([adq, np.abs(dqe[e_on])]), np.concatenate([aq, np.abs(qe[e_on])])
+            dqs, qs = float(np.cumsum(adq)[-1]), float(np.cumsum(aq)[-1])      # (added up in pipe order)
             if not (np.isfinite(dqs) and np.isfinite(qs)):
                 ok = False
                 break
@@ -1445,6 +1762,19 @@ def valve_record(network: "HydraulicNetwork", valve_setting=None, shut=None, sta
     st = np.full(Kv, VALVE_ACTIVE, dtype=np.int64) if status is None else np.asarray(status, dtype=np.int64).copy()
     return {"link": network.valve_links, "psv": network.valve_kind == LINK_PSV, "node": network.valve_node, "hset": hset,
             "live": live, "status": st, "changes": 0, "margin_h": np.inf, "margin_q": np.inf}
+
+
+def emitter_record(network: "HydraulicNetwork", emitter_coefficient, q=None, keep=None):
+    """The emitters of one scenario or step for ``_NewtonRef.run_valves``: ``emitter_coefficient`` [Ke] (0: off); the flows start
+    at the coefficient itself, the flow at one metre of pressure, but where ``keep`` [Ke] (a warm series: the emitter was on in
+    the step before) at ``q``.  None where a coefficient is negative or not finite: the scenario fails."""
+    Ke = network.num_emitters
+    C = np.zeros(0) if Ke == 0 else np.asarray(emitter_coefficient, dtype=np.float64).reshape(Ke).copy()
+    if not (np.isfinite(C).all() and (C >= 0).all()):
+        return None
+    start = C.copy() if q is None or keep is None else np.where(keep, q, C)
+    return {"node": network.emitter_nodes, "z": network.elevation[network.emitter_nodes], "C": C,
+            "gamma": network.emitter_exponent, "q": np.where(C > 0, start, 0.0)}
 
 
 def _valve_link_status(network, record) -> np.ndarray:
@@ -1482,7 +1812,7 @@ def _link_rows(network, S, pump_speed, link_closed):
 
 
 def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed,
-                     with_valves=False, valve_setting=None):
+                     with_valves=False, valve_setting=None, with_emitters=False, emitter_coefficient=None):
     newton = _NewtonRef(network, solver, accuracy, max_iter)
     demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
     S, N, P = demand.shape[0], network.num_nodes, network.num_pipes
@@ -1493,6 +1823,12 @@ def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, m
     iterations, converged, failed = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=bool), np.zeros(S, dtype=bool)
     final_dq, state = np.full(S, np.nan), np.zeros((S, P), dtype=np.uint8)
     changes, margin = np.zeros(S, dtype=np.int32), np.full((S, 2), np.inf)
+    if with_emitters:
+        if network.num_emitters and emitter_coefficient is None:
+            raise ValueError("a network with emitters needs emitter_coefficient")
+        e_coef = np.broadcast_to(np.zeros(0) if network.num_emitters == 0 else np.asarray(emitter_coefficient, dtype=np.float64),
+                                 (S, network.num_emitters))
+        e_flow = np.full((S, network.num_emitters), np.nan)
     for s in range(S):
         c = roughness[s]
         r = _link_resistance(network, c)
@@ -1504,10 +1840,11 @@ def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, m
         vs = None
         if with_valves:
             rec = valve_record(network, None if settings is None else settings[s], law["shut"])
-            if rec is None:
+            emit = emitter_record(network, e_coef[s]) if with_emitters else None
+            if rec is None or (with_emitters and emit is None):
                 failed[s] = True
                 continue
-            H, q, iterations[s], converged[s], ok, rel = newton.run_valves(d, hf, r, network.q_start, law, rec)
+            H, q, iterations[s], converged[s], ok, rel = newton.run_valves(d, hf, r, network.q_start, law, rec, emit)
             vs = _valve_link_status(network, rec)
         else:
             H, q, iterations[s], converged[s], ok, rel = newton.run(d, hf, r, network.q_start, law)
@@ -1518,6 +1855,10 @@ def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, m
         state[s] = link_state_ref(q, law["pump"], law["check"], law["shut"], law["speed"], vs)
         if with_valves:
             changes[s], margin[s] = rec["changes"], (rec["margin_h"], rec["margin_q"])
+        if with_emitters:
+            e_flow[s] = emit["q"]
+    if with_emitters:
+        return HydraulicEmittersReference(head, flow, iterations, converged, failed, final_dq, state, changes, margin, e_flow)
     if with_valves:
         return HydraulicValvesReference(head, flow, iterations, converged, failed, final_dq, state, changes, margin)
     return HydraulicLinksReference(head, flow, iterations, converged, failed, final_dq, state)
@@ -1525,7 +1866,7 @@ def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, m
 
 def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, solver: str = "dense", accuracy: float = ACCURACY,
               max_iter: int = MAX_ITER, pump_speed=None, link_closed=None, links=None, valve_setting=None,
-              valves=None) -> HydraulicReference:
+              valves=None, emitter_coefficient=None, emitters=None) -> HydraulicReference:
     """The algorithm and the stop rule of the kernel in numpy fp64, scenario by scenario, with the kernel's order in every
     sum of the assembly and of the stop rule; the linear solve is the library's.  ``solver``: "dense"
     (``numpy.linalg.solve`` on the N x N system in the given node order) or "banded" (``scipy.linalg.solveh_banded`` in the
@@ -1533,7 +1874,12 @@ def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, sol
     ``links=True``) is solved under THE LINK LAW and returns a ``HydraulicLinksReference``.  A network with regulating valves (or
     ``valve_setting`` [Kv] / [S, Kv], or ``valves=True``) is solved with their status machine (``_NewtonRef.run_valves``) and
     returns a ``HydraulicValvesReference``: the links fields, ``valve_changes`` [S] and ``margin`` [S, 2], the smallest distance
-    of a comparison of the status rules from its threshold over all iterations, in metres and in m3/s."""
+    of a comparison of the status rules from its threshold over all iterations, in metres and in m3/s.  A network with emitters
+    (or ``emitters=True``) is solved with their node term from ``emitter_coefficient`` [Ke] / [S, Ke] and returns a
+    ``HydraulicEmittersReference``: the valves fields and ``emitter_flow`` [S, Ke]."""
+    if emitters or (emitters is None and (network.has_emitters or emitter_coefficient is not None)):
+        return _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed,
+                                True, valve_setting, True, emitter_coefficient)
     if valves or (valves is None and (network.has_valves or valve_setting is not None)):
         return _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed,
                                 True, valve_setting)
@@ -1611,15 +1957,27 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                         pattern_of_node=None, fixed_head=None, solver: str = "dense", warm_start: bool = True,
                         accuracy: float = ACCURACY, max_iter: int = MAX_ITER, pump_speed=None, link_closed=None,
                         speed_multipliers=None, speed_pattern_of_pump=None, links=None, valve_setting=None,
-                        valves=None) -> HydraulicSeriesReference:
+                        valves=None, emitter_coefficient=None, emitter_onset=None, emitters=None) -> HydraulicSeriesReference:
     """``gatres_hydraulic_series`` in numpy fp64, series by series and step by step, on the Newton loop of ``solve_ref``: the
     rounded product demand * multiplier, the tank heads elevation + level, the warm or cold start, ``level_update_ref`` and
     the kernel's failure rules.  head [S, T, N], flow [S, T, P], level [S, T + 1, K], the rest [S, T].  With special links (as
     in ``simulate_series``) it is ``gatres_hydraulic_series_links`` and returns a ``HydraulicSeriesLinksReference``; with
     regulating valves (as in ``simulate_series``) it is ``gatres_hydraulic_series_valves`` and returns a
-    ``HydraulicSeriesValvesReference`` (``valve_changes`` [S, T]; ``margin`` [S, T, 2] as in ``solve_ref``)."""
+    ``HydraulicSeriesValvesReference`` (``valve_changes`` [S, T]; ``margin`` [S, T, 2] as in ``solve_ref``); with emitters (as in
+    ``simulate_series``) it is ``gatres_hydraulic_series_emitters`` and returns a ``HydraulicSeriesEmittersReference``
+    (``emitter_flow`` [S, T, Ke])."""
     newton = _NewtonRef(network, solver, accuracy, max_iter)
     demand, mult, pattern = _series_inputs(network, demand, multipliers, pattern_of_node)
+    with_emitters = bool(emitters) if emitters is not None else (
+        network.has_emitters or emitter_coefficient is not None or emitter_onset is not None)
+    if with_emitters:
+        valves, Ke = True, network.num_emitters
+        if Ke and emitter_coefficient is None:
+            raise ValueError("a network with emitters needs emitter_coefficient")
+        e_coef = np.broadcast_to(np.zeros(0) if Ke == 0 else np.asarray(emitter_coefficient, dtype=np.float64), (demand.shape[0], Ke))
+        e_onset = np.broadcast_to(np.zeros(Ke, dtype=np.int64) if emitter_onset is None or Ke == 0 else
+                                  np.asarray(emitter_onset, dtype=np.int64), (demand.shape[0], Ke))
+        e_flow = np.full((demand.shape[0], mult.shape[2], Ke), np.nan)
     with_valves = bool(valves) if valves is not None else (network.has_valves or valve_setting is not None)
     with_links = with_valves or (bool(links) if links is not None else (
         network.has_links or any(v is not None for v in (pump_speed, link_closed, speed_multipliers, speed_pattern_of_pump))))
@@ -1660,6 +2018,10 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
         elif not newton.inputs_ok(np.zeros(N), hf, c, r):
             continue
         q, lev, valve_status = network.q_start, level0[s].copy(), None
+        if with_emitters:                                   # a bad coefficient fails the series from step 0 on, whatever its onset
+            if emitter_record(network, e_coef[s]) is None:
+                continue
+            e_q, e_was_on = np.zeros(Ke), np.zeros(Ke, dtype=bool)
         for t in range(T):
             m = mult[s, :, t]
             with np.errstate(all="ignore"):
@@ -1682,8 +2044,11 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                                    valve_status if warm_start else None)
                 if rec is None:
                     break
+                emit = None
+                if with_emitters:                           # off before its onset; kept while it stays on in a warm series
+                    emit = emitter_record(network, np.where(t < e_onset[s], 0.0, e_coef[s]), e_q, e_was_on & bool(warm_start))
                 H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run_valves(
-                    d, hf, r, q if warm_start else network.q_start, law, rec)
+                    d, hf, r, q if warm_start else network.q_start, law, rec, emit)
             else:
                 H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run(d, hf, r, q if warm_start else network.q_start, law)
             if not ok:
@@ -1694,12 +2059,18 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
             if with_valves:
                 valve_status = rec["status"]
                 changes[s, t], margin[s, t] = rec["changes"], (rec["margin_h"], rec["margin_q"])
+            if with_emitters:
+                e_flow[s, t] = e_q = emit["q"]
+                e_was_on = emit["C"] > 0
             if with_links:
                 state[s, t] = link_state_ref(q, law["pump"], law["check"], law["shut"], law["speed"],
                                              _valve_link_status(network, rec) if with_valves else None)
             lev, clamped = level_update_ref(network, lev, q, step_seconds)
             level[s, t + 1], limited[s, t] = lev, clamped.any()
         converged[s] &= ~failed[s]
+    if with_emitters:
+        return HydraulicSeriesEmittersReference(head, flow, level, iterations, converged, failed, limited, final_dq, state, changes,
+                                                margin, e_flow)
     if with_valves:
         return HydraulicSeriesValvesReference(head, flow, level, iterations, converged, failed, limited, final_dq, state, changes,
                                               margin)
@@ -1740,12 +2111,14 @@ def series_report(status, valid, allow_limited: bool = False) -> Dict[str, float
 
 
 def series_volume_balance(network: HydraulicNetwork, result, demand, multipliers, step_seconds: float,
-                          pattern_of_node=None) -> np.ndarray:
+                          pattern_of_node=None, count_leaks: bool = True) -> np.ndarray:
     """THE INVARIANT of a series, per series and step, in m3 [S, T]: the change of the stored volume sum_k A_k level_k across the
     step minus dt times the net inflow to the tanks, the latter taken from the OTHER side of the network -- the net outflow of
     the reservoirs (from ``result.flow``) minus the step's total demand (from ``demand`` and ``multipliers``).  It is zero up
     to the mass residual of the step's solution, except across a step whose level was clamped.  ``result`` has ``flow``
-    [S, T, P] and ``level`` [S, T + 1, K] (a ``HydraulicSeriesReference``, or a device result brought to numpy)."""
+    [S, T, P] and ``level`` [S, T + 1, K] (a ``HydraulicSeriesReference``, or a device result brought to numpy).  On a network with
+    emitters ``result.emitter_flow`` [S, T, Ke] is an outflow like the demand: the leaked volume dt * sum q_e leaves the network;
+    ``count_leaks=False`` leaves it out, and the balance is then off by exactly that volume."""
     demand, mult, pattern = _series_inputs(network, demand, multipliers, pattern_of_node)
     flow, level = np.asarray(result.flow, dtype=np.float64), np.asarray(result.level, dtype=np.float64)
     a, b = network.pipes[:, 0], network.pipes[:, 1]
@@ -1755,19 +2128,25 @@ def series_volume_balance(network: HydraulicNetwork, result, demand, multipliers
     out_of_reservoirs = flow[:, :, reservoir[a]].sum(axis=2) - flow[:, :, reservoir[b]].sum(axis=2)
     per_node = demand[:, None, :] * np.swapaxes(mult, 1, 2)[:, :, pattern]              # [S, T, N]
     total_demand = per_node[:, :, ~network.fixed].sum(axis=2)
+    if network.num_emitters and count_leaks:
+        total_demand = total_demand + np.asarray(result.emitter_flow, dtype=np.float64).sum(axis=2)
     stored = (level * network.tank_area[None, None, :]).sum(axis=2)                     # [S, T + 1]
     return (stored[:, 1:] - stored[:, :-1]) - float(step_seconds) * (out_of_reservoirs - total_demand)
 
 
 def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness, fixed_head=None, pump_speed=None,
-                        link_closed=None, law=link_headloss, valve_setting=None, link_state=None) -> Tuple[np.ndarray, np.ndarray]:
+                        link_closed=None, law=link_headloss, valve_setting=None, link_state=None, emitter_flow=None,
+                        emitter_coefficient=None, emitter_law=emitter_headloss) -> Tuple[np.ndarray, np.ndarray]:
     """How well (head, flow) satisfy the model, per scenario: (mass, energy).  mass: the largest junction imbalance
     |inflow - outflow - demand| divided by sum |q| (not divided where that sum is 0); energy: the largest
     |H_a - H_b - h_p(q_p)| over the pipes and |H_f - fixed head| over the fixed nodes, in metres.  NaN where an input is.
     A network with special links (or ``pump_speed`` / ``link_closed``) is held to THE LINK LAW, ``law`` (``link_headloss``; the
     tests plant wrong ones).  A network with regulating valves needs ``link_state`` [S, P], the statuses the solution was
     returned with (and takes ``valve_setting`` [Kv] / [S, Kv], default the network's): an OPEN valve is held to the PIPE branch
-    with r = 0, a CLOSED one to h = 1e8 q, and the energy check of an ACTIVE valve is |H_c - hset|."""
+    with r = 0, a CLOSED one to h = 1e8 q, and the energy check of an ACTIVE valve is |H_c - hset|.  A network with emitters
+    needs ``emitter_flow`` [S, Ke] and ``emitter_coefficient`` [Ke] / [S, Ke]: the mass balance of an emitter's junction counts
+    q_e as an outflow and sum |q| includes |q_e|; the emitter's energy residual is |H_i - z_i - h(q_e)| under ``emitter_law``
+    (``emitter_headloss``), on either branch; an emitter with C = 0 is held to q_e = 0 (its |q_e| joins the mass residual)."""
     head, flow = np.asarray(head, dtype=np.float64), np.asarray(flow, dtype=np.float64)
     demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
     S, N = head.shape[0], network.num_nodes
@@ -1782,12 +2161,22 @@ def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness
     fh = _fixed_heads(network, fixed_head, S)
     a, b, fixed = network.pipes[:, 0].astype(np.int64), network.pipes[:, 1].astype(np.int64), network.fixed
     mass, energy = np.empty(S), np.empty(S)
+    Ke = network.num_emitters
+    if Ke:
+        if emitter_flow is None or emitter_coefficient is None:
+            raise ValueError("a network with emitters needs emitter_flow and emitter_coefficient")
+        e_q = np.asarray(emitter_flow, dtype=np.float64).reshape(S, Ke)
+        e_c = np.broadcast_to(np.asarray(emitter_coefficient, dtype=np.float64), (S, Ke))
     for s in range(S):
         net = np.zeros(N)
         np.add.at(net, b, flow[s])
         np.add.at(net, a, -flow[s])
+        if Ke:                                              # a leak is an outflow of its junction; none where C = 0
+            np.add.at(net, network.emitter_nodes, -np.where(e_c[s] > 0, e_q[s], 0.0))
         imbalance = np.abs(net - demand[s])[~fixed]
-        total = np.abs(flow[s]).sum()
+        if Ke:
+            imbalance = np.concatenate([imbalance, np.abs(e_q[s])[~(e_c[s] > 0)]])
+        total = np.abs(flow[s]).sum() + (np.abs(e_q[s]).sum() if Ke else 0.0)
         worst = imbalance.max() if imbalance.size else 0.0
         mass[s] = worst / total if total > 0 else worst
         if with_links:
@@ -1803,6 +2192,10 @@ def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness
         if network.has_valves:
             on = vstate[s] == VALVE_ACTIVE
             e_link[network.valve_links[on]] = np.abs(head[s][network.valve_node[on]] - (network.elevation[network.valve_node[on]] + settings[s][on]))
+        if Ke and (e_c[s] > 0).any():
+            on, i = e_c[s] > 0, network.emitter_nodes
+            he = emitter_law(e_q[s][on], e_c[s][on], network.emitter_exponent)[0]
+            e_link = np.concatenate([e_link, np.abs(head[s][i[on]] - network.elevation[i[on]] - he)])
         e_pipe = e_link.max()
         e_fixed = np.abs(head[s] - fh[s])[fixed].max()
         energy[s] = max(e_pipe, e_fixed) if not (np.isnan(e_pipe) or np.isnan(e_fixed)) else np.nan

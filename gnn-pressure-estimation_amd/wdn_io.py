@@ -169,7 +169,7 @@ NOMINAL_ROUGHNESS = 100.0               # what a pump or a valve gets in the rou
 NOMINAL_PUMP_DIAMETER = 1.0             # metres: a pump has no diameter; HydraulicNetwork asks for one and reads it nowhere
 
 InpHydraulics = namedtuple("InpHydraulics", "network demand roughness multipliers pattern_of_node pump_speed node_names link_names "
-                                            "pattern_names")
+                                            "pattern_names emitter_coefficient", defaults=(None,))
 
 
 def _inp_sections(source, text) -> "OrderedDict[str, list]":
@@ -199,7 +199,7 @@ def _inp_sections(source, text) -> "OrderedDict[str, list]":
 
 
 def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported_valves: str = "refuse", ignore_controls: bool = False,
-                         device=None, regulating: Optional[str] = None) -> "InpHydraulics":
+                         device=None, regulating: Optional[str] = None, emitters: Optional[str] = None) -> "InpHydraulics":
     """The hydraulic attributes of an EPANET input file as a ``hydraulics.HydraulicNetwork`` and the arrays ``simulate`` and
     ``simulate_series`` take, in SI units.  Read: [JUNCTIONS] (elevation, base demand, pattern), [RESERVOIRS] (head), [TANKS]
     (elevation, initial, minimum and maximum level, diameter), [PIPES] (length, diameter, roughness, minor loss, Open / Closed /
@@ -214,15 +214,25 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
     Refused with a ``ValueError`` that names the offender: flow units other than ``FLOW_UNITS``, a head-loss formula other than
     H-W, a ``POWER`` pump or one without a ``HEAD`` curve, a regulating valve (PRV, PSV, PBV, FCV, GPV) unless
     ``unsupported_valves="open"``, which makes it an open link with its minor loss, [CONTROLS] or [RULES] with content unless
-    ``ignore_controls=True``.  What EPANET does with the rest of the file (demand multiplier, emitters, quality, energy, times)
-    is not read.
+    ``ignore_controls=True``.  What EPANET does with the rest of the file (demand multiplier, emitters unless ``emitters="model"``,
+    quality, energy, times) is not read.
 
     ``regulating="model"`` (default ``None``: everything above, as it always was) makes PRV and PSV valves the regulating valves
     of ``hydraulics`` (THE REGULATING VALVES): the valve runs from its first node to its second, its setting is a pressure in the
     file's pressure unit, converted to metres (SI flow units: metres, or kPa with ``PRESSURE KPA``; US units: psi), and its loss
     coefficient may be 0.  [STATUS] may close such a valve (a shut link); a fixed OPEN status is refused by name.  FCV, PBV and
-    GPV still go by ``unsupported_valves``."""
+    GPV still go by ``unsupported_valves``.
+
+    ``emitters="model"`` (default ``None``: [EMITTERS] is not read, as it always was -- a leaky file is then simulated as tight)
+    makes the lines of [EMITTERS] the emitters of ``hydraulics`` (THE EMITTERS), in file order, with the exponent of [OPTIONS]
+    ``EMITTER EXPONENT`` (default 0.5).  A coefficient is a flow in the file's flow unit at one pressure unit (metres, kPa or psi,
+    as for ``regulating``); the result's ``emitter_coefficient`` [Ke] holds C * flow unit / (metres per pressure unit)^exponent,
+    m3/s per m^exponent.  Refused by name: an emitter on a reservoir or a tank, on no node, or listed twice, and a coefficient
+    that is negative or not finite.  What is still not read: the demand multiplier, pressure-driven demand
+    (``DEMAND MODEL PDA``), quality, energy, times."""
     from . import hydraulics as H
+    if emitters not in (None, "model"):
+        raise ValueError('emitters must be None or "model"')
     if unsupported_valves not in ("refuse", "open"):
         raise ValueError('unsupported_valves must be "refuse" or "open"')
     if regulating not in (None, "model"):
@@ -242,9 +252,9 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
     metre, dia = (1.0, 1e-3) if units in _SI_UNITS else (_FOOT, _FOOT / 12.0)
     num = lambda tok, i, default=0.0: float(tok[i]) if len(tok) > i else default
     pressure_unit = options.get("PRESSURE", "METERS" if units in _SI_UNITS else "PSI").upper()
-    if regulating and pressure_unit not in (("METERS", "KPA") if units in _SI_UNITS else ("PSI",)):
+    if (regulating or emitters) and pressure_unit not in (("METERS", "KPA") if units in _SI_UNITS else ("PSI",)):
         raise ValueError(f"[OPTIONS] PRESSURE {pressure_unit} does not go with UNITS {units}")
-    pressure = {"METERS": 1.0, "PSI": _FOOT / _PSI_PER_FOOT, "KPA": _FOOT / _PSI_PER_FOOT / _KPA_PER_PSI}[pressure_unit] if regulating else 1.0
+    pressure = {"METERS": 1.0, "PSI": _FOOT / _PSI_PER_FOOT, "KPA": _FOOT / _PSI_PER_FOOT / _KPA_PER_PSI}[pressure_unit] if (regulating or emitters) else 1.0
 
     # nodes
     names, elevation, demand, pattern_id = [], [], [], []
@@ -372,10 +382,29 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
         kw.update(pump_links=pump_links, pump_h0=h0, pump_r=rp, pump_n=n)
     if valve_links:
         kw.update(valve_links=valve_links, valve_kind=valve_kind, valve_setting=valve_setting)
+    emitter_coefficient = None
+    if emitters == "model":
+        gamma = float(options.get("EMITTER EXPONENT", 0.5))
+        e_nodes, e_coef = [], []
+        for t in sec.get("EMITTERS", []):
+            if len(t) < 2:
+                raise ValueError(f"[EMITTERS] {t[0]}: needs a junction and a coefficient")
+            if t[0] not in index:
+                raise ValueError(f"[EMITTERS] {t[0]}: no such node")
+            if index[t[0]] in fixed_nodes:
+                raise ValueError(f"[EMITTERS] {t[0]}: an emitter sits on a junction, not on a reservoir or a tank")
+            if index[t[0]] in e_nodes:
+                raise ValueError(f"[EMITTERS] {t[0]}: listed twice")
+            c = float(t[1])
+            if not (np.isfinite(c) and c >= 0):
+                raise ValueError(f"[EMITTERS] {t[0]}: the coefficient {t[1]} must be finite and not negative")
+            e_nodes.append(index[t[0]]); e_coef.append(c * flow / pressure ** gamma)
+        kw.update(emitter_nodes=e_nodes, emitter_exponent=gamma)
+        emitter_coefficient = np.asarray(e_coef, dtype=np.float64)
     network = H.HydraulicNetwork(edge_index, length, diameter, elevation, fixed_nodes, fixed_head, device=device, minor_loss=minor,
                                  check_valve=check, closed=closed, link_reversed=ends_a[:, 0] > ends_a[:, 1], **kw)
     return InpHydraulics(network, np.asarray(demand), np.asarray(rough), mult, pattern_of_node, np.asarray(pump_speed, dtype=np.float64),
-                         names, links, ["1 (constant)"] + list(pats))
+                         names, links, ["1 (constant)"] + list(pats), emitter_coefficient)
 
 
 # ------------------------------------------------------------------------------------------------------------- blosc

@@ -69,7 +69,8 @@ def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_
                            length_range=None, diameter_range=None, elevation_range=None, head_range=None, device=None,
                            num_tanks: int = 0, num_pumps: int = 0, num_check_valves: int = 0, minor_loss_range=None,
                            num_prvs: int = 0, num_psvs: int = 0, valve_seed: int = 0,
-                           valve_minor_loss: float = 2.5):
+                           valve_minor_loss: float = 2.5, num_emitters: int = 0, emitter_exponent: float = 0.5,
+                           emitter_seed: int = 0):
     """A ``hydraulics.HydraulicNetwork`` on ``make_wdn_topology(num_nodes, num_pipes, seed)``: ``num_reservoirs`` of the nodes
     are fixed-head nodes, and lengths, diameters, elevations and reservoir heads are seeded uniform numpy draws from the ranges
     of the reference's scenario generator for C-Town (``hydraulics.LENGTH_RANGE`` and so on) unless given.  The last
@@ -92,7 +93,12 @@ def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_
     of its controlled node in that scenario; ``valve_seed`` picks another layout of the valves on the same network.  A valve
     gets the minor-loss coefficient ``valve_minor_loss``: with K = 0 an OPEN valve sits on the linear floor of the law, where
     its flow jitters by 1e-7 m3/s per ulp of the heads and the stop rule is met by chance (hydraulics.py: WHAT DOES NOT HOLD).
-    ``ValueError`` where that many cannot be placed."""
+    ``ValueError`` where that many cannot be placed.
+
+    EMITTERS (hydraulics.py: THE EMITTERS), drawn after everything else with a generator of their own, so the defaults return what
+    they always did: ``num_emitters`` junctions, in a drawn order, never a fixed-head node nor the controlled node of a
+    regulating valve, get an emitter with the exponent ``emitter_exponent``; ``emitter_seed`` picks other junctions.  The
+    coefficients are a scenario's (``simulate(emitter_coefficient=)``), not the network's."""
     from . import hydraulics as H
     if not 1 <= num_reservoirs < num_nodes:
         raise ValueError("num_reservoirs must lie in [1, num_nodes)")
@@ -116,7 +122,8 @@ def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_
     if num_pumps < 0 or num_check_valves < 0:
         raise ValueError("num_pumps and num_check_valves must not be negative")
     if not (num_pumps or num_check_valves or minor_loss_range is not None):
-        return _with_valves(H, num_prvs, num_psvs, seed, valve_seed, valve_minor_loss, (ei, length, diameter, elevation, fixed_nodes, head), dict(device=device, **kw))
+        return _with_valves(H, num_prvs, num_psvs, seed, valve_seed, valve_minor_loss, (ei, length, diameter, elevation, fixed_nodes, head), dict(device=device, **kw),
+                            (num_emitters, emitter_exponent, emitter_seed))
     # the special links, drawn after everything else
     e = ei.numpy()
     pipes = e[:, e[0] < e[1]].T
@@ -153,17 +160,35 @@ def make_hydraulic_network(num_nodes: int = CTOWN_NODES, num_pipes: int = CTOWN_
     if placed < num_check_valves:
         raise ValueError(f"only {placed} of {num_check_valves} check valves can be placed without cutting a zone off")
     return _with_valves(H, num_prvs, num_psvs, seed, valve_seed, valve_minor_loss, (ei, length, diameter, elevation, fixed_nodes, head),
-                        dict(device=device, minor_loss=minor, check_valve=check, link_reversed=flip, **kw))
+                        dict(device=device, minor_loss=minor, check_valve=check, link_reversed=flip, **kw),
+                        (num_emitters, emitter_exponent, emitter_seed))
 
 
-def _with_valves(H, num_prvs: int, num_psvs: int, seed: int, valve_seed: int, valve_minor_loss: float, args, kw):
-    """The network of ``make_hydraulic_network`` with its regulating valves placed (none: the constructor's call as it was)."""
+def _with_emitters(net, rebuild, seed: int, emitters):
+    """``net`` with its emitters placed (none: ``net`` itself); ``rebuild(emitter_nodes=, emitter_exponent=)`` builds it again."""
+    num_emitters, exponent, emitter_seed = emitters
+    if num_emitters < 0:
+        raise ValueError("num_emitters must not be negative")
+    if num_emitters == 0:
+        return net
+    free = ~net.fixed
+    free[net.valve_node] = False
+    nodes = np.flatnonzero(free)
+    if num_emitters > nodes.size:
+        raise ValueError(f"num_emitters = {num_emitters}, but only {nodes.size} junctions can take an emitter")
+    rng = np.random.RandomState(seed + 32452843 + emitter_seed)
+    return rebuild(emitter_nodes=rng.permutation(nodes)[:num_emitters], emitter_exponent=exponent)
+
+
+def _with_valves(H, num_prvs: int, num_psvs: int, seed: int, valve_seed: int, valve_minor_loss: float, args, kw, emitters=(0, 0.5, 0)):
+    """The network of ``make_hydraulic_network`` with its regulating valves placed (none: the constructor's call as it was), and
+    then its emitters."""
     if num_prvs < 0 or num_psvs < 0:
         raise ValueError("num_prvs and num_psvs must not be negative")
     net = H.HydraulicNetwork(*args, **kw)
     want = ["PRV"] * num_prvs + ["PSV"] * num_psvs
     if not want:
-        return net
+        return _with_emitters(net, lambda **e: H.HydraulicNetwork(*args, **dict(kw, **e)), seed, emitters)
     demand = np.where(net.fixed, 0.0, 0.5 * (H.DEMAND_RANGE[0] + H.DEMAND_RANGE[1]))[None, :]
     roughness = np.full((1, net.num_pipes), 0.5 * (H.ROUGHNESS_RANGE[0] + H.ROUGHNESS_RANGE[1]))
     nominal = H.solve_ref(net, demand, roughness, solver="banded")
@@ -175,11 +200,11 @@ def _with_valves(H, num_prvs: int, num_psvs: int, seed: int, valve_seed: int, va
     links, kinds, settings = [], [], []
     minor = net.minor_loss.copy()
 
-    def build(flip, links, kinds, settings):
+    def build(flip, links, kinds, settings, **e):
         k = minor.copy()
         k[links] = valve_minor_loss
         return H.HydraulicNetwork(*args, **dict(kw, link_reversed=flip, minor_loss=k, valve_links=links, valve_kind=kinds,
-                                                valve_setting=settings))
+                                                valve_setting=settings, **e))
     for p in rng.permutation(net.num_pipes):
         if len(links) == len(want):
             break
@@ -198,7 +223,7 @@ def _with_valves(H, num_prvs: int, num_psvs: int, seed: int, valve_seed: int, va
         links, kinds, settings = links + [int(p)], kinds + [kind], settings + [float(pressure[c])]
     if len(links) < len(want):
         raise ValueError(f"only {len(links)} of {len(want)} regulating valves can be placed")
-    return build(flip, links, kinds, settings)
+    return _with_emitters(build(flip, links, kinds, settings), lambda **e: build(flip, links, kinds, settings, **e), seed, emitters)
 
 
 PUMP_SHUTOFF_RANGE = (20.0, 40.0)       # metres: the shut-off heads make_hydraulic_network draws

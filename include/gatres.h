@@ -1626,6 +1626,78 @@ int gatres_hydraulic_series_valves(const int32_t* pipe_a, const int32_t* pipe_b,
                                    const uint8_t* valve_kind, const double* valve_setting, int64_t valve_setting_stride,
                                    int32_t num_valves, int32_t* valve_changes, void* stream);
 
+/* THE EMITTERS: pressure-dependent outflow at junctions, EPANET's emitter q = C p^gamma -- a leak (symbols only: the ABI stays;
+ * k_hydraulic_emitters.hip, hydraulics.py).  The two launches below are gatres_hydraulic_solve_valves and
+ * gatres_hydraulic_series_valves with a node term for Ke emitters.  Emitter k sits on junction i = emitter_node[k].  It has a
+ * coefficient C >= 0 (m3/s per m^gamma) per scenario and emitter, and the launch has one exponent gamma.  It is a virtual link
+ * from i to the fixed head z_i = elevation[i] with a flow q_e of its own, positive out of the network.  With n = 1 / gamma and
+ * ce = pow(C, -n), both formed once per scenario (in a series: per step) and emitter:
+ * FORWARD BRANCH (q_e >= 0): ca = ce * pow(q_e, n - 1), g = n * ca, h = ca * q_e (h = ce q_e^n).  Where g < 1e-7 the linear floor
+ * of THE MODEL applies (g = 1e-7, h = 1e-7 q_e).  Where g > 1e8 or g is not finite (q_e -> 0 with gamma > 1; a ce that overflowed):
+ * g = 1e8, h = 1e8 q_e.
+ * REVERSE BRANCH (q_e < 0): a leak takes no water in: g = 1e8, h = 1e8 q_e, the reverse branch of a CHECK link.  A junction under
+ * negative pressure p therefore carries -|p| / 1e8, as every shut link of this solver does.
+ * C == 0 in a scenario or step means no emitter there: its row gets nothing, q_e is +0.0, and it adds nothing to the sums of the
+ * stop rule.
+ * ASSEMBLY.  Row of i, after the row's sum over the links in pipe order, with 1 / g formed once:  diag += 1 / g;
+ * f -= q_e - h / g;  f += z_i * (1 / g).  No off-diagonal is written, so the band never widens.
+ * FLOW UPDATE, after the links':  dq = h / g - (H_i - z_i) * (1 / g);  q_e -= dq.
+ * STOP RULE.  |dq| and |q_e| of the emitters that are on join the two sums after the links, in emitter order, added by the same
+ * thread.
+ * START.  q_e = C, the flow at one metre of pressure.
+ * SERIES.  emitter_onset int32, row s at emitter_onset + s * emitter_onset_stride (stride 0 or Ke; NULL: all 0): emitter k has
+ * C = 0 at the steps t < onset[k]; this is how a leak begins in the middle of a series.  With warm_start an emitter that was on in
+ * the step before keeps its q_e; one that has just switched on, and every emitter without warm_start, starts at C.
+ * WHAT DOES NOT HOLD: an emitter on the controlled node of a regulating valve is refused, not modelled: an ACTIVE valve closes
+ * the mass balance at that node over the links alone, and that rule stays as it stands.  Pressure-driven demand (EPANET 2.2's
+ * DEMAND MODEL PDA) would take the same node slot; it is out of scope.  Parity with EPANET is not claimed.
+ * INPUTS after those of the valves launches: emitter_node int32[Ke]; emitter_coef double, row s at emitter_coef + s *
+ * emitter_coef_stride, the stride 0 or Ke; num_emitters = Ke; emitter_exponent = gamma; (series) emitter_onset and its stride.
+ * Ke == 0 is legal (the arrays may be NULL), and the launch then gives every bit of the valves launch.  OUTPUT emitter_flow
+ * double[S][Ke] (series: [S][T][Ke]) at the returned heads' iteration, as flow is; NaN where the scenario or step failed.
+ * FAILED, every scenario of the launch: what fails every scenario of the valves launches; gamma not finite, not positive, or with
+ * 1 / gamma not finite; an emitter node outside [0, N), listed twice, a fixed-head node, or the controlled node of a regulating
+ * valve.  That scenario alone: a C that is negative or not finite (a series with such a C fails from step 0 on, whatever the
+ * onset).
+ * LDS need (hydraulics.emitters_lds_bytes, series_emitters_lds_bytes): the bytes of gatres_hydraulic_solve_valves (of
+ * gatres_hydraulic_series_valves)  +  48 Ke (ce, z, q_e, 1 / g, h / g, row and node per emitter), refused above
+ * GATRES_HYD_LDS_BUDGET.
+ * GATRES_E_BADARG before any launch: what the valves launches refuse; Ke < 0 or Ke > N; Ke > 0 with emitter_node, emitter_coef or
+ * emitter_flow NULL; emitter_coef_stride neither 0 nor Ke; emitter_onset_stride neither 0 nor Ke, or Ke with emitter_onset NULL;
+ * the LDS need above; an output, emitter_flow included, overlapping an input or another output. */
+int gatres_hydraulic_solve_emitters(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                                    const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                                    int32_t half_bandwidth, const double* demand, const double* roughness, const double* fixed_head,
+                                    int64_t fixed_head_stride, int64_t num_scenarios, int32_t num_nodes, int32_t num_pipes,
+                                    double accuracy, int32_t max_iter, float* pressure, double* head, double* flow, int32_t* status,
+                                    double* final_dq, const uint8_t* link_kind, const uint8_t* link_flags, const double* minor,
+                                    const int32_t* pump_link, const double* pump_h0, const double* pump_r, const double* pump_n,
+                                    int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+                                    int64_t closed_stride, uint8_t* link_state, const int32_t* valve_link,
+                                    const uint8_t* valve_kind, const double* valve_setting, int64_t valve_setting_stride,
+                                    int32_t num_valves, int32_t* valve_changes, const int32_t* emitter_node,
+                                    const double* emitter_coef, int64_t emitter_coef_stride, int32_t num_emitters,
+                                    double emitter_exponent, double* emitter_flow, void* stream);
+int gatres_hydraulic_series_emitters(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                                     const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                                     int32_t half_bandwidth, const int32_t* tank_node, const double* tank_area,
+                                     const double* tank_min_level, const double* tank_max_level, int32_t num_tanks,
+                                     const int32_t* pattern_of_node, const double* mult, int64_t mult_stride, int32_t num_patterns,
+                                     const double* demand, const double* roughness, const double* fixed_head,
+                                     int64_t fixed_head_stride, const double* initial_level, int64_t num_series, int32_t num_steps,
+                                     int32_t num_nodes, int32_t num_pipes, double dt, int32_t warm_start, double accuracy,
+                                     int32_t max_iter, float* pressure, double* head, double* flow, double* level, int32_t* status,
+                                     double* final_dq, const uint8_t* link_kind, const uint8_t* link_flags, const double* minor,
+                                     const int32_t* pump_link, const double* pump_h0, const double* pump_r, const double* pump_n,
+                                     int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+                                     int64_t closed_stride, const double* speed_mult, const int32_t* speed_pattern_of_pump,
+                                     int32_t num_speed_patterns, uint8_t* link_state, const int32_t* valve_link,
+                                     const uint8_t* valve_kind, const double* valve_setting, int64_t valve_setting_stride,
+                                     int32_t num_valves, int32_t* valve_changes, const int32_t* emitter_node,
+                                     const double* emitter_coef, int64_t emitter_coef_stride, int32_t num_emitters,
+                                     double emitter_exponent, const int32_t* emitter_onset, int64_t emitter_onset_stride,
+                                     double* emitter_flow, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
