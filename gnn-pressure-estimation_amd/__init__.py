@@ -20,7 +20,8 @@ from .hydraulics import (HydraulicLinksResult, HydraulicNetwork, HydraulicResult
                          pump_curve_from_points, series_report, series_valid_ref, series_volume_balance,
                          simulate_series_ref, solve_ref, tree_solution, HydraulicValvesResult, HydraulicSeriesValvesResult,
                          valve_status_ref, hydraulic_valve_draws, HydraulicEmittersResult, HydraulicSeriesEmittersResult,
-                         emitter_headloss, hydraulic_emitter_draws)
+                         emitter_headloss, hydraulic_emitter_draws, HydraulicPddResult, HydraulicSeriesPddResult, demand_headloss,
+                         pdd_lds_bytes, series_pdd_lds_bytes)
 from .wdn_io import parse_inp_hydraulics
 from .sensitivity import (influence_from_table, linear_spread_ref, sensitivity_fold_ref, sensitivity_rows_from_gx,
                           sensitivity_seeds)
@@ -39,4 +40,5 @@ __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "Simpl
            "HydraulicLinksResult", "HydraulicSeriesLinksResult", "link_headloss", "link_state_ref", "pump_curve_from_points",
            "hydraulic_link_draws", "parse_inp_hydraulics", "HydraulicValvesResult", "HydraulicSeriesValvesResult", "valve_status_ref",
            "hydraulic_valve_draws", "HydraulicEmittersResult", "HydraulicSeriesEmittersResult", "emitter_headloss",
-           "hydraulic_emitter_draws"]
+           "hydraulic_emitter_draws", "HydraulicPddResult", "HydraulicSeriesPddResult", "demand_headloss", "pdd_lds_bytes",
+           "series_pdd_lds_bytes"]

@@ -1,9 +1,9 @@
 // The hydraulic Newton loop, stated once for the two kernels of k_hydraulics.hip (hydraulic_solve_kernel: one steady scenario per
 // workgroup; hydraulic_series_kernel: one series of steps per workgroup) and their two counterparts with pumps, check valves,
 // closed links and minor losses in k_hydraulic_links.hip; and, at the end, with the status machine of the regulating valves for the
-// two kernels of k_hydraulic_valves.hip and, by a compile-time argument of that loop, with the node term of the emitters for the two
-// kernels of k_hydraulic_emitters.hip.  gatres.h states the model, the law at low flow, the link law, the valves, the emitters and
-// the solver.  Everything here works on one workgroup's LDS arrays; every sum runs in a fixed order.
+// two kernels of k_hydraulic_valves.hip and, by compile-time arguments of that loop, with the node term of the emitters for the two
+// kernels of k_hydraulic_emitters.hip and with the node term of the pressure-driven demand for those of k_hydraulic_pdd.hip.
+// gatres.h states the model, the law at low flow, the link law, the valves, the emitters, the pressure-driven demand and the solver.  Everything here works on one workgroup's LDS arrays; every sum runs in a fixed order.
 #pragma once
 #include "gatres_common.h"
 
@@ -331,15 +331,55 @@ __device__ __forceinline__ void emitter_headloss(double q, double ce, double n, 
   *g = gg;
 }
 
+// ---- THE PRESSURE-DRIVEN DEMAND of gatres.h (k_hydraulic_pdd.hip) ----------------------------------------------------------------
+// A junction whose full demand D is positive is a virtual link from the junction to the fixed head z = elevation + Pmin, with a
+// flow q_d of its own, positive out of the network.  The record is indexed by NODE: there are up to N of these, and no thread
+// walks a list.  dd[n] == 0 marks a node that is not pressure-driven (a fixed-head node, a junction with D <= 0): it keeps the
+// fixed draw -dem[n], its 1 / g and h / g stay +0.0, and adding them to the sums of the stop rule changes no bit.
+struct HyPdd {
+  double* dd = nullptr;                                    // [N] the full demand D of a pressure-driven junction, 0 elsewhere
+  double* q = nullptr;                                     // [N] q_d: the start on entry, the result on return
+  double* dinv = nullptr;                                  // [N] 1 / g; after the flow update |dq|
+  double* dy = nullptr;                                    // [N] h / g; after the flow update |q_d|
+  const double* elevation = nullptr;                       // [N] by node (global memory)
+  double pmin = 0.0, dp = 0.0, n = 2.0;                    // Pmin, Preq - Pmin, 1 / exponent: one value each per launch
+};
+
+// demand_headloss of gatres.h / hydraulics.py (D > 0)
+__device__ __forceinline__ void demand_headloss(double q, double D, double dp, double n, double* h, double* g) {
+  if (q < 0.0) {                                           // no demand node feeds the network
+    *g = HY_SHUT_G;
+    *h = HY_SHUT_G * q;
+    return;
+  }
+  if (q > D) {                                             // above the required pressure: the full demand, and a shut link's leak
+    *g = HY_SHUT_G;
+    *h = dp + HY_SHUT_G * (q - D);
+    return;
+  }
+  double gg = ((n * dp) * pow(q / D, n - 1.0)) / D, hh = (gg * q) / n;       // (pow(0, 0) is 1; pow(0, n - 1 < 0) is +inf)
+  if (gg < HY_LINEAR_G) {
+    gg = HY_LINEAR_G;
+    hh = HY_LINEAR_G * q;
+  } else if (!(gg <= HY_SHUT_G)) {                         // (also where g is not finite)
+    gg = HY_SHUT_G;
+    hh = HY_SHUT_G * q;
+  }
+  *h = hh;
+  *g = gg;
+}
+
 // hy_newton<true> with the status machine of the regulating valves; with Kv == 0 every operation on a double is the one of
 // hy_newton<true>, in the same order.  L.code carries the valves' bits (set by the caller: a valve that its input does not shut
 // starts with a status bit or none), L.fx the fixed-head nodes as 1; red[2] takes the iteration's count of changes.  EMIT adds
 // the node term of the emitters E at compile time (the default: the loop the valves kernels have always had); an emitter's
-// junction is never a fixed row nor a valve's controlled node (checked by the caller).
-template <bool EMIT = false>
+// junction is never a fixed row nor a valve's controlled node (checked by the caller).  PDD adds the node term of the
+// pressure-driven demand D at compile time (the default: the loop as it was); such a junction may be a valve's controlled node.
+template <bool EMIT = false, bool PDD = false>
 __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const HyValves& V, const int* __restrict__ position,
                                                            const double* dem, int N, int P, int W, int max_iter, double accuracy,
-                                                           int tid, const HyEmitters& E = HyEmitters()) {
+                                                           int tid, const HyEmitters& E = HyEmitters(),
+                                                           const HyPdd& D = HyPdd()) {
   const int BW = W + 1, Kv = V.Kv;
   double *band = L.band, *y = L.y, *H = L.H, *q = L.q, *rr = L.rr, *pinv = L.pinv, *yv = L.yv, *red = L.red;
   const int *sa = L.sa, *sb = L.sb;
@@ -380,6 +420,15 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
         E.ey[k] = on ? h / g : 0.0;
       }
     }
+    if constexpr (PDD) {                                   // one thread per node evaluates the demand's law
+      for (int n = tid; n < N; n += HY_T) {
+        double h = 0.0, g = 1.0;
+        const bool on = D.dd[n] > 0.0;
+        if (on) demand_headloss(D.q[n], D.dd[n], D.dp, D.n, &h, &g);
+        D.dinv[n] = on ? 1.0 / g : 0.0;
+        D.dy[n] = on ? h / g : 0.0;
+      }
+    }
     __syncthreads();
     // assembly: one thread per row, over the pipes in pipe order; an ACTIVE valve's flow is a fixed draw at its two ends
     for (int n = tid; n < N; n += HY_T) {
@@ -391,6 +440,9 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
         y[r] = H[r];
       } else {
         double diag = 0.0, f = -dem[n];
+        if constexpr (PDD) {                               // a pressure-driven row has no fixed draw
+          if (D.dd[n] > 0.0) f = 0.0;
+        }
         for (int p = 0; p < P; ++p) {
           const int a = sa[p], b = sb[p];
           if (a != r && b != r) continue;
@@ -412,6 +464,14 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
             diag += ei;
             f -= E.q[k] - E.ey[k];
             f += E.z[k] * ei;
+          }
+        }
+        if constexpr (PDD) {                               // then its own demand's term
+          if (D.dd[n] > 0.0) {
+            const double di = D.dinv[n];
+            diag += di;
+            f -= D.q[n] - D.dy[n];
+            f += (D.elevation[n] + D.pmin) * di;
           }
         }
         row[0] = diag;
@@ -467,6 +527,15 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
         E.ey[k] = fabs(qn);
       }
     }
+    if constexpr (PDD) {                                   // the delivered flows, after the emitters'; an ACTIVE valve's controlled
+      for (int n = tid; n < N; n += HY_T) {                // node has its target head here
+        if (!(D.dd[n] > 0.0)) continue;
+        const double dq = D.dy[n] - (H[position[n]] - (D.elevation[n] + D.pmin)) * D.dinv[n], qn = D.q[n] - dq;
+        D.q[n] = qn;
+        D.dinv[n] = fabs(dq);
+        D.dy[n] = fabs(qn);
+      }
+    }
     __syncthreads();
     // one thread per valve: an ACTIVE valve's flow closes the mass balance at its controlled node over the other links in pipe
     // order; then the status from the new heads and the valve's own new flow.  No valve shares a node with another (checked by
@@ -485,7 +554,11 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
           if (sb[o] == cr) inflow += q[o];
           if (sa[o] == cr) inflow -= q[o];
         }
-        const double d = dem[V.node[k]], qn = psv ? inflow - d : d - inflow;
+        double d = dem[V.node[k]];
+        if constexpr (PDD) {                               // the junction's new q_d (written before the barrier above)
+          if (D.dd[V.node[k]] > 0.0) d = D.q[V.node[k]];
+        }
+        const double qn = psv ? inflow - d : d - inflow;
         pinv[p] = fabs(qv - qn);
         yv[p] = fabs(qn);
         q[p] = qn;
@@ -512,6 +585,10 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
         const double* w = tid == 0 ? E.einv : E.ey;
         for (int k = 0; k < E.Ke; ++k)
           if (E.ce[k] >= 0.0) sum += w[k];
+      }
+      if constexpr (PDD) {                                 // then the pressure-driven junctions in node order (+0.0 at the others)
+        const double* w = tid == 0 ? D.dinv : D.dy;
+        for (int n = 0; n < N; ++n) sum += w[n];
       }
       red[tid == 0 ? 0 : 1] = sum;
     } else if (tid == 128) {

@@ -94,8 +94,26 @@ has just switched on starts at C.  Refused by the constructor (``ValueError``; t
 finite and positive, an emitter node outside the network, listed twice, fixed-head, or the controlled node of a regulating valve.
 A coefficient that is negative or not finite fails its scenario (a series: from step 0 on, whatever the onset).  WHAT DOES NOT
 HOLD: an emitter on a valve's controlled node is refused, not modelled (an ACTIVE valve closes that node's mass balance over the
-links alone, and that rule stays as it stands).  Pressure-driven demand (EPANET 2.2's ``DEMAND MODEL PDA``) would take the same
-node slot and is out of scope.  Parity with EPANET is not claimed.
+links alone, and that rule stays as it stands).  Parity with EPANET is not claimed.
+
+THE PRESSURE-DRIVEN DEMAND (gatres.h: THE PRESSURE-DRIVEN DEMAND; csrc/k_hydraulic_pdd.hip; ``demand_headloss``,
+``_NewtonRef.run_valves(pdd=)``).  ``simulate(demand_model="pda", minimum_pressure=, required_pressure=, pressure_exponent=)``
+takes the two pdd launches: the emitters launches with EPANET 2.2's PDA as a node term at every junction that draws.  With
+dp = Preq - Pmin and n = 1 / exponent, a junction i whose full demand D (in a series: demand x the step's multiplier) is positive
+is a virtual link from i to the fixed head z_i = elevation[i] + Pmin with a flow q_d of its own, positive out of the network:
+q_d < 0: g = 1e8, h = 1e8 q_d (no demand node feeds the network); 0 <= q_d <= D: g = n dp (q_d / D)^(n-1) / D, h = g q_d / n =
+dp (q_d / D)^n, with the linear floor where g < 1e-7 and g = 1e8, h = 1e8 q_d where g > 1e8 or g is not finite; q_d > D: g = 1e8,
+h = dp + 1e8 (q_d - D), so a junction above Preq delivers D + (p - Preq) / 1e8, as every shut link leaks.  Junctions with D <= 0
+(an inflow included) and fixed-head nodes keep the fixed draw -demand.  Assembly: a pressure-driven row gets no -demand; after its
+links in pipe order and after an emitter's term, diag += 1/g, f -= q_d - h/g, f += z_i (1/g); no off-diagonal.  Flow update after
+the links' and the emitters': dq = h/g - (H_i - z_i) (1/g), q_d -= dq; |dq| and |q_d| join the sums of the stop rule after the
+links and emitters, in node order.  Start: q_d = D; in a series with ``warm_start`` a junction that was pressure-driven in the
+step before keeps its q_d.  The controlled node of a regulating valve may be pressure-driven: while the valve is ACTIVE the row
+is the identity row, q_d is still updated from the row's head, and the valve's mass balance draws the new q_d.  An emitter and
+pressure-driven demand may share a junction.  The result's ``demand_delivered`` holds q_d at pressure-driven junctions, the demand
+itself at the others, 0 at fixed-head nodes.  ``demand_model="dda"`` takes the same launch demand-driven: every bit of the
+emitters launch.  Refused (``ValueError``; the kernels fail every scenario): pressures that are not finite, dp < 0.1 m (EPANET's
+MINPDIFF), an exponent that is not finite and positive with a finite inverse.  Parity with EPANET is not claimed.
 
 THE SERIES (``simulate_series``, ``generate_series_store``; gatres.h: THE SERIES): extended-period simulation, T steps of
 ``step_seconds`` of one scenario in one launch, one workgroup per series.  Tanks are a subset of the fixed-head nodes: tank k
@@ -130,7 +148,7 @@ the order of the upper end).
 Host restatements in numpy fp64 (the yardsticks of the tests): ``pipe_headloss``, ``solve_ref``, ``hydraulic_residuals``,
 ``hydraulic_draws``, ``tree_solution``, ``simulate_series_ref``, ``level_update_ref``, ``series_valid_ref``,
 ``series_volume_balance``, ``link_headloss``, ``link_state_ref``, ``hydraulic_link_draws``, ``pump_curve_from_points``,
-``valve_status_ref``, ``hydraulic_valve_draws``, ``emitter_headloss`` and ``hydraulic_emitter_draws``.
+``valve_status_ref``, ``hydraulic_valve_draws``, ``emitter_headloss``, ``hydraulic_emitter_draws`` and ``demand_headloss``.
 """
 from __future__ import annotations
 
@@ -216,6 +234,88 @@ def emitter_headloss(q, coefficient, exponent=EMITTER_EXPONENT) -> Tuple[np.ndar
         g = np.where(reverse, SHUT_GRADIENT, g)
         h = np.where(reverse, SHUT_GRADIENT * q, h)
     return h, g
+
+
+# what a launch with a demand model returns: the fields above, and demand_delivered (m3/s out of the network, per scenario or step
+# and node: q_d at a pressure-driven junction, the demand itself at another junction, 0 at a fixed-head node)
+HydraulicPddResult = namedtuple("HydraulicPddResult", HydraulicEmittersResult._fields + ("demand_delivered",))
+HydraulicPddReference = namedtuple("HydraulicPddReference", HydraulicEmittersReference._fields + ("demand_delivered",))
+HydraulicSeriesPddResult = namedtuple("HydraulicSeriesPddResult", HydraulicSeriesEmittersResult._fields + ("demand_delivered",))
+HydraulicSeriesPddReference = namedtuple("HydraulicSeriesPddReference",
+                                         HydraulicSeriesEmittersReference._fields + ("demand_delivered",))
+PRESSURE_EXPONENT = 0.5                 # EPANET's default
+MIN_PRESSURE_DIFFERENCE = 0.1           # EPANET's MINPDIFF, in metres here
+DEMAND_MODELS = {"dda": 0, "pda": 1}    # demand_model of the two pdd launches
+
+
+def demand_headloss(q, D, dp, exponent=PRESSURE_EXPONENT) -> Tuple[np.ndarray, np.ndarray]:
+    """THE PRESSURE-DRIVEN DEMAND, elementwise with the kernel's operations: head loss h and gradient g of the virtual link of a
+    junction with full demand D > 0 at its delivered flow q (positive out of the network), dp = Preq - Pmin, n = 1 / exponent.
+    q < 0: g = 1e8, h = 1e8 q.  0 <= q <= D: g = n dp (q / D)^(n - 1) / D, h = g q / n; the linear floor where g < 1e-7;
+    g = 1e8, h = 1e8 q where g > 1e8 or g is not finite.  q > D: g = 1e8, h = dp + 1e8 (q - D)."""
+    q, D = np.asarray(q, dtype=np.float64), np.asarray(D, dtype=np.float64)
+    dp, n = np.float64(dp), 1.0 / np.float64(exponent)
+    with np.errstate(all="ignore"):
+        g = ((n * dp) * np.power(np.maximum(q, 0.0) / D, n - 1.0)) / D
+        h = (g * q) / n
+        low = g < LINEAR_GRADIENT
+        high = ~low & ~(g <= SHUT_GRADIENT)
+        g = np.where(low, LINEAR_GRADIENT, np.where(high, SHUT_GRADIENT, g))
+        h = np.where(low, LINEAR_GRADIENT * q, np.where(high, SHUT_GRADIENT * q, h))
+        above, reverse = q > D, q < 0
+        g = np.where(above | reverse, SHUT_GRADIENT, g)
+        h = np.where(above, dp + SHUT_GRADIENT * (q - D), np.where(reverse, SHUT_GRADIENT * q, h))
+    return h, g
+
+
+def pdd_arguments(demand_model, minimum_pressure=0.0, required_pressure=None, pressure_exponent=PRESSURE_EXPONENT):
+    """None without a demand model, else the four scalars of the pdd launches: (demand_model, Pmin, Preq, exponent).  Refused with
+    ``ValueError``: a model other than "pda" / "dda", "pda" without ``required_pressure``, pressures that are not finite,
+    Preq - Pmin below 0.1 m, an exponent that is not finite and positive with a finite inverse; and, without a model, any of the
+    three scalars set.  With "dda" the three scalars are not read (an input file's may be handed on as they are)."""
+    given = required_pressure is not None or float(minimum_pressure) != 0.0 or float(pressure_exponent) != PRESSURE_EXPONENT
+    if demand_model is None:
+        if given:
+            raise ValueError("minimum_pressure, required_pressure and pressure_exponent need demand_model='pda'")
+        return None
+    if demand_model not in DEMAND_MODELS:
+        raise ValueError("demand_model must be None, 'pda' or 'dda'")
+    if demand_model == "dda":
+        return (0, 0.0, 0.0, PRESSURE_EXPONENT)
+    if required_pressure is None:
+        raise ValueError("demand_model='pda' needs required_pressure")
+    pmin, preq, e = float(minimum_pressure), float(required_pressure), float(pressure_exponent)
+    if not (np.isfinite(pmin) and np.isfinite(preq)):
+        raise ValueError("minimum_pressure and required_pressure must be finite")
+    if not preq - pmin >= MIN_PRESSURE_DIFFERENCE:
+        raise ValueError(f"required_pressure must exceed minimum_pressure by at least {MIN_PRESSURE_DIFFERENCE} m")
+    with np.errstate(all="ignore"):
+        if not (np.isfinite(e) and e > 0 and np.isfinite(np.float64(1.0) / np.float64(e))):
+            raise ValueError("pressure_exponent must be finite and positive")
+    return (1, pmin, preq, e)
+
+
+def _pdd_keywords(demand_model, minimum_pressure, required_pressure, pressure_exponent) -> dict:
+    """What the store generators hand to ``simulate``: nothing without a demand model (the call it always was)."""
+    if pdd_arguments(demand_model, minimum_pressure, required_pressure, pressure_exponent) is None:
+        return {}
+    return dict(demand_model=demand_model, minimum_pressure=minimum_pressure, required_pressure=required_pressure,
+                pressure_exponent=pressure_exponent)
+
+
+def pdd_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_pumps: int, num_valves: int, num_emitters: int,
+                  demand_model: int = 1) -> int:
+    """What a workgroup of ``gatres_hydraulic_solve_pdd`` takes of the LDS (gatres.h states the same sum): the arrays of the
+    emitters launch and, with demand_model 1, per node D, q_d, 1 / g and h / g."""
+    return emitters_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_pumps, num_valves, num_emitters) + \
+        (32 * num_nodes if demand_model else 0)
+
+
+def series_pdd_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_tanks: int, num_pumps: int, num_valves: int,
+                         num_emitters: int, demand_model: int = 1) -> int:
+    """What a workgroup of ``gatres_hydraulic_series_pdd`` takes of the LDS (gatres.h states the same sum)."""
+    return series_emitters_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_tanks, num_pumps, num_valves, num_emitters) + \
+        (32 * num_nodes if demand_model else 0)
 
 
 def emitters_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_pumps: int, num_valves: int, num_emitters: int) -> int:
@@ -1021,7 +1121,9 @@ class HydraulicNetwork:
 
     def simulate(self, demand, roughness, fixed_head=None, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
                  want_head: bool = True, want_flow: bool = True, pump_speed=None, link_closed=None, links=None,
-                 valve_setting=None, valves=None, emitter_coefficient=None, emitters=None) -> HydraulicResult:
+                 valve_setting=None, valves=None, emitter_coefficient=None, emitters=None, demand_model=None,
+                 minimum_pressure: float = 0.0, required_pressure=None,
+                 pressure_exponent: float = PRESSURE_EXPONENT) -> HydraulicResult:
         """Solve S scenarios on the device.  ``demand`` [S, N] m3/s (ignored at fixed nodes), ``roughness`` [S, P]
         Hazen-Williams coefficients, ``fixed_head`` None (the network's), [N] or [S, N] (read at fixed nodes).  Every field
         of the result is a device tensor; nothing is read back.  A network with a special link or a minor loss (or
@@ -1032,8 +1134,15 @@ class HydraulicNetwork:
         ``gatres_hydraulic_solve_valves`` and returns a ``HydraulicValvesResult``: the links fields and ``valve_changes`` int32 [S].
         A network with emitters (or ``emitters=True``) takes ``gatres_hydraulic_solve_emitters`` with ``emitter_coefficient`` [Ke] /
         [S, Ke] (m3/s per m^gamma, required; 0 is no leak there) and returns a ``HydraulicEmittersResult``: the valves fields and
-        ``emitter_flow`` fp64 [S, Ke], the leaked flows."""
+        ``emitter_flow`` fp64 [S, Ke], the leaked flows.  ``demand_model="pda"`` (THE PRESSURE-DRIVEN DEMAND) takes
+        ``gatres_hydraulic_solve_pdd`` on any network, with ``minimum_pressure``, ``required_pressure`` (required) in metres and
+        ``pressure_exponent``, and returns a ``HydraulicPddResult``: the emitters fields and ``demand_delivered`` fp64 [S, N];
+        ``demand_model="dda"`` takes the same launch demand-driven (every bit of the emitters launch, and the demand itself as
+        ``demand_delivered``).  Without ``demand_model`` the call takes exactly the launches it always took."""
         st, dev, lib = self.static(), self._dev(), _native.load()
+        pdd = pdd_arguments(demand_model, minimum_pressure, required_pressure, pressure_exponent)
+        if pdd is not None:
+            emitters = True
         with_emitters = bool(emitters) if emitters is not None else (self.has_emitters or emitter_coefficient is not None)
         if self.has_emitters and not with_emitters:
             raise ValueError("a network with emitters takes the emitters launch")
@@ -1073,6 +1182,23 @@ class HydraulicNetwork:
             valve_args, changes, _held_v = self._valve_args(S, (S,), valve_setting)
             if with_emitters:
                 emitter_args, emitter_flow, _held_e = self._emitter_args(S, (S,), emitter_coefficient)
+                if pdd is not None:
+                    need = pdd_lds_bytes(N, P, self.half_bandwidth, self.num_pumps, self.num_valves, self.num_emitters, pdd[0])
+                    if need > LDS_BUDGET:
+                        raise ValueError(f"the band of {N} rows with half-bandwidth {self.half_bandwidth} needs {need} bytes of LDS "
+                                         f"with this demand model, the kernel has {LDS_BUDGET}")
+                    delivered = torch.empty((S, N), dtype=torch.float64, device=dev)
+                    rc = lib.gatres_hydraulic_solve_pdd(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
+                                                        st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
+                                                        st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
+                                                        demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P,
+                                                        float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head),
+                                                        _native.ptr(flow), status.data_ptr(), final_dq.data_ptr(), *link_args,
+                                                        link_state.data_ptr(), *valve_args, changes.data_ptr(), *emitter_args,
+                                                        *pdd, delivered.data_ptr(), _native.current_stream(dev))
+                    _native.check(rc, "gatres_hydraulic_solve_pdd")
+                    return HydraulicPddResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status,
+                                              final_dq, link_state, changes, emitter_flow, delivered)
                 rc = lib.gatres_hydraulic_solve_emitters(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
                                                          st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
                                                          st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
@@ -1133,7 +1259,8 @@ class HydraulicNetwork:
                         fixed_head=None, warm_start: bool = True, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
                         want_head: bool = True, want_flow: bool = True, pump_speed=None, link_closed=None, speed_multipliers=None,
                         speed_pattern_of_pump=None, links=None, valve_setting=None, valves=None, emitter_coefficient=None,
-                        emitter_onset=None, emitters=None) -> HydraulicSeriesResult:
+                        emitter_onset=None, emitters=None, demand_model=None, minimum_pressure: float = 0.0,
+                        required_pressure=None, pressure_exponent: float = PRESSURE_EXPONENT) -> HydraulicSeriesResult:
         """``gatres_hydraulic_series``: S series of T steps on the device, one launch.  ``demand`` [S, N] base demands,
         ``roughness`` [S, P], ``multipliers`` [M, T] (for every series) or [S, M, T], ``pattern_of_node`` int [N] with values in
         [0, M) (default: pattern 0 everywhere; host data outside the range raises ``ValueError``, a DEVICE tensor is not read back
@@ -1152,8 +1279,14 @@ class HydraulicNetwork:
         not fit is refused here with ``ValueError``.  A network with emitters (or ``emitters=True``) takes
         ``gatres_hydraulic_series_emitters`` with ``emitter_coefficient`` [Ke] / [S, Ke] and ``emitter_onset`` int [Ke] / [S, Ke]
         (default 0: emitter k leaks nothing at the steps t < onset) and returns a ``HydraulicSeriesEmittersResult`` with
-        ``emitter_flow`` fp64 [S, T, Ke]; with ``warm_start`` an emitter's flow carries over while it stays on."""
+        ``emitter_flow`` fp64 [S, T, Ke]; with ``warm_start`` an emitter's flow carries over while it stays on.  ``demand_model``,
+        ``minimum_pressure``, ``required_pressure`` and ``pressure_exponent`` as in ``simulate``: ``gatres_hydraulic_series_pdd`` and a
+        ``HydraulicSeriesPddResult`` with ``demand_delivered`` fp64 [S, T, N]; a junction is pressure-driven at the steps where
+        its demand times the multiplier is positive, and with ``warm_start`` keeps its delivered flow while it stays so."""
         st, dev, lib = self.static(), self._dev(), _native.load()
+        pdd = pdd_arguments(demand_model, minimum_pressure, required_pressure, pressure_exponent)
+        if pdd is not None:
+            emitters = True
         with_emitters = bool(emitters) if emitters is not None else (
             self.has_emitters or emitter_coefficient is not None or emitter_onset is not None)
         if self.has_emitters and not with_emitters:
@@ -1235,13 +1368,30 @@ class HydraulicNetwork:
                 raise ValueError(f"speed_pattern_of_pump must be [{Kp}] with values in [0, {int(smult.shape[0])})")
             spat = torch.from_numpy(spat.astype(np.int32)).to(dev)
             if with_valves:
-                need = series_emitters_lds_bytes(N, P, self.half_bandwidth, K, Kp, self.num_valves, self.num_emitters)
+                need = series_pdd_lds_bytes(N, P, self.half_bandwidth, K, Kp, self.num_valves, self.num_emitters,
+                                            0 if pdd is None else pdd[0])
                 if need > LDS_BUDGET:                       # (the constructor held a network without tanks to the steady launch's sum)
                     raise ValueError(f"a series on the band of {N} rows with half-bandwidth {self.half_bandwidth} needs {need} bytes "
                                      f"of LDS, the kernel has {LDS_BUDGET}")
                 valve_args, changes, _held_v = self._valve_args(S, (S, T), valve_setting)
                 if with_emitters:
                     emitter_args, emitter_flow, _held_e = self._emitter_args(S, (S, T), emitter_coefficient, emitter_onset, True)
+                    if pdd is not None:
+                        delivered = torch.empty((S, T, N), dtype=torch.float64, device=dev)
+                        rc = lib.gatres_hydraulic_series_pdd(
+                            st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
+                            st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
+                            self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
+                            pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(),
+                            fh.data_ptr(), stride, tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0,
+                            float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(level),
+                            status.data_ptr(), final_dq.data_ptr(), *link_args, smult.data_ptr() if Kp else None,
+                            spat.data_ptr() if Kp else None, int(smult.shape[0]) if Kp else 0, link_state.data_ptr(), *valve_args,
+                            changes.data_ptr(), *emitter_args, *pdd, delivered.data_ptr(), _native.current_stream(dev))
+                        _native.check(rc, "gatres_hydraulic_series_pdd")
+                        return HydraulicSeriesPddResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
+                                                        status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq, link_state,
+                                                        changes, emitter_flow, delivered)
                     rc = lib.gatres_hydraulic_series_emitters(
                         st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
                         st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
@@ -1336,7 +1486,9 @@ class HydraulicNetwork:
                               allow_limited: bool = False, warm_start: bool = True, accuracy: float = ACCURACY,
                               max_iter: int = MAX_ITER, pump_speed_range=None, closed_probability: float = 0.0,
                               speed_multipliers=None, speed_pattern_of_pump=None, valve_setting_range=None,
-                              emitter_coefficient_range=None, leak_probability: float = 1.0, leak_onset_range=None):
+                              emitter_coefficient_range=None, leak_probability: float = 1.0, leak_onset_range=None,
+                              demand_model=None, minimum_pressure: float = 0.0, required_pressure=None,
+                              pressure_exponent: float = PRESSURE_EXPONENT):
         """Draw, simulate and filter ``num_series`` series of ``steps`` steps into a ``SnapshotStore`` over the junctions whose
         rows are series-major (E * steps rows for E kept series: what ``monitor_store(series_length=steps)`` expects).  Base
         demands and roughness per series come from ``draw``, the initial levels from ``draw_levels``; ``multipliers`` default to
@@ -1350,7 +1502,11 @@ class HydraulicNetwork:
         ``generate_store``, per series and valve; ``emitter_coefficient_range`` and ``leak_probability`` as in ``generate_store``,
         per series and emitter, and ``leak_onset_range`` (lo, hi) draws the step at which each leak begins, the floor of a uniform
         number in [lo, hi), on Ke cells after those.  The report then has ``report["leak"]``: device tensors ``coefficient``
-        [kept, Ke], ``flow`` [kept, steps, Ke] and, with ``leak_onset_range``, ``onset`` int32 [kept, Ke] -- the labels."""
+        [kept, Ke], ``flow`` [kept, steps, Ke] and, with ``leak_onset_range``, ``onset`` int32 [kept, Ke] -- the labels.
+        ``demand_model`` and its three scalars as in ``generate_store``: ``report["supply"]`` then holds ``delivered`` and ``full``
+        [kept, steps, N]."""
+        pdd_kw = _pdd_keywords(demand_model, minimum_pressure, required_pressure, pressure_exponent)
+        supply_rows = []
         if num_series < 1 or chunk < 1 or steps < 1:
             raise ValueError("num_series, steps and chunk must be positive")
         st, dev = self.static(), self._dev()
@@ -1393,7 +1549,7 @@ class HydraulicNetwork:
             level0 = self.draw_levels(n, seed, first, *lv)
             res = self.simulate_series(demand, roughness, mult, step_seconds=step_seconds, initial_level=level0,
                                        pattern_of_node=pattern_of_node, warm_start=warm_start, accuracy=accuracy,
-                                       max_iter=max_iter, want_head=False, want_flow=False, **link_kw)
+                                       max_iter=max_iter, want_head=False, want_flow=False, **link_kw, **pdd_kw)
             ok = self.series_valid(res, pressure_range, allow_limited)
             table = torch.cat([res.status.reshape(n, -1), ok.to(torch.int32)[:, None]], dim=1).cpu().numpy()     # the read-back
             tables.append(table)
@@ -1405,6 +1561,11 @@ class HydraulicNetwork:
                 if leak_ranges is not None:
                     leak_rows.append((leak_c.index_select(0, idx), res.emitter_flow.index_select(0, idx),
                                       None if leak_t is None else leak_t.index_select(0, idx)))
+                if pdd_kw:                                  # the full demand of a step: the kernel's one rounded product
+                    pat = torch.zeros(self.num_nodes, dtype=torch.int64, device=dev) if pattern_of_node is None else \
+                        torch.as_tensor(pattern_of_node).to(device=dev, dtype=torch.int64)
+                    full = demand.index_select(0, idx)[:, None, :] * mult.t().index_select(1, pat)[None, :, :]
+                    supply_rows.append((res.demand_delivered.index_select(0, idx), full))
         table = np.concatenate(tables, axis=0)
         report = series_report(table[:, :-1].reshape(-1, steps, HYD_STATUS), table[:, -1], allow_limited)
         if not kept_rows:
@@ -1414,6 +1575,9 @@ class HydraulicNetwork:
                               "flow": torch.cat([f for _, f, _ in leak_rows], dim=0)}
             if leak_onset_range is not None:
                 report["leak"]["onset"] = torch.cat([t for _, _, t in leak_rows], dim=0)
+        if pdd_kw:
+            report["supply"] = {"delivered": torch.cat([d for d, _ in supply_rows], dim=0),
+                                "full": torch.cat([f for _, f in supply_rows], dim=0)}
         store = SnapshotStore(torch.cat(kept_rows, dim=0), self.junction_edge_index, device=dev, normalize=normalize)
         return store, report
 
@@ -1431,7 +1595,9 @@ class HydraulicNetwork:
     def generate_store(self, num_scenarios: int, seed: int, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE,
                        pressure_range: Tuple[float, float] = (0.0, 150.0), chunk: int = 1024, normalize: bool = True,
                        accuracy: float = ACCURACY, max_iter: int = MAX_ITER, pump_speed_range=None, closed_probability: float = 0.0,
-                       valve_setting_range=None, emitter_coefficient_range=None, leak_probability: float = 1.0):
+                       valve_setting_range=None, emitter_coefficient_range=None, leak_probability: float = 1.0,
+                       demand_model=None, minimum_pressure: float = 0.0, required_pressure=None,
+                       pressure_exponent: float = PRESSURE_EXPONENT):
         """Draw, solve and filter ``num_scenarios`` scenarios into a ``SnapshotStore`` over the junctions (pressures in metres
         before the store's normalisation).  Per chunk: draw -> solve -> valid, ONE read-back (status and the valid bytes as one
         tensor), a device ``index_select`` of the kept rows.  Returns ``(store, report)``; the report counts drawn, converged,
@@ -1447,7 +1613,14 @@ class HydraulicNetwork:
         counted as not_converged and dropped in the same way.  ``emitter_coefficient_range`` (lo, hi) draws a coefficient per
         scenario and emitter on Ke cells after all the others, and ``leak_probability`` decides on Ke further cells whether the
         emitter leaks at all (C = 0 where its cell is not below the probability; ``draw_emitters``).  The report then has
-        ``report["leak"]``: device tensors ``coefficient`` and ``flow`` [kept, Ke] of the kept rows -- the labels."""
+        ``report["leak"]``: device tensors ``coefficient`` and ``flow`` [kept, Ke] of the kept rows -- the labels.
+        ``demand_model="pda"`` with ``minimum_pressure``, ``required_pressure`` and ``pressure_exponent`` (as in ``simulate``)
+        solves every scenario pressure-driven; no cell is drawn for it, so the draws are those of the call without it.  The report
+        then has ``report["supply"]``: device tensors ``delivered`` (``demand_delivered``) and ``full`` (the full demand, 0 at
+        fixed-head nodes), fp64 [kept, N] of the kept rows -- the labels of deficient supply: a junction is short by
+        full - delivered."""
+        pdd_kw = _pdd_keywords(demand_model, minimum_pressure, required_pressure, pressure_exponent)
+        supply_rows = []
         if num_scenarios < 1 or chunk < 1:
             raise ValueError("num_scenarios and chunk must be positive")
         st, dev = self.static(), self._dev()
@@ -1471,16 +1644,17 @@ class HydraulicNetwork:
                 res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False,
                                     pump_speed=speed if self.num_pumps else None, link_closed=closed,
                                     valve_setting=setting if valve_setting_range is not None else None,
-                                    emitter_coefficient=leak_c)
+                                    emitter_coefficient=leak_c, **pdd_kw)
             elif link_ranges is None:
                 demand, roughness = self.draw(n, seed, first, *ranges)
-                res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False)
+                res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False,
+                                    **pdd_kw)
             else:
                 demand, roughness, speed, closed, setting = self.draw_valves(n, seed, first, ranges[0], ranges[1], *link_ranges,
                                                                              closed_probability)
                 res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False,
                                     pump_speed=speed if self.num_pumps else None, link_closed=closed,
-                                    valve_setting=setting if valve_setting_range is not None else None)
+                                    valve_setting=setting if valve_setting_range is not None else None, **pdd_kw)
             ok = self.valid(res, pressure_range)
             table = torch.cat([res.status[:, :3], ok.to(torch.int32)[:, None]], dim=1).cpu().numpy()     # the read-back
             rows = np.flatnonzero(table[:, 3])
@@ -1497,6 +1671,8 @@ class HydraulicNetwork:
                 kept_rows.append(res.pressure.index_select(0, idx).index_select(1, st["junctions"]))
                 if leak_ranges is not None:
                     leak_rows.append((leak_c.index_select(0, idx), res.emitter_flow.index_select(0, idx)))
+                if pdd_kw:
+                    supply_rows.append((res.demand_delivered.index_select(0, idx), demand.index_select(0, idx)))
         report["not_converged"] = report["drawn"] - report["converged"] - report["failed"]
         report["out_of_range"] = report["converged"] - report["kept"]
         alive_n = report["drawn"] - report["failed"]
@@ -1507,6 +1683,9 @@ class HydraulicNetwork:
         if leak_ranges is not None:
             report["leak"] = {"coefficient": torch.cat([c for c, _ in leak_rows], dim=0),
                               "flow": torch.cat([f for _, f in leak_rows], dim=0)}
+        if pdd_kw:
+            report["supply"] = {"delivered": torch.cat([d for d, _ in supply_rows], dim=0),
+                                "full": torch.cat([f for _, f in supply_rows], dim=0)}
         store = SnapshotStore(torch.cat(kept_rows, dim=0), self.junction_edge_index, device=dev, normalize=normalize)
         return store, report
 
@@ -1617,13 +1796,14 @@ class _NewtonRef:
                 break
         return H, q, iterations, converged, ok, rel
 
-    def run_valves(self, d, hf, r, q_start, law, valves, emit=None):
+    def run_valves(self, d, hf, r, q_start, law, valves, emit=None, pdd=None):
         """``run`` with THE REGULATING VALVES, the loop of ``hy_newton_valves``: ``valves`` is the record of ``valve_record``; its
         ``status`` [Kv] is the start and is replaced by the end, ``changes`` counts the status changes, ``margin_h`` and
         ``margin_q`` keep the smallest distance of a comparison of the status rules from its threshold (metres, m3/s).  With no
         valve it is ``run`` in every bit.  ``emit``: None, or the record of ``emitter_record`` (THE EMITTERS, the loop of
         ``hy_newton_valves<true>``); its ``q`` [Ke] is the start and is replaced by the end; with no emitter that is on, every
-        bit is the one without the record."""
+        bit is the one without the record.  ``pdd``: None, or the record of ``demand_record`` (THE PRESSURE-DRIVEN DEMAND, the
+        loop of ``hy_newton_valves<true, true>``); its ``q`` [N] is the start and is replaced by the end."""
         N, P = self.net.num_nodes, self.net.num_pipes
         a, b, fixed = self.a, self.b, self.fixed
         link, psv, node, hset, live = valves["link"], valves["psv"], valves["node"], valves["hset"], valves["live"]
@@ -1657,6 +1837,12 @@ class _NewtonRef:
                 with np.errstate(all="ignore"):
                     he, ge = emitter_headloss(qe, np.where(e_on, emit["C"], 1.0), emit["gamma"])
                     einv, ey = np.where(e_on, 1.0 / ge, 0.0), np.where(e_on, he / ge, 0.0)
+            if pdd is not None:
+                d_on, qd = pdd["on"], pdd["q"]
+                with np.errstate(all="ignore"):
+                    hd, gd = demand_headloss(qd, np.where(d_on, pdd["D"], 1.0), pdd["dp"], pdd["exponent"])
+                    dinv, dy = np.where(d_on, 1.0 / gd, 0.0), np.where(d_on, hd / gd, 0.0)
+                F[d_on] = 0.0                               # a pressure-driven row has no fixed draw
             for p in range(P):                              # a row's sums run over its pipes in pipe order, as in the kernel
                 ap, bp, pi, tp = a[p], b[p], pinv[p], t[p]
                 if active[p]:                               # a fixed draw at both ends
@@ -1681,6 +1867,11 @@ class _NewtonRef:
                     diag[i] += einv[k]
                     F[i] -= qe[k] - ey[k]
                     F[i] += emit["z"][k] * einv[k]
+            if pdd is not None:                             # then the junction's own demand term
+                for i in np.flatnonzero(d_on):
+                    diag[i] += dinv[i]
+                    F[i] -= qd[i] - dy[i]
+                    F[i] += pdd["z"][i] * dinv[i]
             diag[fx] = 1.0
             F[fx] = hfe[fx]
             try:
@@ -1708,6 +1899,11 @@ class _NewtonRef:
             if emit is not None:                            # the emitters' flows, after the links'
                 dqe = np.where(e_on, ey - (H[emit["node"]] - emit["z"]) * einv, 0.0)
                 emit["q"] = qe = np.where(e_on, qe - dqe, 0.0)
+            if pdd is not None:                             # the delivered flows, after the emitters'
+                with np.errstate(all="ignore"):
+                    dqd = np.where(d_on, dy - (H - pdd["z"]) * dinv, 0.0)
+                pdd["q"] = qd = np.where(d_on, qd - dqd, 0.0)
+            d_valve = d if pdd is None else np.where(d_on, qd, d)      # what an ACTIVE valve's mass balance draws at its node
             changed = 0
             for k in range(Kv):                             # every valve from the old statuses, the new heads and its own new flow
                 if not live[k]:
@@ -1722,7 +1918,7 @@ class _NewtonRef:
                             inflow += q_new[o]
                         if a[o] == node[k]:
                             inflow -= q_new[o]
-                    qn = inflow - d[node[k]] if psv[k] else d[node[k]] - inflow
+                    qn = inflow - d_valve[node[k]] if psv[k] else d_valve[node[k]] - inflow
                     dq[p], q_new[p] = q[p] - qn, qn
                 qv = q_new[p]
                 ns, mh, mq = _valve_rule(bool(psv[k]), st, H[a[p]], H[b[p]], qv, (law["minor"][p] * abs(qv)) * qv, hset[k])
@@ -1737,6 +1933,8 @@ class _NewtonRef:
             adq, aq = np.abs(dq), np.abs(q)
             if emit is not None:                            # the emitters that are on join the sums after the links
                 adq, aq = np.concatenate([adq, np.abs(dqe[e_on])]), np.concatenate([aq, np.abs(qe[e_on])])
+            if pdd is not None:                             # then the pressure-driven junctions, in node order
+                adq, aq = np.concatenate([adq, np.abs(dqd[d_on])]), np.concatenate([aq, np.abs(qd[d_on])])
             dqs, qs = float(np.cumsum(adq)[-1]), float(np.cumsum(aq)[-1])      # (added up in pipe order)
             if not (np.isfinite(dqs) and np.isfinite(qs)):
                 ok = False
@@ -1777,6 +1975,28 @@ def emitter_record(network: "HydraulicNetwork", emitter_coefficient, q=None, kee
             "gamma": network.emitter_exponent, "q": np.where(C > 0, start, 0.0)}
 
 
+def demand_record(network: "HydraulicNetwork", d, pdd, q=None, keep=None):
+    """The pressure-driven junctions of one scenario or step for ``_NewtonRef.run_valves``: ``d`` [N] the full demands (0 at fixed
+    nodes), ``pdd`` the tuple of ``pdd_arguments`` with model 1.  A junction is pressure-driven where d > 0; its flow starts at d,
+    but where ``keep`` [N] (a warm series: it was pressure-driven in the step before) at ``q``.  None where the head
+    elevation + Pmin of such a junction is not finite: the scenario fails."""
+    d = np.asarray(d, dtype=np.float64)
+    on = ~network.fixed & (d > 0)
+    with np.errstate(all="ignore"):
+        z = network.elevation + np.float64(pdd[1])
+    if not np.isfinite(z[on]).all():
+        return None
+    start = d.copy() if q is None or keep is None else np.where(keep, q, d)
+    return {"on": on, "D": np.where(on, d, 0.0), "z": z, "dp": np.float64(pdd[2]) - np.float64(pdd[1]), "exponent": pdd[3],
+            "q": np.where(on, start, 0.0)}
+
+
+def _delivered(record, d, fixed):
+    """demand_delivered of one scenario or step: q_d where pressure-driven, the demand itself at other junctions, 0 at fixed nodes."""
+    out = np.where(fixed, 0.0, d)
+    return out if record is None else np.where(record["on"], record["q"], out)
+
+
 def _valve_link_status(network, record) -> np.ndarray:
     """Per link: the status of a live valve, -1 elsewhere (what ``link_state_ref`` takes)."""
     vs = np.full(network.num_pipes, -1, dtype=np.int64)
@@ -1812,7 +2032,7 @@ def _link_rows(network, S, pump_speed, link_closed):
 
 
 def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed,
-                     with_valves=False, valve_setting=None, with_emitters=False, emitter_coefficient=None):
+                     with_valves=False, valve_setting=None, with_emitters=False, emitter_coefficient=None, pdd=None):
     newton = _NewtonRef(network, solver, accuracy, max_iter)
     demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
     S, N, P = demand.shape[0], network.num_nodes, network.num_pipes
@@ -1829,6 +2049,7 @@ def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, m
         e_coef = np.broadcast_to(np.zeros(0) if network.num_emitters == 0 else np.asarray(emitter_coefficient, dtype=np.float64),
                                  (S, network.num_emitters))
         e_flow = np.full((S, network.num_emitters), np.nan)
+    delivered = np.full((S, N), np.nan)
     for s in range(S):
         c = roughness[s]
         r = _link_resistance(network, c)
@@ -1841,10 +2062,11 @@ def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, m
         if with_valves:
             rec = valve_record(network, None if settings is None else settings[s], law["shut"])
             emit = emitter_record(network, e_coef[s]) if with_emitters else None
-            if rec is None or (with_emitters and emit is None):
+            dem = demand_record(network, d, pdd) if pdd is not None and pdd[0] else None
+            if rec is None or (with_emitters and emit is None) or (pdd is not None and pdd[0] and dem is None):
                 failed[s] = True
                 continue
-            H, q, iterations[s], converged[s], ok, rel = newton.run_valves(d, hf, r, network.q_start, law, rec, emit)
+            H, q, iterations[s], converged[s], ok, rel = newton.run_valves(d, hf, r, network.q_start, law, rec, emit, dem)
             vs = _valve_link_status(network, rec)
         else:
             H, q, iterations[s], converged[s], ok, rel = newton.run(d, hf, r, network.q_start, law)
@@ -1857,6 +2079,10 @@ def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, m
             changes[s], margin[s] = rec["changes"], (rec["margin_h"], rec["margin_q"])
         if with_emitters:
             e_flow[s] = emit["q"]
+        if pdd is not None:
+            delivered[s] = _delivered(dem, d, fixed)
+    if pdd is not None:
+        return HydraulicPddReference(head, flow, iterations, converged, failed, final_dq, state, changes, margin, e_flow, delivered)
     if with_emitters:
         return HydraulicEmittersReference(head, flow, iterations, converged, failed, final_dq, state, changes, margin, e_flow)
     if with_valves:
@@ -1866,7 +2092,8 @@ def _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, m
 
 def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, solver: str = "dense", accuracy: float = ACCURACY,
               max_iter: int = MAX_ITER, pump_speed=None, link_closed=None, links=None, valve_setting=None,
-              valves=None, emitter_coefficient=None, emitters=None) -> HydraulicReference:
+              valves=None, emitter_coefficient=None, emitters=None, demand_model=None, minimum_pressure: float = 0.0,
+              required_pressure=None, pressure_exponent: float = PRESSURE_EXPONENT) -> HydraulicReference:
     """The algorithm and the stop rule of the kernel in numpy fp64, scenario by scenario, with the kernel's order in every
     sum of the assembly and of the stop rule; the linear solve is the library's.  ``solver``: "dense"
     (``numpy.linalg.solve`` on the N x N system in the given node order) or "banded" (``scipy.linalg.solveh_banded`` in the
@@ -1876,7 +2103,12 @@ def solve_ref(network: HydraulicNetwork, demand, roughness, fixed_head=None, sol
     returns a ``HydraulicValvesReference``: the links fields, ``valve_changes`` [S] and ``margin`` [S, 2], the smallest distance
     of a comparison of the status rules from its threshold over all iterations, in metres and in m3/s.  A network with emitters
     (or ``emitters=True``) is solved with their node term from ``emitter_coefficient`` [Ke] / [S, Ke] and returns a
-    ``HydraulicEmittersReference``: the valves fields and ``emitter_flow`` [S, Ke]."""
+    ``HydraulicEmittersReference``: the valves fields and ``emitter_flow`` [S, Ke].  ``demand_model`` and its three scalars as in
+    ``simulate``: ``gatres_hydraulic_solve_pdd`` and a ``HydraulicPddReference`` with ``demand_delivered`` [S, N]."""
+    pdd = pdd_arguments(demand_model, minimum_pressure, required_pressure, pressure_exponent)
+    if pdd is not None:
+        return _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed,
+                                True, valve_setting, True, emitter_coefficient, pdd)
     if emitters or (emitters is None and (network.has_emitters or emitter_coefficient is not None)):
         return _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed,
                                 True, valve_setting, True, emitter_coefficient)
@@ -1957,7 +2189,9 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                         pattern_of_node=None, fixed_head=None, solver: str = "dense", warm_start: bool = True,
                         accuracy: float = ACCURACY, max_iter: int = MAX_ITER, pump_speed=None, link_closed=None,
                         speed_multipliers=None, speed_pattern_of_pump=None, links=None, valve_setting=None,
-                        valves=None, emitter_coefficient=None, emitter_onset=None, emitters=None) -> HydraulicSeriesReference:
+                        valves=None, emitter_coefficient=None, emitter_onset=None, emitters=None, demand_model=None,
+                        minimum_pressure: float = 0.0, required_pressure=None,
+                        pressure_exponent: float = PRESSURE_EXPONENT) -> HydraulicSeriesReference:
     """``gatres_hydraulic_series`` in numpy fp64, series by series and step by step, on the Newton loop of ``solve_ref``: the
     rounded product demand * multiplier, the tank heads elevation + level, the warm or cold start, ``level_update_ref`` and
     the kernel's failure rules.  head [S, T, N], flow [S, T, P], level [S, T + 1, K], the rest [S, T].  With special links (as
@@ -1965,9 +2199,14 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
     regulating valves (as in ``simulate_series``) it is ``gatres_hydraulic_series_valves`` and returns a
     ``HydraulicSeriesValvesReference`` (``valve_changes`` [S, T]; ``margin`` [S, T, 2] as in ``solve_ref``); with emitters (as in
     ``simulate_series``) it is ``gatres_hydraulic_series_emitters`` and returns a ``HydraulicSeriesEmittersReference``
-    (``emitter_flow`` [S, T, Ke])."""
+    (``emitter_flow`` [S, T, Ke]); with ``demand_model`` (as in ``simulate_series``) it is ``gatres_hydraulic_series_pdd`` and returns
+    a ``HydraulicSeriesPddReference`` (``demand_delivered`` [S, T, N])."""
     newton = _NewtonRef(network, solver, accuracy, max_iter)
     demand, mult, pattern = _series_inputs(network, demand, multipliers, pattern_of_node)
+    pdd = pdd_arguments(demand_model, minimum_pressure, required_pressure, pressure_exponent)
+    if pdd is not None:
+        emitters = True
+        delivered = np.full((demand.shape[0], mult.shape[2], network.num_nodes), np.nan)
     with_emitters = bool(emitters) if emitters is not None else (
         network.has_emitters or emitter_coefficient is not None or emitter_onset is not None)
     if with_emitters:
@@ -2022,6 +2261,7 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
             if emitter_record(network, e_coef[s]) is None:
                 continue
             e_q, e_was_on = np.zeros(Ke), np.zeros(Ke, dtype=bool)
+        d_q, d_was_on = np.zeros(N), np.zeros(N, dtype=bool)
         for t in range(T):
             m = mult[s, :, t]
             with np.errstate(all="ignore"):
@@ -2047,8 +2287,13 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                 emit = None
                 if with_emitters:                           # off before its onset; kept while it stays on in a warm series
                     emit = emitter_record(network, np.where(t < e_onset[s], 0.0, e_coef[s]), e_q, e_was_on & bool(warm_start))
+                dem = None
+                if pdd is not None and pdd[0]:              # kept while the junction stays pressure-driven in a warm series
+                    dem = demand_record(network, d, pdd, d_q, d_was_on & bool(warm_start))
+                    if dem is None:
+                        break
                 H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run_valves(
-                    d, hf, r, q if warm_start else network.q_start, law, rec, emit)
+                    d, hf, r, q if warm_start else network.q_start, law, rec, emit, dem)
             else:
                 H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run(d, hf, r, q if warm_start else network.q_start, law)
             if not ok:
@@ -2062,12 +2307,19 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
             if with_emitters:
                 e_flow[s, t] = e_q = emit["q"]
                 e_was_on = emit["C"] > 0
+            if pdd is not None:
+                delivered[s, t] = _delivered(dem, d, fixed)
+                if dem is not None:
+                    d_q, d_was_on = dem["q"], dem["on"]
             if with_links:
                 state[s, t] = link_state_ref(q, law["pump"], law["check"], law["shut"], law["speed"],
                                              _valve_link_status(network, rec) if with_valves else None)
             lev, clamped = level_update_ref(network, lev, q, step_seconds)
             level[s, t + 1], limited[s, t] = lev, clamped.any()
         converged[s] &= ~failed[s]
+    if pdd is not None:
+        return HydraulicSeriesPddReference(head, flow, level, iterations, converged, failed, limited, final_dq, state, changes,
+                                           margin, e_flow, delivered)
     if with_emitters:
         return HydraulicSeriesEmittersReference(head, flow, level, iterations, converged, failed, limited, final_dq, state, changes,
                                                 margin, e_flow)
@@ -2118,7 +2370,8 @@ def series_volume_balance(network: HydraulicNetwork, result, demand, multipliers
     to the mass residual of the step's solution, except across a step whose level was clamped.  ``result`` has ``flow``
     [S, T, P] and ``level`` [S, T + 1, K] (a ``HydraulicSeriesReference``, or a device result brought to numpy).  On a network with
     emitters ``result.emitter_flow`` [S, T, Ke] is an outflow like the demand: the leaked volume dt * sum q_e leaves the network;
-    ``count_leaks=False`` leaves it out, and the balance is then off by exactly that volume."""
+    ``count_leaks=False`` leaves it out, and the balance is then off by exactly that volume.  A result with ``demand_delivered``
+    [S, T, N] (a launch with a demand model) is balanced with the delivered volume in place of the demanded one."""
     demand, mult, pattern = _series_inputs(network, demand, multipliers, pattern_of_node)
     flow, level = np.asarray(result.flow, dtype=np.float64), np.asarray(result.level, dtype=np.float64)
     a, b = network.pipes[:, 0], network.pipes[:, 1]
@@ -2127,6 +2380,8 @@ def series_volume_balance(network: HydraulicNetwork, result, demand, multipliers
     reservoir = network.fixed & ~tank
     out_of_reservoirs = flow[:, :, reservoir[a]].sum(axis=2) - flow[:, :, reservoir[b]].sum(axis=2)
     per_node = demand[:, None, :] * np.swapaxes(mult, 1, 2)[:, :, pattern]              # [S, T, N]
+    if getattr(result, "demand_delivered", None) is not None:
+        per_node = np.asarray(result.demand_delivered, dtype=np.float64)
     total_demand = per_node[:, :, ~network.fixed].sum(axis=2)
     if network.num_emitters and count_leaks:
         total_demand = total_demand + np.asarray(result.emitter_flow, dtype=np.float64).sum(axis=2)
@@ -2136,7 +2391,9 @@ def series_volume_balance(network: HydraulicNetwork, result, demand, multipliers
 
 def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness, fixed_head=None, pump_speed=None,
                         link_closed=None, law=link_headloss, valve_setting=None, link_state=None, emitter_flow=None,
-                        emitter_coefficient=None, emitter_law=emitter_headloss) -> Tuple[np.ndarray, np.ndarray]:
+                        emitter_coefficient=None, emitter_law=emitter_headloss, demand_delivered=None, demand_model=None,
+                        minimum_pressure: float = 0.0, required_pressure=None, pressure_exponent: float = PRESSURE_EXPONENT,
+                        demand_law=demand_headloss) -> Tuple[np.ndarray, np.ndarray]:
     """How well (head, flow) satisfy the model, per scenario: (mass, energy).  mass: the largest junction imbalance
     |inflow - outflow - demand| divided by sum |q| (not divided where that sum is 0); energy: the largest
     |H_a - H_b - h_p(q_p)| over the pipes and |H_f - fixed head| over the fixed nodes, in metres.  NaN where an input is.
@@ -2146,7 +2403,17 @@ def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness
     with r = 0, a CLOSED one to h = 1e8 q, and the energy check of an ACTIVE valve is |H_c - hset|.  A network with emitters
     needs ``emitter_flow`` [S, Ke] and ``emitter_coefficient`` [Ke] / [S, Ke]: the mass balance of an emitter's junction counts
     q_e as an outflow and sum |q| includes |q_e|; the emitter's energy residual is |H_i - z_i - h(q_e)| under ``emitter_law``
-    (``emitter_headloss``), on either branch; an emitter with C = 0 is held to q_e = 0 (its |q_e| joins the mass residual)."""
+    (``emitter_headloss``), on either branch; an emitter with C = 0 is held to q_e = 0 (its |q_e| joins the mass residual).
+    With ``demand_model="pda"`` (and its scalars, as in ``simulate``) ``demand_delivered`` [S, N] is needed: a junction with a
+    positive demand draws its delivered flow q_d in the mass balance, sum |q| includes |q_d|, and its virtual link's energy
+    residual is |H_i - elevation_i - Pmin - h(q_d)| under ``demand_law`` (``demand_headloss``), on every branch; at the other
+    junctions |delivered - demand| joins the mass residual."""
+    pdd = pdd_arguments(demand_model, minimum_pressure, required_pressure, pressure_exponent)
+    pdd = pdd if pdd is not None and pdd[0] else None
+    if pdd is not None:
+        if demand_delivered is None:
+            raise ValueError("demand_model='pda' needs demand_delivered")
+        d_q = np.asarray(demand_delivered, dtype=np.float64).reshape(np.asarray(head).shape[0], network.num_nodes)
     head, flow = np.asarray(head, dtype=np.float64), np.asarray(flow, dtype=np.float64)
     demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
     S, N = head.shape[0], network.num_nodes
@@ -2173,10 +2440,17 @@ def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness
         np.add.at(net, a, -flow[s])
         if Ke:                                              # a leak is an outflow of its junction; none where C = 0
             np.add.at(net, network.emitter_nodes, -np.where(e_c[s] > 0, e_q[s], 0.0))
-        imbalance = np.abs(net - demand[s])[~fixed]
+        draw = demand[s]
+        if pdd is not None:                                 # a pressure-driven junction draws what it is delivered
+            d_on = ~fixed & (demand[s] > 0)
+            draw = np.where(d_on, d_q[s], demand[s])
+        imbalance = np.abs(net - draw)[~fixed]
         if Ke:
             imbalance = np.concatenate([imbalance, np.abs(e_q[s])[~(e_c[s] > 0)]])
         total = np.abs(flow[s]).sum() + (np.abs(e_q[s]).sum() if Ke else 0.0)
+        if pdd is not None:
+            imbalance = np.concatenate([imbalance, np.abs(d_q[s] - demand[s])[~fixed & ~d_on]])
+            total += np.abs(d_q[s][d_on]).sum()
         worst = imbalance.max() if imbalance.size else 0.0
         mass[s] = worst / total if total > 0 else worst
         if with_links:
@@ -2196,6 +2470,9 @@ def hydraulic_residuals(network: HydraulicNetwork, head, flow, demand, roughness
             on, i = e_c[s] > 0, network.emitter_nodes
             he = emitter_law(e_q[s][on], e_c[s][on], network.emitter_exponent)[0]
             e_link = np.concatenate([e_link, np.abs(head[s][i[on]] - network.elevation[i[on]] - he)])
+        if pdd is not None and d_on.any():
+            hd = demand_law(d_q[s][d_on], demand[s][d_on], pdd[2] - pdd[1], pdd[3])[0]
+            e_link = np.concatenate([e_link, np.abs(head[s][d_on] - network.elevation[d_on] - pdd[1] - hd)])
         e_pipe = e_link.max()
         e_fixed = np.abs(head[s] - fh[s])[fixed].max()
         energy[s] = max(e_pipe, e_fixed) if not (np.isnan(e_pipe) or np.isnan(e_fixed)) else np.nan

@@ -169,7 +169,8 @@ NOMINAL_ROUGHNESS = 100.0               # what a pump or a valve gets in the rou
 NOMINAL_PUMP_DIAMETER = 1.0             # metres: a pump has no diameter; HydraulicNetwork asks for one and reads it nowhere
 
 InpHydraulics = namedtuple("InpHydraulics", "network demand roughness multipliers pattern_of_node pump_speed node_names link_names "
-                                            "pattern_names emitter_coefficient", defaults=(None,))
+                                            "pattern_names emitter_coefficient demand_model minimum_pressure required_pressure "
+                                            "pressure_exponent", defaults=(None,) * 5)
 
 
 def _inp_sections(source, text) -> "OrderedDict[str, list]":
@@ -199,7 +200,8 @@ def _inp_sections(source, text) -> "OrderedDict[str, list]":
 
 
 def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported_valves: str = "refuse", ignore_controls: bool = False,
-                         device=None, regulating: Optional[str] = None, emitters: Optional[str] = None) -> "InpHydraulics":
+                         device=None, regulating: Optional[str] = None, emitters: Optional[str] = None,
+                         demand_model: Optional[str] = None) -> "InpHydraulics":
     """The hydraulic attributes of an EPANET input file as a ``hydraulics.HydraulicNetwork`` and the arrays ``simulate`` and
     ``simulate_series`` take, in SI units.  Read: [JUNCTIONS] (elevation, base demand, pattern), [RESERVOIRS] (head), [TANKS]
     (elevation, initial, minimum and maximum level, diameter), [PIPES] (length, diameter, roughness, minor loss, Open / Closed /
@@ -215,7 +217,7 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
     H-W, a ``POWER`` pump or one without a ``HEAD`` curve, a regulating valve (PRV, PSV, PBV, FCV, GPV) unless
     ``unsupported_valves="open"``, which makes it an open link with its minor loss, [CONTROLS] or [RULES] with content unless
     ``ignore_controls=True``.  What EPANET does with the rest of the file (demand multiplier, emitters unless ``emitters="model"``,
-    quality, energy, times) is not read.
+    the demand model unless ``demand_model="model"``, quality, energy, times) is not read.
 
     ``regulating="model"`` (default ``None``: everything above, as it always was) makes PRV and PSV valves the regulating valves
     of ``hydraulics`` (THE REGULATING VALVES): the valve runs from its first node to its second, its setting is a pressure in the
@@ -228,9 +230,19 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
     ``EMITTER EXPONENT`` (default 0.5).  A coefficient is a flow in the file's flow unit at one pressure unit (metres, kPa or psi,
     as for ``regulating``); the result's ``emitter_coefficient`` [Ke] holds C * flow unit / (metres per pressure unit)^exponent,
     m3/s per m^exponent.  Refused by name: an emitter on a reservoir or a tank, on no node, or listed twice, and a coefficient
-    that is negative or not finite.  What is still not read: the demand multiplier, pressure-driven demand
-    (``DEMAND MODEL PDA``), quality, energy, times."""
+    that is negative or not finite.
+
+    ``demand_model="model"`` (default ``None``: the four options are not read, as they never were -- a file that asks for PDA is
+    then simulated demand-driven) takes from [OPTIONS] ``DEMAND MODEL`` (``DDA``, the default, or ``PDA``), ``MINIMUM PRESSURE``
+    (default 0), ``REQUIRED PRESSURE`` (default 0.1) and ``PRESSURE EXPONENT`` (default 0.5), the pressures converted to metres
+    as for ``regulating``.  The result's ``demand_model`` is "dda" or "pda" and its ``minimum_pressure``, ``required_pressure`` and
+    ``pressure_exponent`` are what ``simulate(demand_model=...)`` takes (THE PRESSURE-DRIVEN DEMAND).  Refused by name: a
+    ``DEMAND MODEL`` word other than DDA or PDA, a value that is not finite, an exponent that is not positive and, with PDA, a
+    required pressure less than 0.1 m above the minimum pressure.  What is still not read: the demand multiplier, quality,
+    energy, times."""
     from . import hydraulics as H
+    if demand_model not in (None, "model"):
+        raise ValueError('demand_model must be None or "model"')
     if emitters not in (None, "model"):
         raise ValueError('emitters must be None or "model"')
     if unsupported_valves not in ("refuse", "open"):
@@ -252,9 +264,9 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
     metre, dia = (1.0, 1e-3) if units in _SI_UNITS else (_FOOT, _FOOT / 12.0)
     num = lambda tok, i, default=0.0: float(tok[i]) if len(tok) > i else default
     pressure_unit = options.get("PRESSURE", "METERS" if units in _SI_UNITS else "PSI").upper()
-    if (regulating or emitters) and pressure_unit not in (("METERS", "KPA") if units in _SI_UNITS else ("PSI",)):
+    if (regulating or emitters or demand_model) and pressure_unit not in (("METERS", "KPA") if units in _SI_UNITS else ("PSI",)):
         raise ValueError(f"[OPTIONS] PRESSURE {pressure_unit} does not go with UNITS {units}")
-    pressure = {"METERS": 1.0, "PSI": _FOOT / _PSI_PER_FOOT, "KPA": _FOOT / _PSI_PER_FOOT / _KPA_PER_PSI}[pressure_unit] if (regulating or emitters) else 1.0
+    pressure = {"METERS": 1.0, "PSI": _FOOT / _PSI_PER_FOOT, "KPA": _FOOT / _PSI_PER_FOOT / _KPA_PER_PSI}[pressure_unit] if (regulating or emitters or demand_model) else 1.0
 
     # nodes
     names, elevation, demand, pattern_id = [], [], [], []
@@ -401,10 +413,31 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
             e_nodes.append(index[t[0]]); e_coef.append(c * flow / pressure ** gamma)
         kw.update(emitter_nodes=e_nodes, emitter_exponent=gamma)
         emitter_coefficient = np.asarray(e_coef, dtype=np.float64)
+    pdd = (None,) * 4
+    if demand_model == "model":
+        word = options.get("DEMAND MODEL", "DDA").upper()
+        if word not in ("DDA", "PDA"):
+            raise ValueError(f"[OPTIONS] DEMAND MODEL {word}: the demand model must be DDA or PDA")
+        values = {}
+        for key, default in (("MINIMUM PRESSURE", 0.0), ("REQUIRED PRESSURE", 0.1), ("PRESSURE EXPONENT", 0.5)):
+            try:
+                values[key] = float(options.get(key, default))
+            except ValueError:
+                values[key] = float("nan")
+            if not np.isfinite(values[key]):
+                raise ValueError(f"[OPTIONS] {key} {options.get(key)}: must be a finite number")
+        p_min, p_req, e = values["MINIMUM PRESSURE"] * pressure, values["REQUIRED PRESSURE"] * pressure, values["PRESSURE EXPONENT"]
+        if not (e > 0 and np.isfinite(1.0 / e)):
+            raise ValueError(f"[OPTIONS] PRESSURE EXPONENT {options.get('PRESSURE EXPONENT')}: must be positive")
+        if word == "PDA" and not p_req - p_min >= H.MIN_PRESSURE_DIFFERENCE:
+            raise ValueError(f"[OPTIONS] REQUIRED PRESSURE {options.get('REQUIRED PRESSURE', 0.1)}: must lie at least "
+                             f"{H.MIN_PRESSURE_DIFFERENCE} m above MINIMUM PRESSURE {options.get('MINIMUM PRESSURE', 0)} "
+                             f"({p_req:.6g} m against {p_min:.6g} m)")
+        pdd = (word.lower(), p_min, p_req, e)
     network = H.HydraulicNetwork(edge_index, length, diameter, elevation, fixed_nodes, fixed_head, device=device, minor_loss=minor,
                                  check_valve=check, closed=closed, link_reversed=ends_a[:, 0] > ends_a[:, 1], **kw)
     return InpHydraulics(network, np.asarray(demand), np.asarray(rough), mult, pattern_of_node, np.asarray(pump_speed, dtype=np.float64),
-                         names, links, ["1 (constant)"] + list(pats), emitter_coefficient)
+                         names, links, ["1 (constant)"] + list(pats), emitter_coefficient, *pdd)
 
 
 # ------------------------------------------------------------------------------------------------------------- blosc

@@ -1650,7 +1650,8 @@ int gatres_hydraulic_series_valves(const int32_t* pipe_a, const int32_t* pipe_b,
  * the step before keeps its q_e; one that has just switched on, and every emitter without warm_start, starts at C.
  * WHAT DOES NOT HOLD: an emitter on the controlled node of a regulating valve is refused, not modelled: an ACTIVE valve closes
  * the mass balance at that node over the links alone, and that rule stays as it stands.  Pressure-driven demand (EPANET 2.2's
- * DEMAND MODEL PDA) would take the same node slot; it is out of scope.  Parity with EPANET is not claimed.
+ * DEMAND MODEL PDA) takes the same node slot, at every junction that draws: THE PRESSURE-DRIVEN DEMAND, below.  Parity with
+ * EPANET is not claimed.
  * INPUTS after those of the valves launches: emitter_node int32[Ke]; emitter_coef double, row s at emitter_coef + s *
  * emitter_coef_stride, the stride 0 or Ke; num_emitters = Ke; emitter_exponent = gamma; (series) emitter_onset and its stride.
  * Ke == 0 is legal (the arrays may be NULL), and the launch then gives every bit of the valves launch.  OUTPUT emitter_flow
@@ -1697,6 +1698,85 @@ int gatres_hydraulic_series_emitters(const int32_t* pipe_a, const int32_t* pipe_
                                      const double* emitter_coef, int64_t emitter_coef_stride, int32_t num_emitters,
                                      double emitter_exponent, const int32_t* emitter_onset, int64_t emitter_onset_stride,
                                      double* emitter_flow, void* stream);
+
+/* THE PRESSURE-DRIVEN DEMAND: EPANET 2.2's DEMAND MODEL PDA (symbols only: the ABI stays; k_hydraulic_pdd.hip, hydraulics.py).
+ * The two launches below are gatres_hydraulic_solve_emitters and gatres_hydraulic_series_emitters with a node term for the
+ * demand.  A launch has demand_model (0 demand-driven, 1 pressure-driven) and three scalars: minimum_pressure Pmin and
+ * required_pressure Preq in metres, pressure_exponent e (EPANET's default 0.5).  dp = Preq - Pmin, n = 1 / e.
+ * WHICH JUNCTIONS.  Junction i is pressure-driven in a scenario (in a series: in a step) where its full demand D_i is positive;
+ * D_i is demand[i], in a series the step's rounded product demand[i] * multiplier.  A junction with D_i <= 0 (an inflow
+ * included) and every fixed-head node keep the fixed draw -demand exactly as in the emitters launches.
+ * THE VIRTUAL LINK.  A pressure-driven junction is a virtual link from i to the fixed head z_i = elevation[i] + Pmin with a flow
+ * q_d of its own, positive out of the network.  Its law (EPANET 2.2's demandheadloss with this solver's gradients 1e8 and 1e-7):
+ *   q_d < 0:        g = 1e8, h = 1e8 q_d: no demand node feeds the network.
+ *   0 <= q_d <= D:  g = ((n * dp) * pow(q_d / D, n - 1)) / D, h = (g * q_d) / n, which is dp (q_d / D)^n.  Where g < 1e-7 the linear
+ *                   floor of THE MODEL applies (g = 1e-7, h = 1e-7 q_d).  Where g > 1e8 or g is not finite: g = 1e8, h = 1e8 q_d.
+ *   q_d > D:        g = 1e8, h = dp + 1e8 (q_d - D).  A junction above Preq delivers D + (p - Preq) / 1e8, as every shut link of
+ *                   this solver leaks; a junction below Pmin carries -|p - Pmin| / 1e8.
+ * ASSEMBLY.  For a pressure-driven row the term -demand is not added (f starts at 0).  After the row's links in pipe order and
+ * after an emitter's term, with 1 / g formed once:  diag += 1 / g;  f -= q_d - h / g;  f += z_i * (1 / g).  No off-diagonal is
+ * written, so the band never widens.
+ * FLOW UPDATE, after the links' and the emitters':  dq = h / g - (H_i - z_i) * (1 / g);  q_d -= dq.
+ * STOP RULE.  |dq| and |q_d| of the pressure-driven junctions join the two sums after the links and the emitters, in node order,
+ * added by the same thread.  (The kernel adds the +0.0 that the other nodes hold in the same arrays, which changes no bit.)
+ * START.  q_d = D.
+ * SERIES.  D changes with the multipliers.  With warm_start a junction that was pressure-driven in the step before keeps its
+ * q_d; one that has just become pressure-driven, and every junction without warm_start, starts at D.  The tank levels follow the
+ * link flows as they always did, so a starved network drains its tanks more slowly.
+ * REGULATING VALVES.  The controlled node of a regulating valve may be pressure-driven.  While the valve is ACTIVE the row is
+ * the identity row it always was, the virtual link's flow update still runs from the row's head (the valve's target), and the
+ * valve's thread closes the mass balance of the node with the junction's new q_d where it reads the demand otherwise.  An
+ * emitter on such a node stays refused.
+ * EMITTERS.  An emitter and pressure-driven demand may share a junction; both terms add, the emitter's first.
+ * INPUTS after those of the emitters launches: demand_model, minimum_pressure, required_pressure, pressure_exponent.  OUTPUT
+ * demand_delivered double[S][N] (series: [S][T][N]): q_d at a pressure-driven junction, the demand itself (the step's product) at
+ * another junction, 0 at a fixed-head node; at the returned heads' iteration, as flow is; NaN where the scenario or step failed.
+ * pressure, head, flow, status, link_state, valve_changes and emitter_flow keep their meaning.
+ * With demand_model 0 the launch gives every bit of the emitters launch on the same inputs; the three scalars are not read, and
+ * demand_delivered may be NULL (where it is not, it gets the demands as said above).
+ * FAILED, every scenario of the launch: what fails every scenario of the emitters launches; with demand_model 1, Pmin or Preq
+ * not finite, dp < 0.1 m (EPANET's MINPDIFF) or not a number, e or 1 / e not finite or not positive.  That scenario or step alone
+ * (a series: from that step on): a pressure-driven junction whose elevation + Pmin is not finite.
+ * LDS need (hydraulics.pdd_lds_bytes, series_pdd_lds_bytes): the bytes of gatres_hydraulic_solve_emitters (of
+ * gatres_hydraulic_series_emitters)  +  with demand_model 1, 32 N (D, q_d, 1 / g and h / g per node; z_i is formed from the
+ * elevation where it is used), refused above GATRES_HYD_LDS_BUDGET.  The 388 / 430 / 3 network of the tests takes 104 680 bytes
+ * (series: 107 904).
+ * GATRES_E_BADARG before any launch: what the emitters launches refuse; demand_model outside {0, 1}; demand_delivered NULL with
+ * demand_model 1; the LDS need above; an output, demand_delivered included, overlapping an input or another output. */
+int gatres_hydraulic_solve_pdd(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                               const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                               int32_t half_bandwidth, const double* demand, const double* roughness, const double* fixed_head,
+                               int64_t fixed_head_stride, int64_t num_scenarios, int32_t num_nodes, int32_t num_pipes,
+                               double accuracy, int32_t max_iter, float* pressure, double* head, double* flow, int32_t* status,
+                               double* final_dq, const uint8_t* link_kind, const uint8_t* link_flags, const double* minor,
+                               const int32_t* pump_link, const double* pump_h0, const double* pump_r, const double* pump_n,
+                               int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+                               int64_t closed_stride, uint8_t* link_state, const int32_t* valve_link,
+                               const uint8_t* valve_kind, const double* valve_setting, int64_t valve_setting_stride,
+                               int32_t num_valves, int32_t* valve_changes, const int32_t* emitter_node,
+                               const double* emitter_coef, int64_t emitter_coef_stride, int32_t num_emitters,
+                               double emitter_exponent, double* emitter_flow, int32_t demand_model, double minimum_pressure,
+                               double required_pressure, double pressure_exponent, double* demand_delivered, void* stream);
+int gatres_hydraulic_series_pdd(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                                const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                                int32_t half_bandwidth, const int32_t* tank_node, const double* tank_area,
+                                const double* tank_min_level, const double* tank_max_level, int32_t num_tanks,
+                                const int32_t* pattern_of_node, const double* mult, int64_t mult_stride, int32_t num_patterns,
+                                const double* demand, const double* roughness, const double* fixed_head,
+                                int64_t fixed_head_stride, const double* initial_level, int64_t num_series, int32_t num_steps,
+                                int32_t num_nodes, int32_t num_pipes, double dt, int32_t warm_start, double accuracy,
+                                int32_t max_iter, float* pressure, double* head, double* flow, double* level, int32_t* status,
+                                double* final_dq, const uint8_t* link_kind, const uint8_t* link_flags, const double* minor,
+                                const int32_t* pump_link, const double* pump_h0, const double* pump_r, const double* pump_n,
+                                int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+                                int64_t closed_stride, const double* speed_mult, const int32_t* speed_pattern_of_pump,
+                                int32_t num_speed_patterns, uint8_t* link_state, const int32_t* valve_link,
+                                const uint8_t* valve_kind, const double* valve_setting, int64_t valve_setting_stride,
+                                int32_t num_valves, int32_t* valve_changes, const int32_t* emitter_node,
+                                const double* emitter_coef, int64_t emitter_coef_stride, int32_t num_emitters,
+                                double emitter_exponent, const int32_t* emitter_onset, int64_t emitter_onset_stride,
+                                double* emitter_flow, int32_t demand_model, double minimum_pressure, double required_pressure,
+                                double pressure_exponent, double* demand_delivered, void* stream);
 
 const char* gatres_version(void);
 
