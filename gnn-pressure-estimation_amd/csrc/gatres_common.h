@@ -97,6 +97,12 @@ static inline int gatres_launch_status() { return (int)hipGetLastError(); }
 static inline hipStream_t gatres_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline bool gatres_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline bool gatres_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+// Do the byte ranges [a, a + na) and [b, b + nb) overlap?  A null pointer is no range: the entry points' overlap checks pass their
+// optional arrays as they are.
+static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
 
 // lanes that cooperate on one feature row: one float4 per lane, rounded up to a power of two
 static inline int gatres_row_lanes(int width) {

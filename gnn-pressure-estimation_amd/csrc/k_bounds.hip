@@ -268,11 +268,6 @@ __global__ __launch_bounds__(BC_T) void node_bound_coverage_kernel(const float* 
   }
 }
 
-static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // What both entry points refuse about their inputs
 static bool bq_inputs_ok(const float* est, const float* truth, int64_t S, int32_t N, const int32_t* observed, int32_t K,
                          const uint8_t* available, int32_t Q) {

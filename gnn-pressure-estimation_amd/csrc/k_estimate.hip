@@ -571,11 +571,6 @@ __global__ __launch_bounds__(LR_T) void layout_error_reduce_kernel(const double*
   for (int f = 0; f < 4; ++f) t[f] = a[f];
 }
 
-static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // The checks and the launch of the staging entry points (AVAIL: with the availability arguments; NOISE / LAYOUTS / TARGETS:
 // first_row is the first pair, rows is NULL and nz / lay / tg holds the noise / layout / target arguments).
 template <bool AVAIL, bool NOISE = false, bool LAYOUTS = false, bool TARGETS = false>

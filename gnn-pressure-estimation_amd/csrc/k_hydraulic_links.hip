@@ -108,30 +108,6 @@ __device__ __forceinline__ bool hy_check_links(const HyLds& L, const HydLinkArgs
   return flag[0] != 0;
 }
 
-// A pump's speed of the scenario or step: w^2 and w^(2-n), formed once.  Bad speeds set *bad.
-__device__ __forceinline__ void hy_set_speed(double* rec, double w, int* bad) {
-  const double w2 = w * w, w2n = w > 0.0 ? pow(w, 2.0 - rec[2]) : 0.0;
-  if (!(w >= 0.0) || !hy_finite(w) || !hy_finite(w2) || !hy_finite(w2n)) *bad = 1;
-  rec[3] = w2;                                             // (a bad speed leaves NaN or its like here; the scenario fails before
-  rec[4] = w2n;                                            //  the law reads the record, and the next scenario or step rewrites
-  rec[5] = w;                                              //  all three: nothing of a failed scenario is carried over)
-}
-
-// A link's code of the scenario or step: HY_SHUT where the static flag, the scenario's byte or a pump speed of zero shuts it.
-__device__ __forceinline__ int hy_link_code(const HyLds& L, int p, const uint8_t* closed, int* bad) {
-  int code = L.code[p] & ~HY_SHUT;
-  const int cl = closed ? closed[p] : 0;
-  if (cl > 1) *bad = 1;
-  if ((code & HY_CLOSED) || cl == 1 || ((code & HY_PUMP) && L.pump[(size_t)(code >> HY_PUMP_SHIFT) * HY_PUMP_REC + 5] == 0.0))
-    code |= HY_SHUT;
-  return code;
-}
-
-// link_state of gatres.h at the returned flow
-__device__ __forceinline__ uint8_t hy_link_state(int code, double q) {
-  return (code & HY_SHUT) ? 2 : ((code & HY_CHECK) && q < 0.0 ? 1 : 0);
-}
-
 __global__ __launch_bounds__(HY_T) void hydraulic_solve_links_kernel(const HydLinksArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hy_smem[];
   const int N = A.N, P = A.P, W = A.W, Kp = A.K.Kp, BW = W + 1, tid = threadIdx.x;
@@ -432,26 +408,6 @@ __global__ __launch_bounds__(HY_T) void hydraulic_series_links_kernel(const HydS
     }
     __syncthreads();                                       // (the next series writes the shared arrays again)
   }
-}
-
-static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
-// Does one of the written ranges overlap a read range or another written range?
-static bool any_overlap(const void* const* wr, const uint64_t* wn, int nw, const void* const* rd, const uint64_t* rn, int nr) {
-  for (int i = 0; i < nw; ++i) {
-    for (int j = 0; j < nr; ++j)
-      if (bytes_overlap(wr[i], wn[i], rd[j], rn[j])) return true;
-    for (int j = i + 1; j < nw; ++j)
-      if (bytes_overlap(wr[i], wn[i], wr[j], wn[j])) return true;
-  }
-  return false;
-}
-
-static inline bool hy_counts_ok(int64_t S, int32_t N, int32_t P) {
-  return S >= 1 && N >= 1 && P >= 1 && S <= INT64_MAX / 64 / ((int64_t)N + (int64_t)P);    // (every byte count below fits)
 }
 
 // the link arguments both entry points share; num_pipes is known to be >= 1

@@ -366,26 +366,6 @@ __global__ __launch_bounds__(HV_LANES) void hydraulic_valid_kernel(const float* 
   }
 }
 
-static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
-// Does one of the written ranges overlap a read range or another written range?
-static bool any_overlap(const void* const* wr, const uint64_t* wn, int nw, const void* const* rd, const uint64_t* rn, int nr) {
-  for (int i = 0; i < nw; ++i) {
-    for (int j = 0; j < nr; ++j)
-      if (bytes_overlap(wr[i], wn[i], rd[j], rn[j])) return true;
-    for (int j = i + 1; j < nw; ++j)
-      if (bytes_overlap(wr[i], wn[i], wr[j], wn[j])) return true;
-  }
-  return false;
-}
-
-static inline bool hy_counts_ok(int64_t S, int32_t N, int32_t P) {
-  return S >= 1 && N >= 1 && P >= 1 && S <= INT64_MAX / 64 / ((int64_t)N + (int64_t)P);    // (every byte count below fits)
-}
-
 }  // namespace
 
 extern "C" int gatres_hydraulic_draw(const double* d_lo, const double* d_hi, const double* c_lo, const double* c_hi,

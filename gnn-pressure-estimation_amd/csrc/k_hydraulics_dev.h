@@ -1,8 +1,9 @@
 // The hydraulic Newton loop, stated once for the two kernels of k_hydraulics.hip (hydraulic_solve_kernel: one steady scenario per
 // workgroup; hydraulic_series_kernel: one series of steps per workgroup) and their two counterparts with pumps, check valves,
-// closed links and minor losses in k_hydraulic_links.hip; and, at the end, with the status machine of the regulating valves for the
-// two kernels of k_hydraulic_valves.hip and, by compile-time arguments of that loop, with the node term of the emitters for the two
-// kernels of k_hydraulic_emitters.hip and with the node term of the pressure-driven demand for those of k_hydraulic_pdd.hip.
+// closed links and minor losses in k_hydraulic_links.hip; and, at the end, with the status machine of the regulating valves and,
+// by compile-time arguments of that loop, with the node terms of the emitters and of the pressure-driven demand, for the two
+// kernel templates of k_hydraulic_network.hip (one instantiation per level: valves, emitters, pressure-driven demand).  Behind the
+// loops stand the helpers the link and network kernels share, and the host checks of every hydraulic entry point.
 // gatres.h states the model, the law at low flow, the link law, the valves, the emitters, the pressure-driven demand and the solver.  Everything here works on one workgroup's LDS arrays; every sum runs in a fixed order.
 #pragma once
 #include "gatres_common.h"
@@ -248,7 +249,7 @@ __device__ __forceinline__ HyNewton hy_newton(const HyLds& L, const int* __restr
   return out;
 }
 
-// ---- THE REGULATING VALVES of gatres.h (k_hydraulic_valves.hip) -------------------------------------------------------------------
+// ---- THE REGULATING VALVES of gatres.h (k_hydraulic_network.hip) -------------------------------------------------------------------
 // A regulating valve's link keeps, above the bits of the link law, what it is and where its status machine stands; a valve is
 // never a pump, so the bits of a pump's index are free.  OPEN is neither status bit.  fx[row] of a valve's controlled node is
 // HY_FX_VALVE while the valve is ACTIVE and 0 otherwise; a fixed-head node has 1 and is never a controlled node.
@@ -296,7 +297,7 @@ struct HyNewtonValves {
   int changes;                                             // status changes over all iterations
 };
 
-// ---- THE EMITTERS of gatres.h (k_hydraulic_emitters.hip) ----------------------------------------------------------------------------
+// ---- THE EMITTERS of gatres.h (k_hydraulic_network.hip) ----------------------------------------------------------------------------
 // An emitter is a virtual link from its junction to the fixed head z = elevation, with a flow of its own, positive out of the
 // network.  ce < 0 marks an emitter that is off in this scenario or step (C == 0): its row gets nothing and its flow is +0.0.
 struct HyEmitters {
@@ -331,7 +332,7 @@ __device__ __forceinline__ void emitter_headloss(double q, double ce, double n, 
   *g = gg;
 }
 
-// ---- THE PRESSURE-DRIVEN DEMAND of gatres.h (k_hydraulic_pdd.hip) ----------------------------------------------------------------
+// ---- THE PRESSURE-DRIVEN DEMAND of gatres.h (k_hydraulic_network.hip) ----------------------------------------------------------------
 // A junction whose full demand D is positive is a virtual link from the junction to the fixed head z = elevation + Pmin, with a
 // flow q_d of its own, positive out of the network.  The record is indexed by NODE: there are up to N of these, and no thread
 // walks a list.  dd[n] == 0 marks a node that is not pressure-driven (a fixed-head node, a junction with D <= 0): it keeps the
@@ -609,6 +610,50 @@ __device__ __forceinline__ HyNewtonValves hy_newton_valves(const HyLds& L, const
     if (out.n.converged) break;
   }
   return out;
+}
+
+// ---- what the link, valve, emitter and demand kernels share around the loop (k_hydraulic_links.hip, k_hydraulic_network.hip) --------
+// A pump's speed of the scenario or step: w^2 and w^(2-n), formed once.  Bad speeds set *bad.
+__device__ __forceinline__ void hy_set_speed(double* rec, double w, int* bad) {
+  const double w2 = w * w, w2n = w > 0.0 ? pow(w, 2.0 - rec[2]) : 0.0;
+  if (!(w >= 0.0) || !hy_finite(w) || !hy_finite(w2) || !hy_finite(w2n)) *bad = 1;
+  rec[3] = w2;                                             // (a bad speed fails the scenario before the law reads the record, and
+  rec[4] = w2n;                                            //  the next scenario or step rewrites all three)
+  rec[5] = w;
+}
+
+// A link's code of the scenario or step: HY_SHUT where the static flag, the scenario's byte or a pump speed of zero shuts it.  A
+// valve's bits stay.
+__device__ __forceinline__ int hy_link_code(const HyLds& L, int p, const uint8_t* closed, int* bad) {
+  int code = L.code[p] & ~HY_SHUT;
+  const int cl = closed ? closed[p] : 0;
+  if (cl > 1) *bad = 1;
+  if ((code & HY_CLOSED) || cl == 1 || ((code & HY_PUMP) && L.pump[(size_t)(code >> HY_PUMP_SHIFT) * HY_PUMP_REC + 5] == 0.0))
+    code |= HY_SHUT;
+  return code;
+}
+
+// link_state of gatres.h at the returned flow and status (a code of the links kernels never carries HY_VALVE)
+__device__ __forceinline__ uint8_t hy_link_state(int code, double q) {
+  if (code & HY_SHUT) return 2;
+  if (code & HY_VALVE) return (uint8_t)hy_valve_status(code);
+  return (code & HY_CHECK) && q < 0.0 ? 1 : 0;
+}
+
+// ---- the host checks every hydraulic entry point makes --------------------------------------------------------------------------------
+// Does one of the written ranges overlap a read range or another written range?  (A null pointer is no range.)
+static bool any_overlap(const void* const* wr, const uint64_t* wn, int nw, const void* const* rd, const uint64_t* rn, int nr) {
+  for (int i = 0; i < nw; ++i) {
+    for (int j = 0; j < nr; ++j)
+      if (bytes_overlap(wr[i], wn[i], rd[j], rn[j])) return true;
+    for (int j = i + 1; j < nw; ++j)
+      if (bytes_overlap(wr[i], wn[i], wr[j], wn[j])) return true;
+  }
+  return false;
+}
+
+static inline bool hy_counts_ok(int64_t S, int32_t N, int32_t P) {
+  return S >= 1 && N >= 1 && P >= 1 && S <= INT64_MAX / 64 / ((int64_t)N + (int64_t)P);    // (every byte count of a launch fits)
 }
 
 }  // namespace

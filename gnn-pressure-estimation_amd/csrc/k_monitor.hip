@@ -288,11 +288,6 @@ __global__ __launch_bounds__(ML_T) void monitor_latch_kernel(const long long* __
   }
 }
 
-static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
 }  // namespace
 
 extern "C" int gatres_cusum_scan(const float* resid, const float* mu, const float* inv_sigma, const uint8_t* available,

@@ -97,11 +97,6 @@ __global__ __launch_bounds__(SR_T) void screen_reject_kernel(const float* __rest
   }
 }
 
-static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
 }  // namespace
 
 extern "C" int gatres_loo_residuals(const float* out, const uint8_t* mask, const float* src, int32_t layout, int64_t src_rows,

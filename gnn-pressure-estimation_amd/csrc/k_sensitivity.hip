@@ -93,11 +93,6 @@ __global__ __launch_bounds__(SS_T) void sensitivity_spread_kernel(const float* _
   out[r] = (float)sqrt(sum);
 }
 
-static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
 }  // namespace
 
 extern "C" int gatres_sensitivity_gather(const float* g_x, const uint8_t* mask, const float* fault, int32_t nodes_per_graph,

@@ -255,11 +255,6 @@ bool stage_args_ok(const int32_t* node_ptr, const uint8_t* mask, int32_t num_gra
 
 static_assert(sizeof(long long) == sizeof(int64_t), "row indices");
 
-static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
 }  // namespace
 
 extern "C" int gatres_mask_generate(const int32_t* node_ptr, int32_t num_graphs, double mask_rate, uint64_t seed,

@@ -36,7 +36,7 @@ causes it is not converged and is dropped by ``valid``, never repaired.  PRV and
 VALVES below; PBV, FCV and GPV valves, power-rated pumps, controls and rules stay out of scope.  Parity with EPANET is not
 claimed and has not been checked.
 
-THE REGULATING VALVES (gatres.h: THE REGULATING VALVES; csrc/k_hydraulic_valves.hip; ``_NewtonRef.run_valves``).  A network built
+THE REGULATING VALVES (gatres.h: THE REGULATING VALVES; csrc/k_hydraulic_network.hip; ``_NewtonRef.run_valves``).  A network built
 with ``valve_links`` takes the two valves launches: the links launches with a status machine for pressure-reducing (PRV) and
 pressure-sustaining (PSV) valves.  A regulating valve is a link from a to b without pipe resistance (r = 0; its length and its
 roughness are not read, as for a pump) and with the minor-loss term m of any link (K = 0 is allowed).  It has a kind and a
@@ -76,7 +76,7 @@ never repaired.  An OPEN valve with K = 0 sits on the linear branch, where its f
 (WHAT DOES NOT HOLD, below) and the stop rule is met by chance: give a valve a loss coefficient where that matters
 (``make_hydraulic_network`` does).  Parity with EPANET is not claimed.  FCV, PBV and GPV valves stay out of scope.
 
-THE EMITTERS (gatres.h: THE EMITTERS; csrc/k_hydraulic_emitters.hip; ``emitter_headloss``, ``_NewtonRef.run_valves(emit=)``).  A
+THE EMITTERS (gatres.h: THE EMITTERS; csrc/k_hydraulic_network.hip; ``emitter_headloss``, ``_NewtonRef.run_valves(emit=)``).  A
 network built with ``emitter_nodes`` takes the two emitters launches: the valves launches with a node term for pressure-dependent
 outflow, EPANET's emitter q = C p^gamma -- a leak.  An emitter sits on a junction i; its coefficient C >= 0 (m3/s per m^gamma)
 belongs to the scenario (``simulate(emitter_coefficient=)``), the exponent gamma to the network, as in EPANET.  It is a virtual
@@ -96,7 +96,7 @@ A coefficient that is negative or not finite fails its scenario (a series: from 
 HOLD: an emitter on a valve's controlled node is refused, not modelled (an ACTIVE valve closes that node's mass balance over the
 links alone, and that rule stays as it stands).  Parity with EPANET is not claimed.
 
-THE PRESSURE-DRIVEN DEMAND (gatres.h: THE PRESSURE-DRIVEN DEMAND; csrc/k_hydraulic_pdd.hip; ``demand_headloss``,
+THE PRESSURE-DRIVEN DEMAND (gatres.h: THE PRESSURE-DRIVEN DEMAND; csrc/k_hydraulic_network.hip; ``demand_headloss``,
 ``_NewtonRef.run_valves(pdd=)``).  ``simulate(demand_model="pda", minimum_pressure=, required_pressure=, pressure_exponent=)``
 takes the two pdd launches: the emitters launches with EPANET 2.2's PDA as a node term at every junction that draws.  With
 dp = Preq - Pmin and n = 1 / exponent, a junction i whose full demand D (in a series: demand x the step's multiplier) is positive
@@ -1177,6 +1177,11 @@ class HydraulicNetwork:
         flow = torch.empty((S, P), dtype=torch.float64, device=dev) if want_flow else None
         status = torch.empty((S, HYD_STATUS), dtype=torch.int32, device=dev)
         final_dq = torch.empty((S,), dtype=torch.float64, device=dev)
+        # the 23 arguments every steady entry point begins with
+        prefix = (st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
+                  st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
+                  self.half_bandwidth, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P, float(accuracy),
+                  int(max_iter), pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), status.data_ptr(), final_dq.data_ptr())
         if with_valves:
             link_args, link_state, _held = self._link_args(S, (S, P), pump_speed, link_closed)
             valve_args, changes, _held_v = self._valve_args(S, (S,), valve_setting)
@@ -1188,57 +1193,28 @@ class HydraulicNetwork:
                         raise ValueError(f"the band of {N} rows with half-bandwidth {self.half_bandwidth} needs {need} bytes of LDS "
                                          f"with this demand model, the kernel has {LDS_BUDGET}")
                     delivered = torch.empty((S, N), dtype=torch.float64, device=dev)
-                    rc = lib.gatres_hydraulic_solve_pdd(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
-                                                        st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
-                                                        st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
-                                                        demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P,
-                                                        float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head),
-                                                        _native.ptr(flow), status.data_ptr(), final_dq.data_ptr(), *link_args,
-                                                        link_state.data_ptr(), *valve_args, changes.data_ptr(), *emitter_args,
-                                                        *pdd, delivered.data_ptr(), _native.current_stream(dev))
+                    rc = lib.gatres_hydraulic_solve_pdd(*prefix, *link_args, link_state.data_ptr(), *valve_args, changes.data_ptr(),
+                                                        *emitter_args, *pdd, delivered.data_ptr(), _native.current_stream(dev))
                     _native.check(rc, "gatres_hydraulic_solve_pdd")
                     return HydraulicPddResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status,
                                               final_dq, link_state, changes, emitter_flow, delivered)
-                rc = lib.gatres_hydraulic_solve_emitters(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
-                                                         st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
-                                                         st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
-                                                         demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P,
-                                                         float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head),
-                                                         _native.ptr(flow), status.data_ptr(), final_dq.data_ptr(), *link_args,
-                                                         link_state.data_ptr(), *valve_args, changes.data_ptr(), *emitter_args,
-                                                         _native.current_stream(dev))
+                rc = lib.gatres_hydraulic_solve_emitters(*prefix, *link_args, link_state.data_ptr(), *valve_args, changes.data_ptr(),
+                                                         *emitter_args, _native.current_stream(dev))
                 _native.check(rc, "gatres_hydraulic_solve_emitters")
                 return HydraulicEmittersResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status,
                                                final_dq, link_state, changes, emitter_flow)
-            rc = lib.gatres_hydraulic_solve_valves(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
-                                                   st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
-                                                   st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
-                                                   demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P,
-                                                   float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head),
-                                                   _native.ptr(flow), status.data_ptr(), final_dq.data_ptr(), *link_args,
-                                                   link_state.data_ptr(), *valve_args, changes.data_ptr(),
+            rc = lib.gatres_hydraulic_solve_valves(*prefix, *link_args, link_state.data_ptr(), *valve_args, changes.data_ptr(),
                                                    _native.current_stream(dev))
             _native.check(rc, "gatres_hydraulic_solve_valves")
             return HydraulicValvesResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status, final_dq,
                                          link_state, changes)
         if with_links:
             link_args, link_state, _held = self._link_args(S, (S, P), pump_speed, link_closed)
-            rc = lib.gatres_hydraulic_solve_links(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
-                                                  st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
-                                                  st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
-                                                  demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P,
-                                                  float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head),
-                                                  _native.ptr(flow), status.data_ptr(), final_dq.data_ptr(), *link_args,
-                                                  link_state.data_ptr(), _native.current_stream(dev))
+            rc = lib.gatres_hydraulic_solve_links(*prefix, *link_args, link_state.data_ptr(), _native.current_stream(dev))
             _native.check(rc, "gatres_hydraulic_solve_links")
             return HydraulicLinksResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status, final_dq,
                                         link_state)
-        rc = lib.gatres_hydraulic_solve(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
-                                        st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
-                                        st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth, demand.data_ptr(),
-                                        roughness.data_ptr(), fh.data_ptr(), stride, S, N, P, float(accuracy), int(max_iter),
-                                        pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), status.data_ptr(),
-                                        final_dq.data_ptr(), _native.current_stream(dev))
+        rc = lib.gatres_hydraulic_solve(*prefix, _native.current_stream(dev))
         _native.check(rc, "gatres_hydraulic_solve")
         return HydraulicResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status, final_dq)
 
@@ -1356,6 +1332,13 @@ class HydraulicNetwork:
         status = torch.empty((S, T, HYD_STATUS), dtype=torch.int32, device=dev)
         final_dq = torch.empty((S, T), dtype=torch.float64, device=dev)
         tp = (lambda t: t.data_ptr()) if K else (lambda t: None)
+        # the 37 arguments every series entry point begins with
+        prefix = (st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
+                  st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
+                  self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
+                  pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride,
+                  tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0, float(accuracy), int(max_iter),
+                  pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(level), status.data_ptr(), final_dq.data_ptr())
         if with_links:
             Kp = self.num_pumps
             link_args, link_state, _held = self._link_args(S, (S, T, P), pump_speed, link_closed)
@@ -1367,6 +1350,7 @@ class HydraulicNetwork:
             if spat.shape != (Kp,) or (Kp and (spat.min() < 0 or spat.max() >= smult.shape[0])):
                 raise ValueError(f"speed_pattern_of_pump must be [{Kp}] with values in [0, {int(smult.shape[0])})")
             spat = torch.from_numpy(spat.astype(np.int32)).to(dev)
+            speed_args = (smult.data_ptr(), spat.data_ptr(), int(smult.shape[0])) if Kp else (None, None, 0)
             if with_valves:
                 need = series_pdd_lds_bytes(N, P, self.half_bandwidth, K, Kp, self.num_valves, self.num_emitters,
                                             0 if pdd is None else pdd[0])
@@ -1379,67 +1363,31 @@ class HydraulicNetwork:
                     if pdd is not None:
                         delivered = torch.empty((S, T, N), dtype=torch.float64, device=dev)
                         rc = lib.gatres_hydraulic_series_pdd(
-                            st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
-                            st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
-                            self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
-                            pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(),
-                            fh.data_ptr(), stride, tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0,
-                            float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(level),
-                            status.data_ptr(), final_dq.data_ptr(), *link_args, smult.data_ptr() if Kp else None,
-                            spat.data_ptr() if Kp else None, int(smult.shape[0]) if Kp else 0, link_state.data_ptr(), *valve_args,
+                            *prefix, *link_args, *speed_args, link_state.data_ptr(), *valve_args,
                             changes.data_ptr(), *emitter_args, *pdd, delivered.data_ptr(), _native.current_stream(dev))
                         _native.check(rc, "gatres_hydraulic_series_pdd")
                         return HydraulicSeriesPddResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
                                                         status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq, link_state,
                                                         changes, emitter_flow, delivered)
                     rc = lib.gatres_hydraulic_series_emitters(
-                        st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
-                        st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
-                        self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
-                        pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(),
-                        fh.data_ptr(), stride, tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0,
-                        float(accuracy), int(max_iter), pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(level),
-                        status.data_ptr(), final_dq.data_ptr(), *link_args, smult.data_ptr() if Kp else None,
-                        spat.data_ptr() if Kp else None, int(smult.shape[0]) if Kp else 0, link_state.data_ptr(), *valve_args,
+                        *prefix, *link_args, *speed_args, link_state.data_ptr(), *valve_args,
                         changes.data_ptr(), *emitter_args, _native.current_stream(dev))
                     _native.check(rc, "gatres_hydraulic_series_emitters")
                     return HydraulicSeriesEmittersResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
                                                          status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq, link_state,
                                                          changes, emitter_flow)
                 rc = lib.gatres_hydraulic_series_valves(
-                    st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
-                    st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
-                    self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
-                    pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(),
-                    stride, tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0, float(accuracy), int(max_iter),
-                    pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(level), status.data_ptr(), final_dq.data_ptr(),
-                    *link_args, smult.data_ptr() if Kp else None, spat.data_ptr() if Kp else None,
-                    int(smult.shape[0]) if Kp else 0, link_state.data_ptr(), *valve_args, changes.data_ptr(),
+                    *prefix, *link_args, *speed_args, link_state.data_ptr(), *valve_args, changes.data_ptr(),
                     _native.current_stream(dev))
                 _native.check(rc, "gatres_hydraulic_series_valves")
                 return HydraulicSeriesValvesResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
                                                    status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq, link_state, changes)
             rc = lib.gatres_hydraulic_series_links(
-                st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
-                st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
-                self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
-                pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride,
-                tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0, float(accuracy), int(max_iter),
-                pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(level), status.data_ptr(), final_dq.data_ptr(),
-                *link_args, smult.data_ptr() if Kp else None, spat.data_ptr() if Kp else None, int(smult.shape[0]) if Kp else 0,
-                link_state.data_ptr(), _native.current_stream(dev))
+                *prefix, *link_args, *speed_args, link_state.data_ptr(), _native.current_stream(dev))
             _native.check(rc, "gatres_hydraulic_series_links")
             return HydraulicSeriesLinksResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0, status[:, :, 2] != 0,
                                               status[:, :, 3] != 0, status, final_dq, link_state)
-        rc = lib.gatres_hydraulic_series(st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(),
-                                         st["q_start"].data_ptr(), st["fixed"].data_ptr(), st["elevation"].data_ptr(),
-                                         st["order"].data_ptr(), st["position"].data_ptr(), self.half_bandwidth,
-                                         tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
-                                         pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(),
-                                         roughness.data_ptr(), fh.data_ptr(), stride, tp(level0), S, T, N, P, float(step_seconds),
-                                         1 if warm_start else 0, float(accuracy), int(max_iter), pressure.data_ptr(),
-                                         _native.ptr(head), _native.ptr(flow), tp(level), status.data_ptr(), final_dq.data_ptr(),
-                                         _native.current_stream(dev))
+        rc = lib.gatres_hydraulic_series(*prefix, _native.current_stream(dev))
         _native.check(rc, "gatres_hydraulic_series")
         return HydraulicSeriesResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0, status[:, :, 2] != 0,
                                      status[:, :, 3] != 0, status, final_dq)

@@ -1543,7 +1543,7 @@ int gatres_hydraulic_series_links(const int32_t* pipe_a, const int32_t* pipe_b, 
                                   int32_t num_speed_patterns, uint8_t* link_state, void* stream);
 
 /* THE REGULATING VALVES: pressure-reducing (PRV) and pressure-sustaining (PSV) valves, with a status machine (symbols only: the
- * ABI stays; k_hydraulic_valves.hip, hydraulics.py).  The two launches below are gatres_hydraulic_solve_links and
+ * ABI stays; k_hydraulic_network.hip, hydraulics.py).  The two launches below are gatres_hydraulic_solve_links and
  * gatres_hydraulic_series_links with link_kind values GATRES_HYD_PRV and GATRES_HYD_PSV allowed; the links launches refuse them as
  * they always did.  A regulating valve is a link from a to b without pipe resistance (r = 0: its coef and roughness are not read,
  * as for a pump) and with the minor-loss term m = minor[p] of any link (m = 0 is allowed).  It has a setting s, a pressure in
@@ -1627,7 +1627,7 @@ int gatres_hydraulic_series_valves(const int32_t* pipe_a, const int32_t* pipe_b,
                                    int32_t num_valves, int32_t* valve_changes, void* stream);
 
 /* THE EMITTERS: pressure-dependent outflow at junctions, EPANET's emitter q = C p^gamma -- a leak (symbols only: the ABI stays;
- * k_hydraulic_emitters.hip, hydraulics.py).  The two launches below are gatres_hydraulic_solve_valves and
+ * k_hydraulic_network.hip, hydraulics.py).  The two launches below are gatres_hydraulic_solve_valves and
  * gatres_hydraulic_series_valves with a node term for Ke emitters.  Emitter k sits on junction i = emitter_node[k].  It has a
  * coefficient C >= 0 (m3/s per m^gamma) per scenario and emitter, and the launch has one exponent gamma.  It is a virtual link
  * from i to the fixed head z_i = elevation[i] with a flow q_e of its own, positive out of the network.  With n = 1 / gamma and
@@ -1699,7 +1699,7 @@ int gatres_hydraulic_series_emitters(const int32_t* pipe_a, const int32_t* pipe_
                                      double emitter_exponent, const int32_t* emitter_onset, int64_t emitter_onset_stride,
                                      double* emitter_flow, void* stream);
 
-/* THE PRESSURE-DRIVEN DEMAND: EPANET 2.2's DEMAND MODEL PDA (symbols only: the ABI stays; k_hydraulic_pdd.hip, hydraulics.py).
+/* THE PRESSURE-DRIVEN DEMAND: EPANET 2.2's DEMAND MODEL PDA (symbols only: the ABI stays; k_hydraulic_network.hip, hydraulics.py).
  * The two launches below are gatres_hydraulic_solve_emitters and gatres_hydraulic_series_emitters with a node term for the
  * demand.  A launch has demand_model (0 demand-driven, 1 pressure-driven) and three scalars: minimum_pressure Pmin and
  * required_pressure Preq in metres, pressure_exponent e (EPANET's default 0.5).  dp = Preq - Pmin, n = 1 / e.

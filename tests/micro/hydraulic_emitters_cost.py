@@ -1,4 +1,4 @@
-"""Cost of the emitters launches (csrc/k_hydraulic_emitters.hip), one JSON line per mode.  Not collected by pytest.
+"""Cost of the emitters launches (csrc/k_hydraulic_network.hip, LV 1), one JSON line per mode.  Not collected by pytest.
 
     python tests/micro/hydraulic_emitters_cost.py [--scenarios 2048] [--steps 24] [--repeats 5] [--emitters 8] [--valves-only]
 

@@ -1,4 +1,4 @@
-"""Cost of the pressure-driven demand launches (csrc/k_hydraulic_pdd.hip), one JSON line per mode.  Not collected by pytest.
+"""Cost of the pressure-driven demand launches (csrc/k_hydraulic_network.hip, LV 2), one JSON line per mode.  Not collected by pytest.
 
     python tests/micro/hydraulic_pdd_cost.py [--scenarios 2048] [--steps 24] [--repeats 5] [--required 20] [--emitters-only]
 

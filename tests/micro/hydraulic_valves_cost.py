@@ -1,4 +1,4 @@
-"""Cost of the valves launches (csrc/k_hydraulic_valves.hip), one JSON line per mode.  Not collected by pytest.
+"""Cost of the valves launches (csrc/k_hydraulic_network.hip, LV 0), one JSON line per mode.  Not collected by pytest.
 
     python tests/micro/hydraulic_valves_cost.py [--scenarios 1024] [--steps 24] [--repeats 5]
 

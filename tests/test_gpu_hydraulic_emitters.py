@@ -1,4 +1,4 @@
-"""Pressure-dependent emitters (leaks) on the device (k_hydraulic_emitters.hip) against their host statements (hydraulics.py): the
+"""Pressure-dependent emitters (leaks) on the device (k_hydraulic_network.hip, LV 1) against their host statements (hydraulics.py): the
 closed forms and bisection roots of hydraulic_emitters_refs.py and a shut emitter; residuals, agreement with ``solve_ref`` and
 EQUAL iterations where the reference is decisive, on networks with one to three emitters beside regulating valves; with no
 emitter, or with every coefficient 0, every bit of the valves launches; the capped grid; the series -- cold steps against the

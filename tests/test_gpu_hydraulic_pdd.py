@@ -1,4 +1,4 @@
-"""Pressure-driven demand on the device (k_hydraulic_pdd.hip) against its host statements (hydraulics.py): the closed forms and
+"""Pressure-driven demand on the device (k_hydraulic_network.hip, LV 2) against its host statements (hydraulics.py): the closed forms and
 shooting roots of hydraulic_pdd_refs.py, a junction above the required and one below the minimum pressure; residuals, agreement
 with ``solve_ref`` and EQUAL iterations, statuses and valve changes on three networks (N < 64; a PRV whose controlled node is
 pressure-driven beside an emitter; N > 256); with ``demand_model="dda"`` every bit of the emitters launches; the capped grid; the

@@ -1,4 +1,4 @@
-"""Pressure-reducing and pressure-sustaining valves on the device (k_hydraulic_valves.hip) against their host statements
+"""Pressure-reducing and pressure-sustaining valves on the device (k_hydraulic_network.hip, LV 0) against their host statements
 (hydraulics.py): the closed forms of hydraulic_valves_refs.py; residuals, agreement with ``solve_ref`` and EQUAL iterations,
 ``link_state`` and ``valve_changes`` on networks with one to three valves (the references are decisive, see
 hydraulic_valves_refs.py); the capped grid; with no valve the two valves launches give every bit of the links launches; a series
