@@ -130,6 +130,12 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
   // mout and tout at conv1's width (24).  tout at conv2's width does not fit beside them without scratch and stays in LDS,
   // as every descriptor does in every other instantiation (profiles/window_descriptor_hoist.txt).
   constexpr bool HOIST = NC == 32 && THREADS == 1024 && NOHUB && PTAB && OW64;
+  // The same instantiations hold each lane's slot of the forward's three hand-off sweeps (F1, F2, F3) in registers, two per
+  // sweep (k_window_stages.h: xch_slot, xch_import2_reg): a sweep opens with its poll.  The backward's sweeps keep the generic
+  // form: B1 and B3 start as waves arrive and B2 runs on idle waves, and their slots made the training launch slower
+  // (profiles/window_sweep_hoist.txt).  Not where the loss is another criterion than MSE (0x8000): beside that code the six slot
+  // registers put the training instantiations into scratch, so those keep the generic sweeps.
+  constexpr bool SWEEP = HOIST && !(PH & 0x8000);
   // PH & 0x2000 (forward-only launches): nobody reads the saved activations (GATRES_MODEL_INFERENCE) -- their stores, a
   // tenth of the forward's VMEM and VALU work, are not compiled
   constexpr bool NOSAVE = PH >= 0 && (PH & 0x2000) != 0 && (PH & 0xff) == GATRES_PHASE_FORWARD;
@@ -431,6 +437,17 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
       qn2 = win_hoist_in<NC / 4>(rw, nbin, fflag);
       qm2 = win_hoist_in<NC / 4>(rw, mbin, nullptr);
     }
+    [[maybe_unused]] XchSlot sF1, sF2, sF3;
+    if constexpr (SWEEP) {     // this lane's slot of the forward's three sweeps
+      FRESH_FWD();
+#define LIST_(T_, N_, I_) I_(lo) I_(hi) T_(const u16, hlist) I_(hcnt)
+      REC_LOADS(LIST_);
+      REC_DEFS(LIST_);
+#undef LIST_
+      sF1 = xch_slot<2 * NC, 2, THREADS>(hlist, hcnt, (unsigned)XL.f1h, hlist, hcnt, (unsigned)XL.f1a);
+      sF2 = xch_slot<NC, 1, THREADS>(hlist, hcnt, (unsigned)XL.f2h, hlist, hcnt, (unsigned)XL.f2a);
+      sF3 = xch_slot<NC, 0, THREADS>(hlist, hcnt, (unsigned)XL.f3, hlist, 0, 0u);
+    }
     const int nb = L.nb;
     for (int b = 0; b < nb; ++b) {
       // (per stage: FRESH_ARGS() / FRESH_FWD() re-read the offsets and tables the stage needs; base / pb are formed where
@@ -474,7 +491,11 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
 #undef LIST_
         ++xc.ep;                                    // exchange F1: the gathers below read h1 / a_src of neighbour rows
         if (!xreg) xch_export2<2 * NC, 2, THREADS>(xc, xbuf, elist, ecnt, hA, (unsigned)XL.f1h, elist, ecnt, sa2, (unsigned)XL.f1a);
-        xch_import2<2 * NC, 2, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f1h, hA, hlist, hcnt, (unsigned)XL.f1a, sa2);
+        if constexpr (SWEEP) {                     // trip 0 from the slots; a longer list's further trips as everywhere else
+          if (xch_import2_reg<2 * NC, 2>(xc, xbuf, sF1, hA, sa2))
+            xch_import2<2 * NC, 2, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f1h, hA, hlist, hcnt, (unsigned)XL.f1a, sa2, THREADS);
+        } else
+          xch_import2<2 * NC, 2, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f1h, hA, hlist, hcnt, (unsigned)XL.f1a, sa2);
         xch_after<THREADS>(xc, pace);
         lds_barrier();
         STAMP();
@@ -547,7 +568,11 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
 #undef LIST_
         ++xc.ep;                                    // exchange F2
         if (!xreg) xch_export2<NC, 1, THREADS>(xc, xbuf, elist, ecnt, hB, (unsigned)XL.f2h, elist, ecnt, sa1, (unsigned)XL.f2a);
-        xch_import2<NC, 1, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f2h, hB, hlist, hcnt, (unsigned)XL.f2a, sa1);
+        if constexpr (SWEEP) {                     // trip 0 from the slots; a longer list's further trips as everywhere else
+          if (xch_import2_reg<NC, 1>(xc, xbuf, sF2, hB, sa1))
+            xch_import2<NC, 1, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f2h, hB, hlist, hcnt, (unsigned)XL.f2a, sa1, THREADS);
+        } else
+          xch_import2<NC, 1, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f2h, hB, hlist, hcnt, (unsigned)XL.f2a, sa1);
         xch_after<THREADS>(xc, pace);
         lds_barrier();
         STAMP();
@@ -588,7 +613,11 @@ __global__ __launch_bounds__(THREADS) void gatres_window_kernel(const FusedArgs 
 #undef LIST_
         ++xc.ep;                                    // exchange F3: K3 averages y2 over neighbour rows
         if (!(xreg && oeg <= wr * NC)) xch_export2<NC, 0, THREADS>(xc, xbuf, elist, ecnt, y2T, (unsigned)XL.f3, elist, 0, y2T, 0u);
-        xch_import2<NC, 0, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f3, y2T, hlist, 0, 0u, y2T);
+        if constexpr (SWEEP) {                     // trip 0 from the slots; a longer list's further trips as everywhere else
+          if (xch_import2_reg<NC, 0>(xc, xbuf, sF3, y2T, y2T))
+            xch_import2<NC, 0, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f3, y2T, hlist, 0, 0u, y2T, THREADS);
+        } else
+          xch_import2<NC, 0, THREADS>(xc, xbuf, hlist, hcnt, (unsigned)XL.f3, y2T, hlist, 0, 0u, y2T);
         xch_after<THREADS>(xc, pace);
         lds_barrier();
         STAMP();

@@ -214,9 +214,10 @@ __device__ __forceinline__ void xch_export2(const Xch& x, const XchBuf& xb, cons
 }
 
 // granules of every listed row / edge of both tables -> the LDS tables, re-read until their tags carry this exchange's epoch
+// (base0: the first access of the first trip to run -- THREADS behind xch_import2_reg, which has run trip 0 from the slots)
 template <int W1, int W2, int THREADS>
 __device__ __forceinline__ void xch_import2(Xch& x, const XchBuf& xb, const u16* l1, int c1, unsigned t1, float* d1,
-                                            const u16* l2, int c2, unsigned t2, float* d2) {
+                                            const u16* l2, int c2, unsigned t2, float* d2, int base0 = 0) {
   constexpr int P1 = XchGeom<W1>::P, P2 = XchGeom<W2>::P, E1 = XchGeom<W1>::E, E2 = XchGeom<W2>::E;
   // ONE granule access per lane and trip: the hand-off lists of a part fit one trip of the workgroup's threads (C-Town, 8 parts:
   // 320 - 700 accesses), and a second, always-empty access per lane cost 13 us per step in index arithmetic and predication
@@ -224,7 +225,7 @@ __device__ __forceinline__ void xch_import2(Xch& x, const XchBuf& xb, const u16*
   constexpr int U = 1;
   const int tid = stage_tid();
   const int n1 = c1 * P1, total = n1 + c2 * P2;
-  for (int base = 0; base < total; base += U * THREADS) {
+  for (int base = base0; base < total; base += U * THREADS) {
     if (base + (tid & ~63) >= total) continue;                             // nothing left for this wave
     int o[U];
     bool valid[U], two[U], first[U];
@@ -311,6 +312,67 @@ __device__ __forceinline__ void xch_import2_by(Xch& x, unsigned ep, const XchBuf
         if (two[u]) d[o[u] + 1] = __uint_as_float(v[u].z);
       }
   }
+}
+
+// SWEEP SLOTS (the REG form of xch_import2).  A lane takes access k = tid of the part's import list in the first trip of
+// every sweep of a phase, and the list is topology: what the generic body derives from it for that trip -- valid, first,
+// the LDS index o and the granule's byte offset -- is formed ONCE per phase, behind the prologue's barrier (beside
+// win_hoist_in), with the generic body's own expressions, and handed to the sweep by value.  The sweep then opens with its
+// poll: no list count, no list entry, no table base and no count-dependent branch in front of it.  `two` follows from
+// `first` at compile time.  XS_MORE (the same in every lane) says that the list is longer than one trip; a wave whose first
+// lane is not valid has nothing in any trip (the generic body's `continue`).
+constexpr unsigned XS_VALID = 0x80000000u, XS_FIRST = 0x40000000u, XS_MORE = 0x20000000u, XS_O = 0x1fffffffu;
+struct XchSlot {
+  unsigned w = 0u;          // XS_VALID | XS_FIRST | XS_MORE | o
+  unsigned off = 0u;        // byte offset of the lane's granule pair in the exchange region
+};
+template <int W1, int W2, int THREADS>
+__device__ __forceinline__ XchSlot xch_slot(const u16* l1, int c1, unsigned t1, const u16* l2, int c2, unsigned t2) {
+  constexpr int P1 = XchGeom<W1>::P, P2 = XchGeom<W2>::P, E1 = XchGeom<W1>::E, E2 = XchGeom<W2>::E;
+  XchSlot s;
+  const int tid = stage_tid();
+  const int n1 = c1 * P1, total = n1 + c2 * P2;
+  if ((tid & ~63) >= total) return s;                                      // nothing for this wave
+  const int k = tid;
+  const bool valid = k < total, first = k < n1;
+  const int kk = first ? k : k - n1;
+  int o;
+  unsigned off;
+  if (!valid)     { o = 0; off = 0; }
+  else if (first) { o = (int)l1[kk / P1] * W1 + E1 * (kk % P1); off = (t1 + (unsigned)o) * 8u; }
+  else            { o = (int)l2[kk / (P2 ? P2 : 1)] * W2 + E2 * (kk % (P2 ? P2 : 1)); off = (t2 + (unsigned)o) * 8u; }
+  s.w = (valid ? XS_VALID : 0u) | (first ? XS_FIRST : 0u) | (total > THREADS ? XS_MORE : 0u) | (unsigned)o;
+  s.off = off;
+  return s;
+}
+// The first trip of xch_import2 from a slot; true (wave-uniform) when the list has further trips: the caller runs them
+// through the generic body (base0 = THREADS).  The slot is copied through an empty asm (as nbr_opaque): its unpacked fields
+// are formed here, not kept alive across the block loop.
+template <int W1, int W2>
+__device__ __forceinline__ bool xch_import2_reg(Xch& x, const XchBuf& xb, XchSlot s, float* d1, float* d2) {
+  constexpr int E1 = XchGeom<W1>::E, E2 = XchGeom<W2>::E;
+  asm volatile("" : "+v"(s.w), "+v"(s.off));
+  const unsigned head = (unsigned)__builtin_amdgcn_readfirstlane((int)s.w);
+  if (!(head & XS_VALID)) return false;                                    // nothing for this wave
+  const bool valid = (s.w & XS_VALID) != 0, first = (s.w & XS_FIRST) != 0;
+  const bool two = first ? E1 == 2 : E2 == 2;
+  const int o = (int)(s.w & XS_O);
+  v4u v;
+  int spin = 0;
+  for (;;) {
+    bool ok = true;
+    if (valid) v = __builtin_amdgcn_raw_buffer_load_b128(xb.r, s.off, 0, 16);
+    ok = ok && (!valid || (v.y == x.ep && (!two || v.w == x.ep)));
+    if (__all(ok || x.dead)) break;
+    __builtin_amdgcn_s_sleep(1);                 // (a failed poll: 64 cycles before the next one -- 0.8 us per step less L2 pressure)
+    if (++spin > SPIN_LIMIT) { *x.err = 1; x.dead = true; }
+  }
+  if (valid) {
+    float* d = first ? d1 : d2;
+    d[o] = __uint_as_float(v.x);
+    if (two) d[o + 1] = __uint_as_float(v.z);
+  }
+  return (head & XS_MORE) != 0;
 }
 
 // After a part's sweep.  pace: announce "exchange ep is behind me" and wait until every other part has announced exchange
