@@ -294,7 +294,7 @@ class _EvalPlan:
     def refresh(self, model) -> "_EvalPlan":
         """The forward's call state and buffers as the model holds them now (through its caches: no device work)."""
         self.state = model._call_state(self.plan)
-        self.saved = model._eval_saved_for(self.plan) if self.state["window"] else None
+        self.saved = model._eval_saved_for(self.plan, self.state["buf_key"]) if self.state["window"] else None
         return self
 
 

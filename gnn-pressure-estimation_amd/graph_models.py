@@ -180,6 +180,43 @@ class _GATResFunction(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------------------------
+# the key of the per-plan work buffers
+# ----------------------------------------------------------------------------------------------
+# positions in work_buffer_key()'s tuple
+KEY_PARTS, KEY_SCRATCH_FLOATS, KEY_SAVED_FLOATS = 5, 6, 7
+_PHASES_TRAIN = 2 | 4 | 16          # GATRES_PHASE_FORWARD | _BACKWARD | _LOSS
+
+
+def work_buffer_key(mref, plan: GraphPlan, num_cus: int = 0) -> tuple:
+    """Everything the size of a plan's work buffers and the state kept inside them depend on, as values (two ``GraphPlan``
+    objects of one topology get one key):
+
+      (num_nodes, num_edges_gat, num_segments, max_segment_nodes, max_segment_edges_gat, parts per segment,
+       scratch floats, saved floats, device)
+
+    The totals alone do not do: csrc/gatres_layout.h sizes the keep / flag / part-slab / granule-exchange regions of scratch
+    and the segment-major ``saved`` slots from the plan's LARGEST segment, so two plans of equal totals need buffers of different
+    sizes with every offset behind those regions elsewhere; and the parts per segment (``gatres_fused_plan``: the largest
+    segment's 16-row tiles, whether the window kernel fits its row windows) decide which flag lines of scratch keep counting
+    hand-off epochs -- a buffer handed from a plan of 7 parts to one of 8 leaves the eighth part an epoch behind for good.
+    ``mref``: the model struct; ``num_cus``: the CUs the split is decided for (0: the current device's)."""
+    import ctypes
+    lib = _native.load()
+    gref = plan.ref()
+    scratch = int(lib.gatres_scratch_floats(mref, gref))
+    if scratch < 0:
+        _native.check(scratch, "gatres_scratch_floats")
+    saved = int(lib.gatres_saved_floats(mref, gref))
+    if saved < 0:
+        _native.check(saved, "gatres_saved_floats")
+    words = (ctypes.c_int32 * 12)()          # (GATRES_FUSED_PLAN_WORDS; word 0 = GATRES_FUSED_PLAN_PARTS)
+    rc = lib.gatres_fused_plan(mref, gref, _PHASES_TRAIN, int(num_cus), words)
+    parts = int(words[0]) if rc == 0 else 0          # (0: no fused launch takes this plan -- nothing persists in scratch)
+    return (plan.num_nodes, plan.num_edges_gat, plan.num_segments, plan.max_segment_nodes, plan.max_segment_edges_gat, parts,
+            scratch, saved, str(plan.device))
+
+
+# ----------------------------------------------------------------------------------------------
 # the model
 # ----------------------------------------------------------------------------------------------
 class GATResMeanConv(_TrackedModule):
@@ -460,18 +497,25 @@ class GATResMeanConv(_TrackedModule):
             _native.check(int(n), "gatres_saved_floats")
         return int(n)
 
-    def _scratch_for(self, plan: GraphPlan) -> Tensor:
-        key = (plan.num_nodes, plan.num_edges_gat, plan.num_segments, str(plan.device))
+    def _cached_buffer(self, key: tuple, need: int, what: str) -> Optional[Tensor]:
+        """The LRU's buffer under ``key`` (now the most recently used), or None.  A hit smaller than ``need`` is refused: the
+        kernels take a raw pointer and trust this size."""
         buf = self._scratch.pop(key, None)
-        if buf is not None:
-            self._scratch[key] = buf          # most recently used last
+        if buf is None:
+            return None
+        if buf.numel() < need:
+            raise RuntimeError(f"cached {what} buffer holds {buf.numel()} floats, the plan needs {need}")
+        self._scratch[key] = buf          # most recently used last
+        return buf
+
+    def _scratch_for(self, plan: GraphPlan, key: Optional[tuple] = None) -> Tensor:
+        key = work_buffer_key(self._cmodel_ref(), plan) if key is None else key
+        n = key[KEY_SCRATCH_FLOATS]
+        buf = self._cached_buffer(key, n, "scratch")
         if buf is None:
             lib = _native.load()
-            n = lib.gatres_scratch_floats(self._cmodel_ref(), plan.ref())
-            if n < 0:
-                _native.check(int(n), "gatres_scratch_floats")
             # zeroed once: the split-segment barrier epochs of the fused kernel live in here (include/gatres.h)
-            buf = torch.zeros(int(n), dtype=torch.float32, device=plan.device)
+            buf = torch.zeros(n, dtype=torch.float32, device=plan.device)
             if buf.is_cuda:
                 # once per device (cached in the library): does the dispatch put workgroups 8 ids apart on one XCD?  Then the
                 # split launches start without their first cross-CU barrier (gatres_probe_xcd_dispatch)
@@ -487,11 +531,13 @@ class GATResMeanConv(_TrackedModule):
         while len(self._scratch) > bound:
             self._scratch.pop(next(iter(self._scratch)))
 
-    def _eval_saved_for(self, plan: GraphPlan) -> Tensor:
-        key = ("eval_saved", plan.num_nodes, plan.num_edges_gat, plan.num_segments, str(plan.device))
-        buf = self._scratch.get(key)
+    def _eval_saved_for(self, plan: GraphPlan, key: Optional[tuple] = None) -> Tensor:
+        key = work_buffer_key(self._cmodel_ref(), plan) if key is None else key
+        n = key[KEY_SAVED_FLOATS]
+        key = ("eval_saved",) + key
+        buf = self._cached_buffer(key, n, "eval saved")
         if buf is None:
-            buf = torch.empty(self._saved_floats(plan), dtype=torch.float32, device=plan.device)
+            buf = torch.empty(n, dtype=torch.float32, device=plan.device)
             self._remember(key, buf)
         return buf
 
@@ -508,14 +554,16 @@ class GATResMeanConv(_TrackedModule):
             # (inference calls pass a copy of the model struct flagged GATRES_MODEL_INFERENCE: the window kernel then takes the
             #  instantiation without the saved-activation stores)
             infer = _native.GatresModel(self.num_blocks, self.nc, int(self._cmodel.act_dtype), _native.MODEL_INFERENCE)
+            buf_key = work_buffer_key(self._cmodel_ref(), plan)
             st = {"plan": plan, "gref": plan.ref(self._cmodel_ref()), "mref": self._cmodel_ref(),
                   "infer": infer, "mref_infer": ctypes.byref(infer),
                   "window": bool(lib.gatres_fused_window_kernel(self._cmodel_ref(), plan.ref())),
-                  "saved_floats": self._saved_floats(plan)}
+                  "saved_floats": buf_key[KEY_SAVED_FLOATS], "buf_key": buf_key}
             if len(self._call_states) >= 8:
                 self._call_states.clear()
             self._call_states[key] = st
-        st["scratch"] = self._scratch_for(plan)      # (through the LRU every time: one scratch buffer per plan, whoever asks)
+        # (through the LRU every time: one scratch buffer per plan, whoever asks -- "per plan" being work_buffer_key)
+        st["scratch"] = self._scratch_for(plan, st["buf_key"])
         return st
 
     def plan_for(self, edge_index: Tensor, num_nodes: int) -> GraphPlan:
@@ -532,7 +580,7 @@ class GATResMeanConv(_TrackedModule):
         elif st["window"]:
             # inference: the window kernel (taken only with a `saved` buffer) is ~17 % faster than the whole-segment-table
             # kernel even though it writes activations nobody reads -- give it a cached throw-away buffer
-            saved = self._eval_saved_for(plan)
+            saved = self._eval_saved_for(plan, st["buf_key"])
         _native.check(lib.gatres_model_forward(st["mref"] if keep else st["mref_infer"], st["gref"], self._flat.data_ptr(), x.data_ptr(), None,
                                                out.data_ptr(), _native.ptr(saved), st["scratch"].data_ptr(),
                                                _native.current_stream(x.device)), "gatres_model_forward")
