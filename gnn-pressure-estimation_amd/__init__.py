@@ -21,7 +21,8 @@ from .hydraulics import (HydraulicLinksResult, HydraulicNetwork, HydraulicResult
                          simulate_series_ref, solve_ref, tree_solution, HydraulicValvesResult, HydraulicSeriesValvesResult,
                          valve_status_ref, hydraulic_valve_draws, HydraulicEmittersResult, HydraulicSeriesEmittersResult,
                          emitter_headloss, hydraulic_emitter_draws, HydraulicPddResult, HydraulicSeriesPddResult, demand_headloss,
-                         pdd_lds_bytes, series_pdd_lds_bytes)
+                         pdd_lds_bytes, series_pdd_lds_bytes, ControlTable, control_table, control_state,
+                         control_step_ref, series_controls_lds_bytes, HydraulicSeriesControlsResult)
 from .wdn_io import parse_inp_hydraulics
 from .sensitivity import (influence_from_table, linear_spread_ref, sensitivity_fold_ref, sensitivity_rows_from_gx,
                           sensitivity_seeds)
@@ -41,4 +42,5 @@ __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "Simpl
            "hydraulic_link_draws", "parse_inp_hydraulics", "HydraulicValvesResult", "HydraulicSeriesValvesResult", "valve_status_ref",
            "hydraulic_valve_draws", "HydraulicEmittersResult", "HydraulicSeriesEmittersResult", "emitter_headloss",
            "hydraulic_emitter_draws", "HydraulicPddResult", "HydraulicSeriesPddResult", "demand_headloss", "pdd_lds_bytes",
-           "series_pdd_lds_bytes"]
+           "series_pdd_lds_bytes", "ControlTable", "control_table", "control_state", "control_step_ref",
+           "series_controls_lds_bytes", "HydraulicSeriesControlsResult"]

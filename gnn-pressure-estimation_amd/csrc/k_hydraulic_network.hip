@@ -7,11 +7,14 @@
 //   LV 2  pdd        PDD: the node term of the demand at every junction that draws, the delivered flows carried along a warm series
 //                    while a junction stays pressure-driven.
 //   hydraulic_solve_network_kernel<LV>    one workgroup per scenario   gatres_hydraulic_solve_{valves,emitters,pdd}
-//   hydraulic_series_network_kernel<LV>   one workgroup per series     gatres_hydraulic_series_{valves,emitters,pdd}
+//   hydraulic_series_network_kernel<LV, CTL>  one workgroup per series  gatres_hydraulic_series_{valves,emitters,pdd} (CTL false)
+//                    CTL: THE CONTROLS of gatres.h, a pass at the start of every step; gatres_hydraulic_series_controls, LV 1 and 2
 // The pdd entry points with demand_model 0 launch LV 1.  With no valve LV 0 gives every bit of the links launches
 // (k_hydraulic_links.hip), with no emitter LV 1 every bit of LV 0.  Every loop is bounded, every sum runs in a fixed order, nothing
 // is shared between scenarios.  No atomics.
 #include "k_hydraulics_dev.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -55,6 +58,19 @@ struct HydEmitterArgs {
 struct HydPddArgs {
   double pmin, preq, exponent;
   double* delivered;                                       // [S][N] (series [S][T][N]); NULL at LV 0, may be NULL at LV 1
+};
+
+// the control table of a series launch with THE CONTROLS (gatres.h); all zero in every other launch
+struct HydControlArgs {
+  const int* link;
+  const uint8_t* action;
+  const double* value;
+  const uint8_t* kind;
+  const int* target;
+  const double* threshold;
+  long long threshold_stride;
+  int Kc;
+  int* changes;                                            // [S][T]
 };
 
 struct HydNetSolveArgs {
@@ -102,7 +118,12 @@ struct HydNetSeriesArgs {
   HydPddArgs D;
 };
 
-constexpr uint64_t HY_EMITTER_LDS = 48;                    // per emitter: ce, z, q, 1 / g, h / g, its row and its node
+// the arguments of the series kernels with THE CONTROLS: the table comes behind everything the other instantiations take
+struct HydNetSeriesCtlArgs : HydNetSeriesArgs {
+  HydControlArgs C;
+};
+
+constexpr uint64_t HY_EMITTER_LDS = 48;                   // per emitter: ce, z, q, 1 / g, h / g, its row and its node
 constexpr uint64_t HY_PDD_LDS = 32;                        // per node at LV 2: D, q_d, 1 / g, h / g
 
 // LDS of a workgroup, as gatres.h states it: the arrays of the links launch, per valve hset, link, row, node and change flag, per
@@ -117,6 +138,9 @@ static inline uint64_t hy_series_network_lds_bytes(uint64_t N, uint64_t P, uint6
   return hy_network_lds_bytes(N, P, W, Kp, Kv, Ke, Nd) + 8 * N + 40 * K;
 }
 
+// what a series with THE CONTROLS adds: per link the override value and the state word, and the four waves' change counts
+static inline uint64_t hy_controls_lds_bytes(uint64_t P) { return 12 * P + 16; }
+
 // A workgroup's LDS, carved for both kernels: the arrays of the Newton loop (HyLds, HyValves, HyEmitters, HyPdd describe them; the
 // scalars of E and D are the kernel's to set), the series' arrays (a steady launch has K = 0 and no dem) and the flag words.  With a
 // null base `bytes` is all the host wants: where the carve ends, which no launch may place past the bytes it asks for.
@@ -128,12 +152,14 @@ struct HyCarve {
   double* dem;                                             // [N] the step's demand by node (series)
   double *lev, *area, *lmin, *lmax;                        // [K] the tank levels of the present step, and the tanks' constants
   int *tnode, *trow;                                       // [K] a tank's node and its solver row
-  int* flag;                                               // [4]: [0] static arrays refused, [1] scenario or step failed, [2] a level clamped
+  double* cval;                                            // [Pc] a link's override of THE CONTROLS (Pc = P with controls, else 0)
+  int *cst, *ccnt;                                         // [Pc] a link's state word (HY_CS_*); [4 with controls] a wave's changes
+  int* flag;                                              // [4]: [0] static arrays refused, [1] scenario or step failed, [2] a level clamped
   uint64_t bytes;
 };
 
 __host__ __device__ __forceinline__ HyCarve hy_carve(unsigned char* base, int N, int P, int W, int K, int Kp, int Kv, int Ke, int Nd,
-                                                     bool series) {
+                                                     bool series, int Pc = 0) {
   HyCarve C;
   const int BW = W + 1, Ns = series ? N : 0;
   C.L.band = reinterpret_cast<double*>(base);              // [N][BW]
@@ -161,7 +187,8 @@ __host__ __device__ __forceinline__ HyCarve hy_carve(unsigned char* base, int N,
   C.D.q = C.D.dd + Nd;
   C.D.dinv = C.D.q + Nd;
   C.D.dy = C.D.dinv + Nd;
-  C.L.sa = reinterpret_cast<int*>(C.D.dy + Nd);            // [P]
+  C.cval = C.D.dy + Nd;                                    // [Pc]
+  C.L.sa = reinterpret_cast<int*>(C.cval + Pc);            // [P]
   C.L.sb = C.L.sa + P;                                     // [P]
   C.L.fx = C.L.sb + P;                                     // [N]
   C.tnode = C.L.fx + N;                                    // [K]
@@ -173,7 +200,9 @@ __host__ __device__ __forceinline__ HyCarve hy_carve(unsigned char* base, int N,
   C.V.chg = C.V.node + Kv;
   C.E.row = C.V.chg + Kv;                                  // [Ke] each
   C.E.node = C.E.row + Ke;
-  C.flag = C.E.node + Ke;                                  // [4]
+  C.cst = C.E.node + Ke;                                   // [Pc]
+  C.ccnt = C.cst + Pc;                                     // [Pc ? 4 : 0]
+  C.flag = C.ccnt + (Pc ? 4 : 0);                          // [4]
   C.V.Kv = Kv;
   C.E.Ke = Ke;
   C.bytes = (uint64_t)(reinterpret_cast<unsigned char*>(C.flag + 4) - base);
@@ -476,14 +505,94 @@ __global__ __launch_bounds__(HY_T) void hydraulic_solve_network_kernel(const Hyd
   }
 }
 
+// ---- THE CONTROLS of a series (gatres.h) ------------------------------------------------------------------------------------------------
+// A link's state word: the control state (HY_CTL_MASK), whether it carries an override, whether a control changed it in the
+// present step, and whether the step restarts the link (its flow at q_start, its valve ACTIVE).
+constexpr int HY_CS_VALUE = 4, HY_CS_CHANGED = 8, HY_CS_RESTART = 16;
+static_assert(GATRES_HYD_CTL_OPEN == 0 && GATRES_HYD_CTL_CLOSED == 1 && GATRES_HYD_CTL_SETTING == 2 && GATRES_HYD_CTL_TANK_BELOW == 0 &&
+                  GATRES_HYD_CTL_TANK_ABOVE == 1 && GATRES_HYD_CTL_NODE_BELOW == 2 && GATRES_HYD_CTL_NODE_ABOVE == 3 &&
+                  GATRES_HYD_CTL_AT_STEP == 4, "gatres.h");
+
+// The static control table, checked, after hy_check_valve_links (L.code holds the links' kinds; flag[0] keeps the verdict): what
+// gatres.h refuses.  Nothing indexes with a control's link, tank or node that was not checked here.  No barrier of its own.
+__device__ __forceinline__ void hy_check_controls(const HyLds& L, const HydControlArgs& A, const uint8_t* __restrict__ fixed, int N,
+                                                  int P, int K, int* flag, int tid) {
+  for (int k = tid; k < A.Kc; k += HY_T) {
+    const int link = A.link[k], action = A.action[k], kind = A.kind[k], target = A.target[k];
+    const double v = A.value[k];
+    bool ok = link >= 0 && link < P && action <= GATRES_HYD_CTL_SETTING && kind <= GATRES_HYD_CTL_AT_STEP && target >= 0;
+    if (ok) {
+      const int code = L.code[link];
+      if ((code & HY_CHECK) && !(code & HY_PUMP)) ok = false;
+      if (action == GATRES_HYD_CTL_SETTING) {
+        if (!(code & (HY_PUMP | HY_VALVE)) || !hy_finite(v) || ((code & HY_PUMP) && !(v >= 0.0))) ok = false;
+      }
+      if (kind <= GATRES_HYD_CTL_TANK_ABOVE) {
+        if (target >= K) ok = false;
+      } else if (kind <= GATRES_HYD_CTL_NODE_ABOVE) {
+        if (target >= N) ok = false;
+        else if (fixed[target] != 0) ok = false;
+      }
+    }
+    if (!ok) flag[0] = 1;
+  }
+}
+
+// The control pass of step t, one thread per link scanning the table in order (so the last control that fires wins, without
+// atomics): reads lev[] (the levels the step starts with) and H[] (the solution of step t - 1), writes the link's state word and
+// override, and leaves the changes of a wave's links in ccnt[wave].  The caller puts a barrier behind it.
+__device__ __forceinline__ void hy_control_pass(const HyCarve& C, const HydControlArgs& A, const double* __restrict__ thr,
+                                                const int* __restrict__ position, const double* __restrict__ elevation, int P, int t,
+                                                int tid) {
+  int n = 0;
+  for (int p = tid; p < P; p += HY_T) {
+    int st = C.cst[p] & ~(HY_CS_CHANGED | HY_CS_RESTART);
+    double val = C.cval[p];
+    for (int k = 0; k < A.Kc; ++k) {
+      if (A.link[k] != p) continue;
+      const int kind = A.kind[k], target = A.target[k];
+      bool fire;
+      if (kind == GATRES_HYD_CTL_AT_STEP) {
+        fire = t == target;
+      } else if (kind <= GATRES_HYD_CTL_TANK_ABOVE) {
+        const double lv = C.lev[target], th = thr[k];
+        fire = kind == GATRES_HYD_CTL_TANK_BELOW ? lv <= th : lv >= th;
+      } else if (t == 0) {
+        fire = false;
+      } else {
+        const double pr = C.L.H[position[target]] - elevation[target], th = thr[k];
+        fire = kind == GATRES_HYD_CTL_NODE_BELOW ? pr <= th : pr >= th;
+      }
+      if (!fire) continue;
+      const int action = A.action[k];
+      int ns = (st & ~HY_CTL_MASK) | (action == GATRES_HYD_CTL_CLOSED ? HY_CTL_CLOSED : HY_CTL_OPEN);
+      double nv = val;
+      if (action == GATRES_HYD_CTL_SETTING) {
+        ns |= HY_CS_VALUE;
+        nv = A.value[k];
+      }
+      const int same = HY_CTL_MASK | HY_CS_VALUE;
+      if ((ns & same) != (st & same) || __double_as_longlong(nv) != __double_as_longlong(val)) {
+        st = ns | HY_CS_CHANGED;
+        val = nv;
+        ++n;
+      }
+    }
+    C.cst[p] = st;
+    C.cval[p] = val;
+  }
+  for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off, 64);
+  if ((tid & 63) == 0) C.ccnt[tid >> 6] = n;
+}
+
 // ---- the series ------------------------------------------------------------------------------------------------------------------------
-template <int LV>
-__global__ __launch_bounds__(HY_T) void hydraulic_series_network_kernel(const HydNetSeriesArgs A) {
+template <int LV, bool CTL>
+__global__ __launch_bounds__(HY_T) void hydraulic_series_network_kernel(const std::conditional_t<CTL, HydNetSeriesCtlArgs, HydNetSeriesArgs> A) {
   constexpr bool EMIT = LV >= 1, PDD = LV >= 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char hy_smem[];
   const int N = A.N, P = A.P, W = A.W, K = A.K, M = A.M, T = A.T, Kp = A.L.Kp, Kv = A.L.Kv, Ke = EMIT ? A.E.Ke : 0, Ms = A.Ms,
             tid = threadIdx.x;
-  HyCarve C = hy_carve(hy_smem, N, P, W, K, Kp, Kv, Ke, PDD ? N : 0, true);
+  HyCarve C = hy_carve(hy_smem, N, P, W, K, Kp, Kv, Ke, PDD ? N : 0, true, CTL ? P : 0);
   hy_carve_scalars<EMIT, PDD>(C, A.E, A.D, A.elevation);
   const HyLds& L = C.L;
   const HyValves& V = C.V;
@@ -523,6 +632,7 @@ __global__ __launch_bounds__(HY_T) void hydraulic_series_network_kernel(const Hy
     const int m = A.speed_pattern[k];
     if (m < 0 || m >= Ms) flag[0] = 1;
   }
+  if constexpr (CTL) hy_check_controls(L, A.C, A.fixed, N, P, K, flag, tid);
   __syncthreads();
   static_bad = flag[0] != 0;
   if constexpr (PDD) static_bad = hy_pdd_bad(A.D) || static_bad;       // (the launch's scalars: the same in every thread)
@@ -537,6 +647,8 @@ __global__ __launch_bounds__(HY_T) void hydraulic_series_network_kernel(const Hy
     const uint8_t* closed = A.L.closed ? A.L.closed + s * A.L.closed_stride : nullptr;
     const double* ecoef = EMIT ? A.E.coef + s * A.E.coef_stride : nullptr;
     const int* onset = EMIT && A.E.onset ? A.E.onset + s * A.E.onset_stride : nullptr;
+    [[maybe_unused]] const double* thr = nullptr;
+    if constexpr (CTL) thr = A.C.threshold + s * A.C.threshold_stride;
     if (tid == 0) flag[1] = static_bad ? 1 : 0;
     __syncthreads();
     if (!static_bad) {
@@ -559,6 +671,14 @@ __global__ __launch_bounds__(HY_T) void hydraulic_series_network_kernel(const Hy
         if (!hy_finite(q0)) flag[1] = 1;
         rr[p] = r;
         q[p] = q0;
+        if constexpr (CTL) {                               // no control has touched a link before step 0
+          C.cst[p] = 0;
+          C.cval[p] = 0.0;
+        }
+      }
+      if constexpr (CTL) {
+        for (int k = tid; k < A.C.Kc; k += HY_T)           // a threshold that is not finite fails the series from step 0 on
+          if (A.C.kind[k] != GATRES_HYD_CTL_AT_STEP && !hy_finite(thr[k])) flag[1] = 1;
       }
       for (int n = tid; n < N; n += HY_T) {                // the reservoirs keep their heads; a tank's row is set at every step
         const bool fixed = A.fixed[n] != 0;
@@ -576,9 +696,15 @@ __global__ __launch_bounds__(HY_T) void hydraulic_series_network_kernel(const Hy
     for (int t = 0; t < T; ++t) {
       const long long st_i = s * T + t;
       int iters = 0, changes = 0;
+      [[maybe_unused]] int ctl_changes = 0;
       bool converged = false;
       double rel = 0.0;
       if (!dead) {
+        if constexpr (CTL) {                               // THE CONTROLS: before the step's inputs are formed
+          hy_control_pass(C, A.C, thr, A.position, A.elevation, P, t, tid);
+          __syncthreads();                                 // (a pump's speed and a valve's start read their link's state)
+          ctl_changes = C.ccnt[0] + C.ccnt[1] + C.ccnt[2] + C.ccnt[3];     // (rewritten two barriers on at the earliest)
+        }
         // the step's inputs: one rounded product per junction and per pump, the tank heads, the start of the flows
         for (int m = tid; m < M; m += HY_T) {
           const double v = mult[(long long)m * T + t];
@@ -588,8 +714,15 @@ __global__ __launch_bounds__(HY_T) void hydraulic_series_network_kernel(const Hy
           const double v = A.speed_mult[(long long)m * T + t];
           if (!(v >= 0.0) || !hy_finite(v)) flag[1] = 1;
         }
-        for (int k = tid; k < Kp; k += HY_T)
-          hy_set_speed(pump + (size_t)k * HY_PUMP_REC, speed[k] * A.speed_mult[(long long)A.speed_pattern[k] * T + t], &flag[1]);
+        for (int k = tid; k < Kp; k += HY_T) {
+          if constexpr (CTL) {                             // a SETTING control's value stands in place of the base speed
+            const int pl = A.L.pump_link[k];               // (checked by hy_check_valve_links)
+            const double w = (C.cst[pl] & HY_CS_VALUE) ? C.cval[pl] : speed[k];
+            hy_set_speed(pump + (size_t)k * HY_PUMP_REC, w * A.speed_mult[(long long)A.speed_pattern[k] * T + t], &flag[1]);
+          } else {
+            hy_set_speed(pump + (size_t)k * HY_PUMP_REC, speed[k] * A.speed_mult[(long long)A.speed_pattern[k] * T + t], &flag[1]);
+          }
+        }
         for (int n = tid; n < N; n += HY_T) {
           double v = 0.0;
           if (A.fixed[n] == 0) {
@@ -607,14 +740,31 @@ __global__ __launch_bounds__(HY_T) void hydraulic_series_network_kernel(const Hy
         }
         __syncthreads();                                   // (a link's code reads its pump's speed)
         for (int p = tid; p < P; p += HY_T) {
-          const int c = hy_link_code(L, p, closed, &flag[1]);
-          code[p] = c;
-          if (c & HY_SHUT) q[p] = 0.0;                     // a shut link starts at rest, warm or cold
-          else if (t > 0 && !A.warm) q[p] = A.q_start[p];
+          if constexpr (CTL) {                             // a link that a control has touched: reopened, it starts anew
+            const int cs = C.cst[p];
+            const bool touched = (cs & HY_CTL_MASK) != HY_CTL_NONE, was_shut = t > 0 && (code[p] & HY_SHUT) != 0;
+            const int c = hy_link_code(L, p, closed, &flag[1], cs & HY_CTL_MASK);
+            if (touched && t > 0 && ((cs & HY_CS_CHANGED) || was_shut)) C.cst[p] = cs | HY_CS_RESTART;
+            code[p] = c;
+            if (c & HY_SHUT) q[p] = 0.0;
+            else if ((t > 0 && !A.warm) || (touched && was_shut)) q[p] = A.q_start[p];
+          } else {
+            const int c = hy_link_code(L, p, closed, &flag[1]);
+            code[p] = c;
+            if (c & HY_SHUT) q[p] = 0.0;                   // a shut link starts at rest, warm or cold
+            else if (t > 0 && !A.warm) q[p] = A.q_start[p];
+          }
         }
         __syncthreads();
-        for (int k = tid; k < Kv; k += HY_T)               // a warm series carries the statuses along with the flows
-          hy_valve_start(L, V, k, A.L.setting[s * A.L.setting_stride + k], A.elevation, t > 0 && A.warm, &flag[1]);
+        for (int k = tid; k < Kv; k += HY_T) {             // a warm series carries the statuses along with the flows
+          if constexpr (CTL) {                             // (V.link was checked; 0 where the launch is refused)
+            const int cs = C.cst[V.link[k]];
+            const double setting = (cs & HY_CS_VALUE) ? C.cval[V.link[k]] : A.L.setting[s * A.L.setting_stride + k];
+            hy_valve_start(L, V, k, setting, A.elevation, t > 0 && A.warm && !(cs & HY_CS_RESTART), &flag[1]);
+          } else {
+            hy_valve_start(L, V, k, A.L.setting[s * A.L.setting_stride + k], A.elevation, t > 0 && A.warm, &flag[1]);
+          }
+        }
         if constexpr (EMIT)
           for (int k = tid; k < Ke; k += HY_T)             // a warm series carries an emitter's flow along while it stays on
             hy_emitter_start(E, k, onset && t < onset[k] ? 0.0 : ecoef[k], t > 0 && A.warm, &flag[1]);
@@ -684,6 +834,7 @@ __global__ __launch_bounds__(HY_T) void hydraulic_series_network_kernel(const Hy
         st[3] = !dead && flag[2] != 0 ? 1 : 0;
         A.final_dq[st_i] = dead ? nan : rel;
         A.L.valve_changes[st_i] = dead ? 0 : changes;
+        if constexpr (CTL) A.C.changes[st_i] = dead ? 0 : ctl_changes;
       }
     }
     __syncthreads();                                       // (the next series writes the shared arrays again)
@@ -787,9 +938,18 @@ static int hy_solve_network(const HydNetSolveArgs& a, int lv, void* stream) {
   return gatres_launch_status();
 }
 
-// The same for a series; num_speed_patterns is the caller's count (a.Ms: 0 where there is no pump)
-static int hy_series_network(HydNetSeriesArgs a, int32_t num_speed_patterns, int lv, void* stream) {
+// The same for a series; num_speed_patterns is the caller's count (a.Ms: 0 where there is no pump).  With ctl the launch has
+// THE CONTROLS: the table *ctl is checked like every other array, and its LDS is added in closed form.
+static int hy_series_network(HydNetSeriesArgs a, int32_t num_speed_patterns, int lv, void* stream, const HydControlArgs* ctl = nullptr) {
   if (lv == 2 && !a.D.delivered) return GATRES_E_BADARG;
+  const HydControlArgs C = ctl ? *ctl : HydControlArgs{};
+  if (ctl) {
+    const HydControlArgs& c = C;
+    if (!c.changes || c.Kc < 0) return GATRES_E_BADARG;
+    if (c.Kc > 0 && (!c.link || !c.action || !c.value || !c.kind || !c.target || !c.threshold)) return GATRES_E_BADARG;
+    if (c.threshold_stride != 0 && c.threshold_stride != (long long)c.Kc) return GATRES_E_BADARG;
+    if (a.S >= 1 && c.Kc > 0 && a.S > INT64_MAX / 64 / (int64_t)c.Kc) return GATRES_E_BADARG;
+  }
   if (!a.pipe_a || !a.pipe_b || !a.coef || !a.q_start || !a.fixed || !a.elevation || !a.order || !a.position) return GATRES_E_BADARG;
   if (!a.pattern || !a.mult || !a.demand || !a.roughness || !a.fixed_head || !a.pressure || !a.status || !a.final_dq)
     return GATRES_E_BADARG;
@@ -810,35 +970,47 @@ static int hy_series_network(HydNetSeriesArgs a, int32_t num_speed_patterns, int
   if (a.mult_stride != 0 && a.mult_stride != (long long)a.M * (long long)a.T) return GATRES_E_BADARG;
   const uint64_t S = (uint64_t)a.S, T = (uint64_t)a.T, N = (uint64_t)a.N, P = (uint64_t)a.P, K = (uint64_t)a.K, M = (uint64_t)a.M,
                  Kp = (uint64_t)a.L.Kp, Kv = (uint64_t)a.L.Kv, Ms = Kp ? (uint64_t)num_speed_patterns : 0, Ke = (uint64_t)a.E.Ke,
-                 Nd = lv == 2 ? N : 0;
-  const uint64_t lds = hy_series_network_lds_bytes(N, P, (uint64_t)a.W, K, Kp, Kv, Ke, Nd);
+                 Nd = lv == 2 ? N : 0, Kc = (uint64_t)C.Kc;
+  const uint64_t lds = hy_series_network_lds_bytes(N, P, (uint64_t)a.W, K, Kp, Kv, Ke, Nd) + (ctl ? hy_controls_lds_bytes(P) : 0);
   if (lds > HY_LDS_BUDGET) return GATRES_E_BADARG;
-  if (hy_carve(nullptr, a.N, a.P, a.W, a.K, a.L.Kp, a.L.Kv, a.E.Ke, (int)Nd, true).bytes > lds) return GATRES_E_BADARG;
-  const void* wr[10] = {a.pressure, a.head, a.flow, K ? a.level : nullptr, a.status, a.final_dq, a.L.link_state, a.L.valve_changes,
-                        Ke ? a.E.flow : nullptr, a.D.delivered};
-  const uint64_t wn[10] = {4 * S * T * N, 8 * S * T * N, 8 * S * T * P, 8 * S * (T + 1) * K, 4 * GATRES_HYD_STATUS * S * T, 8 * S * T,
-                           S * T * P, 4 * S * T, 8 * S * T * Ke, 8 * S * T * N};
-  const void* rd[35] = {a.pipe_a, a.pipe_b, a.coef, a.q_start, a.fixed, a.elevation, a.order, a.position, K ? a.tank_node : nullptr,
+  if (hy_carve(nullptr, a.N, a.P, a.W, a.K, a.L.Kp, a.L.Kv, a.E.Ke, (int)Nd, true, ctl ? a.P : 0).bytes > lds) return GATRES_E_BADARG;
+  const void* wr[11] = {a.pressure, a.head, a.flow, K ? a.level : nullptr, a.status, a.final_dq, a.L.link_state, a.L.valve_changes,
+                        Ke ? a.E.flow : nullptr, a.D.delivered, C.changes};
+  const uint64_t wn[11] = {4 * S * T * N, 8 * S * T * N, 8 * S * T * P, 8 * S * (T + 1) * K, 4 * GATRES_HYD_STATUS * S * T, 8 * S * T,
+                           S * T * P, 4 * S * T, 8 * S * T * Ke, 8 * S * T * N, 4 * S * T};
+  const void* rd[41] = {a.pipe_a, a.pipe_b, a.coef, a.q_start, a.fixed, a.elevation, a.order, a.position, K ? a.tank_node : nullptr,
                         K ? a.tank_area : nullptr, K ? a.tank_min : nullptr, K ? a.tank_max : nullptr, a.pattern, a.mult,
                         a.demand, a.roughness, a.fixed_head, K ? a.level0 : nullptr, a.L.link_kind, a.L.link_flags, a.L.minor,
                         Kp ? a.L.pump_link : nullptr, Kp ? a.L.pump_h0 : nullptr, Kp ? a.L.pump_r : nullptr,
                         Kp ? a.L.pump_n : nullptr, Kp ? a.L.speed : nullptr, a.L.closed, Kp ? a.speed_mult : nullptr,
                         Kp ? a.speed_pattern : nullptr, Kv ? a.L.valve_link : nullptr, Kv ? a.L.valve_kind : nullptr,
-                        Kv ? a.L.setting : nullptr, Ke ? a.E.node : nullptr, Ke ? a.E.coef : nullptr, Ke ? a.E.onset : nullptr};
-  const uint64_t rn[35] = {4 * P, 4 * P, 8 * P, 8 * P, N, 8 * N, 4 * N, 4 * N, 4 * K, 8 * K, 8 * K, 8 * K, 4 * N,
+                        Kv ? a.L.setting : nullptr, Ke ? a.E.node : nullptr, Ke ? a.E.coef : nullptr, Ke ? a.E.onset : nullptr,
+                        Kc ? C.link : nullptr, Kc ? C.action : nullptr, Kc ? C.value : nullptr, Kc ? C.kind : nullptr,
+                        Kc ? C.target : nullptr, Kc ? C.threshold : nullptr};
+  const uint64_t rn[41] = {4 * P, 4 * P, 8 * P, 8 * P, N, 8 * N, 4 * N, 4 * N, 4 * K, 8 * K, 8 * K, 8 * K, 4 * N,
                            a.mult_stride ? 8 * S * M * T : 8 * M * T, 8 * S * N, 8 * S * P, a.fh_stride ? 8 * S * N : 8 * N,
                            8 * S * K, P, P, 8 * P, 4 * Kp, 8 * Kp, 8 * Kp, 8 * Kp, a.L.speed_stride ? 8 * S * Kp : 8 * Kp,
                            a.L.closed_stride ? S * P : P, 8 * Ms * T, 4 * Kp, 4 * Kv, Kv, a.L.setting_stride ? 8 * S * Kv : 8 * Kv,
-                           4 * Ke, a.E.coef_stride ? 8 * S * Ke : 8 * Ke, a.E.onset_stride ? 4 * S * Ke : 4 * Ke};
-  if (any_overlap(wr, wn, 10, rd, rn, 35)) return GATRES_E_BADARG;
-  void (*const kernels[3])(const HydNetSeriesArgs) = {hydraulic_series_network_kernel<0>, hydraulic_series_network_kernel<1>,
-                                                   hydraulic_series_network_kernel<2>};
-  const int e = hy_raise_lds(reinterpret_cast<const void*>(kernels[lv]), lds);
+                           4 * Ke, a.E.coef_stride ? 8 * S * Ke : 8 * Ke, a.E.onset_stride ? 4 * S * Ke : 4 * Ke,
+                           4 * Kc, Kc, 8 * Kc, Kc, 4 * Kc, C.threshold_stride ? 8 * S * Kc : 8 * Kc};
+  if (any_overlap(wr, wn, 11, rd, rn, 41)) return GATRES_E_BADARG;
+  void (*const kernels[3])(const HydNetSeriesArgs) = {hydraulic_series_network_kernel<0, false>, hydraulic_series_network_kernel<1, false>,
+                                                   hydraulic_series_network_kernel<2, false>};
+  void (*const ctl_kernels[3])(const HydNetSeriesCtlArgs) = {nullptr, hydraulic_series_network_kernel<1, true>,
+                                                          hydraulic_series_network_kernel<2, true>};       // (no entry point takes LV 0)
+  const int e = hy_raise_lds(ctl ? reinterpret_cast<const void*>(ctl_kernels[lv]) : reinterpret_cast<const void*>(kernels[lv]), lds);
   if (e != 0) return e;
   if (!Ke) a.E.onset = nullptr;
   a.Ms = (int)Ms;
   const long long wgs = a.S < HY_GRID_CAP ? a.S : HY_GRID_CAP;
-  hipLaunchKernelGGL(kernels[lv], dim3((unsigned)wgs), dim3(HY_T), (size_t)lds, gatres_stream(stream), a);
+  if (ctl) {
+    HydNetSeriesCtlArgs ac;
+    static_cast<HydNetSeriesArgs&>(ac) = a;
+    ac.C = C;
+    hipLaunchKernelGGL(ctl_kernels[lv], dim3((unsigned)wgs), dim3(HY_T), (size_t)lds, gatres_stream(stream), ac);
+  } else {
+    hipLaunchKernelGGL(kernels[lv], dim3((unsigned)wgs), dim3(HY_T), (size_t)lds, gatres_stream(stream), a);
+  }
   return gatres_launch_status();
 }
 
@@ -1039,4 +1211,42 @@ extern "C" int gatres_hydraulic_series_pdd(
                         emitter_onset_stride, emitter_flow);
   a.D = hy_pdd_args(demand_model, minimum_pressure, required_pressure, pressure_exponent, demand_delivered);
   return hy_series_network(a, num_speed_patterns, demand_model ? 2 : 1, stream);
+}
+
+extern "C" int gatres_hydraulic_series_controls(
+    const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start, const uint8_t* fixed,
+    const double* elevation, const int32_t* order, const int32_t* position, int32_t half_bandwidth, const int32_t* tank_node,
+    const double* tank_area, const double* tank_min_level, const double* tank_max_level, int32_t num_tanks,
+    const int32_t* pattern_of_node, const double* mult, int64_t mult_stride, int32_t num_patterns, const double* demand,
+    const double* roughness, const double* fixed_head, int64_t fixed_head_stride, const double* initial_level, int64_t num_series,
+    int32_t num_steps, int32_t num_nodes, int32_t num_pipes, double dt, int32_t warm_start, double accuracy, int32_t max_iter,
+    float* pressure, double* head, double* flow, double* level, int32_t* status, double* final_dq, const uint8_t* link_kind,
+    const uint8_t* link_flags, const double* minor, const int32_t* pump_link, const double* pump_h0, const double* pump_r,
+    const double* pump_n, int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+    int64_t closed_stride, const double* speed_mult, const int32_t* speed_pattern_of_pump, int32_t num_speed_patterns,
+    uint8_t* link_state, const int32_t* valve_link, const uint8_t* valve_kind, const double* valve_setting,
+    int64_t valve_setting_stride, int32_t num_valves, int32_t* valve_changes, const int32_t* emitter_node,
+    const double* emitter_coef, int64_t emitter_coef_stride, int32_t num_emitters, double emitter_exponent,
+    const int32_t* emitter_onset, int64_t emitter_onset_stride, double* emitter_flow, int32_t demand_model,
+    double minimum_pressure, double required_pressure, double pressure_exponent, double* demand_delivered,
+    const int32_t* control_link, const uint8_t* control_action, const double* control_value, const uint8_t* control_kind,
+    const int32_t* control_target, const double* control_threshold, int64_t control_threshold_stride, int32_t num_controls,
+    int32_t* control_changes, void* stream) {
+  if (demand_model != 0 && demand_model != 1) return GATRES_E_BADARG;
+  HydNetSeriesArgs a = hy_series_args(pipe_a, pipe_b, coef, q_start, fixed, elevation, order, position, half_bandwidth, tank_node,
+                                   tank_area, tank_min_level, tank_max_level, num_tanks, pattern_of_node, mult, mult_stride,
+                                   num_patterns, demand, roughness, fixed_head, fixed_head_stride, initial_level, num_series,
+                                   num_steps, num_nodes, num_pipes, dt, warm_start, accuracy, max_iter, pressure, head, flow, level,
+                                   status, final_dq, speed_mult, speed_pattern_of_pump);
+  a.L = hy_valve_args(link_kind, link_flags, minor, pump_link, pump_h0, pump_r, pump_n, num_pumps, speed, speed_stride, closed,
+                      closed_stride, link_state, valve_link, valve_kind, valve_setting, valve_setting_stride, num_valves,
+                      valve_changes);
+  a.E = hy_emitter_args(emitter_node, emitter_coef, emitter_coef_stride, num_emitters, emitter_exponent, emitter_onset,
+                        emitter_onset_stride, emitter_flow);
+  a.D = hy_pdd_args(demand_model, minimum_pressure, required_pressure, pressure_exponent, demand_delivered);
+  HydControlArgs c;
+  c.link = control_link; c.action = control_action; c.value = control_value; c.kind = control_kind; c.target = control_target;
+  c.threshold = control_threshold; c.threshold_stride = (long long)control_threshold_stride; c.Kc = (int)num_controls;
+  c.changes = control_changes;
+  return hy_series_network(a, num_speed_patterns, demand_model ? 2 : 1, stream, &c);
 }

@@ -622,12 +622,21 @@ __device__ __forceinline__ void hy_set_speed(double* rec, double w, int* bad) {
   rec[5] = w;
 }
 
+// A link's control state of a series with THE CONTROLS (gatres.h): the two low bits of its state word; 0 where no control has
+// touched the link in this series, and in every launch without controls.
+constexpr int HY_CTL_NONE = 0, HY_CTL_OPEN = 1, HY_CTL_CLOSED = 2, HY_CTL_MASK = 3;
+
 // A link's code of the scenario or step: HY_SHUT where the static flag, the scenario's byte or a pump speed of zero shuts it.  A
-// valve's bits stay.
-__device__ __forceinline__ int hy_link_code(const HyLds& L, int p, const uint8_t* closed, int* bad) {
+// valve's bits stay.  A control state other than HY_CTL_NONE stands in place of the static flag and the byte: HY_CTL_CLOSED shuts
+// the link, HY_CTL_OPEN leaves it to its pump's speed alone.
+__device__ __forceinline__ int hy_link_code(const HyLds& L, int p, const uint8_t* closed, int* bad, int ctl = HY_CTL_NONE) {
   int code = L.code[p] & ~HY_SHUT;
   const int cl = closed ? closed[p] : 0;
   if (cl > 1) *bad = 1;
+  if (ctl != HY_CTL_NONE) {
+    if (ctl == HY_CTL_CLOSED || ((code & HY_PUMP) && L.pump[(size_t)(code >> HY_PUMP_SHIFT) * HY_PUMP_REC + 5] == 0.0)) code |= HY_SHUT;
+    return code;
+  }
   if ((code & HY_CLOSED) || cl == 1 || ((code & HY_PUMP) && L.pump[(size_t)(code >> HY_PUMP_SHIFT) * HY_PUMP_REC + 5] == 0.0))
     code |= HY_SHUT;
   return code;

@@ -131,8 +131,37 @@ no failure and the series goes on from its flows.
 WHAT DOES NOT HOLD IN A SERIES: EPANET shortens a time step at the moment a tank becomes full or empty and closes the pipes of
 such a tank; this model clamps the level and does neither.  A step after which any level was clamped has status[s][t][3] = 1
 (``limited``), and volume is not conserved across such a step; ``series_valid`` and ``generate_series_store`` drop such series
-unless told otherwise.  Controls and rules stay out of scope.  The limit on flows that should be
-zero (below) carries over unchanged: a step with a zero multiplier will not meet the stop rule.
+unless told otherwise.  Simple controls are THE CONTROLS below; rule-based controls ([RULES]) stay out of scope.  The limit on
+flows that should be zero (below) carries over unchanged: a step with a zero multiplier will not meet the stop rule.
+
+THE CONTROLS (``control_table``, ``simulate_series(controls=)``, ``generate_series_store(controls=)``; gatres.h: THE CONTROLS):
+EPANET's simple controls in a series, ``gatres_hydraulic_series_controls`` -- the pdd launch with a table of Kc >= 0 controls whose
+order matters.  Control k holds link[k]; action[k] (OPEN 0, CLOSED 1, SETTING 2); value[k], read for SETTING only (on a pump the
+base speed in place of pump_speed[s][k'], still multiplied by the step's speed multiplier; on a PRV or PSV the setting in metres
+in place of valve_setting[s][k']); kind[k] (TANK_BELOW 0, TANK_ABOVE 1, NODE_BELOW 2, NODE_ABOVE 3, AT_STEP 4); target[k] (a tank
+index, a junction's node index, a step index); threshold [Kc] or [S, Kc] (a level in metres above the tank's bottom, a pressure
+in metres; not read for AT_STEP).  EVALUATION at the start of step t, before the step's inputs are formed: TANK_BELOW
+level[t][target] <= threshold, TANK_ABOVE >= (the level the step starts with, so at t = 0 too); NODE_BELOW / NODE_ABOVE
+H - elevation of the solution of step t - 1 <= / >= threshold, not at t = 0, whether or not step t - 1 converged; AT_STEP
+t == target (a target of T or more never fires).  Every control whose condition holds applies its action, in table order: the
+last one wins.  Controls are level-triggered, as in EPANET.  STATE per link, reset at the start of every series and kept until a
+control changes it: ctl in {none, open, closed} and an override with a presence flag; OPEN sets ctl = open, CLOSED ctl = closed,
+SETTING stores the override and sets ctl = open.  A control that fires has changed its link when ctl, the flag or the bits of the
+override differ from what they were; ``control_changes`` [S, T] counts these per step.  EFFECT: a link is shut by input when
+ctl == closed, or when ctl == none and the static CLOSED flag or the ``link_closed`` byte says so; ctl == open overrides both.  A
+pump with w == 0 is still shut: a SETTING of 0 switches it off, OPEN gives a pump with base speed 0 no speed.  ``link_state`` 2
+reads "shut by input, by w == 0 or by a control".  A link a control has touched (ctl != none) that was shut in step t - 1 and is
+not in step t starts step t at q_start, warm or cold; its regulating valve starts the step ACTIVE, even warm, when a control
+changed the link at step t or it was shut in step t - 1 (``control_start_ref``).  A link no control has touched behaves as in the
+pdd launch, which an empty table gives bit for bit.  REFUSED (``control_table`` raises ``ValueError``; the kernel fails every
+series): a link outside [0, P), an unknown action or kind, a control on a CHECK pipe that is no pump, SETTING on a link that is
+neither a pump nor a PRV / PSV, a SETTING that is not finite or negative on a pump, a tank index outside [0, K), a node outside
+the network or with a fixed head, a negative step.  A threshold that is not finite fails its series from step 0 on.  WHAT DOES
+NOT HOLD: EPANET shortens a time step so that a level control fires when the level is reached; here levels are read at step
+starts, so a level overshoots its threshold by up to |inflow| dt / A.  EPANET's volume tolerance on level controls is not
+modelled.  A control that cuts a zone off from every fixed-head node gives a step that does not converge (``series_valid`` drops
+it, as with ``link_closed``).  [RULES] and controls on pipe settings (TCV loss, FCV and the like) stay out.  Parity with EPANET
+is not claimed.
 
 WHAT DOES NOT HOLD: flows that should be zero do not come to rest on the linear branch.  A head of 100 m resolves 1.4e-14 m
 in fp64, and on the linear branch a head difference becomes a flow with 1 / g = 1e7: one ulp between two neighbours is
@@ -148,7 +177,8 @@ the order of the upper end).
 Host restatements in numpy fp64 (the yardsticks of the tests): ``pipe_headloss``, ``solve_ref``, ``hydraulic_residuals``,
 ``hydraulic_draws``, ``tree_solution``, ``simulate_series_ref``, ``level_update_ref``, ``series_valid_ref``,
 ``series_volume_balance``, ``link_headloss``, ``link_state_ref``, ``hydraulic_link_draws``, ``pump_curve_from_points``,
-``valve_status_ref``, ``hydraulic_valve_draws``, ``emitter_headloss``, ``hydraulic_emitter_draws`` and ``demand_headloss``.
+``valve_status_ref``, ``hydraulic_valve_draws``, ``emitter_headloss``, ``hydraulic_emitter_draws``, ``demand_headloss``,
+``control_step_ref`` and ``control_start_ref``.
 """
 from __future__ import annotations
 
@@ -328,6 +358,180 @@ def series_emitters_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: in
                               num_emitters: int) -> int:
     """What a workgroup of ``gatres_hydraulic_series_emitters`` takes of the LDS (gatres.h states the same sum)."""
     return series_valves_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_tanks, num_pumps, num_valves) + 48 * num_emitters
+
+
+# ---- THE CONTROLS (gatres.h): EPANET's simple controls in a series ---------------------------------------------------------------
+CONTROL_ACTIONS = {"open": 0, "closed": 1, "setting": 2}            # GATRES_HYD_CTL_OPEN, _CLOSED, _SETTING
+CONTROL_KINDS = {"tank_below": 0, "tank_above": 1, "node_below": 2, "node_above": 3, "at_step": 4}      # GATRES_HYD_CTL_TANK_BELOW ..
+CTL_NONE, CTL_OPEN, CTL_CLOSED = 0, 1, 2                            # a link's control state
+# what a series with controls returns: the fields of the pdd launch, and control_changes (int32 [S, T])
+HydraulicSeriesControlsResult = namedtuple("HydraulicSeriesControlsResult", HydraulicSeriesPddResult._fields + ("control_changes",))
+HydraulicSeriesControlsReference = namedtuple("HydraulicSeriesControlsReference",
+                                              HydraulicSeriesPddReference._fields + ("control_changes",))
+
+
+class ControlTable:
+    """THE TABLE of THE CONTROLS: ``link`` int32, ``action`` uint8 (``CONTROL_ACTIONS``), ``value`` fp64 (read for a setting),
+    ``kind`` uint8 (``CONTROL_KINDS``), ``target`` int32 and ``threshold`` fp64, each [Kc], in the order that decides which control
+    wins.  A plain record: ``control_table`` is what checks one against a network."""
+    ACTIONS, KINDS = CONTROL_ACTIONS, CONTROL_KINDS
+
+    def __init__(self, link, action, value, kind, target, threshold):
+        self.link = np.ascontiguousarray(link, dtype=np.int32).reshape(-1)
+        Kc = self.link.size
+        self.action = np.ascontiguousarray(action, dtype=np.uint8).reshape(Kc)
+        self.value = np.ascontiguousarray(value, dtype=np.float64).reshape(Kc)
+        self.kind = np.ascontiguousarray(kind, dtype=np.uint8).reshape(Kc)
+        self.target = np.ascontiguousarray(target, dtype=np.int32).reshape(Kc)
+        self.threshold = np.ascontiguousarray(threshold, dtype=np.float64).reshape(Kc)
+
+    def __len__(self) -> int:
+        return int(self.link.size)
+
+    @property
+    def num_controls(self) -> int:
+        return int(self.link.size)
+
+
+def control_table(network: "HydraulicNetwork", controls, step_seconds=None) -> ControlTable:
+    """The ``ControlTable`` of ``controls`` on ``network``: a sequence of tuples (link, action, kind, target[, threshold]) such as
+    ``(link, "closed", "tank_above", tank, 4.5)``, ``(link, ("setting", 0.8), "at_step", 12)`` and
+    ``(link, "open", "node_below", node, 20.0)``.  ``action`` is "open", "closed" or ("setting", value); ``kind`` one of
+    ``CONTROL_KINDS``, or "at_time" with a target in seconds, which ``step_seconds`` turns into a step (a time that is no whole
+    number of steps is refused).  A ``ControlTable`` is checked as it is.  ``ValueError``, naming the control, for everything THE
+    CONTROLS refuse: a link outside [0, P), an unknown action or kind, a control on a CHECK pipe that is no pump, a setting on a link
+    that is neither a pump nor a PRV / PSV, a setting that is not finite or is negative on a pump, a tank index outside [0, K), a
+    node outside the network or with a fixed head, a negative step."""
+    P, N, K = network.num_pipes, network.num_nodes, network.num_tanks
+    if isinstance(controls, ControlTable):
+        rows = [(int(controls.link[k]), int(controls.action[k]), float(controls.value[k]), int(controls.kind[k]),
+                 int(controls.target[k]), float(controls.threshold[k])) for k in range(len(controls))]
+    else:
+        rows = []
+        for k, c in enumerate(controls):
+            if len(c) not in (4, 5):
+                raise ValueError(f"control {k}: expected (link, action, kind, target[, threshold]), got {c!r}")
+            link, action, kind, target = c[:4]
+            value = 0.0
+            if isinstance(action, (tuple, list)):
+                if len(action) != 2:
+                    raise ValueError(f"control {k}: a setting is ('setting', value), got {action!r}")
+                action, value = action[0], float(action[1])
+            if action not in CONTROL_ACTIONS:
+                raise ValueError(f"control {k}: unknown action {action!r}")
+            if kind == "at_time":
+                if step_seconds is None:
+                    raise ValueError(f"control {k}: 'at_time' needs step_seconds")
+                steps = float(target) / float(step_seconds)
+                if not (np.isfinite(steps) and steps == np.floor(steps)):
+                    raise ValueError(f"control {k}: the time {target} s is no whole number of steps of {step_seconds} s")
+                kind, target = "at_step", int(steps)
+            if kind not in CONTROL_KINDS:
+                raise ValueError(f"control {k}: unknown kind {kind!r}")
+            if CONTROL_KINDS[kind] != CONTROL_KINDS["at_step"] and len(c) != 5:
+                raise ValueError(f"control {k}: a {kind} control needs a threshold")
+            if int(target) != target:
+                raise ValueError(f"control {k}: the target {target!r} is no index")
+            rows.append((int(link), CONTROL_ACTIONS[action], value, CONTROL_KINDS[kind], int(target),
+                         float(c[4]) if len(c) == 5 else 0.0))
+    for k, (link, action, value, kind, target, _thr) in enumerate(rows):
+        if not 0 <= link < P:
+            raise ValueError(f"control {k}: link {link} is outside [0, {P})")
+        if action not in CONTROL_ACTIONS.values():
+            raise ValueError(f"control {k}: unknown action {action}")
+        if kind not in CONTROL_KINDS.values():
+            raise ValueError(f"control {k}: unknown kind {kind}")
+        pump, valve = bool(network.is_pump[link]), bool(network.is_valve[link])
+        if network.check_valve[link] and not pump:
+            raise ValueError(f"control {k}: link {link} is a CHECK pipe, which takes no control")
+        if action == CONTROL_ACTIONS["setting"]:
+            if not (pump or valve):
+                raise ValueError(f"control {k}: link {link} is neither a pump nor a PRV / PSV and takes no setting")
+            if not np.isfinite(value) or (pump and value < 0):
+                raise ValueError(f"control {k}: the setting {value} of link {link} is not finite or is negative on a pump")
+        if target < 0:
+            raise ValueError(f"control {k}: the target {target} is negative")
+        if kind <= CONTROL_KINDS["tank_above"]:
+            if target >= K:
+                raise ValueError(f"control {k}: tank {target} is outside [0, {K})")
+        elif kind <= CONTROL_KINDS["node_above"]:
+            if target >= N:
+                raise ValueError(f"control {k}: node {target} is outside the network")
+            if network.fixed[target]:
+                raise ValueError(f"control {k}: node {target} is a fixed-head node")
+    cols = list(zip(*rows)) if rows else [[]] * 6
+    return ControlTable(*cols)
+
+
+def series_controls_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_tanks: int, num_pumps: int, num_valves: int,
+                              num_emitters: int, demand_model: int = 1) -> int:
+    """What a workgroup of ``gatres_hydraulic_series_controls`` takes of the LDS (gatres.h states the same sum): the bytes of
+    ``gatres_hydraulic_series_pdd`` and 12 P + 16, per link the override and the state word and the four waves' change counts."""
+    return series_pdd_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_tanks, num_pumps, num_valves, num_emitters,
+                                demand_model) + 12 * num_pipes + 16
+
+
+def control_state(num_links: int) -> dict:
+    """The control state of the links at the start of a series: ``ctl`` [P] (``CTL_NONE``), ``has_value`` [P] False, ``value``
+    [P] 0, and ``changed`` [P], whether a control changed the link in the step last evaluated."""
+    return {"ctl": np.zeros(num_links, dtype=np.int8), "has_value": np.zeros(num_links, dtype=bool),
+            "value": np.zeros(num_links, dtype=np.float64), "changed": np.zeros(num_links, dtype=bool)}
+
+
+def control_step_ref(table: ControlTable, threshold, state: dict, level, pressure_prev, t: int) -> Tuple[dict, int]:
+    """THE CONTROLS at the start of step ``t``, as a plain loop over the table in its order: ``threshold`` [Kc], ``state`` as
+    ``control_state`` leaves it or as the step before returned it, ``level`` [K] the levels the step starts with,
+    ``pressure_prev`` [N] head - elevation of step t - 1 (not read at t = 0).  Returns (the new state, the number of controls that
+    changed their link: its ctl, the presence of an override or the bits of the override)."""
+    thr = np.asarray(threshold, dtype=np.float64)
+    st = {k: v.copy() for k, v in state.items()}
+    st["changed"][:] = False
+    changes = 0
+    for k in range(len(table)):
+        kind, target, p = int(table.kind[k]), int(table.target[k]), int(table.link[k])
+        if kind == CONTROL_KINDS["at_step"]:
+            fire = t == target
+        elif kind == CONTROL_KINDS["tank_below"]:
+            fire = bool(level[target] <= thr[k])
+        elif kind == CONTROL_KINDS["tank_above"]:
+            fire = bool(level[target] >= thr[k])
+        elif t == 0:
+            fire = False
+        elif kind == CONTROL_KINDS["node_below"]:
+            fire = bool(pressure_prev[target] <= thr[k])
+        else:
+            fire = bool(pressure_prev[target] >= thr[k])
+        if not fire:
+            continue
+        action = int(table.action[k])
+        ctl = CTL_CLOSED if action == CONTROL_ACTIONS["closed"] else CTL_OPEN
+        has, val = bool(st["has_value"][p]), st["value"][p]
+        if action == CONTROL_ACTIONS["setting"]:
+            has, val = True, table.value[k]
+        if ctl != st["ctl"][p] or has != st["has_value"][p] or np.float64(val).tobytes() != np.float64(st["value"][p]).tobytes():
+            st["ctl"][p], st["has_value"][p], st["value"][p] = ctl, has, val
+            st["changed"][p] = True
+            changes += 1
+    return st, changes
+
+
+def control_start_ref(state: dict, was_shut, t: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The start rules of THE CONTROLS at step ``t``, per link [P]: (starts at q_start -- a link a control has touched that was shut
+    in step t - 1; it starts at 0 instead where it is still shut --, its regulating valve starts ACTIVE -- such a link that a
+    control changed at step t or that was shut in step t - 1).  Nothing at t = 0."""
+    touched = (state["ctl"] != CTL_NONE) & (t > 0)
+    was_shut = np.asarray(was_shut, dtype=bool)
+    return touched & was_shut, touched & (state["changed"] | was_shut)
+
+
+def _control_inputs(network, controls, control_threshold, S: int, step_seconds=None):
+    """(table, thresholds [S, Kc]) of a call with ``controls``."""
+    table = controls if isinstance(controls, ControlTable) else control_table(network, controls, step_seconds)
+    Kc = len(table)
+    thr = table.threshold if control_threshold is None else np.asarray(control_threshold, dtype=np.float64)
+    if thr.shape not in ((Kc,), (S, Kc)):
+        raise ValueError(f"control_threshold must be [{Kc}] or [{S}, {Kc}]")
+    return table, np.broadcast_to(thr, (S, Kc))
 
 
 def _valve_rule(psv: bool, status: int, Ha: float, Hb: float, q: float, hml: float, hset: float):
@@ -1236,7 +1440,8 @@ class HydraulicNetwork:
                         want_head: bool = True, want_flow: bool = True, pump_speed=None, link_closed=None, speed_multipliers=None,
                         speed_pattern_of_pump=None, links=None, valve_setting=None, valves=None, emitter_coefficient=None,
                         emitter_onset=None, emitters=None, demand_model=None, minimum_pressure: float = 0.0,
-                        required_pressure=None, pressure_exponent: float = PRESSURE_EXPONENT) -> HydraulicSeriesResult:
+                        required_pressure=None, pressure_exponent: float = PRESSURE_EXPONENT, controls=None,
+                        control_threshold=None) -> HydraulicSeriesResult:
         """``gatres_hydraulic_series``: S series of T steps on the device, one launch.  ``demand`` [S, N] base demands,
         ``roughness`` [S, P], ``multipliers`` [M, T] (for every series) or [S, M, T], ``pattern_of_node`` int [N] with values in
         [0, M) (default: pattern 0 everywhere; host data outside the range raises ``ValueError``, a DEVICE tensor is not read back
@@ -1258,9 +1463,17 @@ class HydraulicNetwork:
         ``emitter_flow`` fp64 [S, T, Ke]; with ``warm_start`` an emitter's flow carries over while it stays on.  ``demand_model``,
         ``minimum_pressure``, ``required_pressure`` and ``pressure_exponent`` as in ``simulate``: ``gatres_hydraulic_series_pdd`` and a
         ``HydraulicSeriesPddResult`` with ``demand_delivered`` fp64 [S, T, N]; a junction is pressure-driven at the steps where
-        its demand times the multiplier is positive, and with ``warm_start`` keeps its delivered flow while it stays so."""
+        its demand times the multiplier is positive, and with ``warm_start`` keeps its delivered flow while it stays so.
+        ``controls`` (a ``ControlTable``, or what ``control_table`` takes) gives THE CONTROLS: ``gatres_hydraulic_series_controls``,
+        the pdd launch (demand-driven unless ``demand_model="pda"``) with the table evaluated at the start of every step, and a
+        ``HydraulicSeriesControlsResult`` with ``control_changes`` int32 [S, T]; ``control_threshold`` [Kc] or [S, Kc] overrides the
+        table's thresholds.  With ``controls=None`` nothing changes."""
         st, dev, lib = self.static(), self._dev(), _native.load()
         pdd = pdd_arguments(demand_model, minimum_pressure, required_pressure, pressure_exponent)
+        if controls is None and control_threshold is not None:
+            raise ValueError("control_threshold needs controls")
+        if controls is not None and pdd is None:
+            pdd = (0, 0.0, 0.0, PRESSURE_EXPONENT)
         if pdd is not None:
             emitters = True
         with_emitters = bool(emitters) if emitters is not None else (
@@ -1353,13 +1566,30 @@ class HydraulicNetwork:
             speed_args = (smult.data_ptr(), spat.data_ptr(), int(smult.shape[0])) if Kp else (None, None, 0)
             if with_valves:
                 need = series_pdd_lds_bytes(N, P, self.half_bandwidth, K, Kp, self.num_valves, self.num_emitters,
-                                            0 if pdd is None else pdd[0])
+                                            0 if pdd is None else pdd[0]) + (0 if controls is None else 12 * P + 16)
                 if need > LDS_BUDGET:                       # (the constructor held a network without tanks to the steady launch's sum)
                     raise ValueError(f"a series on the band of {N} rows with half-bandwidth {self.half_bandwidth} needs {need} bytes "
                                      f"of LDS, the kernel has {LDS_BUDGET}")
                 valve_args, changes, _held_v = self._valve_args(S, (S, T), valve_setting)
                 if with_emitters:
                     emitter_args, emitter_flow, _held_e = self._emitter_args(S, (S, T), emitter_coefficient, emitter_onset, True)
+                    if controls is not None:
+                        table, thr = _control_inputs(self, controls, control_threshold, S, step_seconds)
+                        Kc = len(table)
+                        up = lambda a: torch.from_numpy(np.array(a)).to(dev)       # (a copy: a broadcast view is read-only)
+                        held = [up(a) for a in (table.link, table.action, table.value, table.kind, table.target)]
+                        held.append(up(thr if thr.strides[0] else thr[0]))      # ([Kc] where every series has the table's)
+                        cp = (lambda t: t.data_ptr()) if Kc else (lambda t: None)
+                        control_changes = torch.empty((S, T), dtype=torch.int32, device=dev)
+                        delivered = torch.empty((S, T, N), dtype=torch.float64, device=dev)
+                        rc = lib.gatres_hydraulic_series_controls(
+                            *prefix, *link_args, *speed_args, link_state.data_ptr(), *valve_args,
+                            changes.data_ptr(), *emitter_args, *pdd, delivered.data_ptr(), *[cp(t) for t in held],
+                            Kc if held[5].dim() == 2 else 0, Kc, control_changes.data_ptr(), _native.current_stream(dev))
+                        _native.check(rc, "gatres_hydraulic_series_controls")
+                        return HydraulicSeriesControlsResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
+                                                             status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq,
+                                                             link_state, changes, emitter_flow, delivered, control_changes)
                     if pdd is not None:
                         delivered = torch.empty((S, T, N), dtype=torch.float64, device=dev)
                         rc = lib.gatres_hydraulic_series_pdd(
@@ -1436,7 +1666,7 @@ class HydraulicNetwork:
                               speed_multipliers=None, speed_pattern_of_pump=None, valve_setting_range=None,
                               emitter_coefficient_range=None, leak_probability: float = 1.0, leak_onset_range=None,
                               demand_model=None, minimum_pressure: float = 0.0, required_pressure=None,
-                              pressure_exponent: float = PRESSURE_EXPONENT):
+                              pressure_exponent: float = PRESSURE_EXPONENT, controls=None):
         """Draw, simulate and filter ``num_series`` series of ``steps`` steps into a ``SnapshotStore`` over the junctions whose
         rows are series-major (E * steps rows for E kept series: what ``monitor_store(series_length=steps)`` expects).  Base
         demands and roughness per series come from ``draw``, the initial levels from ``draw_levels``; ``multipliers`` default to
@@ -1452,8 +1682,11 @@ class HydraulicNetwork:
         number in [lo, hi), on Ke cells after those.  The report then has ``report["leak"]``: device tensors ``coefficient``
         [kept, Ke], ``flow`` [kept, steps, Ke] and, with ``leak_onset_range``, ``onset`` int32 [kept, Ke] -- the labels.
         ``demand_model`` and its three scalars as in ``generate_store``: ``report["supply"]`` then holds ``delivered`` and ``full``
-        [kept, steps, N]."""
+        [kept, steps, N].  ``controls`` (as in ``simulate_series``: THE CONTROLS) goes to every chunk's launch as it is, so a
+        pump that feeds a tank can be operated and its series kept."""
         pdd_kw = _pdd_keywords(demand_model, minimum_pressure, required_pressure, pressure_exponent)
+        ctl_kw = {} if controls is None else {"controls": controls if isinstance(controls, ControlTable) else
+                                              control_table(self, controls, step_seconds)}
         supply_rows = []
         if num_series < 1 or chunk < 1 or steps < 1:
             raise ValueError("num_series, steps and chunk must be positive")
@@ -1497,7 +1730,7 @@ class HydraulicNetwork:
             level0 = self.draw_levels(n, seed, first, *lv)
             res = self.simulate_series(demand, roughness, mult, step_seconds=step_seconds, initial_level=level0,
                                        pattern_of_node=pattern_of_node, warm_start=warm_start, accuracy=accuracy,
-                                       max_iter=max_iter, want_head=False, want_flow=False, **link_kw, **pdd_kw)
+                                       max_iter=max_iter, want_head=False, want_flow=False, **link_kw, **pdd_kw, **ctl_kw)
             ok = self.series_valid(res, pressure_range, allow_limited)
             table = torch.cat([res.status.reshape(n, -1), ok.to(torch.int32)[:, None]], dim=1).cpu().numpy()     # the read-back
             tables.append(table)
@@ -2139,7 +2372,8 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                         speed_multipliers=None, speed_pattern_of_pump=None, links=None, valve_setting=None,
                         valves=None, emitter_coefficient=None, emitter_onset=None, emitters=None, demand_model=None,
                         minimum_pressure: float = 0.0, required_pressure=None,
-                        pressure_exponent: float = PRESSURE_EXPONENT) -> HydraulicSeriesReference:
+                        pressure_exponent: float = PRESSURE_EXPONENT, controls=None,
+                        control_threshold=None) -> HydraulicSeriesReference:
     """``gatres_hydraulic_series`` in numpy fp64, series by series and step by step, on the Newton loop of ``solve_ref``: the
     rounded product demand * multiplier, the tank heads elevation + level, the warm or cold start, ``level_update_ref`` and
     the kernel's failure rules.  head [S, T, N], flow [S, T, P], level [S, T + 1, K], the rest [S, T].  With special links (as
@@ -2148,10 +2382,21 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
     ``HydraulicSeriesValvesReference`` (``valve_changes`` [S, T]; ``margin`` [S, T, 2] as in ``solve_ref``); with emitters (as in
     ``simulate_series``) it is ``gatres_hydraulic_series_emitters`` and returns a ``HydraulicSeriesEmittersReference``
     (``emitter_flow`` [S, T, Ke]); with ``demand_model`` (as in ``simulate_series``) it is ``gatres_hydraulic_series_pdd`` and returns
-    a ``HydraulicSeriesPddReference`` (``demand_delivered`` [S, T, N])."""
+    a ``HydraulicSeriesPddReference`` (``demand_delivered`` [S, T, N]); with ``controls`` (as in ``simulate_series``) it is
+    ``gatres_hydraulic_series_controls``: ``control_step_ref`` at the start of every step, the start rules of THE CONTROLS, and a
+    ``HydraulicSeriesControlsReference`` (``control_changes`` [S, T], 0 where the step failed)."""
     newton = _NewtonRef(network, solver, accuracy, max_iter)
     demand, mult, pattern = _series_inputs(network, demand, multipliers, pattern_of_node)
     pdd = pdd_arguments(demand_model, minimum_pressure, required_pressure, pressure_exponent)
+    table = None
+    if controls is not None:
+        table, c_thr = _control_inputs(network, controls, control_threshold, demand.shape[0], step_seconds)
+        control_changes = np.zeros((demand.shape[0], mult.shape[2]), dtype=np.int32)
+        evaluated = table.kind != CONTROL_KINDS["at_step"]
+        if pdd is None:
+            pdd = (0, 0.0, 0.0, PRESSURE_EXPONENT)
+    elif control_threshold is not None:
+        raise ValueError("control_threshold needs controls")
     if pdd is not None:
         emitters = True
         delivered = np.full((demand.shape[0], mult.shape[2], network.num_nodes), np.nan)
@@ -2210,6 +2455,10 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                 continue
             e_q, e_was_on = np.zeros(Ke), np.zeros(Ke, dtype=bool)
         d_q, d_was_on = np.zeros(N), np.zeros(N, dtype=bool)
+        if table is not None:                               # a threshold that is not finite fails the series from step 0 on
+            if not np.isfinite(c_thr[s][evaluated]).all():
+                continue
+            cstate, was_shut = control_state(P), np.zeros(P, dtype=bool)
         for t in range(T):
             m = mult[s, :, t]
             with np.errstate(all="ignore"):
@@ -2222,14 +2471,32 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                 sm = smult[:, t]
                 if not (np.isfinite(sm).all() and (sm >= 0).all()):
                     break
+                base = np.ones(network.num_pumps) if speeds is None else speeds[s]
+                if table is not None:                       # THE CONTROLS: before the step's inputs are formed
+                    cstate, n_changed = control_step_ref(table, c_thr[s], cstate, lev,
+                                                         None if t == 0 else head[s, t - 1] - network.elevation, t)
+                    pl = network.pump_links
+                    base = np.where(cstate["has_value"][pl], cstate["value"][pl], base)
                 with np.errstate(all="ignore"):
-                    w = (np.ones(network.num_pumps) if speeds is None else speeds[s]) * sm[spat]
+                    w = base * sm[spat]
                 law = link_law(network, w, None if closed is None else closed[s])
+                if law is not None and table is not None:   # a control state stands in place of the static flag and the byte
+                    law["shut"] = np.where(cstate["ctl"] == CTL_NONE, law["shut"], cstate["ctl"] == CTL_CLOSED)
                 if not newton.link_inputs_ok(d, hf, c, r, law):
                     break
+            q_from = q if warm_start else network.q_start
             if with_valves:                                 # a warm series carries the statuses along with the flows
-                rec = valve_record(network, None if settings is None else settings[s], law["shut"],
-                                   valve_status if warm_start else None)
+                v_set = None if settings is None else settings[s]
+                v_status = valve_status if warm_start else None
+                if table is not None:
+                    reopened, again = control_start_ref(cstate, was_shut, t)
+                    q_from = np.where(reopened, network.q_start, q_from)
+                    vl = network.valve_links
+                    v_set = np.where(cstate["has_value"][vl], cstate["value"][vl], network.valve_setting if v_set is None else v_set)
+                    if v_status is not None and t > 0:      # such a valve starts ACTIVE, even in a warm series
+                        v_status = np.where(again[vl], VALVE_ACTIVE, v_status)
+                    was_shut = law["shut"] | (law["pump"] & (law["speed"] == 0))
+                rec = valve_record(network, v_set, law["shut"], v_status)
                 if rec is None:
                     break
                 emit = None
@@ -2240,8 +2507,7 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                     dem = demand_record(network, d, pdd, d_q, d_was_on & bool(warm_start))
                     if dem is None:
                         break
-                H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run_valves(
-                    d, hf, r, q if warm_start else network.q_start, law, rec, emit, dem)
+                H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run_valves(d, hf, r, q_from, law, rec, emit, dem)
             else:
                 H, q_new, iterations[s, t], converged[s, t], ok, rel = newton.run(d, hf, r, q if warm_start else network.q_start, law)
             if not ok:
@@ -2259,12 +2525,17 @@ def simulate_series_ref(network: HydraulicNetwork, demand, roughness, multiplier
                 delivered[s, t] = _delivered(dem, d, fixed)
                 if dem is not None:
                     d_q, d_was_on = dem["q"], dem["on"]
+            if table is not None:
+                control_changes[s, t] = n_changed
             if with_links:
                 state[s, t] = link_state_ref(q, law["pump"], law["check"], law["shut"], law["speed"],
                                              _valve_link_status(network, rec) if with_valves else None)
             lev, clamped = level_update_ref(network, lev, q, step_seconds)
             level[s, t + 1], limited[s, t] = lev, clamped.any()
         converged[s] &= ~failed[s]
+    if table is not None:
+        return HydraulicSeriesControlsReference(head, flow, level, iterations, converged, failed, limited, final_dq, state, changes,
+                                                margin, e_flow, delivered, control_changes)
     if pdd is not None:
         return HydraulicSeriesPddReference(head, flow, level, iterations, converged, failed, limited, final_dq, state, changes,
                                            margin, e_flow, delivered)

@@ -170,7 +170,7 @@ NOMINAL_PUMP_DIAMETER = 1.0             # metres: a pump has no diameter; Hydrau
 
 InpHydraulics = namedtuple("InpHydraulics", "network demand roughness multipliers pattern_of_node pump_speed node_names link_names "
                                             "pattern_names emitter_coefficient demand_model minimum_pressure required_pressure "
-                                            "pressure_exponent", defaults=(None,) * 5)
+                                            "pressure_exponent controls", defaults=(None,) * 5 + ((),))
 
 
 def _inp_sections(source, text) -> "OrderedDict[str, list]":
@@ -201,7 +201,7 @@ def _inp_sections(source, text) -> "OrderedDict[str, list]":
 
 def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported_valves: str = "refuse", ignore_controls: bool = False,
                          device=None, regulating: Optional[str] = None, emitters: Optional[str] = None,
-                         demand_model: Optional[str] = None) -> "InpHydraulics":
+                         demand_model: Optional[str] = None, controls: Optional[str] = None) -> "InpHydraulics":
     """The hydraulic attributes of an EPANET input file as a ``hydraulics.HydraulicNetwork`` and the arrays ``simulate`` and
     ``simulate_series`` take, in SI units.  Read: [JUNCTIONS] (elevation, base demand, pattern), [RESERVOIRS] (head), [TANKS]
     (elevation, initial, minimum and maximum level, diameter), [PIPES] (length, diameter, roughness, minor loss, Open / Closed /
@@ -239,7 +239,18 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
     ``pressure_exponent`` are what ``simulate(demand_model=...)`` takes (THE PRESSURE-DRIVEN DEMAND).  Refused by name: a
     ``DEMAND MODEL`` word other than DDA or PDA, a value that is not finite, an exponent that is not positive and, with PDA, a
     required pressure less than 0.1 m above the minimum pressure.  What is still not read: the demand multiplier, quality,
-    energy, times."""
+    energy, times.
+
+    ``controls="model"`` (default ``None``: [CONTROLS] with content is refused, as it always was, and ``ignore_controls=True`` still
+    drops it) reads the simple controls of [CONTROLS] for ``hydraulics`` (THE CONTROLS): lines of the forms
+    ``LINK id OPEN|CLOSED|<number> IF NODE id ABOVE|BELOW <number>`` and ``LINK id OPEN|CLOSED|<number> AT TIME <hours | H:MM>``,
+    in file order.  A number is a pump's speed or, with ``regulating="model"``, a PRV's or PSV's setting in the file's pressure
+    unit.  The value of a tank is a level in the file's length unit, that of a junction a pressure in the file's pressure unit,
+    converted as for ``regulating``.  The result's ``controls`` is a tuple of what ``hydraulics.control_table`` takes; AT TIME is
+    kept in seconds, as ``(link, action, "at_time", seconds)``, and ``control_table(network, controls, step_seconds)`` turns it into
+    a step, refusing a time that is no whole number of steps.  Refused by name: ``AT CLOCKTIME``, a line of another form, an
+    unknown link or node, a number on a link that takes no setting, and everything ``control_table`` refuses (a control on a CV
+    pipe, a reservoir as the node).  [RULES] with content is still refused."""
     from . import hydraulics as H
     if demand_model not in (None, "model"):
         raise ValueError('demand_model must be None or "model"')
@@ -249,6 +260,8 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
         raise ValueError('unsupported_valves must be "refuse" or "open"')
     if regulating not in (None, "model"):
         raise ValueError('regulating must be None or "model"')
+    if controls not in (None, "model"):
+        raise ValueError('controls must be None or "model"')
     sec = _inp_sections(source, text)
     options = {" ".join(t[:-1]).upper(): t[-1] for t in sec.get("OPTIONS", []) if len(t) >= 2}
     units = options.get("UNITS", "GPM").upper()
@@ -258,15 +271,15 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
     if formula != "H-W":
         raise ValueError(f"[OPTIONS] HEADLOSS {formula}: only the Hazen-Williams formula (H-W) is modelled")
     for name in ("CONTROLS", "RULES"):
-        if sec.get(name) and not ignore_controls:
+        if sec.get(name) and not ignore_controls and not (name == "CONTROLS" and controls == "model"):
             raise ValueError(f"[{name}] has {len(sec[name])} lines: controls and rules are not modelled (ignore_controls=True drops them)")
     flow = FLOW_UNITS[units]
     metre, dia = (1.0, 1e-3) if units in _SI_UNITS else (_FOOT, _FOOT / 12.0)
     num = lambda tok, i, default=0.0: float(tok[i]) if len(tok) > i else default
     pressure_unit = options.get("PRESSURE", "METERS" if units in _SI_UNITS else "PSI").upper()
-    if (regulating or emitters or demand_model) and pressure_unit not in (("METERS", "KPA") if units in _SI_UNITS else ("PSI",)):
+    if (regulating or emitters or demand_model or controls) and pressure_unit not in (("METERS", "KPA") if units in _SI_UNITS else ("PSI",)):
         raise ValueError(f"[OPTIONS] PRESSURE {pressure_unit} does not go with UNITS {units}")
-    pressure = {"METERS": 1.0, "PSI": _FOOT / _PSI_PER_FOOT, "KPA": _FOOT / _PSI_PER_FOOT / _KPA_PER_PSI}[pressure_unit] if (regulating or emitters or demand_model) else 1.0
+    pressure = {"METERS": 1.0, "PSI": _FOOT / _PSI_PER_FOOT, "KPA": _FOOT / _PSI_PER_FOOT / _KPA_PER_PSI}[pressure_unit] if (regulating or emitters or demand_model or controls) else 1.0
 
     # nodes
     names, elevation, demand, pattern_id = [], [], [], []
@@ -436,8 +449,57 @@ def parse_inp_hydraulics(source=None, *, text: Optional[str] = None, unsupported
         pdd = (word.lower(), p_min, p_req, e)
     network = H.HydraulicNetwork(edge_index, length, diameter, elevation, fixed_nodes, fixed_head, device=device, minor_loss=minor,
                                  check_valve=check, closed=closed, link_reversed=ends_a[:, 0] > ends_a[:, 1], **kw)
+    rows = []
+    if controls == "model" and not ignore_controls:
+        for i, t in enumerate(sec.get("CONTROLS", [])):
+            where = f"[CONTROLS] line {i + 1} ({' '.join(t)})"
+            w = [x.upper() for x in t]
+            if "CLOCKTIME" in w:
+                raise ValueError(f"{where}: AT CLOCKTIME is not modelled")
+            timed = len(w) == 6 and w[3] == "AT" and w[4] == "TIME"
+            if not (w and w[0] == "LINK" and (timed or (len(w) == 8 and w[3] == "IF" and w[4] == "NODE" and w[6] in ("ABOVE", "BELOW")))):
+                raise ValueError(f"{where}: not of the form LINK id status IF NODE id ABOVE|BELOW value or LINK id status AT TIME t")
+            if t[1] not in link_index:
+                raise ValueError(f"{where}: no link {t[1]}")
+            p = link_index[t[1]]
+            if w[2] in ("OPEN", "CLOSED"):
+                action = w[2].lower()
+            else:
+                try:
+                    value = float(t[2])
+                except ValueError:
+                    raise ValueError(f"{where}: the status {t[2]} is neither OPEN, CLOSED nor a number") from None
+                if p in pump_links:
+                    action = ("setting", value)
+                elif p in valve_links:
+                    action = ("setting", value * pressure)
+                else:
+                    raise ValueError(f"{where}: link {t[1]} takes no setting")
+            try:
+                if timed:
+                    hms = [float(x) for x in t[5].split(":")]
+                    if len(hms) > 3 or not all(np.isfinite(x) and x >= 0 for x in hms):
+                        raise ValueError
+                    seconds = sum(x * f for x, f in zip(hms, (3600.0, 60.0, 1.0)))
+                    rows.append((p, action, "at_time", seconds))
+                    continue
+                level = float(t[7])
+            except ValueError:
+                raise ValueError(f"{where}: {t[-1]} is no number") from None
+            if t[5] not in index:
+                raise ValueError(f"{where}: no node {t[5]}")
+            n, side = index[t[5]], w[6].lower()
+            if n in tanks:
+                rows.append((p, action, "tank_" + side, tanks.index(n), level * metre))
+            else:
+                rows.append((p, action, "node_" + side, n, level * pressure))
+        for i, row in enumerate(rows):                      # everything control_table refuses, named by the file's line
+            try:
+                H.control_table(network, [row if row[2] != "at_time" else (row[0], row[1], "at_step", 0)])
+            except ValueError as err:
+                raise ValueError(f"[CONTROLS] line {i + 1} ({' '.join(sec['CONTROLS'][i])}): {str(err).split(': ', 1)[-1]}") from None
     return InpHydraulics(network, np.asarray(demand), np.asarray(rough), mult, pattern_of_node, np.asarray(pump_speed, dtype=np.float64),
-                         names, links, ["1 (constant)"] + list(pats), emitter_coefficient, *pdd)
+                         names, links, ["1 (constant)"] + list(pats), emitter_coefficient, *pdd, tuple(rows))
 
 
 # ------------------------------------------------------------------------------------------------------------- blosc

@@ -1425,8 +1425,8 @@ int gatres_hydraulic_valid(const float* pressure, const int32_t* status, const u
  * WHAT DOES NOT HOLD: EPANET shortens a time step at the moment a tank becomes full or empty and closes the pipes of such a
  * tank; this model clamps the level and does neither.  A step after which a level was clamped gets status[s][t][3] = 1, and
  * volume is not conserved across it.  Pumps, check valves, closed links and minor losses are the matter of THE LINK LAW below
- * (gatres_hydraulic_series_links), PRV and PSV valves of THE REGULATING VALVES (gatres_hydraulic_series_valves); controls and
- * rules are not modelled.  The limit on flows that
+ * (gatres_hydraulic_series_links), PRV and PSV valves of THE REGULATING VALVES (gatres_hydraulic_series_valves); simple controls
+ * of THE CONTROLS (gatres_hydraulic_series_controls); rules are not modelled.  The limit on flows that
  * should be zero carries over: a step with a zero multiplier does not meet the stop rule.
  * FAILURE: a step fails on a multiplier of the step (any of the M) that is negative or not finite, a product demand * mult or
  * a tank head that is not finite, a pivot that is not positive and finite or a non-finite sum of the stop rule; a series fails
@@ -1493,7 +1493,7 @@ int gatres_hydraulic_series_valid(const float* pressure, const int32_t* status, 
  * WHAT DOES NOT HOLD: a zone that CHECK or shut links cut off from every fixed-head node gets heads near -1e8 x demand and
  * usually does not meet the stop rule; such scenarios are counted and dropped by the generators, never repaired.
  * PRV and PSV valves are the matter of THE REGULATING VALVES below, which do have one; PBV, FCV and GPV valves, power-rated pumps,
- * controls and rules stay out of scope.  Parity with EPANET is not claimed and has not been checked.
+ * and rule-based controls stay out of scope (simple controls: THE CONTROLS).  Parity with EPANET is not claimed and has not been checked.
  * STATIC link inputs (device): link_kind, link_flags uint8[P]; minor double[P]; pump_link int32[Kp], the link of pump k;
  * pump_h0, pump_r, pump_n double[Kp].  Kp == 0 is legal, the pump arrays and speed may then be NULL.  PER-SCENARIO: speed
  * double, row s at speed + s * speed_stride, speed_stride 0 or Kp; closed uint8 or NULL, row s at closed + s * closed_stride,
@@ -1578,8 +1578,8 @@ int gatres_hydraulic_series_links(const int32_t* pipe_a, const int32_t* pipe_b, 
  * not quadratic.  Statuses can cycle: such a scenario uses all its iterations, is not converged, and is dropped by
  * gatres_hydraulic_valid, never repaired.  An OPEN valve with m = 0 sits on the linear floor (1 / g = 1e7): its flow moves by
  * 1e-7 m3/s per ulp of the heads, as THE MODEL says of every flow on that branch, and whether such a scenario meets the stop rule
- * is decided by rounding; give a valve a loss coefficient where that matters.  Parity with EPANET is not claimed.  FCV, PBV, GPV, power-rated pumps, controls and rules
- * stay out of scope.  The ACTIVE system is singular unless, with all regulating valves removed, the uncontrolled end of every valve
+ * is decided by rounding; give a valve a loss coefficient where that matters.  Parity with EPANET is not claimed.  FCV, PBV, GPV, power-rated pumps and rule-based
+ * controls stay out of scope.  The ACTIVE system is singular unless, with all regulating valves removed, the uncontrolled end of every valve
  * still reaches a fixed-head node and every junction reaches a fixed-head node or the controlled node of some valve; the caller
  * sees to that (hydraulics.HydraulicNetwork refuses other networks), and a scenario that still produces a bad pivot fails.
  * INPUTS after those of the links launches: valve_link int32[Kv], the link of valve k; valve_kind uint8[Kv], GATRES_HYD_PRV or
@@ -1777,6 +1777,88 @@ int gatres_hydraulic_series_pdd(const int32_t* pipe_a, const int32_t* pipe_b, co
                                 double emitter_exponent, const int32_t* emitter_onset, int64_t emitter_onset_stride,
                                 double* emitter_flow, int32_t demand_model, double minimum_pressure, double required_pressure,
                                 double pressure_exponent, double* demand_delivered, void* stream);
+
+/* THE CONTROLS: EPANET's simple controls on pumps, valves and pipes in a series (a symbol only: the ABI stays;
+ * k_hydraulic_network.hip, hydraulics.py).  gatres_hydraulic_series_controls is gatres_hydraulic_series_pdd with a table of
+ * num_controls = Kc >= 0 controls that switch links by a tank level, a junction pressure or the step's number.  [RULES] stay out.
+ * THE TABLE, in an order that matters.  Control k holds
+ *   control_link[k]       int32   the controlled link;
+ *   control_action[k]     uint8   GATRES_HYD_CTL_OPEN 0, GATRES_HYD_CTL_CLOSED 1, GATRES_HYD_CTL_SETTING 2;
+ *   control_value[k]      double  read for SETTING only: on a pump the base speed, in place of speed[s][k'] (the step's
+ *                                 speed-pattern multiplier still multiplies it); on a PRV or PSV the setting in metres, in place of
+ *                                 valve_setting[s][k'];
+ *   control_kind[k]       uint8   GATRES_HYD_CTL_TANK_BELOW 0, TANK_ABOVE 1, NODE_BELOW 2, NODE_ABOVE 3, AT_STEP 4;
+ *   control_target[k]     int32   a tank index in [0, K) for kinds 0 and 1, a junction's node index for kinds 2 and 3, a step
+ *                                 index for kind 4;
+ *   control_threshold     double  [Kc] (control_threshold_stride 0) or [S][Kc] (stride Kc): a level in metres above the tank's
+ *                                 bottom for kinds 0 and 1, a pressure in metres for kinds 2 and 3; not read for kind 4.
+ * EVALUATION, at the start of step t, before the step's inputs are formed (EPANET's place: between the demands and the solve):
+ *   TANK_BELOW  level[t][target] <= threshold;  TANK_ABOVE  >=.  The level the step starts with, so read at t = 0 too.
+ *   NODE_BELOW / NODE_ABOVE  H - elevation in fp64 from the solution of step t - 1, <= / >= threshold; not evaluated at t = 0;
+ *               evaluated whether or not step t - 1 converged.
+ *   AT_STEP     t == target.  A target of T or more never fires.
+ * Every control whose condition holds applies its action, in table order, so within a step the last one wins.  Controls are
+ * level-triggered, as in EPANET: evaluated at every step, not latched on an edge.
+ * STATE.  Each link carries ctl in {none, open, closed} and an override value with a presence flag, reset at the start of every
+ * series and kept from step to step until a control changes them.  OPEN sets ctl = open.  CLOSED sets ctl = closed.  SETTING
+ * stores the override and sets ctl = open (EPANET: a setting control opens the link).  A control that fires has CHANGED its
+ * link when ctl, the presence flag or the bits of the override differ from what they were; control_changes int32 [S][T] counts
+ * these per step (0 where the step failed).
+ * EFFECT ON THE STEP.  A link is shut by input when ctl == closed, or when ctl == none and the static CLOSED flag or the
+ * scenario's closed byte says so; ctl == open overrides both, so a link that starts closed can be opened.  The rule that a pump
+ * with w == 0 is shut stands: a SETTING of 0 switches a pump off, and OPEN gives a pump with base speed 0 no speed.  link_state
+ * stays as defined; state 2 reads "shut by input, by w == 0 or by a control".  A link with ctl != none that was shut in step
+ * t - 1 and is not shut in step t starts step t at q_start[p], warm or cold (a link no control has touched starts as in
+ * gatres_hydraulic_series_pdd, which an empty table therefore gives bit for bit); a link that becomes shut starts at 0.  A
+ * regulating valve with ctl != none starts the step ACTIVE, even in a warm series, when a control changed its link at step t or
+ * when it was shut in step t - 1.
+ * FAILED, every series of the launch: what fails every series of gatres_hydraulic_series_pdd; a control whose link is outside
+ * [0, P), whose action or kind is unknown, whose link is a CHECK pipe that is no pump (EPANET refuses that too); SETTING on a
+ * link that is neither a pump nor a PRV / PSV, with a value that is not finite, or negative on a pump; a tank index outside [0, K);
+ * a node of kinds 2 and 3 outside [0, N) or with a fixed head; a negative target.  That series alone, from step 0 on: a threshold
+ * of a kind 0 .. 3 control that is not finite.
+ * WHAT DOES NOT HOLD.  EPANET shortens a time step so that a level control fires at the moment the level is reached; here levels
+ * are read at step starts, so a level overshoots its threshold by up to |inflow| dt / A.  EPANET's volume tolerance on level
+ * controls is not modelled.  A control that cuts a zone off from every fixed-head node gives a step that does not converge
+ * (gatres_hydraulic_series_valid drops the series, as with the closed bytes).  [RULES] and controls on pipe settings (a TCV's
+ * loss, an FCV's flow and the like) stay out of scope.  Parity with EPANET is not claimed.
+ * LDS need (hydraulics.series_controls_lds_bytes): the bytes of gatres_hydraulic_series_pdd  +  12 P + 16 (per link the override
+ * and the state word; the change counts of the four waves), refused above GATRES_HYD_LDS_BUDGET.
+ * GATRES_E_BADARG before any launch: what gatres_hydraulic_series_pdd refuses; num_controls < 0; with num_controls > 0 a NULL
+ * table array; control_threshold_stride outside {0, Kc}; control_changes NULL; the LDS need above; an output, control_changes
+ * included, overlapping an input or another output.  num_controls == 0 with NULL table arrays is allowed. */
+#define GATRES_HYD_CTL_OPEN 0
+#define GATRES_HYD_CTL_CLOSED 1
+#define GATRES_HYD_CTL_SETTING 2
+#define GATRES_HYD_CTL_TANK_BELOW 0
+#define GATRES_HYD_CTL_TANK_ABOVE 1
+#define GATRES_HYD_CTL_NODE_BELOW 2
+#define GATRES_HYD_CTL_NODE_ABOVE 3
+#define GATRES_HYD_CTL_AT_STEP 4
+int gatres_hydraulic_series_controls(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                                     const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                                     int32_t half_bandwidth, const int32_t* tank_node, const double* tank_area,
+                                     const double* tank_min_level, const double* tank_max_level, int32_t num_tanks,
+                                     const int32_t* pattern_of_node, const double* mult, int64_t mult_stride, int32_t num_patterns,
+                                     const double* demand, const double* roughness, const double* fixed_head,
+                                     int64_t fixed_head_stride, const double* initial_level, int64_t num_series, int32_t num_steps,
+                                     int32_t num_nodes, int32_t num_pipes, double dt, int32_t warm_start, double accuracy,
+                                     int32_t max_iter, float* pressure, double* head, double* flow, double* level, int32_t* status,
+                                     double* final_dq, const uint8_t* link_kind, const uint8_t* link_flags, const double* minor,
+                                     const int32_t* pump_link, const double* pump_h0, const double* pump_r, const double* pump_n,
+                                     int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+                                     int64_t closed_stride, const double* speed_mult, const int32_t* speed_pattern_of_pump,
+                                     int32_t num_speed_patterns, uint8_t* link_state, const int32_t* valve_link,
+                                     const uint8_t* valve_kind, const double* valve_setting, int64_t valve_setting_stride,
+                                     int32_t num_valves, int32_t* valve_changes, const int32_t* emitter_node,
+                                     const double* emitter_coef, int64_t emitter_coef_stride, int32_t num_emitters,
+                                     double emitter_exponent, const int32_t* emitter_onset, int64_t emitter_onset_stride,
+                                     double* emitter_flow, int32_t demand_model, double minimum_pressure, double required_pressure,
+                                     double pressure_exponent, double* demand_delivered, const int32_t* control_link,
+                                     const uint8_t* control_action, const double* control_value, const uint8_t* control_kind,
+                                     const int32_t* control_target, const double* control_threshold,
+                                     int64_t control_threshold_stride, int32_t num_controls, int32_t* control_changes,
+                                     void* stream);
 
 const char* gatres_version(void);
 
