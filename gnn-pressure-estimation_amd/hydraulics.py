@@ -843,6 +843,53 @@ def _reverse_cuthill_mckee(num_nodes: int, pipes: np.ndarray, fixed: np.ndarray)
     return np.array(out[::-1] + [int(v) for v in np.flatnonzero(fixed)], dtype=np.int32)
 
 
+# ---- THE LAUNCH TABLES: a level's entry point and result class.  A level's arguments are those of the level below and one group
+# more, in the order of the C signature: the prefix | the link group (in a series: and the speed-pattern group), link_state | the valve
+# group, valve_changes | the emitter group with emitter_flow | the pdd scalars, demand_delivered | in a series: the control group
+# with control_changes.  The result gains one field per level in the same way.
+PIPES, LINKS, VALVES, EMITTERS, PDD, CONTROLS = range(6)
+STEADY_LAUNCHES = (("gatres_hydraulic_solve", HydraulicResult), ("gatres_hydraulic_solve_links", HydraulicLinksResult),
+                   ("gatres_hydraulic_solve_valves", HydraulicValvesResult), ("gatres_hydraulic_solve_emitters", HydraulicEmittersResult),
+                   ("gatres_hydraulic_solve_pdd", HydraulicPddResult))
+SERIES_LAUNCHES = (("gatres_hydraulic_series", HydraulicSeriesResult), ("gatres_hydraulic_series_links", HydraulicSeriesLinksResult),
+                   ("gatres_hydraulic_series_valves", HydraulicSeriesValvesResult),
+                   ("gatres_hydraulic_series_emitters", HydraulicSeriesEmittersResult),
+                   ("gatres_hydraulic_series_pdd", HydraulicSeriesPddResult),
+                   ("gatres_hydraulic_series_controls", HydraulicSeriesControlsResult))
+
+
+def _launch_level(network, pdd, controls, emitters, valves, links, emitter_arrays, valve_arrays, link_arrays) -> int:
+    """The level of a ``simulate`` / ``simulate_series`` call.  Controls take the controls launch and a demand model the pdd launch;
+    below them ``emitters`` / ``valves`` / ``links`` decide where given, else the network's ``has_*`` flag or one of the level's
+    arrays (``*_arrays``: the call's arguments, None where not given).  A level takes every level below it, and a network with
+    emitters or regulating valves is refused below its own level."""
+    if controls is not None:
+        return CONTROLS
+    if pdd is not None:
+        return PDD
+    given = lambda arrays: any(a is not None for a in arrays)
+    if bool(emitters) if emitters is not None else (network.has_emitters or given(emitter_arrays)):
+        return EMITTERS
+    if network.has_emitters:
+        raise ValueError("a network with emitters takes the emitters launch")
+    if bool(valves) if valves is not None else (network.has_valves or given(valve_arrays)):
+        return VALVES
+    if network.has_valves:
+        raise ValueError("a network with regulating valves takes the valves launch")
+    return LINKS if (bool(links) if links is not None else (network.has_links or given(link_arrays))) else PIPES
+
+
+def _add_level(call, group) -> None:
+    """One level more on ``call`` = (arguments, result extras, held tensors), from ``group`` = (the group's arguments, its output,
+    what the arguments point into): the arguments and the output's pointer (null for an empty one), the output as the result's next
+    field, and the tensors to keep until the launch is queued."""
+    out = group[1]
+    call[0].extend(group[0])
+    call[0].append(out.data_ptr() if out.numel() else None)
+    call[1].append(out)
+    call[2].append(group[2])
+
+
 class HydraulicNetwork:
     """One water network for the steady-state solver.
 
@@ -1113,9 +1160,10 @@ class HydraulicNetwork:
         return self.device
 
     def static(self) -> Dict[str, torch.Tensor]:
-        """The static arrays of ``gatres_hydraulic_solve``, uploaded once."""
+        """The static arrays of every launch, uploaded once: the network's pipes, fixed heads and tanks, its link, pump, valve and
+        emitter arrays, the default pump speed ``speed1`` and the default pattern ``pattern0``.  A launch reads them from here."""
         if not self._static:
-            dev = self._dev()
+            dev, Kp = self._dev(), self.num_pumps
             up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
             self._static = {"pipe_a": up(self.pipes[:, 0], np.int32), "pipe_b": up(self.pipes[:, 1], np.int32),
                             "coef": up(self.coef, np.float64), "q_start": up(self.q_start, np.float64),
@@ -1125,98 +1173,75 @@ class HydraulicNetwork:
                             "junctions": up(self.junctions, np.int64),
                             "tank_node": up(self.tank_nodes, np.int32), "tank_area": up(self.tank_area, np.float64),
                             "tank_min": up(self.tank_min_level, np.float64), "tank_max": up(self.tank_max_level, np.float64),
-                            "pattern0": torch.zeros(self.num_nodes, dtype=torch.int32, device=dev)}
+                            "pattern0": torch.zeros(self.num_nodes, dtype=torch.int32, device=dev),
+                            "link_kind": up(self.link_kind, np.uint8), "link_flags": up(self.link_flags, np.uint8),
+                            "minor": up(self.minor, np.float64), "pump_link": up(self.pump_links, np.int32),
+                            "pump_h0": up(self.pump_h0, np.float64), "pump_r": up(self.pump_r, np.float64),
+                            "pump_n": up(self.pump_n, np.float64), "speed1": torch.ones(max(Kp, 1), dtype=torch.float64, device=dev),
+                            "valve_link": up(self.valve_links, np.int32), "valve_kind": up(self.valve_kind, np.uint8),
+                            "valve_setting": up(self.valve_setting, np.float64), "emitter_node": up(self.emitter_nodes, np.int32)}
         return self._static
 
+    def _per_scenario(self, a, S: int, K: int, name: str, dtype=torch.float64):
+        """An array that is [K] for the whole launch or [S, K] per scenario: the contiguous device tensor and its stride (0 or K),
+        or (None, 0) without one."""
+        if a is None:
+            return None, 0
+        if isinstance(a, np.ndarray) and not a.flags.writeable:
+            a = a.copy()                                    # (torch does not take a read-only array as it is)
+        t = torch.as_tensor(a, dtype=dtype).to(self._dev()).contiguous()
+        if tuple(t.shape) == (K,):
+            return t, 0
+        if tuple(t.shape) == (S, K):
+            return t, K
+        raise ValueError(f"{name} must be [{K}] or [{S}, {K}]")
+
+    # The three argument groups: each returns (the group's arguments before its output, the output tensor to fill, the tensors of
+    # this call that the arguments point into, which the caller holds until the launch is queued) -- what ``_add_level`` takes.
     def _link_args(self, S: int, state_shape, pump_speed, link_closed):
-        """The twelve link arguments of the two links launches (the static arrays are uploaded once), the ``link_state`` tensor
-        to fill, and the tensors of this call that the arguments point into: the caller holds them until the launch is queued."""
+        """The twelve link arguments of the links launches (no pump pointer without pumps) and ``link_state``."""
         st, dev, P, Kp = self.static(), self._dev(), self.num_pipes, self.num_pumps
-        if "link_kind" not in st:
-            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-            st.update({"link_kind": up(self.link_kind, np.uint8), "link_flags": up(self.link_flags, np.uint8),
-                       "minor": up(self.minor, np.float64), "pump_link": up(self.pump_links, np.int32),
-                       "pump_h0": up(self.pump_h0, np.float64), "pump_r": up(self.pump_r, np.float64),
-                       "pump_n": up(self.pump_n, np.float64), "speed1": torch.ones(max(Kp, 1), dtype=torch.float64, device=dev)})
-        if pump_speed is None:
-            speed, speed_stride = st["speed1"], 0
-        else:
-            speed = torch.as_tensor(pump_speed, dtype=torch.float64).to(dev).contiguous()
-            if tuple(speed.shape) == (Kp,):
-                speed_stride = 0
-            elif tuple(speed.shape) == (S, Kp):
-                speed_stride = Kp
-            else:
-                raise ValueError(f"pump_speed must be [{Kp}] or [{S}, {Kp}]")
-        closed, closed_stride = None, 0
-        if link_closed is not None:
-            closed = torch.as_tensor(link_closed).to(device=dev, dtype=torch.uint8).contiguous()
-            if tuple(closed.shape) == (S, P):
-                closed_stride = P
-            elif tuple(closed.shape) != (P,):
-                raise ValueError(f"link_closed must be [{P}] or [{S}, {P}]")
-        link_state = torch.empty(state_shape, dtype=torch.uint8, device=dev)
-        pp = (lambda t: t.data_ptr()) if Kp else (lambda t: None)
-        return [st["link_kind"].data_ptr(), st["link_flags"].data_ptr(), st["minor"].data_ptr(), pp(st["pump_link"]),
-                pp(st["pump_h0"]), pp(st["pump_r"]), pp(st["pump_n"]), Kp, pp(speed), speed_stride, _native.ptr(closed),
-                closed_stride], link_state, (speed, closed)
+        speed, speed_stride = self._per_scenario(pump_speed, S, Kp, "pump_speed")
+        closed, closed_stride = self._per_scenario(link_closed, S, P, "link_closed", torch.uint8)
+        speed = st["speed1"] if speed is None else speed
+        pumps = [t.data_ptr() if Kp else None for t in (st["pump_link"], st["pump_h0"], st["pump_r"], st["pump_n"], speed)]
+        return [st["link_kind"].data_ptr(), st["link_flags"].data_ptr(), st["minor"].data_ptr(), *pumps[:4], Kp, pumps[4],
+                speed_stride, _native.ptr(closed), closed_stride], torch.empty(state_shape, dtype=torch.uint8, device=dev), (speed, closed)
 
     def _valve_args(self, S: int, changes_shape, valve_setting):
-        """The five valve arguments of the two valves launches before ``valve_changes``, that tensor, and the setting tensor of
-        this call, which the caller holds until the launch is queued."""
-        st, dev, Kv = self.static(), self._dev(), self.num_valves
-        if "valve_link" not in st:
-            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-            st.update({"valve_link": up(self.valve_links, np.int32), "valve_kind": up(self.valve_kind, np.uint8),
-                       "valve_setting": up(self.valve_setting, np.float64)})
-        if valve_setting is None:
-            setting, stride = st["valve_setting"], 0
-        else:
-            setting = torch.as_tensor(valve_setting, dtype=torch.float64).to(dev).contiguous()
-            if tuple(setting.shape) == (Kv,):
-                stride = 0
-            elif tuple(setting.shape) == (S, Kv):
-                stride = Kv
-            else:
-                raise ValueError(f"valve_setting must be [{Kv}] or [{S}, {Kv}]")
-        changes = torch.empty(changes_shape, dtype=torch.int32, device=dev)
-        vp = (lambda t: t.data_ptr()) if Kv else (lambda t: None)
-        return [vp(st["valve_link"]), vp(st["valve_kind"]), vp(setting), stride, Kv], changes, setting
+        """The five valve arguments of the valves launches (default: the network's settings) and ``valve_changes``."""
+        st, Kv = self.static(), self.num_valves
+        setting, stride = self._per_scenario(valve_setting, S, Kv, "valve_setting")
+        setting = st["valve_setting"] if setting is None else setting
+        return [t.data_ptr() if Kv else None for t in (st["valve_link"], st["valve_kind"], setting)] + [stride, Kv], \
+            torch.empty(changes_shape, dtype=torch.int32, device=self._dev()), setting
 
     def _emitter_args(self, S: int, flow_shape, emitter_coefficient, emitter_onset=None, series: bool = False):
-        """The emitter arguments of the two emitters launches (``emitter_flow`` included), the ``emitter_flow`` tensor, and the
-        tensors of this call that the arguments point into, which the caller holds until the launch is queued."""
-        st, dev, Ke = self.static(), self._dev(), self.num_emitters
-        if "emitter_node" not in st:
-            st["emitter_node"] = torch.from_numpy(np.ascontiguousarray(self.emitter_nodes, dtype=np.int32)).to(dev)
+        """The emitter arguments of the emitters launches (in a series: with the onsets) and ``emitter_flow`` [*flow_shape, Ke]."""
+        Ke = self.num_emitters
         if Ke and emitter_coefficient is None:
             raise ValueError("a network with emitters needs emitter_coefficient")
-        coef, stride = None, 0
-        if Ke:
-            coef = torch.as_tensor(emitter_coefficient, dtype=torch.float64).to(dev).contiguous()
-            if tuple(coef.shape) == (S, Ke):
-                stride = Ke
-            elif tuple(coef.shape) != (Ke,):
-                raise ValueError(f"emitter_coefficient must be [{Ke}] or [{S}, {Ke}]")
-        elif emitter_coefficient is not None and torch.as_tensor(emitter_coefficient).numel():
+        if not Ke and emitter_coefficient is not None and torch.as_tensor(emitter_coefficient).numel():
             raise ValueError("emitter_coefficient needs a network with emitters")
-        onset, onset_stride = None, 0
-        if emitter_onset is not None:
-            if not series:
-                raise ValueError("emitter_onset belongs to a series")
-            onset = torch.as_tensor(emitter_onset).to(device=dev, dtype=torch.int32).contiguous()
-            if tuple(onset.shape) == (S, Ke):
-                onset_stride = Ke
-            elif tuple(onset.shape) != (Ke,):
-                raise ValueError(f"emitter_onset must be [{Ke}] or [{S}, {Ke}]")
-            if Ke == 0:
-                onset, onset_stride = None, 0
-        flow = torch.empty(tuple(flow_shape) + (Ke,), dtype=torch.float64, device=dev)
-        ep = (lambda t: t.data_ptr()) if Ke else (lambda t: None)
-        args = [ep(st["emitter_node"]), ep(coef), stride, Ke, float(self.emitter_exponent)]
-        if series:
-            args += [_native.ptr(onset), onset_stride]
-        return args + [ep(flow)], flow, (coef, onset)
+        coef, stride = self._per_scenario(emitter_coefficient if Ke else None, S, Ke, "emitter_coefficient")
+        if emitter_onset is not None and not series:
+            raise ValueError("emitter_onset belongs to a series")
+        onset, onset_stride = self._per_scenario(emitter_onset, S, Ke, "emitter_onset", torch.int32)
+        if Ke == 0:
+            onset, onset_stride = None, 0
+        args = [self.static()["emitter_node"].data_ptr() if Ke else None, _native.ptr(coef), stride, Ke, float(self.emitter_exponent)]
+        return args + ([_native.ptr(onset), onset_stride] if series else []), \
+            torch.empty(tuple(flow_shape) + (Ke,), dtype=torch.float64, device=self._dev()), (coef, onset)
+
+    def _launch(self, launches, level: int, args, lead, flags: int, status, final_dq, extras):
+        """THE call of a launch table's row: the entry point with ``args`` and the stream, checked, and the row's result -- ``lead``,
+        the iterations and ``flags`` flag columns of ``status`` (read after the launch, in stream order), ``status``, ``final_dq``
+        and the level's ``extras``."""
+        name, cls = launches[level]
+        rc = getattr(_native.load(), name)(*args, _native.current_stream(self._dev()))
+        _native.check(rc, name)
+        return cls(*lead, status[..., 0], *[status[..., k] != 0 for k in range(1, flags + 1)], status, final_dq, *extras)
+
 
     def _f64(self, a, shape, name) -> torch.Tensor:
         t = torch.as_tensor(a, dtype=torch.float64).to(self._dev()).contiguous()
@@ -1224,17 +1249,40 @@ class HydraulicNetwork:
             raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
         return t
 
+    def _scenarios(self, demand, roughness, none: str):
+        """(demand [S, N], roughness [S, P], S) of a call, on the device; ``none`` is what it says to S = 0."""
+        demand = torch.as_tensor(demand)
+        if demand.dim() != 2:
+            raise ValueError("demand must be [S, N]")
+        S = int(demand.shape[0])
+        if S < 1:
+            raise ValueError(none)
+        return self._f64(demand, (S, self.num_nodes), "demand"), self._f64(roughness, (S, self.num_pipes), "roughness"), S
+
+    def _draw(self, num_scenarios: int, seed: int, first_scenario: int, d_lo, d_hi, x_lo, x_hi, N: int, C: int):
+        """THE ``gatres_hydraulic_draw`` launch: (demand [S, N], cells [S, C]) from the ranges of the N demand and the C other cells."""
+        dev = self._dev()
+        demand = torch.empty((num_scenarios, N), dtype=torch.float64, device=dev)
+        cells = torch.empty((num_scenarios, C), dtype=torch.float64, device=dev)
+        rc = _native.load().gatres_hydraulic_draw(d_lo.data_ptr(), d_hi.data_ptr(), x_lo.data_ptr(), x_hi.data_ptr(), num_scenarios,
+                                                  N, C, seed % (1 << 64), first_scenario, demand.data_ptr(), cells.data_ptr(),
+                                                  _native.current_stream(dev))
+        _native.check(rc, "gatres_hydraulic_draw")
+        return demand, cells
+
+    def _draw_cells(self, cells: torch.Tensor, closed_probability: float):
+        """The cells of a scenario after its demands, split where the blocks begin: (roughness [S, P], pump_speed [S, Kp],
+        link_closed uint8 [S, P], valve_setting [S, Kv]) and the views of the three emitter blocks (coefficient, leak, onset:
+        [S, Ke] each).  A block that was not drawn is empty."""
+        at = np.cumsum([0, self.num_pipes, self.num_pumps, self.num_pipes, self.num_valves] + 3 * [self.num_emitters]).tolist()
+        block = [cells[:, a:b] for a, b in zip(at, at[1:])]
+        closed = (block[2] < float(closed_probability)).to(torch.uint8).contiguous()
+        return (block[0].contiguous(), block[1].contiguous(), closed, block[3].contiguous()), block[4:]
+
     def draw(self, num_scenarios: int, seed: int, first_scenario: int, d_lo: torch.Tensor, d_hi: torch.Tensor, c_lo: torch.Tensor,
              c_hi: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """``gatres_hydraulic_draw``: (demand [S, N], roughness [S, P]) on the device."""
-        dev, lib = self._dev(), _native.load()
-        demand = torch.empty((num_scenarios, self.num_nodes), dtype=torch.float64, device=dev)
-        roughness = torch.empty((num_scenarios, self.num_pipes), dtype=torch.float64, device=dev)
-        rc = lib.gatres_hydraulic_draw(d_lo.data_ptr(), d_hi.data_ptr(), c_lo.data_ptr(), c_hi.data_ptr(), num_scenarios,
-                                       self.num_nodes, self.num_pipes, seed % (1 << 64), first_scenario, demand.data_ptr(),
-                                       roughness.data_ptr(), _native.current_stream(dev))
-        _native.check(rc, "gatres_hydraulic_draw")
-        return demand, roughness
+        return self._draw(num_scenarios, seed, first_scenario, d_lo, d_hi, c_lo, c_hi, self.num_nodes, self.num_pipes)
 
     def draw_links(self, num_scenarios: int, seed: int, first_scenario: int, d_lo: torch.Tensor, d_hi: torch.Tensor,
                    x_lo: torch.Tensor, x_hi: torch.Tensor, closed_probability: float):
@@ -1247,40 +1295,25 @@ class HydraulicNetwork:
                     x_lo: torch.Tensor, x_hi: torch.Tensor, closed_probability: float):
         """``draw_links`` with the valve cells behind the link cells where ``x_lo``, ``x_hi`` hold their ranges (Kv more entries,
         or none): the four arrays of ``draw_links`` and valve_setting [S, Kv] or [S, 0].  ``hydraulic_valve_draws`` restates it."""
-        dev, lib, P, Kp = self._dev(), _native.load(), self.num_pipes, self.num_pumps
-        C = int(x_lo.shape[0])
-        if C not in (2 * P + Kp, 2 * P + Kp + self.num_valves):
+        C, base = int(x_lo.shape[0]), 2 * self.num_pipes + self.num_pumps
+        if C not in (base, base + self.num_valves):
             raise ValueError("the ranges of the link cells do not fit the network")
-        demand = torch.empty((num_scenarios, self.num_nodes), dtype=torch.float64, device=dev)
-        cells = torch.empty((num_scenarios, C), dtype=torch.float64, device=dev)
-        rc = lib.gatres_hydraulic_draw(d_lo.data_ptr(), d_hi.data_ptr(), x_lo.data_ptr(), x_hi.data_ptr(), num_scenarios,
-                                       self.num_nodes, C, seed % (1 << 64), first_scenario, demand.data_ptr(),
-                                       cells.data_ptr(), _native.current_stream(dev))
-        _native.check(rc, "gatres_hydraulic_draw")
-        closed = (cells[:, P + Kp:2 * P + Kp] < float(closed_probability)).to(torch.uint8).contiguous()
-        return (demand, cells[:, :P].contiguous(), cells[:, P:P + Kp].contiguous(), closed, cells[:, 2 * P + Kp:].contiguous())
+        demand, cells = self._draw(num_scenarios, seed, first_scenario, d_lo, d_hi, x_lo, x_hi, self.num_nodes, C)
+        return (demand, *self._draw_cells(cells, closed_probability)[0])
 
     def draw_emitters(self, num_scenarios: int, seed: int, first_scenario: int, d_lo: torch.Tensor, d_hi: torch.Tensor,
                       x_lo: torch.Tensor, x_hi: torch.Tensor, closed_probability: float, leak_probability: float):
         """``draw_valves`` with the emitter cells behind the Kv valve cells (``x_lo``, ``x_hi``: ``emitter_draw_ranges`` on the
         device, 2 Ke or 3 Ke entries more): the five arrays of ``draw_valves``, emitter_coefficient [S, Ke] and emitter_onset
         int32 [S, Ke] or None.  ``hydraulic_emitter_draws`` restates it."""
-        dev, lib, P, Kp, Kv, Ke = self._dev(), _native.load(), self.num_pipes, self.num_pumps, self.num_valves, self.num_emitters
-        C, base = int(x_lo.shape[0]), 2 * P + Kp + Kv
+        Ke = self.num_emitters
+        C, base = int(x_lo.shape[0]), 2 * self.num_pipes + self.num_pumps + self.num_valves
         if C not in (base + 2 * Ke, base + 3 * Ke):
             raise ValueError("the ranges of the emitter cells do not fit the network")
-        demand = torch.empty((num_scenarios, self.num_nodes), dtype=torch.float64, device=dev)
-        cells = torch.empty((num_scenarios, C), dtype=torch.float64, device=dev)
-        rc = lib.gatres_hydraulic_draw(d_lo.data_ptr(), d_hi.data_ptr(), x_lo.data_ptr(), x_hi.data_ptr(), num_scenarios,
-                                       self.num_nodes, C, seed % (1 << 64), first_scenario, demand.data_ptr(),
-                                       cells.data_ptr(), _native.current_stream(dev))
-        _native.check(rc, "gatres_hydraulic_draw")
-        closed = (cells[:, P + Kp:2 * P + Kp] < float(closed_probability)).to(torch.uint8).contiguous()
-        leaks = cells[:, base + Ke:base + 2 * Ke] < float(leak_probability)
-        coef = torch.where(leaks, cells[:, base:base + Ke], torch.zeros((), dtype=torch.float64, device=dev)).contiguous()
-        onset = cells[:, base + 2 * Ke:].floor().to(torch.int32).contiguous() if C == base + 3 * Ke and Ke else None
-        return (demand, cells[:, :P].contiguous(), cells[:, P:P + Kp].contiguous(), closed, cells[:, 2 * P + Kp:base].contiguous(),
-                coef, onset)
+        demand, cells = self._draw(num_scenarios, seed, first_scenario, d_lo, d_hi, x_lo, x_hi, self.num_nodes, C)
+        links, (coef, leak, onset) = self._draw_cells(cells, closed_probability)
+        coef = torch.where(leak < float(leak_probability), coef, torch.zeros((), dtype=torch.float64, device=cells.device)).contiguous()
+        return (demand, *links, coef, onset.floor().to(torch.int32).contiguous() if C == base + 3 * Ke and Ke else None)
 
     def _emitter_draw_setup(self, ranges, pump_speed_range, closed_probability, valve_setting_range, emitter_coefficient_range,
                             leak_probability, leak_onset_range=None):
@@ -1294,27 +1327,26 @@ class HydraulicNetwork:
             raise ValueError("emitter_coefficient_range needs a network with emitters")
         if not 0.0 <= float(leak_probability) <= 1.0:
             raise ValueError("leak_probability must lie in [0, 1]")
+        self._check_link_draws(pump_speed_range, closed_probability, valve_setting_range)
+        lo, hi = emitter_draw_ranges(ranges[2], ranges[3], self.num_pumps, self.num_valves, self.num_emitters,
+                                     emitter_coefficient_range, leak_onset_range, pump_speed_range, valve_setting_range)
+        return torch.from_numpy(lo).to(self._dev()), torch.from_numpy(hi).to(self._dev())
+
+    def _check_link_draws(self, pump_speed_range, closed_probability, valve_setting_range) -> None:
+        """What both draw setups refuse of the link and valve draws."""
+        if valve_setting_range is not None and self.num_valves == 0:
+            raise ValueError("valve_setting_range needs a network with regulating valves")
         if not 0.0 <= float(closed_probability) < 1.0:
             raise ValueError("closed_probability must lie in [0, 1)")
         if pump_speed_range is not None and self.num_pumps == 0:
             raise ValueError("pump_speed_range needs a network with pumps")
-        if valve_setting_range is not None and self.num_valves == 0:
-            raise ValueError("valve_setting_range needs a network with regulating valves")
-        lo, hi = emitter_draw_ranges(ranges[2], ranges[3], self.num_pumps, self.num_valves, self.num_emitters,
-                                     emitter_coefficient_range, leak_onset_range, pump_speed_range, valve_setting_range)
-        return torch.from_numpy(lo).to(self._dev()), torch.from_numpy(hi).to(self._dev())
 
     def _link_draw_setup(self, ranges, pump_speed_range, closed_probability, valve_setting_range=None):
         """None where a store is generated without link draws (the call it always was), else the device ranges of ``draw_links``
         (of ``draw_valves``: with ``valve_setting_range`` the Kv valve cells come after all the others)."""
         if pump_speed_range is None and not closed_probability and valve_setting_range is None:
             return None
-        if valve_setting_range is not None and self.num_valves == 0:
-            raise ValueError("valve_setting_range needs a network with regulating valves")
-        if not 0.0 <= float(closed_probability) < 1.0:
-            raise ValueError("closed_probability must lie in [0, 1)")
-        if pump_speed_range is not None and self.num_pumps == 0:
-            raise ValueError("pump_speed_range needs a network with pumps")
+        self._check_link_draws(pump_speed_range, closed_probability, valve_setting_range)
         lo, hi = link_draw_ranges(ranges[2], ranges[3], self.num_pumps, pump_speed_range)
         if valve_setting_range is not None:
             v_lo, v_hi = float(valve_setting_range[0]), float(valve_setting_range[1])
@@ -1343,84 +1375,35 @@ class HydraulicNetwork:
         ``pressure_exponent``, and returns a ``HydraulicPddResult``: the emitters fields and ``demand_delivered`` fp64 [S, N];
         ``demand_model="dda"`` takes the same launch demand-driven (every bit of the emitters launch, and the demand itself as
         ``demand_delivered``).  Without ``demand_model`` the call takes exactly the launches it always took."""
-        st, dev, lib = self.static(), self._dev(), _native.load()
+        st, dev, N, P = self.static(), self._dev(), self.num_nodes, self.num_pipes
         pdd = pdd_arguments(demand_model, minimum_pressure, required_pressure, pressure_exponent)
-        if pdd is not None:
-            emitters = True
-        with_emitters = bool(emitters) if emitters is not None else (self.has_emitters or emitter_coefficient is not None)
-        if self.has_emitters and not with_emitters:
-            raise ValueError("a network with emitters takes the emitters launch")
-        if with_emitters:
-            valves = True
-        with_valves = bool(valves) if valves is not None else (self.has_valves or valve_setting is not None)
-        if self.has_valves and not with_valves:
-            raise ValueError("a network with regulating valves takes the valves launch")
-        with_links = with_valves or (bool(links) if links is not None else
-                                     (self.has_links or pump_speed is not None or link_closed is not None))
-        N, P = self.num_nodes, self.num_pipes
-        demand = torch.as_tensor(demand)
-        if demand.dim() != 2:
-            raise ValueError("demand must be [S, N]")
-        S = int(demand.shape[0])
-        if S < 1:
-            raise ValueError("no scenarios")
-        demand = self._f64(demand, (S, N), "demand")
-        roughness = self._f64(roughness, (S, P), "roughness")
-        if fixed_head is None:
-            fh, stride = st["fixed_head"], 0
-        else:
-            fh = torch.as_tensor(fixed_head, dtype=torch.float64).to(dev).contiguous()
-            if tuple(fh.shape) == (N,):
-                stride = 0
-            elif tuple(fh.shape) == (S, N):
-                stride = N
-            else:
-                raise ValueError(f"fixed_head must be [{N}] or [{S}, {N}]")
-        pressure = torch.empty((S, N), dtype=torch.float32, device=dev)
-        head = torch.empty((S, N), dtype=torch.float64, device=dev) if want_head else None
-        flow = torch.empty((S, P), dtype=torch.float64, device=dev) if want_flow else None
-        status = torch.empty((S, HYD_STATUS), dtype=torch.int32, device=dev)
-        final_dq = torch.empty((S,), dtype=torch.float64, device=dev)
+        level = _launch_level(self, pdd, None, emitters, valves, links, (emitter_coefficient,), (valve_setting,),
+                              (pump_speed, link_closed))
+        demand, roughness, S = self._scenarios(demand, roughness, "no scenarios")
+        fh, stride = self._per_scenario(fixed_head, S, N, "fixed_head")
+        fh = st["fixed_head"] if fh is None else fh
+        new = lambda shape, dtype=torch.float64: torch.empty(shape, dtype=dtype, device=dev)
+        pressure, status, final_dq = new((S, N), torch.float32), new((S, HYD_STATUS), torch.int32), new((S,))
+        head, flow = new((S, N)) if want_head else None, new((S, P)) if want_flow else None
         # the 23 arguments every steady entry point begins with
-        prefix = (st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
-                  st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
-                  self.half_bandwidth, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P, float(accuracy),
-                  int(max_iter), pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), status.data_ptr(), final_dq.data_ptr())
-        if with_valves:
-            link_args, link_state, _held = self._link_args(S, (S, P), pump_speed, link_closed)
-            valve_args, changes, _held_v = self._valve_args(S, (S,), valve_setting)
-            if with_emitters:
-                emitter_args, emitter_flow, _held_e = self._emitter_args(S, (S,), emitter_coefficient)
-                if pdd is not None:
-                    need = pdd_lds_bytes(N, P, self.half_bandwidth, self.num_pumps, self.num_valves, self.num_emitters, pdd[0])
-                    if need > LDS_BUDGET:
-                        raise ValueError(f"the band of {N} rows with half-bandwidth {self.half_bandwidth} needs {need} bytes of LDS "
-                                         f"with this demand model, the kernel has {LDS_BUDGET}")
-                    delivered = torch.empty((S, N), dtype=torch.float64, device=dev)
-                    rc = lib.gatres_hydraulic_solve_pdd(*prefix, *link_args, link_state.data_ptr(), *valve_args, changes.data_ptr(),
-                                                        *emitter_args, *pdd, delivered.data_ptr(), _native.current_stream(dev))
-                    _native.check(rc, "gatres_hydraulic_solve_pdd")
-                    return HydraulicPddResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status,
-                                              final_dq, link_state, changes, emitter_flow, delivered)
-                rc = lib.gatres_hydraulic_solve_emitters(*prefix, *link_args, link_state.data_ptr(), *valve_args, changes.data_ptr(),
-                                                         *emitter_args, _native.current_stream(dev))
-                _native.check(rc, "gatres_hydraulic_solve_emitters")
-                return HydraulicEmittersResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status,
-                                               final_dq, link_state, changes, emitter_flow)
-            rc = lib.gatres_hydraulic_solve_valves(*prefix, *link_args, link_state.data_ptr(), *valve_args, changes.data_ptr(),
-                                                   _native.current_stream(dev))
-            _native.check(rc, "gatres_hydraulic_solve_valves")
-            return HydraulicValvesResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status, final_dq,
-                                         link_state, changes)
-        if with_links:
-            link_args, link_state, _held = self._link_args(S, (S, P), pump_speed, link_closed)
-            rc = lib.gatres_hydraulic_solve_links(*prefix, *link_args, link_state.data_ptr(), _native.current_stream(dev))
-            _native.check(rc, "gatres_hydraulic_solve_links")
-            return HydraulicLinksResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status, final_dq,
-                                        link_state)
-        rc = lib.gatres_hydraulic_solve(*prefix, _native.current_stream(dev))
-        _native.check(rc, "gatres_hydraulic_solve")
-        return HydraulicResult(pressure, head, flow, status[:, 0], status[:, 1] != 0, status[:, 2] != 0, status, final_dq)
+        args = [st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
+                st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
+                self.half_bandwidth, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P, float(accuracy),
+                int(max_iter), pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), status.data_ptr(), final_dq.data_ptr()]
+        call = (args, [], [])
+        if level >= LINKS:
+            _add_level(call, self._link_args(S, (S, P), pump_speed, link_closed))
+        if level >= VALVES:
+            _add_level(call, self._valve_args(S, (S,), valve_setting))
+        if level >= EMITTERS:
+            _add_level(call, self._emitter_args(S, (S,), emitter_coefficient))
+        if level >= PDD:
+            need = pdd_lds_bytes(N, P, self.half_bandwidth, self.num_pumps, self.num_valves, self.num_emitters, pdd[0])
+            if need > LDS_BUDGET:
+                raise ValueError(f"the band of {N} rows with half-bandwidth {self.half_bandwidth} needs {need} bytes of LDS "
+                                 f"with this demand model, the kernel has {LDS_BUDGET}")
+            _add_level(call, (pdd, new((S, N)), None))
+        return self._launch(STEADY_LAUNCHES, level, args, (pressure, head, flow), 2, status, final_dq, call[1])
 
     def valid(self, result: HydraulicResult, pressure_range: Tuple[float, float]) -> torch.Tensor:
         """``gatres_hydraulic_valid``: uint8 [S], 1 where the scenario converged, did not fail and every junction pressure lies
@@ -1468,34 +1451,15 @@ class HydraulicNetwork:
         the pdd launch (demand-driven unless ``demand_model="pda"``) with the table evaluated at the start of every step, and a
         ``HydraulicSeriesControlsResult`` with ``control_changes`` int32 [S, T]; ``control_threshold`` [Kc] or [S, Kc] overrides the
         table's thresholds.  With ``controls=None`` nothing changes."""
-        st, dev, lib = self.static(), self._dev(), _native.load()
+        st, dev, N, P, K, Kp = self.static(), self._dev(), self.num_nodes, self.num_pipes, self.num_tanks, self.num_pumps
         pdd = pdd_arguments(demand_model, minimum_pressure, required_pressure, pressure_exponent)
         if controls is None and control_threshold is not None:
             raise ValueError("control_threshold needs controls")
         if controls is not None and pdd is None:
             pdd = (0, 0.0, 0.0, PRESSURE_EXPONENT)
-        if pdd is not None:
-            emitters = True
-        with_emitters = bool(emitters) if emitters is not None else (
-            self.has_emitters or emitter_coefficient is not None or emitter_onset is not None)
-        if self.has_emitters and not with_emitters:
-            raise ValueError("a network with emitters takes the emitters launch")
-        if with_emitters:
-            valves = True
-        with_valves = bool(valves) if valves is not None else (self.has_valves or valve_setting is not None)
-        if self.has_valves and not with_valves:
-            raise ValueError("a network with regulating valves takes the valves launch")
-        with_links = with_valves or (bool(links) if links is not None else (
-            self.has_links or any(v is not None for v in (pump_speed, link_closed, speed_multipliers, speed_pattern_of_pump))))
-        N, P, K = self.num_nodes, self.num_pipes, self.num_tanks
-        demand = torch.as_tensor(demand)
-        if demand.dim() != 2:
-            raise ValueError("demand must be [S, N]")
-        S = int(demand.shape[0])
-        if S < 1:
-            raise ValueError("no series")
-        demand = self._f64(demand, (S, N), "demand")
-        roughness = self._f64(roughness, (S, P), "roughness")
+        level = _launch_level(self, pdd, controls, emitters, valves, links, (emitter_coefficient, emitter_onset), (valve_setting,),
+                              (pump_speed, link_closed, speed_multipliers, speed_pattern_of_pump))
+        demand, roughness, S = self._scenarios(demand, roughness, "no series")
         mult = torch.as_tensor(multipliers, dtype=torch.float64).to(dev).contiguous()
         if mult.dim() == 2 and mult.shape[0] >= 1 and mult.shape[1] >= 1:
             M, T, mult_stride = int(mult.shape[0]), int(mult.shape[1]), 0
@@ -1504,9 +1468,8 @@ class HydraulicNetwork:
             mult_stride = M * T
         else:
             raise ValueError(f"multipliers must be [M, T] or [{S}, M, T]")
-        if pattern_of_node is None:
-            pattern = st["pattern0"]
-        else:
+        pattern = st["pattern0"]
+        if pattern_of_node is not None:
             on_device = isinstance(pattern_of_node, torch.Tensor) and pattern_of_node.is_cuda
             pattern = torch.as_tensor(pattern_of_node)
             if tuple(pattern.shape) != (N,):
@@ -1514,47 +1477,29 @@ class HydraulicNetwork:
             if not on_device and (int(pattern.min()) < 0 or int(pattern.max()) >= M):      # (host data: no read-back)
                 raise ValueError(f"pattern_of_node must hold values in [0, {M})")
             pattern = pattern.to(device=dev, dtype=torch.int32).contiguous()
-        if fixed_head is None:
-            fh, stride = st["fixed_head"], 0
-        else:
-            fh = torch.as_tensor(fixed_head, dtype=torch.float64).to(dev).contiguous()
-            if tuple(fh.shape) == (N,):
-                stride = 0
-            elif tuple(fh.shape) == (S, N):
-                stride = N
-            else:
-                raise ValueError(f"fixed_head must be [{N}] or [{S}, {N}]")
-        if initial_level is None:
-            elev = st["elevation"].index_select(0, st["tank_node"].to(torch.int64))
-            level0 = (fh.reshape(-1, N).index_select(1, st["tank_node"].to(torch.int64)) - elev[None, :]).expand(S, K).contiguous()
-        else:
-            if isinstance(initial_level, np.ndarray):
-                initial_level = np.array(initial_level, dtype=np.float64)                     # (a copy: the array may be read-only)
-            level0 = torch.as_tensor(initial_level, dtype=torch.float64).to(dev)
-            if tuple(level0.shape) == (K,):
-                level0 = level0[None, :].expand(S, K)
-            if tuple(level0.shape) != (S, K):
-                raise ValueError(f"initial_level must be [{K}] or [{S}, {K}]")
-            level0 = level0.contiguous()
+        fh, stride = self._per_scenario(fixed_head, S, N, "fixed_head")
+        fh = st["fixed_head"] if fh is None else fh
+        level0, _ = self._per_scenario(initial_level, S, K, "initial_level")
+        if level0 is None:
+            tanks = st["tank_node"].to(torch.int64)
+            level0 = fh.reshape(-1, N).index_select(1, tanks) - st["elevation"].index_select(0, tanks)[None, :]
+        level0 = (level0[None, :] if level0.dim() == 1 else level0).expand(S, K).contiguous()      # (the launch takes [S, K])
         if not (float(step_seconds) > 0.0 and np.isfinite(float(step_seconds))):
             raise ValueError("step_seconds must be positive and finite")
-        pressure = torch.empty((S, T, N), dtype=torch.float32, device=dev)
-        head = torch.empty((S, T, N), dtype=torch.float64, device=dev) if want_head else None
-        flow = torch.empty((S, T, P), dtype=torch.float64, device=dev) if want_flow else None
-        level = torch.empty((S, T + 1, K), dtype=torch.float64, device=dev)
-        status = torch.empty((S, T, HYD_STATUS), dtype=torch.int32, device=dev)
-        final_dq = torch.empty((S, T), dtype=torch.float64, device=dev)
+        new = lambda shape, dtype=torch.float64: torch.empty(shape, dtype=dtype, device=dev)
+        pressure, status, final_dq = new((S, T, N), torch.float32), new((S, T, HYD_STATUS), torch.int32), new((S, T))
+        head, flow, tank_level = new((S, T, N)) if want_head else None, new((S, T, P)) if want_flow else None, new((S, T + 1, K))
         tp = (lambda t: t.data_ptr()) if K else (lambda t: None)
         # the 37 arguments every series entry point begins with
-        prefix = (st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
-                  st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
-                  self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
-                  pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride,
-                  tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0, float(accuracy), int(max_iter),
-                  pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(level), status.data_ptr(), final_dq.data_ptr())
-        if with_links:
-            Kp = self.num_pumps
-            link_args, link_state, _held = self._link_args(S, (S, T, P), pump_speed, link_closed)
+        args = [st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
+                st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
+                self.half_bandwidth, tp(st["tank_node"]), tp(st["tank_area"]), tp(st["tank_min"]), tp(st["tank_max"]), K,
+                pattern.data_ptr(), mult.data_ptr(), mult_stride, M, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride,
+                tp(level0), S, T, N, P, float(step_seconds), 1 if warm_start else 0, float(accuracy), int(max_iter),
+                pressure.data_ptr(), _native.ptr(head), _native.ptr(flow), tp(tank_level), status.data_ptr(), final_dq.data_ptr()]
+        call = (args, [], [])
+        if level >= LINKS:
+            link_args, link_state, held = self._link_args(S, (S, T, P), pump_speed, link_closed)
             smult = torch.ones((1, T), dtype=torch.float64, device=dev) if speed_multipliers is None else \
                 torch.as_tensor(speed_multipliers, dtype=torch.float64).to(dev).contiguous()
             if smult.dim() != 2 or smult.shape[0] < 1 or smult.shape[1] != T:
@@ -1563,64 +1508,28 @@ class HydraulicNetwork:
             if spat.shape != (Kp,) or (Kp and (spat.min() < 0 or spat.max() >= smult.shape[0])):
                 raise ValueError(f"speed_pattern_of_pump must be [{Kp}] with values in [0, {int(smult.shape[0])})")
             spat = torch.from_numpy(spat.astype(np.int32)).to(dev)
-            speed_args = (smult.data_ptr(), spat.data_ptr(), int(smult.shape[0])) if Kp else (None, None, 0)
-            if with_valves:
-                need = series_pdd_lds_bytes(N, P, self.half_bandwidth, K, Kp, self.num_valves, self.num_emitters,
-                                            0 if pdd is None else pdd[0]) + (0 if controls is None else 12 * P + 16)
-                if need > LDS_BUDGET:                       # (the constructor held a network without tanks to the steady launch's sum)
-                    raise ValueError(f"a series on the band of {N} rows with half-bandwidth {self.half_bandwidth} needs {need} bytes "
-                                     f"of LDS, the kernel has {LDS_BUDGET}")
-                valve_args, changes, _held_v = self._valve_args(S, (S, T), valve_setting)
-                if with_emitters:
-                    emitter_args, emitter_flow, _held_e = self._emitter_args(S, (S, T), emitter_coefficient, emitter_onset, True)
-                    if controls is not None:
-                        table, thr = _control_inputs(self, controls, control_threshold, S, step_seconds)
-                        Kc = len(table)
-                        up = lambda a: torch.from_numpy(np.array(a)).to(dev)       # (a copy: a broadcast view is read-only)
-                        held = [up(a) for a in (table.link, table.action, table.value, table.kind, table.target)]
-                        held.append(up(thr if thr.strides[0] else thr[0]))      # ([Kc] where every series has the table's)
-                        cp = (lambda t: t.data_ptr()) if Kc else (lambda t: None)
-                        control_changes = torch.empty((S, T), dtype=torch.int32, device=dev)
-                        delivered = torch.empty((S, T, N), dtype=torch.float64, device=dev)
-                        rc = lib.gatres_hydraulic_series_controls(
-                            *prefix, *link_args, *speed_args, link_state.data_ptr(), *valve_args,
-                            changes.data_ptr(), *emitter_args, *pdd, delivered.data_ptr(), *[cp(t) for t in held],
-                            Kc if held[5].dim() == 2 else 0, Kc, control_changes.data_ptr(), _native.current_stream(dev))
-                        _native.check(rc, "gatres_hydraulic_series_controls")
-                        return HydraulicSeriesControlsResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
-                                                             status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq,
-                                                             link_state, changes, emitter_flow, delivered, control_changes)
-                    if pdd is not None:
-                        delivered = torch.empty((S, T, N), dtype=torch.float64, device=dev)
-                        rc = lib.gatres_hydraulic_series_pdd(
-                            *prefix, *link_args, *speed_args, link_state.data_ptr(), *valve_args,
-                            changes.data_ptr(), *emitter_args, *pdd, delivered.data_ptr(), _native.current_stream(dev))
-                        _native.check(rc, "gatres_hydraulic_series_pdd")
-                        return HydraulicSeriesPddResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
-                                                        status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq, link_state,
-                                                        changes, emitter_flow, delivered)
-                    rc = lib.gatres_hydraulic_series_emitters(
-                        *prefix, *link_args, *speed_args, link_state.data_ptr(), *valve_args,
-                        changes.data_ptr(), *emitter_args, _native.current_stream(dev))
-                    _native.check(rc, "gatres_hydraulic_series_emitters")
-                    return HydraulicSeriesEmittersResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
-                                                         status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq, link_state,
-                                                         changes, emitter_flow)
-                rc = lib.gatres_hydraulic_series_valves(
-                    *prefix, *link_args, *speed_args, link_state.data_ptr(), *valve_args, changes.data_ptr(),
-                    _native.current_stream(dev))
-                _native.check(rc, "gatres_hydraulic_series_valves")
-                return HydraulicSeriesValvesResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0,
-                                                   status[:, :, 2] != 0, status[:, :, 3] != 0, status, final_dq, link_state, changes)
-            rc = lib.gatres_hydraulic_series_links(
-                *prefix, *link_args, *speed_args, link_state.data_ptr(), _native.current_stream(dev))
-            _native.check(rc, "gatres_hydraulic_series_links")
-            return HydraulicSeriesLinksResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0, status[:, :, 2] != 0,
-                                              status[:, :, 3] != 0, status, final_dq, link_state)
-        rc = lib.gatres_hydraulic_series(*prefix, _native.current_stream(dev))
-        _native.check(rc, "gatres_hydraulic_series")
-        return HydraulicSeriesResult(pressure, head, flow, level, status[:, :, 0], status[:, :, 1] != 0, status[:, :, 2] != 0,
-                                     status[:, :, 3] != 0, status, final_dq)
+            speed_args = [smult.data_ptr(), spat.data_ptr(), int(smult.shape[0])] if Kp else [None, None, 0]
+            _add_level(call, (link_args + speed_args, link_state, (held, smult, spat)))
+        if level >= VALVES:
+            need = series_pdd_lds_bytes(N, P, self.half_bandwidth, K, Kp, self.num_valves, self.num_emitters,
+                                        0 if pdd is None else pdd[0]) + (0 if controls is None else 12 * P + 16)
+            if need > LDS_BUDGET:                           # (the constructor held a network without tanks to the steady launch's sum)
+                raise ValueError(f"a series on the band of {N} rows with half-bandwidth {self.half_bandwidth} needs {need} bytes "
+                                 f"of LDS, the kernel has {LDS_BUDGET}")
+            _add_level(call, self._valve_args(S, (S, T), valve_setting))
+        if level >= EMITTERS:
+            _add_level(call, self._emitter_args(S, (S, T), emitter_coefficient, emitter_onset, True))
+        if level >= PDD:
+            _add_level(call, (pdd, new((S, T, N)), None))
+        if level >= CONTROLS:
+            table = controls if isinstance(controls, ControlTable) else control_table(self, controls, step_seconds)
+            Kc = len(table)
+            thr, thr_stride = self._per_scenario(table.threshold if control_threshold is None else control_threshold, S, Kc,
+                                                 "control_threshold")
+            up = lambda a: torch.from_numpy(np.array(a)).to(dev)
+            held = [up(a) for a in (table.link, table.action, table.value, table.kind, table.target)] + [thr]
+            _add_level(call, ([t.data_ptr() if Kc else None for t in held] + [thr_stride, Kc], new((S, T), torch.int32), held))
+        return self._launch(SERIES_LAUNCHES, level, args, (pressure, head, flow, tank_level), 3, status, final_dq, call[1])
 
     def series_valid(self, result: HydraulicSeriesResult, pressure_range: Tuple[float, float], allow_limited: bool = False) -> torch.Tensor:
         """``gatres_hydraulic_series_valid``: uint8 [S], 1 where every step of the series converged and none failed, no level
@@ -1646,17 +1555,61 @@ class HydraulicNetwork:
     def draw_levels(self, num_series: int, seed: int, first_series: int, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
         """Initial levels [S, K]: ``gatres_hydraulic_draw`` once more, with N := K and P := 1 and the seed
         ``seed + LEVEL_SEED_OFFSET`` (mod 2^64); ``hydraulic_draws`` restates it."""
-        dev, lib, K = self._dev(), _native.load(), self.num_tanks
-        level = torch.empty((num_series, K), dtype=torch.float64, device=dev)
-        if K == 0:
-            return level
-        unit = torch.zeros(2, dtype=torch.float64, device=dev)
-        spare = torch.empty((num_series, 1), dtype=torch.float64, device=dev)
-        rc = lib.gatres_hydraulic_draw(lo.data_ptr(), hi.data_ptr(), unit[:1].data_ptr(), unit[1:].data_ptr(), num_series, K, 1,
-                                       (seed + LEVEL_SEED_OFFSET) % (1 << 64), first_series, level.data_ptr(), spare.data_ptr(),
-                                       _native.current_stream(dev))
-        _native.check(rc, "gatres_hydraulic_draw")
-        return level
+        if self.num_tanks == 0:
+            return torch.empty((num_series, 0), dtype=torch.float64, device=self._dev())
+        unit = torch.zeros(2, dtype=torch.float64, device=self._dev())
+        return self._draw(num_series, seed + LEVEL_SEED_OFFSET, first_series, lo, hi, unit[:1], unit[1:], self.num_tanks, 1)[0]
+
+    def _chunk_draws(self, seed: int, demand_range, roughness_range, pump_speed_range, closed_probability, valve_setting_range,
+                     emitter_coefficient_range, leak_probability, leak_onset_range=None):
+        """The draw of a store generator's chunk: ``draw(n, first)`` -> (demand, roughness, the keyword arguments that hand the
+        drawn link, valve and emitter arrays to ``simulate`` / ``simulate_series``, the leak labels (coefficient, onset) or None).
+        With emitter draws ``draw_emitters``, with link or valve draws ``draw_valves``, else ``draw``: the cells a call always drew."""
+        host_ranges = self.draw_ranges(demand_range, roughness_range)
+        ranges = [torch.from_numpy(a).to(self._dev()) for a in host_ranges]
+        leak_ranges = self._emitter_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range,
+                                               emitter_coefficient_range, leak_probability, leak_onset_range)
+        if leak_ranges is None and self.has_emitters:
+            raise ValueError("a network with emitters needs emitter_coefficient_range")
+        link_ranges = None if leak_ranges is not None else \
+            self._link_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range)
+
+        def draw(n: int, first: int):
+            if leak_ranges is None and link_ranges is None:
+                return (*self.draw(n, seed, first, *ranges), {}, None)
+            kw, labels = {}, None
+            if leak_ranges is not None:
+                demand, roughness, speed, closed, setting, coef, onset = self.draw_emitters(
+                    n, seed, first, ranges[0], ranges[1], *leak_ranges, closed_probability, leak_probability)
+                kw, labels = {"emitter_coefficient": coef, **({} if onset is None else {"emitter_onset": onset})}, (coef, onset)
+            else:
+                demand, roughness, speed, closed, setting = self.draw_valves(n, seed, first, ranges[0], ranges[1], *link_ranges,
+                                                                             closed_probability)
+            kw.update(pump_speed=speed if self.num_pumps else None, link_closed=closed)
+            if valve_setting_range is not None:
+                kw["valve_setting"] = setting
+            return demand, roughness, kw, labels
+        return draw
+
+    def _finish_store(self, kept_rows, leak_rows, supply_rows, report, normalize: bool):
+        """(store, report) of a generator: the kept rows as a ``SnapshotStore`` over the junctions, and the labels of the kept rows
+        as ``report["leak"]`` (coefficient, flow, and onset where it was drawn) and ``report["supply"]`` (delivered, full)."""
+        if leak_rows:
+            coef, flow, onset = [None if rows[0] is None else torch.cat(rows, dim=0) for rows in zip(*leak_rows)]
+            report["leak"] = {"coefficient": coef, "flow": flow, **({} if onset is None else {"onset": onset})}
+        if supply_rows:
+            delivered, full = [torch.cat(rows, dim=0) for rows in zip(*supply_rows)]
+            report["supply"] = {"delivered": delivered, "full": full}
+        return SnapshotStore(torch.cat(kept_rows, dim=0), self.junction_edge_index, device=self._dev(), normalize=normalize), report
+
+    @staticmethod
+    def _keep_labels(idx, res, labels, full, leak_rows, supply_rows) -> None:
+        """The labels of a chunk's kept rows ``idx``: the drawn leaks and their flows, the delivered and the ``full`` demand."""
+        if labels is not None:
+            leak_rows.append((labels[0].index_select(0, idx), res.emitter_flow.index_select(0, idx),
+                              None if labels[1] is None else labels[1].index_select(0, idx)))
+        if full is not None:
+            supply_rows.append((res.demand_delivered.index_select(0, idx), full))
 
     def generate_series_store(self, num_series: int, steps: int, seed: int, *, step_seconds: float = 300.0, multipliers=None,
                               pattern_of_node=None, level_range=None, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE,
@@ -1697,40 +1650,19 @@ class HydraulicNetwork:
         mult = torch.as_tensor(multipliers, dtype=torch.float64).to(dev).contiguous()
         if mult.dim() != 2 or mult.shape[1] != steps:
             raise ValueError(f"multipliers must be [M, {steps}]")
-        host_ranges = self.draw_ranges(demand_range, roughness_range)
-        ranges = [torch.from_numpy(a).to(dev) for a in host_ranges]
-        leak_ranges = self._emitter_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range,
-                                               emitter_coefficient_range, leak_probability, leak_onset_range)
-        if leak_ranges is None and self.has_emitters:
-            raise ValueError("a network with emitters needs emitter_coefficient_range")
-        link_ranges = None if leak_ranges is not None else \
-            self._link_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range)
-        leak_rows = []
+        draw = self._chunk_draws(seed, demand_range, roughness_range, pump_speed_range, closed_probability, valve_setting_range,
+                                 emitter_coefficient_range, leak_probability, leak_onset_range)
         link_kw = {k: v for k, v in (("speed_multipliers", speed_multipliers), ("speed_pattern_of_pump", speed_pattern_of_pump))
                    if v is not None}
         lv = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in self.level_ranges(level_range)]
-        kept_rows, tables = [], []
+        kept_rows, leak_rows, tables = [], [], []
         for first in range(0, num_series, chunk):
             n = min(chunk, num_series - first)
-            if leak_ranges is not None:
-                demand, roughness, speed, closed, setting, leak_c, leak_t = self.draw_emitters(
-                    n, seed, first, ranges[0], ranges[1], *leak_ranges, closed_probability, leak_probability)
-                link_kw.update(pump_speed=speed if self.num_pumps else None, link_closed=closed, emitter_coefficient=leak_c,
-                               emitter_onset=leak_t)
-                if valve_setting_range is not None:
-                    link_kw.update(valve_setting=setting)
-            elif link_ranges is None:
-                demand, roughness = self.draw(n, seed, first, *ranges)
-            else:
-                demand, roughness, speed, closed, setting = self.draw_valves(n, seed, first, ranges[0], ranges[1], *link_ranges,
-                                                                             closed_probability)
-                link_kw.update(pump_speed=speed if self.num_pumps else None, link_closed=closed)
-                if valve_setting_range is not None:
-                    link_kw.update(valve_setting=setting)
+            demand, roughness, drawn_kw, labels = draw(n, first)
             level0 = self.draw_levels(n, seed, first, *lv)
             res = self.simulate_series(demand, roughness, mult, step_seconds=step_seconds, initial_level=level0,
                                        pattern_of_node=pattern_of_node, warm_start=warm_start, accuracy=accuracy,
-                                       max_iter=max_iter, want_head=False, want_flow=False, **link_kw, **pdd_kw, **ctl_kw)
+                                       max_iter=max_iter, want_head=False, want_flow=False, **link_kw, **drawn_kw, **pdd_kw, **ctl_kw)
             ok = self.series_valid(res, pressure_range, allow_limited)
             table = torch.cat([res.status.reshape(n, -1), ok.to(torch.int32)[:, None]], dim=1).cpu().numpy()     # the read-back
             tables.append(table)
@@ -1739,28 +1671,17 @@ class HydraulicNetwork:
                 idx = torch.from_numpy(rows).to(dev)
                 kept = res.pressure.index_select(0, idx).index_select(2, st["junctions"])
                 kept_rows.append(kept.reshape(rows.size * steps, -1))
-                if leak_ranges is not None:
-                    leak_rows.append((leak_c.index_select(0, idx), res.emitter_flow.index_select(0, idx),
-                                      None if leak_t is None else leak_t.index_select(0, idx)))
+                full = None
                 if pdd_kw:                                  # the full demand of a step: the kernel's one rounded product
                     pat = torch.zeros(self.num_nodes, dtype=torch.int64, device=dev) if pattern_of_node is None else \
                         torch.as_tensor(pattern_of_node).to(device=dev, dtype=torch.int64)
                     full = demand.index_select(0, idx)[:, None, :] * mult.t().index_select(1, pat)[None, :, :]
-                    supply_rows.append((res.demand_delivered.index_select(0, idx), full))
+                self._keep_labels(idx, res, labels, full, leak_rows, supply_rows)
         table = np.concatenate(tables, axis=0)
         report = series_report(table[:, :-1].reshape(-1, steps, HYD_STATUS), table[:, -1], allow_limited)
         if not kept_rows:
             raise RuntimeError(f"no series of {num_series} was kept with every junction pressure in {tuple(pressure_range)}: {report}")
-        if leak_ranges is not None:
-            report["leak"] = {"coefficient": torch.cat([c for c, _, _ in leak_rows], dim=0),
-                              "flow": torch.cat([f for _, f, _ in leak_rows], dim=0)}
-            if leak_onset_range is not None:
-                report["leak"]["onset"] = torch.cat([t for _, _, t in leak_rows], dim=0)
-        if pdd_kw:
-            report["supply"] = {"delivered": torch.cat([d for d, _ in supply_rows], dim=0),
-                                "full": torch.cat([f for _, f in supply_rows], dim=0)}
-        store = SnapshotStore(torch.cat(kept_rows, dim=0), self.junction_edge_index, device=dev, normalize=normalize)
-        return store, report
+        return self._finish_store(kept_rows, leak_rows, supply_rows, report, normalize)
 
     def draw_ranges(self, demand_range=DEMAND_RANGE, roughness_range=ROUGHNESS_RANGE):
         """(d_lo, d_hi, c_lo, c_hi) as host fp64 arrays: a (lo, hi) pair of scalars for every junction / pipe, or of arrays
@@ -1805,37 +1726,17 @@ class HydraulicNetwork:
         if num_scenarios < 1 or chunk < 1:
             raise ValueError("num_scenarios and chunk must be positive")
         st, dev = self.static(), self._dev()
-        host_ranges = self.draw_ranges(demand_range, roughness_range)
-        ranges = [torch.from_numpy(a).to(dev) for a in host_ranges]
-        leak_ranges = self._emitter_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range,
-                                               emitter_coefficient_range, leak_probability)
-        if leak_ranges is None and self.has_emitters:
-            raise ValueError("a network with emitters needs emitter_coefficient_range")
-        link_ranges = None if leak_ranges is not None else \
-            self._link_draw_setup(host_ranges, pump_speed_range, closed_probability, valve_setting_range)
+        draw = self._chunk_draws(seed, demand_range, roughness_range, pump_speed_range, closed_probability, valve_setting_range,
+                                 emitter_coefficient_range, leak_probability)
         kept_rows, leak_rows = [], []
         report = {"drawn": 0, "converged": 0, "failed": 0, "not_converged": 0, "out_of_range": 0, "kept": 0, "max_iterations": 0,
                   "mean_iterations": 0.0}
         iter_sum = 0
         for first in range(0, num_scenarios, chunk):
             n = min(chunk, num_scenarios - first)
-            if leak_ranges is not None:
-                demand, roughness, speed, closed, setting, leak_c, _ = self.draw_emitters(
-                    n, seed, first, ranges[0], ranges[1], *leak_ranges, closed_probability, leak_probability)
-                res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False,
-                                    pump_speed=speed if self.num_pumps else None, link_closed=closed,
-                                    valve_setting=setting if valve_setting_range is not None else None,
-                                    emitter_coefficient=leak_c, **pdd_kw)
-            elif link_ranges is None:
-                demand, roughness = self.draw(n, seed, first, *ranges)
-                res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False,
-                                    **pdd_kw)
-            else:
-                demand, roughness, speed, closed, setting = self.draw_valves(n, seed, first, ranges[0], ranges[1], *link_ranges,
-                                                                             closed_probability)
-                res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False,
-                                    pump_speed=speed if self.num_pumps else None, link_closed=closed,
-                                    valve_setting=setting if valve_setting_range is not None else None, **pdd_kw)
+            demand, roughness, drawn_kw, labels = draw(n, first)
+            res = self.simulate(demand, roughness, accuracy=accuracy, max_iter=max_iter, want_head=False, want_flow=False,
+                                **drawn_kw, **pdd_kw)
             ok = self.valid(res, pressure_range)
             table = torch.cat([res.status[:, :3], ok.to(torch.int32)[:, None]], dim=1).cpu().numpy()     # the read-back
             rows = np.flatnonzero(table[:, 3])
@@ -1850,10 +1751,7 @@ class HydraulicNetwork:
             if rows.size:
                 idx = torch.from_numpy(rows).to(dev)
                 kept_rows.append(res.pressure.index_select(0, idx).index_select(1, st["junctions"]))
-                if leak_ranges is not None:
-                    leak_rows.append((leak_c.index_select(0, idx), res.emitter_flow.index_select(0, idx)))
-                if pdd_kw:
-                    supply_rows.append((res.demand_delivered.index_select(0, idx), demand.index_select(0, idx)))
+                self._keep_labels(idx, res, labels, demand.index_select(0, idx) if pdd_kw else None, leak_rows, supply_rows)
         report["not_converged"] = report["drawn"] - report["converged"] - report["failed"]
         report["out_of_range"] = report["converged"] - report["kept"]
         alive_n = report["drawn"] - report["failed"]
@@ -1861,14 +1759,7 @@ class HydraulicNetwork:
         if not kept_rows:
             raise RuntimeError(f"no scenario of {num_scenarios} converged with every junction pressure in {tuple(pressure_range)}: "
                                f"{report}")
-        if leak_ranges is not None:
-            report["leak"] = {"coefficient": torch.cat([c for c, _ in leak_rows], dim=0),
-                              "flow": torch.cat([f for _, f in leak_rows], dim=0)}
-        if pdd_kw:
-            report["supply"] = {"delivered": torch.cat([d for d, _ in supply_rows], dim=0),
-                                "full": torch.cat([f for _, f in supply_rows], dim=0)}
-        store = SnapshotStore(torch.cat(kept_rows, dim=0), self.junction_edge_index, device=dev, normalize=normalize)
-        return store, report
+        return self._finish_store(kept_rows, leak_rows, supply_rows, report, normalize)
 
 
 # ---- host restatements ----------------------------------------------------------------------------------------------------------------
