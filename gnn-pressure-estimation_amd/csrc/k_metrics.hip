@@ -53,14 +53,14 @@ __global__ __launch_bounds__(MET_T) void masked_metrics_kernel(const float* __re
   const int tid = threadIdx.x;
   // pass 1: counts and plain sums
   double a[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // M, loss, |d|, d^2, p, t, n_keep, rel, n_acc
-  for (int i0 = tid; i0 < N; i0 += MET_U * MET_T) {
+  for (long long i0 = tid; i0 < N; i0 += MET_U * MET_T) {
     // (MET_U strides' loads in flight at once -- the launch is one workgroup, so it is load latency that it waits on; the
     //  elements are then taken in stride order: the same association as a plain loop)
     uint8_t mk[MET_U];
     float ov[MET_U], yv[MET_U];
 #pragma unroll
     for (int u = 0; u < MET_U; ++u) {
-      const int i = i0 + u * MET_T;
+      const long long i = i0 + u * MET_T;
       mk[u] = i < N ? mask[i] : 0;
       ov[u] = i < N ? out[i] : 0.f;
       yv[u] = i < N ? y[i] : 0.f;
@@ -94,12 +94,12 @@ __global__ __launch_bounds__(MET_T) void masked_metrics_kernel(const float* __re
   // pass 2: sums centred on the means
   const double pm = s_mean[0], tm = s_mean[1];
   double c[3] = {0.0, 0.0, 0.0};                                   // (p-pm)^2, (t-tm)^2, (p-pm)(t-tm)
-  for (int i0 = tid; i0 < N; i0 += MET_U * MET_T) {
+  for (long long i0 = tid; i0 < N; i0 += MET_U * MET_T) {
     uint8_t mk[MET_U];
     float ov[MET_U], yv[MET_U];
 #pragma unroll
     for (int u = 0; u < MET_U; ++u) {
-      const int i = i0 + u * MET_T;
+      const long long i = i0 + u * MET_T;
       mk[u] = i < N ? mask[i] : 0;
       ov[u] = i < N ? out[i] : 0.f;
       yv[u] = i < N ? y[i] : 0.f;

@@ -232,7 +232,8 @@ def metrics_from_moments(table, graphs_per_batch: Sequence[int], prefix: str = "
     """The loss (``MSELoss`` on scaled values) and the seven metrics of ``get_metric_fn_collection(prefix)`` from a moment
     table ``[B, METRICS_RECORD]``, each batch's value weighted by its graph count and divided by the dataset size
     (train.py:278-279, evaluation.py:340-345).  fp64.  torch's NaN cases carry over: no kept element gives ``error`` NaN,
-    zero variance gives ``corr`` / ``r2`` NaN, an empty mask gives NaN everywhere."""
+    zero variance gives ``corr`` / ``r2`` NaN, an empty mask gives NaN everywhere but ``mynse``, which is 1.0 there as
+    ``calculate_nse`` is on empty tensors (0 / (0 + 1e-12))."""
     T = np.asarray(table, dtype=np.float64).reshape(-1, METRICS_RECORD)
     w = [int(g) for g in graphs_per_batch]
     if len(w) != T.shape[0]:
