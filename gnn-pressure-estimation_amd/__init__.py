@@ -22,7 +22,9 @@ from .hydraulics import (HydraulicLinksResult, HydraulicNetwork, HydraulicResult
                          valve_status_ref, hydraulic_valve_draws, HydraulicEmittersResult, HydraulicSeriesEmittersResult,
                          emitter_headloss, hydraulic_emitter_draws, HydraulicPddResult, HydraulicSeriesPddResult, demand_headloss,
                          pdd_lds_bytes, series_pdd_lds_bytes, ControlTable, control_table, control_state,
-                         control_step_ref, series_controls_lds_bytes, HydraulicSeriesControlsResult)
+                         control_step_ref, series_controls_lds_bytes, HydraulicSeriesControlsResult, HydraulicSensitivityResult,
+                         LeakLocalization, sensitivity_ref, leak_scores_ref, localization_report, sensitivity_lds_bytes,
+                         sensitivity_chunk)
 from .wdn_io import parse_inp_hydraulics
 from .sensitivity import (influence_from_table, linear_spread_ref, sensitivity_fold_ref, sensitivity_rows_from_gx,
                           sensitivity_seeds)
@@ -43,4 +45,5 @@ __all__ = ["FusedAdam", "GATResMeanConv", "GResBlockMeanConv", "GATConv", "Simpl
            "hydraulic_valve_draws", "HydraulicEmittersResult", "HydraulicSeriesEmittersResult", "emitter_headloss",
            "hydraulic_emitter_draws", "HydraulicPddResult", "HydraulicSeriesPddResult", "demand_headloss", "pdd_lds_bytes",
            "series_pdd_lds_bytes", "ControlTable", "control_table", "control_state", "control_step_ref",
-           "series_controls_lds_bytes", "HydraulicSeriesControlsResult"]
+           "series_controls_lds_bytes", "HydraulicSeriesControlsResult",
+           "HydraulicSensitivityResult", "LeakLocalization", "sensitivity_ref", "leak_scores_ref", "localization_report", "sensitivity_lds_bytes", "sensitivity_chunk"]

@@ -21,7 +21,7 @@ ARCH = "gfx950"
 SOURCES = ["k_window.hip", "k_fused_whole.hip", "k_fused_host.hip", "k_aggregate.hip", "k_proj.hip", "k_misc.hip", "k_blocked.hip", "graph_plan.hip",
            "model_driver.hip", "train_driver.hip", "k_autoclip.hip", "k_metrics.hip", "k_epoch.hip", "k_stage.hip", "k_grad_flow.hip", "k_estimate.hip",
            "k_bounds.hip", "k_sensitivity.hip", "k_screen.hip", "k_monitor.hip", "k_hydraulics.hip", "k_hydraulic_links.hip",
-           "k_hydraulic_network.hip"]
+           "k_hydraulic_network.hip", "k_hydraulic_sensitivity.hip"]
 
 
 def _hipcc() -> str:

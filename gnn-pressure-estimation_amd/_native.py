@@ -221,6 +221,8 @@ SIGNATURES = {
                                          [_I32, _P, _I64, _P, _I64, _P, _P, _I32, _P] + [_P, _P, _P, _I64, _I32, _P] +
                                          [_P, _P, _I64, _I32, _F64, _P, _I64, _P] + [_I32, _F64, _F64, _F64, _P] +
                                          [_P] * 6 + [_I64, _I32, _P, _P]),
+    "gatres_hydraulic_sensitivity": (C.c_int, [_P] * 8 + [_I32, _P, _P, _P, _I64, _I64, _I32, _I32, _F64, _I32] + [_P] * 5 +
+                                     [_P] * 7 + [_I32, _P, _I64, _P, _I64, _P] + [_P, _I32, _I32] + [_P] * 7 + [_P]),
     "gatres_version": (C.c_char_p, []),
 }
 

@@ -14,98 +14,8 @@ constexpr size_t HY_LDS_BUDGET = GATRES_HYD_LDS_BUDGET;
 static_assert(GATRES_HYD_STATUS == 4, "status record");
 static_assert(GATRES_HYD_LINK_CHECK == 1 && GATRES_HYD_LINK_CLOSED == 2 && GATRES_HYD_PIPE == 0 && GATRES_HYD_PUMP == 1, "gatres.h");
 
-// the link arrays of a launch, shared by both kernels
-struct HydLinkArgs {
-  const uint8_t *link_kind, *link_flags;
-  const double* minor;
-  const int* pump_link;
-  const double *pump_h0, *pump_r, *pump_n;
-  const double* speed;
-  const uint8_t* closed;
-  long long speed_stride, closed_stride;
-  int Kp;
-  uint8_t* link_state;
-};
-
-struct HydLinksArgs {
-  const int *pipe_a, *pipe_b;
-  const double *coef, *q_start;
-  const uint8_t* fixed;
-  const double* elevation;
-  const int *order, *position;
-  const double *demand, *roughness, *fixed_head;
-  long long fh_stride, S;
-  int N, P, W, max_iter;
-  double accuracy;
-  float* pressure;
-  double *head, *flow;
-  int* status;
-  double* final_dq;
-  HydLinkArgs K;
-};
-
-// LDS of a workgroup, as gatres.h states it: the pipe-only arrays, and per link m and the code, per pump its record
-static inline uint64_t hy_links_lds_bytes(uint64_t N, uint64_t P, uint64_t W, uint64_t Kp) {
-  return 8 * (N * (W + 1) + 2 * N + 4 * P) + 4 * (2 * P + N) + 64 + 12 * P + 8 * HY_PUMP_REC * Kp;
-}
-
 static inline uint64_t hy_series_links_lds_bytes(uint64_t N, uint64_t P, uint64_t W, uint64_t K, uint64_t Kp) {
   return hy_links_lds_bytes(N, P, W, Kp) + 8 * N + 40 * K;
-}
-
-// The static link arrays, checked, after hy_check_static (flag[0] keeps the verdict): fills L.minor, L.code (without HY_SHUT)
-// and the constants of L.pump.  Nothing indexes with a pump index or a pump's link that was not checked here.  Ends behind a
-// barrier; returns true where an array is not what gatres.h states.
-__device__ __forceinline__ bool hy_check_links(const HyLds& L, const HydLinkArgs& K, const double* __restrict__ coef, int P,
-                                               int* flag, int tid) {
-  const int Kp = K.Kp;
-  for (int p = tid; p < P; p += HY_T) {
-    const int kind = K.link_kind[p], fl = K.link_flags[p];
-    const double m = K.minor[p], cf = coef[p];
-    bool ok = kind <= GATRES_HYD_PUMP && fl <= (GATRES_HYD_LINK_CHECK | GATRES_HYD_LINK_CLOSED) && m >= 0.0 && hy_finite(m);
-    if (kind == GATRES_HYD_PIPE && !(cf >= 0.0 && hy_finite(cf) && (cf > 0.0 || m > 0.0))) ok = false;
-    int code = 0;
-    if (ok) {
-      if (kind == GATRES_HYD_PUMP) code |= HY_PUMP | HY_CHECK;
-      if (fl & GATRES_HYD_LINK_CHECK) code |= HY_CHECK;
-      if (fl & GATRES_HYD_LINK_CLOSED) code |= HY_CLOSED;
-    } else {
-      flag[0] = 1;
-    }
-    L.code[p] = code;
-    L.minor[p] = ok ? m : 0.0;
-  }
-  __syncthreads();
-  for (int k = tid; k < Kp; k += HY_T) {
-    const int link = K.pump_link[k];
-    const double h0 = K.pump_h0[k], rp = K.pump_r[k], n = K.pump_n[k];
-    bool ok = link >= 0 && link < P;
-    if (ok) ok = K.link_kind[link] == GATRES_HYD_PUMP;
-    for (int j = 0; ok && j < k; ++j) ok = K.pump_link[j] != link;
-    if (!(h0 >= 0.0) || !hy_finite(h0) || !(rp > 0.0) || !hy_finite(rp) || !(n >= 1.0) || !hy_finite(n)) ok = false;
-    double* rec = L.pump + (size_t)k * HY_PUMP_REC;
-    rec[0] = ok ? h0 : 0.0;
-    rec[1] = ok ? rp : 1.0;
-    rec[2] = ok ? n : 1.0;
-    rec[3] = rec[4] = rec[5] = 0.0;
-    if (ok) L.code[link] |= k << HY_PUMP_SHIFT;            // (one pump per link: checked above)
-    else flag[0] = 1;
-  }
-  __syncthreads();
-  for (int p = tid; p < P; p += HY_T) {                    // every pump link has its record
-    const int code = L.code[p];
-    if (code & HY_PUMP) {
-      const int k = code >> HY_PUMP_SHIFT;
-      bool ok = k < Kp;
-      if (ok) ok = K.pump_link[k] == p;
-      if (!ok) {
-        L.code[p] = 0;
-        flag[0] = 1;
-      }
-    }
-  }
-  __syncthreads();
-  return flag[0] != 0;
 }
 
 __global__ __launch_bounds__(HY_T) void hydraulic_solve_links_kernel(const HydLinksArgs A) {
@@ -408,30 +318,6 @@ __global__ __launch_bounds__(HY_T) void hydraulic_series_links_kernel(const HydS
     }
     __syncthreads();                                       // (the next series writes the shared arrays again)
   }
-}
-
-// the link arguments both entry points share; num_pipes is known to be >= 1
-static bool hy_link_args_ok(const uint8_t* link_kind, const uint8_t* link_flags, const double* minor, const int32_t* pump_link,
-                            const double* pump_h0, const double* pump_r, const double* pump_n, int32_t num_pumps,
-                            const double* speed, int64_t speed_stride, const uint8_t* closed, int64_t closed_stride,
-                            const uint8_t* link_state, int32_t num_pipes) {
-  if (!link_kind || !link_flags || !minor || !link_state) return false;
-  if (num_pumps < 0 || num_pumps > num_pipes) return false;
-  if (num_pumps > 0 && (!pump_link || !pump_h0 || !pump_r || !pump_n || !speed)) return false;
-  if (speed_stride != 0 && speed_stride != (int64_t)num_pumps) return false;
-  if (closed_stride != 0 && (closed_stride != (int64_t)num_pipes || !closed)) return false;
-  return true;
-}
-
-static HydLinkArgs hy_link_args(const uint8_t* link_kind, const uint8_t* link_flags, const double* minor, const int32_t* pump_link,
-                                const double* pump_h0, const double* pump_r, const double* pump_n, int32_t num_pumps,
-                                const double* speed, int64_t speed_stride, const uint8_t* closed, int64_t closed_stride,
-                                uint8_t* link_state) {
-  HydLinkArgs k;
-  k.link_kind = link_kind; k.link_flags = link_flags; k.minor = minor; k.pump_link = pump_link; k.pump_h0 = pump_h0;
-  k.pump_r = pump_r; k.pump_n = pump_n; k.speed = speed; k.closed = closed; k.speed_stride = (long long)speed_stride;
-  k.closed_stride = (long long)closed_stride; k.Kp = (int)num_pumps; k.link_state = link_state;
-  return k;
 }
 
 }  // namespace

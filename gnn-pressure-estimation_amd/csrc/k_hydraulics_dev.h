@@ -649,6 +649,195 @@ __device__ __forceinline__ uint8_t hy_link_state(int code, double q) {
   return (code & HY_CHECK) && q < 0.0 ? 1 : 0;
 }
 
+// ---- what the links launches share (k_hydraulic_links.hip, k_hydraulic_sensitivity.hip) -----------------------------------------------
+// the link arrays of a launch
+struct HydLinkArgs {
+  const uint8_t *link_kind, *link_flags;
+  const double* minor;
+  const int* pump_link;
+  const double *pump_h0, *pump_r, *pump_n;
+  const double* speed;
+  const uint8_t* closed;
+  long long speed_stride, closed_stride;
+  int Kp;
+  uint8_t* link_state;
+};
+
+struct HydLinksArgs {
+  const int *pipe_a, *pipe_b;
+  const double *coef, *q_start;
+  const uint8_t* fixed;
+  const double* elevation;
+  const int *order, *position;
+  const double *demand, *roughness, *fixed_head;
+  long long fh_stride, S;
+  int N, P, W, max_iter;
+  double accuracy;
+  float* pressure;
+  double *head, *flow;
+  int* status;
+  double* final_dq;
+  HydLinkArgs K;
+};
+
+// LDS of a workgroup, as gatres.h states it: the pipe-only arrays, and per link m and the code, per pump its record
+static inline uint64_t hy_links_lds_bytes(uint64_t N, uint64_t P, uint64_t W, uint64_t Kp) {
+  return 8 * (N * (W + 1) + 2 * N + 4 * P) + 4 * (2 * P + N) + 64 + 12 * P + 8 * HY_PUMP_REC * Kp;
+}
+
+// The static link arrays, checked, after hy_check_static (flag[0] keeps the verdict): fills L.minor, L.code (without HY_SHUT)
+// and the constants of L.pump.  Nothing indexes with a pump index or a pump's link that was not checked here.  Ends behind a
+// barrier; returns true where an array is not what gatres.h states.
+__device__ __forceinline__ bool hy_check_links(const HyLds& L, const HydLinkArgs& K, const double* __restrict__ coef, int P,
+                                               int* flag, int tid) {
+  const int Kp = K.Kp;
+  for (int p = tid; p < P; p += HY_T) {
+    const int kind = K.link_kind[p], fl = K.link_flags[p];
+    const double m = K.minor[p], cf = coef[p];
+    bool ok = kind <= GATRES_HYD_PUMP && fl <= (GATRES_HYD_LINK_CHECK | GATRES_HYD_LINK_CLOSED) && m >= 0.0 && hy_finite(m);
+    if (kind == GATRES_HYD_PIPE && !(cf >= 0.0 && hy_finite(cf) && (cf > 0.0 || m > 0.0))) ok = false;
+    int code = 0;
+    if (ok) {
+      if (kind == GATRES_HYD_PUMP) code |= HY_PUMP | HY_CHECK;
+      if (fl & GATRES_HYD_LINK_CHECK) code |= HY_CHECK;
+      if (fl & GATRES_HYD_LINK_CLOSED) code |= HY_CLOSED;
+    } else {
+      flag[0] = 1;
+    }
+    L.code[p] = code;
+    L.minor[p] = ok ? m : 0.0;
+  }
+  __syncthreads();
+  for (int k = tid; k < Kp; k += HY_T) {
+    const int link = K.pump_link[k];
+    const double h0 = K.pump_h0[k], rp = K.pump_r[k], n = K.pump_n[k];
+    bool ok = link >= 0 && link < P;
+    if (ok) ok = K.link_kind[link] == GATRES_HYD_PUMP;
+    for (int j = 0; ok && j < k; ++j) ok = K.pump_link[j] != link;
+    if (!(h0 >= 0.0) || !hy_finite(h0) || !(rp > 0.0) || !hy_finite(rp) || !(n >= 1.0) || !hy_finite(n)) ok = false;
+    double* rec = L.pump + (size_t)k * HY_PUMP_REC;
+    rec[0] = ok ? h0 : 0.0;
+    rec[1] = ok ? rp : 1.0;
+    rec[2] = ok ? n : 1.0;
+    rec[3] = rec[4] = rec[5] = 0.0;
+    if (ok) L.code[link] |= k << HY_PUMP_SHIFT;            // (one pump per link: checked above)
+    else flag[0] = 1;
+  }
+  __syncthreads();
+  for (int p = tid; p < P; p += HY_T) {                    // every pump link has its record
+    const int code = L.code[p];
+    if (code & HY_PUMP) {
+      const int k = code >> HY_PUMP_SHIFT;
+      bool ok = k < Kp;
+      if (ok) ok = K.pump_link[k] == p;
+      if (!ok) {
+        L.code[p] = 0;
+        flag[0] = 1;
+      }
+    }
+  }
+  __syncthreads();
+  return flag[0] != 0;
+}
+
+// ---- THE SENSITIVITIES of gatres.h (k_hydraulic_sensitivity.hip) -------------------------------------------------------------------
+// The law's 1 / g at the flows in L.q, into L.pinv, and into L.yv what a link's roughness moves: -h_C / g, the factor of
+// dh_droughness (0 for a pump, on a 1e8 branch and on the low-flow floor); rough: the scenario's coefficients.  The caller puts
+// a barrier behind it.
+__device__ __forceinline__ void hy_law_gradients(const HyLds& L, const double* __restrict__ rough, int P, int tid) {
+  for (int p = tid; p < P; p += HY_T) {
+    const int code = L.code[p];
+    const double q = L.q[p], r = L.rr[p], m = L.minor[p];
+    double h, g;
+    link_headloss(q, r, m, code, L.pump + (size_t)(code >> HY_PUMP_SHIFT) * HY_PUMP_REC, &h, &g);
+    double gain = 0.0;
+    if (!(code & (HY_SHUT | HY_PUMP)) && !((code & HY_CHECK) && q < 0.0)) {
+      const double aq = fabs(q), ra = r * pow(aq, 0.852);
+      if (!(1.852 * ra + 2.0 * (m * aq) < HY_LINEAR_G)) gain = ((1.852 * ra) * q) / (rough[p] * g);
+    }
+    L.pinv[p] = 1.0 / g;
+    L.yv[p] = gain;
+  }
+}
+
+// The matrix of hy_newton's assembly alone, from the 1 / g in L.pinv: one thread per row, over the pipes in pipe order, unit
+// rows for the fixed nodes.  Ends behind a barrier.
+__device__ __forceinline__ void hy_assemble_matrix(const HyLds& L, const int* __restrict__ position, int N, int P, int W, int tid) {
+  const int BW = W + 1;
+  const int *sa = L.sa, *sb = L.sb, *fx = L.fx;
+  for (int n = tid; n < N; n += HY_T) {
+    const int r = position[n];
+    double* row = L.band + (size_t)r * BW;
+    for (int k = 0; k < BW; ++k) row[k] = 0.0;
+    if (fx[r]) {
+      row[0] = 1.0;
+    } else {
+      double diag = 0.0;
+      for (int p = 0; p < P; ++p) {
+        const int a = sa[p], b = sb[p];
+        if (a != r && b != r) continue;
+        const int o = a == r ? b : a;
+        const double pi = L.pinv[p];
+        diag += pi;
+        if (!fx[o] && o < r) row[r - o] -= pi;             // (r - o <= W: checked by the caller)
+      }
+      row[0] = diag;
+    }
+  }
+  __syncthreads();
+}
+
+// hy_newton's banded LDL^T without a right-hand side: the factor stays in L.band.  Returns true on a bad pivot (the same value
+// in every thread); ends behind a barrier.
+__device__ __forceinline__ bool hy_factorise(const HyLds& L, int N, int W, int tid) {
+  const int BW = W + 1;
+  double* band = L.band;
+  for (int j = 0; j < N; ++j) {
+    const double d = band[(size_t)j * BW];
+    if (!(d > 0.0) || !hy_finite(d)) return true;
+    const int m = W < N - 1 - j ? W : N - 1 - j;
+    for (int e = tid; e < m * m; e += HY_T) {
+      const int r = e / m + 1, c = e - (r - 1) * m + 1;
+      if (c <= r) {
+        const double vr = band[(size_t)(j + r) * BW + r], vc = band[(size_t)(j + c) * BW + c];
+        band[(size_t)(j + r) * BW + (r - c)] -= vr * (vc / d);
+      }
+    }
+    __syncthreads();
+  }
+  return false;
+}
+
+// hy_newton's two substitutions for kc right-hand sides at once against the factor in L.band.  X is [N][stride], the right-hand
+// side's index fastest; the work items of a column step are the (band offset, right-hand side) pairs, one barrier per column, and
+// every right-hand side takes the operations of the loop's single vector in the same order.  On return X[r][c] holds the
+// solution's row r times the pivot d_r: the caller divides (no thread writes the row that the others read).  The caller has put
+// a barrier behind its writes to X; ends behind a barrier.
+__device__ __forceinline__ void hy_substitute_multi(const double* band, double* X, int N, int W, int kc, int stride, int tid) {
+  const int BW = W + 1;
+  for (int j = 0; j < N; ++j) {
+    const double d = band[(size_t)j * BW];
+    const int m = W < N - 1 - j ? W : N - 1 - j;
+    for (int e = tid; e < m * kc; e += HY_T) {
+      const int t = e / kc, c = e - t * kc;
+      const double zj = X[(size_t)j * stride + c] / d;
+      X[(size_t)(j + 1 + t) * stride + c] -= band[(size_t)(j + 1 + t) * BW + (t + 1)] * zj;
+    }
+    __syncthreads();
+  }
+  for (int k = N - 1; k >= 0; --k) {
+    const double d = band[(size_t)k * BW];
+    const int m = W < k ? W : k;
+    for (int e = tid; e < m * kc; e += HY_T) {
+      const int t = e / kc + 1, c = e - (t - 1) * kc;
+      const double xk = X[(size_t)k * stride + c] / d;
+      X[(size_t)(k - t) * stride + c] -= band[(size_t)k * BW + t] * xk;
+    }
+    __syncthreads();
+  }
+}
+
+
 // ---- the host checks every hydraulic entry point makes --------------------------------------------------------------------------------
 // Does one of the written ranges overlap a read range or another written range?  (A null pointer is no range.)
 static bool any_overlap(const void* const* wr, const uint64_t* wn, int nw, const void* const* rd, const uint64_t* rn, int nr) {
@@ -663,6 +852,30 @@ static bool any_overlap(const void* const* wr, const uint64_t* wn, int nw, const
 
 static inline bool hy_counts_ok(int64_t S, int32_t N, int32_t P) {
   return S >= 1 && N >= 1 && P >= 1 && S <= INT64_MAX / 64 / ((int64_t)N + (int64_t)P);    // (every byte count of a launch fits)
+}
+
+// the link arguments both entry points share; num_pipes is known to be >= 1
+static bool hy_link_args_ok(const uint8_t* link_kind, const uint8_t* link_flags, const double* minor, const int32_t* pump_link,
+                            const double* pump_h0, const double* pump_r, const double* pump_n, int32_t num_pumps,
+                            const double* speed, int64_t speed_stride, const uint8_t* closed, int64_t closed_stride,
+                            const uint8_t* link_state, int32_t num_pipes) {
+  if (!link_kind || !link_flags || !minor || !link_state) return false;
+  if (num_pumps < 0 || num_pumps > num_pipes) return false;
+  if (num_pumps > 0 && (!pump_link || !pump_h0 || !pump_r || !pump_n || !speed)) return false;
+  if (speed_stride != 0 && speed_stride != (int64_t)num_pumps) return false;
+  if (closed_stride != 0 && (closed_stride != (int64_t)num_pipes || !closed)) return false;
+  return true;
+}
+
+static HydLinkArgs hy_link_args(const uint8_t* link_kind, const uint8_t* link_flags, const double* minor, const int32_t* pump_link,
+                                const double* pump_h0, const double* pump_r, const double* pump_n, int32_t num_pumps,
+                                const double* speed, int64_t speed_stride, const uint8_t* closed, int64_t closed_stride,
+                                uint8_t* link_state) {
+  HydLinkArgs k;
+  k.link_kind = link_kind; k.link_flags = link_flags; k.minor = minor; k.pump_link = pump_link; k.pump_h0 = pump_h0;
+  k.pump_r = pump_r; k.pump_n = pump_n; k.speed = speed; k.closed = closed; k.speed_stride = (long long)speed_stride;
+  k.closed_stride = (long long)closed_stride; k.Kp = (int)num_pumps; k.link_state = link_state;
+  return k;
 }
 
 }  // namespace

@@ -232,6 +232,10 @@ HydraulicValvesReference = namedtuple("HydraulicValvesReference", HydraulicLinks
 HydraulicSeriesValvesResult = namedtuple("HydraulicSeriesValvesResult", HydraulicSeriesLinksResult._fields + ("valve_changes",))
 HydraulicSeriesValvesReference = namedtuple("HydraulicSeriesValvesReference",
                                             HydraulicSeriesLinksReference._fields + ("valve_changes", "margin"))
+# what ``HydraulicNetwork.sensitivity`` and ``localize_leaks`` return (gatres.h: THE SENSITIVITIES); every field a device tensor
+HydraulicSensitivityResult = namedtuple("HydraulicSensitivityResult", HydraulicLinksResult._fields + ("dh_ddemand", "dh_droughness"))
+LeakLocalization = namedtuple("LeakLocalization", "score leak_flow best residual pressure status dh_ddemand")
+HydraulicSensitivityReference = namedtuple("HydraulicSensitivityReference", "dh_ddemand dh_droughness")
 LINK_PRV, LINK_PSV = 2, 3               # GATRES_HYD_PRV, GATRES_HYD_PSV
 VALVE_OPEN, VALVE_ACTIVE, VALVE_CLOSED = 0, 3, 4      # link_state of a regulating valve (2: shut by input)
 VALVE_HTOL, VALVE_QTOL = 1.524e-4, 2.8316846592e-6    # EPANET's 0.0005 ft and 0.0001 cfs
@@ -682,6 +686,20 @@ def links_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_pum
     """What a workgroup of ``gatres_hydraulic_solve_links`` takes of the LDS (gatres.h states the same sum): a solve workgroup's
     arrays, per link m and its code, per pump h0, rp, n, w^2, w^(2-n) and w."""
     return lds_bytes(num_nodes, num_pipes, half_bandwidth) + 12 * num_pipes + 48 * num_pumps
+
+
+def sensitivity_chunk(num_nodes: int, num_pipes: int, half_bandwidth: int, num_pumps: int, num_sensors: int) -> int:
+    """Kc of ``gatres_hydraulic_sensitivity`` (gatres.h: THE SENSITIVITIES): how many of the K right-hand sides a workgroup takes at
+    once -- as many as fit beside the links arrays and the two score accumulators, 0 where not even one does (the launch is
+    refused)."""
+    room = LDS_BUDGET - links_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_pumps) - 16 * num_nodes
+    return max(0, min(int(num_sensors), room // (8 * (num_nodes + 1))))
+
+
+def sensitivity_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_pumps: int, chunk: int) -> int:
+    """What a workgroup of ``gatres_hydraulic_sensitivity`` takes of the LDS with ``chunk`` right-hand sides at once (gatres.h states
+    the same sum): the links arrays, <z, rho> and <z, z> per row, and per right-hand side its column and its residual."""
+    return links_lds_bytes(num_nodes, num_pipes, half_bandwidth, num_pumps) + 16 * num_nodes + 8 * chunk * (num_nodes + 1)
 
 
 def series_links_lds_bytes(num_nodes: int, num_pipes: int, half_bandwidth: int, num_tanks: int, num_pumps: int) -> int:
@@ -1404,6 +1422,84 @@ class HydraulicNetwork:
                                  f"with this demand model, the kernel has {LDS_BUDGET}")
             _add_level(call, (pdd, new((S, N)), None))
         return self._launch(STEADY_LAUNCHES, level, args, (pressure, head, flow), 2, status, final_dq, call[1])
+
+    def _sensitivity_launch(self, demand, roughness, sensor_nodes, fixed_head, pump_speed, link_closed, accuracy, max_iter, chunk,
+                            readings, want):
+        """THE ``gatres_hydraulic_sensitivity`` launch (gatres.h: THE SENSITIVITIES): the shared outputs and those named in ``want``
+        (a subset of dh_ddemand, dh_droughness, residual, leak_flow, score, best), as a dict of device tensors."""
+        if self.has_valves:
+            raise ValueError("a network with regulating valves has no sensitivities here: an ACTIVE valve's flow is lagged outside "
+                             "the matrix, so the matrix is not the Jacobian")
+        st, dev, N, P = self.static(), self._dev(), self.num_nodes, self.num_pipes
+        demand, roughness, S = self._scenarios(demand, roughness, "no scenarios")
+        sensors = torch.as_tensor(np.array(sensor_nodes) if isinstance(sensor_nodes, np.ndarray) else sensor_nodes)
+        if sensors.dim() != 1 or sensors.numel() < 1 or sensors.dtype.is_floating_point or sensors.dtype == torch.bool:
+            raise ValueError("sensor_nodes must be a list of at least one node index")
+        K = int(sensors.numel())
+        sensors = sensors.to(device=dev, dtype=torch.int32).contiguous()
+        if sensitivity_chunk(N, P, self.half_bandwidth, self.num_pumps, K) < 1:
+            raise ValueError(f"the band of {N} rows with half-bandwidth {self.half_bandwidth} leaves no room in the LDS for one "
+                             f"right-hand side ({LDS_BUDGET} bytes)")
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError("chunk must be at least 1")
+        fh, stride = self._per_scenario(fixed_head, S, N, "fixed_head")
+        fh = st["fixed_head"] if fh is None else fh
+        readings = None if readings is None else self._f64(readings, (S, K), "readings")
+        new = lambda shape, dtype=torch.float64: torch.empty(shape, dtype=dtype, device=dev)
+        out = {"pressure": new((S, N), torch.float32), "head": new((S, N)), "flow": new((S, P)),
+               "status": new((S, HYD_STATUS), torch.int32), "final_dq": new((S,))}
+        shapes = {"dh_ddemand": (S, K, N), "dh_droughness": (S, K, P), "residual": (S, K), "leak_flow": (S, N), "score": (S, N)}
+        for name in want:
+            out[name] = new((S,), torch.int32) if name == "best" else new(shapes[name])
+        args = [st["pipe_a"].data_ptr(), st["pipe_b"].data_ptr(), st["coef"].data_ptr(), st["q_start"].data_ptr(),
+                st["fixed"].data_ptr(), st["elevation"].data_ptr(), st["order"].data_ptr(), st["position"].data_ptr(),
+                self.half_bandwidth, demand.data_ptr(), roughness.data_ptr(), fh.data_ptr(), stride, S, N, P, float(accuracy),
+                int(max_iter), out["pressure"].data_ptr(), out["head"].data_ptr(), out["flow"].data_ptr(), out["status"].data_ptr(),
+                out["final_dq"].data_ptr()]
+        link_args, out["link_state"], held = self._link_args(S, (S, P), pump_speed, link_closed)
+        args += link_args + [out["link_state"].data_ptr(), sensors.data_ptr(), K, 0 if chunk is None else int(chunk),
+                             _native.ptr(readings)]
+        args += [_native.ptr(out.get(name)) for name in ("dh_ddemand", "dh_droughness", "residual", "leak_flow", "score", "best")]
+        rc = _native.load().gatres_hydraulic_sensitivity(*args, _native.current_stream(dev))
+        _native.check(rc, "gatres_hydraulic_sensitivity")
+        return out
+
+    def sensitivity(self, demand, roughness, sensor_nodes, fixed_head=None, pump_speed=None, link_closed=None,
+                    want_roughness: bool = False, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
+                    chunk=None) -> HydraulicSensitivityResult:
+        """Solve S scenarios as ``simulate(links=True)`` does and, in the same launch, the first-order sensitivities of the heads at
+        ``sensor_nodes`` [K] (gatres.h: THE SENSITIVITIES): ``dh_ddemand`` fp64 [S, K, N], dH_sensor / dd_node = -(A^-1) in metres
+        per m3/s (negative: an outflow lowers heads; 0 where the node or the sensor has a fixed head), and with ``want_roughness``
+        ``dh_droughness`` fp64 [S, K, P], dH_sensor / dC_pipe (else None).  The other fields are those of a
+        ``HydraulicLinksResult``, bit for bit.  A failed scenario has NaN.  A network with emitters is taken with its emitters not
+        leaking: the nominal model a leak is measured against.  A network with regulating valves is refused (``ValueError``), and
+        there is no ``demand_model``: neither system has ``A`` for its Jacobian.  ``chunk`` caps the right-hand sides a workgroup
+        takes at once (default: as many as fit, ``sensitivity_chunk``); no output depends on it.  Nothing is read back."""
+        o = self._sensitivity_launch(demand, roughness, sensor_nodes, fixed_head, pump_speed, link_closed, accuracy, max_iter, chunk,
+                                     None, ("dh_ddemand", "dh_droughness") if want_roughness else ("dh_ddemand",))
+        st = o["status"]
+        return HydraulicSensitivityResult(o["pressure"], o["head"], o["flow"], st[:, 0], st[:, 1] != 0, st[:, 2] != 0, st,
+                                          o["final_dq"], o["link_state"], o["dh_ddemand"], o.get("dh_droughness"))
+
+    def localize_leaks(self, readings, demand, roughness, sensor_nodes, fixed_head=None, pump_speed=None, link_closed=None,
+                       want_sensitivity: bool = False, accuracy: float = ACCURACY, max_iter: int = MAX_ITER,
+                       chunk=None) -> LeakLocalization:
+        """Where is the water lost?  ``readings`` fp64 [S, K]: measured pressures in metres at ``sensor_nodes`` (NaN: the sensor is
+        missing in that scenario); ``demand``, ``roughness`` and the rest: the NOMINAL model, without the leak.  One launch solves
+        the model, forms ``residual`` [S, K] = reading - model pressure (fp64 head - elevation) and matches it against every
+        column z_n of ``dh_ddemand`` without writing that matrix: ``score`` [S, N] the cosine <z_n, rho> / (|z_n| |rho|) (+1: the
+        residual is what an outflow at n would cause), ``leak_flow`` [S, N] the least-squares outflow <z_n, rho> / <z_n, z_n> in
+        m3/s, ``best`` int32 [S] the lowest node among those holding the top score (-1 where every score is NaN: a failed scenario,
+        no sensor, a zero residual).  Junctions behind the same sensor cut have proportional columns and scores that differ by
+        rounding alone: ``best`` names one of them (``localization_report`` measures what that means).  ``pressure`` and
+        ``status`` are the model's; ``dh_ddemand`` is None unless ``want_sensitivity``.  Refusals as ``sensitivity``.  Nothing is
+        read back."""
+        if readings is None:
+            raise ValueError("localize_leaks needs readings")
+        want = ("residual", "leak_flow", "score", "best") + (("dh_ddemand",) if want_sensitivity else ())
+        o = self._sensitivity_launch(demand, roughness, sensor_nodes, fixed_head, pump_speed, link_closed, accuracy, max_iter, chunk,
+                                     readings, want)
+        return LeakLocalization(o["score"], o["leak_flow"], o["best"], o["residual"], o["pressure"], o["status"], o.get("dh_ddemand"))
 
     def valid(self, result: HydraulicResult, pressure_range: Tuple[float, float]) -> torch.Tensor:
         """``gatres_hydraulic_valid``: uint8 [S], 1 where the scenario converged, did not fail and every junction pressure lies
@@ -2626,3 +2722,159 @@ def tree_solution(network: HydraulicNetwork, demand, roughness, fixed_head=None)
             h, _ = pipe_headloss(flow[s, p], r[p])
             head[s, v] = head[s, parent[v]] - sign * float(h)
     return head, flow
+
+
+# ---- THE SENSITIVITIES on the host (gatres.h: THE SENSITIVITIES) --------------------------------------------------------------------
+def roughness_gain(network: HydraulicNetwork, q, roughness, law) -> np.ndarray:
+    """-h_C / g per link at the flows q under ``law`` (``link_law``): what a unit of Hazen-Williams coefficient moves the link's
+    flow at fixed heads, ((1.852 ra) q) / (C g) with ra = r |q|^0.852; 0 for a pump, on a 1e8 branch and on the low-flow floor."""
+    q, c = np.asarray(q, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
+    r = _link_resistance(network, c)
+    _, g = link_headloss(q, r, **law)
+    aq = np.abs(q)
+    ra = r * np.power(aq, 0.852)
+    live = ~(law["pump"] | law["shut"] | (law["check"] & (q < 0))) & ~(1.852 * ra + 2.0 * (law["minor"] * aq) < LINEAR_GRADIENT)
+    with np.errstate(all="ignore"):
+        return np.where(live, ((1.852 * ra) * q) / (c * g), 0.0)
+
+
+def sensitivity_ref(network: HydraulicNetwork, demand, roughness, sensor_nodes, fixed_head=None, pump_speed=None, link_closed=None,
+                    flow=None, solver: str = "dense", accuracy: float = ACCURACY,
+                    max_iter: int = MAX_ITER) -> HydraulicSensitivityReference:
+    """THE SENSITIVITIES in numpy fp64: (``dh_ddemand`` [S, K, N], ``dh_droughness`` [S, K, P]).  Per scenario the matrix A of the
+    solver is built from THE LINK LAW's g at ``solve_ref``'s flows under the link law -- or at ``flow`` [S, P] where given (a
+    device result's own flows isolate the linear algebra) -- with unit rows for the fixed-head nodes; dh_ddemand[k][n] =
+    -(A^-1)[sensor k][n], 0 where either has a fixed head; dh_droughness[k][p] = (Z[k][a] - Z[k][b]) * ``roughness_gain``[p].
+    ``solver``: "dense" (``numpy.linalg.solve`` in node order) or "banded" (``scipy.linalg.solveh_banded`` in solver order).  A
+    failed scenario is NaN.  Emitters are taken as not leaking; regulating valves are refused."""
+    if network.has_valves:
+        raise ValueError("a network with regulating valves has no sensitivities here")
+    if solver not in ("dense", "banded"):
+        raise ValueError("solver must be 'dense' or 'banded'")
+    demand, roughness = np.asarray(demand, dtype=np.float64), np.asarray(roughness, dtype=np.float64)
+    sensors = np.asarray(sensor_nodes, dtype=np.int64).reshape(-1)
+    S, N, P, K = demand.shape[0], network.num_nodes, network.num_pipes, sensors.size
+    if K < 1 or sensors.min() < 0 or sensors.max() >= N:
+        raise ValueError("sensor_nodes must be nodes of the network, at least one")
+    if flow is None:
+        flow = _solve_links_ref(network, demand, roughness, fixed_head, solver, accuracy, max_iter, pump_speed, link_closed).flow
+    flow = np.asarray(flow, dtype=np.float64)
+    speeds, closed = _link_rows(network, S, pump_speed, link_closed)
+    a, b, fixed = network.pipes[:, 0].astype(np.int64), network.pipes[:, 1].astype(np.int64), network.fixed
+    jj = ~fixed[a] & ~fixed[b]
+    pos, W = network.position.astype(np.int64), network.half_bandwidth
+    Z, dC = np.full((S, K, N), np.nan), np.full((S, K, P), np.nan)
+    rhs = np.zeros((N, K))
+    rhs[sensors, np.arange(K)] = np.where(fixed[sensors], 0.0, 1.0)
+    for s in range(S):
+        law = link_law(network, None if speeds is None else speeds[s], None if closed is None else closed[s])
+        if law is None or not np.isfinite(flow[s]).all():
+            continue
+        _, g = link_headloss(flow[s], _link_resistance(network, roughness[s]), **law)
+        pinv = 1.0 / g
+        diag = np.zeros(N)
+        for p in range(P):                                  # a row's sum runs over its pipes in pipe order, as in the kernel
+            diag[a[p]] += pinv[p]
+            diag[b[p]] += pinv[p]
+        diag[fixed] = 1.0
+        try:
+            if solver == "dense":
+                A = np.zeros((N, N))
+                A[np.arange(N), np.arange(N)] = diag
+                np.add.at(A, (a[jj], b[jj]), -pinv[jj])
+                np.add.at(A, (b[jj], a[jj]), -pinv[jj])
+                X = np.linalg.solve(A, rhs)
+            else:
+                from scipy.linalg import solveh_banded
+                ab = np.zeros((W + 1, N))
+                ab[0, pos] = diag
+                hi, lo = np.maximum(pos[a[jj]], pos[b[jj]]), np.minimum(pos[a[jj]], pos[b[jj]])
+                np.add.at(ab, (hi - lo, lo), -pinv[jj])
+                Xb = np.empty((N, K))
+                Xb[pos] = rhs
+                X = solveh_banded(ab, Xb, lower=True)[pos]
+        except (np.linalg.LinAlgError, ValueError):
+            continue
+        z = np.where(fixed[None, :] | fixed[sensors][:, None], 0.0, 0.0 - X.T)          # (0.0 - x: a zero stays +0.0)
+        Z[s] = z
+        dC[s] = (z[:, a] - z[:, b]) * roughness_gain(network, flow[s], roughness[s], law)[None, :]
+    return HydraulicSensitivityReference(Z, dC)
+
+
+def leak_scores_ref(dh_ddemand, residual) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The fused localisation of ``gatres_hydraulic_sensitivity`` in numpy, with the kernel's operations in the kernel's order:
+    ``dh_ddemand`` [..., K, N] and ``residual`` [..., K] (NaN: the sensor is missing) give (score [..., N], leak_flow [..., N],
+    best int32 [...]).  <z_n, rho>, <z_n, z_n> and <rho, rho> run over the available k ascending, product and sum rounded on their
+    own; leak_flow = <z, rho> / <z, z>, score = <z, rho> / (sqrt(<z, z>) * sqrt(<rho, rho>)); both NaN where <z, z> == 0 (a
+    fixed-head node has a column of zeros) or the matrix is NaN; every score NaN where <rho, rho> == 0 or no sensor is available;
+    best: the lowest index among those holding the largest score, -1 where there is none."""
+    Z, rho = np.asarray(dh_ddemand, dtype=np.float64), np.asarray(residual, dtype=np.float64)
+    K, N = Z.shape[-2:]
+    lead = Z.shape[:-2]
+    Z, rho = Z.reshape(-1, K, N), rho.reshape(-1, K)
+    num, den, r2, cnt = np.zeros((Z.shape[0], N)), np.zeros((Z.shape[0], N)), np.zeros(Z.shape[0]), np.zeros(Z.shape[0])
+    with np.errstate(all="ignore"):
+        for k in range(K):
+            on = ~np.isnan(rho[:, k])
+            rk = np.where(on, rho[:, k], 0.0)
+            num = np.where(on[:, None], num + Z[:, k, :] * rk[:, None], num)
+            den = np.where(on[:, None], den + Z[:, k, :] * Z[:, k, :], den)
+            r2 = np.where(on, r2 + rk * rk, r2)
+            cnt += on
+        off = (den == 0.0) | np.isnan(den)
+        leak = np.where(off, np.nan, num / den)
+        none = (cnt == 0) | (r2 == 0.0)
+        score = np.where(off | none[:, None], np.nan, num / (np.sqrt(den) * np.sqrt(r2)[:, None]))
+    return score.reshape(lead + (N,)), leak.reshape(lead + (N,)), best_score_ref(score).reshape(lead)
+
+
+def best_score_ref(score) -> np.ndarray:
+    """THE TIE RULE of ``best``: per row of ``score`` [..., N] the lowest index among those holding the maximum, NaN taking no part;
+    -1 where every score is NaN."""
+    score = np.asarray(score, dtype=np.float64)
+    live = ~np.isnan(score)
+    best = np.argmax(np.where(live, score, -np.inf), axis=-1).astype(np.int32)        # (argmax takes the first of equals)
+    return np.where(live.any(axis=-1), best, np.int32(-1)).astype(np.int32)
+
+
+def hop_distances(network: HydraulicNetwork, source: int) -> np.ndarray:
+    """Links between ``source`` and every node of the network's graph (every link counts, whatever its state); -1 where no path is."""
+    N = network.num_nodes
+    adj = [[] for _ in range(N)]
+    for a, b in network.pipes:
+        adj[int(a)].append(int(b))
+        adj[int(b)].append(int(a))
+    dist = np.full(N, -1, dtype=np.int64)
+    dist[int(source)] = 0
+    queue = [int(source)]
+    for v in queue:
+        for w in adj[v]:
+            if dist[w] < 0:
+                dist[w] = dist[v] + 1
+                queue.append(w)
+    return dist
+
+
+def localization_report(network: HydraulicNetwork, localization: LeakLocalization, true_node, tolerance: float = 1e-9) -> Dict[str, np.ndarray]:
+    """How a ``LeakLocalization`` did against the labels, with ONE read-back (scores and best together).  ``true_node``: the leaking
+    node, one for all scenarios or [S].  Per scenario: ``hops`` the links between ``best`` and the true node (-1 where best is -1);
+    ``deficit`` the top score minus the true node's score (0: the true node is among the best; NaN where there is no score);
+    ``above`` how many candidates score more than ``tolerance`` above the true node; and ``best`` itself.  Columns of junctions
+    behind the same sensor cut are proportional, so a deficit at rounding level with hops > 0 is all that the sensors can tell."""
+    score, best = localization.score, localization.best
+    S, N = int(score.shape[0]), network.num_nodes
+    back = torch.cat([score, best.to(torch.float64)[:, None]], dim=1).cpu().numpy()            # the one read-back
+    score, best = back[:, :N], back[:, N].astype(np.int64)
+    true = np.broadcast_to(np.asarray(true_node, dtype=np.int64), (S,))
+    if true.min() < 0 or true.max() >= N:
+        raise ValueError("true_node must be a node of the network")
+    hops = np.full(S, -1, dtype=np.int64)
+    for t in np.unique(true):
+        rows = (true == t) & (best >= 0)
+        hops[rows] = hop_distances(network, int(t))[best[rows]]
+    mine = score[np.arange(S), true]
+    live = ~np.isnan(score)
+    with np.errstate(all="ignore"):
+        top = np.where(live.any(axis=1), np.where(live, score, -np.inf).max(axis=1), np.nan)
+        above = (live & (score > (mine + float(tolerance))[:, None])).sum(axis=1)
+    return {"hops": hops, "deficit": top - mine, "above": above, "best": best}

@@ -1860,6 +1860,63 @@ int gatres_hydraulic_series_controls(const int32_t* pipe_a, const int32_t* pipe_
                                      int64_t control_threshold_stride, int32_t num_controls, int32_t* control_changes,
                                      void* stream);
 
+/* THE SENSITIVITIES: first-order sensitivities of the sensor heads and leak localisation (symbols only: the ABI stays;
+ * k_hydraulic_sensitivity.hip, hydraulics.py: HydraulicNetwork.sensitivity, localize_leaks, sensitivity_ref, leak_scores_ref).
+ * gatres_hydraulic_sensitivity takes the arguments of gatres_hydraulic_solve_links unchanged and in the same order, runs the same
+ * loop (hy_newton<true>) on the same capped grid, one workgroup per scenario, and writes the same pressure, head, flow, status,
+ * final_dq and link_state, bit for bit; here each of them may be NULL.  Then, in the same workgroup, for the K sensors
+ * sensor_node int32[K] (nodes; duplicates are legal and give rows that are equal in every bit):
+ * THE MATRIX.  The global-gradient matrix A of THE SOLVER (A_ii = sum 1/g_p, A_ij = -1/g_p over the junctions, unit rows for
+ * the fixed-head nodes) is the Schur complement of the full Jacobian of (energy, mass) in (q, H), so dH/dd = -A^-1 for an outflow
+ * d at a junction.  The kernel evaluates THE LINK LAW's g at the RETURNED flows (floor 1e-7 and 1e8 branches included: the
+ * sensitivity is that of the kernel's own model), assembles A in the order of THE SOLVER's assembly, factorises it with the same
+ * banded LDL^T, and solves the K unit right-hand sides at the sensors' solver rows against the resident factor, Kc at a time: all
+ * right-hand sides of a chunk move together through each column step, the (band offset, right-hand side) pairs being the work
+ * items, one barrier per column, the block [N][Kc] in LDS with the right-hand side's index fastest; each right-hand side takes
+ * the operations of the loop's single vector in the same order, so a row does not depend on the chunk it falls in.
+ * OUTPUTS, each optional (NULL: not wanted; what a launch computes is a compile-time fact of the instantiation it takes):
+ *   dh_ddemand double[S][K][N]:  Z[k][n] = dH_sensor(k) / dd_n = -(A^-1)[row(k)][row(n)] in metres per m3/s, NEGATIVE where more
+ *     outflow lowers the head; exactly +0.0 where n or the sensor is a fixed-head node.
+ *   dh_droughness double[S][K][P]:  dH_sensor(k) / dC_p.  At fixed demands dH_a - dH_b = g_p dq_p + h_C dC_p, so a change of C_p
+ *     moves the link's flow by -(h_C / g_p) dC_p at fixed heads: an outflow of that size at a and an inflow at b.  Hence
+ *     (Z[k][a] - Z[k][b]) * (-h_C / g_p) with a -> b the link's direction, h_C = dh/dC = -1.852 r |q|^0.852 q / C, formed as
+ *     ((1.852 * ra) * q) / (C * g_p), ra = r * pow(|q|, 0.852).  0 for a pump, for a link on a 1e8 branch (shut, or a CHECK link
+ *     with q < 0) and for a pipe on the low-flow floor.  Raising C on a pipe that feeds the sensor raises its head.
+ *   LOCALISATION, fused (no [S][K][N] in memory): readings double[S][K] are measured pressures in metres at the sensors, NaN
+ *     where a sensor is missing in that scenario.  residual double[S][K]: rho_k = reading_k - (H_sensor(k) - elevation), in
+ *     fp64 (not against the fp32 pressure), NaN where missing.  With z_n the column n of Z over the available sensors,
+ *     leak_flow[s][n] = <z_n, rho> / <z_n, z_n>  (m3/s: the least-squares outflow at n alone) and
+ *     score[s][n] = <z_n, rho> / (sqrt(<z_n, z_n>) * sqrt(<rho, rho>))  (the cosine; +1 is a perfect match for a leak at n),
+ *     every sum over k ascending in fp64, product and sum rounded on their own, accumulated across chunks in LDS.  Both are NaN
+ *     where n is a fixed-head node or <z_n, z_n> == 0.  If <rho, rho> == 0 or no sensor is available every score is NaN.
+ *     best int32[S]: THE TIE RULE -- the lowest node index among those holding the maximum of the scores the kernel itself
+ *     wrote (NaN scores take no part); -1 where every score is NaN.  Columns of junctions behind the same sensor cut are
+ *     proportional, their scores differ by rounding alone: best names one of them, not the leak.
+ * A scenario that ran out of iterations has its sensitivities computed from the returned flows (status tells it apart).  A
+ * scenario that FAILED (status[s][2], or a bad pivot of the second factorisation, which does not touch status) has NaN in every
+ * double output and best = -1.  A sensor_node outside [0, N) fails every scenario of the launch, as a bad static array does.
+ * chunk: 0 takes Kc = the most right-hand sides that fit; a value > 0 caps Kc (no output depends on it).
+ * NOT HERE: regulating valves (an ACTIVE valve's flow is lagged outside the matrix, so A is not the Jacobian), emitters as
+ * unknowns and pressure-driven demand.
+ * LDS need (hydraulics.sensitivity_lds_bytes, sensitivity_chunk): the bytes of gatres_hydraulic_solve_links
+ *   + 16 N (the two score accumulators per row)  +  8 Kc (N + 1) (per right-hand side of a chunk its column and its residual),
+ * Kc = min(K, (GATRES_HYD_LDS_BUDGET - links bytes - 16 N) / (8 (N + 1))), refused where Kc < 1.  On 388 nodes, 430 links, W = 19
+ * without pumps: 92 264 + 6 208 bytes, Kc = 21.
+ * GATRES_E_BADARG before any launch: what gatres_hydraulic_solve_links refuses (but for its NULL outputs); num_sensors < 1;
+ * chunk < 0; sensor_node NULL; byte counts that do not fit; Kc < 1; readings given with none of residual, leak_flow, score and
+ * best, or one of those without readings; an output overlapping an input or another output. */
+int gatres_hydraulic_sensitivity(const int32_t* pipe_a, const int32_t* pipe_b, const double* coef, const double* q_start,
+                                 const uint8_t* fixed, const double* elevation, const int32_t* order, const int32_t* position,
+                                 int32_t half_bandwidth, const double* demand, const double* roughness, const double* fixed_head,
+                                 int64_t fixed_head_stride, int64_t num_scenarios, int32_t num_nodes, int32_t num_pipes,
+                                 double accuracy, int32_t max_iter, float* pressure, double* head, double* flow, int32_t* status,
+                                 double* final_dq, const uint8_t* link_kind, const uint8_t* link_flags, const double* minor,
+                                 const int32_t* pump_link, const double* pump_h0, const double* pump_r, const double* pump_n,
+                                 int32_t num_pumps, const double* speed, int64_t speed_stride, const uint8_t* closed,
+                                 int64_t closed_stride, uint8_t* link_state, const int32_t* sensor_node, int32_t num_sensors,
+                                 int32_t chunk, const double* readings, double* dh_ddemand, double* dh_droughness,
+                                 double* residual, double* leak_flow, double* score, int32_t* best, void* stream);
+
 const char* gatres_version(void);
 
 #ifdef __cplusplus
